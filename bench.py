@@ -14,9 +14,15 @@ process starts `python -m torch.distributed.run --nproc-per-node N` on itself BE
 rank 0's JSON line.  One rank per GPU; independent seeds per rank (replicas only) with one RCCL
 all_gather of the per-run metric means at the end, as MFPolicyTrainer would log per epoch.
 
-The timed block of K steps (barrier + synchronize on both sides, max over ranks) is repeated (>= 5 blocks and
->= 2 s, --min-reps / --min-seconds); `value` is the median block, every block is listed in `reps`.
-Side records of the same run (rank 0, N = 1 only): `value_fp32` / `fp32` (exact-fp32 MFMA, same workload, one engine x 128 runs),
+A plain run sets up, warms up (W steps), times ONE block of exactly K steps (barrier + synchronize on both sides, max over ranks),
+writes the outputs if asked (--dump-outputs DIR) and prints the JSON line: `ms_per_step` = block time / K, `value` = steps of all runs / block
+time.  --min-reps / --min-seconds repeat the block (`value` is then the median block; every block is listed in `reps`).
+--dump-outputs DIR: after the timed steps, what the timed path hands its caller, float32 .npy files: `metrics.npy` (the per-run metric means
+orl_learn_n returned for the timed block, every run of every engine and rank) and `<net>.npy` (the parameters, flat in state_dict order,
+of every net of a fixed sample of 16 runs after the last timed step).  Inputs are seeded: the same arguments give the same inputs.
+--full adds everything else, measured after the headline: the live roofline of the dominant launch (--profile-steps, --profile-dump) and
+the side records below.
+Side records of the same run (--full, rank 0, N = 1 only): `value_fp32` / `fp32` (exact-fp32 MFMA, same workload, one engine x 128 runs),
 `value_fp32_class` / `fp32_class` (precision 2: three fp16 planes per operand in the critic launches, fp32 MFMA elsewhere; same geometry), `target`
 (both over the north_star's 50k), `by_runs` (runs per GPU 1 .. 192), `other_configs` (TD3BC, IQL = BASELINE configs[2], EDAC =
 configs[3]; 128 runs each), `api` (a fused MFPolicyTrainer epoch through offlinerlkit.policy.CQLPolicy / ReplayBuffer with the split
@@ -168,6 +174,23 @@ def learn_all(engines, n):
         for t in ths:
             t.join()
     return res
+
+
+DUMP_RUNS = 16                      # runs whose parameters --dump-outputs writes: 16 x 5 CQL nets x ~73k floats = ~24 MB
+DUMP_NETS = ("actor", "critic1", "critic2", "critic1_old", "critic2_old")        # net ids 0 .. 4 (offlinerlkit/_engine.py NET_*)
+
+
+def dump_outputs(out_dir, engines, metrics_all):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, float32 .npy files in out_dir.  metrics.npy =
+    the per-run metric means orl_learn_n returned (rank, engine, run order); <net>.npy = each net's parameters, flat in state_dict order,
+    of DUMP_RUNS (engine, run) pairs drawn with a fixed seed (rows in ascending engine * runs + run order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "metrics.npy"), metrics_all.reshape(-1, metrics_all.shape[-1]).astype(np.float32))
+    R = engines[0].n_runs
+    picks = np.sort(np.random.RandomState(0).choice(len(engines) * R, min(DUMP_RUNS, len(engines) * R), replace=False))
+    for net, name in enumerate(DUMP_NETS):
+        rows = [np.concatenate([a.ravel() for a in engines[i // R].get_net(int(i % R), net).values()]) for i in picks]
+        np.save(os.path.join(out_dir, name + ".npy"), np.stack(rows).astype(np.float32))
 
 
 def timed_rate(engines, steps, min_seconds, min_reps=1, max_reps=40):
@@ -477,17 +500,21 @@ def main():
                     help="independent engines per GPU (each --runs-per-gpu runs, own HIP stream and host thread): the launch-latency-bound "
                          "256-row phases of one engine overlap the many-row launches of the other (default 2)")
     ap.add_argument("--precision", type=int, default=int(os.environ.get("ORL_PRECISION", "1")), help="0 exact fp32 MFMA, 1 split MFMA (fp16 hi + lo planes; bf16 planes in the variant build), 2 three fp16 planes in the critic launches / fp32 MFMA elsewhere (all parity-gated)")
-    ap.add_argument("--min-reps", type=int, default=5)
-    ap.add_argument("--min-seconds", type=float, default=2.0)
-    ap.add_argument("--no-sides", action="store_true", help="skip fp32 / by_runs / other_configs side records")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--min-reps", type=int, default=1, help="time at least this many blocks of --steps steps (value = the median block)")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="... and repeat the block until this much wall time has passed")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path computed (metrics, sampled parameters) as .npy files to DIR")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline, the side records and the CPU baseline (off: the headline only)")
+    ap.add_argument("--no-sides", action="store_true", help="with --full: skip fp32 / by_runs / other_configs side records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=24.0, help="CPU work of the cpu_baseline sample (four legs share it)")
-    ap.add_argument("--profile-steps", type=int, default=20)
-    ap.add_argument("--profile-dump", default="", help="write the full per-launch-tag timing table (HIP events) to this file")
+    ap.add_argument("--profile-steps", type=int, default=20, help="with --full: eager steps timed per launch tag for the roofline (0: none)")
+    ap.add_argument("--profile-dump", default="", help="with --full: write the full per-launch-tag timing table (HIP events) to this file")
     ap.add_argument("--dataset-size", type=int, default=None, help="transitions of the synthetic buffer (default 1 000 000; --preset config5: the rank's D4RL task size)")
     ap.add_argument("--launch-check", action="store_true", help="print this rank's RANK / LOCAL_RANK / WORLD_SIZE as JSON and exit (no GPU use)")
     ap.add_argument("--rccl-check", action="store_true", help="world-size-1 `nccl` process group on this GPU: the path's collectives on device tensors, then exit")
     args = ap.parse_args()
+    if args.profile_dump and not args.full:
+        ap.error("--profile-dump needs --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_children(args.gpus, sys.argv[1:]))       # the parent has made no GPU call
@@ -575,6 +602,8 @@ def main():
         for r in (0, R - 1):
             for net in (0, 1, 2):
                 assert all(np.isfinite(v).all() for v in g.get_net(r, net).values()), "non-finite parameters after the timed steps"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engines, metrics_all)       # before --full's profiled steps move the parameters on
 
     total_steps = args.steps * R * E * world
     dt_med = float(np.median(reps))
@@ -582,7 +611,7 @@ def main():
     if rank == 0:
         flops_step = cql_algorithmic_flops(od=od, ad=ad)
         roof = None
-        if args.profile_steps > 0:
+        if args.full and args.profile_steps > 0:
             roof = profile_roofline(eng, args.profile_steps, args.precision, R, flops_step, value / world, args.profile_dump)
             if roof and roof["kernel"].startswith("critic."):
                 # one weight-stationary workgroup owns a CU; with several engines per GPU a launch stays on 2 * runs workgroups (one round,
@@ -594,7 +623,7 @@ def main():
         for g in engines:
             g.close()
         engines = []
-        sides = world == 1 and not args.no_sides and (od, ad) == (OBS, ACT)
+        sides = args.full and world == 1 and not args.no_sides and (od, ad) == (OBS, ACT)
         by_runs, fp32, fp32_class, others = None, None, None, None
         api, api_default, config5 = None, None, None
         if sides:
@@ -664,7 +693,7 @@ def main():
                 es[0].close()
                 if t_buf is not buf:
                     t_buf.close()
-        cpu = cpu_baseline(args.cpu_baseline_seconds) if (world == 1 and not args.no_cpu_baseline) else None      # reported baseline: rank 0 at N = 1 only
+        cpu = cpu_baseline(args.cpu_baseline_seconds) if (args.full and world == 1 and not args.no_cpu_baseline) else None     # reported baseline: rank 0 at N = 1 only
         out = {
             "metric": "gradient-steps/sec (CQL, batch=256)", "value": value, "unit": "gradient-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt_med / args.steps * 1e3,

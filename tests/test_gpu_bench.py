@@ -1,7 +1,8 @@
-"""GPU: the driver's bench line.  ``bench.py`` runs in a fresh process (as the driver starts it) on a reduced geometry -- one engine x 8 runs,
+"""GPU: the driver's bench line.  ``bench.py --full`` runs in a fresh process (as the driver starts it) on a reduced geometry -- one engine x 8 runs,
 a 50 000-transition buffer, 5 timed steps, a 2 s CPU sample, no side records -- and the single JSON line it prints must carry every field
 of the contract (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data /
-config.workload, ``roofline`` with the dominant launch measured live, ``cpu_baseline`` with the sample it timed)."""
+config.workload, ``roofline`` with the dominant launch measured live, ``cpu_baseline`` with the sample it timed).  A plain run (no ``--full``)
+times exactly ``--steps`` steps, measures nothing else, and its ``--dump-outputs`` files are the same from run to run."""
 import json
 import os
 import subprocess
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_contract_line():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-sides", "--min-reps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-sides", "--min-reps", "2",
            "--min-seconds", "0", "--engines-per-gpu", "1", "--runs-per-gpu", "8", "--dataset-size", "50000", "--profile-steps", "3",
            "--cpu-baseline-seconds", "2"]
     env = dict(os.environ)
@@ -41,6 +42,37 @@ def test_bench_prints_one_contract_line():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cpu, k
     assert cpu["kind"] == "port" and cpu["value"] > 0 and cpu["cores"] >= 1
+
+
+def test_plain_run_times_the_given_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """Two plain runs (two engines x 8 runs, so the parameter sample spans both engines): one block of exactly --steps steps, no side
+    measurement, and bit-identical --dump-outputs files (seeded inputs; engines beside each other compute what they compute alone)."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    dumps = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--engines-per-gpu", "2",
+                            "--runs-per-gpu", "8", "--dataset-size", "50000", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["reps"]["blocks"] == 1 and d["reps"]["steps_per_block"] == 7
+        assert abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert all(d[k] is None for k in ("roofline", "cpu_baseline", "fp32", "fp32_class", "by_runs", "other_configs", "api"))
+        files = sorted(os.listdir(out))
+        assert files == sorted(["metrics.npy", "actor.npy", "critic1.npy", "critic2.npy", "critic1_old.npy", "critic2_old.npy"])
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["metrics.npy"].shape == (16, 5) and arrs["actor.npy"].shape[0] == 16
+        assert sum(os.path.getsize(out / f) for f in files) < 64 << 20
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 @pytest.mark.parametrize("precision", [1, 2])

@@ -19,8 +19,8 @@ if [ "$what" = all ] || [ "$what" = cql ]; then
   rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU -d $O/1x128_sq1 -o r -- $B --engines-per-gpu 1 --runs-per-gpu 128 > $O/1x128_sq1.log 2>&1
   rocprofv3 --kernel-trace --output-format csv --pmc SQ_INSTS_MFMA SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_INSTS_VMEM -d $O/1x128_sq2 -o r -- $B --engines-per-gpu 1 --runs-per-gpu 128 > $O/1x128_sq2.log 2>&1
   rocprofv3 --kernel-trace --output-format csv --pmc SQ_VALU_MFMA_COEXEC_CYCLES SQ_VALU_MFMA_BUSY_CYCLES -d $O/1x128_sq3 -o r -- $B --engines-per-gpu 1 --runs-per-gpu 128 > $O/1x128_sq3.log 2>&1 || echo "(SQ_VALU_MFMA_COEXEC_CYCLES pass failed)"
-  python3 bench.py --steps 20 --warmup 5 --no-sides --no-cpu-baseline --engines-per-gpu 1 --runs-per-gpu 128 --profile-steps 20 --profile-dump $O/tags_1x128.txt > $O/bench_1x128.json 2> $O/bench_1x128.err
-  python3 bench.py --steps 20 --warmup 5 --no-sides --no-cpu-baseline --engines-per-gpu 1 --runs-per-gpu 128 --precision 0 --profile-steps 10 --profile-dump $O/tags_fp32_1x128.txt > $O/bench_fp32_1x128.json 2> $O/bench_fp32_1x128.err
+  python3 bench.py --steps 20 --warmup 5 --full --min-reps 5 --min-seconds 2 --no-sides --no-cpu-baseline --engines-per-gpu 1 --runs-per-gpu 128 --profile-steps 20 --profile-dump $O/tags_1x128.txt > $O/bench_1x128.json 2> $O/bench_1x128.err
+  python3 bench.py --steps 20 --warmup 5 --full --min-reps 5 --min-seconds 2 --no-sides --no-cpu-baseline --engines-per-gpu 1 --runs-per-gpu 128 --precision 0 --profile-steps 10 --profile-dump $O/tags_fp32_1x128.txt > $O/bench_fp32_1x128.json 2> $O/bench_fp32_1x128.err
 fi
 if [ "$what" = all ] || [ "$what" = few ]; then
   for r in 1 8; do
@@ -45,7 +45,7 @@ if [ "$what" = all ] || [ "$what" = p2 ]; then
   for c in FETCH_SIZE WRITE_SIZE; do
     echo "== precision 2, 1x128: pmc $c"; rocprofv3 --kernel-trace --output-format csv --pmc $c -d $O/p2_$c -o r -- $P2 > $O/p2_$c.log 2>&1
   done
-  python3 bench.py --steps 20 --warmup 5 --no-sides --no-cpu-baseline --engines-per-gpu 1 --runs-per-gpu 128 --precision 2 --profile-steps 20 --profile-dump $O/tags_p2_1x128.txt > $O/bench_p2_1x128.json 2> $O/bench_p2_1x128.err
+  python3 bench.py --steps 20 --warmup 5 --full --min-reps 5 --min-seconds 2 --no-sides --no-cpu-baseline --engines-per-gpu 1 --runs-per-gpu 128 --precision 2 --profile-steps 20 --profile-dump $O/tags_p2_1x128.txt > $O/bench_p2_1x128.json 2> $O/bench_p2_1x128.err
   python3 tools/few_runs_ab.py "-" --runs 1 8 16 32 128 --precision 0 --reps 2 > $O/few_runs_p0.txt 2>/dev/null
   python3 tools/few_runs_ab.py "-" --runs 1 8 16 32 128 --precision 2 --reps 2 > $O/few_runs_p2.txt 2>/dev/null
 fi
