@@ -280,6 +280,72 @@ int orl_profile_enable(orl_engine* e, int on);
 int orl_profile_query(orl_engine* e, int idx, char* name, int name_cap, double* total_ms, int64_t* launches,
                       double* flops_per_launch, double* bytes_per_launch);
 
+/* -- dynamics ensemble (dynamics/ensemble_dynamics.py, modules/dynamics_module.py): its own object ----------------------------
+ * The probabilistic ensemble of MOPO / COMBO: num_ensemble EnsembleLinear MLPs with Swish activations whose output layer gives a
+ * mean and a soft-clamped log-variance for (delta obs, reward).  Like orl_engine it carries n_runs independent runs (seeds); every
+ * host array has a leading run dimension.  Parameters per run, in the reference's state_dict order (orl_dyn_tensor): max_logvar,
+ * min_logvar, then backbones.{i}.{weight,bias,saved_weight,saved_bias} and output_layer.* (weights (K, in, out), biases (K, 1, out));
+ * each tensor starts on a 16-byte boundary of the flat per-run block.  `elites` (int64 in the reference) lives outside the fp32 block
+ * (orl_dyn_set_elites / orl_dyn_get_elites).  Only precision 0 (fp32 MFMA) is implemented. */
+typedef struct orl_dyn_config {
+  int32_t obs_dim, act_dim;
+  int32_t n_hidden;                 /* <= ORL_MAX_HIDDEN */
+  int32_t hidden[ORL_MAX_HIDDEN];
+  int32_t num_ensemble, num_elites, with_reward;
+  float weight_decay[ORL_MAX_HIDDEN + 1];   /* per layer, the output layer last (dynamics_module.py:56-68) */
+  float lr, adam_beta1, adam_beta2, adam_eps;
+  int32_t batch_size;
+  float logvar_loss_coef;
+  int32_t n_runs, device, precision;
+  uint64_t seed;                    /* device Philox seed of orl_dyn_step without teacher-forced noise */
+  float* external_arena;            /* optional caller-owned device block of n_runs * orl_dyn_floats floats (torch aliasing); NULL = hipMalloc */
+} orl_dyn_config;
+
+#define ORL_DYN_PENALTY_ALEATORIC 0      /* max_k || std_k ||  (all out dims) */
+#define ORL_DYN_PENALTY_PAIRWISE_DIFF 1  /* max_k || mean_k - mean over k ||  (obs dims) */
+#define ORL_DYN_PENALTY_ENSEMBLE_STD 2   /* sqrt(mean_d var_k mean_k)  (obs dims) */
+
+typedef struct orl_dynamics orl_dynamics;
+void orl_dyn_config_default(orl_dyn_config* cfg);       /* run_mopo.py defaults: [200]*4, 7 members, 5 elites, its decays, lr 1e-3, batch 256 */
+int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out);
+void orl_dyn_destroy(orl_dynamics* d);
+int orl_dyn_sync(orl_dynamics* d);
+int64_t orl_dyn_floats(orl_dynamics* d);                /* floats of one run's parameter block */
+int64_t orl_dyn_config_floats(const orl_dyn_config* cfg); /* the same before creation (size of external_arena / n_runs) */
+int orl_dyn_num_tensors(orl_dynamics* d);
+int orl_dyn_tensor(orl_dynamics* d, int idx, char* name, int name_cap, int64_t* offset_floats, int32_t* ndim, int64_t shape[4]);
+float* orl_dyn_ptr(orl_dynamics* d, int run);           /* device pointer to the run's parameter block (aliasing from torch) */
+int orl_dyn_set(orl_dynamics* d, int run, const float* host, int64_t n_floats);
+int orl_dyn_get(orl_dynamics* d, int run, float* host, int64_t n_floats);
+/* torch.optim.Adam state of the run: exp_avg / exp_avg_sq over the parameter block (zero where the reference keeps no state:
+ * saved_* get no gradient) and its step count */
+int orl_dyn_adam_get(orl_dynamics* d, int run, float* exp_avg, float* exp_avg_sq, int64_t n_floats, int64_t* step);
+int orl_dyn_adam_set(orl_dynamics* d, int run, const float* exp_avg, const float* exp_avg_sq, int64_t n_floats, int64_t step);
+int orl_dyn_set_elites(orl_dynamics* d, int run, const int64_t* idx, int n);   /* model.set_elites */
+int orl_dyn_get_elites(orl_dynamics* d, int run, int64_t* idx, int cap);       /* returns the number of elites, < 0 on error */
+/* format_samples_for_training output loaded into HBM once: inputs [n][obs+act], targets [n][obs + with_reward] */
+int orl_dyn_load_data(orl_dynamics* d, const float* inputs, const float* targets, int64_t n);
+int orl_dyn_set_scaler(orl_dynamics* d, int run, const float* mu, const float* std);   /* StandardScaler of the run (obs+act each) */
+/* learn() (ensemble_dynamics.py:178-209) for every run: idx host int64 [n_runs][num_ensemble][train_size], rows of the loaded data
+ * (the bootstrap indices composed with the run's train split), in minibatch order; active: host int32 [n_runs] (NULL = all), an
+ * inactive run's parameters and Adam state stay bit for bit.  No host synchronisation inside the epoch; loss_out: host [n_runs]
+ * mean minibatch loss (0 for inactive runs). */
+int orl_dyn_learn_epoch(orl_dynamics* d, const int64_t* idx, int64_t train_size, const int32_t* active, float* loss_out);
+/* validate() (:211-217): idx host int64 [n_runs][holdout_size] rows of the loaded data; mse_out host [n_runs][num_ensemble] */
+int orl_dyn_validate(orl_dynamics* d, const int64_t* idx, int64_t holdout_size, float* mse_out);
+int orl_dyn_update_save(orl_dynamics* d, int run, const int32_t* member_mask);   /* update_save(indexes): mask [num_ensemble] */
+int orl_dyn_load_save(orl_dynamics* d, int run);
+/* step() (:29-80) without the terminal function: obs [n_runs][n][obs_dim], act [n_runs][n][act_dim] (device pointers when on_device).
+ * noise [n_runs][num_ensemble][n][obs_dim + with_reward] and model_idx [n_runs][n] teacher-force the reference's np.random.normal /
+ * random_elite_idxs draws; NULL = device Philox (seed, call counter): N(0,1) noise, model index uniform over the elites.
+ * Outputs [n_runs][n][obs_dim] and [n_runs][n]: reward = raw_reward - penalty_coef * penalty; model_idx_out may be NULL.
+ * Outputs are host arrays, device arrays when on_device. */
+int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n, int on_device, const float* noise,
+                 const int64_t* model_idx, int penalty_mode, float penalty_coef, float* next_obs, float* reward, float* raw_reward,
+                 float* penalty, int32_t* model_idx_out);
+/* test tap: parameter gradient of the LAST minibatch of the last orl_dyn_learn_epoch (flat like orl_dyn_get; decay terms excluded) */
+int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n_floats);
+
 #ifdef __cplusplus
 }
 #endif

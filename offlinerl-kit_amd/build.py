@@ -26,6 +26,8 @@ UNITS = {
     "gemm_inst_rank1.hip": GEMM_H,
     "gemm_inst_wgrad.hip": GEMM_H,
     "gemm_inst_tune.hip": GEMM_H,
+    "gemm_inst_swish.hip": GEMM_H,
+    "dynamics.hip": ["gemm.h", ABI],
     "ws_fwd.hip": WS_H,
     "ws_dgrad.hip": WS_H,
     "ws_fwd3.hip": WS_H,

@@ -1,0 +1,955 @@
+// dynamics.hip — the probabilistic dynamics ensemble of MOPO / COMBO on the device (reference: dynamics/ensemble_dynamics.py,
+// modules/dynamics_module.py): orl_dyn_* of include/orl_engine.h.
+//
+// One minibatch of learn() is a plain run of launches on one stream, enqueued for the whole epoch before the host waits once:
+//   k_dyn_gather       bootstrap rows of the HBM dataset, (x - mu) / std fused in (StandardScaler.transform's fp32 operations)
+//   L x E_BIAS_SWISH   hidden layers on the tiled GEMM (gemm_inst_swish.hip): h = z sigmoid(z), z kept for the backward
+//   1 x E_BIAS         output layer -> [mean | raw logvar]
+//   k_dyn_nll          soft_clamp, the Gaussian NLL terms, d mean / d raw logvar, per-element max / min_logvar gradient terms
+//   k_dyn_nll_reduce   per run: the minibatch loss (mean over rows and dims, summed over members, + coef (sum max - sum min)) and the
+//                      max / min_logvar gradients, reduced in a fixed order
+//   (L+1) x E_WGRAD, L x E_SWISH_GRAD   weight / bias gradients and the Swish-scaled input gradients, top down
+//   k_dyn_adam         torch.optim.Adam with the weight-decay term wd_l W_l folded into the weights' gradients; the decay loss of the
+//                      weights it reads is reduced on the way; inactive runs are skipped (their state stays bit for bit)
+//   k_dyn_loss         adds the decay loss and accumulates the minibatch loss of the active runs
+// Members and runs are batched through blockIdx.z = run * K + member of every GEMM; a 2-D input shared by the members (validate, step)
+// is a member stride of 0.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/orl_engine.h"
+#include "gemm.h"
+
+namespace orl {
+
+int fail(const std::string& msg);      // engine.hip: sets orl_last_error(), returns -1
+
+static inline int rup4(int x) { return (x + 3) & ~3; }
+
+// ---- Philox4x32-10 (device noise / elite choice of step()) ----
+__device__ inline void dyn_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t (&out)[4]) {
+  uint32_t a = (uint32_t)seed, b = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ a, n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ b, n3 = (uint32_t)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    a += 0x9E3779B9u; b += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__device__ inline float dyn_u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+
+// torch.nn.functional.softplus (beta 1, threshold 20) and its derivative
+__device__ inline float dyn_softplus(float y) { return y > 20.f ? y : log1pf(expf(y)); }
+__device__ inline float dyn_dsoftplus(float y) { return y > 20.f ? 1.f : 1.f / (1.f + expf(-y)); }
+
+// rows [row0, row0 + rows) of idx[r][k][*] -> X[r][k][i][0..xp) = (in - mu) / std (zero pads), T[r][k][i][0..D)
+__global__ void k_dyn_gather(const int* __restrict__ idx, long idx_s0, long idx_s1, long row0, int rows, const float* __restrict__ din,
+                             const float* __restrict__ dtg, int in, int D, const float* __restrict__ mu, const float* __restrict__ sd,
+                             float* __restrict__ X, long x_s0, long x_s1, int xp, float* __restrict__ T, long t_s0, long t_s1) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = blockIdx.y, r = blockIdx.z;
+  if (i >= rows) return;
+  const long g = idx[r * idx_s0 + k * idx_s1 + row0 + i];
+  const float* src = din + g * in;
+  const float* m = mu + (long)r * in;
+  const float* s = sd + (long)r * in;
+  float* x = X + r * x_s0 + k * x_s1 + (long)i * xp;
+  for (int c = 0; c < in; ++c) x[c] = (src[c] - m[c]) / s[c];
+  for (int c = in; c < xp; ++c) x[c] = 0.f;
+  if (T) {
+    const float* tg = dtg + g * D;
+    float* t = T + r * t_s0 + k * t_s1 + (long)i * D;
+    for (int d = 0; d < D; ++d) t[d] = tg[d];
+  }
+}
+
+// step(): X[r][i] = scaler(concat(obs, act))
+__global__ void k_dyn_step_input(const float* __restrict__ obs, const float* __restrict__ act, long n, int od, int ad,
+                                 const float* __restrict__ mu, const float* __restrict__ sd, float* __restrict__ X, int xp) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  if (i >= n) return;
+  const int in = od + ad;
+  const float* o = obs + ((long)r * n + i) * od;
+  const float* a = act + ((long)r * n + i) * ad;
+  const float* m = mu + (long)r * in;
+  const float* s = sd + (long)r * in;
+  float* x = X + ((long)r * n + i) * xp;
+  for (int c = 0; c < od; ++c) x[c] = (o[c] - m[c]) / s[c];
+  for (int c = 0; c < ad; ++c) x[od + c] = (a[c] - m[od + c]) / s[od + c];
+  for (int c = in; c < xp; ++c) x[c] = 0.f;
+}
+
+// Gaussian NLL head, one thread per (run, member, row, dim).  OUT / dOUT [r][k][i][op] (mean: cols 0..D, raw logvar: D..2D),
+// T / lterm / gmax / gmin [r][k][i][D] with row stride `bs` rows per (r, k).
+__global__ void k_dyn_nll(const float* __restrict__ OUT, float* __restrict__ dOUT, int op, const float* __restrict__ T,
+                          float* __restrict__ lterm, float* __restrict__ gmax, float* __restrict__ gmin, const float* __restrict__ params,
+                          long P, long off_max, long off_min, int K, int bs, int rows, int D) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  if (e >= (long)K * rows * D) return;
+  const int d = (int)(e % D);
+  const long ki = e / D;
+  const int i = (int)(ki % rows), k = (int)(ki / rows);
+  const long row = ((long)r * K + k) * bs + i;
+  const float mx = params[r * P + off_max + d], mn = params[r * P + off_min + d];
+  const float mean = OUT[row * op + d], x = OUT[row * op + D + d];
+  const float y1 = mx - x;
+  const float l1 = mx - dyn_softplus(y1);
+  const float y2 = l1 - mn;
+  const float lv = mn + dyn_softplus(y2);
+  const float s1 = dyn_dsoftplus(y1), s2 = dyn_dsoftplus(y2);
+  const float inv = expf(-lv);
+  const float diff = mean - T[row * D + d];
+  const float sq = diff * diff * inv;
+  const float scale = 1.0f / ((float)rows * (float)D);
+  const float dmean = 2.f * diff * inv * scale;
+  const float dlv = (1.f - sq) * scale;
+  const float dl1 = dlv * s2;
+  dOUT[row * op + d] = dmean;
+  dOUT[row * op + D + d] = dl1 * s1;
+  lterm[row * D + d] = sq + lv;
+  gmax[row * D + d] = dl1 * (1.f - s1);
+  gmin[row * D + d] = dlv * (1.f - s2);
+}
+
+// per run (blockIdx.x), 1024 threads: the three column sums over (member, row) in a fixed order, the minibatch loss without the decay
+// term, and the max / min_logvar gradients (+coef / -coef of the logvar_loss_coef term) into the gradient block
+__global__ __launch_bounds__(1024) void k_dyn_nll_reduce(const float* __restrict__ lterm, const float* __restrict__ gmax,
+                                                         const float* __restrict__ gmin, int K, int bs, int rows, int D,
+                                                         const float* __restrict__ params, float* __restrict__ G, long P, long off_max,
+                                                         long off_min, float coef, float* __restrict__ nll_out) {
+  __shared__ float red[3 * 64];
+  const int r = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nw = blockDim.x >> 6;
+  const int KR = K * rows;
+  for (int c = w; c < 3 * D; c += nw) {
+    const float* a = c < D ? lterm : (c < 2 * D ? gmax : gmin);
+    const int d = c % D;
+    float s = 0.f;
+    for (int e = lane; e < KR; e += 64) {
+      const int k = e / rows, i = e - k * rows;
+      s += a[(((long)r * K + k) * bs + i) * D + d];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) red[c] = s;
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < D) {
+    G[r * P + off_max + t] = red[D + t] + coef;
+    G[r * P + off_min + t] = red[2 * D + t] - coef;
+  }
+  if (t == 0) {
+    float ls = 0.f, smax = 0.f, smin = 0.f;
+    for (int d = 0; d < D; ++d) {
+      ls += red[d];
+      smax += params[r * P + off_max + d];
+      smin += params[r * P + off_min + d];
+    }
+    nll_out[r] = ls / ((float)rows * (float)D) + (coef * smax - coef * smin);
+  }
+}
+
+struct DynAdamP {
+  float* params; float* m; float* v; const float* G;
+  long P;
+  int nseg;
+  long seg_b[12], seg_e[12];
+  float seg_wd[12];
+  const int* active;
+  const long long* t0;
+  int batch;
+  float lr, b1, b2, eps;
+  float* decay_part;
+  int nblk;
+};
+
+// torch.optim.Adam (exp_avg lerp, exp_avg_sq, bias corrections of the run's own step count) on the trainable tensors of one run; the
+// gradient of the decay loss 0.5 wd_l sum W_l^2 (wd_l W_l) is added to the weights' gradients here and the decay loss of the weights
+// read (those of the minibatch's forward pass) is reduced into decay_part[r][block].  Four floats per thread (tensors are 16-B aligned).
+__global__ __launch_bounds__(256) void k_dyn_adam(DynAdamP p) {
+  __shared__ float s_step, s_bc2s;
+  __shared__ float s_red[4];
+  const int r = blockIdx.y;
+  if (!p.active[r]) return;                                   // uniform per block
+  if (threadIdx.x == 0) {
+    const double t = (double)(p.t0[r] + p.batch + 1);
+    const double bc1 = 1.0 - pow((double)p.b1, t), bc2 = 1.0 - pow((double)p.b2, t);
+    s_step = (float)((double)p.lr / bc1);
+    s_bc2s = (float)sqrt(bc2);
+  }
+  __syncthreads();
+  const long i0 = 4 * ((long)blockIdx.x * blockDim.x + threadIdx.x);
+  float dec = 0.f;
+  int sg = -1;
+  for (int s = 0; s < p.nseg; ++s)
+    if (i0 >= p.seg_b[s] && i0 < p.seg_e[s]) sg = s;
+  if (sg >= 0) {
+    const long o = r * p.P + i0;
+    const float wd = p.seg_wd[sg];
+    const int cnt = (int)min(4L, p.seg_e[sg] - i0);
+    for (int j = 0; j < cnt; ++j) {
+      const float w = p.params[o + j];
+      const float g = p.G[o + j] + wd * w;
+      dec += w * w;
+      const float m = p.m[o + j] + (g - p.m[o + j]) * (1.0f - p.b1);
+      const float v = p.v[o + j] * p.b2 + (1.0f - p.b2) * g * g;
+      p.m[o + j] = m; p.v[o + j] = v;
+      p.params[o + j] = w - s_step * (m / (sqrtf(v) / s_bc2s + p.eps));
+    }
+    dec *= 0.5f * wd;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) dec += __shfl_xor(dec, o, 64);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = dec;
+  __syncthreads();
+  if (threadIdx.x == 0) p.decay_part[(long)r * p.nblk + blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// loss_sum[r] += nll[r] + sum_b decay_part[r][b] for the active runs (fixed order)
+__global__ __launch_bounds__(256) void k_dyn_loss(const float* __restrict__ nll, const float* __restrict__ decay_part, int nblk,
+                                                  const int* __restrict__ active, float* __restrict__ loss_sum) {
+  __shared__ float s_red[4];
+  const int r = blockIdx.x;
+  if (!active[r]) return;
+  float s = 0.f;
+  for (int b = threadIdx.x; b < nblk; b += blockDim.x) s += decay_part[(long)r * nblk + b];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) loss_sum[r] += nll[r] + ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+}
+
+// validate(): mse[r][k] = mean over (row, dim) of (mean - target)^2; OUT [r][k][H][op], T [r][H][D]
+__global__ __launch_bounds__(256) void k_dyn_val_mse(const float* __restrict__ OUT, int op, const float* __restrict__ T, int H, int D,
+                                                     int K, float* __restrict__ mse) {
+  __shared__ float s_red[4];
+  const int k = blockIdx.x, r = blockIdx.y;
+  float s = 0.f;
+  const long n = (long)H * D;
+  for (long e = threadIdx.x; e < n; e += blockDim.x) {
+    const long i = e / D; const int d = (int)(e - i * D);
+    const float diff = OUT[(((long)r * K + k) * H + i) * op + d] - T[((long)r * H + i) * D + d];
+    s += diff * diff;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) mse[r * K + k] = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) / (float)n;
+}
+
+enum { DYN_MAXD = 64 };
+
+struct DynHeadP {
+  const float* OUT; int op;
+  const float* obs; long n; int od, D, K;
+  const float* params; long P, off_max, off_min;
+  const float* noise; const int* midx;
+  const int* elites; int n_elites;
+  uint64_t seed; uint64_t call;
+  int mode; float coef;
+  float* next_obs; float* reward; float* raw_reward; float* penalty; int* midx_out;
+};
+
+// step()'s head, one thread per (run, row): soft_clamp, mean[:-1] += obs, std = sqrt(exp(logvar)), the sample of the chosen member
+// (mean + eps std: double like the reference's float64 noise, then fp32) and the penalty over ALL members
+__global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  if (i >= p.n) return;
+  const int D = p.D, od = p.od, K = p.K;
+  const float* mx = p.params + r * p.P + p.off_max;
+  const float* mn = p.params + r * p.P + p.off_min;
+  const float* obs = p.obs + ((long)r * p.n + i) * od;
+  auto mean_at = [&](int k, int d) {
+    float m = p.OUT[(((long)r * K + k) * p.n + i) * p.op + d];
+    if (d < od) m += obs[d];
+    return m;
+  };
+  auto std_at = [&](int k, int d) {
+    const float x = p.OUT[(((long)r * K + k) * p.n + i) * p.op + D + d];
+    const float l1 = mx[d] - dyn_softplus(mx[d] - x);
+    const float lv = mn[d] + dyn_softplus(l1 - mn[d]);
+    return sqrtf(expf(lv));
+  };
+  int mi;
+  uint32_t rnd[4];
+  if (p.midx) mi = p.midx[(long)r * p.n + i];
+  else {
+    dyn_philox(p.seed, (uint32_t)i, (uint32_t)(i >> 32), (uint32_t)r, (uint32_t)(0x80000000u | (uint32_t)p.call), rnd);
+    mi = p.elites[r * K + (int)(((uint64_t)rnd[0] * (uint64_t)p.n_elites) >> 32)];
+  }
+  for (int d0 = 0; d0 < D; d0 += 4) {
+    if (!p.noise) dyn_philox(p.seed, (uint32_t)i, (uint32_t)(i >> 32), (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)(d0 >> 2), rnd);
+    for (int j = 0; j < 4 && d0 + j < D; ++j) {
+      const int d = d0 + j;
+      double eps;
+      if (p.noise) eps = (double)p.noise[(((long)r * K + mi) * p.n + i) * D + d];
+      else {
+        // Box-Muller on the pair (j & ~1, j | 1) of this Philox word
+        const float u1 = dyn_u01(rnd[j & ~1]), u2 = dyn_u01(rnd[j | 1]);
+        const float rad = sqrtf(-2.0f * logf(u1)), th = 6.28318530717958647692f * u2;
+        eps = (double)((j & 1) ? rad * sinf(th) : rad * cosf(th));
+      }
+      const float s = (float)((double)mean_at(mi, d) + eps * (double)std_at(mi, d));
+      if (d < od) p.next_obs[((long)r * p.n + i) * od + d] = s;
+      else p.raw_reward[(long)r * p.n + i] = s;
+    }
+  }
+  double pen = 0.0;
+  if (p.mode == ORL_DYN_PENALTY_ALEATORIC) {
+    for (int k = 0; k < K; ++k) {
+      double ss = 0.0;
+      for (int d = 0; d < D; ++d) { const double s = std_at(k, d); ss += s * s; }
+      pen = fmax(pen, sqrt(ss));
+    }
+  } else {
+    float mbar[DYN_MAXD];
+    for (int d = 0; d < od; ++d) {
+      double s = 0.0;
+      for (int k = 0; k < K; ++k) s += mean_at(k, d);
+      mbar[d] = (float)(s / K);
+    }
+    if (p.mode == ORL_DYN_PENALTY_PAIRWISE_DIFF) {
+      for (int k = 0; k < K; ++k) {
+        double ss = 0.0;
+        for (int d = 0; d < od; ++d) { const double df = (double)(mean_at(k, d) - mbar[d]); ss += df * df; }
+        pen = fmax(pen, sqrt(ss));
+      }
+    } else {
+      double vs = 0.0;
+      for (int d = 0; d < od; ++d) {
+        double s = 0.0;
+        for (int k = 0; k < K; ++k) { const double df = (double)mean_at(k, d) - (double)mbar[d]; s += df * df; }
+        vs += s / K;
+      }
+      pen = sqrt(vs / od);
+    }
+  }
+  const float penf = (float)pen;
+  const float raw = p.raw_reward[(long)r * p.n + i];
+  p.penalty[(long)r * p.n + i] = penf;
+  p.reward[(long)r * p.n + i] = raw - p.coef * penf;
+  if (p.midx_out) p.midx_out[(long)r * p.n + i] = mi;
+}
+
+}  // namespace orl
+
+using namespace orl;
+
+struct DynTensor { std::string name; long off; std::vector<long> shape; };
+
+struct orl_dynamics {
+  orl_dyn_config c;
+  int R, K, L, od, ad, in, D, O, B;
+  int width[ORL_MAX_HIDDEN + 2], pitch[ORL_MAX_HIDDEN + 2];
+  long P = 0, off_max = 0, off_min = 0;
+  long w_off[ORL_MAX_HIDDEN + 1], b_off[ORL_MAX_HIDDEN + 1], sw_off[ORL_MAX_HIDDEN + 1], sb_off[ORL_MAX_HIDDEN + 1];
+  std::vector<DynTensor> tensors;
+  hipStream_t stream = nullptr;
+  float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *grads = nullptr;
+  int* elites_d = nullptr;
+  std::vector<std::vector<int64_t>> elites_h;
+  std::vector<long long> tstep;
+  float *data_in = nullptr, *data_tg = nullptr; long n_data = 0;
+  float *mu = nullptr, *sd = nullptr;
+  // learn workspaces [R][K][B][pitch]
+  float *X0 = nullptr, *T = nullptr, *OUT = nullptr, *dOUT = nullptr, *dA = nullptr, *dB = nullptr;
+  float *H[ORL_MAX_HIDDEN] = {}, *Z[ORL_MAX_HIDDEN] = {};
+  float *lterm = nullptr, *gmax = nullptr, *gmin = nullptr, *decay_part = nullptr, *nll = nullptr, *loss_sum = nullptr;
+  int nblk = 0;
+  int* active_d = nullptr; long long* t0_d = nullptr;
+  int* idx_d = nullptr; long idx_cap = 0;
+  // validate / step workspaces, grown on demand: rows capacity
+  long s_cap = 0;
+  float *sX = nullptr, *sT = nullptr, *sH0 = nullptr, *sH1 = nullptr, *sOUT = nullptr, *sObs = nullptr, *sAct = nullptr, *sNoise = nullptr;
+  float *sNext = nullptr, *sRew = nullptr, *sRaw = nullptr, *sPen = nullptr;
+  int *sIdx = nullptr, *sMidx = nullptr, *sMidxOut = nullptr;
+  uint64_t step_calls = 0;
+  std::vector<void*> allocs;
+};
+
+static int dyn_alloc(orl_dynamics* d, void** p, size_t bytes) {
+  if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) return fail("orl_dyn: hipMalloc of " + std::to_string(bytes) + " bytes failed");
+  if (hipMemset(*p, 0, bytes ? bytes : 16) != hipSuccess) return fail("orl_dyn: hipMemset failed");
+  d->allocs.push_back(*p);
+  return 0;
+}
+template <class T>
+static int dyn_alloc_t(orl_dynamics* d, T** p, size_t count) { return dyn_alloc(d, (void**)p, sizeof(T) * count); }
+static void dyn_free(orl_dynamics* d, void* p) {
+  if (!p) return;
+  for (auto it = d->allocs.begin(); it != d->allocs.end(); ++it)
+    if (*it == p) { d->allocs.erase(it); break; }
+  hipFree(p);
+}
+
+#define DYN_HIP(expr)                                                                                   \
+  do {                                                                                                  \
+    hipError_t _e = (expr);                                                                             \
+    if (_e != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(_e));               \
+  } while (0)
+#define DYN_LAUNCHED(what)                                                                              \
+  do {                                                                                                  \
+    if (hipGetLastError() != hipSuccess) return fail(std::string(what) + ": launch failed");            \
+  } while (0)
+
+// ---- the matrix products (csrc/gemm.h) ----
+struct DMat { float* p; long s0, s1; int pitch; };   // [run][member][row][pitch]; s1 = 0: one matrix shared by the members
+
+// Y = act(X W_l + b_l) for every (run, member); epi E_BIAS_SWISH (z to Zo when non-null) or E_BIAS
+static int dyn_fwd(orl_dynamics* d, const DMat& X, int M, int l, const DMat& Y, float* Zo, bool swish) {
+  const int in = d->width[l], out = d->width[l + 1];
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.A = {X.p, X.s0, X.s1}; p.a_sr = X.pitch; p.a_sk = 1;
+  p.B = {d->params + d->w_off[l], d->P, (long)in * out}; p.b_sr = 1; p.b_sk = out; p.b_rlim = out & ~3;
+  p.C = Y.p; p.c_s0 = Y.s0; p.c_s1 = Y.s1; p.c_sr = Y.pitch; p.c_sn = 1;
+  p.M = M; p.N = out; p.K = in;
+  p.nz1 = d->K; p.ksplit = 1;
+  p.bias = {d->params + d->b_off[l], d->P, (long)out};
+  p.z_out = Zo;
+  const int nz = d->R * d->K;
+  const int cfg = pick_cfg(p.M, p.N, p.K, nz);
+  const bool kpad = X.pitch >= rup4(in);
+  hipError_t e = swish ? launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_SWISH>(cfg, p, nz, d->stream, kpad, false, P_F32)
+                       : launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(cfg, p, nz, d->stream, kpad, false, P_F32);
+  if (e != hipSuccess) return fail(std::string("orl_dyn forward gemm: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// dX = (dY W_l^T) * Swish'(Zin) where Zin is the pre-activation of layer l's input
+static int dyn_dgrad(orl_dynamics* d, const DMat& dY, int M, int l, const DMat& dX, const DMat& Zin) {
+  const int in = d->width[l], out = d->width[l + 1];
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.A = {dY.p, dY.s0, dY.s1}; p.a_sr = dY.pitch; p.a_sk = 1;
+  p.B = {d->params + d->w_off[l], d->P, (long)in * out}; p.b_sr = out; p.b_sk = 1;
+  p.C = dX.p; p.c_s0 = dX.s0; p.c_s1 = dX.s1; p.c_sr = dX.pitch; p.c_sn = 1;
+  p.M = M; p.N = in; p.K = out;
+  p.nz1 = d->K; p.ksplit = 1;
+  p.aux = {Zin.p, Zin.s0, Zin.s1}; p.aux_sr = Zin.pitch;
+  const int nz = d->R * d->K;
+  const int cfg = pick_cfg(p.M, p.N, p.K, nz);
+  hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_SWISH_GRAD>(cfg, p, nz, d->stream, dY.pitch >= rup4(out), false, P_F32);
+  if (e != hipSuccess) return fail(std::string("orl_dyn dgrad gemm: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// dW_l = X^T dY (stored (in, out)-major like the weight), db_l = column sums of dY, into the gradient block
+static int dyn_wgrad(orl_dynamics* d, const DMat& dY, const DMat& X, int M, int l) {
+  const int in = d->width[l], out = d->width[l + 1];
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.A = {dY.p, dY.s0, dY.s1}; p.a_sr = 1; p.a_sk = dY.pitch;
+  p.B = {X.p, X.s0, X.s1}; p.b_sr = 1; p.b_sk = X.pitch;
+  p.a_rlim = dY.pitch & ~3; p.b_rlim = X.pitch & ~3;
+  p.ones_row = 1 << 30;
+  p.M = out; p.N = in; p.K = M;
+  p.nz1 = d->K; p.ksplit = 1;
+  p.C = d->grads + d->w_off[l]; p.c_sr = 1; p.c_sn = out; p.c_s0 = d->P; p.c_s1 = (long)in * out; p.c_ks = 0;
+  p.bias_out = d->grads + d->b_off[l]; p.bo_s0 = d->P; p.bo_s1 = out; p.bo_ks = 0;
+  const int nz = d->R * d->K;
+  const int cfg = pick_cfg(p.M, p.N, p.K, nz);
+  hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(cfg, p, nz, d->stream, false, false, P_F32);
+  if (e != hipSuccess) return fail(std::string("orl_dyn wgrad gemm: ") + hipGetErrorString(e));
+  return 0;
+}
+
+static int dyn_grow_step(orl_dynamics* d, long rows) {
+  if (rows <= d->s_cap) return 0;
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  float** fs[] = {&d->sX, &d->sT, &d->sH0, &d->sH1, &d->sOUT, &d->sObs, &d->sAct, &d->sNoise, &d->sNext, &d->sRew, &d->sRaw, &d->sPen};
+  for (float** f : fs) { dyn_free(d, *f); *f = nullptr; }
+  int** is[] = {&d->sIdx, &d->sMidx, &d->sMidxOut};
+  for (int** f : is) { dyn_free(d, *f); *f = nullptr; }
+  const long R = d->R, K = d->K;
+  int hmax = 4;
+  for (int l = 1; l <= d->L; ++l) hmax = std::max(hmax, d->pitch[l]);
+  if (dyn_alloc_t(d, &d->sX, R * rows * d->pitch[0]) || dyn_alloc_t(d, &d->sT, R * rows * d->D) ||
+      dyn_alloc_t(d, &d->sH0, R * K * rows * hmax) || dyn_alloc_t(d, &d->sH1, R * K * rows * hmax) ||
+      dyn_alloc_t(d, &d->sOUT, R * K * rows * d->pitch[d->L + 1]) || dyn_alloc_t(d, &d->sObs, R * rows * d->od) ||
+      dyn_alloc_t(d, &d->sAct, R * rows * d->ad) || dyn_alloc_t(d, &d->sNoise, R * K * rows * d->D) ||
+      dyn_alloc_t(d, &d->sNext, R * rows * d->od) || dyn_alloc_t(d, &d->sRew, R * rows) || dyn_alloc_t(d, &d->sRaw, R * rows) ||
+      dyn_alloc_t(d, &d->sPen, R * rows) || dyn_alloc_t(d, &d->sIdx, R * rows) || dyn_alloc_t(d, &d->sMidx, R * rows) ||
+      dyn_alloc_t(d, &d->sMidxOut, R * rows))
+    return -1;
+  d->s_cap = rows;
+  return 0;
+}
+
+// forward of the whole ensemble on a 2-D input shared by the members (validate, step): OUT [R][K][n][pO]
+static int dyn_forward_shared(orl_dynamics* d, long n) {
+  const long R = d->R, K = d->K;
+  (void)R;
+  DMat X = {d->sX, n * d->pitch[0], 0, d->pitch[0]};
+  float* bufs[2] = {d->sH0, d->sH1};
+  for (int l = 0; l < d->L; ++l) {
+    const int pt = d->pitch[l + 1];
+    DMat Y = {bufs[l & 1], K * n * pt, n * pt, pt};
+    if (dyn_fwd(d, X, (int)n, l, Y, nullptr, true)) return -1;
+    X = Y;
+  }
+  const int po = d->pitch[d->L + 1];
+  DMat Y = {d->sOUT, K * n * po, n * po, po};
+  return dyn_fwd(d, X, (int)n, d->L, Y, nullptr, false);
+}
+
+// parameter block: state_dict order, every tensor 16-B aligned; returns its floats
+static long dyn_layout(orl_dynamics* d) {
+  long off = 0;
+  auto add = [&](const std::string& name, std::vector<long> shape) {
+    long n = 1;
+    for (long s : shape) n *= s;
+    d->tensors.push_back({name, off, shape});
+    const long o = off;
+    off += (n + 3) & ~3L;
+    return o;
+  };
+  const long K = d->K;
+  d->off_max = add("max_logvar", {d->D});
+  d->off_min = add("min_logvar", {d->D});
+  for (int l = 0; l <= d->L; ++l) {
+    const std::string pre = l < d->L ? "backbones." + std::to_string(l) + "." : std::string("output_layer.");
+    const long in = d->width[l], o = d->width[l + 1];
+    d->w_off[l] = add(pre + "weight", {K, in, o});
+    d->b_off[l] = add(pre + "bias", {K, 1, o});
+    d->sw_off[l] = add(pre + "saved_weight", {K, in, o});
+    d->sb_off[l] = add(pre + "saved_bias", {K, 1, o});
+  }
+  return off;
+}
+
+extern "C" {
+
+void orl_dyn_config_default(orl_dyn_config* c) {
+  memset(c, 0, sizeof(*c));
+  c->obs_dim = 17; c->act_dim = 6;
+  c->n_hidden = 4;
+  for (int i = 0; i < 4; ++i) c->hidden[i] = 200;
+  c->num_ensemble = 7; c->num_elites = 5; c->with_reward = 1;
+  const float wd[5] = {2.5e-5f, 5e-5f, 7.5e-5f, 7.5e-5f, 1e-4f};
+  for (int i = 0; i < 5; ++i) c->weight_decay[i] = wd[i];
+  c->lr = 1e-3f; c->adam_beta1 = 0.9f; c->adam_beta2 = 0.999f; c->adam_eps = 1e-8f;
+  c->batch_size = 256; c->logvar_loss_coef = 0.01f;
+  c->n_runs = 1; c->device = 0; c->precision = 0; c->seed = 0;
+}
+
+int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out) {
+  if (!cfg || !out) return fail("orl_dyn_create: null argument");
+  *out = nullptr;
+  const orl_dyn_config& c = *cfg;
+  if (c.n_hidden < 1 || c.n_hidden > ORL_MAX_HIDDEN) return fail("orl_dyn_create: n_hidden must be in [1, 4]");
+  if (c.obs_dim < 1 || c.act_dim < 1 || c.batch_size < 1 || c.n_runs < 1) return fail("orl_dyn_create: bad dims");
+  if (c.num_ensemble < 1 || c.num_ensemble > 64 || c.num_elites < 1 || c.num_elites > c.num_ensemble)
+    return fail("orl_dyn_create: need 1 <= num_elites <= num_ensemble <= 64");
+  if (c.obs_dim + (c.with_reward ? 1 : 0) > DYN_MAXD) return fail("orl_dyn_create: obs_dim + with_reward must be <= 64");
+  for (int i = 0; i < c.n_hidden; ++i) if (c.hidden[i] < 1) return fail("orl_dyn_create: bad hidden width");
+  if (c.precision != 0)
+    return fail("orl_dyn_create: the dynamics ensemble implements precision 0 (fp32 MFMA) only; precision 1 / 2 are not supported");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("orl_dyn_create: no HIP device (MI355X) visible");
+  if (c.device < 0 || c.device >= ndev) return fail("orl_dyn_create: device ordinal out of range");
+  if (hipSetDevice(c.device) != hipSuccess) return fail("orl_dyn_create: hipSetDevice failed");
+  orl_dynamics* d = new orl_dynamics();
+  d->c = c;
+  d->R = c.n_runs; d->K = c.num_ensemble; d->L = c.n_hidden; d->od = c.obs_dim; d->ad = c.act_dim;
+  d->in = c.obs_dim + c.act_dim; d->D = c.obs_dim + (c.with_reward ? 1 : 0); d->O = 2 * d->D; d->B = c.batch_size;
+  d->width[0] = d->in;
+  for (int l = 0; l < d->L; ++l) d->width[l + 1] = c.hidden[l];
+  d->width[d->L + 1] = d->O;
+  for (int l = 0; l <= d->L + 1; ++l) d->pitch[l] = rup4(d->width[l]);
+  d->P = dyn_layout(d);
+  const long R = d->R, B = d->B, K = d->K;
+  d->nblk = (int)((d->P + 1023) / 1024);
+  int hmax = 4;
+  for (int l = 1; l <= d->L; ++l) hmax = std::max(hmax, d->pitch[l]);
+  hmax = std::max(hmax, d->pitch[d->L + 1]);
+  bool bad = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess;
+  if (c.external_arena) d->params = c.external_arena;
+  else bad = bad || dyn_alloc_t(d, &d->params, R * d->P);
+  bad = bad || dyn_alloc_t(d, &d->adam_m, R * d->P) || dyn_alloc_t(d, &d->adam_v, R * d->P) ||
+        dyn_alloc_t(d, &d->grads, R * d->P) || dyn_alloc_t(d, &d->elites_d, R * K) || dyn_alloc_t(d, &d->mu, R * d->in) ||
+        dyn_alloc_t(d, &d->sd, R * d->in) || dyn_alloc_t(d, &d->X0, R * K * B * d->pitch[0]) || dyn_alloc_t(d, &d->T, R * K * B * d->D) ||
+        dyn_alloc_t(d, &d->OUT, R * K * B * d->pitch[d->L + 1]) || dyn_alloc_t(d, &d->dOUT, R * K * B * d->pitch[d->L + 1]) ||
+        dyn_alloc_t(d, &d->dA, R * K * B * hmax) || dyn_alloc_t(d, &d->dB, R * K * B * hmax) ||
+        dyn_alloc_t(d, &d->lterm, R * K * B * d->D) || dyn_alloc_t(d, &d->gmax, R * K * B * d->D) ||
+        dyn_alloc_t(d, &d->gmin, R * K * B * d->D) || dyn_alloc_t(d, &d->decay_part, R * d->nblk) || dyn_alloc_t(d, &d->nll, R) ||
+        dyn_alloc_t(d, &d->loss_sum, R) || dyn_alloc_t(d, &d->active_d, R) || dyn_alloc_t(d, &d->t0_d, R);
+  for (int l = 0; l < d->L && !bad; ++l)
+    bad = dyn_alloc_t(d, &d->H[l], R * K * B * d->pitch[l + 1]) || dyn_alloc_t(d, &d->Z[l], R * K * B * d->pitch[l + 1]);
+  if (bad) {
+    const std::string msg = orl_last_error();
+    orl_dyn_destroy(d);
+    return fail(msg.empty() ? "orl_dyn_create: allocation failed" : msg);
+  }
+  d->tstep.assign(R, 0);
+  d->elites_h.assign(R, std::vector<int64_t>());
+  std::vector<int> el(R * K, 0);
+  for (int r = 0; r < R; ++r) {
+    for (int k = 0; k < c.num_elites; ++k) { d->elites_h[r].push_back(k); el[r * K + k] = k; }
+  }
+  if (hipMemcpy(d->elites_d, el.data(), sizeof(int) * el.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    orl_dyn_destroy(d);
+    return fail("orl_dyn_create: elites upload failed");
+  }
+  // scaler defaults to the identity until orl_dyn_set_scaler
+  std::vector<float> one(R * d->in, 1.0f);
+  if (hipMemcpy(d->sd, one.data(), sizeof(float) * one.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    orl_dyn_destroy(d);
+    return fail("orl_dyn_create: scaler upload failed");
+  }
+  *out = d;
+  return 0;
+}
+
+void orl_dyn_destroy(orl_dynamics* d) {
+  if (!d) return;
+  if (d->stream) hipStreamSynchronize(d->stream);
+  for (void* p : d->allocs) hipFree(p);
+  if (d->stream) hipStreamDestroy(d->stream);
+  delete d;
+}
+
+int orl_dyn_sync(orl_dynamics* d) {
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+int64_t orl_dyn_floats(orl_dynamics* d) { return d ? d->P : -1; }
+
+int64_t orl_dyn_config_floats(const orl_dyn_config* c) {
+  if (!c || c->n_hidden < 1 || c->n_hidden > ORL_MAX_HIDDEN) return -1;
+  orl_dynamics d;
+  d.K = c->num_ensemble; d.L = c->n_hidden; d.in = c->obs_dim + c->act_dim; d.D = c->obs_dim + (c->with_reward ? 1 : 0); d.O = 2 * d.D;
+  d.width[0] = d.in;
+  for (int l = 0; l < d.L; ++l) d.width[l + 1] = c->hidden[l];
+  d.width[d.L + 1] = d.O;
+  return dyn_layout(&d);
+}
+int orl_dyn_num_tensors(orl_dynamics* d) { return d ? (int)d->tensors.size() : -1; }
+
+int orl_dyn_tensor(orl_dynamics* d, int idx, char* name, int name_cap, int64_t* offset, int32_t* ndim, int64_t shape[4]) {
+  if (!d || idx < 0 || idx >= (int)d->tensors.size()) return fail("orl_dyn_tensor: index out of range");
+  const DynTensor& t = d->tensors[idx];
+  if (name && name_cap > 0) { strncpy(name, t.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
+  if (offset) *offset = t.off;
+  if (ndim) *ndim = (int32_t)t.shape.size();
+  if (shape) for (size_t i = 0; i < t.shape.size() && i < 4; ++i) shape[i] = t.shape[i];
+  return 0;
+}
+
+float* orl_dyn_ptr(orl_dynamics* d, int run) { return (d && run >= 0 && run < d->R) ? d->params + (long)run * d->P : nullptr; }
+
+static int dyn_check_run(orl_dynamics* d, int run, int64_t n, const char* what) {
+  if (!d) return fail(std::string(what) + ": null handle");
+  if (run < 0 || run >= d->R) return fail(std::string(what) + ": run out of range");
+  if (n >= 0 && n != d->P) return fail(std::string(what) + ": expected " + std::to_string(d->P) + " floats");
+  return 0;
+}
+
+int orl_dyn_set(orl_dynamics* d, int run, const float* host, int64_t n) {
+  if (dyn_check_run(d, run, n, "orl_dyn_set")) return -1;
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  DYN_HIP(hipMemcpy(d->params + (long)run * d->P, host, sizeof(float) * d->P, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int orl_dyn_get(orl_dynamics* d, int run, float* host, int64_t n) {
+  if (dyn_check_run(d, run, n, "orl_dyn_get")) return -1;
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  DYN_HIP(hipMemcpy(host, d->params + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int orl_dyn_adam_get(orl_dynamics* d, int run, float* m, float* v, int64_t n, int64_t* step) {
+  if (dyn_check_run(d, run, n, "orl_dyn_adam_get")) return -1;
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  if (m) DYN_HIP(hipMemcpy(m, d->adam_m + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  if (v) DYN_HIP(hipMemcpy(v, d->adam_v + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  if (step) *step = d->tstep[run];
+  return 0;
+}
+
+int orl_dyn_adam_set(orl_dynamics* d, int run, const float* m, const float* v, int64_t n, int64_t step) {
+  if (dyn_check_run(d, run, n, "orl_dyn_adam_set")) return -1;
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  if (m) DYN_HIP(hipMemcpy(d->adam_m + (long)run * d->P, m, sizeof(float) * d->P, hipMemcpyHostToDevice));
+  if (v) DYN_HIP(hipMemcpy(d->adam_v + (long)run * d->P, v, sizeof(float) * d->P, hipMemcpyHostToDevice));
+  d->tstep[run] = step;
+  return 0;
+}
+
+int orl_dyn_set_elites(orl_dynamics* d, int run, const int64_t* idx, int n) {
+  if (dyn_check_run(d, run, -1, "orl_dyn_set_elites")) return -1;
+  if (n < 1 || n > d->K) return fail("orl_dyn_set_elites: need 1 <= n <= num_ensemble");
+  std::vector<int> el(d->K, 0);
+  for (int i = 0; i < n; ++i) {
+    if (idx[i] < 0 || idx[i] >= d->K) return fail("orl_dyn_set_elites: member index out of range");
+    el[i] = (int)idx[i];
+  }
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  DYN_HIP(hipMemcpy(d->elites_d + (long)run * d->K, el.data(), sizeof(int) * d->K, hipMemcpyHostToDevice));
+  d->elites_h[run].assign(idx, idx + n);
+  return 0;
+}
+
+int orl_dyn_get_elites(orl_dynamics* d, int run, int64_t* idx, int cap) {
+  if (dyn_check_run(d, run, -1, "orl_dyn_get_elites")) return -1;
+  const auto& e = d->elites_h[run];
+  for (int i = 0; i < (int)e.size() && i < cap; ++i) idx[i] = e[i];
+  return (int)e.size();
+}
+
+int orl_dyn_load_data(orl_dynamics* d, const float* inputs, const float* targets, int64_t n) {
+  if (!d || n < 1) return fail("orl_dyn_load_data: empty dataset");
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  dyn_free(d, d->data_in); dyn_free(d, d->data_tg);
+  d->data_in = d->data_tg = nullptr; d->n_data = 0;
+  if (dyn_alloc_t(d, &d->data_in, n * d->in) || dyn_alloc_t(d, &d->data_tg, n * d->D)) return -1;
+  DYN_HIP(hipMemcpy(d->data_in, inputs, sizeof(float) * n * d->in, hipMemcpyHostToDevice));
+  DYN_HIP(hipMemcpy(d->data_tg, targets, sizeof(float) * n * d->D, hipMemcpyHostToDevice));
+  d->n_data = n;
+  return 0;
+}
+
+int orl_dyn_set_scaler(orl_dynamics* d, int run, const float* mu, const float* std) {
+  if (dyn_check_run(d, run, -1, "orl_dyn_set_scaler")) return -1;
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  DYN_HIP(hipMemcpy(d->mu + (long)run * d->in, mu, sizeof(float) * d->in, hipMemcpyHostToDevice));
+  DYN_HIP(hipMemcpy(d->sd + (long)run * d->in, std, sizeof(float) * d->in, hipMemcpyHostToDevice));
+  return 0;
+}
+
+static int dyn_upload_idx(orl_dynamics* d, const int64_t* idx, long count) {
+  std::vector<int> h(count);
+  for (long i = 0; i < count; ++i) {
+    if (idx[i] < 0 || idx[i] >= d->n_data) return fail("orl_dyn: row index " + std::to_string(idx[i]) + " outside the loaded data");
+    h[i] = (int)idx[i];
+  }
+  if (count > d->idx_cap) {
+    DYN_HIP(hipStreamSynchronize(d->stream));
+    dyn_free(d, d->idx_d); d->idx_d = nullptr; d->idx_cap = 0;
+    if (dyn_alloc_t(d, &d->idx_d, count)) return -1;
+    d->idx_cap = count;
+  }
+  DYN_HIP(hipMemcpyAsync(d->idx_d, h.data(), sizeof(int) * count, hipMemcpyHostToDevice, d->stream));
+  DYN_HIP(hipStreamSynchronize(d->stream));      // h is released on return
+  return 0;
+}
+
+int orl_dyn_learn_epoch(orl_dynamics* d, const int64_t* idx, int64_t train_size, const int32_t* active, float* loss_out) {
+  if (!d || !idx || train_size < 1) return fail("orl_dyn_learn_epoch: bad arguments");
+  if (!d->n_data) return fail("orl_dyn_learn_epoch: no data loaded (orl_dyn_load_data)");
+  const int R = d->R, K = d->K, B = d->B, L = d->L, D = d->D;
+  if (dyn_upload_idx(d, idx, (long)R * K * train_size)) return -1;
+  std::vector<int> act(R, 1);
+  if (active) for (int r = 0; r < R; ++r) act[r] = active[r] ? 1 : 0;
+  std::vector<long long> t0(d->tstep.begin(), d->tstep.end());
+  DYN_HIP(hipMemcpy(d->active_d, act.data(), sizeof(int) * R, hipMemcpyHostToDevice));
+  DYN_HIP(hipMemcpy(d->t0_d, t0.data(), sizeof(long long) * R, hipMemcpyHostToDevice));
+  DYN_HIP(hipMemsetAsync(d->loss_sum, 0, sizeof(float) * R, d->stream));
+  const long nb = (train_size + B - 1) / B;
+  const int p0 = d->pitch[0], po = d->pitch[L + 1];
+  DynAdamP a;
+  memset(&a, 0, sizeof(a));
+  a.params = d->params; a.m = d->adam_m; a.v = d->adam_v; a.G = d->grads; a.P = d->P;
+  for (int l = 0; l <= L; ++l) {
+    const long nw = (long)K * d->width[l] * d->width[l + 1], nbias = (long)K * d->width[l + 1];
+    a.seg_b[a.nseg] = d->w_off[l]; a.seg_e[a.nseg] = d->w_off[l] + nw; a.seg_wd[a.nseg++] = d->c.weight_decay[l];
+    a.seg_b[a.nseg] = d->b_off[l]; a.seg_e[a.nseg] = d->b_off[l] + nbias; a.seg_wd[a.nseg++] = 0.f;
+  }
+  a.seg_b[a.nseg] = d->off_max; a.seg_e[a.nseg] = d->off_max + D; a.seg_wd[a.nseg++] = 0.f;
+  a.seg_b[a.nseg] = d->off_min; a.seg_e[a.nseg] = d->off_min + D; a.seg_wd[a.nseg++] = 0.f;
+  a.active = d->active_d; a.t0 = d->t0_d;
+  a.lr = d->c.lr; a.b1 = d->c.adam_beta1; a.b2 = d->c.adam_beta2; a.eps = d->c.adam_eps;
+  a.decay_part = d->decay_part; a.nblk = d->nblk;
+  const long xs1 = (long)B * p0, xs0 = (long)K * xs1;
+  for (long b = 0; b < nb; ++b) {
+    const int rows = (int)std::min<long>(B, train_size - b * B);
+    hipLaunchKernelGGL(k_dyn_gather, dim3((rows + 255) / 256, K, R), dim3(256), 0, d->stream, (const int*)d->idx_d, (long)K * train_size,
+                       (long)train_size, b * B, rows, (const float*)d->data_in, (const float*)d->data_tg, d->in, D, (const float*)d->mu,
+                       (const float*)d->sd, d->X0, xs0, xs1, p0, d->T, (long)K * B * D, (long)B * D);
+    DYN_LAUNCHED("k_dyn_gather");
+    // forward
+    std::vector<DMat> Xs(L + 1), Zs(L);
+    Xs[0] = {d->X0, xs0, xs1, p0};
+    for (int l = 0; l < L; ++l) {
+      const int pt = d->pitch[l + 1];
+      Xs[l + 1] = {d->H[l], (long)K * B * pt, (long)B * pt, pt};
+      Zs[l] = {d->Z[l], (long)K * B * pt, (long)B * pt, pt};
+      if (dyn_fwd(d, Xs[l], rows, l, Xs[l + 1], d->Z[l], true)) return -1;
+    }
+    const DMat Out = {d->OUT, (long)K * B * po, (long)B * po, po}, dOut = {d->dOUT, (long)K * B * po, (long)B * po, po};
+    if (dyn_fwd(d, Xs[L], rows, L, Out, nullptr, false)) return -1;
+    // Gaussian NLL head
+    const long ne = (long)K * rows * D;
+    hipLaunchKernelGGL(k_dyn_nll, dim3((unsigned)((ne + 255) / 256), R), dim3(256), 0, d->stream, (const float*)d->OUT, d->dOUT, po,
+                       (const float*)d->T, d->lterm, d->gmax, d->gmin, (const float*)d->params, d->P, d->off_max, d->off_min, K, B, rows, D);
+    DYN_LAUNCHED("k_dyn_nll");
+    hipLaunchKernelGGL(k_dyn_nll_reduce, dim3(R), dim3(1024), 0, d->stream, (const float*)d->lterm, (const float*)d->gmax,
+                       (const float*)d->gmin, K, B, rows, D, (const float*)d->params, d->grads, d->P, d->off_max, d->off_min,
+                       d->c.logvar_loss_coef, d->nll);
+    DYN_LAUNCHED("k_dyn_nll_reduce");
+    // backward, top down
+    DMat dY = dOut;
+    float* dbuf[2] = {d->dA, d->dB};
+    for (int l = L; l >= 0; --l) {
+      if (dyn_wgrad(d, dY, Xs[l], rows, l)) return -1;
+      if (l > 0) {
+        const int pt = d->pitch[l];
+        const DMat dX = {dbuf[l & 1], (long)K * B * pt, (long)B * pt, pt};
+        if (dyn_dgrad(d, dY, rows, l, dX, Zs[l - 1])) return -1;
+        dY = dX;
+      }
+    }
+    a.batch = (int)b;
+    hipLaunchKernelGGL(k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, d->stream, a);
+    DYN_LAUNCHED("k_dyn_adam");
+    hipLaunchKernelGGL(k_dyn_loss, dim3(R), dim3(256), 0, d->stream, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
+                       (const int*)d->active_d, d->loss_sum);
+    DYN_LAUNCHED("k_dyn_loss");
+  }
+  std::vector<float> ls(R);
+  DYN_HIP(hipMemcpyAsync(ls.data(), d->loss_sum, sizeof(float) * R, hipMemcpyDeviceToHost, d->stream));
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  for (int r = 0; r < R; ++r) {
+    if (act[r]) d->tstep[r] += nb;
+    if (loss_out) loss_out[r] = act[r] ? (float)((double)ls[r] / (double)nb) : 0.f;
+  }
+  return 0;
+}
+
+int orl_dyn_validate(orl_dynamics* d, const int64_t* idx, int64_t H, float* mse_out) {
+  if (!d || !idx || H < 1 || !mse_out) return fail("orl_dyn_validate: bad arguments");
+  if (!d->n_data) return fail("orl_dyn_validate: no data loaded (orl_dyn_load_data)");
+  const int R = d->R, K = d->K, D = d->D;
+  if (dyn_grow_step(d, H)) return -1;
+  if (dyn_upload_idx(d, idx, (long)R * H)) return -1;
+  hipLaunchKernelGGL(k_dyn_gather, dim3((unsigned)((H + 255) / 256), 1, R), dim3(256), 0, d->stream, (const int*)d->idx_d, (long)H, 0L, 0L,
+                     (int)H, (const float*)d->data_in, (const float*)d->data_tg, d->in, D, (const float*)d->mu, (const float*)d->sd, d->sX,
+                     (long)H * d->pitch[0], 0L, d->pitch[0], d->sT, (long)H * D, 0L);
+  DYN_LAUNCHED("k_dyn_gather");
+  if (dyn_forward_shared(d, H)) return -1;
+  float* mse = d->sNoise;      // R * K floats of the noise staging (R * K * H * D)
+  hipLaunchKernelGGL(k_dyn_val_mse, dim3(K, R), dim3(256), 0, d->stream, (const float*)d->sOUT, d->pitch[d->L + 1], (const float*)d->sT,
+                     (int)H, D, K, mse);
+  DYN_LAUNCHED("k_dyn_val_mse");
+  DYN_HIP(hipMemcpyAsync(mse_out, mse, sizeof(float) * R * K, hipMemcpyDeviceToHost, d->stream));
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+int orl_dyn_update_save(orl_dynamics* d, int run, const int32_t* mask) {
+  if (dyn_check_run(d, run, -1, "orl_dyn_update_save")) return -1;
+  float* base = d->params + (long)run * d->P;
+  for (int l = 0; l <= d->L; ++l) {
+    const long nw = (long)d->width[l] * d->width[l + 1], nbias = d->width[l + 1];
+    for (int k = 0; k < d->K; ++k) {
+      if (!mask[k]) continue;
+      DYN_HIP(hipMemcpyAsync(base + d->sw_off[l] + k * nw, base + d->w_off[l] + k * nw, sizeof(float) * nw, hipMemcpyDeviceToDevice, d->stream));
+      DYN_HIP(hipMemcpyAsync(base + d->sb_off[l] + k * nbias, base + d->b_off[l] + k * nbias, sizeof(float) * nbias, hipMemcpyDeviceToDevice, d->stream));
+    }
+  }
+  return 0;
+}
+
+int orl_dyn_load_save(orl_dynamics* d, int run) {
+  if (dyn_check_run(d, run, -1, "orl_dyn_load_save")) return -1;
+  float* base = d->params + (long)run * d->P;
+  for (int l = 0; l <= d->L; ++l) {
+    const long nw = (long)d->K * d->width[l] * d->width[l + 1], nbias = (long)d->K * d->width[l + 1];
+    DYN_HIP(hipMemcpyAsync(base + d->w_off[l], base + d->sw_off[l], sizeof(float) * nw, hipMemcpyDeviceToDevice, d->stream));
+    DYN_HIP(hipMemcpyAsync(base + d->b_off[l], base + d->sb_off[l], sizeof(float) * nbias, hipMemcpyDeviceToDevice, d->stream));
+  }
+  return 0;
+}
+
+int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n, int on_device, const float* noise, const int64_t* model_idx,
+                 int mode, float coef, float* next_obs, float* reward, float* raw_reward, float* penalty, int32_t* midx_out) {
+  if (!d || !obs || !act || n < 1 || !next_obs || !reward || !raw_reward || !penalty) return fail("orl_dyn_step: bad arguments");
+  if (!d->c.with_reward) return fail("orl_dyn_step: needs with_reward (step() splits the reward off the last output)");
+  if (mode < 0 || mode > 2) return fail("orl_dyn_step: unknown penalty mode");
+  const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
+  if (dyn_grow_step(d, n)) return -1;
+  const hipMemcpyKind h2d = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const float* obs_d = obs;
+  const float* act_d = act;
+  if (!on_device) {
+    DYN_HIP(hipMemcpyAsync(d->sObs, obs, sizeof(float) * R * n * od, h2d, d->stream));
+    DYN_HIP(hipMemcpyAsync(d->sAct, act, sizeof(float) * R * n * ad, h2d, d->stream));
+    obs_d = d->sObs; act_d = d->sAct;
+  }
+  const float* noise_d = nullptr;
+  const int* midx_d = nullptr;
+  if (noise) {
+    if (on_device) noise_d = noise;
+    else {
+      DYN_HIP(hipMemcpyAsync(d->sNoise, noise, sizeof(float) * R * K * n * D, h2d, d->stream));
+      noise_d = d->sNoise;
+    }
+  }
+  std::vector<int> mi;
+  if (model_idx) {
+    if (on_device) return fail("orl_dyn_step: teacher-forced model indices are host arrays");
+    mi.resize((size_t)R * n);
+    for (long i = 0; i < (long)R * n; ++i) {
+      if (model_idx[i] < 0 || model_idx[i] >= K) return fail("orl_dyn_step: model index out of range");
+      mi[i] = (int)model_idx[i];
+    }
+    DYN_HIP(hipMemcpyAsync(d->sMidx, mi.data(), sizeof(int) * mi.size(), hipMemcpyHostToDevice, d->stream));
+    midx_d = d->sMidx;
+  }
+  hipLaunchKernelGGL(k_dyn_step_input, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, d->stream, obs_d, act_d, (long)n, od, ad,
+                     (const float*)d->mu, (const float*)d->sd, d->sX, d->pitch[0]);
+  DYN_LAUNCHED("k_dyn_step_input");
+  if (dyn_forward_shared(d, n)) return -1;
+  DynHeadP h;
+  memset(&h, 0, sizeof(h));
+  h.OUT = d->sOUT; h.op = d->pitch[d->L + 1];
+  h.obs = obs_d; h.n = n; h.od = od; h.D = D; h.K = K;
+  h.params = d->params; h.P = d->P; h.off_max = d->off_max; h.off_min = d->off_min;
+  h.noise = noise_d; h.midx = midx_d;
+  h.elites = d->elites_d;
+  h.n_elites = (int)d->elites_h[0].size();
+  for (int r = 1; r < R; ++r)
+    if ((int)d->elites_h[r].size() != h.n_elites) return fail("orl_dyn_step: every run needs the same number of elites");
+  h.seed = d->c.seed; h.call = d->step_calls++;
+  h.mode = mode; h.coef = coef;
+  h.next_obs = on_device ? next_obs : d->sNext;
+  h.reward = on_device ? reward : d->sRew;
+  h.raw_reward = on_device ? raw_reward : d->sRaw;
+  h.penalty = on_device ? penalty : d->sPen;
+  h.midx_out = midx_out ? (on_device ? (int*)midx_out : d->sMidxOut) : nullptr;
+  hipLaunchKernelGGL(k_dyn_head, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, d->stream, h);
+  DYN_LAUNCHED("k_dyn_head");
+  if (!on_device) {
+    DYN_HIP(hipMemcpyAsync(next_obs, d->sNext, sizeof(float) * R * n * od, hipMemcpyDeviceToHost, d->stream));
+    DYN_HIP(hipMemcpyAsync(reward, d->sRew, sizeof(float) * R * n, hipMemcpyDeviceToHost, d->stream));
+    DYN_HIP(hipMemcpyAsync(raw_reward, d->sRaw, sizeof(float) * R * n, hipMemcpyDeviceToHost, d->stream));
+    DYN_HIP(hipMemcpyAsync(penalty, d->sPen, sizeof(float) * R * n, hipMemcpyDeviceToHost, d->stream));
+    if (midx_out) DYN_HIP(hipMemcpyAsync(midx_out, d->sMidxOut, sizeof(int) * R * n, hipMemcpyDeviceToHost, d->stream));
+  }
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n) {
+  if (dyn_check_run(d, run, n, "orl_dyn_debug_grads")) return -1;
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  DYN_HIP(hipMemcpy(host, d->grads + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // extern "C"

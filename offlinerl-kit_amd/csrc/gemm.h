@@ -181,7 +181,9 @@ enum { P_F32 = 0, P_SPLIT = 1, P_BF16X3 = P_SPLIT, P_SPLIT3 = 2 };
 enum { PA_PLAIN = 0, PA_RANK1 = 1, PA_RANK1B = 2 };                    // prologue on A elements (RANK1B: ReLU mask from packed bits)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 enum { PB_PLAIN = 0, PB_ONES = 1 };                                    // prologue on B elements
-enum { E_PLAIN = 0, E_BIAS = 1, E_BIAS_RELU = 2, E_MASK = 3, E_WGRAD = 4 };
+enum { E_PLAIN = 0, E_BIAS = 1, E_BIAS_RELU = 2, E_MASK = 3, E_WGRAD = 4,
+       E_BIAS_SWISH = 5,      // h = z sigmoid(z), z = acc + bias; z also to z_out (C's strides) when non-null (the dynamics ensemble, Swish)
+       E_SWISH_GRAD = 6 };    // C = acc * sigmoid(z) (1 + z (1 - sigmoid(z))) with z = aux[m][n]: the Swish counterpart of E_MASK
 enum { L_SCALAR = 0, L_VECK = 1, L_BLK4 = 2, L_VECKU = 3 };            // operand loaders
 
 struct ZPtr {        // base + z0 * s0 + z1 * s1 (element strides)
@@ -247,7 +249,16 @@ struct GemmP {
   // gridDim.z = ceil(nz / 8); problem z = 8 * blockIdx.z + (blockIdx.x & 7), item = blockIdx.x >> 3 -- every tile of one problem has
   // the same linear-id residue mod 8, i.e. (round-robin placement) the same XCD and its L2, instead of one XCD per tile
   int zmajor, nz_total;
+  // E_BIAS_SWISH: the pre-activation z (what the E_SWISH_GRAD dgrad reads back as aux), same strides as C; null = not stored
+  float* z_out;
 };
+
+// Swish (x sigmoid(x)) and its derivative sigmoid(x) (1 + x (1 - sigmoid(x))): v_exp_f32 + v_rcp_f32 per element
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
+__device__ __forceinline__ float orl_sigmoid(float z) { return __frcp_rn(1.0f + __expf(-z)); }
+__device__ __forceinline__ float orl_swish(float z) { return z * orl_sigmoid(z); }
+__device__ __forceinline__ float orl_dswish(float z) { const float s = orl_sigmoid(z); return s * (1.0f + z * (1.0f - s)); }
+#endif
 
 enum { W0_XP = 28 };     // LDS pitch of the X tile staged by the fused layer-0 weight gradient (floats)
 

@@ -458,7 +458,9 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
   float* bo = (EPI == E_WGRAD && p.bias_out) ? p.bias_out + z0 * p.bo_s0 + z1 * p.bo_s1 + (long)ks * p.bo_ks : nullptr;
   const bool vec_ok = (p.c_sn == 1) && ((p.c_sr & 3) == 0) && ((((uintptr_t)Cg) & 15) == 0) &&
                       (EPI != E_MASK || p.aux_bits != nullptr || (((p.aux_sr & 3) == 0) && ((((uintptr_t)aux) & 15) == 0))) &&
-                      ((EPI != E_BIAS && EPI != E_BIAS_RELU) || ((((uintptr_t)bias) & 15) == 0));
+                      (EPI != E_SWISH_GRAD || (((p.aux_sr & 3) == 0) && ((((uintptr_t)aux) & 15) == 0))) &&
+                      ((EPI != E_BIAS && EPI != E_BIAS_RELU && EPI != E_BIAS_SWISH) || ((((uintptr_t)bias) & 15) == 0));
+  float* __restrict__ zo = (EPI == E_BIAS_SWISH && p.z_out) ? p.z_out + z0 * p.c_s0 + z1 * p.c_s1 : nullptr;
   if (EPI == E_WGRAD && PA == PA_RANK1 && LA == L_BLK4) {
     if (p.tail_w_out && tn == 0) {
       // deterministic reduction of the per-thread partials: sred[k-slot][row], summed in k-slot order
@@ -538,7 +540,7 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
     const int n = n0 + 4 * c4;
     const bool n_ok = n < p.N;
     // the mask tile is fetched first (clamped addresses, no branches) so its latency hides behind the LDS staging
-    f32x4 hv[EPI == E_MASK ? NPASS : 1];
+    f32x4 hv[(EPI == E_MASK || EPI == E_SWISH_GRAD) ? NPASS : 1];
     const bool xbits = (EPI == E_MASK) && (p.aux_bits != nullptr);           // uniform: the mask comes as packed bits
     if (EPI == E_MASK) {
       const unsigned int* xb = p.aux_bits + z0 * p.xb_s0 + z1 * p.xb_s1;
@@ -548,6 +550,14 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
         m = m < p.M ? m : p.M - 1;
         if (xbits) hv[i][0] = __uint_as_float(xb[(long)m * p.xb_g + ((n_ok ? n : 0) >> 5)]);
         else hv[i] = *(const f32x4*)&aux[(long)m * p.aux_sr + (n_ok ? n : 0)];
+      }
+    }
+    if (EPI == E_SWISH_GRAD) {
+#pragma unroll
+      for (int i = 0; i < NPASS; ++i) {
+        int m = m0 + r0 + i * RPP;
+        m = m < p.M ? m : p.M - 1;
+        hv[i] = *(const f32x4*)&aux[(long)m * p.aux_sr + (n_ok ? n : 0)];
       }
     }
     // fused layer-0 weight gradient: this thread's pieces of the X tile [TM][W0_XP], fetched now for the same reason
@@ -567,7 +577,7 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
       }
     }
     f32x4 bv = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (EPI == E_BIAS || EPI == E_BIAS_RELU) bv = *(const f32x4*)&bias[n_ok ? n : 0];
+    if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH) bv = *(const f32x4*)&bias[n_ok ? n : 0];
     const bool tq = (EPI == E_BIAS_RELU) && (p.tq_out != nullptr);       // uniform
     f32x4 tw = (f32x4){0.f, 0.f, 0.f, 0.f};
     float tq_bias = 0.f;
@@ -596,7 +606,16 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
       const int m = m0 + r;
       if (r < TM) {
         f32x4 v = *(const f32x4*)&cs[r * CP + 4 * c4];
-        if (EPI == E_BIAS || EPI == E_BIAS_RELU) v += bv;
+        if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH) v += bv;
+        if (EPI == E_BIAS_SWISH) {
+          if (zo && n_ok && m < p.M) *(f32x4*)&zo[(long)m * p.c_sr + n] = v;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = orl_swish(v[j]);
+        }
+        if (EPI == E_SWISH_GRAD) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] *= orl_dswish(hv[i][j]);
+        }
         if (EPI == E_BIAS_RELU) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
@@ -691,7 +710,17 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
         f32x4 v = acc[a][b];
         const int nlim = p.N;
         if (vec_ok && nb + 4 <= nlim) {
-          if (EPI == E_BIAS || EPI == E_BIAS_RELU) { const f32x4 bv = *(const f32x4*)&bias[nb]; v += bv; }
+          if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH) { const f32x4 bv = *(const f32x4*)&bias[nb]; v += bv; }
+          if (EPI == E_BIAS_SWISH) {
+            if (zo) *(f32x4*)&zo[(long)m * p.c_sr + nb] = v;
+  #pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = orl_swish(v[r]);
+          }
+          if (EPI == E_SWISH_GRAD) {
+            const f32x4 zv = *(const f32x4*)&aux[(long)m * p.aux_sr + nb];
+  #pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] *= orl_dswish(zv[r]);
+          }
           if (EPI == E_BIAS_RELU) {
   #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
@@ -711,6 +740,12 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
             if (EPI == E_BIAS) x += bias[n];
             if (EPI == E_BIAS_RELU) { x += bias[n]; x = x > 0.f ? x : 0.f; }
             if (EPI == E_MASK) x = aux[(long)m * p.aux_sr + n] > 0.f ? x : 0.f;
+            if (EPI == E_BIAS_SWISH) {
+              x += bias[n];
+              if (zo) zo[(long)m * p.c_sr + (long)n * p.c_sn] = x;
+              x = orl_swish(x);
+            }
+            if (EPI == E_SWISH_GRAD) x *= orl_dswish(aux[(long)m * p.aux_sr + n]);
             Cg[(long)m * p.c_sr + (long)n * p.c_sn] = x;
           }
         }

@@ -48,7 +48,13 @@ ABI_SYMBOLS = [
     "orl_buffer_normalize_obs", "orl_buffer_sample", "orl_buffer_size", "orl_engine_attach_buffer", "orl_step", "orl_learn_n",
     "orl_health", "orl_health_check", "orl_health_clear", "orl_num_metrics", "orl_metric_name", "orl_step_count",
     "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
+    # dynamics ensemble (orl_dynamics)
+    "orl_dyn_config_default", "orl_dyn_create", "orl_dyn_destroy", "orl_dyn_sync", "orl_dyn_floats", "orl_dyn_config_floats",
+    "orl_dyn_num_tensors", "orl_dyn_tensor", "orl_dyn_ptr", "orl_dyn_set", "orl_dyn_get", "orl_dyn_adam_get", "orl_dyn_adam_set",
+    "orl_dyn_set_elites", "orl_dyn_get_elites", "orl_dyn_load_data", "orl_dyn_set_scaler", "orl_dyn_learn_epoch", "orl_dyn_validate",
+    "orl_dyn_update_save", "orl_dyn_load_save", "orl_dyn_step", "orl_dyn_debug_grads",
 ]
+DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
 
 
 class OrlConfig(C.Structure):
@@ -71,6 +77,18 @@ class OrlConfig(C.Structure):
         ("cql_cons_row0", C.c_int32), ("cql_cons_rows", C.c_int32), ("cql_real_rows", C.c_int32),
         ("vae_hidden", C.c_int32), ("vae_latent", C.c_int32), ("mcq_lambda", C.c_float), ("behavior_lr", C.c_float),
         ("ws_one_round", C.c_int32), ("ws_cus", C.c_int32), ("actor_dropout", C.c_float),
+        ("external_arena", C.c_void_p),
+    ]
+
+
+class OrlDynConfig(C.Structure):
+    _fields_ = [
+        ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_HIDDEN),
+        ("num_ensemble", C.c_int32), ("num_elites", C.c_int32), ("with_reward", C.c_int32),
+        ("weight_decay", C.c_float * (MAX_HIDDEN + 1)),
+        ("lr", C.c_float), ("adam_beta1", C.c_float), ("adam_beta2", C.c_float), ("adam_eps", C.c_float),
+        ("batch_size", C.c_int32), ("logvar_loss_coef", C.c_float),
+        ("n_runs", C.c_int32), ("device", C.c_int32), ("precision", C.c_int32), ("seed", C.c_uint64),
         ("external_arena", C.c_void_p),
     ]
 
@@ -161,9 +179,42 @@ def load_library(path: Optional[str] = None):
     lib.orl_profile_enable.argtypes = [C.c_void_p, C.c_int]
     lib.orl_profile_query.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double),
                                       C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    _bind_dynamics(lib)
     if path is None:
         _lib = lib
     return lib
+
+
+def _bind_dynamics(lib) -> None:
+    P, I64, F, VP = C.c_void_p, C.c_int64, C.c_float, C.c_void_p
+    lib.orl_dyn_config_default.argtypes = [C.POINTER(OrlDynConfig)]
+    lib.orl_dyn_config_default.restype = None
+    lib.orl_dyn_create.argtypes = [C.POINTER(OrlDynConfig), C.POINTER(C.c_void_p)]
+    lib.orl_dyn_destroy.argtypes = [P]
+    lib.orl_dyn_destroy.restype = None
+    lib.orl_dyn_sync.argtypes = [P]
+    lib.orl_dyn_floats.argtypes = [P]
+    lib.orl_dyn_floats.restype = I64
+    lib.orl_dyn_config_floats.argtypes = [C.POINTER(OrlDynConfig)]
+    lib.orl_dyn_config_floats.restype = I64
+    lib.orl_dyn_num_tensors.argtypes = [P]
+    lib.orl_dyn_tensor.argtypes = [P, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    lib.orl_dyn_ptr.argtypes = [P, C.c_int]
+    lib.orl_dyn_ptr.restype = VP
+    lib.orl_dyn_set.argtypes = [P, C.c_int, VP, I64]
+    lib.orl_dyn_get.argtypes = [P, C.c_int, VP, I64]
+    lib.orl_dyn_adam_get.argtypes = [P, C.c_int, VP, VP, I64, C.POINTER(C.c_int64)]
+    lib.orl_dyn_adam_set.argtypes = [P, C.c_int, VP, VP, I64, I64]
+    lib.orl_dyn_set_elites.argtypes = [P, C.c_int, VP, C.c_int]
+    lib.orl_dyn_get_elites.argtypes = [P, C.c_int, VP, C.c_int]
+    lib.orl_dyn_load_data.argtypes = [P, VP, VP, I64]
+    lib.orl_dyn_set_scaler.argtypes = [P, C.c_int, VP, VP]
+    lib.orl_dyn_learn_epoch.argtypes = [P, VP, I64, VP, VP]
+    lib.orl_dyn_validate.argtypes = [P, VP, I64, VP]
+    lib.orl_dyn_update_save.argtypes = [P, C.c_int, VP]
+    lib.orl_dyn_load_save.argtypes = [P, C.c_int]
+    lib.orl_dyn_step.argtypes = [P, VP, VP, I64, C.c_int, VP, VP, C.c_int, F, VP, VP, VP, VP, VP]
+    lib.orl_dyn_debug_grads.argtypes = [P, C.c_int, VP, I64]
 
 
 def split_bits() -> int:
@@ -496,3 +547,160 @@ def debug_gemm(cfg: int, mode: int, A, B, v0=None, v1=None, ksplit=1, precision=
                               p0.ctypes.data if p0 is not None else None, p1.ctypes.data if p1 is not None else None,
                               out.ctypes.data, ksplit, precision), "orl_debug_gemm")
     return out
+
+
+def default_dyn_config(**over) -> OrlDynConfig:
+    """orl_dyn_config_default (run_mopo.py's dynamics defaults) with overrides; ``hidden`` / ``weight_decay`` take lists"""
+    cfg = OrlDynConfig()
+    load_library().orl_dyn_config_default(C.byref(cfg))
+    names = {f[0] for f in OrlDynConfig._fields_}
+    for k, v in over.items():
+        if k == "hidden":
+            cfg.n_hidden = len(v)
+            for i, h in enumerate(v):
+                cfg.hidden[i] = int(h)
+        elif k == "weight_decay":
+            for i, w in enumerate(v):
+                cfg.weight_decay[i] = float(w)
+        elif k in names:
+            setattr(cfg, k, v)
+        else:
+            raise KeyError(f"unknown dynamics config field {k!r}")
+    return cfg
+
+
+class Dynamics:
+    """RAII wrapper over ``orl_dynamics*``: the dynamics ensemble's parameters, Adam state, HBM dataset and kernels."""
+
+    def __init__(self, cfg: OrlDynConfig):
+        self.lib = load_library()
+        self.cfg = cfg
+        self._h = C.c_void_p()
+        _check(self.lib.orl_dyn_create(C.byref(cfg), C.byref(self._h)), "orl_dyn_create")
+        self.n_runs, self.K = cfg.n_runs, cfg.num_ensemble
+        self.od, self.ad = cfg.obs_dim, cfg.act_dim
+        self.D = cfg.obs_dim + (1 if cfg.with_reward else 0)
+        self.P = int(self.lib.orl_dyn_floats(self._h))
+        self.tensors = []
+        for i in range(self.lib.orl_dyn_num_tensors(self._h)):
+            name = C.create_string_buffer(128)
+            off, ndim, shape = C.c_int64(), C.c_int32(), (C.c_int64 * 4)()
+            _check(self.lib.orl_dyn_tensor(self._h, i, name, 128, C.byref(off), C.byref(ndim), shape), "orl_dyn_tensor")
+            self.tensors.append((name.value.decode(), off.value, tuple(shape[k] for k in range(ndim.value))))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.lib.orl_dyn_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        _check(self.lib.orl_dyn_sync(self._h), "orl_dyn_sync")
+
+    def ptr(self, run: int) -> int:
+        return self.lib.orl_dyn_ptr(self._h, run)
+
+    def set_params(self, run: int, params: Dict[str, np.ndarray]):
+        flat = np.zeros(self.P, dtype=np.float32)
+        for name, off, shape in self.tensors:
+            a = _f32(params[name])
+            if a.size != int(np.prod(shape)):
+                raise ValueError(f"{name}: expected shape {shape}, got {a.shape}")
+            flat[off:off + a.size] = a.ravel()
+        _check(self.lib.orl_dyn_set(self._h, run, flat.ctypes.data, self.P), "orl_dyn_set")
+
+    def _unflat(self, flat) -> Dict[str, np.ndarray]:
+        return {name: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in self.tensors}
+
+    def get_params(self, run: int) -> Dict[str, np.ndarray]:
+        flat = np.empty(self.P, dtype=np.float32)
+        _check(self.lib.orl_dyn_get(self._h, run, flat.ctypes.data, self.P), "orl_dyn_get")
+        return self._unflat(flat)
+
+    def adam_state(self, run: int):
+        """(exp_avg, exp_avg_sq) as tensor dicts and the step count"""
+        m, v, t = np.empty(self.P, np.float32), np.empty(self.P, np.float32), C.c_int64()
+        _check(self.lib.orl_dyn_adam_get(self._h, run, m.ctypes.data, v.ctypes.data, self.P, C.byref(t)), "orl_dyn_adam_get")
+        return self._unflat(m), self._unflat(v), t.value
+
+    def set_adam_state(self, run: int, m: Dict, v: Dict, step: int):
+        fm, fv = np.zeros(self.P, np.float32), np.zeros(self.P, np.float32)
+        for name, off, shape in self.tensors:
+            if name in m:
+                fm[off:off + int(np.prod(shape))] = _f32(m[name]).ravel()
+                fv[off:off + int(np.prod(shape))] = _f32(v[name]).ravel()
+        _check(self.lib.orl_dyn_adam_set(self._h, run, fm.ctypes.data, fv.ctypes.data, self.P, int(step)), "orl_dyn_adam_set")
+
+    def debug_grads(self, run: int) -> Dict[str, np.ndarray]:
+        flat = np.empty(self.P, dtype=np.float32)
+        _check(self.lib.orl_dyn_debug_grads(self._h, run, flat.ctypes.data, self.P), "orl_dyn_debug_grads")
+        return self._unflat(flat)
+
+    def set_elites(self, run: int, idx):
+        a = np.ascontiguousarray(idx, dtype=np.int64)
+        _check(self.lib.orl_dyn_set_elites(self._h, run, a.ctypes.data, a.size), "orl_dyn_set_elites")
+
+    def get_elites(self, run: int) -> np.ndarray:
+        a = np.zeros(self.K, dtype=np.int64)
+        n = self.lib.orl_dyn_get_elites(self._h, run, a.ctypes.data, self.K)
+        if n < 0:
+            raise RuntimeError(f"orl_dyn_get_elites failed: {last_error()}")
+        return a[:n].copy()
+
+    def load_data(self, inputs, targets):
+        x, t = _f32(inputs), _f32(targets)
+        assert x.shape[1] == self.od + self.ad and t.shape == (x.shape[0], self.D), (x.shape, t.shape)
+        _check(self.lib.orl_dyn_load_data(self._h, x.ctypes.data, t.ctypes.data, x.shape[0]), "orl_dyn_load_data")
+
+    def set_scaler(self, run: int, mu, std):
+        m, s = _f32(mu).ravel(), _f32(std).ravel()
+        assert m.size == self.od + self.ad and s.size == m.size
+        _check(self.lib.orl_dyn_set_scaler(self._h, run, m.ctypes.data, s.ctypes.data), "orl_dyn_set_scaler")
+
+    def learn_epoch(self, idx, active=None) -> np.ndarray:
+        """idx: [R][K][train_size] rows of the loaded data in minibatch order; returns the [R] mean minibatch losses"""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        assert idx.ndim == 3 and idx.shape[:2] == (self.n_runs, self.K), idx.shape
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        loss = np.zeros(self.n_runs, dtype=np.float32)
+        _check(self.lib.orl_dyn_learn_epoch(self._h, idx.ctypes.data, idx.shape[2], None if act is None else act.ctypes.data,
+                                            loss.ctypes.data), "orl_dyn_learn_epoch")
+        return loss
+
+    def validate(self, idx) -> np.ndarray:
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        assert idx.ndim == 2 and idx.shape[0] == self.n_runs
+        out = np.zeros((self.n_runs, self.K), dtype=np.float32)
+        _check(self.lib.orl_dyn_validate(self._h, idx.ctypes.data, idx.shape[1], out.ctypes.data), "orl_dyn_validate")
+        return out
+
+    def update_save(self, run: int, mask):
+        m = np.ascontiguousarray(mask, dtype=np.int32)
+        assert m.size == self.K
+        _check(self.lib.orl_dyn_update_save(self._h, run, m.ctypes.data), "orl_dyn_update_save")
+
+    def load_save(self, run: int):
+        _check(self.lib.orl_dyn_load_save(self._h, run), "orl_dyn_load_save")
+
+    def step(self, obs, act, noise=None, model_idx=None, mode: str = "aleatoric", coef: float = 0.0):
+        """obs [R][N][od], act [R][N][ad] host arrays; noise [R][K][N][od+1] / model_idx [R][N] teacher-force the draws
+        (None: device Philox).  Returns (next_obs, reward, raw_reward, penalty, model_idx)."""
+        o, a = _f32(obs), _f32(act)
+        R, n = o.shape[0], o.shape[1]
+        assert R == self.n_runs and a.shape[:2] == (R, n)
+        nz = None if noise is None else _f32(noise)
+        if nz is not None:
+            assert nz.shape == (R, self.K, n, self.D), nz.shape
+        mi = None if model_idx is None else np.ascontiguousarray(model_idx, dtype=np.int64)
+        nxt = np.empty((R, n, self.od), np.float32)
+        rew, raw, pen = np.empty((R, n), np.float32), np.empty((R, n), np.float32), np.empty((R, n), np.float32)
+        mo = np.empty((R, n), np.int32)
+        _check(self.lib.orl_dyn_step(self._h, o.ctypes.data, a.ctypes.data, n, 0, None if nz is None else nz.ctypes.data,
+                                     None if mi is None else mi.ctypes.data, DYN_PENALTY[mode], float(coef), nxt.ctypes.data,
+                                     rew.ctypes.data, raw.ctypes.data, pen.ctypes.data, mo.ctypes.data), "orl_dyn_step")
+        return nxt, rew, raw, pen, mo

@@ -1,0 +1,343 @@
+"""The dynamics ensemble of the model-based algorithms (reference: dynamics/base_dynamics.py, dynamics/ensemble_dynamics.py) on the HIP
+engine (``orl_dyn_*`` of include/orl_engine.h, csrc/dynamics.hip).
+
+``EnsembleDynamics`` keeps the reference's host logic -- the holdout split, the scaler, the bootstrap and shuffle indices, the 1 %
+improvement rule, the elites, the logger keys, ``save`` / ``load`` -- and consumes the host RNGs in the reference's order
+(``torch.utils.data.random_split``, ``np.random.randint``, ``np.random.uniform`` per epoch).  The arithmetic runs on the device: one
+``learn()`` epoch is one call that enqueues every minibatch without a host round trip, ``validate`` and ``step`` are one call each.
+
+``step`` draws its Gaussian noise and its elite per row from a device Philox stream by default (``seed`` of
+``set_engine_options``): the reference's ``np.random.normal`` / ``np.random.choice`` stream cannot be reproduced on the device, so
+the samples are distributed like the reference's, not equal to them.  Pass ``noise`` / ``model_idxs`` to ``step`` to teacher-force
+the reference's draws.
+
+Multi-run: ``set_engine_options(n_runs=R)`` trains R independent ensembles (runs) in the same launches.  Each run has its own holdout
+split, scaler, bootstrap indices, early-stopping counter and elites; ``train`` loops until every run has stopped.  The torch module
+shows the run chosen by ``select_run`` (run 0 by default).
+"""
+from __future__ import annotations
+
+import os
+from typing import Callable, Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _engine
+from ..utils.scaler import StandardScaler
+
+
+class BaseDynamics(object):
+    def __init__(self, model: nn.Module, optim: torch.optim.Optimizer) -> None:
+        super().__init__()
+        self.model = model
+        self.optim = optim
+
+    def step(self, obs: np.ndarray, action: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Dict]:
+        raise NotImplementedError
+
+
+def _fresh_model_params(model, seed: int) -> Dict[str, torch.Tensor]:
+    """the constructor's initialisation under torch seed ``seed`` (runs r > 0 of a multi-run ensemble)"""
+    from ..modules import EnsembleDynamicsModel
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        m = EnsembleDynamicsModel(model.obs_dim, model.action_dim, model.hidden_dims, model.num_ensemble, model.num_elites,
+                                  weight_decays=model.weight_decays, with_reward=bool(model._with_reward))
+    return dict(m.named_parameters())
+
+
+class EnsembleDynamics(BaseDynamics):
+    def __init__(self, model: nn.Module, optim: torch.optim.Optimizer, scaler: StandardScaler,
+                 terminal_fn: Callable[[np.ndarray, np.ndarray, np.ndarray], np.ndarray], penalty_coef: float = 0.0,
+                 uncertainty_mode: str = "aleatoric") -> None:
+        super().__init__(model, optim)
+        if uncertainty_mode not in _engine.DYN_PENALTY:
+            raise ValueError(f"unknown uncertainty_mode {uncertainty_mode!r}")
+        self.scaler = scaler
+        self.terminal_fn = terminal_fn
+        self._penalty_coef = penalty_coef
+        self._uncertainty_mode = uncertainty_mode
+        self._n_runs, self._seed = 1, 0
+        self._eng: Optional[_engine.Dynamics] = None
+        self._arena = None
+        self._shape = None             # (batch_size, logvar_loss_coef) the engine was built for
+        self._cur_run = 0
+        self.scalers: List[StandardScaler] = [scaler]
+        self._data_key = None
+
+    # ---- engine binding ----
+    def set_engine_options(self, n_runs: int = 1, seed: Optional[int] = None) -> None:
+        if self._eng is not None:
+            raise RuntimeError("set_engine_options before the first train() / step()")
+        self._n_runs = int(n_runs)
+        self._seed = int(seed) if seed is not None else 0
+        self.scalers = [self.scaler] + [StandardScaler(self.scaler.mu, self.scaler.std) for _ in range(self._n_runs - 1)]
+
+    def _device(self) -> torch.device:
+        dev = self.model.device
+        if dev.type != "cuda":
+            if not torch.cuda.is_available():
+                raise RuntimeError("the dynamics ensemble runs on the HIP engine: no HIP device (MI355X) visible")
+            dev = torch.device("cuda", 0)
+        return torch.device("cuda", dev.index or 0)
+
+    def _bind(self, batch_size: int = 256, logvar_loss_coef: float = 0.01) -> None:
+        shape = (int(batch_size), float(logvar_loss_coef))
+        if self._eng is not None and self._shape == shape:
+            return
+        carried = None
+        if self._eng is not None:
+            carried = [(self._eng.get_params(r), self._eng.adam_state(r), self._eng.get_elites(r)) for r in range(self._n_runs)]
+            self._unbind()
+        dev = self._device()
+        m = self.model
+        g = self.optim.param_groups[0] if self.optim is not None else {"lr": 1e-3, "betas": (0.9, 0.999), "eps": 1e-8}
+        if self.optim is not None and g.get("weight_decay", 0.0):
+            raise NotImplementedError("the dynamics optimizer's own weight_decay is not supported (the model's weight_decays are)")
+        cfg = _engine.default_dyn_config(obs_dim=m.obs_dim, act_dim=m.action_dim, hidden=m.hidden_dims, num_ensemble=m.num_ensemble,
+                                         num_elites=m.num_elites, with_reward=int(bool(m._with_reward)), weight_decay=m.weight_decays,
+                                         lr=float(g["lr"]), adam_beta1=float(g["betas"][0]), adam_beta2=float(g["betas"][1]),
+                                         adam_eps=float(g["eps"]), batch_size=shape[0], logvar_loss_coef=shape[1],
+                                         n_runs=self._n_runs, device=dev.index, precision=0, seed=self._seed)
+        P = int(_engine.load_library().orl_dyn_config_floats(cfg))
+        self._arena = torch.zeros(self._n_runs * P, dtype=torch.float32, device=dev)
+        cfg.external_arena = self._arena.data_ptr()
+        torch.cuda.synchronize(dev)
+        self._eng = _engine.Dynamics(cfg)
+        self._shape = shape
+        m.to(dev)
+        m.device = dev
+        for r in range(self._n_runs):
+            if carried is not None:
+                params, (am, av, t), el = carried[r]
+                self._eng.set_params(r, params)
+                self._eng.set_adam_state(r, am, av, t)
+                self._eng.set_elites(r, el)
+                continue
+            src = dict(m.named_parameters()) if r == 0 else _fresh_model_params(m, self._seed + r)
+            self._eng.set_params(r, {k: v.detach().cpu().numpy() for k, v in src.items() if k != "elites"})
+            self._eng.set_elites(r, src["elites"].detach().cpu().numpy())
+        self._cur_run = -1
+        self.select_run(0)
+        self._data_key = None
+
+    def _unbind(self) -> None:
+        if self._eng is None:
+            return
+        self._eng.sync()
+        for p in self.model.parameters():
+            p.data = p.data.clone()
+        self._eng.close()
+        self._eng, self._arena, self._shape = None, None, None
+
+    def _views(self, run: int):
+        off0 = (self._eng.ptr(run) - self._arena.data_ptr()) // 4
+        for name, off, shape in self._eng.tensors:
+            n = int(np.prod(shape))
+            yield name, self._arena[off0 + off: off0 + off + n].view(shape)
+
+    def select_run(self, run: int) -> None:
+        """point the torch module (forward, state_dict, save) and ``self.scaler`` at run ``run``"""
+        if self._eng is None:
+            if run != 0:
+                raise RuntimeError("select_run before the engine exists: only run 0")
+            return
+        if run == self._cur_run:
+            return
+        params = dict(self.model.named_parameters())
+        for name, view in self._views(run):
+            params[name].data = view
+        self.model.set_elites([int(i) for i in self._eng.get_elites(run)])
+        self.scaler = self.scalers[run]
+        self._cur_run = run
+
+    def _sync_torch(self) -> None:
+        torch.cuda.synchronize(self._arena.device)
+
+    def _push_elites_from_model(self) -> None:
+        self._eng.set_elites(self._cur_run, self.model.elites.detach().cpu().numpy())
+
+    # ---- reference API ----
+    @torch.no_grad()
+    def step(self, obs: np.ndarray, action: np.ndarray, noise: Optional[np.ndarray] = None,
+             model_idxs: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Dict]:
+        """ensemble_dynamics.py:29-80.  obs (N, obs_dim) for the selected run, or (R, N, obs_dim) for every run.  ``noise``
+        (K, N, obs_dim + 1) / (R, K, N, obs_dim + 1) and ``model_idxs`` (N,) / (R, N) teacher-force the reference's draws; by default
+        they come from the device Philox stream."""
+        self._bind(*(self._shape or (256, 0.01)))
+        self._sync_torch()
+        self._push_elites_from_model()
+        obs = np.asarray(obs, dtype=np.float32)
+        action = np.asarray(action, dtype=np.float32)
+        batched = obs.ndim == 3
+        R = self._n_runs
+        if batched:
+            o, a, nz, mi = obs, action, noise, model_idxs
+        else:
+            o, a = np.broadcast_to(obs, (R,) + obs.shape), np.broadcast_to(action, (R,) + action.shape)
+            nz = None if noise is None else np.broadcast_to(noise, (R,) + np.shape(noise))
+            mi = None if model_idxs is None else np.broadcast_to(model_idxs, (R,) + np.shape(model_idxs))
+        for r in range(R):
+            sc = self.scalers[r]
+            if sc.mu is None:
+                raise RuntimeError("the scaler is not fitted: train() or load() the dynamics first")
+            self._eng.set_scaler(r, sc.mu, sc.std)
+        nxt, rew, raw, pen, midx = self._eng.step(o, a, nz, mi, self._uncertainty_mode, float(self._penalty_coef))
+        if not batched:
+            r = self._cur_run
+            nxt, rew, raw, pen, midx = nxt[r], rew[r], raw[r], pen[r], midx[r]
+        reward = rew[..., None]
+        terminal = self.terminal_fn(obs, action, nxt)
+        info = {"raw_reward": raw[..., None], "model_idxs": midx}
+        if self._penalty_coef:
+            info["penalty"] = pen[..., None]
+        return nxt, reward if self._penalty_coef else raw[..., None], terminal, info
+
+    def sample_next_obss(self, obs, action, num_samples: int):
+        raise NotImplementedError("sample_next_obss is used by MOBILE only, which this package does not implement")
+
+    def format_samples_for_training(self, data: Dict) -> Tuple[np.ndarray, np.ndarray]:
+        obss = data["observations"]
+        actions = data["actions"]
+        next_obss = data["next_observations"]
+        rewards = data["rewards"]
+        delta_obss = next_obss - obss
+        inputs = np.concatenate((obss, actions), axis=-1)
+        targets = np.concatenate((delta_obss, rewards), axis=-1)
+        return inputs, targets
+
+    def _load(self, inputs: np.ndarray, targets: np.ndarray, key) -> None:
+        if self._data_key is not key:
+            self._eng.load_data(inputs, targets)
+            self._data_key = key
+
+    def train(self, data: Dict, logger, max_epochs: Optional[float] = None, max_epochs_since_update: int = 5, batch_size: int = 256,
+              holdout_ratio: float = 0.2, logvar_loss_coef: float = 0.01) -> None:
+        """ensemble_dynamics.py:111-176 with the arithmetic on the device; returns nothing, like the reference"""
+        self._bind(batch_size, logvar_loss_coef)
+        self._sync_torch()
+        inputs, targets = self.format_samples_for_training(data)
+        inputs, targets = np.asarray(inputs, np.float32), np.asarray(targets, np.float32)
+        trace = self.train_trace = {"train_idx": [], "holdout_idx": [], "data_idxes": [], "train_loss": [], "holdout_loss": []}
+        R, K = self._n_runs, self.model.num_ensemble
+        data_size = inputs.shape[0]
+        holdout_size = min(int(data_size * holdout_ratio), 1000)
+        train_size = data_size - holdout_size
+        train_idx, hold_idx, data_idxes = [], [], []
+        for r in range(R):
+            tr, ho = torch.utils.data.random_split(range(data_size), (train_size, holdout_size))
+            tr, ho = np.asarray(tr.indices, np.int64), np.asarray(ho.indices, np.int64)
+            self.scalers[r].fit(inputs[tr])
+            train_idx.append(tr); hold_idx.append(ho)
+            data_idxes.append(np.random.randint(train_size, size=[K, train_size]))
+        self.scaler = self.scalers[self._cur_run]
+        trace["train_idx"], trace["holdout_idx"] = train_idx, hold_idx
+        self._eng.load_data(inputs, targets)
+        self._data_key = None
+        for r in range(R):
+            self._eng.set_scaler(r, self.scalers[r].mu, self.scalers[r].std)
+        hold = np.stack(hold_idx)
+        holdout_losses = [[1e10] * K for _ in range(R)]
+        cnt = [0] * R
+        active = np.ones(R, np.int32)
+        epoch = 0
+        logger.log("Training dynamics:")
+        while active.any():
+            epoch += 1
+            trace["data_idxes"].append([d.copy() for d in data_idxes])
+            rows = np.stack([train_idx[r][data_idxes[r]] for r in range(R)])
+            train_loss = self._eng.learn_epoch(rows, active)
+            new_losses = self._eng.validate(hold)
+            trace["train_loss"].append(train_loss.copy()); trace["holdout_loss"].append(new_losses.copy())
+            r0 = self._cur_run
+            if active[r0]:
+                logger.logkv("loss/dynamics_train_loss", float(train_loss[r0]))
+                logger.logkv("loss/dynamics_holdout_loss", float(np.sort(new_losses[r0])[:self.model.num_elites].mean()))
+                logger.set_timestep(epoch)
+                logger.dumpkvs(exclude=["policy_training_progress"])
+            for r in range(R):
+                if not active[r]:
+                    continue
+                idxes = np.argsort(np.random.uniform(size=data_idxes[r].shape), axis=-1)
+                data_idxes[r] = data_idxes[r][np.arange(K)[:, None], idxes]
+                indexes = []
+                for i in range(K):
+                    new_loss, old_loss = float(new_losses[r][i]), holdout_losses[r][i]
+                    if (old_loss - new_loss) / old_loss > 0.01:
+                        indexes.append(i)
+                        holdout_losses[r][i] = new_loss
+                if indexes:
+                    mask = np.zeros(K, np.int32)
+                    mask[indexes] = 1
+                    self._eng.update_save(r, mask)
+                    cnt[r] = 0
+                else:
+                    cnt[r] += 1
+                if cnt[r] >= max_epochs_since_update or (max_epochs and epoch >= max_epochs):
+                    active[r] = 0
+                    trace.setdefault("stop_epoch", [0] * R)[r] = epoch
+        self._eng.sync()
+        trace["elites"] = []
+        for r in range(R):
+            el = self.select_elites(holdout_losses[r])
+            self._eng.set_elites(r, el)
+            self._eng.load_save(r)
+            trace["elites"].append(el)
+        self._eng.sync()
+        cur, self._cur_run = self._cur_run, -1
+        self.select_run(cur)
+        self.save(logger.model_dir)
+        self.model.eval()
+        logger.log("elites:{} , holdout loss: {}".format(trace["elites"][cur], (np.sort(holdout_losses[cur])[:self.model.num_elites]).mean()))
+
+    def learn(self, inputs: np.ndarray, targets: np.ndarray, batch_size: int = 256, logvar_loss_coef: float = 0.01) -> float:
+        """ensemble_dynamics.py:178-209 on already-scaled [K, n, ...] arrays (every run learns them); returns the selected run's loss"""
+        self._bind(batch_size, logvar_loss_coef)
+        self._sync_torch()
+        K, n = inputs.shape[0], inputs.shape[1]
+        self._eng.load_data(np.asarray(inputs, np.float32).reshape(K * n, -1), np.asarray(targets, np.float32).reshape(K * n, -1))
+        self._data_key = None
+        for r in range(self._n_runs):
+            self._eng.set_scaler(r, np.zeros(inputs.shape[-1], np.float32), np.ones(inputs.shape[-1], np.float32))
+        rows = np.broadcast_to((np.arange(K)[:, None] * n + np.arange(n)[None, :])[None], (self._n_runs, K, n))
+        return float(self._eng.learn_epoch(rows)[self._cur_run])
+
+    @torch.no_grad()
+    def validate(self, inputs: np.ndarray, targets: np.ndarray) -> List[float]:
+        """ensemble_dynamics.py:211-217 on already-scaled (n, ...) arrays; the selected run's per-member MSE"""
+        self._bind(*(self._shape or (256, 0.01)))
+        self._sync_torch()
+        n = inputs.shape[0]
+        self._eng.load_data(np.asarray(inputs, np.float32), np.asarray(targets, np.float32))
+        self._data_key = None
+        for r in range(self._n_runs):
+            self._eng.set_scaler(r, np.zeros(inputs.shape[-1], np.float32), np.ones(inputs.shape[-1], np.float32))
+        out = self._eng.validate(np.broadcast_to(np.arange(n)[None], (self._n_runs, n)))
+        return list(out[self._cur_run])
+
+    def select_elites(self, metrics: List) -> List[int]:
+        pairs = [(metric, index) for metric, index in zip(metrics, range(len(metrics)))]
+        pairs = sorted(pairs, key=lambda x: x[0])
+        return [pairs[i][1] for i in range(self.model.num_elites)]
+
+    def save(self, save_path: str) -> None:
+        if self._eng is not None:
+            self._eng.sync()
+        sd = self.model.state_dict()
+        torch.save(type(sd)((k, v.detach().clone()) for k, v in sd.items()), os.path.join(save_path, "dynamics.pth"))
+        self.scaler.save_scaler(save_path)
+
+    def load(self, load_path: str) -> None:
+        if self._eng is not None:
+            self._sync_torch()
+        state = torch.load(os.path.join(load_path, "dynamics.pth"), map_location=self.model.device)
+        if "elites" in state and tuple(state["elites"].shape) != tuple(self.model.elites.shape):
+            self.model.set_elites([int(i) for i in state["elites"]])
+        self.model.load_state_dict(state)
+        self.scaler.load_scaler(load_path)
+        self.scalers[self._cur_run] = self.scaler
+        if self._eng is not None:
+            torch.cuda.synchronize(self._arena.device)
+            self._push_elites_from_model()

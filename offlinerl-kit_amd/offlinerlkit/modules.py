@@ -169,3 +169,86 @@ class EnsembleCritic(nn.Module):
         if actions is not None:
             x = torch.cat([x, _as_input(actions, self.device)], dim=-1)
         return self.model(x)
+
+
+# ---- dynamics ensemble (reference: modules/dynamics_module.py:9-119) ----
+
+class Swish(nn.Module):
+    """x * sigmoid(x) (dynamics_module.py:9-16)"""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return x * torch.sigmoid(x)
+
+
+def soft_clamp(x: torch.Tensor, _min: Optional[torch.Tensor] = None, _max: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """clamp keeping a gradient (dynamics_module.py:19-29): max - softplus(max - x), then min + softplus(x - min)"""
+    if _max is not None:
+        x = _max - torch.nn.functional.softplus(_max - x)
+    if _min is not None:
+        x = _min + torch.nn.functional.softplus(x - _min)
+    return x
+
+
+class EnsembleDynamicsModel(nn.Module):
+    """Probabilistic ensemble of ``num_ensemble`` Swish MLPs (dynamics_module.py:32-119); the output layer gives [mean | logvar] of
+    (delta obs, reward).  Same parameter registration order (state_dict keys) and, under the same torch seed, the same initial
+    parameters as the reference.  Training runs in the HIP engine (``offlinerlkit.dynamics.EnsembleDynamics``), which re-points these
+    parameters at its arena; ``forward`` stays a torch function for evaluation."""
+
+    def __init__(self, obs_dim: int, action_dim: int, hidden_dims: Sequence[int], num_ensemble: int = 7, num_elites: int = 5,
+                 activation=Swish, weight_decays: Optional[Sequence[float]] = None, with_reward: bool = True,
+                 device: str = "cpu") -> None:
+        super().__init__()
+        self.num_ensemble = num_ensemble
+        self.num_elites = num_elites
+        self._with_reward = with_reward
+        self.device = torch.device(device)
+        if activation is not Swish:
+            raise NotImplementedError("the engine's dynamics kernels implement the Swish activation only")
+        self.activation = activation()
+        if weight_decays is None:
+            weight_decays = [0.0] * (len(hidden_dims) + 1)
+        assert len(weight_decays) == (len(hidden_dims) + 1)
+        self.obs_dim, self.action_dim = int(obs_dim), int(action_dim)
+        self.hidden_dims = [int(h) for h in hidden_dims]
+        self.weight_decays = [float(w) for w in weight_decays]
+        dims = [obs_dim + action_dim] + list(hidden_dims)
+        self.backbones = nn.ModuleList([EnsembleLinear(i, o, num_ensemble, w) for i, o, w in zip(dims[:-1], dims[1:], weight_decays[:-1])])
+        self.output_layer = EnsembleLinear(dims[-1], 2 * (obs_dim + self._with_reward), num_ensemble, weight_decays[-1])
+        self.register_parameter("max_logvar", nn.Parameter(torch.ones(obs_dim + self._with_reward) * 0.5, requires_grad=True))
+        self.register_parameter("min_logvar", nn.Parameter(torch.ones(obs_dim + self._with_reward) * -10, requires_grad=True))
+        self.register_parameter("elites", nn.Parameter(torch.tensor(list(range(0, self.num_elites))), requires_grad=False))
+        self.to(self.device)
+
+    def forward(self, obs_action):
+        obs_action = torch.as_tensor(obs_action, dtype=torch.float32).to(self.device)
+        output = obs_action
+        for layer in self.backbones:
+            output = self.activation(layer(output))
+        mean, logvar = torch.chunk(self.output_layer(output), 2, dim=-1)
+        logvar = soft_clamp(logvar, self.min_logvar, self.max_logvar)
+        return mean, logvar
+
+    def load_save(self) -> None:
+        for layer in self.backbones:
+            layer.load_save()
+        self.output_layer.load_save()
+
+    def update_save(self, indexes) -> None:
+        for layer in self.backbones:
+            layer.update_save(indexes)
+        self.output_layer.update_save(indexes)
+
+    def get_decay_loss(self) -> torch.Tensor:
+        decay_loss = 0
+        for layer in self.backbones:
+            decay_loss += layer.get_decay_loss()
+        decay_loss += self.output_layer.get_decay_loss()
+        return decay_loss
+
+    def set_elites(self, indexes) -> None:
+        assert len(indexes) <= self.num_ensemble and max(indexes) < self.num_ensemble
+        self.register_parameter("elites", nn.Parameter(torch.tensor(list(indexes), device=self.device), requires_grad=False))
+
+    def random_elite_idxs(self, batch_size: int) -> np.ndarray:
+        return np.random.choice(self.elites.data.cpu().numpy(), size=batch_size)
