@@ -2,9 +2,10 @@
 policy/model_based/combo.py:12-241) on the HIP engine.
 
 ``MOPOPolicy.learn`` and ``COMBOPolicy.learn`` take ``{"real": batch, "fake": batch}``, concatenate real rows first and run the SAC /
-CQL-variant update of the engine on the mixed batch.  The dynamics model itself (ensembles, penalties, ``MBPolicyTrainer``) stays out
-of scope: ``rollout`` only needs an object with ``step(obs, act) -> (next_obs, reward, terminal, info)``.  These policies are
-host-fed (``learn``): the fused device-sampling loop ``learn_n`` draws from ONE replay buffer and does not apply to a real + model pair.
+CQL-variant update of the engine on the mixed batch.  ``rollout`` needs an object with ``step(obs, act) -> (next_obs, reward, terminal,
+info)``: ``offlinerlkit.dynamics.EnsembleDynamics`` with a function of ``utils.termination_fns``.  ``policy_trainer.MBPolicyTrainer`` runs
+the reference's loop around them.  These policies are host-fed (``learn``): the fused device-sampling loop ``learn_n`` draws from ONE
+replay buffer and does not apply to a real + model pair.
 """
 from __future__ import annotations
 

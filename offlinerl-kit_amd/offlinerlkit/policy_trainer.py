@@ -1,4 +1,5 @@
-"""MFPolicyTrainer (reference: offlinerlkit/policy_trainer/mf_policy_trainer.py:17-118).
+"""MFPolicyTrainer (reference: offlinerlkit/policy_trainer/mf_policy_trainer.py:17-118) and MBPolicyTrainer (reference:
+offlinerlkit/policy_trainer/mb_policy_trainer.py:17-198).
 
 Same constructor, same logged keys, same per-epoch order (train steps -> lr_scheduler.step -> evaluate -> log ->
 checkpoint) and the same return value.  Two inner loops:
@@ -16,13 +17,18 @@ run is evaluated, logged as ``run<i>/<key>`` (plain keys = mean over runs) and c
 Multi-GPU: independent runs, one process per GPU (replicas only).  When ``torch.distributed`` is initialised the
 per-epoch metric vector of every rank is all-gathered (RCCL over xGMI on GPUs, gloo on CPU) so rank 0 can log
 all runs; no other collective exists on this path.
+
+MBPolicyTrainer is the reference's model-based loop (MOPO / COMBO): per step, a rollout every ``rollout_freq`` timesteps
+(``policy.rollout`` from a ``real_buffer.sample`` of initial states, appended to ``fake_buffer``), then a real and a model minibatch
+split by ``real_ratio`` and one ``policy.learn({"real": ..., "fake": ...})``.  The draw order, logged keys, checkpoints and the final
+``dynamics.save`` are the reference's; evaluation, the multi-run ``run<i>/...`` keys and the per-run checkpoints are MFPolicyTrainer's.
 """
 from __future__ import annotations
 
 import os
 import time
 from collections import deque
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -246,5 +252,160 @@ class MFPolicyTrainer:
                         obs[i] = envs[i].reset()
                     else:
                         active[i] = False
+        return {"eval/episode_reward": [d["episode_reward"] for d in done_eps],
+                "eval/episode_length": [d["episode_length"] for d in done_eps]}
+
+
+def _host(x) -> np.ndarray:
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+class MBPolicyTrainer(MFPolicyTrainer):
+    """Constructor = mb_policy_trainer.py:18-55.  ``rollout_setting`` = (rollout_freq, rollout_batch_size, rollout_length)."""
+
+    def __init__(self, policy, eval_env, real_buffer, fake_buffer, logger, rollout_setting: Tuple[int, int, int], epoch: int = 1000,
+                 step_per_epoch: int = 1000, batch_size: int = 256, real_ratio: float = 0.05, eval_episodes: int = 10,
+                 lr_scheduler=None, dynamics_update_freq: int = 0, horizon: Optional[int] = None, progress: bool = False) -> None:
+        super().__init__(policy, eval_env, real_buffer, logger, epoch=epoch, step_per_epoch=step_per_epoch, batch_size=batch_size,
+                         eval_episodes=eval_episodes, lr_scheduler=lr_scheduler, fused=False, progress=progress)
+        self.real_buffer = real_buffer
+        self.fake_buffer = fake_buffer
+        self.horizon = horizon
+        self._rollout_freq, self._rollout_batch_size, self._rollout_length = rollout_setting
+        self._dynamics_update_freq = dynamics_update_freq
+        self._real_ratio = real_ratio
+        self.is_gymnasium_env = hasattr(self._score_env(), "get_true_observation")
+        assert (not self.is_gymnasium_env) or (self.horizon is not None), "Horizon must be specified for Gymnasium env"
+
+    # ---- the reference's inner loop (mb_policy_trainer.py:66-102) -----------------------------------------
+    def _rollout(self) -> None:
+        init_obss = _host(self.real_buffer.sample(self._rollout_batch_size)["observations"])
+        rollout_transitions, rollout_info = self.policy.rollout(init_obss, self._rollout_length)
+        self.fake_buffer.add_batch(**rollout_transitions)
+        self.logger.log("num rollout transitions: {}, reward mean: {:.4f}".format(rollout_info["num_transitions"], rollout_info["reward_mean"]))
+        for k, v in rollout_info.items():
+            self.logger.logkv_mean("rollout_info/" + k, v)
+
+    def _train_mb_epoch(self, e: int, num_timesteps: int) -> int:
+        it = range(self._step_per_epoch)
+        if self._progress:
+            from tqdm import tqdm
+            it = tqdm(it, desc=f"Epoch #{e}/{self._epoch}")
+        for _ in it:
+            if num_timesteps % self._rollout_freq == 0:
+                self._rollout()
+            real_sample_size = int(self._batch_size * self._real_ratio)
+            fake_sample_size = self._batch_size - real_sample_size
+            real_batch = self.real_buffer.sample(batch_size=real_sample_size)
+            fake_batch = self.fake_buffer.sample(batch_size=fake_sample_size)
+            loss = self.policy.learn({"real": real_batch, "fake": fake_batch})
+            if self._progress:
+                it.set_postfix(**loss)
+            for k, v in loss.items():
+                self.logger.logkv_mean(k, v)
+            if 0 < self._dynamics_update_freq and (num_timesteps + 1) % self._dynamics_update_freq == 0:
+                for k, v in self.policy.update_dynamics(self.real_buffer).items():
+                    self.logger.logkv_mean(k, v)
+            num_timesteps += 1
+        self._check_health()
+        return num_timesteps
+
+    # ---- reference API ---------------------------------------------------------------------
+    def train(self) -> Dict[str, float]:
+        start_time = time.time()
+        num_timesteps = 0
+        last_10_performance = deque(maxlen=10)
+        n_runs = int(getattr(self.policy, "n_runs", 1))
+        for e in range(1, self._epoch + 1):
+            self.policy.train()
+            num_timesteps = self._train_mb_epoch(e, num_timesteps)
+            if self.lr_scheduler is not None:
+                self.lr_scheduler.step()
+            if n_runs == 1:
+                eval_info = self._evaluate()
+            else:
+                grouped = self._env_groups(n_runs) if self.horizon is None and not self.is_gymnasium_env else None
+                per_run_all = self._evaluate_runs_batched(grouped) if grouped is not None else None
+                per_run = []
+                for r in range(n_runs):
+                    if per_run_all is not None:
+                        per_run.append(per_run_all[r])
+                    else:
+                        self.policy.select_run(r)
+                        per_run.append(self._evaluate())
+                    self._log_eval(per_run[-1], f"run{r}/", None)
+                self.policy.select_run(0)
+                eval_info = {k: [x for info in per_run for x in info[k]] for k in per_run[0]}      # pooled over runs
+            self._log_eval(eval_info, "", last_10_performance)
+            self.logger.set_timestep(num_timesteps)
+            self.logger.dumpkvs(exclude=["dynamics_training_progress"])
+            self._checkpoint(self.logger.checkpoint_dir, n_runs)
+        self.logger.log("total time: {:.2f}s".format(time.time() - start_time))
+        self._checkpoint(self.logger.model_dir, n_runs)
+        self.policy.dynamics.save(self.logger.model_dir)
+        self.logger.close()
+        return {"last_10_performance": np.mean(last_10_performance)}
+
+    def _log_eval(self, eval_info: Dict[str, List[float]], prefix: str, last_10: Optional[deque]) -> None:
+        """mb_policy_trainer.py:108-121: gymnasium envs log the raw return, the others the normalised one (never both)"""
+        ep_reward_mean, ep_reward_std = np.mean(eval_info["eval/episode_reward"]), np.std(eval_info["eval/episode_reward"])
+        ep_length_mean, ep_length_std = np.mean(eval_info["eval/episode_length"]), np.std(eval_info["eval/episode_length"])
+        if self.is_gymnasium_env:
+            if last_10 is not None:
+                last_10.append(ep_reward_mean)
+            self.logger.logkv(prefix + "eval/episode_reward", ep_reward_mean)
+            self.logger.logkv(prefix + "eval/episode_reward_std", ep_reward_std)
+        else:
+            env = self._score_env()
+            norm_ep_rew_mean = env.get_normalized_score(ep_reward_mean) * 100
+            norm_ep_rew_std = env.get_normalized_score(ep_reward_std) * 100
+            if last_10 is not None:
+                last_10.append(norm_ep_rew_mean)
+            self.logger.logkv(prefix + "eval/normalized_episode_reward", norm_ep_rew_mean)
+            self.logger.logkv(prefix + "eval/normalized_episode_reward_std", norm_ep_rew_std)
+        self.logger.logkv(prefix + "eval/episode_length", ep_length_mean)
+        self.logger.logkv(prefix + "eval/episode_length_std", ep_length_std)
+
+    def _evaluate(self) -> Dict[str, List[float]]:
+        """mb_policy_trainer.py:131-198: a fixed ``horizon`` per episode (terminals ignored) and gymnasium envs on one env; without
+        either, MFPolicyTrainer's evaluation (the same episode loop, or lockstep envs for a list)"""
+        if self.horizon is None and not self.is_gymnasium_env:
+            return super()._evaluate()
+        env = self.eval_env
+        gym_api = self.is_gymnasium_env
+        self.policy.eval()
+
+        def reset():
+            if gym_api:
+                o, _ = env.reset()
+                return env.get_true_observation(o)
+            return env.reset()
+
+        def step(o):
+            action = self.policy.select_action(o.reshape(1, -1), deterministic=True)
+            if gym_api:
+                nxt, reward, terminal, _, _ = env.step(action.flatten())
+                return env.get_true_observation(nxt), reward, terminal
+            nxt, reward, terminal, _ = env.step(action.flatten())
+            return nxt, reward, terminal
+
+        obs = reset()
+        done_eps: List[Dict[str, float]] = []
+        ep_reward, ep_len = 0, 0
+        while len(done_eps) < self._eval_episodes:
+            if self.horizon is not None:
+                for _ in range(self.horizon):
+                    obs, reward, _ = step(obs)
+                    ep_reward += reward
+                    ep_len += 1
+                finished = True
+            else:
+                obs, reward, finished = step(obs)
+                ep_reward += reward
+                ep_len += 1
+            if finished:
+                done_eps.append({"episode_reward": ep_reward, "episode_length": ep_len})
+                ep_reward, ep_len = 0, 0
+                obs = reset()
         return {"eval/episode_reward": [d["episode_reward"] for d in done_eps],
                 "eval/episode_length": [d["episode_length"] for d in done_eps]}
