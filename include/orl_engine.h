@@ -233,6 +233,36 @@ int orl_buffer_sample(orl_buffer* b, const int64_t* idx, int32_t batch, uint64_t
                       float* next_obs_out, float* rew_out, float* term_out);
 /* lets orl_learn_n sample this buffer on the device (the buffer must outlive the engine's use of it) */
 int orl_engine_attach_buffer(orl_engine* e, orl_buffer* b);
+/* -- growable ring: the model-rollout buffer of MOPO / COMBO kept in HBM ------------------------------------------------------
+ * ReplayBuffer.__init__ (buffer/buffer.py:8-32): `capacity` rows allocated once, size 0, write position 0.  The device arrays do not
+ * move until the next reserve / load.  The current size also lives in a device cell, which the samplers of orl_learn_n read for the
+ * model source: a captured graph stays valid while the ring grows. */
+int orl_buffer_reserve(orl_buffer* b, int64_t capacity);
+/* add_batch (buffer/buffer.py:52-70): rows land at (ptr + i) % capacity, ptr = (ptr + n) % capacity, size = min(size + n, capacity).
+ * Packed arrays obs/next_obs [n][obs_dim], act [n][act_dim], rew/term [n]; host pointers, device pointers when on_device.
+ * n > capacity is refused.  On return the rows are visible to every stream of the process. */
+int orl_buffer_append(orl_buffer* b, const float* obs, const float* act, const float* next_obs, const float* rew, const float* term,
+                      int64_t n, int on_device);
+/* the loop body of rollout() (policy/model_based/mopo.py:45-79, combo.py:67-108) for one model step; every array pointer is a DEVICE pointer to a
+ * packed array.  Evaluates the termination test `term_kind` (0 never done, 1 halfcheetah, 2 hopper, 3 walker2d, 4 ant / antangle,
+ * 5 humanoid, 6 pen: utils/termination_fns.py of the reference, its NaN behaviour and hopper's upper-bound-only check included) on
+ * next_obs, appends all n transitions with terminals = the test's result (0 / 1), writes the next_obs rows of the transitions that
+ * did NOT terminate densely and in their original order to alive_next_obs (room for n rows, not overlapping next_obs), and returns
+ * their count and the float64 sum of rew through the two HOST pointers.  A kind that reads an observation column the buffer does not
+ * have (pen: column 26; hopper / walker2d: column 1) is refused.
+ * Health: rollouts are not range-checked when they are appended (the precision-1 dataset check of orl_engine_attach_buffer is a
+ * one-off over a fixed dataset); a model row beyond the operand range shows in the sticky ORL_HEALTH_* flags and the operand scan of
+ * orl_health_check like any other operand. */
+int orl_buffer_append_rollout(orl_buffer* b, int32_t term_kind, const float* obs, const float* act, const float* next_obs,
+                              const float* rew, int64_t n, float* alive_next_obs, int64_t* n_alive, double* rew_sum);
+/* rows [row0, row0 + n) of the store back to packed host arrays (sample_all, buffer/buffer.py:108-115, and tests); a ring may be read
+ * up to its capacity (rows never written are zero) */
+int orl_buffer_read(orl_buffer* b, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term);
+/* the real + model batch of MBPolicyTrainer (policy_trainer/mb_policy_trainer.py:78-85; _cat of mopo.py:81-84, combo.py:111-113) inside
+ * orl_learn_n: batch rows [0, real_rows) are drawn from the buffer of orl_engine_attach_buffer, rows [real_rows, batch_size) from the
+ * ring `model`; every row keeps its Philox counter.  0 < real_rows < batch_size, same dims and device as the engine; NULL detaches.
+ * orl_learn_n fails while the ring is empty and, for CQL engines, when real_rows differs from cql_real_rows. */
+int orl_engine_attach_model_buffer(orl_engine* e, orl_buffer* model, int32_t real_rows);
 
 /* -- the hot path ---------------------------------------------------------------- */
 /* policy.learn(batch) with explicit noise: one gradient step for every run.

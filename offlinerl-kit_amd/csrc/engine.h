@@ -93,7 +93,13 @@ struct Buffer {             // HBM-resident replay buffer (buffer/buffer.py)
   long long* idx = nullptr; long idx_cap = 0;
   unsigned long long counter = 0;
   float absmax = -1.f; unsigned long long absmax_gen = ~0ull;   // max |obs|, |next_obs|, |act| of generation absmax_gen (engines at precision 1 ask for it)
-  unsigned long long gen = 0;   // bumped by every orl_buffer_load: engines re-capture graphs that hold the old dataset pointers / size
+  unsigned long long gen = 0;   // bumped by every orl_buffer_load / orl_buffer_reserve: engines re-capture graphs that hold the old dataset pointers / size
+  // growable ring (orl_buffer_reserve): `cap` rows allocated once, rows land at (ptr + i) % cap, n = min(n + i, cap) as in add_batch
+  // (buffer.py:52-70).  d_n mirrors n in a device cell: kernels that sample the ring as the MODEL source read the size from it, so a
+  // captured graph stays valid while the ring grows.
+  long cap = 0, ptr = 0;
+  long long* d_n = nullptr;
+  int* roll_alive = nullptr; double* roll_rew = nullptr; long roll_blocks = 0;   // per-block scratch of k_roll_term / k_roll_scatter, then 2 result cells
   ~Buffer();
 };
 
@@ -140,6 +146,10 @@ struct Engine {
   Buffer* buf = nullptr;       // attached replay buffer (not owned)
   long long* d_idx = nullptr;  // [R][B] minibatch indices of the current step (recorded by k_prepare's rewards job)
   unsigned long long buf_gen = 0;   // Buffer::gen the captured graphs were built against
+  long buf_n = 0;                   // Buffer::n they were built against (a ring attached as the primary source grows)
+  Buffer* mbuf = nullptr;      // model-rollout ring (orl_engine_attach_model_buffer, not owned): batch rows [mbuf_real_rows, B) are drawn from it
+  int mbuf_real_rows = 0;
+  unsigned long long mbuf_gen = 0;
   void drop_graphs();
   // split-K slab table of the last adam() launch per net (orl_debug_grads sums the slabs the way k_adam does)
   std::vector<std::pair<long, int>> last_segs[ORL_NUM_NETS];

@@ -193,6 +193,9 @@ Buffer::~Buffer() {
   hipSetDevice(dev);
   for (float* p : {obs, nobs, act, rew, term}) if (p) hipFree(p);
   if (idx) hipFree(idx);
+  if (d_n) hipFree(d_n);
+  if (roll_alive) hipFree(roll_alive);
+  if (roll_rew) hipFree(roll_rew);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1288,6 +1291,10 @@ int Engine::enqueue_sample() {
   g.b_act = W("b_act").p; g.act_rs = W("b_act").rs; g.d_ap = AP;
   g.b_rew = W("b_rew").p; g.rew_rs = W("b_rew").rs; g.b_term = W("b_term").p; g.term_rs = W("b_term").rs;
   g.seed = cfg.seed; g.gstep = gstep;
+  if (mbuf) {
+    g.m_obs = mbuf->obs; g.m_nobs = mbuf->nobs; g.m_act = mbuf->act; g.m_rew = mbuf->rew; g.m_term = mbuf->term;
+    g.m_n = mbuf->d_n; g.real_rows = mbuf_real_rows;
+  }
   ORL_LAUNCH("gather", k_gather, dim3((unsigned)(((long)B * g.W + 255) / 256), R), dim3(256), g);
   return 0;
 }
@@ -1344,6 +1351,10 @@ int Engine::enqueue_prepare(bool sampling, bool devnoise) {
     // the minibatch indices (np.random.randint(0, size, B), buffer.py:98) are drawn inside k_prepare by every consumer of a batch row
     // (same Philox counter -> same index) and recorded once in d_idx: no separate index-drawing node in front of the step
     p.idx = d_idx; p.idx_rs = B; p.draw = 1; p.idx_out = d_idx;
+    if (mbuf) {
+      p.m_obs = mbuf->obs; p.m_nobs = mbuf->nobs; p.m_act = mbuf->act; p.m_rew = mbuf->rew; p.m_term = mbuf->term;
+      p.m_n = mbuf->d_n; p.real_rows = mbuf_real_rows;
+    }
   }
   Mat o2 = W("b_obs2");
   p.b_obs = o2.p; p.b_nobs = o2.p + (long)B * OP; p.bo_rs = o2.rs; p.b_op = OP;
@@ -1588,13 +1599,123 @@ int orl_buffer_load(orl_buffer* h, const float* obs, const float* act, const flo
   if (upload_padded(&b.rew, rew, n, 1, 1)) return -1;
   if (upload_padded(&b.term, term, n, 1, 1)) return -1;
   b.n = n;
+  b.cap = 0; b.ptr = 0;  // (a loaded dataset is not a ring)
+  if (b.d_n) { const long long nn = n; ORL_HIP(hipMemcpy(b.d_n, &nn, sizeof(nn), hipMemcpyHostToDevice)); }
   b.gen++;               // the arrays moved: engines that captured them re-capture (orl_learn_n)
+  return 0;
+}
+
+// ---- growable ring ----
+static int ring_publish(Buffer& b) {
+  const long long nn = b.n;
+  ORL_HIP(hipMemcpy(b.d_n, &nn, sizeof(nn), hipMemcpyHostToDevice));
+  ORL_HIP(hipDeviceSynchronize());        // the appended rows and the new size are visible to every stream of the process
+  b.absmax_gen = ~0ull;
+  return 0;
+}
+int orl_buffer_reserve(orl_buffer* h, int64_t capacity) {
+  if (!h || capacity < 1) return fail("orl_buffer_reserve: bad arguments");
+  Buffer& b = h->b;
+  ORL_HIP(hipSetDevice(b.dev));
+  ORL_HIP(hipDeviceSynchronize());
+  for (float** p : {&b.obs, &b.nobs, &b.act, &b.rew, &b.term}) if (*p) { hipFree(*p); *p = nullptr; }
+  const long pitch[5] = {b.OP, b.OP, b.AP, 1, 1};
+  float** arr[5] = {&b.obs, &b.nobs, &b.act, &b.rew, &b.term};
+  for (int k = 0; k < 5; ++k) {
+    ORL_HIP(hipMalloc((void**)arr[k], sizeof(float) * capacity * pitch[k]));
+    ORL_HIP(hipMemset(*arr[k], 0, sizeof(float) * capacity * pitch[k]));
+  }
+  if (!b.d_n) ORL_HIP(hipMalloc((void**)&b.d_n, sizeof(long long)));
+  b.cap = capacity; b.ptr = 0; b.n = 0;
+  b.gen++;
+  return ring_publish(b);
+}
+// rows [0, n) of a packed source -> ring rows (ptr + i) % cap: at most two contiguous pieces
+static int ring_copy(float* dst, int pitch, const float* src, int dim, long cap, long ptr, long n, hipMemcpyKind kind) {
+  const long first = std::min(n, cap - ptr);
+  ORL_HIP(hipMemcpy2D(dst + ptr * pitch, sizeof(float) * pitch, src, sizeof(float) * dim, sizeof(float) * dim, first, kind));
+  if (n > first)
+    ORL_HIP(hipMemcpy2D(dst, sizeof(float) * pitch, src + first * dim, sizeof(float) * dim, sizeof(float) * dim, n - first, kind));
+  return 0;
+}
+int orl_buffer_append(orl_buffer* h, const float* obs, const float* act, const float* next_obs, const float* rew, const float* term,
+                      int64_t n, int on_device) {
+  if (!h || !obs || !act || !next_obs || !rew || !term || n < 1) return fail("orl_buffer_append: bad arguments");
+  Buffer& b = h->b;
+  if (b.cap < 1) return fail("orl_buffer_append: not a ring (orl_buffer_reserve first)");
+  if (n > b.cap) return fail("orl_buffer_append: more rows than the ring's capacity");
+  ORL_HIP(hipSetDevice(b.dev));
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (ring_copy(b.obs, b.OP, obs, b.od, b.cap, b.ptr, n, kind)) return -1;
+  if (ring_copy(b.nobs, b.OP, next_obs, b.od, b.cap, b.ptr, n, kind)) return -1;
+  if (ring_copy(b.act, b.AP, act, b.ad, b.cap, b.ptr, n, kind)) return -1;
+  if (ring_copy(b.rew, 1, rew, 1, b.cap, b.ptr, n, kind)) return -1;
+  if (ring_copy(b.term, 1, term, 1, b.cap, b.ptr, n, kind)) return -1;
+  b.ptr = (b.ptr + n) % b.cap;
+  b.n = std::min(b.n + (long)n, b.cap);
+  return ring_publish(b);
+}
+int orl_buffer_append_rollout(orl_buffer* h, int32_t term_kind, const float* obs, const float* act, const float* next_obs, const float* rew,
+                              int64_t n, float* alive_next_obs, int64_t* n_alive, double* rew_sum) {
+  if (!h || !obs || !act || !next_obs || !rew || !alive_next_obs || !n_alive || !rew_sum || n < 1) return fail("orl_buffer_append_rollout: bad arguments");
+  Buffer& b = h->b;
+  if (b.cap < 1) return fail("orl_buffer_append_rollout: not a ring (orl_buffer_reserve first)");
+  if (n > b.cap) return fail("orl_buffer_append_rollout: more rows than the ring's capacity");
+  if (term_kind < 0 || term_kind >= ORL_TERM_KINDS) return fail("orl_buffer_append_rollout: unknown termination kind");
+  const int need = term_kind == ORL_TERM_PEN ? 27 : ((term_kind == ORL_TERM_HOPPER || term_kind == ORL_TERM_WALKER2D) ? 2 : 1);
+  if (b.od < need) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "orl_buffer_append_rollout: termination kind %d reads observation column %d, the buffer has %d columns", (int)term_kind, need - 1, b.od);
+    return fail(msg);
+  }
+  if (alive_next_obs == next_obs) return fail("orl_buffer_append_rollout: alive_next_obs must not overlap next_obs");
+  ORL_HIP(hipSetDevice(b.dev));
+  const long blocks = (n + 255) / 256;
+  if (blocks > b.roll_blocks) {
+    if (b.roll_alive) hipFree(b.roll_alive);
+    if (b.roll_rew) hipFree(b.roll_rew);
+    b.roll_alive = nullptr; b.roll_rew = nullptr; b.roll_blocks = 0;
+    ORL_HIP(hipMalloc((void**)&b.roll_alive, sizeof(int) * blocks + sizeof(long long) * 2));
+    ORL_HIP(hipMalloc((void**)&b.roll_rew, sizeof(double) * (blocks + 1)));
+    b.roll_blocks = blocks;
+  }
+  RollP p;
+  memset(&p, 0, sizeof(p));
+  p.kind = term_kind; p.obs = obs; p.act = act; p.nobs = next_obs; p.rew = rew; p.n = n; p.od = b.od; p.ad = b.ad;
+  p.r_obs = b.obs; p.r_nobs = b.nobs; p.r_act = b.act; p.r_rew = b.rew; p.r_term = b.term; p.OP = b.OP; p.AP = b.AP; p.cap = b.cap; p.ptr = b.ptr;
+  p.alive_nobs = alive_next_obs;
+  p.blk_alive = b.roll_alive; p.blk_rew = b.roll_rew;
+  p.n_alive_out = (long long*)(b.roll_alive + ((b.roll_blocks + 1) & ~1L));      // 8-byte aligned, behind the block counts
+  p.rew_sum_out = b.roll_rew + b.roll_blocks;
+  hipLaunchKernelGGL(k_roll_term, dim3((unsigned)blocks), dim3(256), 0, 0, p);
+  hipLaunchKernelGGL(k_roll_scatter, dim3((unsigned)blocks), dim3(256), 0, 0, p);
+  ORL_HIP(hipGetLastError());
+  long long na = 0; double rs = 0.0;
+  ORL_HIP(hipMemcpy(&na, p.n_alive_out, sizeof(na), hipMemcpyDeviceToHost));
+  ORL_HIP(hipMemcpy(&rs, p.rew_sum_out, sizeof(rs), hipMemcpyDeviceToHost));
+  *n_alive = na; *rew_sum = rs;
+  b.ptr = (b.ptr + n) % b.cap;
+  b.n = std::min(b.n + (long)n, b.cap);
+  return ring_publish(b);
+}
+int orl_buffer_read(orl_buffer* h, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term) {
+  if (!h || n < 1 || row0 < 0 || !obs || !act || !next_obs || !rew || !term) return fail("orl_buffer_read: bad arguments");
+  Buffer& b = h->b;
+  const long rows = b.cap > 0 ? b.cap : b.n;
+  if (!b.obs || row0 + n > rows) return fail("orl_buffer_read: rows beyond the store");
+  ORL_HIP(hipSetDevice(b.dev));
+  ORL_HIP(hipDeviceSynchronize());
+  ORL_HIP(hipMemcpy2D(obs, sizeof(float) * b.od, b.obs + row0 * b.OP, sizeof(float) * b.OP, sizeof(float) * b.od, n, hipMemcpyDeviceToHost));
+  ORL_HIP(hipMemcpy2D(next_obs, sizeof(float) * b.od, b.nobs + row0 * b.OP, sizeof(float) * b.OP, sizeof(float) * b.od, n, hipMemcpyDeviceToHost));
+  ORL_HIP(hipMemcpy2D(act, sizeof(float) * b.ad, b.act + row0 * b.AP, sizeof(float) * b.AP, sizeof(float) * b.ad, n, hipMemcpyDeviceToHost));
+  ORL_HIP(hipMemcpy(rew, b.rew + row0, sizeof(float) * n, hipMemcpyDeviceToHost));
+  ORL_HIP(hipMemcpy(term, b.term + row0, sizeof(float) * n, hipMemcpyDeviceToHost));
   return 0;
 }
 int64_t orl_buffer_size(orl_buffer* h) { return h->b.n; }
 int orl_buffer_normalize_obs(orl_buffer* h, float eps, float* mean_out, float* std_out) {
   Buffer& b = h->b;
-  if (!b.obs) return fail("normalize_obs: empty buffer");
+  if (!b.obs || b.n < 1) return fail("normalize_obs: empty buffer");
   ORL_HIP(hipSetDevice(b.dev));
   double* sums = nullptr;
   ORL_HIP(hipMalloc((void**)&sums, sizeof(double) * 2 * b.od));
@@ -1628,7 +1749,7 @@ int orl_buffer_normalize_obs(orl_buffer* h, float eps, float* mean_out, float* s
 int orl_buffer_sample(orl_buffer* h, const int64_t* idx, int32_t batch, uint64_t seed, float* obs_out, float* act_out,
                       float* next_obs_out, float* rew_out, float* term_out) {
   Buffer& b = h->b;
-  if (!b.obs) return fail("sample: empty buffer");
+  if (!b.obs || b.n < 1) return fail("sample: empty buffer");
   if (batch < 1 || !obs_out || !act_out || !next_obs_out || !rew_out || !term_out) return fail("sample: bad arguments");
   ORL_HIP(hipSetDevice(b.dev));
   if (idx) {
@@ -1683,8 +1804,20 @@ int orl_engine_attach_buffer(orl_engine* h, orl_buffer* b) {
     }
   }
   h->e.buf = &b->b;
-  h->e.buf_gen = b->b.gen;
+  h->e.buf_gen = b->b.gen; h->e.buf_n = b->b.n;
   h->e.drop_graphs();             // captured graphs hold the old dataset pointers
+  return 0;
+}
+
+int orl_engine_attach_model_buffer(orl_engine* h, orl_buffer* m, int32_t real_rows) {
+  Engine& e = h->e;
+  if (!m) { if (e.mbuf) { e.mbuf = nullptr; e.mbuf_real_rows = 0; e.drop_graphs(); } return 0; }
+  if (m->b.od != e.od || m->b.ad != e.ad) return fail("attach_model_buffer: obs/act dims differ from the engine's");
+  if (m->b.dev != e.dev) return fail("attach_model_buffer: buffer lives on another device");
+  if (!m->b.d_n || m->b.cap < 1) return fail("attach_model_buffer: the model buffer must be a ring (orl_buffer_reserve)");
+  if (real_rows <= 0 || real_rows >= e.B) return fail("attach_model_buffer: real_rows must be in (0, batch_size)");
+  e.mbuf = &m->b; e.mbuf_real_rows = real_rows; e.mbuf_gen = m->b.gen;
+  e.drop_graphs();
   return 0;
 }
 
@@ -1735,12 +1868,20 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
   Engine& e = h->e;
   ORL_HIP(hipSetDevice(e.dev));
   if (n_steps <= 0) return fail("n_steps must be positive");
-  if (!e.buf || !e.buf->obs) return fail("orl_learn_n: no replay buffer attached");
+  if (!e.buf || !e.buf->obs || e.buf->n < 1) return fail("orl_learn_n: no replay buffer attached");
+  if (e.mbuf) {
+    if (!e.mbuf->obs || e.mbuf->n < 1) return fail("orl_learn_n: the model buffer is empty (roll the dynamics out into it first)");
+    if (e.cfg.algo == ORL_ALGO_CQL && e.mbuf_real_rows != e.cfg.cql_real_rows)
+      return fail("orl_learn_n: the model buffer's real_rows differs from the engine's cql_real_rows (COMBO's row layout)");
+  }
   ORL_HIP(hipMemsetAsync(e.metrics_sum, 0, sizeof(float) * e.R * e.nm, e.stream));
-  if (e.buf_gen != e.buf->gen) {       // the buffer was reloaded since the graphs were captured: they hold freed pointers and the old size
+  // the buffer was reloaded (or, a ring attached as the primary source, grew) since the graphs were captured: they hold freed pointers
+  // and the old size.  The model ring's size is read from its device cell: growth needs no re-capture, only a new reserve / load does.
+  if (e.buf_gen != e.buf->gen || e.buf_n != e.buf->n || (e.mbuf && e.mbuf_gen != e.mbuf->gen)) {
     ORL_HIP(hipStreamSynchronize(e.stream));
     e.drop_graphs();
-    e.buf_gen = e.buf->gen;
+    e.buf_gen = e.buf->gen; e.buf_n = e.buf->n;
+    if (e.mbuf) e.mbuf_gen = e.mbuf->gen;
   }
   const bool graphable = e.use_graph && !e.prof_on;
   if (graphable) {

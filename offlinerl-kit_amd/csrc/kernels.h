@@ -109,28 +109,159 @@ struct GatherP {
   unsigned long long seed;
   const unsigned long long* gstep;
   unsigned long long counter;                      // used when gstep == nullptr
+  // second source (orl_engine_attach_model_buffer): batch rows [real_rows, B) come from the model ring, whose current size is read from
+  // its device cell (the ring grows between replays of a captured graph); m_obs == nullptr: one source, the path above
+  const float *m_obs, *m_nobs, *m_act, *m_rew, *m_term;
+  const long long* m_n;
+  int real_rows;
 };
 __global__ void k_gather(GatherP p) {
   const int r = blockIdx.y;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int row = t / p.W, c = t - row * p.W;
   if (row >= p.B) return;
+  // the source of a batch row is a function of the row alone: real rows first, model rows behind them (mopo.py:81-84); the row keeps
+  // its Philox counter, only the range and the base pointers change
+  const bool mdl = p.m_obs && row >= p.real_rows;
+  const float *s_obs = mdl ? p.m_obs : p.obs, *s_nobs = mdl ? p.m_nobs : p.nobs, *s_act = mdl ? p.m_act : p.act;
+  const float *s_rew = mdl ? p.m_rew : p.rew, *s_term = mdl ? p.m_term : p.term;
   long j;
   if (p.idx) j = p.idx[(long)r * p.idx_rs + row];
   else {
     const unsigned long long ctr = p.gstep ? *p.gstep : p.counter;
+    const long n = mdl ? (long)*p.m_n : p.n;
     Philox ph(p.seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(r + 1));
     uint32_t o[4];
     ph((uint32_t)row, 0x51u, (uint32_t)ctr, 0x1D5u ^ (uint32_t)(ctr >> 32), o);
-    j = (long)(((unsigned long long)o[0] * (unsigned long long)p.n) >> 32);
+    j = (long)(((unsigned long long)o[0] * (unsigned long long)n) >> 32);
   }
   if (c < p.d_op) {
-    const float vo = c < p.od ? p.obs[j * p.OP + c] : 0.f, vn = c < p.od ? p.nobs[j * p.OP + c] : 0.f;
+    const float vo = c < p.od ? s_obs[j * p.OP + c] : 0.f, vn = c < p.od ? s_nobs[j * p.OP + c] : 0.f;
     p.b_obs[(long)r * p.obs_rs + (long)row * p.d_op + c] = vo;
     p.b_nobs[(long)r * p.nobs_rs + (long)row * p.d_op + c] = vn;
   }
-  if (c < p.d_ap) p.b_act[(long)r * p.act_rs + (long)row * p.d_ap + c] = c < p.ad ? p.act[j * p.AP + c] : 0.f;
-  if (c == 0) { p.b_rew[(long)r * p.rew_rs + row] = p.rew[j]; p.b_term[(long)r * p.term_rs + row] = p.term[j]; }
+  if (c < p.d_ap) p.b_act[(long)r * p.act_rs + (long)row * p.d_ap + c] = c < p.ad ? s_act[j * p.AP + c] : 0.f;
+  if (c == 0) { p.b_rew[(long)r * p.rew_rs + row] = s_rew[j]; p.b_term[(long)r * p.term_rs + row] = s_term[j]; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// one model-rollout step's bookkeeping (policy/model_based/mopo.py:45-79) on the device: the termination test of
+// utils/termination_fns.py on next_obs, all n transitions appended to the HBM ring (rows (ptr + i) % cap), the next_obs rows of the
+// transitions that did NOT terminate compacted densely and IN THEIR ORIGINAL ORDER (the dynamics' Philox draws are keyed by row
+// position), their count and the float64 sum of the rewards.  Two passes over ceil(n / 256) blocks: k_roll_term writes the 0 / 1
+// terminals and per-block (alive count, reward sum); k_roll_scatter turns the counts of the blocks in front of it into its offset,
+// ranks its own rows with wave ballots (64 lanes, 64-bit masks) and copies.  A fixed block order, no tickets: the result does not
+// depend on which block runs first.  Sources are packed [n][od] / [n][ad] arrays (not 16-byte aligned at od = 17), so the copies are
+// coalesced scalar loads; the pad columns of the ring rows are written as zeros.
+// ------------------------------------------------------------------------------------------------
+enum { ORL_TERM_NONE = 0, ORL_TERM_HALFCHEETAH, ORL_TERM_HOPPER, ORL_TERM_WALKER2D, ORL_TERM_ANT, ORL_TERM_HUMANOID, ORL_TERM_PEN, ORL_TERM_KINDS };
+__device__ inline bool orl_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+// the numpy comparisons of the reference restated: every test below is false on NaN, like numpy's
+__device__ inline bool orl_term_done(int kind, const float* x, int od) {
+  switch (kind) {
+    case ORL_TERM_HALFCHEETAH: {
+      bool in = true;
+      for (int c = 0; c < od; ++c) in = in && (x[c] > -100.f) && (x[c] < 100.f);
+      return !in;
+    }
+    case ORL_TERM_HOPPER: {             // abs(next_obs[:, 1:] < 100): an upper bound only, on columns 1..
+      bool ok = true;
+      for (int c = 0; c < od; ++c) ok = ok && orl_finite(x[c]) && (c == 0 || x[c] < 100.f);
+      return !(ok && x[0] > .7f && fabsf(x[1]) < .2f);
+    }
+    case ORL_TERM_WALKER2D: {
+      bool in = true;
+      for (int c = 0; c < od; ++c) in = in && (x[c] > -100.f) && (x[c] < 100.f);
+      return !(in && x[0] > 0.8f && x[0] < 2.0f && x[1] > -1.0f && x[1] < 1.0f);
+    }
+    case ORL_TERM_ANT: {
+      bool fin = true;
+      for (int c = 0; c < od; ++c) fin = fin && orl_finite(x[c]);
+      return !(fin && x[0] >= 0.2f && x[0] <= 1.0f);
+    }
+    case ORL_TERM_HUMANOID: return (x[0] < 1.0f) || (x[0] > 2.0f);      // NaN: not done
+    case ORL_TERM_PEN: return x[26] < 0.075f;                           // (od >= 27 is checked on the host)
+    default: return false;
+  }
+}
+struct RollP {
+  int kind;
+  const float *obs, *act, *nobs, *rew;   // packed [n][od], [n][ad], [n][od], [n]
+  long n; int od, ad;
+  float *r_obs, *r_nobs, *r_act, *r_rew, *r_term; int OP, AP; long cap, ptr;   // the ring
+  float* alive_nobs;                     // [<= n][od] packed; must not overlap nobs
+  int* blk_alive; double* blk_rew;       // [gridDim.x] scratch
+  long long* n_alive_out; double* rew_sum_out;
+};
+__global__ void k_roll_term(RollP p) {
+  __shared__ int sh_a[4];
+  __shared__ double sh_r[4];
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  bool alive = false;
+  double rw = 0.0;
+  if (i < p.n) {
+    const bool done = orl_term_done(p.kind, p.nobs + i * p.od, p.od);
+    p.r_term[(p.ptr + i) % p.cap] = done ? 1.0f : 0.0f;
+    alive = !done;
+    rw = (double)p.rew[i];
+  }
+  const unsigned long long m = __ballot(alive);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rw += __shfl_down(rw, o, 64);
+  if ((threadIdx.x & 63) == 0) { sh_a[threadIdx.x >> 6] = __popcll(m); sh_r[threadIdx.x >> 6] = rw; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    p.blk_alive[blockIdx.x] = sh_a[0] + sh_a[1] + sh_a[2] + sh_a[3];
+    p.blk_rew[blockIdx.x] = ((sh_r[0] + sh_r[1]) + sh_r[2]) + sh_r[3];
+  }
+}
+__global__ void k_roll_scatter(RollP p) {
+  __shared__ int sh_part[256];
+  __shared__ int sh_w[4];
+  __shared__ int sh_dst[256];
+  const int tid = threadIdx.x;
+  const long row0 = (long)blockIdx.x * 256, i = row0 + tid;
+  // alive rows of the blocks in front of this one (integers: the order of the sum does not matter)
+  int part = 0;
+  for (int b = tid; b < (int)blockIdx.x; b += 256) part += p.blk_alive[b];
+  sh_part[tid] = part;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) sh_part[tid] += sh_part[tid + o];
+    __syncthreads();
+  }
+  const int blk_off = sh_part[0];
+  const bool alive = i < p.n && p.r_term[(p.ptr + i) % p.cap] == 0.0f;
+  const unsigned long long m = __ballot(alive);
+  const int lane = tid & 63, w = tid >> 6;
+  if (lane == 0) sh_w[w] = __popcll(m);
+  __syncthreads();
+  int woff = 0;
+  for (int k = 0; k < w; ++k) woff += sh_w[k];
+  sh_dst[tid] = alive ? blk_off + woff + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+  __syncthreads();
+  const int rows = (int)(p.n - row0 < 256 ? p.n - row0 : 256);
+  for (int e = tid; e < rows * p.OP; e += 256) {
+    const int row = e / p.OP, c = e - row * p.OP;
+    const long src = (row0 + row) * p.od + c, dst = ((p.ptr + row0 + row) % p.cap) * p.OP + c;
+    p.r_obs[dst] = c < p.od ? p.obs[src] : 0.f;
+    p.r_nobs[dst] = c < p.od ? p.nobs[src] : 0.f;
+  }
+  for (int e = tid; e < rows * p.AP; e += 256) {
+    const int row = e / p.AP, c = e - row * p.AP;
+    p.r_act[((p.ptr + row0 + row) % p.cap) * p.AP + c] = c < p.ad ? p.act[(row0 + row) * p.ad + c] : 0.f;
+  }
+  for (int e = tid; e < rows * p.od; e += 256) {
+    const int row = e / p.od, c = e - row * p.od;
+    const int d = sh_dst[row];
+    if (d >= 0) p.alive_nobs[(long)d * p.od + c] = p.nobs[(row0 + row) * p.od + c];
+  }
+  if (i < p.n) p.r_rew[(p.ptr + i) % p.cap] = p.rew[i];
+  if (blockIdx.x == 0 && tid == 0) {      // totals in block order (a few hundred terms at 50 000 rows)
+    long long na = 0; double rs = 0.0;
+    for (int b = 0; b < (int)gridDim.x; ++b) { na += p.blk_alive[b]; rs += p.blk_rew[b]; }
+    *p.n_alive_out = na; *p.rew_sum_out = rs;
+  }
 }
 
 // normalize_obs (buffer.py:88-94): per-column mean / population std in double, then in-place scaling
@@ -230,6 +361,11 @@ struct PrepP {
   // step counter without a k_tick node (CQL): this kernel reads `gstep` = the PRE cell, which the step's loss kernel advances once every
   // reader of the step is behind it (k_cql_loss_rows), and publishes it to the cell every later kernel of the step reads.  null: off.
   unsigned long long* gstep_publish;
+  // second source (orl_engine_attach_model_buffer): batch rows >= real_rows are drawn from the model ring (size in its device cell);
+  // m_obs == nullptr: one source
+  const float *m_obs, *m_nobs, *m_act, *m_rew, *m_term;
+  const long long* m_n;
+  int real_rows;
 };
 // np.random.randint(0, size, B) (buffer.py:98) on the device: one Philox call per (run, batch row), drawn ONCE per step and shared by
 // every consumer of that row (batch slots, actor / critic input rows and their N-fold repeats)
@@ -277,8 +413,11 @@ __global__ void k_prepare(PrepP p) {
     const int b = jb.src_row0 + (jb.mod ? row % jb.mod : row) / jb.rep;
     const float* srow;
     if (p.d_obs) {
-      const long j = p.draw ? (long)orl_draw_index(p.seed, r, b, *p.gstep, p.n) : (long)p.idx[(long)r * p.idx_rs + b];
-      srow = (jb.src == PS_OBS ? p.d_obs : (jb.src == PS_NOBS ? p.d_nobs : p.d_act)) + j * (jb.src == PS_ACT ? p.AP : p.OP);
+      // every consumer of batch row b re-draws its index: the source (real / model) is a function of b alone
+      const bool mdl = p.m_obs && b >= p.real_rows;
+      const long j = p.draw ? (long)orl_draw_index(p.seed, r, b, *p.gstep, mdl ? (long)*p.m_n : p.n) : (long)p.idx[(long)r * p.idx_rs + b];
+      const float* base = jb.src == PS_OBS ? (mdl ? p.m_obs : p.d_obs) : (jb.src == PS_NOBS ? (mdl ? p.m_nobs : p.d_nobs) : (mdl ? p.m_act : p.d_act));
+      srow = base + j * (jb.src == PS_ACT ? p.AP : p.OP);
     } else {
       srow = jb.src == PS_ACT ? p.b_act + (long)r * p.ba_rs + (long)b * p.b_ap
                               : (jb.src == PS_OBS ? p.b_obs : p.b_nobs) + (long)r * p.bo_rs + (long)b * p.b_op;
@@ -302,13 +441,14 @@ __global__ void k_prepare(PrepP p) {
   } else if (jb.src != PS_ZERO && col < jb.ncopy) {
     const int b = jb.src_row0 + (jb.mod ? row % jb.mod : row) / jb.rep;
     if (p.d_obs) {
-      const long j = p.draw ? (long)orl_draw_index(p.seed, r, b, *p.gstep, p.n) : (long)p.idx[(long)r * p.idx_rs + b];
+      const bool mdl = p.m_obs && b >= p.real_rows;
+      const long j = p.draw ? (long)orl_draw_index(p.seed, r, b, *p.gstep, mdl ? (long)*p.m_n : p.n) : (long)p.idx[(long)r * p.idx_rs + b];
       switch (jb.src) {
-        case PS_OBS: v = p.d_obs[j * p.OP + col]; break;
-        case PS_NOBS: v = p.d_nobs[j * p.OP + col]; break;
-        case PS_ACT: v = p.d_act[j * p.AP + col]; break;
-        case PS_REW: v = p.d_rew[j]; if (p.draw && p.idx_out) p.idx_out[(long)r * p.idx_rs + b] = j; break;
-        default: v = p.d_term[j]; break;
+        case PS_OBS: v = (mdl ? p.m_obs : p.d_obs)[j * p.OP + col]; break;
+        case PS_NOBS: v = (mdl ? p.m_nobs : p.d_nobs)[j * p.OP + col]; break;
+        case PS_ACT: v = (mdl ? p.m_act : p.d_act)[j * p.AP + col]; break;
+        case PS_REW: v = (mdl ? p.m_rew : p.d_rew)[j]; if (p.draw && p.idx_out) p.idx_out[(long)r * p.idx_rs + b] = j; break;
+        default: v = (mdl ? p.m_term : p.d_term)[j]; break;
       }
     } else {
       switch (jb.src) {

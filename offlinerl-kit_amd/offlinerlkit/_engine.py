@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "orl_net_tensor", "orl_net_ptr", "orl_net_set", "orl_net_get", "orl_scalar_set", "orl_scalar_get",
     "orl_set_lr", "orl_reset_optimizers", "orl_adam_get", "orl_adam_set", "orl_set_step_count", "orl_buffer_create", "orl_buffer_destroy", "orl_buffer_load",
     "orl_buffer_normalize_obs", "orl_buffer_sample", "orl_buffer_size", "orl_engine_attach_buffer", "orl_step", "orl_learn_n",
+    "orl_buffer_reserve", "orl_buffer_append", "orl_buffer_append_rollout", "orl_buffer_read", "orl_engine_attach_model_buffer",
     "orl_health", "orl_health_check", "orl_health_clear", "orl_num_metrics", "orl_metric_name", "orl_step_count",
     "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
     # dynamics ensemble (orl_dynamics)
@@ -159,6 +160,12 @@ def load_library(path: Optional[str] = None):
     lib.orl_buffer_size.argtypes = [C.c_void_p]
     lib.orl_buffer_size.restype = C.c_int64
     lib.orl_engine_attach_buffer.argtypes = [C.c_void_p, C.c_void_p]
+    lib.orl_buffer_reserve.argtypes = [C.c_void_p, C.c_int64]
+    lib.orl_buffer_append.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_int]
+    lib.orl_buffer_append_rollout.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p,
+                                                                                           C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.orl_buffer_read.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5
+    lib.orl_engine_attach_model_buffer.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.orl_step.argtypes = [C.c_void_p, C.POINTER(OrlBatch), C.POINTER(OrlNoise), C.c_void_p]
     lib.orl_learn_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_health.argtypes = [C.c_void_p, C.c_void_p]
@@ -254,6 +261,10 @@ def apply_config(cfg: OrlConfig, over: Dict) -> None:
 
 def _f32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _is_tensor(a) -> bool:
+    return type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
 
 
 class Engine:
@@ -368,6 +379,12 @@ class Engine:
     def attach_buffer(self, buf: "DeviceBuffer"):
         _check(self.lib.orl_engine_attach_buffer(self._h, buf._h if buf is not None else None), "orl_engine_attach_buffer")
         self._buf = buf   # keep alive
+
+    def attach_model_buffer(self, buf: Optional["DeviceBuffer"], real_rows: int = 0):
+        """batch rows [0, real_rows) from the attached buffer, rows [real_rows, B) from the ring ``buf`` (None detaches)"""
+        _check(self.lib.orl_engine_attach_model_buffer(self._h, buf._h if buf is not None else None, int(real_rows)),
+               "orl_engine_attach_model_buffer")
+        self._mbuf = buf  # keep alive
 
     # ---- hot path ----
     def step(self, batch: Optional[Dict[str, np.ndarray]], noise: Optional[List[np.ndarray]], on_device=False) -> np.ndarray:
@@ -524,6 +541,66 @@ class DeviceBuffer:
         std = np.zeros(self.obs_dim, dtype=np.float32)
         _check(self.lib.orl_buffer_normalize_obs(self._h, float(eps), mean.ctypes.data, std.ctypes.data), "orl_buffer_normalize_obs")
         return mean, std
+
+    # ---- growable ring (the model-rollout buffer) ----
+    def reserve(self, capacity: int):
+        _check(self.lib.orl_buffer_reserve(self._h, int(capacity)), "orl_buffer_reserve")
+        self.capacity = int(capacity)
+
+    def append(self, obs, act, next_obs, rew, term):
+        """``add_batch`` on the device.  Host arrays, or torch tensors on this buffer's device (all five of one kind)."""
+        arrs = (obs, act, next_obs, rew, term)
+        if any(_is_tensor(a) for a in arrs):
+            import torch
+            ts = [a.detach().to(dtype=torch.float32).contiguous() for a in arrs]
+            if any(t.device.type != "cuda" or (t.device.index or 0) != self.device for t in ts):
+                raise ValueError("append: device sources must be tensors on the buffer's device")
+            n = int(ts[0].shape[0])
+            self._check_rows(n, [tuple(t.shape) for t in ts])
+            torch.cuda.current_stream(ts[0].device).synchronize()
+            ptrs, dev = [t.data_ptr() for t in ts], 1
+        else:
+            ts = [_f32(obs), _f32(act), _f32(next_obs), _f32(rew).ravel(), _f32(term).ravel()]
+            n = int(ts[0].shape[0])
+            self._check_rows(n, [t.shape for t in ts])
+            ptrs, dev = [t.ctypes.data for t in ts], 0
+        _check(self.lib.orl_buffer_append(self._h, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], n, dev), "orl_buffer_append")
+
+    def _check_rows(self, n: int, shapes):
+        so, sa, sn, sr, st = shapes
+        if tuple(so) != (n, self.obs_dim) or tuple(sn) != (n, self.obs_dim) or tuple(sa) != (n, self.act_dim) \
+                or int(np.prod(sr)) != n or int(np.prod(st)) != n:
+            raise ValueError(f"append: shapes {shapes} do not describe {n} rows of ({self.obs_dim}, {self.act_dim})")
+
+    def append_rollout(self, term_kind: int, obs, act, next_obs, rew, alive_next_obs):
+        """one rollout step (orl_buffer_append_rollout): torch tensors on this buffer's device, packed fp32; ``alive_next_obs`` has
+        room for every row.  Returns (n_alive, float64 reward sum)."""
+        import torch
+        n = int(obs.shape[0])
+        for name, t, shape in (("obs", obs, (n, self.obs_dim)), ("act", act, (n, self.act_dim)), ("next_obs", next_obs, (n, self.obs_dim)),
+                               ("rew", rew, None), ("alive_next_obs", alive_next_obs, None)):
+            if not _is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" \
+                    or (t.device.index or 0) != self.device:
+                raise ValueError(f"append_rollout: {name} must be a contiguous fp32 tensor on the buffer's device")
+            if shape is not None and tuple(t.shape) != shape:
+                raise ValueError(f"append_rollout: {name} has shape {tuple(t.shape)}, expected {shape}")
+        if rew.numel() != n or alive_next_obs.numel() < n * self.obs_dim:
+            raise ValueError("append_rollout: rew needs n values, alive_next_obs room for n rows")
+        torch.cuda.current_stream(obs.device).synchronize()
+        na, rs = C.c_int64(), C.c_double()
+        _check(self.lib.orl_buffer_append_rollout(self._h, int(term_kind), obs.data_ptr(), act.data_ptr(), next_obs.data_ptr(), rew.data_ptr(),
+                                                  n, alive_next_obs.data_ptr(), C.byref(na), C.byref(rs)), "orl_buffer_append_rollout")
+        return int(na.value), float(rs.value)
+
+    def read_rows(self, row0: int, n: int):
+        """(obs, act, next_obs, rew [n, 1], term [n, 1]) host copies of rows [row0, row0 + n)"""
+        obs, nobs = np.empty((n, self.obs_dim), np.float32), np.empty((n, self.obs_dim), np.float32)
+        act = np.empty((n, self.act_dim), np.float32)
+        rew, term = np.empty((n, 1), np.float32), np.empty((n, 1), np.float32)
+        if n > 0:
+            _check(self.lib.orl_buffer_read(self._h, int(row0), int(n), obs.ctypes.data, act.ctypes.data, nobs.ctypes.data, rew.ctypes.data,
+                                            term.ctypes.data), "orl_buffer_read")
+        return obs, act, nobs, rew, term
 
     def sample_into(self, idx, batch: int, seed: int, obs_ptr: int, act_ptr: int, nobs_ptr: int, rew_ptr: int, term_ptr: int):
         """Gather into caller-owned device arrays (raw device pointers)."""
@@ -704,3 +781,21 @@ class Dynamics:
                                      None if mi is None else mi.ctypes.data, DYN_PENALTY[mode], float(coef), nxt.ctypes.data,
                                      rew.ctypes.data, raw.ctypes.data, pen.ctypes.data, mo.ctypes.data), "orl_dyn_step")
         return nxt, rew, raw, pen, mo
+
+    def step_device(self, obs, act, mode: str = "aleatoric", coef: float = 0.0):
+        """``step`` on torch tensors of the engine's device: obs [R][N][od], act [R][N][ad] contiguous fp32; draws from the device Philox
+        stream.  Returns (next_obs [R][N][od], reward, raw_reward, penalty [R][N]) tensors."""
+        import torch
+        R, n = int(obs.shape[0]), int(obs.shape[1])
+        if R != self.n_runs or tuple(obs.shape) != (R, n, self.od) or tuple(act.shape) != (R, n, self.ad):
+            raise ValueError(f"step_device: obs {tuple(obs.shape)} / act {tuple(act.shape)} are not [{self.n_runs}, N, {self.od}] / [.., {self.ad}]")
+        for t in (obs, act):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" or (t.device.index or 0) != self.cfg.device:
+                raise ValueError("step_device: contiguous fp32 tensors on the engine's device")
+        dev = obs.device
+        nxt = torch.empty((R, n, self.od), dtype=torch.float32, device=dev)
+        rew, raw, pen = (torch.empty((R, n), dtype=torch.float32, device=dev) for _ in range(3))
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self.lib.orl_dyn_step(self._h, obs.data_ptr(), act.data_ptr(), n, 1, None, None, DYN_PENALTY[mode], float(coef),
+                                     nxt.data_ptr(), rew.data_ptr(), raw.data_ptr(), pen.data_ptr(), None), "orl_dyn_step")
+        return nxt, rew, raw, pen

@@ -195,6 +195,41 @@ class EnsembleDynamics(BaseDynamics):
             info["penalty"] = pen[..., None]
         return nxt, reward if self._penalty_coef else raw[..., None], terminal, info
 
+    @property
+    def term_kind(self) -> Optional[int]:
+        """the ``TERM_*`` kind of the termination function (utils.termination_fns), None when it is not a fixed row-wise test"""
+        from ..utils import termination_fns
+        return termination_fns.term_kind(self.terminal_fn)
+
+    @torch.no_grad()
+    def step_device(self, obs: torch.Tensor, action: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, Dict]:
+        """``step`` without the termination function, on tensors of the engine's device and without a host round trip: obs (N, obs_dim),
+        action (N, act_dim) -> (next_obs (N, obs_dim), reward (N,), info).  Same scaler, elites and penalty handling as ``step``; the
+        draws come from the device Philox stream (the same stream, keyed by the call counter, as ``step`` without teacher forcing).
+        With several runs every run steps the same rows and the selected run's outputs are returned.  The termination test is left to
+        the consumer (``DeviceBuffer.append_rollout`` runs ``term_kind`` on the device)."""
+        self._bind(*(self._shape or (256, 0.01)))
+        self._sync_torch()
+        self._push_elites_from_model()
+        dev = self._arena.device
+        R = self._n_runs
+        o = torch.as_tensor(obs, dtype=torch.float32, device=dev)
+        a = torch.as_tensor(action, dtype=torch.float32, device=dev)
+        if o.dim() != 2 or a.dim() != 2 or o.shape[0] != a.shape[0]:
+            raise ValueError(f"step_device: obs {tuple(o.shape)} / action {tuple(a.shape)} must be (N, obs_dim) / (N, act_dim)")
+        for r in range(R):
+            sc = self.scalers[r]
+            if sc.mu is None:
+                raise RuntimeError("the scaler is not fitted: train() or load() the dynamics first")
+            self._eng.set_scaler(r, sc.mu, sc.std)
+        nxt, rew, raw, pen = self._eng.step_device(o.unsqueeze(0).expand(R, *o.shape).contiguous(), a.unsqueeze(0).expand(R, *a.shape).contiguous(),
+                                                   self._uncertainty_mode, float(self._penalty_coef))
+        r = self._cur_run
+        info = {"raw_reward": raw[r]}
+        if self._penalty_coef:
+            info["penalty"] = pen[r]
+        return nxt[r], (rew[r] if self._penalty_coef else raw[r]), info
+
     def sample_next_obss(self, obs, action, num_samples: int):
         raise NotImplementedError("sample_next_obss is used by MOBILE only, which this package does not implement")
 

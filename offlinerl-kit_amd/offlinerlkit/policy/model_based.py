@@ -4,8 +4,12 @@ policy/model_based/combo.py:12-241) on the HIP engine.
 ``MOPOPolicy.learn`` and ``COMBOPolicy.learn`` take ``{"real": batch, "fake": batch}``, concatenate real rows first and run the SAC /
 CQL-variant update of the engine on the mixed batch.  ``rollout`` needs an object with ``step(obs, act) -> (next_obs, reward, terminal,
 info)``: ``offlinerlkit.dynamics.EnsembleDynamics`` with a function of ``utils.termination_fns``.  ``policy_trainer.MBPolicyTrainer`` runs
-the reference's loop around them.  These policies are host-fed (``learn``): the fused device-sampling loop ``learn_n`` draws from ONE
-replay buffer and does not apply to a real + model pair.
+the reference's loop around them.
+
+The fused epoch (``MBPolicyTrainer(fused=True)``) keeps the model buffer in an HBM ring (``ReplayBuffer.reserve_device``):
+``rollout_device`` rolls the dynamics forward without a host round trip (``EnsembleDynamics.step_device`` and the termination /
+compaction kernel behind ``DeviceBuffer.append_rollout``) and ``learn_n(n_steps, real_buffer, fake_buffer, ...)`` draws the real and
+the model rows of every minibatch inside ``orl_learn_n`` (``orl_engine_attach_model_buffer``).
 """
 from __future__ import annotations
 
@@ -57,6 +61,63 @@ def _rollout(policy, init_obss: np.ndarray, rollout_length: int, uniform: bool) 
             break
         observations = next_observations[nonterm]
     return {k: np.concatenate(v, axis=0) for k, v in out.items()}, {"num_transitions": num_transitions, "reward_mean": rewards_arr.mean()}
+
+
+def _rollout_device(policy, real_buffer, fake_buffer, rollout_batch_size: int, rollout_length: int, init_obss, uniform: bool) -> Dict:
+    """``_rollout`` with every array on the device: the transitions go straight into ``fake_buffer``'s HBM ring.  One host sync per
+    model step (the count of surviving rows sizes the next step).  The compaction keeps the surviving rows in their order, so the
+    dynamics consumes the Philox draws the host rollout consumes."""
+    dyn = policy.dynamics
+    kind = getattr(dyn, "term_kind", None)
+    if kind is None or not hasattr(dyn, "step_device"):
+        raise NotImplementedError("rollout_device: the dynamics' termination function is not one of the fixed row-wise tests of "
+                                  "utils.termination_fns (an obs_unnormalization wrapper, door or another callable carries no term_kind): "
+                                  "the device rollout cannot evaluate it; use rollout() / MBPolicyTrainer(fused=False)")
+    ring = fake_buffer.reserve_device()
+    if init_obss is None:
+        init_obss = real_buffer.sample(rollout_batch_size)["observations"]
+    dev = torch.device("cuda", ring.device)
+    obs = torch.as_tensor(init_obss, dtype=torch.float32, device=dev).reshape(len(init_obss), -1).contiguous()
+    num_transitions, rew_sum = 0, 0.0
+    with torch.no_grad():
+        for _ in range(rollout_length):
+            n = int(obs.shape[0])
+            if uniform:
+                sp = policy.action_space
+                act = torch.empty((n, sp.shape[0]), dtype=torch.float32, device=dev).uniform_(float(sp.low[0]), float(sp.high[0]))
+            else:
+                act, _ = policy.actforward(obs, False)
+                act = act.to(torch.float32).contiguous()
+            nxt, rew, _ = dyn.step_device(obs, act)
+            alive = torch.empty_like(nxt)
+            n_alive, s = ring.append_rollout(kind, obs, act, nxt.contiguous(), rew.contiguous(), alive)
+            fake_buffer._advance(n)
+            num_transitions += n
+            rew_sum += s
+            if n_alive == 0:
+                break
+            obs = alive[:n_alive]
+    return {"num_transitions": num_transitions, "reward_mean": rew_sum / num_transitions}
+
+
+def _learn_n_mb(policy, n_steps: int, real_buffer, fake_buffer, batch_size: int, real_ratio: float) -> Dict[str, float]:
+    """``n_steps`` x (sample real, sample model, learn) fused on the device: both index draws inside ``orl_learn_n``"""
+    if real_buffer is None or fake_buffer is None:
+        raise NotImplementedError(f"{type(policy).__name__} mixes a real and a model-rollout buffer per batch: "
+                                  "learn_n(n_steps, real_buffer, fake_buffer, ...), or learn({'real': ..., 'fake': ...})")
+    real_rows = int(batch_size * real_ratio)               # mb_policy_trainer.py:81-82
+    policy._bind(batch_size)
+    real = real_buffer.device_buffer() if hasattr(real_buffer, "device_buffer") else real_buffer
+    model = fake_buffer.reserve_device() if hasattr(fake_buffer, "reserve_device") else fake_buffer
+    key = (real, model, real_rows)
+    if policy._attached != key:
+        policy._eng.attach_buffer(real)
+        policy._eng.attach_model_buffer(model, real_rows)
+        policy._attached = key
+    policy._push_lrs()
+    m, ms = policy._eng.learn_n(int(n_steps))
+    policy.last_learn_n_ms = ms
+    return policy._result(m)
 
 
 class SACPolicy(_TanhGaussPolicy):
@@ -112,8 +173,15 @@ class MOPOPolicy(SACPolicy):
     def learn(self, batch: Dict, noise=None) -> Dict[str, float]:
         return super().learn(_cat(batch), noise) if "real" in batch else super().learn(batch, noise)
 
-    def learn_n(self, *a, **k):
-        raise NotImplementedError("MOPO mixes a real and a model-rollout buffer per batch: use learn({'real': ..., 'fake': ...})")
+    def rollout_device(self, real_buffer, fake_buffer, rollout_batch_size: int, rollout_length: int, init_obss=None) -> Dict:
+        """``rollout`` + ``fake_buffer.add_batch`` on the device; returns the reference's rollout info"""
+        return _rollout_device(self, real_buffer, fake_buffer, rollout_batch_size, rollout_length, init_obss, False)
+
+    def learn_n(self, n_steps: int, real_buffer, fake_buffer=None, batch_size: int = 256, real_ratio: float = 0.05) -> Dict[str, float]:
+        """the inner loop of MBPolicyTrainer (mb_policy_trainer.py:78-90) fused on the device: rows [0, int(batch_size * real_ratio))
+        of every minibatch from ``real_buffer``, the rest from ``fake_buffer``'s ring; returns the per-key means.  The single-buffer
+        form of the model-free policies is refused: every batch mixes a real and a model-rollout buffer."""
+        return _learn_n_mb(self, n_steps, real_buffer, fake_buffer, batch_size, real_ratio)
 
 
 class COMBOPolicy(CQLPolicy):
@@ -159,5 +227,21 @@ class COMBOPolicy(CQLPolicy):
                 self._rows = rows
         return super().learn(_cat(batch), noise)
 
-    def learn_n(self, *a, **k):
-        raise NotImplementedError("COMBO mixes a real and a model-rollout buffer per batch: use learn({'real': ..., 'fake': ...})")
+    def rollout_device(self, real_buffer, fake_buffer, rollout_batch_size: int, rollout_length: int, init_obss=None) -> Dict:
+        """``rollout`` + ``fake_buffer.add_batch`` on the device (uniform actions from torch's device generator when ``uniform_rollout``)"""
+        return _rollout_device(self, real_buffer, fake_buffer, rollout_batch_size, rollout_length, init_obss, self._uniform_rollout)
+
+    def learn_n(self, n_steps: int, real_buffer, fake_buffer=None, batch_size: int = 256, real_ratio: float = 0.05) -> Dict[str, float]:
+        """as ``MOPOPolicy.learn_n``; the real / model split is part of the engine's row layout, so a changed split re-binds"""
+        if real_buffer is None or fake_buffer is None:
+            return _learn_n_mb(self, n_steps, real_buffer, fake_buffer, batch_size, real_ratio)      # raises
+        real_rows = int(batch_size * real_ratio)
+        rows = (real_rows, int(batch_size) - real_rows)
+        if rows != self._rows:
+            if self._eng is not None:
+                carried = self._unbind()
+                self._rows = rows
+                self._rebind_with(carried, rows[0] + rows[1])
+            else:
+                self._rows = rows
+        return _learn_n_mb(self, n_steps, real_buffer, fake_buffer, batch_size, real_ratio)

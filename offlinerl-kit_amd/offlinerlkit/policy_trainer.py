@@ -22,6 +22,8 @@ MBPolicyTrainer is the reference's model-based loop (MOPO / COMBO): per step, a 
 (``policy.rollout`` from a ``real_buffer.sample`` of initial states, appended to ``fake_buffer``), then a real and a model minibatch
 split by ``real_ratio`` and one ``policy.learn({"real": ..., "fake": ...})``.  The draw order, logged keys, checkpoints and the final
 ``dynamics.save`` are the reference's; evaluation, the multi-run ``run<i>/...`` keys and the per-run checkpoints are MFPolicyTrainer's.
+``MBPolicyTrainer(fused=True)`` keeps the model buffer in an HBM ring and runs an epoch as device rollouts at the reference's
+timesteps with ONE ``policy.learn_n`` between two of them (``fused_mb_schedule``).
 """
 from __future__ import annotations
 
@@ -260,12 +262,38 @@ def _host(x) -> np.ndarray:
     return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
 
 
+def fused_mb_schedule(num_timesteps: int, step_per_epoch: int, rollout_freq: int) -> List[Tuple[bool, int]]:
+    """One epoch of the model-based loop (mb_policy_trainer.py:66-102) that starts at timestep ``num_timesteps``, as chunks
+    ``(rollout_first, n_steps)``: a rollout happens in front of exactly the timesteps ``t`` with ``t % rollout_freq == 0``, and the
+    training steps between two such points (or up to the epoch's end) form one chunk.  No chunk is empty and the lengths sum to
+    ``step_per_epoch``."""
+    if rollout_freq < 1 or step_per_epoch < 0:
+        raise ValueError("rollout_freq must be >= 1 and step_per_epoch >= 0")
+    out, t, end = [], num_timesteps, num_timesteps + step_per_epoch
+    while t < end:
+        nxt = min(end, (t // rollout_freq + 1) * rollout_freq)
+        out.append((t % rollout_freq == 0, nxt - t))
+        t = nxt
+    return out
+
+
 class MBPolicyTrainer(MFPolicyTrainer):
-    """Constructor = mb_policy_trainer.py:18-55.  ``rollout_setting`` = (rollout_freq, rollout_batch_size, rollout_length)."""
+    """Constructor = mb_policy_trainer.py:18-55.  ``rollout_setting`` = (rollout_freq, rollout_batch_size, rollout_length).
+
+    ``fused=True`` runs an epoch on the device: at every timestep ``t`` with ``t % rollout_freq == 0`` one ``policy.rollout_device``
+    into ``fake_buffer``'s HBM ring (``fake_buffer.reserve_device()``, called here), and between those points ONE
+    ``policy.learn_n(steps, real_buffer, fake_buffer, batch_size, real_ratio)``.  The logged loss keys are the step-weighted means of
+    the chunks (what ``logkv_mean`` holds after the same steps); the rollout log line, the ``rollout_info/*`` keys, evaluation,
+    checkpoints, health check and ``dynamics.save`` are those of the host loop.  What differs from the host loop: the minibatch indices
+    of both buffers come from the device Philox stream instead of numpy's (as for ``MFPolicyTrainer(fused=True)``), and the model
+    draws of a rollout from the dynamics' device stream; runs are reproducible from the seed but not index-identical to the
+    reference.  Refused at construction: ``dynamics_update_freq > 0`` (only RAMBO updates its dynamics), a policy without
+    ``rollout_device``, a dynamics whose termination function is not one of the fixed row-wise tests (no ``term_kind``)."""
 
     def __init__(self, policy, eval_env, real_buffer, fake_buffer, logger, rollout_setting: Tuple[int, int, int], epoch: int = 1000,
                  step_per_epoch: int = 1000, batch_size: int = 256, real_ratio: float = 0.05, eval_episodes: int = 10,
-                 lr_scheduler=None, dynamics_update_freq: int = 0, horizon: Optional[int] = None, progress: bool = False) -> None:
+                 lr_scheduler=None, dynamics_update_freq: int = 0, horizon: Optional[int] = None, progress: bool = False,
+                 fused: bool = False) -> None:
         super().__init__(policy, eval_env, real_buffer, logger, epoch=epoch, step_per_epoch=step_per_epoch, batch_size=batch_size,
                          eval_episodes=eval_episodes, lr_scheduler=lr_scheduler, fused=False, progress=progress)
         self.real_buffer = real_buffer
@@ -276,6 +304,18 @@ class MBPolicyTrainer(MFPolicyTrainer):
         self._real_ratio = real_ratio
         self.is_gymnasium_env = hasattr(self._score_env(), "get_true_observation")
         assert (not self.is_gymnasium_env) or (self.horizon is not None), "Horizon must be specified for Gymnasium env"
+        self._fused_mb = bool(fused)
+        if self._fused_mb:
+            if dynamics_update_freq > 0:
+                raise ValueError("MBPolicyTrainer(fused=True): dynamics_update_freq > 0 is not supported (only RAMBO has update_dynamics, "
+                                 "and its dynamics changes between the steps of a chunk)")
+            if not (hasattr(policy, "rollout_device") and hasattr(policy, "learn_n")):
+                raise ValueError(f"MBPolicyTrainer(fused=True): {type(policy).__name__} has no rollout_device / two-buffer learn_n")
+            if getattr(getattr(policy, "dynamics", None), "term_kind", None) is None:
+                raise ValueError("MBPolicyTrainer(fused=True): the dynamics' termination function is not one of the fixed row-wise tests of "
+                                 "utils.termination_fns (no term_kind: an obs_unnormalization wrapper, door or another callable), so the "
+                                 "device rollout cannot evaluate it; use fused=False")
+            fake_buffer.reserve_device()
 
     # ---- the reference's inner loop (mb_policy_trainer.py:66-102) -----------------------------------------
     def _rollout(self) -> None:
@@ -286,7 +326,29 @@ class MBPolicyTrainer(MFPolicyTrainer):
         for k, v in rollout_info.items():
             self.logger.logkv_mean("rollout_info/" + k, v)
 
+    def _rollout_fused(self) -> None:
+        rollout_info = self.policy.rollout_device(self.real_buffer, self.fake_buffer, self._rollout_batch_size, self._rollout_length)
+        self.logger.log("num rollout transitions: {}, reward mean: {:.4f}".format(rollout_info["num_transitions"], rollout_info["reward_mean"]))
+        for k, v in rollout_info.items():
+            self.logger.logkv_mean("rollout_info/" + k, v)
+
+    def _train_mb_epoch_fused(self, e: int, num_timesteps: int) -> int:
+        sums: Dict[str, float] = {}
+        for rollout_first, steps in fused_mb_schedule(num_timesteps, self._step_per_epoch, self._rollout_freq):
+            if rollout_first:
+                self._rollout_fused()
+            means = self.policy.learn_n(steps, self.real_buffer, self.fake_buffer, self._batch_size, self._real_ratio)
+            for k, v in means.items():
+                sums[k] = sums.get(k, 0.0) + float(v) * steps
+            num_timesteps += steps
+        for k, v in sums.items():
+            self.logger.logkv(k, v / self._step_per_epoch)
+        self._check_health()
+        return num_timesteps
+
     def _train_mb_epoch(self, e: int, num_timesteps: int) -> int:
+        if self._fused_mb:
+            return self._train_mb_epoch_fused(e, num_timesteps)
         it = range(self._step_per_epoch)
         if self._progress:
             from tqdm import tqdm

@@ -7,9 +7,10 @@ outputs bit for bit, quirks included:
     test fails), humanoid and pen compare false on NaN and leave them not done;
   * pendulum returns float zeros, door returns ``None``.
 
-Functions that are a fixed row-wise test of ``next_obs`` carry a ``term_kind`` attribute (``TERM_*`` below), which names the test a
-device termination kernel would have to run.  No such kernel exists yet and nothing in the package reads the tags.  ``obs_unnormalization``
-wrappers, door and arbitrary callables carry none.
+Functions that are a fixed row-wise test of ``next_obs`` carry a ``term_kind`` attribute (``TERM_*`` below), which names the test the
+device rollout runs instead of the function (``orl_buffer_append_rollout``: ``EnsembleDynamics.term_kind`` ->
+``policy.rollout_device`` -> ``DeviceBuffer.append_rollout``; the values are the C ABI's kind numbers).  ``obs_unnormalization``
+wrappers, door and arbitrary callables carry none and are host only.
 """
 from __future__ import annotations
 

@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""Model-based training-loop throughput at the halfcheetah shape of run_mopo.py / run_combo.py (obs 17, act 6, dynamics [200] x 4 with
+7 members, policy [256, 256] (COMBO [256, 256, 256]), batch 256, real_ratio 0.05 (COMBO 0.5), rollouts (1000, 50 000, 5), model buffer
+1.25 M rows, a synthetic 1 M-row dataset, the halfcheetah termination test): MBPolicyTrainer's host loop (fused=False) against the fused
+loop (fused=True), in ONE invocation and alternating -- a warm-up block of each, then three timed blocks each of 2 000 training steps
+including their two rollouts, timed with a host clock around work that ends in a device synchronise.  Also the rollout alone (ms per
+50 000 x 5 rollout, both paths).  Everything is built from seeds (an untrained dynamics ensemble with a unit scaler: the arithmetic per
+row is that of a trained one).  Prints one JSON object; --out writes it too.  Needs a GPU."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "offlinerl-kit_amd"))
+from offlinerlkit.buffer import ReplayBuffer  # noqa: E402
+from offlinerlkit.dynamics import EnsembleDynamics  # noqa: E402
+from offlinerlkit.modules import ActorProb, Critic, EnsembleDynamicsModel, TanhDiagGaussian  # noqa: E402
+from offlinerlkit.nets import MLP  # noqa: E402
+from offlinerlkit.policy import COMBOPolicy, MOPOPolicy  # noqa: E402
+from offlinerlkit.policy_trainer import MBPolicyTrainer  # noqa: E402
+from offlinerlkit.utils.scaler import StandardScaler  # noqa: E402
+from offlinerlkit.utils.termination_fns import termination_fn_halfcheetah  # noqa: E402
+
+DEV = "cuda:0"
+OD, AD, DYN_HID, K, E, B = 17, 6, [200, 200, 200, 200], 7, 5, 256
+DECAYS = [2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4]
+ROLLOUT = (1000, 50_000, 5)
+MODEL_ROWS, DATA_ROWS, BLOCK = 1_250_000, 1_000_000, 2_000
+
+
+class Space:
+    low, high, shape = -np.ones(AD, np.float32), np.ones(AD, np.float32), (AD,)
+
+
+class NullLogger:
+    def log(self, *a, **k):
+        pass
+
+    def logkv(self, *a, **k):
+        pass
+
+    logkv_mean = logkv
+
+
+def dataset(rows):
+    rng = np.random.default_rng(0)
+    obs = rng.normal(size=(rows, OD)).astype(np.float32)
+    return dict(observations=obs, actions=rng.uniform(-1, 1, size=(rows, AD)).astype(np.float32),
+                next_observations=(obs + 0.1 * rng.normal(size=(rows, OD))).astype(np.float32),
+                rewards=rng.normal(size=rows).astype(np.float32), terminals=np.zeros(rows, np.float32))
+
+
+def make_policy(algo):
+    torch.manual_seed(1)
+    model = EnsembleDynamicsModel(OD, AD, DYN_HID, num_ensemble=K, num_elites=E, weight_decays=DECAYS, device=DEV)
+    scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
+    dyn = EnsembleDynamics(model, torch.optim.Adam(model.parameters(), lr=1e-3), scaler, termination_fn_halfcheetah,
+                           penalty_coef=2.5 if algo == "mopo" else 0.0, uncertainty_mode="aleatoric")
+    dyn.set_engine_options(seed=7)
+    hid = [256, 256] if algo == "mopo" else [256, 256, 256]
+    adam = lambda m, lr: torch.optim.Adam(m.parameters(), lr=lr)
+    actor = ActorProb(MLP(OD, hid), TanhDiagGaussian(hid[-1], AD, unbounded=True, conditioned_sigma=True), DEV)
+    c1, c2 = Critic(MLP(OD + AD, hid), DEV), Critic(MLP(OD + AD, hid), DEV)
+    log_alpha = torch.zeros(1, requires_grad=True, device=DEV)
+    alpha = (-float(AD), log_alpha, torch.optim.Adam([log_alpha], lr=1e-4))
+    if algo == "mopo":
+        pol = MOPOPolicy(dyn, actor, c1, c2, adam(actor, 1e-4), adam(c1, 3e-4), adam(c2, 3e-4), tau=0.005, gamma=0.99, alpha=alpha)
+    else:
+        pol = COMBOPolicy(dyn, actor, c1, c2, adam(actor, 1e-4), adam(c1, 3e-4), adam(c2, 3e-4), Space(), tau=0.005, gamma=0.99, alpha=alpha,
+                          cql_weight=5.0, temperature=1.0, max_q_backup=False, deterministic_backup=True, with_lagrange=False,
+                          num_repeart_actions=10, uniform_rollout=False, rho_s="mix")
+    pol.set_engine_options(seed=3)
+    return pol
+
+
+def measure(algo, ds, blocks, block_steps, profile_only=False):
+    real_ratio = 0.05 if algo == "mopo" else 0.5
+    real = ReplayBuffer(len(ds["rewards"]), (OD,), np.float32, AD, np.float32, device=DEV)
+    real.load_dataset(ds)
+    pol = make_policy(algo)
+    pol.train()
+    trainers, t_now = {}, {}
+    for name in ("host", "fused"):
+        fake = ReplayBuffer(MODEL_ROWS, (OD,), np.float32, AD, np.float32, device=DEV)
+        trainers[name] = MBPolicyTrainer(pol, None, real, fake, NullLogger(), ROLLOUT, epoch=1, step_per_epoch=block_steps, batch_size=B,
+                                         real_ratio=real_ratio, fused=(name == "fused"))
+        t_now[name] = 0
+
+    def block(name):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        t_now[name] = trainers[name]._train_mb_epoch(1, t_now[name])
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    if profile_only:
+        block("fused")
+        return dict(algo=algo, fused_block_seconds=block("fused"))
+    np.random.seed(0)
+    torch.manual_seed(0)
+    warm = {name: block(name) for name in ("host", "fused")}
+    secs = {"host": [], "fused": []}
+    for _ in range(blocks):
+        for name in ("host", "fused"):
+            secs[name].append(block(name))
+    sps = {name: [block_steps / s for s in v] for name, v in secs.items()}
+
+    def rollout_ms(name, reps=3):
+        tr, out = trainers[name], []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tr._rollout_fused() if name == "fused" else tr._rollout()
+            torch.cuda.synchronize()
+            out.append(1e3 * (time.perf_counter() - t0))
+        return out
+    roll = {name: rollout_ms(name) for name in ("host", "fused")}
+    host_spread = max(sps["host"]) - min(sps["host"])
+    gain = float(np.mean(sps["fused"]) - np.mean(sps["host"]))
+    return dict(algo=algo, real_ratio=real_ratio, block_steps=block_steps, rollouts_per_block=len([t for t in range(block_steps) if t % ROLLOUT[0] == 0]),
+                warmup_block_seconds=warm, block_seconds=secs, steps_per_s=sps,
+                steps_per_s_mean={k: float(np.mean(v)) for k, v in sps.items()}, host_spread_steps_per_s=host_spread,
+                fused_minus_host_steps_per_s=gain, clears_bar=bool(gain > host_spread),
+                speedup=float(np.mean(sps["fused"]) / np.mean(sps["host"])),
+                rollout_ms=roll, rollout_ms_mean={k: float(np.mean(v)) for k, v in roll.items()},
+                model_rows={name: trainers[name].fake_buffer._size for name in trainers})
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=3)
+    ap.add_argument("--block-steps", type=int, default=BLOCK)
+    ap.add_argument("--algos", default="mopo,combo")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--profile-block", action="store_true", help="a warm-up and one fused MOPO block only (for a kernel trace)")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mb_throughput: no HIP device visible (the loops under test run on the GPU)")
+    ds = dataset(DATA_ROWS)
+    if a.profile_block:
+        print(json.dumps(measure("mopo", ds, 1, a.block_steps, profile_only=True)))
+        return
+    res = {"shape": dict(obs=OD, act=AD, dynamics_hidden=DYN_HID, members=K, batch=B, rollout=ROLLOUT, model_rows=MODEL_ROWS, data_rows=DATA_ROWS),
+           "device": torch.cuda.get_device_name(0), "results": [measure(x, ds, a.blocks, a.block_steps) for x in a.algos.split(",")]}
+    s = json.dumps(res, indent=1)
+    print(s)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(s + "\n")
+
+
+if __name__ == "__main__":
+    main()
