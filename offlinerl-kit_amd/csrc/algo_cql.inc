@@ -108,8 +108,8 @@ static int sac_actor_phase(Engine* e, const NetRef& actor, const NetRef& crit, i
     w.eps = e->W("n_eps_actor").p; w.eps_s0 = e->W("n_eps_actor").rs;
     w.xa = xa.p; w.xa_s0 = xa.rs; w.xa_pitch = xa.pitch; w.xa_col = od;
     w.logp = e->W("logp_a").p; w.logp_s0 = e->W("logp_a").rs;
-    w.qa = e->W("qa").p; w.qa_s0 = e->W("qa").rs; w.qa_s1 = e->W("qa").cs;
-    w.ga = dxa.p; w.ga_s0 = dxa.rs; w.ga_s1 = dxa.cs; w.ga_pitch = dxa.pitch; w.K = Kc;
+    w.qa = e->W("qa").z();
+    w.ga = dxa.z(); w.ga_pitch = dxa.pitch; w.K = Kc;
     w.W1 = actor.base + al.w_off[1]; w.w1_s0 = actor.rs;
     w.Wh = actor.base + al.w_off[2]; w.wh_s0 = actor.rs;
     w.out = e->grads + actor.g_off; w.o_s0 = (long)e->max_slab * e->P_train; w.o_ks = e->P_train;
@@ -121,14 +121,12 @@ static int sac_actor_phase(Engine* e, const NetRef& actor, const NetRef& crit, i
     w.m_actor = 0; w.m_alpha_loss = slot_alpha_loss; w.m_alpha = slot_alpha_loss + 1;
     w.part = e->aloss_part; w.ticket = e->cql_ticket;
     w.M = B; w.A = A; w.f32 = e->ws_f32();
-    w.lab_clk = (unsigned long long*)(e->aloss_part + (long)e->R * SB_MAXGROUPS * 2);      // (16 stamps behind the partial sums; written by lab builds only)
+    w.lab_clk = e->lab_clk(0);      // (16 stamps behind the partial sums; written by lab builds only)
     if (al.out_dim == 2 * A && small_abwd_supported(w)) {
       e->watch_range(ah[0], B, SB_N, 1, "actor.bwd");
-      e->prof_begin("actor.bwd_fused", 2.0 * B * (double)e->R * (2.0 * SB_N * SB_N + 2.0 * SB_N * 2 * A + (double)SB_N * (w.in0 + 1)),
-                    4.0 * e->R * (B * (double)(2 * SB_N + w.in0 + 6 * A + 4) + (double)SB_N * SB_N + (B / SB_ROWS) * (double)al.size));
-      hipError_t err = launch_small_abwd(w, e->R, e->stream);
-      e->prof_end();
-      if (err != hipSuccess) return fail(std::string("small_abwd launch: ") + hipGetErrorString(err));
+      if (e->timed("small_abwd", "actor.bwd_fused", false, 2.0 * B * (double)e->R * (2.0 * SB_N * SB_N + 2.0 * SB_N * 2 * A + (double)SB_N * (w.in0 + 1)),
+                   4.0 * e->R * (B * (double)(2 * SB_N + w.in0 + 6 * A + 4) + (double)SB_N * SB_N + (B / SB_ROWS) * (double)al.size),
+                   [&] { return launch_small_abwd(w, e->R, e->stream); })) return -1;
       const std::vector<int> ks(L + 1, B / SB_ROWS);
       return e->adam(ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, make_segs(al, ks, ks), -1);
     }

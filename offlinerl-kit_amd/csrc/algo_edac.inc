@@ -110,7 +110,7 @@ int Engine::edac_step() {
     cur_gscale = s_delta;                                  // the A operands of the sweep's wgrads are the deltas
     auto delta = [&](int l) { return (l == L - 1) ? DY::virt(ch[L - 1], ones) : DY::plain(dd[l]); };
     // (3) adjoint sweep: dW_0[action rows] += gamma^T delta_0 ; t_0 = (gamma W_0[action rows]) (.) m_0
-    int ks = wgrad_ksplit(cl.layer_out(0), A, B, nz, ksplit_cap);
+    int ks = wgrad_ksplit(cl.layer_out(0), A, B, nz);
     if (linear_wgrad(delta(0), gam, B, crit, 0, ks, ksW[0], false, "edac.wgrad0", od, A, nullptr, nullptr, s_gamma)) return -1;
     ksW[0] += ks;
     {
@@ -134,13 +134,13 @@ int Engine::edac_step() {
       } else if (linear_fwd(gam, B, crit, 0, tt[0], E_MASK, &ch[0], "edac.t0", od, A, nullptr, nullptr, nullptr, nullptr, s_gamma)) return -1;
     }
     for (int l = 1; l < L; ++l) {
-      ks = wgrad_ksplit(cl.layer_out(l), cl.layer_in(l), B, nz, ksplit_cap);
+      ks = wgrad_ksplit(cl.layer_out(l), cl.layer_in(l), B, nz);
       if (linear_wgrad(delta(l), tt[l - 1], B, crit, l, ks, ksW[l], false, "edac.wgrad", 0, -1, nullptr, nullptr, s_gamma)) return -1;
       ksW[l] += ks;
       if (linear_fwd(tt[l - 1], B, crit, l, tt[l], E_MASK, &ch[l], "edac.t", 0, -1, nullptr, nullptr, nullptr, nullptr, s_gamma)) return -1;
     }
     // dw_tail += sum_b t_{L-1}
-    ks = wgrad_ksplit(1, cl.layer_in(L), B, nz, ksplit_cap);
+    ks = wgrad_ksplit(1, cl.layer_in(L), B, nz);
     cur_gscale = nullptr;                                  // A = ones
     if (linear_wgrad(DY::plain(ones), tt[L - 1], B, crit, L, ks, ksW[L], false, "edac.wgrad_tail", 0, -1, nullptr, nullptr, s_gamma)) return -1;
     ksW[L] += ks;

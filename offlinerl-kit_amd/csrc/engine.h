@@ -70,6 +70,9 @@ struct Mat {
   Mat cols(int c0) const { Mat m = *this; m.p = p + c0; m.bits = nullptr; return m; }
   Mat net(int c) const { Mat m = *this; m.p = p + c * cs; if (bits) m.bits = bits + c * bcs; return m; }
   Mat shared() const { Mat m = *this; m.cs = 0; m.bcs = 0; return m; }
+  ZPtr z() const { return {p, rs, cs}; }
+  ZOut zo() const { return {p, rs, cs}; }
+  ZBits zbits() const { return {bits, brs, bcs}; }
 };
 struct NetRef {
   float* base = nullptr;  // params of run 0, member 0
@@ -77,6 +80,8 @@ struct NetRef {
   long g_off = 0;         // offset of the family's gradients inside a run's gradient slab
   const NetLayout* lay = nullptr;
   int nz1 = 1;            // members driven by a launch
+  ZPtr w(int l) const { return {base + lay->w_off[l], rs, lay->w_ms[l]}; }   // weight / bias block of layer l (l == L: the tail)
+  ZPtr b(int l) const { return {base + lay->b_off[l], rs, lay->b_ms[l]}; }
 };
 
 struct ProfEntry {
@@ -130,6 +135,8 @@ struct Engine {
   float* grads = nullptr;      // [R][max_slab][P_train]
   int max_slab = 128;          // split-K slabs per parameter (the fused layer-0 weight gradient writes one per row tile)
   int ksplit_cap = 32;         // cap of the split-K factor chosen for a stand-alone wgrad launch
+  int wgrad_wg_target = 512, wgrad_long_min = 4, wgrad_small_ks = 1;   // wgrad_ksplit's rules (ORL_WGRAD_WG_TARGET / _LONG_MIN / _SMALL_KS)
+  int wgrad_ksplit(int Mout, int Nout, int Krows, int nz) const;
   RunScalars* scalars = nullptr;
   Hyper* hyper = nullptr;
   Hyper hyper_host;
@@ -218,7 +225,9 @@ struct Engine {
   float* gscale_inv_b = nullptr;     // [R] constant scale of seeds whose entries are +-1/B (actor-loss dq)
   unsigned int* cql_ticket = nullptr;  // [R] arrival counters of k_cql_loss_rows
   int lab_slot = 0;                    // lab builds: which stamp block the next one-launch forward writes (reset per step)
-  float* aloss_part = nullptr;         // [R][SB_MAXGROUPS][2] per-row-group loss sums of the fused actor update (small_bwd.h)
+  float* aloss_part = nullptr;         // [R][SB_MAXGROUPS][2] per-row-group loss sums of the fused actor update (small_bwd.h), then the lab stamps
+  // lab builds ("lab_clk" tap, 192 floats): stamp word 0 = the fused actor update, 16 + 12 * slot: one-launch forwards, 64: critic forward, 72: wgrad
+  unsigned long long* lab_clk(int word) const { return (unsigned long long*)(aloss_part + (long)R * SB_MAXGROUPS * 2) + word; }
   // health (include/orl_engine.h: ORL_HEALTH_*): device words raised by kernels (k_adam: non-finite gradient; k_range_scan), the sticky
   // host copy that also holds what the host finds in the metrics it reads back, and the matrices of the last enqueued step that enter
   // the MFMAs as fp16 planes with operand scale 1 (registered by linear_fwd / mlp_forward while the step is enqueued or captured)
@@ -234,6 +243,7 @@ struct Engine {
 
   ~Engine();
   int init(const orl_config& c);
+  void read_env();             // every ORL_* knob of the engine, read once per engine
   Mat alloc(const std::string& name, long rows, int pitch, int nets = 1);
   Mat& W(const std::string& n) { return ws.at(n); }
   float* raw_alloc(size_t bytes);
@@ -242,6 +252,20 @@ struct Engine {
   MetricsP mp() const { return MetricsP{metrics_last, metrics_sum, nm}; }
 
   // launch helpers (enqueue on stream)
+  // prof_begin (tag + "@p3" for a three-plane flavour) / launch() / prof_end, and the error text "<what> launch <tag>: <hip error>"
+  template <class F>
+  int timed(const char* what, const char* tag, bool p3, double flops, double bytes, F launch) {
+    prof_begin(p3 ? (std::string(tag) + "@p3").c_str() : tag, flops, bytes);
+    const hipError_t err = launch();
+    prof_end();
+    return err == hipSuccess ? 0 : fail(std::string(what) + " launch " + tag + ": " + hipGetErrorString(err));
+  }
+  int tail_add(const ZOut& out, long out_sm, const ZOut& part, int nparts, int M, int nz1, const char* tag);
+  // the one place each parameter struct of the weight-stationary / few-rows kernels is created (engine.hip); 1 = shape not served
+  WsFwdP ws_fwd_p(const Mat& X, int M, const NetRef& nr, int layer, const Mat& Y, const Mat* dmask) const;
+  int ws_dgrad(const DY& dy, int M, const NetRef& nr, int layer, const Mat& maskH, const Mat* w0_X, const Mat* dX, int max_blocks, const char* tag, int* slabs);
+  int ws_wgrad(const DY& dy, const Mat& X, int M, const NetRef& nr, int layer, const Mat* recompute_X0, const char* tag, int* slabs);
+  SmallFwdP small_fwd_p(const Mat& X, int M, const NetRef& nr, const Mat* H0, const Mat* H1, const Mat& out) const;
   int linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const Mat& Y, int epi, const Mat* maskH, const char* tag,
                  int in_row0 = 0, int in_rows = -1, const Mat* tail_out = nullptr, bool* tail_fused = nullptr,
                  const Mat* fuse_X0 = nullptr, const char* tag0 = nullptr, const float* x_dscale = nullptr);

@@ -404,11 +404,8 @@ static int run_gemm(Engine* e, int cfg, const GemmP& p, int nz, const char* tag,
                                    (EPI == E_MASK ? (double)p.M * p.N / (p.aux_bits ? 32.0 : 1.0) : 0.0));
   double bytes_adj = bytes;
   if (EPI == E_MASK && p.w0_out) bytes_adj += 4.0 * nz * ((double)p.M * p.w0_xsr - (p.C ? 0.0 : (double)p.M * p.N));
-  e->prof_begin(tag, flops + (EPI == E_MASK && p.w0_out ? 2.0 * p.M * (double)p.N * (p.w0_in + 1) * nz : 0.0), bytes_adj);
-  hipError_t err = launch_gemm<PA, PB, EPI>(cfg, p, nz, e->stream, a_kpad, e->force_scalar, e->mm_prec());
-  e->prof_end();
-  if (err != hipSuccess) return fail(std::string("gemm launch ") + tag + ": " + hipGetErrorString(err));
-  return 0;
+  return e->timed("gemm", tag, false, flops + (EPI == E_MASK && p.w0_out ? 2.0 * p.M * (double)p.N * (p.w0_in + 1) * nz : 0.0), bytes_adj,
+                  [&] { return launch_gemm<PA, PB, EPI>(cfg, p, nz, e->stream, a_kpad, e->force_scalar, e->mm_prec()); });
 }
 
 // gradient w.r.t. a layer output [M x out].  rank1: dz = (H > 0) ? rowv[m] * w_tail[n] : 0 (never materialised)
@@ -419,6 +416,41 @@ struct DY {
   static DY plain(const Mat& m) { DY d; d.m = m; return d; }
   static DY virt(const Mat& H, const Mat& dq) { DY d; d.rank1 = true; d.m = H; d.rowv = dq; return d; }
 };
+
+// out[m] += the column-tile partial sums a fused single-output tail left in `part` ([nparts][M] per net)
+int Engine::tail_add(const ZOut& out, long out_sm, const ZOut& part, int nparts, int M, int nz1, const char* tag) {
+  TailAddP t;
+  t.out = out.p; t.o_s0 = out.s0; t.o_s1 = out.s1; t.o_sm = out_sm;
+  t.part = part.p; t.p_s0 = part.s0; t.p_s1 = part.s1; t.p_ts = M; t.nparts = nparts; t.M = M; t.nz1 = nz1;
+  prof_begin((std::string(tag) + ".tail_add").c_str(), 0);
+  hipLaunchKernelGGL(k_tail_add, dim3((M + 255) / 256, R * nz1), dim3(256), 0, stream, t);
+  prof_end();
+  return hipGetLastError() == hipSuccess ? 0 : fail("tail_add launch");
+}
+
+// Y = relu(X W^T + b) and the mask words of Y for a 256 x 256 layer; the caller adds the fused tail / first layer / three-plane scratch.
+// dmask != null: the plain dgrad mode -- X = the gradient w.r.t. the layer's output, Y = (X B^T) (.) dmask with B = the weights viewed transposed
+WsFwdP Engine::ws_fwd_p(const Mat& X, int M, const NetRef& nr, int layer, const Mat& Y, const Mat* dmask) const {
+  const NetLayout& l = *nr.lay;
+  const int in = l.layer_in(layer), out = l.layer_out(layer);
+  WsFwdP w;
+  memset(&w, 0, sizeof(w));
+  w.X = X.z(); w.x_pitch = X.pitch;
+  w.W = nr.w(layer);
+  w.Y = Y.zo(); w.y_pitch = Y.pitch;
+  if (dmask) {
+    // B[n = input unit][k = output unit]: nn.Linear W (out, in) -> element (k, n) at k * in + n; EnsembleLinear (in, out) -> n * out + k
+    if (l.ens) { w.w_sn = out; w.w_sk = 1; } else { w.w_sn = 1; w.w_sk = in; }
+    w.dmask = dmask->zbits(); w.dm_g = dmask->bg;
+    w.gscale = cur_gscale;
+  } else {
+    if (l.ens) { w.w_sn = 1; w.w_sk = out; } else { w.w_sn = in; w.w_sk = 1; }      // EnsembleLinear keeps (in, out)-major weights
+    w.bias = nr.b(layer);
+    w.mb = Y.zbits(); w.mb_g = Y.bg;
+  }
+  w.M = M; w.nz1 = nr.nz1; w.f32 = ws_f32();
+  return w;
+}
 
 // fuse_X0 (layer == 1 only): X = hs[0] has not been computed yet; it is relu(fuse_X0 W0^T + b0).  The weight-stationary kernel
 // produces it inside this launch (stores it to X for the backward pass); any other path first runs layer 0 on its own.
@@ -435,18 +467,19 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
   GemmP p;
   memset(&p, 0, sizeof(p));
   p.b_scale = ORL_WSCALE; p.a_dscale = x_dscale;      // split precision: static scale of the weight operand, dynamic one of a gradient-like input
-  p.A = {X.p, X.rs, X.cs};
+  p.A = X.z();
   p.a_sr = X.pitch; p.a_sk = 1;
-  if (l.ens) { p.B = {nr.base + l.w_off[layer] + (long)in_row0 * out, nr.rs, l.w_ms[layer]}; p.b_sr = 1; p.b_sk = out; p.b_rlim = out & ~3; }
-  else { p.B = {nr.base + l.w_off[layer] + in_row0, nr.rs, l.w_ms[layer]}; p.b_sr = in; p.b_sk = 1; }
+  p.B = nr.w(layer);
+  if (l.ens) { p.B.p += (long)in_row0 * out; p.b_sr = 1; p.b_sk = out; p.b_rlim = out & ~3; }
+  else { p.B.p += in_row0; p.b_sr = in; p.b_sk = 1; }
   p.C = Y.p; p.c_s0 = Y.rs; p.c_s1 = Y.cs; p.c_sr = Y.pitch; p.c_sn = 1;
   p.M = M; p.N = out; p.K = in_rows;
   const bool a_kpad = X.pitch >= ((in_rows + 3) & ~3);   // input matrices are zero-padded to 16 B rows
   p.nz1 = nr.nz1; p.ksplit = 1;
   vals_dead.erase(Y.p);
-  p.bias = {nr.base + l.b_off[layer], nr.rs, l.b_ms[layer]};
+  p.bias = nr.b(layer);
   if (maskH) {
-    p.aux = {maskH->p, maskH->rs, maskH->cs}; p.aux_sr = maskH->pitch;
+    p.aux = maskH->z(); p.aux_sr = maskH->pitch;
     // the ReLU mask as packed bits (1/32 of the bytes) when the forward pass that produced the activation left them behind
     if (epi == E_MASK && maskH->bits && bits_live.count(maskH->bits) && out == maskH->pitch && aligned16(maskH->p) && (maskH->pitch & 3) == 0) {
       p.aux_bits = maskH->bits; p.xb_s0 = maskH->brs; p.xb_s1 = maskH->bcs; p.xb_g = maskH->bg;
@@ -458,35 +491,23 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
   // weight-stationary row-streaming kernel (csrc/ws_gemm.h) for the many-row 256 x 256 hidden layers in split-bf16 precision
   if (epi == E_BIAS_RELU && ws_precision_ok() && !no_ws && !force_scalar && in_row0 == 0 && in_rows == in &&
       Y.bits && Y.pitch == out && (long)M * nz >= ws_fwd_min_rows) {   // measured faster than the 16x64 tiles from 16 x 256 rows up
-    WsFwdP w;
-    memset(&w, 0, sizeof(w));
-    w.X = X.p; w.x_s0 = X.rs; w.x_s1 = X.cs; w.x_pitch = X.pitch;
-    w.W = nr.base + l.w_off[layer]; w.w_s0 = nr.rs; w.w_s1 = l.w_ms[layer];
-    if (l.ens) { w.w_sn = 1; w.w_sk = out; } else { w.w_sn = in; w.w_sk = 1; }      // EnsembleLinear keeps (in, out)-major weights
-    w.bias = nr.base + l.b_off[layer]; w.b_s0 = nr.rs; w.b_s1 = l.b_ms[layer];
-    w.Y = Y.p; w.y_s0 = Y.rs; w.y_s1 = Y.cs; w.y_pitch = Y.pitch;
-    w.mb = Y.bits; w.mb_s0 = Y.brs; w.mb_s1 = Y.bcs; w.mb_g = Y.bg;
-    w.M = M; w.nz1 = nr.nz1; w.f32 = this->ws_f32();
+    WsFwdP w = ws_fwd_p(X, M, nr, layer, Y, nullptr);
     const bool want_tail = tail_out && tail_fused && layer == l.L - 1 && l.out_dim == 1;
-    if (want_tail) {
-      w.tw = nr.base + l.w_off[l.L]; w.tw_s0 = nr.rs; w.tw_s1 = l.w_ms[l.L];
-      w.tb = nr.base + l.b_off[l.L]; w.tb_s0 = nr.rs; w.tb_s1 = l.b_ms[l.L];
-      w.tq = tail_out->p; w.tq_s0 = tail_out->rs; w.tq_s1 = tail_out->cs; w.tq_sm = tail_out->pitch;
-    }
+    if (want_tail) { w.tw = nr.w(l.L); w.tb = nr.b(l.L); w.tq = tail_out->zo(); w.tq_sm = tail_out->pitch; }
     // With the single-output tail folded in, the backward pass of a many-row batch needs only the mask bits of this activation
     // (ws_dgrad_w0 / ws_wgrad's derived tail gradients): the activation itself then never goes to HBM.
     const bool elide = want_tail && layer >= 1 && (fwd_only || (elide_top && !l.ens && ws_wgrad_rows_ok(M, nz)));
-    if (elide) w.Y = nullptr;
+    if (elide) w.Y.p = nullptr;
     const bool ws_ok = ws_fwd_supported(w, in, out);
     bool fused0 = false;
     if (ws_ok && fuse_X0 && layer == 1 && X.bits && X.pitch == in) {
-      w.X0 = fuse_X0->p; w.x0_s0 = fuse_X0->rs; w.x0_s1 = fuse_X0->cs; w.x0_pitch = fuse_X0->pitch; w.in0 = l.layer_in(0);
-      w.W0 = nr.base + l.w_off[0]; w.w0_s0 = nr.rs; w.w0_s1 = l.w_ms[0];
+      w.X0 = fuse_X0->z(); w.x0_pitch = fuse_X0->pitch; w.in0 = l.layer_in(0);
+      w.W0 = nr.w(0);
       if (l.ens) { w.w0_sn = 1; w.w0_sk = l.layer_out(0); } else { w.w0_sn = l.layer_in(0); w.w0_sk = 1; }
-      w.b0 = nr.base + l.b_off[0]; w.b0_s0 = nr.rs; w.b0_s1 = l.b_ms[0];
-      w.mb0 = X.bits; w.mb0_s0 = X.brs; w.mb0_s1 = X.bcs; w.mb0_g = X.bg;
+      w.b0 = nr.b(0);
+      w.mb0 = X.zbits(); w.mb0_g = X.bg;
       fused0 = ws_fwd01_supported(w) && aligned16(fuse_X0->p);
-      if (!fused0) w.X0 = nullptr;
+      if (!fused0) w.X0.p = nullptr;
       else if (fwd_only || (!want_tail && recompute_h0_ok(l, layer, M, nz))) w.x0_discard = 1;      // (a three-layer net's middle-layer wgrad rebuilds h0 from the input rows)
     }
     if (fuse_X0 && !fused0) {      // layer 0 on its own, then this layer
@@ -497,39 +518,29 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
       // precision 2: the fused first + second layer + tail forward of a many-row single-output net has a three-plane flavour (ws_fwd3.hip);
       // its two column halves leave two tail partial sums
       bool fwd3 = false;
-      if (p3(1) && (fused0 || !w.X0) && ws_dump && (!want_tail || ws.count("tq_scratch"))) {
+      if (p3(1) && (fused0 || !w.X0.p) && ws_dump && (!want_tail || ws.count("tq_scratch"))) {
         bool room = true;
         if (want_tail) {
           const Mat& sc = ws.at("tq_scratch");
           room = (long)M <= sc.cs && nr.nz1 <= tq_scratch_nets;
-          if (room) { w.tq2 = sc.p; w.tq2_s0 = sc.rs; w.tq2_s1 = sc.cs; }
+          if (room) w.tq2 = sc.zo();
         }
         if (room) {
           w.np3 = 1; w.dump = ws_dump;
           fwd3 = ws_fwd3_supported(w, in, out);
-          if (!fwd3) { w.np3 = 0; w.tq2 = nullptr; w.dump = nullptr; }
+          if (!fwd3) { w.np3 = 0; w.tq2.p = nullptr; w.dump = nullptr; }
         }
       }
       const double f0 = fused0 ? 2.0 * M * (double)in * (w.in0 + 1) * nz : 0.0;
-      prof_begin(fwd3 ? (std::string(tag) + "@p3").c_str() : tag, f0 + 2.0 * M * (double)out * (in + (want_tail ? 1 : 0)) * nz,
-                 4.0 * nz * ((fused0 ? (double)M * w.x0_pitch : 0.0) + (w.x0_discard ? (double)M * in / 32 : (double)M * in) + (double)out * in +
-                             (elide ? (double)M * out / 32 : (double)M * out)));
       if (fused0) bits_live.insert(X.bits);
       if (w.x0_discard) vals_dead.insert(X.p);
       else if (fused0) vals_dead.erase(X.p);
-      if (M >= 1024 && !fwd_only) w.lab_clk = (unsigned long long*)(aloss_part + (long)R * SB_MAXGROUPS * 2) + 64;      // (lab builds: the critic pass)
-      hipError_t err = fwd3 ? launch_ws_fwd3(w, nz, ws_blocks_per_problem(M / WS_ROWS, 2 * nz, 10, 1 << 20, ws_geo), stream) : launch_ws_fwd(w, nz, stream, ws_geo);
-      prof_end();
-      if (err != hipSuccess) return fail(std::string("ws_fwd launch ") + tag + ": " + hipGetErrorString(err));
-      if (fwd3 && want_tail) {
-        TailAddP t;
-        t.out = w.tq; t.o_s0 = w.tq_s0; t.o_s1 = w.tq_s1; t.o_sm = w.tq_sm;
-        t.part = w.tq2; t.p_s0 = w.tq2_s0; t.p_s1 = w.tq2_s1; t.p_ts = M; t.nparts = 1; t.M = M; t.nz1 = nr.nz1;
-        prof_begin((std::string(tag) + ".tail_add").c_str(), 0);
-        hipLaunchKernelGGL(k_tail_add, dim3((M + 255) / 256, nz), dim3(256), 0, stream, t);
-        prof_end();
-        if (hipGetLastError() != hipSuccess) return fail("tail_add launch");
-      }
+      if (M >= 1024 && !fwd_only) w.lab_clk = lab_clk(64);      // (lab builds: the critic pass)
+      if (timed("ws_fwd", tag, fwd3, f0 + 2.0 * M * (double)out * (in + (want_tail ? 1 : 0)) * nz,
+                4.0 * nz * ((fused0 ? (double)M * w.x0_pitch : 0.0) + (w.x0_discard ? (double)M * in / 32 : (double)M * in) + (double)out * in +
+                            (elide ? (double)M * out / 32 : (double)M * out)),
+                [&] { return fwd3 ? launch_ws_fwd3(w, nz, ws_blocks_per_problem(M / WS_ROWS, 2 * nz, 10, 1 << 20, ws_geo), stream) : launch_ws_fwd(w, nz, stream, ws_geo); })) return -1;
+      if (fwd3 && want_tail && tail_add(w.tq, w.tq_sm, w.tq2, 1, M, nr.nz1, tag)) return -1;
       bits_live.insert(Y.bits);
       if (elide) vals_dead.insert(Y.p);
       if (tail_fused) *tail_fused = want_tail;
@@ -548,12 +559,12 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
   if (tail_fused) *tail_fused = false;
   int tq_parts = 0;
   if (tail_out && tail_fused && epi == E_BIAS_RELU && layer == l.L - 1 && l.out_dim == 1 && !force_scalar && ws.count("tq_scratch")) {
-    const float* tw = nr.base + l.w_off[l.L];
-    tq_parts = tq_fused_parts(cfg, p, tw, nr.rs, l.w_ms[l.L]);
+    const ZPtr tw = nr.w(l.L);
+    tq_parts = tq_fused_parts(cfg, p, tw.p, tw.s0, tw.s1);
     const Mat& sc = ws.at("tq_scratch");
     if (tq_parts >= 1 && (long)(tq_parts - 1) * M <= sc.cs && nr.nz1 <= tq_scratch_nets) {
-      p.tq_w = {tw, nr.rs, l.w_ms[l.L]};
-      p.tq_b = {nr.base + l.b_off[l.L], nr.rs, l.b_ms[l.L]};
+      p.tq_w = tw;
+      p.tq_b = nr.b(l.L);
       p.tq_out = tail_out->p; p.tq_s0 = tail_out->rs; p.tq_s1 = tail_out->cs; p.tq_sm = tail_out->pitch;
       p.tq_part = sc.p; p.tq_ps0 = sc.rs; p.tq_ps1 = sc.cs; p.tq_ts = M;
       *tail_fused = true;
@@ -561,15 +572,7 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
   }
   if (tq_parts >= 1) {
     if (run_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_RELU>(this, cfg, p, nz, tag, a_kpad)) return -1;
-    if (tq_parts > 1) {
-      TailAddP t;
-      t.out = p.tq_out; t.o_s0 = p.tq_s0; t.o_s1 = p.tq_s1; t.o_sm = p.tq_sm;
-      t.part = p.tq_part; t.p_s0 = p.tq_ps0; t.p_s1 = p.tq_ps1; t.p_ts = p.tq_ts; t.nparts = tq_parts - 1; t.M = M; t.nz1 = nr.nz1;
-      prof_begin((std::string(tag) + ".tail_add").c_str(), 0);
-      hipLaunchKernelGGL(k_tail_add, dim3((M + 255) / 256, nz), dim3(256), 0, stream, t);
-      prof_end();
-      if (hipGetLastError() != hipSuccess) return fail("tail_add launch");
-    }
+    if (tq_parts > 1) return tail_add(tail_out->zo(), tail_out->pitch, ws.at("tq_scratch").zo(), tq_parts - 1, M, nr.nz1, tag);
     return 0;
   }
   switch (epi) {
@@ -580,6 +583,44 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
   }
 }
 
+// Weight-stationary dgrad into the first hidden activation (mask words maskH).  Incoming gradient: dy.rank1 -> (mask words of the top activation,
+// dq, w_tail), else the materialised dz1 (PLAIN).  Result: w0_X != null -> the layer-0 gradient slabs (*slabs, one per workgroup), else dz0
+// stored to dX.  max_blocks caps the workgroups per net.  Returns 1 when the kernels do not serve the shape (nothing enqueued), else 0 / -1.
+int Engine::ws_dgrad(const DY& dy, int M, const NetRef& nr, int layer, const Mat& maskH, const Mat* w0_X, const Mat* dX, int max_blocks,
+                     const char* tag, int* slabs) {
+  const NetLayout& l = *nr.lay;
+  const int in = l.layer_in(layer), out = l.layer_out(layer), nz = R * nr.nz1;
+  WsDgradP w;
+  memset(&w, 0, sizeof(w));
+  if (dy.rank1) {
+    w.abits = dy.m.zbits(); w.ab_g = dy.m.bg;
+    w.dq = dy.rowv.z(); w.dq_sm = dy.rowv.pitch;
+    w.wt = nr.w(l.L);
+  } else { w.Z = dy.m.z(); w.z_pitch = dy.m.pitch; }
+  w.xbits = maskH.zbits(); w.xb_g = maskH.bg;
+  w.W = nr.w(layer);
+  // nn.Linear keeps (out, in)-major weights, EnsembleLinear (in, out)-major ones: the same holds for the gradient slabs
+  if (l.ens) { w.w_sn = out; w.w_sk = 1; } else { w.w_sn = 1; w.w_sk = in; }
+  if (w0_X) {
+    w.X = w0_X->z(); w.x_pitch = w0_X->pitch; w.in0 = l.layer_in(0);
+    float* g = grads + nr.g_off;
+    w.w0_out = g + l.w_off[0]; w.b0_out = g + l.b_off[0];
+    w.o_rs = (long)max_slab * P_train; w.o_ms = l.w_ms[0]; w.ob_ms = l.b_ms[0]; w.o_ks = P_train;
+    if (l.ens) { w.o_sr = 1; w.o_sc = l.layer_out(0); } else { w.o_sr = l.layer_in(0); w.o_sc = 1; }
+    w.gscale = cur_gscale;
+  } else { w.C = dX->zo(); w.c_pitch = dX->pitch; }      // (no dynamic scale: the stored values are the true ones)
+  w.M = M; w.nz1 = nr.nz1; w.f32 = ws_f32();
+  if (!ws_dgrad_supported(w, out, in)) return 1;
+  const bool d3 = p3(2) && ws_dgrad3_supported(w, out, in);      // precision 2: three planes, two workgroups (column halves) per slab
+  const int per_z = ws_dgrad_blocks(M, d3 ? 2 * nz : nz, max_blocks, ws_geo);
+  const double flops = 2.0 * M * (double)in * (out + (w0_X ? w.in0 + 1 : 0)) * nz;
+  const double bytes = nz * (4.0 * in * out + (dy.rank1 ? M * (double)(in + out) / 8 : 4.0 * M * (double)out + M * (double)in / 8) +
+                             (w0_X ? 4.0 * M * (w.x_pitch + 1) + 4.0 * per_z * in * (w.in0 + 1) : 4.0 * M * (in + 1)));
+  if (timed("ws_dgrad", tag, d3, flops, bytes, [&] { return d3 ? launch_ws_dgrad3_w0(w, nz, per_z, stream) : launch_ws_dgrad_w0(w, nz, per_z, stream); })) return -1;
+  if (slabs) *slabs = per_z;
+  return 0;
+}
+
 int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int col0, int ncols, const Mat* maskH,
                          const Mat& dX, const char* tag, const Mat* w0_X, bool store_dx, int* w0_slabs) {
   const NetLayout& l = *nr.lay;
@@ -588,19 +629,20 @@ int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int c
   memset(&p, 0, sizeof(p));
   p.a_dscale = cur_gscale; p.b_scale = ORL_WSCALE;     // split precision: A = a gradient matrix of the current backward pass, B = weights
   if (mm_prec() == P_SPLIT3) p.a_scale = ORL_GSCALE3;   // three planes: 2^5 more headroom above fp16's 2^-24 grid for the matrix's small elements
-  p.A = {dy.m.p, dy.m.rs, dy.m.cs};
+  p.A = dy.m.z();
   p.a_sr = dy.m.pitch; p.a_sk = 1;
   if (dy.rank1) {
     p.a_trans = 0;
-    p.rowv = {dy.rowv.p, dy.rowv.rs, dy.rowv.cs};
-    p.colv = {nr.base + l.w_off[l.L], nr.rs, l.w_ms[l.L]};
+    p.rowv = dy.rowv.z();
+    p.colv = nr.w(l.L);
   }
-  if (l.ens) { p.B = {nr.base + l.w_off[layer] + (long)col0 * out, nr.rs, l.w_ms[layer]}; p.b_sr = out; p.b_sk = 1; }
-  else { p.B = {nr.base + l.w_off[layer] + col0, nr.rs, l.w_ms[layer]}; p.b_sr = 1; p.b_sk = in; p.b_rlim = (in - col0) & ~3; }
+  p.B = nr.w(layer);
+  if (l.ens) { p.B.p += (long)col0 * out; p.b_sr = out; p.b_sk = 1; }
+  else { p.B.p += col0; p.b_sr = 1; p.b_sk = in; p.b_rlim = (in - col0) & ~3; }
   p.C = dX.p; p.c_s0 = dX.rs; p.c_s1 = dX.cs; p.c_sr = dX.pitch; p.c_sn = 1;
   p.M = M; p.N = ncols; p.K = out;
   p.nz1 = nr.nz1; p.ksplit = 1;
-  if (maskH) { p.aux = {maskH->p, maskH->rs, maskH->cs}; p.aux_sr = maskH->pitch; }
+  if (maskH) { p.aux = maskH->z(); p.aux_sr = maskH->pitch; }
   const int nz = R * nr.nz1;
   if (w0_slabs) *w0_slabs = 0;
   if (maskH && maskH->bits && bits_live.count(maskH->bits) && ncols == maskH->pitch && aligned16(maskH->p) && (maskH->pitch & 3) == 0) {
@@ -610,88 +652,28 @@ int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int c
   if (w0_X && w0_slabs && !store_dx && maskH && dy.rank1 && layer == 1 && col0 == 0 && !l.ens && !force_scalar &&
       ws_precision_ok() && p.aux_bits && dy.m.bits && bits_live.count(dy.m.bits) && out == dy.m.pitch &&
       ncols == in && (long)M * nz >= ws_bwd_min_rows) {
-    WsDgradP w;
-    memset(&w, 0, sizeof(w));
-    w.abits = dy.m.bits; w.ab_s0 = dy.m.brs; w.ab_s1 = dy.m.bcs; w.ab_g = dy.m.bg;
-    w.xbits = maskH->bits; w.xb_s0 = maskH->brs; w.xb_s1 = maskH->bcs; w.xb_g = maskH->bg;
-    w.dq = dy.rowv.p; w.dq_s0 = dy.rowv.rs; w.dq_s1 = dy.rowv.cs; w.dq_sm = dy.rowv.pitch;
-    w.wt = nr.base + l.w_off[l.L]; w.wt_s0 = nr.rs; w.wt_s1 = l.w_ms[l.L];
-    w.W = nr.base + l.w_off[layer]; w.w_s0 = nr.rs; w.w_s1 = l.w_ms[layer]; w.w_sn = 1; w.w_sk = in;
-    w.X = w0_X->p; w.x_s0 = w0_X->rs; w.x_s1 = w0_X->cs; w.x_pitch = w0_X->pitch; w.in0 = l.layer_in(0);
-    float* g = grads + nr.g_off;
-    w.w0_out = g + l.w_off[0]; w.b0_out = g + l.b_off[0];
-    w.o_s0 = (long)max_slab * P_train; w.o_s1 = l.w_ms[0]; w.ob_s1 = l.b_ms[0]; w.o_ks = P_train; w.o_sr = l.layer_in(0); w.o_sc = 1;
-    w.M = M; w.nz1 = nr.nz1; w.f32 = this->ws_f32(); w.gscale = cur_gscale;
-    if (ws_dgrad_supported(w, out, in)) {
-      const bool d3 = p3(2) && ws_dgrad3_supported(w, out, in);      // precision 2: three planes, two workgroups (column halves) per slab
-      const int per_z = ws_dgrad_blocks(M, d3 ? 2 * nz : nz, max_slab, ws_geo);
-      prof_begin(d3 ? (std::string(tag) + "@p3").c_str() : tag, 2.0 * M * (double)in * (out + l.layer_in(0) + 1) * nz,
-                 nz * (4.0 * in * out + M * (double)(in + out) / 8 + 4.0 * M * (w0_X->pitch + 1) + 4.0 * per_z * in * (l.layer_in(0) + 1)));
-      hipError_t err = d3 ? launch_ws_dgrad3_w0(w, nz, per_z, stream) : launch_ws_dgrad_w0(w, nz, per_z, stream);
-      prof_end();
-      if (err != hipSuccess) return fail(std::string("ws_dgrad launch ") + tag + ": " + hipGetErrorString(err));
-      *w0_slabs = per_z;
-      return 0;
-    }
+    const int rc = ws_dgrad(dy, M, nr, layer, *maskH, w0_X, nullptr, max_slab, tag, w0_slabs);
+    if (rc <= 0) return rc;
   }
   // same kernel, storing variant (no layer-0 gradient): e.g. the critic backward of the actor loss, where dz0 feeds dL/da
   if (!(w0_X && w0_slabs) && maskH && dy.rank1 && col0 == 0 && !force_scalar && ws_precision_ok() && p.aux_bits &&
       dy.m.bits && bits_live.count(dy.m.bits) && out == dy.m.pitch && ncols == in && dX.pitch >= in && (long)M * nz >= ws_bwd_min_rows) {
-    WsDgradP w;
-    memset(&w, 0, sizeof(w));
-    w.abits = dy.m.bits; w.ab_s0 = dy.m.brs; w.ab_s1 = dy.m.bcs; w.ab_g = dy.m.bg;
-    w.xbits = maskH->bits; w.xb_s0 = maskH->brs; w.xb_s1 = maskH->bcs; w.xb_g = maskH->bg;
-    w.dq = dy.rowv.p; w.dq_s0 = dy.rowv.rs; w.dq_s1 = dy.rowv.cs; w.dq_sm = dy.rowv.pitch;
-    w.wt = nr.base + l.w_off[l.L]; w.wt_s0 = nr.rs; w.wt_s1 = l.w_ms[l.L];
-    w.W = nr.base + l.w_off[layer]; w.w_s0 = nr.rs; w.w_s1 = l.w_ms[layer];
-    if (l.ens) { w.w_sn = out; w.w_sk = 1; } else { w.w_sn = 1; w.w_sk = in; }
-    w.C = dX.p; w.c_s0 = dX.rs; w.c_s1 = dX.cs; w.c_pitch = dX.pitch;
-    w.M = M; w.nz1 = nr.nz1; w.f32 = this->ws_f32();
-    if (ws_dgrad_supported(w, out, in)) {
-      const bool d3 = p3(2) && ws_dgrad3_supported(w, out, in);      // precision 2: three planes, two workgroups (column halves) per net
-      const int per_z = ws_dgrad_blocks(M, d3 ? 2 * nz : nz, 1 << 20, ws_geo);
-      prof_begin(d3 ? (std::string(tag) + "@p3").c_str() : tag, 2.0 * M * (double)in * out * nz, nz * (4.0 * in * out + M * (double)(in + out) / 8 + 4.0 * M * (in + 1)));
-      hipError_t err = d3 ? launch_ws_dgrad3_w0(w, nz, per_z, stream) : launch_ws_dgrad_w0(w, nz, per_z, stream);
-      prof_end();
-      if (err != hipSuccess) return fail(std::string("ws_dgrad launch ") + tag + ": " + hipGetErrorString(err));
-      return 0;
-    }
+    const int rc = ws_dgrad(dy, M, nr, layer, *maskH, nullptr, &dX, 1 << 20, tag, nullptr);
+    if (rc <= 0) return rc;
   }
   // the same fused kernel fed with a MATERIALISED gradient (a three-layer net's middle layer): dz0 = 1[h0 > 0] (dz1 W1) never leaves the
   // registers, dW0 / db0 come out as one slab per workgroup
   if (w0_X && w0_slabs && !store_dx && maskH && !dy.rank1 && layer == 1 && col0 == 0 && !force_scalar && ws_precision_ok() &&
       p.aux_bits && dy.m.pitch == out && ncols == in && (long)M * nz >= ws_dgrad_plain_min_rows) {
-    WsDgradP w;
-    memset(&w, 0, sizeof(w));
-    w.Z = dy.m.p; w.z_s0 = dy.m.rs; w.z_s1 = dy.m.cs; w.z_pitch = dy.m.pitch;
-    w.xbits = maskH->bits; w.xb_s0 = maskH->brs; w.xb_s1 = maskH->bcs; w.xb_g = maskH->bg;
-    w.W = nr.base + l.w_off[layer]; w.w_s0 = nr.rs; w.w_s1 = l.w_ms[layer];
-    w.X = w0_X->p; w.x_s0 = w0_X->rs; w.x_s1 = w0_X->cs; w.x_pitch = w0_X->pitch; w.in0 = l.layer_in(0);
-    float* g = grads + nr.g_off;
-    w.w0_out = g + l.w_off[0]; w.b0_out = g + l.b_off[0];
-    w.o_s0 = (long)max_slab * P_train; w.o_s1 = l.w_ms[0]; w.ob_s1 = l.b_ms[0]; w.o_ks = P_train;
-    // nn.Linear keeps (out, in)-major weights, EnsembleLinear (in, out)-major ones: the same holds for the gradient slabs
-    if (l.ens) { w.w_sn = out; w.w_sk = 1; w.o_sr = 1; w.o_sc = l.layer_out(0); }
-    else { w.w_sn = 1; w.w_sk = in; w.o_sr = l.layer_in(0); w.o_sc = 1; }
-    w.M = M; w.nz1 = nr.nz1; w.f32 = this->ws_f32(); w.gscale = cur_gscale;
-    if (ws_dgrad_supported(w, out, in)) {
-      const bool d3 = p3(2) && ws_dgrad3_supported(w, out, in);      // precision 2: three planes of dz1 and of W1
-      const int per_z = ws_dgrad_blocks(M, d3 ? 2 * nz : nz, max_slab, ws_geo);
-      prof_begin(d3 ? (std::string(tag) + "@p3").c_str() : tag, 2.0 * M * (double)in * (out + l.layer_in(0) + 1) * nz,
-                 nz * (4.0 * in * out + 4.0 * M * (double)out + M * (double)in / 8 + 4.0 * M * (w0_X->pitch + 1) + 4.0 * per_z * in * (l.layer_in(0) + 1)));
-      hipError_t err = d3 ? launch_ws_dgrad3_w0(w, nz, per_z, stream) : launch_ws_dgrad_w0(w, nz, per_z, stream);
-      prof_end();
-      if (err != hipSuccess) return fail(std::string("ws_dgrad launch ") + tag + ": " + hipGetErrorString(err));
-      *w0_slabs = per_z;
-      return 0;
-    }
+    const int rc = ws_dgrad(dy, M, nr, layer, *maskH, w0_X, nullptr, max_slab, tag, w0_slabs);
+    if (rc <= 0) return rc;
   }
   if (w0_X && w0_slabs && maskH && layer == 1 && col0 == 0 && !l.ens && !force_scalar) {
     // fuse the layer-0 weight / bias gradient into this launch's epilogue (one slab per row tile)
     const int slabs = w0_fused_slabs(p, nz, l.layer_in(0), w0_X->pitch, w0_X->p, w0_X->rs, w0_X->cs, max_slab);
     if (slabs > 0) {
       float* g = grads + nr.g_off;
-      p.w0_x = {w0_X->p, w0_X->rs, w0_X->cs}; p.w0_xsr = w0_X->pitch; p.w0_in = l.layer_in(0);
+      p.w0_x = w0_X->z(); p.w0_xsr = w0_X->pitch; p.w0_in = l.layer_in(0);
       p.w0_out = g + l.w_off[0]; p.w0_bias = g + l.b_off[0];
       p.w0_s0 = (long)max_slab * P_train; p.w0_s1 = l.w_ms[0]; p.w0_bs1 = l.b_ms[0]; p.w0_ks = P_train; p.w0_sr = l.layer_in(0);
       if (!store_dx) p.C = nullptr;
@@ -702,22 +684,11 @@ int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int c
   // in gradient mode (B = the weights viewed transposed, epilogue = mask from bits)
   if (!dy.rank1 && !p.w0_out && maskH && p.aux_bits && col0 == 0 && ncols == in && ws_precision_ok() && !force_scalar &&
       dy.m.pitch == out && dX.pitch == in && (long)M * nz >= ws_bwd_min_rows) {
-    WsFwdP w;
-    memset(&w, 0, sizeof(w));
-    w.X = dy.m.p; w.x_s0 = dy.m.rs; w.x_s1 = dy.m.cs; w.x_pitch = dy.m.pitch;
-    w.W = nr.base + l.w_off[layer]; w.w_s0 = nr.rs; w.w_s1 = l.w_ms[layer];
-    // B[n = input unit][k = output unit]: nn.Linear W (out, in) -> element (k, n) at k * in + n; EnsembleLinear (in, out) -> n * out + k
-    if (l.ens) { w.w_sn = out; w.w_sk = 1; } else { w.w_sn = 1; w.w_sk = in; }
-    w.Y = dX.p; w.y_s0 = dX.rs; w.y_s1 = dX.cs; w.y_pitch = dX.pitch;
-    w.dmask = maskH->bits; w.dm_s0 = maskH->brs; w.dm_s1 = maskH->bcs; w.dm_g = maskH->bg;
-    w.M = M; w.nz1 = nr.nz1; w.f32 = this->ws_f32(); w.gscale = cur_gscale;
+    const WsFwdP w = ws_fwd_p(dy.m, M, nr, layer, dX, maskH);
     if (ws_fwd_supported(w, out, in)) {
       const bool f3 = p3(2) && ws_fwd3_supported(w, out, in);       // precision 2: three planes of dz and of the weights (column halves)
-      prof_begin(f3 ? (std::string(tag) + "@p3").c_str() : tag, 2.0 * M * (double)in * out * nz, nz * (4.0 * M * out + 4.0 * in * out + 4.0 * M * in + M * (double)in / 8));
-      hipError_t err = f3 ? launch_ws_fwd3(w, nz, ws_blocks_per_problem(M / WS_ROWS, 2 * nz, 10, 1 << 20, ws_geo), stream) : launch_ws_fwd(w, nz, stream, ws_geo);
-      prof_end();
-      if (err != hipSuccess) return fail(std::string("ws dgrad launch ") + tag + ": " + hipGetErrorString(err));
-      return 0;
+      return timed("ws dgrad", tag, f3, 2.0 * M * (double)in * out * nz, nz * (4.0 * M * out + 4.0 * in * out + 4.0 * M * in + M * (double)in / 8),
+                   [&] { return f3 ? launch_ws_fwd3(w, nz, ws_blocks_per_problem(M / WS_ROWS, 2 * nz, 10, 1 << 20, ws_geo), stream) : launch_ws_fwd(w, nz, stream, ws_geo); });
     }
   }
   if (dy.rank1) {
@@ -730,11 +701,7 @@ int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int c
         const double flops = 2.0 * q.M * (double)q.N * q.K * nz + (q.w0_out ? 2.0 * q.M * (double)q.N * (q.w0_in + 1) * nz : 0.0);
         const double bytes = nz * (4.0 * q.N * q.K + q.M * (double)q.K / 8 + (q.C ? 4.0 * q.M * q.N : 0.0) +
                                    (q.aux_bits ? q.M * (double)q.N / 8 : 4.0 * q.M * q.N) + (q.w0_out ? 4.0 * q.M * q.w0_xsr : 0.0));
-        prof_begin(tag, flops, bytes);
-        hipError_t err = launch_gemm_rank1_bits<E_MASK>(tcfg, q, nz, stream, this->mm_prec());
-        prof_end();
-        if (err != hipSuccess) return fail(std::string("gemm launch ") + tag + ": " + hipGetErrorString(err));
-        return 0;
+        return timed("gemm", tag, false, flops, bytes, [&] { return launch_gemm_rank1_bits<E_MASK>(tcfg, q, nz, stream, mm_prec()); });
       }
     }
     if (vals_dead.count(dy.m.p)) return fail(std::string("dgrad ") + tag + ": the activation values were not stored by the forward pass");
@@ -746,7 +713,7 @@ int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int c
 }
 
 // split-K factor for a weight gradient: enough workgroups to fill 256 CUs, chunk aligned
-static int wgrad_ksplit(int Mout, int Nout, int Krows, int nz, int cap) {
+int Engine::wgrad_ksplit(int Mout, int Nout, int Krows, int nz) const {
   const int cfg = pick_cfg(Mout, Nout, Krows, nz);
   int TM, TN, TK;
   switch (cfg) {
@@ -759,20 +726,61 @@ static int wgrad_ksplit(int Mout, int Nout, int Krows, int nz, int cap) {
   }
   const int tiles = ((Mout + TM - 1) / TM) * ((Nout + TN - 1) / TN) * nz;
   const int kchunks = (Krows + TK - 1) / TK;
-  static const int target = [] { const char* f = getenv("ORL_WGRAD_WG_TARGET"); return (f && atoi(f) > 0) ? atoi(f) : 512; }();
-  static const int long_min = [] { const char* f = getenv("ORL_WGRAD_LONG_MIN"); return (f && atoi(f) > 0) ? atoi(f) : 4; }();
-  int ks = (target + tiles - 1) / tiles;
+  int ks = (wgrad_wg_target + tiles - 1) / tiles;
   // many batched nets fill the CUs without split-K, but workgroups that all stream thousands of rows from the same offset of
   // equally strided matrices run 2x slower (measured at 256 nets x 7936 rows, fp32: 12.8 -> 5.4 ms): keep >= 4 k-ranges
-  if (Krows >= 4096) ks = std::max(ks, long_min);
-  static const int small_ks = [] { const char* f = getenv("ORL_WGRAD_SMALL_KS"); return (f && atoi(f) > 0) ? atoi(f) : 1; }();
+  if (Krows >= 4096) ks = std::max(ks, wgrad_long_min);
   // 256-row wgrads of many nets: round 2 measured two k-ranges 1.5x faster than one -- with the item-major workgroup mapping, where the four
   // tiles of a net sat on four XCDs.  With the z-major mapping (gemm_kernel.h) one range wins: EDAC 15.4k -> 16.9k steps/s, IQL +2.5 %,
   // TD3+BC +2.5 % at 128 runs (Adam reads half the slabs).  ORL_WGRAD_SMALL_KS=2 restores the old rule for A/B runs.
-  if (cfg == CFG_SQ && Krows < 1024 && kchunks >= 8) ks = std::max(ks, small_ks);
-  ks = std::max(1, std::min(ks, std::min(cap, kchunks)));
+  if (cfg == CFG_SQ && Krows < 1024 && kchunks >= 8) ks = std::max(ks, wgrad_small_ks);
+  ks = std::max(1, std::min(ks, std::min(ksplit_cap, kchunks)));
   while (ks > 1 && (kchunks + ks - 1) / ks < 2) --ks;
   return ks;
+}
+
+// Output-stationary wgrad, one split-K slab per workgroup from slab 0 (*slabs).  dy.rank1: the top hidden layer -- dz^T from the packed ReLU mask,
+// G = dq (.) X; the tail layer's gradients ride along, from the activation streamed through registers or, if the forward did not store it, derived
+// from the accumulators.  Else dy.m = a materialised dZ; recompute_X0 != null: X is rebuilt from the net's input rows.  Returns as ws_dgrad.
+int Engine::ws_wgrad(const DY& dy, const Mat& X, int M, const NetRef& nr, int layer, const Mat* recompute_X0, const char* tag, int* slabs) {
+  const NetLayout& l = *nr.lay;
+  const int in = l.layer_in(layer), out = l.layer_out(layer), nz = R * nr.nz1;
+  const bool derived = dy.rank1 && vals_dead.count(dy.m.p) > 0;
+  float* g = grads + nr.g_off;
+  WsWgradP w;
+  memset(&w, 0, sizeof(w));
+  w.H0 = X.z(); w.h0_pitch = X.pitch;
+  w.dW = g + l.w_off[layer]; w.db = g + l.b_off[layer];
+  w.o_rs = (long)max_slab * P_train; w.o_msw = l.w_ms[layer]; w.o_msb = l.b_ms[layer]; w.o_ks = P_train;
+  if (dy.rank1) {
+    w.abits = dy.m.zbits(); w.ab_g = dy.m.bg;
+    w.dq = dy.rowv.z(); w.dq_sm = dy.rowv.pitch;
+    w.wt = nr.w(l.L);
+    if (derived) { w.W1 = nr.w(layer); w.b1 = nr.b(layer); }
+    else { w.H1 = dy.m.z(); w.h1_pitch = dy.m.pitch; }
+    w.dwt = g + l.w_off[l.L]; w.dbt = g + l.b_off[l.L]; w.o_mswt = l.w_ms[l.L]; w.o_msbt = l.b_ms[l.L];
+    w.np3 = p3(4) && derived;                                        // precision 2: three planes of G = dq (.) h0 (ws_wgrad_kernel<5>)
+    w.lab_clk = lab_clk(72);
+  } else {
+    w.dZ = dy.m.z(); w.dz_pitch = dy.m.pitch;
+    if (recompute_X0) {                            // h0 = relu(X0 W0^T + b0) is rebuilt inside the launch
+      w.X0 = recompute_X0->z(); w.x0_pitch = recompute_X0->pitch; w.in0 = l.layer_in(0);
+      w.W0 = nr.w(0); w.w0_sn = l.layer_in(0); w.w0_sk = 1;
+      w.b0 = nr.b(0);
+    }
+  }
+  w.M = M; w.nz1 = nr.nz1; w.f32 = ws_f32(); w.gscale = cur_gscale;
+  if (!ws_wgrad_supported(w, out, in)) return 1;
+  const bool w3 = !dy.rank1 && p3(4) && ws_wgrad3p_supported(w, out, in);      // precision 2: three planes of dZ and of H0, two workgroups (halves of the output rows) per slab
+  // one round (prologue 1 << 20): the slab write + derived tail gradients per workgroup cost more than idle CUs (4 slabs at 192 nets: 540 us
+  // either way, and Adam then reads 4 slabs)
+  const int per_z = ws_dgrad_blocks(M, w3 ? 2 * nz : nz, dy.rank1 ? ws_wgrad_slab_cap : max_slab, ws_geo, 1 << 20);
+  const double flops = 2.0 * M * (double)in * (dy.rank1 ? out + 2 : out + 1 + (recompute_X0 ? w.in0 + 1 : 0)) * nz;
+  const double bytes = dy.rank1 ? nz * ((derived ? M * (double)out / 8 : 4.0 * M * (double)out) + 4.0 * M * (in + 1) + 4.0 * per_z * out * (in + 2))
+                                : nz * (4.0 * M * (double)((recompute_X0 ? w.x0_pitch : in) + out) + 4.0 * per_z * out * (in + 1));
+  if (timed("ws_wgrad", tag, w3 || w.np3, flops, bytes, [&] { return w3 ? launch_ws_wgrad3p(w, nz, per_z, stream) : launch_ws_wgrad(w, nz, per_z, stream); })) return -1;
+  *slabs = per_z;
+  return 0;
 }
 
 // slabs_out: number of split-K slabs actually written (== ksplit unless the weight-stationary kernel chose its own decomposition)
@@ -788,15 +796,15 @@ int Engine::linear_wgrad(const DY& dy, const Mat& X, int M, const NetRef& nr, in
   memset(&p, 0, sizeof(p));
   p.a_dscale = cur_gscale; p.b_dscale = x_dscale;      // split precision: A = dY^T of the current backward pass; B = X (an activation, or a gradient-like matrix with its own scale)
   if (mm_prec() == P_SPLIT3) { p.a_scale = ORL_GSCALE3; if (x_dscale) p.b_scale = ORL_GSCALE3; }
-  p.A = {dy.m.p, dy.m.rs, dy.m.cs};
+  p.A = dy.m.z();
   p.a_sr = 1; p.a_sk = dy.m.pitch;
   if (out == 1 && dy.m.pitch == 1 && !dy.rank1) p.a_sr = 4;   // a [1 x M] row vector: k-contiguous, any row stride -> vector loads
   if (dy.rank1) {
     p.a_trans = 1;
-    p.rowv = {dy.rowv.p, dy.rowv.rs, dy.rowv.cs};
-    p.colv = {nr.base + l.w_off[l.L], nr.rs, l.w_ms[l.L]};
+    p.rowv = dy.rowv.z();
+    p.colv = nr.w(l.L);
   }
-  p.B = {X.p, X.rs, X.cs};
+  p.B = X.z();
   p.b_sr = 1; p.b_sk = X.pitch;
   p.a_rlim = dy.m.pitch & ~3; p.b_rlim = X.pitch & ~3;
   p.ones_row = 1 << 30;
@@ -815,64 +823,16 @@ int Engine::linear_wgrad(const DY& dy, const Mat& X, int M, const NetRef& nr, in
   if (slabs_out && fuse_tail && dy.rank1 && with_bias && slab0 == 0 && ws_precision_ok() && !force_scalar && !l.ens &&
       dy.m.bits && bits_live.count(dy.m.bits) && out == dy.m.pitch && in_row0 == 0 && in_rows == in && X.pitch == in &&
       ws_wgrad_rows_ok(M, nz)) {
-    const bool derived = vals_dead.count(dy.m.p) > 0;
-    WsWgradP w;
-    memset(&w, 0, sizeof(w));
-    w.abits = dy.m.bits; w.ab_s0 = dy.m.brs; w.ab_s1 = dy.m.bcs; w.ab_g = dy.m.bg;
-    w.dq = dy.rowv.p; w.dq_s0 = dy.rowv.rs; w.dq_s1 = dy.rowv.cs; w.dq_sm = dy.rowv.pitch;
-    w.H0 = X.p; w.h0_s0 = X.rs; w.h0_s1 = X.cs; w.h0_pitch = X.pitch;
-    w.wt = nr.base + l.w_off[l.L]; w.wt_s0 = nr.rs; w.wt_s1 = l.w_ms[l.L];
-    w.dW = g + l.w_off[layer]; w.db = g + l.b_off[layer];
-    w.o_s0 = g_rs; w.o_s1w = l.w_ms[layer]; w.o_s1b = l.b_ms[layer]; w.o_ks = P_train;
-    // the activation values are streamed through registers as well: tail-layer gradients (and db) from the same pass, same slabs
-    // (or, when the forward pass did not store h1, derived from the accumulators: see WsWgradP)
-    if (derived) {
-      w.W1 = nr.base + l.w_off[layer]; w.w1_s0 = nr.rs; w.w1_s1 = l.w_ms[layer];
-      w.b1 = nr.base + l.b_off[layer]; w.b1_s0 = nr.rs; w.b1_s1 = l.b_ms[layer];
-    } else { w.H1 = dy.m.p; w.h1_s0 = dy.m.rs; w.h1_s1 = dy.m.cs; w.h1_pitch = dy.m.pitch; }
-    w.dwt = g + l.w_off[l.L]; w.dbt = g + l.b_off[l.L]; w.o_s1wt = l.w_ms[l.L]; w.o_s1bt = l.b_ms[l.L];
-    w.M = M; w.nz1 = nr.nz1; w.f32 = this->ws_f32(); w.gscale = cur_gscale;
-    w.np3 = p3(4) && derived;                                        // precision 2: three planes of G = dq (.) h0 (ws_wgrad_kernel<5>)
-    if (ws_wgrad_supported(w, out, in)) {
-      const int per_z = ws_dgrad_blocks(M, nz, ws_wgrad_slab_cap, ws_geo, 1 << 20);      // one round: the slab write + derived tail gradients per workgroup cost more than idle CUs (4 slabs at 192 nets: 540 us either way, and Adam then reads 4 slabs)
-      prof_begin(w.np3 ? (std::string(tag) + "@p3").c_str() : tag, 2.0 * M * (double)in * (out + 2) * nz,
-                 nz * ((derived ? M * (double)out / 8 : 4.0 * M * (double)out) + 4.0 * M * (in + 1) + 4.0 * per_z * out * (in + 2)));
-      w.lab_clk = (unsigned long long*)(aloss_part + (long)R * SB_MAXGROUPS * 2) + 72;
-      hipError_t err = launch_ws_wgrad(w, nz, per_z, stream);
-      prof_end();
-      if (err != hipSuccess) return fail(std::string("ws_wgrad launch ") + tag + ": " + hipGetErrorString(err));
-      *fuse_tail = true;
-      *slabs_out = per_z;
-      return 0;
-    }
+    const int rc = ws_wgrad(dy, X, M, nr, layer, nullptr, tag, slabs_out);
+    if (rc == 0) *fuse_tail = true;
+    if (rc <= 0) return rc;
   }
   // the same output-stationary kernel for a hidden layer BELOW the top one of a many-row batch: dZ is a materialised matrix (three products
   // per block instead of the rank-1 form's two, no mask / w_tail); one slab per workgroup
   if (slabs_out && !dy.rank1 && with_bias && slab0 == 0 && ws_precision_ok() && !force_scalar && !l.ens && !x_dscale && in_row0 == 0 &&
       in_rows == in && X.pitch == in && dy.m.pitch == out && ws_wgrad_rows_ok(M, nz)) {
-    WsWgradP w;
-    memset(&w, 0, sizeof(w));
-    w.dZ = dy.m.p; w.dz_s0 = dy.m.rs; w.dz_s1 = dy.m.cs; w.dz_pitch = dy.m.pitch;
-    w.H0 = X.p; w.h0_s0 = X.rs; w.h0_s1 = X.cs; w.h0_pitch = X.pitch;
-    if (x_dead) {                                  // h0 = relu(X0 W0^T + b0) is rebuilt inside the launch
-      w.X0 = recompute_X0->p; w.x0_s0 = recompute_X0->rs; w.x0_s1 = recompute_X0->cs; w.x0_pitch = recompute_X0->pitch; w.in0 = l.layer_in(0);
-      w.W0 = nr.base + l.w_off[0]; w.w0_s0 = nr.rs; w.w0_s1 = l.w_ms[0]; w.w0_sn = l.layer_in(0); w.w0_sk = 1;
-      w.b0 = nr.base + l.b_off[0]; w.b0_s0 = nr.rs; w.b0_s1 = l.b_ms[0];
-    }
-    w.dW = g + l.w_off[layer]; w.db = g + l.b_off[layer];
-    w.o_s0 = g_rs; w.o_s1w = l.w_ms[layer]; w.o_s1b = l.b_ms[layer]; w.o_ks = P_train;
-    w.M = M; w.nz1 = nr.nz1; w.f32 = this->ws_f32(); w.gscale = cur_gscale;
-    if (ws_wgrad_supported(w, out, in)) {
-      const bool w3 = p3(4) && ws_wgrad3p_supported(w, out, in);      // precision 2: three planes of dZ and of H0, two workgroups (halves of the output rows) per slab
-      const int per_z = ws_dgrad_blocks(M, w3 ? 2 * nz : nz, max_slab, ws_geo, 1 << 20);
-      prof_begin(w3 ? (std::string(tag) + "@p3").c_str() : tag, 2.0 * M * (double)in * (out + 1 + (x_dead ? w.in0 + 1 : 0)) * nz,
-                 nz * (4.0 * M * (double)((x_dead ? w.x0_pitch : in) + out) + 4.0 * per_z * out * (in + 1)));
-      hipError_t err = w3 ? launch_ws_wgrad3p(w, nz, per_z, stream) : launch_ws_wgrad(w, nz, per_z, stream);
-      prof_end();
-      if (err != hipSuccess) return fail(std::string("ws_wgrad launch ") + tag + ": " + hipGetErrorString(err));
-      *slabs_out = per_z;
-      return 0;
-    }
+    const int rc = ws_wgrad(dy, X, M, nr, layer, x_dead ? recompute_X0 : nullptr, tag, slabs_out);
+    if (rc <= 0) return rc;
   }
   if (x_dead) return fail(std::string("wgrad ") + tag + ": the input activation was not stored and the recomputing kernel does not serve this shape");
   if (dy.rank1 && vals_dead.count(dy.m.p)) return fail(std::string("wgrad ") + tag + ": the activation values were not stored by the forward pass");
@@ -934,6 +894,23 @@ int Engine::assemble(const Mat& obs, const Mat* act, const Mat& X, int row0, int
   return 0;
 }
 
+// the whole [in0 -> 256 -> 256 -> out] pass of few batched rows as one launch (small_fwd.h); H0 / H1 null: the hidden activations are not stored.
+// The caller adds the sampling jobs or the QG mode's gradient output.
+SmallFwdP Engine::small_fwd_p(const Mat& X, int M, const NetRef& nr, const Mat* H0, const Mat* H1, const Mat& out) const {
+  const NetLayout& l = *nr.lay;
+  SmallFwdP w;
+  memset(&w, 0, sizeof(w));
+  w.X = X.z(); w.x_pitch = X.pitch; w.in0 = l.layer_in(0);
+  w.W0 = nr.w(0); w.b0 = nr.b(0);
+  w.W1 = nr.w(1); w.b1 = nr.b(1);
+  w.Wt = nr.w(2); w.bt = nr.b(2);
+  if (H0) w.H0 = H0->zo();
+  if (H1) w.H1 = H1->zo();
+  w.OUT = out.zo(); w.o_pitch = out.pitch; w.out_dim = l.out_dim;
+  w.M = M; w.nz1 = nr.nz1; w.f32 = ws_f32();
+  return w;
+}
+
 int Engine::mlp_forward(const Mat& X, int M, const NetRef& nr, std::vector<Mat>& hs, const Mat& out, const char* tag,
                         const SampleJob* jobs, int njobs, bool* jobs_done) {
   const NetLayout& l = *nr.lay;
@@ -943,21 +920,7 @@ int Engine::mlp_forward(const Mat& X, int M, const NetRef& nr, std::vector<Mat>&
   // few batched rows (one to a few runs per engine): the whole pass as ONE launch (small_fwd.h) instead of layer 0 + layer 1 + tail
   if (small_fwd_on && Ln == 2 && !l.ens && !no_ws && !force_scalar && l.H[0] == SF_N && l.H[1] == SF_N && hs[0].pitch == SF_N && hs[1].pitch == SF_N &&
       (long)M * R * nr.nz1 <= small_fwd_max_rows) {
-    SmallFwdP w;
-    memset(&w, 0, sizeof(w));
-    w.X = X.p; w.x_s0 = X.rs; w.x_s1 = X.cs; w.x_pitch = X.pitch; w.in0 = l.layer_in(0);
-    w.W0 = nr.base + l.w_off[0]; w.w0_s0 = nr.rs; w.w0_s1 = l.w_ms[0];
-    w.b0 = nr.base + l.b_off[0]; w.b0_s0 = nr.rs; w.b0_s1 = l.b_ms[0];
-    w.W1 = nr.base + l.w_off[1]; w.w1_s0 = nr.rs; w.w1_s1 = l.w_ms[1];
-    w.b1 = nr.base + l.b_off[1]; w.b1_s0 = nr.rs; w.b1_s1 = l.b_ms[1];
-    w.Wt = nr.base + l.w_off[2]; w.wt_s0 = nr.rs; w.wt_s1 = l.w_ms[2];
-    w.bt = nr.base + l.b_off[2]; w.bt_s0 = nr.rs; w.bt_s1 = l.b_ms[2];
-    if (!fwd_only) {
-      w.H0 = hs[0].p; w.h0_s0 = hs[0].rs; w.h0_s1 = hs[0].cs;
-      w.H1 = hs[1].p; w.h1_s0 = hs[1].rs; w.h1_s1 = hs[1].cs;
-    }
-    w.OUT = out.p; w.o_s0 = out.rs; w.o_s1 = out.cs; w.o_pitch = out.pitch; w.out_dim = l.out_dim;
-    w.M = M; w.nz1 = nr.nz1; w.f32 = ws_f32();
+    SmallFwdP w = small_fwd_p(X, M, nr, fwd_only ? nullptr : &hs[0], fwd_only ? nullptr : &hs[1], out);
     if (fuse_small && jobs && jobs_done && njobs >= 1 && njobs <= 3 && nr.nz1 == 1 && l.out_dim == 2 * ad && ad <= 8 && out.pitch == l.out_dim) {
       w.njobs = njobs; w.A = ad;
       for (int i = 0; i < njobs; ++i) w.job[i] = jobs[i];
@@ -965,14 +928,12 @@ int Engine::mlp_forward(const Mat& X, int M, const NetRef& nr, std::vector<Mat>&
     }
     if (small_fwd_supported(w)) {
       const int nz = R * nr.nz1;
-      if (lab_slot < 4) w.lab_clk = (unsigned long long*)(aloss_part + (long)R * SB_MAXGROUPS * 2) + 16 + 12 * lab_slot++;
       watch_range(X, M, w.in0, X.cs ? nr.nz1 : 1, tag);
       if (!fwd_only) watch_range(hs[0], M, SF_N, nr.nz1, tag);      // (h1 meets the tail weights in fp32 vector arithmetic)
-      prof_begin(tag, 2.0 * M * (double)nz * (SF_N * (double)(w.in0 + 1) + (double)SF_N * SF_N + (double)SF_N * l.out_dim),
-                 4.0 * nz * (M * (double)(X.pitch + (fwd_only ? 0 : 2 * SF_N) + l.out_dim) + (double)SF_N * (w.in0 + SF_N + l.out_dim + 2)));
-      hipError_t err = launch_small_fwd(w, nz, stream);
-      prof_end();
-      if (err != hipSuccess) return fail(std::string("small_fwd launch ") + tag + ": " + hipGetErrorString(err));
+      if (lab_slot < 4) w.lab_clk = lab_clk(16 + 12 * lab_slot++);
+      if (timed("small_fwd", tag, false, 2.0 * M * (double)nz * (SF_N * (double)(w.in0 + 1) + (double)SF_N * SF_N + (double)SF_N * l.out_dim),
+                4.0 * nz * (M * (double)(X.pitch + (fwd_only ? 0 : 2 * SF_N) + l.out_dim) + (double)SF_N * (w.in0 + SF_N + l.out_dim + 2)),
+                [&] { return launch_small_fwd(w, nz, stream); })) return -1;
       if (w.njobs) *jobs_done = true;
       for (int i = 0; i < 2; ++i) {
         if (hs[i].bits) bits_live.erase(hs[i].bits);      // no packed masks from this path: the backward reads 1[h > 0] from the values
@@ -996,28 +957,15 @@ int Engine::mlp_qgrad(const Mat& X, int M, const NetRef& nr, const Mat& q, const
   *done = false;
   if (!(fuse_small && small_fwd_on && l.L == 2 && !l.ens && !no_ws && !force_scalar && l.H[0] == SF_N && l.H[1] == SF_N && l.out_dim == 1 &&
         (long)M * R * nr.nz1 <= small_fwd_max_rows)) return 0;
-  SmallFwdP w;
-  memset(&w, 0, sizeof(w));
-  w.X = X.p; w.x_s0 = X.rs; w.x_s1 = X.cs; w.x_pitch = X.pitch; w.in0 = l.layer_in(0);
-  w.W0 = nr.base + l.w_off[0]; w.w0_s0 = nr.rs; w.w0_s1 = l.w_ms[0];
-  w.b0 = nr.base + l.b_off[0]; w.b0_s0 = nr.rs; w.b0_s1 = l.b_ms[0];
-  w.W1 = nr.base + l.w_off[1]; w.w1_s0 = nr.rs; w.w1_s1 = l.w_ms[1];
-  w.b1 = nr.base + l.b_off[1]; w.b1_s0 = nr.rs; w.b1_s1 = l.b_ms[1];
-  w.Wt = nr.base + l.w_off[2]; w.wt_s0 = nr.rs; w.wt_s1 = l.w_ms[2];
-  w.bt = nr.base + l.b_off[2]; w.bt_s0 = nr.rs; w.bt_s1 = l.b_ms[2];
-  w.OUT = q.p; w.o_s0 = q.rs; w.o_s1 = q.cs; w.o_pitch = q.pitch; w.out_dim = 1;
-  w.G = G.p; w.g_s0 = G.rs; w.g_s1 = G.cs; w.g_pitch = G.pitch; w.gc0 = gc0; w.gn = gn;
-  w.M = M; w.nz1 = nr.nz1; w.f32 = ws_f32();
+  SmallFwdP w = small_fwd_p(X, M, nr, nullptr, nullptr, q);
+  w.G = G.zo(); w.g_pitch = G.pitch; w.gc0 = gc0; w.gn = gn;
   if (!small_fwd_supported(w)) return 0;
   const int nz = R * nr.nz1;
-  if (lab_slot < 4) w.lab_clk = (unsigned long long*)(aloss_part + (long)R * SB_MAXGROUPS * 2) + 16 + 12 * lab_slot++;
   watch_range(X, M, w.in0, X.cs ? nr.nz1 : 1, tag);
   // forward (layer 0, layer 1, tail) + the unit-seed backward through layer 1 and the gn input columns of layer 0
-  prof_begin(tag, 2.0 * M * (double)nz * (SF_N * (double)(w.in0 + 1) + 2.0 * SF_N * SF_N + SF_N + (double)SF_N * gn),
-             4.0 * nz * (M * (double)(X.pitch + 1 + gn) + 2.0 * SF_N * SF_N + (double)SF_N * (w.in0 + 3)));
-  hipError_t err = launch_small_fwd(w, nz, stream);
-  prof_end();
-  if (err != hipSuccess) return fail(std::string("small_qgrad launch ") + tag + ": " + hipGetErrorString(err));
+  if (lab_slot < 4) w.lab_clk = lab_clk(16 + 12 * lab_slot++);
+  if (timed("small_qgrad", tag, false, 2.0 * M * (double)nz * (SF_N * (double)(w.in0 + 1) + 2.0 * SF_N * SF_N + SF_N + (double)SF_N * gn),
+            4.0 * nz * (M * (double)(X.pitch + 1 + gn) + 2.0 * SF_N * SF_N + (double)SF_N * (w.in0 + 3)), [&] { return launch_small_fwd(w, nz, stream); })) return -1;
   *done = true;
   return 0;
 }
@@ -1078,7 +1026,7 @@ static int mlp_backward(Engine* e, const NetRef& nr, const Mat& X, const std::ve
   e->cur_gscale = gscale_given ? gscale_given : e->grad_scale(dTail, M, l.out_dim, nr.nz1, tag);
   if (e->split_scales() && !e->cur_gscale) return -1;
   if (want_w) {
-    for (int i = 0; i <= L; ++i) ks[i] = wgrad_ksplit(l.layer_out(i), l.layer_in(i), M, nz, e->ksplit_cap);
+    for (int i = 0; i <= L; ++i) ks[i] = e->wgrad_ksplit(l.layer_out(i), l.layer_in(i), M, nz);
     if (!rank1 && e->linear_wgrad(DY::plain(dTail), hs[L - 1], M, nr, L, ks[L], 0, true, (t + ".wgrad_tail").c_str())) return -1;
   }
   DY cur;
@@ -1177,6 +1125,48 @@ int Engine::build_common() {
   return 0;
 }
 
+// every environment knob of the engine; they override the defaults of engine.h and the orl_config fields init() stored before
+void Engine::read_env() {
+  enum Kind { FLAG, NFLAG, POS_I, POS_L, ANY_I };      // != 0 / == 0 -> bool; a value > 0 -> int / long (anything else ignored); any int
+  int cus = 0;
+  const struct { const char* name; void* field; Kind kind; } knobs[] = {
+      {"ORL_FORK", &fork_on, FLAG},
+      {"ORL_WS", &use_ws, FLAG},
+      {"ORL_WS32", &use_ws32, FLAG},
+      {"ORL_WS_KEEP_H1", &elide_top, NFLAG},
+      {"ORL_WS_RECOMPUTE_H0", &recompute_h0, FLAG},
+      {"ORL_WS_ONE_ROUND", &ws_geo.one_round, FLAG},
+      {"ORL_WS_CUS", &cus, POS_I},
+      {"ORL_WS_FWD_MIN", &ws_fwd_min_rows, POS_L},
+      {"ORL_WS_BWD_MIN", &ws_bwd_min_rows, POS_L},
+      {"ORL_WS_DGRAD_PLAIN_MIN", &ws_dgrad_plain_min_rows, POS_L},
+      {"ORL_WS_WGRAD_MIN", &ws_wgrad_min_rows, POS_L},
+      {"ORL_WS_WGRAD_MIN_M", &ws_wgrad_min_m, POS_I},
+      {"ORL_WS_WGRAD_SLABS", &ws_wgrad_slab_cap, POS_I},
+      {"ORL_SMALL_FWD", &small_fwd_on, FLAG},
+      {"ORL_SMALL_FWD_MAX", &small_fwd_max_rows, POS_L},
+      {"ORL_FUSE_SMALL", &fuse_small, FLAG},
+      {"ORL_P3", &p3_mask, ANY_I},
+      {"ORL_WGRAD_WG_TARGET", &wgrad_wg_target, POS_I},
+      {"ORL_WGRAD_LONG_MIN", &wgrad_long_min, POS_I},
+      {"ORL_WGRAD_SMALL_KS", &wgrad_small_ks, POS_I},
+  };
+  for (const auto& k : knobs) {
+    const char* f = getenv(k.name);
+    if (!f) continue;
+    const long v = atol(f);
+    switch (k.kind) {
+      case FLAG: *(bool*)k.field = v != 0; break;
+      case NFLAG: *(bool*)k.field = v == 0; break;
+      case POS_I: if (v > 0) *(int*)k.field = (int)v; break;
+      case POS_L: if (v > 0) *(long*)k.field = v; break;
+      case ANY_I: *(int*)k.field = (int)v; break;
+    }
+  }
+  ws_wgrad_slab_cap = std::min(ws_wgrad_slab_cap, max_slab);
+  if (cus >= 8 && cus <= 256) ws_geo.cus = cus;
+}
+
 int Engine::init(const orl_config& c) {
   cfg = c;
   int ndev = 0;
@@ -1192,7 +1182,10 @@ int Engine::init(const orl_config& c) {
   ORL_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
   ORL_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
   ORL_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-  { const char* f = getenv("ORL_FORK"); if (f) fork_on = atoi(f) != 0; }
+  // launch geometry of the weight-stationary kernels: config fields, overridden once (here) by the environment
+  ws_geo.one_round = c.ws_one_round != 0;
+  ws_geo.cus = (c.ws_cus >= 8 && c.ws_cus <= 256) ? c.ws_cus : 256;
+  read_env();
   R = c.n_runs; B = c.batch_size; od = c.obs_dim; ad = c.act_dim;
   N = c.num_repeat_actions > 0 ? c.num_repeat_actions : 1;
   OP = rup(od, 4); AP = rup(ad, 4); XP = rup(od + ad, 4); L = c.n_hidden;
@@ -1236,25 +1229,6 @@ int Engine::init(const orl_config& c) {
   for (auto& s : sc) { memset(&s, 0, sizeof(s)); s.alpha = c.auto_alpha ? 1.0f : c.alpha; s.alpha_bwd = s.alpha; s.cons_scale = 1.f; }
   ORL_HIP(hipMemcpyAsync(scalars, sc.data(), sizeof(RunScalars) * R, hipMemcpyHostToDevice, stream));
   ORL_HIP(hipStreamSynchronize(stream));
-  { const char* f = getenv("ORL_WS_WGRAD_MIN"); if (f && atol(f) > 0) ws_wgrad_min_rows = atol(f); }
-  { const char* f = getenv("ORL_WS_WGRAD_MIN_M"); if (f && atoi(f) > 0) ws_wgrad_min_m = atoi(f); }
-  { const char* f = getenv("ORL_WS_WGRAD_SLABS"); if (f && atoi(f) > 0) ws_wgrad_slab_cap = std::min(atoi(f), max_slab); }
-  { const char* f = getenv("ORL_WS_DGRAD_PLAIN_MIN"); if (f && atol(f) > 0) ws_dgrad_plain_min_rows = atol(f); }
-  { const char* f = getenv("ORL_WS_FWD_MIN"); if (f && atol(f) > 0) ws_fwd_min_rows = atol(f); }
-  { const char* f = getenv("ORL_SMALL_FWD"); if (f) small_fwd_on = atoi(f) != 0; }
-  { const char* f = getenv("ORL_FUSE_SMALL"); if (f) fuse_small = atoi(f) != 0; }
-  { const char* f = getenv("ORL_WS_RECOMPUTE_H0"); if (f) recompute_h0 = atoi(f) != 0; }
-  { const char* f = getenv("ORL_P3"); if (f) p3_mask = atoi(f); }
-  { const char* f = getenv("ORL_SMALL_FWD_MAX"); if (f && atol(f) > 0) small_fwd_max_rows = atol(f); }
-  { const char* f = getenv("ORL_WS_BWD_MIN"); if (f && atol(f) > 0) ws_bwd_min_rows = atol(f); }
-  { const char* f = getenv("ORL_WS_KEEP_H1"); elide_top = !(f && atoi(f) != 0); }
-  { const char* f = getenv("ORL_WS"); use_ws = !(f && atoi(f) == 0); }
-  { const char* f = getenv("ORL_WS32"); use_ws32 = !(f && atoi(f) == 0); }
-  // launch geometry of the weight-stationary kernels: config fields, overridden once (here) by the environment
-  ws_geo.one_round = c.ws_one_round != 0;
-  ws_geo.cus = (c.ws_cus >= 8 && c.ws_cus <= 256) ? c.ws_cus : 256;
-  { const char* f = getenv("ORL_WS_ONE_ROUND"); if (f) ws_geo.one_round = atoi(f) != 0; }
-  { const char* f = getenv("ORL_WS_CUS"); const int x = f ? atoi(f) : 0; if (x >= 8 && x <= 256) ws_geo.cus = x; }
   if (build_common()) return -1;
   int rc = -1;
   switch (c.algo) {
@@ -1266,7 +1240,7 @@ int Engine::init(const orl_config& c) {
     case ORL_ALGO_MCQ: rc = mcq_build(); break;
   }
   if (rc) return rc;
-  { Mat lc; lc.p = aloss_part + (long)R * SB_MAXGROUPS * 2; lc.pitch = 192; taps["lab_clk"] = {lc, 1, 192}; }      // shader-clock stamps of lab builds (small_bwd.hip)
+  { Mat lc; lc.p = (float*)lab_clk(0); lc.pitch = 192; taps["lab_clk"] = {lc, 1, 192}; }      // shader-clock stamps of lab builds (small_bwd.hip)
   for (auto& ns : noise_slots) taps[ns.name] = {W(ns.name), ns.rows, ns.cols ? ns.cols : ad};      // the noise arrays of the last step
   nm = (int)metric_names.size();
   if (nm > ORL_MAX_METRICS) return fail("too many metrics");

@@ -186,11 +186,16 @@ enum { E_PLAIN = 0, E_BIAS = 1, E_BIAS_RELU = 2, E_MASK = 3, E_WGRAD = 4,
        E_SWISH_GRAD = 6 };    // C = acc * sigmoid(z) (1 + z (1 - sigmoid(z))) with z = aux[m][n]: the Swish counterpart of E_MASK
 enum { L_SCALAR = 0, L_VECK = 1, L_BLK4 = 2, L_VECKU = 3 };            // operand loaders
 
-struct ZPtr {        // base + z0 * s0 + z1 * s1 (element strides)
-  const float* p;
+template <typename T>
+struct ZView {       // base + z0 * s0 + z1 * s1 (element strides)
+  T* p;
   long s0, s1;
-  __host__ __device__ const float* at(int z0, int z1) const { return p ? p + z0 * s0 + z1 * s1 : nullptr; }
+  __host__ __device__ T* at(int z0, int z1) const { return p ? p + z0 * s0 + z1 * s1 : nullptr; }
+  bool vec4() const { return (((uintptr_t)p) & 15) == 0 && !(s0 & 3) && !(s1 & 3); }   // host: every problem's base is 16-byte aligned (null included)
 };
+using ZPtr = ZView<const float>;     // operand read by a kernel
+using ZOut = ZView<float>;           // result written by a kernel
+using ZBits = ZView<unsigned int>;   // packed ReLU-mask words (GemmP::mb_out layout), read or written
 
 struct GemmP {
   ZPtr A, B;

@@ -29,8 +29,8 @@ struct SmallABwdP {
   const float* eps; long eps_s0;                                // [M][A]
   const float* xa; long xa_s0; int xa_pitch, xa_col;            // sampled actions a = tanh(u) at xa[m][xa_col + a]
   const float* logp; long logp_s0;                              // [M]
-  const float* qa; long qa_s0, qa_s1;                           // [K][M] critic values Q_k(s, a)
-  const float* ga; long ga_s0, ga_s1; int ga_pitch;             // [K][M][ga_pitch] unit-seed gradients dQ_k / da
+  ZPtr qa;                                                      // [K][M] critic values Q_k(s, a)
+  ZPtr ga; int ga_pitch;                                        // [K][M][ga_pitch] unit-seed gradients dQ_k / da
   int K;                                                        // critics (2)
   const float* W1; long w1_s0;                                  // actor layer 1 (256, 256) row-major
   const float* Wh; long wh_s0;                                  // head (2A, 256) row-major

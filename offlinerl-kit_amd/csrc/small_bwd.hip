@@ -119,8 +119,8 @@ __global__ __launch_bounds__(SB_NT) void small_abwd_kernel(const SmallABwdP p) {
     const int r = tid >> 4, j = tid & 15;
     const int a = j < A ? j : (j < A2 ? j - A : 0);
     const long m = row0 + r;
-    const float q0 = (p.qa + z0 * p.qa_s0)[m], q1 = (p.qa + z0 * p.qa_s0 + p.qa_s1)[m];
-    const float g0 = (p.ga + z0 * p.ga_s0)[m * p.ga_pitch + a], g1 = (p.ga + z0 * p.ga_s0 + p.ga_s1)[m * p.ga_pitch + a];
+    const float q0 = (p.qa.p + z0 * p.qa.s0)[m], q1 = (p.qa.p + z0 * p.qa.s0 + p.qa.s1)[m];
+    const float g0 = (p.ga.p + z0 * p.ga.s0)[m * p.ga_pitch + a], g1 = (p.ga.p + z0 * p.ga.s0 + p.ga.s1)[m * p.ga_pitch + a];
     const float lsr = (p.head + z0 * p.head_s0)[m * A2 + A + a];
     const float ep = (p.eps + z0 * p.eps_s0)[m * A + a];
     const float act = (p.xa + z0 * p.xa_s0)[m * p.xa_pitch + p.xa_col + a];

@@ -55,13 +55,13 @@ __global__ __launch_bounds__(SF_NT) void small_fwd_kernel(const SmallFwdP p) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int g = blockIdx.x, z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
   const int ncol0 = 32 * wave;
-  const float* __restrict__ Xg = p.X + z0 * p.x_s0 + z1 * p.x_s1 + (long)g * SF_ROWS * p.x_pitch;
-  const float* __restrict__ W0g = p.W0 + z0 * p.w0_s0 + z1 * p.w0_s1;
-  const float* __restrict__ b0g = p.b0 + z0 * p.b0_s0 + z1 * p.b0_s1;
-  const float* __restrict__ W1g = p.W1 + z0 * p.w1_s0 + z1 * p.w1_s1;
-  const float* __restrict__ b1g = p.b1 + z0 * p.b1_s0 + z1 * p.b1_s1;
-  const float* __restrict__ Wtg = p.Wt + z0 * p.wt_s0 + z1 * p.wt_s1;
-  const float* __restrict__ btg = p.bt + z0 * p.bt_s0 + z1 * p.bt_s1;
+  const float* __restrict__ Xg = p.X.p + z0 * p.X.s0 + z1 * p.X.s1 + (long)g * SF_ROWS * p.x_pitch;
+  const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
+  const float* __restrict__ b0g = p.b0.p + z0 * p.b0.s0 + z1 * p.b0.s1;
+  const float* __restrict__ W1g = p.W1.p + z0 * p.W1.s0 + z1 * p.W1.s1;
+  const float* __restrict__ b1g = p.b1.p + z0 * p.b1.s0 + z1 * p.b1.s1;
+  const float* __restrict__ Wtg = p.Wt.p + z0 * p.Wt.s0 + z1 * p.Wt.s1;
+  const float* __restrict__ btg = p.bt.p + z0 * p.bt.s0 + z1 * p.bt.s1;
 
   SF_STAMP(0);
   // ---- one 32-wide k chunk of weights: thread t moves the float4 (unit n = (t + 512 i) >> 3, k = 4 ((t + 512 i) & 7) ..), i = 0..3 ----
@@ -223,8 +223,8 @@ __global__ __launch_bounds__(SF_NT) void small_fwd_kernel(const SmallFwdP p) {
   };
   zero_acc();
   constexpr float inv_sc = F32 ? 1.0f : 1.0f / ORL_WSCALE;
-  float* __restrict__ H0g = p.H0 ? p.H0 + z0 * p.h0_s0 + z1 * p.h0_s1 + (long)g * SF_ROWS * SF_N : nullptr;
-  float* __restrict__ H1g = p.H1 ? p.H1 + z0 * p.h1_s0 + z1 * p.h1_s1 + (long)g * SF_ROWS * SF_N : nullptr;
+  float* __restrict__ H0g = p.H0.p ? p.H0.p + z0 * p.H0.s0 + z1 * p.H0.s1 + (long)g * SF_ROWS * SF_N : nullptr;
+  float* __restrict__ H1g = p.H1.p ? p.H1.p + z0 * p.H1.s0 + z1 * p.H1.s1 + (long)g * SF_ROWS * SF_N : nullptr;
 
   // products of chunk c: operands swapped (weights first), lane (li, lq) then holds C[m = 16 s + li][n = ncol0 + 16 cb + 4 lq + r]
   auto compute = [&](int c) __attribute__((always_inline)) {
@@ -453,12 +453,12 @@ __global__ __launch_bounds__(SF_NT) void small_fwd_kernel(const SmallFwdP p) {
         float x = 0.f;
 #pragma unroll
         for (int w = 0; w < 32; ++w) x += gred[(w * SF_ROWS + r) * 8 + a];      // fixed order
-        (p.G + z0 * p.g_s0 + z1 * p.g_s1)[((long)g * SF_ROWS + r) * p.g_pitch + a] = x;
+        (p.G.p + z0 * p.G.s0 + z1 * p.G.s1)[((long)g * SF_ROWS + r) * p.g_pitch + a] = x;
       } else if (a == 8) {
         float x = sBT[0];
 #pragma unroll
         for (int w = 0; w < 32; ++w) x += qred[w * SF_ROWS + r];                // fixed order
-        (p.OUT + z0 * p.o_s0 + z1 * p.o_s1)[((long)g * SF_ROWS + r) * p.o_pitch] = x;
+        (p.OUT.p + z0 * p.OUT.s0 + z1 * p.OUT.s1)[((long)g * SF_ROWS + r) * p.o_pitch] = x;
       }
     }
     SF_STAMP(7);
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(SF_NT) void small_fwd_kernel(const SmallFwdP p) {
       float a = sBT[o];
 #pragma unroll
       for (int w = 0; w < 8; ++w) a += red[(w * SF_ROWS + r) * SF_MAXOUT + o];       // fixed order
-      (p.OUT + z0 * p.o_s0 + z1 * p.o_s1)[((long)g * SF_ROWS + r) * p.o_pitch + o] = a;
+      (p.OUT.p + z0 * p.OUT.s0 + z1 * p.OUT.s1)[((long)g * SF_ROWS + r) * p.o_pitch + o] = a;
       shead[r * SF_MAXOUT + o] = a;
     }
   } else {
@@ -513,7 +513,7 @@ __global__ __launch_bounds__(SF_NT) void small_fwd_kernel(const SmallFwdP p) {
       float a = sBT[0];
 #pragma unroll
       for (int w = 0; w < 32; ++w) a += red[w * SF_ROWS + tid];                       // fixed order
-      (p.OUT + z0 * p.o_s0 + z1 * p.o_s1)[((long)g * SF_ROWS + tid) * p.o_pitch] = a;
+      (p.OUT.p + z0 * p.OUT.s0 + z1 * p.OUT.s1)[((long)g * SF_ROWS + tid) * p.o_pitch] = a;
     }
   }
   SF_STAMP(5);
@@ -556,7 +556,7 @@ hipError_t launch_small_fwd(const SmallFwdP& p, int nz, hipStream_t st) {
   }();
   if (attr_err != hipSuccess) return attr_err;
   const dim3 grid(p.M / SF_ROWS, 1, nz), block(SF_NT);
-  if (p.G) {
+  if (p.G.p) {
     if (p.f32) hipLaunchKernelGGL((small_fwd_kernel<true, true>), grid, block, sf_lds_bytes<true>(), st, p);
     else hipLaunchKernelGGL((small_fwd_kernel<false, true>), grid, block, sf_lds_bytes<false>(), st, p);
   } else if (p.f32) hipLaunchKernelGGL((small_fwd_kernel<true, false>), grid, block, sf_lds_bytes<true>(), st, p);

@@ -16,13 +16,13 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad_w0_kernel(const WsDgradP p) {
   __shared__ u32x2_t mlut[16];                                     // 4 mask bits -> 4 bf16 values
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
-  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits + z0 * p.ab_s0 + z1 * p.ab_s1;
-  const unsigned int* __restrict__ xb = p.xbits + z0 * p.xb_s0 + z1 * p.xb_s1;
-  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq + z0 * p.dq_s0 + z1 * p.dq_s1;
-  const float* __restrict__ Wg = p.W + z0 * p.w_s0 + z1 * p.w_s1;
-  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt + z0 * p.wt_s0 + z1 * p.wt_s1;
-  const float* __restrict__ Xg = p.X + z0 * p.x_s0 + z1 * p.x_s1;
-  const float* __restrict__ Zg = PLAIN ? p.Z + z0 * p.z_s0 + z1 * p.z_s1 : nullptr;
+  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits.p + z0 * p.abits.s0 + z1 * p.abits.s1;
+  const unsigned int* __restrict__ xb = p.xbits.p + z0 * p.xbits.s0 + z1 * p.xbits.s1;
+  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq.p + z0 * p.dq.s0 + z1 * p.dq.s1;
+  const float* __restrict__ Wg = p.W.p + z0 * p.W.s0 + z1 * p.W.s1;
+  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt.p + z0 * p.wt.s0 + z1 * p.wt.s1;
+  const float* __restrict__ Xg = p.X.p + z0 * p.X.s0 + z1 * p.X.s1;
+  const float* __restrict__ Zg = PLAIN ? p.Z.p + z0 * p.Z.s0 + z1 * p.Z.s1 : nullptr;
   const int ncol0 = 32 * wave;
   // split precision: dq (PLAIN: dz1) enters scaled by the run's dynamic gradient scale (W0 variant only: the stored dz0 of the STORE variant
   // must be the true values), the resident products by ORL_WWSCALE (PLAIN: ORL_WSCALE); dz0 therefore carries gs * that scale into the
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad_w0_kernel(const WsDgradP p) {
   unsigned int sm_word;
   float sx[2];
   const int xe = W0 ? WS_ROWS * p.x_pitch : 0;                       // X elements of a row group (<= 1024)
-  float* __restrict__ Cg = STORE ? p.C + z0 * p.c_s0 + z1 * p.c_s1 : nullptr;
+  float* __restrict__ Cg = STORE ? p.C.p + z0 * p.C.s0 + z1 * p.C.s1 : nullptr;
   // X element e = tid + 512 i of a row group -> X^T position (column c, row rr); surplus threads use a pad slot that is never read
   // (rows are consumed as 32 of the WD_XP entries); computed once: no division and no predication inside the loop
   int xo[2];
@@ -237,8 +237,8 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad_w0_kernel(const WsDgradP p) {
   for (; g < p.groups; g += gs, ++it) iteration(g, it, false);
   if (!W0) return;
   // one slab per workgroup: lane (li, lq) holds dW0^T[c = 16 cbk + 4 lq + r][n = ncol0 + 16 cb + li]
-  float* wo = p.w0_out + z0 * p.o_s0 + z1 * p.o_s1 + (long)blockIdx.x * p.o_ks;
-  float* bo = p.b0_out + z0 * p.o_s0 + z1 * p.ob_s1 + (long)blockIdx.x * p.o_ks;
+  float* wo = p.w0_out + z0 * p.o_rs + z1 * p.o_ms + (long)blockIdx.x * p.o_ks;
+  float* bo = p.b0_out + z0 * p.o_rs + z1 * p.ob_ms + (long)blockIdx.x * p.o_ks;
 #pragma unroll
   for (int cbk = 0; cbk < 2; ++cbk)
 #pragma unroll
@@ -272,13 +272,13 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad32_w0_kernel(const WsDgradP p) 
   __shared__ f32x4 mlut32[16];                                      // 4 mask bits -> 4 floats (0.0 / 1.0)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
-  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits + z0 * p.ab_s0 + z1 * p.ab_s1;
-  const unsigned int* __restrict__ xb = p.xbits + z0 * p.xb_s0 + z1 * p.xb_s1;
-  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq + z0 * p.dq_s0 + z1 * p.dq_s1;
-  const float* __restrict__ Wg = p.W + z0 * p.w_s0 + z1 * p.w_s1;
-  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt + z0 * p.wt_s0 + z1 * p.wt_s1;
-  const float* __restrict__ Xg = p.X + z0 * p.x_s0 + z1 * p.x_s1;
-  const float* __restrict__ Zg = PLAIN ? p.Z + z0 * p.z_s0 + z1 * p.z_s1 : nullptr;
+  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits.p + z0 * p.abits.s0 + z1 * p.abits.s1;
+  const unsigned int* __restrict__ xb = p.xbits.p + z0 * p.xbits.s0 + z1 * p.xbits.s1;
+  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq.p + z0 * p.dq.s0 + z1 * p.dq.s1;
+  const float* __restrict__ Wg = p.W.p + z0 * p.W.s0 + z1 * p.W.s1;
+  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt.p + z0 * p.wt.s0 + z1 * p.wt.s1;
+  const float* __restrict__ Xg = p.X.p + z0 * p.X.s0 + z1 * p.X.s1;
+  const float* __restrict__ Zg = PLAIN ? p.Z.p + z0 * p.Z.s0 + z1 * p.Z.s1 : nullptr;
   const int ncol0 = 32 * wave;
 
   f32x4 bw[2][16];
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad32_w0_kernel(const WsDgradP p) 
   unsigned int sm_word;
   float sx[2];
   const int xe = W0 ? WS_ROWS * p.x_pitch : 0;
-  float* __restrict__ Cg = STORE ? p.C + z0 * p.c_s0 + z1 * p.c_s1 : nullptr;
+  float* __restrict__ Cg = STORE ? p.C.p + z0 * p.C.s0 + z1 * p.C.s1 : nullptr;
   int xo[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -431,8 +431,8 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad32_w0_kernel(const WsDgradP p) 
   int g = g0, it = 0;
   for (; g < p.groups; g += gs, ++it) iteration(g, it);
   if (!W0) return;
-  float* wo = p.w0_out + z0 * p.o_s0 + z1 * p.o_s1 + (long)blockIdx.x * p.o_ks;
-  float* bo = p.b0_out + z0 * p.o_s0 + z1 * p.ob_s1 + (long)blockIdx.x * p.o_ks;
+  float* wo = p.w0_out + z0 * p.o_rs + z1 * p.o_ms + (long)blockIdx.x * p.o_ks;
+  float* bo = p.b0_out + z0 * p.o_rs + z1 * p.ob_ms + (long)blockIdx.x * p.o_ks;
 #pragma unroll
   for (int cbk = 0; cbk < 2; ++cbk)
 #pragma unroll
@@ -456,12 +456,12 @@ hipError_t launch_ws_dgrad_w0(WsDgradP p, int nz, int per_z, hipStream_t st) {
       return e;
     }();
     if (attr_err != hipSuccess) return attr_err;
-    if (p.Z) hipLaunchKernelGGL((ws_dgrad32_w0_kernel<true, false, true>), grid, block, ws_dgrad32_lds_bytes(), st, p);
+    if (p.Z.p) hipLaunchKernelGGL((ws_dgrad32_w0_kernel<true, false, true>), grid, block, ws_dgrad32_lds_bytes(), st, p);
     else if (p.w0_out) hipLaunchKernelGGL((ws_dgrad32_w0_kernel<true, false>), grid, block, ws_dgrad32_lds_bytes(), st, p);
     else hipLaunchKernelGGL((ws_dgrad32_w0_kernel<false, true>), grid, block, ws_dgrad32_lds_bytes(), st, p);
     return hipGetLastError();
   }
-  if (p.Z) {
+  if (p.Z.p) {
     static const hipError_t attr_err = hipFuncSetAttribute((const void*)ws_dgrad_w0_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_dgrad_lds_bytes(true));
     if (attr_err != hipSuccess) return attr_err;
     hipLaunchKernelGGL((ws_dgrad_w0_kernel<true, false, true>), grid, block, ws_dgrad_lds_bytes(true), st, p);

@@ -30,14 +30,14 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad3_w0_kernel(const WsDgradP p) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int half = blockIdx.y;
   const int z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
-  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits + z0 * p.ab_s0 + z1 * p.ab_s1;
-  const float* __restrict__ Zg = PLAIN ? p.Z + z0 * p.z_s0 + z1 * p.z_s1 : nullptr;
-  const unsigned int* __restrict__ xb = p.xbits + z0 * p.xb_s0 + z1 * p.xb_s1;
-  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq + z0 * p.dq_s0 + z1 * p.dq_s1;
-  const float* __restrict__ Wg = p.W + z0 * p.w_s0 + z1 * p.w_s1;
-  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt + z0 * p.wt_s0 + z1 * p.wt_s1;
-  const float* __restrict__ Xg = W0 ? p.X + z0 * p.x_s0 + z1 * p.x_s1 : nullptr;
-  float* __restrict__ Cg = W0 ? nullptr : p.C + z0 * p.c_s0 + z1 * p.c_s1;
+  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits.p + z0 * p.abits.s0 + z1 * p.abits.s1;
+  const float* __restrict__ Zg = PLAIN ? p.Z.p + z0 * p.Z.s0 + z1 * p.Z.s1 : nullptr;
+  const unsigned int* __restrict__ xb = p.xbits.p + z0 * p.xbits.s0 + z1 * p.xbits.s1;
+  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq.p + z0 * p.dq.s0 + z1 * p.dq.s1;
+  const float* __restrict__ Wg = p.W.p + z0 * p.W.s0 + z1 * p.W.s1;
+  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt.p + z0 * p.wt.s0 + z1 * p.wt.s1;
+  const float* __restrict__ Xg = W0 ? p.X.p + z0 * p.X.s0 + z1 * p.X.s1 : nullptr;
+  float* __restrict__ Cg = W0 ? nullptr : p.C.p + z0 * p.C.s0 + z1 * p.C.s1;
   const int ncol0 = 128 * half + 16 * wave;
   // dq enters scaled by the run's dynamic gradient scale, the resident products by ORL_WWSCALE; dz0 carries gs * that scale into the second stage
   const float gsc = (W0 && p.gscale) ? p.gscale[z0] : 1.f;
@@ -244,8 +244,8 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad3_w0_kernel(const WsDgradP p) {
   }
   if (!W0) return;
   // one slab per (workgroup pair): lane (li, lq) holds dW0^T[c = 16 cbk + 4 lq + r][n = ncol0 + li]
-  float* wo = p.w0_out + z0 * p.o_s0 + z1 * p.o_s1 + (long)blockIdx.x * p.o_ks;
-  float* bo = p.b0_out + z0 * p.o_s0 + z1 * p.ob_s1 + (long)blockIdx.x * p.o_ks;
+  float* wo = p.w0_out + z0 * p.o_rs + z1 * p.o_ms + (long)blockIdx.x * p.o_ks;
+  float* bo = p.b0_out + z0 * p.o_rs + z1 * p.ob_ms + (long)blockIdx.x * p.o_ks;
 #pragma unroll
   for (int cbk = 0; cbk < 2; ++cbk)
 #pragma unroll
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad3_w0_kernel(const WsDgradP p) {
 
 hipError_t launch_ws_dgrad3_w0(WsDgradP p, int nz, int per_z, hipStream_t st) {
   p.groups = p.M / WS_ROWS;
-  if (p.Z) {
+  if (p.Z.p) {
     static const hipError_t attr_err = hipFuncSetAttribute((const void*)ws_dgrad3_w0_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_dgrad3_lds_bytes(true));
     if (attr_err != hipSuccess) return attr_err;
     hipLaunchKernelGGL((ws_dgrad3_w0_kernel<true, true>), dim3(per_z, 2, nz), dim3(WS_NT), ws_dgrad3_lds_bytes(true), st, p);

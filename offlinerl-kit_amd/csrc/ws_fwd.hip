@@ -27,13 +27,13 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   float* cst = (float*)((char*)ws_smem + ws_fwd_lds_bytes(L0) - sizeof(float) * 2 * WS_N);   // [bias | tail weights]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
-  const float* __restrict__ Xg = p.X + z0 * p.x_s0 + z1 * p.x_s1;
-  const float* __restrict__ Wg = p.W + z0 * p.w_s0 + z1 * p.w_s1;
-  const float* __restrict__ bg = DG ? nullptr : p.bias + z0 * p.b_s0 + z1 * p.b_s1;
-  float* __restrict__ Yg = p.Y + z0 * p.y_s0 + z1 * p.y_s1;
+  const float* __restrict__ Xg = p.X.p + z0 * p.X.s0 + z1 * p.X.s1;
+  const float* __restrict__ Wg = p.W.p + z0 * p.W.s0 + z1 * p.W.s1;
+  const float* __restrict__ bg = DG ? nullptr : p.bias.p + z0 * p.bias.s0 + z1 * p.bias.s1;
+  float* __restrict__ Yg = p.Y.p + z0 * p.Y.s0 + z1 * p.Y.s1;
   const int ncol0 = 16 * WS_CB * wave;
   float* __restrict__ Y0g = L0 ? const_cast<float*>(Xg) : nullptr;       // L0: h0 is written where the plain kernel reads it
-  const float* __restrict__ X0g = L0 ? p.X0 + z0 * p.x0_s0 + z1 * p.x0_s1 : nullptr;
+  const float* __restrict__ X0g = L0 ? p.X0.p + z0 * p.X0.s0 + z1 * p.X0.s1 : nullptr;
 
   WS_STAMP(0);
   // ---- resident B fragments: lane (li, lq) supplies W[n = ncol0 + 16 cb + li][k = 32 ks + 8 lq .. +7] ----
@@ -89,8 +89,8 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   hx8 b0h[WS_CB], b0l[WS_CB];
   f32x4 b0w[WS_CB][2];                              // F32: k = 16 t + 4 lq + e
   if (L0) {
-    const float* __restrict__ W0g = p.W0 + z0 * p.w0_s0 + z1 * p.w0_s1;
-    const float* __restrict__ b0g = p.b0 + z0 * p.b0_s0 + z1 * p.b0_s1;
+    const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
+    const float* __restrict__ b0g = p.b0.p + z0 * p.b0.s0 + z1 * p.b0.s1;
 #pragma unroll
     for (int cb = 0; cb < WS_CB; ++cb) {
       const int n = ncol0 + 16 * cb + li;
@@ -122,9 +122,9 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   // epilogue constants of this lane's columns n = ncol0 + 16 cb + 4 lq + r sit in LDS (not in 16 VGPRs next to the 128 VGPRs of
   // resident B fragments, and not re-read from global memory: vmcnt is in-order, so waiting for such a load in the epilogue would
   // also wait for every activation store issued before it)
-  const float* __restrict__ twg = TQ ? p.tw + z0 * p.tw_s0 + z1 * p.tw_s1 : bg;
+  const float* __restrict__ twg = TQ ? p.tw.p + z0 * p.tw.s0 + z1 * p.tw.s1 : bg;
   if (!DG && tid < WS_N) { cst[tid] = bg[tid]; cst[WS_N + tid] = twg[tid]; }      // visible after the prologue's barriers
-  const float tbias = TQ ? (p.tb + z0 * p.tb_s0 + z1 * p.tb_s1)[0] : 0.f;
+  const float tbias = TQ ? (p.tb.p + z0 * p.tb.s0 + z1 * p.tb.s1)[0] : 0.f;
   // split precision: the accumulators carry ORL_WSCALE (weights) and, in gradient mode, the run's dynamic gradient scale (staged rows)
   const float a_sc = (DG && !F32 && p.gscale) ? p.gscale[z0] : 1.f;
   const float inv_sc = F32 ? 1.f : 1.0f / (ORL_WSCALE * a_sc);
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
       const unsigned int d0 = nb[0], d1 = nb[1];
       const unsigned int lo16 = (d0 & 0xFu) | ((d0 >> 4) & 0xF0u) | ((d0 >> 8) & 0xF00u) | ((d0 >> 12) & 0xF000u);
       const unsigned int hi16 = (d1 & 0xFu) | ((d1 >> 4) & 0xF0u) | ((d1 >> 8) & 0xF00u) | ((d1 >> 12) & 0xF000u);
-      p.mb0[z0 * p.mb0_s0 + z1 * p.mb0_s1 + ((long)g * WS_ROWS + row) * p.mb0_g + wd] = lo16 | (hi16 << 16);
+      p.mb0.p[z0 * p.mb0.s0 + z1 * p.mb0.s1 + ((long)g * WS_ROWS + row) * p.mb0_g + wd] = lo16 | (hi16 << 16);
     }
   };
 
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   };
   auto epilogue = [&](const f32x4 (&acc)[WS_SUB][WS_CB], int g, int par) __attribute__((always_inline)) {
     if (DG) {                                      // gradient epilogue: ReLU mask of the receiving activation from its packed bits
-      const unsigned int* __restrict__ dm = p.dmask + z0 * p.dm_s0 + z1 * p.dm_s1;
+      const unsigned int* __restrict__ dm = p.dmask.p + z0 * p.dmask.s0 + z1 * p.dmask.s1;
 #pragma unroll
       for (int s = 0; s < WS_SUB; ++s) {
         const long m = (long)g * WS_ROWS + 16 * s + li;
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
       const unsigned int d0 = nb[0], d1 = nb[1];
       const unsigned int lo16 = (d0 & 0xFu) | ((d0 >> 4) & 0xF0u) | ((d0 >> 8) & 0xF00u) | ((d0 >> 12) & 0xF000u);
       const unsigned int hi16 = (d1 & 0xFu) | ((d1 >> 4) & 0xF0u) | ((d1 >> 8) & 0xF00u) | ((d1 >> 12) & 0xF000u);
-      p.mb[z0 * p.mb_s0 + z1 * p.mb_s1 + (long)m * p.mb_g + wd] = lo16 | (hi16 << 16);
+      p.mb.p[z0 * p.mb.s0 + z1 * p.mb.s1 + (long)m * p.mb_g + wd] = lo16 | (hi16 << 16);
     }
     if (TQ && tid < WS_ROWS) {                       // eight column-slice partial sums per row, fixed order
       const int m = g * WS_ROWS + tid;
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
       float a = tbias;
 #pragma unroll
       for (int w = 0; w < WS_NW; ++w) a += q8[w * WS_ROWS];
-      p.tq[z0 * p.tq_s0 + z1 * p.tq_s1 + (long)m * p.tq_sm] = a;
+      p.tq.p[z0 * p.tq.s0 + z1 * p.tq.s1 + (long)m * p.tq_sm] = a;
     }
   };
 
@@ -528,18 +528,18 @@ static hipError_t ws_fwd_attrs() {
 
 template <bool F32>
 static void ws_fwd_dispatch(const WsFwdP& p, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-  const bool l0 = p.X0 != nullptr;
-  if (p.dmask) hipLaunchKernelGGL((ws_fwd_kernel<false, false, true, true, F32>), grid, block, lds, st, p);
-  else if (l0 && p.x0_discard && !(p.tq && p.Y)) {     // forward-only passes (storing h0 anyway is always correct: any other shape takes the storing flavour)
-    if (p.tq) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, false, F32, false>), grid, block, lds, st, p);
+  const bool l0 = p.X0.p != nullptr;
+  if (p.dmask.p) hipLaunchKernelGGL((ws_fwd_kernel<false, false, true, true, F32>), grid, block, lds, st, p);
+  else if (l0 && p.x0_discard && !(p.tq.p && p.Y.p)) {     // forward-only passes (storing h0 anyway is always correct: any other shape takes the storing flavour)
+    if (p.tq.p) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, false, F32, false>), grid, block, lds, st, p);
     else hipLaunchKernelGGL((ws_fwd_kernel<false, true, false, true, F32, false>), grid, block, lds, st, p);
   } else if (l0) {
-    if (p.tq && !p.Y) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, false, F32>), grid, block, lds, st, p);
-    else if (p.tq) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, true, F32>), grid, block, lds, st, p);
+    if (p.tq.p && !p.Y.p) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, false, F32>), grid, block, lds, st, p);
+    else if (p.tq.p) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, true, F32>), grid, block, lds, st, p);
     else hipLaunchKernelGGL((ws_fwd_kernel<false, true, false, true, F32>), grid, block, lds, st, p);
   } else {
-    if (p.tq && !p.Y) hipLaunchKernelGGL((ws_fwd_kernel<true, false, false, false, F32>), grid, block, lds, st, p);
-    else if (p.tq) hipLaunchKernelGGL((ws_fwd_kernel<true, false, false, true, F32>), grid, block, lds, st, p);
+    if (p.tq.p && !p.Y.p) hipLaunchKernelGGL((ws_fwd_kernel<true, false, false, false, F32>), grid, block, lds, st, p);
+    else if (p.tq.p) hipLaunchKernelGGL((ws_fwd_kernel<true, false, false, true, F32>), grid, block, lds, st, p);
     else hipLaunchKernelGGL((ws_fwd_kernel<false, false, false, true, F32>), grid, block, lds, st, p);
   }
 }
@@ -548,7 +548,7 @@ hipError_t launch_ws_fwd(WsFwdP p, int nz, hipStream_t st, const WsGeom& geo) {
   p.groups = (p.M + WS_ROWS - 1) / WS_ROWS;
   // one workgroup per CU (register-resident weights): whole rounds of 256 workgroups over the nz problems (ws_blocks_per_problem)
   const int per_z = ws_blocks_per_problem(p.groups, nz, 10, 1 << 20, geo);
-  const size_t lds = ws_fwd_lds_bytes(p.X0 != nullptr);
+  const size_t lds = ws_fwd_lds_bytes(p.X0.p != nullptr);
   static const hipError_t attr_err = [] {       // thread-safe one-time initialisation (engines may launch from several host threads)
     hipError_t e = ws_fwd_attrs<false>();
     return e == hipSuccess ? ws_fwd_attrs<true>() : e;

@@ -37,14 +37,14 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int half = blockIdx.y;
   const int z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
-  const float* __restrict__ Wg = p.W + z0 * p.w_s0 + z1 * p.w_s1;
-  const float* __restrict__ bg = DG ? nullptr : p.bias + z0 * p.b_s0 + z1 * p.b_s1;
-  const unsigned int* __restrict__ dmg = DG ? p.dmask + z0 * p.dm_s0 + z1 * p.dm_s1 : nullptr;
+  const float* __restrict__ Wg = p.W.p + z0 * p.W.s0 + z1 * p.W.s1;
+  const float* __restrict__ bg = DG ? nullptr : p.bias.p + z0 * p.bias.s0 + z1 * p.bias.s1;
+  const unsigned int* __restrict__ dmg = DG ? p.dmask.p + z0 * p.dmask.s0 + z1 * p.dmask.s1 : nullptr;
   const float a_sc = (DG && p.gscale) ? p.gscale[z0] : 1.f;          // gradient mode: the staged rows carry the run's dynamic gradient scale
-  float* __restrict__ Y0g = const_cast<float*>(p.X) + z0 * p.x_s0 + z1 * p.x_s1;      // h0 is written where the plain kernel reads it
-  float* __restrict__ Yg = SY ? p.Y + z0 * p.y_s0 + z1 * p.y_s1 : nullptr;
-  const float* __restrict__ X0g = L0 ? p.X0 + z0 * p.x0_s0 + z1 * p.x0_s1 : nullptr;
-  const float* __restrict__ Xg = p.X + z0 * p.x_s0 + z1 * p.x_s1;           // L0 = false: the layer's input rows
+  float* __restrict__ Y0g = const_cast<float*>(p.X.p) + z0 * p.X.s0 + z1 * p.X.s1;      // h0 is written where the plain kernel reads it
+  float* __restrict__ Yg = SY ? p.Y.p + z0 * p.Y.s0 + z1 * p.Y.s1 : nullptr;
+  const float* __restrict__ X0g = L0 ? p.X0.p + z0 * p.X0.s0 + z1 * p.X0.s1 : nullptr;
+  const float* __restrict__ Xg = p.X.p + z0 * p.X.s0 + z1 * p.X.s1;           // L0 = false: the layer's input rows
   const int ncol1 = 128 * half + 16 * wave;                              // layer-1 columns of this wave
   const int ncol0 = 32 * wave;                                           // h0 columns this wave produces
   // the h0 store of a wave whose columns belong to the other half lands in a per-workgroup scratch line (row pitch 0)
@@ -76,8 +76,8 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
   // first-layer fragments of columns ncol0 + 16 cb + li, K = 32: W0'[n][k] = W0[n][k] (k < in0), b0[n] (k == in0), 0 beyond (unscaled, as in ws_fwd)
   hx8 b0h[2], b0m[2], b0l[2];
   if constexpr (L0) {
-    const float* __restrict__ W0g = p.W0 + z0 * p.w0_s0 + z1 * p.w0_s1;
-    const float* __restrict__ b0g = p.b0 + z0 * p.b0_s0 + z1 * p.b0_s1;
+    const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
+    const float* __restrict__ b0g = p.b0.p + z0 * p.b0.s0 + z1 * p.b0.s1;
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
       const int n = ncol0 + 16 * cb + li;
@@ -94,10 +94,10 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
       ws_split8x3(a, b, b0h[cb], b0m[cb], b0l[cb]);
     }
   }
-  const float* __restrict__ twg = TQ ? p.tw + z0 * p.tw_s0 + z1 * p.tw_s1 : bg;
+  const float* __restrict__ twg = TQ ? p.tw.p + z0 * p.tw.s0 + z1 * p.tw.s1 : bg;
   if (!DG && tid < WS_N) { cst[tid] = bg[tid]; cst[WS_N + tid] = twg[tid]; }     // visible after the prologue's barriers
-  const float tbias = (TQ && half == 0) ? (p.tb + z0 * p.tb_s0 + z1 * p.tb_s1)[0] : 0.f;
-  float* __restrict__ tqo = !TQ ? nullptr : (half == 0 ? p.tq + z0 * p.tq_s0 + z1 * p.tq_s1 : p.tq2 + z0 * p.tq2_s0 + z1 * p.tq2_s1);
+  const float tbias = (TQ && half == 0) ? (p.tb.p + z0 * p.tb.s0 + z1 * p.tb.s1)[0] : 0.f;
+  float* __restrict__ tqo = !TQ ? nullptr : (half == 0 ? p.tq.p + z0 * p.tq.s0 + z1 * p.tq.s1 : p.tq2.p + z0 * p.tq2.s0 + z1 * p.tq2.s1);
   const long tqsm = half == 0 ? p.tq_sm : 1;
   const float inv_sc = 1.0f / (ORL_WSCALE * a_sc);
 
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
       const unsigned int d0 = nb[0], d1 = nb[1];
       const unsigned int lo16 = (d0 & 0xFu) | ((d0 >> 4) & 0xF0u) | ((d0 >> 8) & 0xF00u) | ((d0 >> 12) & 0xF000u);
       const unsigned int hi16 = (d1 & 0xFu) | ((d1 >> 4) & 0xF0u) | ((d1 >> 8) & 0xF00u) | ((d1 >> 12) & 0xF000u);
-      p.mb0[z0 * p.mb0_s0 + z1 * p.mb0_s1 + ((long)g * WS_ROWS + row) * p.mb0_g + wd] = lo16 | (hi16 << 16);
+      p.mb0.p[z0 * p.mb0.s0 + z1 * p.mb0.s1 + ((long)g * WS_ROWS + row) * p.mb0_g + wd] = lo16 | (hi16 << 16);
     }
   };
   // the epilogue of one 16 x 16 block of h1 (row block s): bias, ReLU, tail partial sum, 4 mask bits -> LDS
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
       const unsigned int d0 = nb[0], d1 = nb[1];
       const unsigned int lo16 = (d0 & 0xFu) | ((d0 >> 4) & 0xF0u) | ((d0 >> 8) & 0xF00u) | ((d0 >> 12) & 0xF000u);
       const unsigned int hi16 = (d1 & 0xFu) | ((d1 >> 4) & 0xF0u) | ((d1 >> 8) & 0xF00u) | ((d1 >> 12) & 0xF000u);
-      p.mb[z0 * p.mb_s0 + z1 * p.mb_s1 + (long)m * p.mb_g + 4 * half + wd] = lo16 | (hi16 << 16);
+      p.mb.p[z0 * p.mb.s0 + z1 * p.mb.s1 + (long)m * p.mb_g + 4 * half + wd] = lo16 | (hi16 << 16);
     }
     if (TQ && tid >= WS_NT - WS_ROWS) {                                  // eight column-slice partial sums per row, fixed order
       const int row = tid - (WS_NT - WS_ROWS), m = g * WS_ROWS + row;
@@ -375,12 +375,12 @@ hipError_t launch_ws_fwd3(WsFwdP p, int nz, int per_z, hipStream_t st) {
   if (attr_err != hipSuccess) return attr_err;
   const dim3 grid(per_z, 2, nz), block(WS_NT);
   const size_t lds = ws_fwd3_lds_bytes();
-  const bool tq = p.tq != nullptr, sy = p.Y != nullptr, xs = !p.x0_discard;
-  if (p.dmask) {                                    // plain dgrad mode
+  const bool tq = p.tq.p != nullptr, sy = p.Y.p != nullptr, xs = !p.x0_discard;
+  if (p.dmask.p) {                                    // plain dgrad mode
     hipLaunchKernelGGL((ws_fwd3_kernel<false, true, false, false, true>), grid, block, lds, st, p);
     return hipGetLastError();
   }
-  if (!p.X0) {                                      // no fused first layer: the input rows are staged from HBM
+  if (!p.X0.p) {                                      // no fused first layer: the input rows are staged from HBM
     if (tq && !sy) hipLaunchKernelGGL((ws_fwd3_kernel<true, false, false, false>), grid, block, lds, st, p);
     else if (tq && sy) hipLaunchKernelGGL((ws_fwd3_kernel<true, true, false, false>), grid, block, lds, st, p);
     else if (!tq && sy) hipLaunchKernelGGL((ws_fwd3_kernel<false, true, false, false>), grid, block, lds, st, p);

@@ -35,34 +35,34 @@ namespace orl {
 #endif
 
 struct WsFwdP {
-  const float* X; long x_s0, x_s1; int x_pitch;        // input activations [z][M][K] fp32, K == 256
-  const float* W; long w_s0, w_s1;                      // weights of problem z; element (n, k) at W[n * w_sn + k * w_sk]:
+  ZPtr X; int x_pitch;                                  // input activations [z][M][K] fp32, K == 256
+  ZPtr W;                                               // weights of problem z; element (n, k) at W[n * w_sn + k * w_sk]:
   long w_sn, w_sk;                                      //   nn.Linear (out, in): w_sn = 256, w_sk = 1; EnsembleLinear (in, out): w_sn = 1, w_sk = 256
-  const float* bias; long b_s0, b_s1;
-  float* Y; long y_s0, y_s1; int y_pitch;               // relu(X W^T + b) [z][M][256]
-  unsigned int* mb; long mb_s0, mb_s1; int mb_g;        // packed ReLU mask of Y (gemm.h layout) or null
-  const float* tw; long tw_s0, tw_s1;                   // fused tail: q[m] = Y[m] . tw + tb  (null = off)
-  const float* tb; long tb_s0, tb_s1;
-  float* tq; long tq_s0, tq_s1, tq_sm;
+  ZPtr bias;
+  ZOut Y; int y_pitch;                                  // relu(X W^T + b) [z][M][256]
+  ZBits mb; int mb_g;                                   // packed ReLU mask of Y (gemm.h layout) or null
+  ZPtr tw;                                              // fused tail: q[m] = Y[m] . tw + tb  (null = off)
+  ZPtr tb;
+  ZOut tq; long tq_sm;
   unsigned long long* lab_clk;                          // lab builds (-DSB_LAB_CLOCK): shader-clock stamps of workgroup (0, 0, 0)
   int M, nz1, groups;                                   // groups = ceil(M / WS_ROWS)
   // fused first layer (template L0): X is then PRODUCED here as relu(X0 W0^T + b0) from the narrow input rows X0 (in0 + 1 <= 32 columns
   // incl. the bias as a ones column), stored to `X` for the backward pass, and handed to the second layer through LDS only
-  const float* X0; long x0_s0, x0_s1; int x0_pitch, in0;
+  ZPtr X0; int x0_pitch, in0;
   int x0_discard;               // fused first layer of a forward-only pass: h0 goes to LDS and its mask bits to HBM, the values are not stored
-  const float* W0; long w0_s0, w0_s1, w0_sn, w0_sk;     // element (n, k) at W0[n * w0_sn + k * w0_sk] ((256, in0) row-major: in0, 1)
-  const float* b0; long b0_s0, b0_s1;
-  unsigned int* mb0; long mb0_s0, mb0_s1; int mb0_g;    // packed ReLU mask of X (= h0)
+  ZPtr W0; long w0_sn, w0_sk;                           // element (n, k) at W0[n * w0_sn + k * w0_sk] ((256, in0) row-major: in0, 1)
+  ZPtr b0;
+  ZBits mb0; int mb0_g;                                 // packed ReLU mask of X (= h0)
   // plain dgrad mode (template DG): Y = (X B^T) (.) mask, B given by the strides above (W viewed transposed), no bias / ReLU / mask
   // emission; `dmask` = packed ReLU mask of the activation the gradient flows into
-  const unsigned int* dmask; long dm_s0, dm_s1; int dm_g;
+  ZBits dmask; int dm_g;
   int f32;                                              // exact fp32 arithmetic (v_mfma_f32_16x16x4_f32) instead of the split 16-bit planes
   const float* gscale;                                  // DG, split precision: dynamic power-of-two scale of the gradient rows X, one float per run (z0); null = 1
   // precision 2 (ws_fwd3_kernel: three fp16 planes; fused first layer + fused tail, top activation not stored): a workgroup owns half of the
   // columns, so the tail comes out as two partial sums -- half 0 writes tq (with the tail bias), half 1 tq2[z][m] (k_tail_add folds it in);
   // `dump`: WS_DUMP_SLOTS scratch lines of WS_N floats for the h0 blocks a half computes but does not own
   int np3;
-  float* tq2; long tq2_s0, tq2_s1;
+  ZOut tq2;
   float* dump;
 };
 enum { WS_DUMP_SLOTS = 8192 };
@@ -112,19 +112,19 @@ static inline int ws_blocks_per_problem(int groups, int nz, int prologue, int ca
 }
 
 static inline bool ws_fwd_supported(const WsFwdP& p, int K, int N) {
-  if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS) || (!p.mb && !p.dmask)) return false;
-  if (!aligned16(p.X) || (p.x_pitch & 3) || (p.x_s0 & 3) || (p.x_s1 & 3)) return false;
-  if (p.w_sk == 1 && (!aligned16(p.W) || (p.w_s0 & 3) || (p.w_s1 & 3) || (p.w_sn & 3))) return false;
-  if (p.dmask) { if (p.tq || p.X0 || p.dm_g != 8) return false; }
-  else if (!aligned16(p.bias) || (p.b_s0 & 3) || (p.b_s1 & 3)) return false;
-  if (!p.Y && (!p.tq || !p.mb)) return false;      // the activation may stay unstored only when the tail is folded in
-  if (!aligned16(p.Y) || (p.y_pitch & 3) || (p.y_s0 & 3) || (p.y_s1 & 3)) return false;
-  if (p.tq && (!aligned16(p.tw) || (p.tw_s0 & 3) || (p.tw_s1 & 3))) return false;
+  if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS) || (!p.mb.p && !p.dmask.p)) return false;
+  if (!p.X.vec4() || (p.x_pitch & 3)) return false;
+  if (p.w_sk == 1 && (!p.W.vec4() || (p.w_sn & 3))) return false;
+  if (p.dmask.p) { if (p.tq.p || p.X0.p || p.dm_g != 8) return false; }
+  else if (!p.bias.vec4()) return false;
+  if (!p.Y.p && (!p.tq.p || !p.mb.p)) return false;      // the activation may stay unstored only when the tail is folded in
+  if (!p.Y.vec4() || (p.y_pitch & 3)) return false;
+  if (p.tq.p && !p.tw.vec4()) return false;
   return true;
 }
 
 static inline bool ws_fwd01_supported(const WsFwdP& p) {      // extra conditions of the fused first layer
-  if (!p.X0 || !p.mb0 || p.mb0_g != 8 || p.in0 + 1 > 32 || p.in0 >= p.x0_pitch || p.x0_pitch > 32 || WS_ROWS * p.x0_pitch > 2 * WS_NT) return false;
+  if (!p.X0.p || !p.mb0.p || p.mb0_g != 8 || p.in0 + 1 > 32 || p.in0 >= p.x0_pitch || p.x0_pitch > 32 || WS_ROWS * p.x0_pitch > 2 * WS_NT) return false;
   return true;
 }
 hipError_t launch_ws_fwd(WsFwdP p, int nz, hipStream_t st, const WsGeom& geo);      // ws_fwd.hip
@@ -135,10 +135,10 @@ static constexpr size_t ws_fwd3_lds_bytes() {
 }
 static inline bool ws_fwd3_supported(const WsFwdP& p, int K, int N) {
   if (!ws_fwd_supported(p, K, N)) return false;
-  if (p.dmask) return p.Y != nullptr;                                             // plain dgrad mode (ws_fwd_supported: no tail, no fused first layer, 8 mask words per row)
-  if (p.tq && !p.tq2) return false;
-  const bool tq = p.tq != nullptr, sy = p.Y != nullptr, xs = !p.x0_discard;      // the flavours the engine's passes use (ws_fwd3.hip)
-  if (!p.X0) return (tq || sy) && (p.M % WS_ROWS) == 0;                           // input rows from HBM
+  if (p.dmask.p) return p.Y.p != nullptr;                                             // plain dgrad mode (ws_fwd_supported: no tail, no fused first layer, 8 mask words per row)
+  if (p.tq.p && !p.tq2.p) return false;
+  const bool tq = p.tq.p != nullptr, sy = p.Y.p != nullptr, xs = !p.x0_discard;      // the flavours the engine's passes use (ws_fwd3.hip)
+  if (!p.X0.p) return (tq || sy) && (p.M % WS_ROWS) == 0;                           // input rows from HBM
   if (!ws_fwd01_supported(p) || !p.dump) return false;
   return (tq && !sy) || (tq && sy && xs) || (!tq && sy);
 }
@@ -160,19 +160,19 @@ hipError_t launch_ws_fwd3(WsFwdP p, int nz, int per_z, hipStream_t st);         
 // split-K slab per workgroup.  dz0 itself never exists outside registers.
 // =====================================================================================================================
 struct WsDgradP {
-  const unsigned int* abits; long ab_s0, ab_s1; int ab_g;     // mask words of the top hidden activation (K = 256 columns)
-  const unsigned int* xbits; long xb_s0, xb_s1; int xb_g;     // mask words of the layer-0 activation (N = 256 columns)
-  const float* dq; long dq_s0, dq_s1, dq_sm;                   // dLoss/dq per row
-  const float* wt; long wt_s0, wt_s1;                          // w_tail [256]
-  const float* W; long w_s0, w_s1, w_sn, w_sk;                 // W1: element (k = output unit, n = input unit) at W[n * w_sn + k * w_sk]
+  ZBits abits; int ab_g;                                      // mask words of the top hidden activation (K = 256 columns)
+  ZBits xbits; int xb_g;                                      // mask words of the layer-0 activation (N = 256 columns)
+  ZPtr dq; long dq_sm;                                         // dLoss/dq per row
+  ZPtr wt;                                                     // w_tail [256]
+  ZPtr W; long w_sn, w_sk;                                     // W1: element (k = output unit, n = input unit) at W[n * w_sn + k * w_sk]
                                                                //   nn.Linear (out, in): w_sn = 1, w_sk = 256; EnsembleLinear (in, out): 256, 1
-  const float* X; long x_s0, x_s1; int x_pitch, in0;           // layer-0 input rows [M][x_pitch], in0 + 1 <= 32
-  float* w0_out; float* b0_out; long o_s0, o_s1, ob_s1, o_ks; int o_sr, o_sc;   // slab outputs (dW0 element (unit n, input c) at n * o_sr + c * o_sc: nn.Linear (in0, 1), EnsembleLinear (1, 256); db0 [256]); W0 variant
-  float* C; long c_s0, c_s1; int c_pitch;                      // dz0 [M][256]; STORE variant
+  ZPtr X; int x_pitch, in0;                                    // layer-0 input rows [M][x_pitch], in0 + 1 <= 32
+  float* w0_out; float* b0_out; long o_rs, o_ms, ob_ms, o_ks; int o_sr, o_sc;   // slab outputs, run / member / slab strides (dW0 element (unit n, input c) at n * o_sr + c * o_sc: nn.Linear (in0, 1), EnsembleLinear (1, 256); db0 [256]); W0 variant
+  ZOut C; int c_pitch;                                         // dz0 [M][256]; STORE variant
   // PLAIN variant (Z != nullptr; W0 only): the incoming gradient is a materialised matrix dz1 [M][256] (a hidden layer below the top
   // one) instead of (mask bits, dq, w_tail):  dz0 = 1[h0 > 0] * (dz1 W1),  dW0 / db0 as above.  The A image gets a lo plane (three
   // products per block), B' = W1 itself.
-  const float* Z; long z_s0, z_s1; int z_pitch;
+  ZPtr Z; int z_pitch;
   int M, nz1, groups;
   int f32;                                                     // exact fp32 arithmetic (ws_dgrad32_w0_kernel) instead of the split 16-bit planes
   const float* gscale;                                         // split precision: dynamic power-of-two scale applied to dq / dz1, one float per run (z0); null = 1
@@ -184,16 +184,15 @@ static constexpr size_t ws_dgrad_lds_bytes(bool plain = false) {     // mask ima
 
 static inline bool ws_dgrad_supported(const WsDgradP& p, int K, int N) {
   if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS)) return false;
-  if (p.Z) {
-    if (!p.w0_out || p.C || !p.xbits || p.xb_g != 8) return false;
-    if (!aligned16(p.Z) || (p.z_pitch & 3) || (p.z_s0 & 3) || (p.z_s1 & 3)) return false;
+  if (p.Z.p) {
+    if (!p.w0_out || p.C.p || !p.xbits.p || p.xb_g != 8) return false;
+    if (!p.Z.vec4() || (p.z_pitch & 3)) return false;
     return !(p.in0 + 1 > 32 || p.in0 >= p.x_pitch || p.x_pitch > 32 || WS_ROWS * p.x_pitch > 2 * WS_NT);
   }
-  if (!p.abits || !p.xbits || p.ab_g != 8 || p.xb_g != 8) return false;
+  if (!p.abits.p || !p.xbits.p || p.ab_g != 8 || p.xb_g != 8) return false;
   if (p.w0_out && (p.in0 + 1 > 32 || p.in0 >= p.x_pitch || p.x_pitch > 32 || WS_ROWS * p.x_pitch > 2 * WS_NT)) return false;
-  if (!p.w0_out && !p.C) return false;
-  if (!aligned16(p.wt) || (p.wt_s0 & 3) || (p.wt_s1 & 3)) return false;
-  return true;
+  if (!p.w0_out && !p.C.p) return false;
+  return p.wt.vec4();
 }
 // blocks per problem (= split-K slabs written per problem)
 static inline int ws_dgrad_blocks(int M, int nz, int max_slab, const WsGeom& geo, int prologue = 10) {
@@ -207,8 +206,8 @@ static constexpr size_t ws_dgrad3_lds_bytes(bool plain = false) {      // mask i
 }
 static inline bool ws_dgrad3_supported(const WsDgradP& p, int K, int N) {      // from mask bits: the W0 flavour (nothing stored) or the storing one; or the plain W0 flavour
   if (!ws_dgrad_supported(p, K, N)) return false;
-  if (p.Z) return true;                                                        // (ws_dgrad_supported checked w0_out / !C / xbits)
-  return (p.w0_out && !p.C) || (!p.w0_out && p.C);
+  if (p.Z.p) return true;                                                      // (ws_dgrad_supported checked w0_out / !C / xbits)
+  return (p.w0_out && !p.C.p) || (!p.w0_out && p.C.p);
 }
 hipError_t launch_ws_dgrad3_w0(WsDgradP p, int nz, int per_z, hipStream_t st);     // ws_dgrad3.hip
 
@@ -229,32 +228,32 @@ hipError_t launch_ws_dgrad3_w0(WsDgradP p, int nz, int per_z, hipStream_t st);  
 // of each iteration (a full iteration in flight).  One split-K slab per workgroup.
 // =====================================================================================================================
 struct WsWgradP {
-  const unsigned int* abits; long ab_s0, ab_s1; int ab_g;     // mask words of the top hidden activation h1
-  const float* dq; long dq_s0, dq_s1, dq_sm;
-  const float* H0; long h0_s0, h0_s1; int h0_pitch;            // input of the top hidden layer [M][256]
-  const float* wt; long wt_s0, wt_s1;                          // w_tail [256]
-  float *dW, *db;                                              // slab outputs; run stride o_s0, member strides below, slab stride o_ks
-  long o_s0, o_s1w, o_s1b, o_ks;
+  ZBits abits; int ab_g;                                      // mask words of the top hidden activation h1
+  ZPtr dq; long dq_sm;
+  ZPtr H0; int h0_pitch;                                       // input of the top hidden layer [M][256]
+  ZPtr wt;                                                     // w_tail [256]
+  float *dW, *db;                                              // slab outputs; run stride o_rs, member strides o_ms*, slab stride o_ks
+  long o_rs, o_msw, o_msb, o_ks;
   // TAILS variant: h1 itself is streamed too (through registers only) and the launch also produces the tail layer's gradients
   //   dw_tail[k] = sum_m dq[m] h1[m][k],  db_tail = sum_m dq[m];  db1 then comes from the same pass (no MFMA operand for it)
-  const float* H1; long h1_s0, h1_s1; int h1_pitch;
-  float *dwt, *dbt; long o_s1wt, o_s1bt;
+  ZPtr H1; int h1_pitch;
+  float *dwt, *dbt; long o_mswt, o_msbt;
   // DERIVED variant (H1 == nullptr, W1 != nullptr): h1 was never stored.  With G[n][k] = sum_m dq[m] 1[h1[m][n] > 0] h0[m][k] (the
   // accumulators before the w_tail scaling) and g[n] = sum_m dq[m] 1[h1[m][n] > 0], h1 = relu(h0 W1^T + b1) gives
   //   dw_tail[n] = sum_m dq[m] h1[m][n] = sum_k W1[n][k] G[n][k] + b1[n] g[n]      (linear in G, so it holds per slab)
-  const float* W1; long w1_s0, w1_s1;                          // [256][256] (out, in) row-major
-  const float* b1; long b1_s0, b1_s1;
+  ZPtr W1;                                                     // [256][256] (out, in) row-major
+  ZPtr b1;
   // PLAIN variant (dZ != nullptr): the gradient w.r.t. this layer's output is a materialised matrix (a hidden layer below the top one):
   //   dW[k][n] = sum_m dZ[m][k] * H0[m][n],  db[k] = sum_m dZ[m][k]
   // Same output-stationary structure; the A operand has a lo plane now (three products per block instead of two), no mask, no w_tail.
-  const float* dZ; long dz_s0, dz_s1; int dz_pitch;
+  ZPtr dZ; int dz_pitch;
   // RECOMPUTE variant of PLAIN (X0 != nullptr): H0 = relu(X0 W0^T + b0) was NOT stored by the forward pass (a three-layer net's first hidden
   // activation: 2 GB written and 2 GB read per step at 128 runs for a matrix that 12 MFMAs per wave and row group rebuild from a 24-column
   // input).  Every wave reproduces its own 32 columns of the group with the forward's instruction sequence (bit-identical values) straight
   // into the H image.  in0 + 1 <= 32, x0_pitch <= 32.
-  const float* X0; long x0_s0, x0_s1; int x0_pitch, in0;
-  const float* W0; long w0_s0, w0_s1, w0_sn, w0_sk;
-  const float* b0; long b0_s0, b0_s1;
+  ZPtr X0; int x0_pitch, in0;
+  ZPtr W0; long w0_sn, w0_sk;
+  ZPtr b0;
   unsigned long long* lab_clk;                                 // lab builds (-DSB_LAB_CLOCK): shader-clock stamps of workgroup (0, 0, 0)
   int M, nz1, groups;
   int f32;                                                     // exact fp32 arithmetic (ws_wgrad32_kernel) instead of the split 16-bit planes
@@ -267,25 +266,25 @@ static constexpr size_t ws_wgrad_lds_bytes(bool plain = false, bool recompute = 
 }
 
 static inline bool ws_wgrad_supported(const WsWgradP& p, int K, int N) {
-  if (p.dZ) {
+  if (p.dZ.p) {
     if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS)) return false;
-    if (!aligned16(p.dZ) || (p.dz_pitch & 3) || (p.dz_s0 & 3) || (p.dz_s1 & 3)) return false;
-    if (p.X0) return p.W0 && p.b0 && p.in0 + 1 <= 32 && p.in0 < p.x0_pitch + 1 && p.x0_pitch <= 32 && p.in0 <= p.x0_pitch && WS_ROWS * p.x0_pitch <= 2 * WS_NT;
-    return aligned16(p.H0) && !(p.h0_pitch & 3) && !(p.h0_s0 & 3) && !(p.h0_s1 & 3);
+    if (!p.dZ.vec4() || (p.dz_pitch & 3)) return false;
+    if (p.X0.p) return p.W0.p && p.b0.p && p.in0 + 1 <= 32 && p.in0 < p.x0_pitch + 1 && p.x0_pitch <= 32 && p.in0 <= p.x0_pitch && WS_ROWS * p.x0_pitch <= 2 * WS_NT;
+    return p.H0.vec4() && !(p.h0_pitch & 3);
   }
-  if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS) || !p.abits || p.ab_g != 8) return false;
-  if (p.np3 && (p.H1 || !p.W1)) return false;
-  if (!aligned16(p.H0) || (p.h0_pitch & 3) || (p.h0_s0 & 3) || (p.h0_s1 & 3)) return false;
-  if (!p.H1 && p.W1 && (!p.b1 || !p.dwt || !p.dbt)) return false;
-  if (p.H1 && (!aligned16(p.H1) || (p.h1_pitch & 3) || (p.h1_s0 & 3) || (p.h1_s1 & 3) || !p.dwt || !p.dbt)) return false;
-  return aligned16(p.wt) && !(p.wt_s0 & 3) && !(p.wt_s1 & 3);
+  if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS) || !p.abits.p || p.ab_g != 8) return false;
+  if (p.np3 && (p.H1.p || !p.W1.p)) return false;
+  if (!p.H0.vec4() || (p.h0_pitch & 3)) return false;
+  if (!p.H1.p && p.W1.p && (!p.b1.p || !p.dwt || !p.dbt)) return false;
+  if (p.H1.p && (!p.H1.vec4() || (p.h1_pitch & 3) || !p.dwt || !p.dbt)) return false;
+  return p.wt.vec4();
 }
 hipError_t launch_ws_wgrad(WsWgradP p, int nz, int per_z, hipStream_t st);      // ws_wgrad.hip
 // precision 2, plain (materialised dZ) flavour: three planes of both operands; a workgroup owns half of the output rows (grid.y = 2)
 // (ws_wgrad3p.hip).  LDS: 2 buffers x {3 x [32][128] dZ planes, 3 x [32][256] H0 planes} + the ones block
 static constexpr size_t ws_wgrad3p_lds_bytes() { return (size_t)2 * (3 * WS_ROWS * 128 + 3 * WS_ROWS * WS_K) * 2 + (size_t)WS_ROWS * 16 * 2; }
 static inline bool ws_wgrad3p_supported(const WsWgradP& p, int K, int N) {
-  return p.dZ && !p.X0 && ws_wgrad_supported(p, K, N);
+  return p.dZ.p && !p.X0.p && ws_wgrad_supported(p, K, N);
 }
 hipError_t launch_ws_wgrad3p(WsWgradP p, int nz, int per_z, hipStream_t st);     // ws_wgrad3p.hip
 

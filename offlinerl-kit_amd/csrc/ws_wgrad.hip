@@ -26,15 +26,15 @@ __device__ __forceinline__ void ww_finish(const WsWgradP& p, float* ws_smem, con
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   // `inv`: the MFMA accumulators (acc, accb) carry the dynamic gradient scale of the split-precision kernel; tacc / bacc / dqsum do not
   // ---- one slab per workgroup ----
-  const long so = z0 * p.o_s0 + (long)blockIdx.x * p.o_ks;
-  float* dW = p.dW + so + z1 * p.o_s1w;
-  float* db = p.db + so + z1 * p.o_s1b;
+  const long so = z0 * p.o_rs + (long)blockIdx.x * p.o_ks;
+  float* dW = p.dW + so + z1 * p.o_msw;
+  float* db = p.db + so + z1 * p.o_msb;
   // ---- MODE 2, first: the tail gradient's partial sums (they need the accumulators and W1 only) BEFORE the slab stores -- vmcnt returns
   // in order, so a load issued behind 128 stores waits for all of them.  The W1 elements are fetched 16 at a time (one exposed L2 latency
   // per two k blocks; one load -> wait -> multiply round trip per element cost ~40 us per workgroup), and the 16 lanes of a row group are
   // summed with DPP row operations on the vector ALU instead of four dependent ds_bpermute round trips per element.
   if (MODE == 2) {
-    const float* __restrict__ W1g = p.W1 + z0 * p.w1_s0 + z1 * p.w1_s1;
+    const float* __restrict__ W1g = p.W1.p + z0 * p.W1.s0 + z1 * p.W1.s1;
     float* red = ws_smem;                                            // the images are dead after the loop's last barrier
 #pragma unroll
     for (int kb2 = 0; kb2 < 16; kb2 += 2) {
@@ -104,14 +104,14 @@ __device__ __forceinline__ void ww_finish(const WsWgradP& p, float* ws_smem, con
 #pragma unroll
       for (int w = 0; w < 8; ++w) a += red[w * WS_K + tid];
       const float gs1 = red[8 * WS_K + tid];
-      p.dwt[so + z1 * p.o_s1wt + tid] = a + (p.b1 + z0 * p.b1_s0 + z1 * p.b1_s1)[tid] * gs1;
+      p.dwt[so + z1 * p.o_mswt + tid] = a + (p.b1.p + z0 * p.b1.s0 + z1 * p.b1.s1)[tid] * gs1;
       db[tid] = wtg[tid] * gs1;
     }
     if (tid == 0) {
       float a = 0.f;
 #pragma unroll
       for (int w = 0; w < 8; ++w) a += red[9 * WS_K + w];
-      p.dbt[so + z1 * p.o_s1bt] = a;
+      p.dbt[so + z1 * p.o_msbt] = a;
     }
     return;
   }
@@ -136,14 +136,14 @@ __device__ __forceinline__ void ww_finish(const WsWgradP& p, float* ws_smem, con
     float a = 0.f, b = 0.f;
 #pragma unroll
     for (int w = 0; w < 8; ++w) { a += red[w * WS_K + tid]; b += red[(8 + w) * WS_K + tid]; }
-    p.dwt[so + z1 * p.o_s1wt + tid] = a;
+    p.dwt[so + z1 * p.o_mswt + tid] = a;
     db[tid] = wtg[tid] * b;
   }
   if (tid == 0) {
     float a = 0.f;
 #pragma unroll
     for (int w = 0; w < 8; ++w) a += red[16 * WS_K + w];
-    p.dbt[so + z1 * p.o_s1bt] = a;
+    p.dbt[so + z1 * p.o_msbt] = a;
   }
 }
 
@@ -163,10 +163,10 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad_kernel(const WsWgradP p) {
   __shared__ u32x2_t mlut[16];                                      // 4 mask bits -> 4 bf16 values
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
-  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits + z0 * p.ab_s0 + z1 * p.ab_s1;
-  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq + z0 * p.dq_s0 + z1 * p.dq_s1;
-  const float* __restrict__ H0g = p.H0 + z0 * p.h0_s0 + z1 * p.h0_s1;
-  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt + z0 * p.wt_s0 + z1 * p.wt_s1;
+  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits.p + z0 * p.abits.s0 + z1 * p.abits.s1;
+  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq.p + z0 * p.dq.s0 + z1 * p.dq.s1;
+  const float* __restrict__ H0g = p.H0.p + z0 * p.H0.s0 + z1 * p.H0.s1;
+  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt.p + z0 * p.wt.s0 + z1 * p.wt.s1;
   const int ncol0 = 32 * wave;
   // split precision: G = (dq * gs) (.) h0 (PLAIN: dZ * gs) with the run's dynamic power-of-two gradient scale gs, divided out of the slab in ww_finish
   const float gsc = p.gscale ? p.gscale[z0] : 1.f;
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad_kernel(const WsWgradP p) {
   f32x4 tacc = (f32x4){0.f, 0.f, 0.f, 0.f}, bacc = (f32x4){0.f, 0.f, 0.f, 0.f};   // TAILS: dw_tail / db1 partials of columns 4 (tid & 63) ..
   float dqsum = 0.f;
   // second streamed matrix: TAILS h1 (registers only), PLAIN dZ (the A operand)
-  const float* __restrict__ H1g = TAILS ? p.H1 + z0 * p.h1_s0 + z1 * p.h1_s1 : (PLAIN ? p.dZ + z0 * p.dz_s0 + z1 * p.dz_s1 : nullptr);
+  const float* __restrict__ H1g = TAILS ? p.H1.p + z0 * p.H1.s0 + z1 * p.H1.s1 : (PLAIN ? p.dZ.p + z0 * p.dZ.s0 + z1 * p.dZ.s1 : nullptr);
   const int h1_pitch = PLAIN ? p.dz_pitch : p.h1_pitch;
   float sdq[4];
   unsigned int sm_word;
@@ -193,11 +193,11 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad_kernel(const WsWgradP p) {
   // ---- RECOMP: first-layer fragments of this wave's 32 columns (K = 32: W0'[n][k] = W0[n][k] (k < in0), b0[n] (k == in0), 0 beyond) and the
   // staging of the narrow input rows -- ws_fwd_kernel<., L0>'s producer, writing into this kernel's H image ----
   float* Xl = (float*)(dqimg + 2 * DQP * WS_ROWS * 16);             // [buf][32][WS_XLP]: hi plane in 16-bit slots 0..31, lo plane in 32..63 of a row
-  const float* __restrict__ X0g = RECOMP ? p.X0 + z0 * p.x0_s0 + z1 * p.x0_s1 : nullptr;
+  const float* __restrict__ X0g = RECOMP ? p.X0.p + z0 * p.X0.s0 + z1 * p.X0.s1 : nullptr;
   hx8 b0h[2], b0l[2];
   if (RECOMP) {
-    const float* __restrict__ W0g = p.W0 + z0 * p.w0_s0 + z1 * p.w0_s1;
-    const float* __restrict__ b0g = p.b0 + z0 * p.b0_s0 + z1 * p.b0_s1;
+    const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
+    const float* __restrict__ b0g = p.b0.p + z0 * p.b0.s0 + z1 * p.b0.s1;
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
       const int n = ncol0 + 16 * cb + li;
@@ -515,11 +515,11 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad32_kernel(const WsWgradP p) {
   __shared__ f32x4 mlut[16];                                        // 4 mask bits -> 4 floats (0.0 / 1.0)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
-  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits + z0 * p.ab_s0 + z1 * p.ab_s1;
-  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq + z0 * p.dq_s0 + z1 * p.dq_s1;
-  const float* __restrict__ H0g = p.H0 + z0 * p.h0_s0 + z1 * p.h0_s1;
-  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt + z0 * p.wt_s0 + z1 * p.wt_s1;
-  const float* __restrict__ H1g = TAILS ? p.H1 + z0 * p.h1_s0 + z1 * p.h1_s1 : (PLAIN ? p.dZ + z0 * p.dz_s0 + z1 * p.dz_s1 : nullptr);
+  const unsigned int* __restrict__ ab = PLAIN ? nullptr : p.abits.p + z0 * p.abits.s0 + z1 * p.abits.s1;
+  const float* __restrict__ dqg = PLAIN ? nullptr : p.dq.p + z0 * p.dq.s0 + z1 * p.dq.s1;
+  const float* __restrict__ H0g = p.H0.p + z0 * p.H0.s0 + z1 * p.H0.s1;
+  const float* __restrict__ wtg = PLAIN ? nullptr : p.wt.p + z0 * p.wt.s0 + z1 * p.wt.s1;
+  const float* __restrict__ H1g = TAILS ? p.H1.p + z0 * p.H1.s0 + z1 * p.H1.s1 : (PLAIN ? p.dZ.p + z0 * p.dZ.s0 + z1 * p.dZ.s1 : nullptr);
   const int h1_pitch = PLAIN ? p.dz_pitch : p.h1_pitch;
   const int ncol0 = 32 * wave;
 
@@ -536,11 +536,11 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad32_kernel(const WsWgradP p) {
   float sdq[4];
   unsigned int sm_word;
   // ---- RECOMP: first-layer fragments (k = 16 t + 4 lq + e) of this wave's columns and the narrow-input staging (ws_fwd_kernel<., L0, ., ., F32>) ----
-  const float* __restrict__ X0g = RECOMP ? p.X0 + z0 * p.x0_s0 + z1 * p.x0_s1 : nullptr;
+  const float* __restrict__ X0g = RECOMP ? p.X0.p + z0 * p.X0.s0 + z1 * p.X0.s1 : nullptr;
   f32x4 b0w[2][2];
   if (RECOMP) {
-    const float* __restrict__ W0g = p.W0 + z0 * p.w0_s0 + z1 * p.w0_s1;
-    const float* __restrict__ b0g = p.b0 + z0 * p.b0_s0 + z1 * p.b0_s1;
+    const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
+    const float* __restrict__ b0g = p.b0.p + z0 * p.b0.s0 + z1 * p.b0.s1;
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
       const int n = ncol0 + 16 * cb + li;
@@ -741,12 +741,12 @@ hipError_t launch_ws_wgrad(WsWgradP p, int nz, int per_z, hipStream_t st) {
   }();
   if (attr_err != hipSuccess) return attr_err;
   const dim3 grid(per_z, 1, nz), block(WS_NT);
-  if (p.dZ && p.X0) {                              // ... with the layer's input activation recomputed from the net's narrow input
+  if (p.dZ.p && p.X0.p) {                              // ... with the layer's input activation recomputed from the net's narrow input
     if (p.f32) hipLaunchKernelGGL(ws_wgrad32_kernel<4>, grid, block, ws_wgrad32_lds_bytes(true), st, p);
     else hipLaunchKernelGGL(ws_wgrad_kernel<4>, grid, block, ws_wgrad_lds_bytes(true, true), st, p);
     return hipGetLastError();
   }
-  if (p.dZ) {                                      // plain (materialised) gradient: a hidden layer below the top one
+  if (p.dZ.p) {                                      // plain (materialised) gradient: a hidden layer below the top one
     if (p.f32) hipLaunchKernelGGL(ws_wgrad32_kernel<3>, grid, block, ws_wgrad32_lds_bytes(), st, p);
     else hipLaunchKernelGGL(ws_wgrad_kernel<3>, grid, block, ws_wgrad_lds_bytes(true), st, p);
     return hipGetLastError();
@@ -756,13 +756,13 @@ hipError_t launch_ws_wgrad(WsWgradP p, int nz, int per_z, hipStream_t st) {
     return hipGetLastError();
   }
   if (p.f32) {
-    if (p.H1) hipLaunchKernelGGL(ws_wgrad32_kernel<1>, grid, block, ws_wgrad32_lds_bytes(), st, p);
-    else if (p.W1) hipLaunchKernelGGL(ws_wgrad32_kernel<2>, grid, block, ws_wgrad32_lds_bytes(), st, p);
+    if (p.H1.p) hipLaunchKernelGGL(ws_wgrad32_kernel<1>, grid, block, ws_wgrad32_lds_bytes(), st, p);
+    else if (p.W1.p) hipLaunchKernelGGL(ws_wgrad32_kernel<2>, grid, block, ws_wgrad32_lds_bytes(), st, p);
     else hipLaunchKernelGGL(ws_wgrad32_kernel<0>, grid, block, ws_wgrad32_lds_bytes(), st, p);
     return hipGetLastError();
   }
-  if (p.H1) hipLaunchKernelGGL(ws_wgrad_kernel<1>, grid, block, ws_wgrad_lds_bytes(), st, p);
-  else if (p.W1) hipLaunchKernelGGL(ws_wgrad_kernel<2>, grid, block, ws_wgrad_lds_bytes(), st, p);
+  if (p.H1.p) hipLaunchKernelGGL(ws_wgrad_kernel<1>, grid, block, ws_wgrad_lds_bytes(), st, p);
+  else if (p.W1.p) hipLaunchKernelGGL(ws_wgrad_kernel<2>, grid, block, ws_wgrad_lds_bytes(), st, p);
   else hipLaunchKernelGGL(ws_wgrad_kernel<0>, grid, block, ws_wgrad_lds_bytes(), st, p);
   return hipGetLastError();
 }

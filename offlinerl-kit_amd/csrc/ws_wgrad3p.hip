@@ -34,8 +34,8 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad3p_kernel(const WsWgradP p) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int half = blockIdx.y;
   const int z = blockIdx.z, z0 = z / p.nz1, z1 = z - z0 * p.nz1;
-  const float* __restrict__ H0g = p.H0 + z0 * p.h0_s0 + z1 * p.h0_s1;
-  const float* __restrict__ Zg = p.dZ + z0 * p.dz_s0 + z1 * p.dz_s1 + W3_ZK * half;      // this half's 128 columns of dZ
+  const float* __restrict__ H0g = p.H0.p + z0 * p.H0.s0 + z1 * p.H0.s1;
+  const float* __restrict__ Zg = p.dZ.p + z0 * p.dZ.s0 + z1 * p.dZ.s1 + W3_ZK * half;      // this half's 128 columns of dZ
   const int ncol0 = 32 * wave;
   const float gsc = p.gscale ? p.gscale[z0] : 1.f;                   // dZ enters times the run's dynamic gradient scale, divided out of the slab
 
@@ -166,9 +166,9 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad3p_kernel(const WsWgradP p) {
 
   // ---- one slab per workgroup pair: this half's rows k = 128 half + 16 kb + 4 lq + r, columns n = ncol0 + 16 nb + li ----
   const float inv = 1.0f / gsc;
-  const long so = z0 * p.o_s0 + (long)blockIdx.x * p.o_ks;
-  float* dW = p.dW + so + z1 * p.o_s1w;
-  float* db = p.db + so + z1 * p.o_s1b;
+  const long so = z0 * p.o_rs + (long)blockIdx.x * p.o_ks;
+  float* dW = p.dW + so + z1 * p.o_msw;
+  float* db = p.db + so + z1 * p.o_msb;
 #pragma unroll
   for (int kb = 0; kb < 8; ++kb)
 #pragma unroll
