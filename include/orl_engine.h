@@ -255,6 +255,16 @@ int orl_buffer_append(orl_buffer* b, const float* obs, const float* act, const f
  * orl_health_check like any other operand. */
 int orl_buffer_append_rollout(orl_buffer* b, int32_t term_kind, const float* obs, const float* act, const float* next_obs,
                               const float* rew, int64_t n, float* alive_next_obs, int64_t* n_alive, double* rew_sum);
+/* orl_buffer_append_rollout for n_runs rings in ONE launch pair (the per-run model rings of a multi-run MOPO / COMBO policy).  The
+ * sources are packed DEVICE arrays [n_runs][row_stride][dim] (rew [n_runs][row_stride]) of which run r owns the first n[r] rows
+ * (0 <= n[r] <= row_stride, n[r] == 0 is legal); alive_next_obs has the layout of next_obs and receives run r's surviving rows densely,
+ * in order, at the head of run r's block -- rows past n_alive[r] are not written.  Ring r advances by n[r]: every ring keeps its own
+ * write position, size and device size cell.  n, n_alive and rew_sum are HOST arrays of n_runs entries; the 2 * n_runs results come
+ * back in one device-to-host copy.  The rings are distinct, reserved, of one shape and on one device; the refusals of the single-ring
+ * call are made per ring and name the run. */
+int orl_buffer_append_rollout_runs(orl_buffer* const* rings, int32_t n_runs, int32_t term_kind, const float* obs, const float* act,
+                                   const float* next_obs, const float* rew, int64_t row_stride, const int64_t* n, float* alive_next_obs,
+                                   int64_t* n_alive, double* rew_sum);
 /* rows [row0, row0 + n) of the store back to packed host arrays (sample_all, buffer/buffer.py:108-115, and tests); a ring may be read
  * up to its capacity (rows never written are zero) */
 int orl_buffer_read(orl_buffer* b, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term);
@@ -263,6 +273,11 @@ int orl_buffer_read(orl_buffer* b, int64_t row0, int64_t n, float* obs, float* a
  * ring `model`; every row keeps its Philox counter.  0 < real_rows < batch_size, same dims and device as the engine; NULL detaches.
  * orl_learn_n fails while the ring is empty and, for CQL engines, when real_rows differs from cql_real_rows. */
 int orl_engine_attach_model_buffer(orl_engine* e, orl_buffer* model, int32_t real_rows);
+/* one model ring PER RUN: the model rows of run r's minibatches are drawn from models[r] only, with that ring's size read from its own
+ * device cell.  n must equal the engine's n_runs; real_rows as above; every ring has the engine's dims and device.  orl_learn_n fails
+ * while any run's ring is empty (the message names the run); a new reserve of any ring re-captures the graphs.  NULL or n == 0 detaches.
+ * Attaching one form (this or orl_engine_attach_model_buffer) replaces the other. */
+int orl_engine_attach_model_buffers(orl_engine* e, orl_buffer* const* models, int32_t n, int32_t real_rows);
 
 /* -- the hot path ---------------------------------------------------------------- */
 /* policy.learn(batch) with explicit noise: one gradient step for every run.

@@ -105,6 +105,9 @@ struct Buffer {             // HBM-resident replay buffer (buffer/buffer.py)
   long cap = 0, ptr = 0;
   long long* d_n = nullptr;
   int* roll_alive = nullptr; double* roll_rew = nullptr; long roll_blocks = 0;   // per-block scratch of k_roll_term / k_roll_scatter, then 2 result cells
+  // orl_buffer_append_rollout_runs keeps its scratch with the FIRST ring of the call: [runs] ring table, [runs] alive counts, [runs]
+  // reward sums (the two read back in one copy), then [runs][blocks] reward sums and alive counts
+  void* runs_scratch = nullptr; long runs_scratch_runs = 0, runs_scratch_blocks = 0;
   ~Buffer();
 };
 
@@ -157,6 +160,12 @@ struct Engine {
   Buffer* mbuf = nullptr;      // model-rollout ring (orl_engine_attach_model_buffer, not owned): batch rows [mbuf_real_rows, B) are drawn from it
   int mbuf_real_rows = 0;
   unsigned long long mbuf_gen = 0;
+  // per-run model rings (orl_engine_attach_model_buffers, not owned): run r draws its model rows from mbufs[r] through m_tab[r]; either
+  // this or mbuf is set, never both
+  std::vector<Buffer*> mbufs;
+  std::vector<unsigned long long> mbufs_gen;
+  ModelSrc* m_tab = nullptr;   // [R], device
+  int upload_model_table();
   void drop_graphs();
   // split-K slab table of the last adam() launch per net (orl_debug_grads sums the slabs the way k_adam does)
   std::vector<std::pair<long, int>> last_segs[ORL_NUM_NETS];

@@ -196,6 +196,7 @@ Buffer::~Buffer() {
   if (d_n) hipFree(d_n);
   if (roll_alive) hipFree(roll_alive);
   if (roll_rew) hipFree(roll_rew);
+  if (runs_scratch) hipFree(runs_scratch);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1269,6 +1270,9 @@ int Engine::enqueue_sample() {
     g.m_obs = mbuf->obs; g.m_nobs = mbuf->nobs; g.m_act = mbuf->act; g.m_rew = mbuf->rew; g.m_term = mbuf->term;
     g.m_n = mbuf->d_n; g.real_rows = mbuf_real_rows;
   }
+  if (!mbufs.empty()) {      // per-run rings: the table carries the sources, m_obs only says that there is a model source
+    g.m_tab = m_tab; g.m_obs = mbufs[0]->obs; g.real_rows = mbuf_real_rows;
+  }
   ORL_LAUNCH("gather", k_gather, dim3((unsigned)(((long)B * g.W + 255) / 256), R), dim3(256), g);
   return 0;
 }
@@ -1328,6 +1332,9 @@ int Engine::enqueue_prepare(bool sampling, bool devnoise) {
     if (mbuf) {
       p.m_obs = mbuf->obs; p.m_nobs = mbuf->nobs; p.m_act = mbuf->act; p.m_rew = mbuf->rew; p.m_term = mbuf->term;
       p.m_n = mbuf->d_n; p.real_rows = mbuf_real_rows;
+    }
+    if (!mbufs.empty()) {      // per-run rings: the table carries the sources, m_obs only says that there is a model source
+      p.m_tab = m_tab; p.m_obs = mbufs[0]->obs; p.real_rows = mbuf_real_rows;
     }
   }
   Mat o2 = W("b_obs2");
@@ -1655,8 +1662,9 @@ int orl_buffer_append_rollout(orl_buffer* h, int32_t term_kind, const float* obs
   }
   RollP p;
   memset(&p, 0, sizeof(p));
-  p.kind = term_kind; p.obs = obs; p.act = act; p.nobs = next_obs; p.rew = rew; p.n = n; p.od = b.od; p.ad = b.ad;
-  p.r_obs = b.obs; p.r_nobs = b.nobs; p.r_act = b.act; p.r_rew = b.rew; p.r_term = b.term; p.OP = b.OP; p.AP = b.AP; p.cap = b.cap; p.ptr = b.ptr;
+  p.kind = term_kind; p.obs = obs; p.act = act; p.nobs = next_obs; p.rew = rew; p.row_stride = n; p.od = b.od; p.ad = b.ad;
+  RollRing& g = p.ring;
+  g.obs = b.obs; g.nobs = b.nobs; g.act = b.act; g.rew = b.rew; g.term = b.term; g.OP = b.OP; g.AP = b.AP; g.cap = b.cap; g.ptr = b.ptr; g.n = n;
   p.alive_nobs = alive_next_obs;
   p.blk_alive = b.roll_alive; p.blk_rew = b.roll_rew;
   p.n_alive_out = (long long*)(b.roll_alive + ((b.roll_blocks + 1) & ~1L));      // 8-byte aligned, behind the block counts
@@ -1671,6 +1679,81 @@ int orl_buffer_append_rollout(orl_buffer* h, int32_t term_kind, const float* obs
   b.ptr = (b.ptr + n) % b.cap;
   b.n = std::min(b.n + (long)n, b.cap);
   return ring_publish(b);
+}
+int orl_buffer_append_rollout_runs(orl_buffer* const* rings, int32_t n_runs, int32_t term_kind, const float* obs, const float* act,
+                                   const float* next_obs, const float* rew, int64_t row_stride, const int64_t* n, float* alive_next_obs,
+                                   int64_t* n_alive, double* rew_sum) {
+  const char* F = "orl_buffer_append_rollout_runs";
+  if (!rings || n_runs < 1 || !obs || !act || !next_obs || !rew || !alive_next_obs || !n || !n_alive || !rew_sum || row_stride < 1)
+    return fail(std::string(F) + ": bad arguments");
+  if (term_kind < 0 || term_kind >= ORL_TERM_KINDS) return fail(std::string(F) + ": unknown termination kind");
+  if (alive_next_obs == next_obs) return fail(std::string(F) + ": alive_next_obs must not overlap next_obs");
+  const int need = term_kind == ORL_TERM_PEN ? 27 : ((term_kind == ORL_TERM_HOPPER || term_kind == ORL_TERM_WALKER2D) ? 2 : 1);
+  char msg[224];
+  long nmax = 0;
+  for (int r = 0; r < n_runs; ++r) {
+    if (!rings[r]) { snprintf(msg, sizeof(msg), "%s: run %d: null ring", F, r); return fail(msg); }
+    const Buffer& b = rings[r]->b;
+    const Buffer& b0 = rings[0]->b;
+    for (int q = 0; q < r; ++q)
+      if (rings[q] == rings[r]) { snprintf(msg, sizeof(msg), "%s: run %d: the ring of run %d again (one ring per run)", F, r, q); return fail(msg); }
+    if (b.cap < 1) { snprintf(msg, sizeof(msg), "%s: run %d: not a ring (orl_buffer_reserve first)", F, r); return fail(msg); }
+    if (b.od != b0.od || b.ad != b0.ad || b.dev != b0.dev) {
+      snprintf(msg, sizeof(msg), "%s: run %d: dims / device (%d, %d, device %d) differ from run 0's (%d, %d, device %d)", F, r, b.od, b.ad, b.dev,
+               b0.od, b0.ad, b0.dev);
+      return fail(msg);
+    }
+    if (n[r] < 0 || n[r] > row_stride) { snprintf(msg, sizeof(msg), "%s: run %d: %lld rows do not fit the row stride %lld", F, r, (long long)n[r], (long long)row_stride); return fail(msg); }
+    if (n[r] > b.cap) { snprintf(msg, sizeof(msg), "%s: run %d: more rows than the ring's capacity", F, r); return fail(msg); }
+    if (b.od < need) {
+      snprintf(msg, sizeof(msg), "%s: run %d: termination kind %d reads observation column %d, the buffer has %d columns", F, r, (int)term_kind, need - 1, b.od);
+      return fail(msg);
+    }
+    nmax = std::max(nmax, (long)n[r]);
+  }
+  Buffer& b0 = rings[0]->b;
+  ORL_HIP(hipSetDevice(b0.dev));
+  const long R = n_runs, blocks = std::max(1L, (nmax + 255) / 256);
+  if (R > b0.runs_scratch_runs || blocks > b0.runs_scratch_blocks) {
+    const long cr = std::max(R, b0.runs_scratch_runs), cb = std::max(blocks, b0.runs_scratch_blocks);
+    if (b0.runs_scratch) hipFree(b0.runs_scratch);
+    b0.runs_scratch = nullptr; b0.runs_scratch_runs = 0; b0.runs_scratch_blocks = 0;
+    ORL_HIP(hipMalloc(&b0.runs_scratch, cr * (sizeof(RollRing) + 16) + cr * cb * 12));
+    b0.runs_scratch_runs = cr; b0.runs_scratch_blocks = cb;
+  }
+  // (every piece is a multiple of 8 bytes long except the last)
+  RollRing* tab = (RollRing*)b0.runs_scratch;
+  long long* out_n = (long long*)(tab + b0.runs_scratch_runs);
+  double* out_rew = (double*)(out_n + R);
+  double* blk_rew = (double*)(out_n + 2 * b0.runs_scratch_runs);
+  int* blk_alive = (int*)(blk_rew + b0.runs_scratch_runs * b0.runs_scratch_blocks);
+  std::vector<RollRing> host(R);
+  for (int r = 0; r < n_runs; ++r) {
+    const Buffer& b = rings[r]->b;
+    RollRing& g = host[r];
+    g.obs = b.obs; g.nobs = b.nobs; g.act = b.act; g.rew = b.rew; g.term = b.term; g.OP = b.OP; g.AP = b.AP; g.cap = b.cap; g.ptr = b.ptr;
+    g.n = n[r]; g.size_cell = b.d_n; g.size = std::min(b.n + (long)n[r], b.cap);
+  }
+  ORL_HIP(hipMemcpy(tab, host.data(), sizeof(RollRing) * R, hipMemcpyHostToDevice));
+  RollP p;
+  memset(&p, 0, sizeof(p));
+  p.kind = term_kind; p.obs = obs; p.act = act; p.nobs = next_obs; p.rew = rew; p.row_stride = row_stride; p.od = b0.od; p.ad = b0.ad;
+  p.tab = tab; p.alive_nobs = alive_next_obs; p.blk_alive = blk_alive; p.blk_rew = blk_rew; p.n_alive_out = out_n; p.rew_sum_out = out_rew;
+  hipLaunchKernelGGL(k_roll_term, dim3((unsigned)blocks, (unsigned)R), dim3(256), 0, 0, p);
+  hipLaunchKernelGGL(k_roll_scatter, dim3((unsigned)blocks, (unsigned)R), dim3(256), 0, 0, p);
+  ORL_HIP(hipGetLastError());
+  std::vector<long long> res(2 * R);          // [R] alive counts, then [R] reward sums (doubles): one read for both
+  ORL_HIP(hipMemcpy(res.data(), out_n, sizeof(long long) * 2 * R, hipMemcpyDeviceToHost));
+  for (int r = 0; r < n_runs; ++r) {
+    Buffer& b = rings[r]->b;
+    n_alive[r] = res[r];
+    memcpy(&rew_sum[r], &res[R + r], sizeof(double));
+    b.ptr = (b.ptr + n[r]) % b.cap;
+    b.n = std::min(b.n + (long)n[r], b.cap);     // (the kernel published the same value to the ring's size cell)
+    b.absmax_gen = ~0ull;
+  }
+  ORL_HIP(hipDeviceSynchronize());            // the appended rows and the new sizes are visible to every stream of the process
+  return 0;
 }
 int orl_buffer_read(orl_buffer* h, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term) {
   if (!h || n < 1 || row0 < 0 || !obs || !act || !next_obs || !rew || !term) return fail("orl_buffer_read: bad arguments");
@@ -1785,14 +1868,59 @@ int orl_engine_attach_buffer(orl_engine* h, orl_buffer* b) {
 
 int orl_engine_attach_model_buffer(orl_engine* h, orl_buffer* m, int32_t real_rows) {
   Engine& e = h->e;
-  if (!m) { if (e.mbuf) { e.mbuf = nullptr; e.mbuf_real_rows = 0; e.drop_graphs(); } return 0; }
+  if (!m) { if (e.mbuf || !e.mbufs.empty()) { e.mbuf = nullptr; e.mbufs.clear(); e.mbuf_real_rows = 0; e.drop_graphs(); } return 0; }
   if (m->b.od != e.od || m->b.ad != e.ad) return fail("attach_model_buffer: obs/act dims differ from the engine's");
   if (m->b.dev != e.dev) return fail("attach_model_buffer: buffer lives on another device");
   if (!m->b.d_n || m->b.cap < 1) return fail("attach_model_buffer: the model buffer must be a ring (orl_buffer_reserve)");
   if (real_rows <= 0 || real_rows >= e.B) return fail("attach_model_buffer: real_rows must be in (0, batch_size)");
   e.mbuf = &m->b; e.mbuf_real_rows = real_rows; e.mbuf_gen = m->b.gen;
+  e.mbufs.clear();
   e.drop_graphs();
   return 0;
+}
+
+// the per-run source table of k_gather / k_prepare (engine-owned: captured graphs hold its address)
+int Engine::upload_model_table() {
+  std::vector<ModelSrc> host(mbufs.size());
+  mbufs_gen.resize(mbufs.size());
+  for (size_t r = 0; r < mbufs.size(); ++r) {
+    const Buffer& b = *mbufs[r];
+    host[r].obs = b.obs; host[r].nobs = b.nobs; host[r].act = b.act; host[r].rew = b.rew; host[r].term = b.term; host[r].n = b.d_n;
+    mbufs_gen[r] = b.gen;
+  }
+  ORL_HIP(hipStreamSynchronize(stream));
+  ORL_HIP(hipMemcpy(m_tab, host.data(), sizeof(ModelSrc) * host.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int orl_engine_attach_model_buffers(orl_engine* h, orl_buffer* const* models, int32_t n, int32_t real_rows) {
+  Engine& e = h->e;
+  if (!models || n == 0) return orl_engine_attach_model_buffer(h, nullptr, 0);
+  char msg[192];
+  if (n != e.cfg.n_runs) {
+    snprintf(msg, sizeof(msg), "attach_model_buffers: %d rings for an engine of %d runs (one ring per run)", (int)n, (int)e.cfg.n_runs);
+    return fail(msg);
+  }
+  for (int r = 0; r < n; ++r) {
+    const char* why = nullptr;
+    if (!models[r]) why = "null ring";
+    else if (models[r]->b.od != e.od || models[r]->b.ad != e.ad) why = "obs/act dims differ from the engine's";
+    else if (models[r]->b.dev != e.dev) why = "buffer lives on another device";
+    else if (!models[r]->b.d_n || models[r]->b.cap < 1) why = "the model buffer must be a ring (orl_buffer_reserve)";
+    if (why) { snprintf(msg, sizeof(msg), "attach_model_buffers: run %d: %s", r, why); return fail(msg); }
+  }
+  if (real_rows <= 0 || real_rows >= e.B) return fail("attach_model_buffers: real_rows must be in (0, batch_size)");
+  ORL_HIP(hipSetDevice(e.dev));
+  if (!e.m_tab) {
+    e.m_tab = (ModelSrc*)e.raw_alloc(sizeof(ModelSrc) * e.R);
+    if (!e.m_tab) return fail("attach_model_buffers: hipMalloc of the source table");
+  }
+  e.mbuf = nullptr;
+  e.mbufs.clear();
+  for (int r = 0; r < n; ++r) e.mbufs.push_back(&models[r]->b);
+  e.mbuf_real_rows = real_rows;
+  e.drop_graphs();
+  return e.upload_model_table();
 }
 
 // ---- hot path ----
@@ -1843,19 +1971,28 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
   ORL_HIP(hipSetDevice(e.dev));
   if (n_steps <= 0) return fail("n_steps must be positive");
   if (!e.buf || !e.buf->obs || e.buf->n < 1) return fail("orl_learn_n: no replay buffer attached");
-  if (e.mbuf) {
-    if (!e.mbuf->obs || e.mbuf->n < 1) return fail("orl_learn_n: the model buffer is empty (roll the dynamics out into it first)");
+  for (size_t r = 0; r < e.mbufs.size(); ++r)
+    if (!e.mbufs[r]->obs || e.mbufs[r]->n < 1) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "orl_learn_n: the model buffer of run %d is empty (roll the dynamics out into it first)", (int)r);
+      return fail(msg);
+    }
+  if (e.mbuf || !e.mbufs.empty()) {
+    if (e.mbuf && (!e.mbuf->obs || e.mbuf->n < 1)) return fail("orl_learn_n: the model buffer is empty (roll the dynamics out into it first)");
     if (e.cfg.algo == ORL_ALGO_CQL && e.mbuf_real_rows != e.cfg.cql_real_rows)
       return fail("orl_learn_n: the model buffer's real_rows differs from the engine's cql_real_rows (COMBO's row layout)");
   }
   ORL_HIP(hipMemsetAsync(e.metrics_sum, 0, sizeof(float) * e.R * e.nm, e.stream));
   // the buffer was reloaded (or, a ring attached as the primary source, grew) since the graphs were captured: they hold freed pointers
   // and the old size.  The model ring's size is read from its device cell: growth needs no re-capture, only a new reserve / load does.
-  if (e.buf_gen != e.buf->gen || e.buf_n != e.buf->n || (e.mbuf && e.mbuf_gen != e.mbuf->gen)) {
+  bool rings_moved = false;
+  for (size_t r = 0; r < e.mbufs.size(); ++r) rings_moved = rings_moved || e.mbufs_gen[r] != e.mbufs[r]->gen;
+  if (e.buf_gen != e.buf->gen || e.buf_n != e.buf->n || (e.mbuf && e.mbuf_gen != e.mbuf->gen) || rings_moved) {
     ORL_HIP(hipStreamSynchronize(e.stream));
     e.drop_graphs();
     e.buf_gen = e.buf->gen; e.buf_n = e.buf->n;
     if (e.mbuf) e.mbuf_gen = e.mbuf->gen;
+    if (rings_moved && e.upload_model_table()) return -1;      // (a reserve moved a ring's arrays: the table holds the old pointers)
   }
   const bool graphable = e.use_graph && !e.prof_on;
   if (graphable) {

@@ -98,6 +98,13 @@ __global__ void k_grad_scale(GradScaleP p) {
 // (coalesced within the row) and rows are independent random 64-128 B segments.
 // grid (ceil(B*W/256), R) with W = max(OP, AP).
 // ------------------------------------------------------------------------------------------------
+// one model ring as the samplers see it: the arrays and the device cell that holds the current size.  With per-run model rings
+// (orl_engine_attach_model_buffers) a table of these, one per run, sits in engine-owned device memory: the captured graph holds the
+// table's address, the rings grow behind it.
+struct ModelSrc { const float *obs, *nobs, *act, *rew, *term; const long long* n; };
+// (r = blockIdx.y: block-uniform, the table entry comes by scalar loads; `one` is the single ring of the launch parameters, handed over
+// field by field: a reference to the parameter block itself put k_prepare's 2 KB job table into scratch memory)
+__device__ inline ModelSrc orl_model_src(const ModelSrc* tab, int r, ModelSrc one) { return tab ? tab[r] : one; }
 struct GatherP {
   const float *obs, *nobs, *act, *rew, *term;  // dataset [n][OP], [n][OP], [n][AP], [n], [n]
   long n;
@@ -114,6 +121,7 @@ struct GatherP {
   const float *m_obs, *m_nobs, *m_act, *m_rew, *m_term;
   const long long* m_n;
   int real_rows;
+  const ModelSrc* m_tab;                           // per-run model rings (orl_engine_attach_model_buffers), or null: the ring above for every run
 };
 __global__ void k_gather(GatherP p) {
   const int r = blockIdx.y;
@@ -123,13 +131,14 @@ __global__ void k_gather(GatherP p) {
   // the source of a batch row is a function of the row alone: real rows first, model rows behind them (mopo.py:81-84); the row keeps
   // its Philox counter, only the range and the base pointers change
   const bool mdl = p.m_obs && row >= p.real_rows;
-  const float *s_obs = mdl ? p.m_obs : p.obs, *s_nobs = mdl ? p.m_nobs : p.nobs, *s_act = mdl ? p.m_act : p.act;
-  const float *s_rew = mdl ? p.m_rew : p.rew, *s_term = mdl ? p.m_term : p.term;
+  const ModelSrc m = orl_model_src(p.m_tab, r, ModelSrc{p.m_obs, p.m_nobs, p.m_act, p.m_rew, p.m_term, p.m_n});
+  const float *s_obs = mdl ? m.obs : p.obs, *s_nobs = mdl ? m.nobs : p.nobs, *s_act = mdl ? m.act : p.act;
+  const float *s_rew = mdl ? m.rew : p.rew, *s_term = mdl ? m.term : p.term;
   long j;
   if (p.idx) j = p.idx[(long)r * p.idx_rs + row];
   else {
     const unsigned long long ctr = p.gstep ? *p.gstep : p.counter;
-    const long n = mdl ? (long)*p.m_n : p.n;
+    const long n = mdl ? (long)*m.n : p.n;
     Philox ph(p.seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(r + 1));
     uint32_t o[4];
     ph((uint32_t)row, 0x51u, (uint32_t)ctr, 0x1D5u ^ (uint32_t)(ctr >> 32), o);
@@ -184,26 +193,41 @@ __device__ inline bool orl_term_done(int kind, const float* x, int od) {
     default: return false;
   }
 }
+// Several rings in one launch pair (orl_buffer_append_rollout_runs): blockIdx.y is the run, the sources are [runs][row_stride][dim]
+// arrays of which run r owns the first tab[r].n rows, and the ring of a run is read from a table in device memory (uploaded per call:
+// at 128 runs it does not fit the kernel arguments).  A block whose first row lies at or past its run's row count leaves before any
+// barrier (the test is uniform per block); the per-block scratch is [runs][gridDim.x] and the totals of a run are summed over the blocks
+// that had rows, in block order.
+struct RollRing {
+  float *obs, *nobs, *act, *rew, *term; int OP, AP; long cap, ptr;   // the ring
+  long n;                                // rows of this call
+  long long* size_cell; long long size;  // non-null: the ring's device size cell and its value after this call
+};
 struct RollP {
   int kind;
-  const float *obs, *act, *nobs, *rew;   // packed [n][od], [n][ad], [n][od], [n]
-  long n; int od, ad;
-  float *r_obs, *r_nobs, *r_act, *r_rew, *r_term; int OP, AP; long cap, ptr;   // the ring
-  float* alive_nobs;                     // [<= n][od] packed; must not overlap nobs
-  int* blk_alive; double* blk_rew;       // [gridDim.x] scratch
-  long long* n_alive_out; double* rew_sum_out;
+  const float *obs, *act, *nobs, *rew;   // packed [runs][row_stride][od], [..][ad], [..][od], [runs][row_stride]
+  long row_stride; int od, ad;
+  RollRing ring;                         // tab == nullptr: the one ring (gridDim.y == 1)
+  const RollRing* tab;                   // [gridDim.y], device memory
+  float* alive_nobs;                     // [runs][row_stride][od] packed, run r compacted into its own block; must not overlap nobs
+  int* blk_alive; double* blk_rew;       // [gridDim.y][gridDim.x] scratch
+  long long* n_alive_out; double* rew_sum_out;   // [gridDim.y]
 };
 __global__ void k_roll_term(RollP p) {
   __shared__ int sh_a[4];
   __shared__ double sh_r[4];
+  const int r = blockIdx.y;
+  const RollRing g = p.tab ? p.tab[r] : p.ring;
+  if ((long)blockIdx.x * 256 >= g.n) return;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const float* nobs = p.nobs + (long)r * p.row_stride * p.od;
   bool alive = false;
   double rw = 0.0;
-  if (i < p.n) {
-    const bool done = orl_term_done(p.kind, p.nobs + i * p.od, p.od);
-    p.r_term[(p.ptr + i) % p.cap] = done ? 1.0f : 0.0f;
+  if (i < g.n) {
+    const bool done = orl_term_done(p.kind, nobs + i * p.od, p.od);
+    g.term[(g.ptr + i) % g.cap] = done ? 1.0f : 0.0f;
     alive = !done;
-    rw = (double)p.rew[i];
+    rw = (double)p.rew[(long)r * p.row_stride + i];
   }
   const unsigned long long m = __ballot(alive);
 #pragma unroll
@@ -211,19 +235,31 @@ __global__ void k_roll_term(RollP p) {
   if ((threadIdx.x & 63) == 0) { sh_a[threadIdx.x >> 6] = __popcll(m); sh_r[threadIdx.x >> 6] = rw; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    p.blk_alive[blockIdx.x] = sh_a[0] + sh_a[1] + sh_a[2] + sh_a[3];
-    p.blk_rew[blockIdx.x] = ((sh_r[0] + sh_r[1]) + sh_r[2]) + sh_r[3];
+    p.blk_alive[(long)r * gridDim.x + blockIdx.x] = sh_a[0] + sh_a[1] + sh_a[2] + sh_a[3];
+    p.blk_rew[(long)r * gridDim.x + blockIdx.x] = ((sh_r[0] + sh_r[1]) + sh_r[2]) + sh_r[3];
   }
 }
 __global__ void k_roll_scatter(RollP p) {
   __shared__ int sh_part[256];
   __shared__ int sh_w[4];
   __shared__ int sh_dst[256];
-  const int tid = threadIdx.x;
+  const int tid = threadIdx.x, r = blockIdx.y;
+  const RollRing g = p.tab ? p.tab[r] : p.ring;
   const long row0 = (long)blockIdx.x * 256, i = row0 + tid;
+  if (row0 >= g.n) {                      // (a run without rows: its block 0 still reports the totals)
+    if (blockIdx.x == 0 && tid == 0) {
+      p.n_alive_out[r] = 0; p.rew_sum_out[r] = 0.0;
+      if (g.size_cell) *g.size_cell = g.size;
+    }
+    return;
+  }
+  const float *s_obs = p.obs + (long)r * p.row_stride * p.od, *s_nobs = p.nobs + (long)r * p.row_stride * p.od;
+  const float *s_act = p.act + (long)r * p.row_stride * p.ad, *s_rew = p.rew + (long)r * p.row_stride;
+  float* alive_nobs = p.alive_nobs + (long)r * p.row_stride * p.od;
+  const int* blk_alive = p.blk_alive + (long)r * gridDim.x;
   // alive rows of the blocks in front of this one (integers: the order of the sum does not matter)
   int part = 0;
-  for (int b = tid; b < (int)blockIdx.x; b += 256) part += p.blk_alive[b];
+  for (int b = tid; b < (int)blockIdx.x; b += 256) part += blk_alive[b];
   sh_part[tid] = part;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -231,7 +267,7 @@ __global__ void k_roll_scatter(RollP p) {
     __syncthreads();
   }
   const int blk_off = sh_part[0];
-  const bool alive = i < p.n && p.r_term[(p.ptr + i) % p.cap] == 0.0f;
+  const bool alive = i < g.n && g.term[(g.ptr + i) % g.cap] == 0.0f;
   const unsigned long long m = __ballot(alive);
   const int lane = tid & 63, w = tid >> 6;
   if (lane == 0) sh_w[w] = __popcll(m);
@@ -240,27 +276,30 @@ __global__ void k_roll_scatter(RollP p) {
   for (int k = 0; k < w; ++k) woff += sh_w[k];
   sh_dst[tid] = alive ? blk_off + woff + __popcll(m & ((1ull << lane) - 1ull)) : -1;
   __syncthreads();
-  const int rows = (int)(p.n - row0 < 256 ? p.n - row0 : 256);
-  for (int e = tid; e < rows * p.OP; e += 256) {
-    const int row = e / p.OP, c = e - row * p.OP;
-    const long src = (row0 + row) * p.od + c, dst = ((p.ptr + row0 + row) % p.cap) * p.OP + c;
-    p.r_obs[dst] = c < p.od ? p.obs[src] : 0.f;
-    p.r_nobs[dst] = c < p.od ? p.nobs[src] : 0.f;
+  const int rows = (int)(g.n - row0 < 256 ? g.n - row0 : 256);
+  for (int e = tid; e < rows * g.OP; e += 256) {
+    const int row = e / g.OP, c = e - row * g.OP;
+    const long src = (row0 + row) * p.od + c, dst = ((g.ptr + row0 + row) % g.cap) * g.OP + c;
+    g.obs[dst] = c < p.od ? s_obs[src] : 0.f;
+    g.nobs[dst] = c < p.od ? s_nobs[src] : 0.f;
   }
-  for (int e = tid; e < rows * p.AP; e += 256) {
-    const int row = e / p.AP, c = e - row * p.AP;
-    p.r_act[((p.ptr + row0 + row) % p.cap) * p.AP + c] = c < p.ad ? p.act[(row0 + row) * p.ad + c] : 0.f;
+  for (int e = tid; e < rows * g.AP; e += 256) {
+    const int row = e / g.AP, c = e - row * g.AP;
+    g.act[((g.ptr + row0 + row) % g.cap) * g.AP + c] = c < p.ad ? s_act[(row0 + row) * p.ad + c] : 0.f;
   }
   for (int e = tid; e < rows * p.od; e += 256) {
     const int row = e / p.od, c = e - row * p.od;
     const int d = sh_dst[row];
-    if (d >= 0) p.alive_nobs[(long)d * p.od + c] = p.nobs[(row0 + row) * p.od + c];
+    if (d >= 0) alive_nobs[(long)d * p.od + c] = s_nobs[(row0 + row) * p.od + c];
   }
-  if (i < p.n) p.r_rew[(p.ptr + i) % p.cap] = p.rew[i];
+  if (i < g.n) g.rew[(g.ptr + i) % g.cap] = s_rew[i];
   if (blockIdx.x == 0 && tid == 0) {      // totals in block order (a few hundred terms at 50 000 rows)
     long long na = 0; double rs = 0.0;
-    for (int b = 0; b < (int)gridDim.x; ++b) { na += p.blk_alive[b]; rs += p.blk_rew[b]; }
-    *p.n_alive_out = na; *p.rew_sum_out = rs;
+    const int nb = (int)((g.n + 255) / 256);
+    const double* blk_rew = p.blk_rew + (long)r * gridDim.x;
+    for (int b = 0; b < nb; ++b) { na += blk_alive[b]; rs += blk_rew[b]; }
+    p.n_alive_out[r] = na; p.rew_sum_out[r] = rs;
+    if (g.size_cell) *g.size_cell = g.size;
   }
 }
 
@@ -366,6 +405,7 @@ struct PrepP {
   const float *m_obs, *m_nobs, *m_act, *m_rew, *m_term;
   const long long* m_n;
   int real_rows;
+  const ModelSrc* m_tab;                              // per-run model rings, or null (GatherP::m_tab)
 };
 // np.random.randint(0, size, B) (buffer.py:98) on the device: one Philox call per (run, batch row), drawn ONCE per step and shared by
 // every consumer of that row (batch slots, actor / critic input rows and their N-fold repeats)
@@ -415,8 +455,9 @@ __global__ void k_prepare(PrepP p) {
     if (p.d_obs) {
       // every consumer of batch row b re-draws its index: the source (real / model) is a function of b alone
       const bool mdl = p.m_obs && b >= p.real_rows;
-      const long j = p.draw ? (long)orl_draw_index(p.seed, r, b, *p.gstep, mdl ? (long)*p.m_n : p.n) : (long)p.idx[(long)r * p.idx_rs + b];
-      const float* base = jb.src == PS_OBS ? (mdl ? p.m_obs : p.d_obs) : (jb.src == PS_NOBS ? (mdl ? p.m_nobs : p.d_nobs) : (mdl ? p.m_act : p.d_act));
+      const ModelSrc m = orl_model_src(p.m_tab, r, ModelSrc{p.m_obs, p.m_nobs, p.m_act, p.m_rew, p.m_term, p.m_n});
+      const long j = p.draw ? (long)orl_draw_index(p.seed, r, b, *p.gstep, mdl ? (long)*m.n : p.n) : (long)p.idx[(long)r * p.idx_rs + b];
+      const float* base = jb.src == PS_OBS ? (mdl ? m.obs : p.d_obs) : (jb.src == PS_NOBS ? (mdl ? m.nobs : p.d_nobs) : (mdl ? m.act : p.d_act));
       srow = base + j * (jb.src == PS_ACT ? p.AP : p.OP);
     } else {
       srow = jb.src == PS_ACT ? p.b_act + (long)r * p.ba_rs + (long)b * p.b_ap
@@ -442,13 +483,14 @@ __global__ void k_prepare(PrepP p) {
     const int b = jb.src_row0 + (jb.mod ? row % jb.mod : row) / jb.rep;
     if (p.d_obs) {
       const bool mdl = p.m_obs && b >= p.real_rows;
-      const long j = p.draw ? (long)orl_draw_index(p.seed, r, b, *p.gstep, mdl ? (long)*p.m_n : p.n) : (long)p.idx[(long)r * p.idx_rs + b];
+      const ModelSrc m = orl_model_src(p.m_tab, r, ModelSrc{p.m_obs, p.m_nobs, p.m_act, p.m_rew, p.m_term, p.m_n});
+      const long j = p.draw ? (long)orl_draw_index(p.seed, r, b, *p.gstep, mdl ? (long)*m.n : p.n) : (long)p.idx[(long)r * p.idx_rs + b];
       switch (jb.src) {
-        case PS_OBS: v = (mdl ? p.m_obs : p.d_obs)[j * p.OP + col]; break;
-        case PS_NOBS: v = (mdl ? p.m_nobs : p.d_nobs)[j * p.OP + col]; break;
-        case PS_ACT: v = (mdl ? p.m_act : p.d_act)[j * p.AP + col]; break;
-        case PS_REW: v = (mdl ? p.m_rew : p.d_rew)[j]; if (p.draw && p.idx_out) p.idx_out[(long)r * p.idx_rs + b] = j; break;
-        default: v = (mdl ? p.m_term : p.d_term)[j]; break;
+        case PS_OBS: v = (mdl ? m.obs : p.d_obs)[j * p.OP + col]; break;
+        case PS_NOBS: v = (mdl ? m.nobs : p.d_nobs)[j * p.OP + col]; break;
+        case PS_ACT: v = (mdl ? m.act : p.d_act)[j * p.AP + col]; break;
+        case PS_REW: v = (mdl ? m.rew : p.d_rew)[j]; if (p.draw && p.idx_out) p.idx_out[(long)r * p.idx_rs + b] = j; break;
+        default: v = (mdl ? m.term : p.d_term)[j]; break;
       }
     } else {
       switch (jb.src) {

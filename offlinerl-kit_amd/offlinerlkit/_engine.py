@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import warnings
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "orl_set_lr", "orl_reset_optimizers", "orl_adam_get", "orl_adam_set", "orl_set_step_count", "orl_buffer_create", "orl_buffer_destroy", "orl_buffer_load",
     "orl_buffer_normalize_obs", "orl_buffer_sample", "orl_buffer_size", "orl_engine_attach_buffer", "orl_step", "orl_learn_n",
     "orl_buffer_reserve", "orl_buffer_append", "orl_buffer_append_rollout", "orl_buffer_read", "orl_engine_attach_model_buffer",
+    "orl_buffer_append_rollout_runs", "orl_engine_attach_model_buffers",
     "orl_health", "orl_health_check", "orl_health_clear", "orl_num_metrics", "orl_metric_name", "orl_step_count",
     "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
     # dynamics ensemble (orl_dynamics)
@@ -166,6 +167,9 @@ def load_library(path: Optional[str] = None):
                                                                                            C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     lib.orl_buffer_read.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5
     lib.orl_engine_attach_model_buffer.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    lib.orl_buffer_append_rollout_runs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int32] + [C.c_void_p] * 4 + \
+        [C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.orl_engine_attach_model_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32]
     lib.orl_step.argtypes = [C.c_void_p, C.POINTER(OrlBatch), C.POINTER(OrlNoise), C.c_void_p]
     lib.orl_learn_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_health.argtypes = [C.c_void_p, C.c_void_p]
@@ -386,6 +390,15 @@ class Engine:
                "orl_engine_attach_model_buffer")
         self._mbuf = buf  # keep alive
 
+    def attach_model_buffers(self, bufs: Optional[Sequence["DeviceBuffer"]], real_rows: int = 0):
+        """one model ring per run (orl_engine_attach_model_buffers): run r draws batch rows [real_rows, B) from ``bufs[r]`` only; None or
+        an empty sequence detaches.  Replaces a ring attached with ``attach_model_buffer`` and the other way round."""
+        bufs = list(bufs) if bufs is not None else []
+        arr = (C.c_void_p * max(len(bufs), 1))(*[b._h.value for b in bufs])
+        _check(self.lib.orl_engine_attach_model_buffers(self._h, arr if bufs else None, len(bufs), int(real_rows)),
+               "orl_engine_attach_model_buffers")
+        self._mbuf = bufs or None  # keep alive
+
     # ---- hot path ----
     def step(self, batch: Optional[Dict[str, np.ndarray]], noise: Optional[List[np.ndarray]], on_device=False) -> np.ndarray:
         """batch/noise: host arrays with a leading run dimension (or raw device pointers when on_device)."""
@@ -591,6 +604,39 @@ class DeviceBuffer:
         _check(self.lib.orl_buffer_append_rollout(self._h, int(term_kind), obs.data_ptr(), act.data_ptr(), next_obs.data_ptr(), rew.data_ptr(),
                                                   n, alive_next_obs.data_ptr(), C.byref(na), C.byref(rs)), "orl_buffer_append_rollout")
         return int(na.value), float(rs.value)
+
+    @staticmethod
+    def append_rollout_runs(rings: Sequence["DeviceBuffer"], term_kind: int, obs, act, next_obs, rew, n: Sequence[int], alive_next_obs):
+        """one rollout step of every run (orl_buffer_append_rollout_runs): ``rings[r]`` receives the first ``n[r]`` rows of run r.
+        obs / next_obs / alive_next_obs [R, stride, obs_dim], act [R, stride, act_dim], rew [R, stride]: contiguous fp32 tensors on the
+        rings' device.  Returns (n_alive int64 [R], float64 reward sums [R])."""
+        import torch
+        rings = list(rings)
+        if not rings:
+            raise ValueError("append_rollout_runs: no rings")
+        R, b0 = len(rings), rings[0]
+        if obs.dim() != 3:
+            raise ValueError(f"append_rollout_runs: obs has shape {tuple(obs.shape)}, expected [{R}, stride, {b0.obs_dim}]")
+        stride = int(obs.shape[1])
+        for name, t, shape in (("obs", obs, (R, stride, b0.obs_dim)), ("act", act, (R, stride, b0.act_dim)),
+                               ("next_obs", next_obs, (R, stride, b0.obs_dim)), ("rew", rew, None),
+                               ("alive_next_obs", alive_next_obs, (R, stride, b0.obs_dim))):
+            if not _is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" \
+                    or (t.device.index or 0) != b0.device:
+                raise ValueError(f"append_rollout_runs: {name} must be a contiguous fp32 tensor on the rings' device")
+            if shape is not None and tuple(t.shape) != shape:
+                raise ValueError(f"append_rollout_runs: {name} has shape {tuple(t.shape)}, expected {shape}")
+        if rew.numel() != R * stride:
+            raise ValueError(f"append_rollout_runs: rew needs {R} x {stride} values")
+        if len(n) != R:
+            raise ValueError(f"append_rollout_runs: {len(n)} row counts for {R} rings")
+        torch.cuda.current_stream(obs.device).synchronize()
+        hs = (C.c_void_p * R)(*[b._h.value for b in rings])
+        cn = (C.c_int64 * R)(*[int(x) for x in n])
+        na, rs = (C.c_int64 * R)(), (C.c_double * R)()
+        _check(b0.lib.orl_buffer_append_rollout_runs(hs, R, int(term_kind), obs.data_ptr(), act.data_ptr(), next_obs.data_ptr(), rew.data_ptr(),
+                                                     stride, cn, alive_next_obs.data_ptr(), na, rs), "orl_buffer_append_rollout_runs")
+        return np.array(na[:], dtype=np.int64), np.array(rs[:], dtype=np.float64)
 
     def read_rows(self, row0: int, n: int):
         """(obs, act, next_obs, rew [n, 1], term [n, 1]) host copies of rows [row0, row0 + n)"""

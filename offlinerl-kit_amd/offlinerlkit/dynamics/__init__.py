@@ -230,6 +230,40 @@ class EnsembleDynamics(BaseDynamics):
             info["penalty"] = pen[r]
         return nxt[r], (rew[r] if self._penalty_coef else raw[r]), info
 
+    @torch.no_grad()
+    def step_device_runs(self, obs: torch.Tensor, action: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, Dict]:
+        """``step_device`` for R row blocks at once: obs (R, N, obs_dim), action (R, N, act_dim) -> (next_obs (R, N, obs_dim), reward
+        (R, N), info).  With ``n_runs == R`` ensembles block r is stepped by run r; with ONE ensemble the blocks are folded into that
+        run's rows (R * N rows of one call, so block r's Philox draws are keyed by the row positions r * N ...).  Any other number of
+        runs is refused.  Rows that are padding must hold finite values; their outputs mean nothing."""
+        self._bind(*(self._shape or (256, 0.01)))
+        self._sync_torch()
+        self._push_elites_from_model()
+        dev = self._arena.device
+        o = torch.as_tensor(obs, dtype=torch.float32, device=dev)
+        a = torch.as_tensor(action, dtype=torch.float32, device=dev)
+        if o.dim() != 3 or a.dim() != 3 or o.shape[:2] != a.shape[:2]:
+            raise ValueError(f"step_device_runs: obs {tuple(o.shape)} / action {tuple(a.shape)} must be (R, N, obs_dim) / (R, N, act_dim)")
+        R, n = int(o.shape[0]), int(o.shape[1])
+        if self._n_runs not in (1, R):
+            raise ValueError(f"step_device_runs: {R} row blocks need a dynamics of {R} runs or of one (shared) run, this one has {self._n_runs}")
+        for r in range(self._n_runs):
+            sc = self.scalers[r]
+            if sc.mu is None:
+                raise RuntimeError("the scaler is not fitted: train() or load() the dynamics first")
+            self._eng.set_scaler(r, sc.mu, sc.std)
+        shared = self._n_runs != R
+        o, a = o.contiguous(), a.contiguous()
+        if shared:
+            o, a = o.view(1, R * n, -1), a.view(1, R * n, -1)
+        nxt, rew, raw, pen = self._eng.step_device(o, a, self._uncertainty_mode, float(self._penalty_coef))
+        if shared:
+            nxt, rew, raw, pen = nxt.view(R, n, -1), rew.view(R, n), raw.view(R, n), pen.view(R, n)
+        info = {"raw_reward": raw}
+        if self._penalty_coef:
+            info["penalty"] = pen
+        return nxt, (rew if self._penalty_coef else raw), info
+
     def sample_next_obss(self, obs, action, num_samples: int):
         raise NotImplementedError("sample_next_obss is used by MOBILE only, which this package does not implement")
 

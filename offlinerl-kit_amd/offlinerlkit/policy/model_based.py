@@ -10,11 +10,17 @@ The fused epoch (``MBPolicyTrainer(fused=True)``) keeps the model buffer in an H
 ``rollout_device`` rolls the dynamics forward without a host round trip (``EnsembleDynamics.step_device`` and the termination /
 compaction kernel behind ``DeviceBuffer.append_rollout``) and ``learn_n(n_steps, real_buffer, fake_buffer, ...)`` draws the real and
 the model rows of every minibatch inside ``orl_learn_n`` (``orl_engine_attach_model_buffer``).
+
+Per-run model rings: where ``fake_buffer`` is a sequence of ``n_runs`` ``ReplayBuffer``s (instead of one), run r of a multi-run policy
+rolls ITS actor through run r of the dynamics (or a shared one-run ensemble) into ring r and draws its model rows from ring r only --
+R independent seeds.  All runs share the launches: one batched actor forward (``actforward_runs``), one ``step_device_runs``, one
+``DeviceBuffer.append_rollout_runs`` per model step, and ``orl_engine_attach_model_buffers`` for ``learn_n``.  One ``ReplayBuffer``
+keeps the single shared ring, filled by the selected run's actor.
 """
 from __future__ import annotations
 
 from collections import defaultdict
-from typing import Dict, Tuple, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -100,19 +106,100 @@ def _rollout_device(policy, real_buffer, fake_buffer, rollout_batch_size: int, r
     return {"num_transitions": num_transitions, "reward_mean": rew_sum / num_transitions}
 
 
+def per_run_rings(policy, fake_buffer) -> Optional[List]:
+    """``fake_buffer`` given as a sequence -> the list of the runs' buffers (checked: one per run, same dims, capacity and device);
+    a single buffer -> None"""
+    if not isinstance(fake_buffer, (list, tuple)):
+        return None
+    bufs = list(fake_buffer)
+    R = int(getattr(policy, "n_runs", 1))
+    if len(bufs) != R:
+        raise ValueError(f"per-run model buffers: {len(bufs)} buffers for a policy of n_runs = {R} (one ring per run)")
+    if len({id(b) for b in bufs}) != R:
+        raise ValueError("per-run model buffers: the same buffer is listed twice (one ring per run)")
+    shape = lambda b: (tuple(b.obs_shape), int(b.action_dim), int(b._max_size), str(b.device))
+    for r, b in enumerate(bufs):
+        if shape(b) != shape(bufs[0]):
+            raise ValueError(f"per-run model buffers: run {r}'s buffer (obs shape, action dim, capacity, device) = {shape(b)} differs "
+                             f"from run 0's {shape(bufs[0])}")
+    return bufs
+
+
+def _rollout_device_runs(policy, real_buffer, bufs, rollout_batch_size: int, rollout_length: int, init_obss, uniform: bool) -> Dict:
+    """``_rollout_device`` for the R runs of a policy at once, run r into ``bufs[r]``: one batched actor forward, one dynamics step
+    and one termination / compaction launch pair per model step for all runs.  The runs' live row counts diverge; every step runs at
+    the largest one, with zeroed padding rows behind a run's live rows (finite inputs, ignored outputs).  One host sync per model step."""
+    dyn = policy.dynamics
+    kind = getattr(dyn, "term_kind", None)
+    if kind is None or not hasattr(dyn, "step_device_runs"):
+        raise NotImplementedError("rollout_device: the dynamics' termination function is not one of the fixed row-wise tests of "
+                                  "utils.termination_fns (an obs_unnormalization wrapper, door or another callable carries no term_kind): "
+                                  "the device rollout cannot evaluate it; use rollout() / MBPolicyTrainer(fused=False)")
+    R, N = len(bufs), int(rollout_batch_size)
+    if int(getattr(dyn, "_n_runs", 1)) not in (1, R):
+        raise ValueError(f"per-run model buffers: the dynamics carries {dyn._n_runs} runs; {R} (run r rolls through ensemble r) or 1 (shared)")
+    rings = [b.reserve_device() for b in bufs]
+    if init_obss is None:
+        init_obss = real_buffer.sample(R * N)["observations"]
+    dev = torch.device("cuda", rings[0].device)
+    obs = torch.as_tensor(init_obss, dtype=torch.float32, device=dev).reshape(R, N, -1).contiguous()
+    if not uniform and policy._eng is None:
+        policy._bind(256)                      # (the stacked actor tensors live in the engine's arena)
+    live = np.full(R, N, dtype=np.int64)
+    num_transitions, rew_sum = np.zeros(R, np.int64), np.zeros(R, np.float64)
+    with torch.no_grad():
+        for _ in range(rollout_length):
+            nmax = int(live.max())
+            obs = obs[:, :nmax].contiguous()
+            if uniform:
+                sp = policy.action_space
+                act = torch.empty((R, nmax, sp.shape[0]), dtype=torch.float32, device=dev).uniform_(float(sp.low[0]), float(sp.high[0]))
+            else:
+                act = policy.actforward_runs(obs, False).contiguous()
+            nxt, rew, _ = dyn.step_device_runs(obs, act)
+            alive = torch.zeros_like(nxt)      # zeros: the rows past a run's survivors are the next step's padding
+            n_alive, s = _engine.DeviceBuffer.append_rollout_runs(rings, kind, obs, act, nxt.contiguous(), rew.contiguous(), live, alive)
+            for r in range(R):
+                if live[r]:
+                    bufs[r]._advance(int(live[r]))
+            num_transitions += live
+            rew_sum += s
+            live = n_alive
+            if int(live.max()) == 0:
+                break
+            obs = alive
+    return {"num_transitions": num_transitions, "reward_mean": rew_sum / np.maximum(num_transitions, 1)}
+
+
+def _rollout_device_any(policy, real_buffer, fake_buffer, rollout_batch_size: int, rollout_length: int, init_obss, uniform: bool) -> Dict:
+    bufs = per_run_rings(policy, fake_buffer)
+    if bufs is None:
+        return _rollout_device(policy, real_buffer, fake_buffer, rollout_batch_size, rollout_length, init_obss, uniform)
+    return _rollout_device_runs(policy, real_buffer, bufs, rollout_batch_size, rollout_length, init_obss, uniform)
+
+
 def _learn_n_mb(policy, n_steps: int, real_buffer, fake_buffer, batch_size: int, real_ratio: float) -> Dict[str, float]:
-    """``n_steps`` x (sample real, sample model, learn) fused on the device: both index draws inside ``orl_learn_n``"""
+    """``n_steps`` x (sample real, sample model, learn) fused on the device: both index draws inside ``orl_learn_n``.  A sequence of
+    buffers as ``fake_buffer``: run r's model rows from ring r (``orl_engine_attach_model_buffers``)."""
     if real_buffer is None or fake_buffer is None:
         raise NotImplementedError(f"{type(policy).__name__} mixes a real and a model-rollout buffer per batch: "
                                   "learn_n(n_steps, real_buffer, fake_buffer, ...), or learn({'real': ..., 'fake': ...})")
+    bufs = per_run_rings(policy, fake_buffer)
     real_rows = int(batch_size * real_ratio)               # mb_policy_trainer.py:81-82
     policy._bind(batch_size)
     real = real_buffer.device_buffer() if hasattr(real_buffer, "device_buffer") else real_buffer
-    model = fake_buffer.reserve_device() if hasattr(fake_buffer, "reserve_device") else fake_buffer
-    key = (real, model, real_rows)
+    if bufs is not None:
+        models = tuple(b.reserve_device() for b in bufs)
+        key = (real, models, real_rows)
+    else:
+        model = fake_buffer.reserve_device() if hasattr(fake_buffer, "reserve_device") else fake_buffer
+        key = (real, model, real_rows)
     if policy._attached != key:
         policy._eng.attach_buffer(real)
-        policy._eng.attach_model_buffer(model, real_rows)
+        if bufs is not None:
+            policy._eng.attach_model_buffers(models, real_rows)
+        else:
+            policy._eng.attach_model_buffer(model, real_rows)
         policy._attached = key
     policy._push_lrs()
     m, ms = policy._eng.learn_n(int(n_steps))
@@ -174,8 +261,10 @@ class MOPOPolicy(SACPolicy):
         return super().learn(_cat(batch), noise) if "real" in batch else super().learn(batch, noise)
 
     def rollout_device(self, real_buffer, fake_buffer, rollout_batch_size: int, rollout_length: int, init_obss=None) -> Dict:
-        """``rollout`` + ``fake_buffer.add_batch`` on the device; returns the reference's rollout info"""
-        return _rollout_device(self, real_buffer, fake_buffer, rollout_batch_size, rollout_length, init_obss, False)
+        """``rollout`` + ``fake_buffer.add_batch`` on the device; returns the reference's rollout info.  ``fake_buffer`` = a sequence of
+        ``n_runs`` buffers: every run rolls its own actor into its own ring, ``rollout_batch_size`` initial states each, and the info
+        holds per-run arrays ``num_transitions[R]`` / ``reward_mean[R]``"""
+        return _rollout_device_any(self, real_buffer, fake_buffer, rollout_batch_size, rollout_length, init_obss, False)
 
     def learn_n(self, n_steps: int, real_buffer, fake_buffer=None, batch_size: int = 256, real_ratio: float = 0.05) -> Dict[str, float]:
         """the inner loop of MBPolicyTrainer (mb_policy_trainer.py:78-90) fused on the device: rows [0, int(batch_size * real_ratio))
@@ -229,7 +318,7 @@ class COMBOPolicy(CQLPolicy):
 
     def rollout_device(self, real_buffer, fake_buffer, rollout_batch_size: int, rollout_length: int, init_obss=None) -> Dict:
         """``rollout`` + ``fake_buffer.add_batch`` on the device (uniform actions from torch's device generator when ``uniform_rollout``)"""
-        return _rollout_device(self, real_buffer, fake_buffer, rollout_batch_size, rollout_length, init_obss, self._uniform_rollout)
+        return _rollout_device_any(self, real_buffer, fake_buffer, rollout_batch_size, rollout_length, init_obss, self._uniform_rollout)
 
     def learn_n(self, n_steps: int, real_buffer, fake_buffer=None, batch_size: int = 256, real_ratio: float = 0.05) -> Dict[str, float]:
         """as ``MOPOPolicy.learn_n``; the real / model split is part of the engine's row layout, so a changed split re-binds"""

@@ -73,6 +73,30 @@ class _TanhGaussPolicy(EnginePolicy):
         squashed, raw = dist.mode() if deterministic else dist.rsample()
         return squashed, dist.log_prob(squashed, raw)
 
+    def actforward_runs(self, obs: torch.Tensor, deterministic: bool = False) -> torch.Tensor:
+        """``actforward`` of EVERY run in one batched forward (the rollouts of a multi-run model-based policy): ``obs``
+        [n_runs, N, obs_dim] on the engine's device -> squashed actions [n_runs, N, act_dim]; block r goes through run r's live actor
+        (``_stacked_net``).  Sampling is ``TanhNormalWrapper.rsample``: mu + exp(clamp(log_sigma, -5, 2)) * eps, eps from torch's
+        device generator, then tanh."""
+        if self._eng is None:
+            raise RuntimeError("actforward_runs before the engine is bound (learn / learn_n binds it)")
+        if any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.actor.modules()):
+            raise NotImplementedError("actforward_runs: an actor with dropout is not supported (the batched forward has no dropout masks)")
+        if obs.dim() != 3 or obs.shape[0] != self._n_runs:
+            raise ValueError(f"obs: expected [n_runs = {self._n_runs}, N, obs_dim], got {tuple(obs.shape)}")
+        P = self._stacked_net(_engine.NET_ACTOR)
+        lin = lambda h, name: torch.baddbmm(P[name + ".bias"].unsqueeze(1), h, P[name + ".weight"].transpose(1, 2))
+        with torch.no_grad():
+            h = obs.to(device=self._arena.device, dtype=torch.float32)
+            idx = sorted(int(k[len("backbone.model."):-len(".weight")]) for k in P if k.startswith("backbone.model.") and k.endswith(".weight"))
+            for i in idx:
+                h = torch.relu(lin(h, f"backbone.model.{i}"))
+            mu = lin(h, "dist_net.mu")
+            if deterministic:
+                return torch.tanh(mu)
+            sigma = torch.clamp(lin(h, "dist_net.sigma"), min=-5.0, max=2.0).exp()
+            return torch.tanh(mu + sigma * torch.randn_like(mu))
+
     def select_action(self, obs: np.ndarray, deterministic: bool = False) -> np.ndarray:
         with torch.no_grad():
             action, _ = self.actforward(obs, deterministic)

@@ -284,7 +284,9 @@ class MBPolicyTrainer(MFPolicyTrainer):
     into ``fake_buffer``'s HBM ring (``fake_buffer.reserve_device()``, called here), and between those points ONE
     ``policy.learn_n(steps, real_buffer, fake_buffer, batch_size, real_ratio)``.  The logged loss keys are the step-weighted means of
     the chunks (what ``logkv_mean`` holds after the same steps); the rollout log line, the ``rollout_info/*`` keys, evaluation,
-    checkpoints, health check and ``dynamics.save`` are those of the host loop.  What differs from the host loop: the minibatch indices
+    checkpoints, health check and ``dynamics.save`` are those of the host loop.  ``fake_buffer`` may be a sequence of ``policy.n_runs``
+    buffers: one model ring per run, run r rolled by its own actor through run r of the dynamics (or a shared one-run ensemble) and
+    sampled by run r only; ``run<r>/rollout_info/*`` per run, the plain keys their mean (``fused=True`` only).  What differs from the host loop: the minibatch indices
     of both buffers come from the device Philox stream instead of numpy's (as for ``MFPolicyTrainer(fused=True)``), and the model
     draws of a rollout from the dynamics' device stream; runs are reproducible from the seed but not index-identical to the
     reference.  Refused at construction: ``dynamics_update_freq > 0`` (only RAMBO updates its dynamics), a policy without
@@ -315,7 +317,21 @@ class MBPolicyTrainer(MFPolicyTrainer):
                 raise ValueError("MBPolicyTrainer(fused=True): the dynamics' termination function is not one of the fixed row-wise tests of "
                                  "utils.termination_fns (no term_kind: an obs_unnormalization wrapper, door or another callable), so the "
                                  "device rollout cannot evaluate it; use fused=False")
-            fake_buffer.reserve_device()
+        from .policy.model_based import per_run_rings
+        self._fake_runs = per_run_rings(policy, fake_buffer)          # a sequence of n_runs buffers: one model ring per run
+        if self._fake_runs is not None and not self._fused_mb:
+            raise ValueError("MBPolicyTrainer(fused=False): per-run model buffers (a sequence as fake_buffer) need fused=True; the host "
+                             "loop stays the reference's single-buffer loop")
+        if self._fused_mb:
+            if self._fake_runs is not None:
+                dyn_runs = int(getattr(policy.dynamics, "_n_runs", 1))
+                if dyn_runs not in (1, len(self._fake_runs)):
+                    raise ValueError(f"MBPolicyTrainer(fused=True): per-run model buffers need a dynamics of {len(self._fake_runs)} runs "
+                                     f"(run r rolls through ensemble r) or of one shared run, this one carries {dyn_runs}")
+                for b in self._fake_runs:
+                    b.reserve_device()
+            else:
+                fake_buffer.reserve_device()
 
     # ---- the reference's inner loop (mb_policy_trainer.py:66-102) -----------------------------------------
     def _rollout(self) -> None:
@@ -328,6 +344,17 @@ class MBPolicyTrainer(MFPolicyTrainer):
 
     def _rollout_fused(self) -> None:
         rollout_info = self.policy.rollout_device(self.real_buffer, self.fake_buffer, self._rollout_batch_size, self._rollout_length)
+        if self._fake_runs is not None:
+            # per-run rings: run<r>/rollout_info/* per run, the plain keys = mean over runs (as the loss keys); the log line carries the
+            # summed transitions and the transition-weighted reward mean
+            nt, rm = np.asarray(rollout_info["num_transitions"], np.float64), np.asarray(rollout_info["reward_mean"], np.float64)
+            self.logger.log("num rollout transitions: {}, reward mean: {:.4f}".format(int(nt.sum()), float((nt * rm).sum() / max(nt.sum(), 1.0))))
+            for r in range(len(nt)):
+                self.logger.logkv_mean(f"run{r}/rollout_info/num_transitions", float(nt[r]))
+                self.logger.logkv_mean(f"run{r}/rollout_info/reward_mean", float(rm[r]))
+            self.logger.logkv_mean("rollout_info/num_transitions", float(nt.mean()))
+            self.logger.logkv_mean("rollout_info/reward_mean", float(rm.mean()))
+            return
         self.logger.log("num rollout transitions: {}, reward mean: {:.4f}".format(rollout_info["num_transitions"], rollout_info["reward_mean"]))
         for k, v in rollout_info.items():
             self.logger.logkv_mean("rollout_info/" + k, v)

@@ -5,7 +5,12 @@
 loop (fused=True), in ONE invocation and alternating -- a warm-up block of each, then three timed blocks each of 2 000 training steps
 including their two rollouts, timed with a host clock around work that ends in a device synchronise.  Also the rollout alone (ms per
 50 000 x 5 rollout, both paths).  Everything is built from seeds (an untrained dynamics ensemble with a unit scaler: the arithmetic per
-row is that of a trained one).  Prints one JSON object; --out writes it too.  Needs a GPU."""
+row is that of a trained one).  Prints one JSON object; --out writes it too.  Needs a GPU.
+
+--runs R measures, instead, R independent seeds in the same invocation and alternating the same way: ONE R-run policy with per-run model
+rings (a list of R model buffers: every run rolls its own actor through its own run of an R-run dynamics into its own ring) against the
+baseline of R single-run fused trainings run one after the other, each with its own policy, dynamics and ring.  The figure is aggregate
+run-steps per second: R x block steps / seconds of the block, rollouts included."""
 import argparse
 import json
 import os
@@ -55,13 +60,13 @@ def dataset(rows):
                 rewards=rng.normal(size=rows).astype(np.float32), terminals=np.zeros(rows, np.float32))
 
 
-def make_policy(algo):
-    torch.manual_seed(1)
+def make_policy(algo, n_runs=1, seed=0):
+    torch.manual_seed(1 + seed)
     model = EnsembleDynamicsModel(OD, AD, DYN_HID, num_ensemble=K, num_elites=E, weight_decays=DECAYS, device=DEV)
     scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
     dyn = EnsembleDynamics(model, torch.optim.Adam(model.parameters(), lr=1e-3), scaler, termination_fn_halfcheetah,
                            penalty_coef=2.5 if algo == "mopo" else 0.0, uncertainty_mode="aleatoric")
-    dyn.set_engine_options(seed=7)
+    dyn.set_engine_options(n_runs=n_runs, seed=7 + seed)
     hid = [256, 256] if algo == "mopo" else [256, 256, 256]
     adam = lambda m, lr: torch.optim.Adam(m.parameters(), lr=lr)
     actor = ActorProb(MLP(OD, hid), TanhDiagGaussian(hid[-1], AD, unbounded=True, conditioned_sigma=True), DEV)
@@ -74,8 +79,56 @@ def make_policy(algo):
         pol = COMBOPolicy(dyn, actor, c1, c2, adam(actor, 1e-4), adam(c1, 3e-4), adam(c2, 3e-4), Space(), tau=0.005, gamma=0.99, alpha=alpha,
                           cql_weight=5.0, temperature=1.0, max_q_backup=False, deterministic_backup=True, with_lagrange=False,
                           num_repeart_actions=10, uniform_rollout=False, rho_s="mix")
-    pol.set_engine_options(seed=3)
+    pol.set_engine_options(n_runs=n_runs, seed=3 + seed)
     return pol
+
+
+def measure_runs(algo, ds, blocks, block_steps, runs):
+    """per-run rings at ``runs`` runs against ``runs`` single-run fused trainings one after the other"""
+    real_ratio = 0.05 if algo == "mopo" else 0.5
+    real = ReplayBuffer(len(ds["rewards"]), (OD,), np.float32, AD, np.float32, device=DEV)
+    real.load_dataset(ds)
+    fake = lambda: ReplayBuffer(MODEL_ROWS, (OD,), np.float32, AD, np.float32, device=DEV)
+    trainer = lambda pol, fk: MBPolicyTrainer(pol, None, real, fk, NullLogger(), ROLLOUT, epoch=1, step_per_epoch=block_steps, batch_size=B,
+                                              real_ratio=real_ratio, fused=True)
+    pol = make_policy(algo, n_runs=runs)
+    pol.train()
+    batched = trainer(pol, [fake() for _ in range(runs)])
+    singles = []
+    for r in range(runs):
+        p1 = make_policy(algo, seed=100 + r)
+        p1.train()
+        singles.append(trainer(p1, fake()))
+    t_now = {"per_run_rings": 0, "sequential": 0}
+
+    def block(name):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if name == "per_run_rings":
+            t_now[name] = batched._train_mb_epoch(1, t_now[name])
+        else:
+            for tr in singles:
+                end = tr._train_mb_epoch(1, t_now[name])
+            t_now[name] = end
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    names = ("sequential", "per_run_rings")
+    np.random.seed(0)
+    torch.manual_seed(0)
+    warm = {name: block(name) for name in names}
+    secs = {name: [] for name in names}
+    for _ in range(blocks):
+        for name in names:
+            secs[name].append(block(name))
+    rsps = {name: [runs * block_steps / s for s in v] for name, v in secs.items()}
+    base_spread = max(rsps["sequential"]) - min(rsps["sequential"])
+    gain = float(np.mean(rsps["per_run_rings"]) - np.mean(rsps["sequential"]))
+    return dict(algo=algo, runs=runs, real_ratio=real_ratio, block_steps=block_steps,
+                rollouts_per_block=len([t for t in range(block_steps) if t % ROLLOUT[0] == 0]), warmup_block_seconds=warm, block_seconds=secs,
+                run_steps_per_s=rsps, run_steps_per_s_mean={k: float(np.mean(v)) for k, v in rsps.items()},
+                sequential_spread_run_steps_per_s=base_spread, per_run_rings_minus_sequential_run_steps_per_s=gain,
+                clears_bar=bool(gain > base_spread), speedup=float(np.mean(rsps["per_run_rings"]) / np.mean(rsps["sequential"])),
+                model_rows=dict(per_run_rings=[b._size for b in batched.fake_buffer], sequential=[tr.fake_buffer._size for tr in singles]))
 
 
 def measure(algo, ds, blocks, block_steps, profile_only=False):
@@ -136,6 +189,7 @@ def main():
     ap.add_argument("--block-steps", type=int, default=BLOCK)
     ap.add_argument("--algos", default="mopo,combo")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--runs", type=int, default=0, help="R > 1: per-run model rings at R runs against R sequential single-run fused trainings")
     ap.add_argument("--profile-block", action="store_true", help="a warm-up and one fused MOPO block only (for a kernel trace)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -145,7 +199,8 @@ def main():
         print(json.dumps(measure("mopo", ds, 1, a.block_steps, profile_only=True)))
         return
     res = {"shape": dict(obs=OD, act=AD, dynamics_hidden=DYN_HID, members=K, batch=B, rollout=ROLLOUT, model_rows=MODEL_ROWS, data_rows=DATA_ROWS),
-           "device": torch.cuda.get_device_name(0), "results": [measure(x, ds, a.blocks, a.block_steps) for x in a.algos.split(",")]}
+           "device": torch.cuda.get_device_name(0), "results": [measure_runs(x, ds, a.blocks, a.block_steps, a.runs) if a.runs > 1 else measure(x, ds, a.blocks, a.block_steps)
+                       for x in a.algos.split(",")]}
     s = json.dumps(res, indent=1)
     print(s)
     if a.out:
