@@ -388,8 +388,38 @@ int orl_dyn_load_save(orl_dynamics* d, int run);
 int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n, int on_device, const float* noise,
                  const int64_t* model_idx, int penalty_mode, float penalty_coef, float* next_obs, float* reward, float* raw_reward,
                  float* penalty, int32_t* model_idx_out);
-/* test tap: parameter gradient of the LAST minibatch of the last orl_dyn_learn_epoch (flat like orl_dyn_get; decay terms excluded) */
+/* test tap: parameter gradient of the LAST minibatch of the last orl_dyn_learn_epoch, or of the last orl_dynadv_update, whichever
+ * ran later (flat like orl_dyn_get; decay terms excluded) */
 int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n_floats);
+
+/* -- RAMBO's adversarial model update (policy/model_based/rambo.py:129-207) on an orl_dynamics ------------------------------------
+ * One update of dynamics_step_and_forward is two calls; the caller computes the advantage (actor and critics) between them.
+ * The optimizer (dynamics_adv_optim) has its own exp_avg / exp_avg_sq / step count: orl_dyn_learn_epoch's Adam state is never touched,
+ * and the forward's activations, workspaces and kept sample belong to these calls alone (orl_dyn_step / validate / learn_epoch
+ * between the two calls leave them alone).  fp32, run-batched like every orl_dyn_* call. */
+/* Adam hyper-parameters of the adversarial optimizer, adv_weight, and the row counts of a call (rollout rows Ba, dataset rows Bs).
+ * Allocates the state on the first call (zero moments, step 0); a later call keeps the state and re-sizes the workspaces. */
+int orl_dynadv_configure(orl_dynamics* d, float lr, float adam_beta1, float adam_beta2, float adam_eps, float adv_weight,
+                         int32_t rollout_rows, int32_t sl_rows);
+/* Forward: obs [n_runs][Ba][obs_dim], act [n_runs][Ba][act_dim] rollout rows and sl_* [n_runs][Bs][..] dataset rows (sl_rew
+ * [n_runs][Bs]) are scaled and concatenated into one input shared by the members; one ensemble forward keeps the activations.
+ * The row's sample s = mean_m + std_m * eps_m (fp32, like Normal.sample) of its member m gives next_obs [n_runs][Ba][obs_dim] and
+ * reward [n_runs][Ba]; s stays on the device for the update.  noise [n_runs][num_ensemble][Ba][obs_dim + 1] (device when on_device)
+ * and model_idx (HOST int64 [n_runs][Ba]) teacher-force the draws; NULL = device Philox / uniform over the run's elites.
+ * model_idx_out [n_runs][Ba] may be NULL.  Arrays are device pointers when on_device.  Synchronises the stream before returning. */
+int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, const float* sl_obs, const float* sl_act,
+                       const float* sl_next_obs, const float* sl_rew, int on_device, const float* noise, const int64_t* model_idx,
+                       float* next_obs, float* reward, int32_t* model_idx_out);
+/* Update: advantage [n_runs][Ba] (already normalised; device pointer when on_device).  Loss = adv_weight * mean_i(log_prob_i A_i)
+ * + Gaussian NLL of the dataset rows + decay + 0.001 (sum max_logvar - sum min_logvar), where log_prob_i is the log of the elite
+ * mixture's density at the kept sample, computed as a log-sum-exp (finite where the reference's exp underflows).  One backward over
+ * the Ba + Bs rows and one Adam step of the adversarial optimizer.  active: host int32 [n_runs] (NULL = all); an inactive run's
+ * parameters and state stay bit for bit.  metrics_out: host [n_runs][4] = all_loss, sl_loss, adv_loss (unweighted), mean log_prob
+ * (zeros for inactive runs).  Fails without a pending orl_dynadv_forward: one update per forward. */
+int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, const int32_t* active, float* metrics_out);
+/* the adversarial optimizer's state, as orl_dyn_adam_get / orl_dyn_adam_set */
+int orl_dynadv_adam_get(orl_dynamics* d, int run, float* exp_avg, float* exp_avg_sq, int64_t n_floats, int64_t* step);
+int orl_dynadv_adam_set(orl_dynamics* d, int run, const float* exp_avg, const float* exp_avg_sq, int64_t n_floats, int64_t step);
 
 #ifdef __cplusplus
 }

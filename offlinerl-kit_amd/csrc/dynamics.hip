@@ -13,7 +13,7 @@
 //                      weights it reads is reduced on the way; inactive runs are skipped (their state stays bit for bit)
 //   k_dyn_loss         adds the decay loss and accumulates the minibatch loss of the active runs
 // Members and runs are batched through blockIdx.z = run * K + member of every GEMM; a 2-D input shared by the members (validate, step)
-// is a member stride of 0.
+// is a member stride of 0.  RAMBO's adversarial update of the same ensemble (orl_dynadv_*) is described where its kernels start.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -344,6 +344,286 @@ __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
   if (p.midx_out) p.midx_out[(long)r * p.n + i] = mi;
 }
 
+// ---- RAMBO's adversarial model update (reference: policy/model_based/rambo.py:129-207): orl_dynadv_* ----
+// One update is two calls with the caller's advantage between them:
+//   forward   k_dyn_adv_input (scale + concatenate the Ba rollout rows and the Bs dataset rows into ONE input shared by the members,
+//             the supervised target), L x E_BIAS_SWISH + E_BIAS with the pre-activations kept, k_dyn_adv_sample
+//   update    k_dyn_adv_head (mixture log-prob + policy-gradient term on the rollout rows, the Gaussian NLL on the dataset rows),
+//             k_dyn_adv_reduce, ONE backward over the Ba + Bs rows, k_dyn_adam on the adversarial optimizer's state, k_dyn_adv_metrics
+
+// rows [0, Ba): scaler(concat(obs, act)), obs kept for the head; rows [Ba, Ba + Bs): scaler(concat(sl_obs, sl_act)) and the target
+// T[r][j] = [sl_next_obs - sl_obs, sl_rew]
+__global__ void k_dyn_adv_input(const float* __restrict__ obs, const float* __restrict__ act, const float* __restrict__ sl_obs,
+                                const float* __restrict__ sl_act, const float* __restrict__ sl_next, const float* __restrict__ sl_rew,
+                                int Ba, int Bs, int od, int ad, const float* __restrict__ mu, const float* __restrict__ sd,
+                                float* __restrict__ X, int xp, float* __restrict__ T, int D, float* __restrict__ obs_keep) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  const int N = Ba + Bs;
+  if (i >= N) return;
+  const bool sl = i >= Ba;
+  const long j = sl ? (long)r * Bs + (i - Ba) : (long)r * Ba + i;
+  const float* o = (sl ? sl_obs : obs) + j * od;
+  const float* a = (sl ? sl_act : act) + j * ad;
+  const int in = od + ad;
+  const float* m = mu + (long)r * in;
+  const float* s = sd + (long)r * in;
+  float* x = X + ((long)r * N + i) * xp;
+  for (int c = 0; c < od; ++c) x[c] = (o[c] - m[c]) / s[c];
+  for (int c = 0; c < ad; ++c) x[od + c] = (a[c] - m[od + c]) / s[od + c];
+  for (int c = in; c < xp; ++c) x[c] = 0.f;
+  if (sl) {
+    float* t = T + j * D;
+    const float* nx = sl_next + j * od;
+    for (int c = 0; c < od; ++c) t[c] = nx[c] - o[c];
+    t[od] = sl_rew[j];
+  } else {
+    for (int c = 0; c < od; ++c) obs_keep[j * od + c] = o[c];
+  }
+}
+
+struct DynAdvSampleP {
+  const float* OUT; int op;
+  const float* obs; int Ba, N, od, D, K;
+  const float* params; long P, off_max, off_min;
+  const float* noise; const int* midx;
+  const int* elites; int n_elites;
+  uint64_t seed; uint64_t call;
+  float* next_obs; float* reward; float* S; int* midx_out;
+};
+
+// the sampling head, one thread per (run, rollout row, four output dims): s = mean_m + std_m eps_m of the row's member m in fp32
+// (torch.normal: eps std rounded, then + mean), kept in S[r][i][D] for the update
+__global__ __launch_bounds__(256) void k_dyn_adv_sample(DynAdvSampleP p) {
+  const int nq = (p.D + 3) >> 2;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  if (e >= p.Ba * nq) return;
+  const int i = e / nq, q = e - i * nq;
+  const int D = p.D, od = p.od, K = p.K;
+  const float* mx = p.params + r * p.P + p.off_max;
+  const float* mn = p.params + r * p.P + p.off_min;
+  int mi;
+  uint32_t rnd[4];
+  if (p.midx) mi = p.midx[(long)r * p.Ba + i];
+  else {
+    dyn_philox(p.seed, (uint32_t)i, 0u, (uint32_t)r, (uint32_t)(0x80000000u | (uint32_t)p.call), rnd);
+    mi = p.elites[r * K + (int)(((uint64_t)rnd[0] * (uint64_t)p.n_elites) >> 32)];
+  }
+  if (!p.noise) dyn_philox(p.seed, (uint32_t)i, 0u, (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)q, rnd);
+  const float* out = p.OUT + (((long)r * K + mi) * p.N + i) * p.op;
+  const long ri = (long)r * p.Ba + i;
+  for (int j = 0; j < 4 && 4 * q + j < D; ++j) {
+    const int d = 4 * q + j;
+    float eps;
+    if (p.noise) eps = p.noise[(((long)r * K + mi) * p.Ba + i) * D + d];
+    else {
+      const float u1 = dyn_u01(rnd[j & ~1]), u2 = dyn_u01(rnd[j | 1]);
+      const float rad = sqrtf(-2.0f * logf(u1)), th = 6.28318530717958647692f * u2;
+      eps = (j & 1) ? rad * sinf(th) : rad * cosf(th);
+    }
+    float mean = out[d];
+    if (d < od) mean += p.obs[ri * od + d];
+    const float x = out[D + d];
+    const float l1 = mx[d] - dyn_softplus(mx[d] - x);
+    const float lv = mn[d] + dyn_softplus(l1 - mn[d]);
+    const float s = __fadd_rn(mean, __fmul_rn(sqrtf(expf(lv)), eps));
+    p.S[ri * D + d] = s;
+    if (d < od) p.next_obs[ri * od + d] = s;
+    else p.reward[ri] = s;
+  }
+  if (q == 0 && p.midx_out) p.midx_out[ri] = mi;
+}
+
+struct DynAdvHeadP {
+  const float* OUT; float* dOUT; int op;
+  const float* obs; const float* S; const float* T; const float* adv;
+  float* lterm; float* gmax; float* gmin; double* rowlp;
+  const float* params; long P, off_max, off_min;
+  const int* elites; int n_elites;
+  int K, D, od, Ba, Bs, wpb;
+  float adv_weight;
+};
+
+// the head of the update, one WAVE per (run, row), lanes over (member, dim); blockDim = 64 wpb, dynamic LDS wpb (K D + 64) doubles.
+// Rollout rows (i < Ba): lp_k = sum_d Normal(mean_k, std_k).log_prob(s) summed in double in dim order, the elite mixture as a
+// log-sum-exp (finite where exp(lp_k) underflows), w_k = softmax over the elites (exactly 0 elsewhere) and the gradient
+// adv_weight A_i / Ba w_k through mean, soft_clamp and max / min_logvar.  Dataset rows: k_dyn_nll's terms with Bs rows.
+__global__ void k_dyn_adv_head(DynAdvHeadP p) {
+  extern __shared__ double adv_sm[];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = blockIdx.y;
+  const int K = p.K, D = p.D, KD = K * D, N = p.Ba + p.Bs;
+  const int i = blockIdx.x * p.wpb + w;
+  const bool valid = i < N, roll = valid && i < p.Ba;
+  double* lp = adv_sm + (long)w * (KD + 64);
+  double* wk = lp + KD;
+  const float* mxp = p.params + r * p.P + p.off_max;
+  const float* mnp = p.params + r * p.P + p.off_min;
+  const long ri = (long)r * p.Ba + i;
+  if (roll) {
+    for (int e = lane; e < KD; e += 64) {
+      const int k = e / D, d = e - k * D;
+      const float* out = p.OUT + (((long)r * K + k) * N + i) * p.op;
+      float mean = out[d];
+      if (d < p.od) mean += p.obs[ri * p.od + d];
+      const float x = out[D + d];
+      const float l1 = mxp[d] - dyn_softplus(mxp[d] - x);
+      const float lv = mnp[d] + dyn_softplus(l1 - mnp[d]);
+      const float sdv = sqrtf(expf(lv));
+      const float z = p.S[ri * D + d] - mean;
+      lp[e] = (double)(-(z * z) / (2.f * (sdv * sdv)) - logf(sdv) - 0.91893853320467274178f);
+    }
+  }
+  __syncthreads();
+  if (roll) {
+    double s = 0.0;
+    bool el = false;
+    if (lane < K) {
+      for (int d = 0; d < D; ++d) s += lp[lane * D + d];
+      for (int j = 0; j < p.n_elites; ++j) el = el || (p.elites[r * K + j] == lane);
+    }
+    double m = el ? s : -INFINITY;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    const double ex = el ? exp(s - m) : 0.0;
+    double sum = ex;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    wk[lane] = ex / sum;
+    if (lane == 0) p.rowlp[ri] = m + log(sum) - log((double)p.n_elites);
+  }
+  __syncthreads();
+  if (!valid) return;
+  if (roll) {
+    const float c0 = p.adv_weight * p.adv[ri] / (float)p.Ba;
+    for (int e = lane; e < KD; e += 64) {
+      const int k = e / D, d = e - k * D;
+      const long row = ((long)r * K + k) * N + i;
+      const float* out = p.OUT + row * p.op;
+      float mean = out[d];
+      if (d < p.od) mean += p.obs[ri * p.od + d];
+      const float x = out[D + d];
+      const float y1 = mxp[d] - x;
+      const float l1 = mxp[d] - dyn_softplus(y1);
+      const float y2 = l1 - mnp[d];
+      const float lv = mnp[d] + dyn_softplus(y2);
+      const float s1 = dyn_dsoftplus(y1), s2 = dyn_dsoftplus(y2);
+      const float inv = expf(-lv);
+      const float z = p.S[ri * D + d] - mean;
+      const float c = c0 * (float)wk[k];
+      const float dlv = c * 0.5f * (z * z * inv - 1.f);
+      const float dl1 = dlv * s2;
+      p.dOUT[row * p.op + d] = c * z * inv;
+      p.dOUT[row * p.op + D + d] = dl1 * s1;
+      p.lterm[row * D + d] = 0.f;
+      p.gmax[row * D + d] = dl1 * (1.f - s1);
+      p.gmin[row * D + d] = dlv * (1.f - s2);
+    }
+  } else {
+    const long tj = (long)r * p.Bs + (i - p.Ba);
+    const float scale = 1.0f / ((float)p.Bs * (float)D);
+    for (int e = lane; e < KD; e += 64) {
+      const int k = e / D, d = e - k * D;
+      const long row = ((long)r * K + k) * N + i;
+      const float mean = p.OUT[row * p.op + d], x = p.OUT[row * p.op + D + d];
+      const float y1 = mxp[d] - x;
+      const float l1 = mxp[d] - dyn_softplus(y1);
+      const float y2 = l1 - mnp[d];
+      const float lv = mnp[d] + dyn_softplus(y2);
+      const float s1 = dyn_dsoftplus(y1), s2 = dyn_dsoftplus(y2);
+      const float inv = expf(-lv);
+      const float diff = mean - p.T[tj * D + d];
+      const float sq = diff * diff * inv;
+      const float dlv = (1.f - sq) * scale;
+      const float dl1 = dlv * s2;
+      p.dOUT[row * p.op + d] = 2.f * diff * inv * scale;
+      p.dOUT[row * p.op + D + d] = dl1 * s1;
+      p.lterm[row * D + d] = sq + lv;
+      p.gmax[row * D + d] = dl1 * (1.f - s1);
+      p.gmin[row * D + d] = dlv * (1.f - s2);
+    }
+  }
+}
+
+// per run (blockIdx.x), 1024 threads, fixed order: the NLL terms' column sums over the dataset rows, the max / min_logvar gradient
+// columns over all rows (+coef / -coef), sum_i log_prob_i A_i and sum_i log_prob_i over the rollout rows (double)
+__global__ __launch_bounds__(1024) void k_dyn_adv_reduce(const float* __restrict__ lterm, const float* __restrict__ gmax,
+                                                         const float* __restrict__ gmin, const double* __restrict__ rowlp,
+                                                         const float* __restrict__ adv, int K, int Ba, int Bs, int D,
+                                                         const float* __restrict__ params, float* __restrict__ G, long P, long off_max,
+                                                         long off_min, float coef, float* __restrict__ nll_out, float* __restrict__ advm) {
+  __shared__ float red[3 * 64];
+  __shared__ double red2[2];
+  const int r = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nw = blockDim.x >> 6;
+  const int N = Ba + Bs;
+  for (int c = w; c < 3 * D + 2; c += nw) {
+    if (c < 3 * D) {
+      const float* a = c < D ? lterm : (c < 2 * D ? gmax : gmin);
+      const int d = c % D;
+      const int i0 = c < D ? Ba : 0, rows = N - i0;
+      const int KR = K * rows;
+      float s = 0.f;
+      for (int e = lane; e < KR; e += 64) {
+        const int k = e / rows, i = i0 + (e - k * rows);
+        s += a[(((long)r * K + k) * N + i) * D + d];
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      if (lane == 0) red[c] = s;
+    } else {
+      const bool wa = c == 3 * D;
+      double s = 0.0;
+      for (int i = lane; i < Ba; i += 64) s += wa ? rowlp[(long)r * Ba + i] * (double)adv[(long)r * Ba + i] : rowlp[(long)r * Ba + i];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      if (lane == 0) red2[c - 3 * D] = s;
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < D) {
+    G[r * P + off_max + t] = red[D + t] + coef;
+    G[r * P + off_min + t] = red[2 * D + t] - coef;
+  }
+  if (t == 0) {
+    float ls = 0.f, smax = 0.f, smin = 0.f;
+    for (int d = 0; d < D; ++d) {
+      ls += red[d];
+      smax += params[r * P + off_max + d];
+      smin += params[r * P + off_min + d];
+    }
+    nll_out[r] = ls / ((float)Bs * (float)D) + (coef * smax - coef * smin);
+    advm[2 * r] = (float)(red2[0] / (double)Ba);
+    advm[2 * r + 1] = (float)(red2[1] / (double)Ba);
+  }
+}
+
+// metrics[r] = {all_loss, sl_loss (NLL + decay + logvar terms), adv_loss (unweighted), mean log_prob}; zeros for an inactive run
+__global__ __launch_bounds__(256) void k_dyn_adv_metrics(const float* __restrict__ nll, const float* __restrict__ decay_part, int nblk,
+                                                         const int* __restrict__ active, const float* __restrict__ advm, float adv_weight,
+                                                         float* __restrict__ metrics) {
+  __shared__ float s_red[4];
+  const int r = blockIdx.x;
+  float s = 0.f;
+  if (active[r])
+    for (int b = threadIdx.x; b < nblk; b += blockDim.x) s += decay_part[(long)r * nblk + b];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float* m = metrics + 4 * r;
+    if (!active[r]) { m[0] = m[1] = m[2] = m[3] = 0.f; return; }
+    const float sl = nll[r] + ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+    m[0] = adv_weight * advm[2 * r] + sl;
+    m[1] = sl;
+    m[2] = advm[2 * r];
+    m[3] = advm[2 * r + 1];
+  }
+}
+
 }  // namespace orl
 
 using namespace orl;
@@ -377,6 +657,21 @@ struct orl_dynamics {
   float *sNext = nullptr, *sRew = nullptr, *sRaw = nullptr, *sPen = nullptr;
   int *sIdx = nullptr, *sMidx = nullptr, *sMidxOut = nullptr;
   uint64_t step_calls = 0;
+  // RAMBO's adversarial update (orl_dynadv_*): its own optimizer state, workspaces over Ba + Bs rows and the kept sample
+  bool adv_on = false, adv_pending = false;
+  int aBa = 0, aBs = 0;
+  float adv_lr = 0.f, adv_b1 = 0.9f, adv_b2 = 0.999f, adv_eps = 1e-8f, adv_weight = 0.f;
+  float *adv_m = nullptr, *adv_v = nullptr;
+  std::vector<long long> adv_tstep;
+  uint64_t adv_calls = 0;
+  float *aX = nullptr, *aT = nullptr, *aOUT = nullptr, *adOUT = nullptr, *adA = nullptr, *adB = nullptr;
+  float *aH[ORL_MAX_HIDDEN] = {}, *aZ[ORL_MAX_HIDDEN] = {};
+  float *aLterm = nullptr, *aGmax = nullptr, *aGmin = nullptr, *aS = nullptr, *aObs = nullptr, *aAdv = nullptr, *aAdvm = nullptr,
+        *aMetrics = nullptr;
+  double* aRowlp = nullptr;
+  float *aInObs = nullptr, *aInAct = nullptr, *aSlObs = nullptr, *aSlAct = nullptr, *aSlNext = nullptr, *aSlRew = nullptr,
+        *aNoise = nullptr, *aNext = nullptr, *aRew = nullptr;
+  int *aMidx = nullptr, *aMidxOut = nullptr;
   std::vector<void*> allocs;
 };
 
@@ -465,6 +760,23 @@ static int dyn_wgrad(orl_dynamics* d, const DMat& dY, const DMat& X, int M, int 
   hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(cfg, p, nz, d->stream, false, false, P_F32);
   if (e != hipSuccess) return fail(std::string("orl_dyn wgrad gemm: ") + hipGetErrorString(e));
   return 0;
+}
+
+// k_dyn_adam's arguments less the optimizer (m, v, lr, betas, eps, batch): the trainable segments with their decays
+static DynAdamP dyn_adam_params(orl_dynamics* d) {
+  DynAdamP a;
+  memset(&a, 0, sizeof(a));
+  a.params = d->params; a.G = d->grads; a.P = d->P;
+  for (int l = 0; l <= d->L; ++l) {
+    const long nw = (long)d->K * d->width[l] * d->width[l + 1], nbias = (long)d->K * d->width[l + 1];
+    a.seg_b[a.nseg] = d->w_off[l]; a.seg_e[a.nseg] = d->w_off[l] + nw; a.seg_wd[a.nseg++] = d->c.weight_decay[l];
+    a.seg_b[a.nseg] = d->b_off[l]; a.seg_e[a.nseg] = d->b_off[l] + nbias; a.seg_wd[a.nseg++] = 0.f;
+  }
+  a.seg_b[a.nseg] = d->off_max; a.seg_e[a.nseg] = d->off_max + d->D; a.seg_wd[a.nseg++] = 0.f;
+  a.seg_b[a.nseg] = d->off_min; a.seg_e[a.nseg] = d->off_min + d->D; a.seg_wd[a.nseg++] = 0.f;
+  a.active = d->active_d; a.t0 = d->t0_d;
+  a.decay_part = d->decay_part; a.nblk = d->nblk;
+  return a;
 }
 
 static int dyn_grow_step(orl_dynamics* d, long rows) {
@@ -762,19 +1074,9 @@ int orl_dyn_learn_epoch(orl_dynamics* d, const int64_t* idx, int64_t train_size,
   DYN_HIP(hipMemsetAsync(d->loss_sum, 0, sizeof(float) * R, d->stream));
   const long nb = (train_size + B - 1) / B;
   const int p0 = d->pitch[0], po = d->pitch[L + 1];
-  DynAdamP a;
-  memset(&a, 0, sizeof(a));
-  a.params = d->params; a.m = d->adam_m; a.v = d->adam_v; a.G = d->grads; a.P = d->P;
-  for (int l = 0; l <= L; ++l) {
-    const long nw = (long)K * d->width[l] * d->width[l + 1], nbias = (long)K * d->width[l + 1];
-    a.seg_b[a.nseg] = d->w_off[l]; a.seg_e[a.nseg] = d->w_off[l] + nw; a.seg_wd[a.nseg++] = d->c.weight_decay[l];
-    a.seg_b[a.nseg] = d->b_off[l]; a.seg_e[a.nseg] = d->b_off[l] + nbias; a.seg_wd[a.nseg++] = 0.f;
-  }
-  a.seg_b[a.nseg] = d->off_max; a.seg_e[a.nseg] = d->off_max + D; a.seg_wd[a.nseg++] = 0.f;
-  a.seg_b[a.nseg] = d->off_min; a.seg_e[a.nseg] = d->off_min + D; a.seg_wd[a.nseg++] = 0.f;
-  a.active = d->active_d; a.t0 = d->t0_d;
+  DynAdamP a = dyn_adam_params(d);
+  a.m = d->adam_m; a.v = d->adam_v;
   a.lr = d->c.lr; a.b1 = d->c.adam_beta1; a.b2 = d->c.adam_beta2; a.eps = d->c.adam_eps;
-  a.decay_part = d->decay_part; a.nblk = d->nblk;
   const long xs1 = (long)B * p0, xs0 = (long)K * xs1;
   for (long b = 0; b < nb; ++b) {
     const int rows = (int)std::min<long>(B, train_size - b * B);
@@ -949,6 +1251,224 @@ int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n) {
   if (dyn_check_run(d, run, n, "orl_dyn_debug_grads")) return -1;
   DYN_HIP(hipStreamSynchronize(d->stream));
   DYN_HIP(hipMemcpy(host, d->grads + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- RAMBO's adversarial update ----
+int orl_dynadv_configure(orl_dynamics* d, float lr, float beta1, float beta2, float eps, float adv_weight, int32_t rollout_rows,
+                         int32_t sl_rows) {
+  if (!d) return fail("orl_dynadv_configure: null handle");
+  if (rollout_rows < 1 || sl_rows < 1) return fail("orl_dynadv_configure: need rollout_rows >= 1 and sl_rows >= 1");
+  if (!d->c.with_reward) return fail("orl_dynadv_configure: needs with_reward (the sample's last dim is the reward)");
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  const long R = d->R, K = d->K, D = d->D, L = d->L;
+  d->adv_lr = lr; d->adv_b1 = beta1; d->adv_b2 = beta2; d->adv_eps = eps; d->adv_weight = adv_weight;
+  if (!d->adv_m) {
+    if (dyn_alloc_t(d, &d->adv_m, R * d->P) || dyn_alloc_t(d, &d->adv_v, R * d->P)) return -1;
+    d->adv_tstep.assign(R, 0);
+  }
+  if (d->adv_on && d->aBa == rollout_rows && d->aBs == sl_rows) return 0;
+  d->adv_pending = false;
+  float** fs[] = {&d->aX, &d->aT, &d->aOUT, &d->adOUT, &d->adA, &d->adB, &d->aLterm, &d->aGmax, &d->aGmin, &d->aS, &d->aObs, &d->aAdv,
+                  &d->aAdvm, &d->aMetrics, &d->aInObs, &d->aInAct, &d->aSlObs, &d->aSlAct, &d->aSlNext, &d->aSlRew, &d->aNoise, &d->aNext,
+                  &d->aRew};
+  for (float** f : fs) { dyn_free(d, *f); *f = nullptr; }
+  for (int l = 0; l < L; ++l) { dyn_free(d, d->aH[l]); dyn_free(d, d->aZ[l]); d->aH[l] = d->aZ[l] = nullptr; }
+  dyn_free(d, d->aRowlp); d->aRowlp = nullptr;
+  dyn_free(d, d->aMidx); dyn_free(d, d->aMidxOut); d->aMidx = d->aMidxOut = nullptr;
+  d->adv_on = false;
+  const long Ba = rollout_rows, Bs = sl_rows, N = Ba + Bs;
+  int hmax = 4;
+  for (int l = 1; l <= L + 1; ++l) hmax = std::max(hmax, d->pitch[l]);
+  const long po = d->pitch[L + 1];
+  bool bad = dyn_alloc_t(d, &d->aX, R * N * d->pitch[0]) || dyn_alloc_t(d, &d->aT, R * Bs * D) || dyn_alloc_t(d, &d->aOUT, R * K * N * po) ||
+             dyn_alloc_t(d, &d->adOUT, R * K * N * po) || dyn_alloc_t(d, &d->adA, R * K * N * hmax) ||
+             dyn_alloc_t(d, &d->adB, R * K * N * hmax) || dyn_alloc_t(d, &d->aLterm, R * K * N * D) ||
+             dyn_alloc_t(d, &d->aGmax, R * K * N * D) || dyn_alloc_t(d, &d->aGmin, R * K * N * D) || dyn_alloc_t(d, &d->aS, R * Ba * D) ||
+             dyn_alloc_t(d, &d->aObs, R * Ba * d->od) || dyn_alloc_t(d, &d->aAdv, R * Ba) || dyn_alloc_t(d, &d->aAdvm, R * 2) ||
+             dyn_alloc_t(d, &d->aMetrics, R * 4) || dyn_alloc_t(d, &d->aRowlp, R * Ba) || dyn_alloc_t(d, &d->aInObs, R * Ba * d->od) ||
+             dyn_alloc_t(d, &d->aInAct, R * Ba * d->ad) || dyn_alloc_t(d, &d->aSlObs, R * Bs * d->od) ||
+             dyn_alloc_t(d, &d->aSlAct, R * Bs * d->ad) || dyn_alloc_t(d, &d->aSlNext, R * Bs * d->od) ||
+             dyn_alloc_t(d, &d->aSlRew, R * Bs) || dyn_alloc_t(d, &d->aNoise, R * K * Ba * D) || dyn_alloc_t(d, &d->aNext, R * Ba * d->od) ||
+             dyn_alloc_t(d, &d->aRew, R * Ba) || dyn_alloc_t(d, &d->aMidx, R * Ba) || dyn_alloc_t(d, &d->aMidxOut, R * Ba);
+  for (int l = 0; l < L && !bad; ++l)
+    bad = dyn_alloc_t(d, &d->aH[l], R * K * N * d->pitch[l + 1]) || dyn_alloc_t(d, &d->aZ[l], R * K * N * d->pitch[l + 1]);
+  if (bad) return -1;
+  d->aBa = rollout_rows; d->aBs = sl_rows;
+  d->adv_on = true;
+  return 0;
+}
+
+int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, const float* sl_obs, const float* sl_act,
+                       const float* sl_next_obs, const float* sl_rew, int on_device, const float* noise, const int64_t* model_idx,
+                       float* next_obs, float* reward, int32_t* midx_out) {
+  if (!d || !obs || !act || !sl_obs || !sl_act || !sl_next_obs || !sl_rew || !next_obs || !reward)
+    return fail("orl_dynadv_forward: bad arguments");
+  if (!d->adv_on) return fail("orl_dynadv_forward: orl_dynadv_configure first");
+  const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad, L = d->L;
+  const long Ba = d->aBa, Bs = d->aBs, N = Ba + Bs;
+  d->adv_pending = false;
+  if (!on_device) {
+    const hipMemcpyKind h2d = hipMemcpyHostToDevice;
+    DYN_HIP(hipMemcpyAsync(d->aInObs, obs, sizeof(float) * R * Ba * od, h2d, d->stream));
+    DYN_HIP(hipMemcpyAsync(d->aInAct, act, sizeof(float) * R * Ba * ad, h2d, d->stream));
+    DYN_HIP(hipMemcpyAsync(d->aSlObs, sl_obs, sizeof(float) * R * Bs * od, h2d, d->stream));
+    DYN_HIP(hipMemcpyAsync(d->aSlAct, sl_act, sizeof(float) * R * Bs * ad, h2d, d->stream));
+    DYN_HIP(hipMemcpyAsync(d->aSlNext, sl_next_obs, sizeof(float) * R * Bs * od, h2d, d->stream));
+    DYN_HIP(hipMemcpyAsync(d->aSlRew, sl_rew, sizeof(float) * R * Bs, h2d, d->stream));
+    obs = d->aInObs; act = d->aInAct; sl_obs = d->aSlObs; sl_act = d->aSlAct; sl_next_obs = d->aSlNext; sl_rew = d->aSlRew;
+  }
+  const float* noise_d = nullptr;
+  const int* midx_d = nullptr;
+  if (noise) {
+    if (on_device) noise_d = noise;
+    else {
+      DYN_HIP(hipMemcpyAsync(d->aNoise, noise, sizeof(float) * R * K * Ba * D, hipMemcpyHostToDevice, d->stream));
+      noise_d = d->aNoise;
+    }
+  }
+  std::vector<int> mi;
+  if (model_idx) {
+    mi.resize((size_t)R * Ba);
+    for (long i = 0; i < (long)R * Ba; ++i) {
+      if (model_idx[i] < 0 || model_idx[i] >= K) return fail("orl_dynadv_forward: model index out of range");
+      mi[i] = (int)model_idx[i];
+    }
+    DYN_HIP(hipMemcpyAsync(d->aMidx, mi.data(), sizeof(int) * mi.size(), hipMemcpyHostToDevice, d->stream));
+    midx_d = d->aMidx;
+  }
+  const int p0 = d->pitch[0], po = d->pitch[L + 1];
+  hipLaunchKernelGGL(k_dyn_adv_input, dim3((unsigned)((N + 255) / 256), R), dim3(256), 0, d->stream, obs, act, sl_obs, sl_act, sl_next_obs,
+                     sl_rew, (int)Ba, (int)Bs, od, ad, (const float*)d->mu, (const float*)d->sd, d->aX, p0, d->aT, D, d->aObs);
+  DYN_LAUNCHED("k_dyn_adv_input");
+  DMat X = {d->aX, N * p0, 0, p0};
+  for (int l = 0; l < L; ++l) {
+    const int pt = d->pitch[l + 1];
+    const DMat Y = {d->aH[l], (long)K * N * pt, N * pt, pt};
+    if (dyn_fwd(d, X, (int)N, l, Y, d->aZ[l], true)) return -1;
+    X = Y;
+  }
+  const DMat Out = {d->aOUT, (long)K * N * po, N * po, po};
+  if (dyn_fwd(d, X, (int)N, L, Out, nullptr, false)) return -1;
+  DynAdvSampleP s;
+  memset(&s, 0, sizeof(s));
+  s.OUT = d->aOUT; s.op = po;
+  s.obs = d->aObs; s.Ba = (int)Ba; s.N = (int)N; s.od = od; s.D = D; s.K = K;
+  s.params = d->params; s.P = d->P; s.off_max = d->off_max; s.off_min = d->off_min;
+  s.noise = noise_d; s.midx = midx_d;
+  s.elites = d->elites_d;
+  s.n_elites = (int)d->elites_h[0].size();
+  for (int r = 1; r < R; ++r)
+    if ((int)d->elites_h[r].size() != s.n_elites) return fail("orl_dynadv_forward: every run needs the same number of elites");
+  s.seed = d->c.seed ^ 0x9E3779B97F4A7C15ull; s.call = d->adv_calls++;
+  s.next_obs = on_device ? next_obs : d->aNext;
+  s.reward = on_device ? reward : d->aRew;
+  s.S = d->aS;
+  s.midx_out = midx_out ? (on_device ? (int*)midx_out : d->aMidxOut) : nullptr;
+  const long ns = Ba * ((D + 3) / 4);
+  hipLaunchKernelGGL(k_dyn_adv_sample, dim3((unsigned)((ns + 255) / 256), R), dim3(256), 0, d->stream, s);
+  DYN_LAUNCHED("k_dyn_adv_sample");
+  if (!on_device) {
+    DYN_HIP(hipMemcpyAsync(next_obs, d->aNext, sizeof(float) * R * Ba * od, hipMemcpyDeviceToHost, d->stream));
+    DYN_HIP(hipMemcpyAsync(reward, d->aRew, sizeof(float) * R * Ba, hipMemcpyDeviceToHost, d->stream));
+    if (midx_out) DYN_HIP(hipMemcpyAsync(midx_out, d->aMidxOut, sizeof(int) * R * Ba, hipMemcpyDeviceToHost, d->stream));
+  }
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  d->adv_pending = true;
+  return 0;
+}
+
+int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, const int32_t* active, float* metrics_out) {
+  if (!d || !advantage) return fail("orl_dynadv_update: bad arguments");
+  if (!d->adv_on || !d->adv_pending) return fail("orl_dynadv_update: no pending forward (orl_dynadv_forward first; one update per forward)");
+  const int R = d->R, K = d->K, D = d->D, L = d->L;
+  const long Ba = d->aBa, Bs = d->aBs, N = Ba + Bs;
+  d->adv_pending = false;
+  std::vector<int> act(R, 1);
+  if (active) for (int r = 0; r < R; ++r) act[r] = active[r] ? 1 : 0;
+  std::vector<long long> t0(d->adv_tstep.begin(), d->adv_tstep.end());
+  DYN_HIP(hipMemcpyAsync(d->active_d, act.data(), sizeof(int) * R, hipMemcpyHostToDevice, d->stream));
+  DYN_HIP(hipMemcpyAsync(d->t0_d, t0.data(), sizeof(long long) * R, hipMemcpyHostToDevice, d->stream));
+  const float* adv_d = advantage;
+  if (!on_device) {
+    DYN_HIP(hipMemcpyAsync(d->aAdv, advantage, sizeof(float) * R * Ba, hipMemcpyHostToDevice, d->stream));
+    adv_d = d->aAdv;
+  }
+  const int po = d->pitch[L + 1];
+  DynAdvHeadP h;
+  memset(&h, 0, sizeof(h));
+  h.OUT = d->aOUT; h.dOUT = d->adOUT; h.op = po;
+  h.obs = d->aObs; h.S = d->aS; h.T = d->aT; h.adv = adv_d;
+  h.lterm = d->aLterm; h.gmax = d->aGmax; h.gmin = d->aGmin; h.rowlp = d->aRowlp;
+  h.params = d->params; h.P = d->P; h.off_max = d->off_max; h.off_min = d->off_min;
+  h.elites = d->elites_d; h.n_elites = (int)d->elites_h[0].size();
+  for (int r = 1; r < R; ++r)
+    if ((int)d->elites_h[r].size() != h.n_elites) return fail("orl_dynadv_update: every run needs the same number of elites");
+  h.K = K; h.D = D; h.od = d->od; h.Ba = (int)Ba; h.Bs = (int)Bs;
+  h.adv_weight = d->adv_weight;
+  const size_t per_wave = sizeof(double) * ((size_t)K * D + 64);
+  h.wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (32 * 1024) / per_wave));
+  if (per_wave > 48 * 1024) return fail("orl_dynadv_update: num_ensemble * (obs_dim + 1) is too large for the head's LDS");
+  hipLaunchKernelGGL(k_dyn_adv_head, dim3((unsigned)((N + h.wpb - 1) / h.wpb), R), dim3(64 * h.wpb), per_wave * h.wpb, d->stream, h);
+  DYN_LAUNCHED("k_dyn_adv_head");
+  hipLaunchKernelGGL(k_dyn_adv_reduce, dim3(R), dim3(1024), 0, d->stream, (const float*)d->aLterm, (const float*)d->aGmax,
+                     (const float*)d->aGmin, (const double*)d->aRowlp, adv_d, K, (int)Ba, (int)Bs, D, (const float*)d->params, d->grads,
+                     d->P, d->off_max, d->off_min, 0.001f, d->nll, d->aAdvm);
+  DYN_LAUNCHED("k_dyn_adv_reduce");
+  // ONE backward over the Ba + Bs rows, top down; layer 0's input is shared by the members (member stride 0)
+  std::vector<DMat> Xs(L + 1), Zs(L);
+  Xs[0] = {d->aX, N * d->pitch[0], 0, d->pitch[0]};
+  for (int l = 0; l < L; ++l) {
+    const int pt = d->pitch[l + 1];
+    Xs[l + 1] = {d->aH[l], (long)K * N * pt, N * pt, pt};
+    Zs[l] = {d->aZ[l], (long)K * N * pt, N * pt, pt};
+  }
+  DMat dY = {d->adOUT, (long)K * N * po, N * po, po};
+  float* dbuf[2] = {d->adA, d->adB};
+  for (int l = L; l >= 0; --l) {
+    if (dyn_wgrad(d, dY, Xs[l], (int)N, l)) return -1;
+    if (l > 0) {
+      const int pt = d->pitch[l];
+      const DMat dX = {dbuf[l & 1], (long)K * N * pt, N * pt, pt};
+      if (dyn_dgrad(d, dY, (int)N, l, dX, Zs[l - 1])) return -1;
+      dY = dX;
+    }
+  }
+  DynAdamP a = dyn_adam_params(d);
+  a.m = d->adv_m; a.v = d->adv_v;
+  a.lr = d->adv_lr; a.b1 = d->adv_b1; a.b2 = d->adv_b2; a.eps = d->adv_eps;
+  a.batch = 0;
+  hipLaunchKernelGGL(k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, d->stream, a);
+  DYN_LAUNCHED("k_dyn_adam");
+  hipLaunchKernelGGL(k_dyn_adv_metrics, dim3(R), dim3(256), 0, d->stream, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
+                     (const int*)d->active_d, (const float*)d->aAdvm, d->adv_weight, d->aMetrics);
+  DYN_LAUNCHED("k_dyn_adv_metrics");
+  std::vector<float> ms((size_t)R * 4);
+  DYN_HIP(hipMemcpyAsync(ms.data(), d->aMetrics, sizeof(float) * ms.size(), hipMemcpyDeviceToHost, d->stream));
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  for (int r = 0; r < R; ++r)
+    if (act[r]) d->adv_tstep[r] += 1;
+  if (metrics_out) memcpy(metrics_out, ms.data(), sizeof(float) * ms.size());
+  return 0;
+}
+
+int orl_dynadv_adam_get(orl_dynamics* d, int run, float* m, float* v, int64_t n, int64_t* step) {
+  if (dyn_check_run(d, run, n, "orl_dynadv_adam_get")) return -1;
+  if (!d->adv_m) return fail("orl_dynadv_adam_get: orl_dynadv_configure first");
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  if (m) DYN_HIP(hipMemcpy(m, d->adv_m + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  if (v) DYN_HIP(hipMemcpy(v, d->adv_v + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  if (step) *step = d->adv_tstep[run];
+  return 0;
+}
+
+int orl_dynadv_adam_set(orl_dynamics* d, int run, const float* m, const float* v, int64_t n, int64_t step) {
+  if (dyn_check_run(d, run, n, "orl_dynadv_adam_set")) return -1;
+  if (!d->adv_m) return fail("orl_dynadv_adam_set: orl_dynadv_configure first");
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  if (m) DYN_HIP(hipMemcpy(d->adv_m + (long)run * d->P, m, sizeof(float) * d->P, hipMemcpyHostToDevice));
+  if (v) DYN_HIP(hipMemcpy(d->adv_v + (long)run * d->P, v, sizeof(float) * d->P, hipMemcpyHostToDevice));
+  d->adv_tstep[run] = step;
   return 0;
 }
 

@@ -55,7 +55,10 @@ ABI_SYMBOLS = [
     "orl_dyn_num_tensors", "orl_dyn_tensor", "orl_dyn_ptr", "orl_dyn_set", "orl_dyn_get", "orl_dyn_adam_get", "orl_dyn_adam_set",
     "orl_dyn_set_elites", "orl_dyn_get_elites", "orl_dyn_load_data", "orl_dyn_set_scaler", "orl_dyn_learn_epoch", "orl_dyn_validate",
     "orl_dyn_update_save", "orl_dyn_load_save", "orl_dyn_step", "orl_dyn_debug_grads",
+    # RAMBO's adversarial update on an orl_dynamics
+    "orl_dynadv_configure", "orl_dynadv_forward", "orl_dynadv_update", "orl_dynadv_adam_get", "orl_dynadv_adam_set",
 ]
+ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
 
 
@@ -226,6 +229,11 @@ def _bind_dynamics(lib) -> None:
     lib.orl_dyn_load_save.argtypes = [P, C.c_int]
     lib.orl_dyn_step.argtypes = [P, VP, VP, I64, C.c_int, VP, VP, C.c_int, F, VP, VP, VP, VP, VP]
     lib.orl_dyn_debug_grads.argtypes = [P, C.c_int, VP, I64]
+    lib.orl_dynadv_configure.argtypes = [P, F, F, F, F, F, C.c_int32, C.c_int32]
+    lib.orl_dynadv_forward.argtypes = [P] + [VP] * 6 + [C.c_int, VP, VP, VP, VP, VP]
+    lib.orl_dynadv_update.argtypes = [P, VP, C.c_int, VP, VP]
+    lib.orl_dynadv_adam_get.argtypes = [P, C.c_int, VP, VP, I64, C.POINTER(C.c_int64)]
+    lib.orl_dynadv_adam_set.argtypes = [P, C.c_int, VP, VP, I64, I64]
 
 
 def split_bits() -> int:
@@ -845,3 +853,90 @@ class Dynamics:
         _check(self.lib.orl_dyn_step(self._h, obs.data_ptr(), act.data_ptr(), n, 1, None, None, DYN_PENALTY[mode], float(coef),
                                      nxt.data_ptr(), rew.data_ptr(), raw.data_ptr(), pen.data_ptr(), None), "orl_dyn_step")
         return nxt, rew, raw, pen
+
+    # ---- RAMBO's adversarial update (orl_dynadv_*) ----
+    def adv_configure(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, adv_weight: float = 0.0, rollout_rows: int = 256,
+                      sl_rows: int = 256):
+        _check(self.lib.orl_dynadv_configure(self._h, float(lr), float(betas[0]), float(betas[1]), float(eps), float(adv_weight),
+                                             int(rollout_rows), int(sl_rows)), "orl_dynadv_configure")
+        self.adv_rows = (int(rollout_rows), int(sl_rows))
+
+    def _adv_shapes(self):
+        R, (Ba, Bs) = self.n_runs, self.adv_rows
+        return [(R, Ba, self.od), (R, Ba, self.ad), (R, Bs, self.od), (R, Bs, self.ad), (R, Bs, self.od), (R, Bs)]
+
+    def adv_forward(self, obs, act, sl_obs, sl_act, sl_next_obs, sl_rew, noise=None, model_idx=None):
+        """host arrays with a leading run dimension (``adv_configure``'s row counts); noise [R][K][Ba][od+1] / model_idx [R][Ba]
+        teacher-force the draws (None: device Philox).  Returns (next_obs [R][Ba][od], reward [R][Ba], model_idx [R][Ba])."""
+        arrs = [_f32(a) for a in (obs, act, sl_obs, sl_act, sl_next_obs, sl_rew)]
+        arrs[5] = arrs[5].reshape(arrs[5].shape[0], -1)
+        for a, shp in zip(arrs, self._adv_shapes()):
+            if a.shape != shp:
+                raise ValueError(f"adv_forward: array of shape {a.shape}, expected {shp}")
+        R, Ba = self.n_runs, self.adv_rows[0]
+        nz = None if noise is None else _f32(noise)
+        if nz is not None and nz.shape != (R, self.K, Ba, self.D):
+            raise ValueError(f"adv_forward: noise of shape {nz.shape}, expected {(R, self.K, Ba, self.D)}")
+        mi = None if model_idx is None else np.ascontiguousarray(model_idx, dtype=np.int64)
+        if mi is not None and mi.shape != (R, Ba):
+            raise ValueError(f"adv_forward: model_idx of shape {mi.shape}, expected {(R, Ba)}")
+        nxt, rew, mo = np.empty((R, Ba, self.od), np.float32), np.empty((R, Ba), np.float32), np.empty((R, Ba), np.int32)
+        _check(self.lib.orl_dynadv_forward(self._h, *[a.ctypes.data for a in arrs], 0, None if nz is None else nz.ctypes.data,
+                                           None if mi is None else mi.ctypes.data, nxt.ctypes.data, rew.ctypes.data, mo.ctypes.data),
+               "orl_dynadv_forward")
+        return nxt, rew, mo
+
+    def adv_update(self, advantage, active=None) -> np.ndarray:
+        """advantage [R][Ba] host array; returns the [R][4] metric table (``ADV_METRICS``)"""
+        a = _f32(advantage).reshape(self.n_runs, -1)
+        if a.shape != (self.n_runs, self.adv_rows[0]):
+            raise ValueError(f"adv_update: advantage of shape {a.shape}, expected {(self.n_runs, self.adv_rows[0])}")
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        m = np.zeros((self.n_runs, 4), np.float32)
+        _check(self.lib.orl_dynadv_update(self._h, a.ctypes.data, 0, None if act is None else act.ctypes.data, m.ctypes.data),
+               "orl_dynadv_update")
+        return m
+
+    def _check_dev(self, what, t, shape):
+        import torch
+        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" or \
+                (t.device.index or 0) != self.cfg.device:
+            raise ValueError(f"{what}: expected a contiguous fp32 tensor of shape {tuple(shape)} on the engine's device, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+
+    def adv_forward_device(self, obs, act, sl_obs, sl_act, sl_next_obs, sl_rew):
+        """``adv_forward`` on torch tensors of the engine's device, draws from the device Philox stream; returns (next_obs, reward)"""
+        import torch
+        ts = (obs, act, sl_obs, sl_act, sl_next_obs, sl_rew)
+        for t, shp in zip(ts, self._adv_shapes()):
+            self._check_dev("adv_forward_device", t, shp)
+        R, Ba = self.n_runs, self.adv_rows[0]
+        nxt = torch.empty((R, Ba, self.od), dtype=torch.float32, device=obs.device)
+        rew = torch.empty((R, Ba), dtype=torch.float32, device=obs.device)
+        torch.cuda.current_stream(obs.device).synchronize()
+        _check(self.lib.orl_dynadv_forward(self._h, *[t.data_ptr() for t in ts], 1, None, None, nxt.data_ptr(), rew.data_ptr(), None),
+               "orl_dynadv_forward")
+        return nxt, rew
+
+    def adv_update_device(self, advantage, active=None) -> np.ndarray:
+        import torch
+        self._check_dev("adv_update_device", advantage, (self.n_runs, self.adv_rows[0]))
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        m = np.zeros((self.n_runs, 4), np.float32)
+        torch.cuda.current_stream(advantage.device).synchronize()
+        _check(self.lib.orl_dynadv_update(self._h, advantage.data_ptr(), 1, None if act is None else act.ctypes.data, m.ctypes.data),
+               "orl_dynadv_update")
+        return m
+
+    def adv_adam_state(self, run: int):
+        m, v, t = np.empty(self.P, np.float32), np.empty(self.P, np.float32), C.c_int64()
+        _check(self.lib.orl_dynadv_adam_get(self._h, run, m.ctypes.data, v.ctypes.data, self.P, C.byref(t)), "orl_dynadv_adam_get")
+        return self._unflat(m), self._unflat(v), t.value
+
+    def set_adv_adam_state(self, run: int, m: Dict, v: Dict, step: int):
+        fm, fv = np.zeros(self.P, np.float32), np.zeros(self.P, np.float32)
+        for name, off, shape in self.tensors:
+            if name in m:
+                fm[off:off + int(np.prod(shape))] = _f32(m[name]).ravel()
+                fv[off:off + int(np.prod(shape))] = _f32(v[name]).ravel()
+        _check(self.lib.orl_dynadv_adam_set(self._h, run, fm.ctypes.data, fv.ctypes.data, self.P, int(step)), "orl_dynadv_adam_set")

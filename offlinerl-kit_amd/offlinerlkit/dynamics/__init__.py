@@ -14,6 +14,9 @@ the reference's draws.
 Multi-run: ``set_engine_options(n_runs=R)`` trains R independent ensembles (runs) in the same launches.  Each run has its own holdout
 split, scaler, bootstrap indices, early-stopping counter and elites; ``train`` loops until every run has stopped.  The torch module
 shows the run chosen by ``select_run`` (run 0 by default).
+
+RAMBO's adversarial update (``bind_adversary``, ``adv_forward`` / ``adv_update`` and their ``_device`` forms; ``orl_dynadv_*``) trains
+the same parameters with a second optimizer whose Adam state is separate from ``optim``'s; ``save`` / ``load`` are unchanged.
 """
 from __future__ import annotations
 
@@ -66,6 +69,7 @@ class EnsembleDynamics(BaseDynamics):
         self._cur_run = 0
         self.scalers: List[StandardScaler] = [scaler]
         self._data_key = None
+        self._adv_key = None           # (lr, betas, eps, adv_weight, rollout rows, dataset rows) of the bound adversarial optimizer
 
     # ---- engine binding ----
     def set_engine_options(self, n_runs: int = 1, seed: Optional[int] = None) -> None:
@@ -89,7 +93,8 @@ class EnsembleDynamics(BaseDynamics):
             return
         carried = None
         if self._eng is not None:
-            carried = [(self._eng.get_params(r), self._eng.adam_state(r), self._eng.get_elites(r)) for r in range(self._n_runs)]
+            carried = [(self._eng.get_params(r), self._eng.adam_state(r), self._eng.get_elites(r),
+                        self._eng.adv_adam_state(r) if self._adv_key is not None else None) for r in range(self._n_runs)]
             self._unbind()
         dev = self._device()
         m = self.model
@@ -109,12 +114,16 @@ class EnsembleDynamics(BaseDynamics):
         self._shape = shape
         m.to(dev)
         m.device = dev
+        if self._adv_key is not None:      # the adversarial optimizer follows the parameters into the new engine
+            self._adv_configure(self._adv_key)
         for r in range(self._n_runs):
             if carried is not None:
-                params, (am, av, t), el = carried[r]
+                params, (am, av, t), el, adv = carried[r]
                 self._eng.set_params(r, params)
                 self._eng.set_adam_state(r, am, av, t)
                 self._eng.set_elites(r, el)
+                if adv is not None:
+                    self._eng.set_adv_adam_state(r, *adv)
                 continue
             src = dict(m.named_parameters()) if r == 0 else _fresh_model_params(m, self._seed + r)
             self._eng.set_params(r, {k: v.detach().cpu().numpy() for k, v in src.items() if k != "elites"})
@@ -263,6 +272,83 @@ class EnsembleDynamics(BaseDynamics):
         if self._penalty_coef:
             info["penalty"] = pen
         return nxt, (rew if self._penalty_coef else raw), info
+
+    # ---- RAMBO's adversarial update (rambo.py:129-207; orl_dynadv_* of the engine) ----
+    def _adv_configure(self, key) -> None:
+        lr, betas, eps, w, ba, bs = key
+        self._eng.adv_configure(lr, betas, eps, w, ba, bs)
+
+    def bind_adversary(self, optim: torch.optim.Optimizer, adv_weight: float, rollout_rows: int, sl_rows: int) -> None:
+        """bind ``dynamics_adv_optim`` (read for lr / betas / eps; its Adam state lives in the engine, separate from ``optim``'s), the
+        weight of the adversarial term and the row counts of a call.  Cheap when nothing changed; a changed row count re-sizes the
+        workspaces and keeps the optimizer state."""
+        self._bind(*(self._shape or (256, 0.01)))
+        if not isinstance(optim, torch.optim.Adam):
+            raise NotImplementedError("the adversarial dynamics optimizer must be torch.optim.Adam")
+        g = optim.param_groups[0]
+        if g.get("weight_decay", 0.0) or g.get("amsgrad", False):
+            raise NotImplementedError("Adam weight_decay / amsgrad of the adversarial dynamics optimizer are not supported")
+        key = (float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]), float(adv_weight), int(rollout_rows),
+               int(sl_rows))
+        if key != self._adv_key:
+            self._adv_configure(key)
+            self._adv_key = key
+
+    def _adv_ready(self) -> None:
+        if self._adv_key is None:
+            raise RuntimeError("bind_adversary(optim, adv_weight, rollout_rows, sl_rows) before the adversarial calls")
+        self._sync_torch()
+        self._push_elites_from_model()
+        for r in range(self._n_runs):
+            sc = self.scalers[r]
+            if sc.mu is None:
+                raise RuntimeError("the scaler is not fitted: train() or load() the dynamics first")
+            self._eng.set_scaler(r, sc.mu, sc.std)
+
+    def _adv_metrics(self, m: np.ndarray) -> Dict[str, float]:
+        return {k: float(v) for k, v in zip(_engine.ADV_METRICS, m[self._cur_run])}
+
+    @torch.no_grad()
+    def adv_forward(self, obs, act, sl_obs, sl_act, sl_next_obs, sl_rew, noise: Optional[np.ndarray] = None,
+                    model_idxs: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """first half of ``dynamics_step_and_forward`` on numpy arrays: (Ba, obs_dim) rollout rows and (Bs, ..) dataset rows (every
+        run sees them) -> (next_obs, reward (Ba,), model_idxs) of the selected run; the sample stays on the device for ``adv_update``.
+        ``noise`` (K, Ba, obs_dim + 1) / ``model_idxs`` (Ba,) teacher-force the draws."""
+        self._adv_ready()
+        R = self._n_runs
+        bc = lambda a: None if a is None else np.broadcast_to(np.asarray(a), (R,) + np.shape(a))
+        sl_rew = np.asarray(sl_rew, np.float32).reshape(-1)
+        nxt, rew, mi = self._eng.adv_forward(bc(obs), bc(act), bc(sl_obs), bc(sl_act), bc(sl_next_obs), bc(sl_rew), bc(noise), bc(model_idxs))
+        r = self._cur_run
+        return nxt[r], rew[r], mi[r]
+
+    @torch.no_grad()
+    def adv_update(self, advantage, active=None) -> Dict[str, float]:
+        """second half on a numpy advantage (Ba,), already normalised: the adversarial Adam step; returns ``all_loss``, ``sl_loss``,
+        ``adv_loss`` (unweighted) and ``adv_log_prob`` of the selected run"""
+        a = np.asarray(advantage, np.float32).reshape(-1)
+        return self._adv_metrics(self._eng.adv_update(np.broadcast_to(a, (self._n_runs,) + a.shape), active))
+
+    @torch.no_grad()
+    def adv_forward_device(self, obs, act, sl_obs, sl_act, sl_next_obs, sl_rew) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``adv_forward`` on tensors (moved to the engine's device if they are elsewhere), draws from the device Philox stream; returns
+        device tensors (next_obs (Ba, obs_dim), reward (Ba,))"""
+        self._adv_ready()
+        dev, R = self._arena.device, self._n_runs
+
+        def prep(x, cols):
+            t = torch.as_tensor(x, dtype=torch.float32, device=dev).reshape(-1, cols) if cols else \
+                torch.as_tensor(x, dtype=torch.float32, device=dev).reshape(-1)
+            return t.unsqueeze(0).expand(R, *t.shape).contiguous()
+        od, ad = self.model.obs_dim, self.model.action_dim
+        nxt, rew = self._eng.adv_forward_device(prep(obs, od), prep(act, ad), prep(sl_obs, od), prep(sl_act, ad), prep(sl_next_obs, od),
+                                                prep(sl_rew, 0))
+        return nxt[self._cur_run], rew[self._cur_run]
+
+    @torch.no_grad()
+    def adv_update_device(self, advantage: torch.Tensor, active=None) -> Dict[str, float]:
+        a = torch.as_tensor(advantage, dtype=torch.float32, device=self._arena.device).reshape(-1)
+        return self._adv_metrics(self._eng.adv_update_device(a.unsqueeze(0).expand(self._n_runs, -1).contiguous(), active))
 
     def sample_next_obss(self, obs, action, num_samples: int):
         raise NotImplementedError("sample_next_obss is used by MOBILE only, which this package does not implement")

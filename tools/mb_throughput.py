@@ -10,7 +10,13 @@ row is that of a trained one).  Prints one JSON object; --out writes it too.  Ne
 --runs R measures, instead, R independent seeds in the same invocation and alternating the same way: ONE R-run policy with per-run model
 rings (a list of R model buffers: every run rolls its own actor through its own run of an R-run dynamics into its own ring) against the
 baseline of R single-run fused trainings run one after the other, each with its own policy, dynamics and ring.  The figure is aggregate
-run-steps per second: R x block steps / seconds of the block, rollouts included."""
+run-steps per second: R x block steps / seconds of the block, rollouts included.
+
+--rambo measures, instead, RAMBO's adversarial model update at run_rambo.py's shape (dynamics [200] x 4, 7 members, 5 elites, policy
+[256, 256], 256 rollout + 256 dataset rows per step, adv_rollout_length 5, adv_weight 3e-4, 1000 steps per update):
+``RAMBOPolicy.update_dynamics`` on the engine against a stock-torch restatement of the same update (the reference's
+``dynamics_step_and_forward`` with torch autograd and torch.optim.Adam on the same GPU, same buffer draws, actor and critics), a warm-up
+of each and then alternating timed updates.  The figure is model-update steps per second."""
 import argparse
 import json
 import os
@@ -26,7 +32,7 @@ from offlinerlkit.buffer import ReplayBuffer  # noqa: E402
 from offlinerlkit.dynamics import EnsembleDynamics  # noqa: E402
 from offlinerlkit.modules import ActorProb, Critic, EnsembleDynamicsModel, TanhDiagGaussian  # noqa: E402
 from offlinerlkit.nets import MLP  # noqa: E402
-from offlinerlkit.policy import COMBOPolicy, MOPOPolicy  # noqa: E402
+from offlinerlkit.policy import COMBOPolicy, MOPOPolicy, RAMBOPolicy  # noqa: E402
 from offlinerlkit.policy_trainer import MBPolicyTrainer  # noqa: E402
 from offlinerlkit.utils.scaler import StandardScaler  # noqa: E402
 from offlinerlkit.utils.termination_fns import termination_fn_halfcheetah  # noqa: E402
@@ -183,6 +189,95 @@ def measure(algo, ds, blocks, block_steps, profile_only=False):
                 model_rows={name: trainers[name].fake_buffer._size for name in trainers})
 
 
+def torch_update_dynamics(pol, model, optim, mu, std, real, steps, rows, length, adv_weight, gamma):
+    """rambo.py:95-207 in stock torch on the GPU: the loop of ``update_dynamics`` around an autograd ``dynamics_step_and_forward``"""
+    done, info = 0, {}
+    elites = model.elites.data
+    while done < steps:
+        obs = real.sample(rows)["observations"]
+        for _ in range(length):
+            with torch.no_grad():
+                act, _ = pol.actforward(obs, False)
+            b = real.sample(rows)
+            x = (torch.cat([obs, act], -1) - mu) / std
+            diff_mean, logvar = model(x)
+            mean = torch.cat([diff_mean[..., :-1] + obs, diff_mean[..., -1:]], -1)
+            dist = torch.distributions.Normal(mean, torch.sqrt(torch.exp(logvar)))
+            ens = dist.sample()
+            idx = torch.as_tensor(model.random_elite_idxs(rows), device=obs.device)
+            sample = ens[idx, torch.arange(rows, device=obs.device)]
+            nxt, rew = sample[..., :-1], sample[..., -1:]
+            term = torch.as_tensor(termination_fn_halfcheetah(obs.cpu().numpy(), act.cpu().numpy(), nxt.cpu().numpy()), device=obs.device)
+            lp = dist.log_prob(sample).sum(-1, keepdim=True)[elites]
+            log_prob = (lp.double().exp() * (1 / len(elites))).sum(0).log().float()
+            with torch.no_grad():
+                na, _ = pol.actforward(nxt, True)
+                next_q = torch.minimum(pol.critic1(nxt, na), pol.critic2(nxt, na))
+                value = rew + (1 - term.float()) * gamma * next_q
+                adv = value - torch.minimum(pol.critic1(obs, act), pol.critic2(obs, act))
+                adv = (adv - adv.mean()) / (adv.std() + 1e-6)
+            adv_loss = (log_prob * adv).mean()
+            sx = (torch.cat([b["observations"], b["actions"]], -1) - mu) / std
+            target = torch.cat([b["next_observations"] - b["observations"], b["rewards"]], -1)
+            sm, slv = model(sx)
+            sl = (torch.pow(sm - target, 2) * torch.exp(-slv)).mean(dim=(1, 2)).sum() + slv.mean(dim=(1, 2)).sum()
+            sl = sl + model.get_decay_loss() + 0.001 * model.max_logvar.sum() - 0.001 * model.min_logvar.sum()
+            loss = adv_weight * adv_loss + sl
+            optim.zero_grad()
+            loss.backward()
+            optim.step()
+            info = {"all_loss": loss.item(), "sl_loss": sl.item(), "adv_loss": adv_loss.item(), "adv_log_prob": log_prob.mean().item()}
+            done += 1
+            obs = nxt.detach()
+            if done == 1000:
+                break
+    return info
+
+
+def measure_rambo(ds, blocks, steps):
+    rows, length, w, gamma = 256, 5, 3e-4, 0.99
+    real = ReplayBuffer(len(ds["rewards"]), (OD,), np.float32, AD, np.float32, device=DEV)
+    real.load_dataset(ds)
+    torch.manual_seed(1)
+    adam = lambda m, lr: torch.optim.Adam(m.parameters(), lr=lr)
+    mk_model = lambda: EnsembleDynamicsModel(OD, AD, DYN_HID, num_ensemble=K, num_elites=E, weight_decays=DECAYS, device=DEV)
+    model, tmodel = mk_model(), mk_model()
+    tmodel.load_state_dict(model.state_dict())
+    scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
+    dyn = EnsembleDynamics(model, adam(model, 3e-4), scaler, termination_fn_halfcheetah)
+    actor = ActorProb(MLP(OD, [256, 256]), TanhDiagGaussian(256, AD, unbounded=True, conditioned_sigma=True), DEV)
+    c1, c2 = Critic(MLP(OD + AD, [256, 256]), DEV), Critic(MLP(OD + AD, [256, 256]), DEV)
+    pol = RAMBOPolicy(dyn, actor, c1, c2, adam(actor, 1e-4), adam(c1, 3e-4), adam(c2, 3e-4), adam(model, 3e-4), tau=0.005, gamma=gamma,
+                      alpha=0.2, adv_weight=w, adv_train_steps=steps, adv_rollout_batch_size=rows, adv_rollout_length=length, device=DEV)
+    topt = adam(tmodel, 3e-4)
+    mu, std = torch.zeros(OD + AD, device=DEV), torch.ones(OD + AD, device=DEV)
+    last = {}
+
+    def block(name, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if name == "engine":
+            pol._adv_train_steps = n
+            last[name] = pol.update_dynamics(real)
+        else:
+            last[name] = torch_update_dynamics(pol, tmodel, topt, mu, std, real, n, rows, length, w, gamma)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    names = ("torch", "engine")
+    np.random.seed(0)
+    torch.manual_seed(0)
+    warm = {name: block(name, 100) for name in names}
+    secs = {name: [] for name in names}
+    for _ in range(blocks):
+        for name in names:
+            secs[name].append(block(name, steps))
+    sps = {name: [steps / x for x in v] for name, v in secs.items()}
+    return dict(mode="rambo_update_dynamics", steps=steps, rows=[rows, rows], rollout_length=length, adv_weight=w,
+                warmup_seconds_100_steps=warm, seconds=secs, steps_per_s=sps, steps_per_s_mean={k: float(np.mean(v)) for k, v in sps.items()},
+                speedup=float(np.mean(sps["engine"]) / np.mean(sps["torch"])),
+                last_losses={k: {a: float(b) for a, b in v.items()} for k, v in last.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=3)
@@ -191,9 +286,21 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--runs", type=int, default=0, help="R > 1: per-run model rings at R runs against R sequential single-run fused trainings")
     ap.add_argument("--profile-block", action="store_true", help="a warm-up and one fused MOPO block only (for a kernel trace)")
+    ap.add_argument("--rambo", action="store_true", help="RAMBO's update_dynamics (engine) against its stock-torch restatement")
+    ap.add_argument("--rambo-steps", type=int, default=1000)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mb_throughput: no HIP device visible (the loops under test run on the GPU)")
+    if a.rambo:
+        res = {"shape": dict(obs=OD, act=AD, dynamics_hidden=DYN_HID, members=K, elites=E, policy_hidden=[256, 256]),
+               "device": torch.cuda.get_device_name(0), "results": [measure_rambo(dataset(200_000), a.blocks, a.rambo_steps)]}
+        s = json.dumps(res, indent=1)
+        print(s)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(s + "\n")
+        return
     ds = dataset(DATA_ROWS)
     if a.profile_block:
         print(json.dumps(measure("mopo", ds, 1, a.block_steps, profile_only=True)))
