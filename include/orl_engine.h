@@ -59,6 +59,7 @@ extern "C" {
 #define ORL_ALGO_EDAC 3  /* policy/model_free/edac.py:88-166  */
 #define ORL_ALGO_SAC 4   /* policy/model_free/sac.py:88-140 (MOPOPolicy.learn on the real+model batch, model_based/mopo.py:81-84) */
 #define ORL_ALGO_MCQ 5   /* policy/model_free/mcq.py:48-126 (SAC critics / actor + the VAE behaviour policy of nets/vae.py) */
+#define ORL_ALGO_MOBILE 6 /* policy/model_based/mobile.py:130-196 (SAC schedule + the model-Bellman-inconsistency penalty; needs orl_engine_set_next_samples) */
 
 /* per-run health flags (orl_health).  The reference raises nothing when a run diverges (its losses simply turn nan); here a diverging run
  * can additionally be MASKED by the arithmetic -- the ReLU of the matrix kernels works on the integer view of the activations and maps a NaN
@@ -158,6 +159,11 @@ typedef struct orl_config {
    * floats) so that framework tensors can alias engine parameters; NULL = the
    * engine allocates with hipMalloc. */
   float* external_arena;
+  /* MOBILE (policy/model_based/mobile.py:19-57, 130-162): num_samples S and the dynamics' elite count E (the penalty pass runs on
+   * S * E * batch_size rows), the number of leading batch rows that are real data (their penalty is zeroed, mobile.py:154) and the
+   * penalty coefficient; deterministic_backup is CQL's field */
+  int32_t mobile_num_samples, mobile_num_elites, mobile_real_rows;
+  float penalty_coef;
 } orl_config;
 
 /* Replay minibatch: the dict ReplayBuffer.sample returns (buffer.py:96-106).
@@ -177,6 +183,7 @@ typedef struct orl_batch {
  * EDAC: [0] eps_actor, [1] eps_next.  TD3BC: [0] eps_target (B,A).  IQL: none.  SAC: [0] eps_next, [1] eps_actor (B,A).
  * MCQ: [0] eps_vae (B,Z), [1] eps_next (B,A), [2] z_ood (2B*N,Z) N(0,1) (clamped to +-0.5 by the engine like VAE.decode), [3] eps_ood (2B,A),
  * [4] eps_actor (B,A).
+ * MOBILE: [0] eps_lcb (S*E*B,A), [1] eps_next (B,A), [2] eps_actor (B,A).
  * Each array has a leading n_runs dimension. */
 typedef struct orl_noise {
   const float* slot[ORL_MAX_NOISE];
@@ -288,6 +295,17 @@ int orl_step(orl_engine* e, const orl_batch* batch, const orl_noise* noise, floa
  * sampling and noise on device; metrics_mean: host [n_runs][ORL_MAX_METRICS] epoch means;
  * elapsed_ms (optional): HIP-event time of the n steps on the engine stream. */
 int orl_learn_n(orl_engine* e, int n_steps, float* metrics_mean, float* elapsed_ms);
+/* MOBILE: the next-state samples of the batch the NEXT orl_step learns, [n_runs][S * E * batch][obs_dim] in the row order of
+ * orl_dynsample_next (row (s * E + e) * batch + b).  A device pointer (on_device) is borrowed until that step has run -- nothing is
+ * copied, the producer must have finished writing (orl_dynsample_next synchronises its stream) --; a host pointer is copied in.  One
+ * orl_step (or one orl_engine_lcb_penalty) consumes the samples; orl_step on a MOBILE engine without pending samples fails before it
+ * launches anything, and orl_learn_n fails on a MOBILE engine (the dynamics forward is not on the engine's stream). */
+int orl_engine_set_next_samples(orl_engine* e, const float* samples, int on_device);
+/* MOBILE's compute_lcb (mobile.py:130-142) alone: the penalty pass of orl_step on the pending samples, WITHOUT the zeroing of the real
+ * rows and without touching parameters, optimizer state or the step counter.  eps_lcb [n_runs][S * E * batch][act_dim] teacher-forces
+ * the actor's draws (NULL: device Philox); penalty_out [n_runs][batch]; both are device pointers when on_device.  The "penalty" and
+ * "lcb_q" taps hold the result afterwards. */
+int orl_engine_lcb_penalty(orl_engine* e, const float* eps_lcb, float* penalty_out, int on_device);
 /* Sticky per-run health flags (ORL_HEALTH_* bits), flags_out: host uint32[n_runs] (may be NULL); returns the OR over the runs, < 0 on
  * error.  orl_step / orl_learn_n update the flags from what they already read back (metrics; one word per run that k_adam raises on a
  * non-finite gradient) and, at precision 1, scan the step's MFMA operands for the fp16-plane range when a run turned non-finite.
@@ -388,6 +406,16 @@ int orl_dyn_load_save(orl_dynamics* d, int run);
 int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n, int on_device, const float* noise,
                  const int64_t* model_idx, int penalty_mode, float penalty_coef, float* next_obs, float* reward, float* raw_reward,
                  float* penalty, int32_t* model_idx_out);
+/* sample_next_obss (:82-99) for MOBILE: one shared-input ensemble forward on the n rows, then for each of num_samples samples and each
+ * ELITE (in orl_dyn_set_elites order) mean + eps * std with mean[..., :obs_dim] += obs, in fp32 with the two roundings of
+ * randn_like(std) * std + mean.  next_obs [n_runs][num_samples * E * n][obs_dim], row (s * E + e) * n + b: the reference's
+ * reshape(-1, obs_dim).  noise [n_runs][num_samples][E][n][obs_dim + with_reward] teacher-forces the draws (the reward column is drawn
+ * and dropped); NULL = a device Philox stream of this entry point alone, keyed by (seed, its own call counter, run, sample, elite
+ * position, row, dim): orl_dyn_step and orl_dynadv_forward draw what they draw without this call.  Pointers are device pointers when
+ * on_device (then nothing visits the host); the call ends with a stream synchronisation.  Refused: num_samples < 1, fewer than 2
+ * elites, runs with different elite counts.  (Named orl_dynsample_*, not orl_dyn_*, like orl_dynadv_*.) */
+int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int64_t n, int32_t num_samples, int on_device,
+                       const float* noise, float* next_obs);
 /* test tap: parameter gradient of the LAST minibatch of the last orl_dyn_learn_epoch, or of the last orl_dynadv_update, whichever
  * ran later (flat like orl_dyn_get; decay terms excluded) */
 int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n_floats);

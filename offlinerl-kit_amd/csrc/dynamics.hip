@@ -344,6 +344,55 @@ __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
   if (p.midx_out) p.midx_out[(long)r * p.n + i] = mi;
 }
 
+// ---- MOBILE's next-state samples (reference: dynamics/ensemble_dynamics.py:82-99): orl_dynsample_next ----
+struct DynSampleNextP {
+  const float* OUT; int op;
+  const float* obs; long n; int od, D, K, S, E;
+  const float* params; long P, off_max, off_min;
+  const float* noise;                 // [R][S][E][n][D] or null
+  const int* elites;                  // [R][K], the first E entries in set_elites order
+  uint64_t seed; uint64_t call;
+  float* next_obs;                    // [R][S * E * n][od], row (s * E + e) * n + b
+};
+
+// one thread per (run, sample s, elite position e, row b, four output dims): mean_m + eps std_m of elite m = elites[e] in fp32 with
+// two roundings (randn_like(std) * std, then + mean); the reward column is drawn like the others and dropped
+__global__ __launch_bounds__(256) void k_dyn_sample_next(DynSampleNextP p) {
+  const int nq = (p.D + 3) >> 2;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  const long rows = (long)p.S * p.E * p.n;
+  if (t >= rows * nq) return;
+  const long row = t / nq;
+  const int q = (int)(t - row * nq);
+  const long se = row / p.n, b = row - se * p.n;
+  const int e = (int)(se % p.E);
+  const int D = p.D, od = p.od, K = p.K;
+  const int mi = p.elites[r * K + e];
+  const float* mx = p.params + r * p.P + p.off_max;
+  const float* mn = p.params + r * p.P + p.off_min;
+  uint32_t rnd[4];
+  if (!p.noise) dyn_philox(p.seed, (uint32_t)b, (uint32_t)se, (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)q, rnd);
+  const float* out = p.OUT + (((long)r * K + mi) * p.n + b) * p.op;
+  const float* obs = p.obs + ((long)r * p.n + b) * od;
+  float* dst = p.next_obs + ((long)r * rows + row) * od;
+  for (int j = 0; j < 4 && 4 * q + j < od; ++j) {
+    const int d = 4 * q + j;
+    float eps;
+    if (p.noise) eps = p.noise[((long)r * rows + row) * D + d];
+    else {
+      const float u1 = dyn_u01(rnd[j & ~1]), u2 = dyn_u01(rnd[j | 1]);
+      const float rad = sqrtf(-2.0f * logf(u1)), th = 6.28318530717958647692f * u2;
+      eps = (j & 1) ? rad * sinf(th) : rad * cosf(th);
+    }
+    const float mean = out[d] + obs[d];
+    const float x = out[D + d];
+    const float l1 = mx[d] - dyn_softplus(mx[d] - x);
+    const float lv = mn[d] + dyn_softplus(l1 - mn[d]);
+    dst[d] = __fadd_rn(mean, __fmul_rn(eps, sqrtf(expf(lv))));
+  }
+}
+
 // ---- RAMBO's adversarial model update (reference: policy/model_based/rambo.py:129-207): orl_dynadv_* ----
 // One update is two calls with the caller's advantage between them:
 //   forward   k_dyn_adv_input (scale + concatenate the Ba rollout rows and the Bs dataset rows into ONE input shared by the members,
@@ -657,6 +706,10 @@ struct orl_dynamics {
   float *sNext = nullptr, *sRew = nullptr, *sRaw = nullptr, *sPen = nullptr;
   int *sIdx = nullptr, *sMidx = nullptr, *sMidxOut = nullptr;
   uint64_t step_calls = 0;
+  // MOBILE's samples (orl_dynsample_next): its own call counter, host-noise staging and host-output staging, grown on demand
+  uint64_t sample_calls = 0;
+  long m_cap = 0;
+  float *mNoise = nullptr, *mNext = nullptr;
   // RAMBO's adversarial update (orl_dynadv_*): its own optimizer state, workspaces over Ba + Bs rows and the kept sample
   bool adv_on = false, adv_pending = false;
   int aBa = 0, aBs = 0;
@@ -1243,6 +1296,58 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
     DYN_HIP(hipMemcpyAsync(penalty, d->sPen, sizeof(float) * R * n, hipMemcpyDeviceToHost, d->stream));
     if (midx_out) DYN_HIP(hipMemcpyAsync(midx_out, d->sMidxOut, sizeof(int) * R * n, hipMemcpyDeviceToHost, d->stream));
   }
+  DYN_HIP(hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+// ---- MOBILE's next-state samples ----
+int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int64_t n, int32_t num_samples, int on_device,
+                       const float* noise, float* next_obs) {
+  if (!d || !obs || !act || n < 1 || !next_obs) return fail("orl_dynsample_next: bad arguments");
+  if (num_samples < 1) return fail("orl_dynsample_next: num_samples must be >= 1");
+  const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
+  const int E = (int)d->elites_h[0].size();
+  for (int r = 1; r < R; ++r)
+    if ((int)d->elites_h[r].size() != E) return fail("orl_dynsample_next: every run needs the same number of elites");
+  if (E < 2) return fail("orl_dynsample_next: needs at least 2 elites (the standard deviation over one elite is NaN)");
+  const long S = num_samples, rows = S * E * n;
+  if (rows * ((D + 3) / 4) > (1L << 38) || n > 0x7fffffffL) return fail("orl_dynsample_next: too many rows");
+  if (dyn_grow_step(d, n)) return -1;
+  if (!on_device && rows > d->m_cap) {
+    DYN_HIP(hipStreamSynchronize(d->stream));
+    dyn_free(d, d->mNoise); dyn_free(d, d->mNext);
+    d->mNoise = d->mNext = nullptr; d->m_cap = 0;
+    if (dyn_alloc_t(d, &d->mNoise, (size_t)R * rows * D) || dyn_alloc_t(d, &d->mNext, (size_t)R * rows * od)) return -1;
+    d->m_cap = rows;
+  }
+  const float* obs_d = obs;
+  const float* act_d = act;
+  const float* noise_d = noise;
+  if (!on_device) {
+    DYN_HIP(hipMemcpyAsync(d->sObs, obs, sizeof(float) * R * n * od, hipMemcpyHostToDevice, d->stream));
+    DYN_HIP(hipMemcpyAsync(d->sAct, act, sizeof(float) * R * n * ad, hipMemcpyHostToDevice, d->stream));
+    obs_d = d->sObs; act_d = d->sAct;
+    if (noise) {
+      DYN_HIP(hipMemcpyAsync(d->mNoise, noise, sizeof(float) * R * rows * D, hipMemcpyHostToDevice, d->stream));
+      noise_d = d->mNoise;
+    }
+  }
+  hipLaunchKernelGGL(k_dyn_step_input, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, d->stream, obs_d, act_d, (long)n, od, ad,
+                     (const float*)d->mu, (const float*)d->sd, d->sX, d->pitch[0]);
+  DYN_LAUNCHED("k_dyn_step_input");
+  if (dyn_forward_shared(d, n)) return -1;
+  DynSampleNextP p;
+  memset(&p, 0, sizeof(p));
+  p.OUT = d->sOUT; p.op = d->pitch[d->L + 1];
+  p.obs = obs_d; p.n = n; p.od = od; p.D = D; p.K = K; p.S = (int)S; p.E = E;
+  p.params = d->params; p.P = d->P; p.off_max = d->off_max; p.off_min = d->off_min;
+  p.noise = noise_d; p.elites = d->elites_d;
+  p.seed = d->c.seed ^ 0xD1B54A32D192ED03ull; p.call = d->sample_calls++;
+  p.next_obs = on_device ? next_obs : d->mNext;
+  const long nt = rows * ((D + 3) / 4);
+  hipLaunchKernelGGL(k_dyn_sample_next, dim3((unsigned)((nt + 255) / 256), R), dim3(256), 0, d->stream, p);
+  DYN_LAUNCHED("k_dyn_sample_next");
+  if (!on_device) DYN_HIP(hipMemcpyAsync(next_obs, d->mNext, sizeof(float) * R * rows * od, hipMemcpyDeviceToHost, d->stream));
   DYN_HIP(hipStreamSynchronize(d->stream));
   return 0;
 }

@@ -166,6 +166,8 @@ struct Engine {
   std::vector<unsigned long long> mbufs_gen;
   ModelSrc* m_tab = nullptr;   // [R], device
   int upload_model_table();
+  // MOBILE: the next-state samples the next step consumes (orl_engine_set_next_samples): a borrowed device pointer or the engine's own copy
+  const float* mobile_samples = nullptr; long mobile_samples_rs = 0; bool mobile_pending = false;
   void drop_graphs();
   // split-K slab table of the last adam() launch per net (orl_debug_grads sums the slabs the way k_adam does)
   std::vector<std::pair<long, int>> last_segs[ORL_NUM_NETS];
@@ -331,6 +333,7 @@ struct Engine {
   int edac_build(); int edac_step();
   int sac_build(); int sac_step();
   int mcq_build(); int mcq_step();
+  int mobile_build(); int mobile_step(); int mobile_penalty(int real_rows);
 };
 
 }  // namespace orl

@@ -153,7 +153,7 @@ static int build_layouts(const orl_config& c, NetLayout* lay, long* net_off, boo
   long o = 0, t = 0;
   auto train = [&](int id, const NetLayout& l) { lay[id] = l; net_off[id] = o; o += l.stride(); };
   auto target = [&](int id, const NetLayout& l) { lay[id] = l; net_off[id] = t; is_tgt[id] = true; t += l.stride(); };
-  if (c.algo == ORL_ALGO_CQL || c.algo == ORL_ALGO_SAC || c.algo == ORL_ALGO_MCQ) {
+  if (c.algo == ORL_ALGO_CQL || c.algo == ORL_ALGO_SAC || c.algo == ORL_ALGO_MCQ || c.algo == ORL_ALGO_MOBILE) {
     train(ORL_NET_ACTOR, make_mlp_layout(od, c.hidden, L, TAIL_TANH_GAUSS, ad));
     train(ORL_NET_CRITIC1, crit); train(ORL_NET_CRITIC2, crit);
     target(ORL_NET_CRITIC1_OLD, crit); target(ORL_NET_CRITIC2_OLD, crit);
@@ -1098,6 +1098,7 @@ static SampleJob make_job(int head_row0, int rows, int rep, const Mat& eps, cons
 #include "algo_edac.inc"
 #include "algo_sac.inc"
 #include "algo_mcq.inc"
+#include "algo_mobile.inc"
 
 namespace orl {
 
@@ -1189,6 +1190,8 @@ int Engine::init(const orl_config& c) {
   read_env();
   R = c.n_runs; B = c.batch_size; od = c.obs_dim; ad = c.act_dim;
   N = c.num_repeat_actions > 0 ? c.num_repeat_actions : 1;
+  // MOBILE: the longest row batch is the penalty pass's S * E * B rows; N sizes the tail scratch of build_common for it (9 B N >= 3 S E B)
+  if (c.algo == ORL_ALGO_MOBILE) N = std::max(1, (std::max(c.mobile_num_samples, 1) * std::max(c.mobile_num_elites, 1) + 2) / 3);
   OP = rup(od, 4); AP = rup(ad, 4); XP = rup(od + ad, 4); L = c.n_hidden;
   K = (c.algo == ORL_ALGO_EDAC) ? c.num_critics : 2;
   const long arena_floats = (long)R * (P_train + P_tgt);
@@ -1239,6 +1242,7 @@ int Engine::init(const orl_config& c) {
     case ORL_ALGO_EDAC: rc = edac_build(); break;
     case ORL_ALGO_SAC: rc = sac_build(); break;
     case ORL_ALGO_MCQ: rc = mcq_build(); break;
+    case ORL_ALGO_MOBILE: rc = mobile_build(); break;
   }
   if (rc) return rc;
   { Mat lc; lc.p = (float*)lab_clk(0); lc.pitch = 192; taps["lab_clk"] = {lc, 1, 192}; }      // shader-clock stamps of lab builds (small_bwd.hip)
@@ -1364,6 +1368,7 @@ int Engine::enqueue_step(int variant) {
     case ORL_ALGO_EDAC: rc = edac_step(); break;
     case ORL_ALGO_SAC: rc = sac_step(); break;
     case ORL_ALGO_MCQ: rc = mcq_step(); break;
+    case ORL_ALGO_MOBILE: rc = mobile_step(); break;
   }
   if (rc) return rc;
   if (tick_folded) return 0;               // the step's own kernels advanced the counter
@@ -1389,9 +1394,9 @@ extern "C" {
 
 const char* orl_last_error(void) { return g_err.c_str(); }
 #ifdef ORL_SPLIT_BF16
-const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-bf16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ)"; }
+const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-bf16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE)"; }
 #else
-const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-fp16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ)"; }
+const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-fp16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE)"; }
 #endif
 int orl_split_bits(void) { return ORL_SPLIT_BITS; }
 
@@ -1414,6 +1419,8 @@ void orl_config_default(orl_config* c, int32_t algo) {
   if (algo == ORL_ALGO_EDAC) { c->n_hidden = 3; c->hidden[2] = 256; c->deterministic_backup = 0; }
   if (algo == ORL_ALGO_SAC) { c->actor_lr = 1e-4f; c->critic_lr = 3e-4f; c->deterministic_backup = 0; }   /* run_mopo.py:33-34 */
   c->vae_hidden = 750; c->vae_latent = 2 * c->act_dim; c->mcq_lambda = 0.9f; c->behavior_lr = 1e-3f;   /* run_mcq.py:34-36, 93-99 */
+  c->mobile_num_samples = 10; c->mobile_num_elites = 5; c->mobile_real_rows = 12; c->penalty_coef = 1.5f;   /* run_mobile.py:45-52: int(256 * 0.05) real rows */
+  if (algo == ORL_ALGO_MOBILE) { c->deterministic_backup = 1; }                                             /* run_mobile.py:157 */
   if (algo == ORL_ALGO_MCQ) { c->hidden[0] = c->hidden[1] = 400; c->actor_lr = c->critic_lr = c->alpha_lr = 3e-4f; c->target_entropy = -(float)c->act_dim; }
 }
 
@@ -1937,6 +1944,8 @@ int orl_step(orl_engine* h, const orl_batch* b, const orl_noise* nz, float* metr
   Engine& e = h->e;
   ORL_HIP(hipSetDevice(e.dev));
   const int B = e.B;
+  if (e.cfg.algo == ORL_ALGO_MOBILE && !e.mobile_pending)
+    return fail("orl_step: a MOBILE engine needs the next-state samples of this batch first (orl_engine_set_next_samples; one step per call)");
   if (b) {
     const bool dv = b->on_device != 0;
     if (copy_rows(e, e.W("b_obs2"), b->observations, B, e.od, dv, 0)) return -1;
@@ -1952,9 +1961,11 @@ int orl_step(orl_engine* h, const orl_batch* b, const orl_noise* nz, float* metr
   }
   if (!e.prep.empty()) { if (e.enqueue_prepare(false, nz == nullptr)) return -1; }
   else if (!nz) { if (e.enqueue_noise()) return -1; }
+  e.mobile_pending = false;      // (consumed, also by a step that fails below: the borrowed pointer is not kept)
   if (e.enqueue_step(e.step_variant())) return -1;
   e.step_host++;
   ORL_HIP(hipStreamSynchronize(e.stream));
+  e.mobile_samples = nullptr;
   std::vector<float> m(e.R * e.nm);
   ORL_HIP(hipMemcpy(m.data(), e.metrics_last, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
   if (metrics) {
@@ -1970,6 +1981,9 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
   Engine& e = h->e;
   ORL_HIP(hipSetDevice(e.dev));
   if (n_steps <= 0) return fail("n_steps must be positive");
+  if (e.cfg.algo == ORL_ALGO_MOBILE)
+    return fail("orl_learn_n: not available for MOBILE engines (every step needs the dynamics' next-state samples of its batch: "
+                "orl_dynsample_next, orl_engine_set_next_samples, orl_step)");
   if (!e.buf || !e.buf->obs || e.buf->n < 1) return fail("orl_learn_n: no replay buffer attached");
   for (size_t r = 0; r < e.mbufs.size(); ++r)
     if (!e.mbufs[r]->obs || e.mbufs[r]->n < 1) {
@@ -2040,6 +2054,50 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
   unsigned int bad = 0;
   if (e.health_update(m.data(), n_steps, &bad)) return -1;
   return bad ? ORL_RC_UNHEALTHY : 0;
+}
+
+int orl_engine_set_next_samples(orl_engine* h, const float* samples, int on_device) {
+  Engine& e = h->e;
+  if (e.cfg.algo != ORL_ALGO_MOBILE) return fail("orl_engine_set_next_samples: not a MOBILE engine");
+  if (!samples) return fail("orl_engine_set_next_samples: null samples");
+  ORL_HIP(hipSetDevice(e.dev));
+  const int M = e.cfg.mobile_num_samples * e.cfg.mobile_num_elites * e.B;
+  if (on_device) { e.mobile_samples = samples; e.mobile_samples_rs = (long)M * e.od; }
+  else {
+    const Mat& in = e.W("samples_in");
+    if (copy_rows(e, in, samples, M, e.od, false)) return -1;
+    e.mobile_samples = in.p; e.mobile_samples_rs = in.rs;
+  }
+  e.mobile_pending = true;
+  return 0;
+}
+
+int orl_engine_lcb_penalty(orl_engine* h, const float* eps_lcb, float* penalty_out, int on_device) {
+  Engine& e = h->e;
+  if (e.cfg.algo != ORL_ALGO_MOBILE) return fail("orl_engine_lcb_penalty: not a MOBILE engine");
+  if (!penalty_out) return fail("orl_engine_lcb_penalty: null output");
+  if (!e.mobile_pending) return fail("orl_engine_lcb_penalty: no pending samples (orl_engine_set_next_samples first)");
+  ORL_HIP(hipSetDevice(e.dev));
+  const int M = e.cfg.mobile_num_samples * e.cfg.mobile_num_elites * e.B;
+  const Mat& eps = e.W("n_eps_lcb");
+  if (eps_lcb) { if (copy_rows(e, eps, eps_lcb, M, e.ad, on_device != 0)) return -1; }
+  else {
+    // the draws of noise slot 0 at the current step counter (the next orl_step draws the same ones: the counter does not move here)
+    const long n = e.ws_len.at("n_eps_lcb");
+    hipLaunchKernelGGL(k_noise, dim3((unsigned)((n / 4 + 256) / 256), e.R), dim3(256), 0, e.stream, eps.p, n, 0, e.cfg.act_low, e.cfg.act_high,
+                       e.cfg.seed, (const unsigned long long*)e.gstep, 1u);
+    if (hipGetLastError() != hipSuccess) return fail("orl_engine_lcb_penalty: noise launch failed");
+  }
+  e.mobile_pending = false;
+  e.gscale_next = 0; e.cur_gscale = nullptr; e.lab_slot = 0;
+  if (e.mobile_penalty(0)) return -1;
+  const Mat& pen = e.W("penalty");
+  for (int r = 0; r < e.R; ++r)
+    ORL_HIP(hipMemcpyAsync(penalty_out + (long)r * e.B, pen.p + r * pen.rs, sizeof(float) * e.B,
+                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e.stream));
+  ORL_HIP(hipStreamSynchronize(e.stream));
+  e.mobile_samples = nullptr;
+  return 0;
 }
 
 int orl_health(orl_engine* h, uint32_t* flags_out) {

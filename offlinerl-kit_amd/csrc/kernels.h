@@ -1492,4 +1492,116 @@ __global__ void k_edac_gamma(EdacGP p) {
   }
 }
 
+// ================================================================================================
+// MOBILE (model_based/mobile.py:130-196; tests/mobile_oracle.py)
+// ================================================================================================
+// the next-state samples [R][M][od] as the actor's input rows (pitch OP, zero padded) and as the observation columns of the target
+// critics' input rows (pitch XP; the action columns are the sampling job's, the padding is zeroed).  grid (ceil(M / 256), R)
+struct MobileInP {
+  const float* smp; long smp_rs;            // [R][M][od]
+  float* xs; long xs_rs; int OP;            // [R][M][OP]
+  float* xl; long xl_rs; int XP;            // [R][M][XP]
+  int M, od, ad;
+};
+__global__ void k_mobile_assemble(MobileInP p) {
+  const int r = blockIdx.y;
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= p.M) return;
+  const float* s = p.smp + (long)r * p.smp_rs + (long)row * p.od;
+  float* a = p.xs + (long)r * p.xs_rs + (long)row * p.OP;
+  float* x = p.xl + (long)r * p.xl_rs + (long)row * p.XP;
+  for (int c = 0; c < p.od; ++c) { const float v = s[c]; a[c] = v; x[c] = v; }
+  for (int c = p.od; c < p.OP; ++c) a[c] = 0.f;
+  for (int c = p.od + p.ad; c < p.XP; ++c) x[c] = 0.f;
+}
+
+// compute_lcb's reduction (mobile.py:138-140), one thread per (run, batch row b): qmin[s, e] = min(q1, q2) of row (s E + e) B + b,
+// m[e] = (sum_s qmin[s, e]) / S, pen[b] = sqrt(sum_e (m[e] - mean_e m)^2 / (E - 1)) (torch's unbiased std); rows b < real_rows get 0
+// (mobile.py:154).  Sums in double, s and e ascending: a fixed order, no atomics on floats.  A non-finite penalty raises the run's
+// ORL_HEALTH_NONFINITE_LOSS.  grid (ceil(B / 256), R)
+enum { LCB_MAX_E = 64 };
+struct LcbP {
+  const float* ql; long ql_rs, ql_cs;       // target critics on the samples [R][2][M]
+  float* qmin; long qm_rs;                  // [R][M]
+  float* pen; long pen_rs;                  // [R][B]
+  int B, S, E, real_rows;
+  unsigned int* health;
+};
+__global__ __launch_bounds__(256) void k_lcb_penalty(LcbP p) {
+  const int r = blockIdx.y;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= p.B) return;
+  const float* q1 = p.ql + (long)r * p.ql_rs;
+  const float* q2 = q1 + p.ql_cs;
+  float* qm = p.qmin + (long)r * p.qm_rs;
+  double m[LCB_MAX_E];
+  double tot = 0.0;
+  for (int e = 0; e < p.E; ++e) {
+    double acc = 0.0;
+    for (int s = 0; s < p.S; ++s) {
+      const long row = ((long)s * p.E + e) * p.B + b;
+      const float v = fminf(q1[row], q2[row]);
+      qm[row] = v;
+      acc += (double)v;
+    }
+    m[e] = (double)(float)(acc / (double)p.S);      // (the reference's mean(0) is an fp32 tensor)
+    tot += m[e];
+  }
+  const double mean = tot / (double)p.E;
+  double ss = 0.0;
+  for (int e = 0; e < p.E; ++e) { const double d = m[e] - mean; ss += d * d; }
+  const float pen = (float)sqrt(ss / (double)(p.E - 1));
+  if (!(fabsf(pen) <= 3.4e38f)) atomicOr(p.health + r, (unsigned int)ORL_HEALTH_NONFINITE_LOSS);
+  p.pen[(long)r * p.pen_rs + b] = b < p.real_rows ? 0.f : pen;
+}
+
+// MOBILE's TD target and critic loss (mobile.py:151-164): y = max((r - c pen) + gamma (1 - d) (min qt - alpha logp'), 0) -- a NaN stays
+// NaN like torch.clamp's --, ONE loss = mean over (2, B) of (q_c - y)^2, so dq_c = 2 (q_c - y) / (2 B).  grid (R), block 256
+struct MobileTdP {
+  const float* q; long q_rs, q_cs; float* dq;    // [R][2][B]
+  const float* qt; long qt_rs, qt_cs;            // target critics at (s', a') [R][2][B]
+  const float* rew; const float* term; long bt_rs;
+  const float* logp_next; long lpn_rs;
+  const float* pen; long pen_rs;                 // [R][B]
+  float* target_q; long tq_rs;
+  int B; float gamma, pen_coef; int use_alpha;
+  const RunScalars* sc; int auto_alpha; float fixed_alpha;
+  MetricsP m; int slot;
+  float* gs_out;                                 // split precision: dynamic scale of dq [R], or null
+};
+__global__ void k_mobile_td_loss(MobileTdP p) {
+  __shared__ float sh[4];
+  const int r = blockIdx.x;
+  const int B = p.B;
+  const float alpha = p.auto_alpha ? p.sc[r].alpha : p.fixed_alpha;
+  float* tq = p.target_q + (long)r * p.tq_rs;
+  const float* qt = p.qt + (long)r * p.qt_rs;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    float nq = fminf(qt[b], qt[p.qt_cs + b]);
+    if (p.use_alpha) nq = __fsub_rn(nq, __fmul_rn(alpha, p.logp_next[(long)r * p.lpn_rs + b]));
+    const float rp = __fsub_rn(p.rew[(long)r * p.bt_rs + b], __fmul_rn(p.pen_coef, p.pen[(long)r * p.pen_rs + b]));
+    const float g = __fmul_rn(p.gamma, __fsub_rn(1.0f, p.term[(long)r * p.bt_rs + b]));
+    const float y = __fadd_rn(rp, __fmul_rn(g, nq));
+    tq[b] = y < 0.f ? 0.f : y;
+  }
+  __syncthreads();
+  float total = 0.f, amax = 0.f;
+  const float inv = 1.0f / (float)(2 * B);
+  for (int c = 0; c < 2; ++c) {
+    const float* q = p.q + (long)r * p.q_rs + (long)c * p.q_cs;
+    float* dq = p.dq + (long)r * p.q_rs + (long)c * p.q_cs;
+    float s = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+      const float d = q[b] - tq[b];
+      s += d * d;
+      const float g = 2.0f * d * inv;
+      dq[b] = g;
+      amax = fmaxf(amax, fabsf(g));
+    }
+    total += block_sum256(s, sh);
+  }
+  if (threadIdx.x == 0) metric_set(p.m, r, p.slot, total * inv);
+  grad_scale_publish(amax, sh, p.gs_out, r);
+}
+
 }  // namespace orl

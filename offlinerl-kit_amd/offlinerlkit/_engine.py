@@ -16,8 +16,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "liborlengine.so")
 
-ALGO_CQL, ALGO_IQL, ALGO_TD3BC, ALGO_EDAC, ALGO_SAC, ALGO_MCQ = 0, 1, 2, 3, 4, 5
-ALGO_ID = {"cql": ALGO_CQL, "iql": ALGO_IQL, "td3bc": ALGO_TD3BC, "edac": ALGO_EDAC, "sac": ALGO_SAC, "mcq": ALGO_MCQ}
+ALGO_CQL, ALGO_IQL, ALGO_TD3BC, ALGO_EDAC, ALGO_SAC, ALGO_MCQ, ALGO_MOBILE = 0, 1, 2, 3, 4, 5, 6
+ALGO_ID = {"cql": ALGO_CQL, "iql": ALGO_IQL, "td3bc": ALGO_TD3BC, "edac": ALGO_EDAC, "sac": ALGO_SAC, "mcq": ALGO_MCQ,
+           "mobile": ALGO_MOBILE}
 MAX_HIDDEN, MAX_METRICS, MAX_NOISE = 4, 8, 6
 NET_ACTOR, NET_CRITIC1, NET_CRITIC2, NET_CRITIC1_OLD, NET_CRITIC2_OLD, NET_CRITIC_V, NET_ACTOR_OLD, NET_VAE_ENC, NET_VAE_DEC = range(9)
 NUM_NETS = 9
@@ -57,6 +58,8 @@ ABI_SYMBOLS = [
     "orl_dyn_update_save", "orl_dyn_load_save", "orl_dyn_step", "orl_dyn_debug_grads",
     # RAMBO's adversarial update on an orl_dynamics
     "orl_dynadv_configure", "orl_dynadv_forward", "orl_dynadv_update", "orl_dynadv_adam_get", "orl_dynadv_adam_set",
+    # MOBILE: next-state samples of the dynamics, their hand-over to the policy engine, compute_lcb alone
+    "orl_dynsample_next", "orl_engine_set_next_samples", "orl_engine_lcb_penalty",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -83,6 +86,7 @@ class OrlConfig(C.Structure):
         ("vae_hidden", C.c_int32), ("vae_latent", C.c_int32), ("mcq_lambda", C.c_float), ("behavior_lr", C.c_float),
         ("ws_one_round", C.c_int32), ("ws_cus", C.c_int32), ("actor_dropout", C.c_float),
         ("external_arena", C.c_void_p),
+        ("mobile_num_samples", C.c_int32), ("mobile_num_elites", C.c_int32), ("mobile_real_rows", C.c_int32), ("penalty_coef", C.c_float),
     ]
 
 
@@ -175,6 +179,8 @@ def load_library(path: Optional[str] = None):
     lib.orl_engine_attach_model_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32]
     lib.orl_step.argtypes = [C.c_void_p, C.POINTER(OrlBatch), C.POINTER(OrlNoise), C.c_void_p]
     lib.orl_learn_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    lib.orl_engine_set_next_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.orl_engine_lcb_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_health.argtypes = [C.c_void_p, C.c_void_p]
     lib.orl_health_check.argtypes = [C.c_void_p, C.c_void_p]
     lib.orl_health_clear.argtypes = [C.c_void_p]
@@ -234,6 +240,7 @@ def _bind_dynamics(lib) -> None:
     lib.orl_dynadv_update.argtypes = [P, VP, C.c_int, VP, VP]
     lib.orl_dynadv_adam_get.argtypes = [P, C.c_int, VP, VP, I64, C.POINTER(C.c_int64)]
     lib.orl_dynadv_adam_set.argtypes = [P, C.c_int, VP, VP, I64, I64]
+    lib.orl_dynsample_next.argtypes = [P, VP, VP, I64, C.c_int32, C.c_int, VP, VP]
 
 
 def split_bits() -> int:
@@ -439,6 +446,27 @@ class Engine:
         m = np.zeros((self.n_runs, MAX_METRICS), dtype=np.float32)
         self._check_step(self.lib.orl_step(self._h, bp, npz, m.ctypes.data), "orl_step")
         return m[:, :len(self.metric_names)]
+
+    def set_next_samples(self, samples, on_device=False):
+        """MOBILE: the [n_runs][S * E * B][obs_dim] next-state samples the next ``step`` consumes: a host array (copied in) or, with
+        ``on_device``, a raw device pointer that is borrowed until that step has run (the caller keeps the memory alive)"""
+        if on_device:
+            ptr = int(samples)
+        else:
+            self._samples_keep = _f32(samples)
+            ptr = self._samples_keep.ctypes.data
+        _check(self.lib.orl_engine_set_next_samples(self._h, ptr, 1 if on_device else 0), "orl_engine_set_next_samples")
+
+    def lcb_penalty(self, eps_lcb=None, out_ptr: Optional[int] = None, on_device=False):
+        """MOBILE's compute_lcb on the pending samples, real rows not zeroed: returns the [n_runs][B] penalty (host array), or writes it
+        to the device pointer ``out_ptr`` when ``on_device`` (``eps_lcb`` is then a device pointer too, or None for device draws)"""
+        if on_device:
+            _check(self.lib.orl_engine_lcb_penalty(self._h, None if eps_lcb is None else int(eps_lcb), int(out_ptr), 1), "orl_engine_lcb_penalty")
+            return None
+        e = None if eps_lcb is None else _f32(eps_lcb)
+        out = np.zeros((self.n_runs, self.cfg.batch_size), dtype=np.float32)
+        _check(self.lib.orl_engine_lcb_penalty(self._h, None if e is None else e.ctypes.data, out.ctypes.data, 0), "orl_engine_lcb_penalty")
+        return out
 
     def learn_n(self, n_steps: int):
         m = np.zeros((self.n_runs, MAX_METRICS), dtype=np.float32)
@@ -853,6 +881,37 @@ class Dynamics:
         _check(self.lib.orl_dyn_step(self._h, obs.data_ptr(), act.data_ptr(), n, 1, None, None, DYN_PENALTY[mode], float(coef),
                                      nxt.data_ptr(), rew.data_ptr(), raw.data_ptr(), pen.data_ptr(), None), "orl_dyn_step")
         return nxt, rew, raw, pen
+
+    # ---- MOBILE's next-state samples (orl_dynsample_next) ----
+    def sample_next(self, obs, act, num_samples: int, noise=None) -> np.ndarray:
+        """obs [R][n][od], act [R][n][ad] host arrays -> [R][S][E][n][od] samples of every elite (``set_elites`` order); noise
+        [R][S][E][n][od + 1] teacher-forces the draws (None: the entry point's own device Philox stream)"""
+        o, a = _f32(obs), _f32(act)
+        R, n = o.shape[0], o.shape[1]
+        assert R == self.n_runs and a.shape[:2] == (R, n)
+        E, S = len(self.get_elites(0)), int(num_samples)
+        nz = None if noise is None else _f32(noise)
+        if nz is not None and nz.shape != (R, S, E, n, self.D):
+            raise ValueError(f"sample_next: noise of shape {nz.shape}, expected {(R, S, E, n, self.D)}")
+        out = np.empty((R, max(S, 0), E, n, self.od), np.float32)
+        _check(self.lib.orl_dynsample_next(self._h, o.ctypes.data, a.ctypes.data, n, S, 0, None if nz is None else nz.ctypes.data,
+                                           out.ctypes.data), "orl_dynsample_next")
+        return out
+
+    def sample_next_device(self, obs, act, num_samples: int, noise=None):
+        """``sample_next`` on contiguous fp32 torch tensors of the engine's device (noise too, when given); nothing visits the host"""
+        import torch
+        R, n = int(obs.shape[0]), int(obs.shape[1])
+        self._check_dev("sample_next_device", obs, (self.n_runs, n, self.od))
+        self._check_dev("sample_next_device", act, (self.n_runs, n, self.ad))
+        E, S = len(self.get_elites(0)), int(num_samples)
+        if noise is not None:
+            self._check_dev("sample_next_device", noise, (R, S, E, n, self.D))
+        out = torch.empty((R, max(S, 0), E, n, self.od), dtype=torch.float32, device=obs.device)
+        torch.cuda.current_stream(obs.device).synchronize()
+        _check(self.lib.orl_dynsample_next(self._h, obs.data_ptr(), act.data_ptr(), n, S, 1, None if noise is None else noise.data_ptr(),
+                                           out.data_ptr()), "orl_dynsample_next")
+        return out
 
     # ---- RAMBO's adversarial update (orl_dynadv_*) ----
     def adv_configure(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, adv_weight: float = 0.0, rollout_rows: int = 256,

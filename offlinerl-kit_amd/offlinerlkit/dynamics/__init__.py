@@ -350,8 +350,38 @@ class EnsembleDynamics(BaseDynamics):
         a = torch.as_tensor(advantage, dtype=torch.float32, device=self._arena.device).reshape(-1)
         return self._adv_metrics(self._eng.adv_update_device(a.unsqueeze(0).expand(self._n_runs, -1).contiguous(), active))
 
-    def sample_next_obss(self, obs, action, num_samples: int):
-        raise NotImplementedError("sample_next_obss is used by MOBILE only, which this package does not implement")
+    @torch.no_grad()
+    def sample_next_obss_device(self, obs, action, num_samples: int, noise=None) -> torch.Tensor:
+        """ensemble_dynamics.py:82-99 on the device (``orl_dynsample_next``): obs (B, obs_dim), action (B, act_dim), tensors or numpy
+        arrays -> (num_samples, E, B, obs_dim) on the engine's device, one sample of every ELITE (in ``model.elites`` order) per draw;
+        nothing visits the host when the inputs are device tensors.  ``noise`` (num_samples, E, B, obs_dim + 1) teacher-forces the
+        reference's ``randn_like`` draws (the reward column is drawn and dropped); by default they come from a device Philox stream
+        of this call alone, so ``step``'s draws are what they are without it.  With several runs every run samples the same rows
+        and the selected run's samples are returned."""
+        self._bind(*(self._shape or (256, 0.01)))
+        self._sync_torch()
+        self._push_elites_from_model()
+        dev, R = self._arena.device, self._n_runs
+        o = torch.as_tensor(obs, dtype=torch.float32, device=dev)
+        a = torch.as_tensor(action, dtype=torch.float32, device=dev)
+        if o.dim() != 2 or a.dim() != 2 or o.shape[0] != a.shape[0]:
+            raise ValueError(f"sample_next_obss: obs {tuple(o.shape)} / action {tuple(a.shape)} must be (B, obs_dim) / (B, act_dim)")
+        for r in range(R):
+            sc = self.scalers[r]
+            if sc.mu is None:
+                raise RuntimeError("the scaler is not fitted: train() or load() the dynamics first")
+            self._eng.set_scaler(r, sc.mu, sc.std)
+        nz = None
+        if noise is not None:
+            nz = torch.as_tensor(noise, dtype=torch.float32, device=dev)
+            nz = nz.unsqueeze(0).expand(R, *nz.shape).contiguous()
+        out = self._eng.sample_next_device(o.unsqueeze(0).expand(R, *o.shape).contiguous(), a.unsqueeze(0).expand(R, *a.shape).contiguous(),
+                                           int(num_samples), nz)
+        return out[self._cur_run]
+
+    def sample_next_obss(self, obs, action, num_samples: int) -> torch.Tensor:
+        """ensemble_dynamics.py:82-99: (num_samples, E, B, obs_dim) next observations on the dynamics' device (MOBILE's compute_lcb)"""
+        return self.sample_next_obss_device(obs, action, num_samples)
 
     def format_samples_for_training(self, data: Dict) -> Tuple[np.ndarray, np.ndarray]:
         obss = data["observations"]

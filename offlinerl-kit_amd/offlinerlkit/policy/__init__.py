@@ -1,7 +1,8 @@
 """offlinerlkit.policy — the four model-free policies of the hot path plus SAC and the model-based callers whose ``learn`` reuses
 its kernels (MOPO, COMBO, MCQ: SURVEY §8(f)3), engine-backed, and RAMBO, whose adversarial update of the dynamics ensemble runs on the
-dynamics engine (``orl_dynadv_*``).
-(The reference package also exports MOBILE / RCSL / diffusion policies; those are out of scope here.)"""
+dynamics engine (``orl_dynadv_*``), and MOBILE, whose penalty pass runs on the dynamics engine (``orl_dynsample_next``) and the policy
+engine (``ORL_ALGO_MOBILE``).
+(The reference package also exports RCSL / diffusion policies; those are out of scope here.)"""
 from .base_policy import BasePolicy, EnginePolicy
 from .iql import IQLPolicy
 from .sac_family import CQLPolicy, EDACPolicy
@@ -9,6 +10,7 @@ from .td3bc import TD3BCPolicy
 from .model_based import SACPolicy, MOPOPolicy, COMBOPolicy
 from .mcq import MCQPolicy
 from .rambo import RAMBOPolicy
+from .mobile import MOBILEPolicy
 
 __all__ = ["BasePolicy", "EnginePolicy", "CQLPolicy", "IQLPolicy", "TD3BCPolicy", "EDACPolicy", "SACPolicy", "MOPOPolicy", "COMBOPolicy", "MCQPolicy",
-           "RAMBOPolicy"]
+           "RAMBOPolicy", "MOBILEPolicy"]

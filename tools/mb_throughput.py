@@ -16,7 +16,13 @@ run-steps per second: R x block steps / seconds of the block, rollouts included.
 [256, 256], 256 rollout + 256 dataset rows per step, adv_rollout_length 5, adv_weight 3e-4, 1000 steps per update):
 ``RAMBOPolicy.update_dynamics`` on the engine against a stock-torch restatement of the same update (the reference's
 ``dynamics_step_and_forward`` with torch autograd and torch.optim.Adam on the same GPU, same buffer draws, actor and critics), a warm-up
-of each and then alternating timed updates.  The figure is model-update steps per second."""
+of each and then alternating timed updates.  The figure is model-update steps per second.
+
+--mobile measures, instead, ``MOBILEPolicy.learn`` in the host loop at run_mobile.py's shape (policy [256, 256], dynamics [200] x 4, 7
+members, 5 elites, 10 samples: 12 800 penalty rows per step, batch 256 with 12 real rows, penalty_coef 1.5, deterministic backup) against
+a stock-torch restatement of the same step (mobile.py:130-196 with torch autograd and torch.optim.Adam on the same GPU, same batches), a
+warm-up of each and then alternating timed blocks; the figure is gradient steps per second.  It also prints the HIP-event split of one
+block into the penalty pass (the ``lcb`` launches of orl_profile_query) and the rest of the step."""
 import argparse
 import json
 import os
@@ -32,7 +38,7 @@ from offlinerlkit.buffer import ReplayBuffer  # noqa: E402
 from offlinerlkit.dynamics import EnsembleDynamics  # noqa: E402
 from offlinerlkit.modules import ActorProb, Critic, EnsembleDynamicsModel, TanhDiagGaussian  # noqa: E402
 from offlinerlkit.nets import MLP  # noqa: E402
-from offlinerlkit.policy import COMBOPolicy, MOPOPolicy, RAMBOPolicy  # noqa: E402
+from offlinerlkit.policy import COMBOPolicy, MOBILEPolicy, MOPOPolicy, RAMBOPolicy  # noqa: E402
 from offlinerlkit.policy_trainer import MBPolicyTrainer  # noqa: E402
 from offlinerlkit.utils.scaler import StandardScaler  # noqa: E402
 from offlinerlkit.utils.termination_fns import termination_fn_halfcheetah  # noqa: E402
@@ -278,6 +284,112 @@ def measure_rambo(ds, blocks, steps):
                 last_losses={k: {a: float(b) for a, b in v.items()} for k, v in last.items()})
 
 
+def torch_mobile_learn(t, obs, act, nobs, rew, term, real_rows, S, coef, gamma, tau, target_entropy):
+    """mobile.py:130-196 in stock torch on the GPU (auto-alpha, deterministic backup): ``t`` holds the modules and optimizers"""
+    model, elites = t["model"], t["model"].elites.data
+    with torch.no_grad():
+        mean, logvar = model((torch.cat([obs, act], -1) - t["mu"]) / t["std"])
+        mean = torch.cat([mean[..., :-1] + obs, mean[..., -1:]], -1)[elites]
+        std = torch.sqrt(torch.exp(logvar))[elites]
+        nxt = torch.stack([mean + torch.randn_like(std) * std for _ in range(S)], 0)[..., :-1]
+        s, e, b, od = nxt.shape
+        flat = nxt.reshape(-1, od)
+        a_l, _ = t["actforward"](flat)
+        q = torch.minimum(t["critics_old"][0](flat, a_l), t["critics_old"][1](flat, a_l)).reshape(s, e, b, 1)
+        pen = q.mean(0).std(0)
+        pen[:real_rows] = 0.0
+        na, _ = t["actforward"](nobs)
+        next_q = torch.minimum(t["critics_old"][0](nobs, na), t["critics_old"][1](nobs, na))
+        target = torch.clamp((rew - coef * pen) + gamma * (1 - term) * next_q, 0, None)
+    qs = torch.stack([c(obs, act) for c in t["critics"]], 0)
+    critic_loss = ((qs - target) ** 2).mean()
+    t["critics_optim"].zero_grad(); critic_loss.backward(); t["critics_optim"].step()
+    a, logp = t["actforward"](obs)
+    alpha = t["log_alpha"].detach().exp().clamp(0.0, 1.0)
+    actor_loss = -torch.minimum(t["critics"][0](obs, a), t["critics"][1](obs, a)).mean() + alpha * logp.mean()
+    t["actor_optim"].zero_grad(); actor_loss.backward(); t["actor_optim"].step()
+    alpha_loss = -(t["log_alpha"] * (logp.detach() + target_entropy)).mean()
+    t["alpha_optim"].zero_grad(); alpha_loss.backward(); t["alpha_optim"].step()
+    with torch.no_grad():
+        for o, n in zip(t["critics_old"].parameters(), t["critics"].parameters()):
+            o.mul_(1.0 - tau).add_(n, alpha=tau)
+    return {"loss/actor": actor_loss.item(), "loss/critic": critic_loss.item(), "loss/alpha": alpha_loss.item()}
+
+
+def measure_mobile(ds, blocks, steps):
+    from copy import deepcopy
+    S, coef, gamma, tau, real_rows = 10, 1.5, 0.99, 0.005, int(B * 0.05)
+    real = ReplayBuffer(len(ds["rewards"]), (OD,), np.float32, AD, np.float32, device=DEV)
+    real.load_dataset(ds)
+    half = len(ds["rewards"]) // 2
+    fake = ReplayBuffer(half, (OD,), np.float32, AD, np.float32, device=DEV)      # model rows: any transitions do for the arithmetic
+    fake.load_dataset({k: v[:half] for k, v in ds.items()})
+    torch.manual_seed(1)
+    adam = lambda m, lr: torch.optim.Adam(m.parameters(), lr=lr)
+    mk_model = lambda: EnsembleDynamicsModel(OD, AD, DYN_HID, num_ensemble=K, num_elites=E, weight_decays=DECAYS, device=DEV)
+    model, tmodel = mk_model(), mk_model()
+    tmodel.load_state_dict(model.state_dict())
+    scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
+    dyn = EnsembleDynamics(model, adam(model, 1e-3), scaler, termination_fn_halfcheetah)
+    mk_actor = lambda: ActorProb(MLP(OD, [256, 256]), TanhDiagGaussian(256, AD, unbounded=True, conditioned_sigma=True), DEV)
+    mk_critics = lambda: torch.nn.ModuleList([Critic(MLP(OD + AD, [256, 256]), DEV), Critic(MLP(OD + AD, [256, 256]), DEV)])
+    actor, critics = mk_actor(), mk_critics()
+    tactor, tcritics = deepcopy(actor), deepcopy(critics)
+    log_alpha = torch.zeros(1, requires_grad=True, device=DEV)
+    pol = MOBILEPolicy(dyn, actor, critics, adam(actor, 1e-4), adam(critics, 3e-4), tau=tau, gamma=gamma,
+                       alpha=(-float(AD), log_alpha, torch.optim.Adam([log_alpha], lr=1e-4)), penalty_coef=coef, num_samples=S,
+                       deterministic_backup=True)
+    pol.set_engine_options(seed=3)
+    pol.train()
+    tla = torch.zeros(1, requires_grad=True, device=DEV)
+
+    def actforward(o):
+        dist = tactor(o)
+        sq, raw = dist.rsample()
+        return sq, dist.log_prob(sq, raw)
+    t = dict(model=tmodel, mu=torch.zeros(OD + AD, device=DEV), std=torch.ones(OD + AD, device=DEV), actforward=actforward, critics=tcritics,
+             critics_old=deepcopy(tcritics), critics_optim=adam(tcritics, 3e-4), actor_optim=adam(tactor, 1e-4), log_alpha=tla,
+             alpha_optim=torch.optim.Adam([tla], lr=1e-4))
+    last = {}
+
+    def block(name, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            rb, fb = real.sample(real_rows), fake.sample(B - real_rows)
+            if name == "engine":
+                last[name] = pol.learn({"real": rb, "fake": fb})
+            else:
+                mix = {k: torch.cat([rb[k], fb[k]], 0) for k in rb}
+                last[name] = torch_mobile_learn(t, mix["observations"], mix["actions"], mix["next_observations"], mix["rewards"],
+                                                mix["terminals"], real_rows, S, coef, gamma, tau, -float(AD))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    names = ("torch", "engine")
+    np.random.seed(0)
+    torch.manual_seed(0)
+    warm = {name: block(name, 100) for name in names}
+    secs = {name: [] for name in names}
+    for _ in range(blocks):
+        for name in names:
+            secs[name].append(block(name, steps))
+    sps = {name: [steps / x for x in v] for name, v in secs.items()}
+    # HIP-event split of the engine's step (profiling serialises nothing here: the launches of a step are one stream already)
+    pol.engine.profile_enable(True)
+    n_prof = min(steps, 200)
+    block("engine", n_prof)
+    table = pol.engine.profile_table()
+    pol.engine.profile_enable(False)
+    pen_ms = sum(r["total_ms"] for r in table if "lcb" in r["name"]) / n_prof
+    rest_ms = sum(r["total_ms"] for r in table if "lcb" not in r["name"]) / n_prof
+    return dict(mode="mobile_learn", steps=steps, batch=B, real_rows=real_rows, num_samples=S, elites=E, penalty_rows=S * E * B,
+                warmup_seconds_100_steps=warm, seconds=secs, steps_per_s=sps, steps_per_s_mean={k: float(np.mean(v)) for k, v in sps.items()},
+                speedup=float(np.mean(sps["engine"]) / np.mean(sps["torch"])),
+                engine_kernel_ms_per_step=dict(penalty_pass=pen_ms, rest=rest_ms),
+                penalty_launches={r["name"]: r["total_ms"] / n_prof for r in table if "lcb" in r["name"]},
+                last_losses={k: {a: float(b) for a, b in v.items()} for k, v in last.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=3)
@@ -288,9 +400,21 @@ def main():
     ap.add_argument("--profile-block", action="store_true", help="a warm-up and one fused MOPO block only (for a kernel trace)")
     ap.add_argument("--rambo", action="store_true", help="RAMBO's update_dynamics (engine) against its stock-torch restatement")
     ap.add_argument("--rambo-steps", type=int, default=1000)
+    ap.add_argument("--mobile", action="store_true", help="MOBILEPolicy.learn (engine, host loop) against its stock-torch restatement")
+    ap.add_argument("--mobile-steps", type=int, default=500)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mb_throughput: no HIP device visible (the loops under test run on the GPU)")
+    if a.mobile:
+        res = {"shape": dict(obs=OD, act=AD, dynamics_hidden=DYN_HID, members=K, elites=E, policy_hidden=[256, 256]),
+               "device": torch.cuda.get_device_name(0), "results": [measure_mobile(dataset(200_000), a.blocks, a.mobile_steps)]}
+        s = json.dumps(res, indent=1)
+        print(s)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(s + "\n")
+        return
     if a.rambo:
         res = {"shape": dict(obs=OD, act=AD, dynamics_hidden=DYN_HID, members=K, elites=E, policy_hidden=[256, 256]),
                "device": torch.cuda.get_device_name(0), "results": [measure_rambo(dataset(200_000), a.blocks, a.rambo_steps)]}
