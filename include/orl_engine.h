@@ -60,6 +60,9 @@ extern "C" {
 #define ORL_ALGO_SAC 4   /* policy/model_free/sac.py:88-140 (MOPOPolicy.learn on the real+model batch, model_based/mopo.py:81-84) */
 #define ORL_ALGO_MCQ 5   /* policy/model_free/mcq.py:48-126 (SAC critics / actor + the VAE behaviour policy of nets/vae.py) */
 #define ORL_ALGO_MOBILE 6 /* policy/model_based/mobile.py:130-196 (SAC schedule + the model-Bellman-inconsistency penalty; needs orl_engine_set_next_samples) */
+#define ORL_ALGO_RCSL 7   /* policy/rcsl/rcsl.py:123-151: one net (ORL_NET_ACTOR) = MLP(obs_dim + 1, hidden, act_dim) of modules/rcsl_module.py, MSE on the
+                           * dataset action, Adam with actor_lr / ORL_OPT_ACTOR; metric "loss".  The return-to-go travels where the other algorithms
+                           * carry the reward: orl_batch.rewards and the `rew` column of an orl_buffer */
 
 /* per-run health flags (orl_health).  The reference raises nothing when a run diverges (its losses simply turn nan); here a diverging run
  * can additionally be MASKED by the arithmetic -- the ReLU of the matrix kernels works on the integer view of the activations and maps a NaN
@@ -171,9 +174,9 @@ typedef struct orl_config {
 typedef struct orl_batch {
   const float* observations;
   const float* actions;
-  const float* next_observations;
-  const float* rewards;
-  const float* terminals;
+  const float* next_observations; /* RCSL: not read, may be NULL */
+  const float* rewards;           /* RCSL: the returns-to-go ("rtgs") */
+  const float* terminals;         /* RCSL: not read, may be NULL */
   int32_t on_device; /* 0: host pointers (copied in), 1: device pointers */
 } orl_batch;
 
@@ -228,7 +231,9 @@ typedef struct orl_buffer orl_buffer;
 /* ReplayBuffer.__init__ (:8-32): an empty HBM-resident SoA store on `device` */
 int orl_buffer_create(int32_t obs_dim, int32_t act_dim, int32_t device, orl_buffer** out);
 void orl_buffer_destroy(orl_buffer* b);
-/* load_dataset (:72-86): host arrays -> HBM SoA; obs/next_obs [n][obs_dim], act [n][act_dim], rew/term [n] */
+/* load_dataset (:72-86): host arrays -> HBM SoA; obs/next_obs [n][obs_dim], act [n][act_dim], rew/term [n].  A buffer that feeds an RCSL
+ * engine carries the return-to-go in `rew`; at precision >= 1 orl_engine_attach_buffer range-checks that column like the observations
+ * (it is an MFMA operand there: |rtg| < 65504), and orl_health_check covers it with the net's input. */
 int orl_buffer_load(orl_buffer* b, const float* obs, const float* act, const float* next_obs, const float* rew,
                     const float* term, int64_t n);
 /* normalize_obs (:88-94): (x - mean) / (std + eps) in place on the device; mean/std(+eps) (obs_dim each) to host */
@@ -295,6 +300,18 @@ int orl_step(orl_engine* e, const orl_batch* batch, const orl_noise* noise, floa
  * sampling and noise on device; metrics_mean: host [n_runs][ORL_MAX_METRICS] epoch means;
  * elapsed_ms (optional): HIP-event time of the n steps on the engine stream. */
 int orl_learn_n(orl_engine* e, int n_steps, float* metrics_mean, float* elapsed_ms);
+/* RcslPolicyTrainer's inner loop (rcsl_policy_trainer.py:104-134) over a caller-supplied row order:
+ * step s of run r learns rows order[r][s*B + b] of the attached buffer; a negative entry is padding.
+ * order: int64 [n_runs][order_len] (a device pointer when on_device), order_len a multiple of batch_size; it is copied into an
+ * engine-owned device array.  One shuffled pass of DataLoader(shuffle=True) is a permutation of [0, N) padded with -1 to a multiple of
+ * B: a padding row contributes nothing to the loss, its gradient row is zero and the mean divides by valid rows x act_dim, which is the
+ * reference's partial last batch.  The position within the epoch lives in a device cell: one captured step graph serves every step of
+ * every epoch.  The row's index, padding included, is recorded per step (a padding row reads row 0 of the dataset).
+ * metrics_mean: host [n_runs][ORL_MAX_METRICS], the unweighted mean over the order_len / B steps (logkv_mean per batch).
+ * Refused before a step is launched: no buffer attached, order_len not a multiple of B, an entry >= the buffer's size (host orders are
+ * checked on the host, device orders by one checking launch), a step whose rows are all padding, an engine that is not RCSL. */
+int orl_learn_epoch(orl_engine* e, const int64_t* order, int64_t order_len, int on_device,
+                    float* metrics_mean, float* elapsed_ms);
 /* MOBILE: the next-state samples of the batch the NEXT orl_step learns, [n_runs][S * E * batch][obs_dim] in the row order of
  * orl_dynsample_next (row (s * E + e) * batch + b).  A device pointer (on_device) is borrowed until that step has run -- nothing is
  * copied, the producer must have finished writing (orl_dynsample_next synchronises its stream) --; a host pointer is copied in.  One
@@ -321,7 +338,7 @@ int64_t orl_step_count(orl_engine* e);
 
 /* -- test / profiling taps --------------------------------------------------------- */
 /* copies an intermediate of the LAST step to host: returns number of floats written or <0.
- * names: "q1","q2","target_q","q1a","q2a","logp_a", ... (algorithm specific); every engine also has the minibatch of the last
+ * names: "q1","q2","target_q","q1a","q2a","logp_a", ... (algorithm specific; RCSL: "pred", "rcsl_x" = [obs | rtg]); every engine also has the minibatch of the last
  * step ("b_obs","b_nobs","b_act","b_rew","b_term": what ReplayBuffer.sample returned / the device sampler drew) and its noise
  * arrays under their orl_noise slot names ("n_eps_actor", ...). */
 int64_t orl_debug_read(orl_engine* e, int run, const char* name, float* host, int64_t cap);

@@ -98,6 +98,7 @@ struct Buffer {             // HBM-resident replay buffer (buffer/buffer.py)
   long long* idx = nullptr; long idx_cap = 0;
   unsigned long long counter = 0;
   float absmax = -1.f; unsigned long long absmax_gen = ~0ull;   // max |obs|, |next_obs|, |act| of generation absmax_gen (engines at precision 1 ask for it)
+  float rew_absmax = -1.f; unsigned long long rew_absmax_gen = ~0ull;   // max |rew| likewise (RCSL engines: the column holds the return-to-go, an MFMA operand)
   unsigned long long gen = 0;   // bumped by every orl_buffer_load / orl_buffer_reserve: engines re-capture graphs that hold the old dataset pointers / size
   // growable ring (orl_buffer_reserve): `cap` rows allocated once, rows land at (ptr + i) % cap, n = min(n + i, cap) as in add_batch
   // (buffer.py:52-70).  d_n mirrors n in a device cell: kernels that sample the ring as the MODEL source read the size from it, so a
@@ -168,6 +169,13 @@ struct Engine {
   int upload_model_table();
   // MOBILE: the next-state samples the next step consumes (orl_engine_set_next_samples): a borrowed device pointer or the engine's own copy
   const float* mobile_samples = nullptr; long mobile_samples_rs = 0; bool mobile_pending = false;
+  // RCSL: where the step's rows come from (kernels.h: RI_SLOTS orl_step, RI_DRAWN orl_learn_n, RI_ORDER orl_learn_epoch); the ordered
+  // epoch's row order [R][order_len] (engine-owned, grown when needed: the captured graph holds its address), the device cell with the
+  // epoch's first step / length, and the flag word of the checking launch.  graph_exec[0] is the drawn step, graph_exec[1] the ordered one.
+  int rcsl_mode = 0;
+  long long* d_order = nullptr; long d_order_cap = 0;
+  EpochCell* epoch_cell = nullptr;
+  unsigned int* order_flags = nullptr;
   void drop_graphs();
   // split-K slab table of the last adam() launch per net (orl_debug_grads sums the slabs the way k_adam does)
   std::vector<std::pair<long, int>> last_segs[ORL_NUM_NETS];
@@ -334,6 +342,7 @@ struct Engine {
   int sac_build(); int sac_step();
   int mcq_build(); int mcq_step();
   int mobile_build(); int mobile_step(); int mobile_penalty(int real_rows);
+  int rcsl_build(); int rcsl_step(); int rcsl_prepare(int mode);
 };
 
 }  // namespace orl

@@ -35,7 +35,7 @@ static void add_tensor(NetLayout& l, const std::string& name, long off, std::ini
   l.tensors.push_back(t);
 }
 
-enum TailKind { TAIL_CRITIC, TAIL_TANH_GAUSS, TAIL_GAUSS, TAIL_DET };
+enum TailKind { TAIL_CRITIC, TAIL_TANH_GAUSS, TAIL_GAUSS, TAIL_DET, TAIL_LINEAR };
 
 // seq_step: distance of consecutive Linear layers in the backbone's nn.Sequential -- 2 for [Linear, ReLU], 3 when every ReLU is followed by
 // nn.Dropout (nets/mlp.py:20-23): the state_dict keys are backbone.model.{0, 3, 6, ...} then
@@ -76,6 +76,12 @@ static NetLayout make_mlp_layout(int in_dim, const int* hidden, int L, TailKind 
     l.w_off[L] = off; add_tensor(l, "dist_net.mu.weight", off, {act_dim, d}); off += (long)act_dim * d;
     l.b_off[L] = off; add_tensor(l, "dist_net.mu.bias", off, {act_dim}); off += act_dim;
     l.extra_off = off; add_tensor(l, "dist_net.sigma_param", off, {act_dim, 1}); off += act_dim;
+  } else if (tail == TAIL_LINEAR) {
+    // the output layer is the backbone's own last nn.Linear (nets/mlp.py with output_dim: RcslModule): no tanh, no distribution head
+    const std::string n = "backbone.model." + std::to_string(seq_step * L);
+    l.out_dim = act_dim;
+    l.w_off[L] = off; add_tensor(l, n + ".weight", off, {act_dim, d}); off += (long)act_dim * d;
+    l.b_off[L] = off; add_tensor(l, n + ".bias", off, {act_dim}); off += act_dim;
   } else {
     l.out_dim = act_dim;
     l.w_off[L] = off; add_tensor(l, "last.weight", off, {act_dim, d}); off += (long)act_dim * d;
@@ -179,6 +185,8 @@ static int build_layouts(const orl_config& c, NetLayout* lay, long* net_off, boo
     const NetLayout ens = make_ensemble_layout(od + ad, c.hidden, L, c.num_critics);
     train(ORL_NET_CRITIC1, ens);
     target(ORL_NET_CRITIC1_OLD, ens);
+  } else if (c.algo == ORL_ALGO_RCSL) {
+    train(ORL_NET_ACTOR, make_mlp_layout(od + 1, c.hidden, L, TAIL_LINEAR, ad));      // MLP(obs_dim + 1, hidden, act_dim) of RcslModule
   } else {
     return fail("unknown algorithm id");
   }
@@ -1099,6 +1107,7 @@ static SampleJob make_job(int head_row0, int rows, int rep, const Mat& eps, cons
 #include "algo_sac.inc"
 #include "algo_mcq.inc"
 #include "algo_mobile.inc"
+#include "algo_rcsl.inc"
 
 namespace orl {
 
@@ -1243,6 +1252,7 @@ int Engine::init(const orl_config& c) {
     case ORL_ALGO_SAC: rc = sac_build(); break;
     case ORL_ALGO_MCQ: rc = mcq_build(); break;
     case ORL_ALGO_MOBILE: rc = mobile_build(); break;
+    case ORL_ALGO_RCSL: rc = rcsl_build(); break;
   }
   if (rc) return rc;
   { Mat lc; lc.p = (float*)lab_clk(0); lc.pitch = 192; taps["lab_clk"] = {lc, 1, 192}; }      // shader-clock stamps of lab builds (small_bwd.hip)
@@ -1260,6 +1270,7 @@ int Engine::init(const orl_config& c) {
 }
 
 int Engine::enqueue_sample() {
+  if (cfg.algo == ORL_ALGO_RCSL) return 0;      // rcsl_step's own input launch gathers (k_rcsl_prepare)
   if (!buf || !buf->obs) return fail("no replay buffer attached (orl_engine_attach_buffer)");
   GatherP g;
   memset(&g, 0, sizeof(g));
@@ -1369,6 +1380,7 @@ int Engine::enqueue_step(int variant) {
     case ORL_ALGO_SAC: rc = sac_step(); break;
     case ORL_ALGO_MCQ: rc = mcq_step(); break;
     case ORL_ALGO_MOBILE: rc = mobile_step(); break;
+    case ORL_ALGO_RCSL: rc = rcsl_step(); break;
   }
   if (rc) return rc;
   if (tick_folded) return 0;               // the step's own kernels advanced the counter
@@ -1394,9 +1406,9 @@ extern "C" {
 
 const char* orl_last_error(void) { return g_err.c_str(); }
 #ifdef ORL_SPLIT_BF16
-const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-bf16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE)"; }
+const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-bf16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL)"; }
 #else
-const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-fp16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE)"; }
+const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-fp16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL)"; }
 #endif
 int orl_split_bits(void) { return ORL_SPLIT_BITS; }
 
@@ -1421,6 +1433,7 @@ void orl_config_default(orl_config* c, int32_t algo) {
   c->vae_hidden = 750; c->vae_latent = 2 * c->act_dim; c->mcq_lambda = 0.9f; c->behavior_lr = 1e-3f;   /* run_mcq.py:34-36, 93-99 */
   c->mobile_num_samples = 10; c->mobile_num_elites = 5; c->mobile_real_rows = 12; c->penalty_coef = 1.5f;   /* run_mobile.py:45-52: int(256 * 0.05) real rows */
   if (algo == ORL_ALGO_MOBILE) { c->deterministic_backup = 1; }                                             /* run_mobile.py:157 */
+  if (algo == ORL_ALGO_RCSL) { c->n_hidden = 4; for (int i = 0; i < 4; ++i) c->hidden[i] = 200; c->actor_lr = 1e-3f; }   /* run_rcsl.py:125-127 */
   if (algo == ORL_ALGO_MCQ) { c->hidden[0] = c->hidden[1] = 400; c->actor_lr = c->critic_lr = c->alpha_lr = 3e-4f; c->target_entropy = -(float)c->act_dim; }
 }
 
@@ -1598,7 +1611,7 @@ static int ring_publish(Buffer& b) {
   const long long nn = b.n;
   ORL_HIP(hipMemcpy(b.d_n, &nn, sizeof(nn), hipMemcpyHostToDevice));
   ORL_HIP(hipDeviceSynchronize());        // the appended rows and the new size are visible to every stream of the process
-  b.absmax_gen = ~0ull;
+  b.absmax_gen = ~0ull; b.rew_absmax_gen = ~0ull;
   return 0;
 }
 int orl_buffer_reserve(orl_buffer* h, int64_t capacity) {
@@ -1757,7 +1770,7 @@ int orl_buffer_append_rollout_runs(orl_buffer* const* rings, int32_t n_runs, int
     memcpy(&rew_sum[r], &res[R + r], sizeof(double));
     b.ptr = (b.ptr + n[r]) % b.cap;
     b.n = std::min(b.n + (long)n[r], b.cap);     // (the kernel published the same value to the ring's size cell)
-    b.absmax_gen = ~0ull;
+    b.absmax_gen = ~0ull; b.rew_absmax_gen = ~0ull;
   }
   ORL_HIP(hipDeviceSynchronize());            // the appended rows and the new sizes are visible to every stream of the process
   return 0;
@@ -1867,6 +1880,28 @@ int orl_engine_attach_buffer(orl_engine* h, orl_buffer* b) {
       return fail(msg);
     }
   }
+  if (h->e.split_scales() && h->e.cfg.algo == ORL_ALGO_RCSL && b->b.rew) {
+    // the reward column holds the return-to-go, column obs_dim of the net's input: an MFMA operand like the observations
+    Buffer& bb = b->b;
+    if (bb.rew_absmax_gen != bb.gen) {
+      ORL_HIP(hipSetDevice(bb.dev));
+      unsigned int* d = nullptr;
+      ORL_HIP(hipMalloc((void**)&d, sizeof(unsigned int)));
+      ORL_HIP(hipMemset(d, 0, sizeof(unsigned int)));
+      hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, 0, (const float*)bb.rew, bb.n, d);
+      unsigned int bits = 0;
+      ORL_HIP(hipMemcpy(&bits, d, sizeof(bits), hipMemcpyDeviceToHost));
+      hipFree(d);
+      memcpy(&bb.rew_absmax, &bits, sizeof(float));
+      bb.rew_absmax_gen = bb.gen;
+    }
+    if (!(bb.rew_absmax < 65504.0f)) {
+      char msg[256];
+      snprintf(msg, sizeof(msg), "attach_buffer: the dataset's returns-to-go (reward column) reach |x| = %g, beyond the operand range of "
+               "precision 1 (fp16 hi + lo planes, |x| < 65504): scale the returns or use precision 0", (double)bb.rew_absmax);
+      return fail(msg);
+    }
+  }
   h->e.buf = &b->b;
   h->e.buf_gen = b->b.gen; h->e.buf_n = b->b.n;
   h->e.drop_graphs();             // captured graphs hold the old dataset pointers
@@ -1876,6 +1911,7 @@ int orl_engine_attach_buffer(orl_engine* h, orl_buffer* b) {
 int orl_engine_attach_model_buffer(orl_engine* h, orl_buffer* m, int32_t real_rows) {
   Engine& e = h->e;
   if (!m) { if (e.mbuf || !e.mbufs.empty()) { e.mbuf = nullptr; e.mbufs.clear(); e.mbuf_real_rows = 0; e.drop_graphs(); } return 0; }
+  if (e.cfg.algo == ORL_ALGO_RCSL) return fail("attach_model_buffer: not available for RCSL engines (one dataset, no real + model batch)");
   if (m->b.od != e.od || m->b.ad != e.ad) return fail("attach_model_buffer: obs/act dims differ from the engine's");
   if (m->b.dev != e.dev) return fail("attach_model_buffer: buffer lives on another device");
   if (!m->b.d_n || m->b.cap < 1) return fail("attach_model_buffer: the model buffer must be a ring (orl_buffer_reserve)");
@@ -1903,6 +1939,7 @@ int Engine::upload_model_table() {
 int orl_engine_attach_model_buffers(orl_engine* h, orl_buffer* const* models, int32_t n, int32_t real_rows) {
   Engine& e = h->e;
   if (!models || n == 0) return orl_engine_attach_model_buffer(h, nullptr, 0);
+  if (e.cfg.algo == ORL_ALGO_RCSL) return fail("attach_model_buffers: not available for RCSL engines (one dataset, no real + model batch)");
   char msg[192];
   if (n != e.cfg.n_runs) {
     snprintf(msg, sizeof(msg), "attach_model_buffers: %d rings for an engine of %d runs (one ring per run)", (int)n, (int)e.cfg.n_runs);
@@ -1949,11 +1986,13 @@ int orl_step(orl_engine* h, const orl_batch* b, const orl_noise* nz, float* metr
   if (b) {
     const bool dv = b->on_device != 0;
     if (copy_rows(e, e.W("b_obs2"), b->observations, B, e.od, dv, 0)) return -1;
-    if (copy_rows(e, e.W("b_obs2"), b->next_observations, B, e.od, dv, B)) return -1;
+    const bool rcsl = e.cfg.algo == ORL_ALGO_RCSL;      // (reads observations, actions and the return-to-go in `rewards` only)
+    if (!(rcsl && !b->next_observations) && copy_rows(e, e.W("b_obs2"), b->next_observations, B, e.od, dv, B)) return -1;
     if (copy_rows(e, e.W("b_act"), b->actions, B, e.ad, dv)) return -1;
     if (copy_rows(e, e.W("b_rew"), b->rewards, B, 1, dv)) return -1;
-    if (copy_rows(e, e.W("b_term"), b->terminals, B, 1, dv)) return -1;
+    if (!(rcsl && !b->terminals) && copy_rows(e, e.W("b_term"), b->terminals, B, 1, dv)) return -1;
   }
+  e.rcsl_mode = RI_SLOTS;
   if (nz) {
     const bool dv = nz->on_device != 0;
     for (size_t i = 0; i < e.noise_slots.size(); ++i)
@@ -1996,6 +2035,7 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
     if (e.cfg.algo == ORL_ALGO_CQL && e.mbuf_real_rows != e.cfg.cql_real_rows)
       return fail("orl_learn_n: the model buffer's real_rows differs from the engine's cql_real_rows (COMBO's row layout)");
   }
+  e.rcsl_mode = RI_DRAWN;
   ORL_HIP(hipMemsetAsync(e.metrics_sum, 0, sizeof(float) * e.R * e.nm, e.stream));
   // the buffer was reloaded (or, a ring attached as the primary source, grew) since the graphs were captured: they hold freed pointers
   // and the old size.  The model ring's size is read from its device cell: growth needs no re-capture, only a new reserve / load does.
@@ -2050,6 +2090,107 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
   if (metrics_mean) {
     for (int r = 0; r < e.R; ++r)
       for (int k = 0; k < ORL_MAX_METRICS; ++k) metrics_mean[r * ORL_MAX_METRICS + k] = k < e.nm ? m[r * e.nm + k] / n_steps : 0.f;
+  }
+  unsigned int bad = 0;
+  if (e.health_update(m.data(), n_steps, &bad)) return -1;
+  return bad ? ORL_RC_UNHEALTHY : 0;
+}
+
+int orl_learn_epoch(orl_engine* h, const int64_t* order, int64_t order_len, int on_device, float* metrics_mean, float* elapsed_ms) {
+  Engine& e = h->e;
+  ORL_HIP(hipSetDevice(e.dev));
+  if (e.cfg.algo != ORL_ALGO_RCSL)
+    return fail("orl_learn_epoch: available for RCSL engines only (the other algorithms sample with replacement: orl_learn_n)");
+  if (!order) return fail("orl_learn_epoch: null row order");
+  if (!e.buf || !e.buf->obs || e.buf->n < 1) return fail("orl_learn_epoch: no replay buffer attached");
+  const int B = e.B;
+  if (order_len <= 0 || order_len % B != 0) return fail("orl_learn_epoch: order_len must be a positive multiple of batch_size (pad the tail with -1)");
+  const long n_steps = order_len / B, total = (long)e.R * order_len, n = e.buf->n;
+  static_assert(sizeof(long long) == sizeof(int64_t), "row orders are int64");
+  if (!on_device) {
+    for (int r = 0; r < e.R; ++r)
+      for (long s = 0; s < n_steps; ++s) {
+        bool any = false;
+        const int64_t* o = order + (long)r * order_len + s * B;
+        for (int b = 0; b < B; ++b) {
+          if (o[b] >= n) {
+            char msg[192];
+            snprintf(msg, sizeof(msg), "orl_learn_epoch: run %d, step %ld: row %lld is beyond the buffer's %ld rows", r, s, (long long)o[b], n);
+            return fail(msg);
+          }
+          any = any || o[b] >= 0;
+        }
+        if (!any) {
+          char msg[160];
+          snprintf(msg, sizeof(msg), "orl_learn_epoch: run %d, step %ld: every row is padding", r, s);
+          return fail(msg);
+        }
+      }
+  }
+  // the engine's own copy of the order: grown when needed, and only then are the graphs (which hold its address) dropped
+  ORL_HIP(hipStreamSynchronize(e.stream));
+  if (total > e.d_order_cap) {
+    e.drop_graphs();
+    long long* p = nullptr;
+    ORL_HIP(hipMalloc((void**)&p, sizeof(long long) * total));
+    if (e.d_order) {
+      e.allocs.erase(std::remove(e.allocs.begin(), e.allocs.end(), (void*)e.d_order), e.allocs.end());
+      hipFree(e.d_order);
+    }
+    e.allocs.push_back(p);
+    e.d_order = p; e.d_order_cap = total;
+  }
+  ORL_HIP(hipMemcpy(e.d_order, order, sizeof(long long) * total, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  if (on_device) {      // one checking launch with a flag word: nothing of the epoch is launched when it comes back raised
+    ORL_HIP(hipMemsetAsync(e.order_flags, 0, sizeof(unsigned int), e.stream));
+    hipLaunchKernelGGL(k_order_check, dim3((unsigned)n_steps, e.R), dim3(256), 0, e.stream, (const long long*)e.d_order, (long)order_len, B, n, e.order_flags);
+    if (hipGetLastError() != hipSuccess) return fail("orl_learn_epoch: checking launch failed");
+    unsigned int fl = 0;
+    ORL_HIP(hipMemcpyAsync(&fl, e.order_flags, sizeof(fl), hipMemcpyDeviceToHost, e.stream));
+    ORL_HIP(hipStreamSynchronize(e.stream));
+    if (fl & 1u) return fail("orl_learn_epoch: the row order holds an entry beyond the buffer's rows");
+    if (fl & 2u) return fail("orl_learn_epoch: the row order holds a step whose rows are all padding");
+  }
+  const EpochCell cell{e.step_host, (long long)n_steps, (long long)order_len};
+  ORL_HIP(hipMemcpy(e.epoch_cell, &cell, sizeof(cell), hipMemcpyHostToDevice));
+  e.rcsl_mode = RI_ORDER;
+  ORL_HIP(hipMemsetAsync(e.metrics_sum, 0, sizeof(float) * e.R * e.nm, e.stream));
+  if (e.buf_gen != e.buf->gen || e.buf_n != e.buf->n) {      // (reloaded since the graphs were captured: they hold freed pointers / the old size)
+    e.drop_graphs();
+    e.buf_gen = e.buf->gen; e.buf_n = e.buf->n;
+  }
+  const bool graphable = e.use_graph && !e.prof_on;
+  if (graphable && !e.graph_exec[1]) {
+    ORL_HIP(hipStreamBeginCapture(e.stream, hipStreamCaptureModeRelaxed));
+    const int rc = e.enqueue_step(0);
+    const hipError_t ce = hipStreamEndCapture(e.stream, &e.graph[1]);
+    if (rc) return -1;
+    if (ce != hipSuccess) return fail(std::string("graph capture: ") + hipGetErrorString(ce));
+    ORL_HIP(hipGraphInstantiate(&e.graph_exec[1], e.graph[1], nullptr, nullptr, 0));
+  }
+  struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+  } ev;
+  ORL_HIP(hipEventCreate(&ev.a));
+  ORL_HIP(hipEventCreate(&ev.b));
+  if (e.prof_on) { e.prof.clear(); e.ev_used = 0; }
+  ORL_HIP(hipEventRecord(ev.a, e.stream));
+  for (long s = 0; s < n_steps; ++s) {
+    if (graphable) { ORL_HIP(hipGraphLaunch(e.graph_exec[1], e.stream)); }
+    else if (e.enqueue_step(0)) return -1;
+    e.step_host++;
+  }
+  ORL_HIP(hipEventRecord(ev.b, e.stream));
+  ORL_HIP(hipStreamSynchronize(e.stream));
+  float ms = 0.f;
+  ORL_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+  if (elapsed_ms) *elapsed_ms = ms;
+  std::vector<float> m(e.R * e.nm);
+  ORL_HIP(hipMemcpy(m.data(), e.metrics_sum, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
+  if (metrics_mean) {
+    for (int r = 0; r < e.R; ++r)
+      for (int k = 0; k < ORL_MAX_METRICS; ++k) metrics_mean[r * ORL_MAX_METRICS + k] = k < e.nm ? m[r * e.nm + k] / (float)n_steps : 0.f;
   }
   unsigned int bad = 0;
   if (e.health_update(m.data(), n_steps, &bad)) return -1;

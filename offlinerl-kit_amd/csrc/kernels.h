@@ -1604,4 +1604,107 @@ __global__ void k_mobile_td_loss(MobileTdP p) {
   grad_scale_publish(amax, sh, p.gs_out, r);
 }
 
+// ================================================================================================
+// RCSL (policy/rcsl/rcsl.py:123-151): pred = MLP([obs | rtg]), loss = mean((pred - act)^2)
+// ================================================================================================
+// where an ordered epoch (orl_learn_epoch) stands: written by the host before the epoch's first step, read by every step's prepare launch,
+// so one captured step graph serves every step of every epoch
+struct EpochCell {
+  unsigned long long base;    // value of the step counter at the epoch's first step: position = *gstep - base
+  long long n_steps;          // steps of the epoch (order_len / B); a position beyond it yields padding rows only
+  long long order_len;        // entries per run
+};
+// the step's inputs in one launch: batch slots, the input matrix X = (obs | rtg | 0-pad) and the recorded row indices.  The index of batch
+// row b comes from MODE: RI_SLOTS the batch slots hold the rows already (orl_step: nothing is gathered, no index is recorded), RI_DRAWN
+// orl_draw_index as in k_prepare (orl_learn_n), RI_ORDER entry position * B + b of the run's row order (orl_learn_epoch; negative = padding:
+// the row reads dataset row 0 and keeps its negative index in d_idx, which k_rcsl_loss masks by).
+// grid (ceil(B * W / 256), R) with W = max(XP, AP); one thread per (batch row, column).
+enum { RI_SLOTS = 0, RI_DRAWN = 1, RI_ORDER = 2 };
+struct RcslPrepP {
+  const float *d_obs, *d_act, *d_rtg; long n; int OP, AP;      // dataset (rtg in the buffer's reward column)
+  float* b_obs; long bo_rs; float* b_act; long ba_rs; float* b_rtg; long br_rs;
+  float* X; long x_rs; int XP;
+  long long* idx_out;                                          // [R][B]
+  const long long* order; const EpochCell* cell;               // RI_ORDER
+  int B, od, W;
+  unsigned long long seed; const unsigned long long* gstep;
+};
+template <int MODE>
+__global__ void k_rcsl_prepare(RcslPrepP p) {
+  const int r = blockIdx.y;
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;
+  const int b = (int)(u / p.W), c = (int)(u - (long)b * p.W);
+  if (b >= p.B) return;
+  float* x = p.X + (long)r * p.x_rs + (long)b * p.XP;
+  float* bo = p.b_obs + (long)r * p.bo_rs + (long)b * p.OP;
+  float* brt = p.b_rtg + (long)r * p.br_rs + b;
+  if (MODE == RI_SLOTS) {
+    if (c < p.XP) x[c] = c < p.od ? bo[c] : (c == p.od ? *brt : 0.f);
+    return;
+  }
+  long long j;
+  if (MODE == RI_DRAWN) j = orl_draw_index(p.seed, r, b, *p.gstep, p.n);
+  else {
+    const unsigned long long pos = *p.gstep - p.cell->base;
+    j = pos < (unsigned long long)p.cell->n_steps ? p.order[(long)r * p.cell->order_len + (long)pos * p.B + b] : -1;
+    if (j >= p.n) j = -1;                                      // (refused by the host before the epoch starts; never read out of bounds)
+  }
+  const long row = j < 0 ? 0 : (long)j;
+  if (c < p.XP) {
+    const float v = c < p.od ? p.d_obs[row * p.OP + c] : 0.f;
+    const float t = p.d_rtg[row];
+    x[c] = c == p.od ? t : v;
+    if (c < p.OP) bo[c] = v;
+    if (c == 0) { *brt = t; p.idx_out[(long)r * p.B + b] = j; }
+  }
+  if (c < p.AP) p.b_act[(long)r * p.ba_rs + (long)b * p.AP + c] = p.d_act[row * p.AP + c];
+}
+
+// one checking launch over a device-resident row order: bit 0 an entry >= n, bit 1 a step whose rows are all padding.  grid (n_steps, R)
+__global__ void k_order_check(const long long* order, long order_len, int B, long n, unsigned int* flags) {
+  __shared__ int any_valid;
+  if (threadIdx.x == 0) any_valid = 0;
+  __syncthreads();
+  const long long* o = order + (long)blockIdx.y * order_len + (long)blockIdx.x * B;
+  bool bad = false, valid = false;
+  for (int b = threadIdx.x; b < B; b += 256) { bad = bad || o[b] >= n; valid = valid || o[b] >= 0; }
+  if (bad) atomicOr(flags, 1u);
+  if (valid) any_valid = 1;
+  __syncthreads();
+  if (threadIdx.x == 0 && !any_valid) atomicOr(flags, 2u);
+}
+
+// loss = sum over valid rows and act_dim of (pred - act)^2 / (valid_rows * A); dpred = 2 (pred - act) / (valid_rows * A), zero on padding
+// rows (idx < 0; idx == nullptr: every row is valid).  grid (R), block 256.
+struct RcslLossP {
+  const float* pred; long pred_rs;      // [R][B][A]
+  const float* act; long act_rs; int apitch;
+  float* dpred;                         // [R][B][A]
+  const long long* idx;                 // [R][B] recorded row indices, or null
+  int B, A; MetricsP m; int slot;
+  float* gs_out;                        // split precision: dynamic scale of dpred [R], or null
+};
+__global__ void k_rcsl_loss(RcslLossP p) {
+  __shared__ float sh[4];
+  const int r = blockIdx.x;
+  const long long* idx = p.idx ? p.idx + (long)r * p.B : nullptr;
+  float nv = 0.f;                       // (a count below 2^24: exact in fp32)
+  for (int b = threadIdx.x; b < p.B; b += 256) nv += (!idx || idx[b] >= 0) ? 1.0f : 0.0f;
+  nv = block_sum256(nv, sh);
+  const float cnt = nv * (float)p.A;
+  float s = 0.f, amax = 0.f;
+  for (int e = threadIdx.x; e < p.B * p.A; e += 256) {
+    const int b = e / p.A, a = e - b * p.A;
+    const bool valid = !idx || idx[b] >= 0;
+    const float d = p.pred[(long)r * p.pred_rs + e] - p.act[(long)r * p.act_rs + (long)b * p.apitch + a];
+    const float g = valid ? 2.0f * d / cnt : 0.f;
+    if (valid) s += d * d;
+    p.dpred[(long)r * p.pred_rs + e] = g;
+    amax = fmaxf(amax, fabsf(g));
+  }
+  s = block_sum256(s, sh);
+  if (threadIdx.x == 0) metric_set(p.m, r, p.slot, cnt > 0.f ? s / cnt : 0.f);
+  grad_scale_publish(amax, sh, p.gs_out, r);
+}
+
 }  // namespace orl

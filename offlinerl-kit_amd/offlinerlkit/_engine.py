@@ -16,9 +16,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "liborlengine.so")
 
-ALGO_CQL, ALGO_IQL, ALGO_TD3BC, ALGO_EDAC, ALGO_SAC, ALGO_MCQ, ALGO_MOBILE = 0, 1, 2, 3, 4, 5, 6
+ALGO_CQL, ALGO_IQL, ALGO_TD3BC, ALGO_EDAC, ALGO_SAC, ALGO_MCQ, ALGO_MOBILE, ALGO_RCSL = 0, 1, 2, 3, 4, 5, 6, 7
 ALGO_ID = {"cql": ALGO_CQL, "iql": ALGO_IQL, "td3bc": ALGO_TD3BC, "edac": ALGO_EDAC, "sac": ALGO_SAC, "mcq": ALGO_MCQ,
-           "mobile": ALGO_MOBILE}
+           "mobile": ALGO_MOBILE, "rcsl": ALGO_RCSL}
 MAX_HIDDEN, MAX_METRICS, MAX_NOISE = 4, 8, 6
 NET_ACTOR, NET_CRITIC1, NET_CRITIC2, NET_CRITIC1_OLD, NET_CRITIC2_OLD, NET_CRITIC_V, NET_ACTOR_OLD, NET_VAE_ENC, NET_VAE_DEC = range(9)
 NUM_NETS = 9
@@ -60,6 +60,8 @@ ABI_SYMBOLS = [
     "orl_dynadv_configure", "orl_dynadv_forward", "orl_dynadv_update", "orl_dynadv_adam_get", "orl_dynadv_adam_set",
     # MOBILE: next-state samples of the dynamics, their hand-over to the policy engine, compute_lcb alone
     "orl_dynsample_next", "orl_engine_set_next_samples", "orl_engine_lcb_penalty",
+    # RCSL: one ordered pass over the attached buffer
+    "orl_learn_epoch",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -179,6 +181,7 @@ def load_library(path: Optional[str] = None):
     lib.orl_engine_attach_model_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32]
     lib.orl_step.argtypes = [C.c_void_p, C.POINTER(OrlBatch), C.POINTER(OrlNoise), C.c_void_p]
     lib.orl_learn_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    lib.orl_learn_epoch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_engine_set_next_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_lcb_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_health.argtypes = [C.c_void_p, C.c_void_p]
@@ -422,7 +425,9 @@ class Engine:
         if batch is not None:
             b = OrlBatch()
             for k in ("observations", "actions", "next_observations", "rewards", "terminals"):
-                v = batch[k]
+                v = batch.get(k)
+                if v is None:                    # (RCSL engines read neither next_observations nor terminals; any other engine refuses NULL)
+                    continue
                 if on_device:
                     setattr(b, k, int(v))
                 else:
@@ -472,6 +477,23 @@ class Engine:
         m = np.zeros((self.n_runs, MAX_METRICS), dtype=np.float32)
         ms = C.c_float()
         self._check_step(self.lib.orl_learn_n(self._h, n_steps, m.ctypes.data, C.byref(ms)), "orl_learn_n")
+        return m[:, :len(self.metric_names)], ms.value
+
+    def learn_epoch(self, order, on_device=False):
+        """RCSL: one ordered pass (orl_learn_epoch).  ``order``: int64 [n_runs][order_len] host array, or with ``on_device`` a
+        ``(device pointer, order_len)`` pair; negative entries are padding.  Returns (mean metrics [n_runs][n_metrics], elapsed ms)."""
+        if on_device:
+            ptr, order_len = int(order[0]), int(order[1])
+        else:
+            a = np.ascontiguousarray(order, dtype=np.int64)
+            if a.ndim == 1:
+                a = np.ascontiguousarray(np.broadcast_to(a, (self.n_runs, a.shape[0])))
+            if a.ndim != 2 or a.shape[0] != self.n_runs:
+                raise ValueError(f"order: expected [n_runs = {self.n_runs}, order_len], got {a.shape}")
+            ptr, order_len = a.ctypes.data, int(a.shape[1])
+        m = np.zeros((self.n_runs, MAX_METRICS), dtype=np.float32)
+        ms = C.c_float()
+        self._check_step(self.lib.orl_learn_epoch(self._h, ptr, order_len, 1 if on_device else 0, m.ctypes.data, C.byref(ms)), "orl_learn_epoch")
         return m[:, :len(self.metric_names)], ms.value
 
     # ---- health (include/orl_engine.h: ORL_HEALTH_*) ----

@@ -148,6 +148,23 @@ class Critic(nn.Module):
         return self.last(self.backbone(x))
 
 
+class RcslModule(nn.Module):
+    """Return-conditioned policy network: backbone([obs | rtg]) (modules/rcsl_module.py:8-33).  The backbone is an ``MLP`` built with
+    ``output_dim = act_dim``: its last Linear is the output layer, so the state_dict keys are ``backbone.model.{0,2,...,2L}.*``."""
+
+    def __init__(self, backbone: nn.Module, device: str = "cpu") -> None:
+        super().__init__()
+        self.device = torch.device(device)
+        self.backbone = backbone.to(device)
+
+    def forward(self, obs: Union[np.ndarray, torch.Tensor], rtg: Union[np.ndarray, torch.Tensor]) -> torch.Tensor:
+        obs = _as_input(obs, self.device)
+        rtg = _as_input(rtg, self.device)
+        if rtg.dim() == 1:
+            rtg = rtg.unsqueeze(-1)
+        return self.backbone(torch.cat([obs, rtg], dim=-1))
+
+
 class EnsembleCritic(nn.Module):
     """K parallel critic MLPs built from EnsembleLinear; output (K, B, 1) (ensemble_critic_module.py:11-44)."""
 

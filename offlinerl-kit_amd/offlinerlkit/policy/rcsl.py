@@ -1,0 +1,139 @@
+"""RCSL policy (reference: policy/rcsl/rcsl.py:18-163) on the HIP engine: pred = MLP([obs | rtg]), MSE on the dataset action.
+
+The return-to-go travels where the other algorithms carry the reward (``orl_batch.rewards``, the ``rew`` column of a ``DeviceBuffer``).
+``learn_epoch`` is the reference trainer's inner loop -- one pass over a shuffled dataset, every row once, last batch partial -- as one
+engine call over a caller-supplied row order (``orl_learn_epoch``).  ``rollout()`` needs the diffusion behaviour policy and is not here.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _engine
+from .base_policy import EnginePolicy, _adam_hyper, _backbone_dims
+
+
+def epoch_order(n_rows: int, batch_size: int, n_runs: int = 1, generator: Optional[torch.Generator] = None) -> np.ndarray:
+    """Row order of one epoch, int64 [n_runs, ceil(n_rows / B) * B]: one ``torch.randperm(n_rows)`` per run (the index stream of a
+    ``DataLoader(shuffle=True)`` sampler, drawn in run order from the global generator unless one is given), padded at the tail with -1."""
+    steps = -(-int(n_rows) // int(batch_size))
+    order = np.full((int(n_runs), steps * int(batch_size)), -1, dtype=np.int64)
+    for r in range(int(n_runs)):
+        order[r, :n_rows] = torch.randperm(int(n_rows), generator=generator).numpy()
+    return order
+
+
+class RcslPolicy(EnginePolicy):
+    ALGO = "rcsl"
+
+    def __init__(self, dynamics, rollout_policy, rcsl: nn.Module, rcsl_optim: torch.optim.Optimizer, device="cpu") -> None:
+        super().__init__()
+        self.dynamics = dynamics
+        self.rollout_policy = rollout_policy
+        self.rcsl = rcsl
+        self.rcsl_optim = rcsl_optim
+        self.device = device
+        _adam_hyper(rcsl_optim)
+        self._dims()
+
+    def _dims(self):
+        in_dim, outs = _backbone_dims(self.rcsl.backbone)
+        if len(outs) < 2:
+            raise NotImplementedError("RcslPolicy expects MLP(obs_dim + 1, hidden_dims, output_dim=act_dim): at least one hidden layer and the output layer")
+        hidden, act_dim = outs[:-1], outs[-1]
+        if len(hidden) > _engine.MAX_HIDDEN:
+            raise NotImplementedError(f"the HIP engine supports up to {_engine.MAX_HIDDEN} hidden layers, the backbone has {len(hidden)}")
+        n_mods = len(list(self.rcsl.backbone.model))
+        if n_mods != 2 * len(hidden) + 1 or getattr(self.rcsl.backbone, "activation_cls", nn.ReLU) is not nn.ReLU:
+            raise NotImplementedError("RcslPolicy expects a [Linear, ReLU] x L + Linear backbone")
+        return in_dim - 1, act_dim, hidden
+
+    def _nets(self):
+        return {_engine.NET_ACTOR: self.rcsl}
+
+    def _optims(self):
+        return {_engine.OPT_ACTOR: self.rcsl_optim}
+
+    def _config(self) -> Dict:
+        od, ad, hidden = self._dims()
+        return dict(obs_dim=od, act_dim=ad, hidden=hidden, actor_lr=float(self.rcsl_optim.param_groups[0]["lr"]))
+
+    def rollout(self, init_obss, rollout_length):
+        raise NotImplementedError("RcslPolicy.rollout needs the diffusion behaviour policy, which this package does not have")
+
+    def learn(self, batch: Dict) -> Dict[str, float]:
+        """One gradient step on ``{"observations", "actions", "rtgs"}``: [B, ...] arrays shared by every run or [n_runs, B, ...]."""
+        R = self._n_runs
+        obs = batch["observations"]
+        if np.ndim(obs) not in (2, 3):
+            raise ValueError(f"observations: expected [B, obs_dim] or [n_runs, B, obs_dim], got shape {tuple(obs.shape)}")
+        B = int(obs.shape[-2])
+        self._bind(B)
+        dev = self._arena.device
+        keep, ptrs = [], {}
+        for k, name, cols in (("observations", "observations", None), ("actions", "actions", None), ("rewards", "rtgs", 1)):
+            t = torch.as_tensor(batch[name], dtype=torch.float32, device=dev)
+            if cols == 1 and (t.dim() == 1 or (t.dim() == 2 and t.shape[-1] != 1)):
+                t = t.unsqueeze(-1)                          # rtgs as [B] / [n_runs, B]
+            if t.dim() == 2:
+                t = t.unsqueeze(0).expand(R, *t.shape)
+            elif t.dim() != 3 or t.shape[0] != R:
+                raise ValueError(f"{name}: shape {tuple(t.shape)} is neither [rows, cols] nor [n_runs = {R}, rows, cols]")
+            if t.shape[1] != B:
+                raise ValueError(f"{name}: {t.shape[1]} rows, observations have {B}")
+            t = t.contiguous()
+            keep.append(t)
+            ptrs[k] = t.data_ptr()
+        self._push_lrs()
+        torch.cuda.current_stream(dev).synchronize()
+        return self._result(self._eng.step(ptrs, None, on_device=True))
+
+    def learn_epoch(self, device_buffer, order, batch_size: int = 256) -> Dict[str, float]:
+        """One ordered pass over ``device_buffer`` (rtgs in its reward column): step s of run r learns rows
+        ``order[r, s * B : (s + 1) * B]``, negative entries are padding (``epoch_order`` builds such an order).  ``order``: int64
+        [n_runs, len] (or [len], shared by the runs) numpy array, or a torch tensor on the engine's device.  Returns the per-key means
+        over the steps -- what ``logger.logkv_mean`` per batch holds at the end of the reference's epoch."""
+        self._bind(int(batch_size))
+        if self._attached is not device_buffer:
+            self._eng.attach_buffer(device_buffer)
+            self._attached = device_buffer
+        self._push_lrs()
+        if isinstance(order, torch.Tensor) and order.device.type == "cuda":
+            o = order.to(dtype=torch.int64)
+            if o.dim() == 1:
+                o = o.unsqueeze(0).expand(self._n_runs, -1)
+            if o.dim() != 2 or o.shape[0] != self._n_runs:
+                raise ValueError(f"order: expected [n_runs = {self._n_runs}, order_len], got {tuple(o.shape)}")
+            o = o.contiguous()
+            torch.cuda.current_stream(o.device).synchronize()
+            m, ms = self._eng.learn_epoch((o.data_ptr(), int(o.shape[1])), on_device=True)
+        else:
+            m, ms = self._eng.learn_epoch(order.cpu().numpy() if isinstance(order, torch.Tensor) else order)
+        self.last_learn_epoch_ms = ms
+        return self._result(m)
+
+    def select_action(self, obs: np.ndarray, rtg) -> np.ndarray:
+        with torch.no_grad():
+            action = self.rcsl.forward(obs, rtg)
+        return action.cpu().numpy()
+
+    def select_action_runs(self, obs: np.ndarray, rtg: np.ndarray) -> np.ndarray:
+        """Actions of EVERY run in one batched forward: ``obs`` [n_runs, E, obs_dim], ``rtg`` [n_runs, E] or [n_runs, E, 1]"""
+        if self._eng is None:
+            raise RuntimeError("select_action_runs before the first learn(): no engine is bound yet")
+        P = self._stacked_net(_engine.NET_ACTOR)
+        with torch.no_grad():
+            o = torch.as_tensor(np.asarray(obs, dtype=np.float32), device=self._arena.device)
+            g = torch.as_tensor(np.asarray(rtg, dtype=np.float32), device=self._arena.device)
+            if g.dim() == 2:
+                g = g.unsqueeze(-1)
+            h = torch.cat([o, g], dim=-1)
+            idx = sorted(int(k[len("backbone.model."):-len(".weight")]) for k in P if k.endswith(".weight"))
+            for n, i in enumerate(idx):
+                h = torch.baddbmm(P[f"backbone.model.{i}.bias"].unsqueeze(1), h, P[f"backbone.model.{i}.weight"].transpose(1, 2))
+                if n + 1 < len(idx):
+                    h = torch.relu(h)
+            return h.cpu().numpy()

@@ -24,6 +24,9 @@ split by ``real_ratio`` and one ``policy.learn({"real": ..., "fake": ...})``.  T
 ``dynamics.save`` are the reference's; evaluation, the multi-run ``run<i>/...`` keys and the per-run checkpoints are MFPolicyTrainer's.
 ``MBPolicyTrainer(fused=True)`` keeps the model buffer in an HBM ring and runs an epoch as device rollouts at the reference's
 timesteps with ONE ``policy.learn_n`` between two of them (``fused_mb_schedule``).
+
+RcslPolicyTrainer (reference: offlinerlkit/policy_trainer/rcsl_policy_trainer.py:21-365) is at the end of the module: one shuffled pass
+over the dataset per epoch, in-process batches (``fused=False``) or one ``policy.learn_epoch`` on the device (``fused=True``).
 """
 from __future__ import annotations
 
@@ -496,5 +499,219 @@ class MBPolicyTrainer(MFPolicyTrainer):
                 done_eps.append({"episode_reward": ep_reward, "episode_length": ep_len})
                 ep_reward, ep_len = 0, 0
                 obs = reset()
+        return {"eval/episode_reward": [d["episode_reward"] for d in done_eps],
+                "eval/episode_length": [d["episode_length"] for d in done_eps]}
+
+
+class DictDataset(torch.utils.data.Dataset):
+    """A dict of equally long arrays as a map-style dataset: item i is ``{key: array[i]}`` (reference: utils/dataset.py DictDataset)."""
+
+    def __init__(self, dataset: Dict[str, np.ndarray]) -> None:
+        self._data = dict(dataset)
+        self._len = len(next(iter(self._data.values())))
+
+    def __len__(self) -> int:
+        return self._len
+
+    def __getitem__(self, idx):
+        return {k: v[idx] for k, v in self._data.items()}
+
+
+class RcslPolicyTrainer:
+    """RcslPolicyTrainer (reference: offlinerlkit/policy_trainer/rcsl_policy_trainer.py:21-365): per epoch ONE pass over the shuffled
+    dataset -- every row once, last batch partial --, ``lr_scheduler.step()``, evaluation conditioned on ``goal`` (the return-to-go starts at
+    ``goal`` and drops by every reward), the reference's logged keys in its order, ``checkpoint_dir/policy.pth`` each epoch and
+    ``model_dir/policy.pth`` at the end.  ``offline_ratio`` 0 trains on ``rollout_dataset``, 1 on ``offline_dataset``; anything else is refused.
+
+    ``fused=False``: the batches of a shuffled ``DataLoader`` drawn in this process (``num_workers`` is accepted and ignored: no worker
+    process is ever started), each through ``policy.learn``.  ``fused=True`` (the default when the policy has ``learn_epoch`` and a GPU is
+    visible): the dataset is loaded once into a ``DeviceBuffer`` with ``rtgs`` in its reward column, and an epoch is one ``torch.randperm``
+    per run, padded with -1 to a multiple of the batch size, and one ``policy.learn_epoch``."""
+
+    def __init__(self, policy, eval_env, offline_dataset: Dict[str, np.ndarray], rollout_dataset: Dict[str, np.ndarray], goal: float, logger,
+                 seed, eval_env2=None, epoch: int = 1000, step_per_epoch: int = 1000, batch_size: int = 256, offline_ratio: float = 0,
+                 eval_episodes: int = 10, lr_scheduler=None, horizon: Optional[int] = None, num_workers=1,
+                 fused: Optional[bool] = None) -> None:
+        self.policy = policy
+        self.eval_env = eval_env
+        self.eval_env2 = eval_env2
+        self.horizon = horizon
+        self.offline_dataset = offline_dataset
+        self.rollout_dataset = rollout_dataset
+        self.goal = goal
+        self.logger = logger
+        self._epoch = epoch
+        self._step_per_epoch = step_per_epoch
+        self._batch_size = batch_size
+        self._offline_ratio = offline_ratio
+        self._eval_episodes = eval_episodes
+        self.lr_scheduler = lr_scheduler
+        self.num_workers = num_workers
+        self.env_seed = seed
+        self.is_gymnasium_env = hasattr(self.eval_env, "get_true_observation")
+        assert (not self.is_gymnasium_env) or (self.horizon is not None), "Horizon must be specified for Gymnasium env"
+        if fused is None:
+            fused = hasattr(policy, "learn_epoch") and torch.cuda.is_available()
+        self._fused = bool(fused)
+        self._dbuf = None
+
+    def _dataset(self) -> Dict[str, np.ndarray]:
+        if self._offline_ratio == 0:
+            return self.rollout_dataset
+        if self._offline_ratio == 1:
+            return self.offline_dataset
+        raise NotImplementedError
+
+    def _device_buffer(self, data: Dict[str, np.ndarray]):
+        from . import _engine
+        obs = np.asarray(data["observations"], dtype=np.float32)
+        act = np.asarray(data["actions"], dtype=np.float32)
+        n = len(obs)
+        nxt = np.asarray(data["next_observations"], dtype=np.float32) if "next_observations" in data else obs
+        term = np.asarray(data["terminals"], dtype=np.float32).reshape(n) if "terminals" in data else np.zeros(n, np.float32)
+        dev = torch.cuda.current_device()
+        pdev = getattr(getattr(self.policy, "rcsl", None), "device", None)
+        if pdev is not None and torch.device(pdev).type == "cuda" and torch.device(pdev).index is not None:
+            dev = torch.device(pdev).index
+        buf = _engine.DeviceBuffer(obs.shape[1], act.shape[1], dev)
+        buf.load(obs, act, nxt, np.asarray(data["rtgs"], dtype=np.float32).reshape(n), term)      # rtgs travel in the reward column
+        return buf
+
+    def _train_epoch(self, data: Dict[str, np.ndarray], loader) -> int:
+        from .policy.rcsl import epoch_order
+        if self._fused:
+            n = len(data["observations"])
+            order = epoch_order(n, self._batch_size, int(getattr(self.policy, "n_runs", 1)))
+            means = self.policy.learn_epoch(self._dbuf, order, self._batch_size)
+            for k, v in means.items():
+                self.logger.logkv(k, v)
+            return order.shape[1] // self._batch_size
+        steps = 0
+        for batch in loader:
+            loss_dict = self.policy.learn(batch)
+            for k, v in loss_dict.items():
+                self.logger.logkv_mean(k, v)
+            steps += 1
+        return steps
+
+    def train(self) -> Dict[str, float]:
+        start_time = time.time()
+        num_timesteps = 0
+        last_10_performance = deque(maxlen=10)
+        data = self._dataset()
+        loader = None
+        if self._fused:
+            self._dbuf = self._device_buffer(data)
+        else:
+            # the reference's DataLoader(shuffle=True) with the batches collated in THIS process: num_workers = 0 whatever was asked for
+            loader = torch.utils.data.DataLoader(DictDataset(data), batch_size=self._batch_size, shuffle=True, num_workers=0)
+        for e in range(1, self._epoch + 1):
+            self.policy.train()
+            num_timesteps += self._train_epoch(data, loader)
+            if self.lr_scheduler is not None:
+                self.lr_scheduler.step()
+            check = getattr(self.policy, "check_health", None)
+            if callable(check):
+                check()
+            eval_info = self._evaluate()
+            ep_reward_mean, ep_reward_std = np.mean(eval_info["eval/episode_reward"]), np.std(eval_info["eval/episode_reward"])
+            ep_reward_max, ep_reward_min = np.max(eval_info["eval/episode_reward"]), np.min(eval_info["eval/episode_reward"])
+            ep_length_mean, ep_length_std = np.mean(eval_info["eval/episode_length"]), np.std(eval_info["eval/episode_length"])
+            normalized = hasattr(self.eval_env, "get_normalized_score")
+            if not normalized:
+                last_10_performance.append(ep_reward_mean)
+                self.logger.logkv("eval/episode_reward", ep_reward_mean)
+                self.logger.logkv("eval/episode_reward_std", ep_reward_std)
+            else:
+                norm_ep_rew_mean = self.eval_env.get_normalized_score(ep_reward_mean) * 100
+                last_10_performance.append(norm_ep_rew_mean)
+                self.logger.logkv("eval/normalized_episode_reward", norm_ep_rew_mean)
+                self.logger.logkv("eval/normalized_episode_reward_std", self.eval_env.get_normalized_score(ep_reward_std) * 100)
+                self.logger.logkv("eval/normalized_episode_reward_max", self.eval_env.get_normalized_score(ep_reward_max) * 100)
+                self.logger.logkv("eval/normalized_episode_reward_min", self.eval_env.get_normalized_score(ep_reward_min) * 100)
+            self.logger.logkv("eval/episode_length", ep_length_mean)
+            self.logger.logkv("eval/episode_length_std", ep_length_std)
+            if self.eval_env2 is not None:
+                info2 = self._evaluate_no_fix_seed()
+                rew2_mean, rew2_std = np.mean(info2["eval/episode_reward"]), np.std(info2["eval/episode_reward"])
+                len2_mean, len2_std = np.mean(info2["eval/episode_length"]), np.std(info2["eval/episode_length"])
+                # (the reference appends the FIXED-seed figure a second time here, rcsl_policy_trainer.py:167,173: kept)
+                if not normalized:
+                    last_10_performance.append(ep_reward_mean)
+                    self.logger.logkv("eval/episode_reward_no_fix_seed", rew2_mean)
+                    self.logger.logkv("eval/episode_reward_std_no_fix_seed", rew2_std)
+                else:
+                    last_10_performance.append(norm_ep_rew_mean)
+                    self.logger.logkv("eval/normalized_episode_reward_no_fix_seed", self.eval_env.get_normalized_score(rew2_mean) * 100)
+                    self.logger.logkv("eval/normalized_episode_reward_std_no_fix_seed", self.eval_env.get_normalized_score(rew2_std) * 100)
+                self.logger.logkv("eval/episode_length_no_fix_seed", len2_mean)
+                self.logger.logkv("eval/episode_length_std_no_fix_seed", len2_std)
+            self.logger.set_timestep(num_timesteps)
+            self.logger.dumpkvs(exclude=["dynamics_training_progress"])
+            torch.save(self.policy.state_dict(), os.path.join(self.logger.checkpoint_dir, "policy.pth"))
+        self.logger.log("total time: {:.2f}s".format(time.time() - start_time))
+        torch.save(self.policy.state_dict(), os.path.join(self.logger.model_dir, "policy.pth"))
+        self.logger.close()
+        return {"last_10_performance": np.mean(last_10_performance)}
+
+    def _evaluate(self) -> Dict[str, List[float]]:
+        self.eval_env.reset(seed=self.env_seed)      # fixed seed, every epoch (rcsl_policy_trainer.py:197)
+        return self._rollout_eval(self.eval_env)
+
+    def _evaluate_no_fix_seed(self) -> Dict[str, List[float]]:
+        assert self.eval_env2 is not None
+        return self._rollout_eval(self.eval_env2)
+
+    def _rollout_eval(self, env) -> Dict[str, List[float]]:
+        """the evaluation loop of ``_evaluate`` / ``_evaluate_no_fix_seed`` (rcsl_policy_trainer.py:199-276, 288-365)"""
+        gymnasium = self.is_gymnasium_env
+
+        def reset():
+            if gymnasium:
+                o, _ = env.reset()
+                return env.get_true_observation(o)
+            return env.reset()
+
+        def step(action):
+            if hasattr(env, "get_true_observation"):
+                nxt, reward, terminal, _, _ = env.step(action.flatten())
+            else:
+                nxt, reward, terminal, _ = env.step(action.flatten())
+            if gymnasium:
+                nxt = env.get_true_observation(nxt)
+            return nxt, reward, terminal
+
+        def goal():
+            return torch.tensor([[self.goal]]).type(torch.float32)
+
+        self.policy.eval()
+        obs = reset()
+        done_eps = []
+        episode_reward, episode_length = 0, 0
+        if gymnasium:      # fixed-horizon episodes, the terminal flag is not consulted
+            while len(done_eps) < self._eval_episodes:
+                rtg = goal()
+                for _ in range(self.horizon):
+                    action = self.policy.select_action(obs.reshape(1, -1), rtg)
+                    obs, reward, _ = step(action)
+                    episode_reward += reward
+                    rtg = rtg - reward
+                    episode_length += 1
+                done_eps.append({"episode_reward": episode_reward, "episode_length": episode_length})
+                episode_reward, episode_length = 0, 0
+                obs = reset()
+        else:
+            rtg = goal()
+            while len(done_eps) < self._eval_episodes:
+                action = self.policy.select_action(obs.reshape(1, -1), rtg)
+                obs, reward, terminal = step(action)
+                episode_reward += reward
+                rtg = rtg - reward
+                episode_length += 1
+                if terminal:
+                    done_eps.append({"episode_reward": episode_reward, "episode_length": episode_length})
+                    episode_reward, episode_length = 0, 0
+                    obs = reset()
+                    rtg = goal()
         return {"eval/episode_reward": [d["episode_reward"] for d in done_eps],
                 "eval/episode_length": [d["episode_length"] for d in done_eps]}

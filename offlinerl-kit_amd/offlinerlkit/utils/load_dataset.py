@@ -123,3 +123,49 @@ def load_dataset_file(path: str) -> Dict[str, np.ndarray]:
         with h5py.File(path, "r") as f:
             return {k: f[k][()] for k in ("observations", "actions", "rewards", "terminals", "timeouts", "next_observations") if k in f}
     raise ValueError(f"unsupported dataset file {path!r} (.npz or .hdf5)")
+
+
+def discount_cumsum(x: np.ndarray, gamma: float = 1.0) -> np.ndarray:
+    """Return-to-go of a reward sequence (reference: offlinerlkit/utils/cumsum.py:3-11): out[t] = x[t] + gamma * out[t + 1], accumulated
+    from the end in the dtype of ``x`` like the reference's loop."""
+    x = np.asarray(x)
+    out = np.zeros_like(x)
+    if x.shape[0] == 0:
+        return out
+    out[-1] = x[-1]
+    for t in reversed(range(x.shape[0] - 1)):
+        out[t] = x[t] + gamma * out[t + 1]
+    return out
+
+
+def traj_rtg_datasets(env=None, input_path: Optional[str] = None, data_path: Optional[str] = None,
+                      dataset: Optional[Dict[str, np.ndarray]] = None):
+    """Trajectory dataset with returns-to-go for the RCSL policies (reference: load_dataset.py:232-313): the transitions are split into
+    episodes at terminals / timeouts (without a ``timeouts`` field: every 1000 steps), each episode gets ``rtgs`` = the undiscounted
+    reward-to-go, and the incomplete last trajectory is dropped.  Returns ``(dataset, init_obss, max_return)``; ``dataset`` has
+    observations / next_observations / actions / rewards / rtgs / terminals in the source dtypes.  ``dataset=`` skips ``env.get_dataset``;
+    ``data_path`` pickles the list of episodes like the reference."""
+    if dataset is None:
+        dataset = env.get_dataset(h5path=input_path)
+    keys = ["observations", "next_observations", "actions", "rewards", "terminals"]
+    n = dataset["rewards"].shape[0]
+    use_timeouts = "timeouts" in dataset
+    paths = []
+    start, episode_step = 0, 0
+    for i in range(n):
+        final = bool(dataset["timeouts"][i]) if use_timeouts else (episode_step == 1000 - 1)
+        if bool(dataset["terminals"][i]) or final:
+            episode_step = 0
+            ep = {k: np.array([dataset[k][j] for j in range(start, i + 1)]) for k in keys}
+            ep["rtgs"] = discount_cumsum(ep["rewards"])
+            paths.append(ep)
+            start = i + 1
+        episode_step += 1
+    init_obss = np.array([p["observations"][0] for p in paths]).astype(np.float32)
+    returns = np.array([np.sum(p["rewards"]) for p in paths])
+    if data_path is not None:
+        import pickle
+        with open(data_path, "wb") as f:
+            pickle.dump(paths, f)
+    full = {k: np.concatenate([p[k] for p in paths], axis=0) for k in ["observations", "next_observations", "actions", "rewards", "rtgs", "terminals"]}
+    return full, init_obss, np.max(returns)
