@@ -63,6 +63,10 @@ extern "C" {
 #define ORL_ALGO_RCSL 7   /* policy/rcsl/rcsl.py:123-151: one net (ORL_NET_ACTOR) = MLP(obs_dim + 1, hidden, act_dim) of modules/rcsl_module.py, MSE on the
                            * dataset action, Adam with actor_lr / ORL_OPT_ACTOR; metric "loss".  The return-to-go travels where the other algorithms
                            * carry the reward: orl_batch.rewards and the `rew` column of an orl_buffer */
+#define ORL_ALGO_RCSL_GAUSS 8 /* policy/rcsl/rcsl_gauss.py:123-154: ORL_NET_ACTOR = MLP(obs_dim + 1, hidden, act_dim) -> z, then DiagGaussian(act_dim, act_dim,
+                           * unbounded, conditioned_sigma) of modules/dist_module.py:45-93: mu = W_mu z + b_mu, s = clamp(W_sigma z + b_sigma, -5, 2),
+                           * loss = mean((mu - a)^2 exp(-s)) + mean(s), Adam with actor_lr / ORL_OPT_ACTOR; metric "loss".  Inputs, buffers, orl_learn_epoch
+                           * and every refusal as for ORL_ALGO_RCSL */
 
 /* per-run health flags (orl_health).  The reference raises nothing when a run diverges (its losses simply turn nan); here a diverging run
  * can additionally be MASKED by the arithmetic -- the ReLU of the matrix kernels works on the integer view of the activations and maps a NaN
@@ -309,7 +313,7 @@ int orl_learn_n(orl_engine* e, int n_steps, float* metrics_mean, float* elapsed_
  * every epoch.  The row's index, padding included, is recorded per step (a padding row reads row 0 of the dataset).
  * metrics_mean: host [n_runs][ORL_MAX_METRICS], the unweighted mean over the order_len / B steps (logkv_mean per batch).
  * Refused before a step is launched: no buffer attached, order_len not a multiple of B, an entry >= the buffer's size (host orders are
- * checked on the host, device orders by one checking launch), a step whose rows are all padding, an engine that is not RCSL. */
+ * checked on the host, device orders by one checking launch), a step whose rows are all padding, an engine that is neither RCSL nor RCSL_GAUSS. */
 int orl_learn_epoch(orl_engine* e, const int64_t* order, int64_t order_len, int on_device,
                     float* metrics_mean, float* elapsed_ms);
 /* MOBILE: the next-state samples of the batch the NEXT orl_step learns, [n_runs][S * E * batch][obs_dim] in the row order of
@@ -338,7 +342,7 @@ int64_t orl_step_count(orl_engine* e);
 
 /* -- test / profiling taps --------------------------------------------------------- */
 /* copies an intermediate of the LAST step to host: returns number of floats written or <0.
- * names: "q1","q2","target_q","q1a","q2a","logp_a", ... (algorithm specific; RCSL: "pred", "rcsl_x" = [obs | rtg]); every engine also has the minibatch of the last
+ * names: "q1","q2","target_q","q1a","q2a","logp_a", ... (algorithm specific; RCSL: "pred", "rcsl_x" = [obs | rtg]; RCSL_GAUSS: "z", "mu", "logvar" (post-clamp), "rcsl_x"); every engine also has the minibatch of the last
  * step ("b_obs","b_nobs","b_act","b_rew","b_term": what ReplayBuffer.sample returned / the device sampler drew) and its noise
  * arrays under their orl_noise slot names ("n_eps_actor", ...). */
 int64_t orl_debug_read(orl_engine* e, int run, const char* name, float* host, int64_t cap);

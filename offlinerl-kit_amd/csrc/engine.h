@@ -49,7 +49,7 @@ struct NetLayout {
   long b_off[ORL_MAX_HIDDEN + 1] = {0};
   long w_ms[ORL_MAX_HIDDEN + 1] = {0};   // member strides
   long b_ms[ORL_MAX_HIDDEN + 1] = {0};
-  long extra_off = -1;                   // IQL sigma_param
+  long extra_off = -1;                   // IQL sigma_param; RCSL_GAUSS: the four DiagGaussian head tensors
   long size = 0;                         // floats of ONE net (ens: of the whole ensemble)
   long stride() const { return (size + 3) & ~3L; }   // arena stride: keeps every net 16-B aligned
   std::vector<TensorInfo> tensors;
@@ -343,6 +343,7 @@ struct Engine {
   int mcq_build(); int mcq_step();
   int mobile_build(); int mobile_step(); int mobile_penalty(int real_rows);
   int rcsl_build(); int rcsl_step(); int rcsl_prepare(int mode);
+  int rcslg_build(); int rcslg_step();
 };
 
 }  // namespace orl

@@ -35,7 +35,10 @@ static void add_tensor(NetLayout& l, const std::string& name, long off, std::ini
   l.tensors.push_back(t);
 }
 
-enum TailKind { TAIL_CRITIC, TAIL_TANH_GAUSS, TAIL_GAUSS, TAIL_DET, TAIL_LINEAR };
+enum TailKind { TAIL_CRITIC, TAIL_TANH_GAUSS, TAIL_GAUSS, TAIL_DET, TAIL_LINEAR, TAIL_LINEAR_GAUSS };
+
+// the two return-conditioned algorithms share inputs, buffers, the ordered epoch and every refusal
+static inline bool is_rcsl(int algo) { return algo == ORL_ALGO_RCSL || algo == ORL_ALGO_RCSL_GAUSS; }
 
 // seq_step: distance of consecutive Linear layers in the backbone's nn.Sequential -- 2 for [Linear, ReLU], 3 when every ReLU is followed by
 // nn.Dropout (nets/mlp.py:20-23): the state_dict keys are backbone.model.{0, 3, 6, ...} then
@@ -76,12 +79,21 @@ static NetLayout make_mlp_layout(int in_dim, const int* hidden, int L, TailKind 
     l.w_off[L] = off; add_tensor(l, "dist_net.mu.weight", off, {act_dim, d}); off += (long)act_dim * d;
     l.b_off[L] = off; add_tensor(l, "dist_net.mu.bias", off, {act_dim}); off += act_dim;
     l.extra_off = off; add_tensor(l, "dist_net.sigma_param", off, {act_dim, 1}); off += act_dim;
-  } else if (tail == TAIL_LINEAR) {
+  } else if (tail == TAIL_LINEAR || tail == TAIL_LINEAR_GAUSS) {
     // the output layer is the backbone's own last nn.Linear (nets/mlp.py with output_dim: RcslModule): no tanh, no distribution head
     const std::string n = "backbone.model." + std::to_string(seq_step * L);
     l.out_dim = act_dim;
     l.w_off[L] = off; add_tensor(l, n + ".weight", off, {act_dim, d}); off += (long)act_dim * d;
     l.b_off[L] = off; add_tensor(l, n + ".bias", off, {act_dim}); off += act_dim;
+    if (tail == TAIL_LINEAR_GAUSS) {
+      // RcslGaussianModule: that output is the latent z (act_dim wide) of DiagGaussian(act_dim, act_dim, conditioned_sigma): two A x A heads
+      // behind the body, unstacked and in the reference's state_dict order; k_rcslg_head reads them and writes their gradients (slab 0)
+      l.extra_off = off;
+      add_tensor(l, "dist_net.mu.weight", off, {act_dim, act_dim}); off += (long)act_dim * act_dim;
+      add_tensor(l, "dist_net.mu.bias", off, {act_dim}); off += act_dim;
+      add_tensor(l, "dist_net.sigma.weight", off, {act_dim, act_dim}); off += (long)act_dim * act_dim;
+      add_tensor(l, "dist_net.sigma.bias", off, {act_dim}); off += act_dim;
+    }
   } else {
     l.out_dim = act_dim;
     l.w_off[L] = off; add_tensor(l, "last.weight", off, {act_dim, d}); off += (long)act_dim * d;
@@ -187,6 +199,8 @@ static int build_layouts(const orl_config& c, NetLayout* lay, long* net_off, boo
     target(ORL_NET_CRITIC1_OLD, ens);
   } else if (c.algo == ORL_ALGO_RCSL) {
     train(ORL_NET_ACTOR, make_mlp_layout(od + 1, c.hidden, L, TAIL_LINEAR, ad));      // MLP(obs_dim + 1, hidden, act_dim) of RcslModule
+  } else if (c.algo == ORL_ALGO_RCSL_GAUSS) {
+    train(ORL_NET_ACTOR, make_mlp_layout(od + 1, c.hidden, L, TAIL_LINEAR_GAUSS, ad));      // RcslGaussianModule: backbone + DiagGaussian heads
   } else {
     return fail("unknown algorithm id");
   }
@@ -1108,6 +1122,7 @@ static SampleJob make_job(int head_row0, int rows, int rep, const Mat& eps, cons
 #include "algo_mcq.inc"
 #include "algo_mobile.inc"
 #include "algo_rcsl.inc"
+#include "algo_rcsl_gauss.inc"
 
 namespace orl {
 
@@ -1253,6 +1268,7 @@ int Engine::init(const orl_config& c) {
     case ORL_ALGO_MCQ: rc = mcq_build(); break;
     case ORL_ALGO_MOBILE: rc = mobile_build(); break;
     case ORL_ALGO_RCSL: rc = rcsl_build(); break;
+    case ORL_ALGO_RCSL_GAUSS: rc = rcslg_build(); break;
   }
   if (rc) return rc;
   { Mat lc; lc.p = (float*)lab_clk(0); lc.pitch = 192; taps["lab_clk"] = {lc, 1, 192}; }      // shader-clock stamps of lab builds (small_bwd.hip)
@@ -1270,7 +1286,7 @@ int Engine::init(const orl_config& c) {
 }
 
 int Engine::enqueue_sample() {
-  if (cfg.algo == ORL_ALGO_RCSL) return 0;      // rcsl_step's own input launch gathers (k_rcsl_prepare)
+  if (is_rcsl(cfg.algo)) return 0;      // rcsl_step's / rcslg_step's own input launch gathers (k_rcsl_prepare)
   if (!buf || !buf->obs) return fail("no replay buffer attached (orl_engine_attach_buffer)");
   GatherP g;
   memset(&g, 0, sizeof(g));
@@ -1381,6 +1397,7 @@ int Engine::enqueue_step(int variant) {
     case ORL_ALGO_MCQ: rc = mcq_step(); break;
     case ORL_ALGO_MOBILE: rc = mobile_step(); break;
     case ORL_ALGO_RCSL: rc = rcsl_step(); break;
+    case ORL_ALGO_RCSL_GAUSS: rc = rcslg_step(); break;
   }
   if (rc) return rc;
   if (tick_folded) return 0;               // the step's own kernels advanced the counter
@@ -1406,9 +1423,9 @@ extern "C" {
 
 const char* orl_last_error(void) { return g_err.c_str(); }
 #ifdef ORL_SPLIT_BF16
-const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-bf16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL)"; }
+const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-bf16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL RCSL_GAUSS)"; }
 #else
-const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-fp16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL)"; }
+const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-fp16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL RCSL_GAUSS)"; }
 #endif
 int orl_split_bits(void) { return ORL_SPLIT_BITS; }
 
@@ -1434,6 +1451,7 @@ void orl_config_default(orl_config* c, int32_t algo) {
   c->mobile_num_samples = 10; c->mobile_num_elites = 5; c->mobile_real_rows = 12; c->penalty_coef = 1.5f;   /* run_mobile.py:45-52: int(256 * 0.05) real rows */
   if (algo == ORL_ALGO_MOBILE) { c->deterministic_backup = 1; }                                             /* run_mobile.py:157 */
   if (algo == ORL_ALGO_RCSL) { c->n_hidden = 4; for (int i = 0; i < 4; ++i) c->hidden[i] = 200; c->actor_lr = 1e-3f; }   /* run_rcsl.py:125-127 */
+  if (algo == ORL_ALGO_RCSL_GAUSS) { c->n_hidden = 4; for (int i = 0; i < 4; ++i) c->hidden[i] = 1024; c->actor_lr = 1e-3f; }   /* run_rcsl_gauss.py */
   if (algo == ORL_ALGO_MCQ) { c->hidden[0] = c->hidden[1] = 400; c->actor_lr = c->critic_lr = c->alpha_lr = 3e-4f; c->target_entropy = -(float)c->act_dim; }
 }
 
@@ -1880,7 +1898,7 @@ int orl_engine_attach_buffer(orl_engine* h, orl_buffer* b) {
       return fail(msg);
     }
   }
-  if (h->e.split_scales() && h->e.cfg.algo == ORL_ALGO_RCSL && b->b.rew) {
+  if (h->e.split_scales() && is_rcsl(h->e.cfg.algo) && b->b.rew) {
     // the reward column holds the return-to-go, column obs_dim of the net's input: an MFMA operand like the observations
     Buffer& bb = b->b;
     if (bb.rew_absmax_gen != bb.gen) {
@@ -1911,7 +1929,7 @@ int orl_engine_attach_buffer(orl_engine* h, orl_buffer* b) {
 int orl_engine_attach_model_buffer(orl_engine* h, orl_buffer* m, int32_t real_rows) {
   Engine& e = h->e;
   if (!m) { if (e.mbuf || !e.mbufs.empty()) { e.mbuf = nullptr; e.mbufs.clear(); e.mbuf_real_rows = 0; e.drop_graphs(); } return 0; }
-  if (e.cfg.algo == ORL_ALGO_RCSL) return fail("attach_model_buffer: not available for RCSL engines (one dataset, no real + model batch)");
+  if (is_rcsl(e.cfg.algo)) return fail("attach_model_buffer: not available for RCSL engines (one dataset, no real + model batch)");
   if (m->b.od != e.od || m->b.ad != e.ad) return fail("attach_model_buffer: obs/act dims differ from the engine's");
   if (m->b.dev != e.dev) return fail("attach_model_buffer: buffer lives on another device");
   if (!m->b.d_n || m->b.cap < 1) return fail("attach_model_buffer: the model buffer must be a ring (orl_buffer_reserve)");
@@ -1939,7 +1957,7 @@ int Engine::upload_model_table() {
 int orl_engine_attach_model_buffers(orl_engine* h, orl_buffer* const* models, int32_t n, int32_t real_rows) {
   Engine& e = h->e;
   if (!models || n == 0) return orl_engine_attach_model_buffer(h, nullptr, 0);
-  if (e.cfg.algo == ORL_ALGO_RCSL) return fail("attach_model_buffers: not available for RCSL engines (one dataset, no real + model batch)");
+  if (is_rcsl(e.cfg.algo)) return fail("attach_model_buffers: not available for RCSL engines (one dataset, no real + model batch)");
   char msg[192];
   if (n != e.cfg.n_runs) {
     snprintf(msg, sizeof(msg), "attach_model_buffers: %d rings for an engine of %d runs (one ring per run)", (int)n, (int)e.cfg.n_runs);
@@ -1986,7 +2004,7 @@ int orl_step(orl_engine* h, const orl_batch* b, const orl_noise* nz, float* metr
   if (b) {
     const bool dv = b->on_device != 0;
     if (copy_rows(e, e.W("b_obs2"), b->observations, B, e.od, dv, 0)) return -1;
-    const bool rcsl = e.cfg.algo == ORL_ALGO_RCSL;      // (reads observations, actions and the return-to-go in `rewards` only)
+    const bool rcsl = is_rcsl(e.cfg.algo);      // (reads observations, actions and the return-to-go in `rewards` only)
     if (!(rcsl && !b->next_observations) && copy_rows(e, e.W("b_obs2"), b->next_observations, B, e.od, dv, B)) return -1;
     if (copy_rows(e, e.W("b_act"), b->actions, B, e.ad, dv)) return -1;
     if (copy_rows(e, e.W("b_rew"), b->rewards, B, 1, dv)) return -1;
@@ -2099,7 +2117,7 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
 int orl_learn_epoch(orl_engine* h, const int64_t* order, int64_t order_len, int on_device, float* metrics_mean, float* elapsed_ms) {
   Engine& e = h->e;
   ORL_HIP(hipSetDevice(e.dev));
-  if (e.cfg.algo != ORL_ALGO_RCSL)
+  if (!is_rcsl(e.cfg.algo))
     return fail("orl_learn_epoch: available for RCSL engines only (the other algorithms sample with replacement: orl_learn_n)");
   if (!order) return fail("orl_learn_epoch: null row order");
   if (!e.buf || !e.buf->obs || e.buf->n < 1) return fail("orl_learn_epoch: no replay buffer attached");

@@ -1707,4 +1707,109 @@ __global__ void k_rcsl_loss(RcslLossP p) {
   grad_scale_publish(amax, sh, p.gs_out, r);
 }
 
+// ================================================================================================
+// Gaussian RCSL (policy/rcsl/rcsl_gauss.py:123-154; modules/dist_module.py:80-93; tests/rcsl_gauss_oracle.py)
+//   z = MLP([obs | rtg]) (A wide), mu = W_mu z + b_mu, s = clamp(W_sigma z + b_sigma, lo, hi) read as a log-variance:
+//   loss = (sum over valid rows x A of (mu - a)^2 e^-s + s) / cnt, cnt = valid rows x A
+//   dmu = 2 (mu - a) e^-s / cnt;  ds = (1 - (mu - a)^2 e^-s) / cnt where the clamp is inactive, 0 where it is;  both 0 on padding rows
+//   dz = W_mu^T dmu + W_sigma^T ds (the dTail of mlp_backward);  head gradients = sums over the rows, written to slab 0 of the arena.
+// One workgroup of 256 (4 waves of 64) per run, fp32 throughout.  The rows pass through LDS in chunks of RG_CH: z, dmu and ds of a chunk
+// (3 x RG_CH x A floats) plus the two A x A heads, 32.5 KiB at A = 32 whatever B is.  Every sum runs in an order fixed by (thread, chunk,
+// row) alone -- no floating-point atomics, nothing depends on the run index --, so identical runs stay bit-identical.
+// Head gradient o of the 2 (A^2 + A) (the arena order: mu.weight, mu.bias, sigma.weight, sigma.bias) belongs to thread o % 256, which adds
+// the rows of every chunk in ascending order into a register.
+// ================================================================================================
+enum { RG_CH = 64, RG_AMAX = 32, RG_OUTS = (2 * (RG_AMAX * RG_AMAX + RG_AMAX) + 255) / 256 };
+struct RcslGaussP {
+  const float* z; long z_rs;            // [R][B][A] latent (pitch A)
+  const float* act; long act_rs; int apitch;
+  const float* head; long head_rs;      // [R] the four head tensors inside the parameter block: W_mu [A][A], b_mu [A], W_sigma [A][A], b_sigma [A]
+  float* g_head; long gh_rs;            // [R] their gradients, slab 0 of the gradient arena
+  float* dz;                            // [R][B][A]
+  float* mu; float* logvar;             // [R][B][A] taps (post-clamp)
+  const long long* idx;                 // [R][B] recorded row indices (negative = padding), or null: every row is valid
+  int B, A; float lo, hi; MetricsP m; int slot;
+  float* gs_out;                        // split precision: dynamic scale of dz [R], or null
+};
+__global__ __launch_bounds__(256) void k_rcslg_head(RcslGaussP p) {
+  __shared__ float sh[4];
+  __shared__ float wmu[RG_AMAX * (RG_AMAX + 1)], wsg[RG_AMAX * (RG_AMAX + 1)];      // row stride A + 1: a column walk touches every bank once
+  __shared__ float bmu[RG_AMAX], bsg[RG_AMAX];
+  __shared__ float zs[RG_CH * RG_AMAX], dm[RG_CH * RG_AMAX], dsg[RG_CH * RG_AMAX];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int A = p.A, B = p.B, AA = A * A, WS = A + 1, HALF = AA + A, NOUT = 2 * HALF;
+  const long long* idx = p.idx ? p.idx + (long)r * B : nullptr;
+  const float* hd = p.head + (long)r * p.head_rs;
+  for (int e = tid; e < AA; e += 256) {
+    const int a = e / A, k = e - a * A;
+    wmu[a * WS + k] = hd[e];
+    wsg[a * WS + k] = hd[HALF + e];
+  }
+  for (int a = tid; a < A; a += 256) { bmu[a] = hd[AA + a]; bsg[a] = hd[HALF + AA + a]; }
+  float nv = 0.f;                       // (a count below 2^24: exact in fp32)
+  for (int b = tid; b < B; b += 256) nv += (!idx || idx[b] >= 0) ? 1.0f : 0.0f;
+  nv = block_sum256(nv, sh);            // (its barriers also publish the heads)
+  const float cnt = nv * (float)A, inv = cnt > 0.f ? 1.0f / cnt : 0.f;
+  float acc[RG_OUTS];
+#pragma unroll
+  for (int j = 0; j < RG_OUTS; ++j) acc[j] = 0.f;
+  float ls = 0.f, amax = 0.f;
+  const long zb = (long)r * p.z_rs;
+  for (int b0 = 0; b0 < B; b0 += RG_CH) {
+    const int rows = min(RG_CH, B - b0), n = rows * A;
+    __syncthreads();                    // the previous chunk's readers are done
+    for (int e = tid; e < n; e += 256) zs[e] = p.z[zb + (long)b0 * A + e];
+    __syncthreads();
+    for (int e = tid; e < n; e += 256) {
+      const int i = e / A, a = e - i * A, b = b0 + i;
+      float mu = bmu[a], sr = bsg[a];
+      for (int k = 0; k < A; ++k) {
+        const float zv = zs[i * A + k];
+        mu = fmaf(wmu[a * WS + k], zv, mu);
+        sr = fmaf(wsg[a * WS + k], zv, sr);
+      }
+      const bool open = sr >= p.lo && sr <= p.hi;      // torch.clamp passes the gradient where lo <= x <= hi
+      const float s = fminf(fmaxf(sr, p.lo), p.hi);
+      p.mu[zb + (long)b0 * A + e] = mu;
+      p.logvar[zb + (long)b0 * A + e] = s;
+      const bool valid = !idx || idx[b] >= 0;
+      const float d = mu - p.act[(long)r * p.act_rs + (long)b * p.apitch + a];
+      const float iv = expf(-s), q = d * d * iv;
+      if (valid) ls += q + s;
+      dm[e] = valid ? 2.0f * d * iv * inv : 0.f;
+      dsg[e] = (valid && open) ? (1.0f - q) * inv : 0.f;
+    }
+    __syncthreads();
+    for (int e = tid; e < n; e += 256) {
+      const int i = e / A, k = e - i * A;
+      float g = 0.f;
+      for (int a = 0; a < A; ++a) g = fmaf(wmu[a * WS + k], dm[i * A + a], fmaf(wsg[a * WS + k], dsg[i * A + a], g));
+      p.dz[zb + (long)b0 * A + e] = g;
+      amax = fmaxf(amax, fabsf(g));
+    }
+#pragma unroll
+    for (int j = 0; j < RG_OUTS; ++j) {
+      const int o = tid + j * 256;
+      if (o < NOUT) {
+        const int h = o >= HALF ? 1 : 0, q = o - h * HALF;
+        const bool bias = q >= AA;
+        const int a = bias ? q - AA : q / A, k = bias ? 0 : q - a * A;
+        const float* D = h ? dsg : dm;
+        float t = acc[j];
+        for (int i = 0; i < rows; ++i) t = fmaf(D[i * A + a], bias ? 1.0f : zs[i * A + k], t);
+        acc[j] = t;
+      }
+    }
+  }
+  float* gh = p.g_head + (long)r * p.gh_rs;
+#pragma unroll
+  for (int j = 0; j < RG_OUTS; ++j) {
+    const int o = tid + j * 256;
+    if (o < NOUT) gh[o] = acc[j];
+  }
+  ls = block_sum256(ls, sh);
+  if (tid == 0) metric_set(p.m, r, p.slot, ls * inv);
+  grad_scale_publish(amax, sh, p.gs_out, r);
+}
+
 }  // namespace orl

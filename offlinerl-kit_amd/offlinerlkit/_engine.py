@@ -16,9 +16,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "liborlengine.so")
 
-ALGO_CQL, ALGO_IQL, ALGO_TD3BC, ALGO_EDAC, ALGO_SAC, ALGO_MCQ, ALGO_MOBILE, ALGO_RCSL = 0, 1, 2, 3, 4, 5, 6, 7
+ALGO_CQL, ALGO_IQL, ALGO_TD3BC, ALGO_EDAC, ALGO_SAC, ALGO_MCQ, ALGO_MOBILE, ALGO_RCSL, ALGO_RCSL_GAUSS = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ALGO_ID = {"cql": ALGO_CQL, "iql": ALGO_IQL, "td3bc": ALGO_TD3BC, "edac": ALGO_EDAC, "sac": ALGO_SAC, "mcq": ALGO_MCQ,
-           "mobile": ALGO_MOBILE, "rcsl": ALGO_RCSL}
+           "mobile": ALGO_MOBILE, "rcsl": ALGO_RCSL, "rcsl_gauss": ALGO_RCSL_GAUSS}
 MAX_HIDDEN, MAX_METRICS, MAX_NOISE = 4, 8, 6
 NET_ACTOR, NET_CRITIC1, NET_CRITIC2, NET_CRITIC1_OLD, NET_CRITIC2_OLD, NET_CRITIC_V, NET_ACTOR_OLD, NET_VAE_ENC, NET_VAE_DEC = range(9)
 NUM_NETS = 9

@@ -165,6 +165,31 @@ class RcslModule(nn.Module):
         return self.backbone(torch.cat([obs, rtg], dim=-1))
 
 
+class RcslGaussianModule(nn.Module):
+    """Return-conditioned Gaussian policy network: dist_net(backbone([obs | rtg])) (modules/rcsl_gauss_module.py:12-54).  ``forward``
+    returns the ``NormalWrapper`` (scale = exp of the clamped head output), ``get_dist_params`` the pair (mu, that same clamped output),
+    which ``RcslGaussianPolicy.learn`` reads as a log-variance: the reference's asymmetry, kept."""
+
+    def __init__(self, backbone: nn.Module, dist_net: DiagGaussian, device: str = "cpu") -> None:
+        super().__init__()
+        self.device = torch.device(device)
+        self.backbone = backbone.to(device)
+        self.dist_net = dist_net.to(device)
+
+    def _latent(self, obs, rtg) -> torch.Tensor:
+        obs = _as_input(obs, self.device)
+        rtg = _as_input(rtg, self.device)
+        if rtg.dim() == 1:
+            rtg = rtg.unsqueeze(-1)
+        return self.backbone(torch.cat([obs, rtg], dim=-1))
+
+    def forward(self, obs: Union[np.ndarray, torch.Tensor], rtg: Union[np.ndarray, torch.Tensor]) -> torch.distributions.Normal:
+        return self.dist_net(self._latent(obs, rtg))
+
+    def get_dist_params(self, obs: Union[np.ndarray, torch.Tensor], rtg: Union[np.ndarray, torch.Tensor]):
+        return self.dist_net.get_dist_params(self._latent(obs, rtg))
+
+
 class EnsembleCritic(nn.Module):
     """K parallel critic MLPs built from EnsembleLinear; output (K, B, 1) (ensemble_critic_module.py:11-44)."""
 

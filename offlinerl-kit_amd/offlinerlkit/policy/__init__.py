@@ -1,10 +1,11 @@
 """offlinerlkit.policy — the four model-free policies of the hot path plus SAC and the model-based callers whose ``learn`` reuses
 its kernels (MOPO, COMBO, MCQ: SURVEY §8(f)3), engine-backed, and RAMBO, whose adversarial update of the dynamics ensemble runs on the
 dynamics engine (``orl_dynadv_*``), and MOBILE, whose penalty pass runs on the dynamics engine (``orl_dynsample_next``) and the policy
-engine (``ORL_ALGO_MOBILE``), and RCSL's deterministic return-conditioned policy (``ORL_ALGO_RCSL``: one MLP on [obs | rtg], MSE on the
-dataset action; ``learn_epoch`` is one ordered pass over the dataset, ``orl_learn_epoch``).
-(The reference package also exports RcslGaussianPolicy, the diffusion behaviour policy and the autoregressive models; those are out of
-scope here, and with them ``RcslPolicy.rollout``.)"""
+engine (``ORL_ALGO_MOBILE``), and RCSL's return-conditioned policies: the deterministic one (``ORL_ALGO_RCSL``: one MLP on [obs | rtg],
+MSE on the dataset action) and the Gaussian one (``ORL_ALGO_RCSL_GAUSS``: the same MLP down to a latent, a DiagGaussian head with a
+clamped state-conditioned sigma, Gaussian NLL); ``learn_epoch`` is one ordered pass over the dataset (``orl_learn_epoch``).
+(The reference package also exports the diffusion behaviour policy and the autoregressive models; those are out of scope here, and with
+them ``RcslPolicy.rollout`` / ``RcslGaussianPolicy.rollout``.)"""
 from .base_policy import BasePolicy, EnginePolicy
 from .iql import IQLPolicy
 from .sac_family import CQLPolicy, EDACPolicy
@@ -13,7 +14,7 @@ from .model_based import SACPolicy, MOPOPolicy, COMBOPolicy
 from .mcq import MCQPolicy
 from .rambo import RAMBOPolicy
 from .mobile import MOBILEPolicy
-from .rcsl import RcslPolicy
+from .rcsl import RcslPolicy, RcslGaussianPolicy
 
 __all__ = ["BasePolicy", "EnginePolicy", "CQLPolicy", "IQLPolicy", "TD3BCPolicy", "EDACPolicy", "SACPolicy", "MOPOPolicy", "COMBOPolicy", "MCQPolicy",
-           "RAMBOPolicy", "MOBILEPolicy", "RcslPolicy"]
+           "RAMBOPolicy", "MOBILEPolicy", "RcslPolicy", "RcslGaussianPolicy"]

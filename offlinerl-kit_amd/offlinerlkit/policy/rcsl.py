@@ -1,4 +1,6 @@
-"""RCSL policy (reference: policy/rcsl/rcsl.py:18-163) on the HIP engine: pred = MLP([obs | rtg]), MSE on the dataset action.
+"""RCSL policies on the HIP engine.  ``RcslPolicy`` (reference: policy/rcsl/rcsl.py:18-163): pred = MLP([obs | rtg]), MSE on the dataset
+action.  ``RcslGaussianPolicy`` (policy/rcsl/rcsl_gauss.py:18-168): z = MLP([obs | rtg]), a ``DiagGaussian`` head with a state-conditioned,
+clamped sigma, the Gaussian negative log-likelihood of the dataset action.  Both share everything but the network tail (``_RcslBase``).
 
 The return-to-go travels where the other algorithms carry the reward (``orl_batch.rewards``, the ``rew`` column of a ``DeviceBuffer``).
 ``learn_epoch`` is the reference trainer's inner loop -- one pass over a shuffled dataset, every row once, last batch partial -- as one
@@ -26,8 +28,9 @@ def epoch_order(n_rows: int, batch_size: int, n_runs: int = 1, generator: Option
     return order
 
 
-class RcslPolicy(EnginePolicy):
-    ALGO = "rcsl"
+class _RcslBase(EnginePolicy):
+    """what the two return-conditioned policies share: the constructor, the backbone check, ``learn`` on {observations, actions, rtgs},
+    ``learn_epoch`` and the refusal of ``rollout``"""
 
     def __init__(self, dynamics, rollout_policy, rcsl: nn.Module, rcsl_optim: torch.optim.Optimizer, device="cpu") -> None:
         super().__init__()
@@ -42,13 +45,13 @@ class RcslPolicy(EnginePolicy):
     def _dims(self):
         in_dim, outs = _backbone_dims(self.rcsl.backbone)
         if len(outs) < 2:
-            raise NotImplementedError("RcslPolicy expects MLP(obs_dim + 1, hidden_dims, output_dim=act_dim): at least one hidden layer and the output layer")
+            raise NotImplementedError(f"{type(self).__name__} expects MLP(obs_dim + 1, hidden_dims, output_dim=act_dim): at least one hidden layer and the output layer")
         hidden, act_dim = outs[:-1], outs[-1]
         if len(hidden) > _engine.MAX_HIDDEN:
             raise NotImplementedError(f"the HIP engine supports up to {_engine.MAX_HIDDEN} hidden layers, the backbone has {len(hidden)}")
         n_mods = len(list(self.rcsl.backbone.model))
         if n_mods != 2 * len(hidden) + 1 or getattr(self.rcsl.backbone, "activation_cls", nn.ReLU) is not nn.ReLU:
-            raise NotImplementedError("RcslPolicy expects a [Linear, ReLU] x L + Linear backbone")
+            raise NotImplementedError(f"{type(self).__name__} expects a [Linear, ReLU] x L + Linear backbone")
         return in_dim - 1, act_dim, hidden
 
     def _nets(self):
@@ -62,7 +65,7 @@ class RcslPolicy(EnginePolicy):
         return dict(obs_dim=od, act_dim=ad, hidden=hidden, actor_lr=float(self.rcsl_optim.param_groups[0]["lr"]))
 
     def rollout(self, init_obss, rollout_length):
-        raise NotImplementedError("RcslPolicy.rollout needs the diffusion behaviour policy, which this package does not have")
+        raise NotImplementedError(f"{type(self).__name__}.rollout needs the diffusion behaviour policy, which this package does not have")
 
     def learn(self, batch: Dict) -> Dict[str, float]:
         """One gradient step on ``{"observations", "actions", "rtgs"}``: [B, ...] arrays shared by every run or [n_runs, B, ...]."""
@@ -115,6 +118,28 @@ class RcslPolicy(EnginePolicy):
         self.last_learn_epoch_ms = ms
         return self._result(m)
 
+    def _backbone_runs(self, obs, rtg):
+        """-> (backbone output of EVERY run [n_runs, E, act_dim] in one batched forward, the stacked net tensors); ``obs`` [n_runs, E,
+        obs_dim], ``rtg`` [n_runs, E] or [n_runs, E, 1]"""
+        if self._eng is None:
+            raise RuntimeError("select_action_runs before the first learn(): no engine is bound yet")
+        P = self._stacked_net(_engine.NET_ACTOR)
+        o = torch.as_tensor(np.asarray(obs, dtype=np.float32), device=self._arena.device)
+        g = torch.as_tensor(np.asarray(rtg, dtype=np.float32), device=self._arena.device)
+        if g.dim() == 2:
+            g = g.unsqueeze(-1)
+        h = torch.cat([o, g], dim=-1)
+        idx = sorted(int(k[len("backbone.model."):-len(".weight")]) for k in P if k.startswith("backbone.model.") and k.endswith(".weight"))
+        for n, i in enumerate(idx):
+            h = torch.baddbmm(P[f"backbone.model.{i}.bias"].unsqueeze(1), h, P[f"backbone.model.{i}.weight"].transpose(1, 2))
+            if n + 1 < len(idx):
+                h = torch.relu(h)
+        return h, P
+
+
+class RcslPolicy(_RcslBase):
+    ALGO = "rcsl"
+
     def select_action(self, obs: np.ndarray, rtg) -> np.ndarray:
         with torch.no_grad():
             action = self.rcsl.forward(obs, rtg)
@@ -122,18 +147,47 @@ class RcslPolicy(EnginePolicy):
 
     def select_action_runs(self, obs: np.ndarray, rtg: np.ndarray) -> np.ndarray:
         """Actions of EVERY run in one batched forward: ``obs`` [n_runs, E, obs_dim], ``rtg`` [n_runs, E] or [n_runs, E, 1]"""
-        if self._eng is None:
-            raise RuntimeError("select_action_runs before the first learn(): no engine is bound yet")
-        P = self._stacked_net(_engine.NET_ACTOR)
         with torch.no_grad():
-            o = torch.as_tensor(np.asarray(obs, dtype=np.float32), device=self._arena.device)
-            g = torch.as_tensor(np.asarray(rtg, dtype=np.float32), device=self._arena.device)
-            if g.dim() == 2:
-                g = g.unsqueeze(-1)
-            h = torch.cat([o, g], dim=-1)
-            idx = sorted(int(k[len("backbone.model."):-len(".weight")]) for k in P if k.endswith(".weight"))
-            for n, i in enumerate(idx):
-                h = torch.baddbmm(P[f"backbone.model.{i}.bias"].unsqueeze(1), h, P[f"backbone.model.{i}.weight"].transpose(1, 2))
-                if n + 1 < len(idx):
-                    h = torch.relu(h)
-            return h.cpu().numpy()
+            return self._backbone_runs(obs, rtg)[0].cpu().numpy()
+
+
+class RcslGaussianPolicy(_RcslBase):
+    """``rcsl`` is a ``RcslGaussianModule``: an ``MLP(obs_dim + 1, hidden, output_dim=act_dim)`` backbone and
+    ``DiagGaussian(act_dim, act_dim, unbounded=True, conditioned_sigma=True)`` with the default clamp (-5, 2) -- what run_rcsl_gauss.py
+    builds; anything else is refused.  ``learn`` reads the clamped head output as a log-variance, ``select_action`` samples
+    ``Normal(mu, exp(that output))``: the reference's asymmetry, reproduced."""
+    ALGO = "rcsl_gauss"
+    SIGMA_BOUNDS = (-5.0, 2.0)
+
+    def _dims(self):
+        od, act_dim, hidden = super()._dims()
+        dist = getattr(self.rcsl, "dist_net", None)
+        if dist is None or not hasattr(dist, "mu"):
+            raise NotImplementedError("RcslGaussianPolicy expects a RcslGaussianModule(backbone, DiagGaussian)")
+        if not getattr(dist, "_unbounded", False):
+            raise NotImplementedError("RcslGaussianPolicy: DiagGaussian(unbounded=False) (mu = max_mu * tanh) is not implemented by the HIP engine")
+        if not getattr(dist, "_c_sigma", False):
+            raise NotImplementedError("RcslGaussianPolicy: DiagGaussian(conditioned_sigma=False) (a free sigma_param) is not implemented by the HIP engine")
+        if dist.mu.in_features != act_dim or dist.mu.out_features != act_dim or dist.sigma.in_features != act_dim or dist.sigma.out_features != act_dim:
+            raise NotImplementedError(f"RcslGaussianPolicy: DiagGaussian must have latent_dim == output_dim == act_dim = {act_dim} (the backbone's "
+                                      f"output), got {dist.mu.in_features} -> {dist.mu.out_features}")
+        if (float(dist._sigma_min), float(dist._sigma_max)) != self.SIGMA_BOUNDS:
+            raise NotImplementedError(f"RcslGaussianPolicy: the HIP engine clamps the sigma head to {self.SIGMA_BOUNDS} (DiagGaussian's "
+                                      f"defaults), got ({dist._sigma_min}, {dist._sigma_max})")
+        return od, act_dim, hidden
+
+    def select_action(self, obs: np.ndarray, rtg) -> np.ndarray:
+        with torch.no_grad():
+            action = self.rcsl.forward(obs, rtg).rsample()
+        return action.cpu().numpy()
+
+    def select_action_runs(self, obs: np.ndarray, rtg: np.ndarray, deterministic: bool = False) -> np.ndarray:
+        """Actions of EVERY run in one batched forward: ``obs`` [n_runs, E, obs_dim], ``rtg`` [n_runs, E] or [n_runs, E, 1].  Sampled as
+        ``select_action`` samples; ``deterministic``: the mean."""
+        with torch.no_grad():
+            z, P = self._backbone_runs(obs, rtg)
+            mu = torch.baddbmm(P["dist_net.mu.bias"].unsqueeze(1), z, P["dist_net.mu.weight"].transpose(1, 2))
+            if deterministic:
+                return mu.cpu().numpy()
+            s = torch.baddbmm(P["dist_net.sigma.bias"].unsqueeze(1), z, P["dist_net.sigma.weight"].transpose(1, 2)).clamp(*self.SIGMA_BOUNDS)
+            return (mu + s.exp() * torch.randn_like(mu)).cpu().numpy()

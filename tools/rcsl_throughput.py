@@ -5,7 +5,9 @@ and at 8 runs per engine, against a stock-torch restatement of the same epoch on
 device-resident arrays, nn.Linear / ReLU forward, autograd, torch.optim.Adam, one ``.item()`` per batch like the reference's ``learn``;
 R runs = R such models trained one after the other).  One invocation, alternating: a warm-up epoch of each, then ``--blocks`` timed
 epochs of each, timed with a host clock around work that ends in a device synchronise.  A synthetic dataset of ``--rows`` rows (default
-100 000 = 391 steps, the last batch partial).  The figure is run-steps per second.  Prints one JSON object; --out writes it too.  Needs a GPU."""
+100 000 = 391 steps, the last batch partial).  The figure is run-steps per second.  Prints one JSON object; --out writes it too.  Needs a GPU.
+``--gauss``: the same measurement of ``RcslGaussianPolicy`` at run_rcsl_gauss.py's shape (MLP [1024] x 4 down to an act_dim-wide latent, the
+DiagGaussian head with a clamped state-conditioned sigma, Gaussian NLL; k_rcslg_head in place of the MSE launch)."""
 import argparse
 import json
 import os
@@ -18,13 +20,14 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "offlinerl-kit_amd"))
 from offlinerlkit import _engine  # noqa: E402
-from offlinerlkit.modules import RcslModule  # noqa: E402
+from offlinerlkit.modules import DiagGaussian, RcslGaussianModule, RcslModule  # noqa: E402
 from offlinerlkit.nets import MLP  # noqa: E402
-from offlinerlkit.policy import RcslPolicy  # noqa: E402
+from offlinerlkit.policy import RcslGaussianPolicy, RcslPolicy  # noqa: E402
 from offlinerlkit.policy.rcsl import epoch_order  # noqa: E402
 
 DEV = "cuda:0"
 OD, AD, HID, B, LR = 11, 3, [200, 200, 200, 200], 256, 1e-3
+HID_GAUSS = [1024, 1024, 1024, 1024]
 
 
 def dataset(rows):
@@ -42,6 +45,13 @@ def engine_epoch(pol, buf, rows, runs):
     return (order.shape[1] // B) * runs / (time.perf_counter() - t0)
 
 
+def torch_loss(net, x, act):
+    if isinstance(net, RcslGaussianModule):
+        mu, logvar = net.dist_net.get_dist_params(net.backbone(x))
+        return (torch.pow(mu - act, 2) * torch.exp(-logvar)).mean() + logvar.mean()
+    return torch.pow(net(x) - act, 2).mean()
+
+
 def torch_epoch(models, data, rows):
     steps = 0
     torch.cuda.synchronize()
@@ -51,7 +61,7 @@ def torch_epoch(models, data, rows):
         for s in range(0, rows, B):
             idx = perm[s:s + B]
             x = torch.cat([data["observations"].index_select(0, idx), data["rtgs"].index_select(0, idx)], dim=-1)
-            loss = torch.pow(net(x) - data["actions"].index_select(0, idx), 2).mean()
+            loss = torch_loss(net, x, data["actions"].index_select(0, idx))
             opt.zero_grad()
             loss.backward()
             opt.step()
@@ -61,16 +71,23 @@ def torch_epoch(models, data, rows):
     return steps / (time.perf_counter() - t0)
 
 
-def measure(ds, rows, runs, blocks):
+def make_module(gauss):
+    if gauss:
+        return RcslGaussianModule(MLP(input_dim=OD + 1, hidden_dims=HID_GAUSS, output_dim=AD),
+                                  DiagGaussian(AD, AD, unbounded=True, conditioned_sigma=True), DEV)
+    return RcslModule(MLP(input_dim=OD + 1, hidden_dims=HID, output_dim=AD), DEV)
+
+
+def measure(ds, rows, runs, blocks, gauss=False):
     torch.manual_seed(1)
-    mod = RcslModule(MLP(input_dim=OD + 1, hidden_dims=HID, output_dim=AD), DEV)
-    pol = RcslPolicy(None, None, mod, torch.optim.Adam(mod.parameters(), lr=LR), DEV)
+    mod = make_module(gauss)
+    pol = (RcslGaussianPolicy if gauss else RcslPolicy)(None, None, mod, torch.optim.Adam(mod.parameters(), lr=LR), DEV)
     pol.set_engine_options(n_runs=runs, seed=3)
     buf = _engine.DeviceBuffer(OD, AD, 0)
     buf.load(ds["observations"], ds["actions"], ds["observations"], ds["rtgs"].reshape(rows), np.zeros(rows, np.float32))
     models = []
     for _ in range(runs):
-        net = MLP(input_dim=OD + 1, hidden_dims=HID, output_dim=AD).to(DEV)
+        net = make_module(True) if gauss else MLP(input_dim=OD + 1, hidden_dims=HID, output_dim=AD).to(DEV)
         models.append((net, torch.optim.Adam(net.parameters(), lr=LR)))
     data = {k: torch.as_tensor(v, device=DEV) for k, v in ds.items()}
     engine_epoch(pol, buf, rows, runs); torch_epoch(models, data, rows)          # warm-up: graph capture / allocator
@@ -87,11 +104,13 @@ def main():
     ap.add_argument("--rows", type=int, default=100_000)
     ap.add_argument("--blocks", type=int, default=3)
     ap.add_argument("--runs", type=int, nargs="*", default=[1, 8])
+    ap.add_argument("--gauss", action="store_true", help="RcslGaussianPolicy at run_rcsl_gauss.py's shape ([1024] x 4)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ds = dataset(a.rows)
-    res = dict(shape=dict(obs_dim=OD, act_dim=AD, hidden=HID, batch=B, rows=a.rows, steps_per_epoch=-(-a.rows // B)),
-               device=torch.cuda.get_device_name(0), results=[measure(ds, a.rows, r, a.blocks) for r in a.runs])
+    res = dict(policy="RcslGaussianPolicy" if a.gauss else "RcslPolicy", precision=int(os.environ.get("ORL_PRECISION", "0")),
+               shape=dict(obs_dim=OD, act_dim=AD, hidden=HID_GAUSS if a.gauss else HID, batch=B, rows=a.rows, steps_per_epoch=-(-a.rows // B)),
+               device=torch.cuda.get_device_name(0), results=[measure(ds, a.rows, r, a.blocks, a.gauss) for r in a.runs])
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
