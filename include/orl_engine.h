@@ -67,6 +67,12 @@ extern "C" {
                            * unbounded, conditioned_sigma) of modules/dist_module.py:45-93: mu = W_mu z + b_mu, s = clamp(W_sigma z + b_sigma, -5, 2),
                            * loss = mean((mu - a)^2 exp(-s)) + mean(s), Adam with actor_lr / ORL_OPT_ACTOR; metric "loss".  Inputs, buffers, orl_learn_epoch
                            * and every refusal as for ORL_ALGO_RCSL */
+#define ORL_ALGO_AUTOREG 9 /* policy/others/autoregressive.py:9-124: p(a | s) = prod_j N(a_j | s, a_<j).  ORL_NET_ACTOR = [Linear, LeakyReLU(0.01)] x (L + 1):
+                           * Linear(obs_dim + 2 act_dim, h0), ..., Linear(h_{L-1}, 2), tensors model.{0, 2, ..., 2L}.{weight, bias}; act_dim <= 32.  A batch
+                           * row b becomes act_dim input rows j * B + b = [obs | act[k] 1[k < j] | onehot_j] with target act[j]; (mean, logstd) = the two
+                           * (activated) outputs, loss = mean Gaussian NLL over the expanded rows, Adam with actor_lr / ORL_OPT_ACTOR; metric "loss".
+                           * Buffers, orl_learn_n, orl_learn_epoch and the refusals as for ORL_ALGO_RCSL, but no return-to-go is read:
+                           * orl_batch.rewards may be NULL and a buffer's `rew` column is not range-checked.  Sampling: orl_autoreg_sample */
 
 /* per-run health flags (orl_health).  The reference raises nothing when a run diverges (its losses simply turn nan); here a diverging run
  * can additionally be MASKED by the arithmetic -- the ReLU of the matrix kernels works on the integer view of the activations and maps a NaN
@@ -313,9 +319,16 @@ int orl_learn_n(orl_engine* e, int n_steps, float* metrics_mean, float* elapsed_
  * every epoch.  The row's index, padding included, is recorded per step (a padding row reads row 0 of the dataset).
  * metrics_mean: host [n_runs][ORL_MAX_METRICS], the unweighted mean over the order_len / B steps (logkv_mean per batch).
  * Refused before a step is launched: no buffer attached, order_len not a multiple of B, an entry >= the buffer's size (host orders are
- * checked on the host, device orders by one checking launch), a step whose rows are all padding, an engine that is neither RCSL nor RCSL_GAUSS. */
+ * checked on the host, device orders by one checking launch), a step whose rows are all padding, an engine that is none of RCSL, RCSL_GAUSS, AUTOREG. */
 int orl_learn_epoch(orl_engine* e, const int64_t* order, int64_t order_len, int on_device,
                     float* metrics_mean, float* elapsed_ms);
+/* AUTOREG: AutoregressivePolicy.forward (autoregressive.py:28-54) for n rows per run: act_dim forward-only passes, between them
+ * a_j = mean + exp(logstd) * eps_j goes into the input of the next pass; no host synchronisation but the one at the end.
+ * obs [n_runs][n][obs_dim]; eps [n_runs][n][act_dim] standard normals teacher-force the draws (NULL: a device Philox stream keyed by
+ * (seed, this entry point's own call counter, run, row, dim)); act_out [n_runs][n][act_dim]; all three are device pointers when on_device.
+ * Workspaces are sized for n at the first call and regrown when n grows.  Parameters, optimizer state, the step counter and the
+ * noise streams of orl_learn_n are not touched.  Refused on any other engine. */
+int orl_autoreg_sample(orl_engine* e, const float* obs, int64_t n, const float* eps, int on_device, float* act_out);
 /* MOBILE: the next-state samples of the batch the NEXT orl_step learns, [n_runs][S * E * batch][obs_dim] in the row order of
  * orl_dynsample_next (row (s * E + e) * batch + b).  A device pointer (on_device) is borrowed until that step has run -- nothing is
  * copied, the producer must have finished writing (orl_dynsample_next synchronises its stream) --; a host pointer is copied in.  One
@@ -342,7 +355,7 @@ int64_t orl_step_count(orl_engine* e);
 
 /* -- test / profiling taps --------------------------------------------------------- */
 /* copies an intermediate of the LAST step to host: returns number of floats written or <0.
- * names: "q1","q2","target_q","q1a","q2a","logp_a", ... (algorithm specific; RCSL: "pred", "rcsl_x" = [obs | rtg]; RCSL_GAUSS: "z", "mu", "logvar" (post-clamp), "rcsl_x"); every engine also has the minibatch of the last
+ * names: "q1","q2","target_q","q1a","q2a","logp_a", ... (algorithm specific; RCSL: "pred", "rcsl_x" = [obs | rtg]; RCSL_GAUSS: "z", "mu", "logvar" (post-clamp), "rcsl_x"; AUTOREG: "ar_x" [A * B][obs_dim + 2 A], "ar_out" [A * B][2] (post-activation), "ar_target" [A * B]); every engine also has the minibatch of the last
  * step ("b_obs","b_nobs","b_act","b_rew","b_term": what ReplayBuffer.sample returned / the device sampler drew) and its noise
  * arrays under their orl_noise slot names ("n_eps_actor", ...). */
 int64_t orl_debug_read(orl_engine* e, int run, const char* name, float* host, int64_t cap);

@@ -326,6 +326,9 @@ struct Engine {
   int mlp_forward_dropout(const Mat& X, int M, const NetRef& nr, std::vector<Mat>& hs, const Mat& out, const char* tag, float p,
                           const std::vector<Mat>& masks);
   int scale_inplace(const Mat& m, int rows, int cols, int nets, float s, const Mat* mask, const char* tag);
+  // the net's activation is LeakyReLU(0.01) (ORL_ALGO_AUTOREG): hidden layers run E_BIAS_LEAKY, masked dgrads E_LEAKY_MASK, on the tiled GEMM
+  // only -- the weight-stationary launches, the one-launch few-rows passes, the packed mask bits and the fused layer-0 gradient bake in ReLU
+  bool leaky = false;
   bool no_ws = false;          // set while a dropout forward is enqueued: its layers must exist one by one
   float bwd_scale = 1.0f;      // mlp_backward: every masked dz of the pass is multiplied by this (1 / (1 - p) of a dropout backbone)
 
@@ -344,6 +347,14 @@ struct Engine {
   int mobile_build(); int mobile_step(); int mobile_penalty(int real_rows);
   int rcsl_build(); int rcsl_step(); int rcsl_prepare(int mode);
   int rcslg_build(); int rcslg_step();
+  int autoreg_build(); int autoreg_step(); int autoreg_prepare(int mode);
+  // orl_autoreg_sample: workspaces for n rows per run (input, hidden activations, tail, eps), regrown when n grows; the call counter of
+  // the device-drawn stream lives in a device cell of its own (the step counter and orl_learn_n's streams stay untouched)
+  int autoreg_sample(const float* obs, long n, const float* eps, bool on_device, float* act_out);
+  int autoreg_sample_room(long n);
+  long ar_cap = 0;
+  Mat ar_sx, ar_sz, ar_seps, ar_sobs; std::vector<Mat> ar_sh;
+  unsigned long long* ar_calls = nullptr;
 };
 
 }  // namespace orl

@@ -39,10 +39,12 @@ enum TailKind { TAIL_CRITIC, TAIL_TANH_GAUSS, TAIL_GAUSS, TAIL_DET, TAIL_LINEAR,
 
 // the two return-conditioned algorithms share inputs, buffers, the ordered epoch and every refusal
 static inline bool is_rcsl(int algo) { return algo == ORL_ALGO_RCSL || algo == ORL_ALGO_RCSL_GAUSS; }
+// ... and the autoregressive behaviour policy shares all of that but the return-to-go, which it does not read
+static inline bool is_epoch_algo(int algo) { return is_rcsl(algo) || algo == ORL_ALGO_AUTOREG; }
 
 // seq_step: distance of consecutive Linear layers in the backbone's nn.Sequential -- 2 for [Linear, ReLU], 3 when every ReLU is followed by
 // nn.Dropout (nets/mlp.py:20-23): the state_dict keys are backbone.model.{0, 3, 6, ...} then
-static NetLayout make_mlp_layout(int in_dim, const int* hidden, int L, TailKind tail, int act_dim, int seq_step = 2) {
+static NetLayout make_mlp_layout(int in_dim, const int* hidden, int L, TailKind tail, int act_dim, int seq_step = 2, const std::string& prefix = "backbone.model.") {
   NetLayout l;
   l.present = true;
   l.in_dim = in_dim;
@@ -52,10 +54,10 @@ static NetLayout make_mlp_layout(int in_dim, const int* hidden, int L, TailKind 
   for (int i = 0; i < L; ++i) {
     l.H[i] = hidden[i];
     l.w_off[i] = off;
-    add_tensor(l, "backbone.model." + std::to_string(seq_step * i) + ".weight", off, {hidden[i], d});
+    add_tensor(l, prefix + std::to_string(seq_step * i) + ".weight", off, {hidden[i], d});
     off += (long)hidden[i] * d;
     l.b_off[i] = off;
-    add_tensor(l, "backbone.model." + std::to_string(seq_step * i) + ".bias", off, {hidden[i]});
+    add_tensor(l, prefix + std::to_string(seq_step * i) + ".bias", off, {hidden[i]});
     off += hidden[i];
     d = hidden[i];
   }
@@ -81,7 +83,7 @@ static NetLayout make_mlp_layout(int in_dim, const int* hidden, int L, TailKind 
     l.extra_off = off; add_tensor(l, "dist_net.sigma_param", off, {act_dim, 1}); off += act_dim;
   } else if (tail == TAIL_LINEAR || tail == TAIL_LINEAR_GAUSS) {
     // the output layer is the backbone's own last nn.Linear (nets/mlp.py with output_dim: RcslModule): no tanh, no distribution head
-    const std::string n = "backbone.model." + std::to_string(seq_step * L);
+    const std::string n = prefix + std::to_string(seq_step * L);
     l.out_dim = act_dim;
     l.w_off[L] = off; add_tensor(l, n + ".weight", off, {act_dim, d}); off += (long)act_dim * d;
     l.b_off[L] = off; add_tensor(l, n + ".bias", off, {act_dim}); off += act_dim;
@@ -201,6 +203,10 @@ static int build_layouts(const orl_config& c, NetLayout* lay, long* net_off, boo
     train(ORL_NET_ACTOR, make_mlp_layout(od + 1, c.hidden, L, TAIL_LINEAR, ad));      // MLP(obs_dim + 1, hidden, act_dim) of RcslModule
   } else if (c.algo == ORL_ALGO_RCSL_GAUSS) {
     train(ORL_NET_ACTOR, make_mlp_layout(od + 1, c.hidden, L, TAIL_LINEAR_GAUSS, ad));      // RcslGaussianModule: backbone + DiagGaussian heads
+  } else if (c.algo == ORL_ALGO_AUTOREG) {
+    // AutoregressivePolicy.model: [Linear, LeakyReLU] x (L + 1), keys model.{0, 2, ...}; the last Linear has the two outputs (mean, logstd)
+    if (ad > AR_AMAX) return fail("AUTOREG: act_dim beyond 32");
+    train(ORL_NET_ACTOR, make_mlp_layout(od + 2 * ad, c.hidden, L, TAIL_LINEAR, 2, 2, "model."));
   } else {
     return fail("unknown algorithm id");
   }
@@ -504,7 +510,7 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
   if (maskH) {
     p.aux = maskH->z(); p.aux_sr = maskH->pitch;
     // the ReLU mask as packed bits (1/32 of the bytes) when the forward pass that produced the activation left them behind
-    if (epi == E_MASK && maskH->bits && bits_live.count(maskH->bits) && out == maskH->pitch && aligned16(maskH->p) && (maskH->pitch & 3) == 0) {
+    if (epi == E_MASK && !leaky && maskH->bits && bits_live.count(maskH->bits) && out == maskH->pitch && aligned16(maskH->p) && (maskH->pitch & 3) == 0) {
       p.aux_bits = maskH->bits; p.xb_s0 = maskH->brs; p.xb_s1 = maskH->bcs; p.xb_g = maskH->bg;
     }
   }
@@ -571,7 +577,7 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
     }
   }
   if (fuse_X0) {                   // no fused path: layer 0 first
-    if (linear_fwd(*fuse_X0, M, nr, 0, X, E_BIAS_RELU, nullptr, tag0 ? tag0 : tag)) return -1;
+    if (linear_fwd(*fuse_X0, M, nr, 0, X, epi, nullptr, tag0 ? tag0 : tag)) return -1;
   }
   if (Y.bits) {
     if (epi == E_BIAS_RELU && !force_scalar && out == Y.pitch && mb_supported(cfg, p)) {
@@ -602,6 +608,8 @@ int Engine::linear_fwd(const Mat& X, int M, const NetRef& nr, int layer, const M
     case E_BIAS_RELU: return run_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_RELU>(this, cfg, p, nz, tag, a_kpad);
     case E_BIAS: return run_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(this, CFG_AUTO, p, nz, tag, a_kpad);
     case E_MASK: return run_gemm<PA_PLAIN, PB_PLAIN, E_MASK>(this, CFG_AUTO, p, nz, tag, a_kpad);
+    case E_BIAS_LEAKY: return run_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_LEAKY>(this, cfg, p, nz, tag, a_kpad);
+    case E_LEAKY_MASK: return run_gemm<PA_PLAIN, PB_PLAIN, E_LEAKY_MASK>(this, CFG_AUTO, p, nz, tag, a_kpad);
     default: return run_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(this, CFG_AUTO, p, nz, tag, a_kpad);
   }
 }
@@ -668,7 +676,7 @@ int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int c
   if (maskH) { p.aux = maskH->z(); p.aux_sr = maskH->pitch; }
   const int nz = R * nr.nz1;
   if (w0_slabs) *w0_slabs = 0;
-  if (maskH && maskH->bits && bits_live.count(maskH->bits) && ncols == maskH->pitch && aligned16(maskH->p) && (maskH->pitch & 3) == 0) {
+  if (maskH && !leaky && maskH->bits && bits_live.count(maskH->bits) && ncols == maskH->pitch && aligned16(maskH->p) && (maskH->pitch & 3) == 0) {
     p.aux_bits = maskH->bits; p.xb_s0 = maskH->brs; p.xb_s1 = maskH->bcs; p.xb_g = maskH->bg;
   }
   // weight-stationary fused kernel (csrc/ws_gemm.h): top-layer dgrad from mask bits + layer-0 weight gradient, nothing stored
@@ -691,7 +699,7 @@ int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int c
     const int rc = ws_dgrad(dy, M, nr, layer, *maskH, w0_X, nullptr, max_slab, tag, w0_slabs);
     if (rc <= 0) return rc;
   }
-  if (w0_X && w0_slabs && maskH && layer == 1 && col0 == 0 && !l.ens && !force_scalar) {
+  if (w0_X && w0_slabs && maskH && layer == 1 && col0 == 0 && !l.ens && !force_scalar && !leaky) {      // (the fused epilogue bakes in the ReLU mask)
     // fuse the layer-0 weight / bias gradient into this launch's epilogue (one slab per row tile)
     const int slabs = w0_fused_slabs(p, nz, l.layer_in(0), w0_X->pitch, w0_X->p, w0_X->rs, w0_X->cs, max_slab);
     if (slabs > 0) {
@@ -731,6 +739,7 @@ int Engine::linear_dgrad(const DY& dy, int M, const NetRef& nr, int layer, int c
     if (maskH) return run_gemm<PA_RANK1, PB_PLAIN, E_MASK>(this, CFG_AUTO, p, nz, tag);
     return run_gemm<PA_RANK1, PB_PLAIN, E_PLAIN>(this, CFG_AUTO, p, nz, tag);
   }
+  if (maskH && leaky) return run_gemm<PA_PLAIN, PB_PLAIN, E_LEAKY_MASK>(this, CFG_AUTO, p, nz, tag);      // (a leaky net has two outputs: never rank-1)
   if (maskH) return run_gemm<PA_PLAIN, PB_PLAIN, E_MASK>(this, CFG_AUTO, p, nz, tag);
   return run_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(this, CFG_AUTO, p, nz, tag);
 }
@@ -852,7 +861,7 @@ int Engine::linear_wgrad(const DY& dy, const Mat& X, int M, const NetRef& nr, in
   }
   // the same output-stationary kernel for a hidden layer BELOW the top one of a many-row batch: dZ is a materialised matrix (three products
   // per block instead of the rank-1 form's two, no mask / w_tail); one slab per workgroup
-  if (slabs_out && !dy.rank1 && with_bias && slab0 == 0 && ws_precision_ok() && !force_scalar && !l.ens && !x_dscale && in_row0 == 0 &&
+  if (slabs_out && !dy.rank1 && !leaky && with_bias && slab0 == 0 && ws_precision_ok() && !force_scalar && !l.ens && !x_dscale && in_row0 == 0 &&
       in_rows == in && X.pitch == in && dy.m.pitch == out && ws_wgrad_rows_ok(M, nz)) {
     const int rc = ws_wgrad(dy, X, M, nr, layer, x_dead ? recompute_X0 : nullptr, tag, slabs_out);
     if (rc <= 0) return rc;
@@ -941,7 +950,7 @@ int Engine::mlp_forward(const Mat& X, int M, const NetRef& nr, std::vector<Mat>&
   std::string t = tag;
   if (jobs_done) *jobs_done = false;
   // few batched rows (one to a few runs per engine): the whole pass as ONE launch (small_fwd.h) instead of layer 0 + layer 1 + tail
-  if (small_fwd_on && Ln == 2 && !l.ens && !no_ws && !force_scalar && l.H[0] == SF_N && l.H[1] == SF_N && hs[0].pitch == SF_N && hs[1].pitch == SF_N &&
+  if (small_fwd_on && !leaky && Ln == 2 && !l.ens && !no_ws && !force_scalar && l.H[0] == SF_N && l.H[1] == SF_N && hs[0].pitch == SF_N && hs[1].pitch == SF_N &&
       (long)M * R * nr.nz1 <= small_fwd_max_rows) {
     SmallFwdP w = small_fwd_p(X, M, nr, fwd_only ? nullptr : &hs[0], fwd_only ? nullptr : &hs[1], out);
     if (fuse_small && jobs && jobs_done && njobs >= 1 && njobs <= 3 && nr.nz1 == 1 && l.out_dim == 2 * ad && ad <= 8 && out.pitch == l.out_dim) {
@@ -968,7 +977,7 @@ int Engine::mlp_forward(const Mat& X, int M, const NetRef& nr, std::vector<Mat>&
   bool tail_done = false;
   for (int i = 0; i < Ln; ++i) {
     if (i == 0 && Ln >= 2) continue;         // layer 0 is issued together with layer 1 (fused into it when the ws kernel applies)
-    if (linear_fwd(i == 0 ? X : hs[i - 1], M, nr, i, hs[i], E_BIAS_RELU, nullptr, (t + ".fwd" + std::to_string(i)).c_str(), 0, -1,
+    if (linear_fwd(i == 0 ? X : hs[i - 1], M, nr, i, hs[i], leaky ? E_BIAS_LEAKY : E_BIAS_RELU, nullptr, (t + ".fwd" + std::to_string(i)).c_str(), 0, -1,
                    i == Ln - 1 ? &out : nullptr, i == Ln - 1 ? &tail_done : nullptr, i == 1 ? &X : nullptr, (t + ".fwd0").c_str())) return -1;
   }
   if (tail_done) return 0;                 // single-output tail folded into the last hidden layer's epilogue
@@ -1123,6 +1132,7 @@ static SampleJob make_job(int head_row0, int rows, int rep, const Mat& eps, cons
 #include "algo_mobile.inc"
 #include "algo_rcsl.inc"
 #include "algo_rcsl_gauss.inc"
+#include "algo_autoreg.inc"
 
 namespace orl {
 
@@ -1213,6 +1223,7 @@ int Engine::init(const orl_config& c) {
   ws_geo.cus = (c.ws_cus >= 8 && c.ws_cus <= 256) ? c.ws_cus : 256;
   read_env();
   R = c.n_runs; B = c.batch_size; od = c.obs_dim; ad = c.act_dim;
+  leaky = c.algo == ORL_ALGO_AUTOREG;
   N = c.num_repeat_actions > 0 ? c.num_repeat_actions : 1;
   // MOBILE: the longest row batch is the penalty pass's S * E * B rows; N sizes the tail scratch of build_common for it (9 B N >= 3 S E B)
   if (c.algo == ORL_ALGO_MOBILE) N = std::max(1, (std::max(c.mobile_num_samples, 1) * std::max(c.mobile_num_elites, 1) + 2) / 3);
@@ -1269,6 +1280,7 @@ int Engine::init(const orl_config& c) {
     case ORL_ALGO_MOBILE: rc = mobile_build(); break;
     case ORL_ALGO_RCSL: rc = rcsl_build(); break;
     case ORL_ALGO_RCSL_GAUSS: rc = rcslg_build(); break;
+    case ORL_ALGO_AUTOREG: rc = autoreg_build(); break;
   }
   if (rc) return rc;
   { Mat lc; lc.p = (float*)lab_clk(0); lc.pitch = 192; taps["lab_clk"] = {lc, 1, 192}; }      // shader-clock stamps of lab builds (small_bwd.hip)
@@ -1286,7 +1298,7 @@ int Engine::init(const orl_config& c) {
 }
 
 int Engine::enqueue_sample() {
-  if (is_rcsl(cfg.algo)) return 0;      // rcsl_step's / rcslg_step's own input launch gathers (k_rcsl_prepare)
+  if (is_epoch_algo(cfg.algo)) return 0;      // rcsl_step's / rcslg_step's / autoreg_step's own input launch gathers (k_rcsl_prepare, k_autoreg_prepare)
   if (!buf || !buf->obs) return fail("no replay buffer attached (orl_engine_attach_buffer)");
   GatherP g;
   memset(&g, 0, sizeof(g));
@@ -1398,6 +1410,7 @@ int Engine::enqueue_step(int variant) {
     case ORL_ALGO_MOBILE: rc = mobile_step(); break;
     case ORL_ALGO_RCSL: rc = rcsl_step(); break;
     case ORL_ALGO_RCSL_GAUSS: rc = rcslg_step(); break;
+    case ORL_ALGO_AUTOREG: rc = autoreg_step(); break;
   }
   if (rc) return rc;
   if (tick_folded) return 0;               // the step's own kernels advanced the counter
@@ -1423,9 +1436,9 @@ extern "C" {
 
 const char* orl_last_error(void) { return g_err.c_str(); }
 #ifdef ORL_SPLIT_BF16
-const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-bf16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL RCSL_GAUSS)"; }
+const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-bf16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL RCSL_GAUSS AUTOREG)"; }
 #else
-const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-fp16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL RCSL_GAUSS)"; }
+const char* orl_version(void) { return "orl-engine 0.5 (gfx950; fp32 MFMA + split-fp16 MFMA; CQL IQL TD3BC EDAC SAC(MOPO) COMBO MCQ MOBILE RCSL RCSL_GAUSS AUTOREG)"; }
 #endif
 int orl_split_bits(void) { return ORL_SPLIT_BITS; }
 
@@ -1451,6 +1464,7 @@ void orl_config_default(orl_config* c, int32_t algo) {
   c->mobile_num_samples = 10; c->mobile_num_elites = 5; c->mobile_real_rows = 12; c->penalty_coef = 1.5f;   /* run_mobile.py:45-52: int(256 * 0.05) real rows */
   if (algo == ORL_ALGO_MOBILE) { c->deterministic_backup = 1; }                                             /* run_mobile.py:157 */
   if (algo == ORL_ALGO_RCSL) { c->n_hidden = 4; for (int i = 0; i < 4; ++i) c->hidden[i] = 200; c->actor_lr = 1e-3f; }   /* run_rcsl.py:125-127 */
+  if (algo == ORL_ALGO_AUTOREG) { c->n_hidden = 4; for (int i = 0; i < 4; ++i) c->hidden[i] = 200; c->actor_lr = 1e-3f; }   /* run_regress.py */
   if (algo == ORL_ALGO_RCSL_GAUSS) { c->n_hidden = 4; for (int i = 0; i < 4; ++i) c->hidden[i] = 1024; c->actor_lr = 1e-3f; }   /* run_rcsl_gauss.py */
   if (algo == ORL_ALGO_MCQ) { c->hidden[0] = c->hidden[1] = 400; c->actor_lr = c->critic_lr = c->alpha_lr = 3e-4f; c->target_entropy = -(float)c->act_dim; }
 }
@@ -1929,7 +1943,7 @@ int orl_engine_attach_buffer(orl_engine* h, orl_buffer* b) {
 int orl_engine_attach_model_buffer(orl_engine* h, orl_buffer* m, int32_t real_rows) {
   Engine& e = h->e;
   if (!m) { if (e.mbuf || !e.mbufs.empty()) { e.mbuf = nullptr; e.mbufs.clear(); e.mbuf_real_rows = 0; e.drop_graphs(); } return 0; }
-  if (is_rcsl(e.cfg.algo)) return fail("attach_model_buffer: not available for RCSL engines (one dataset, no real + model batch)");
+  if (is_epoch_algo(e.cfg.algo)) return fail("attach_model_buffer: not available for RCSL engines (one dataset, no real + model batch)");
   if (m->b.od != e.od || m->b.ad != e.ad) return fail("attach_model_buffer: obs/act dims differ from the engine's");
   if (m->b.dev != e.dev) return fail("attach_model_buffer: buffer lives on another device");
   if (!m->b.d_n || m->b.cap < 1) return fail("attach_model_buffer: the model buffer must be a ring (orl_buffer_reserve)");
@@ -1957,7 +1971,7 @@ int Engine::upload_model_table() {
 int orl_engine_attach_model_buffers(orl_engine* h, orl_buffer* const* models, int32_t n, int32_t real_rows) {
   Engine& e = h->e;
   if (!models || n == 0) return orl_engine_attach_model_buffer(h, nullptr, 0);
-  if (is_rcsl(e.cfg.algo)) return fail("attach_model_buffers: not available for RCSL engines (one dataset, no real + model batch)");
+  if (is_epoch_algo(e.cfg.algo)) return fail("attach_model_buffers: not available for RCSL engines (one dataset, no real + model batch)");
   char msg[192];
   if (n != e.cfg.n_runs) {
     snprintf(msg, sizeof(msg), "attach_model_buffers: %d rings for an engine of %d runs (one ring per run)", (int)n, (int)e.cfg.n_runs);
@@ -2004,10 +2018,11 @@ int orl_step(orl_engine* h, const orl_batch* b, const orl_noise* nz, float* metr
   if (b) {
     const bool dv = b->on_device != 0;
     if (copy_rows(e, e.W("b_obs2"), b->observations, B, e.od, dv, 0)) return -1;
-    const bool rcsl = is_rcsl(e.cfg.algo);      // (reads observations, actions and the return-to-go in `rewards` only)
+    const bool rcsl = is_epoch_algo(e.cfg.algo);      // (reads observations, actions and the return-to-go in `rewards` only)
+    const bool no_rtg = e.cfg.algo == ORL_ALGO_AUTOREG;      // (... and the autoregressive policy not even that)
     if (!(rcsl && !b->next_observations) && copy_rows(e, e.W("b_obs2"), b->next_observations, B, e.od, dv, B)) return -1;
     if (copy_rows(e, e.W("b_act"), b->actions, B, e.ad, dv)) return -1;
-    if (copy_rows(e, e.W("b_rew"), b->rewards, B, 1, dv)) return -1;
+    if (!(no_rtg && !b->rewards) && copy_rows(e, e.W("b_rew"), b->rewards, B, 1, dv)) return -1;
     if (!(rcsl && !b->terminals) && copy_rows(e, e.W("b_term"), b->terminals, B, 1, dv)) return -1;
   }
   e.rcsl_mode = RI_SLOTS;
@@ -2117,7 +2132,7 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
 int orl_learn_epoch(orl_engine* h, const int64_t* order, int64_t order_len, int on_device, float* metrics_mean, float* elapsed_ms) {
   Engine& e = h->e;
   ORL_HIP(hipSetDevice(e.dev));
-  if (!is_rcsl(e.cfg.algo))
+  if (!is_epoch_algo(e.cfg.algo))
     return fail("orl_learn_epoch: available for RCSL engines only (the other algorithms sample with replacement: orl_learn_n)");
   if (!order) return fail("orl_learn_epoch: null row order");
   if (!e.buf || !e.buf->obs || e.buf->n < 1) return fail("orl_learn_epoch: no replay buffer attached");
@@ -2213,6 +2228,15 @@ int orl_learn_epoch(orl_engine* h, const int64_t* order, int64_t order_len, int 
   unsigned int bad = 0;
   if (e.health_update(m.data(), n_steps, &bad)) return -1;
   return bad ? ORL_RC_UNHEALTHY : 0;
+}
+
+int orl_autoreg_sample(orl_engine* h, const float* obs, int64_t n, const float* eps, int on_device, float* act_out) {
+  Engine& e = h->e;
+  if (e.cfg.algo != ORL_ALGO_AUTOREG) return fail("orl_autoreg_sample: not an AUTOREG engine");
+  if (!obs || !act_out) return fail("orl_autoreg_sample: null observations / output");
+  if (n < 1 || n > (1 << 24)) return fail("orl_autoreg_sample: n must be in [1, 2^24] rows per run");
+  ORL_HIP(hipSetDevice(e.dev));
+  return e.autoreg_sample(obs, (long)n, eps, on_device != 0, act_out);
 }
 
 int orl_engine_set_next_samples(orl_engine* h, const float* samples, int on_device) {

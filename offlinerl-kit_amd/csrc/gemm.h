@@ -183,7 +183,11 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 enum { PB_PLAIN = 0, PB_ONES = 1 };                                    // prologue on B elements
 enum { E_PLAIN = 0, E_BIAS = 1, E_BIAS_RELU = 2, E_MASK = 3, E_WGRAD = 4,
        E_BIAS_SWISH = 5,      // h = z sigmoid(z), z = acc + bias; z also to z_out (C's strides) when non-null (the dynamics ensemble, Swish)
-       E_SWISH_GRAD = 6 };    // C = acc * sigmoid(z) (1 + z (1 - sigmoid(z))) with z = aux[m][n]: the Swish counterpart of E_MASK
+       E_SWISH_GRAD = 6,      // C = acc * sigmoid(z) (1 + z (1 - sigmoid(z))) with z = aux[m][n]: the Swish counterpart of E_MASK
+       E_BIAS_LEAKY = 7,      // h = v > 0 ? v : 0.01 v, v = acc + bias (nn.LeakyReLU's default slope: the autoregressive policy)
+       E_LEAKY_MASK = 8 };    // C = acc * (h > 0 ? 1 : 0.01) with the stored activation h = aux[m][n] (the slope is positive: h has the sign of
+                              // its pre-activation; h == 0 takes the slope, as leaky_relu_backward does): the LeakyReLU counterpart of E_MASK
+#define ORL_LEAKY_SLOPE 0.01f
 enum { L_SCALAR = 0, L_VECK = 1, L_BLK4 = 2, L_VECKU = 3 };            // operand loaders
 
 template <typename T>

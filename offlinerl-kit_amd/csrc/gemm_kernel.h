@@ -458,8 +458,8 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
   float* bo = (EPI == E_WGRAD && p.bias_out) ? p.bias_out + z0 * p.bo_s0 + z1 * p.bo_s1 + (long)ks * p.bo_ks : nullptr;
   const bool vec_ok = (p.c_sn == 1) && ((p.c_sr & 3) == 0) && ((((uintptr_t)Cg) & 15) == 0) &&
                       (EPI != E_MASK || p.aux_bits != nullptr || (((p.aux_sr & 3) == 0) && ((((uintptr_t)aux) & 15) == 0))) &&
-                      (EPI != E_SWISH_GRAD || (((p.aux_sr & 3) == 0) && ((((uintptr_t)aux) & 15) == 0))) &&
-                      ((EPI != E_BIAS && EPI != E_BIAS_RELU && EPI != E_BIAS_SWISH) || ((((uintptr_t)bias) & 15) == 0));
+                      ((EPI != E_SWISH_GRAD && EPI != E_LEAKY_MASK) || (((p.aux_sr & 3) == 0) && ((((uintptr_t)aux) & 15) == 0))) &&
+                      ((EPI != E_BIAS && EPI != E_BIAS_RELU && EPI != E_BIAS_SWISH && EPI != E_BIAS_LEAKY) || ((((uintptr_t)bias) & 15) == 0));
   float* __restrict__ zo = (EPI == E_BIAS_SWISH && p.z_out) ? p.z_out + z0 * p.c_s0 + z1 * p.c_s1 : nullptr;
   if (EPI == E_WGRAD && PA == PA_RANK1 && LA == L_BLK4) {
     if (p.tail_w_out && tn == 0) {
@@ -540,7 +540,7 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
     const int n = n0 + 4 * c4;
     const bool n_ok = n < p.N;
     // the mask tile is fetched first (clamped addresses, no branches) so its latency hides behind the LDS staging
-    f32x4 hv[(EPI == E_MASK || EPI == E_SWISH_GRAD) ? NPASS : 1];
+    f32x4 hv[(EPI == E_MASK || EPI == E_SWISH_GRAD || EPI == E_LEAKY_MASK) ? NPASS : 1];
     const bool xbits = (EPI == E_MASK) && (p.aux_bits != nullptr);           // uniform: the mask comes as packed bits
     if (EPI == E_MASK) {
       const unsigned int* xb = p.aux_bits + z0 * p.xb_s0 + z1 * p.xb_s1;
@@ -552,7 +552,7 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
         else hv[i] = *(const f32x4*)&aux[(long)m * p.aux_sr + (n_ok ? n : 0)];
       }
     }
-    if (EPI == E_SWISH_GRAD) {
+    if (EPI == E_SWISH_GRAD || EPI == E_LEAKY_MASK) {
 #pragma unroll
       for (int i = 0; i < NPASS; ++i) {
         int m = m0 + r0 + i * RPP;
@@ -577,7 +577,7 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
       }
     }
     f32x4 bv = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH) bv = *(const f32x4*)&bias[n_ok ? n : 0];
+    if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH || EPI == E_BIAS_LEAKY) bv = *(const f32x4*)&bias[n_ok ? n : 0];
     const bool tq = (EPI == E_BIAS_RELU) && (p.tq_out != nullptr);       // uniform
     f32x4 tw = (f32x4){0.f, 0.f, 0.f, 0.f};
     float tq_bias = 0.f;
@@ -606,7 +606,7 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
       const int m = m0 + r;
       if (r < TM) {
         f32x4 v = *(const f32x4*)&cs[r * CP + 4 * c4];
-        if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH) v += bv;
+        if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH || EPI == E_BIAS_LEAKY) v += bv;
         if (EPI == E_BIAS_SWISH) {
           if (zo && n_ok && m < p.M) *(f32x4*)&zo[(long)m * p.c_sr + n] = v;
 #pragma unroll
@@ -619,6 +619,14 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
         if (EPI == E_BIAS_RELU) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
+        }
+        if (EPI == E_BIAS_LEAKY) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : ORL_LEAKY_SLOPE * v[j];
+        }
+        if (EPI == E_LEAKY_MASK) {                             // h has the sign of its pre-activation; h == 0 takes the slope (leaky_relu_backward)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] *= hv[i][j] > 0.f ? 1.0f : ORL_LEAKY_SLOPE;
         }
         if (EPI == E_MASK) {
           if (xbits) {
@@ -710,7 +718,7 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
         f32x4 v = acc[a][b];
         const int nlim = p.N;
         if (vec_ok && nb + 4 <= nlim) {
-          if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH) { const f32x4 bv = *(const f32x4*)&bias[nb]; v += bv; }
+          if (EPI == E_BIAS || EPI == E_BIAS_RELU || EPI == E_BIAS_SWISH || EPI == E_BIAS_LEAKY) { const f32x4 bv = *(const f32x4*)&bias[nb]; v += bv; }
           if (EPI == E_BIAS_SWISH) {
             if (zo) *(f32x4*)&zo[(long)m * p.c_sr + nb] = v;
   #pragma unroll
@@ -724,6 +732,15 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
           if (EPI == E_BIAS_RELU) {
   #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
+          }
+          if (EPI == E_BIAS_LEAKY) {
+  #pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : ORL_LEAKY_SLOPE * v[r];
+          }
+          if (EPI == E_LEAKY_MASK) {
+            const f32x4 hv = *(const f32x4*)&aux[(long)m * p.aux_sr + nb];
+  #pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] *= hv[r] > 0.f ? 1.0f : ORL_LEAKY_SLOPE;
           }
           if (EPI == E_MASK) {
             const f32x4 hv = *(const f32x4*)&aux[(long)m * p.aux_sr + nb];
@@ -740,6 +757,8 @@ __global__ __launch_bounds__(CFG::NT) void gemm16_kernel(const GemmP p) {
             if (EPI == E_BIAS) x += bias[n];
             if (EPI == E_BIAS_RELU) { x += bias[n]; x = x > 0.f ? x : 0.f; }
             if (EPI == E_MASK) x = aux[(long)m * p.aux_sr + n] > 0.f ? x : 0.f;
+            if (EPI == E_BIAS_LEAKY) { x += bias[n]; x = x > 0.f ? x : ORL_LEAKY_SLOPE * x; }
+            if (EPI == E_LEAKY_MASK) x *= aux[(long)m * p.aux_sr + n] > 0.f ? 1.0f : ORL_LEAKY_SLOPE;
             if (EPI == E_BIAS_SWISH) {
               x += bias[n];
               if (zo) zo[(long)m * p.c_sr + (long)n * p.c_sn] = x;

@@ -1812,4 +1812,138 @@ __global__ __launch_bounds__(256) void k_rcslg_head(RcslGaussP p) {
   grad_scale_publish(amax, sh, p.gs_out, r);
 }
 
+// ================================================================================================
+// Autoregressive behaviour policy (policy/others/autoregressive.py:64-96; tests/autoreg_oracle.py)
+//   p(a | s) = prod_j N(a_j | s, a_<j): every batch row b becomes A expanded rows j * B + b (the reference's order) of the input
+//   X = [obs_b | act_b[k] 1[k < j] | onehot_j | 0-pad] with the target t = act_b[j]; the net ends in Linear(., 2) + LeakyReLU:
+//   out = leaky(z_tail), mean = out[0], logstd = out[1], loss = mean over valid expanded rows of logstd + ((t - mean) e^-logstd)^2 / 2 + log(2 pi) / 2.
+// ================================================================================================
+enum { AR_AMAX = 32 };
+// the step's inputs in one launch; MODE as for k_rcsl_prepare (the return-to-go is not read: the reward column, where there is one, only
+// fills its batch slot).  grid (ceil(B * XP / 256), R); one thread per (batch row, input column), which writes that column of the A expanded rows.
+struct AutoregPrepP {
+  const float *d_obs, *d_act, *d_rew; long n; int OP, AP;      // dataset (d_rew may be null)
+  float* b_obs; long bo_rs; float* b_act; long ba_rs; float* b_rew; long br_rs;
+  float* X; long x_rs; int XP;                                 // [R][A * B][XP]
+  float* T; long t_rs;                                         // [R][A * B]
+  long long* idx_out;                                          // [R][B]
+  const long long* order; const EpochCell* cell;               // RI_ORDER
+  int B, od, A;
+  unsigned long long seed; const unsigned long long* gstep;
+};
+template <int MODE>
+__global__ void k_autoreg_prepare(AutoregPrepP p) {
+  const int r = blockIdx.y;
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;
+  const int b = (int)(u / p.XP), c = (int)(u - (long)b * p.XP);
+  if (b >= p.B) return;
+  float* bo = p.b_obs + (long)r * p.bo_rs + (long)b * p.OP;
+  float* ba = p.b_act + (long)r * p.ba_rs + (long)b * p.AP;
+  const float *so = bo, *sa = ba;
+  if (MODE != RI_SLOTS) {
+    long long j;
+    if (MODE == RI_DRAWN) j = orl_draw_index(p.seed, r, b, *p.gstep, p.n);
+    else {
+      const unsigned long long pos = *p.gstep - p.cell->base;
+      j = pos < (unsigned long long)p.cell->n_steps ? p.order[(long)r * p.cell->order_len + (long)pos * p.B + b] : -1;
+      if (j >= p.n) j = -1;                                    // (refused by the host before the epoch starts; never read out of bounds)
+    }
+    const long row = j < 0 ? 0 : (long)j;
+    so = p.d_obs + row * p.OP; sa = p.d_act + row * p.AP;
+    if (c == 0) {
+      p.idx_out[(long)r * p.B + b] = j;
+      if (p.d_rew) p.b_rew[(long)r * p.br_rs + b] = p.d_rew[row];
+    }
+  }
+  const int k = c - p.od;                                      // action column k, one-hot column k - A
+  float v = 0.f;
+  if (c < p.od) v = so[c];
+  else if (k < p.A) v = sa[k];
+  if (MODE != RI_SLOTS) {                                      // the batch slots ("b_obs", "b_act") show what was gathered
+    if (c < p.od) bo[c] = v;
+    else if (k < p.A) ba[k] = v;
+  }
+  float* x = p.X + (long)r * p.x_rs + (long)b * p.XP + c;
+  const long js = (long)p.B * p.XP;
+  for (int j = 0; j < p.A; ++j) {
+    float w = 0.f;
+    if (c < p.od) w = v;
+    else if (k < p.A) w = k < j ? v : 0.f;
+    else if (k < 2 * p.A) w = (k - p.A == j) ? 1.0f : 0.f;
+    x[j * js] = w;
+  }
+  if (c >= p.od && k < p.A) p.T[(long)r * p.t_rs + (long)k * p.B + b] = v;
+}
+
+// out = leaky(z_tail), the masked Gaussian NLL, dz_tail = dLoss/dout * leaky'(out), the metric and the split-precision scale in one launch.
+// One workgroup of 256 per run; thread t owns the expanded rows t, t + 256, ... and the block sum has a fixed shape: no floating-point
+// atomics, nothing depends on the run index, so identical runs stay bit-identical and an ordered epoch equals its steps one by one.
+// A padding batch row (idx < 0) invalidates its A expanded rows; the mean divides by valid rows x A.
+struct AutoregHeadP {
+  const float* z; long z_rs;            // [R][M][2] tail pre-activation
+  const float* T; long t_rs;            // [R][M]
+  float* out; float* dz;                // [R][M][2] (strides of z)
+  const long long* idx;                 // [R][B] recorded row indices (negative = padding), or null: every row is valid
+  int B, A; MetricsP m; int slot;
+  float* gs_out;                        // split precision: dynamic scale of dz [R], or null
+};
+__global__ __launch_bounds__(256) void k_autoreg_head(AutoregHeadP p) {
+  __shared__ float sh[4];
+  const int r = blockIdx.x, tid = threadIdx.x, B = p.B, M = p.A * p.B;
+  const long long* idx = p.idx ? p.idx + (long)r * B : nullptr;
+  float nv = 0.f;                       // (a count below 2^24: exact in fp32)
+  for (int b = tid; b < B; b += 256) nv += (!idx || idx[b] >= 0) ? 1.0f : 0.0f;
+  nv = block_sum256(nv, sh);
+  const float cnt = nv * (float)p.A, inv = cnt > 0.f ? 1.0f / cnt : 0.f;
+  const float* z = p.z + (long)r * p.z_rs;
+  const float* T = p.T + (long)r * p.t_rs;
+  float* out = p.out + (long)r * p.z_rs;
+  float* dz = p.dz + (long)r * p.z_rs;
+  float ls = 0.f, amax = 0.f;
+  for (int m = tid; m < M; m += 256) {
+    const int b = m % B;
+    const bool valid = !idx || idx[b] >= 0;
+    const float z0 = z[2 * m], z1 = z[2 * m + 1];
+    const float mean = z0 > 0.f ? z0 : ORL_LEAKY_SLOPE * z0, lsd = z1 > 0.f ? z1 : ORL_LEAKY_SLOPE * z1;
+    out[2 * m] = mean; out[2 * m + 1] = lsd;
+    const float is = expf(-lsd), d = (T[m] - mean) * is;
+    if (valid) ls += lsd + 0.5f * d * d + 0.9189385332046727f;
+    const float g0 = valid ? -d * is * inv * (mean > 0.f ? 1.0f : ORL_LEAKY_SLOPE) : 0.f;
+    const float g1 = valid ? (1.0f - d * d) * inv * (lsd > 0.f ? 1.0f : ORL_LEAKY_SLOPE) : 0.f;
+    dz[2 * m] = g0; dz[2 * m + 1] = g1;
+    amax = fmaxf(amax, fmaxf(fabsf(g0), fabsf(g1)));
+  }
+  ls = block_sum256(ls, sh);
+  if (tid == 0) metric_set(p.m, r, p.slot, ls * inv);
+  grad_scale_publish(amax, sh, p.gs_out, r);
+}
+
+// sampling (autoregressive.py:28-54), between two forward passes: a_j = mean + e^logstd eps_j from the tail of pass j goes to column
+// od + j of the input, the one-hot moves on to j + 1.  (The reference's "logstd.exp() == 0 -> mean" is the same value: no branch.)
+// first != 0: the launch in front of pass 0 instead -- X = [obs | 0 | onehot_0 | 0-pad].  grid (ceil(n / 256), R)
+struct AutoregDrawP {
+  const float* z; long z_rs;            // [R][n][2] tail pre-activation of pass j
+  const float* eps; long e_rs;          // [R][n][A]
+  const float* obs; long o_rs;          // [R][n][od] (first launch)
+  float* X; long x_rs; int XP;
+  long n; int od, A, j, first;
+};
+__global__ void k_autoreg_draw(AutoregDrawP p) {
+  const int r = blockIdx.y;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.n) return;
+  float* x = p.X + (long)r * p.x_rs + i * p.XP;
+  if (p.first) {
+    const float* o = p.obs + (long)r * p.o_rs + i * p.od;
+    for (int c = 0; c < p.XP; ++c) x[c] = c < p.od ? o[c] : (c == p.od + p.A ? 1.0f : 0.f);
+    return;
+  }
+  const float* z = p.z + (long)r * p.z_rs + 2 * i;
+  const float z0 = z[0], z1 = z[1];
+  const float mean = z0 > 0.f ? z0 : ORL_LEAKY_SLOPE * z0, lsd = z1 > 0.f ? z1 : ORL_LEAKY_SLOPE * z1;
+  x[p.od + p.j] = mean + expf(lsd) * p.eps[(long)r * p.e_rs + i * p.A + p.j];
+  x[p.od + p.A + p.j] = 0.f;
+  if (p.j + 1 < p.A) x[p.od + p.A + p.j + 1] = 1.0f;
+}
+
 }  // namespace orl

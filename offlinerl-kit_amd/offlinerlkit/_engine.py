@@ -16,9 +16,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "liborlengine.so")
 
-ALGO_CQL, ALGO_IQL, ALGO_TD3BC, ALGO_EDAC, ALGO_SAC, ALGO_MCQ, ALGO_MOBILE, ALGO_RCSL, ALGO_RCSL_GAUSS = 0, 1, 2, 3, 4, 5, 6, 7, 8
+ALGO_CQL, ALGO_IQL, ALGO_TD3BC, ALGO_EDAC, ALGO_SAC, ALGO_MCQ, ALGO_MOBILE, ALGO_RCSL, ALGO_RCSL_GAUSS, ALGO_AUTOREG = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ALGO_ID = {"cql": ALGO_CQL, "iql": ALGO_IQL, "td3bc": ALGO_TD3BC, "edac": ALGO_EDAC, "sac": ALGO_SAC, "mcq": ALGO_MCQ,
-           "mobile": ALGO_MOBILE, "rcsl": ALGO_RCSL, "rcsl_gauss": ALGO_RCSL_GAUSS}
+           "mobile": ALGO_MOBILE, "rcsl": ALGO_RCSL, "rcsl_gauss": ALGO_RCSL_GAUSS, "autoreg": ALGO_AUTOREG}
 MAX_HIDDEN, MAX_METRICS, MAX_NOISE = 4, 8, 6
 NET_ACTOR, NET_CRITIC1, NET_CRITIC2, NET_CRITIC1_OLD, NET_CRITIC2_OLD, NET_CRITIC_V, NET_ACTOR_OLD, NET_VAE_ENC, NET_VAE_DEC = range(9)
 NUM_NETS = 9
@@ -62,6 +62,8 @@ ABI_SYMBOLS = [
     "orl_dynsample_next", "orl_engine_set_next_samples", "orl_engine_lcb_penalty",
     # RCSL: one ordered pass over the attached buffer
     "orl_learn_epoch",
+    # the autoregressive behaviour policy: sequential sampling
+    "orl_autoreg_sample",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -182,6 +184,7 @@ def load_library(path: Optional[str] = None):
     lib.orl_step.argtypes = [C.c_void_p, C.POINTER(OrlBatch), C.POINTER(OrlNoise), C.c_void_p]
     lib.orl_learn_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_learn_epoch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    lib.orl_autoreg_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
     lib.orl_engine_set_next_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_lcb_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_health.argtypes = [C.c_void_p, C.c_void_p]
@@ -495,6 +498,24 @@ class Engine:
         ms = C.c_float()
         self._check_step(self.lib.orl_learn_epoch(self._h, ptr, order_len, 1 if on_device else 0, m.ctypes.data, C.byref(ms)), "orl_learn_epoch")
         return m[:, :len(self.metric_names)], ms.value
+
+    def autoreg_sample(self, obs, eps=None, n: Optional[int] = None, out_ptr: Optional[int] = None, on_device=False):
+        """AUTOREG: actions for ``obs`` [n_runs][n][obs_dim] (orl_autoreg_sample); ``eps`` [n_runs][n][act_dim] teacher-forces the
+        standard normals (None: device Philox).  Host arrays in, a host array [n_runs][n][act_dim] out; with ``on_device`` ``obs`` /
+        ``eps`` / ``out_ptr`` are raw device pointers and ``n`` the rows per run."""
+        if on_device:
+            _check(self.lib.orl_autoreg_sample(self._h, int(obs), int(n), None if eps is None else int(eps), 1, int(out_ptr)), "orl_autoreg_sample")
+            return None
+        o = _f32(obs)
+        if o.ndim != 3 or o.shape[0] != self.n_runs or o.shape[2] != self.cfg.obs_dim:
+            raise ValueError(f"obs: expected [n_runs = {self.n_runs}, n, obs_dim = {self.cfg.obs_dim}], got {o.shape}")
+        e = None if eps is None else _f32(eps)
+        if e is not None and e.shape != (self.n_runs, o.shape[1], self.cfg.act_dim):
+            raise ValueError(f"eps: expected {(self.n_runs, o.shape[1], self.cfg.act_dim)}, got {e.shape}")
+        out = np.zeros((self.n_runs, o.shape[1], self.cfg.act_dim), dtype=np.float32)
+        _check(self.lib.orl_autoreg_sample(self._h, o.ctypes.data, o.shape[1], None if e is None else e.ctypes.data, 0, out.ctypes.data),
+               "orl_autoreg_sample")
+        return out
 
     # ---- health (include/orl_engine.h: ORL_HEALTH_*) ----
     def _check_step(self, rc: int, what: str):

@@ -3,9 +3,11 @@ its kernels (MOPO, COMBO, MCQ: SURVEY §8(f)3), engine-backed, and RAMBO, whose 
 dynamics engine (``orl_dynadv_*``), and MOBILE, whose penalty pass runs on the dynamics engine (``orl_dynsample_next``) and the policy
 engine (``ORL_ALGO_MOBILE``), and RCSL's return-conditioned policies: the deterministic one (``ORL_ALGO_RCSL``: one MLP on [obs | rtg],
 MSE on the dataset action) and the Gaussian one (``ORL_ALGO_RCSL_GAUSS``: the same MLP down to a latent, a DiagGaussian head with a
-clamped state-conditioned sigma, Gaussian NLL); ``learn_epoch`` is one ordered pass over the dataset (``orl_learn_epoch``).
-(The reference package also exports the diffusion behaviour policy and the autoregressive models; those are out of scope here, and with
-them ``RcslPolicy.rollout`` / ``RcslGaussianPolicy.rollout``.)"""
+clamped state-conditioned sigma, Gaussian NLL); ``learn_epoch`` is one ordered pass over the dataset (``orl_learn_epoch``).  Their
+``rollout`` rolls a behaviour policy through a dynamics model; the behaviour policy here is ``AutoregressivePolicy``
+(``ORL_ALGO_AUTOREG``: p(a | s) as a product of per-dimension Gaussians from one LeakyReLU net, trained on the act_dim-fold expanded
+batch and sampled by ``orl_autoreg_sample``).
+(The reference package also exports the diffusion behaviour policy, which needs ``diffusers``; it is out of scope here.)"""
 from .base_policy import BasePolicy, EnginePolicy
 from .iql import IQLPolicy
 from .sac_family import CQLPolicy, EDACPolicy
@@ -15,6 +17,7 @@ from .mcq import MCQPolicy
 from .rambo import RAMBOPolicy
 from .mobile import MOBILEPolicy
 from .rcsl import RcslPolicy, RcslGaussianPolicy
+from .autoregressive import AutoregressivePolicy
 
 __all__ = ["BasePolicy", "EnginePolicy", "CQLPolicy", "IQLPolicy", "TD3BCPolicy", "EDACPolicy", "SACPolicy", "MOPOPolicy", "COMBOPolicy", "MCQPolicy",
-           "RAMBOPolicy", "MOBILEPolicy", "RcslPolicy", "RcslGaussianPolicy"]
+           "RAMBOPolicy", "MOBILEPolicy", "RcslPolicy", "RcslGaussianPolicy", "AutoregressivePolicy"]

@@ -4,11 +4,13 @@ clamped sigma, the Gaussian negative log-likelihood of the dataset action.  Both
 
 The return-to-go travels where the other algorithms carry the reward (``orl_batch.rewards``, the ``rew`` column of a ``DeviceBuffer``).
 ``learn_epoch`` is the reference trainer's inner loop -- one pass over a shuffled dataset, every row once, last batch partial -- as one
-engine call over a caller-supplied row order (``orl_learn_epoch``).  ``rollout()`` needs the diffusion behaviour policy and is not here.
+engine call over a caller-supplied row order (``orl_learn_epoch``).  ``rollout()`` (rcsl.py:57-120) rolls a behaviour policy -- here
+``AutoregressivePolicy``, or anything with the diffusion policy's interface -- through a dynamics model on the host.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from collections import defaultdict
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -28,47 +30,12 @@ def epoch_order(n_rows: int, batch_size: int, n_runs: int = 1, generator: Option
     return order
 
 
-class _RcslBase(EnginePolicy):
-    """what the two return-conditioned policies share: the constructor, the backbone check, ``learn`` on {observations, actions, rtgs},
-    ``learn_epoch`` and the refusal of ``rollout``"""
+class _EpochPolicy(EnginePolicy):
+    """what the policies trained by ``RcslPolicyTrainer`` share (the two return-conditioned ones and ``AutoregressivePolicy``): a step on
+    named batch arrays and ``learn_epoch``"""
 
-    def __init__(self, dynamics, rollout_policy, rcsl: nn.Module, rcsl_optim: torch.optim.Optimizer, device="cpu") -> None:
-        super().__init__()
-        self.dynamics = dynamics
-        self.rollout_policy = rollout_policy
-        self.rcsl = rcsl
-        self.rcsl_optim = rcsl_optim
-        self.device = device
-        _adam_hyper(rcsl_optim)
-        self._dims()
-
-    def _dims(self):
-        in_dim, outs = _backbone_dims(self.rcsl.backbone)
-        if len(outs) < 2:
-            raise NotImplementedError(f"{type(self).__name__} expects MLP(obs_dim + 1, hidden_dims, output_dim=act_dim): at least one hidden layer and the output layer")
-        hidden, act_dim = outs[:-1], outs[-1]
-        if len(hidden) > _engine.MAX_HIDDEN:
-            raise NotImplementedError(f"the HIP engine supports up to {_engine.MAX_HIDDEN} hidden layers, the backbone has {len(hidden)}")
-        n_mods = len(list(self.rcsl.backbone.model))
-        if n_mods != 2 * len(hidden) + 1 or getattr(self.rcsl.backbone, "activation_cls", nn.ReLU) is not nn.ReLU:
-            raise NotImplementedError(f"{type(self).__name__} expects a [Linear, ReLU] x L + Linear backbone")
-        return in_dim - 1, act_dim, hidden
-
-    def _nets(self):
-        return {_engine.NET_ACTOR: self.rcsl}
-
-    def _optims(self):
-        return {_engine.OPT_ACTOR: self.rcsl_optim}
-
-    def _config(self) -> Dict:
-        od, ad, hidden = self._dims()
-        return dict(obs_dim=od, act_dim=ad, hidden=hidden, actor_lr=float(self.rcsl_optim.param_groups[0]["lr"]))
-
-    def rollout(self, init_obss, rollout_length):
-        raise NotImplementedError(f"{type(self).__name__}.rollout needs the diffusion behaviour policy, which this package does not have")
-
-    def learn(self, batch: Dict) -> Dict[str, float]:
-        """One gradient step on ``{"observations", "actions", "rtgs"}``: [B, ...] arrays shared by every run or [n_runs, B, ...]."""
+    def _step_on(self, batch: Dict, fields) -> Dict[str, float]:
+        """One gradient step; ``fields``: (orl_batch slot, batch key, 1 for a per-row scalar that may come without its column axis)"""
         R = self._n_runs
         obs = batch["observations"]
         if np.ndim(obs) not in (2, 3):
@@ -77,7 +44,7 @@ class _RcslBase(EnginePolicy):
         self._bind(B)
         dev = self._arena.device
         keep, ptrs = [], {}
-        for k, name, cols in (("observations", "observations", None), ("actions", "actions", None), ("rewards", "rtgs", 1)):
+        for k, name, cols in fields:
             t = torch.as_tensor(batch[name], dtype=torch.float32, device=dev)
             if cols == 1 and (t.dim() == 1 or (t.dim() == 2 and t.shape[-1] != 1)):
                 t = t.unsqueeze(-1)                          # rtgs as [B] / [n_runs, B]
@@ -117,6 +84,93 @@ class _RcslBase(EnginePolicy):
             m, ms = self._eng.learn_epoch(order.cpu().numpy() if isinstance(order, torch.Tensor) else order)
         self.last_learn_epoch_ms = ms
         return self._result(m)
+
+
+class _RcslBase(_EpochPolicy):
+    """what the two return-conditioned policies share: the constructor, the backbone check, ``learn`` on {observations, actions, rtgs}
+    and ``rollout``"""
+
+    def __init__(self, dynamics, rollout_policy, rcsl: nn.Module, rcsl_optim: torch.optim.Optimizer, device="cpu") -> None:
+        super().__init__()
+        self.dynamics = dynamics
+        self.rollout_policy = rollout_policy
+        self.rcsl = rcsl
+        self.rcsl_optim = rcsl_optim
+        self.device = device
+        _adam_hyper(rcsl_optim)
+        self._dims()
+
+    def _dims(self):
+        in_dim, outs = _backbone_dims(self.rcsl.backbone)
+        if len(outs) < 2:
+            raise NotImplementedError(f"{type(self).__name__} expects MLP(obs_dim + 1, hidden_dims, output_dim=act_dim): at least one hidden layer and the output layer")
+        hidden, act_dim = outs[:-1], outs[-1]
+        if len(hidden) > _engine.MAX_HIDDEN:
+            raise NotImplementedError(f"the HIP engine supports up to {_engine.MAX_HIDDEN} hidden layers, the backbone has {len(hidden)}")
+        n_mods = len(list(self.rcsl.backbone.model))
+        if n_mods != 2 * len(hidden) + 1 or getattr(self.rcsl.backbone, "activation_cls", nn.ReLU) is not nn.ReLU:
+            raise NotImplementedError(f"{type(self).__name__} expects a [Linear, ReLU] x L + Linear backbone")
+        return in_dim - 1, act_dim, hidden
+
+    def _nets(self):
+        return {_engine.NET_ACTOR: self.rcsl}
+
+    def _optims(self):
+        return {_engine.OPT_ACTOR: self.rcsl_optim}
+
+    def _config(self) -> Dict:
+        od, ad, hidden = self._dims()
+        return dict(obs_dim=od, act_dim=ad, hidden=hidden, actor_lr=float(self.rcsl_optim.param_groups[0]["lr"]))
+
+    def rollout(self, init_obss: np.ndarray, rollout_length: int) -> Tuple[Dict[str, np.ndarray], Dict]:
+        """Rolls ``rollout_policy`` through ``dynamics`` from ``init_obss`` for up to ``rollout_length`` steps, a batch of trajectories at a
+        time (rcsl.py:57-120).  Transitions: obss, next_obss, actions, rewards [N, 1], terminals [N, 1], traj_idxs [N], acc_rets [N] (the
+        return accumulated BEFORE the transition), rtgs [N, 1] = the trajectory's return - acc_rets; info: num_transitions, reward_mean,
+        returns [trajectories].  A rollout policy with ``sample_init_noise`` (the diffusion interface) gets its per-trajectory noise,
+        thinned to the surviving trajectories, as ``select_action``'s second argument; any other one (``AutoregressivePolicy``) gets None."""
+        if self.dynamics is None or self.rollout_policy is None:
+            raise NotImplementedError(f"{type(self).__name__}.rollout needs both a dynamics model and a rollout (behaviour) policy; "
+                                      f"this policy was built with dynamics={self.dynamics!r}, rollout_policy={self.rollout_policy!r}")
+        num_transitions = 0
+        rewards_arr = np.array([])
+        rollout_transitions = defaultdict(list)
+        valid_idxs = np.arange(init_obss.shape[0])      # trajectories still running
+        returns = np.zeros(init_obss.shape[0])          # return of every trajectory
+        acc_returns = np.zeros(init_obss.shape[0])      # return accumulated so far, of the running ones
+        observations = init_obss
+        frozen = hasattr(self.rollout_policy, "sample_init_noise")
+        frozen_noise = self.rollout_policy.sample_init_noise(init_obss.shape[0]) if frozen else None
+        for _ in range(rollout_length):
+            actions = self.rollout_policy.select_action(observations, frozen_noise)
+            next_observations, rewards, terminals, info = self.dynamics.step(observations, actions)
+            rollout_transitions["obss"].append(observations)
+            rollout_transitions["next_obss"].append(next_observations)
+            rollout_transitions["actions"].append(actions)
+            rollout_transitions["rewards"].append(rewards)
+            rollout_transitions["terminals"].append(terminals)
+            rollout_transitions["traj_idxs"].append(valid_idxs)
+            rollout_transitions["acc_rets"].append(acc_returns)
+            num_transitions += len(observations)
+            rewards_arr = np.append(rewards_arr, rewards.flatten())
+            returns[valid_idxs] = returns[valid_idxs] + rewards.flatten()
+            acc_returns = acc_returns + rewards.flatten()
+            nonterm_mask = (~terminals).flatten()
+            if nonterm_mask.sum() == 0:
+                break
+            observations = next_observations[nonterm_mask]
+            valid_idxs = valid_idxs[nonterm_mask]
+            acc_returns = acc_returns[nonterm_mask]
+            if frozen:
+                frozen_noise = frozen_noise[nonterm_mask]
+        for k, v in rollout_transitions.items():
+            rollout_transitions[k] = np.concatenate(v, axis=0)
+        rtgs = returns[rollout_transitions["traj_idxs"]] - rollout_transitions["acc_rets"]
+        rollout_transitions["rtgs"] = rtgs[..., None]
+        return rollout_transitions, {"num_transitions": num_transitions, "reward_mean": rewards_arr.mean(), "returns": returns}
+
+    def learn(self, batch: Dict) -> Dict[str, float]:
+        """One gradient step on ``{"observations", "actions", "rtgs"}``: [B, ...] arrays shared by every run or [n_runs, B, ...]."""
+        return self._step_on(batch, (("observations", "observations", None), ("actions", "actions", None), ("rewards", "rtgs", 1)))
 
     def _backbone_runs(self, obs, rtg):
         """-> (backbone output of EVERY run [n_runs, E, act_dim] in one batched forward, the stacked net tensors); ``obs`` [n_runs, E,
