@@ -369,6 +369,54 @@ int orl_debug_grads(orl_engine* e, int run, int net, float* host, int64_t n_floa
 /* runs one generic GEMM tile configuration on host data (kernel unit tests): see csrc/gemm.h */
 int orl_debug_gemm(int cfg, int mode, int M, int N, int K, const float* A, const float* B, const float* v0,
                    const float* v1, float* C, int ksplit, int precision);
+/* The wider kernel unit-test tap: one launch of the tiled GEMM template with any epilogue, tile shape, batch (nz0 x nz1 problems),
+ * row pitches, base offsets and fused side outputs (csrc/gemm.h, GemmP).  Every array is a host array that is copied to the device
+ * WHOLE and (results) copied back WHOLE, so pad columns, guard rows and whatever the caller pre-filled them with come back untouched
+ * wherever the kernel did not write.  Problem (z0, z1), split-K slab ks, row r starts at  off + z0 s0 + z1 s1 + ks ks + r pitch
+ * (elements; 32-bit words for the mask arrays); `off` not a multiple of 4 gives a base that is not 16-byte aligned. */
+typedef struct orl_gemm_buf {
+  void* host;            /* null = not used */
+  int64_t n;             /* elements in the array */
+  int64_t off, pitch, s0, s1, ks;
+} orl_gemm_buf;
+typedef struct orl_gemm_ex {
+  int32_t cfg;           /* tile shape 0..6 (csrc/gemm.h CFG_*); + 16 forces the scalar operand loaders */
+  int32_t layout;        /* 0: A [M][K], B [N][K] (forward)   1: A [M][K], B [K][N] (dgrad)   2: A [K][M], B [K][N] (wgrad, epi 4 only) */
+  int32_t epi;           /* 0..8: E_PLAIN, E_BIAS, E_BIAS_RELU, E_MASK, E_WGRAD, E_BIAS_SWISH, E_SWISH_GRAD, E_BIAS_LEAKY, E_LEAKY_MASK */
+  int32_t pa;            /* 0: A as stored   1: rank-1 operand (A > 0 ? rowv * colv : 0), epi 0 / 3 / 4   2: the same from the mask words a_bits (epi 3) */
+  int32_t precision;     /* 0 fp32 MFMA, 1 two 16-bit planes, 2 three planes */
+  int32_t M, N, K, nz0, nz1, ksplit;
+  int32_t a_kpad;        /* layout 0 / 1: A's rows are zero-padded to a multiple of 4 in k (the tap zero-fills the pad of the device copy) */
+  int32_t c_trans;       /* epi 4: C stored (N, M)-major -- c_sr = 1, c_sn = C.pitch */
+  int32_t c_null;        /* with w0: the masked tile itself is not stored */
+  int32_t w0_in;         /* with w0: input columns of layer 0 (w0_x holds them, pitch <= 28) */
+  int32_t tq_sm;         /* with tq_out: element stride between rows of tq_out */
+  int32_t dry_run;       /* check the arguments and fill the report only: no device call */
+  /* operands */
+  orl_gemm_buf A, B, bias, aux, rowv, colv;
+  orl_gemm_buf aux_bits;      /* epi 3: the mask as packed words (pitch = words per row); aux must still be given, it is what a launch reads that does not honour the words */
+  orl_gemm_buf a_bits;        /* pa 2 */
+  orl_gemm_buf tq_w, tq_b;    /* fused single-output tail of epi 2: weights [N], bias [1] */
+  orl_gemm_buf w0_x;          /* fused layer-0 weight gradient of epi 3: the layer-0 input rows [M][pitch] */
+  /* results (copied back whole) */
+  orl_gemm_buf C;             /* [M][N], or [N][M] with c_trans; ks = split-K slab stride */
+  orl_gemm_buf z_out;         /* epi 5: the pre-activation, C's geometry (only host / n are read) */
+  orl_gemm_buf bias_out;      /* epi 4: row sums of A^T [M] per slab */
+  orl_gemm_buf mb_out;        /* epi 2: mask words of the stored activation (pitch = words per row) */
+  orl_gemm_buf tq_out;        /* [M] x tq_sm */
+  orl_gemm_buf tq_part;       /* [column tile - 1][pitch >= M] */
+  orl_gemm_buf w0_out;        /* [row tile (ks)][N][pitch >= w0_in] */
+  orl_gemm_buf w0_bias;       /* [row tile (ks)][N]; s0 and ks must equal w0_out's */
+  /* report: what the launch does with these arguments (filled before the device is touched) */
+  int32_t r_cfg;              /* tile shape that runs (precision 2 reroutes CFG_WG to CFG_SQ) */
+  int32_t r_la_pick, r_lb_pick;   /* pick_loader per operand (0 scalar, 1 VECK, 2 BLK4, 3 VECKU) */
+  int32_t r_la, r_lb;             /* the instantiated pair after the rank-1 and pairing fall-backs */
+  int32_t r_zmajor;
+  int32_t r_store;            /* store path of problem (0, 0), slab 0: 0 staged through LDS, 1 direct 16-byte (scalar tail block), 2 scalar, 3 transposed through LDS */
+  int32_t r_store_mixed;      /* some problem / slab takes another store path */
+  int32_t r_mb, r_tq_parts, r_w0_slabs, r_aux_bits, r_a_bits;   /* requested side output honoured (0 = not) */
+} orl_gemm_ex;
+int orl_debug_gemm_ex(orl_gemm_ex* args);
 /* times `reps` launches of one GEMM tile configuration on random data (kind 0 forward, 1 dgrad, 2 wgrad) */
 int orl_debug_gemm_time(int cfg, int kind, int M, int N, int K, int nz, int ksplit, int reps, float* ms_out);
 /* average duration (ms) of the kernel with the largest accumulated time during the last orl_learn_n

@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "orl_buffer_reserve", "orl_buffer_append", "orl_buffer_append_rollout", "orl_buffer_read", "orl_engine_attach_model_buffer",
     "orl_buffer_append_rollout_runs", "orl_engine_attach_model_buffers",
     "orl_health", "orl_health_check", "orl_health_clear", "orl_num_metrics", "orl_metric_name", "orl_step_count",
-    "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
+    "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_ex", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
     # dynamics ensemble (orl_dynamics)
     "orl_dyn_config_default", "orl_dyn_create", "orl_dyn_destroy", "orl_dyn_sync", "orl_dyn_floats", "orl_dyn_config_floats",
     "orl_dyn_num_tensors", "orl_dyn_tensor", "orl_dyn_ptr", "orl_dyn_set", "orl_dyn_get", "orl_dyn_adam_get", "orl_dyn_adam_set",
@@ -113,6 +113,22 @@ class OrlBatch(C.Structure):
 
 class OrlNoise(C.Structure):
     _fields_ = [("slot", C.c_void_p * MAX_NOISE), ("on_device", C.c_int32)]
+
+
+class OrlGemmBuf(C.Structure):
+    _fields_ = [("host", C.c_void_p), ("n", C.c_int64), ("off", C.c_int64), ("pitch", C.c_int64), ("s0", C.c_int64), ("s1", C.c_int64),
+                ("ks", C.c_int64)]
+
+
+GEMM_EX_INTS = ("cfg", "layout", "epi", "pa", "precision", "M", "N", "K", "nz0", "nz1", "ksplit", "a_kpad", "c_trans", "c_null", "w0_in", "tq_sm", "dry_run")
+GEMM_EX_BUFS = ("A", "B", "bias", "aux", "rowv", "colv", "aux_bits", "a_bits", "tq_w", "tq_b", "w0_x",
+                "C", "z_out", "bias_out", "mb_out", "tq_out", "tq_part", "w0_out", "w0_bias")
+GEMM_EX_REPORT = ("r_cfg", "r_la_pick", "r_lb_pick", "r_la", "r_lb", "r_zmajor", "r_store", "r_store_mixed", "r_mb", "r_tq_parts", "r_w0_slabs",
+                  "r_aux_bits", "r_a_bits")
+
+
+class OrlGemmEx(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in GEMM_EX_INTS] + [(k, OrlGemmBuf) for k in GEMM_EX_BUFS] + [(k, C.c_int32) for k in GEMM_EX_REPORT]
 
 
 _lib = None
@@ -201,6 +217,7 @@ def load_library(path: Optional[str] = None):
     lib.orl_debug_read_bits.restype = C.c_int64
     lib.orl_debug_grads.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]
     lib.orl_debug_gemm.argtypes = [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_int, C.c_int]
+    lib.orl_debug_gemm_ex.argtypes = [C.POINTER(OrlGemmEx)]
     lib.orl_debug_gemm_time.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_float)]
     lib.orl_profile_enable.argtypes = [C.c_void_p, C.c_int]
     lib.orl_profile_query.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double),
@@ -749,6 +766,80 @@ def debug_gemm(cfg: int, mode: int, A, B, v0=None, v1=None, ksplit=1, precision=
                               p0.ctypes.data if p0 is not None else None, p1.ctypes.data if p1 is not None else None,
                               out.ctypes.data, ksplit, precision), "orl_debug_gemm")
     return out
+
+
+GEMM_SENTINEL = 0xDEADBEEF      # pre-fill of every result array of the wide tap (pad columns, guard rows and guard bands keep it)
+GEMM_PAD_NAN = 0x7FC0DEAD       # pre-fill of the operand arrays: a quiet NaN, so a pad element that reaches a result poisons it
+
+
+class GemmArray:
+    """One array of the wide GEMM tap (orl_debug_gemm_ex).  Logical elements [nz0][nz1][nslab][rows][cols] sit in a flat 32-bit buffer
+    at ``off + z0 s0 + z1 s1 + ks kstride + r pitch + c``; every problem slab carries ``guard`` rows after its last row, the pitch may
+    exceed ``cols``, and the buffer ends in a guard band.  ``z1_major`` interleaves the problems the other way round (s0 < s1),
+    ``share_z1`` gives the members of a run one copy (s1 = 0).  Everything that is not a logical element holds ``fill``."""
+
+    def __init__(self, rows, cols, nz0=1, nz1=1, nslab=1, pitch=None, off=0, guard=2, z1_major=False, share_z1=False, stride_pad=0,
+                 fill=GEMM_SENTINEL, dtype=np.float32, kstride=None):
+        self.dtype = np.dtype(dtype)
+        assert self.dtype.itemsize == 4
+        self.pitch = int(cols if pitch is None else pitch)
+        self.off, self.fill = int(off), int(fill)
+        self.kstride = (((rows + guard) * self.pitch + 3) & ~3) + int(stride_pad)
+        if kstride is not None:      # a slab stride shared with another array
+            assert kstride >= self.kstride
+            self.kstride = int(kstride)
+        prob = nslab * self.kstride
+        m1 = 1 if share_z1 else nz1
+        if share_z1:
+            self.s0, self.s1 = prob, 0
+        elif z1_major:
+            self.s0, self.s1 = prob, nz0 * prob
+        else:
+            self.s0, self.s1 = nz1 * prob, prob
+        self.n = self.off + nz0 * m1 * prob + 4
+        ix = np.ix_(*[np.arange(k, dtype=np.int64) for k in (nz0, m1, nslab, rows, cols)])
+        self.idx = self.off + ix[0] * self.s0 + ix[1] * self.s1 + ix[2] * self.kstride + ix[3] * self.pitch + ix[4]
+        assert self.idx.max() < self.n
+        self.raw = np.full(self.n, self.fill, dtype=np.uint32)
+
+    def put(self, data):
+        """logical data, any shape that reshapes to [nz0][nz1 (1 when shared)][nslab][rows][cols]"""
+        self.raw.view(self.dtype)[self.idx] = np.asarray(data, dtype=self.dtype).reshape(self.idx.shape)
+        return self
+
+    def get(self) -> np.ndarray:
+        return self.raw.view(self.dtype)[self.idx]
+
+    def outside(self) -> np.ndarray:
+        """the words that are no logical element, as stored"""
+        keep = np.ones(self.n, dtype=bool)
+        keep[self.idx.ravel()] = False
+        return self.raw[keep]
+
+    def desc(self) -> "OrlGemmBuf":
+        return OrlGemmBuf(self.raw.ctypes.data, self.n, self.off, self.pitch, self.s0, self.s1, self.kstride)
+
+
+def debug_gemm_ex(arrays: Dict[str, GemmArray], **ints) -> Dict[str, int]:
+    """The wide kernel unit-test tap (orl_debug_gemm_ex): one launch of the tiled GEMM template.  ``arrays`` maps the names of
+    include/orl_engine.h's orl_gemm_ex (A, B, bias, aux, ..., C, z_out, mb_out, ...) to GemmArray objects; result arrays are updated in
+    place, whole.  ``ints`` are the integer fields (cfg, layout, epi, pa, precision, M, N, K, nz0, nz1, ksplit, a_kpad, c_trans, c_null,
+    w0_in, tq_sm; dry_run = 1 stops after the checks and the report, without a device).  Returns the tap's report of what the launch did (r_* fields without the prefix).  Refused combinations raise
+    before any device call."""
+    lib = load_library()
+    a = OrlGemmEx()
+    a.nz0 = a.nz1 = a.ksplit = a.tq_sm = 1
+    for k, v in ints.items():
+        if k not in GEMM_EX_INTS:
+            raise TypeError(f"debug_gemm_ex: unknown field {k}")
+        setattr(a, k, int(v))
+    for k, v in arrays.items():
+        if k not in GEMM_EX_BUFS:
+            raise TypeError(f"debug_gemm_ex: unknown array {k}")
+        if v is not None:
+            setattr(a, k, v.desc())
+    _check(lib.orl_debug_gemm_ex(C.byref(a)), "orl_debug_gemm_ex")
+    return {k[2:]: int(getattr(a, k)) for k in GEMM_EX_REPORT}
 
 
 def default_dyn_config(**over) -> OrlDynConfig:
