@@ -8,17 +8,11 @@ namespace orl {
 int Engine::autoreg_build() {
   const int A = ad, M = A * B;
   metric_names = {"loss"};
-  for (int i = 0; i < L; ++i) {
-    const int h = cfg.hidden[i];
-    const std::string s = std::to_string(i);
-    alloc("ah" + s, M, h); alloc("dah" + s, M, h);
-  }
+  if (epoch_build(M)) return -1;
   alloc("ar_x", M, rup(od + 2 * A, 4));
   alloc("ar_z", M, 2); alloc("ar_dz", M, 2); alloc("ar_out", M, 2); alloc("ar_target", M, 1);
-  epoch_cell = (EpochCell*)raw_alloc(sizeof(EpochCell));
-  order_flags = (unsigned int*)raw_alloc(sizeof(unsigned int));
   ar_calls = (unsigned long long*)raw_alloc(sizeof(unsigned long long));
-  if (!epoch_cell || !order_flags || !ar_calls) return fail("hipMalloc epoch cell");
+  if (!ar_calls) return fail("hipMalloc sample counter");
   if (hipMemset(ar_calls, 0, sizeof(unsigned long long)) != hipSuccess) return fail("hipMemset sample counter");
   taps["ar_x"] = {W("ar_x"), M, od + 2 * A};
   taps["ar_out"] = {W("ar_out"), M, 2};
@@ -26,49 +20,25 @@ int Engine::autoreg_build() {
   return 0;
 }
 
-// the step's input launch: mode RI_SLOTS (orl_step), RI_DRAWN (orl_learn_n) or RI_ORDER (orl_learn_epoch)
 int Engine::autoreg_prepare(int mode) {
   AutoregPrepP p;
   memset(&p, 0, sizeof(p));
   const Mat x = W("ar_x"), o2 = W("b_obs2"), act = W("b_act"), rew = W("b_rew"), t = W("ar_target");
   p.b_obs = o2.p; p.bo_rs = o2.rs; p.b_act = act.p; p.ba_rs = act.rs; p.b_rew = rew.p; p.br_rs = rew.rs;
-  p.X = x.p; p.x_rs = x.rs; p.XP = x.pitch; p.T = t.p; p.t_rs = t.rs; p.OP = OP; p.AP = AP;
-  p.idx_out = d_idx; p.B = B; p.od = od; p.A = ad;
-  p.seed = cfg.seed; p.gstep = gstep;
-  if (mode != RI_SLOTS) {
-    if (!buf || !buf->obs) return fail("no replay buffer attached (orl_engine_attach_buffer)");
-    p.d_obs = buf->obs; p.d_act = buf->act; p.d_rew = buf->rew; p.n = buf->n;
-    p.order = d_order; p.cell = epoch_cell;
-    if (mode == RI_ORDER && !d_order) return fail("ordered epoch without a row order");
-  }
-  const dim3 grid((unsigned)(((long)B * p.XP + 255) / 256), R);
-  if (mode == RI_SLOTS) ORL_LAUNCH("autoreg_prepare", k_autoreg_prepare<RI_SLOTS>, grid, dim3(256), p);
-  else if (mode == RI_DRAWN) ORL_LAUNCH("autoreg_prepare", k_autoreg_prepare<RI_DRAWN>, grid, dim3(256), p);
-  else ORL_LAUNCH("autoreg_prepare", k_autoreg_prepare<RI_ORDER>, grid, dim3(256), p);
-  return 0;
+  p.X = x.p; p.x_rs = x.rs; p.XP = x.pitch; p.T = t.p; p.t_rs = t.rs; p.A = ad;
+  static void (*const kern[3])(AutoregPrepP) = {k_autoreg_prepare<RI_SLOTS>, k_autoreg_prepare<RI_DRAWN>, k_autoreg_prepare<RI_ORDER>};
+  return epoch_prepare("autoreg_prepare", p, p.d_rew, mode, dim3((unsigned)(((long)B * p.XP + 255) / 256), R), kern);
 }
 
 int Engine::autoreg_step() {
-  const NetRef net = net_ref(ORL_NET_ACTOR, 1);
-  const int M = ad * B;
-  std::vector<Mat> ah, dah;
-  for (int i = 0; i < L; ++i) { ah.push_back(W("ah" + std::to_string(i))); dah.push_back(W("dah" + std::to_string(i))); }
-  const Mat x = W("ar_x"), z = W("ar_z");
-  if (autoreg_prepare(rcsl_mode)) return -1;
-  if (mlp_forward(x, M, net, ah, z, "autoreg")) return -1;
-  float* gs = nullptr;
-  {
+  return supervised_step(W("ar_x"), ad * B, W("ar_z"), W("ar_dz"), "autoreg", [&](float* gs, const long long* idx) {
     AutoregHeadP p; memset(&p, 0, sizeof(p));
-    p.z = z.p; p.z_rs = z.rs; p.T = W("ar_target").p; p.t_rs = W("ar_target").rs;
+    p.z = W("ar_z").p; p.z_rs = W("ar_z").rs; p.T = W("ar_target").p; p.t_rs = W("ar_target").rs;
     p.out = W("ar_out").p; p.dz = W("ar_dz").p;
-    p.idx = rcsl_mode == RI_SLOTS ? nullptr : d_idx;      // (orl_step: every row of the caller's batch is valid)
-    p.B = B; p.A = ad; p.m = mp(); p.m.nm = (int)metric_names.size(); p.slot = 0;
-    p.gs_out = gs = gscale_slot();                        // (split precision: the seed kernel publishes the dynamic scale of its backward pass)
+    p.idx = idx; p.B = B; p.A = ad; p.m = mp(); p.slot = 0; p.gs_out = gs;
     ORL_LAUNCH("autoreg_head", k_autoreg_head, dim3(R), dim3(256), p);
-  }
-  BwdOut bo;
-  if (mlp_backward(this, net, x, ah, M, W("ar_dz"), dah, true, false, 0, 0, nullptr, "autoreg.bwd", &bo, gs)) return -1;
-  return adam(ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, make_segs(*net.lay, bo.ks, bo.ks), -1);
+    return 0;
+  });
 }
 
 // workspaces of orl_autoreg_sample for n rows per run; regrown (never shrunk) when n grows

@@ -13,6 +13,37 @@ static inline void cql_rows(const Engine* e, int& c0, int& Bc, int& Br) {
   Br = e->cfg.cql_real_rows > 0 ? e->cfg.cql_real_rows : e->B;
 }
 
+// What sac_actor_phase consumes, for Kc critics (CQL, EDAC, SAC, MCQ, MOBILE).  The noise-slot ORDER is each algorithm's own contract
+// (the reference's draw order): the caller lists n_eps_actor in its noise_slots.
+void Engine::sac_family_alloc(int Kc) {
+  const int A = ad;
+  alloc("n_eps_actor", B, A);
+  alloc_layers("ah", B); alloc_layers("dah", B); alloc_layers("ca", B, Kc); alloc_layers("dca", B, Kc);
+  alloc("head", B, 2 * A); alloc("dhead", B, 2 * A); alloc("xa", B, XP); alloc("logp_a", B, 1);
+  alloc("qa", B, 1, Kc); alloc("dqa", B, 1, Kc); alloc("dxa", B, A, Kc);
+}
+
+// the operands every TD-style critic loss reads the same way (TdLossP, MobileTdP, McqLossP, CqlLossP)
+template <class P>
+static void td_operands(Engine* e, P& p, bool with_logp_next = true) {
+  p.q = e->W("q").z(); p.dq = e->W("dq").p; p.qt = e->W("qt").z();
+  p.rew = e->W("b_rew").p; p.term = e->W("b_term").p; p.bt_rs = e->W("b_rew").rs;
+  if (with_logp_next) { p.logp_next = e->W("logp_next").p; p.lpn_rs = e->W("logp_next").rs; }
+  p.target_q = e->W("target_q").p; p.tq_rs = e->W("target_q").rs;
+}
+
+// twin / ensemble TD loss (k_td_loss) of SAC, EDAC and TD3+BC: seeds dq, metric slot(s) from 1; *gs_out: the dynamic scale it publishes
+int Engine::td_loss(int Kc, int Kt, int rep, int use_alpha, int sum_over_k, bool with_logp_next, float** gs_out) {
+  TdLossP p; memset(&p, 0, sizeof(p));
+  td_operands(this, p, with_logp_next);
+  p.Kt = Kt; p.use_alpha = use_alpha;
+  p.B = B; p.K = Kc; p.rep = rep; p.gamma = cfg.gamma; p.sum_over_k = sum_over_k;
+  p.sc = scalars; p.auto_alpha = cfg.auto_alpha; p.fixed_alpha = cfg.alpha; p.m = mp(); p.slot0 = 1;
+  p.gs_out = *gs_out = gscale_slot();               // (split precision: the seed kernel publishes the dynamic scale of its backward pass)
+  ORL_LAUNCH("td_loss", k_td_loss, dim3(R), dim3(256), p);
+  return 0;
+}
+
 int Engine::cql_build() {
   int c0, Bc, Br;
   cql_rows(this, c0, Bc, Br);
@@ -20,21 +51,14 @@ int Engine::cql_build() {
   metric_names = {"loss/actor", "loss/critic1", "loss/critic2"};
   add_sac_metrics(this);
   if (cfg.with_lagrange) { metric_names.push_back("loss/cql_alpha"); metric_names.push_back("cql_alpha"); }
-  alloc("n_eps_actor", B, A); alloc("n_eps_next", Bt, A); alloc("n_urand", BN, A);
+  sac_family_alloc(2);
+  alloc("n_eps_next", Bt, A); alloc("n_urand", BN, A);
   alloc("n_eps_pi", BN, A); alloc("n_eps_npi", BN, A);
   noise_slots = {{"n_eps_actor", 0, B}, {"n_eps_next", 0, Bt}, {"n_urand", 1, BN}, {"n_eps_pi", 0, BN}, {"n_eps_npi", 0, BN}};
-  for (int i = 0; i < L; ++i) {
-    const int h = cfg.hidden[i];
-    const std::string s = std::to_string(i);
-    alloc("ah" + s, B, h); alloc("dah" + s, B, h); alloc("ah2_" + s, 2 * B, h);
-    alloc("ca" + s, B, h, 2); alloc("dca" + s, B, h, 2);
-    alloc("ct" + s, Bt, h, 2); alloc("ch" + s, Mc, h, 2);
-    if (i < L - 1) alloc("dch" + s, Mc, h, 2);
-  }
-  alloc("head", B, 2 * A); alloc("head2", 2 * B, 2 * A); alloc("dhead", B, 2 * A);
-  alloc("xa", B, XP); alloc("xt", Bt, XP); alloc("xc", Mc, XP);
-  alloc("logp_a", B, 1); alloc("logp_next", Bt, 1); alloc("logp_pi", BN, 1); alloc("logp_npi", BN, 1);
-  alloc("qa", B, 1, 2); alloc("dqa", B, 1, 2); alloc("dxa", B, A, 2);
+  alloc_layers("ah2_", 2 * B); alloc_layers("ct", Bt, 2); alloc_layers("ch", Mc, 2); alloc_layers("dch", Mc, 2, L - 1);
+  alloc("head2", 2 * B, 2 * A);
+  alloc("xt", Bt, XP); alloc("xc", Mc, XP);
+  alloc("logp_next", Bt, 1); alloc("logp_pi", BN, 1); alloc("logp_npi", BN, 1);
   alloc("qt", Bt, 1, 2); alloc("q", Mc, 1, 2); alloc("dq", Mc, 1, 2); alloc("target_q", B, 1);
   loss_nblk = std::max(1, std::min(32, (BN + 511) / 512));
   alloc("loss_part", 2L * loss_nblk, 4);
@@ -74,96 +98,90 @@ int Engine::cql_build() {
 }
 
 // SAC-style actor update shared by CQL and EDAC: a ~ pi(s), L = mean(alpha logp - min_k Q_k(s,a)), alpha step.
-static int sac_actor_phase(Engine* e, const NetRef& actor, const NetRef& crit, int Kc, bool clamp_alpha01, int slot_alpha_loss) {
-  const int B = e->B, A = e->ad, L = e->L, od = e->od;
-  Mat obs = e->W("b_obs2");
-  std::vector<Mat> ah, dah, ca, dca;
-  for (int i = 0; i < L; ++i) {
-    const std::string s = std::to_string(i);
-    ah.push_back(e->W("ah" + s)); dah.push_back(e->W("dah" + s)); ca.push_back(e->W("ca" + s)); dca.push_back(e->W("dca" + s));
-  }
-  Mat xa = e->W("xa").shared();
+int Engine::sac_actor_phase(const NetRef& actor, const NetRef& crit, int Kc, bool clamp_alpha01, int slot_alpha_loss) {
+  const int A = ad;
+  Mat obs = W("b_obs2");
+  std::vector<Mat> ah = layers("ah"), dah = layers("dah"), ca = layers("ca"), dca = layers("dca");
+  Mat xa = W("xa").shared();
   // a ~ pi(s): the one-launch forward samples in its epilogue when it applies (few batched rows); otherwise a k_tanh_sample launch.
   // (the observation columns of xa are written before this point: k_prepare, or the assemble launch of engines without a job table)
-  if (e->prep.empty() && e->assemble(obs, nullptr, xa, 0, B, 1)) return -1;
-  SampleJob j = make_job(0, B, 1, e->W("n_eps_actor"), xa, od, 0, e->W("logp_a"));
+  if (prep.empty() && assemble(obs, nullptr, xa, 0, B, 1)) return -1;
+  SampleJob j = make_job(0, B, 1, W("n_eps_actor"), xa, od, 0, W("logp_a"));
   bool sampled = false;
-  if (e->mlp_forward(obs, B, actor, ah, e->W("head"), "actor", &j, 1, &sampled)) return -1;
-  if (!sampled && launch_sample(e, e->W("head"), A, &j, 1)) return -1;
+  if (mlp_forward(obs, B, actor, ah, W("head"), "actor", &j, 1, &sampled)) return -1;
+  if (!sampled && launch_sample(this, W("head"), A, &j, 1)) return -1;
   // Q_k(s, pi(s)) and, where the one-launch forward + backward applies (two 256-wide layers, few batched rows), dQ_k / da for a unit seed
   // in the same launch: the loss kernel below then only weighs the two gradients (-1/B on the smaller Q, cql.py:93-98)
-  Mat dxa = e->W("dxa");
+  Mat dxa = W("dxa");
   bool qg = false;
-  if (e->mlp_qgrad(xa, B, crit, e->W("qa"), dxa, od, A, "critic_a.qgrad", &qg)) return -1;
-  if (!qg && e->mlp_forward(xa, B, crit, ca, e->W("qa"), "critic_a")) return -1;
+  if (mlp_qgrad(xa, B, crit, W("qa"), dxa, od, A, "critic_a.qgrad", &qg)) return -1;
+  if (!qg && mlp_forward(xa, B, crit, ca, W("qa"), "critic_a")) return -1;
   // actor loss + temperature step + head backward + actor backward as ONE launch when the unit-seed critic gradients exist and the actor is
   // two 256-wide layers on few batched rows (small_bwd.h): one split-K slab of every actor tensor per 32-row group
-  if (qg && e->fuse_small && L == 2 && actor.lay->H[0] == SB_N && actor.lay->H[1] == SB_N && !e->vals_dead.count(ah[0].p) && !e->vals_dead.count(ah[1].p) &&
-      B / SB_ROWS <= e->max_slab) {
+  if (qg && fuse_small && L == 2 && actor.lay->H[0] == SB_N && actor.lay->H[1] == SB_N && !vals_dead.count(ah[0].p) && !vals_dead.count(ah[1].p) &&
+      B / SB_ROWS <= max_slab) {
     const NetLayout& al = *actor.lay;
     SmallABwdP w; memset(&w, 0, sizeof(w));
     w.X = obs.p; w.x_s0 = obs.rs; w.x_pitch = obs.pitch; w.in0 = al.layer_in(0);
     w.H0 = ah[0].p; w.h0_s0 = ah[0].rs; w.H1 = ah[1].p; w.h1_s0 = ah[1].rs;
-    w.head = e->W("head").p; w.head_s0 = e->W("head").rs;
-    w.eps = e->W("n_eps_actor").p; w.eps_s0 = e->W("n_eps_actor").rs;
+    w.head = W("head").p; w.head_s0 = W("head").rs;
+    w.eps = W("n_eps_actor").p; w.eps_s0 = W("n_eps_actor").rs;
     w.xa = xa.p; w.xa_s0 = xa.rs; w.xa_pitch = xa.pitch; w.xa_col = od;
-    w.logp = e->W("logp_a").p; w.logp_s0 = e->W("logp_a").rs;
-    w.qa = e->W("qa").z();
+    w.logp = W("logp_a").p; w.logp_s0 = W("logp_a").rs;
+    w.qa = W("qa").z();
     w.ga = dxa.z(); w.ga_pitch = dxa.pitch; w.K = Kc;
     w.W1 = actor.base + al.w_off[1]; w.w1_s0 = actor.rs;
     w.Wh = actor.base + al.w_off[2]; w.wh_s0 = actor.rs;
-    w.out = e->grads + actor.g_off; w.o_s0 = (long)e->max_slab * e->P_train; w.o_ks = e->P_train;
+    w.out = grads + actor.g_off; w.o_s0 = (long)max_slab * P_train; w.o_ks = P_train;
     w.off_w0 = al.w_off[0]; w.off_b0 = al.b_off[0]; w.off_w1 = al.w_off[1]; w.off_b1 = al.b_off[1]; w.off_wh = al.w_off[2]; w.off_bh = al.b_off[2];
-    w.sc = e->scalars; w.hy = e->hyper; w.auto_alpha = e->cfg.auto_alpha; w.fixed_alpha = e->cfg.alpha;
-    w.target_entropy = e->cfg.target_entropy; w.clamp_alpha01 = clamp_alpha01 ? 1 : 0;
-    w.b1 = e->cfg.adam_beta1; w.b2 = e->cfg.adam_beta2; w.adam_eps = e->cfg.adam_eps; w.gstep = e->gstep;
-    w.metrics_last = e->metrics_last; w.metrics_sum = e->metrics_sum; w.nm = (int)e->metric_names.size();
+    w.sc = scalars; w.hy = hyper; w.auto_alpha = cfg.auto_alpha; w.fixed_alpha = cfg.alpha;
+    w.target_entropy = cfg.target_entropy; w.clamp_alpha01 = clamp_alpha01 ? 1 : 0;
+    w.b1 = cfg.adam_beta1; w.b2 = cfg.adam_beta2; w.adam_eps = cfg.adam_eps; w.gstep = gstep;
+    w.metrics_last = metrics_last; w.metrics_sum = metrics_sum; w.nm = (int)metric_names.size();
     w.m_actor = 0; w.m_alpha_loss = slot_alpha_loss; w.m_alpha = slot_alpha_loss + 1;
-    w.part = e->aloss_part; w.ticket = e->cql_ticket;
-    w.M = B; w.A = A; w.f32 = e->ws_f32();
-    w.lab_clk = e->lab_clk(0);      // (16 stamps behind the partial sums; written by lab builds only)
+    w.part = aloss_part; w.ticket = cql_ticket;
+    w.M = B; w.A = A; w.f32 = ws_f32();
+    w.lab_clk = lab_clk(0);      // (16 stamps behind the partial sums; written by lab builds only)
     if (al.out_dim == 2 * A && small_abwd_supported(w)) {
-      e->watch_range(ah[0], B, SB_N, 1, "actor.bwd");
-      if (e->timed("small_abwd", "actor.bwd_fused", false, 2.0 * B * (double)e->R * (2.0 * SB_N * SB_N + 2.0 * SB_N * 2 * A + (double)SB_N * (w.in0 + 1)),
-                   4.0 * e->R * (B * (double)(2 * SB_N + w.in0 + 6 * A + 4) + (double)SB_N * SB_N + (B / SB_ROWS) * (double)al.size),
-                   [&] { return launch_small_abwd(w, e->R, e->stream); })) return -1;
+      watch_range(ah[0], B, SB_N, 1, "actor.bwd");
+      if (timed("small_abwd", "actor.bwd_fused", false, 2.0 * B * (double)R * (2.0 * SB_N * SB_N + 2.0 * SB_N * 2 * A + (double)SB_N * (w.in0 + 1)),
+                   4.0 * R * (B * (double)(2 * SB_N + w.in0 + 6 * A + 4) + (double)SB_N * SB_N + (B / SB_ROWS) * (double)al.size),
+                   [&] { return launch_small_abwd(w, R, stream); })) return -1;
       const std::vector<int> ks(L + 1, B / SB_ROWS);
-      return e->adam(ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, make_segs(al, ks, ks), -1);
+      return adam(ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, make_segs(al, ks, ks), -1);
     }
   }
   {
     ActorLossP p; memset(&p, 0, sizeof(p));
-    p.qa = e->W("qa").p; p.qa_rs = e->W("qa").rs; p.qa_cs = e->W("qa").cs; p.dqa = e->W("dqa").p;
-    p.logp = e->W("logp_a").p; p.logp_rs = e->W("logp_a").rs; p.B = B; p.K = Kc;
-    p.sc = e->scalars; p.hy = e->hyper; p.auto_alpha = e->cfg.auto_alpha; p.fixed_alpha = e->cfg.alpha;
-    p.target_entropy = e->cfg.target_entropy; p.clamp_alpha01 = clamp_alpha01 ? 1 : 0;
-    p.b1 = e->cfg.adam_beta1; p.b2 = e->cfg.adam_beta2; p.eps = e->cfg.adam_eps; p.gstep = e->gstep;
-    p.metrics_last = e->metrics_last; p.metrics_sum = e->metrics_sum; p.nm = (int)e->metric_names.size();
+    p.qa = W("qa").z(); p.dqa = W("dqa").p;
+    p.logp = W("logp_a").p; p.logp_rs = W("logp_a").rs; p.B = B; p.K = Kc;
+    p.sc = scalars; p.hy = hyper; p.auto_alpha = cfg.auto_alpha; p.fixed_alpha = cfg.alpha;
+    p.target_entropy = cfg.target_entropy; p.clamp_alpha01 = clamp_alpha01 ? 1 : 0;
+    p.b1 = cfg.adam_beta1; p.b2 = cfg.adam_beta2; p.eps = cfg.adam_eps; p.gstep = gstep;
+    p.metrics_last = metrics_last; p.metrics_sum = metrics_sum; p.nm = (int)metric_names.size();
     p.m_actor = 0; p.m_alpha_loss = slot_alpha_loss; p.m_alpha = slot_alpha_loss + 1;
-    e->prof_begin("actor_loss", 0);
-    hipLaunchKernelGGL(k_actor_loss, dim3(e->R), dim3(256), 0, e->stream, p);
-    e->prof_end();
+    prof_begin("actor_loss", 0);
+    hipLaunchKernelGGL(k_actor_loss, dim3(R), dim3(256), 0, stream, p);
+    prof_end();
   }
   // (split precision: the seed dqa holds -1/B or 0 -- its scale is a constant of the engine; dhead's comes from k_head_bwd itself when
   // the batch is one workgroup)
-  if (!qg && mlp_backward(e, crit, xa, ca, B, e->W("dqa"), dca, false, true, od, A, &dxa, "critic_a.bwd", nullptr,
-                          e->split_scales() ? e->gscale_inv_b : nullptr)) return -1;
-  float* gs_head = (e->split_scales() && B <= 256) ? e->gscale_slot() : nullptr;
+  const InputGrad da{od, A, &dxa};
+  if (!qg && mlp_backward(this, crit, xa, ca, B, W("dqa"), dca, false, &da, "critic_a.bwd", nullptr, split_scales() ? gscale_inv_b : nullptr)) return -1;
+  float* gs_head = (split_scales() && B <= 256) ? gscale_slot() : nullptr;
   {
     HeadBwdP p; memset(&p, 0, sizeof(p));
     p.gs_out = gs_head;
-    p.dxa = dxa.p; p.dxa_rs = dxa.rs; p.dxa_cs = dxa.cs; p.dxa_pitch = A; p.K = Kc;
-    if (qg) { p.dqa = e->W("dqa").p; p.dqa_rs = e->W("dqa").rs; p.dqa_cs = e->W("dqa").cs; }
-    p.head = e->W("head").p; p.head_rs = e->W("head").rs; p.eps = e->W("n_eps_actor").p; p.eps_rs = e->W("n_eps_actor").rs;
-    p.xa = xa.p; p.xa_rs = xa.rs; p.XP = e->XP; p.od = od; p.dhead = e->W("dhead").p; p.dhead_rs = e->W("dhead").rs;
-    p.sc = e->scalars; p.auto_alpha = e->cfg.auto_alpha; p.fixed_alpha = e->cfg.alpha; p.B = B; p.A = A;
-    e->prof_begin("head_bwd", 0);
-    hipLaunchKernelGGL(k_head_bwd, dim3((B + 255) / 256, e->R), dim3(256), 0, e->stream, p);
-    e->prof_end();
+    p.dxa = dxa.z(); p.dxa_pitch = A; p.K = Kc;
+    if (qg) p.dqa = W("dqa").z();
+    p.head = W("head").p; p.head_rs = W("head").rs; p.eps = W("n_eps_actor").p; p.eps_rs = W("n_eps_actor").rs;
+    p.xa = xa.p; p.xa_rs = xa.rs; p.XP = XP; p.od = od; p.dhead = W("dhead").p; p.dhead_rs = W("dhead").rs;
+    p.sc = scalars; p.auto_alpha = cfg.auto_alpha; p.fixed_alpha = cfg.alpha; p.B = B; p.A = A;
+    prof_begin("head_bwd", 0);
+    hipLaunchKernelGGL(k_head_bwd, dim3((B + 255) / 256, R), dim3(256), 0, stream, p);
+    prof_end();
   }
-  BwdOut bo;
-  if (mlp_backward(e, actor, obs, ah, B, e->W("dhead"), dah, true, false, 0, 0, nullptr, "actor.bwd", &bo, gs_head)) return -1;
-  return e->adam(ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, make_segs(*actor.lay, bo.ks, bo.ks), -1);
+  return train_net(actor, ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, obs, ah, B, W("dhead"), dah, "actor.bwd", gs_head);
 }
 
 int Engine::cql_step() {
@@ -171,17 +189,12 @@ int Engine::cql_step() {
   cql_rows(this, c0, Bc, Br);
   const int A = ad, BN = Bc * N, Mc = B + 3 * BN, Bt = cfg.max_q_backup ? B * N : B;
   const NetRef actor = net_ref(ORL_NET_ACTOR, 1), crit = net_ref(ORL_NET_CRITIC1, 2), tgt = net_ref(ORL_NET_CRITIC1_OLD, 2);
-  Mat obs = W("b_obs2"), nobs = W("b_obs2").rows(B), obs2 = W("b_obs2");
-  std::vector<Mat> ah2, ct, ch, dch;
-  for (int i = 0; i < L; ++i) {
-    const std::string s = std::to_string(i);
-    ah2.push_back(W("ah2_" + s)); ct.push_back(W("ct" + s)); ch.push_back(W("ch" + s));
-    dch.push_back(i < L - 1 ? W("dch" + s) : Mat());
-  }
+  Mat obs2 = W("b_obs2");
+  std::vector<Mat> ah2 = layers("ah2_"), ct = layers("ct"), ch = layers("ch"), dch = layers("dch");
   Mat xt = W("xt").shared(), xc = W("xc").shared();
 
   // ---------------- phase A: actor + temperature (cql.py:92-106) ----------------
-  if (sac_actor_phase(this, actor, crit, 2, false, 3)) return -1;
+  if (sac_actor_phase(actor, crit, 2, false, 3)) return -1;
 
   // ---------------- phase T: targets + repeated-action sampling with the UPDATED actor ----------------
   // critic input rows (written by k_prepare): [0,B) (obs, a_data) ; [B,B+BN) (obs rep, a_pi) ; next BN (obs rep, a_next_pi) ;
@@ -196,26 +209,15 @@ int Engine::cql_step() {
     if (mlp_forward_only(obs2, 2 * B, actor, ah2, W("head2"), "actor2", jobs, 3, &sampled)) return -1;
     if (!sampled && launch_sample(this, W("head2"), A, jobs, 3)) return -1;
   }
-  // The target critics' forward and the critics' forward are independent of each other (both read what the actor pass above wrote).  With few
-  // runs per engine the target pass is one small launch (small_fwd.h): it runs on the side stream next to the critics' weight-stationary
-  // launch instead of in front of it.  (Many runs: both launches fill the GPU, and at precision 2 both would use the tail scratch.)
-  const bool side_target = small_fwd_on && L == 2 && (long)Bt * 2 * R <= small_fwd_max_rows && (long)Mc * 2 * R >= ws_fwd_min_rows;
-  if (side_target && fork_side()) return -1;
   if (mlp_forward_only(xt, Bt, tgt, ct, W("qt"), "target")) return -1;
-  if (side_target) fork_main();
 
   // ---------------- phase C: critics (cql.py:132-190) ----------------
   if (mlp_forward(xc, Mc, crit, ch, W("q"), "critic")) return -1;
-  if (side_target && fork_join()) return -1;
   float* gs_dq = nullptr;
   {
     CqlLossP p; memset(&p, 0, sizeof(p));
-    p.q = W("q").p; p.q_rs = W("q").rs; p.q_cs = W("q").cs; p.dq = W("dq").p;
-    p.qt = W("qt").p; p.qt_rs = W("qt").rs; p.qt_cs = W("qt").cs;
-    p.rew = W("b_rew").p; p.term = W("b_term").p; p.bt_rs = W("b_rew").rs;
-    p.logp_next = W("logp_next").p; p.lpn_rs = W("logp_next").rs;
+    td_operands(this, p);
     p.logp_pi = W("logp_pi").p; p.logp_npi = W("logp_npi").p; p.lpp_rs = W("logp_pi").rs;
-    p.target_q = W("target_q").p; p.tq_rs = W("target_q").rs;
     p.B = B; p.N = N; p.A = A; p.Bc = Bc; p.Br = Br; p.gamma = cfg.gamma; p.w = cfg.cql_weight; p.T = cfg.temperature; p.thr = cfg.lagrange_threshold;
     p.max_q_backup = cfg.max_q_backup; p.det_backup = cfg.deterministic_backup; p.with_lagrange = cfg.with_lagrange;
     p.auto_alpha = cfg.auto_alpha; p.fixed_alpha = cfg.alpha;
@@ -228,9 +230,7 @@ int Engine::cql_step() {
     p.gstep_next = tick_folded ? gstep_pre : nullptr;
     ORL_LAUNCH("cql_loss", k_cql_loss_rows, dim3(loss_nblk, 2, R), dim3(256), p);      // (the last workgroup of a run to arrive finishes it)
   }
-  BwdOut bc;
-  if (mlp_backward(this, crit, xc, ch, Mc, W("dq"), dch, true, false, 0, 0, nullptr, "critic.bwd", &bc, gs_dq)) return -1;
-  return adam(ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, make_segs(*crit.lay, bc.ks, bc.ks), ORL_NET_CRITIC1_OLD);
+  return train_net(crit, ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, xc, ch, Mc, W("dq"), dch, "critic.bwd", gs_dq, ORL_NET_CRITIC1_OLD);
 }
 
 }  // namespace orl

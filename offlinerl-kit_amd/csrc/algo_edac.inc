@@ -8,21 +8,14 @@ int Engine::edac_build() {
   const int rep = cfg.max_q_backup ? 10 : 1, Bt = B * rep;   // edac.py:116 hard-codes 10 repeats
   metric_names = {"loss/actor", "loss/critics"};
   add_sac_metrics(this);
-  alloc("n_eps_actor", B, A); alloc("n_eps_next", Bt, A);
+  sac_family_alloc(Kc);
+  alloc("n_eps_next", Bt, A);
   noise_slots = {{"n_eps_actor", 0, B}, {"n_eps_next", 0, Bt}};
-  for (int i = 0; i < L; ++i) {
-    const int h = cfg.hidden[i];
-    const std::string s = std::to_string(i);
-    alloc("ah" + s, B, h); alloc("dah" + s, B, h); alloc("ah2_" + s, Bt > B ? B : B, h);
-    alloc("ca" + s, B, h, Kc); alloc("dca" + s, B, h, Kc);
-    alloc("ct" + s, Bt, h, Kc); alloc("ch" + s, B, h, Kc);
-    if (i < L - 1) { alloc("dch" + s, B, h, Kc); alloc("dd" + s, B, h, Kc); }
-    alloc("tt" + s, B, h, Kc);
-  }
-  alloc("head", B, 2 * A); alloc("head2", B, 2 * A); alloc("dhead", B, 2 * A);
-  alloc("xa", B, XP); alloc("xt", Bt, XP); alloc("xq", B, XP);
-  alloc("logp_a", B, 1); alloc("logp_next", Bt, 1);
-  alloc("qa", B, 1, Kc); alloc("dqa", B, 1, Kc); alloc("dxa", B, A, Kc);
+  alloc_layers("ah2_", B); alloc_layers("ct", Bt, Kc); alloc_layers("ch", B, Kc); alloc_layers("tt", B, Kc);
+  alloc_layers("dch", B, Kc, L - 1); alloc_layers("dd", B, Kc, L - 1);
+  alloc("head2", B, 2 * A);
+  alloc("xt", Bt, XP); alloc("xq", B, XP);
+  alloc("logp_next", Bt, 1);
   alloc("qt", Bt, 1, Kc); alloc("q", B, 1, Kc); alloc("dq", B, 1, Kc); alloc("target_q", B, 1);
   alloc("g", B, A, Kc); alloc("gamma", B, A, Kc);
   taps["qs"] = {W("q"), (long)B * Kc, 1};
@@ -40,17 +33,12 @@ int Engine::edac_step() {
   const int rep = cfg.max_q_backup ? 10 : 1, Bt = B * rep;
   const NetRef actor = net_ref(ORL_NET_ACTOR, 1), crit = net_ref(ORL_NET_CRITIC1, Kc), tgt = net_ref(ORL_NET_CRITIC1_OLD, Kc);
   Mat obs = W("b_obs2"), nobs = W("b_obs2").rows(B), act = W("b_act");
-  std::vector<Mat> ah2, ct, ch, dch, dd, tt;
-  for (int i = 0; i < L; ++i) {
-    const std::string s = std::to_string(i);
-    ah2.push_back(W("ah2_" + s)); ct.push_back(W("ct" + s)); ch.push_back(W("ch" + s)); tt.push_back(W("tt" + s));
-    dch.push_back(i < L - 1 ? W("dch" + s) : Mat()); dd.push_back(i < L - 1 ? W("dd" + s) : Mat());
-  }
+  std::vector<Mat> ah2 = layers("ah2_"), ct = layers("ct"), ch = layers("ch"), dch = layers("dch"), dd = layers("dd"), tt = layers("tt");
   Mat xt = W("xt").shared(), xq = W("xq").shared();
   const MetricsP m{metrics_last, metrics_sum, (int)metric_names.size()};
 
   // ---- actor + temperature (edac.py:96-110; alpha clamped to [0,1]) ----
-  if (sac_actor_phase(this, actor, crit, Kc, true, 2)) return -1;
+  if (sac_actor_phase(actor, crit, Kc, true, 2)) return -1;
 
   // ---- target with the UPDATED actor (edac.py:112-131) ----
   if (mlp_forward_only(nobs, B, actor, ah2, W("head2"), "actor2")) return -1;
@@ -65,21 +53,9 @@ int Engine::edac_step() {
   if (assemble(obs, &act, xq, 0, B, 1)) return -1;
   if (mlp_forward(xq, B, crit, ch, W("q"), "critic")) return -1;
   float* gs_dq = nullptr;
-  {
-    TdLossP p; memset(&p, 0, sizeof(p));
-    p.q = W("q").p; p.q_rs = W("q").rs; p.q_cs = W("q").cs; p.dq = W("dq").p;
-    p.qt = W("qt").p; p.qt_rs = W("qt").rs; p.qt_cs = W("qt").cs; p.Kt = Kc;
-    p.rew = W("b_rew").p; p.term = W("b_term").p; p.bt_rs = W("b_rew").rs;
-    p.logp_next = W("logp_next").p; p.lpn_rs = W("logp_next").rs;
-    p.use_alpha = (!cfg.max_q_backup && !cfg.deterministic_backup) ? 1 : 0;
-    p.target_q = W("target_q").p; p.tq_rs = W("target_q").rs;
-    p.B = B; p.K = Kc; p.rep = rep; p.gamma = cfg.gamma; p.sum_over_k = 1;
-    p.sc = scalars; p.auto_alpha = cfg.auto_alpha; p.fixed_alpha = cfg.alpha; p.m = m; p.slot0 = 1;
-    p.gs_out = gs_dq = gscale_slot();               // (split precision: the seed kernel publishes the dynamic scale of its backward pass)
-    ORL_LAUNCH("td_loss", k_td_loss, dim3(R), dim3(256), p);
-  }
+  if (td_loss(Kc, Kc, rep, (!cfg.max_q_backup && !cfg.deterministic_backup) ? 1 : 0, 1, true, &gs_dq)) return -1;
   BwdOut bc;
-  if (mlp_backward(this, crit, xq, ch, B, W("dq"), dch, true, false, 0, 0, nullptr, "critic.bwd", &bc, gs_dq)) return -1;
+  if (mlp_backward(this, crit, xq, ch, B, W("dq"), dch, true, nullptr, "critic.bwd", &bc, gs_dq)) return -1;
   std::vector<int> ksW = bc.ks, ksB = bc.ks;
 
   // ---- gradient-diversity term (edac.py:136-149) ----
@@ -96,7 +72,8 @@ int Engine::edac_step() {
       if (!s_delta) return -1;
     }
     // (1) unit-seed backward: delta_l = dQ_k/dz_l (top layer stays virtual), g = dQ_k/da
-    if (mlp_backward(this, crit, xq, ch, B, ones, dd, false, true, od, A, &g, "edac.delta", nullptr, s_delta)) return -1;
+    const InputGrad da{od, A, &g};
+    if (mlp_backward(this, crit, xq, ch, B, ones, dd, false, &da, "edac.delta", nullptr, s_delta)) return -1;
     // (2) gamma = d(eta * L_g)/dg ; adds eta*L_g to loss/critics
     float* s_gamma = nullptr;
     {

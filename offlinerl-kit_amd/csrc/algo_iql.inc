@@ -4,24 +4,15 @@ namespace orl {
 int Engine::iql_build() {
   const int A = ad;
   metric_names = {"loss/actor", "loss/q1", "loss/q2", "loss/v"};
-  for (int i = 0; i < L; ++i) {
-    const int h = cfg.hidden[i];
-    const std::string s = std::to_string(i);
-    alloc("ah" + s, B, h); alloc("dah" + s, B, h);
-    alloc("qo_h" + s, B, h, 2); alloc("q_h" + s, B, h, 2); alloc("dq_h" + s, B, h, 2);
-    alloc("v_h" + s, B, h); alloc("dv_h" + s, B, h); alloc("v2_h" + s, 2 * B, h);
-  }
+  alloc_layers("ah", B); alloc_layers("dah", B);
+  alloc_layers("qo_h", B, 2); alloc_layers("q_h", B, 2); alloc_layers("dq_h", B, 2);
+  alloc_layers("v_h", B); alloc_layers("dv_h", B); alloc_layers("v2_h", 2 * B);
   alloc("xq", B, XP);
   alloc("qo", B, 1, 2); alloc("q", B, 1, 2); alloc("dq", B, 1, 2);
   alloc("v", B, 1); alloc("dv", B, 1); alloc("v2", 2 * B, 1); alloc("qmin", B, 1); alloc("exp_a", B, 1); alloc("target_q", B, 1);
   alloc("mraw", B, A); alloc("dmraw", B, A);
   if (cfg.actor_dropout > 0.f) {      // keep masks of the actor backbone's nn.Dropout layers, one per hidden layer (run_iql.py:106)
-    for (int i = 0; i < L; ++i) {
-      const std::string n = "n_drop_a" + std::to_string(i);
-      alloc(n, B, cfg.hidden[i]);
-      NoiseSlot ns; ns.name = n; ns.kind = 2; ns.rows = B; ns.cols = cfg.hidden[i];
-      noise_slots.push_back(ns);
-    }
+    for (const std::string& n : alloc_layers("n_drop_a", B)) noise_slots.push_back({n, 2, B, W(n).pitch});
   }
   taps["q1"] = {W("q").net(0), B, 1};
   taps["q2"] = {W("q").net(1), B, 1};
@@ -36,12 +27,8 @@ int Engine::iql_step() {
   const NetRef actor = net_ref(ORL_NET_ACTOR, 1), qn = net_ref(ORL_NET_CRITIC1, 2), qo = net_ref(ORL_NET_CRITIC1_OLD, 2),
                vn = net_ref(ORL_NET_CRITIC_V, 1);
   Mat obs = W("b_obs2"), obs2 = W("b_obs2"), act = W("b_act");
-  std::vector<Mat> ah, dah, qoh, qh, dqh, vh, dvh, v2h;
-  for (int i = 0; i < L; ++i) {
-    const std::string s = std::to_string(i);
-    ah.push_back(W("ah" + s)); dah.push_back(W("dah" + s)); qoh.push_back(W("qo_h" + s)); qh.push_back(W("q_h" + s));
-    dqh.push_back(W("dq_h" + s)); vh.push_back(W("v_h" + s)); dvh.push_back(W("dv_h" + s)); v2h.push_back(W("v2_h" + s));
-  }
+  std::vector<Mat> ah = layers("ah"), dah = layers("dah"), qoh = layers("qo_h"), qh = layers("q_h"), dqh = layers("dq_h"),
+                   vh = layers("v_h"), dvh = layers("dv_h"), v2h = layers("v2_h");
   Mat xq = W("xq").shared();
   if (assemble(obs, &act, xq, 0, B, 1)) return -1;
 
@@ -51,21 +38,19 @@ int Engine::iql_step() {
   if (mlp_forward(obs, B, vn, vh, W("v"), "v")) return -1;
   {
     IqlVP p; memset(&p, 0, sizeof(p));
-    p.qo = W("qo").p; p.qo_rs = W("qo").rs; p.qo_cs = W("qo").cs; p.v = W("v").p; p.v_rs = W("v").rs; p.dv = W("dv").p;
+    p.qo = W("qo").z(); p.v = W("v").p; p.v_rs = W("v").rs; p.dv = W("dv").p;
     p.qmin = W("qmin").p; p.qmin_rs = W("qmin").rs; p.B = B; p.expectile = cfg.expectile; p.m = mp(); p.m.nm = (int)metric_names.size(); p.slot = 3;
     p.gs_out = gs_v = gscale_slot();               // (split precision: the seed kernel publishes the dynamic scale of its backward pass)
     ORL_LAUNCH("iql_v_loss", k_iql_v_loss, dim3(R), dim3(256), p);
   }
-  BwdOut bv;
-  if (mlp_backward(this, vn, obs, vh, B, W("dv"), dvh, true, false, 0, 0, nullptr, "v.bwd", &bv, gs_v)) return -1;
-  if (adam(ORL_NET_CRITIC_V, 1, ORL_OPT_CRITIC_V, make_segs(*vn.lay, bv.ks, bv.ks), -1)) return -1;
+  if (train_net(vn, ORL_NET_CRITIC_V, 1, ORL_OPT_CRITIC_V, obs, vh, B, W("dv"), dvh, "v.bwd", gs_v)) return -1;
 
   // ---- critics (iql.py:100-116): target from the UPDATED V ----
   if (mlp_forward(xq, B, qn, qh, W("q"), "q")) return -1;
   if (mlp_forward_only(obs2, 2 * B, vn, v2h, W("v2"), "v2")) return -1;
   {
     IqlQP p; memset(&p, 0, sizeof(p));
-    p.q = W("q").p; p.q_rs = W("q").rs; p.q_cs = W("q").cs; p.dq = W("dq").p;
+    p.q = W("q").z(); p.dq = W("dq").p;
     p.v2 = W("v2").p; p.v2_rs = W("v2").rs; p.qmin = W("qmin").p; p.qmin_rs = W("qmin").rs;
     p.rew = W("b_rew").p; p.term = W("b_term").p; p.bt_rs = W("b_rew").rs;
     p.exp_a = W("exp_a").p; p.ea_rs = W("exp_a").rs; p.target_q = W("target_q").p; p.tq_rs = W("target_q").rs;
@@ -73,17 +58,13 @@ int Engine::iql_step() {
     p.gs_out = gs_q = gscale_slot();
     ORL_LAUNCH("iql_q_loss", k_iql_q_loss, dim3(R), dim3(256), p);
   }
-  BwdOut bq;
-  if (mlp_backward(this, qn, xq, qh, B, W("dq"), dqh, true, false, 0, 0, nullptr, "q.bwd", &bq, gs_q)) return -1;
   // Polyak fused here is safe: the actor step below only needs exp_a, already computed from the old targets
-  if (adam(ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, make_segs(*qn.lay, bq.ks, bq.ks), ORL_NET_CRITIC1_OLD)) return -1;
+  if (train_net(qn, ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, xq, qh, B, W("dq"), dqh, "q.bwd", gs_q, ORL_NET_CRITIC1_OLD)) return -1;
 
   // ---- actor (iql.py:118-131) ----
   const float pdrop = cfg.actor_dropout;
   if (pdrop > 0.f) {                   // policy.train() mode: the actor backbone's Dropout layers are active in this forward (iql.py:127)
-    std::vector<Mat> masks;
-    for (int i = 0; i < L; ++i) masks.push_back(W("n_drop_a" + std::to_string(i)));
-    if (mlp_forward_dropout(obs, B, actor, ah, W("mraw"), "actor", pdrop, masks)) return -1;
+    if (mlp_forward_dropout(obs, B, actor, ah, W("mraw"), "actor", pdrop, layers("n_drop_a"))) return -1;
   } else if (mlp_forward(obs, B, actor, ah, W("mraw"), "actor")) return -1;
   {
     IqlAP p; memset(&p, 0, sizeof(p));
@@ -97,12 +78,10 @@ int Engine::iql_step() {
     p.gs_out = gs_a = gscale_slot();
     ORL_LAUNCH("iql_actor_loss", k_iql_actor_loss, dim3(R), dim3(256), p);
   }
-  BwdOut ba;
   bwd_scale = pdrop > 0.f ? 1.0f / (1.0f - pdrop) : 1.0f;
-  const int rc_a = mlp_backward(this, actor, obs, ah, B, W("dmraw"), dah, true, false, 0, 0, nullptr, "actor.bwd", &ba, gs_a);
+  const int rc_a = train_net(actor, ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, obs, ah, B, W("dmraw"), dah, "actor.bwd", gs_a);
   bwd_scale = 1.0f;
-  if (rc_a) return -1;
-  return adam(ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, make_segs(*actor.lay, ba.ks, ba.ks), -1);
+  return rc_a;
 }
 
 }  // namespace orl

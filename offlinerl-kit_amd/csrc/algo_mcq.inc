@@ -8,26 +8,19 @@ int Engine::mcq_build() {
   const int DP = (od + Z + 3) & ~3;                       // decoder input pitch (obs | z)
   metric_names = {"loss/actor", "loss/critic1", "loss/critic2", "loss/behavior_policy"};
   add_sac_metrics(this);
-  alloc("n_eps_vae", B, Z); alloc("n_eps_next", B, A); alloc("n_z_ood", BN2, Z); alloc("n_eps_ood", B2, A); alloc("n_eps_actor", B, A);
+  alloc("n_eps_vae", B, Z); alloc("n_eps_next", B, A); alloc("n_z_ood", BN2, Z); alloc("n_eps_ood", B2, A);
+  sac_family_alloc(2);
   noise_slots = {{"n_eps_vae", 0, B, Z}, {"n_eps_next", 0, B, A}, {"n_z_ood", 0, BN2, Z}, {"n_eps_ood", 0, B2, A}, {"n_eps_actor", 0, B, A}};
-  for (int i = 0; i < L; ++i) {
-    const int h = cfg.hidden[i];
-    const std::string s = std::to_string(i);
-    alloc("ah" + s, B, h); alloc("dah" + s, B, h); alloc("ah2_" + s, B2, h);
-    alloc("ca" + s, B, h, 2); alloc("dca" + s, B, h, 2);
-    alloc("ct" + s, B, h, 2); alloc("cto" + s, BN2, h, 2);
-    alloc("q_h" + s, 3 * B, h, 2); alloc("dq_h" + s, 3 * B, h, 2);
-  }
-  for (int i = 0; i < 2; ++i) {
-    const std::string s = std::to_string(i);
-    alloc("eh" + s, B, VH); alloc("deh" + s, B, VH); alloc("dh" + s, B, VH); alloc("ddh" + s, B, VH); alloc("doh" + s, BN2, VH);
-  }
+  alloc_layers("ah2_", B2); alloc_layers("ct", B, 2); alloc_layers("cto", BN2, 2);
+  alloc_layers("q_h", 3 * B, 2); alloc_layers("dq_h", 3 * B, 2);
+  // (the VAE's two hidden layers are vae_hidden wide, whatever the policy nets are)
+  alloc_layers("eh", B, 1, 2, VH); alloc_layers("deh", B, 1, 2, VH); alloc_layers("dh", B, 1, 2, VH); alloc_layers("ddh", B, 1, 2, VH);
+  alloc_layers("doh", BN2, 1, 2, VH);
   alloc("ehead", B, 2 * Z); alloc("dehead", B, 2 * Z); alloc("vstd", B, Z); alloc("xd", B, DP); alloc("dxd", B, Z);
   alloc("m3", B, A); alloc("dm3", B, A); alloc("xdo", BN2, DP); alloc("m3o", BN2, A);
-  alloc("head", B, 2 * A); alloc("head2", B2, 2 * A); alloc("dhead", B, 2 * A);
-  alloc("xa", B, XP); alloc("xt", B, XP); alloc("xto", BN2, XP); alloc("xq3", 3 * B, XP);
-  alloc("logp_a", B, 1); alloc("logp_next", B, 1); alloc("logp_ood", B2, 1);
-  alloc("qa", B, 1, 2); alloc("dqa", B, 1, 2); alloc("dxa", B, A, 2);
+  alloc("head2", B2, 2 * A);
+  alloc("xt", B, XP); alloc("xto", BN2, XP); alloc("xq3", 3 * B, XP);
+  alloc("logp_next", B, 1); alloc("logp_ood", B2, 1);
   alloc("qt", B, 1, 2); alloc("qto", BN2, 1, 2); alloc("q", 3 * B, 1, 2); alloc("dq", 3 * B, 1, 2);
   alloc("target_q", B, 1); alloc("target_ood", B2, 1);
   taps["q1"] = {W("q").net(0), B, 1};
@@ -44,15 +37,8 @@ int Engine::mcq_step() {
   const NetRef actor = net_ref(ORL_NET_ACTOR, 1), crit = net_ref(ORL_NET_CRITIC1, 2), tgt = net_ref(ORL_NET_CRITIC1_OLD, 2),
                enc = net_ref(ORL_NET_VAE_ENC, 1), dec = net_ref(ORL_NET_VAE_DEC, 1);
   Mat obs = W("b_obs2"), nobs = W("b_obs2").rows(B), obs2 = W("b_obs2"), act = W("b_act");
-  std::vector<Mat> ah2, ct, cto, qh, dqh, eh, deh, dh, ddh, doh;
-  for (int i = 0; i < L; ++i) {
-    const std::string s = std::to_string(i);
-    ah2.push_back(W("ah2_" + s)); ct.push_back(W("ct" + s)); cto.push_back(W("cto" + s)); qh.push_back(W("q_h" + s)); dqh.push_back(W("dq_h" + s));
-  }
-  for (int i = 0; i < 2; ++i) {
-    const std::string s = std::to_string(i);
-    eh.push_back(W("eh" + s)); deh.push_back(W("deh" + s)); dh.push_back(W("dh" + s)); ddh.push_back(W("ddh" + s)); doh.push_back(W("doh" + s));
-  }
+  std::vector<Mat> ah2 = layers("ah2_"), ct = layers("ct"), cto = layers("cto"), qh = layers("q_h"), dqh = layers("dq_h");
+  std::vector<Mat> eh = layers("eh"), deh = layers("deh"), dh = layers("dh"), ddh = layers("ddh"), doh = layers("doh");
   Mat xq3 = W("xq3").shared(), xq = xq3, xs = W("xq3").shared().rows(B), xt = W("xt").shared(), xto = W("xto").shared();
   Mat xd = W("xd"), xdo = W("xdo");
   const MetricsP m{metrics_last, metrics_sum, (int)metric_names.size()};
@@ -77,17 +63,17 @@ int Engine::mcq_step() {
     p.B = B; p.A = A; p.Z = Z; p.max_action = cfg.max_action; p.m = m; p.slot = 3;
     ORL_LAUNCH("vae.loss", k_vae_loss, dim3(R), dim3(256), p);
   }
-  BwdOut bd, be;
+  BwdOut bd;
   Mat dxd = W("dxd");
-  if (mlp_backward(this, dec, xd, dh, B, W("dm3"), ddh, true, true, od, Z, &dxd, "vae.dec.bwd", &bd)) return -1;
+  const InputGrad dz{od, Z, &dxd};
+  if (mlp_backward(this, dec, xd, dh, B, W("dm3"), ddh, true, &dz, "vae.dec.bwd", &bd)) return -1;
   {
     VaeHeadBwdP p; memset(&p, 0, sizeof(p));
     p.dz = dxd.p; p.dz_rs = dxd.rs; p.ehead = W("ehead").p; p.eh_rs = W("ehead").rs; p.stdv = W("vstd").p; p.std_rs = W("vstd").rs;
     p.eps = W("n_eps_vae").p; p.eps_rs = W("n_eps_vae").rs; p.dehead = W("dehead").p; p.B = B; p.Z = Z;
     ORL_LAUNCH("vae.head_bwd", k_vae_head_bwd, dim3((B * Z + 255) / 256, R), dim3(256), p);
   }
-  if (mlp_backward(this, enc, xq, eh, B, W("dehead"), deh, true, false, 0, 0, nullptr, "vae.enc.bwd", &be)) return -1;
-  if (adam(ORL_NET_VAE_ENC, 1, ORL_OPT_VAE, make_segs(*enc.lay, be.ks, be.ks), -1)) return -1;
+  if (train_net(enc, ORL_NET_VAE_ENC, 1, ORL_OPT_VAE, xq, eh, B, W("dehead"), deh, "vae.enc.bwd", nullptr)) return -1;
   if (adam(ORL_NET_VAE_DEC, 1, ORL_OPT_VAE, make_segs(*dec.lay, bd.ks, bd.ks), -1)) return -1;
 
   // ---- one actor forward on [s; s'] serves the TD target's a' ~ pi(s') and the OOD actions pi([s; s']) (mcq.py:63, 80) ----
@@ -122,19 +108,15 @@ int Engine::mcq_step() {
   if (mlp_forward(xq3, 3 * B, crit, qh, W("q"), "critic")) return -1;
   {
     McqLossP p; memset(&p, 0, sizeof(p));
-    p.q = W("q").p; p.q_rs = W("q").rs; p.q_cs = W("q").cs; p.dq = W("dq").p;
-    p.qt = W("qt").p; p.qt_rs = W("qt").rs; p.qt_cs = W("qt").cs; p.qto = W("qto").p; p.qto_rs = W("qto").rs; p.qto_cs = W("qto").cs;
-    p.rew = W("b_rew").p; p.term = W("b_term").p; p.bt_rs = W("b_rew").rs; p.logp_next = W("logp_next").p; p.lpn_rs = W("logp_next").rs;
-    p.target_q = W("target_q").p; p.tq_rs = W("target_q").rs; p.target_ood = W("target_ood").p; p.to_rs = W("target_ood").rs;
+    td_operands(this, p);
+    p.qto = W("qto").z(); p.target_ood = W("target_ood").p; p.to_rs = W("target_ood").rs;
     p.B = B; p.N = N; p.gamma = cfg.gamma; p.lambda = cfg.mcq_lambda; p.sc = scalars; p.auto_alpha = cfg.auto_alpha; p.fixed_alpha = cfg.alpha;
     p.m = m; p.slot0 = 1;
     ORL_LAUNCH("mcq_loss", k_mcq_loss, dim3(R), dim3(256), p);
   }
-  BwdOut bc;
-  if (mlp_backward(this, crit, xq3, qh, 3 * B, W("dq"), dqh, true, false, 0, 0, nullptr, "critic.bwd", &bc)) return -1;
-  if (adam(ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, make_segs(*crit.lay, bc.ks, bc.ks), ORL_NET_CRITIC1_OLD)) return -1;
+  if (train_net(crit, ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, xq3, qh, 3 * B, W("dq"), dqh, "critic.bwd", nullptr, ORL_NET_CRITIC1_OLD)) return -1;
   // ---- actor + temperature against the UPDATED critics (mcq.py:96-111; alpha clamped to [0, 1]) ----
-  return sac_actor_phase(this, actor, crit, 2, true, 4);
+  return sac_actor_phase(actor, crit, 2, true, 4);
 }
 
 }  // namespace orl

@@ -4,23 +4,15 @@
 // [0, 1], Polyak at the end.  Included by engine.hip.
 namespace orl {
 
-int Engine::sac_build() {
+// SAC's workspaces and taps; MOBILE (algo_mobile.inc) adds its penalty pass to them.  The callers list the noise slots.
+void Engine::sac_alloc() {
   const int A = ad;
-  metric_names = {"loss/actor", "loss/critic1", "loss/critic2"};
-  add_sac_metrics(this);
-  alloc("n_eps_next", B, A); alloc("n_eps_actor", B, A);
-  noise_slots = {{"n_eps_next", 0, B}, {"n_eps_actor", 0, B}};      // the reference's draw order: actforward(next_obss) first (sac.py:95)
-  for (int i = 0; i < L; ++i) {
-    const int h = cfg.hidden[i];
-    const std::string s = std::to_string(i);
-    alloc("ah" + s, B, h); alloc("dah" + s, B, h); alloc("an_h" + s, B, h);
-    alloc("ca" + s, B, h, 2); alloc("dca" + s, B, h, 2);
-    alloc("ct" + s, B, h, 2); alloc("q_h" + s, B, h, 2); alloc("dq_h" + s, B, h, 2);
-  }
-  alloc("head", B, 2 * A); alloc("head_n", B, 2 * A); alloc("dhead", B, 2 * A);
-  alloc("xa", B, XP); alloc("xt", B, XP); alloc("xq", B, XP);
-  alloc("logp_a", B, 1); alloc("logp_next", B, 1);
-  alloc("qa", B, 1, 2); alloc("dqa", B, 1, 2); alloc("dxa", B, A, 2);
+  sac_family_alloc(2);
+  alloc("n_eps_next", B, A);
+  alloc_layers("an_h", B); alloc_layers("ct", B, 2); alloc_layers("q_h", B, 2); alloc_layers("dq_h", B, 2);
+  alloc("head_n", B, 2 * A);
+  alloc("xt", B, XP); alloc("xq", B, XP);
+  alloc("logp_next", B, 1);
   alloc("qt", B, 1, 2); alloc("q", B, 1, 2); alloc("dq", B, 1, 2); alloc("target_q", B, 1);
   taps["q1"] = {W("q").net(0), B, 1};
   taps["q2"] = {W("q").net(1), B, 1};
@@ -28,51 +20,48 @@ int Engine::sac_build() {
   taps["q2a"] = {W("qa").net(1), B, 1};
   taps["logp_a"] = {W("logp_a"), B, 1};
   taps["target_q"] = {W("target_q"), B, 1};
+}
+
+int Engine::sac_build() {
+  metric_names = {"loss/actor", "loss/critic1", "loss/critic2"};
+  add_sac_metrics(this);
+  sac_alloc();
+  noise_slots = {{"n_eps_next", 0, B}, {"n_eps_actor", 0, B}};      // the reference's draw order: actforward(next_obss) first (sac.py:95)
   return 0;
 }
 
-int Engine::sac_step() {
-  const int A = ad;
-  const NetRef actor = net_ref(ORL_NET_ACTOR, 1), crit = net_ref(ORL_NET_CRITIC1, 2), tgt = net_ref(ORL_NET_CRITIC1_OLD, 2);
-  Mat obs = W("b_obs2"), nobs = W("b_obs2").rows(B), act = W("b_act");
-  std::vector<Mat> anh, ct, qh, dqh;
-  for (int i = 0; i < L; ++i) {
-    const std::string s = std::to_string(i);
-    anh.push_back(W("an_h" + s)); ct.push_back(W("ct" + s)); qh.push_back(W("q_h" + s)); dqh.push_back(W("dq_h" + s));
-  }
-  Mat xt = W("xt").shared(), xq = W("xq").shared();
-  const MetricsP m{metrics_last, metrics_sum, (int)metric_names.size()};
-
-  // ---- TD target (sac.py:94-100): a' ~ pi(s'), y = r + gamma (1 - d) (min Q_old(s', a') - alpha logp') ----
+// TD target inputs (sac.py:94-100): a' ~ pi(s') with the CURRENT actor, then the target critics on (s', a')
+int Engine::sac_td_target() {
+  const NetRef actor = net_ref(ORL_NET_ACTOR, 1), tgt = net_ref(ORL_NET_CRITIC1_OLD, 2);
+  Mat nobs = W("b_obs2").rows(B), xt = W("xt").shared();
+  std::vector<Mat> anh = layers("an_h"), ct = layers("ct");
   if (mlp_forward_only(nobs, B, actor, anh, W("head_n"), "actor_next")) return -1;
   if (assemble(nobs, nullptr, xt, 0, B, 1)) return -1;
-  {
-    SampleJob j = make_job(0, B, 1, W("n_eps_next"), xt, od, 0, W("logp_next"));
-    if (launch_sample(this, W("head_n"), A, &j, 1)) return -1;
-  }
-  if (mlp_forward_only(xt, B, tgt, ct, W("qt"), "target")) return -1;
-  // ---- critics (sac.py:93, 102-110) ----
+  SampleJob j = make_job(0, B, 1, W("n_eps_next"), xt, od, 0, W("logp_next"));
+  if (launch_sample(this, W("head_n"), ad, &j, 1)) return -1;
+  return mlp_forward_only(xt, B, tgt, ct, W("qt"), "target");
+}
+
+// critics (sac.py:93, 102-110): Q(s, a), loss_launch(gs) seeds dq and publishes its scale in gs, backward, Adam.  The Polyak update fused
+// into the Adam launch is safe: nothing behind it reads the targets (sac.py:131 syncs after the actor step; same values either way)
+template <class F>
+int Engine::sac_critics(F loss_launch) {
+  const NetRef crit = net_ref(ORL_NET_CRITIC1, 2);
+  Mat obs = W("b_obs2"), act = W("b_act"), xq = W("xq").shared();
+  std::vector<Mat> qh = layers("q_h"), dqh = layers("dq_h");
   if (assemble(obs, &act, xq, 0, B, 1)) return -1;
   if (mlp_forward(xq, B, crit, qh, W("q"), "critic")) return -1;
   float* gs_dq = nullptr;
-  {
-    TdLossP p; memset(&p, 0, sizeof(p));
-    p.q = W("q").p; p.q_rs = W("q").rs; p.q_cs = W("q").cs; p.dq = W("dq").p;
-    p.qt = W("qt").p; p.qt_rs = W("qt").rs; p.qt_cs = W("qt").cs; p.Kt = 2;
-    p.rew = W("b_rew").p; p.term = W("b_term").p; p.bt_rs = W("b_rew").rs;
-    p.logp_next = W("logp_next").p; p.lpn_rs = W("logp_next").rs; p.use_alpha = 1;
-    p.target_q = W("target_q").p; p.tq_rs = W("target_q").rs;
-    p.B = B; p.K = 2; p.rep = 1; p.gamma = cfg.gamma; p.sum_over_k = 0;
-    p.sc = scalars; p.auto_alpha = cfg.auto_alpha; p.fixed_alpha = cfg.alpha; p.m = m; p.slot0 = 1;
-    p.gs_out = gs_dq = gscale_slot();               // (split precision: the seed kernel publishes the dynamic scale of its backward pass)
-    ORL_LAUNCH("td_loss", k_td_loss, dim3(R), dim3(256), p);
-  }
-  BwdOut bc;
-  if (mlp_backward(this, crit, xq, qh, B, W("dq"), dqh, true, false, 0, 0, nullptr, "critic.bwd", &bc, gs_dq)) return -1;
-  // Polyak fused here is safe: nothing below reads the targets (sac.py:131 syncs after the actor step; same values either way)
-  if (adam(ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, make_segs(*crit.lay, bc.ks, bc.ks), ORL_NET_CRITIC1_OLD)) return -1;
+  if (loss_launch(&gs_dq)) return -1;
+  return train_net(crit, ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, xq, qh, B, W("dq"), dqh, "critic.bwd", gs_dq, ORL_NET_CRITIC1_OLD);
+}
+
+int Engine::sac_step() {
+  // ---- TD target: y = r + gamma (1 - d) (min Q_old(s', a') - alpha logp'), then the critics ----
+  if (sac_td_target()) return -1;
+  if (sac_critics([&](float** gs) { return td_loss(2, 2, 1, 1, 0, true, gs); })) return -1;
   // ---- actor + temperature against the UPDATED critics (sac.py:112-129; alpha clamped to [0, 1]) ----
-  return sac_actor_phase(this, actor, crit, 2, true, 3);
+  return sac_actor_phase(net_ref(ORL_NET_ACTOR, 1), net_ref(ORL_NET_CRITIC1, 2), 2, true, 3);
 }
 
 }  // namespace orl

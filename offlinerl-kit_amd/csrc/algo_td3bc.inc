@@ -6,13 +6,9 @@ int Engine::td3bc_build() {
   metric_names = {"loss/actor", "loss/critic1", "loss/critic2"};
   alloc("n_eps_target", B, A);
   noise_slots = {{"n_eps_target", 0, B}};
-  for (int i = 0; i < L; ++i) {
-    const int h = cfg.hidden[i];
-    const std::string s = std::to_string(i);
-    alloc("ah" + s, B, h); alloc("dah" + s, B, h); alloc("ao_h" + s, B, h);
-    alloc("ct" + s, B, h, 2); alloc("q_h" + s, B, h, 2); alloc("dq_h" + s, B, h, 2);
-    alloc("cp_h" + s, B, h); alloc("dcp_h" + s, B, h);
-  }
+  alloc_layers("ah", B); alloc_layers("dah", B); alloc_layers("ao_h", B);
+  alloc_layers("ct", B, 2); alloc_layers("q_h", B, 2); alloc_layers("dq_h", B, 2);
+  alloc_layers("cp_h", B); alloc_layers("dcp_h", B);
   alloc("xq", B, XP); alloc("xt", B, XP); alloc("xa", B, XP);
   alloc("mraw_t", B, A); alloc("mraw", B, A); alloc("dmraw", B, A); alloc("dxa", B, A);
   alloc("qt", B, 1, 2); alloc("q", B, 1, 2); alloc("dq", B, 1, 2); alloc("qpi", B, 1); alloc("dqpi", B, 1); alloc("target_q", B, 1);
@@ -28,12 +24,8 @@ int Engine::td3bc_step(bool actor_step) {
   const NetRef actor = net_ref(ORL_NET_ACTOR, 1), actor_old = net_ref(ORL_NET_ACTOR_OLD, 1), crit = net_ref(ORL_NET_CRITIC1, 2),
                crit1 = net_ref(ORL_NET_CRITIC1, 1), tgt = net_ref(ORL_NET_CRITIC1_OLD, 2);
   Mat obs = W("b_obs2"), nobs = W("b_obs2").rows(B), act = W("b_act");
-  std::vector<Mat> ah, dah, aoh, ct, qh, dqh, cph, dcph;
-  for (int i = 0; i < L; ++i) {
-    const std::string s = std::to_string(i);
-    ah.push_back(W("ah" + s)); dah.push_back(W("dah" + s)); aoh.push_back(W("ao_h" + s)); ct.push_back(W("ct" + s));
-    qh.push_back(W("q_h" + s)); dqh.push_back(W("dq_h" + s)); cph.push_back(W("cp_h" + s)); dcph.push_back(W("dcp_h" + s));
-  }
+  std::vector<Mat> ah = layers("ah"), dah = layers("dah"), aoh = layers("ao_h"), ct = layers("ct"), qh = layers("q_h"), dqh = layers("dq_h"),
+                   cph = layers("cp_h"), dcph = layers("dcp_h");
   Mat xq = W("xq").shared(), xt = W("xt").shared(), xa = W("xa").shared();
   const MetricsP m{metrics_last, metrics_sum, (int)metric_names.size()};
 
@@ -52,21 +44,10 @@ int Engine::td3bc_step(bool actor_step) {
   // ---- critics (td3bc.py:88,95-104) ----
   if (assemble(obs, &act, xq, 0, B, 1)) return -1;
   if (mlp_forward(xq, B, crit, qh, W("q"), "critic")) return -1;
-  {
-    TdLossP p; memset(&p, 0, sizeof(p));
-    p.q = W("q").p; p.q_rs = W("q").rs; p.q_cs = W("q").cs; p.dq = W("dq").p;
-    p.qt = W("qt").p; p.qt_rs = W("qt").rs; p.qt_cs = W("qt").cs; p.Kt = 2;
-    p.rew = W("b_rew").p; p.term = W("b_term").p; p.bt_rs = W("b_rew").rs;
-    p.target_q = W("target_q").p; p.tq_rs = W("target_q").rs;
-    p.B = B; p.K = 2; p.rep = 1; p.gamma = cfg.gamma; p.sum_over_k = 0; p.sc = scalars; p.m = m; p.slot0 = 1;
-    p.gs_out = gs_dq = gscale_slot();               // (split precision: the seed kernel publishes the dynamic scale of its backward pass)
-    ORL_LAUNCH("td_loss", k_td_loss, dim3(R), dim3(256), p);
-  }
-  BwdOut bc;
-  if (mlp_backward(this, crit, xq, qh, B, W("dq"), dqh, true, false, 0, 0, nullptr, "critic.bwd", &bc, gs_dq)) return -1;
+  if (td_loss(2, 2, 1, 0, 0, false, &gs_dq)) return -1;
   // on the delayed-update steps the critics' Polyak sync (td3bc.py:65-71, after both updates) rides in their Adam launch: the actor phase below
   // reads the ONLINE critic only, and the targets are not read again before the next step
-  if (adam(ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, make_segs(*crit.lay, bc.ks, bc.ks), actor_step ? ORL_NET_CRITIC1_OLD : -1)) return -1;
+  if (train_net(crit, ORL_NET_CRITIC1, 2, ORL_OPT_CRITIC, xq, qh, B, W("dq"), dqh, "critic.bwd", gs_dq, actor_step ? ORL_NET_CRITIC1_OLD : -1)) return -1;
 
   if (!actor_step) {
     ORL_LAUNCH("td3_report", k_td3_report_last, dim3(R), dim3(64), (const RunScalars*)scalars, m, 0);
@@ -90,7 +71,8 @@ int Engine::td3bc_step(bool actor_step) {
     ORL_LAUNCH("td3_actor_loss", k_td3_actor_loss, dim3(R), dim3(256), p);
   }
   Mat dxa = W("dxa");
-  if (mlp_backward(this, crit1, xa, cph, B, W("dqpi"), dcph, false, true, od, A, &dxa, "critic_pi.bwd", nullptr, gs_pi)) return -1;
+  const InputGrad da{od, A, &dxa};
+  if (mlp_backward(this, crit1, xa, cph, B, W("dqpi"), dcph, false, &da, "critic_pi.bwd", nullptr, gs_pi)) return -1;
   {
     Td3ActorBwdP p; memset(&p, 0, sizeof(p));
     p.dxa = dxa.p; p.dxa_rs = dxa.rs; p.dxa_pitch = A; p.xa = xa.p; p.xa_rs = xa.rs; p.XP = XP; p.od = od;
@@ -99,10 +81,8 @@ int Engine::td3bc_step(bool actor_step) {
     p.gs_out = gs_a = gscale_slot();
     ORL_LAUNCH("td3_actor_bwd", k_td3_actor_bwd, dim3(R), dim3(256), p);
   }
-  BwdOut ba;
-  if (mlp_backward(this, actor, obs, ah, B, W("dmraw"), dah, true, false, 0, 0, nullptr, "actor.bwd", &ba, gs_a)) return -1;
   const unsigned long long f = cfg.update_actor_freq > 0 ? cfg.update_actor_freq : 1;
-  return adam(ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, make_segs(*actor.lay, ba.ks, ba.ks), ORL_NET_ACTOR_OLD, f);
+  return train_net(actor, ORL_NET_ACTOR, 1, ORL_OPT_ACTOR, obs, ah, B, W("dmraw"), dah, "actor.bwd", gs_a, ORL_NET_ACTOR_OLD, f);
 }
 
 }  // namespace orl

@@ -118,16 +118,6 @@ struct Engine {
   orl_config cfg;
   int dev = 0;
   hipStream_t stream = nullptr;
-  // A second stream for launches that do not depend on each other (CQL: the target critics' forward next to the critics' forward, both fed
-  // by the actor pass before them): fork_side() makes `stream` the side stream until fork_main(); fork_join() makes the main stream wait for
-  // the side work.  Inside a graph capture the three calls become a fork / join of the captured graph.  OFF by default (ORL_FORK=1 enables it):
-  // measured 10 us per step SLOWER at 1 - 8 runs per engine -- a fork / join of graph branches costs more than the 12 us launch it hides.
-  hipStream_t side_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool fork_on = false, forked = false;
-  int fork_side();
-  void fork_main() { if (forked) std::swap(stream, side_stream); }
-  int fork_join();
   int R = 1, B = 0, N = 0, od = 0, ad = 0, OP = 0, AP = 0, XP = 0, L = 0, K = 2;
   NetLayout lay[ORL_NUM_NETS];
   float* arena = nullptr;      // [R][P_train] then [R][P_tgt]
@@ -138,7 +128,6 @@ struct Engine {
   float* adam_v = nullptr;
   float* grads = nullptr;      // [R][max_slab][P_train]
   int max_slab = 128;          // split-K slabs per parameter (the fused layer-0 weight gradient writes one per row tile)
-  int ksplit_cap = 32;         // cap of the split-K factor chosen for a stand-alone wgrad launch
   int wgrad_wg_target = 512, wgrad_long_min = 4, wgrad_small_ks = 1;   // wgrad_ksplit's rules (ORL_WGRAD_WG_TARGET / _LONG_MIN / _SMALL_KS)
   int wgrad_ksplit(int Mout, int Nout, int Krows, int nz) const;
   RunScalars* scalars = nullptr;
@@ -265,6 +254,12 @@ struct Engine {
   void read_env();             // every ORL_* knob of the engine, read once per engine
   Mat alloc(const std::string& name, long rows, int pitch, int nets = 1);
   Mat& W(const std::string& n) { return ws.at(n); }
+  // a per-layer workspace family: "<stem>0" .. "<stem><upto - 1>" (upto < 0: all L layers), layer i with pitch cfg.hidden[i]; layers()
+  // returns its L views in one lookup, an empty Mat where upto stopped short (the top layer of a dgrad family is never materialised).
+  // width > 0: a net of its own depth -- `upto` layers, all that wide (MCQ's VAE).  Returns the workspace names.
+  std::vector<std::string> alloc_layers(const std::string& stem, long rows, int nets = 1, int upto = -1, int width = 0);
+  std::vector<Mat> layers(const std::string& stem) const { return families.at(stem); }
+  std::map<std::string, std::vector<Mat>> families;
   float* raw_alloc(size_t bytes);
   float* net_ptr(int run, int net) const;
   NetRef net_ref(int net, int members) const;
@@ -306,6 +301,10 @@ struct Engine {
     return recompute_h0 && layer == 1 && l.L >= 3 && !l.ens && ws_precision_ok() && ws_wgrad_rows_ok(M, nz);
   }
   int adam(int net, int nnets, int lr_slot, const std::vector<std::pair<long, int>>& segs, int target_net, unsigned long long t_div = 1);
+  // the weight gradients of a net from the seed dL/d(tail output) (no input gradient), then its Adam step (target_net >= 0: with the fused
+  // Polyak update of that net); gs: the seed's dynamic scale where its kernel published one (split precision), else null
+  int train_net(const NetRef& nr, int net, int members, int opt, const Mat& X, const std::vector<Mat>& hs, int M, const Mat& seed,
+                std::vector<Mat>& dhs, const char* tag, const float* gs, int target_net = -1, unsigned long long t_div = 1);
   int polyak(int target_net, int src_net, int nnets);
   void prof_begin(const char* name, double flops, double bytes = 0);
   void prof_end();
@@ -334,9 +333,15 @@ struct Engine {
 
   int enqueue_sample();
   int enqueue_noise();
+  int enqueue_inputs() { return prep.empty() ? (enqueue_sample() || enqueue_noise()) : enqueue_prepare(true, true); }   // a drawn batch and its noise
   int enqueue_step(int variant);
   int step_variant() const;
   int n_variants() const;
+  // n_steps steps between two timing events: variant v of the step is the captured graph slot0 + v (captured here when missing; eager launches
+  // when graphs are off or the run is profiled), with_inputs: every step draws its batch first.  Ends in finish() on the metric sums.
+  int run_steps(int slot0, long n_steps, bool with_inputs, float* metrics_mean, float* elapsed_ms);
+  // reads [R][nm] metrics back from `src`, hands them out divided by `divisor` in rows of ORL_MAX_METRICS, updates the health words
+  int finish(const float* src, float divisor, float* metrics_out, long steps);
   int build_common();
   int cql_build(); int cql_step();
   int iql_build(); int iql_step();
@@ -348,6 +353,16 @@ struct Engine {
   int rcsl_build(); int rcsl_step(); int rcsl_prepare(int mode);
   int rcslg_build(); int rcslg_step();
   int autoreg_build(); int autoreg_step(); int autoreg_prepare(int mode);
+  // phases shared between algorithms (algo_cql.inc: the SAC family; algo_sac.inc: SAC / MOBILE; algo_rcsl.inc: the supervised policies)
+  void sac_family_alloc(int Kc);      // what sac_actor_phase consumes, for Kc critics
+  int sac_actor_phase(const NetRef& actor, const NetRef& crit, int Kc, bool clamp_alpha01, int slot_alpha_loss);
+  int td_loss(int Kc, int Kt, int rep, int use_alpha, int sum_over_k, bool with_logp_next, float** gs_out);
+  void sac_alloc();                   // SAC's workspaces and taps (MOBILE adds its penalty pass to them)
+  int sac_td_target();                // a' ~ pi(s'), the target critics on (s', a')
+  template <class F> int sac_critics(F loss_launch);      // critics on (s, a), loss_launch(gs) seeds dq, backward + Adam with the fused Polyak
+  int epoch_build(long rows);         // hidden activations of the one net on `rows` rows, the ordered epoch's cell and flag word
+  template <class P> int epoch_prepare(const char* tag, P& p, const float*& d_rew, int mode, dim3 grid, void (*const kern[3])(P));
+  template <class F> int supervised_step(const Mat& x, int M, const Mat& out, const Mat& dseed, const char* tag, F head_launch);
   // orl_autoreg_sample: workspaces for n rows per run (input, hidden activations, tail, eps), regrown when n grows; the call counter of
   // the device-drawn stream lives in a device cell of its own (the step counter and orl_learn_n's streams stay untouched)
   int autoreg_sample(const float* obs, long n, const float* eps, bool on_device, float* act_out);

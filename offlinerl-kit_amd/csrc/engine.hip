@@ -237,10 +237,6 @@ Engine::~Engine() {
   }
   for (auto& e : ev_pool) hipEventDestroy(e);
   for (void* p : allocs) hipFree(p);
-  if (forked) std::swap(stream, side_stream);
-  if (ev_fork) hipEventDestroy(ev_fork);
-  if (ev_join) hipEventDestroy(ev_join);
-  if (side_stream) hipStreamDestroy(side_stream);
   if (stream) hipStreamDestroy(stream);
 }
 
@@ -278,6 +274,18 @@ Mat Engine::alloc(const std::string& name, long rows, int pitch, int nets) {
   return m;
 }
 
+std::vector<std::string> Engine::alloc_layers(const std::string& stem, long rows, int nets, int upto, int width) {
+  const int n = upto < 0 ? L : upto;
+  std::vector<Mat>& fam = families[stem];
+  fam.assign(width > 0 ? n : L, Mat());
+  std::vector<std::string> names;
+  for (int i = 0; i < n; ++i) {
+    names.push_back(stem + std::to_string(i));
+    fam[i] = alloc(names.back(), rows, width > 0 ? width : cfg.hidden[i], nets);
+  }
+  return names;
+}
+
 float* Engine::net_ptr(int run, int net) const {
   if (net < 0 || net >= ORL_NUM_NETS || !lay[net].present) return nullptr;
   if (net_is_target[net]) return arena + (long)R * P_train + (long)run * P_tgt + net_off[net];
@@ -313,21 +321,6 @@ void Engine::prof_begin(const char* name, double flops, double bytes) {
 void Engine::prof_end() {
   if (!prof_on) return;
   hipEventRecord(prof.back().b, stream);
-}
-
-int Engine::fork_side() {
-  forked = false;
-  if (!fork_on || prof_on) return 0;                 // (the per-tag timing of a profiled run brackets launches on the main stream)
-  if (hipEventRecord(ev_fork, stream) != hipSuccess || hipStreamWaitEvent(side_stream, ev_fork, 0) != hipSuccess) return fail("fork: event");
-  std::swap(stream, side_stream);
-  forked = true;
-  return 0;
-}
-int Engine::fork_join() {
-  if (!forked) return 0;
-  forked = false;                                    // (fork_main() has swapped the streams back: side_stream holds the side work)
-  if (hipEventRecord(ev_join, side_stream) != hipSuccess || hipStreamWaitEvent(stream, ev_join, 0) != hipSuccess) return fail("join: event");
-  return 0;
 }
 
 float* Engine::gscale_slot() {
@@ -766,7 +759,7 @@ int Engine::wgrad_ksplit(int Mout, int Nout, int Krows, int nz) const {
   // tiles of a net sat on four XCDs.  With the z-major mapping (gemm_kernel.h) one range wins: EDAC 15.4k -> 16.9k steps/s, IQL +2.5 %,
   // TD3+BC +2.5 % at 128 runs (Adam reads half the slabs).  ORL_WGRAD_SMALL_KS=2 restores the old rule for A/B runs.
   if (cfg == CFG_SQ && Krows < 1024 && kchunks >= 8) ks = std::max(ks, wgrad_small_ks);
-  ks = std::max(1, std::min(ks, std::min(ksplit_cap, kchunks)));
+  ks = std::max(1, std::min(ks, std::min(32, kchunks)));
   while (ks > 1 && (kchunks + ks - 1) / ks < 2) --ks;
   return ks;
 }
@@ -1043,10 +1036,13 @@ static std::vector<std::pair<long, int>> make_segs(const NetLayout& l, const std
 }
 
 // generic backward through an MLP family.  dTail: [M x out_dim] gradient w.r.t. the tail output.
+// dxin (optional): also the gradient w.r.t. the input columns [col0, col0 + ncols), written to *dX.
 struct BwdOut { std::vector<int> ks; };
+struct InputGrad { int col0, ncols; const Mat* dX; };
 static int mlp_backward(Engine* e, const NetRef& nr, const Mat& X, const std::vector<Mat>& hs, int M, const Mat& dTail,
-                        std::vector<Mat>& dz, bool want_w, bool want_dx, int dx_col0, int dx_ncols, const Mat* dX,
-                        const char* tag, BwdOut* out, const float* gscale_given = nullptr) {
+                        std::vector<Mat>& dz, bool want_w, const InputGrad* dxin, const char* tag, BwdOut* out,
+                        const float* gscale_given = nullptr) {
+  const bool want_dx = dxin != nullptr;
   const NetLayout& l = *nr.lay;
   const int L = l.L;
   const bool rank1 = (l.out_dim == 1);
@@ -1092,11 +1088,18 @@ static int mlp_backward(Engine* e, const NetRef& nr, const Mat& X, const std::ve
       if (e->bwd_scale != 1.0f && e->scale_inplace(dz[i - 1], M, l.layer_out(i - 1), nr.nz1, e->bwd_scale, nullptr, (t + ".dropout_bwd").c_str())) return -1;
       cur = DY::plain(dz[i - 1]);
     } else if (want_dx) {
-      if (e->linear_dgrad(cur, M, nr, 0, dx_col0, dx_ncols, nullptr, *dX, (t + ".dgrad_x").c_str())) return -1;
+      if (e->linear_dgrad(cur, M, nr, 0, dxin->col0, dxin->ncols, nullptr, *dxin->dX, (t + ".dgrad_x").c_str())) return -1;
     }
   }
   if (out) out->ks = ks;
   return 0;
+}
+
+int Engine::train_net(const NetRef& nr, int net, int members, int opt, const Mat& X, const std::vector<Mat>& hs, int M, const Mat& seed,
+                      std::vector<Mat>& dhs, const char* tag, const float* gs, int target_net, unsigned long long t_div) {
+  BwdOut b;
+  if (mlp_backward(this, nr, X, hs, M, seed, dhs, true, nullptr, tag, &b, gs)) return -1;
+  return adam(net, members, opt, make_segs(*nr.lay, b.ks, b.ks), target_net, t_div);
 }
 
 // tanh-Gaussian sampling launch (up to 3 jobs)
@@ -1166,7 +1169,6 @@ void Engine::read_env() {
   enum Kind { FLAG, NFLAG, POS_I, POS_L, ANY_I };      // != 0 / == 0 -> bool; a value > 0 -> int / long (anything else ignored); any int
   int cus = 0;
   const struct { const char* name; void* field; Kind kind; } knobs[] = {
-      {"ORL_FORK", &fork_on, FLAG},
       {"ORL_WS", &use_ws, FLAG},
       {"ORL_WS32", &use_ws32, FLAG},
       {"ORL_WS_KEEP_H1", &elide_top, NFLAG},
@@ -1215,9 +1217,6 @@ int Engine::init(const orl_config& c) {
     return fail("actor_dropout: supported for IQL only (run_iql.py --dropout_rate), 0 < p < 1");
   if (build_layouts(c, lay, net_off, net_is_target, &P_train, &P_tgt)) return -1;
   ORL_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  ORL_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
-  ORL_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-  ORL_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
   // launch geometry of the weight-stationary kernels: config fields, overridden once (here) by the environment
   ws_geo.one_round = c.ws_one_round != 0;
   ws_geo.cus = (c.ws_cus >= 8 && c.ws_cus <= 256) ? c.ws_cus : 256;
@@ -1416,6 +1415,55 @@ int Engine::enqueue_step(int variant) {
   if (tick_folded) return 0;               // the step's own kernels advanced the counter
   hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, stream, gstep);
   return hipGetLastError() == hipSuccess ? 0 : fail("tick launch");
+}
+
+int Engine::run_steps(int slot0, long n_steps, bool with_inputs, float* metrics_mean, float* elapsed_ms) {
+  const bool graphable = use_graph && !prof_on;
+  if (graphable) {
+    for (int v = 0; v < n_variants(); ++v) {
+      if (graph_exec[slot0 + v]) continue;
+      ORL_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
+      const int rc = (with_inputs && enqueue_inputs()) || enqueue_step(v);
+      const hipError_t ce = hipStreamEndCapture(stream, &graph[slot0 + v]);
+      if (rc) return -1;
+      if (ce != hipSuccess) return fail(std::string("graph capture: ") + hipGetErrorString(ce));
+      ORL_HIP(hipGraphInstantiate(&graph_exec[slot0 + v], graph[slot0 + v], nullptr, nullptr, 0));
+    }
+  }
+  // (the two timing events are released on every exit path, early error returns included)
+  struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+  } ev;
+  ORL_HIP(hipEventCreate(&ev.a));
+  ORL_HIP(hipEventCreate(&ev.b));
+  if (prof_on) { prof.clear(); ev_used = 0; }
+  ORL_HIP(hipEventRecord(ev.a, stream));
+  for (long s = 0; s < n_steps; ++s) {
+    const int v = step_variant();
+    if (graphable) { ORL_HIP(hipGraphLaunch(graph_exec[slot0 + v], stream)); }
+    else if ((with_inputs && enqueue_inputs()) || enqueue_step(v)) return -1;
+    step_host++;
+  }
+  ORL_HIP(hipEventRecord(ev.b, stream));
+  ORL_HIP(hipStreamSynchronize(stream));
+  float ms = 0.f;
+  ORL_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+  if (elapsed_ms) *elapsed_ms = ms;
+  return finish(metrics_sum, (float)n_steps, metrics_mean, n_steps);      // (a non-finite metric of ANY of the steps stays in its sum)
+}
+
+// Called after the stream has been synchronised.
+int Engine::finish(const float* src, float divisor, float* metrics_out, long steps) {
+  std::vector<float> m(R * nm);
+  ORL_HIP(hipMemcpy(m.data(), src, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
+  if (metrics_out) {
+    for (int r = 0; r < R; ++r)
+      for (int k = 0; k < ORL_MAX_METRICS; ++k) metrics_out[r * ORL_MAX_METRICS + k] = k < nm ? m[r * nm + k] / divisor : 0.f;
+  }
+  unsigned int bad = 0;
+  if (health_update(m.data(), steps, &bad)) return -1;
+  return bad ? ORL_RC_UNHEALTHY : 0;
 }
 
 }  // namespace orl
@@ -2038,15 +2086,7 @@ int orl_step(orl_engine* h, const orl_batch* b, const orl_noise* nz, float* metr
   e.step_host++;
   ORL_HIP(hipStreamSynchronize(e.stream));
   e.mobile_samples = nullptr;
-  std::vector<float> m(e.R * e.nm);
-  ORL_HIP(hipMemcpy(m.data(), e.metrics_last, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
-  if (metrics) {
-    for (int r = 0; r < e.R; ++r)
-      for (int k = 0; k < ORL_MAX_METRICS; ++k) metrics[r * ORL_MAX_METRICS + k] = k < e.nm ? m[r * e.nm + k] : 0.f;
-  }
-  unsigned int bad = 0;
-  if (e.health_update(m.data(), 1, &bad)) return -1;
-  return bad ? ORL_RC_UNHEALTHY : 0;
+  return e.finish(e.metrics_last, 1.0f, metrics, 1);
 }
 
 int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_ms) {
@@ -2081,52 +2121,7 @@ int orl_learn_n(orl_engine* h, int n_steps, float* metrics_mean, float* elapsed_
     if (e.mbuf) e.mbuf_gen = e.mbuf->gen;
     if (rings_moved && e.upload_model_table()) return -1;      // (a reserve moved a ring's arrays: the table holds the old pointers)
   }
-  const bool graphable = e.use_graph && !e.prof_on;
-  if (graphable) {
-    for (int v = 0; v < e.n_variants(); ++v) {
-      if (e.graph_exec[v]) continue;
-      ORL_HIP(hipStreamBeginCapture(e.stream, hipStreamCaptureModeRelaxed));
-      int rc = (e.prep.empty() ? (e.enqueue_sample() || e.enqueue_noise()) : e.enqueue_prepare(true, true)) || e.enqueue_step(v);
-      hipError_t ce = hipStreamEndCapture(e.stream, &e.graph[v]);
-      if (rc) return -1;
-      if (ce != hipSuccess) return fail(std::string("graph capture: ") + hipGetErrorString(ce));
-      ORL_HIP(hipGraphInstantiate(&e.graph_exec[v], e.graph[v], nullptr, nullptr, 0));
-    }
-  }
-  // (the two timing events are released on every exit path, early error returns included)
-  struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-  } ev;
-  ORL_HIP(hipEventCreate(&ev.a));
-  ORL_HIP(hipEventCreate(&ev.b));
-  const hipEvent_t t0 = ev.a, t1 = ev.b;
-  if (e.prof_on) { e.prof.clear(); e.ev_used = 0; }
-  ORL_HIP(hipEventRecord(t0, e.stream));
-  for (int s = 0; s < n_steps; ++s) {
-    const int v = e.step_variant();
-    if (graphable) { ORL_HIP(hipGraphLaunch(e.graph_exec[v], e.stream)); }
-    else {
-      if (e.prep.empty()) { if (e.enqueue_sample()) return -1; if (e.enqueue_noise()) return -1; }
-      else if (e.enqueue_prepare(true, true)) return -1;
-      if (e.enqueue_step(v)) return -1;
-    }
-    e.step_host++;
-  }
-  ORL_HIP(hipEventRecord(t1, e.stream));
-  ORL_HIP(hipStreamSynchronize(e.stream));
-  float ms = 0.f;
-  ORL_HIP(hipEventElapsedTime(&ms, t0, t1));
-  if (elapsed_ms) *elapsed_ms = ms;
-  std::vector<float> m(e.R * e.nm);
-  ORL_HIP(hipMemcpy(m.data(), e.metrics_sum, sizeof(float) * m.size(), hipMemcpyDeviceToHost));      // (a non-finite metric of ANY of the n steps stays in its sum)
-  if (metrics_mean) {
-    for (int r = 0; r < e.R; ++r)
-      for (int k = 0; k < ORL_MAX_METRICS; ++k) metrics_mean[r * ORL_MAX_METRICS + k] = k < e.nm ? m[r * e.nm + k] / n_steps : 0.f;
-  }
-  unsigned int bad = 0;
-  if (e.health_update(m.data(), n_steps, &bad)) return -1;
-  return bad ? ORL_RC_UNHEALTHY : 0;
+  return e.run_steps(0, n_steps, true, metrics_mean, elapsed_ms);
 }
 
 int orl_learn_epoch(orl_engine* h, const int64_t* order, int64_t order_len, int on_device, float* metrics_mean, float* elapsed_ms) {
@@ -2192,42 +2187,7 @@ int orl_learn_epoch(orl_engine* h, const int64_t* order, int64_t order_len, int 
     e.drop_graphs();
     e.buf_gen = e.buf->gen; e.buf_n = e.buf->n;
   }
-  const bool graphable = e.use_graph && !e.prof_on;
-  if (graphable && !e.graph_exec[1]) {
-    ORL_HIP(hipStreamBeginCapture(e.stream, hipStreamCaptureModeRelaxed));
-    const int rc = e.enqueue_step(0);
-    const hipError_t ce = hipStreamEndCapture(e.stream, &e.graph[1]);
-    if (rc) return -1;
-    if (ce != hipSuccess) return fail(std::string("graph capture: ") + hipGetErrorString(ce));
-    ORL_HIP(hipGraphInstantiate(&e.graph_exec[1], e.graph[1], nullptr, nullptr, 0));
-  }
-  struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-  } ev;
-  ORL_HIP(hipEventCreate(&ev.a));
-  ORL_HIP(hipEventCreate(&ev.b));
-  if (e.prof_on) { e.prof.clear(); e.ev_used = 0; }
-  ORL_HIP(hipEventRecord(ev.a, e.stream));
-  for (long s = 0; s < n_steps; ++s) {
-    if (graphable) { ORL_HIP(hipGraphLaunch(e.graph_exec[1], e.stream)); }
-    else if (e.enqueue_step(0)) return -1;
-    e.step_host++;
-  }
-  ORL_HIP(hipEventRecord(ev.b, e.stream));
-  ORL_HIP(hipStreamSynchronize(e.stream));
-  float ms = 0.f;
-  ORL_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-  if (elapsed_ms) *elapsed_ms = ms;
-  std::vector<float> m(e.R * e.nm);
-  ORL_HIP(hipMemcpy(m.data(), e.metrics_sum, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
-  if (metrics_mean) {
-    for (int r = 0; r < e.R; ++r)
-      for (int k = 0; k < ORL_MAX_METRICS; ++k) metrics_mean[r * ORL_MAX_METRICS + k] = k < e.nm ? m[r * e.nm + k] / (float)n_steps : 0.f;
-  }
-  unsigned int bad = 0;
-  if (e.health_update(m.data(), n_steps, &bad)) return -1;
-  return bad ? ORL_RC_UNHEALTHY : 0;
+  return e.run_steps(1, n_steps, false, metrics_mean, elapsed_ms);      // (graph_exec[1]: the ordered step)
 }
 
 int orl_autoreg_sample(orl_engine* h, const float* obs, int64_t n, const float* eps, int on_device, float* act_out) {

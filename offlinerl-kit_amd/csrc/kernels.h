@@ -579,7 +579,7 @@ __device__ inline float block_sum256(float v, float* sh) {
 // grid (R), block 256, loops over B.  K critics (2 for CQL).
 // ------------------------------------------------------------------------------------------------
 struct ActorLossP {
-  const float* qa; long qa_rs, qa_cs;      // [R][K][B]
+  ZPtr qa;                                 // [R][K][B]
   float* dqa;                              // same layout
   const float* logp; long logp_rs;         // [R][B]
   int B, K;
@@ -598,13 +598,13 @@ __global__ void k_actor_loss(ActorLossP p) {
   float s_loss = 0.f, s_lp = 0.f;
   const float gq = -1.0f / (float)p.B;
   for (int b = threadIdx.x; b < p.B; b += 256) {
-    const float* q = p.qa + (long)r * p.qa_rs + b;
+    const float* q = p.qa.p + (long)r * p.qa.s0 + b;
     float qmin = q[0];
-    for (int c = 1; c < p.K; ++c) qmin = fminf(qmin, q[(long)c * p.qa_cs]);
+    for (int c = 1; c < p.K; ++c) qmin = fminf(qmin, q[(long)c * p.qa.s1]);
     int nmin = 0;
-    for (int c = 0; c < p.K; ++c) nmin += (q[(long)c * p.qa_cs] == qmin);
-    float* dq = p.dqa + (long)r * p.qa_rs + b;
-    for (int c = 0; c < p.K; ++c) dq[(long)c * p.qa_cs] = (q[(long)c * p.qa_cs] == qmin) ? gq / (float)nmin : 0.f;
+    for (int c = 0; c < p.K; ++c) nmin += (q[(long)c * p.qa.s1] == qmin);
+    float* dq = p.dqa + (long)r * p.qa.s0 + b;
+    for (int c = 0; c < p.K; ++c) dq[(long)c * p.qa.s1] = (q[(long)c * p.qa.s1] == qmin) ? gq / (float)nmin : 0.f;
     const float lp = p.logp[(long)r * p.logp_rs + b];
     s_loss += alpha * lp - qmin;
     s_lp += lp;
@@ -637,8 +637,8 @@ __global__ void k_actor_loss(ActorLossP p) {
 // grid (ceil(B/256), R)
 // ------------------------------------------------------------------------------------------------
 struct HeadBwdP {
-  const float* dxa; long dxa_rs, dxa_cs; int dxa_pitch; int K;  // [R][K][B][pitch] action-column grads
-  const float* dqa; long dqa_rs, dqa_cs;                           // non-null: dxa holds UNIT-seed gradients dq_c / da (the one-launch forward +
+  ZPtr dxa; int dxa_pitch; int K;                               // [R][K][B][pitch] action-column grads
+  ZPtr dqa;                                                        // non-null: dxa holds UNIT-seed gradients dq_c / da (the one-launch forward +
                                                                    // backward, small_fwd.h QG mode); da = sum_c dqa[c][b] dxa[c][b]
   const float* head; long head_rs;                                // [R][B][2A]
   const float* eps; long eps_rs;                                  // [R][B][A]
@@ -664,7 +664,7 @@ __global__ void k_head_bwd(HeadBwdP p) {
   for (int a = 0; a < A; ++a) {
     float da = 0.f;
     for (int c = 0; c < p.K; ++c)
-      da += (p.dqa ? p.dqa[(long)r * p.dqa_rs + (long)c * p.dqa_cs + b] : 1.0f) * p.dxa[(long)r * p.dxa_rs + (long)c * p.dxa_cs + (long)b * p.dxa_pitch + a];
+      da += (p.dqa.p ? p.dqa.p[(long)r * p.dqa.s0 + (long)c * p.dqa.s1 + b] : 1.0f) * p.dxa.p[(long)r * p.dxa.s0 + (long)c * p.dxa.s1 + (long)b * p.dxa_pitch + a];
     const float lsr = h[A + a];
     const float sg = expf(fminf(fmaxf(lsr, -5.0f), 2.0f));
     const float act = x[a];
@@ -689,9 +689,9 @@ __global__ void k_head_bwd(HeadBwdP p) {
 //   rows of q[c]: [0,B) data, [B,B+BN) pi, [B+BN,B+2BN) next-pi, [B+2BN,B+3BN) random
 // ------------------------------------------------------------------------------------------------
 struct CqlLossP {
-  const float* q; long q_rs, q_cs;         // [R][2][Mc]
+  ZPtr q;                                  // [R][2][Mc]
   float* dq;                               // [R][2][Mc]
-  const float* qt; long qt_rs, qt_cs;      // target critics [R][2][Bt]  (Bt = B or B*N with max_q_backup)
+  ZPtr qt;                                 // target critics [R][2][Bt]  (Bt = B or B*N with max_q_backup)
   const float* rew; const float* term; long bt_rs;  // [R][B]
   const float* logp_next; long lpn_rs;     // [R][B]   (stochastic backup)
   const float* logp_pi; const float* logp_npi; long lpp_rs;   // [R][BN]
@@ -718,12 +718,12 @@ __global__ void k_cql_loss_rows(CqlLossP p) {
   float cs = 1.0f;
   if (p.with_lagrange) cs = fminf(fmaxf(expf(sc.cql_log_alpha), 0.f), 1e6f);
   const float log_rand = logf(powf(0.5f, (float)p.A));
-  const float* q = p.q + (long)r * p.q_rs + (long)c * p.q_cs;
-  float* dq = p.dq + (long)r * p.q_rs + (long)c * p.q_cs;
+  const float* q = p.q.p + (long)r * p.q.s0 + (long)c * p.q.s1;
+  float* dq = p.dq + (long)r * p.q.s0 + (long)c * p.q.s1;
   float s_td = 0.f, s_q = 0.f, s_lse = 0.f, amax = 0.f;
   if (blk == 0) {
-    const float* t0 = p.qt + (long)r * p.qt_rs;
-    const float* t1 = t0 + p.qt_cs;
+    const float* t0 = p.qt.p + (long)r * p.qt.s0;
+    const float* t1 = t0 + p.qt.s1;
     for (int b = threadIdx.x; b < B; b += 256) {
       float nq;
       if (p.max_q_backup) {
@@ -990,7 +990,7 @@ __device__ inline void metric_set(const MetricsP& m, int r, int slot, float v) {
 
 // value loss: diff = min(q1_old,q2_old) - v ; w = diff>0 ? tau_e : 1-tau_e ; L = mean(w diff^2) ; dv = -2 w diff / B
 struct IqlVP {
-  const float* qo; long qo_rs, qo_cs;   // [R][2][B] target critics at (s,a)
+  ZPtr qo;                              // [R][2][B] target critics at (s,a)
   const float* v; long v_rs;            // [R][B]
   float* dv;                            // [R][B]
   float* qmin; long qmin_rs;            // [R][B] keeps min(q_old) for the actor weights
@@ -1002,8 +1002,8 @@ __global__ void k_iql_v_loss(IqlVP p) {
   const int r = blockIdx.x;
   float s = 0.f, amax = 0.f;
   for (int b = threadIdx.x; b < p.B; b += 256) {
-    const float* q = p.qo + (long)r * p.qo_rs + b;
-    const float qm = fminf(q[0], q[p.qo_cs]);
+    const float* q = p.qo.p + (long)r * p.qo.s0 + b;
+    const float qm = fminf(q[0], q[p.qo.s1]);
     const float d = qm - p.v[(long)r * p.v_rs + b];
     const float w = d > 0.f ? p.expectile : 1.0f - p.expectile;
     s += w * d * d;
@@ -1020,7 +1020,7 @@ __global__ void k_iql_v_loss(IqlVP p) {
 // Q losses + advantage weights: y = r + gamma (1-d) V_new(s') ; dq_i = 2 (q_i - y)/B ;
 // exp_a = min(exp((min q_old - V_new(s)) * beta), 100)
 struct IqlQP {
-  const float* q; long q_rs, q_cs;      // [R][2][B]
+  ZPtr q;                               // [R][2][B]
   float* dq;
   const float* v2; long v2_rs;          // [R][2B]: rows [0,B) V_new(s), [B,2B) V_new(s')
   const float* qmin; long qmin_rs;
@@ -1038,11 +1038,11 @@ __global__ void k_iql_q_loss(IqlQP p) {
     const float* v2 = p.v2 + (long)r * p.v2_rs;
     const float y = p.rew[(long)r * p.bt_rs + b] + p.gamma * (1.0f - p.term[(long)r * p.bt_rs + b]) * v2[p.B + b];
     p.target_q[(long)r * p.tq_rs + b] = y;
-    const float* q = p.q + (long)r * p.q_rs + b;
-    float* dq = p.dq + (long)r * p.q_rs + b;
-    const float d1 = q[0] - y, d2 = q[p.q_cs] - y;
+    const float* q = p.q.p + (long)r * p.q.s0 + b;
+    float* dq = p.dq + (long)r * p.q.s0 + b;
+    const float d1 = q[0] - y, d2 = q[p.q.s1] - y;
     s1 += d1 * d1; s2 += d2 * d2;
-    dq[0] = 2.0f * d1 / (float)p.B; dq[p.q_cs] = 2.0f * d2 / (float)p.B;
+    dq[0] = 2.0f * d1 / (float)p.B; dq[p.q.s1] = 2.0f * d2 / (float)p.B;
     amax = fmaxf(amax, 2.0f * fmaxf(fabsf(d1), fabsf(d2)) / (float)p.B);
     p.exp_a[(long)r * p.ea_rs + b] = fminf(expf((p.qmin[(long)r * p.qmin_rs + b] - v2[b]) * p.beta), 100.0f);
   }
@@ -1135,8 +1135,8 @@ __global__ void k_det_action(DetActP p) {
 
 // twin-critic TD loss (also IQL-free algorithms): y = r + gamma (1-d) (min_c qt_c - alpha*logp_next) ; dq_c = 2 (q_c - y)/B
 struct TdLossP {
-  const float* q; long q_rs, q_cs; float* dq;    // [R][K][B]
-  const float* qt; long qt_rs, qt_cs; int Kt;    // target critics [R][Kt][Bt]
+  ZPtr q; float* dq;                             // [R][K][B]
+  ZPtr qt; int Kt;                               // target critics [R][Kt][Bt]
   const float* rew; const float* term; long bt_rs;
   const float* logp_next; long lpn_rs;           // or null
   float* target_q; long tq_rs;
@@ -1155,7 +1155,7 @@ __global__ void k_td_loss(TdLossP p) {
   for (int b = threadIdx.x; b < B; b += 256) {
     float nq = INFINITY;
     for (int c = 0; c < p.Kt; ++c) {
-      const float* t = p.qt + (long)r * p.qt_rs + (long)c * p.qt_cs;
+      const float* t = p.qt.p + (long)r * p.qt.s0 + (long)c * p.qt.s1;
       float v = -INFINITY;
       for (int n = 0; n < p.rep; ++n) v = fmaxf(v, t[b * p.rep + n]);
       nq = fminf(nq, v);
@@ -1166,8 +1166,8 @@ __global__ void k_td_loss(TdLossP p) {
   __syncthreads();
   float total = 0.f, amax = 0.f;
   for (int c = 0; c < p.K; ++c) {
-    const float* q = p.q + (long)r * p.q_rs + (long)c * p.q_cs;
-    float* dq = p.dq + (long)r * p.q_rs + (long)c * p.q_cs;
+    const float* q = p.q.p + (long)r * p.q.s0 + (long)c * p.q.s1;
+    float* dq = p.dq + (long)r * p.q.s0 + (long)c * p.q.s1;
     float s = 0.f;
     for (int b = threadIdx.x; b < B; b += 256) {
       const float d = q[b] - tq[b];
@@ -1325,9 +1325,9 @@ __global__ void k_clamp_latent(const float* z, long z_rs, float* xd, long xd_rs,
 //   y_in = r + gamma (1 - d) (min_c qt_c - alpha logp') ; y_ood[j] = min_c max_n qto_c[j N + n]
 //   L_c = lambda mse(q_c[:B] - y_in) + (1 - lambda) mse(q_c[B:] - y_ood) ; dq accordingly.  grid (R), block 256
 struct McqLossP {
-  const float* q; long q_rs, q_cs; float* dq;        // [R][2][3B]
-  const float* qt; long qt_rs, qt_cs;                // target critics on (s', a') [R][2][B]
-  const float* qto; long qto_rs, qto_cs;             // target critics on the 2B*N sampled pairs [R][2][2BN]
+  ZPtr q; float* dq;                                 // [R][2][3B]
+  ZPtr qt;                                           // target critics on (s', a') [R][2][B]
+  ZPtr qto;                                          // target critics on the 2B*N sampled pairs [R][2][2BN]
   const float* rew; const float* term; long bt_rs; const float* logp_next; long lpn_rs;
   float* target_q; long tq_rs; float* target_ood; long to_rs;     // [R][B], [R][2B]
   int B, N; float gamma, lambda;
@@ -1339,21 +1339,21 @@ __global__ void k_mcq_loss(McqLossP p) {
   const float alpha = p.auto_alpha ? p.sc[r].alpha : p.fixed_alpha;
   float* yi = p.target_q + (long)r * p.tq_rs;
   float* yo = p.target_ood + (long)r * p.to_rs;
-  const float* t0 = p.qt + (long)r * p.qt_rs;
-  const float* o0 = p.qto + (long)r * p.qto_rs;
+  const float* t0 = p.qt.p + (long)r * p.qt.s0;
+  const float* o0 = p.qto.p + (long)r * p.qto.s0;
   for (int b = threadIdx.x; b < B; b += 256) {
-    const float nq = fminf(t0[b], t0[p.qt_cs + b]) - alpha * p.logp_next[(long)r * p.lpn_rs + b];
+    const float nq = fminf(t0[b], t0[p.qt.s1 + b]) - alpha * p.logp_next[(long)r * p.lpn_rs + b];
     yi[b] = p.rew[(long)r * p.bt_rs + b] + p.gamma * (1.0f - p.term[(long)r * p.bt_rs + b]) * nq;
   }
   for (int j = threadIdx.x; j < 2 * B; j += 256) {
     float m0 = -INFINITY, m1 = -INFINITY;
-    for (int n = 0; n < p.N; ++n) { m0 = fmaxf(m0, o0[(long)j * p.N + n]); m1 = fmaxf(m1, o0[p.qto_cs + (long)j * p.N + n]); }
+    for (int n = 0; n < p.N; ++n) { m0 = fmaxf(m0, o0[(long)j * p.N + n]); m1 = fmaxf(m1, o0[p.qto.s1 + (long)j * p.N + n]); }
     yo[j] = fminf(m0, m1);
   }
   __syncthreads();
   for (int c = 0; c < 2; ++c) {
-    const float* q = p.q + (long)r * p.q_rs + (long)c * p.q_cs;
-    float* dq = p.dq + (long)r * p.q_rs + (long)c * p.q_cs;
+    const float* q = p.q.p + (long)r * p.q.s0 + (long)c * p.q.s1;
+    float* dq = p.dq + (long)r * p.q.s0 + (long)c * p.q.s1;
     float s_in = 0.f, s_ood = 0.f;
     for (int b = threadIdx.x; b < B; b += 256) {
       const float d = q[b] - yi[b];
@@ -1521,7 +1521,7 @@ __global__ void k_mobile_assemble(MobileInP p) {
 // ORL_HEALTH_NONFINITE_LOSS.  grid (ceil(B / 256), R)
 enum { LCB_MAX_E = 64 };
 struct LcbP {
-  const float* ql; long ql_rs, ql_cs;       // target critics on the samples [R][2][M]
+  ZPtr ql;                                  // target critics on the samples [R][2][M]
   float* qmin; long qm_rs;                  // [R][M]
   float* pen; long pen_rs;                  // [R][B]
   int B, S, E, real_rows;
@@ -1531,8 +1531,8 @@ __global__ __launch_bounds__(256) void k_lcb_penalty(LcbP p) {
   const int r = blockIdx.y;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= p.B) return;
-  const float* q1 = p.ql + (long)r * p.ql_rs;
-  const float* q2 = q1 + p.ql_cs;
+  const float* q1 = p.ql.p + (long)r * p.ql.s0;
+  const float* q2 = q1 + p.ql.s1;
   float* qm = p.qmin + (long)r * p.qm_rs;
   double m[LCB_MAX_E];
   double tot = 0.0;
@@ -1558,8 +1558,8 @@ __global__ __launch_bounds__(256) void k_lcb_penalty(LcbP p) {
 // MOBILE's TD target and critic loss (mobile.py:151-164): y = max((r - c pen) + gamma (1 - d) (min qt - alpha logp'), 0) -- a NaN stays
 // NaN like torch.clamp's --, ONE loss = mean over (2, B) of (q_c - y)^2, so dq_c = 2 (q_c - y) / (2 B).  grid (R), block 256
 struct MobileTdP {
-  const float* q; long q_rs, q_cs; float* dq;    // [R][2][B]
-  const float* qt; long qt_rs, qt_cs;            // target critics at (s', a') [R][2][B]
+  ZPtr q; float* dq;                             // [R][2][B]
+  ZPtr qt;                                       // target critics at (s', a') [R][2][B]
   const float* rew; const float* term; long bt_rs;
   const float* logp_next; long lpn_rs;
   const float* pen; long pen_rs;                 // [R][B]
@@ -1575,9 +1575,9 @@ __global__ void k_mobile_td_loss(MobileTdP p) {
   const int B = p.B;
   const float alpha = p.auto_alpha ? p.sc[r].alpha : p.fixed_alpha;
   float* tq = p.target_q + (long)r * p.tq_rs;
-  const float* qt = p.qt + (long)r * p.qt_rs;
+  const float* qt = p.qt.p + (long)r * p.qt.s0;
   for (int b = threadIdx.x; b < B; b += 256) {
-    float nq = fminf(qt[b], qt[p.qt_cs + b]);
+    float nq = fminf(qt[b], qt[p.qt.s1 + b]);
     if (p.use_alpha) nq = __fsub_rn(nq, __fmul_rn(alpha, p.logp_next[(long)r * p.lpn_rs + b]));
     const float rp = __fsub_rn(p.rew[(long)r * p.bt_rs + b], __fmul_rn(p.pen_coef, p.pen[(long)r * p.pen_rs + b]));
     const float g = __fmul_rn(p.gamma, __fsub_rn(1.0f, p.term[(long)r * p.bt_rs + b]));
@@ -1588,8 +1588,8 @@ __global__ void k_mobile_td_loss(MobileTdP p) {
   float total = 0.f, amax = 0.f;
   const float inv = 1.0f / (float)(2 * B);
   for (int c = 0; c < 2; ++c) {
-    const float* q = p.q + (long)r * p.q_rs + (long)c * p.q_cs;
-    float* dq = p.dq + (long)r * p.q_rs + (long)c * p.q_cs;
+    const float* q = p.q.p + (long)r * p.q.s0 + (long)c * p.q.s1;
+    float* dq = p.dq + (long)r * p.q.s0 + (long)c * p.q.s1;
     float s = 0.f;
     for (int b = threadIdx.x; b < B; b += 256) {
       const float d = q[b] - tq[b];
