@@ -417,6 +417,52 @@ typedef struct orl_gemm_ex {
   int32_t r_mb, r_tq_parts, r_w0_slabs, r_aux_bits, r_a_bits;   /* requested side output honoured (0 = not) */
 } orl_gemm_ex;
 int orl_debug_gemm_ex(orl_gemm_ex* args);
+/* The unit-test tap of the weight-stationary kernels (csrc/ws_gemm.h): ONE launch of one launch_ws_* function on host arrays.  Arrays
+ * are described as in orl_debug_gemm_ex, copied to the device WHOLE and ALL copied back WHOLE (operands too), so guard words come back
+ * untouched wherever the kernel did not write and an operand that comes back changed was written by the kernel.  An array named like a field of WsFwdP / WsDgradP / WsWgradP IS that field ("given or
+ * not" picks the flavour); its `pitch` is the field's pitch (x_pitch, y_pitch, mb_g, x0_pitch, ab_g, c_pitch, h0_pitch, ...; 32-bit
+ * words for the mask arrays), s0 / s1 the run / member strides, and, for the slab results (w0_out, b0_out, dW, db, dwt, dbt), s0 / s1
+ * / ks = o_rs / the member stride / o_ks.  b0_out shares w0_out's s0 and ks; db, dwt and dbt share dW's.  Before the first HIP call the
+ * tap checks every extent against the array sizes, refuses what the matching *_supported predicate refuses, per_z < 1, per_z > M / 32,
+ * M > 4096 and nz0 * nz1 > 64, and fills the report. */
+enum { ORL_WS_FWD = 0, ORL_WS_FWD3 = 1, ORL_WS_DGRAD = 2, ORL_WS_DGRAD3 = 3, ORL_WS_WGRAD = 4, ORL_WS_WGRAD3P = 5 };
+typedef struct orl_ws_ex {
+  int32_t kind;          /* ORL_WS_*: launch_ws_fwd, launch_ws_fwd3, launch_ws_dgrad_w0, launch_ws_dgrad3_w0, launch_ws_wgrad, launch_ws_wgrad3p */
+  int32_t f32;           /* exact fp32 arithmetic (fwd, dgrad, wgrad) */
+  int32_t np3;           /* wgrad: three planes of G (ws_wgrad_kernel<5>) */
+  int32_t M, nz0, nz1;
+  int32_t per_z;         /* workgroups (= split-K slabs) per problem; launch_ws_fwd gets it through WsGeom{cus = per_z * nz, one_round} */
+  int32_t in0;           /* input columns of the first layer (fused first layer, layer-0 gradient, recompute) */
+  int32_t x0_discard;    /* fwd / fwd3 with X0: h0 is not stored */
+  int32_t w_sn, w_sk;    /* fwd / dgrad: strides of W (nn.Linear: fwd 256, 1, dgrad 1, 256; EnsembleLinear the other way round) */
+  int32_t w0_sn, w0_sk;  /* strides of W0 */
+  int32_t o_sr, o_sc;    /* dgrad: strides of a w0_out element (unit n, input c) inside a slab */
+  int32_t tq_sm, dq_sm;  /* element strides between the rows of tq / dq */
+  int32_t dry_run;       /* check the arguments and fill the report only: no device call */
+  /* operands */
+  orl_gemm_buf X;             /* fwd: input rows [M][pitch >= 256] (with X0: the RESULT h0, copied back); dgrad: layer-0 input rows [M][pitch <= 32] */
+  orl_gemm_buf W, bias;       /* fwd: the layer; dgrad: W1 (no bias) */
+  orl_gemm_buf tw, tb;        /* fwd: fused tail weights [256], bias [1] */
+  orl_gemm_buf X0, W0, b0;    /* fwd: fused first layer; wgrad: h0 recomputed (X0 rows [M][pitch <= 32]) */
+  orl_gemm_buf dmask;         /* fwd: plain dgrad mode, mask words of the receiving activation */
+  orl_gemm_buf abits, xbits;  /* dgrad / wgrad: mask words of the top (abits) and the layer-0 (xbits) activation */
+  orl_gemm_buf dq, wt;        /* dgrad / wgrad: dLoss/dq per row, w_tail [256] */
+  orl_gemm_buf Z;             /* dgrad: materialised incoming gradient (PLAIN) */
+  orl_gemm_buf H0, H1, W1, b1, dZ;   /* wgrad */
+  orl_gemm_buf gscale;        /* one float per run (z0), flat from `off` */
+  /* results */
+  orl_gemm_buf Y, mb, mb0, tq, tq2;       /* fwd */
+  orl_gemm_buf C, w0_out, b0_out;         /* dgrad: dz0 (STORE) or the dW0 / db0 slabs (W0) */
+  orl_gemm_buf dW, db, dwt, dbt;          /* wgrad slabs */
+  /* report (filled before the device is touched) */
+  int32_t r_launcher;         /* = kind */
+  int32_t r_flavour;          /* index into the tap's table of instantiations (orl_debug_ws_flavour) */
+  int32_t r_lds;              /* dynamic LDS bytes of the launch */
+  int32_t r_groups;           /* M / 32 */
+} orl_ws_ex;
+int orl_debug_ws(orl_ws_ex* args);
+/* name of instantiation `idx` of the tap's table ("ws_fwd<TQ,L0,DG,SY,F32,XS>", "ws_wgrad32<MODE>", ...); NULL past its end */
+const char* orl_debug_ws_flavour(int idx);
 /* times `reps` launches of one GEMM tile configuration on random data (kind 0 forward, 1 dgrad, 2 wgrad) */
 int orl_debug_gemm_time(int cfg, int kind, int M, int N, int K, int nz, int ksplit, int reps, float* ms_out);
 /* average duration (ms) of the kernel with the largest accumulated time during the last orl_learn_n

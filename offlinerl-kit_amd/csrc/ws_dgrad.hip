@@ -256,10 +256,7 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad_w0_kernel(const WsDgradP p) {
 // mask of h1 expanded from its bits into an fp32 LDS image (16-byte chunks XOR-swizzled with the row, as in ws_fwd's fp32 image;
 // a lane's ds_read_b128 = four MFMA k steps), and dW0^T += X^T dz0 on the same instruction with the accumulators as B operand
 // (k step r = the lane's row 4 lq + r) and X^T rows read as float4 from an fp32 image.
-enum { WD32_XP = WS_ROWS + 4 };                                      // float pitch of an X^T row
-static constexpr size_t ws_dgrad32_lds_bytes() {
-  return sizeof(float) * ((size_t)2 * WS_ROWS * WS_K + (size_t)2 * 32 * WD32_XP + (size_t)2 * (WS_ROWS + WS_NW * WS_ROWS));
-}
+// (WD32_XP = the float pitch of an X^T row, and ws_dgrad32_lds_bytes(): ws_gemm.h)
 
 template <bool W0, bool STORE, bool PLAIN = false>                   // PLAIN: A image = the materialised dz1 rows (WsDgradP::Z), B' = W1
 __global__ __launch_bounds__(WS_NT) void ws_dgrad32_w0_kernel(const WsDgradP p) {

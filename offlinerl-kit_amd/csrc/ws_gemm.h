@@ -182,6 +182,12 @@ static constexpr size_t ws_dgrad_lds_bytes(bool plain = false) {     // mask ima
   return (size_t)(plain ? 4 : 2) * WS_ROWS * WS_PITCH * 2 + (size_t)2 * 2 * 32 * WD_XP * 2 + (size_t)2 * (WS_ROWS + WS_NW * WS_ROWS) * 4;
 }
 
+// exact-fp32 flavour (ws_dgrad32_w0_kernel): fp32 mask image + X^T images + epilogue operands
+enum { WD32_XP = WS_ROWS + 4 };                                      // float pitch of an X^T row
+static constexpr size_t ws_dgrad32_lds_bytes() {
+  return sizeof(float) * ((size_t)2 * WS_ROWS * WS_K + (size_t)2 * 32 * WD32_XP + (size_t)2 * (WS_ROWS + WS_NW * WS_ROWS));
+}
+
 static inline bool ws_dgrad_supported(const WsDgradP& p, int K, int N) {
   if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS)) return false;
   if (p.Z.p) {
@@ -265,11 +271,18 @@ static constexpr size_t ws_wgrad_lds_bytes(bool plain = false, bool recompute = 
   return (size_t)2 * ((plain || p3) ? 4 : 3) * WW_IMG * 2 + (size_t)2 * (p3 ? 3 : 2) * WS_ROWS * 16 * 2 + (recompute ? sizeof(float) * 2 * WS_ROWS * WS_XLP : 0);
 }
 
+// exact-fp32 flavour (ws_wgrad32_kernel): row-major fp32 images [32 rows][WW32_P]
+enum { WW32_P = 272, WW32_IMG = WS_ROWS * WW32_P };
+static constexpr size_t ws_wgrad32_lds_bytes(bool recompute = false) {
+  return sizeof(float) * ((size_t)2 * 2 * WW32_IMG + 2 * WS_ROWS + (recompute ? 2 * WS_ROWS * WS_XLP : 0)) > sizeof(float) * 17 * WS_K
+             ? sizeof(float) * ((size_t)2 * 2 * WW32_IMG + 2 * WS_ROWS + (recompute ? 2 * WS_ROWS * WS_XLP : 0)) : sizeof(float) * 17 * WS_K;
+}
+
 static inline bool ws_wgrad_supported(const WsWgradP& p, int K, int N) {
   if (p.dZ.p) {
     if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS)) return false;
     if (!p.dZ.vec4() || (p.dz_pitch & 3)) return false;
-    if (p.X0.p) return p.W0.p && p.b0.p && p.in0 + 1 <= 32 && p.in0 < p.x0_pitch + 1 && p.x0_pitch <= 32 && p.in0 <= p.x0_pitch && WS_ROWS * p.x0_pitch <= 2 * WS_NT;
+    if (p.X0.p) return p.W0.p && p.b0.p && p.in0 + 1 <= 32 && p.in0 < p.x0_pitch && p.x0_pitch <= 32 && WS_ROWS * p.x0_pitch <= 2 * WS_NT;   // (in0 < x0_pitch: the ones column must exist in the staged row, as in ws_fwd01_supported)
     return p.H0.vec4() && !(p.h0_pitch & 3);
   }
   if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS) || !p.abits.p || p.ab_g != 8) return false;

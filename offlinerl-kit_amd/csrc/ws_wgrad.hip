@@ -498,11 +498,7 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad_kernel(const WsWgradP p) {
 // images [32 rows][WW32_P]: a lane group lq reads 16 consecutive floats of row 4 step + lq, and the row pitch of 272 floats (16 mod 64
 // banks) puts the four rows of one read on disjoint banks.  32 rows = 8 MFMA k steps; two 16-row k blocks of the output are in flight
 // so that dependent MFMAs stay four instructions apart.
-enum { WW32_P = 272, WW32_IMG = WS_ROWS * WW32_P };
-static constexpr size_t ws_wgrad32_lds_bytes(bool recompute = false) {
-  return sizeof(float) * ((size_t)2 * 2 * WW32_IMG + 2 * WS_ROWS + (recompute ? 2 * WS_ROWS * WS_XLP : 0)) > sizeof(float) * 17 * WS_K
-             ? sizeof(float) * ((size_t)2 * 2 * WW32_IMG + 2 * WS_ROWS + (recompute ? 2 * WS_ROWS * WS_XLP : 0)) : sizeof(float) * 17 * WS_K;
-}
+// (WW32_P, WW32_IMG and ws_wgrad32_lds_bytes(): ws_gemm.h)
 
 template <int MODE>
 __global__ __launch_bounds__(WS_NT) void ws_wgrad32_kernel(const WsWgradP p) {

@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "orl_buffer_reserve", "orl_buffer_append", "orl_buffer_append_rollout", "orl_buffer_read", "orl_engine_attach_model_buffer",
     "orl_buffer_append_rollout_runs", "orl_engine_attach_model_buffers",
     "orl_health", "orl_health_check", "orl_health_clear", "orl_num_metrics", "orl_metric_name", "orl_step_count",
-    "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_ex", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
+    "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_ex", "orl_debug_ws", "orl_debug_ws_flavour", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
     # dynamics ensemble (orl_dynamics)
     "orl_dyn_config_default", "orl_dyn_create", "orl_dyn_destroy", "orl_dyn_sync", "orl_dyn_floats", "orl_dyn_config_floats",
     "orl_dyn_num_tensors", "orl_dyn_tensor", "orl_dyn_ptr", "orl_dyn_set", "orl_dyn_get", "orl_dyn_adam_get", "orl_dyn_adam_set",
@@ -129,6 +129,19 @@ GEMM_EX_REPORT = ("r_cfg", "r_la_pick", "r_lb_pick", "r_la", "r_lb", "r_zmajor",
 
 class OrlGemmEx(C.Structure):
     _fields_ = [(k, C.c_int32) for k in GEMM_EX_INTS] + [(k, OrlGemmBuf) for k in GEMM_EX_BUFS] + [(k, C.c_int32) for k in GEMM_EX_REPORT]
+
+
+WS_KINDS = {"fwd": 0, "fwd3": 1, "dgrad": 2, "dgrad3": 3, "wgrad": 4, "wgrad3p": 5}
+WS_EX_INTS = ("kind", "f32", "np3", "M", "nz0", "nz1", "per_z", "in0", "x0_discard", "w_sn", "w_sk", "w0_sn", "w0_sk", "o_sr", "o_sc", "tq_sm", "dq_sm",
+              "dry_run")
+WS_EX_OPERANDS = ("X", "W", "bias", "tw", "tb", "X0", "W0", "b0", "dmask", "abits", "xbits", "dq", "wt", "Z", "H0", "H1", "W1", "b1", "dZ", "gscale")
+WS_EX_RESULTS = ("Y", "mb", "mb0", "tq", "tq2", "C", "w0_out", "b0_out", "dW", "db", "dwt", "dbt")
+WS_EX_BUFS = WS_EX_OPERANDS + WS_EX_RESULTS
+WS_EX_REPORT = ("r_launcher", "r_flavour", "r_lds", "r_groups")
+
+
+class OrlWsEx(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in WS_EX_INTS] + [(k, OrlGemmBuf) for k in WS_EX_BUFS] + [(k, C.c_int32) for k in WS_EX_REPORT]
 
 
 _lib = None
@@ -218,6 +231,9 @@ def load_library(path: Optional[str] = None):
     lib.orl_debug_grads.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]
     lib.orl_debug_gemm.argtypes = [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_int, C.c_int]
     lib.orl_debug_gemm_ex.argtypes = [C.POINTER(OrlGemmEx)]
+    lib.orl_debug_ws.argtypes = [C.POINTER(OrlWsEx)]
+    lib.orl_debug_ws_flavour.argtypes = [C.c_int]
+    lib.orl_debug_ws_flavour.restype = C.c_char_p
     lib.orl_debug_gemm_time.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_float)]
     lib.orl_profile_enable.argtypes = [C.c_void_p, C.c_int]
     lib.orl_profile_query.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double),
@@ -840,6 +856,42 @@ def debug_gemm_ex(arrays: Dict[str, GemmArray], **ints) -> Dict[str, int]:
             setattr(a, k, v.desc())
     _check(lib.orl_debug_gemm_ex(C.byref(a)), "orl_debug_gemm_ex")
     return {k[2:]: int(getattr(a, k)) for k in GEMM_EX_REPORT}
+
+
+def ws_flavours() -> List[str]:
+    """the table of ws_* kernel instantiations inside the weight-stationary tap; a launch reports an index into it"""
+    lib = load_library()
+    out = []
+    while True:
+        s = lib.orl_debug_ws_flavour(len(out))
+        if s is None:
+            return out
+        out.append(s.decode())
+
+
+def debug_ws(kind: str, arrays: Dict[str, GemmArray], **ints) -> Dict[str, object]:
+    """The unit-test tap of the weight-stationary kernels (orl_debug_ws): one launch of launch_ws_<kind> (``kind`` in WS_KINDS).
+    ``arrays`` maps the names of include/orl_engine.h's orl_ws_ex -- the field names of WsFwdP / WsDgradP / WsWgradP -- to GemmArray
+    objects; which arrays are given picks the flavour.  Every array, operands included, is updated in place from the device copy, whole.
+    ``ints``: f32, np3, M, nz0, nz1, per_z, in0, x0_discard, w_sn, w_sk, w0_sn, w0_sk, o_sr, o_sc, tq_sm, dq_sm; dry_run = 1 stops after
+    the checks and the report, without a device.  Returns the report (launcher, flavour = the instantiation's name, flavour_id, lds,
+    groups).  Refused combinations raise before any device call."""
+    lib = load_library()
+    a = OrlWsEx()
+    a.kind = WS_KINDS[kind]
+    a.nz0 = a.nz1 = a.per_z = a.tq_sm = a.dq_sm = 1
+    for k, v in ints.items():
+        if k not in WS_EX_INTS or k == "kind":
+            raise TypeError(f"debug_ws: unknown field {k}")
+        setattr(a, k, int(v))
+    for k, v in arrays.items():
+        if k not in WS_EX_BUFS:
+            raise TypeError(f"debug_ws: unknown array {k}")
+        if v is not None:
+            setattr(a, k, v.desc())
+    _check(lib.orl_debug_ws(C.byref(a)), "orl_debug_ws")
+    name = lib.orl_debug_ws_flavour(a.r_flavour)
+    return {"launcher": int(a.r_launcher), "flavour": name.decode(), "flavour_id": int(a.r_flavour), "lds": int(a.r_lds), "groups": int(a.r_groups)}
 
 
 def default_dyn_config(**over) -> OrlDynConfig:
