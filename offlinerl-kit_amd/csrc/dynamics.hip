@@ -14,6 +14,12 @@
 //   k_dyn_loss         adds the decay loss and accumulates the minibatch loss of the active runs
 // Members and runs are batched through blockIdx.z = run * K + member of every GEMM; a 2-D input shared by the members (validate, step)
 // is a member stride of 0.  RAMBO's adversarial update of the same ensemble (orl_dynadv_*) is described where its kernels start.
+//
+// Every formula that more than one kernel needs exists ONCE, as a device function below: dyn_soft_clamp(_grad) and dyn_std (every
+// logvar and std of this file), dyn_nll_elem (the NLL element of k_dyn_nll and of k_dyn_adv_head's dataset rows), dyn_col_sum and
+// dyn_reduce_tail (the two reduce kernels), dyn_block_sum256, dyn_draw_elite, dyn_scale_row, and rng.h's Philox / box_muller_one.
+// A sampler that must agree with another bit for bit agrees because both call the same function.  On the host, DynWs is the one
+// workspace type (learn, adversarial update, and step as a forward-only view) and dyn_forward / dyn_backward are the only layer loops.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -23,6 +29,7 @@
 
 #include "../../include/orl_engine.h"
 #include "gemm.h"
+#include "rng.h"
 
 namespace orl {
 
@@ -30,24 +37,73 @@ int fail(const std::string& msg);      // engine.hip: sets orl_last_error(), ret
 
 static inline int rup4(int x) { return (x + 3) & ~3; }
 
-// ---- Philox4x32-10 (device noise / elite choice of step()) ----
-__device__ inline void dyn_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t (&out)[4]) {
-  uint32_t a = (uint32_t)seed, b = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ a, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ b, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    a += 0x9E3779B9u; b += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ inline float dyn_u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
 // torch.nn.functional.softplus (beta 1, threshold 20) and its derivative
 __device__ inline float dyn_softplus(float y) { return y > 20.f ? y : log1pf(expf(y)); }
 __device__ inline float dyn_dsoftplus(float y) { return y > 20.f ? 1.f : 1.f / (1.f + expf(-y)); }
+
+// soft_clamp of a raw logvar x (modules/dynamics_module.py): l1 = mx - softplus(mx - x), lv = mn + softplus(l1 - mn), with
+// s1 = d l1 / d x and s2 = d lv / d l1.  Every logvar of this file comes from here: the training heads, step() and both samplers.
+struct DynClamp { float lv, s1, s2; };
+__device__ __forceinline__ DynClamp dyn_soft_clamp_grad(float x, float mx, float mn) {
+  const float y1 = mx - x;
+  const float l1 = mx - dyn_softplus(y1);
+  const float y2 = l1 - mn;
+  return {mn + dyn_softplus(y2), dyn_dsoftplus(y1), dyn_dsoftplus(y2)};
+}
+__device__ __forceinline__ float dyn_soft_clamp(float x, float mx, float mn) { return dyn_soft_clamp_grad(x, mx, mn).lv; }
+// std = sqrt(exp(logvar)) as the reference writes it
+__device__ __forceinline__ float dyn_std(float x, float mx, float mn) { return sqrtf(expf(dyn_soft_clamp(x, mx, mn))); }
+
+// One element of the Gaussian NLL ((mean - target)^2 exp(-lv) + lv, times `scale` in the gradients): d / d mean, d / d raw logvar,
+// the loss term and the element's share of the max / min_logvar gradients.
+struct DynNll { float dmean, draw, lterm, gmax, gmin; };
+__device__ __forceinline__ DynNll dyn_nll_elem(float mean, float x, float target, float mx, float mn, float scale) {
+  const DynClamp c = dyn_soft_clamp_grad(x, mx, mn);
+  const float inv = expf(-c.lv);
+  const float diff = mean - target;
+  const float sq = diff * diff * inv;
+  const float dlv = (1.f - sq) * scale;
+  const float dl1 = dlv * c.s2;
+  return {2.f * diff * inv * scale, dl1 * c.s1, sq + c.lv, dl1 * (1.f - c.s1), dlv * (1.f - c.s2)};
+}
+// ... stored: dOUT [row][op] (mean: cols 0..D, raw logvar: D..2D), lterm / gmax / gmin [row][D]
+__device__ __forceinline__ void dyn_store_elem(const DynNll& g, long row, int d, int op, int D, float* dOUT, float* lterm, float* gmax,
+                                               float* gmin) {
+  dOUT[row * op + d] = g.dmean;
+  dOUT[row * op + D + d] = g.draw;
+  lterm[row * D + d] = g.lterm;
+  gmax[row * D + d] = g.gmax;
+  gmin[row * D + d] = g.gmin;
+}
+
+// sum over the 64 lanes of a wave, in every lane
+template <class T>
+__device__ __forceinline__ T dyn_wave_sum(T s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+// sum over a 256-thread block, for thread 0: the four wave sums as (s0 + s1) + (s2 + s3)
+__device__ __forceinline__ float dyn_block_sum256(float s) {
+  __shared__ float s_red[4];
+  s = dyn_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// the member of a row drawn from the run's elites with the first word of a Philox draw
+__device__ __forceinline__ int dyn_draw_elite(const int* elites, int r, int K, int n_elites, uint32_t rnd0) {
+  return elites[r * K + (int)(((uint64_t)rnd0 * (uint64_t)n_elites) >> 32)];
+}
+
+// x[0..xp) = (concat(o[0..od), a[0..ad)) - mu) / std with zero pads: StandardScaler.transform's fp32 operations
+__device__ __forceinline__ void dyn_scale_row(const float* o, int od, const float* a, int ad, const float* m, const float* s, float* x,
+                                              int xp) {
+  for (int c = 0; c < od; ++c) x[c] = (o[c] - m[c]) / s[c];
+  for (int c = 0; c < ad; ++c) x[od + c] = (a[c] - m[od + c]) / s[od + c];
+  for (int c = od + ad; c < xp; ++c) x[c] = 0.f;
+}
 
 // rows [row0, row0 + rows) of idx[r][k][*] -> X[r][k][i][0..xp) = (in - mu) / std (zero pads), T[r][k][i][0..D)
 __global__ void k_dyn_gather(const int* __restrict__ idx, long idx_s0, long idx_s1, long row0, int rows, const float* __restrict__ din,
@@ -57,12 +113,7 @@ __global__ void k_dyn_gather(const int* __restrict__ idx, long idx_s0, long idx_
   const int k = blockIdx.y, r = blockIdx.z;
   if (i >= rows) return;
   const long g = idx[r * idx_s0 + k * idx_s1 + row0 + i];
-  const float* src = din + g * in;
-  const float* m = mu + (long)r * in;
-  const float* s = sd + (long)r * in;
-  float* x = X + r * x_s0 + k * x_s1 + (long)i * xp;
-  for (int c = 0; c < in; ++c) x[c] = (src[c] - m[c]) / s[c];
-  for (int c = in; c < xp; ++c) x[c] = 0.f;
+  dyn_scale_row(din + g * in, in, nullptr, 0, mu + (long)r * in, sd + (long)r * in, X + r * x_s0 + k * x_s1 + (long)i * xp, xp);
   if (T) {
     const float* tg = dtg + g * D;
     float* t = T + r * t_s0 + k * t_s1 + (long)i * D;
@@ -76,15 +127,8 @@ __global__ void k_dyn_step_input(const float* __restrict__ obs, const float* __r
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int r = blockIdx.y;
   if (i >= n) return;
-  const int in = od + ad;
-  const float* o = obs + ((long)r * n + i) * od;
-  const float* a = act + ((long)r * n + i) * ad;
-  const float* m = mu + (long)r * in;
-  const float* s = sd + (long)r * in;
-  float* x = X + ((long)r * n + i) * xp;
-  for (int c = 0; c < od; ++c) x[c] = (o[c] - m[c]) / s[c];
-  for (int c = 0; c < ad; ++c) x[od + c] = (a[c] - m[od + c]) / s[od + c];
-  for (int c = in; c < xp; ++c) x[c] = 0.f;
+  const long ri = (long)r * n + i;
+  dyn_scale_row(obs + ri * od, od, act + ri * ad, ad, mu + (long)r * (od + ad), sd + (long)r * (od + ad), X + ri * xp, xp);
 }
 
 // Gaussian NLL head, one thread per (run, member, row, dim).  OUT / dOUT [r][k][i][op] (mean: cols 0..D, raw logvar: D..2D),
@@ -99,50 +143,29 @@ __global__ void k_dyn_nll(const float* __restrict__ OUT, float* __restrict__ dOU
   const long ki = e / D;
   const int i = (int)(ki % rows), k = (int)(ki / rows);
   const long row = ((long)r * K + k) * bs + i;
-  const float mx = params[r * P + off_max + d], mn = params[r * P + off_min + d];
-  const float mean = OUT[row * op + d], x = OUT[row * op + D + d];
-  const float y1 = mx - x;
-  const float l1 = mx - dyn_softplus(y1);
-  const float y2 = l1 - mn;
-  const float lv = mn + dyn_softplus(y2);
-  const float s1 = dyn_dsoftplus(y1), s2 = dyn_dsoftplus(y2);
-  const float inv = expf(-lv);
-  const float diff = mean - T[row * D + d];
-  const float sq = diff * diff * inv;
-  const float scale = 1.0f / ((float)rows * (float)D);
-  const float dmean = 2.f * diff * inv * scale;
-  const float dlv = (1.f - sq) * scale;
-  const float dl1 = dlv * s2;
-  dOUT[row * op + d] = dmean;
-  dOUT[row * op + D + d] = dl1 * s1;
-  lterm[row * D + d] = sq + lv;
-  gmax[row * D + d] = dl1 * (1.f - s1);
-  gmin[row * D + d] = dlv * (1.f - s2);
+  const DynNll g = dyn_nll_elem(OUT[row * op + d], OUT[row * op + D + d], T[row * D + d], params[r * P + off_max + d],
+                                params[r * P + off_min + d], 1.0f / ((float)rows * (float)D));
+  dyn_store_elem(g, row, d, op, D, dOUT, lterm, gmax, gmin);
 }
 
-// per run (blockIdx.x), 1024 threads: the three column sums over (member, row) in a fixed order, the minibatch loss without the decay
-// term, and the max / min_logvar gradients (+coef / -coef of the logvar_loss_coef term) into the gradient block
-__global__ __launch_bounds__(1024) void k_dyn_nll_reduce(const float* __restrict__ lterm, const float* __restrict__ gmax,
-                                                         const float* __restrict__ gmin, int K, int bs, int rows, int D,
-                                                         const float* __restrict__ params, float* __restrict__ G, long P, long off_max,
-                                                         long off_min, float coef, float* __restrict__ nll_out) {
-  __shared__ float red[3 * 64];
-  const int r = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int nw = blockDim.x >> 6;
+// The two reduce kernels, one workgroup of 1024 threads per run.  Column c of [lterm | gmax | gmin] summed by one wave over
+// (member k, row i0 + i) of a[r][k][bs rows][D] in a fixed order: lane stride 64 over e -> (k, i), then the shuffle tree.
+__device__ __forceinline__ float dyn_col_sum(const float* lterm, const float* gmax, const float* gmin, int c, int D, int r, int K, int bs,
+                                             int i0, int rows, int lane) {
+  const float* a = c < D ? lterm : (c < 2 * D ? gmax : gmin);
+  const int d = c % D;
   const int KR = K * rows;
-  for (int c = w; c < 3 * D; c += nw) {
-    const float* a = c < D ? lterm : (c < 2 * D ? gmax : gmin);
-    const int d = c % D;
-    float s = 0.f;
-    for (int e = lane; e < KR; e += 64) {
-      const int k = e / rows, i = e - k * rows;
-      s += a[(((long)r * K + k) * bs + i) * D + d];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) red[c] = s;
+  float s = 0.f;
+  for (int e = lane; e < KR; e += 64) {
+    const int k = e / rows, i = i0 + (e - k * rows);
+    s += a[(((long)r * K + k) * bs + i) * D + d];
   }
-  __syncthreads();
+  return dyn_wave_sum(s);
+}
+// ... and their tail on the 3 D column sums: the max / min_logvar gradients (+coef / -coef of the logvar-bound term) into the gradient
+// block and the loss without the decay term, the NLL a mean over `rows` rows and D dims
+__device__ __forceinline__ void dyn_reduce_tail(const float* red, int r, int rows, int D, const float* params, float* G, long P, long off_max,
+                                                long off_min, float coef, float* nll_out) {
   const int t = threadIdx.x;
   if (t < D) {
     G[r * P + off_max + t] = red[D + t] + coef;
@@ -157,6 +180,23 @@ __global__ __launch_bounds__(1024) void k_dyn_nll_reduce(const float* __restrict
     }
     nll_out[r] = ls / ((float)rows * (float)D) + (coef * smax - coef * smin);
   }
+}
+
+// per run (blockIdx.x): the three column sums over (member, row), the minibatch loss without the decay term and the max / min_logvar
+// gradients
+__global__ __launch_bounds__(1024) void k_dyn_nll_reduce(const float* __restrict__ lterm, const float* __restrict__ gmax,
+                                                         const float* __restrict__ gmin, int K, int bs, int rows, int D,
+                                                         const float* __restrict__ params, float* __restrict__ G, long P, long off_max,
+                                                         long off_min, float coef, float* __restrict__ nll_out) {
+  __shared__ float red[3 * 64];
+  const int r = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nw = blockDim.x >> 6;
+  for (int c = w; c < 3 * D; c += nw) {
+    const float s = dyn_col_sum(lterm, gmax, gmin, c, D, r, K, bs, 0, rows, lane);
+    if (lane == 0) red[c] = s;
+  }
+  __syncthreads();
+  dyn_reduce_tail(red, r, rows, D, params, G, P, off_max, off_min, coef, nll_out);
 }
 
 struct DynAdamP {
@@ -178,7 +218,6 @@ struct DynAdamP {
 // read (those of the minibatch's forward pass) is reduced into decay_part[r][block].  Four floats per thread (tensors are 16-B aligned).
 __global__ __launch_bounds__(256) void k_dyn_adam(DynAdamP p) {
   __shared__ float s_step, s_bc2s;
-  __shared__ float s_red[4];
   const int r = blockIdx.y;
   if (!p.active[r]) return;                                   // uniform per block
   if (threadIdx.x == 0) {
@@ -208,32 +247,24 @@ __global__ __launch_bounds__(256) void k_dyn_adam(DynAdamP p) {
     }
     dec *= 0.5f * wd;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) dec += __shfl_xor(dec, o, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = dec;
-  __syncthreads();
-  if (threadIdx.x == 0) p.decay_part[(long)r * p.nblk + blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+  dec = dyn_block_sum256(dec);
+  if (threadIdx.x == 0) p.decay_part[(long)r * p.nblk + blockIdx.x] = dec;
 }
 
 // loss_sum[r] += nll[r] + sum_b decay_part[r][b] for the active runs (fixed order)
 __global__ __launch_bounds__(256) void k_dyn_loss(const float* __restrict__ nll, const float* __restrict__ decay_part, int nblk,
                                                   const int* __restrict__ active, float* __restrict__ loss_sum) {
-  __shared__ float s_red[4];
   const int r = blockIdx.x;
   if (!active[r]) return;
   float s = 0.f;
   for (int b = threadIdx.x; b < nblk; b += blockDim.x) s += decay_part[(long)r * nblk + b];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) loss_sum[r] += nll[r] + ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+  s = dyn_block_sum256(s);
+  if (threadIdx.x == 0) loss_sum[r] += nll[r] + s;
 }
 
 // validate(): mse[r][k] = mean over (row, dim) of (mean - target)^2; OUT [r][k][H][op], T [r][H][D]
 __global__ __launch_bounds__(256) void k_dyn_val_mse(const float* __restrict__ OUT, int op, const float* __restrict__ T, int H, int D,
                                                      int K, float* __restrict__ mse) {
-  __shared__ float s_red[4];
   const int k = blockIdx.x, r = blockIdx.y;
   float s = 0.f;
   const long n = (long)H * D;
@@ -242,11 +273,8 @@ __global__ __launch_bounds__(256) void k_dyn_val_mse(const float* __restrict__ O
     const float diff = OUT[(((long)r * K + k) * H + i) * op + d] - T[((long)r * H + i) * D + d];
     s += diff * diff;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) mse[r * K + k] = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) / (float)n;
+  s = dyn_block_sum256(s);
+  if (threadIdx.x == 0) mse[r * K + k] = s / (float)n;
 }
 
 enum { DYN_MAXD = 64 };
@@ -278,30 +306,21 @@ __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
     return m;
   };
   auto std_at = [&](int k, int d) {
-    const float x = p.OUT[(((long)r * K + k) * p.n + i) * p.op + D + d];
-    const float l1 = mx[d] - dyn_softplus(mx[d] - x);
-    const float lv = mn[d] + dyn_softplus(l1 - mn[d]);
-    return sqrtf(expf(lv));
+    return dyn_std(p.OUT[(((long)r * K + k) * p.n + i) * p.op + D + d], mx[d], mn[d]);
   };
   int mi;
   uint32_t rnd[4];
+  const Philox ph(p.seed);
   if (p.midx) mi = p.midx[(long)r * p.n + i];
   else {
-    dyn_philox(p.seed, (uint32_t)i, (uint32_t)(i >> 32), (uint32_t)r, (uint32_t)(0x80000000u | (uint32_t)p.call), rnd);
-    mi = p.elites[r * K + (int)(((uint64_t)rnd[0] * (uint64_t)p.n_elites) >> 32)];
+    ph((uint32_t)i, (uint32_t)(i >> 32), (uint32_t)r, (uint32_t)(0x80000000u | (uint32_t)p.call), rnd);
+    mi = dyn_draw_elite(p.elites, r, K, p.n_elites, rnd[0]);
   }
   for (int d0 = 0; d0 < D; d0 += 4) {
-    if (!p.noise) dyn_philox(p.seed, (uint32_t)i, (uint32_t)(i >> 32), (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)(d0 >> 2), rnd);
+    if (!p.noise) ph((uint32_t)i, (uint32_t)(i >> 32), (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)(d0 >> 2), rnd);
     for (int j = 0; j < 4 && d0 + j < D; ++j) {
       const int d = d0 + j;
-      double eps;
-      if (p.noise) eps = (double)p.noise[(((long)r * K + mi) * p.n + i) * D + d];
-      else {
-        // Box-Muller on the pair (j & ~1, j | 1) of this Philox word
-        const float u1 = dyn_u01(rnd[j & ~1]), u2 = dyn_u01(rnd[j | 1]);
-        const float rad = sqrtf(-2.0f * logf(u1)), th = 6.28318530717958647692f * u2;
-        eps = (double)((j & 1) ? rad * sinf(th) : rad * cosf(th));
-      }
+      const double eps = p.noise ? (double)p.noise[(((long)r * K + mi) * p.n + i) * D + d] : (double)box_muller_one(rnd, j);
       const float s = (float)((double)mean_at(mi, d) + eps * (double)std_at(mi, d));
       if (d < od) p.next_obs[((long)r * p.n + i) * od + d] = s;
       else p.raw_reward[(long)r * p.n + i] = s;
@@ -355,8 +374,8 @@ struct DynSampleNextP {
   float* next_obs;                    // [R][S * E * n][od], row (s * E + e) * n + b
 };
 
-// one thread per (run, sample s, elite position e, row b, four output dims): mean_m + eps std_m of elite m = elites[e] in fp32 with
-// two roundings (randn_like(std) * std, then + mean); the reward column is drawn like the others and dropped
+// one thread per (run, sample s, elite position e, row b, four output dims): mean_m + eps std_m of elite m = elites[e], std_m from
+// dyn_std like k_dyn_head's; the reward column is drawn like the others and dropped
 __global__ __launch_bounds__(256) void k_dyn_sample_next(DynSampleNextP p) {
   const int nq = (p.D + 3) >> 2;
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -372,24 +391,16 @@ __global__ __launch_bounds__(256) void k_dyn_sample_next(DynSampleNextP p) {
   const float* mx = p.params + r * p.P + p.off_max;
   const float* mn = p.params + r * p.P + p.off_min;
   uint32_t rnd[4];
-  if (!p.noise) dyn_philox(p.seed, (uint32_t)b, (uint32_t)se, (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)q, rnd);
+  if (!p.noise) Philox(p.seed)((uint32_t)b, (uint32_t)se, (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)q, rnd);
   const float* out = p.OUT + (((long)r * K + mi) * p.n + b) * p.op;
   const float* obs = p.obs + ((long)r * p.n + b) * od;
   float* dst = p.next_obs + ((long)r * rows + row) * od;
   for (int j = 0; j < 4 && 4 * q + j < od; ++j) {
     const int d = 4 * q + j;
-    float eps;
-    if (p.noise) eps = p.noise[((long)r * rows + row) * D + d];
-    else {
-      const float u1 = dyn_u01(rnd[j & ~1]), u2 = dyn_u01(rnd[j | 1]);
-      const float rad = sqrtf(-2.0f * logf(u1)), th = 6.28318530717958647692f * u2;
-      eps = (j & 1) ? rad * sinf(th) : rad * cosf(th);
-    }
+    const float eps = p.noise ? p.noise[((long)r * rows + row) * D + d] : box_muller_one(rnd, j);
     const float mean = out[d] + obs[d];
-    const float x = out[D + d];
-    const float l1 = mx[d] - dyn_softplus(mx[d] - x);
-    const float lv = mn[d] + dyn_softplus(l1 - mn[d]);
-    dst[d] = __fadd_rn(mean, __fmul_rn(eps, sqrtf(expf(lv))));
+    // two roundings in fp32: the reference's mean + torch.randn_like(std) * std
+    dst[d] = __fadd_rn(mean, __fmul_rn(eps, dyn_std(out[D + d], mx[d], mn[d])));
   }
 }
 
@@ -414,13 +425,7 @@ __global__ void k_dyn_adv_input(const float* __restrict__ obs, const float* __re
   const long j = sl ? (long)r * Bs + (i - Ba) : (long)r * Ba + i;
   const float* o = (sl ? sl_obs : obs) + j * od;
   const float* a = (sl ? sl_act : act) + j * ad;
-  const int in = od + ad;
-  const float* m = mu + (long)r * in;
-  const float* s = sd + (long)r * in;
-  float* x = X + ((long)r * N + i) * xp;
-  for (int c = 0; c < od; ++c) x[c] = (o[c] - m[c]) / s[c];
-  for (int c = 0; c < ad; ++c) x[od + c] = (a[c] - m[od + c]) / s[od + c];
-  for (int c = in; c < xp; ++c) x[c] = 0.f;
+  dyn_scale_row(o, od, a, ad, mu + (long)r * (od + ad), sd + (long)r * (od + ad), X + ((long)r * N + i) * xp, xp);
   if (sl) {
     float* t = T + j * D;
     const float* nx = sl_next + j * od;
@@ -454,29 +459,22 @@ __global__ __launch_bounds__(256) void k_dyn_adv_sample(DynAdvSampleP p) {
   const float* mn = p.params + r * p.P + p.off_min;
   int mi;
   uint32_t rnd[4];
+  const Philox ph(p.seed);
   if (p.midx) mi = p.midx[(long)r * p.Ba + i];
   else {
-    dyn_philox(p.seed, (uint32_t)i, 0u, (uint32_t)r, (uint32_t)(0x80000000u | (uint32_t)p.call), rnd);
-    mi = p.elites[r * K + (int)(((uint64_t)rnd[0] * (uint64_t)p.n_elites) >> 32)];
+    ph((uint32_t)i, 0u, (uint32_t)r, (uint32_t)(0x80000000u | (uint32_t)p.call), rnd);
+    mi = dyn_draw_elite(p.elites, r, K, p.n_elites, rnd[0]);
   }
-  if (!p.noise) dyn_philox(p.seed, (uint32_t)i, 0u, (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)q, rnd);
+  if (!p.noise) ph((uint32_t)i, 0u, (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)q, rnd);
   const float* out = p.OUT + (((long)r * K + mi) * p.N + i) * p.op;
   const long ri = (long)r * p.Ba + i;
   for (int j = 0; j < 4 && 4 * q + j < D; ++j) {
     const int d = 4 * q + j;
-    float eps;
-    if (p.noise) eps = p.noise[(((long)r * K + mi) * p.Ba + i) * D + d];
-    else {
-      const float u1 = dyn_u01(rnd[j & ~1]), u2 = dyn_u01(rnd[j | 1]);
-      const float rad = sqrtf(-2.0f * logf(u1)), th = 6.28318530717958647692f * u2;
-      eps = (j & 1) ? rad * sinf(th) : rad * cosf(th);
-    }
+    const float eps = p.noise ? p.noise[(((long)r * K + mi) * p.Ba + i) * D + d] : box_muller_one(rnd, j);
     float mean = out[d];
     if (d < od) mean += p.obs[ri * od + d];
-    const float x = out[D + d];
-    const float l1 = mx[d] - dyn_softplus(mx[d] - x);
-    const float lv = mn[d] + dyn_softplus(l1 - mn[d]);
-    const float s = __fadd_rn(mean, __fmul_rn(sqrtf(expf(lv)), eps));
+    // two roundings in fp32: the reference's torch.distributions.Normal(mean, std).sample() = torch.normal: std * eps, then + mean
+    const float s = __fadd_rn(mean, __fmul_rn(dyn_std(out[D + d], mx[d], mn[d]), eps));
     p.S[ri * D + d] = s;
     if (d < od) p.next_obs[ri * od + d] = s;
     else p.reward[ri] = s;
@@ -497,7 +495,7 @@ struct DynAdvHeadP {
 // the head of the update, one WAVE per (run, row), lanes over (member, dim); blockDim = 64 wpb, dynamic LDS wpb (K D + 64) doubles.
 // Rollout rows (i < Ba): lp_k = sum_d Normal(mean_k, std_k).log_prob(s) summed in double in dim order, the elite mixture as a
 // log-sum-exp (finite where exp(lp_k) underflows), w_k = softmax over the elites (exactly 0 elsewhere) and the gradient
-// adv_weight A_i / Ba w_k through mean, soft_clamp and max / min_logvar.  Dataset rows: k_dyn_nll's terms with Bs rows.
+// adv_weight A_i / Ba w_k through mean, soft_clamp and max / min_logvar.  Dataset rows: dyn_nll_elem, as in k_dyn_nll, with Bs rows.
 __global__ void k_dyn_adv_head(DynAdvHeadP p) {
   extern __shared__ double adv_sm[];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -516,10 +514,7 @@ __global__ void k_dyn_adv_head(DynAdvHeadP p) {
       const float* out = p.OUT + (((long)r * K + k) * N + i) * p.op;
       float mean = out[d];
       if (d < p.od) mean += p.obs[ri * p.od + d];
-      const float x = out[D + d];
-      const float l1 = mxp[d] - dyn_softplus(mxp[d] - x);
-      const float lv = mnp[d] + dyn_softplus(l1 - mnp[d]);
-      const float sdv = sqrtf(expf(lv));
+      const float sdv = dyn_std(out[D + d], mxp[d], mnp[d]);
       const float z = p.S[ri * D + d] - mean;
       lp[e] = (double)(-(z * z) / (2.f * (sdv * sdv)) - logf(sdv) - 0.91893853320467274178f);
     }
@@ -536,9 +531,7 @@ __global__ void k_dyn_adv_head(DynAdvHeadP p) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
     const double ex = el ? exp(s - m) : 0.0;
-    double sum = ex;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    const double sum = dyn_wave_sum(ex);
     wk[lane] = ex / sum;
     if (lane == 0) p.rowlp[ri] = m + log(sum) - log((double)p.n_elites);
   }
@@ -552,22 +545,14 @@ __global__ void k_dyn_adv_head(DynAdvHeadP p) {
       const float* out = p.OUT + row * p.op;
       float mean = out[d];
       if (d < p.od) mean += p.obs[ri * p.od + d];
-      const float x = out[D + d];
-      const float y1 = mxp[d] - x;
-      const float l1 = mxp[d] - dyn_softplus(y1);
-      const float y2 = l1 - mnp[d];
-      const float lv = mnp[d] + dyn_softplus(y2);
-      const float s1 = dyn_dsoftplus(y1), s2 = dyn_dsoftplus(y2);
-      const float inv = expf(-lv);
+      const DynClamp cl = dyn_soft_clamp_grad(out[D + d], mxp[d], mnp[d]);
+      const float inv = expf(-cl.lv);
       const float z = p.S[ri * D + d] - mean;
       const float c = c0 * (float)wk[k];
       const float dlv = c * 0.5f * (z * z * inv - 1.f);
-      const float dl1 = dlv * s2;
-      p.dOUT[row * p.op + d] = c * z * inv;
-      p.dOUT[row * p.op + D + d] = dl1 * s1;
-      p.lterm[row * D + d] = 0.f;
-      p.gmax[row * D + d] = dl1 * (1.f - s1);
-      p.gmin[row * D + d] = dlv * (1.f - s2);
+      const float dl1 = dlv * cl.s2;
+      dyn_store_elem({c * z * inv, dl1 * cl.s1, 0.f, dl1 * (1.f - cl.s1), dlv * (1.f - cl.s2)}, row, d, p.op, D, p.dOUT, p.lterm, p.gmax,
+                     p.gmin);
     }
   } else {
     const long tj = (long)r * p.Bs + (i - p.Ba);
@@ -575,22 +560,8 @@ __global__ void k_dyn_adv_head(DynAdvHeadP p) {
     for (int e = lane; e < KD; e += 64) {
       const int k = e / D, d = e - k * D;
       const long row = ((long)r * K + k) * N + i;
-      const float mean = p.OUT[row * p.op + d], x = p.OUT[row * p.op + D + d];
-      const float y1 = mxp[d] - x;
-      const float l1 = mxp[d] - dyn_softplus(y1);
-      const float y2 = l1 - mnp[d];
-      const float lv = mnp[d] + dyn_softplus(y2);
-      const float s1 = dyn_dsoftplus(y1), s2 = dyn_dsoftplus(y2);
-      const float inv = expf(-lv);
-      const float diff = mean - p.T[tj * D + d];
-      const float sq = diff * diff * inv;
-      const float dlv = (1.f - sq) * scale;
-      const float dl1 = dlv * s2;
-      p.dOUT[row * p.op + d] = 2.f * diff * inv * scale;
-      p.dOUT[row * p.op + D + d] = dl1 * s1;
-      p.lterm[row * D + d] = sq + lv;
-      p.gmax[row * D + d] = dl1 * (1.f - s1);
-      p.gmin[row * D + d] = dlv * (1.f - s2);
+      const DynNll g = dyn_nll_elem(p.OUT[row * p.op + d], p.OUT[row * p.op + D + d], p.T[tj * D + d], mxp[d], mnp[d], scale);
+      dyn_store_elem(g, row, d, p.op, D, p.dOUT, p.lterm, p.gmax, p.gmin);
     }
   }
 }
@@ -609,41 +580,20 @@ __global__ __launch_bounds__(1024) void k_dyn_adv_reduce(const float* __restrict
   const int N = Ba + Bs;
   for (int c = w; c < 3 * D + 2; c += nw) {
     if (c < 3 * D) {
-      const float* a = c < D ? lterm : (c < 2 * D ? gmax : gmin);
-      const int d = c % D;
-      const int i0 = c < D ? Ba : 0, rows = N - i0;
-      const int KR = K * rows;
-      float s = 0.f;
-      for (int e = lane; e < KR; e += 64) {
-        const int k = e / rows, i = i0 + (e - k * rows);
-        s += a[(((long)r * K + k) * N + i) * D + d];
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      const int i0 = c < D ? Ba : 0;
+      const float s = dyn_col_sum(lterm, gmax, gmin, c, D, r, K, N, i0, N - i0, lane);
       if (lane == 0) red[c] = s;
     } else {
       const bool wa = c == 3 * D;
       double s = 0.0;
       for (int i = lane; i < Ba; i += 64) s += wa ? rowlp[(long)r * Ba + i] * (double)adv[(long)r * Ba + i] : rowlp[(long)r * Ba + i];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      s = dyn_wave_sum(s);
       if (lane == 0) red2[c - 3 * D] = s;
     }
   }
   __syncthreads();
-  const int t = threadIdx.x;
-  if (t < D) {
-    G[r * P + off_max + t] = red[D + t] + coef;
-    G[r * P + off_min + t] = red[2 * D + t] - coef;
-  }
-  if (t == 0) {
-    float ls = 0.f, smax = 0.f, smin = 0.f;
-    for (int d = 0; d < D; ++d) {
-      ls += red[d];
-      smax += params[r * P + off_max + d];
-      smin += params[r * P + off_min + d];
-    }
-    nll_out[r] = ls / ((float)Bs * (float)D) + (coef * smax - coef * smin);
+  dyn_reduce_tail(red, r, Bs, D, params, G, P, off_max, off_min, coef, nll_out);
+  if (threadIdx.x == 0) {
     advm[2 * r] = (float)(red2[0] / (double)Ba);
     advm[2 * r + 1] = (float)(red2[1] / (double)Ba);
   }
@@ -653,19 +603,15 @@ __global__ __launch_bounds__(1024) void k_dyn_adv_reduce(const float* __restrict
 __global__ __launch_bounds__(256) void k_dyn_adv_metrics(const float* __restrict__ nll, const float* __restrict__ decay_part, int nblk,
                                                          const int* __restrict__ active, const float* __restrict__ advm, float adv_weight,
                                                          float* __restrict__ metrics) {
-  __shared__ float s_red[4];
   const int r = blockIdx.x;
   float s = 0.f;
   if (active[r])
     for (int b = threadIdx.x; b < nblk; b += blockDim.x) s += decay_part[(long)r * nblk + b];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  s = dyn_block_sum256(s);
   if (threadIdx.x == 0) {
     float* m = metrics + 4 * r;
     if (!active[r]) { m[0] = m[1] = m[2] = m[3] = 0.f; return; }
-    const float sl = nll[r] + ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+    const float sl = nll[r] + s;
     m[0] = adv_weight * advm[2 * r] + sl;
     m[1] = sl;
     m[2] = advm[2 * r];
@@ -678,6 +624,17 @@ __global__ __launch_bounds__(256) void k_dyn_adv_metrics(const float* __restrict
 using namespace orl;
 
 struct DynTensor { std::string name; long off; std::vector<long> shape; };
+
+// A training workspace: the matrices of one forward + backward over `rows` rows per (run, member), [R][K][rows][pitch] each.
+// `shared`: layer 0's input X is ONE [R][rows][pitch] matrix for the members (member stride 0).  The forward-only step workspace is a
+// view of the same type: X, OUT and H[l] alternating between two buffers, `rows` set by each call.
+struct DynWs {
+  long rows = 0;
+  bool shared = false;
+  float *X = nullptr, *OUT = nullptr, *dOUT = nullptr, *dA = nullptr, *dB = nullptr;
+  float *H[ORL_MAX_HIDDEN] = {}, *Z[ORL_MAX_HIDDEN] = {};
+  float *lterm = nullptr, *gmax = nullptr, *gmin = nullptr;
+};
 
 struct orl_dynamics {
   orl_dyn_config c;
@@ -693,16 +650,15 @@ struct orl_dynamics {
   std::vector<long long> tstep;
   float *data_in = nullptr, *data_tg = nullptr; long n_data = 0;
   float *mu = nullptr, *sd = nullptr;
-  // learn workspaces [R][K][B][pitch]
-  float *X0 = nullptr, *T = nullptr, *OUT = nullptr, *dOUT = nullptr, *dA = nullptr, *dB = nullptr;
-  float *H[ORL_MAX_HIDDEN] = {}, *Z[ORL_MAX_HIDDEN] = {};
-  float *lterm = nullptr, *gmax = nullptr, *gmin = nullptr, *decay_part = nullptr, *nll = nullptr, *loss_sum = nullptr;
+  DynWs lw;                                  // learn(): B rows, an input per member
+  float *T = nullptr, *decay_part = nullptr, *nll = nullptr, *loss_sum = nullptr;
   int nblk = 0;
   int* active_d = nullptr; long long* t0_d = nullptr;
   int* idx_d = nullptr; long idx_cap = 0;
   // validate / step workspaces, grown on demand: rows capacity
   long s_cap = 0;
-  float *sX = nullptr, *sT = nullptr, *sH0 = nullptr, *sH1 = nullptr, *sOUT = nullptr, *sObs = nullptr, *sAct = nullptr, *sNoise = nullptr;
+  DynWs sw;
+  float *sT = nullptr, *sH0 = nullptr, *sH1 = nullptr, *sObs = nullptr, *sAct = nullptr, *sNoise = nullptr;
   float *sNext = nullptr, *sRew = nullptr, *sRaw = nullptr, *sPen = nullptr;
   int *sIdx = nullptr, *sMidx = nullptr, *sMidxOut = nullptr;
   uint64_t step_calls = 0;
@@ -717,10 +673,8 @@ struct orl_dynamics {
   float *adv_m = nullptr, *adv_v = nullptr;
   std::vector<long long> adv_tstep;
   uint64_t adv_calls = 0;
-  float *aX = nullptr, *aT = nullptr, *aOUT = nullptr, *adOUT = nullptr, *adA = nullptr, *adB = nullptr;
-  float *aH[ORL_MAX_HIDDEN] = {}, *aZ[ORL_MAX_HIDDEN] = {};
-  float *aLterm = nullptr, *aGmax = nullptr, *aGmin = nullptr, *aS = nullptr, *aObs = nullptr, *aAdv = nullptr, *aAdvm = nullptr,
-        *aMetrics = nullptr;
+  DynWs aw;                                  // Ba + Bs rows, one input shared by the members
+  float *aT = nullptr, *aS = nullptr, *aObs = nullptr, *aAdv = nullptr, *aAdvm = nullptr, *aMetrics = nullptr;
   double* aRowlp = nullptr;
   float *aInObs = nullptr, *aInAct = nullptr, *aSlObs = nullptr, *aSlAct = nullptr, *aSlNext = nullptr, *aSlRew = nullptr,
         *aNoise = nullptr, *aNext = nullptr, *aRew = nullptr;
@@ -742,26 +696,56 @@ static void dyn_free(orl_dynamics* d, void* p) {
     if (*it == p) { d->allocs.erase(it); break; }
   hipFree(p);
 }
+template <class... T>
+static void dyn_release(orl_dynamics* d, T**... ps) { ((dyn_free(d, *ps), *ps = nullptr), ...); }
+
+static int dyn_hmax(const orl_dynamics* d, int last) {      // widest pitch of layers 1 .. last
+  int hmax = 4;
+  for (int l = 1; l <= last; ++l) hmax = std::max(hmax, d->pitch[l]);
+  return hmax;
+}
+
+static void dyn_ws_release(orl_dynamics* d, DynWs& w) {
+  dyn_release(d, &w.X, &w.OUT, &w.dOUT, &w.dA, &w.dB, &w.lterm, &w.gmax, &w.gmin);
+  for (int l = 0; l < d->L; ++l) dyn_release(d, &w.H[l], &w.Z[l]);
+  w.rows = 0;
+}
+static int dyn_ws_alloc(orl_dynamics* d, DynWs& w, long rows, bool shared) {
+  dyn_ws_release(d, w);
+  const long RK = (long)d->R * d->K * rows, po = d->pitch[d->L + 1], hmax = dyn_hmax(d, d->L + 1);
+  bool bad = dyn_alloc_t(d, &w.X, (shared ? d->R * rows : RK) * d->pitch[0]) || dyn_alloc_t(d, &w.OUT, RK * po) ||
+             dyn_alloc_t(d, &w.dOUT, RK * po) || dyn_alloc_t(d, &w.dA, RK * hmax) || dyn_alloc_t(d, &w.dB, RK * hmax) ||
+             dyn_alloc_t(d, &w.lterm, RK * d->D) || dyn_alloc_t(d, &w.gmax, RK * d->D) || dyn_alloc_t(d, &w.gmin, RK * d->D);
+  for (int l = 0; l < d->L && !bad; ++l) bad = dyn_alloc_t(d, &w.H[l], RK * d->pitch[l + 1]) || dyn_alloc_t(d, &w.Z[l], RK * d->pitch[l + 1]);
+  if (bad) return -1;
+  w.rows = rows; w.shared = shared;
+  return 0;
+}
 
 #define DYN_HIP(expr)                                                                                   \
   do {                                                                                                  \
     hipError_t _e = (expr);                                                                             \
     if (_e != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(_e));               \
   } while (0)
-#define DYN_LAUNCHED(what)                                                                              \
+// one kernel launch on the object's stream (d->stream) and its check
+#define DYN_LAUNCH(kernel, grid, block, lds, ...)                                                       \
   do {                                                                                                  \
-    if (hipGetLastError() != hipSuccess) return fail(std::string(what) + ": launch failed");            \
+    hipLaunchKernelGGL(kernel, grid, block, lds, d->stream, __VA_ARGS__);                               \
+    if (hipGetLastError() != hipSuccess) return fail(#kernel ": launch failed");                        \
   } while (0)
 
 // ---- the matrix products (csrc/gemm.h) ----
-struct DMat { float* p; long s0, s1; int pitch; };   // [run][member][row][pitch]; s1 = 0: one matrix shared by the members
+struct DMat {                                        // [run][member][row][pitch]; s1 = 0: one matrix shared by the members
+  float* p; long s0, s1; int pitch;
+  ZPtr z() const { return {p, s0, s1}; }
+};
 
 // Y = act(X W_l + b_l) for every (run, member); epi E_BIAS_SWISH (z to Zo when non-null) or E_BIAS
 static int dyn_fwd(orl_dynamics* d, const DMat& X, int M, int l, const DMat& Y, float* Zo, bool swish) {
   const int in = d->width[l], out = d->width[l + 1];
   GemmP p;
   memset(&p, 0, sizeof(p));
-  p.A = {X.p, X.s0, X.s1}; p.a_sr = X.pitch; p.a_sk = 1;
+  p.A = X.z(); p.a_sr = X.pitch; p.a_sk = 1;
   p.B = {d->params + d->w_off[l], d->P, (long)in * out}; p.b_sr = 1; p.b_sk = out; p.b_rlim = out & ~3;
   p.C = Y.p; p.c_s0 = Y.s0; p.c_s1 = Y.s1; p.c_sr = Y.pitch; p.c_sn = 1;
   p.M = M; p.N = out; p.K = in;
@@ -782,12 +766,12 @@ static int dyn_dgrad(orl_dynamics* d, const DMat& dY, int M, int l, const DMat& 
   const int in = d->width[l], out = d->width[l + 1];
   GemmP p;
   memset(&p, 0, sizeof(p));
-  p.A = {dY.p, dY.s0, dY.s1}; p.a_sr = dY.pitch; p.a_sk = 1;
+  p.A = dY.z(); p.a_sr = dY.pitch; p.a_sk = 1;
   p.B = {d->params + d->w_off[l], d->P, (long)in * out}; p.b_sr = out; p.b_sk = 1;
   p.C = dX.p; p.c_s0 = dX.s0; p.c_s1 = dX.s1; p.c_sr = dX.pitch; p.c_sn = 1;
   p.M = M; p.N = in; p.K = out;
   p.nz1 = d->K; p.ksplit = 1;
-  p.aux = {Zin.p, Zin.s0, Zin.s1}; p.aux_sr = Zin.pitch;
+  p.aux = Zin.z(); p.aux_sr = Zin.pitch;
   const int nz = d->R * d->K;
   const int cfg = pick_cfg(p.M, p.N, p.K, nz);
   hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_SWISH_GRAD>(cfg, p, nz, d->stream, dY.pitch >= rup4(out), false, P_F32);
@@ -800,8 +784,8 @@ static int dyn_wgrad(orl_dynamics* d, const DMat& dY, const DMat& X, int M, int 
   const int in = d->width[l], out = d->width[l + 1];
   GemmP p;
   memset(&p, 0, sizeof(p));
-  p.A = {dY.p, dY.s0, dY.s1}; p.a_sr = 1; p.a_sk = dY.pitch;
-  p.B = {X.p, X.s0, X.s1}; p.b_sr = 1; p.b_sk = X.pitch;
+  p.A = dY.z(); p.a_sr = 1; p.a_sk = dY.pitch;
+  p.B = X.z(); p.b_sr = 1; p.b_sk = X.pitch;
   p.a_rlim = dY.pitch & ~3; p.b_rlim = X.pitch & ~3;
   p.ones_row = 1 << 30;
   p.M = out; p.N = in; p.K = M;
@@ -832,43 +816,62 @@ static DynAdamP dyn_adam_params(orl_dynamics* d) {
   return a;
 }
 
+// matrix p of a workspace at layer l's width, and the workspace's layer-0 input
+static DMat dyn_mat(const orl_dynamics* d, const DynWs& w, float* p, int l) {
+  const long pt = d->pitch[l];
+  return {p, d->K * w.rows * pt, w.rows * pt, (int)pt};
+}
+static DMat dyn_input(const orl_dynamics* d, const DynWs& w) {
+  DMat X = dyn_mat(d, w, w.X, 0);
+  if (w.shared) { X.s0 = X.s1; X.s1 = 0; }
+  return X;
+}
+
+// forward of the whole ensemble over the first `rows` rows of a workspace: L x E_BIAS_SWISH (pre-activations to Z when kept), E_BIAS
+static int dyn_forward(orl_dynamics* d, const DynWs& w, int rows, bool keep_z) {
+  DMat X = dyn_input(d, w);
+  for (int l = 0; l < d->L; ++l) {
+    const DMat Y = dyn_mat(d, w, w.H[l], l + 1);
+    if (dyn_fwd(d, X, rows, l, Y, keep_z ? w.Z[l] : nullptr, true)) return -1;
+    X = Y;
+  }
+  return dyn_fwd(d, X, rows, d->L, dyn_mat(d, w, w.OUT, d->L + 1), nullptr, false);
+}
+
+// backward from dOUT, top down: weight / bias gradients into the gradient block, input gradients alternating between dA and dB
+static int dyn_backward(orl_dynamics* d, const DynWs& w, int rows) {
+  DMat dY = dyn_mat(d, w, w.dOUT, d->L + 1);
+  for (int l = d->L; l >= 0; --l) {
+    if (dyn_wgrad(d, dY, l ? dyn_mat(d, w, w.H[l - 1], l) : dyn_input(d, w), rows, l)) return -1;
+    if (l > 0) {
+      const DMat dX = dyn_mat(d, w, (l & 1) ? w.dB : w.dA, l);
+      if (dyn_dgrad(d, dY, rows, l, dX, dyn_mat(d, w, w.Z[l - 1], l))) return -1;
+      dY = dX;
+    }
+  }
+  return 0;
+}
+
 static int dyn_grow_step(orl_dynamics* d, long rows) {
   if (rows <= d->s_cap) return 0;
   DYN_HIP(hipStreamSynchronize(d->stream));
-  float** fs[] = {&d->sX, &d->sT, &d->sH0, &d->sH1, &d->sOUT, &d->sObs, &d->sAct, &d->sNoise, &d->sNext, &d->sRew, &d->sRaw, &d->sPen};
-  for (float** f : fs) { dyn_free(d, *f); *f = nullptr; }
-  int** is[] = {&d->sIdx, &d->sMidx, &d->sMidxOut};
-  for (int** f : is) { dyn_free(d, *f); *f = nullptr; }
+  DynWs& w = d->sw;
+  dyn_release(d, &w.X, &d->sT, &d->sH0, &d->sH1, &w.OUT, &d->sObs, &d->sAct, &d->sNoise, &d->sNext, &d->sRew, &d->sRaw, &d->sPen, &d->sIdx,
+              &d->sMidx, &d->sMidxOut);
   const long R = d->R, K = d->K;
-  int hmax = 4;
-  for (int l = 1; l <= d->L; ++l) hmax = std::max(hmax, d->pitch[l]);
-  if (dyn_alloc_t(d, &d->sX, R * rows * d->pitch[0]) || dyn_alloc_t(d, &d->sT, R * rows * d->D) ||
+  const int hmax = dyn_hmax(d, d->L);
+  if (dyn_alloc_t(d, &w.X, R * rows * d->pitch[0]) || dyn_alloc_t(d, &d->sT, R * rows * d->D) ||
       dyn_alloc_t(d, &d->sH0, R * K * rows * hmax) || dyn_alloc_t(d, &d->sH1, R * K * rows * hmax) ||
-      dyn_alloc_t(d, &d->sOUT, R * K * rows * d->pitch[d->L + 1]) || dyn_alloc_t(d, &d->sObs, R * rows * d->od) ||
+      dyn_alloc_t(d, &w.OUT, R * K * rows * d->pitch[d->L + 1]) || dyn_alloc_t(d, &d->sObs, R * rows * d->od) ||
       dyn_alloc_t(d, &d->sAct, R * rows * d->ad) || dyn_alloc_t(d, &d->sNoise, R * K * rows * d->D) ||
       dyn_alloc_t(d, &d->sNext, R * rows * d->od) || dyn_alloc_t(d, &d->sRew, R * rows) || dyn_alloc_t(d, &d->sRaw, R * rows) ||
       dyn_alloc_t(d, &d->sPen, R * rows) || dyn_alloc_t(d, &d->sIdx, R * rows) || dyn_alloc_t(d, &d->sMidx, R * rows) ||
       dyn_alloc_t(d, &d->sMidxOut, R * rows))
     return -1;
+  for (int l = 0; l < d->L; ++l) w.H[l] = (l & 1) ? d->sH1 : d->sH0;
+  w.shared = true;
   d->s_cap = rows;
   return 0;
-}
-
-// forward of the whole ensemble on a 2-D input shared by the members (validate, step): OUT [R][K][n][pO]
-static int dyn_forward_shared(orl_dynamics* d, long n) {
-  const long R = d->R, K = d->K;
-  (void)R;
-  DMat X = {d->sX, n * d->pitch[0], 0, d->pitch[0]};
-  float* bufs[2] = {d->sH0, d->sH1};
-  for (int l = 0; l < d->L; ++l) {
-    const int pt = d->pitch[l + 1];
-    DMat Y = {bufs[l & 1], K * n * pt, n * pt, pt};
-    if (dyn_fwd(d, X, (int)n, l, Y, nullptr, true)) return -1;
-    X = Y;
-  }
-  const int po = d->pitch[d->L + 1];
-  DMat Y = {d->sOUT, K * n * po, n * po, po};
-  return dyn_fwd(d, X, (int)n, d->L, Y, nullptr, false);
 }
 
 // parameter block: state_dict order, every tensor 16-B aligned; returns its floats
@@ -894,6 +897,58 @@ static long dyn_layout(orl_dynamics* d) {
     d->sb_off[l] = add(pre + "saved_bias", {K, 1, o});
   }
   return off;
+}
+
+// the elite count that every run shares, or -1 with the refusal of the call named
+static int dyn_n_elites(orl_dynamics* d, const char* what) {
+  const int E = (int)d->elites_h[0].size();
+  for (int r = 1; r < d->R; ++r)
+    if ((int)d->elites_h[r].size() != E) return fail(std::string(what) + ": every run needs the same number of elites");
+  return E;
+}
+
+// teacher-forced member indices: int64 -> int with the range check into h, uploaded to dst on the stream (h lives until the call's
+// final synchronise)
+static int dyn_upload_midx(orl_dynamics* d, const int64_t* idx, long count, std::vector<int>& h, int* dst, const char* what) {
+  h.resize((size_t)count);
+  for (long i = 0; i < count; ++i) {
+    if (idx[i] < 0 || idx[i] >= d->K) return fail(std::string(what) + ": model index out of range");
+    h[i] = (int)idx[i];
+  }
+  DYN_HIP(hipMemcpyAsync(dst, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, d->stream));
+  return 0;
+}
+
+// k_dyn_adam's run state: the active flags (into act as well; all runs when null) and the optimizer's step counts; either a blocking
+// copy or one on the stream, whose sources then live until the call's final synchronise
+static int dyn_upload_run_state(orl_dynamics* d, const int32_t* active, const std::vector<long long>& tstep, std::vector<int>& act,
+                                bool on_stream) {
+  act.assign(d->R, 1);
+  if (active) for (int r = 0; r < d->R; ++r) act[r] = active[r] ? 1 : 0;
+  auto upload = [&](void* dst, const void* src, size_t bytes) {
+    return on_stream ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d->stream) : hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+  };
+  DYN_HIP(upload(d->active_d, act.data(), sizeof(int) * d->R));
+  DYN_HIP(upload(d->t0_d, tstep.data(), sizeof(long long) * d->R));
+  return 0;
+}
+
+// Staging of a call's arrays.  In: a host array is copied to `stage` on the stream and p repointed there; a device array (on_device)
+// or a null one stays.  dyn_dst: where the kernel writes an output; out: the staged output copied back to the host on the stream.
+template <class T>
+static int dyn_stage_in(orl_dynamics* d, const T*& p, T* stage, size_t count, int on_device) {
+  if (on_device || !p) return 0;
+  DYN_HIP(hipMemcpyAsync(stage, p, sizeof(T) * count, hipMemcpyHostToDevice, d->stream));
+  p = stage;
+  return 0;
+}
+template <class T>
+static T* dyn_dst(T* user, T* stage, int on_device) { return user && !on_device ? stage : user; }
+template <class T>
+static int dyn_stage_out(orl_dynamics* d, T* user, const T* stage, size_t count, int on_device) {
+  if (on_device || !user) return 0;
+  DYN_HIP(hipMemcpyAsync(user, stage, sizeof(T) * count, hipMemcpyDeviceToHost, d->stream));
+  return 0;
 }
 
 extern "C" {
@@ -938,22 +993,14 @@ int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out) {
   d->P = dyn_layout(d);
   const long R = d->R, B = d->B, K = d->K;
   d->nblk = (int)((d->P + 1023) / 1024);
-  int hmax = 4;
-  for (int l = 1; l <= d->L; ++l) hmax = std::max(hmax, d->pitch[l]);
-  hmax = std::max(hmax, d->pitch[d->L + 1]);
   bool bad = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess;
   if (c.external_arena) d->params = c.external_arena;
   else bad = bad || dyn_alloc_t(d, &d->params, R * d->P);
   bad = bad || dyn_alloc_t(d, &d->adam_m, R * d->P) || dyn_alloc_t(d, &d->adam_v, R * d->P) ||
         dyn_alloc_t(d, &d->grads, R * d->P) || dyn_alloc_t(d, &d->elites_d, R * K) || dyn_alloc_t(d, &d->mu, R * d->in) ||
-        dyn_alloc_t(d, &d->sd, R * d->in) || dyn_alloc_t(d, &d->X0, R * K * B * d->pitch[0]) || dyn_alloc_t(d, &d->T, R * K * B * d->D) ||
-        dyn_alloc_t(d, &d->OUT, R * K * B * d->pitch[d->L + 1]) || dyn_alloc_t(d, &d->dOUT, R * K * B * d->pitch[d->L + 1]) ||
-        dyn_alloc_t(d, &d->dA, R * K * B * hmax) || dyn_alloc_t(d, &d->dB, R * K * B * hmax) ||
-        dyn_alloc_t(d, &d->lterm, R * K * B * d->D) || dyn_alloc_t(d, &d->gmax, R * K * B * d->D) ||
-        dyn_alloc_t(d, &d->gmin, R * K * B * d->D) || dyn_alloc_t(d, &d->decay_part, R * d->nblk) || dyn_alloc_t(d, &d->nll, R) ||
-        dyn_alloc_t(d, &d->loss_sum, R) || dyn_alloc_t(d, &d->active_d, R) || dyn_alloc_t(d, &d->t0_d, R);
-  for (int l = 0; l < d->L && !bad; ++l)
-    bad = dyn_alloc_t(d, &d->H[l], R * K * B * d->pitch[l + 1]) || dyn_alloc_t(d, &d->Z[l], R * K * B * d->pitch[l + 1]);
+        dyn_alloc_t(d, &d->sd, R * d->in) || dyn_ws_alloc(d, d->lw, B, false) || dyn_alloc_t(d, &d->T, R * K * B * d->D) ||
+        dyn_alloc_t(d, &d->decay_part, R * d->nblk) || dyn_alloc_t(d, &d->nll, R) || dyn_alloc_t(d, &d->loss_sum, R) ||
+        dyn_alloc_t(d, &d->active_d, R) || dyn_alloc_t(d, &d->t0_d, R);
   if (bad) {
     const std::string msg = orl_last_error();
     orl_dyn_destroy(d);
@@ -1038,20 +1085,27 @@ int orl_dyn_get(orl_dynamics* d, int run, float* host, int64_t n) {
   return 0;
 }
 
-int orl_dyn_adam_get(orl_dynamics* d, int run, float* m, float* v, int64_t n, int64_t* step) {
-  if (dyn_check_run(d, run, n, "orl_dyn_adam_get")) return -1;
+// one run's Adam moments to (get) or from (set) host arrays, either of which may be null
+static int dyn_adam_xfer(orl_dynamics* d, int run, float* dev_m, float* dev_v, const float* m, const float* v, bool get) {
   DYN_HIP(hipStreamSynchronize(d->stream));
-  if (m) DYN_HIP(hipMemcpy(m, d->adam_m + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
-  if (v) DYN_HIP(hipMemcpy(v, d->adam_v + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  const float* host[2] = {m, v};
+  float* dev[2] = {dev_m + (long)run * d->P, dev_v + (long)run * d->P};
+  for (int i = 0; i < 2; ++i) {
+    if (!host[i]) continue;
+    if (get) DYN_HIP(hipMemcpy(const_cast<float*>(host[i]), dev[i], sizeof(float) * d->P, hipMemcpyDeviceToHost));
+    else DYN_HIP(hipMemcpy(dev[i], host[i], sizeof(float) * d->P, hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
+int orl_dyn_adam_get(orl_dynamics* d, int run, float* m, float* v, int64_t n, int64_t* step) {
+  if (dyn_check_run(d, run, n, "orl_dyn_adam_get") || dyn_adam_xfer(d, run, d->adam_m, d->adam_v, m, v, true)) return -1;
   if (step) *step = d->tstep[run];
   return 0;
 }
 
 int orl_dyn_adam_set(orl_dynamics* d, int run, const float* m, const float* v, int64_t n, int64_t step) {
-  if (dyn_check_run(d, run, n, "orl_dyn_adam_set")) return -1;
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  if (m) DYN_HIP(hipMemcpy(d->adam_m + (long)run * d->P, m, sizeof(float) * d->P, hipMemcpyHostToDevice));
-  if (v) DYN_HIP(hipMemcpy(d->adam_v + (long)run * d->P, v, sizeof(float) * d->P, hipMemcpyHostToDevice));
+  if (dyn_check_run(d, run, n, "orl_dyn_adam_set") || dyn_adam_xfer(d, run, d->adam_m, d->adam_v, m, v, false)) return -1;
   d->tstep[run] = step;
   return 0;
 }
@@ -1117,64 +1171,36 @@ static int dyn_upload_idx(orl_dynamics* d, const int64_t* idx, long count) {
 int orl_dyn_learn_epoch(orl_dynamics* d, const int64_t* idx, int64_t train_size, const int32_t* active, float* loss_out) {
   if (!d || !idx || train_size < 1) return fail("orl_dyn_learn_epoch: bad arguments");
   if (!d->n_data) return fail("orl_dyn_learn_epoch: no data loaded (orl_dyn_load_data)");
-  const int R = d->R, K = d->K, B = d->B, L = d->L, D = d->D;
+  const int R = d->R, K = d->K, B = d->B, D = d->D;
+  const DynWs& w = d->lw;
   if (dyn_upload_idx(d, idx, (long)R * K * train_size)) return -1;
-  std::vector<int> act(R, 1);
-  if (active) for (int r = 0; r < R; ++r) act[r] = active[r] ? 1 : 0;
-  std::vector<long long> t0(d->tstep.begin(), d->tstep.end());
-  DYN_HIP(hipMemcpy(d->active_d, act.data(), sizeof(int) * R, hipMemcpyHostToDevice));
-  DYN_HIP(hipMemcpy(d->t0_d, t0.data(), sizeof(long long) * R, hipMemcpyHostToDevice));
+  std::vector<int> act;
+  if (dyn_upload_run_state(d, active, d->tstep, act, false)) return -1;
   DYN_HIP(hipMemsetAsync(d->loss_sum, 0, sizeof(float) * R, d->stream));
   const long nb = (train_size + B - 1) / B;
-  const int p0 = d->pitch[0], po = d->pitch[L + 1];
+  const int p0 = d->pitch[0], po = d->pitch[d->L + 1];
   DynAdamP a = dyn_adam_params(d);
   a.m = d->adam_m; a.v = d->adam_v;
   a.lr = d->c.lr; a.b1 = d->c.adam_beta1; a.b2 = d->c.adam_beta2; a.eps = d->c.adam_eps;
   const long xs1 = (long)B * p0, xs0 = (long)K * xs1;
   for (long b = 0; b < nb; ++b) {
     const int rows = (int)std::min<long>(B, train_size - b * B);
-    hipLaunchKernelGGL(k_dyn_gather, dim3((rows + 255) / 256, K, R), dim3(256), 0, d->stream, (const int*)d->idx_d, (long)K * train_size,
-                       (long)train_size, b * B, rows, (const float*)d->data_in, (const float*)d->data_tg, d->in, D, (const float*)d->mu,
-                       (const float*)d->sd, d->X0, xs0, xs1, p0, d->T, (long)K * B * D, (long)B * D);
-    DYN_LAUNCHED("k_dyn_gather");
-    // forward
-    std::vector<DMat> Xs(L + 1), Zs(L);
-    Xs[0] = {d->X0, xs0, xs1, p0};
-    for (int l = 0; l < L; ++l) {
-      const int pt = d->pitch[l + 1];
-      Xs[l + 1] = {d->H[l], (long)K * B * pt, (long)B * pt, pt};
-      Zs[l] = {d->Z[l], (long)K * B * pt, (long)B * pt, pt};
-      if (dyn_fwd(d, Xs[l], rows, l, Xs[l + 1], d->Z[l], true)) return -1;
-    }
-    const DMat Out = {d->OUT, (long)K * B * po, (long)B * po, po}, dOut = {d->dOUT, (long)K * B * po, (long)B * po, po};
-    if (dyn_fwd(d, Xs[L], rows, L, Out, nullptr, false)) return -1;
+    DYN_LAUNCH(k_dyn_gather, dim3((rows + 255) / 256, K, R), dim3(256), 0, (const int*)d->idx_d, (long)K * train_size,
+                (long)train_size, b * B, rows, (const float*)d->data_in, (const float*)d->data_tg, d->in, D, (const float*)d->mu,
+                (const float*)d->sd, w.X, xs0, xs1, p0, d->T, (long)K * B * D, (long)B * D);
+    if (dyn_forward(d, w, rows, true)) return -1;
     // Gaussian NLL head
     const long ne = (long)K * rows * D;
-    hipLaunchKernelGGL(k_dyn_nll, dim3((unsigned)((ne + 255) / 256), R), dim3(256), 0, d->stream, (const float*)d->OUT, d->dOUT, po,
-                       (const float*)d->T, d->lterm, d->gmax, d->gmin, (const float*)d->params, d->P, d->off_max, d->off_min, K, B, rows, D);
-    DYN_LAUNCHED("k_dyn_nll");
-    hipLaunchKernelGGL(k_dyn_nll_reduce, dim3(R), dim3(1024), 0, d->stream, (const float*)d->lterm, (const float*)d->gmax,
-                       (const float*)d->gmin, K, B, rows, D, (const float*)d->params, d->grads, d->P, d->off_max, d->off_min,
-                       d->c.logvar_loss_coef, d->nll);
-    DYN_LAUNCHED("k_dyn_nll_reduce");
-    // backward, top down
-    DMat dY = dOut;
-    float* dbuf[2] = {d->dA, d->dB};
-    for (int l = L; l >= 0; --l) {
-      if (dyn_wgrad(d, dY, Xs[l], rows, l)) return -1;
-      if (l > 0) {
-        const int pt = d->pitch[l];
-        const DMat dX = {dbuf[l & 1], (long)K * B * pt, (long)B * pt, pt};
-        if (dyn_dgrad(d, dY, rows, l, dX, Zs[l - 1])) return -1;
-        dY = dX;
-      }
-    }
+    DYN_LAUNCH(k_dyn_nll, dim3((unsigned)((ne + 255) / 256), R), dim3(256), 0, (const float*)w.OUT, w.dOUT, po,
+                (const float*)d->T, w.lterm, w.gmax, w.gmin, (const float*)d->params, d->P, d->off_max, d->off_min, K, B, rows, D);
+    DYN_LAUNCH(k_dyn_nll_reduce, dim3(R), dim3(1024), 0, (const float*)w.lterm, (const float*)w.gmax,
+                (const float*)w.gmin, K, B, rows, D, (const float*)d->params, d->grads, d->P, d->off_max, d->off_min,
+                d->c.logvar_loss_coef, d->nll);
+    if (dyn_backward(d, w, rows)) return -1;
     a.batch = (int)b;
-    hipLaunchKernelGGL(k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, d->stream, a);
-    DYN_LAUNCHED("k_dyn_adam");
-    hipLaunchKernelGGL(k_dyn_loss, dim3(R), dim3(256), 0, d->stream, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
-                       (const int*)d->active_d, d->loss_sum);
-    DYN_LAUNCHED("k_dyn_loss");
+    DYN_LAUNCH(k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, a);
+    DYN_LAUNCH(k_dyn_loss, dim3(R), dim3(256), 0, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
+                (const int*)d->active_d, d->loss_sum);
   }
   std::vector<float> ls(R);
   DYN_HIP(hipMemcpyAsync(ls.data(), d->loss_sum, sizeof(float) * R, hipMemcpyDeviceToHost, d->stream));
@@ -1192,15 +1218,14 @@ int orl_dyn_validate(orl_dynamics* d, const int64_t* idx, int64_t H, float* mse_
   const int R = d->R, K = d->K, D = d->D;
   if (dyn_grow_step(d, H)) return -1;
   if (dyn_upload_idx(d, idx, (long)R * H)) return -1;
-  hipLaunchKernelGGL(k_dyn_gather, dim3((unsigned)((H + 255) / 256), 1, R), dim3(256), 0, d->stream, (const int*)d->idx_d, (long)H, 0L, 0L,
-                     (int)H, (const float*)d->data_in, (const float*)d->data_tg, d->in, D, (const float*)d->mu, (const float*)d->sd, d->sX,
-                     (long)H * d->pitch[0], 0L, d->pitch[0], d->sT, (long)H * D, 0L);
-  DYN_LAUNCHED("k_dyn_gather");
-  if (dyn_forward_shared(d, H)) return -1;
+  DYN_LAUNCH(k_dyn_gather, dim3((unsigned)((H + 255) / 256), 1, R), dim3(256), 0, (const int*)d->idx_d, (long)H, 0L, 0L,
+              (int)H, (const float*)d->data_in, (const float*)d->data_tg, d->in, D, (const float*)d->mu, (const float*)d->sd, d->sw.X,
+              (long)H * d->pitch[0], 0L, d->pitch[0], d->sT, (long)H * D, 0L);
+  d->sw.rows = H;
+  if (dyn_forward(d, d->sw, (int)H, false)) return -1;
   float* mse = d->sNoise;      // R * K floats of the noise staging (R * K * H * D)
-  hipLaunchKernelGGL(k_dyn_val_mse, dim3(K, R), dim3(256), 0, d->stream, (const float*)d->sOUT, d->pitch[d->L + 1], (const float*)d->sT,
-                     (int)H, D, K, mse);
-  DYN_LAUNCHED("k_dyn_val_mse");
+  DYN_LAUNCH(k_dyn_val_mse, dim3(K, R), dim3(256), 0, (const float*)d->sw.OUT, d->pitch[d->L + 1], (const float*)d->sT,
+              (int)H, D, K, mse);
   DYN_HIP(hipMemcpyAsync(mse_out, mse, sizeof(float) * R * K, hipMemcpyDeviceToHost, d->stream));
   DYN_HIP(hipStreamSynchronize(d->stream));
   return 0;
@@ -1231,6 +1256,14 @@ int orl_dyn_load_save(orl_dynamics* d, int run) {
   return 0;
 }
 
+// step() / sample_next(): scaler(concat(obs, act)) into the step workspace and the ensemble's forward over its n rows
+static int dyn_step_forward(orl_dynamics* d, const float* obs, const float* act, long n) {
+  DYN_LAUNCH(k_dyn_step_input, dim3((unsigned)((n + 255) / 256), d->R), dim3(256), 0, obs, act, n, d->od, d->ad,
+              (const float*)d->mu, (const float*)d->sd, d->sw.X, d->pitch[0]);
+  d->sw.rows = n;
+  return dyn_forward(d, d->sw, (int)n, false);
+}
+
 int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n, int on_device, const float* noise, const int64_t* model_idx,
                  int mode, float coef, float* next_obs, float* reward, float* raw_reward, float* penalty, int32_t* midx_out) {
   if (!d || !obs || !act || n < 1 || !next_obs || !reward || !raw_reward || !penalty) return fail("orl_dyn_step: bad arguments");
@@ -1238,64 +1271,35 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
   if (mode < 0 || mode > 2) return fail("orl_dyn_step: unknown penalty mode");
   const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
   if (dyn_grow_step(d, n)) return -1;
-  const hipMemcpyKind h2d = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const float* obs_d = obs;
-  const float* act_d = act;
-  if (!on_device) {
-    DYN_HIP(hipMemcpyAsync(d->sObs, obs, sizeof(float) * R * n * od, h2d, d->stream));
-    DYN_HIP(hipMemcpyAsync(d->sAct, act, sizeof(float) * R * n * ad, h2d, d->stream));
-    obs_d = d->sObs; act_d = d->sAct;
-  }
-  const float* noise_d = nullptr;
-  const int* midx_d = nullptr;
-  if (noise) {
-    if (on_device) noise_d = noise;
-    else {
-      DYN_HIP(hipMemcpyAsync(d->sNoise, noise, sizeof(float) * R * K * n * D, h2d, d->stream));
-      noise_d = d->sNoise;
-    }
-  }
+  if (dyn_stage_in(d, obs, d->sObs, (size_t)R * n * od, on_device) || dyn_stage_in(d, act, d->sAct, (size_t)R * n * ad, on_device) ||
+      dyn_stage_in(d, noise, d->sNoise, (size_t)R * K * n * D, on_device))
+    return -1;
   std::vector<int> mi;
   if (model_idx) {
     if (on_device) return fail("orl_dyn_step: teacher-forced model indices are host arrays");
-    mi.resize((size_t)R * n);
-    for (long i = 0; i < (long)R * n; ++i) {
-      if (model_idx[i] < 0 || model_idx[i] >= K) return fail("orl_dyn_step: model index out of range");
-      mi[i] = (int)model_idx[i];
-    }
-    DYN_HIP(hipMemcpyAsync(d->sMidx, mi.data(), sizeof(int) * mi.size(), hipMemcpyHostToDevice, d->stream));
-    midx_d = d->sMidx;
+    if (dyn_upload_midx(d, model_idx, (long)R * n, mi, d->sMidx, "orl_dyn_step")) return -1;
   }
-  hipLaunchKernelGGL(k_dyn_step_input, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, d->stream, obs_d, act_d, (long)n, od, ad,
-                     (const float*)d->mu, (const float*)d->sd, d->sX, d->pitch[0]);
-  DYN_LAUNCHED("k_dyn_step_input");
-  if (dyn_forward_shared(d, n)) return -1;
+  if (dyn_step_forward(d, obs, act, n)) return -1;
   DynHeadP h;
   memset(&h, 0, sizeof(h));
-  h.OUT = d->sOUT; h.op = d->pitch[d->L + 1];
-  h.obs = obs_d; h.n = n; h.od = od; h.D = D; h.K = K;
+  h.OUT = d->sw.OUT; h.op = d->pitch[d->L + 1];
+  h.obs = obs; h.n = n; h.od = od; h.D = D; h.K = K;
   h.params = d->params; h.P = d->P; h.off_max = d->off_max; h.off_min = d->off_min;
-  h.noise = noise_d; h.midx = midx_d;
+  h.noise = noise; h.midx = model_idx ? d->sMidx : nullptr;
   h.elites = d->elites_d;
-  h.n_elites = (int)d->elites_h[0].size();
-  for (int r = 1; r < R; ++r)
-    if ((int)d->elites_h[r].size() != h.n_elites) return fail("orl_dyn_step: every run needs the same number of elites");
+  if ((h.n_elites = dyn_n_elites(d, "orl_dyn_step")) < 0) return -1;
   h.seed = d->c.seed; h.call = d->step_calls++;
   h.mode = mode; h.coef = coef;
-  h.next_obs = on_device ? next_obs : d->sNext;
-  h.reward = on_device ? reward : d->sRew;
-  h.raw_reward = on_device ? raw_reward : d->sRaw;
-  h.penalty = on_device ? penalty : d->sPen;
-  h.midx_out = midx_out ? (on_device ? (int*)midx_out : d->sMidxOut) : nullptr;
-  hipLaunchKernelGGL(k_dyn_head, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, d->stream, h);
-  DYN_LAUNCHED("k_dyn_head");
-  if (!on_device) {
-    DYN_HIP(hipMemcpyAsync(next_obs, d->sNext, sizeof(float) * R * n * od, hipMemcpyDeviceToHost, d->stream));
-    DYN_HIP(hipMemcpyAsync(reward, d->sRew, sizeof(float) * R * n, hipMemcpyDeviceToHost, d->stream));
-    DYN_HIP(hipMemcpyAsync(raw_reward, d->sRaw, sizeof(float) * R * n, hipMemcpyDeviceToHost, d->stream));
-    DYN_HIP(hipMemcpyAsync(penalty, d->sPen, sizeof(float) * R * n, hipMemcpyDeviceToHost, d->stream));
-    if (midx_out) DYN_HIP(hipMemcpyAsync(midx_out, d->sMidxOut, sizeof(int) * R * n, hipMemcpyDeviceToHost, d->stream));
-  }
+  h.next_obs = dyn_dst(next_obs, d->sNext, on_device);
+  h.reward = dyn_dst(reward, d->sRew, on_device);
+  h.raw_reward = dyn_dst(raw_reward, d->sRaw, on_device);
+  h.penalty = dyn_dst(penalty, d->sPen, on_device);
+  h.midx_out = dyn_dst((int*)midx_out, d->sMidxOut, on_device);
+  DYN_LAUNCH(k_dyn_head, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, h);
+  if (dyn_stage_out(d, next_obs, d->sNext, (size_t)R * n * od, on_device) || dyn_stage_out(d, reward, d->sRew, (size_t)R * n, on_device) ||
+      dyn_stage_out(d, raw_reward, d->sRaw, (size_t)R * n, on_device) || dyn_stage_out(d, penalty, d->sPen, (size_t)R * n, on_device) ||
+      dyn_stage_out(d, (int*)midx_out, d->sMidxOut, (size_t)R * n, on_device))
+    return -1;
   DYN_HIP(hipStreamSynchronize(d->stream));
   return 0;
 }
@@ -1306,48 +1310,34 @@ int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int6
   if (!d || !obs || !act || n < 1 || !next_obs) return fail("orl_dynsample_next: bad arguments");
   if (num_samples < 1) return fail("orl_dynsample_next: num_samples must be >= 1");
   const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
-  const int E = (int)d->elites_h[0].size();
-  for (int r = 1; r < R; ++r)
-    if ((int)d->elites_h[r].size() != E) return fail("orl_dynsample_next: every run needs the same number of elites");
+  const int E = dyn_n_elites(d, "orl_dynsample_next");
+  if (E < 0) return -1;
   if (E < 2) return fail("orl_dynsample_next: needs at least 2 elites (the standard deviation over one elite is NaN)");
   const long S = num_samples, rows = S * E * n;
   if (rows * ((D + 3) / 4) > (1L << 38) || n > 0x7fffffffL) return fail("orl_dynsample_next: too many rows");
   if (dyn_grow_step(d, n)) return -1;
   if (!on_device && rows > d->m_cap) {
     DYN_HIP(hipStreamSynchronize(d->stream));
-    dyn_free(d, d->mNoise); dyn_free(d, d->mNext);
-    d->mNoise = d->mNext = nullptr; d->m_cap = 0;
+    dyn_release(d, &d->mNoise, &d->mNext);
+    d->m_cap = 0;
     if (dyn_alloc_t(d, &d->mNoise, (size_t)R * rows * D) || dyn_alloc_t(d, &d->mNext, (size_t)R * rows * od)) return -1;
     d->m_cap = rows;
   }
-  const float* obs_d = obs;
-  const float* act_d = act;
-  const float* noise_d = noise;
-  if (!on_device) {
-    DYN_HIP(hipMemcpyAsync(d->sObs, obs, sizeof(float) * R * n * od, hipMemcpyHostToDevice, d->stream));
-    DYN_HIP(hipMemcpyAsync(d->sAct, act, sizeof(float) * R * n * ad, hipMemcpyHostToDevice, d->stream));
-    obs_d = d->sObs; act_d = d->sAct;
-    if (noise) {
-      DYN_HIP(hipMemcpyAsync(d->mNoise, noise, sizeof(float) * R * rows * D, hipMemcpyHostToDevice, d->stream));
-      noise_d = d->mNoise;
-    }
-  }
-  hipLaunchKernelGGL(k_dyn_step_input, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, d->stream, obs_d, act_d, (long)n, od, ad,
-                     (const float*)d->mu, (const float*)d->sd, d->sX, d->pitch[0]);
-  DYN_LAUNCHED("k_dyn_step_input");
-  if (dyn_forward_shared(d, n)) return -1;
+  if (dyn_stage_in(d, obs, d->sObs, (size_t)R * n * od, on_device) || dyn_stage_in(d, act, d->sAct, (size_t)R * n * ad, on_device) ||
+      dyn_stage_in(d, noise, d->mNoise, (size_t)R * rows * D, on_device))
+    return -1;
+  if (dyn_step_forward(d, obs, act, n)) return -1;
   DynSampleNextP p;
   memset(&p, 0, sizeof(p));
-  p.OUT = d->sOUT; p.op = d->pitch[d->L + 1];
-  p.obs = obs_d; p.n = n; p.od = od; p.D = D; p.K = K; p.S = (int)S; p.E = E;
+  p.OUT = d->sw.OUT; p.op = d->pitch[d->L + 1];
+  p.obs = obs; p.n = n; p.od = od; p.D = D; p.K = K; p.S = (int)S; p.E = E;
   p.params = d->params; p.P = d->P; p.off_max = d->off_max; p.off_min = d->off_min;
-  p.noise = noise_d; p.elites = d->elites_d;
+  p.noise = noise; p.elites = d->elites_d;
   p.seed = d->c.seed ^ 0xD1B54A32D192ED03ull; p.call = d->sample_calls++;
-  p.next_obs = on_device ? next_obs : d->mNext;
+  p.next_obs = dyn_dst(next_obs, d->mNext, on_device);
   const long nt = rows * ((D + 3) / 4);
-  hipLaunchKernelGGL(k_dyn_sample_next, dim3((unsigned)((nt + 255) / 256), R), dim3(256), 0, d->stream, p);
-  DYN_LAUNCHED("k_dyn_sample_next");
-  if (!on_device) DYN_HIP(hipMemcpyAsync(next_obs, d->mNext, sizeof(float) * R * rows * od, hipMemcpyDeviceToHost, d->stream));
+  DYN_LAUNCH(k_dyn_sample_next, dim3((unsigned)((nt + 255) / 256), R), dim3(256), 0, p);
+  if (dyn_stage_out(d, next_obs, d->mNext, (size_t)R * rows * od, on_device)) return -1;
   DYN_HIP(hipStreamSynchronize(d->stream));
   return 0;
 }
@@ -1366,7 +1356,7 @@ int orl_dynadv_configure(orl_dynamics* d, float lr, float beta1, float beta2, fl
   if (rollout_rows < 1 || sl_rows < 1) return fail("orl_dynadv_configure: need rollout_rows >= 1 and sl_rows >= 1");
   if (!d->c.with_reward) return fail("orl_dynadv_configure: needs with_reward (the sample's last dim is the reward)");
   DYN_HIP(hipStreamSynchronize(d->stream));
-  const long R = d->R, K = d->K, D = d->D, L = d->L;
+  const long R = d->R, K = d->K, D = d->D;
   d->adv_lr = lr; d->adv_b1 = beta1; d->adv_b2 = beta2; d->adv_eps = eps; d->adv_weight = adv_weight;
   if (!d->adv_m) {
     if (dyn_alloc_t(d, &d->adv_m, R * d->P) || dyn_alloc_t(d, &d->adv_v, R * d->P)) return -1;
@@ -1374,31 +1364,19 @@ int orl_dynadv_configure(orl_dynamics* d, float lr, float beta1, float beta2, fl
   }
   if (d->adv_on && d->aBa == rollout_rows && d->aBs == sl_rows) return 0;
   d->adv_pending = false;
-  float** fs[] = {&d->aX, &d->aT, &d->aOUT, &d->adOUT, &d->adA, &d->adB, &d->aLterm, &d->aGmax, &d->aGmin, &d->aS, &d->aObs, &d->aAdv,
-                  &d->aAdvm, &d->aMetrics, &d->aInObs, &d->aInAct, &d->aSlObs, &d->aSlAct, &d->aSlNext, &d->aSlRew, &d->aNoise, &d->aNext,
-                  &d->aRew};
-  for (float** f : fs) { dyn_free(d, *f); *f = nullptr; }
-  for (int l = 0; l < L; ++l) { dyn_free(d, d->aH[l]); dyn_free(d, d->aZ[l]); d->aH[l] = d->aZ[l] = nullptr; }
-  dyn_free(d, d->aRowlp); d->aRowlp = nullptr;
-  dyn_free(d, d->aMidx); dyn_free(d, d->aMidxOut); d->aMidx = d->aMidxOut = nullptr;
+  dyn_ws_release(d, d->aw);
+  dyn_release(d, &d->aT, &d->aS, &d->aObs, &d->aAdv, &d->aAdvm, &d->aMetrics, &d->aRowlp, &d->aInObs, &d->aInAct, &d->aSlObs, &d->aSlAct,
+              &d->aSlNext, &d->aSlRew, &d->aNoise, &d->aNext, &d->aRew, &d->aMidx, &d->aMidxOut);
   d->adv_on = false;
-  const long Ba = rollout_rows, Bs = sl_rows, N = Ba + Bs;
-  int hmax = 4;
-  for (int l = 1; l <= L + 1; ++l) hmax = std::max(hmax, d->pitch[l]);
-  const long po = d->pitch[L + 1];
-  bool bad = dyn_alloc_t(d, &d->aX, R * N * d->pitch[0]) || dyn_alloc_t(d, &d->aT, R * Bs * D) || dyn_alloc_t(d, &d->aOUT, R * K * N * po) ||
-             dyn_alloc_t(d, &d->adOUT, R * K * N * po) || dyn_alloc_t(d, &d->adA, R * K * N * hmax) ||
-             dyn_alloc_t(d, &d->adB, R * K * N * hmax) || dyn_alloc_t(d, &d->aLterm, R * K * N * D) ||
-             dyn_alloc_t(d, &d->aGmax, R * K * N * D) || dyn_alloc_t(d, &d->aGmin, R * K * N * D) || dyn_alloc_t(d, &d->aS, R * Ba * D) ||
-             dyn_alloc_t(d, &d->aObs, R * Ba * d->od) || dyn_alloc_t(d, &d->aAdv, R * Ba) || dyn_alloc_t(d, &d->aAdvm, R * 2) ||
-             dyn_alloc_t(d, &d->aMetrics, R * 4) || dyn_alloc_t(d, &d->aRowlp, R * Ba) || dyn_alloc_t(d, &d->aInObs, R * Ba * d->od) ||
-             dyn_alloc_t(d, &d->aInAct, R * Ba * d->ad) || dyn_alloc_t(d, &d->aSlObs, R * Bs * d->od) ||
-             dyn_alloc_t(d, &d->aSlAct, R * Bs * d->ad) || dyn_alloc_t(d, &d->aSlNext, R * Bs * d->od) ||
-             dyn_alloc_t(d, &d->aSlRew, R * Bs) || dyn_alloc_t(d, &d->aNoise, R * K * Ba * D) || dyn_alloc_t(d, &d->aNext, R * Ba * d->od) ||
-             dyn_alloc_t(d, &d->aRew, R * Ba) || dyn_alloc_t(d, &d->aMidx, R * Ba) || dyn_alloc_t(d, &d->aMidxOut, R * Ba);
-  for (int l = 0; l < L && !bad; ++l)
-    bad = dyn_alloc_t(d, &d->aH[l], R * K * N * d->pitch[l + 1]) || dyn_alloc_t(d, &d->aZ[l], R * K * N * d->pitch[l + 1]);
-  if (bad) return -1;
+  const long Ba = rollout_rows, Bs = sl_rows;
+  if (dyn_ws_alloc(d, d->aw, Ba + Bs, true) || dyn_alloc_t(d, &d->aT, R * Bs * D) || dyn_alloc_t(d, &d->aS, R * Ba * D) ||
+      dyn_alloc_t(d, &d->aObs, R * Ba * d->od) || dyn_alloc_t(d, &d->aAdv, R * Ba) || dyn_alloc_t(d, &d->aAdvm, R * 2) ||
+      dyn_alloc_t(d, &d->aMetrics, R * 4) || dyn_alloc_t(d, &d->aRowlp, R * Ba) || dyn_alloc_t(d, &d->aInObs, R * Ba * d->od) ||
+      dyn_alloc_t(d, &d->aInAct, R * Ba * d->ad) || dyn_alloc_t(d, &d->aSlObs, R * Bs * d->od) ||
+      dyn_alloc_t(d, &d->aSlAct, R * Bs * d->ad) || dyn_alloc_t(d, &d->aSlNext, R * Bs * d->od) ||
+      dyn_alloc_t(d, &d->aSlRew, R * Bs) || dyn_alloc_t(d, &d->aNoise, R * K * Ba * D) || dyn_alloc_t(d, &d->aNext, R * Ba * d->od) ||
+      dyn_alloc_t(d, &d->aRew, R * Ba) || dyn_alloc_t(d, &d->aMidx, R * Ba) || dyn_alloc_t(d, &d->aMidxOut, R * Ba))
+    return -1;
   d->aBa = rollout_rows; d->aBs = sl_rows;
   d->adv_on = true;
   return 0;
@@ -1410,74 +1388,39 @@ int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, cons
   if (!d || !obs || !act || !sl_obs || !sl_act || !sl_next_obs || !sl_rew || !next_obs || !reward)
     return fail("orl_dynadv_forward: bad arguments");
   if (!d->adv_on) return fail("orl_dynadv_forward: orl_dynadv_configure first");
-  const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad, L = d->L;
-  const long Ba = d->aBa, Bs = d->aBs, N = Ba + Bs;
+  const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
+  const size_t Ba = d->aBa, Bs = d->aBs, N = Ba + Bs;
+  const DynWs& w = d->aw;
   d->adv_pending = false;
-  if (!on_device) {
-    const hipMemcpyKind h2d = hipMemcpyHostToDevice;
-    DYN_HIP(hipMemcpyAsync(d->aInObs, obs, sizeof(float) * R * Ba * od, h2d, d->stream));
-    DYN_HIP(hipMemcpyAsync(d->aInAct, act, sizeof(float) * R * Ba * ad, h2d, d->stream));
-    DYN_HIP(hipMemcpyAsync(d->aSlObs, sl_obs, sizeof(float) * R * Bs * od, h2d, d->stream));
-    DYN_HIP(hipMemcpyAsync(d->aSlAct, sl_act, sizeof(float) * R * Bs * ad, h2d, d->stream));
-    DYN_HIP(hipMemcpyAsync(d->aSlNext, sl_next_obs, sizeof(float) * R * Bs * od, h2d, d->stream));
-    DYN_HIP(hipMemcpyAsync(d->aSlRew, sl_rew, sizeof(float) * R * Bs, h2d, d->stream));
-    obs = d->aInObs; act = d->aInAct; sl_obs = d->aSlObs; sl_act = d->aSlAct; sl_next_obs = d->aSlNext; sl_rew = d->aSlRew;
-  }
-  const float* noise_d = nullptr;
-  const int* midx_d = nullptr;
-  if (noise) {
-    if (on_device) noise_d = noise;
-    else {
-      DYN_HIP(hipMemcpyAsync(d->aNoise, noise, sizeof(float) * R * K * Ba * D, hipMemcpyHostToDevice, d->stream));
-      noise_d = d->aNoise;
-    }
-  }
+  if (dyn_stage_in(d, obs, d->aInObs, R * Ba * od, on_device) || dyn_stage_in(d, act, d->aInAct, R * Ba * ad, on_device) ||
+      dyn_stage_in(d, sl_obs, d->aSlObs, R * Bs * od, on_device) || dyn_stage_in(d, sl_act, d->aSlAct, R * Bs * ad, on_device) ||
+      dyn_stage_in(d, sl_next_obs, d->aSlNext, R * Bs * od, on_device) || dyn_stage_in(d, sl_rew, d->aSlRew, R * Bs, on_device) ||
+      dyn_stage_in(d, noise, d->aNoise, R * K * Ba * D, on_device))
+    return -1;
   std::vector<int> mi;
-  if (model_idx) {
-    mi.resize((size_t)R * Ba);
-    for (long i = 0; i < (long)R * Ba; ++i) {
-      if (model_idx[i] < 0 || model_idx[i] >= K) return fail("orl_dynadv_forward: model index out of range");
-      mi[i] = (int)model_idx[i];
-    }
-    DYN_HIP(hipMemcpyAsync(d->aMidx, mi.data(), sizeof(int) * mi.size(), hipMemcpyHostToDevice, d->stream));
-    midx_d = d->aMidx;
-  }
-  const int p0 = d->pitch[0], po = d->pitch[L + 1];
-  hipLaunchKernelGGL(k_dyn_adv_input, dim3((unsigned)((N + 255) / 256), R), dim3(256), 0, d->stream, obs, act, sl_obs, sl_act, sl_next_obs,
-                     sl_rew, (int)Ba, (int)Bs, od, ad, (const float*)d->mu, (const float*)d->sd, d->aX, p0, d->aT, D, d->aObs);
-  DYN_LAUNCHED("k_dyn_adv_input");
-  DMat X = {d->aX, N * p0, 0, p0};
-  for (int l = 0; l < L; ++l) {
-    const int pt = d->pitch[l + 1];
-    const DMat Y = {d->aH[l], (long)K * N * pt, N * pt, pt};
-    if (dyn_fwd(d, X, (int)N, l, Y, d->aZ[l], true)) return -1;
-    X = Y;
-  }
-  const DMat Out = {d->aOUT, (long)K * N * po, N * po, po};
-  if (dyn_fwd(d, X, (int)N, L, Out, nullptr, false)) return -1;
+  if (model_idx && dyn_upload_midx(d, model_idx, (long)(R * Ba), mi, d->aMidx, "orl_dynadv_forward")) return -1;
+  const int p0 = d->pitch[0], po = d->pitch[d->L + 1];
+  DYN_LAUNCH(k_dyn_adv_input, dim3((unsigned)((N + 255) / 256), R), dim3(256), 0, obs, act, sl_obs, sl_act, sl_next_obs,
+              sl_rew, (int)Ba, (int)Bs, od, ad, (const float*)d->mu, (const float*)d->sd, w.X, p0, d->aT, D, d->aObs);
+  if (dyn_forward(d, w, (int)N, true)) return -1;
   DynAdvSampleP s;
   memset(&s, 0, sizeof(s));
-  s.OUT = d->aOUT; s.op = po;
+  s.OUT = w.OUT; s.op = po;
   s.obs = d->aObs; s.Ba = (int)Ba; s.N = (int)N; s.od = od; s.D = D; s.K = K;
   s.params = d->params; s.P = d->P; s.off_max = d->off_max; s.off_min = d->off_min;
-  s.noise = noise_d; s.midx = midx_d;
+  s.noise = noise; s.midx = model_idx ? d->aMidx : nullptr;
   s.elites = d->elites_d;
-  s.n_elites = (int)d->elites_h[0].size();
-  for (int r = 1; r < R; ++r)
-    if ((int)d->elites_h[r].size() != s.n_elites) return fail("orl_dynadv_forward: every run needs the same number of elites");
+  if ((s.n_elites = dyn_n_elites(d, "orl_dynadv_forward")) < 0) return -1;
   s.seed = d->c.seed ^ 0x9E3779B97F4A7C15ull; s.call = d->adv_calls++;
-  s.next_obs = on_device ? next_obs : d->aNext;
-  s.reward = on_device ? reward : d->aRew;
+  s.next_obs = dyn_dst(next_obs, d->aNext, on_device);
+  s.reward = dyn_dst(reward, d->aRew, on_device);
   s.S = d->aS;
-  s.midx_out = midx_out ? (on_device ? (int*)midx_out : d->aMidxOut) : nullptr;
+  s.midx_out = dyn_dst((int*)midx_out, d->aMidxOut, on_device);
   const long ns = Ba * ((D + 3) / 4);
-  hipLaunchKernelGGL(k_dyn_adv_sample, dim3((unsigned)((ns + 255) / 256), R), dim3(256), 0, d->stream, s);
-  DYN_LAUNCHED("k_dyn_adv_sample");
-  if (!on_device) {
-    DYN_HIP(hipMemcpyAsync(next_obs, d->aNext, sizeof(float) * R * Ba * od, hipMemcpyDeviceToHost, d->stream));
-    DYN_HIP(hipMemcpyAsync(reward, d->aRew, sizeof(float) * R * Ba, hipMemcpyDeviceToHost, d->stream));
-    if (midx_out) DYN_HIP(hipMemcpyAsync(midx_out, d->aMidxOut, sizeof(int) * R * Ba, hipMemcpyDeviceToHost, d->stream));
-  }
+  DYN_LAUNCH(k_dyn_adv_sample, dim3((unsigned)((ns + 255) / 256), R), dim3(256), 0, s);
+  if (dyn_stage_out(d, next_obs, d->aNext, R * Ba * od, on_device) || dyn_stage_out(d, reward, d->aRew, R * Ba, on_device) ||
+      dyn_stage_out(d, (int*)midx_out, d->aMidxOut, R * Ba, on_device))
+    return -1;
   DYN_HIP(hipStreamSynchronize(d->stream));
   d->adv_pending = true;
   return 0;
@@ -1486,68 +1429,38 @@ int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, cons
 int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, const int32_t* active, float* metrics_out) {
   if (!d || !advantage) return fail("orl_dynadv_update: bad arguments");
   if (!d->adv_on || !d->adv_pending) return fail("orl_dynadv_update: no pending forward (orl_dynadv_forward first; one update per forward)");
-  const int R = d->R, K = d->K, D = d->D, L = d->L;
+  const int R = d->R, K = d->K, D = d->D;
   const long Ba = d->aBa, Bs = d->aBs, N = Ba + Bs;
+  const DynWs& w = d->aw;
   d->adv_pending = false;
-  std::vector<int> act(R, 1);
-  if (active) for (int r = 0; r < R; ++r) act[r] = active[r] ? 1 : 0;
-  std::vector<long long> t0(d->adv_tstep.begin(), d->adv_tstep.end());
-  DYN_HIP(hipMemcpyAsync(d->active_d, act.data(), sizeof(int) * R, hipMemcpyHostToDevice, d->stream));
-  DYN_HIP(hipMemcpyAsync(d->t0_d, t0.data(), sizeof(long long) * R, hipMemcpyHostToDevice, d->stream));
-  const float* adv_d = advantage;
-  if (!on_device) {
-    DYN_HIP(hipMemcpyAsync(d->aAdv, advantage, sizeof(float) * R * Ba, hipMemcpyHostToDevice, d->stream));
-    adv_d = d->aAdv;
-  }
-  const int po = d->pitch[L + 1];
+  std::vector<int> act;
+  if (dyn_upload_run_state(d, active, d->adv_tstep, act, true)) return -1;
+  if (dyn_stage_in(d, advantage, d->aAdv, (size_t)R * Ba, on_device)) return -1;
   DynAdvHeadP h;
   memset(&h, 0, sizeof(h));
-  h.OUT = d->aOUT; h.dOUT = d->adOUT; h.op = po;
-  h.obs = d->aObs; h.S = d->aS; h.T = d->aT; h.adv = adv_d;
-  h.lterm = d->aLterm; h.gmax = d->aGmax; h.gmin = d->aGmin; h.rowlp = d->aRowlp;
+  h.OUT = w.OUT; h.dOUT = w.dOUT; h.op = d->pitch[d->L + 1];
+  h.obs = d->aObs; h.S = d->aS; h.T = d->aT; h.adv = advantage;
+  h.lterm = w.lterm; h.gmax = w.gmax; h.gmin = w.gmin; h.rowlp = d->aRowlp;
   h.params = d->params; h.P = d->P; h.off_max = d->off_max; h.off_min = d->off_min;
-  h.elites = d->elites_d; h.n_elites = (int)d->elites_h[0].size();
-  for (int r = 1; r < R; ++r)
-    if ((int)d->elites_h[r].size() != h.n_elites) return fail("orl_dynadv_update: every run needs the same number of elites");
+  h.elites = d->elites_d;
+  if ((h.n_elites = dyn_n_elites(d, "orl_dynadv_update")) < 0) return -1;
   h.K = K; h.D = D; h.od = d->od; h.Ba = (int)Ba; h.Bs = (int)Bs;
   h.adv_weight = d->adv_weight;
   const size_t per_wave = sizeof(double) * ((size_t)K * D + 64);
   h.wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (32 * 1024) / per_wave));
   if (per_wave > 48 * 1024) return fail("orl_dynadv_update: num_ensemble * (obs_dim + 1) is too large for the head's LDS");
-  hipLaunchKernelGGL(k_dyn_adv_head, dim3((unsigned)((N + h.wpb - 1) / h.wpb), R), dim3(64 * h.wpb), per_wave * h.wpb, d->stream, h);
-  DYN_LAUNCHED("k_dyn_adv_head");
-  hipLaunchKernelGGL(k_dyn_adv_reduce, dim3(R), dim3(1024), 0, d->stream, (const float*)d->aLterm, (const float*)d->aGmax,
-                     (const float*)d->aGmin, (const double*)d->aRowlp, adv_d, K, (int)Ba, (int)Bs, D, (const float*)d->params, d->grads,
-                     d->P, d->off_max, d->off_min, 0.001f, d->nll, d->aAdvm);
-  DYN_LAUNCHED("k_dyn_adv_reduce");
-  // ONE backward over the Ba + Bs rows, top down; layer 0's input is shared by the members (member stride 0)
-  std::vector<DMat> Xs(L + 1), Zs(L);
-  Xs[0] = {d->aX, N * d->pitch[0], 0, d->pitch[0]};
-  for (int l = 0; l < L; ++l) {
-    const int pt = d->pitch[l + 1];
-    Xs[l + 1] = {d->aH[l], (long)K * N * pt, N * pt, pt};
-    Zs[l] = {d->aZ[l], (long)K * N * pt, N * pt, pt};
-  }
-  DMat dY = {d->adOUT, (long)K * N * po, N * po, po};
-  float* dbuf[2] = {d->adA, d->adB};
-  for (int l = L; l >= 0; --l) {
-    if (dyn_wgrad(d, dY, Xs[l], (int)N, l)) return -1;
-    if (l > 0) {
-      const int pt = d->pitch[l];
-      const DMat dX = {dbuf[l & 1], (long)K * N * pt, N * pt, pt};
-      if (dyn_dgrad(d, dY, (int)N, l, dX, Zs[l - 1])) return -1;
-      dY = dX;
-    }
-  }
+  DYN_LAUNCH(k_dyn_adv_head, dim3((unsigned)((N + h.wpb - 1) / h.wpb), R), dim3(64 * h.wpb), per_wave * h.wpb, h);
+  DYN_LAUNCH(k_dyn_adv_reduce, dim3(R), dim3(1024), 0, (const float*)w.lterm, (const float*)w.gmax,
+              (const float*)w.gmin, (const double*)d->aRowlp, advantage, K, (int)Ba, (int)Bs, D, (const float*)d->params, d->grads,
+              d->P, d->off_max, d->off_min, 0.001f, d->nll, d->aAdvm);
+  if (dyn_backward(d, w, (int)N)) return -1;      // ONE backward over the Ba + Bs rows
   DynAdamP a = dyn_adam_params(d);
   a.m = d->adv_m; a.v = d->adv_v;
   a.lr = d->adv_lr; a.b1 = d->adv_b1; a.b2 = d->adv_b2; a.eps = d->adv_eps;
   a.batch = 0;
-  hipLaunchKernelGGL(k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, d->stream, a);
-  DYN_LAUNCHED("k_dyn_adam");
-  hipLaunchKernelGGL(k_dyn_adv_metrics, dim3(R), dim3(256), 0, d->stream, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
-                     (const int*)d->active_d, (const float*)d->aAdvm, d->adv_weight, d->aMetrics);
-  DYN_LAUNCHED("k_dyn_adv_metrics");
+  DYN_LAUNCH(k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, a);
+  DYN_LAUNCH(k_dyn_adv_metrics, dim3(R), dim3(256), 0, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
+              (const int*)d->active_d, (const float*)d->aAdvm, d->adv_weight, d->aMetrics);
   std::vector<float> ms((size_t)R * 4);
   DYN_HIP(hipMemcpyAsync(ms.data(), d->aMetrics, sizeof(float) * ms.size(), hipMemcpyDeviceToHost, d->stream));
   DYN_HIP(hipStreamSynchronize(d->stream));
@@ -1560,9 +1473,7 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
 int orl_dynadv_adam_get(orl_dynamics* d, int run, float* m, float* v, int64_t n, int64_t* step) {
   if (dyn_check_run(d, run, n, "orl_dynadv_adam_get")) return -1;
   if (!d->adv_m) return fail("orl_dynadv_adam_get: orl_dynadv_configure first");
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  if (m) DYN_HIP(hipMemcpy(m, d->adv_m + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
-  if (v) DYN_HIP(hipMemcpy(v, d->adv_v + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
+  if (dyn_adam_xfer(d, run, d->adv_m, d->adv_v, m, v, true)) return -1;
   if (step) *step = d->adv_tstep[run];
   return 0;
 }
@@ -1570,9 +1481,7 @@ int orl_dynadv_adam_get(orl_dynamics* d, int run, float* m, float* v, int64_t n,
 int orl_dynadv_adam_set(orl_dynamics* d, int run, const float* m, const float* v, int64_t n, int64_t step) {
   if (dyn_check_run(d, run, n, "orl_dynadv_adam_set")) return -1;
   if (!d->adv_m) return fail("orl_dynadv_adam_set: orl_dynadv_configure first");
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  if (m) DYN_HIP(hipMemcpy(d->adv_m + (long)run * d->P, m, sizeof(float) * d->P, hipMemcpyHostToDevice));
-  if (v) DYN_HIP(hipMemcpy(d->adv_v + (long)run * d->P, v, sizeof(float) * d->P, hipMemcpyHostToDevice));
+  if (dyn_adam_xfer(d, run, d->adv_m, d->adv_v, m, v, false)) return -1;
   d->adv_tstep[run] = step;
   return 0;
 }
