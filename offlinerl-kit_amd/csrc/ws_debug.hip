@@ -2,7 +2,6 @@
 // function on host arrays, every check before the first HIP call.  Host code only.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -16,29 +15,12 @@ int fail(const std::string& msg);      // engine.hip: sets orl_last_error(), ret
 
 namespace {
 
-// Every instantiation of the ws_* kernels; a launch reports its index.
+// Every instantiation of the ws_* kernels = the launchers' own tables (ws_gemm.h: WsTable), in the order of the tap's kinds; a launch reports the
+// row its launcher's selector picked, counted through all six.
 //   ws_fwd<TQ,L0,DG,SY,F32,XS>  ws_fwd3<TQ,SY,XS,L0,DG>  ws_dgrad<W0,STORE,PLAIN> (ws_dgrad32: the exact-fp32 kernel)  ws_dgrad3<W0,PLAIN>
 //   ws_wgrad<MODE> / ws_wgrad32<MODE>  ws_wgrad3p
-static const char* const WS_FLAVOURS[] = {
-    "ws_fwd<1,0,0,1,0,1>", "ws_fwd<0,0,0,1,0,1>", "ws_fwd<1,1,0,1,0,1>", "ws_fwd<0,1,0,1,0,1>", "ws_fwd<0,0,1,1,0,1>", "ws_fwd<1,1,0,0,0,1>",
-    "ws_fwd<1,0,0,0,0,1>", "ws_fwd<1,1,0,0,0,0>", "ws_fwd<0,1,0,1,0,0>",
-    "ws_fwd<1,0,0,1,1,1>", "ws_fwd<0,0,0,1,1,1>", "ws_fwd<1,1,0,1,1,1>", "ws_fwd<0,1,0,1,1,1>", "ws_fwd<0,0,1,1,1,1>", "ws_fwd<1,1,0,0,1,1>",
-    "ws_fwd<1,0,0,0,1,1>", "ws_fwd<1,1,0,0,1,0>", "ws_fwd<0,1,0,1,1,0>",
-    "ws_fwd3<1,0,1,1,0>", "ws_fwd3<1,1,1,1,0>", "ws_fwd3<0,1,1,1,0>", "ws_fwd3<1,0,0,1,0>", "ws_fwd3<0,1,0,1,0>", "ws_fwd3<1,0,0,0,0>",
-    "ws_fwd3<1,1,0,0,0>", "ws_fwd3<0,1,0,0,0>", "ws_fwd3<0,1,0,0,1>",
-    "ws_dgrad<1,0,0>", "ws_dgrad<0,1,0>", "ws_dgrad<1,0,1>", "ws_dgrad32<1,0,0>", "ws_dgrad32<0,1,0>", "ws_dgrad32<1,0,1>",
-    "ws_dgrad3<1,0>", "ws_dgrad3<0,0>", "ws_dgrad3<1,1>",
-    "ws_wgrad<0>", "ws_wgrad<1>", "ws_wgrad<2>", "ws_wgrad<3>", "ws_wgrad<4>", "ws_wgrad<5>",
-    "ws_wgrad32<0>", "ws_wgrad32<1>", "ws_wgrad32<2>", "ws_wgrad32<3>", "ws_wgrad32<4>",
-    "ws_wgrad3p",
-};
-enum { WS_NFLAVOURS = sizeof(WS_FLAVOURS) / sizeof(WS_FLAVOURS[0]) };
-
-static int flavour_id(const char* name) {
-  for (int i = 0; i < WS_NFLAVOURS; ++i)
-    if (!strcmp(WS_FLAVOURS[i], name)) return i;
-  return -1;
-}
+typedef const WsTable& (*WsTableFn)();
+static const WsTableFn WS_TABLES[] = {ws_fwd_table, ws_fwd3_table, ws_dgrad_table, ws_dgrad3_table, ws_wgrad_table, ws_wgrad3p_table};
 
 struct WsDev {      // device copies of the tap's arrays: freed on every return path
   std::vector<void*> ptrs;
@@ -73,7 +55,14 @@ using namespace orl;
 
 extern "C" {
 
-const char* orl_debug_ws_flavour(int idx) { return (idx >= 0 && idx < WS_NFLAVOURS) ? WS_FLAVOURS[idx] : nullptr; }
+const char* orl_debug_ws_flavour(int idx) {
+  for (WsTableFn table : WS_TABLES) {
+    const WsTable& t = table();
+    if (idx >= 0 && idx < t.n) return t.rows[idx].name;
+    idx -= t.n;
+  }
+  return nullptr;
+}
 
 int orl_debug_ws(orl_ws_ex* a) {
   if (!a) return fail("orl_debug_ws: null arguments");
@@ -135,10 +124,8 @@ int orl_debug_ws(orl_ws_ex* a) {
     if (b.n <= 0 || b.off < 0 || b.off + nz0 > b.n) return bad("gscale: one float per run (nz0) from its offset");
   }
 
-  int lds = 0;
-  char name[64] = "";
   if (fwd) {
-    const bool dgm = has(B_DMASK), tq = has(B_TQ), sy = has(B_Y), xs = !a->x0_discard;
+    const bool dgm = has(B_DMASK), tq = has(B_TQ), sy = has(B_Y);
     if (a->tq_sm < 1) return bad("tq_sm must be >= 1");
     if (has(B_TW) != tq || has(B_TB) != tq) return bad("the fused tail needs tw, tb and tq together");
     if (kind == ORL_WS_FWD3 && tq && !has(B_TQ2)) return bad("the three-plane forward writes its tail as two partial sums: tq needs tq2");
@@ -159,17 +146,6 @@ int orl_debug_ws(orl_ws_ex* a) {
       if (bufs[B_MB0]->pitch != 8) return bad("mb0_g (mb0's pitch) must be 8 words");
       if (!narrow_fit(B_X0) || !strided_fit(B_W0, a->w0_sn, a->w0_sk, WS_N, a->in0, 1, false) || !fits(B_B0, WS_N, 1, false) || !rows_fit(B_MB0, 8, true)) return bad(why);
     }
-    if (kind == ORL_WS_FWD) {
-      lds = (int)ws_fwd_lds_bytes(l0);
-      const int f = a->f32 != 0;
-      if (dgm) snprintf(name, sizeof(name), "ws_fwd<0,0,1,1,%d,1>", f);
-      else if (l0 && !xs && !(tq && sy)) snprintf(name, sizeof(name), tq ? "ws_fwd<1,1,0,0,%d,0>" : "ws_fwd<0,1,0,1,%d,0>", f);
-      else snprintf(name, sizeof(name), "ws_fwd<%d,%d,0,%d,%d,1>", tq, l0, !(tq && !sy), f);
-    } else {
-      lds = (int)ws_fwd3_lds_bytes();
-      if (dgm) snprintf(name, sizeof(name), "ws_fwd3<0,1,0,0,1>");
-      else snprintf(name, sizeof(name), "ws_fwd3<%d,%d,%d,%d,0>", tq, sy, l0 && xs, l0);
-    }
   } else if (dg) {
     const bool plain = has(B_Z), w0 = has(B_W0O), store = has(B_C);
     if (a->dq_sm < 1) return bad("dq_sm must be >= 1");
@@ -189,13 +165,6 @@ int orl_debug_ws(orl_ws_ex* a) {
     } else {
       if (has(B_X)) return bad("X belongs to the dW0 / db0 flavour");
       if (!rows_fit(B_C, WS_N, true)) return bad(why);
-    }
-    if (kind == ORL_WS_DGRAD) {
-      lds = (int)(a->f32 ? ws_dgrad32_lds_bytes() : ws_dgrad_lds_bytes(plain));
-      snprintf(name, sizeof(name), "%s<%d,%d,%d>", a->f32 ? "ws_dgrad32" : "ws_dgrad", w0, store, plain);
-    } else {
-      lds = (int)ws_dgrad3_lds_bytes(plain);
-      snprintf(name, sizeof(name), "ws_dgrad3<%d,%d>", w0, plain);
     }
   } else {
     const bool plain = has(B_DZ), tails = has(B_H1), derived = !tails && has(B_W1);
@@ -223,14 +192,6 @@ int orl_debug_ws(orl_ws_ex* a) {
     if (has(B_DWT)) {
       if (!fits(B_DWT, WS_K, per_z, true) || !fits(B_DBT, 1, per_z, true)) return bad(why);
       if (a->dwt.s0 != a->dW.s0 || a->dwt.ks != a->dW.ks || a->dbt.s0 != a->dW.s0 || a->dbt.ks != a->dW.ks) return bad("dwt and dbt share dW's s0 and slab stride");
-    }
-    if (kind == ORL_WS_WGRAD3P) {
-      lds = (int)ws_wgrad3p_lds_bytes();
-      snprintf(name, sizeof(name), "ws_wgrad3p");
-    } else {
-      const int mode = plain ? (recomp ? 4 : 3) : (a->np3 ? 5 : (tails ? 1 : (derived ? 2 : 0)));
-      if (a->f32) { lds = (int)ws_wgrad32_lds_bytes(recomp); snprintf(name, sizeof(name), "ws_wgrad32<%d>", mode); }
-      else { lds = (int)ws_wgrad_lds_bytes(plain, recomp, mode == 5); snprintf(name, sizeof(name), "ws_wgrad<%d>", mode); }
     }
   }
 
@@ -287,19 +248,21 @@ int orl_debug_ws(orl_ws_ex* a) {
   for (int i = 0; i < B_COUNT; ++i) fake[i] = (char*)(uintptr_t)4096;
   params(fake, (float*)(uintptr_t)4096);
   bool ok = false;
+  int row = -1;      // the instantiation the launcher will take: its own selector's row of its own table
   const char* pred = "";
   switch (kind) {
-    case ORL_WS_FWD: ok = ws_fwd_supported(pf, WS_K, WS_N) && (!l0 || ws_fwd01_supported(pf)); pred = "ws_fwd_supported / ws_fwd01_supported"; break;
-    case ORL_WS_FWD3: ok = ws_fwd3_supported(pf, WS_K, WS_N); pred = "ws_fwd3_supported"; break;
-    case ORL_WS_DGRAD: ok = ws_dgrad_supported(pd, WS_K, WS_N); pred = "ws_dgrad_supported"; break;
-    case ORL_WS_DGRAD3: ok = ws_dgrad3_supported(pd, WS_K, WS_N); pred = "ws_dgrad3_supported"; break;
-    case ORL_WS_WGRAD: ok = ws_wgrad_supported(pw, WS_K, WS_N); pred = "ws_wgrad_supported"; break;
-    default: ok = ws_wgrad3p_supported(pw, WS_K, WS_N); pred = "ws_wgrad3p_supported"; break;
+    case ORL_WS_FWD: ok = ws_fwd_supported(pf, WS_K, WS_N) && (!l0 || ws_fwd01_supported(pf)); row = ws_fwd_flavour(pf); pred = "ws_fwd_supported / ws_fwd01_supported"; break;
+    case ORL_WS_FWD3: ok = ws_fwd3_supported(pf, WS_K, WS_N); row = ws_fwd3_flavour(pf); pred = "ws_fwd3_supported"; break;
+    case ORL_WS_DGRAD: ok = ws_dgrad_supported(pd, WS_K, WS_N); row = ws_dgrad_flavour(pd); pred = "ws_dgrad_supported"; break;
+    case ORL_WS_DGRAD3: ok = ws_dgrad3_supported(pd, WS_K, WS_N); row = ws_dgrad3_flavour(pd); pred = "ws_dgrad3_supported"; break;
+    case ORL_WS_WGRAD: ok = ws_wgrad_supported(pw, WS_K, WS_N); row = ws_wgrad_flavour(pw); pred = "ws_wgrad_supported"; break;
+    default: ok = ws_wgrad3p_supported(pw, WS_K, WS_N); row = ws_wgrad3p_flavour(pw); pred = "ws_wgrad3p_supported"; break;
   }
   if (!ok) return bad(std::string("refused by ") + pred + " (M >= 256 in whole row groups, 16-byte aligned vector operands, pitches and strides that are multiples of 4, a flavour the launcher has)");
-  const int id = flavour_id(name);
-  if (id < 0) return bad(std::string("no instantiation ") + name + " exists");
-  a->r_launcher = kind; a->r_flavour = id; a->r_lds = lds; a->r_groups = groups;
+  int id = 0;
+  if (row < 0) return bad("the launcher has no instantiation for these parameters");
+  for (int k = 0; k < kind; ++k) id += WS_TABLES[k]().n;
+  a->r_launcher = kind; a->r_flavour = id + row; a->r_lds = (int)WS_TABLES[kind]().rows[row].lds; a->r_groups = groups;
   if (a->dry_run) return 0;
 
   // ---- device ----

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad_w0_kernel(const WsDgradP p) {
         const int r = (tid >> 6) + 8 * i, kq = tid & 63;              // columns 4 kq ..: half (kq & 1) of the 16-byte chunk kq >> 1
         hx4 h, l;
         orl_split4(sz[i] * gsc, h, l);
-        const int o = r * WS_PITCH + ((((kq >> 1) ^ (r & 15)) << 3) | ((kq & 1) << 2));
+        const int o = ws_a_off(r, kq);
         *(hx4*)(dh + o) = h;
         *(hx4*)(dh + WS_ROWS * WS_PITCH + o) = l;
       }
@@ -242,13 +242,7 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad_w0_kernel(const WsDgradP p) {
 #pragma unroll
   for (int cbk = 0; cbk < 2; ++cbk)
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = 16 * cbk + 4 * lq + r, n = ncol0 + 16 * cb + li;
-        if (c < p.in0) wo[(long)n * p.o_sr + (long)c * p.o_sc] = d2[cbk][cb][r] * out_inv;
-        else if (c == p.in0) bo[n] = d2[cbk][cb][r] * out_inv;
-      }
+    for (int cb = 0; cb < 2; ++cb) ws_w0_slab_block(p, wo, bo, d2[cbk][cb], 16 * cbk, lq, ncol0 + 16 * cb + li, out_inv);
 }
 
 // ---- exact-fp32 flavour (precision 0): same structure on v_mfma_f32_16x16x4_f32 ----
@@ -433,40 +427,30 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad32_w0_kernel(const WsDgradP p) 
 #pragma unroll
   for (int cbk = 0; cbk < 2; ++cbk)
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = 16 * cbk + 4 * lq + r, n = ncol0 + 16 * cb + li;
-        if (c < p.in0) wo[(long)n * p.o_sr + (long)c * p.o_sc] = d2[cbk][cb][r];
-        else if (c == p.in0) bo[n] = d2[cbk][cb][r];
-      }
+    for (int cb = 0; cb < 2; ++cb) ws_w0_slab_block(p, wo, bo, d2[cbk][cb], 16 * cbk, lq, ncol0 + 16 * cb + li, 1.0f);
+}
+
+#define WS_DGRAD_ROW(NAME, KERNEL, W0, STORE, PLAIN, LDS) {NAME "<" #W0 "," #STORE "," #PLAIN ">", (const void*)KERNEL<W0, STORE, PLAIN>, LDS}
+const WsTable& ws_dgrad_table() {
+  static const WsFlavour rows[] = {
+      WS_DGRAD_ROW("ws_dgrad", ws_dgrad_w0_kernel, 1, 0, 0, ws_dgrad_lds_bytes()), WS_DGRAD_ROW("ws_dgrad", ws_dgrad_w0_kernel, 0, 1, 0, ws_dgrad_lds_bytes()),
+      WS_DGRAD_ROW("ws_dgrad", ws_dgrad_w0_kernel, 1, 0, 1, ws_dgrad_lds_bytes(true)),
+      WS_DGRAD_ROW("ws_dgrad32", ws_dgrad32_w0_kernel, 1, 0, 0, ws_dgrad32_lds_bytes()), WS_DGRAD_ROW("ws_dgrad32", ws_dgrad32_w0_kernel, 0, 1, 0, ws_dgrad32_lds_bytes()),
+      WS_DGRAD_ROW("ws_dgrad32", ws_dgrad32_w0_kernel, 1, 0, 1, ws_dgrad32_lds_bytes())};
+  static const WsTable t = {rows, 6};
+  return t;
+}
+
+int ws_dgrad_flavour(const WsDgradP& p) {
+  const int row = p.Z.p ? 2 : (p.w0_out ? 0 : (p.C.p ? 1 : -1));      // plain; dW0 / db0 slabs; the stored dz0
+  return row < 0 ? -1 : row + (p.f32 ? 3 : 0);
 }
 
 hipError_t launch_ws_dgrad_w0(WsDgradP p, int nz, int per_z, hipStream_t st) {
   p.groups = p.M / WS_ROWS;
-  const dim3 grid(per_z, 1, nz), block(WS_NT);
-  if (p.f32) {
-    static const hipError_t attr_err = [] {
-      hipError_t e = hipFuncSetAttribute((const void*)ws_dgrad32_w0_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_dgrad32_lds_bytes());
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_dgrad32_w0_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_dgrad32_lds_bytes());
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_dgrad32_w0_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_dgrad32_lds_bytes());
-      return e;
-    }();
-    if (attr_err != hipSuccess) return attr_err;
-    if (p.Z.p) hipLaunchKernelGGL((ws_dgrad32_w0_kernel<true, false, true>), grid, block, ws_dgrad32_lds_bytes(), st, p);
-    else if (p.w0_out) hipLaunchKernelGGL((ws_dgrad32_w0_kernel<true, false>), grid, block, ws_dgrad32_lds_bytes(), st, p);
-    else hipLaunchKernelGGL((ws_dgrad32_w0_kernel<false, true>), grid, block, ws_dgrad32_lds_bytes(), st, p);
-    return hipGetLastError();
-  }
-  if (p.Z.p) {
-    static const hipError_t attr_err = hipFuncSetAttribute((const void*)ws_dgrad_w0_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_dgrad_lds_bytes(true));
-    if (attr_err != hipSuccess) return attr_err;
-    hipLaunchKernelGGL((ws_dgrad_w0_kernel<true, false, true>), grid, block, ws_dgrad_lds_bytes(true), st, p);
-    return hipGetLastError();
-  }
-  if (p.w0_out) hipLaunchKernelGGL((ws_dgrad_w0_kernel<true, false>), grid, block, ws_dgrad_lds_bytes(), st, p);
-  else hipLaunchKernelGGL((ws_dgrad_w0_kernel<false, true>), grid, block, ws_dgrad_lds_bytes(), st, p);
-  return hipGetLastError();
+  static const hipError_t attr_err = ws_table_attrs(ws_dgrad_table());
+  if (attr_err != hipSuccess) return attr_err;
+  return ws_table_launch(ws_dgrad_table(), ws_dgrad_flavour(p), dim3(per_z, 1, nz), p, st);
 }
 
 }  // namespace orl

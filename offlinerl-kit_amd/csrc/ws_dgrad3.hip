@@ -115,7 +115,7 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad3_w0_kernel(const WsDgradP p) {
         const int r = (tid >> 6) + 8 * i, kq = tid & 63;              // columns 4 kq ..: half (kq & 1) of the 16-byte chunk kq >> 1
         hx4 h, mm, l;
         orl_split4x3(sz[i] * gsc, h, mm, l);
-        const int o = r * WS_PITCH + ((((kq >> 1) ^ (r & 15)) << 3) | ((kq & 1) << 2));
+        const int o = ws_a_off(r, kq);
         *(hx4*)(dh + o) = h;
         *(hx4*)(dh + WS_ROWS * WS_PITCH + o) = mm;
         *(hx4*)(dh + 2 * WS_ROWS * WS_PITCH + o) = l;
@@ -247,26 +247,26 @@ __global__ __launch_bounds__(WS_NT) void ws_dgrad3_w0_kernel(const WsDgradP p) {
   float* wo = p.w0_out + z0 * p.o_rs + z1 * p.o_ms + (long)blockIdx.x * p.o_ks;
   float* bo = p.b0_out + z0 * p.o_rs + z1 * p.ob_ms + (long)blockIdx.x * p.o_ks;
 #pragma unroll
-  for (int cbk = 0; cbk < 2; ++cbk)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int c = 16 * cbk + 4 * lq + r, n = ncol0 + li;
-      if (c < p.in0) wo[(long)n * p.o_sr + (long)c * p.o_sc] = d2[cbk][r] * out_inv;
-      else if (c == p.in0) bo[n] = d2[cbk][r] * out_inv;
-    }
+  for (int cbk = 0; cbk < 2; ++cbk) ws_w0_slab_block(p, wo, bo, d2[cbk], 16 * cbk, lq, ncol0 + li, out_inv);
+}
+
+#define WS_DGRAD3_ROW(W0, PLAIN) {"ws_dgrad3<" #W0 "," #PLAIN ">", (const void*)ws_dgrad3_w0_kernel<W0, PLAIN>, ws_dgrad3_lds_bytes(PLAIN)}
+const WsTable& ws_dgrad3_table() {
+  static const WsFlavour rows[] = {WS_DGRAD3_ROW(1, 0), WS_DGRAD3_ROW(0, 0), WS_DGRAD3_ROW(1, 1)};
+  static const WsTable t = {rows, 3};
+  return t;
+}
+
+int ws_dgrad3_flavour(const WsDgradP& p) {
+  if (p.Z.p) return 2;
+  return (p.w0_out != nullptr) == (p.C.p != nullptr) ? -1 : (p.w0_out ? 0 : 1);      // either the slabs or the stored dz0
 }
 
 hipError_t launch_ws_dgrad3_w0(WsDgradP p, int nz, int per_z, hipStream_t st) {
   p.groups = p.M / WS_ROWS;
-  if (p.Z.p) {
-    static const hipError_t attr_err = hipFuncSetAttribute((const void*)ws_dgrad3_w0_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_dgrad3_lds_bytes(true));
-    if (attr_err != hipSuccess) return attr_err;
-    hipLaunchKernelGGL((ws_dgrad3_w0_kernel<true, true>), dim3(per_z, 2, nz), dim3(WS_NT), ws_dgrad3_lds_bytes(true), st, p);
-    return hipGetLastError();
-  }
-  if (p.w0_out) hipLaunchKernelGGL(ws_dgrad3_w0_kernel<true>, dim3(per_z, 2, nz), dim3(WS_NT), ws_dgrad3_lds_bytes(), st, p);
-  else hipLaunchKernelGGL(ws_dgrad3_w0_kernel<false>, dim3(per_z, 2, nz), dim3(WS_NT), ws_dgrad3_lds_bytes(), st, p);
-  return hipGetLastError();
+  static const hipError_t attr_err = ws_table_attrs(ws_dgrad3_table());
+  if (attr_err != hipSuccess) return attr_err;
+  return ws_table_launch(ws_dgrad3_table(), ws_dgrad3_flavour(p), dim3(per_z, 2, nz), p, st);
 }
 
 }  // namespace orl

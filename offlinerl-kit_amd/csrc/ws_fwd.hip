@@ -40,8 +40,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   // F32: lane (li, lq) supplies W[n][k = 16 t + 4 lq .. + 3], t = 0..15 (element e of the float4 = MFMA k step e of block t)
   hx8 bh[WS_CB][F32 ? 1 : 8], bl[WS_CB][F32 ? 1 : 8];
   f32x4 bw[WS_CB][F32 ? 16 : 1];
-  // The layout test (w_sk == 1) sits OUTSIDE the fragment loops and all loads of a layout are issued before the first conversion: with the
-  // test inside, every fragment was its own load -> wait -> split round trip (16 - 32 serialized L2 latencies = the ~20 us floor of a launch)
+  // (the layout test w_sk == 1 sits OUTSIDE the fragment loops, all loads before the first conversion: ws_device.h, ws_w_frag_load)
   if constexpr (F32) {
     if (p.w_sk == 1) {
 #pragma unroll
@@ -61,24 +60,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   } else {
     // the resident weights carry the static scale ORL_WSCALE (divided out in the epilogue): hi stays in fp16's normal range
     f32x4 raw[WS_CB][8][2];
-    if (p.w_sk == 1) {
-#pragma unroll
-      for (int cb = 0; cb < WS_CB; ++cb)
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-          const float* src = Wg + (long)(ncol0 + 16 * cb + li) * p.w_sn + (32 * ks + 8 * lq);
-          raw[cb][ks][0] = *(const f32x4*)src; raw[cb][ks][1] = *(const f32x4*)(src + 4);
-        }
-    } else {                                           // (in, out)-major weights: eight strided loads per fragment, once per workgroup
-#pragma unroll
-      for (int cb = 0; cb < WS_CB; ++cb)
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-          const float* src = Wg + (long)(ncol0 + 16 * cb + li) * p.w_sn + (long)(32 * ks + 8 * lq) * p.w_sk;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { raw[cb][ks][0][j] = src[(long)j * p.w_sk]; raw[cb][ks][1][j] = src[(long)(4 + j) * p.w_sk]; }
-        }
-    }
+    ws_w_frag_load(Wg, p.w_sn, p.w_sk, ncol0, li, lq, raw);
 #pragma unroll
     for (int cb = 0; cb < WS_CB; ++cb)
 #pragma unroll
@@ -86,7 +68,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   }
   WS_STAMP(1);
   // L0: first-layer fragments of the same columns, K = 32: W0'[n][k] = W0[n][k] (k < in0), b0[n] (k == in0), 0 beyond
-  hx8 b0h[WS_CB], b0l[WS_CB];
+  hx8 b0[WS_CB][2];                                 // [hi, lo]
   f32x4 b0w[WS_CB][2];                              // F32: k = 16 t + 4 lq + e
   if (L0) {
     const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
@@ -94,29 +76,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
 #pragma unroll
     for (int cb = 0; cb < WS_CB; ++cb) {
       const int n = ncol0 + 16 * cb + li;
-      f32x4 a, b;
-      // clamped addresses and 0 / 1 factors, not guarded loads (each guard is a branch with its own wait: twelve serialized round trips
-      // per workgroup and problem).  0 * w is exact for finite weights; a diverged run's Inf / NaN would spread into the zero columns.
-      const float bn = b0g[n];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int k0 = 8 * lq + j, k1 = k0 + 4;
-        const float w0 = W0g[(long)n * p.w0_sn + (long)(k0 < p.in0 ? k0 : p.in0 - 1) * p.w0_sk];
-        const float w1 = W0g[(long)n * p.w0_sn + (long)(k1 < p.in0 ? k1 : p.in0 - 1) * p.w0_sk];
-        a[j] = (k0 < p.in0 ? 1.f : 0.f) * w0 + (k0 == p.in0 ? 1.f : 0.f) * bn;
-        b[j] = (k1 < p.in0 ? 1.f : 0.f) * w1 + (k1 == p.in0 ? 1.f : 0.f) * bn;
-      }
-      if constexpr (!F32) ws_split8(a, b, b0h[cb], b0l[cb]);
-      if constexpr (F32) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int k = 16 * t + 4 * lq + j;
-            const float w = W0g[(long)n * p.w0_sn + (long)(k < p.in0 ? k : p.in0 - 1) * p.w0_sk];
-            b0w[cb][t][j] = (k < p.in0 ? 1.f : 0.f) * w + (k == p.in0 ? 1.f : 0.f) * bn;
-          }
-      }
+      if constexpr (F32) ws_w0_frag(p, W0g, n, lq, b0g[n], b0w[cb]); else ws_w0_frag(p, W0g, n, lq, b0g[n], b0[cb]);
     }
   }
   // epilogue constants of this lane's columns n = ncol0 + 16 cb + 4 lq + r sit in LDS (not in 16 VGPRs next to the 128 VGPRs of
@@ -132,18 +92,14 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   // ---- staging of one row group: thread t moves float4 #(t + 512 i), i = 0..7, of the [64][256] tile ----
   // one staging register set: refilled with group g + 2 gs right after group g + gs has been written to LDS
   f32x4 st0[WS_LD];
-  auto load_group = [&](int g, f32x4 (&st)[WS_LD]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < WS_LD; ++i) {
-      const int idx = tid + WS_NT * i, r = idx >> 6, kq = idx & 63;
-      int m = g * WS_ROWS + r; m = m < p.M ? m : p.M - 1;
-      st[i] = *(const f32x4*)&Xg[(long)m * p.x_pitch + 4 * kq];
-    }
-  };
   auto load_piece = [&](int g, f32x4 (&st)[WS_LD], int i) __attribute__((always_inline)) {
     const int idx = tid + WS_NT * i, r = idx >> 6, kq = idx & 63;
     int m = g * WS_ROWS + r; m = m < p.M ? m : p.M - 1;
     st[i] = *(const f32x4*)&Xg[(long)m * p.x_pitch + 4 * kq];
+  };
+  auto load_group = [&](int g, f32x4 (&st)[WS_LD]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < WS_LD; ++i) load_piece(g, st, i);
   };
   auto store_group = [&](int buf, const f32x4 (&st)[WS_LD], int i0 = 0, int i1 = WS_LD) __attribute__((always_inline)) {
     hx_t* dh = Ah + (long)buf * 2 * WS_ROWS * WS_PITCH;
@@ -157,9 +113,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
       }
       hx4 h, l;
       if (DG) orl_split4(st[i] * a_sc, h, l); else orl_split4(st[i], h, l);
-      // 16-byte chunk c = k / 8 of row r lives at chunk c ^ (r & 15): ds_read_b128 of a fragment column is then conflict-free
-      // for the hardware's 16-lane groups (which mix lanes of two neighbouring chunks), and these 8-byte stores stay so too
-      const int o = r * WS_PITCH + ((((kq >> 1) ^ (r & 15)) << 3) | ((kq & 1) << 2));
+      const int o = ws_a_off(r, kq);                      // (XOR-swizzled 16-byte chunks: ws_device.h)
       *(hx4*)(dh + o) = h;
       *(hx4*)(dl + o) = l;
     }
@@ -170,62 +124,23 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   constexpr int XI = (WS_ROWS * 32 + WS_NT - 1) / WS_NT;              // narrow-input elements per thread (two at 512 threads)
   int xr[XI], xc[XI];
   float sx[XI];
-#pragma unroll
-  for (int i = 0; i < XI; ++i) {
-    const int e = tid + WS_NT * i;
-    xr[i] = L0 ? e / (L0 ? p.x0_pitch : 1) : 0; xc[i] = L0 ? e - xr[i] * p.x0_pitch : 0;
-    if (L0 && e >= xe) { xr[i] = 0; xc[i] = 32; }       // never read (rows are consumed as 32 columns of the 36-float pitch)
-  }
-  auto loadX = [&](int g) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < XI; ++i) { const int e = tid + WS_NT * i; sx[i] = X0g[(long)g * xe + (e < xe ? e : xe - 1)]; }   // clamped, not predicated
-  };
-  // Split-bf16: the narrow rows are split ONCE here, by the two staging threads of an element, into a hi plane (bf16 slots 0..31 of
-  // the 144-byte row) and a lo plane (slots 32..63) -- not by every wave in prod_x (eight times the same 32 vector instructions per
-  // group, and vector instructions do not overlap with a SIMD's MFMAs).  Surplus threads write the pad slots 64 / 65.
-  auto storeX = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      const float x = (xc[i] == p.in0) ? 1.0f : sx[i];
-      if constexpr (F32) Xl[(buf * WS_ROWS + xr[i]) * WS_XLP + xc[i]] = x;   // surplus threads: pad column 32
-      else {
-        hx_t* row = (hx_t*)(Xl + (buf * WS_ROWS + xr[i]) * WS_XLP);
-        const bool pad = xc[i] >= 32;
-        hx_t hh, ll;
-        orl_split1(x, hh, ll);
-        row[pad ? 64 : xc[i]] = hh;
-        row[pad ? 65 : 32 + xc[i]] = ll;
-      }
-    }
-  };
+  ws_x_index(L0, tid, p.x0_pitch, xe, xr, xc);
+  auto loadX = [&](int g) __attribute__((always_inline)) { ws_x_load(X0g, g, xe, tid, sx); };
+  // (the narrow rows are split once, by their staging threads, into a hi and a lo plane of the 144-byte row: ws_device.h)
+  auto storeX = [&](int buf) __attribute__((always_inline)) { ws_x_store<F32 ? 0 : 2, WS_XLP>(Xl, buf, p.in0, xr, xc, sx); };
   // produce(g): h0 rows of group g for this wave's columns -> global (fp32), the LDS image `buf` (split bf16), mask nibbles
   f32x4 fx32[2];                                     // F32: the narrow-input fragments of prod_x (k = 16 t + 4 lq + e)
-  auto prod_x = [&](int xbuf, int s, hx8& xah, hx8& xal) __attribute__((always_inline)) {
-    if constexpr (F32) {
-      const float* xrow = Xl + (xbuf * WS_ROWS + 16 * s + li) * WS_XLP + 4 * lq;
-      fx32[0] = *(const f32x4*)xrow; fx32[1] = *(const f32x4*)(xrow + 16);
-    } else {
-      const hx_t* xrow = (const hx_t*)(Xl + (xbuf * WS_ROWS + 16 * s + li) * WS_XLP) + 8 * lq;
-      xah = *(const hx8*)xrow; xal = *(const hx8*)(xrow + 32);
-    }
+  auto prod_x = [&](int xbuf, int s, hx8 (&xa)[2]) __attribute__((always_inline)) {
+    if constexpr (F32) ws_x_frag<WS_XLP>(Xl, xbuf, s, li, lq, fx32); else ws_x_frag<WS_XLP>(Xl, xbuf, s, li, lq, xa);
   };
-  auto prod_block = [&](int g, int buf, int par, int s, int cb, const hx8& xah, const hx8& xal) __attribute__((always_inline)) {
+  auto prod_block = [&](int g, int buf, int par, int s, int cb, const hx8 (&xa)[2]) __attribute__((always_inline)) {
     hx_t* dh = Ah + (long)buf * 2 * WS_ROWS * WS_PITCH;
     hx_t* dl = dh + WS_ROWS * WS_PITCH;
     const int r = 16 * s + li;
     const long m = (long)g * WS_ROWS + r;
-    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if constexpr (F32) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v = __builtin_amdgcn_mfma_f32_16x16x4f32(b0w[cb][t][e], fx32[t][e], v, 0, 0, 0);
-    } else {
-      v = ORL_MFMA_16x16x32(b0l[cb], xah, v);
-      v = ORL_MFMA_16x16x32(b0h[cb], xal, v);
-      v = ORL_MFMA_16x16x32(b0h[cb], xah, v);
-    }
-    const unsigned int nib0 = orl_relu_mask4(v);
+    f32x4 v;
+    unsigned int nib0;
+    if constexpr (F32) nib0 = ws_h0_block(b0w[cb], fx32, v); else nib0 = ws_h0_block(b0[cb], xa, v);
     const int k = ncol0 + 16 * cb + 4 * lq;                      // h0 columns k .. k + 3 of row r (lane holds C[m = li][n = 4 lq + j])
     if constexpr (XS) *(f32x4*)&Y0g[m * p.x_pitch + k] = v;
     if constexpr (F32) {
@@ -233,7 +148,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
     } else {
     hx4 h, l;
     orl_split4(v, h, l);
-    const int o = r * WS_PITCH + ((((k >> 3) ^ (r & 15)) << 3) | (((k >> 2) & 1) << 2));
+    const int o = ws_a_off(r, k >> 2);
     *(hx4*)(dh + o) = h;
     *(hx4*)(dl + o) = l;
     }
@@ -242,20 +157,17 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   auto produce = [&](int g, int buf, int xbuf, int par) __attribute__((always_inline)) {
 #pragma unroll
     for (int s = 0; s < WS_SUB; ++s) {
-      hx8 xah, xal;
-      prod_x(xbuf, s, xah, xal);
+      hx8 xa[2];
+      prod_x(xbuf, s, xa);
 #pragma unroll
-      for (int cb = 0; cb < WS_CB; ++cb) prod_block(g, buf, par, s, cb, xah, xal);
+      for (int cb = 0; cb < WS_CB; ++cb) prod_block(g, buf, par, s, cb, xa);
     }
   };
   auto finish0 = [&](int g, int par) __attribute__((always_inline)) {  // after the barrier that follows produce(g): pack the h0 mask
     if (tid < WS_ROWS * 8) {
       const int row = tid >> 3, wd = tid & 7;
-      const unsigned int* nb = (const unsigned int*)(nbs0 + (par * WS_ROWS + row) * WS_NBP + 8 * wd);
-      const unsigned int d0 = nb[0], d1 = nb[1];
-      const unsigned int lo16 = (d0 & 0xFu) | ((d0 >> 4) & 0xF0u) | ((d0 >> 8) & 0xF00u) | ((d0 >> 12) & 0xF000u);
-      const unsigned int hi16 = (d1 & 0xFu) | ((d1 >> 4) & 0xF0u) | ((d1 >> 8) & 0xF00u) | ((d1 >> 12) & 0xF000u);
-      p.mb0.p[z0 * p.mb0.s0 + z1 * p.mb0.s1 + ((long)g * WS_ROWS + row) * p.mb0_g + wd] = lo16 | (hi16 << 16);
+      const unsigned int word = ws_pack_nibbles(nbs0 + (par * WS_ROWS + row) * WS_NBP + 8 * wd);
+      p.mb0.p[z0 * p.mb0.s0 + z1 * p.mb0.s1 + ((long)g * WS_ROWS + row) * p.mb0_g + wd] = word;
     }
   };
 
@@ -333,19 +245,13 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
     if (DG) return;
     if (tid < WS_ROWS * 8) {                         // thread (row, word): eight nibbles -> one 32-column mask word
       const int row = tid >> 3, wd = tid & 7, m = g * WS_ROWS + row;
-      const unsigned int* nb = (const unsigned int*)(nbs + (par * WS_ROWS + row) * WS_NBP + 8 * wd);
-      const unsigned int d0 = nb[0], d1 = nb[1];
-      const unsigned int lo16 = (d0 & 0xFu) | ((d0 >> 4) & 0xF0u) | ((d0 >> 8) & 0xF00u) | ((d0 >> 12) & 0xF000u);
-      const unsigned int hi16 = (d1 & 0xFu) | ((d1 >> 4) & 0xF0u) | ((d1 >> 8) & 0xF00u) | ((d1 >> 12) & 0xF000u);
-      p.mb.p[z0 * p.mb.s0 + z1 * p.mb.s1 + (long)m * p.mb_g + wd] = lo16 | (hi16 << 16);
+      const unsigned int word = ws_pack_nibbles(nbs + (par * WS_ROWS + row) * WS_NBP + 8 * wd);
+      p.mb.p[z0 * p.mb.s0 + z1 * p.mb.s1 + (long)m * p.mb_g + wd] = word;
     }
     if (TQ && tid < WS_ROWS) {                       // eight column-slice partial sums per row, fixed order
       const int m = g * WS_ROWS + tid;
-      const float* q8 = qs + par * WS_NW * WS_ROWS + tid;
-      float a = tbias;
-#pragma unroll
-      for (int w = 0; w < WS_NW; ++w) a += q8[w * WS_ROWS];
-      p.tq.p[z0 * p.tq.s0 + z1 * p.tq.s1 + (long)m * p.tq_sm] = a;
+      const float q = ws_tail_sum(qs + par * WS_NW * WS_ROWS + tid, tbias);
+      p.tq.p[z0 * p.tq.s0 + z1 * p.tq.s1 + (long)m * p.tq_sm] = q;
     }
   };
 
@@ -362,7 +268,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
       for (int cb = 0; cb < WS_CB; ++cb) acc[s][cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const bool fine = steady && !DG;
     float fpart = 0.f;
-    hx8 fxah, fxal;
+    hx8 fxa[2];
     // Steady state: the work of the other pipeline stages is cut into eight pieces, one per k step, and fenced together with that
     // step's 12 MFMAs -- the default scheduler otherwise clusters all 96 MFMAs and the matrix pipe idles during the epilogue /
     // staging arithmetic.  k steps 0..3: the four 16 x 16 blocks of the previous group's epilogue; 4..7: the four blocks of the next
@@ -381,8 +287,8 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
             if (cb == 3) epi_row(par, s, fpart);
           } else if (L0) {
             const int s = (pc - 8) >> 2, cb = (pc - 8) & 3;
-            if (cb == 0) prod_x((it + 1) & 1, s, fxah, fxal);
-            prod_block(g + gs, buf ^ 1, (it + 1) & 1, s, cb, fxah, fxal);
+            if (cb == 0) prod_x((it + 1) & 1, s, fxa);
+            prod_block(g + gs, buf ^ 1, (it + 1) & 1, s, cb, fxa);
           } else {
             store_group(buf ^ 1, stn, pc - 8, pc - 7);
             load_piece(g + 2 * gs, stn, pc - 8);
@@ -399,8 +305,8 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
         } else if (ks == 4 || ks == 6) {
           const int s = (ks - 4) >> 1;
           if (L0) {
-            prod_x((it + 1) & 1, s, fxah, fxal);
-            prod_block(g + gs, buf ^ 1, (it + 1) & 1, s, 0, fxah, fxal);
+            prod_x((it + 1) & 1, s, fxa);
+            prod_block(g + gs, buf ^ 1, (it + 1) & 1, s, 0, fxa);
           } else {
             store_group(buf ^ 1, stn, s, s + 1);
             load_piece(g + 2 * gs, stn, s);
@@ -415,8 +321,8 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
         if (cb == 1) epi_row(par, s, fpart);
       } else if (L0) {
         const int s = (ks - 4) >> 1, cb = (ks - 4) & 1;
-        if (cb == 0) prod_x((it + 1) & 1, s, fxah, fxal);
-        prod_block(g + gs, buf ^ 1, (it + 1) & 1, s, cb, fxah, fxal);
+        if (cb == 0) prod_x((it + 1) & 1, s, fxa);
+        prod_block(g + gs, buf ^ 1, (it + 1) & 1, s, cb, fxa);
       } else {
         store_group(buf ^ 1, stn, ks - 4, ks - 3);
         load_piece(g + 2 * gs, stn, ks - 4);
@@ -447,7 +353,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
       hx8 fah2[WS_SUB], fal2[WS_SUB];
 #pragma unroll
       for (int s = 0; s < WS_SUB; ++s) {
-        const int o = (16 * s + li) * WS_PITCH + (((4 * ks + lq) ^ li) << 3);
+        const int o = ws_a_frag(s, li, 4 * ks + lq);
         fah2[s] = *(const hx8*)&ah[o]; fal2[s] = *(const hx8*)&al[o];
       }
 #pragma unroll
@@ -511,53 +417,36 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd_kernel(const WsFwdP p) {
   WS_STAMP(6);
 }
 
-template <bool F32>
-static hipError_t ws_fwd_attrs() {
-  const int big = (int)ws_fwd_lds_bytes(true);
-  hipError_t e = hipFuncSetAttribute((const void*)ws_fwd_kernel<true, false, false, true, F32>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd_kernel<false, false, false, true, F32>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd_kernel<true, true, false, true, F32>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd_kernel<false, true, false, true, F32>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd_kernel<false, false, true, true, F32>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd_kernel<true, true, false, false, F32>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd_kernel<true, false, false, false, F32>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd_kernel<true, true, false, false, F32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd_kernel<false, true, false, true, F32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  return e;
+// rows 0..8: the split-precision instantiations <TQ, L0, DG, SY, ., XS>; rows 9..17: their exact-fp32 siblings
+#define WS_FWD_ROW(TQ, L0, DG, SY, F32, XS) \
+  {"ws_fwd<" #TQ "," #L0 "," #DG "," #SY "," #F32 "," #XS ">", (const void*)ws_fwd_kernel<TQ, L0, DG, SY, F32, XS>, ws_fwd_lds_bytes(L0)}
+#define WS_FWD_ROWS(F32) \
+  WS_FWD_ROW(1, 0, 0, 1, F32, 1), WS_FWD_ROW(0, 0, 0, 1, F32, 1), WS_FWD_ROW(1, 1, 0, 1, F32, 1), WS_FWD_ROW(0, 1, 0, 1, F32, 1), WS_FWD_ROW(0, 0, 1, 1, F32, 1), \
+  WS_FWD_ROW(1, 1, 0, 0, F32, 1), WS_FWD_ROW(1, 0, 0, 0, F32, 1), WS_FWD_ROW(1, 1, 0, 0, F32, 0), WS_FWD_ROW(0, 1, 0, 1, F32, 0)
+const WsTable& ws_fwd_table() {
+  static const WsFlavour rows[] = {WS_FWD_ROWS(0), WS_FWD_ROWS(1)};
+  static const WsTable t = {rows, 18};
+  return t;
 }
 
-template <bool F32>
-static void ws_fwd_dispatch(const WsFwdP& p, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-  const bool l0 = p.X0.p != nullptr;
-  if (p.dmask.p) hipLaunchKernelGGL((ws_fwd_kernel<false, false, true, true, F32>), grid, block, lds, st, p);
-  else if (l0 && p.x0_discard && !(p.tq.p && p.Y.p)) {     // forward-only passes (storing h0 anyway is always correct: any other shape takes the storing flavour)
-    if (p.tq.p) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, false, F32, false>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((ws_fwd_kernel<false, true, false, true, F32, false>), grid, block, lds, st, p);
-  } else if (l0) {
-    if (p.tq.p && !p.Y.p) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, false, F32>), grid, block, lds, st, p);
-    else if (p.tq.p) hipLaunchKernelGGL((ws_fwd_kernel<true, true, false, true, F32>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((ws_fwd_kernel<false, true, false, true, F32>), grid, block, lds, st, p);
-  } else {
-    if (p.tq.p && !p.Y.p) hipLaunchKernelGGL((ws_fwd_kernel<true, false, false, false, F32>), grid, block, lds, st, p);
-    else if (p.tq.p) hipLaunchKernelGGL((ws_fwd_kernel<true, false, false, true, F32>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((ws_fwd_kernel<false, false, false, true, F32>), grid, block, lds, st, p);
-  }
+int ws_fwd_flavour(const WsFwdP& p) {
+  const bool tq = p.tq.p != nullptr, sy = p.Y.p != nullptr, l0 = p.X0.p != nullptr;
+  if (!tq && !sy) return -1;
+  int row;
+  if (p.dmask.p) row = 4;                                              // plain dgrad mode
+  else if (l0 && p.x0_discard && !(tq && sy)) row = tq ? 7 : 8;         // forward-only passes (storing h0 anyway is always correct: any other shape takes the storing flavour)
+  else if (l0) row = tq ? (sy ? 2 : 5) : 3;
+  else row = tq ? (sy ? 0 : 6) : 1;
+  return row + (p.f32 ? 9 : 0);
 }
 
 hipError_t launch_ws_fwd(WsFwdP p, int nz, hipStream_t st, const WsGeom& geo) {
   p.groups = (p.M + WS_ROWS - 1) / WS_ROWS;
   // one workgroup per CU (register-resident weights): whole rounds of 256 workgroups over the nz problems (ws_blocks_per_problem)
   const int per_z = ws_blocks_per_problem(p.groups, nz, 10, 1 << 20, geo);
-  const size_t lds = ws_fwd_lds_bytes(p.X0.p != nullptr);
-  static const hipError_t attr_err = [] {       // thread-safe one-time initialisation (engines may launch from several host threads)
-    hipError_t e = ws_fwd_attrs<false>();
-    return e == hipSuccess ? ws_fwd_attrs<true>() : e;
-  }();
+  static const hipError_t attr_err = ws_table_attrs(ws_fwd_table());       // thread-safe one-time initialisation (engines may launch from several host threads)
   if (attr_err != hipSuccess) return attr_err;
-  const dim3 grid(per_z, 1, nz), block(WS_NT);
-  if (p.f32) ws_fwd_dispatch<true>(p, grid, block, lds, st);
-  else ws_fwd_dispatch<false>(p, grid, block, lds, st);
-  return hipGetLastError();
+  return ws_table_launch(ws_fwd_table(), ws_fwd_flavour(p), dim3(per_z, 1, nz), p, st);
 }
 
 }  // namespace orl

@@ -15,8 +15,6 @@
 
 namespace orl {
 
-enum { WF3_XLP = 52 };      // float pitch of a narrow-input row: three planes of 32 fp16 slots + pad (208 B: sixteen rows cover the 64 banks once)
-
 // TQ: the single-output tail folded in (two partial sums); SY: the top activation is stored (each half its 128 columns); XS: h0 is stored
 // (false: forward-only passes, WsFwdP::x0_discard).  L0 = false: no fused first layer -- the layer's input rows come from HBM (a hidden layer
 // above the second one of a deeper net: run_cql.py:31's [256, 256, 256]) and are split into the three planes while both halves stage them.
@@ -55,44 +53,18 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
   // ---- resident layer-1 fragments: lane (li, lq) supplies W1[n = ncol1 + li][k = 32 ks + 8 lq .. + 7], times ORL_WSCALE ----
   hx8 bh[8], bm[8], bl[8];
   {
-    f32x4 raw[8][2];
-    if (p.w_sk == 1) {                                                   // nn.Linear (out, in): k-contiguous rows
+    f32x4 raw[1][8][2];
+    ws_w_frag_load(Wg, p.w_sn, p.w_sk, ncol1, li, lq, raw);
 #pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const float* src = Wg + (long)(ncol1 + li) * p.w_sn + (32 * ks + 8 * lq);
-        raw[ks][0] = *(const f32x4*)src; raw[ks][1] = *(const f32x4*)(src + 4);
-      }
-    } else {                                                             // EnsembleLinear (in, out): eight strided loads per fragment, once per workgroup
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const float* src = Wg + (long)(ncol1 + li) * p.w_sn + (long)(32 * ks + 8 * lq) * p.w_sk;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { raw[ks][0][j] = src[(long)j * p.w_sk]; raw[ks][1][j] = src[(long)(4 + j) * p.w_sk]; }
-      }
-    }
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) ws_split8x3(raw[ks][0] * ORL_WSCALE, raw[ks][1] * ORL_WSCALE, bh[ks], bm[ks], bl[ks]);
+    for (int ks = 0; ks < 8; ++ks) ws_split8x3(raw[0][ks][0] * ORL_WSCALE, raw[0][ks][1] * ORL_WSCALE, bh[ks], bm[ks], bl[ks]);
   }
   // first-layer fragments of columns ncol0 + 16 cb + li, K = 32: W0'[n][k] = W0[n][k] (k < in0), b0[n] (k == in0), 0 beyond (unscaled, as in ws_fwd)
-  hx8 b0h[2], b0m[2], b0l[2];
+  hx8 b0[2][3];                                                          // [cb][hi, mid, lo]
   if constexpr (L0) {
     const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
     const float* __restrict__ b0g = p.b0.p + z0 * p.b0.s0 + z1 * p.b0.s1;
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const int n = ncol0 + 16 * cb + li;
-      f32x4 a, b;
-      const float bn = b0g[n];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {                                      // clamped addresses and 0 / 1 factors, not guarded loads (ws_fwd.hip)
-        const int k0 = 8 * lq + j, k1 = k0 + 4;
-        const float w0 = W0g[(long)n * p.w0_sn + (long)(k0 < p.in0 ? k0 : p.in0 - 1) * p.w0_sk];
-        const float w1 = W0g[(long)n * p.w0_sn + (long)(k1 < p.in0 ? k1 : p.in0 - 1) * p.w0_sk];
-        a[j] = (k0 < p.in0 ? 1.f : 0.f) * w0 + (k0 == p.in0 ? 1.f : 0.f) * bn;
-        b[j] = (k1 < p.in0 ? 1.f : 0.f) * w1 + (k1 == p.in0 ? 1.f : 0.f) * bn;
-      }
-      ws_split8x3(a, b, b0h[cb], b0m[cb], b0l[cb]);
-    }
+    for (int cb = 0; cb < 2; ++cb) ws_w0_frag(p, W0g, ncol0 + 16 * cb + li, lq, b0g[ncol0 + 16 * cb + li], b0[cb]);
   }
   const float* __restrict__ twg = TQ ? p.tw.p + z0 * p.tw.s0 + z1 * p.tw.s1 : bg;
   if (!DG && tid < WS_N) { cst[tid] = bg[tid]; cst[WS_N + tid] = twg[tid]; }     // visible after the prologue's barriers
@@ -105,12 +77,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
   const int xe = L0 ? WS_ROWS * p.x0_pitch : 0;
   int xr[2], xc[2];
   float sx[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int e = tid + WS_NT * i;
-    xr[i] = L0 ? e / (L0 ? p.x0_pitch : 1) : 0; xc[i] = L0 ? e - xr[i] * p.x0_pitch : 0;
-    if (L0 && e >= xe) { xr[i] = 0; xc[i] = 32; }                        // surplus threads: pad slots
-  }
+  ws_x_index(L0, tid, p.x0_pitch, xe, xr, xc);
   // ---- L0 = false: staging of one [32][256] row group from HBM (thread t moves float4 #(t + 512 i), i = 0..3), split into three planes ----
   f32x4 st0[WS_LD];
   auto load_piece = [&](int g, int i) __attribute__((always_inline)) {
@@ -122,50 +89,26 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
     const int idx = tid + WS_NT * i, r = idx >> 6, kq = idx & 63;
     hx4 h, mm, l;
     if (DG) orl_split4x3(st0[i] * a_sc, h, mm, l); else orl_split4x3(st0[i], h, mm, l);
-    const int o = r * WS_PITCH + ((((kq >> 1) ^ (r & 15)) << 3) | ((kq & 1) << 2));
+    const int o = ws_a_off(r, kq);
     *(hx4*)(dh + o) = h;
     *(hx4*)(dh + WS_ROWS * WS_PITCH + o) = mm;
     *(hx4*)(dh + 2 * WS_ROWS * WS_PITCH + o) = l;
   };
-  auto loadX = [&](int g) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { const int e = tid + WS_NT * i; sx[i] = X0g[(long)g * xe + (e < xe ? e : xe - 1)]; }   // clamped, not predicated
-  };
-  auto storeX = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float x = (xc[i] == p.in0) ? 1.0f : sx[i];
-      hx_t* row = (hx_t*)(Xl + (buf * WS_ROWS + xr[i]) * WF3_XLP);
-      const bool pad = xc[i] >= 32;
-      hx_t hh, mm, ll;
-      orl_split1x3(x, hh, mm, ll);
-      row[pad ? 96 : xc[i]] = hh;
-      row[pad ? 97 : 32 + xc[i]] = mm;
-      row[pad ? 98 : 64 + xc[i]] = ll;
-    }
-  };
-  auto prod_x = [&](int xbuf, int s, hx8& xah, hx8& xam, hx8& xal) __attribute__((always_inline)) {
-    const hx_t* xrow = (const hx_t*)(Xl + (xbuf * WS_ROWS + 16 * s + li) * WF3_XLP) + 8 * lq;
-    xah = *(const hx8*)xrow; xam = *(const hx8*)(xrow + 32); xal = *(const hx8*)(xrow + 64);
-  };
+  auto loadX = [&](int g) __attribute__((always_inline)) { ws_x_load(X0g, g, xe, tid, sx); };
+  auto storeX = [&](int buf) __attribute__((always_inline)) { ws_x_store<3, WF3_XLP>(Xl, buf, p.in0, xr, xc, sx); };
+  auto prod_x = [&](int xbuf, int s, hx8 (&xa)[3]) __attribute__((always_inline)) { ws_x_frag<WF3_XLP>(Xl, xbuf, s, li, lq, xa); };
   // one 16 x 16 block of h0 (row block s, column block cb of this wave) -> global (fp32), the three planes of LDS image `buf`, mask nibbles
-  auto prod_block = [&](int g, int buf, int par, int s, int cb, const hx8& xah, const hx8& xam, const hx8& xal) __attribute__((always_inline)) {
+  auto prod_block = [&](int g, int buf, int par, int s, int cb, const hx8 (&xa)[3]) __attribute__((always_inline)) {
     hx_t* dh = Ah + (long)buf * 3 * WS_ROWS * WS_PITCH;
     const int r = 16 * s + li;
     const long m = (long)g * WS_ROWS + r;
-    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-    v = ORL_MFMA_16x16x32(b0l[cb], xah, v);
-    v = ORL_MFMA_16x16x32(b0h[cb], xal, v);
-    v = ORL_MFMA_16x16x32(b0m[cb], xam, v);
-    v = ORL_MFMA_16x16x32(b0m[cb], xah, v);
-    v = ORL_MFMA_16x16x32(b0h[cb], xam, v);
-    v = ORL_MFMA_16x16x32(b0h[cb], xah, v);
-    const unsigned int nib0 = orl_relu_mask4(v);
+    f32x4 v;
+    const unsigned int nib0 = ws_h0_block(b0[cb], xa, v);
     const int k = ncol0 + 16 * cb + 4 * lq;                              // h0 columns k .. k + 3 of row r
     if constexpr (XS) *(f32x4*)&y0b[m * y0p + k] = v;
     hx4 h, mm, l;
     orl_split4x3(v, h, mm, l);
-    const int o = r * WS_PITCH + ((((k >> 3) ^ (r & 15)) << 3) | (((k >> 2) & 1) << 2));
+    const int o = ws_a_off(r, k >> 2);
     *(hx4*)(dh + o) = h;
     *(hx4*)(dh + WS_ROWS * WS_PITCH + o) = mm;
     *(hx4*)(dh + 2 * WS_ROWS * WS_PITCH + o) = l;
@@ -174,20 +117,17 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
   auto produce = [&](int g, int buf, int xbuf, int par) __attribute__((always_inline)) {
 #pragma unroll
     for (int s = 0; s < WS_SUB; ++s) {
-      hx8 xah, xam, xal;
-      prod_x(xbuf, s, xah, xam, xal);
+      hx8 xa[3];
+      prod_x(xbuf, s, xa);
 #pragma unroll
-      for (int cb = 0; cb < 2; ++cb) prod_block(g, buf, par, s, cb, xah, xam, xal);
+      for (int cb = 0; cb < 2; ++cb) prod_block(g, buf, par, s, cb, xa);
     }
   };
   auto finish0 = [&](int g, int par) __attribute__((always_inline)) {    // after the barrier that follows produce(g): pack the h0 mask (half 0 only)
     if (tid < WS_ROWS * 8 && half == 0) {
       const int row = tid >> 3, wd = tid & 7;
-      const unsigned int* nb = (const unsigned int*)(nbs0 + (par * WS_ROWS + row) * WS_NBP + 8 * wd);
-      const unsigned int d0 = nb[0], d1 = nb[1];
-      const unsigned int lo16 = (d0 & 0xFu) | ((d0 >> 4) & 0xF0u) | ((d0 >> 8) & 0xF00u) | ((d0 >> 12) & 0xF000u);
-      const unsigned int hi16 = (d1 & 0xFu) | ((d1 >> 4) & 0xF0u) | ((d1 >> 8) & 0xF00u) | ((d1 >> 12) & 0xF000u);
-      p.mb0.p[z0 * p.mb0.s0 + z1 * p.mb0.s1 + ((long)g * WS_ROWS + row) * p.mb0_g + wd] = lo16 | (hi16 << 16);
+      const unsigned int word = ws_pack_nibbles(nbs0 + (par * WS_ROWS + row) * WS_NBP + 8 * wd);
+      p.mb0.p[z0 * p.mb0.s0 + z1 * p.mb0.s1 + ((long)g * WS_ROWS + row) * p.mb0_g + wd] = word;
     }
   };
   // the epilogue of one 16 x 16 block of h1 (row block s): bias, ReLU, tail partial sum, 4 mask bits -> LDS
@@ -216,19 +156,13 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
   auto finish = [&](int g, int par) __attribute__((always_inline)) {     // after the barrier that follows the epilogue of group g
     if (!DG && tid < WS_ROWS * 4) {                                      // thread (row, word of this half): eight nibbles -> one 32-column mask word
       const int row = tid >> 2, wd = tid & 3, m = g * WS_ROWS + row;
-      const unsigned int* nb = (const unsigned int*)(nbs + (par * WS_ROWS + row) * WS_NBP + 8 * wd);
-      const unsigned int d0 = nb[0], d1 = nb[1];
-      const unsigned int lo16 = (d0 & 0xFu) | ((d0 >> 4) & 0xF0u) | ((d0 >> 8) & 0xF00u) | ((d0 >> 12) & 0xF000u);
-      const unsigned int hi16 = (d1 & 0xFu) | ((d1 >> 4) & 0xF0u) | ((d1 >> 8) & 0xF00u) | ((d1 >> 12) & 0xF000u);
-      p.mb.p[z0 * p.mb.s0 + z1 * p.mb.s1 + (long)m * p.mb_g + 4 * half + wd] = lo16 | (hi16 << 16);
+      const unsigned int word = ws_pack_nibbles(nbs + (par * WS_ROWS + row) * WS_NBP + 8 * wd);
+      p.mb.p[z0 * p.mb.s0 + z1 * p.mb.s1 + (long)m * p.mb_g + 4 * half + wd] = word;
     }
     if (TQ && tid >= WS_NT - WS_ROWS) {                                  // eight column-slice partial sums per row, fixed order
       const int row = tid - (WS_NT - WS_ROWS), m = g * WS_ROWS + row;
-      const float* q8 = qs + par * WS_NW * WS_ROWS + row;
-      float a = tbias;
-#pragma unroll
-      for (int w = 0; w < WS_NW; ++w) a += q8[w * WS_ROWS];
-      tqo[(long)m * tqsm] = a;
+      const float q = ws_tail_sum(qs + par * WS_NW * WS_ROWS + row, tbias);
+      tqo[(long)m * tqsm] = q;
     }
   };
 
@@ -269,7 +203,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
     f32x4 acc[WS_SUB];
 #pragma unroll
     for (int s = 0; s < WS_SUB; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    hx8 fxah, fxam, fxal;
+    hx8 fxa[3];
     // steady state, one piece per k step (fenced with that step's 12 MFMAs): 0, 1 the two epilogue blocks of the previous group; 2 .. 5 the four
     // first-layer blocks of the next group; 6 the narrow rows of the group after next
     auto piece = [&](int ks) __attribute__((always_inline)) {
@@ -278,8 +212,8 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
       else if (ks < 6) {
         if constexpr (L0) {
           const int s = (ks - 2) >> 1, cb = (ks - 2) & 1;
-          if (cb == 0) prod_x((it + 1) & 1, s, fxah, fxam, fxal);
-          prod_block(g + gs, buf ^ 1, (it + 1) & 1, s, cb, fxah, fxam, fxal);
+          if (cb == 0) prod_x((it + 1) & 1, s, fxa);
+          prod_block(g + gs, buf ^ 1, (it + 1) & 1, s, cb, fxa);
         } else {                                                         // the staging register is refilled right after it was written to LDS
           store_piece(buf ^ 1, ks - 2);
           load_piece(g + 2 * gs, ks - 2);
@@ -291,7 +225,7 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
       hx8 fah[WS_SUB], fam[WS_SUB], fal[WS_SUB];
 #pragma unroll
       for (int s = 0; s < WS_SUB; ++s) {
-        const int o = (16 * s + li) * WS_PITCH + (((4 * ks + lq) ^ li) << 3);
+        const int o = ws_a_frag(s, li, 4 * ks + lq);
         fah[s] = *(const hx8*)&ah[o]; fam[s] = *(const hx8*)&am[o]; fal[s] = *(const hx8*)&al[o];
       }
       // smallest terms first; operands swapped: D[n][m], lane holds C[m = li][n = 4 lq + r]
@@ -357,43 +291,28 @@ __global__ __launch_bounds__(WS_NT) void ws_fwd3_kernel(const WsFwdP p) {
   finish(g - gs, (it - 1) & 1);
 }
 
+#define WS_FWD3_ROW(TQ, SY, XS, L0, DG) {"ws_fwd3<" #TQ "," #SY "," #XS "," #L0 "," #DG ">", (const void*)ws_fwd3_kernel<TQ, SY, XS, L0, DG>, ws_fwd3_lds_bytes()}
+const WsTable& ws_fwd3_table() {
+  static const WsFlavour rows[] = {WS_FWD3_ROW(1, 0, 1, 1, 0), WS_FWD3_ROW(1, 1, 1, 1, 0), WS_FWD3_ROW(0, 1, 1, 1, 0), WS_FWD3_ROW(1, 0, 0, 1, 0), WS_FWD3_ROW(0, 1, 0, 1, 0),
+                                               WS_FWD3_ROW(1, 0, 0, 0, 0), WS_FWD3_ROW(1, 1, 0, 0, 0), WS_FWD3_ROW(0, 1, 0, 0, 0), WS_FWD3_ROW(0, 1, 0, 0, 1)};
+  static const WsTable t = {rows, 9};
+  return t;
+}
+
+int ws_fwd3_flavour(const WsFwdP& p) {
+  const bool tq = p.tq.p != nullptr, sy = p.Y.p != nullptr, xs = !p.x0_discard;
+  if (p.dmask.p) return sy ? 8 : -1;                  // plain dgrad mode
+  if (!tq && !sy) return -1;
+  if (!p.X0.p) return tq ? (sy ? 6 : 5) : 7;          // no fused first layer: the input rows are staged from HBM
+  if (xs) return tq ? (sy ? 1 : 0) : 2;
+  return tq ? (sy ? -1 : 3) : 4;                      // h0 discarded: forward-only passes (tail alone, or the activation alone)
+}
+
 hipError_t launch_ws_fwd3(WsFwdP p, int nz, int per_z, hipStream_t st) {
   p.groups = p.M / WS_ROWS;
-  static const hipError_t attr_err = [] {
-    const int lds = (int)ws_fwd3_lds_bytes();
-    hipError_t e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<true, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<true, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<false, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_fwd3_kernel<false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    return e;
-  }();
+  static const hipError_t attr_err = ws_table_attrs(ws_fwd3_table());
   if (attr_err != hipSuccess) return attr_err;
-  const dim3 grid(per_z, 2, nz), block(WS_NT);
-  const size_t lds = ws_fwd3_lds_bytes();
-  const bool tq = p.tq.p != nullptr, sy = p.Y.p != nullptr, xs = !p.x0_discard;
-  if (p.dmask.p) {                                    // plain dgrad mode
-    hipLaunchKernelGGL((ws_fwd3_kernel<false, true, false, false, true>), grid, block, lds, st, p);
-    return hipGetLastError();
-  }
-  if (!p.X0.p) {                                      // no fused first layer: the input rows are staged from HBM
-    if (tq && !sy) hipLaunchKernelGGL((ws_fwd3_kernel<true, false, false, false>), grid, block, lds, st, p);
-    else if (tq && sy) hipLaunchKernelGGL((ws_fwd3_kernel<true, true, false, false>), grid, block, lds, st, p);
-    else if (!tq && sy) hipLaunchKernelGGL((ws_fwd3_kernel<false, true, false, false>), grid, block, lds, st, p);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-  }
-  if (tq && !sy && xs) hipLaunchKernelGGL((ws_fwd3_kernel<true, false, true>), grid, block, lds, st, p);
-  else if (tq && sy && xs) hipLaunchKernelGGL((ws_fwd3_kernel<true, true, true>), grid, block, lds, st, p);
-  else if (!tq && sy && xs) hipLaunchKernelGGL((ws_fwd3_kernel<false, true, true>), grid, block, lds, st, p);
-  else if (tq && !sy && !xs) hipLaunchKernelGGL((ws_fwd3_kernel<true, false, false>), grid, block, lds, st, p);
-  else if (!tq && sy && !xs) hipLaunchKernelGGL((ws_fwd3_kernel<false, true, false>), grid, block, lds, st, p);
-  else return hipErrorInvalidValue;                 // (ws_fwd3_supported refuses every other combination)
-  return hipGetLastError();
+  return ws_table_launch(ws_fwd3_table(), ws_fwd3_flavour(p), dim3(per_z, 2, nz), p, st);
 }
 
 }  // namespace orl

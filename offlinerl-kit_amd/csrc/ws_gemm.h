@@ -71,8 +71,28 @@ enum { WS_DUMP_SLOTS = 8192 };
 #define WS_WAVES 8      // 16 waves (16 columns each) measured slower: the 128-VGPR budget spills
 #endif
 enum { WS_ROWS = 32, WS_K = 256, WS_N = 256, WS_PITCH = WS_K, WS_NW = WS_WAVES, WS_NT = 64 * WS_NW, WS_CB = WS_N / 16 / WS_NW };   // unpadded rows: 16-byte chunks are XOR-swizzled; WS_CB 16-column blocks per wave
-enum { WS_SUB = WS_ROWS / 16, WS_LD = WS_ROWS * WS_K / 4 / WS_NT };
-enum { WS_NBP = 68, WS_XLP = 36 };      // byte pitch of a mask-nibble row (64 used) / float pitch of a narrow-input row (32 used): odd multiples of 4 B / 16 B spread the rows over the banks   // 16-row blocks per group; float4 loads per thread per group
+enum { WS_SUB = WS_ROWS / 16, WS_LD = WS_ROWS * WS_K / 4 / WS_NT };      // 16-row blocks per group; float4 loads per thread per group
+enum { WS_NBP = 68, WS_XLP = 36 };      // byte pitch of a mask-nibble row (64 used) / float pitch of a narrow-input row (32 used): odd multiples of 4 B / 16 B spread the rows over the banks
+enum { WF3_XLP = 52 };                  // precision 2: float pitch of a narrow-input row, three planes of 32 fp16 slots + pad (208 B: sixteen rows cover the 64 banks once)
+
+// One instantiation of a launcher: the name the unit tap reports, the kernel and its dynamic LDS bytes.  Every launcher file holds ONE table
+// of its instantiations and ONE selector ws_<x>_flavour(p) = the row that serves p (-1: no such flavour).  The launcher, the *_supported
+// predicate below and the tap (ws_debug.hip) all ask that selector, so they cannot disagree about which kernel a parameter set takes.
+// (ws_<x>_table() returns a function-local static: a const array at namespace scope would be emitted into the device code object as well.)
+struct WsFlavour { const char* name; const void* kernel; size_t lds; };
+struct WsTable { const WsFlavour* rows; int n; };
+static inline hipError_t ws_table_attrs(const WsTable& t) {
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < t.n && e == hipSuccess; ++i) e = hipFuncSetAttribute(t.rows[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.rows[i].lds);
+  return e;
+}
+template <class P>
+static inline hipError_t ws_table_launch(const WsTable& t, int row, dim3 grid, P& p, hipStream_t st) {
+  if (row < 0 || row >= t.n) return hipErrorInvalidValue;
+  void* args[] = {&p};
+  (void)hipLaunchKernel(t.rows[row].kernel, grid, dim3(WS_NT), args, t.rows[row].lds, st);
+  return hipGetLastError();
+}
 // LDS: A image [2 buffers][hi, lo][WS_ROWS][256] bf16 (swizzled) + tail partial sums [2][WS_NW waves][WS_ROWS] floats
 //      + ReLU-mask nibbles [2][WS_ROWS][64] bytes
 static constexpr size_t ws_fwd_lds_bytes(bool l0 = false) {
@@ -111,13 +131,15 @@ static inline int ws_blocks_per_problem(int groups, int nz, int prologue, int ca
   return best;
 }
 
+const WsTable& ws_fwd_table();                                                   // ws_fwd.hip
+int ws_fwd_flavour(const WsFwdP& p);
 static inline bool ws_fwd_supported(const WsFwdP& p, int K, int N) {
   if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS) || (!p.mb.p && !p.dmask.p)) return false;
   if (!p.X.vec4() || (p.x_pitch & 3)) return false;
   if (p.w_sk == 1 && (!p.W.vec4() || (p.w_sn & 3))) return false;
   if (p.dmask.p) { if (p.tq.p || p.X0.p || p.dm_g != 8) return false; }
   else if (!p.bias.vec4()) return false;
-  if (!p.Y.p && (!p.tq.p || !p.mb.p)) return false;      // the activation may stay unstored only when the tail is folded in
+  if (ws_fwd_flavour(p) < 0 || (!p.Y.p && !p.mb.p)) return false;      // the activation may stay unstored only when the tail is folded in
   if (!p.Y.vec4() || (p.y_pitch & 3)) return false;
   if (p.tq.p && !p.tw.vec4()) return false;
   return true;
@@ -130,17 +152,15 @@ static inline bool ws_fwd01_supported(const WsFwdP& p) {      // extra condition
 hipError_t launch_ws_fwd(WsFwdP p, int nz, hipStream_t st, const WsGeom& geo);      // ws_fwd.hip
 // precision 2: LDS = A image [2][hi, mid, lo][32][256] + tail partial sums + mask nibbles of h1 / h0 + narrow input rows (three planes) + bias / tail weights
 static constexpr size_t ws_fwd3_lds_bytes() {
-  return (size_t)2 * 3 * WS_ROWS * WS_PITCH * 2 + sizeof(float) * 2 * WS_NW * WS_ROWS + 2 * WS_ROWS * WS_NBP + sizeof(float) * 2 * WS_ROWS * 52 +
+  return (size_t)2 * 3 * WS_ROWS * WS_PITCH * 2 + sizeof(float) * 2 * WS_NW * WS_ROWS + 2 * WS_ROWS * WS_NBP + sizeof(float) * 2 * WS_ROWS * WF3_XLP +
          2 * WS_ROWS * WS_NBP + sizeof(float) * 2 * WS_N;
 }
+const WsTable& ws_fwd3_table();                                                  // ws_fwd3.hip
+int ws_fwd3_flavour(const WsFwdP& p);
 static inline bool ws_fwd3_supported(const WsFwdP& p, int K, int N) {
-  if (!ws_fwd_supported(p, K, N)) return false;
-  if (p.dmask.p) return p.Y.p != nullptr;                                             // plain dgrad mode (ws_fwd_supported: no tail, no fused first layer, 8 mask words per row)
-  if (p.tq.p && !p.tq2.p) return false;
-  const bool tq = p.tq.p != nullptr, sy = p.Y.p != nullptr, xs = !p.x0_discard;      // the flavours the engine's passes use (ws_fwd3.hip)
-  if (!p.X0.p) return (tq || sy) && (p.M % WS_ROWS) == 0;                           // input rows from HBM
-  if (!ws_fwd01_supported(p) || !p.dump) return false;
-  return (tq && !sy) || (tq && sy && xs) || (!tq && sy);
+  if (!ws_fwd_supported(p, K, N) || (p.tq.p && !p.tq2.p)) return false;              // (plain dgrad mode: ws_fwd_supported allows no tail and no fused first layer)
+  if (p.X0.p && (!ws_fwd01_supported(p) || !p.dump)) return false;
+  return ws_fwd3_flavour(p) >= 0;                                                    // the flavours the engine's passes use
 }
 hipError_t launch_ws_fwd3(WsFwdP p, int nz, int per_z, hipStream_t st);              // ws_fwd3.hip (grid.y = 2 column halves)
 
@@ -188,6 +208,8 @@ static constexpr size_t ws_dgrad32_lds_bytes() {
   return sizeof(float) * ((size_t)2 * WS_ROWS * WS_K + (size_t)2 * 32 * WD32_XP + (size_t)2 * (WS_ROWS + WS_NW * WS_ROWS));
 }
 
+const WsTable& ws_dgrad_table();                                                 // ws_dgrad.hip
+int ws_dgrad_flavour(const WsDgradP& p);
 static inline bool ws_dgrad_supported(const WsDgradP& p, int K, int N) {
   if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS)) return false;
   if (p.Z.p) {
@@ -197,7 +219,7 @@ static inline bool ws_dgrad_supported(const WsDgradP& p, int K, int N) {
   }
   if (!p.abits.p || !p.xbits.p || p.ab_g != 8 || p.xb_g != 8) return false;
   if (p.w0_out && (p.in0 + 1 > 32 || p.in0 >= p.x_pitch || p.x_pitch > 32 || WS_ROWS * p.x_pitch > 2 * WS_NT)) return false;
-  if (!p.w0_out && !p.C.p) return false;
+  if (ws_dgrad_flavour(p) < 0) return false;
   return p.wt.vec4();
 }
 // blocks per problem (= split-K slabs written per problem)
@@ -210,10 +232,10 @@ hipError_t launch_ws_dgrad_w0(WsDgradP p, int nz, int per_z, hipStream_t st);   
 static constexpr size_t ws_dgrad3_lds_bytes(bool plain = false) {      // mask image (plain: three planes of dz1) + X^T images (three planes) + epilogue operands
   return (size_t)2 * (plain ? 3 : 1) * WS_ROWS * WS_PITCH * 2 + (size_t)2 * 3 * 32 * WD_XP * 2 + (size_t)2 * (WS_ROWS + WS_NW * WS_ROWS) * 4;
 }
+const WsTable& ws_dgrad3_table();                                                // ws_dgrad3.hip
+int ws_dgrad3_flavour(const WsDgradP& p);
 static inline bool ws_dgrad3_supported(const WsDgradP& p, int K, int N) {      // from mask bits: the W0 flavour (nothing stored) or the storing one; or the plain W0 flavour
-  if (!ws_dgrad_supported(p, K, N)) return false;
-  if (p.Z.p) return true;                                                      // (ws_dgrad_supported checked w0_out / !C / xbits)
-  return (p.w0_out && !p.C.p) || (!p.w0_out && p.C.p);
+  return ws_dgrad_supported(p, K, N) && ws_dgrad3_flavour(p) >= 0;
 }
 hipError_t launch_ws_dgrad3_w0(WsDgradP p, int nz, int per_z, hipStream_t st);     // ws_dgrad3.hip
 
@@ -278,6 +300,8 @@ static constexpr size_t ws_wgrad32_lds_bytes(bool recompute = false) {
              ? sizeof(float) * ((size_t)2 * 2 * WW32_IMG + 2 * WS_ROWS + (recompute ? 2 * WS_ROWS * WS_XLP : 0)) : sizeof(float) * 17 * WS_K;
 }
 
+const WsTable& ws_wgrad_table();                                                 // ws_wgrad.hip
+int ws_wgrad_flavour(const WsWgradP& p);
 static inline bool ws_wgrad_supported(const WsWgradP& p, int K, int N) {
   if (p.dZ.p) {
     if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS)) return false;
@@ -286,7 +310,7 @@ static inline bool ws_wgrad_supported(const WsWgradP& p, int K, int N) {
     return p.H0.vec4() && !(p.h0_pitch & 3);
   }
   if (K != WS_K || N != WS_N || p.M < 256 || (p.M % WS_ROWS) || !p.abits.p || p.ab_g != 8) return false;
-  if (p.np3 && (p.H1.p || !p.W1.p)) return false;
+  if (ws_wgrad_flavour(p) < 0) return false;
   if (!p.H0.vec4() || (p.h0_pitch & 3)) return false;
   if (!p.H1.p && p.W1.p && (!p.b1.p || !p.dwt || !p.dbt)) return false;
   if (p.H1.p && (!p.H1.vec4() || (p.h1_pitch & 3) || !p.dwt || !p.dbt)) return false;
@@ -296,8 +320,10 @@ hipError_t launch_ws_wgrad(WsWgradP p, int nz, int per_z, hipStream_t st);      
 // precision 2, plain (materialised dZ) flavour: three planes of both operands; a workgroup owns half of the output rows (grid.y = 2)
 // (ws_wgrad3p.hip).  LDS: 2 buffers x {3 x [32][128] dZ planes, 3 x [32][256] H0 planes} + the ones block
 static constexpr size_t ws_wgrad3p_lds_bytes() { return (size_t)2 * (3 * WS_ROWS * 128 + 3 * WS_ROWS * WS_K) * 2 + (size_t)WS_ROWS * 16 * 2; }
+const WsTable& ws_wgrad3p_table();                                               // ws_wgrad3p.hip
+int ws_wgrad3p_flavour(const WsWgradP& p);
 static inline bool ws_wgrad3p_supported(const WsWgradP& p, int K, int N) {
-  return p.dZ.p && !p.X0.p && ws_wgrad_supported(p, K, N);
+  return ws_wgrad3p_flavour(p) >= 0 && ws_wgrad_supported(p, K, N);
 }
 hipError_t launch_ws_wgrad3p(WsWgradP p, int nz, int per_z, hipStream_t st);     // ws_wgrad3p.hip
 

@@ -194,65 +194,27 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad_kernel(const WsWgradP p) {
   // staging of the narrow input rows -- ws_fwd_kernel<., L0>'s producer, writing into this kernel's H image ----
   float* Xl = (float*)(dqimg + 2 * DQP * WS_ROWS * 16);             // [buf][32][WS_XLP]: hi plane in 16-bit slots 0..31, lo plane in 32..63 of a row
   const float* __restrict__ X0g = RECOMP ? p.X0.p + z0 * p.X0.s0 + z1 * p.X0.s1 : nullptr;
-  hx8 b0h[2], b0l[2];
+  hx8 b0[2][2];                                                     // [cb][hi, lo]
   if (RECOMP) {
     const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
     const float* __restrict__ b0g = p.b0.p + z0 * p.b0.s0 + z1 * p.b0.s1;
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const int n = ncol0 + 16 * cb + li;
-      f32x4 a, b;
-      const float bn = b0g[n];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {                                  // clamped addresses and 0 / 1 factors, not guarded loads (ws_fwd.hip)
-        const int k0 = 8 * lq + j, k1 = k0 + 4;
-        const float w0 = W0g[(long)n * p.w0_sn + (long)(k0 < p.in0 ? k0 : p.in0 - 1) * p.w0_sk];
-        const float w1 = W0g[(long)n * p.w0_sn + (long)(k1 < p.in0 ? k1 : p.in0 - 1) * p.w0_sk];
-        a[j] = (k0 < p.in0 ? 1.f : 0.f) * w0 + (k0 == p.in0 ? 1.f : 0.f) * bn;
-        b[j] = (k1 < p.in0 ? 1.f : 0.f) * w1 + (k1 == p.in0 ? 1.f : 0.f) * bn;
-      }
-      ws_split8(a, b, b0h[cb], b0l[cb]);
-    }
+    for (int cb = 0; cb < 2; ++cb) ws_w0_frag(p, W0g, ncol0 + 16 * cb + li, lq, b0g[ncol0 + 16 * cb + li], b0[cb]);
   }
   const int xe = RECOMP ? WS_ROWS * p.x0_pitch : 0;
   int xr[2], xc[2];
   float sx[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int e = tid + WS_NT * i;
-    xr[i] = RECOMP ? e / (RECOMP ? p.x0_pitch : 1) : 0; xc[i] = RECOMP ? e - xr[i] * p.x0_pitch : 0;
-    if (RECOMP && e >= xe) { xr[i] = 0; xc[i] = 32; }               // surplus threads: pad slots
-  }
-  auto loadX = [&](int g) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { const int e = tid + WS_NT * i; sx[i] = X0g[(long)g * xe + (e < xe ? e : xe - 1)]; }   // clamped, not predicated
-  };
-  auto storeX = [&](int xbuf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float x = (xc[i] == p.in0) ? 1.0f : sx[i];
-      hx_t* row = (hx_t*)(Xl + (xbuf * WS_ROWS + xr[i]) * WS_XLP);
-      const bool pad = xc[i] >= 32;
-      hx_t hh, ll;
-      orl_split1(x, hh, ll);
-      row[pad ? 64 : xc[i]] = hh;
-      row[pad ? 65 : 32 + xc[i]] = ll;
-    }
-  };
-  hx8 xah, xal;
-  auto prod_x = [&](int xbuf, int s) __attribute__((always_inline)) {
-    const hx_t* xrow = (const hx_t*)(Xl + (xbuf * WS_ROWS + 16 * s + li) * WS_XLP) + 8 * lq;
-    xah = *(const hx8*)xrow; xal = *(const hx8*)(xrow + 32);
-  };
-  // one 16 x 16 block of h0 of the group staged in Xl[xbuf] -> the H planes of image `buf` (the forward's three products and ReLU, bit for bit)
+  ws_x_index(RECOMP, tid, p.x0_pitch, xe, xr, xc);
+  auto loadX = [&](int g) __attribute__((always_inline)) { ws_x_load(X0g, g, xe, tid, sx); };
+  auto storeX = [&](int xbuf) __attribute__((always_inline)) { ws_x_store<2, WS_XLP>(Xl, xbuf, p.in0, xr, xc, sx); };
+  hx8 xa[2];
+  auto prod_x = [&](int xbuf, int s) __attribute__((always_inline)) { ws_x_frag<WS_XLP>(Xl, xbuf, s, li, lq, xa); };
+  // one 16 x 16 block of h0 of the group staged in Xl[xbuf] -> the H planes of image `buf` (ws_h0_block: the forward's own products and ReLU)
   auto prod_block = [&](int buf, int s, int cb) __attribute__((always_inline)) {
     hx_t* gh = img + (long)buf * NPL * WW_IMG + (NPL - 2) * WW_IMG;
     hx_t* gl = gh + WW_IMG;
-    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-    v = ORL_MFMA_16x16x32(b0l[cb], xah, v);
-    v = ORL_MFMA_16x16x32(b0h[cb], xal, v);
-    v = ORL_MFMA_16x16x32(b0h[cb], xah, v);
-    orl_relu_mask4(v);
+    f32x4 v;
+    ws_h0_block(b0[cb], xa, v);
     hx4 h, l;
     orl_split4(v, h, l);
     const int k = ncol0 + 16 * cb + 4 * lq;                          // the lane holds C[m = 16 s + li][n = k .. k + 3]
@@ -538,49 +500,20 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad32_kernel(const WsWgradP p) {
     const float* __restrict__ W0g = p.W0.p + z0 * p.W0.s0 + z1 * p.W0.s1;
     const float* __restrict__ b0g = p.b0.p + z0 * p.b0.s0 + z1 * p.b0.s1;
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const int n = ncol0 + 16 * cb + li;
-      const float bn = b0g[n];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int k = 16 * t + 4 * lq + j;
-          const float w = W0g[(long)n * p.w0_sn + (long)(k < p.in0 ? k : p.in0 - 1) * p.w0_sk];
-          b0w[cb][t][j] = (k < p.in0 ? 1.f : 0.f) * w + (k == p.in0 ? 1.f : 0.f) * bn;
-        }
-    }
+    for (int cb = 0; cb < 2; ++cb) ws_w0_frag(p, W0g, ncol0 + 16 * cb + li, lq, b0g[ncol0 + 16 * cb + li], b0w[cb]);
   }
   const int xe = RECOMP ? WS_ROWS * p.x0_pitch : 0;
   int xr[2], xc[2];
   float sx[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int e = tid + WS_NT * i;
-    xr[i] = RECOMP ? e / (RECOMP ? p.x0_pitch : 1) : 0; xc[i] = RECOMP ? e - xr[i] * p.x0_pitch : 0;
-    if (RECOMP && e >= xe) { xr[i] = 0; xc[i] = 32; }               // surplus threads: pad column 32 (rows are consumed as 32 columns of the 36-float pitch)
-  }
-  auto loadX = [&](int g) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { const int e = tid + WS_NT * i; sx[i] = X0g[(long)g * xe + (e < xe ? e : xe - 1)]; }
-  };
-  auto storeX = [&](int xbuf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) Xl[(xbuf * WS_ROWS + xr[i]) * WS_XLP + xc[i]] = (xc[i] == p.in0) ? 1.0f : sx[i];
-  };
+  ws_x_index(RECOMP, tid, p.x0_pitch, xe, xr, xc);
+  auto loadX = [&](int g) __attribute__((always_inline)) { ws_x_load(X0g, g, xe, tid, sx); };
+  auto storeX = [&](int xbuf) __attribute__((always_inline)) { ws_x_store<0, WS_XLP>(Xl, xbuf, p.in0, xr, xc, sx); };
   f32x4 fx32[2];
-  auto prod_x = [&](int xbuf, int s) __attribute__((always_inline)) {
-    const float* xrow = Xl + (xbuf * WS_ROWS + 16 * s + li) * WS_XLP + 4 * lq;
-    fx32[0] = *(const f32x4*)xrow; fx32[1] = *(const f32x4*)(xrow + 16);
-  };
+  auto prod_x = [&](int xbuf, int s) __attribute__((always_inline)) { ws_x_frag<WS_XLP>(Xl, xbuf, s, li, lq, fx32); };
   auto prod_block = [&](int buf, int s, int cb) __attribute__((always_inline)) {
     float* gi = img + (long)buf * 2 * WW32_IMG + WW32_IMG;
-    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v = __builtin_amdgcn_mfma_f32_16x16x4f32(b0w[cb][t][e], fx32[t][e], v, 0, 0, 0);
-    orl_relu_mask4(v);
+    f32x4 v;
+    ws_h0_block(b0w[cb], fx32, v);
     *(f32x4*)(gi + (16 * s + li) * WW32_P + ncol0 + 16 * cb + 4 * lq) = v;      // the lane holds C[m = 16 s + li][n = ncol0 + 16 cb + 4 lq ..]
   };
   // (uniform part of every global address on the scalar ALU, per-thread part computed once: see ws_wgrad_kernel)
@@ -719,48 +652,27 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad32_kernel(const WsWgradP p) {
   ww_finish<(MODE == 4 ? 3 : MODE)>(p, ws_smem, acc, accb, tacc, bacc, dqsum, wtg, z0, z1, ncol0);
 }
 
+// rows 0..5: ws_wgrad_kernel<MODE>; rows 6..10: ws_wgrad32_kernel<MODE>
+#define WS_WGRAD_ROW(MODE) {"ws_wgrad<" #MODE ">", (const void*)ws_wgrad_kernel<MODE>, ws_wgrad_lds_bytes(MODE == 3 || MODE == 4, MODE == 4, MODE == 5)}
+#define WS_WGRAD32_ROW(MODE) {"ws_wgrad32<" #MODE ">", (const void*)ws_wgrad32_kernel<MODE>, ws_wgrad32_lds_bytes(MODE == 4)}
+const WsTable& ws_wgrad_table() {
+  static const WsFlavour rows[] = {WS_WGRAD_ROW(0), WS_WGRAD_ROW(1), WS_WGRAD_ROW(2), WS_WGRAD_ROW(3), WS_WGRAD_ROW(4), WS_WGRAD_ROW(5),
+                                                WS_WGRAD32_ROW(0), WS_WGRAD32_ROW(1), WS_WGRAD32_ROW(2), WS_WGRAD32_ROW(3), WS_WGRAD32_ROW(4)};
+  static const WsTable t = {rows, 11};
+  return t;
+}
+
+int ws_wgrad_flavour(const WsWgradP& p) {
+  if (p.dZ.p) return (p.X0.p ? 4 : 3) + (p.f32 ? 6 : 0);      // plain (materialised) gradient: a hidden layer below the top one; X0: its input recomputed from the net's narrow input
+  if (p.np3) return (p.H1.p || !p.W1.p) ? -1 : 5;             // precision 2: three G planes, the derived-tail flavour only (overrides f32)
+  return (p.H1.p ? 1 : (p.W1.p ? 2 : 0)) + (p.f32 ? 6 : 0);
+}
+
 hipError_t launch_ws_wgrad(WsWgradP p, int nz, int per_z, hipStream_t st) {
   p.groups = p.M / WS_ROWS;
-  static const hipError_t attr_err = [] {
-    hipError_t e = hipFuncSetAttribute((const void*)ws_wgrad_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad_lds_bytes());
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad_lds_bytes());
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad_lds_bytes());
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad32_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad32_lds_bytes());
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad32_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad32_lds_bytes());
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad32_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad32_lds_bytes());
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad_lds_bytes(true));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad32_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad32_lds_bytes());
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad_lds_bytes(true, true));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad32_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad32_lds_bytes(true));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ws_wgrad_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad_lds_bytes(false, false, true));
-    return e;
-  }();
+  static const hipError_t attr_err = ws_table_attrs(ws_wgrad_table());
   if (attr_err != hipSuccess) return attr_err;
-  const dim3 grid(per_z, 1, nz), block(WS_NT);
-  if (p.dZ.p && p.X0.p) {                              // ... with the layer's input activation recomputed from the net's narrow input
-    if (p.f32) hipLaunchKernelGGL(ws_wgrad32_kernel<4>, grid, block, ws_wgrad32_lds_bytes(true), st, p);
-    else hipLaunchKernelGGL(ws_wgrad_kernel<4>, grid, block, ws_wgrad_lds_bytes(true, true), st, p);
-    return hipGetLastError();
-  }
-  if (p.dZ.p) {                                      // plain (materialised) gradient: a hidden layer below the top one
-    if (p.f32) hipLaunchKernelGGL(ws_wgrad32_kernel<3>, grid, block, ws_wgrad32_lds_bytes(), st, p);
-    else hipLaunchKernelGGL(ws_wgrad_kernel<3>, grid, block, ws_wgrad_lds_bytes(true), st, p);
-    return hipGetLastError();
-  }
-  if (p.np3) {                                     // precision 2: three G planes (the derived-tail flavour only: ws_wgrad_supported)
-    hipLaunchKernelGGL(ws_wgrad_kernel<5>, grid, block, ws_wgrad_lds_bytes(false, false, true), st, p);
-    return hipGetLastError();
-  }
-  if (p.f32) {
-    if (p.H1.p) hipLaunchKernelGGL(ws_wgrad32_kernel<1>, grid, block, ws_wgrad32_lds_bytes(), st, p);
-    else if (p.W1.p) hipLaunchKernelGGL(ws_wgrad32_kernel<2>, grid, block, ws_wgrad32_lds_bytes(), st, p);
-    else hipLaunchKernelGGL(ws_wgrad32_kernel<0>, grid, block, ws_wgrad32_lds_bytes(), st, p);
-    return hipGetLastError();
-  }
-  if (p.H1.p) hipLaunchKernelGGL(ws_wgrad_kernel<1>, grid, block, ws_wgrad_lds_bytes(), st, p);
-  else if (p.W1.p) hipLaunchKernelGGL(ws_wgrad_kernel<2>, grid, block, ws_wgrad_lds_bytes(), st, p);
-  else hipLaunchKernelGGL(ws_wgrad_kernel<0>, grid, block, ws_wgrad_lds_bytes(), st, p);
-  return hipGetLastError();
+  return ws_table_launch(ws_wgrad_table(), ws_wgrad_flavour(p), dim3(per_z, 1, nz), p, st);
 }
 
 }  // namespace orl

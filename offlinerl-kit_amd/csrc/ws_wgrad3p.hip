@@ -181,12 +181,19 @@ __global__ __launch_bounds__(WS_NT) void ws_wgrad3p_kernel(const WsWgradP p) {
   }
 }
 
+const WsTable& ws_wgrad3p_table() {
+  static const WsFlavour rows[] = {{"ws_wgrad3p", (const void*)ws_wgrad3p_kernel, ws_wgrad3p_lds_bytes()}};
+  static const WsTable t = {rows, 1};
+  return t;
+}
+
+int ws_wgrad3p_flavour(const WsWgradP& p) { return (p.dZ.p && !p.X0.p) ? 0 : -1; }      // the plain flavour with a stored H0
+
 hipError_t launch_ws_wgrad3p(WsWgradP p, int nz, int per_z, hipStream_t st) {
   p.groups = p.M / WS_ROWS;
-  static const hipError_t attr_err = hipFuncSetAttribute((const void*)ws_wgrad3p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ws_wgrad3p_lds_bytes());
+  static const hipError_t attr_err = ws_table_attrs(ws_wgrad3p_table());
   if (attr_err != hipSuccess) return attr_err;
-  hipLaunchKernelGGL(ws_wgrad3p_kernel, dim3(per_z, 2, nz), dim3(WS_NT), ws_wgrad3p_lds_bytes(), st, p);
-  return hipGetLastError();
+  return ws_table_launch(ws_wgrad3p_table(), ws_wgrad3p_flavour(p), dim3(per_z, 2, nz), p, st);
 }
 
 }  // namespace orl

@@ -196,6 +196,13 @@ REFUSALS = [
     ("W1 too short", dict(F["ws_wgrad32<2>"], short={"W1": 5}), "W1: the array is shorter"),
     ("dbt too short", dict(F["ws_wgrad<1>"], short={"dbt": 66049}), "dbt: the array is shorter"),
     ("gscale shorter than the runs", dict(F["ws_wgrad<3>"], gscale=2.0, short={"gscale": 1}), "gscale: one float per run"),
+    # combinations the launcher's table has no instantiation for (the predicates ask the launchers' selectors, csrc/ws_gemm.h)
+    ("fwd3: tail, stored activation and discarded h0", dict(F["ws_fwd3<1,1,1,1,0>"], discard=True), "refused by ws_fwd3_supported"),
+    ("fwd3: tail, stored activation and discarded h0, other depth", dict(F["ws_fwd3<1,1,1,1,0>"], discard=True, M=352, per_z=3), "refused by ws_fwd3_supported"),
+    ("fwd3: neither tail nor Y", dict(F["ws_fwd3<0,1,0,0,0>"], sy=False), "refused by ws_fwd3_supported"),
+    ("fwd3: neither tail nor Y, fused first layer", dict(F["ws_fwd3<0,1,1,1,0>"], sy=False), "refused by ws_fwd3_supported"),
+    ("fwd: neither tail nor Y", dict(F["ws_fwd<0,0,0,1,0,1>"], sy=False), "refused by ws_fwd_supported"),
+    ("wgrad: np3 with H1", dict(F["ws_wgrad<1>"], np3=1), "np3 is the derived-tail flavour"),
 ]
 
 
@@ -234,6 +241,15 @@ def test_refusals_of_array_combinations():
     ]:
         with pytest.raises(RuntimeError, match="orl_debug_ws failed: orl_debug_ws: .*" + msg):
             _engine.debug_ws(c.kind, c.arrays, **c.ints)
+    # dgrad3: both or neither of w0_out and C -- no such instantiation (ws_dgrad3_flavour)
+    c = w.build(**F["ws_dgrad3<0,0>"])
+    del c.arrays["C"]
+    with pytest.raises(RuntimeError, match="give either the dW0 / db0 slabs .w0_out, b0_out. or C .the stored dz0., not both and not neither"):
+        _engine.debug_ws(c.kind, c.arrays, **c.ints)
+    c, both = w.build(**F["ws_dgrad3<1,0>"]), w.build(**F["ws_dgrad3<0,0>"])
+    c.arrays["C"] = both.arrays["C"]
+    with pytest.raises(RuntimeError, match="give either the dW0 / db0 slabs .w0_out, b0_out. or C .the stored dz0., not both and not neither"):
+        _engine.debug_ws(c.kind, c.arrays, **c.ints)
     # np3 with H1: the three-plane wgrad is the derived-tail flavour
     c = w.build(**dict(F["ws_wgrad<1>"], np3=1))
     with pytest.raises(RuntimeError, match="np3 is the derived-tail flavour"):
