@@ -290,6 +290,46 @@ int orl_buffer_append_rollout_runs(orl_buffer* const* rings, int32_t n_runs, int
 /* rows [row0, row0 + n) of the store back to packed host arrays (sample_all, buffer/buffer.py:108-115, and tests); a ring may be read
  * up to its capacity (rows never written are zero) */
 int orl_buffer_read(orl_buffer* b, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term);
+
+/* -- trajectory store: the RCSL rollout's bookkeeping (policy/rcsl/rcsl.py:57-120) kept in HBM --------------------------------
+ * Rows of up to `capacity_rows` transitions of up to `n_traj` trajectories: obs / next_obs / act (the padded pitches of orl_buffer, pad
+ * columns zero), rew and term (0 / 1) float32, the trajectory index int32, the return accumulated BEFORE the transition and the
+ * return-to-go float64; per trajectory its return, float64; and the live trajectories -- (index, accumulated return) pairs -- in two
+ * arrays that the steps fill alternately.  float64 because the reference keeps `returns` / `acc_returns` in np.zeros arrays and adds
+ * the float32 rewards to them: the same promotion and the same single add per step give the same bits. */
+typedef struct orl_traj orl_traj;
+int orl_traj_create(int32_t obs_dim, int32_t act_dim, int32_t device, int64_t n_traj, int64_t capacity_rows, orl_traj** out);
+void orl_traj_destroy(orl_traj* t);
+/* a new rollout of n_traj trajectories (at most the count given at creation): no rows, returns 0, live = 0 .. n_traj - 1 with
+ * accumulated return 0, reward sum 0 */
+int orl_traj_reset(orl_traj* t, int64_t n_traj);
+/* the loop body of rollout() (rcsl.py:72-105) for one model step; every array pointer is a DEVICE pointer to a packed array and row i
+ * belongs to the i-th live trajectory, so n must equal the live count.  Evaluates the termination test `term_kind` (as in
+ * orl_buffer_append_rollout) on next_obs; appends the n transitions with terminals = the test's result, traj_idx = the live index and
+ * acc_ret = the live accumulated return; adds rew (promoted to float64) to the trajectory's return -- a trajectory has one live row,
+ * so a plain store --; writes the survivors' next_obs rows densely and IN THEIR ORIGINAL ORDER to alive_next_obs (room for n rows, not
+ * overlapping next_obs) and their (index, accumulated return + rew) pairs, in the same order, to the other live array; adds the
+ * float64 sum of rew, formed in block order, to the running reward sum.  The survivor count comes back through the HOST pointer
+ * n_alive: the one device-to-host read of a step (it sizes the next one).
+ * Refused before any launch: n != live count, more rows than the capacity left, an unknown kind, a kind that reads an observation
+ * column the store does not have (pen: column 26; hopper / walker2d: column 1), alive_next_obs == next_obs. */
+int orl_traj_append_step(orl_traj* t, int32_t term_kind, const float* obs, const float* act, const float* next_obs, const float* rew,
+                         int64_t n, float* alive_next_obs, int64_t* n_alive);
+/* the end of rollout() (rcsl.py:107-112): rtg[row] = returns[traj_idx[row]] - acc_ret[row] in float64.  HOST outputs, each may be
+ * NULL: the row count, the running reward sum, the n_traj returns.  Calling it twice is harmless; a later append_step needs a new
+ * finish before the returns-to-go are read or exported. */
+int orl_traj_finish(orl_traj* t, int64_t* rows, double* reward_sum, double* returns_host);
+/* rows [row0, row0 + n) back to packed host arrays (obs / next_obs [n][obs_dim], act [n][act_dim], the rest [n]); any pointer may
+ * be NULL; rtg after orl_traj_finish only */
+int orl_traj_read(orl_traj* t, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term,
+                  int32_t* traj_idx, double* acc_ret, double* rtg);
+/* run_mbrcsl.py's filter and the RCSL dataset in one: after orl_traj_finish, appends the rows of the trajectories with
+ * returns > threshold (float64 compare, false on NaN; use_threshold == 0 keeps every row), in their order, behind the rows of the
+ * reserved ring `dst`: obs / act / next_obs / term as stored, rew := (float)rtg -- the layout orl_learn_epoch reads.  The ring's size
+ * cell is published as by orl_buffer_append.  HOST outputs: the rows appended, the trajectories above the threshold (all of them
+ * without one).  The kept rows are counted first, so every refusal happens before a row is written: dst is not a ring, its dims or
+ * device differ, or the kept rows exceed capacity - size (an RCSL dataset must not wrap). */
+int orl_traj_export(orl_traj* t, int use_threshold, double threshold, orl_buffer* dst, int64_t* rows_kept, int64_t* traj_kept);
 /* the real + model batch of MBPolicyTrainer (policy_trainer/mb_policy_trainer.py:78-85; _cat of mopo.py:81-84, combo.py:111-113) inside
  * orl_learn_n: batch rows [0, real_rows) are drawn from the buffer of orl_engine_attach_buffer, rows [real_rows, batch_size) from the
  * ring `model`; every row keeps its Philox counter.  0 < real_rows < batch_size, same dims and device as the engine; NULL detaches.

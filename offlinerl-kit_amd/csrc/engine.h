@@ -112,6 +112,21 @@ struct Buffer {             // HBM-resident replay buffer (buffer/buffer.py)
   ~Buffer();
 };
 
+struct Traj {               // HBM-resident trajectory store of the RCSL rollout (policy/rcsl/rcsl.py:57-120): orl_traj
+  int dev = 0, od = 0, ad = 0, OP = 0, AP = 0;
+  long n_traj_cap = 0, cap = 0;           // sizes given at creation: trajectories, rows
+  long n_traj = 0, rows = 0, live = 0;    // of the current rollout: trajectories, rows appended, trajectories still running
+  int half = 0;                           // which of the two live arrays holds the running trajectories
+  bool finished = false;                  // rtg[] is valid for rows [0, rows)
+  float *obs = nullptr, *nobs = nullptr, *act = nullptr, *rew = nullptr, *term = nullptr;
+  int* tidx = nullptr; double *acc = nullptr, *rtg = nullptr;
+  double* returns = nullptr;
+  int* live_idx[2] = {nullptr, nullptr}; double* live_acc[2] = {nullptr, nullptr};
+  int* blk_cnt = nullptr; double* blk_rew = nullptr;      // per-block scratch: max(blocks of a step, blocks of an export)
+  long long* cells = nullptr; double* rew_total = nullptr; // 3 result cells, the running reward sum
+  ~Traj();
+};
+
 struct DY;  // backward seed description (engine.hip)
 
 struct Engine {

@@ -226,6 +226,13 @@ Buffer::~Buffer() {
   if (roll_rew) hipFree(roll_rew);
   if (runs_scratch) hipFree(runs_scratch);
 }
+Traj::~Traj() {
+  hipSetDevice(dev);
+  for (void* p : {(void*)obs, (void*)nobs, (void*)act, (void*)rew, (void*)term, (void*)tidx, (void*)acc, (void*)rtg, (void*)returns,
+                  (void*)live_idx[0], (void*)live_idx[1], (void*)live_acc[0], (void*)live_acc[1], (void*)blk_cnt, (void*)blk_rew,
+                  (void*)cells, (void*)rew_total})
+    if (p) hipFree(p);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Engine basics
@@ -1479,6 +1486,9 @@ struct orl_engine {
 struct orl_buffer {
   Buffer b;
 };
+struct orl_traj {
+  Traj t;
+};
 
 extern "C" {
 
@@ -1870,6 +1880,173 @@ int orl_buffer_read(orl_buffer* h, int64_t row0, int64_t n, float* obs, float* a
   return 0;
 }
 int64_t orl_buffer_size(orl_buffer* h) { return h->b.n; }
+
+// ---- trajectory store (the RCSL rollout) ----
+static int traj_alloc_bytes(void** p, size_t bytes) {
+  ORL_HIP(hipMalloc(p, bytes));
+  ORL_HIP(hipMemset(*p, 0, bytes));
+  return 0;
+}
+#define traj_alloc(pp, n) traj_alloc_bytes((void**)(pp), sizeof(**(pp)) * (size_t)(n))
+static TrajP traj_params(Traj& t) {
+  TrajP p;
+  memset(&p, 0, sizeof(p));
+  p.obs = t.obs; p.nobs = t.nobs; p.act = t.act; p.rew = t.rew; p.term = t.term; p.tidx = t.tidx; p.acc = t.acc; p.rtg = t.rtg;
+  p.OP = t.OP; p.AP = t.AP; p.od = t.od; p.ad = t.ad; p.returns = t.returns; p.n_traj = t.n_traj;
+  p.live_idx = t.live_idx[t.half]; p.live_acc = t.live_acc[t.half]; p.next_idx = t.live_idx[t.half ^ 1]; p.next_acc = t.live_acc[t.half ^ 1];
+  p.blk_cnt = t.blk_cnt; p.blk_rew = t.blk_rew; p.cells = t.cells; p.rew_total = t.rew_total;
+  return p;
+}
+int orl_traj_create(int32_t obs_dim, int32_t act_dim, int32_t device, int64_t n_traj, int64_t capacity_rows, orl_traj** out) {
+  if (!out || obs_dim < 1 || act_dim < 1 || n_traj < 1 || capacity_rows < 1 || n_traj > 0x7fffffffLL || capacity_rows > 0x7fffffffLL)
+    return fail("orl_traj_create: bad arguments");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device available: the trajectory store lives in MI355X HBM");
+  if (device < 0 || device >= ndev) return fail("bad device ordinal");
+  ORL_HIP(hipSetDevice(device));
+  orl_traj* h = new orl_traj();
+  Traj& t = h->t;
+  t.dev = device; t.od = obs_dim; t.ad = act_dim; t.OP = rup(obs_dim, 4); t.AP = rup(act_dim, 4);
+  t.n_traj_cap = n_traj; t.cap = capacity_rows;
+  const long blocks = (std::max((long)n_traj, (long)capacity_rows) + 255) / 256;
+  if (traj_alloc(&t.obs, t.cap * t.OP) || traj_alloc(&t.nobs, t.cap * t.OP) || traj_alloc(&t.act, t.cap * t.AP) || traj_alloc(&t.rew, t.cap) ||
+      traj_alloc(&t.term, t.cap) || traj_alloc(&t.tidx, t.cap) || traj_alloc(&t.acc, t.cap) || traj_alloc(&t.rtg, t.cap) ||
+      traj_alloc(&t.returns, n_traj) || traj_alloc(&t.live_idx[0], n_traj) || traj_alloc(&t.live_idx[1], n_traj) ||
+      traj_alloc(&t.live_acc[0], n_traj) || traj_alloc(&t.live_acc[1], n_traj) || traj_alloc(&t.blk_cnt, blocks) ||
+      traj_alloc(&t.blk_rew, blocks) || traj_alloc(&t.cells, 3) || traj_alloc(&t.rew_total, 1)) {
+    delete h;
+    *out = nullptr;
+    return -1;
+  }
+  *out = h;
+  return orl_traj_reset(h, n_traj);
+}
+void orl_traj_destroy(orl_traj* h) { delete h; }
+int orl_traj_reset(orl_traj* h, int64_t n_traj) {
+  if (!h || n_traj < 1) return fail("orl_traj_reset: bad arguments");
+  Traj& t = h->t;
+  if (n_traj > t.n_traj_cap) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "orl_traj_reset: %lld trajectories, the store was created for %lld", (long long)n_traj, (long long)t.n_traj_cap);
+    return fail(msg);
+  }
+  ORL_HIP(hipSetDevice(t.dev));
+  t.n_traj = n_traj; t.rows = 0; t.live = n_traj; t.half = 1; t.finished = false;
+  TrajP p = traj_params(t);                 // (half = 1: the kernel fills the `next` half, 0, which then becomes the current one)
+  hipLaunchKernelGGL(k_traj_reset, dim3((unsigned)((n_traj + 255) / 256)), dim3(256), 0, 0, p);
+  ORL_HIP(hipGetLastError());
+  t.half = 0;
+  return 0;
+}
+int orl_traj_append_step(orl_traj* h, int32_t term_kind, const float* obs, const float* act, const float* next_obs, const float* rew, int64_t n,
+                         float* alive_next_obs, int64_t* n_alive) {
+  if (!h || !obs || !act || !next_obs || !rew || !alive_next_obs || !n_alive || n < 1) return fail("orl_traj_append_step: bad arguments");
+  Traj& t = h->t;
+  char msg[200];
+  if (n != t.live) {
+    snprintf(msg, sizeof(msg), "orl_traj_append_step: %lld rows, %lld trajectories are live", (long long)n, (long long)t.live);
+    return fail(msg);
+  }
+  if (t.rows + n > t.cap) {
+    snprintf(msg, sizeof(msg), "orl_traj_append_step: %lld rows + %lld more than the store's capacity %lld", (long long)t.rows, (long long)n, (long long)t.cap);
+    return fail(msg);
+  }
+  if (term_kind < 0 || term_kind >= ORL_TERM_KINDS) return fail("orl_traj_append_step: unknown termination kind");
+  const int need = term_kind == ORL_TERM_PEN ? 27 : ((term_kind == ORL_TERM_HOPPER || term_kind == ORL_TERM_WALKER2D) ? 2 : 1);
+  if (t.od < need) {
+    snprintf(msg, sizeof(msg), "orl_traj_append_step: termination kind %d reads observation column %d, the buffer has %d columns", (int)term_kind, need - 1, t.od);
+    return fail(msg);
+  }
+  if (alive_next_obs == next_obs) return fail("orl_traj_append_step: alive_next_obs must not overlap next_obs");
+  ORL_HIP(hipSetDevice(t.dev));
+  TrajP p = traj_params(t);
+  p.kind = term_kind; p.s_obs = obs; p.s_act = act; p.s_nobs = next_obs; p.s_rew = rew; p.row0 = t.rows; p.n = n; p.alive_nobs = alive_next_obs;
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(k_traj_term, dim3(blocks), dim3(256), 0, 0, p);
+  ORL_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_traj_scatter, dim3(blocks), dim3(256), 0, 0, p);
+  ORL_HIP(hipGetLastError());
+  long long na = 0;
+  ORL_HIP(hipMemcpy(&na, t.cells, sizeof(na), hipMemcpyDeviceToHost));      // the one read of a step: it sizes the next one
+  t.rows += n; t.live = na; t.half ^= 1; t.finished = false;
+  *n_alive = na;
+  return 0;
+}
+int orl_traj_finish(orl_traj* h, int64_t* rows, double* reward_sum, double* returns_host) {
+  if (!h) return fail("orl_traj_finish: bad arguments");
+  Traj& t = h->t;
+  ORL_HIP(hipSetDevice(t.dev));
+  if (t.rows > 0) {
+    TrajP p = traj_params(t);
+    p.n = t.rows;
+    hipLaunchKernelGGL(k_traj_finish, dim3((unsigned)((t.rows + 255) / 256)), dim3(256), 0, 0, p);
+    ORL_HIP(hipGetLastError());
+  }
+  ORL_HIP(hipDeviceSynchronize());
+  t.finished = true;
+  if (rows) *rows = t.rows;
+  if (reward_sum) ORL_HIP(hipMemcpy(reward_sum, t.rew_total, sizeof(double), hipMemcpyDeviceToHost));
+  if (returns_host) ORL_HIP(hipMemcpy(returns_host, t.returns, sizeof(double) * t.n_traj, hipMemcpyDeviceToHost));
+  return 0;
+}
+int orl_traj_read(orl_traj* h, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term, int32_t* traj_idx,
+                  double* acc_ret, double* rtg) {
+  if (!h || n < 0 || row0 < 0) return fail("orl_traj_read: bad arguments");
+  Traj& t = h->t;
+  if (row0 + n > t.rows) return fail("orl_traj_read: rows beyond the store");
+  if (rtg && !t.finished) return fail("orl_traj_read: the returns-to-go exist after orl_traj_finish");
+  if (n == 0) return 0;
+  ORL_HIP(hipSetDevice(t.dev));
+  ORL_HIP(hipDeviceSynchronize());
+  if (obs) ORL_HIP(hipMemcpy2D(obs, sizeof(float) * t.od, t.obs + row0 * t.OP, sizeof(float) * t.OP, sizeof(float) * t.od, n, hipMemcpyDeviceToHost));
+  if (next_obs) ORL_HIP(hipMemcpy2D(next_obs, sizeof(float) * t.od, t.nobs + row0 * t.OP, sizeof(float) * t.OP, sizeof(float) * t.od, n, hipMemcpyDeviceToHost));
+  if (act) ORL_HIP(hipMemcpy2D(act, sizeof(float) * t.ad, t.act + row0 * t.AP, sizeof(float) * t.AP, sizeof(float) * t.ad, n, hipMemcpyDeviceToHost));
+  if (rew) ORL_HIP(hipMemcpy(rew, t.rew + row0, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (term) ORL_HIP(hipMemcpy(term, t.term + row0, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (traj_idx) ORL_HIP(hipMemcpy(traj_idx, t.tidx + row0, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (acc_ret) ORL_HIP(hipMemcpy(acc_ret, t.acc + row0, sizeof(double) * n, hipMemcpyDeviceToHost));
+  if (rtg) ORL_HIP(hipMemcpy(rtg, t.rtg + row0, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+int orl_traj_export(orl_traj* h, int use_threshold, double threshold, orl_buffer* dst, int64_t* rows_kept, int64_t* traj_kept) {
+  if (!h || !dst) return fail("orl_traj_export: bad arguments");
+  Traj& t = h->t;
+  Buffer& b = dst->b;
+  char msg[224];
+  if (!t.finished) return fail("orl_traj_export: the returns-to-go exist after orl_traj_finish");
+  if (b.cap < 1) return fail("orl_traj_export: the destination is not a ring (orl_buffer_reserve first)");
+  if (b.od != t.od || b.ad != t.ad || b.dev != t.dev) {
+    snprintf(msg, sizeof(msg), "orl_traj_export: the ring's dims / device (%d, %d, device %d) differ from the store's (%d, %d, device %d)", b.od, b.ad,
+             b.dev, t.od, t.ad, t.dev);
+    return fail(msg);
+  }
+  ORL_HIP(hipSetDevice(t.dev));
+  long long res[2] = {0, 0};
+  TrajP p = traj_params(t);
+  p.n = t.rows; p.use_thr = use_threshold ? 1 : 0; p.thr = threshold;
+  const long blocks = (t.rows + 255) / 256;
+  if (blocks > 0) {
+    hipLaunchKernelGGL(k_traj_count, dim3((unsigned)blocks), dim3(256), 0, 0, p);
+    ORL_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_traj_total, dim3(1), dim3(256), 0, 0, p, blocks);
+  ORL_HIP(hipGetLastError());
+  ORL_HIP(hipMemcpy(res, t.cells + 1, sizeof(res), hipMemcpyDeviceToHost));
+  if (res[0] > b.cap - b.n) {               // (an RCSL dataset does not wrap; nothing has been written)
+    snprintf(msg, sizeof(msg), "orl_traj_export: %lld rows to keep, the ring has room for %lld (capacity %lld, size %lld)", res[0],
+             (long long)(b.cap - b.n), (long long)b.cap, (long long)b.n);
+    return fail(msg);
+  }
+  if (rows_kept) *rows_kept = res[0];
+  if (traj_kept) *traj_kept = res[1];
+  if (res[0] == 0) return 0;
+  p.d_obs = b.obs; p.d_nobs = b.nobs; p.d_act = b.act; p.d_rew = b.rew; p.d_term = b.term; p.d_row0 = b.ptr;      // (size < capacity: ptr == size)
+  hipLaunchKernelGGL(k_traj_export, dim3((unsigned)blocks), dim3(256), 0, 0, p);
+  ORL_HIP(hipGetLastError());
+  b.ptr = (b.ptr + res[0]) % b.cap;
+  b.n += res[0];
+  return ring_publish(b);
+}
 int orl_buffer_normalize_obs(orl_buffer* h, float eps, float* mean_out, float* std_out) {
   Buffer& b = h->b;
   if (!b.obs || b.n < 1) return fail("normalize_obs: empty buffer");

@@ -214,9 +214,33 @@ __global__ void k_roll_term(RollP p) {
     p.blk_rew[(long)r * gridDim.x + blockIdx.x] = ((sh_r[0] + sh_r[1]) + sh_r[2]) + sh_r[3];
   }
 }
-__global__ void k_roll_scatter(RollP p) {
+// The stable rank of a flagged row among ALL flagged rows of a launch of 256-thread blocks, -1 for a row that is not flagged: the flagged
+// rows of the blocks in front (blk_cnt[0 .. blockIdx.x), written by the counting pass; integers, so the order of the sum does not
+// matter), those of the waves in front within the block, and the wave-ballot rank (64 lanes, 64-bit masks).  Every thread of the block
+// calls it, once per kernel (it owns its shared memory and has barriers inside).  k_roll_scatter, k_traj_scatter and k_traj_export
+// compact with it.
+__device__ inline int orl_stable_rank(bool flag, const int* blk_cnt) {
   __shared__ int sh_part[256];
   __shared__ int sh_w[4];
+  const int tid = threadIdx.x;
+  int part = 0;
+  for (int b = tid; b < (int)blockIdx.x; b += 256) part += blk_cnt[b];
+  sh_part[tid] = part;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) sh_part[tid] += sh_part[tid + o];
+    __syncthreads();
+  }
+  const int blk_off = sh_part[0];
+  const unsigned long long m = __ballot(flag);
+  const int lane = tid & 63, w = tid >> 6;
+  if (lane == 0) sh_w[w] = __popcll(m);
+  __syncthreads();
+  int woff = 0;
+  for (int k = 0; k < w; ++k) woff += sh_w[k];
+  return flag ? blk_off + woff + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+}
+__global__ void k_roll_scatter(RollP p) {
   __shared__ int sh_dst[256];
   const int tid = threadIdx.x, r = blockIdx.y;
   const RollRing g = p.tab ? p.tab[r] : p.ring;
@@ -232,24 +256,8 @@ __global__ void k_roll_scatter(RollP p) {
   const float *s_act = p.act + (long)r * p.row_stride * p.ad, *s_rew = p.rew + (long)r * p.row_stride;
   float* alive_nobs = p.alive_nobs + (long)r * p.row_stride * p.od;
   const int* blk_alive = p.blk_alive + (long)r * gridDim.x;
-  // alive rows of the blocks in front of this one (integers: the order of the sum does not matter)
-  int part = 0;
-  for (int b = tid; b < (int)blockIdx.x; b += 256) part += blk_alive[b];
-  sh_part[tid] = part;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sh_part[tid] += sh_part[tid + o];
-    __syncthreads();
-  }
-  const int blk_off = sh_part[0];
   const bool alive = i < g.n && g.term[(g.ptr + i) % g.cap] == 0.0f;
-  const unsigned long long m = __ballot(alive);
-  const int lane = tid & 63, w = tid >> 6;
-  if (lane == 0) sh_w[w] = __popcll(m);
-  __syncthreads();
-  int woff = 0;
-  for (int k = 0; k < w; ++k) woff += sh_w[k];
-  sh_dst[tid] = alive ? blk_off + woff + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+  sh_dst[tid] = orl_stable_rank(alive, blk_alive);
   __syncthreads();
   const int rows = (int)(g.n - row0 < 256 ? g.n - row0 : 256);
   for (int e = tid; e < rows * g.OP; e += 256) {
@@ -276,6 +284,157 @@ __global__ void k_roll_scatter(RollP p) {
     p.n_alive_out[r] = na; p.rew_sum_out[r] = rs;
     if (g.size_cell) *g.size_cell = g.size;
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// the trajectory store (orl_traj): the bookkeeping of the RCSL rollout (policy/rcsl/rcsl.py:57-120) on the device.  A row carries, next to
+// the transition, its trajectory, the return accumulated BEFORE it and -- after k_traj_finish -- its return-to-go; returns / accumulated
+// returns are float64 because the host keeps them in np.zeros arrays (float64 + float32 promoted, one add per step: the same rounding).
+// A step is the launch pair of the ring rollout: k_traj_term (terminals, per-block alive count and reward sum), k_traj_scatter (rows,
+// stable compaction of the survivors' next_obs and of the live (trajectory, accumulated return) pairs into the other half of the
+// ping-pong arrays).  A trajectory has at most one live row, so returns[] is updated by a plain read-add-store.  The export is the
+// same two-pass compaction over the stored rows: k_traj_count / k_traj_total count (the host refuses a ring that is too small before a
+// row is written), k_traj_export scatters.  Fixed block order everywhere, no tickets, no atomics.
+// ------------------------------------------------------------------------------------------------
+struct TrajP {
+  float *obs, *nobs, *act, *rew, *term; int* tidx; double *acc, *rtg;   // the rows: [cap][OP], [cap][OP], [cap][AP], [cap] each
+  int OP, AP, od, ad;
+  double* returns;                                                       // [n_traj]
+  long n_traj;
+  const int* live_idx; const double* live_acc;                           // the live trajectories of this step, [n]
+  int* next_idx; double* next_acc;                                       // ... of the next one (the other half)
+  int kind;
+  const float *s_obs, *s_act, *s_nobs, *s_rew;                           // packed sources [n][od], [n][ad], [n][od], [n]
+  long row0, n;                                                          // step: rows [row0, row0 + n) are appended; finish / export: rows [0, n)
+  float* alive_nobs;
+  int* blk_cnt; double* blk_rew;                                         // per-block scratch
+  long long* cells;                                                      // [0] survivors of the step, [1] rows kept, [2] trajectories kept
+  double* rew_total;                                                     // running sum of every appended reward
+  int use_thr; double thr;                                               // export: keep rows of trajectories with returns > thr
+  float *d_obs, *d_nobs, *d_act, *d_rew, *d_term; long d_row0;           // export: the destination ring (same pitches) and its first free row
+};
+__global__ void k_traj_reset(TrajP p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < p.n_traj) { p.returns[i] = 0.0; p.next_idx[i] = (int)i; p.next_acc[i] = 0.0; }
+  if (i == 0) *p.rew_total = 0.0;
+}
+__global__ void k_traj_term(TrajP p) {
+  __shared__ int sh_a[4];
+  __shared__ double sh_r[4];
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  bool alive = false;
+  double rw = 0.0;
+  if (i < p.n) {
+    const bool done = orl_term_done(p.kind, p.s_nobs + i * p.od, p.od);
+    p.term[p.row0 + i] = done ? 1.0f : 0.0f;
+    alive = !done;
+    rw = (double)p.s_rew[i];
+  }
+  const unsigned long long m = __ballot(alive);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rw += __shfl_down(rw, o, 64);
+  if ((threadIdx.x & 63) == 0) { sh_a[threadIdx.x >> 6] = __popcll(m); sh_r[threadIdx.x >> 6] = rw; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    p.blk_cnt[blockIdx.x] = sh_a[0] + sh_a[1] + sh_a[2] + sh_a[3];
+    p.blk_rew[blockIdx.x] = ((sh_r[0] + sh_r[1]) + sh_r[2]) + sh_r[3];
+  }
+}
+__global__ void k_traj_scatter(TrajP p) {
+  __shared__ int sh_dst[256];
+  const int tid = threadIdx.x;
+  const long b0 = (long)blockIdx.x * 256, i = b0 + tid;
+  const bool alive = i < p.n && p.term[p.row0 + i] == 0.0f;
+  const int d = orl_stable_rank(alive, p.blk_cnt);
+  sh_dst[tid] = d;
+  __syncthreads();
+  const int rows = (int)(p.n - b0 < 256 ? p.n - b0 : 256);
+  for (int e = tid; e < rows * p.OP; e += 256) {
+    const int row = e / p.OP, c = e - row * p.OP;
+    const long src = (b0 + row) * p.od + c, dst = (p.row0 + b0 + row) * p.OP + c;
+    p.obs[dst] = c < p.od ? p.s_obs[src] : 0.f;
+    p.nobs[dst] = c < p.od ? p.s_nobs[src] : 0.f;
+  }
+  for (int e = tid; e < rows * p.AP; e += 256) {
+    const int row = e / p.AP, c = e - row * p.AP;
+    p.act[(p.row0 + b0 + row) * p.AP + c] = c < p.ad ? p.s_act[(b0 + row) * p.ad + c] : 0.f;
+  }
+  for (int e = tid; e < rows * p.od; e += 256) {
+    const int row = e / p.od, c = e - row * p.od;
+    const int dd = sh_dst[row];
+    if (dd >= 0) p.alive_nobs[(long)dd * p.od + c] = p.s_nobs[(b0 + row) * p.od + c];
+  }
+  if (i < p.n) {
+    const int t = p.live_idx[i];
+    const double a = p.live_acc[i], r = (double)p.s_rew[i];
+    p.rew[p.row0 + i] = p.s_rew[i];
+    p.tidx[p.row0 + i] = t;
+    p.acc[p.row0 + i] = a;
+    p.returns[t] = p.returns[t] + r;        // (the only live row of trajectory t)
+    if (d >= 0) { p.next_idx[d] = t; p.next_acc[d] = a + r; }
+  }
+  if (blockIdx.x == 0 && tid == 0) {        // totals in block order
+    long long na = 0; double rs = 0.0;
+    for (int b = 0; b < (int)gridDim.x; ++b) { na += p.blk_cnt[b]; rs += p.blk_rew[b]; }
+    p.cells[0] = na;
+    *p.rew_total = *p.rew_total + rs;
+  }
+}
+__global__ void k_traj_finish(TrajP p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < p.n) p.rtg[i] = p.returns[p.tidx[i]] - p.acc[i];
+}
+// (a NaN return is not above any threshold, as in numpy)
+__device__ inline bool orl_traj_keep(int use_thr, double thr, const double* returns, int t) { return !use_thr || returns[t] > thr; }
+__global__ void k_traj_count(TrajP p) {
+  __shared__ int sh_a[4];
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const bool keep = i < p.n && orl_traj_keep(p.use_thr, p.thr, p.returns, p.tidx[i]);
+  const unsigned long long m = __ballot(keep);
+  if ((threadIdx.x & 63) == 0) sh_a[threadIdx.x >> 6] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) p.blk_cnt[blockIdx.x] = sh_a[0] + sh_a[1] + sh_a[2] + sh_a[3];
+}
+// one block: the kept rows (the sum of k_traj_count's `nblk` block counts) and the kept trajectories
+__global__ void k_traj_total(TrajP p, long nblk) {
+  __shared__ long long sh_r[256], sh_t[256];
+  const int tid = threadIdx.x;
+  long long r = 0, t = 0;
+  for (long b = tid; b < nblk; b += 256) r += p.blk_cnt[b];
+  for (long j = tid; j < p.n_traj; j += 256) t += orl_traj_keep(p.use_thr, p.thr, p.returns, (int)j) ? 1 : 0;
+  sh_r[tid] = r; sh_t[tid] = t;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) { sh_r[tid] += sh_r[tid + o]; sh_t[tid] += sh_t[tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) { p.cells[1] = sh_r[0]; p.cells[2] = sh_t[0]; }
+}
+// kept rows -> ring rows d_row0 + rank (the host has checked that they fit without wrapping), rew := (float)rtg
+__global__ void k_traj_export(TrajP p) {
+  __shared__ int sh_dst[256];
+  const int tid = threadIdx.x;
+  const long b0 = (long)blockIdx.x * 256, i = b0 + tid;
+  const bool keep = i < p.n && orl_traj_keep(p.use_thr, p.thr, p.returns, p.tidx[i]);
+  const int d = orl_stable_rank(keep, p.blk_cnt);
+  sh_dst[tid] = d;
+  __syncthreads();
+  const int rows = (int)(p.n - b0 < 256 ? p.n - b0 : 256);
+  for (int e = tid; e < rows * p.OP; e += 256) {
+    const int row = e / p.OP, c = e - row * p.OP;
+    const int dd = sh_dst[row];
+    if (dd >= 0) {
+      const long src = (b0 + row) * p.OP + c, dst = (p.d_row0 + dd) * p.OP + c;
+      p.d_obs[dst] = p.obs[src];
+      p.d_nobs[dst] = p.nobs[src];
+    }
+  }
+  for (int e = tid; e < rows * p.AP; e += 256) {
+    const int row = e / p.AP, c = e - row * p.AP;
+    const int dd = sh_dst[row];
+    if (dd >= 0) p.d_act[(p.d_row0 + dd) * p.AP + c] = p.act[(b0 + row) * p.AP + c];
+  }
+  if (d >= 0) { p.d_rew[p.d_row0 + d] = (float)p.rtg[i]; p.d_term[p.d_row0 + d] = p.term[i]; }
 }
 
 // normalize_obs (buffer.py:88-94): per-column mean / population std in double, then in-place scaling

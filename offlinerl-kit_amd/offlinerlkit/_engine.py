@@ -64,6 +64,8 @@ ABI_SYMBOLS = [
     "orl_learn_epoch",
     # the autoregressive behaviour policy: sequential sampling
     "orl_autoreg_sample",
+    # the RCSL rollout's trajectory store
+    "orl_traj_create", "orl_traj_destroy", "orl_traj_reset", "orl_traj_append_step", "orl_traj_finish", "orl_traj_read", "orl_traj_export",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -210,6 +212,14 @@ def load_library(path: Optional[str] = None):
     lib.orl_buffer_append_rollout_runs.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int32] + [C.c_void_p] * 4 + \
         [C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     lib.orl_engine_attach_model_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32]
+    lib.orl_traj_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
+    lib.orl_traj_destroy.argtypes = [C.c_void_p]
+    lib.orl_traj_destroy.restype = None
+    lib.orl_traj_reset.argtypes = [C.c_void_p, C.c_int64]
+    lib.orl_traj_append_step.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.orl_traj_finish.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p]
+    lib.orl_traj_read.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 8
+    lib.orl_traj_export.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.orl_step.argtypes = [C.c_void_p, C.POINTER(OrlBatch), C.POINTER(OrlNoise), C.c_void_p]
     lib.orl_learn_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_learn_epoch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
@@ -768,6 +778,79 @@ class DeviceBuffer:
             assert idx.size == batch
             p = idx.ctypes.data
         _check(self.lib.orl_buffer_sample(self._h, p, batch, seed, obs_ptr, act_ptr, nobs_ptr, rew_ptr, term_ptr), "orl_buffer_sample")
+
+
+class TrajStore:
+    """RAII wrapper over ``orl_traj*``: the HBM-resident trajectory store of the RCSL rollout (rows with their trajectory index,
+    accumulated return and return-to-go; per-trajectory returns; the live trajectories)."""
+
+    def __init__(self, obs_dim: int, act_dim: int, n_traj: int, capacity_rows: int, device: int = 0):
+        self.lib = load_library()
+        self.obs_dim, self.act_dim, self.device = int(obs_dim), int(act_dim), int(device)
+        self.max_traj, self.capacity_rows, self.n_traj = int(n_traj), int(capacity_rows), int(n_traj)
+        self._h = C.c_void_p()
+        _check(self.lib.orl_traj_create(self.obs_dim, self.act_dim, self.device, self.max_traj, self.capacity_rows, C.byref(self._h)),
+               "orl_traj_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.lib.orl_traj_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, n_traj: int):
+        _check(self.lib.orl_traj_reset(self._h, int(n_traj)), "orl_traj_reset")
+        self.n_traj = int(n_traj)
+
+    def append_step(self, term_kind: int, obs, act, next_obs, rew, alive_next_obs) -> int:
+        """one model step of the rollout (orl_traj_append_step): contiguous fp32 torch tensors on the store's device, row i of the i-th
+        live trajectory; ``alive_next_obs`` has room for every row.  Returns the survivor count."""
+        import torch
+        n = int(obs.shape[0])
+        for name, t, shape in (("obs", obs, (n, self.obs_dim)), ("act", act, (n, self.act_dim)), ("next_obs", next_obs, (n, self.obs_dim)),
+                               ("rew", rew, None), ("alive_next_obs", alive_next_obs, None)):
+            if not _is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" \
+                    or (t.device.index or 0) != self.device:
+                raise ValueError(f"append_step: {name} must be a contiguous fp32 tensor on the store's device")
+            if shape is not None and tuple(t.shape) != shape:
+                raise ValueError(f"append_step: {name} has shape {tuple(t.shape)}, expected {shape}")
+        if rew.numel() != n or alive_next_obs.numel() < n * self.obs_dim:
+            raise ValueError("append_step: rew needs n values, alive_next_obs room for n rows")
+        torch.cuda.current_stream(obs.device).synchronize()
+        na = C.c_int64()
+        _check(self.lib.orl_traj_append_step(self._h, int(term_kind), obs.data_ptr(), act.data_ptr(), next_obs.data_ptr(), rew.data_ptr(), n,
+                                             alive_next_obs.data_ptr(), C.byref(na)), "orl_traj_append_step")
+        return int(na.value)
+
+    def finish(self):
+        """the returns-to-go of every row (orl_traj_finish) -> (rows, float64 reward sum, returns float64 [n_traj])"""
+        rows, rs = C.c_int64(), C.c_double()
+        returns = np.empty(self.n_traj, dtype=np.float64)
+        _check(self.lib.orl_traj_finish(self._h, C.byref(rows), C.byref(rs), returns.ctypes.data), "orl_traj_finish")
+        return int(rows.value), float(rs.value), returns
+
+    def read(self, row0: int, n: int) -> Dict[str, np.ndarray]:
+        """host copies of rows [row0, row0 + n): obs, act, next_obs, rew [n], term [n] fp32, traj_idx int32 [n], acc_ret / rtg float64 [n]"""
+        n = int(n)
+        out = dict(obs=np.empty((n, self.obs_dim), np.float32), act=np.empty((n, self.act_dim), np.float32),
+                   next_obs=np.empty((n, self.obs_dim), np.float32), rew=np.empty(n, np.float32), term=np.empty(n, np.float32),
+                   traj_idx=np.empty(n, np.int32), acc_ret=np.empty(n, np.float64), rtg=np.empty(n, np.float64))
+        _check(self.lib.orl_traj_read(self._h, int(row0), n, *[out[k].ctypes.data for k in ("obs", "act", "next_obs", "rew", "term", "traj_idx",
+                                                                                            "acc_ret", "rtg")]), "orl_traj_read")
+        return out
+
+    def export(self, ring: "DeviceBuffer", threshold: Optional[float] = None):
+        """the rows of the trajectories with ``returns > threshold`` (all rows without one) appended to the reserved ring ``ring`` with
+        the return-to-go in its reward column (orl_traj_export) -> (rows kept, trajectories kept)"""
+        rk, tk = C.c_int64(), C.c_int64()
+        _check(self.lib.orl_traj_export(self._h, int(threshold is not None), float(0.0 if threshold is None else threshold), ring._h,
+                                        C.byref(rk), C.byref(tk)), "orl_traj_export")
+        return int(rk.value), int(tk.value)
 
 
 def debug_gemm(cfg: int, mode: int, A, B, v0=None, v1=None, ksplit=1, precision=0, M=None, N=None, K=None) -> np.ndarray:

@@ -6,7 +6,9 @@ MSE on the dataset action) and the Gaussian one (``ORL_ALGO_RCSL_GAUSS``: the sa
 clamped state-conditioned sigma, Gaussian NLL); ``learn_epoch`` is one ordered pass over the dataset (``orl_learn_epoch``).  Their
 ``rollout`` rolls a behaviour policy through a dynamics model; the behaviour policy here is ``AutoregressivePolicy``
 (``ORL_ALGO_AUTOREG``: p(a | s) as a product of per-dimension Gaussians from one LeakyReLU net, trained on the act_dim-fold expanded
-batch and sampled by ``orl_autoreg_sample``).
+batch and sampled by ``orl_autoreg_sample``).  ``rollout_device`` is that rollout with every array in HBM: ``select_action_device``,
+``EnsembleDynamics.step_device`` and the trajectory store (``orl_traj_*``: per-row trajectory index, accumulated return and return-to-go,
+float64 returns), whose thresholded export is the ``DeviceBuffer`` ``learn_epoch`` reads; ``rcsl.collect_rollouts_device`` loops the two.
 (The reference package also exports the diffusion behaviour policy, which needs ``diffusers``; it is out of scope here.)"""
 from .base_policy import BasePolicy, EnginePolicy
 from .iql import IQLPolicy

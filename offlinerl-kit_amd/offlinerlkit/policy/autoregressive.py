@@ -121,17 +121,23 @@ class AutoregressivePolicy(_EpochPolicy):
         """Sampled actions for ``obs`` [n, obs_dim], any n (the reference's ``forward`` serves one row: its ``if logstd.exp() == 0`` raises
         on more; batched rows are its row-wise generalisation).  The standard normals are ``torch.randn((n, act_dim))`` on the device's
         torch generator, so ``torch.manual_seed`` reproduces; ``rtg`` is accepted and ignored.  With several runs: the selected run's."""
+        return self.select_action_device(torch.as_tensor(np.asarray(obs, dtype=np.float32))).cpu().numpy()
+
+    def select_action_device(self, obs: torch.Tensor) -> torch.Tensor:
+        """``select_action`` without the host round trip: ``obs`` [n, obs_dim] (moved to the engine's device when it is elsewhere) ->
+        actions [n, act_dim] on the engine's device.  The same ``torch.randn((n, act_dim))`` draw, so under one ``torch.manual_seed`` it
+        consumes the stream ``select_action`` consumes; with several runs: the selected run's rows."""
         if self._eng is None:
             self._bind(256)
         dev = self._arena.device
-        o = torch.as_tensor(np.asarray(obs, dtype=np.float32), device=dev).reshape(-1, self.obs_dim)
+        o = torch.as_tensor(obs, dtype=torch.float32, device=dev).reshape(-1, self.obs_dim)
         eps = torch.randn((o.shape[0], self.act_dim), device=dev)
         R, r = self._n_runs, max(self._cur_run, 0)
         if R > 1:
             eps_all = torch.zeros((R,) + tuple(eps.shape), device=dev)
             eps_all[r] = eps
-            return self._sample(o.unsqueeze(0).expand(R, -1, -1), eps_all)[r].cpu().numpy()
-        return self._sample(o.unsqueeze(0), eps.unsqueeze(0))[0].cpu().numpy()
+            return self._sample(o.unsqueeze(0).expand(R, -1, -1), eps_all)[r]
+        return self._sample(o.unsqueeze(0), eps.unsqueeze(0))[0]
 
     def select_action_runs(self, obs: np.ndarray, rtg=None) -> np.ndarray:
         """Sampled actions of EVERY run in one call: ``obs`` [n_runs, E, obs_dim] -> [n_runs, E, act_dim]; the normals are one

@@ -6,6 +6,9 @@ The return-to-go travels where the other algorithms carry the reward (``orl_batc
 ``learn_epoch`` is the reference trainer's inner loop -- one pass over a shuffled dataset, every row once, last batch partial -- as one
 engine call over a caller-supplied row order (``orl_learn_epoch``).  ``rollout()`` (rcsl.py:57-120) rolls a behaviour policy -- here
 ``AutoregressivePolicy``, or anything with the diffusion policy's interface -- through a dynamics model on the host.
+``rollout_device()`` is the same rollout with every array in HBM (``TrajStore``: ``orl_traj_*``); its ``DeviceRollout`` exports the
+trajectories above a return threshold straight into the ``DeviceBuffer`` ``learn_epoch`` reads, and ``collect_rollouts_device`` is the
+collection loop of run_mbrcsl.py around the two.
 """
 from __future__ import annotations
 
@@ -28,6 +31,26 @@ def epoch_order(n_rows: int, batch_size: int, n_runs: int = 1, generator: Option
     for r in range(int(n_runs)):
         order[r, :n_rows] = torch.randperm(int(n_rows), generator=generator).numpy()
     return order
+
+
+class DeviceRollout:
+    """What ``rollout_device`` leaves in HBM: a finished ``TrajStore`` (rows with trajectory index, accumulated return, return-to-go)."""
+
+    def __init__(self, store: "_engine.TrajStore", rows: int) -> None:
+        self.store = store
+        self.rows = int(rows)
+
+    def to_host(self) -> Dict[str, np.ndarray]:
+        """the transition dict of ``rollout()``: its keys in its order, its shapes and dtypes"""
+        d = self.store.read(0, self.rows)
+        return {"obss": d["obs"], "next_obss": d["next_obs"], "actions": d["act"], "rewards": d["rew"][:, None],
+                "terminals": d["term"][:, None] != 0.0, "traj_idxs": d["traj_idx"].astype(np.int64), "acc_rets": d["acc_ret"],
+                "rtgs": d["rtg"][:, None]}
+
+    def export(self, device_buffer_ring, threshold: Optional[float] = None) -> Tuple[int, int]:
+        """Appends the rows of the trajectories with ``returns > threshold`` (every row without a threshold) to the reserved ring
+        ``device_buffer_ring``, returns-to-go in its reward column -> (rows kept, trajectories kept)."""
+        return self.store.export(device_buffer_ring, threshold)
 
 
 class _EpochPolicy(EnginePolicy):
@@ -168,6 +191,49 @@ class _RcslBase(_EpochPolicy):
         rollout_transitions["rtgs"] = rtgs[..., None]
         return rollout_transitions, {"num_transitions": num_transitions, "reward_mean": rewards_arr.mean(), "returns": returns}
 
+    def rollout_device(self, init_obss, rollout_length: int, store: Optional["_engine.TrajStore"] = None) -> Tuple[DeviceRollout, Dict]:
+        """``rollout`` with every array on the device: actions from ``rollout_policy.select_action_device``, the model step from
+        ``dynamics.step_device``, the bookkeeping in a ``TrajStore`` (termination test, rows, per-trajectory returns, the stable compaction
+        of the survivors).  One host read per model step -- the survivor count, which sizes the next step --, then the returns and the
+        reward sum.  The compaction keeps the surviving rows in their order, so the policy's ``torch.randn`` draw and the dynamics' Philox
+        draws, both keyed by row position, are the ones the host rollout consumes.  ``store``: a ``TrajStore`` to reuse (reset here);
+        by default a new one of ``len(init_obss) * rollout_length`` rows.  -> (DeviceRollout, info with the keys of ``rollout``)"""
+        if self.dynamics is None or self.rollout_policy is None:
+            raise NotImplementedError(f"{type(self).__name__}.rollout_device needs both a dynamics model and a rollout (behaviour) policy; "
+                                      f"this policy was built with dynamics={self.dynamics!r}, rollout_policy={self.rollout_policy!r}")
+        dyn, pol = self.dynamics, self.rollout_policy
+        kind = getattr(dyn, "term_kind", None)
+        if kind is None or not hasattr(dyn, "step_device"):
+            raise NotImplementedError("rollout_device: the dynamics' termination function is not one of the fixed row-wise tests of "
+                                      "utils.termination_fns (an obs_unnormalization wrapper, door or another callable carries no term_kind): "
+                                      "the device rollout cannot evaluate it; use rollout()")
+        if hasattr(pol, "sample_init_noise") or not hasattr(pol, "select_action_device"):
+            raise NotImplementedError(f"rollout_device: the rollout policy {type(pol).__name__} has no select_action_device (a policy with "
+                                      "sample_init_noise, the frozen-noise interface, is host-only): use rollout()")
+        n_traj, L = int(len(init_obss)), int(rollout_length)
+        if n_traj < 1 or L < 1:
+            raise ValueError(f"rollout_device: {n_traj} initial states, rollout_length {L}")
+        obs = init_obss if isinstance(init_obss, torch.Tensor) else torch.as_tensor(np.asarray(init_obss, dtype=np.float32))
+        if obs.device.type != "cuda":
+            pdev = torch.device(getattr(pol, "device", "cuda"))
+            obs = obs.to(pdev if pdev.type == "cuda" else torch.device("cuda", torch.cuda.current_device()))
+        obs = obs.to(torch.float32).reshape(n_traj, -1).contiguous()
+        dev = obs.device
+        if store is None:
+            store = _engine.TrajStore(int(obs.shape[1]), int(pol.act_dim), n_traj, n_traj * L, dev.index or 0)
+        store.reset(n_traj)
+        with torch.no_grad():
+            for _ in range(L):
+                act = pol.select_action_device(obs).to(torch.float32).contiguous()
+                nxt, rew, _ = dyn.step_device(obs, act)
+                alive = torch.empty_like(nxt)
+                n_alive = store.append_step(kind, obs, act, nxt.contiguous(), rew.contiguous(), alive)
+                if n_alive == 0:
+                    break
+                obs = alive[:n_alive]
+        rows, rew_sum, returns = store.finish()
+        return DeviceRollout(store, rows), {"num_transitions": rows, "reward_mean": rew_sum / rows, "returns": returns}
+
     def learn(self, batch: Dict) -> Dict[str, float]:
         """One gradient step on ``{"observations", "actions", "rtgs"}``: [B, ...] arrays shared by every run or [n_runs, B, ...]."""
         return self._step_on(batch, (("observations", "observations", None), ("actions", "actions", None), ("rewards", "rtgs", 1)))
@@ -245,3 +311,34 @@ class RcslGaussianPolicy(_RcslBase):
                 return mu.cpu().numpy()
             s = torch.baddbmm(P["dist_net.sigma.bias"].unsqueeze(1), z, P["dist_net.sigma.weight"].transpose(1, 2)).clamp(*self.SIGMA_BOUNDS)
             return (mu + s.exp() * torch.randn_like(mu)).cpu().numpy()
+
+
+def collect_rollouts_device(policy, init_obss_dataset, rollout_batch: int, horizon: int, threshold: float, num_need_traj: int, max_epochs: int,
+                            capacity_rows: int, rng=np.random):
+    """The collection loop of run_mbrcsl.py (``get_rollout_trajs``) on the device: per epoch ``rollout_batch`` initial states drawn with
+    ``rng.randint`` from ``init_obss_dataset`` [M, obs_dim], one ``policy.rollout_device`` of up to ``horizon`` steps, and the export of
+    the trajectories with ``returns > threshold`` into ONE ring of ``capacity_rows`` rows; until ``num_need_traj`` trajectories have been
+    kept or ``max_epochs`` epochs have run.  -> (the ring: a ``DeviceBuffer`` with returns-to-go in its reward column, ready for
+    ``learn_epoch``; info: num_traj, returns (of the kept trajectories, float64), max_return (their maximum, -inf when none was
+    kept), epochs)"""
+    if int(max_epochs) < 1 or int(rollout_batch) < 1 or int(num_need_traj) < 1:
+        raise ValueError(f"collect_rollouts_device: max_epochs {max_epochs}, rollout_batch {rollout_batch}, num_need_traj {num_need_traj}: "
+                         "each must be at least 1")
+    init = np.asarray(init_obss_dataset, dtype=np.float32)
+    init = init.reshape(len(init), -1)
+    ring, store = None, None
+    kept, num_traj, epochs = [], 0, 0
+    while num_traj < int(num_need_traj) and epochs < int(max_epochs):
+        idx = rng.randint(len(init), size=int(rollout_batch))
+        roll, info = policy.rollout_device(init[idx], horizon, store=store)
+        if store is None:                      # (the first rollout made the store; every later one reuses it)
+            store = roll.store
+            ring = _engine.DeviceBuffer(store.obs_dim, store.act_dim, store.device)
+            ring.reserve(int(capacity_rows))
+        _, n_kept = roll.export(ring, threshold)
+        returns = info["returns"]
+        kept.append(returns[returns > threshold])
+        num_traj += n_kept
+        epochs += 1
+    returns = np.concatenate(kept)
+    return ring, {"num_traj": num_traj, "returns": returns, "max_return": float(returns.max()) if len(returns) else -np.inf, "epochs": epochs}

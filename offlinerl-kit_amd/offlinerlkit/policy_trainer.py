@@ -523,6 +523,10 @@ class RcslPolicyTrainer:
     ``goal`` and drops by every reward), the reference's logged keys in its order, ``checkpoint_dir/policy.pth`` each epoch and
     ``model_dir/policy.pth`` at the end.  ``offline_ratio`` 0 trains on ``rollout_dataset``, 1 on ``offline_dataset``; anything else is refused.
 
+    ``rollout_dataset`` may also be the dict of ``rollout()`` / ``DeviceRollout.to_host()`` (``obss`` / ``next_obss`` keys) or, on the
+    fused path, a ``DeviceBuffer`` that already holds returns-to-go in its reward column (``DeviceRollout.export``,
+    ``collect_rollouts_device``): it is trained on as it is, nothing is uploaded.
+
     ``fused=False``: the batches of a shuffled ``DataLoader`` drawn in this process (``num_workers`` is accepted and ignored: no worker
     process is ever started), each through ``policy.learn``.  ``fused=True`` (the default when the policy has ``learn_epoch`` and a GPU is
     visible): the dataset is loaded once into a ``DeviceBuffer`` with ``rtgs`` in its reward column, and an epoch is one ``torch.randperm``
@@ -562,12 +566,20 @@ class RcslPolicyTrainer:
             return self.offline_dataset
         raise NotImplementedError
 
-    def _device_buffer(self, data: Dict[str, np.ndarray]):
+    def _device_buffer(self, data):
+        """the training data as a ``DeviceBuffer`` with rtgs in its reward column: a ``DeviceBuffer`` that already is one (an exported
+        device rollout) as it is; a dict with ``observations`` / ``next_observations``, or with the ``obss`` / ``next_obss`` of
+        ``rollout()`` (the two spellings the reference's ``DictDataset`` serves), uploaded once"""
         from . import _engine
-        obs = np.asarray(data["observations"], dtype=np.float32)
+        if isinstance(data, _engine.DeviceBuffer):
+            if data.size() < 1:
+                raise ValueError("RcslPolicyTrainer: the rollout DeviceBuffer is empty")
+            return data
+        ko, kn = ("observations", "next_observations") if "observations" in data else ("obss", "next_obss")
+        obs = np.asarray(data[ko], dtype=np.float32)
         act = np.asarray(data["actions"], dtype=np.float32)
         n = len(obs)
-        nxt = np.asarray(data["next_observations"], dtype=np.float32) if "next_observations" in data else obs
+        nxt = np.asarray(data[kn], dtype=np.float32) if kn in data else obs
         term = np.asarray(data["terminals"], dtype=np.float32).reshape(n) if "terminals" in data else np.zeros(n, np.float32)
         dev = torch.cuda.current_device()
         pdev = getattr(getattr(self.policy, "rcsl", None), "device", None)
@@ -580,8 +592,7 @@ class RcslPolicyTrainer:
     def _train_epoch(self, data: Dict[str, np.ndarray], loader) -> int:
         from .policy.rcsl import epoch_order
         if self._fused:
-            n = len(data["observations"])
-            order = epoch_order(n, self._batch_size, int(getattr(self.policy, "n_runs", 1)))
+            order = epoch_order(self._dbuf.size(), self._batch_size, int(getattr(self.policy, "n_runs", 1)))
             means = self.policy.learn_epoch(self._dbuf, order, self._batch_size)
             for k, v in means.items():
                 self.logger.logkv(k, v)
@@ -602,6 +613,8 @@ class RcslPolicyTrainer:
         loader = None
         if self._fused:
             self._dbuf = self._device_buffer(data)
+        elif not isinstance(data, dict):
+            raise NotImplementedError("RcslPolicyTrainer(fused=False) trains on a dict of host arrays; a DeviceBuffer needs fused=True")
         else:
             # the reference's DataLoader(shuffle=True) with the batches collated in THIS process: num_workers = 0 whatever was asked for
             loader = torch.utils.data.DataLoader(DictDataset(data), batch_size=self._batch_size, shuffle=True, num_workers=0)

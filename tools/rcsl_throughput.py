@@ -12,7 +12,14 @@ DiagGaussian head with a clamped state-conditioned sigma, Gaussian NLL; k_rcslg_
 rows per step, LeakyReLU on the tiled GEMM, k_autoreg_head) against the torch ``fit`` of an unbound policy object (plain nn.Linear /
 nn.LeakyReLU, autograd, torch.optim.Adam); and, in the same run, ``select_action`` on 256 rows (orl_autoreg_sample: 3 forward-only passes
 with k_autoreg_draw between them, the normals from torch.randn) against the reference's sequential torch loop over the same rows
-(``sampling``: calls per second, alternating blocks of ``--sample-calls`` calls)."""
+(``sampling``: calls per second, alternating blocks of ``--sample-calls`` calls).
+``--rollout``: the rollout stage of run_mbrcsl.py at its shape on hopper -- ``RcslPolicy.rollout`` (host bookkeeping, arrays through the host
+every model step) against ``RcslPolicy.rollout_device`` (``TrajStore``: orl_traj_*) on the same GPU: an ``EnsembleDynamics`` of 7 members /
+5 elites, [200] x 4, an ``AutoregressivePolicy`` [200] x 4, ``--trajectories`` (256) trajectories of ``--horizon`` (1000) steps, a termination
+function that never fires so the length is fixed, freshly initialised nets (the work per step does not depend on the weights).  A warm-up
+rollout of each, then ``--blocks`` timed rollouts of each, alternating; the figure is transitions per second.  Then, once, the wall time
+of the device path's pieces over one more rollout (action sampling, dynamics step, store append; each ends in a host synchronisation).
+Writes profiles/rcsl_rollout_throughput.json unless --out names another file."""
 import argparse
 import json
 import os
@@ -151,6 +158,66 @@ def measure(ds, rows, runs, blocks, gauss=False, autoreg=False, sample_calls=0):
     return out
 
 
+def measure_rollout(n_traj, horizon, blocks):
+    from offlinerlkit.dynamics import EnsembleDynamics
+    from offlinerlkit.modules import EnsembleDynamicsModel
+    from offlinerlkit.utils.scaler import StandardScaler
+    from offlinerlkit.utils.termination_fns import termination_fn_default
+    torch.manual_seed(1)
+    model = EnsembleDynamicsModel(OD, AD, HID, num_ensemble=7, num_elites=5, weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=DEV)
+    scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
+    dyn = EnsembleDynamics(model, torch.optim.Adam(model.parameters(), lr=1e-3), scaler, termination_fn_default)
+    dyn.set_engine_options(seed=3)
+    ar = AutoregressivePolicy(OD, AD, HID, LR, DEV)
+    mod = make_module(False)
+    pol = RcslPolicy(dyn, ar, mod, torch.optim.Adam(mod.parameters(), lr=LR), DEV)
+    init = np.random.default_rng(0).normal(size=(n_traj, OD)).astype(np.float32)
+    store = _engine.TrajStore(OD, AD, n_traj, n_traj * horizon, 0)
+
+    def host():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, info = pol.rollout(init, horizon)
+        torch.cuda.synchronize()
+        return info["num_transitions"] / (time.perf_counter() - t0)
+
+    def device():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, info = pol.rollout_device(init, horizon, store=store)
+        torch.cuda.synchronize()
+        return info["num_transitions"] / (time.perf_counter() - t0)
+    host(); device()                                   # warm-up: engine binding, allocator
+    h, d = [], []
+    for _ in range(blocks):
+        h.append(host()); d.append(device())
+    # where the device path's time goes: the same loop with a clock around each piece (every piece ends in a host synchronisation)
+    parts = dict(select_action_device=0.0, step_device=0.0, append_step=0.0)
+    obs = torch.as_tensor(init, device=DEV)
+    store.reset(n_traj)
+    t_all = time.perf_counter()
+    with torch.no_grad():
+        for _ in range(horizon):
+            t0 = time.perf_counter()
+            act = ar.select_action_device(obs).contiguous()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            nxt, rew, _ = dyn.step_device(obs, act)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            alive = torch.empty_like(nxt)
+            n_alive = store.append_step(dyn.term_kind, obs, act, nxt.contiguous(), rew.contiguous(), alive)
+            t3 = time.perf_counter()
+            parts["select_action_device"] += t1 - t0; parts["step_device"] += t2 - t1; parts["append_step"] += t3 - t2
+            obs = alive[:n_alive]
+    total = time.perf_counter() - t_all
+    rows, rew_sum, _ = store.finish()
+    return dict(trajectories=n_traj, horizon=horizon, transitions=rows, host_transitions_per_s=h, device_transitions_per_s=d,
+                host_median=float(np.median(h)), device_median=float(np.median(d)), speedup=float(np.median(d) / np.median(h)),
+                device_ms_per_step={k: 1e3 * v / horizon for k, v in parts.items()}, device_ms_per_step_total=1e3 * total / horizon,
+                rewards_finite=bool(np.isfinite(rew_sum)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000)
@@ -159,8 +226,19 @@ def main():
     ap.add_argument("--gauss", action="store_true", help="RcslGaussianPolicy at run_rcsl_gauss.py's shape ([1024] x 4)")
     ap.add_argument("--autoreg", action="store_true", help="AutoregressivePolicy at run_regress.py's shape ([200] x 4, 768 expanded rows), and select_action on 256 rows")
     ap.add_argument("--sample-calls", type=int, default=50)
+    ap.add_argument("--rollout", action="store_true", help="RcslPolicy.rollout against rollout_device at run_mbrcsl.py's shape on hopper")
+    ap.add_argument("--trajectories", type=int, default=256)
+    ap.add_argument("--horizon", type=int, default=1000)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.rollout:
+        res = dict(stage="RcslPolicy.rollout vs rollout_device", shape=dict(obs_dim=OD, act_dim=AD, dynamics_hidden=HID, ensemble=7, elites=5,
+                                                                          behaviour_hidden=HID, termination="none"),
+                   device=torch.cuda.get_device_name(0), result=measure_rollout(a.trajectories, a.horizon, a.blocks))
+        print(json.dumps(res))
+        with open(a.out or os.path.join(ROOT, "profiles", "rcsl_rollout_throughput.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     ds = dataset(a.rows)
     res = dict(policy="AutoregressivePolicy" if a.autoreg else "RcslGaussianPolicy" if a.gauss else "RcslPolicy", precision=int(os.environ.get("ORL_PRECISION", "0")),
                shape=dict(obs_dim=OD, act_dim=AD, hidden=HID_GAUSS if a.gauss else HID, batch=B, rows=a.rows, steps_per_epoch=-(-a.rows // B)),
