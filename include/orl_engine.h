@@ -617,6 +617,69 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
 int orl_dynadv_adam_get(orl_dynamics* d, int run, float* exp_avg, float* exp_avg_sq, int64_t n_floats, int64_t* step);
 int orl_dynadv_adam_set(orl_dynamics* d, int run, const float* exp_avg, const float* exp_avg_sq, int64_t n_floats, int64_t step);
 
+/* the int32 indices of the live trajectories of the current rollout, in row order, widened to int64 into the DEVICE array
+ * out_device (room for the live count, which is returned; < 0 on error).  Live indices ascend and are never compacted, so a per-trajectory
+ * table (a frozen noise, say) is indexed with them directly. */
+int64_t orl_traj_live(orl_traj* t, int64_t* out_device);
+
+/* -- DiffusionBC: the diffusion behaviour policy (policy/others/diffusion.py, nets/unet.py at sequence length 1) ---------------
+ * The network is ConditionalUnet1D called with one time step: every Conv1d(k, padding = k / 2) reads its centre tap only, the
+ * down / up sampling is absent, and the U-Net is a FiLM-conditioned residual MLP of GroupNorm + Mish blocks with skip concatenations.
+ * The engine keeps the centre taps as dense [out][in] matrices; the off-centre taps never receive a gradient and stay with the caller.
+ * One object = one run, precision 0 (fp32 MFMA). */
+#define ORL_DIFF_MAX_LEVELS 4
+typedef struct orl_diffusion orl_diffusion;
+typedef struct {
+  int32_t obs_dim, act_dim;
+  int32_t step_embed_dim;           /* diffusion_step_embed_dim, even and >= 4 */
+  int32_t n_levels;                 /* len(down_dims), 1 .. ORL_DIFF_MAX_LEVELS */
+  int32_t down_dims[ORL_DIFF_MAX_LEVELS];
+  int32_t kernel_size;              /* odd: only the centre tap takes part */
+  int32_t n_groups;                 /* of the blocks' norms: every channel count is a multiple of it; final_conv's norm has 8 */
+  int32_t num_diffusion_iters;      /* N */
+  int32_t batch_size;
+  float adam_beta1, adam_beta2, adam_eps;
+  int32_t n_runs, device, precision;
+  uint64_t seed;
+} orl_diffusion_config;
+void orl_diffusion_config_default(orl_diffusion_config* cfg);  /* hopper: 11 / 3, embed 256, [256, 512, 1024], k 5, 8 groups, N 10, batch 256 */
+/* Refused: n_runs != 1, precision != 0, an even kernel_size, a channel count that n_groups does not divide, a group wider than 512,
+ * down_dims[0] not a multiple of 8 (final_conv's norm is GroupNorm(8) whatever n_groups is). */
+int orl_diffusion_create(const orl_diffusion_config* cfg, orl_diffusion** out);
+void orl_diffusion_destroy(orl_diffusion* d);
+int64_t orl_diffusion_floats(orl_diffusion* d);          /* floats of the parameter block */
+int orl_diffusion_num_tensors(orl_diffusion* d);
+/* tensor idx of the block: its state_dict name, offset and shape (a conv weight is its centre tap, [out][in]) */
+int orl_diffusion_tensor(orl_diffusion* d, int idx, char* name, int name_cap, int64_t* offset_floats, int32_t* ndim, int64_t shape[4]);
+/* which: 0 parameters, 1 EMA parameters, 2 exp_avg, 3 exp_avg_sq; host arrays of orl_diffusion_floats floats */
+int orl_diffusion_set(orl_diffusion* d, int which, const float* host, int64_t n_floats);
+int orl_diffusion_get(orl_diffusion* d, int which, float* host, int64_t n_floats);
+int orl_diffusion_set_step_count(orl_diffusion* d, int64_t k);   /* optimizer steps taken: Adam's t, the lr index, the EMA step, the RNG counter */
+int64_t orl_diffusion_step_count(orl_diffusion* d);
+/* acp: alphas_cumprod, float32 [N].  coef: float32 [N][5] per sampling step t = {sqrt(acp_t), sqrt(1 - acp_t), the x0 coefficient,
+ * the x coefficient, sigma_t (0 at t = 0)} of the DDPM update  x <- c0 clip((x - s1 e) / s0, -1, 1) + c1 x + sigma z. */
+int orl_diffusion_set_schedule(orl_diffusion* d, const float* acp, const float* coef);
+/* the learning rate of optimizer step k, float64 [n], uploaded once; a step past the table is refused */
+int orl_diffusion_set_lr(orl_diffusion* d, const double* table, int64_t n);
+int orl_diffusion_attach_buffer(orl_diffusion* d, orl_buffer* b);    /* the dataset rows (obs, act) the steps gather */
+/* One optimizer step on `rows` (1 .. batch_size) rows idx[] of the attached buffer: x_t, the network, the MSE against eps, the
+ * backward, Adam with lr[k], the EMA.  t (int64 [rows], 0 .. N-1) and eps (float32 [rows][act_dim]) teacher-force the draws; NULL:
+ * device Philox keyed by (seed, k, row).  All pointers are HOST pointers.  loss_out: the minibatch loss (synchronous). */
+int orl_diffusion_step(orl_diffusion* d, const int64_t* idx, int32_t rows, const int64_t* t, const float* eps, float* loss_out);
+/* ceil(n_rows / batch_size) steps over order[0 .. n_rows) (int64, a device pointer when on_device), the last one short; no host
+ * synchronisation but the one at the end.  losses_out: host, one loss per step. */
+int orl_diffusion_learn_epoch(orl_diffusion* d, const int64_t* order, int64_t n_rows, int on_device, float* losses_out);
+/* select_action for n rows: x starts at init_noise (row i reads row noise_idx[i] of it when noise_idx is given, else row i), then
+ * N forward-only passes on the EMA parameters with the DDPM update between them; z (float32 [N][n][act_dim], entry t used at step t > 0)
+ * teacher-forces the update's noise, NULL: device Philox on a stream of its own.  obs [n][obs_dim], init_noise [*][act_dim],
+ * act_out [n][act_dim]; every array is a device pointer when on_device.  One host synchronisation, at the end. */
+int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const float* init_noise, const int64_t* noise_idx,
+                         int64_t noise_rows, const float* z, int on_device, float* act_out);
+/* test taps of the last step: "pred", "eps", "x_t", "t" (as floats), "gf" (the condition vector), "film", "loss"; of the last
+ * sample: "z" (the last noise drawn), "x".  Returns the floats written, < 0 on error. */
+int64_t orl_diffusion_debug_read(orl_diffusion* d, const char* name, float* host, int64_t cap);
+int orl_diffusion_debug_grads(orl_diffusion* d, float* host, int64_t n_floats);   /* parameter gradient of the last step */
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ UNITS = {
     "gemm_inst_swish.hip": GEMM_H,
     "gemm_inst_leaky.hip": GEMM_H,
     "dynamics.hip": ["gemm.h", "rng.h", ABI],
+    "diffusion.hip": ["gemm.h", "rng.h", ABI],
     "ws_fwd.hip": WS_H,
     "ws_dgrad.hip": WS_H,
     "ws_fwd3.hip": WS_H,

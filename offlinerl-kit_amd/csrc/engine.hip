@@ -1489,6 +1489,12 @@ struct orl_buffer {
 struct orl_traj {
   Traj t;
 };
+namespace orl {
+// diffusion.hip: the dataset rows a DiffusionBC gathers (device, dims, pitches, size, the obs / act arrays)
+void buffer_view(const orl_buffer* b, int* dev, int* od, int* ad, int* OP, int* AP, long* n, const float** obs, const float** act) {
+  *dev = b->b.dev; *od = b->b.od; *ad = b->b.ad; *OP = b->b.OP; *AP = b->b.AP; *n = b->b.n; *obs = b->b.obs; *act = b->b.act;
+}
+}  // namespace orl
 
 extern "C" {
 
@@ -1988,6 +1994,16 @@ int orl_traj_finish(orl_traj* h, int64_t* rows, double* reward_sum, double* retu
   if (reward_sum) ORL_HIP(hipMemcpy(reward_sum, t.rew_total, sizeof(double), hipMemcpyDeviceToHost));
   if (returns_host) ORL_HIP(hipMemcpy(returns_host, t.returns, sizeof(double) * t.n_traj, hipMemcpyDeviceToHost));
   return 0;
+}
+int64_t orl_traj_live(orl_traj* h, int64_t* out_device) {
+  if (!h || !out_device) return fail("orl_traj_live: bad arguments");
+  Traj& t = h->t;
+  if (hipSetDevice(t.dev) != hipSuccess) return fail("orl_traj_live: hipSetDevice failed");
+  if (t.live > 0) {
+    hipLaunchKernelGGL(k_traj_live, dim3((unsigned)((t.live + 255) / 256)), dim3(256), 0, 0, t.live_idx[t.half], t.live, (long long*)out_device);
+    if (hipGetLastError() != hipSuccess) return fail("orl_traj_live: launch failed");
+  }
+  return t.live;
 }
 int orl_traj_read(orl_traj* h, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term, int32_t* traj_idx,
                   double* acc_ret, double* rtg) {

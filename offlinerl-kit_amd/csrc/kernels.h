@@ -384,6 +384,11 @@ __global__ void k_traj_finish(TrajP p) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < p.n) p.rtg[i] = p.returns[p.tidx[i]] - p.acc[i];
 }
+// orl_traj_live: the live trajectory indices, widened to int64 (an index tensor for a per-trajectory table)
+__global__ void k_traj_live(const int* __restrict__ live_idx, long n, long long* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = live_idx[i];
+}
 // (a NaN return is not above any threshold, as in numpy)
 __device__ inline bool orl_traj_keep(int use_thr, double thr, const double* returns, int t) { return !use_thr || returns[t] > thr; }
 __global__ void k_traj_count(TrajP p) {

@@ -6,6 +6,7 @@ parameters into the HIP engine's arena and re-points ``param.data`` at views of 
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence
 
 import torch
@@ -118,3 +119,102 @@ class VAE(nn.Module):
         a = torch.relu(self.d1(torch.cat([obs, z], 1)))
         a = torch.relu(self.d2(a))
         return self.max_action * torch.tanh(self.d3(a))
+
+
+# ---- the diffusion behaviour policy's noise-prediction net (reference: offlinerlkit/nets/unet.py) ---------------------------------
+# Thin torch modules whose constructor signatures, parameter registration order (hence state_dict keys and, under one torch seed, the
+# initial values) and conv weight shapes [out, in, k] are the reference's.  Their ``forward`` serves CPU checks and the stock-torch
+# baseline; DiffusionBC trains and samples on the HIP engine (csrc/diffusion.hip), which keeps the centre taps only.
+
+class SinusoidalPosEmb(nn.Module):
+    """t [B] -> [sin(t f_j) | cos(t f_j)] [B, dim], f_j = exp(-j ln(10000) / (dim / 2 - 1))"""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.dim = dim
+
+    def forward(self, x):
+        half = self.dim // 2
+        freq = torch.exp(torch.arange(half, device=x.device) * -(math.log(10000) / (half - 1)))
+        arg = x[:, None] * freq[None, :]
+        return torch.cat((arg.sin(), arg.cos()), dim=-1)
+
+
+class Conv1dBlock(nn.Module):
+    """Conv1d(k, padding k // 2) -> GroupNorm -> Mish, as ``self.block``"""
+
+    def __init__(self, inp_channels, out_channels, kernel_size, n_groups=8):
+        super().__init__()
+        self.block = nn.Sequential(nn.Conv1d(inp_channels, out_channels, kernel_size, padding=kernel_size // 2),
+                                   nn.GroupNorm(n_groups, out_channels), nn.Mish())
+
+    def forward(self, x):
+        return self.block(x)
+
+
+class ConditionalResidualBlock1D(nn.Module):
+    """two Conv1dBlocks with a FiLM (per-channel scale and bias from ``cond_encoder(cond)``) between them and a residual path
+    (a 1x1 conv when the channel counts differ)"""
+
+    def __init__(self, in_channels, out_channels, cond_dim, kernel_size=3, n_groups=8):
+        super().__init__()
+        self.blocks = nn.ModuleList([Conv1dBlock(in_channels, out_channels, kernel_size, n_groups=n_groups),
+                                     Conv1dBlock(out_channels, out_channels, kernel_size, n_groups=n_groups)])
+        self.out_channels = out_channels
+        self.cond_encoder = nn.Sequential(nn.Mish(), nn.Linear(cond_dim, 2 * out_channels), nn.Unflatten(-1, (-1, 1)))
+        self.residual_conv = nn.Conv1d(in_channels, out_channels, 1) if in_channels != out_channels else nn.Identity()
+
+    def forward(self, x, cond):
+        """x [B, in_channels, T], cond [B, cond_dim] -> [B, out_channels, T]"""
+        film = self.cond_encoder(cond).reshape(cond.shape[0], 2, self.out_channels, 1)
+        y = film[:, 0] * self.blocks[0](x) + film[:, 1]
+        return self.blocks[1](y) + self.residual_conv(x)
+
+
+class ConditionalUnet1D(nn.Module):
+    """The reference's 1-D U-Net without its (commented-out) down / up sampling: two residual blocks per level on the way down, two in
+    the middle, two per level on the way up over [x | skip], then Conv1dBlock + 1x1 conv.  Every block is conditioned on
+    [step encoder(t) | global_cond]."""
+
+    def __init__(self, input_dim, global_cond_dim, diffusion_step_embed_dim=256, down_dims=[256, 512, 1024], kernel_size=5, n_groups=8):
+        super().__init__()
+        dims = [input_dim] + list(down_dims)
+        dsed = diffusion_step_embed_dim
+        cond_dim = dsed + global_cond_dim
+        pairs = list(zip(dims[:-1], dims[1:]))
+
+        def block(cin, cout):
+            return ConditionalResidualBlock1D(cin, cout, cond_dim=cond_dim, kernel_size=kernel_size, n_groups=n_groups)
+
+        # construction order = the order the reference draws its initial values in; attribute order = its state_dict order
+        step_encoder = nn.Sequential(SinusoidalPosEmb(dsed), nn.Linear(dsed, 4 * dsed), nn.Mish(), nn.Linear(4 * dsed, dsed))
+        self.mid_modules = nn.ModuleList([block(dims[-1], dims[-1]), block(dims[-1], dims[-1])])
+        down = nn.ModuleList([nn.ModuleList([block(cin, cout), block(cout, cout)]) for cin, cout in pairs])
+        up = nn.ModuleList([nn.ModuleList([block(2 * cout, cin), block(cin, cin)]) for cin, cout in reversed(pairs[1:])])
+        final = nn.Sequential(Conv1dBlock(down_dims[0], down_dims[0], kernel_size=kernel_size), nn.Conv1d(down_dims[0], input_dim, 1))
+        self.diffusion_step_encoder = step_encoder
+        self.up_modules = up
+        self.down_modules = down
+        self.final_conv = final
+
+    def forward(self, sample, timestep, global_cond=None):
+        """sample [B, T, input_dim], timestep [B] or a scalar, global_cond [B, global_cond_dim] -> [B, T, input_dim]"""
+        x = sample.moveaxis(-1, -2)
+        t = timestep
+        if not torch.is_tensor(t):
+            t = torch.tensor([t], dtype=torch.long, device=x.device)
+        elif t.dim() == 0:
+            t = t[None].to(x.device)
+        emb = self.diffusion_step_encoder[0](t.expand(x.shape[0])).to(x.dtype)       # (float32 in use; float64 nets are for checks)
+        cond = self.diffusion_step_encoder[1:](emb)
+        if global_cond is not None:
+            cond = torch.cat([cond, global_cond], dim=-1)
+        skips = []
+        for first, second in self.down_modules:
+            x = second(first(x, cond), cond)
+            skips.append(x)
+        for m in self.mid_modules:
+            x = m(x, cond)
+        for first, second in self.up_modules:
+            x = second(first(torch.cat((x, skips.pop()), dim=1), cond), cond)
+        return self.final_conv(x).moveaxis(-1, -2)

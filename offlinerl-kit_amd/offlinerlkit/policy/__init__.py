@@ -9,7 +9,8 @@ clamped state-conditioned sigma, Gaussian NLL); ``learn_epoch`` is one ordered p
 batch and sampled by ``orl_autoreg_sample``).  ``rollout_device`` is that rollout with every array in HBM: ``select_action_device``,
 ``EnsembleDynamics.step_device`` and the trajectory store (``orl_traj_*``: per-row trajectory index, accumulated return and return-to-go,
 float64 returns), whose thresholded export is the ``DeviceBuffer`` ``learn_epoch`` reads; ``rcsl.collect_rollouts_device`` loops the two.
-(The reference package also exports the diffusion behaviour policy, which needs ``diffusers``; it is out of scope here.)"""
+``DiffusionBC`` is the pipeline's default behaviour policy: a DDPM over actions whose noise-prediction U-Net, at the sequence length 1
+it is used at, trains and samples on ``orl_diffusion_*``; its frozen per-trajectory noise stays in HBM through ``rollout_device``."""
 from .base_policy import BasePolicy, EnginePolicy
 from .iql import IQLPolicy
 from .sac_family import CQLPolicy, EDACPolicy
@@ -20,6 +21,7 @@ from .rambo import RAMBOPolicy
 from .mobile import MOBILEPolicy
 from .rcsl import RcslPolicy, RcslGaussianPolicy
 from .autoregressive import AutoregressivePolicy
+from .diffusion import DiffusionBC
 
 __all__ = ["BasePolicy", "EnginePolicy", "CQLPolicy", "IQLPolicy", "TD3BCPolicy", "EDACPolicy", "SACPolicy", "MOPOPolicy", "COMBOPolicy", "MCQPolicy",
-           "RAMBOPolicy", "MOBILEPolicy", "RcslPolicy", "RcslGaussianPolicy", "AutoregressivePolicy"]
+           "RAMBOPolicy", "MOBILEPolicy", "RcslPolicy", "RcslGaussianPolicy", "AutoregressivePolicy", "DiffusionBC"]

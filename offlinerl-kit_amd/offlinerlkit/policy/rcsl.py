@@ -196,7 +196,10 @@ class _RcslBase(_EpochPolicy):
         ``dynamics.step_device``, the bookkeeping in a ``TrajStore`` (termination test, rows, per-trajectory returns, the stable compaction
         of the survivors).  One host read per model step -- the survivor count, which sizes the next step --, then the returns and the
         reward sum.  The compaction keeps the surviving rows in their order, so the policy's ``torch.randn`` draw and the dynamics' Philox
-        draws, both keyed by row position, are the ones the host rollout consumes.  ``store``: a ``TrajStore`` to reuse (reset here);
+        draws, both keyed by row position, are the ones the host rollout consumes.  A rollout policy with ``device_frozen_noise = True``,
+        ``sample_init_noise`` and ``select_action_device(obs, init_noise)`` (``DiffusionBC``) gets its per-trajectory noise [n_traj, 1,
+        act_dim], drawn once, and every step the live trajectory indices (``store.live_index()``) as ``noise_index``: the policy's sampler
+        gathers the rows.  ``store``: a ``TrajStore`` to reuse (reset here);
         by default a new one of ``len(init_obss) * rollout_length`` rows.  -> (DeviceRollout, info with the keys of ``rollout``)"""
         if self.dynamics is None or self.rollout_policy is None:
             raise NotImplementedError(f"{type(self).__name__}.rollout_device needs both a dynamics model and a rollout (behaviour) policy; "
@@ -207,7 +210,8 @@ class _RcslBase(_EpochPolicy):
             raise NotImplementedError("rollout_device: the dynamics' termination function is not one of the fixed row-wise tests of "
                                       "utils.termination_fns (an obs_unnormalization wrapper, door or another callable carries no term_kind): "
                                       "the device rollout cannot evaluate it; use rollout()")
-        if hasattr(pol, "sample_init_noise") or not hasattr(pol, "select_action_device"):
+        frozen = bool(getattr(pol, "device_frozen_noise", False)) and hasattr(pol, "select_action_device") and hasattr(pol, "sample_init_noise")
+        if not frozen and (hasattr(pol, "sample_init_noise") or not hasattr(pol, "select_action_device")):
             raise NotImplementedError(f"rollout_device: the rollout policy {type(pol).__name__} has no select_action_device (a policy with "
                                       "sample_init_noise, the frozen-noise interface, is host-only): use rollout()")
         n_traj, L = int(len(init_obss)), int(rollout_length)
@@ -222,9 +226,16 @@ class _RcslBase(_EpochPolicy):
         if store is None:
             store = _engine.TrajStore(int(obs.shape[1]), int(pol.act_dim), n_traj, n_traj * L, dev.index or 0)
         store.reset(n_traj)
+        # the frozen-noise interface on the device (DiffusionBC): one draw per trajectory; every step the sampler gathers the rows of
+        # the live trajectories -- the rows rollout() keeps by thinning its copy
+        noise = pol.sample_init_noise(n_traj) if frozen else None
         with torch.no_grad():
             for _ in range(L):
-                act = pol.select_action_device(obs).to(torch.float32).contiguous()
+                if frozen:
+                    act = pol.select_action_device(obs, noise, noise_index=store.live_index())
+                else:
+                    act = pol.select_action_device(obs)
+                act = act.to(torch.float32).contiguous()
                 nxt, rew, _ = dyn.step_device(obs, act)
                 alive = torch.empty_like(nxt)
                 n_alive = store.append_step(kind, obs, act, nxt.contiguous(), rew.contiguous(), alive)

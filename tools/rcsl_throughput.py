@@ -19,7 +19,13 @@ every model step) against ``RcslPolicy.rollout_device`` (``TrajStore``: orl_traj
 function that never fires so the length is fixed, freshly initialised nets (the work per step does not depend on the weights).  A warm-up
 rollout of each, then ``--blocks`` timed rollouts of each, alternating; the figure is transitions per second.  Then, once, the wall time
 of the device path's pieces over one more rollout (action sampling, dynamics step, store append; each ends in a host synchronisation).
-Writes profiles/rcsl_rollout_throughput.json unless --out names another file."""
+Writes profiles/rcsl_rollout_throughput.json unless --out names another file.
+``--diffusion``: ``DiffusionBC`` at the default shape on hopper (ConditionalUnet1D [256, 512, 1024], embedding 256, N = 10, batch 256), three
+figures from one run: (1) one training epoch over ``--rows`` rows (orl_diffusion_learn_epoch) against autograd + torch.optim.Adam on the
+project's own ``ConditionalUnet1D`` on the same GPU (steps per second); (2) ``select_action`` on 256 rows (orl_diffusion_sample: 10
+forward-only passes) against the same DDPM loop in torch on that module (calls per second); (3) ``RcslPolicy.rollout_device`` with the
+frozen noise in HBM against the host ``rollout()`` (transitions per second; ``--trajectories`` x ``--horizon``).  Writes
+profiles/diffusion_throughput.json unless --out names another file."""
 import argparse
 import json
 import os
@@ -218,6 +224,124 @@ def measure_rollout(n_traj, horizon, blocks):
                 rewards_finite=bool(np.isfinite(rew_sum)))
 
 
+def measure_diffusion(rows, blocks, sample_calls, n_traj, horizon):
+    from offlinerlkit.dynamics import EnsembleDynamics
+    from offlinerlkit.modules import EnsembleDynamicsModel
+    from offlinerlkit.nets import ConditionalUnet1D
+    from offlinerlkit.policy import DiffusionBC
+    from offlinerlkit.utils.diffusion_logger import Logger
+    from offlinerlkit.utils.scaler import StandardScaler
+    from offlinerlkit.utils.termination_fns import termination_fn_default
+
+    class Cfg:
+        act_dim, obs_dim, num_epochs, num_diffusion_iters, batch_size, save_ckpt_freq = AD, OD, 1000, 10, B, 10 ** 9
+        device, path, num_workers, spectral_norm = DEV, None, 1, False
+    ds = dataset(rows)
+    torch.manual_seed(0)
+    bc = DiffusionBC(Cfg(), (ds["observations"], ds["actions"]), Logger(None))
+    eng = bc._attach()
+    net = ConditionalUnet1D(AD, OD).to(DEV)
+    net.load_state_dict(bc.noise_pred_net.state_dict())
+    opt = torch.optim.Adam(net.parameters(), lr=1e-4)
+    obs_d, act_d = torch.as_tensor(ds["observations"], device=DEV), torch.as_tensor(ds["actions"], device=DEV)
+    acp = torch.as_tensor(bc.alphas_cumprod, device=DEV)
+    steps = -(-rows // B)
+
+    def engine_epoch():
+        order = torch.randperm(rows, device=DEV)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        losses = eng.learn_epoch(order)
+        return steps / (time.perf_counter() - t0), float(losses[-1])
+
+    def torch_epoch():
+        order = torch.randperm(rows, device=DEV)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for s in range(0, rows, B):
+            idx = order[s:s + B]
+            a = act_d[idx].unsqueeze(1)
+            noise = torch.randn_like(a)
+            t = torch.randint(0, 10, (len(idx),), device=DEV)
+            xt = acp[t].sqrt().reshape(-1, 1, 1) * a + (1 - acp[t]).sqrt().reshape(-1, 1, 1) * noise
+            loss = torch.nn.functional.mse_loss(net(xt, t, global_cond=obs_d[idx]), noise)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            last = loss.item()                          # one read per batch, like the reference's record_mean(loss.item())
+        torch.cuda.synchronize()
+        return steps / (time.perf_counter() - t0), last
+    engine_epoch(); torch_epoch()
+    e, r = [], []
+    for _ in range(blocks):
+        e.append(engine_epoch()); r.append(torch_epoch())
+    train = dict(rows=rows, steps_per_epoch=steps, engine_steps_per_s=[x[0] for x in e], torch_steps_per_s=[x[0] for x in r],
+                 engine_median=float(np.median([x[0] for x in e])), torch_median=float(np.median([x[0] for x in r])),
+                 last_losses=dict(engine=e[-1][1], torch=r[-1][1]))
+    train["speedup"] = train["engine_median"] / train["torch_median"]
+    # (2) select_action on 256 rows: the engine's EMA weights are the initial ones of `bc`; torch runs the same loop on a copy of them
+    ema = ConditionalUnet1D(AD, OD).to(DEV)
+    ema.load_state_dict(bc.noise_pred_net.state_dict())
+    coef = torch.as_tensor(bc.ddpm_coef, device=DEV)
+    o256 = obs_d[:256].contiguous()
+
+    def engine_sample():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(sample_calls):
+            bc.select_action_device(o256, None)
+        torch.cuda.synchronize()
+        return sample_calls / (time.perf_counter() - t0)
+
+    def torch_sample():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            for _ in range(sample_calls):
+                x = torch.randn((256, 1, AD), device=DEV)
+                for t in range(9, -1, -1):
+                    e_ = ema(x, t, global_cond=o256)
+                    x0 = ((x - coef[t, 1] * e_) / coef[t, 0]).clamp(-1, 1)
+                    x = coef[t, 2] * x0 + coef[t, 3] * x
+                    if t > 0:
+                        x = x + coef[t, 4] * torch.randn_like(x)
+                x.cpu()
+        return sample_calls / (time.perf_counter() - t0)
+    engine_sample(); torch_sample()
+    se, st = [], []
+    for _ in range(blocks):
+        se.append(engine_sample()); st.append(torch_sample())
+    sampling = dict(rows=256, engine_calls_per_s=se, torch_calls_per_s=st, engine_median=float(np.median(se)), torch_median=float(np.median(st)),
+                    speedup=float(np.median(se) / np.median(st)))
+    # (3) the rollout stage with the diffusion behaviour policy
+    torch.manual_seed(1)
+    model = EnsembleDynamicsModel(OD, AD, HID, num_ensemble=7, num_elites=5, weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=DEV)
+    scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
+    dyn = EnsembleDynamics(model, torch.optim.Adam(model.parameters(), lr=1e-3), scaler, termination_fn_default)
+    dyn.set_engine_options(seed=3)
+    mod = make_module(False)
+    pol = RcslPolicy(dyn, bc, mod, torch.optim.Adam(mod.parameters(), lr=LR), DEV)
+    init = np.random.default_rng(0).normal(size=(n_traj, OD)).astype(np.float32)
+    store = _engine.TrajStore(OD, AD, n_traj, n_traj * horizon, 0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, info = fn()
+        torch.cuda.synchronize()
+        return info["num_transitions"] / (time.perf_counter() - t0)
+    host = lambda: timed(lambda: pol.rollout(init, horizon))
+    device = lambda: timed(lambda: pol.rollout_device(init, horizon, store=store))
+    h, dv = [], []
+    for i in range(blocks + 1):                          # the first pair is the warm-up
+        a, b = host(), device()
+        if i:
+            h.append(a); dv.append(b)
+    rollout = dict(trajectories=n_traj, horizon=horizon, host_transitions_per_s=h, device_transitions_per_s=dv, host_median=float(np.median(h)),
+                   device_median=float(np.median(dv)), speedup=float(np.median(dv) / np.median(h)))
+    return dict(training_epoch=train, select_action=sampling, rollout=rollout)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000)
@@ -230,7 +354,17 @@ def main():
     ap.add_argument("--trajectories", type=int, default=256)
     ap.add_argument("--horizon", type=int, default=1000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--diffusion", action="store_true", help="DiffusionBC at the default shape: a training epoch, select_action on 256 rows, the rollout")
     a = ap.parse_args()
+    if a.diffusion:
+        res = dict(policy="DiffusionBC", shape=dict(obs_dim=OD, act_dim=AD, down_dims=[256, 512, 1024], step_embed_dim=256, kernel_size=5,
+                                                    n_groups=8, num_diffusion_iters=10, batch=B),
+                   device=torch.cuda.get_device_name(0), blocks=a.blocks,
+                   result=measure_diffusion(a.rows, a.blocks, a.sample_calls, a.trajectories, a.horizon))
+        print(json.dumps(res))
+        with open(a.out or os.path.join(ROOT, "profiles", "diffusion_throughput.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if a.rollout:
         res = dict(stage="RcslPolicy.rollout vs rollout_device", shape=dict(obs_dim=OD, act_dim=AD, dynamics_hidden=HID, ensemble=7, elites=5,
                                                                           behaviour_hidden=HID, termination="none"),
