@@ -1,0 +1,211 @@
+// devobj.h — the host layer under every device object of the C ABI (engine.h, dynamics.hip, diffusion.hip): error plumbing, the
+// tracked allocator, the parameter block's tensor table, flat-block transfers, call staging, and the GemmP of a linear layer's three
+// products from matrix views.  A new stand-alone model starts from these instead of copying them ("Device-object layer").
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/orl_engine.h"
+#include "gemm.h"
+
+namespace orl {
+
+void set_error(const std::string& msg);   // engine.hip: the text orl_last_error() returns
+int fail(const std::string& msg);         // set_error, returns -1
+void buffer_view(const orl_buffer* b, int* dev, int* od, int* ad, int* OP, int* AP, long* n, const float** obs, const float** act);
+
+#define ORL_HIP(expr)                                                                            \
+  do {                                                                                           \
+    hipError_t _e = (expr);                                                                      \
+    if (_e != hipSuccess) {                                                                      \
+      ::orl::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                       \
+      return -1;                                                                                 \
+    }                                                                                            \
+  } while (0)
+// one kernel launch on `stream` with `lds` dynamic LDS bytes, and its check (engine.hip's ORL_LAUNCH is the profiled one)
+#define DEV_LAUNCH(stream, kernel, grid, block, lds, ...)                                        \
+  do {                                                                                           \
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                           \
+    if (hipGetLastError() != hipSuccess) return ::orl::fail(#kernel ": launch failed");          \
+  } while (0)
+
+static inline int rup4(int x) { return (x + 3) & ~3; }
+
+// Device allocations of one object.  alloc: zero-filled, an empty request gets 16 bytes; `who` prefixes the error texts.
+struct DevAllocs {
+  const char* who;
+  std::vector<void*> ptrs;
+  template <class T>
+  int alloc(T** p, size_t count) {
+    const size_t bytes = sizeof(T) * count, nb = bytes ? bytes : 16;
+    if (hipMalloc((void**)p, nb) != hipSuccess) return fail(std::string(who) + ": hipMalloc of " + std::to_string(bytes) + " bytes failed");
+    if (hipMemset(*p, 0, nb) != hipSuccess) return fail(std::string(who) + ": hipMemset failed");
+    ptrs.push_back(*p);
+    return 0;
+  }
+  void free(void* p) {
+    if (!p) return;
+    for (auto it = ptrs.begin(); it != ptrs.end(); ++it)
+      if (*it == p) { ptrs.erase(it); break; }
+    hipFree(p);
+  }
+  template <class... T>
+  void release(T**... ps) { ((free(*ps), *ps = nullptr), ...); }
+  // grow on demand: when n elements do not fit, wait for the stream, then replace *p by a fresh array of n and record the capacity
+  template <class T>
+  int grow(T** p, long* cap, long n, hipStream_t stream) {
+    if (n <= *cap) return 0;
+    ORL_HIP(hipStreamSynchronize(stream));
+    release(p);
+    *cap = 0;
+    if (alloc(p, (size_t)n)) return -1;
+    *cap = n;
+    return 0;
+  }
+  void free_all() {
+    for (void* p : ptrs) hipFree(p);
+    ptrs.clear();
+  }
+};
+
+// The tensors of a parameter block in state_dict order: what orl_net_tensor / orl_dyn_tensor / orl_diffusion_tensor answer from.
+struct TensorInfo {
+  std::string name;
+  long off;
+  int ndim;
+  long shape[4];
+};
+struct TensorTable {
+  std::vector<TensorInfo> rows;
+  long off = 0;      // running offset of add()
+  int size() const { return (int)rows.size(); }
+  // a tensor at an offset the caller laid out
+  void put(const std::string& name, long at, std::initializer_list<long> shape) {
+    TensorInfo t{name, at, (int)shape.size(), {1, 1, 1, 1}};
+    int i = 0;
+    for (long s : shape) t.shape[i++] = s;
+    rows.push_back(t);
+  }
+  long align4() { return off = (off + 3) & ~3L; }
+  // the next tensor of a packed block, returns its offset.  align_start: it begins on 4 floats (16 bytes); pad_size: it also ends there
+  long add(const std::string& name, std::initializer_list<long> shape, bool align_start, bool pad_size) {
+    if (align_start) align4();
+    const long at = off;
+    long n = 1;
+    for (long s : shape) n *= s;
+    put(name, at, shape);
+    off += n;
+    if (pad_size) align4();
+    return at;
+  }
+  // 1 when idx is out of range (the entry point words its own error); shape slots past ndim read 1
+  int query(int idx, char* name, int name_cap, int64_t* offset, int32_t* ndim, int64_t shape[4]) const {
+    if (idx < 0 || idx >= size()) return 1;
+    const TensorInfo& t = rows[idx];
+    if (name && name_cap > 0) snprintf(name, name_cap, "%s", t.name.c_str());
+    if (offset) *offset = t.off;
+    if (ndim) *ndim = t.ndim;
+    if (shape) for (int i = 0; i < 4; ++i) shape[i] = t.shape[i];
+    return 0;
+  }
+};
+
+// a flat float block to / from the host once the stream has drained
+static inline int block_to_host(hipStream_t stream, float* host, const float* dev, long floats) {
+  ORL_HIP(hipStreamSynchronize(stream));
+  ORL_HIP(hipMemcpy(host, dev, sizeof(float) * floats, hipMemcpyDeviceToHost));
+  return 0;
+}
+static inline int block_from_host(hipStream_t stream, float* dev, const float* host, long floats) {
+  ORL_HIP(hipStreamSynchronize(stream));
+  ORL_HIP(hipMemcpy(dev, host, sizeof(float) * floats, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// Staging of a call's arrays.  In: a host array is copied to `stage` on the stream and p repointed there; a device array (on_device)
+// or a null one stays.  stage_dst: where the kernel writes an output; out: the staged output copied back to the host on the stream.
+template <class T>
+static int stage_in(hipStream_t stream, const T*& p, T* stage, size_t count, int on_device) {
+  if (on_device || !p) return 0;
+  ORL_HIP(hipMemcpyAsync(stage, p, sizeof(T) * count, hipMemcpyHostToDevice, stream));
+  p = stage;
+  return 0;
+}
+template <class T>
+static T* stage_dst(T* user, T* stage, int on_device) { return user && !on_device ? stage : user; }
+template <class T>
+static int stage_out(hipStream_t stream, T* user, const T* stage, size_t count, int on_device) {
+  if (on_device || !user) return 0;
+  ORL_HIP(hipMemcpyAsync(user, stage, sizeof(T) * count, hipMemcpyDeviceToHost, stream));
+  return 0;
+}
+
+// ---- a linear layer's products on the tiled GEMM (gemm.h) ----
+// [z0][z1][rows][pitch] matrix (strides s0, s1; both 0: one matrix) or a column slice of one; lim = floats readable from p within a row
+struct DevMat {
+  float* p = nullptr;
+  long s0 = 0, s1 = 0;
+  int pitch = 0, lim = 0;
+  DevMat cols(int c0) const { DevMat m = *this; m.p += c0; m.lim -= c0; return m; }
+  ZPtr z() const { return {p, s0, s1}; }
+};
+// weight and bias of a layer (or their gradients) batched like the matrices.  in_major: EnsembleLinear's (in, out)-major weight,
+// else nn.Linear's (out, in)-major one (the l.ens distinction of Engine::linear_fwd)
+struct LinearP {
+  ZOut w, b;
+  int in, out;
+  bool in_major;
+  int members;       // z1 extent (GemmP::nz1)
+};
+static inline GemmP gemm_zero() {
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.ksplit = 1;
+  return p;
+}
+// Y = X W + b.  Epilogue fields (z_out), tile choice and a_kpad are the caller's.  In the forward and the dgrad b_rlim is set exactly
+// where the weight's rows are contiguous along N: it lets launch_gemm pick the 4-row block loader.
+static inline GemmP linear_fwd_p(const DevMat& X, int M, const LinearP& l, const DevMat& Y) {
+  GemmP p = gemm_zero();
+  p.A = X.z(); p.a_sr = X.pitch; p.a_sk = 1;
+  p.B = {l.w.p, l.w.s0, l.w.s1};
+  if (l.in_major) { p.b_sr = 1; p.b_sk = l.out; p.b_rlim = l.out & ~3; }
+  else { p.b_sr = l.in; p.b_sk = 1; }
+  p.C = Y.p; p.c_s0 = Y.s0; p.c_s1 = Y.s1; p.c_sr = Y.pitch; p.c_sn = 1;
+  p.M = M; p.N = l.out; p.K = l.in; p.nz1 = l.members;
+  p.bias = {l.b.p, l.b.s0, l.b.s1};
+  return p;
+}
+// dX = dY W^T (the caller adds aux for a masked epilogue)
+static inline GemmP linear_dgrad_p(const DevMat& dY, int M, const LinearP& l, const DevMat& dX) {
+  GemmP p = gemm_zero();
+  p.A = dY.z(); p.a_sr = dY.pitch; p.a_sk = 1;
+  p.B = {l.w.p, l.w.s0, l.w.s1};
+  if (l.in_major) { p.b_sr = l.out; p.b_sk = 1; }
+  else { p.b_sr = 1; p.b_sk = l.in; p.b_rlim = l.in & ~3; }
+  p.C = dX.p; p.c_s0 = dX.s0; p.c_s1 = dX.s1; p.c_sr = dX.pitch; p.c_sn = 1;
+  p.M = M; p.N = l.in; p.K = l.out; p.nz1 = l.members;
+  return p;
+}
+// dW = X^T dY in the weight's own layout and db = the column sums of dY, into the gradient blocks g.w / g.b
+static inline GemmP linear_wgrad_p(const DevMat& dY, const DevMat& X, int M, const LinearP& g) {
+  GemmP p = gemm_zero();
+  p.A = dY.z(); p.a_sr = 1; p.a_sk = dY.pitch; p.a_rlim = dY.lim & ~3;
+  p.B = X.z(); p.b_sr = 1; p.b_sk = X.pitch; p.b_rlim = X.lim & ~3;
+  p.ones_row = 1 << 30;
+  p.M = g.out; p.N = g.in; p.K = M; p.nz1 = g.members;
+  p.C = g.w.p; p.c_s0 = g.w.s0; p.c_s1 = g.w.s1;
+  if (g.in_major) { p.c_sr = 1; p.c_sn = g.out; }
+  else { p.c_sr = g.in; p.c_sn = 1; }
+  p.bias_out = g.b.p; p.bo_s0 = g.b.s0; p.bo_s1 = g.b.s1;
+  return p;
+}
+static inline int gemm_done(hipError_t e, const char* what) {
+  return e == hipSuccess ? 0 : fail(std::string(what) + " gemm: " + hipGetErrorString(e));
+}
+
+}  // namespace orl

@@ -20,6 +20,8 @@
 //   k_diff_loss       the MSE, its seed 2 (pred - eps) / (rows act_dim)
 //   k_diff_adam_ema   torch.optim.Adam with lr[k] read from the device table, then ema <- ema decay + p (1 - decay)
 // Sampling is N forward-only passes on the EMA block with k_diff_ddpm between them and one host synchronisation at the end.
+// Allocation, the tensor table, transfers, staging and the GemmP of a Linear's products come from devobj.h; the wave / block sums
+// and softplus from reduce.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,34 +29,21 @@
 #include <string>
 #include <vector>
 
-#include "../../include/orl_engine.h"
-#include "gemm.h"
+#include "devobj.h"
+#include "reduce.h"
 #include "rng.h"
 
 namespace orl {
-
-int fail(const std::string& msg);      // engine.hip: sets orl_last_error(), returns -1
-void buffer_view(const orl_buffer* b, int* dev, int* od, int* ad, int* OP, int* AP, long* n, const float** obs, const float** act);
-
-static inline int diff_rup4(int x) { return (x + 3) & ~3; }
 
 enum { DIFF_NJ = 8, DIFF_MAX_TERMS = 4 };
 enum { DIFF_FINAL_GROUPS = 8 };      // final_conv's Conv1dBlock is built without n_groups: always GroupNorm(8)
 enum { DIFF_TAG_T = 1u, DIFF_TAG_EPS = 2u, DIFF_TAG_Z = 3u };     // Philox streams: c3 = tag << 28 | high bits of the counter
 
-template <class T>
-__device__ __forceinline__ T diff_wave_sum(T s) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
-
 // nn.Mish: x tanh(softplus(x)), and what its backward needs
 struct DiffMish { float y, dy; };
-__device__ __forceinline__ float diff_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float diff_mish(float x) { return x * tanhf(diff_softplus(x)); }
+__device__ __forceinline__ float diff_mish(float x) { return x * tanhf(softplus(x)); }
 __device__ __forceinline__ DiffMish diff_mish_grad(float x) {
-  const float ts = tanhf(diff_softplus(x));
+  const float ts = tanhf(softplus(x));
   const float sg = 1.f / (1.f + expf(-x));
   return {x * ts, ts + x * sg * (1.f - ts * ts)};
 }
@@ -167,14 +156,14 @@ __device__ __forceinline__ void diff_group_stats(const DiffNormP& p, int row, in
     v[j] = c < p.cg ? p.h[(long)row * p.hp + c0 + c] : 0.f;
     s += v[j];
   }
-  mean = diff_wave_sum(s) / (float)p.cg;
+  mean = wave_sum(s) / (float)p.cg;
   float q = 0.f;
 #pragma unroll
   for (int j = 0; j < DIFF_NJ; ++j) {
     const float dlt = (lane + 64 * j) < p.cg ? v[j] - mean : 0.f;
     q += dlt * dlt;
   }
-  rstd = 1.f / sqrtf(diff_wave_sum(q) / (float)p.cg + 1e-5f);
+  rstd = 1.f / sqrtf(wave_sum(q) / (float)p.cg + 1e-5f);
 }
 
 // GroupNorm (eps 1e-5, affine) + Mish + the optional FiLM or residual tail; one block per row, one wave per group
@@ -228,8 +217,8 @@ __global__ void k_diff_norm_bwd(DiffNormP p) {
       s2 += dxh[j] * xh[j];
     }
   }
-  s1 = diff_wave_sum(s1) / (float)p.cg;
-  s2 = diff_wave_sum(s2) / (float)p.cg;
+  s1 = wave_sum(s1) / (float)p.cg;
+  s2 = wave_sum(s2) / (float)p.cg;
 #pragma unroll
   for (int j = 0; j < DIFF_NJ; ++j) {
     if (lane + 64 * j >= p.cg) break;
@@ -249,7 +238,6 @@ __global__ void k_diff_colsum(const float* __restrict__ part, long pn, int rows,
 // loss = mean over (rows x ad) of (pred - eps)^2, dPRED = 2 (pred - eps) / (rows ad); one block, fixed order
 __global__ __launch_bounds__(256) void k_diff_loss(const float* __restrict__ pred, int pp, const float* __restrict__ eps, int rows, int ad,
                                                    float* __restrict__ dpred, float* loss_out, float* loss_last) {      // (the two may be one cell)
-  __shared__ float red[4];
   const int n = rows * ad;
   const float inv = 1.f / (float)n;
   float s = 0.f;
@@ -259,11 +247,9 @@ __global__ __launch_bounds__(256) void k_diff_loss(const float* __restrict__ pre
     s += df * df;
     dpred[(long)r * pp + d] = 2.f * df * inv;
   }
-  s = diff_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  s = block_sum256_pairwise(s);
   if (threadIdx.x == 0) {
-    const float l = ((red[0] + red[1]) + (red[2] + red[3])) * inv;
+    const float l = s * inv;
     *loss_out = l;
     *loss_last = l;
   }
@@ -314,11 +300,6 @@ __global__ void k_diff_ddpm(float* __restrict__ x, int xp, const float* __restri
 
 using namespace orl;
 
-struct DiffTensor { std::string name; long off; std::vector<long> shape; };
-struct DView {                     // [rows][pitch] matrix or a column slice of one; lim = floats readable from p within a row
-  float* p = nullptr; int pitch = 0; int lim = 0;
-  DView cols(int c0) const { return {p + c0, pitch, lim - c0}; }
-};
 struct DiffBlock {
   int in, out; bool res;
   long w0, b0, w1, b1;             // [W0; Wr] stacked when res (2 out rows), likewise [b0; br]
@@ -330,11 +311,11 @@ struct DiffBlock {
 // activations of one pass over `cap` rows; the backward's buffers when train
 struct DiffWs {
   long cap = 0; bool train = false;
-  DView XT, E0, Z1, M1, GF, MC, FILM, HF, YF, PRED;
-  std::vector<DView> CAT, HR, Y1, H2, OUT;
+  DevMat XT, E0, Z1, M1, GF, MC, FILM, HF, YF, PRED;
+  std::vector<DevMat> CAT, HR, Y1, H2, OUT;
   // backward
-  DView dPRED, dYF, dHF, dLAST, dFILM, dMC, dE, dM1, dZ1, dH2, dY1;
-  std::vector<DView> D2, DR, DX;
+  DevMat dPRED, dYF, dHF, dLAST, dFILM, dMC, dE, dM1, dZ1, dH2, dY1;
+  std::vector<DevMat> D2, DR, DX;
   float* part = nullptr;
 };
 
@@ -345,7 +326,7 @@ struct orl_diffusion {
   int last_block = 0;
   long P = 0, s1w = 0, s1b = 0, s2w = 0, s2b = 0, f0w = 0, f0b = 0, f1w = 0, f1b = 0, fn = 0, cw = 0, cb = 0, norm_off = 0, norm_n = 0;
   int film_cols = 0, start_dim = 0;
-  std::vector<DiffTensor> tensors;
+  TensorTable tensors;
   hipStream_t stream = nullptr;
   float *params = nullptr, *ema = nullptr, *adam_m = nullptr, *adam_v = nullptr, *grads = nullptr;
   float *acp = nullptr, *coef = nullptr; bool have_sched = false;
@@ -362,39 +343,14 @@ struct orl_diffusion {
   float *sObs = nullptr, *sX = nullptr, *sNoise = nullptr, *sZ = nullptr, *sZkeep = nullptr, *sOut = nullptr;
   long long* sIdx = nullptr;
   long last_sample_n = 0; int last_rows = 0;
-  std::vector<void*> allocs;
+  DevAllocs mem{"orl_diffusion"};
 };
 
-#define DIFF_HIP(expr)                                                                                  \
-  do {                                                                                                  \
-    hipError_t _e = (expr);                                                                             \
-    if (_e != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(_e));               \
-  } while (0)
-#define DIFF_LAUNCH(kernel, grid, block, ...)                                                           \
-  do {                                                                                                  \
-    hipLaunchKernelGGL(kernel, grid, block, 0, d->stream, __VA_ARGS__);                                 \
-    if (hipGetLastError() != hipSuccess) return fail(#kernel ": launch failed");                        \
-  } while (0)
-
-static int diff_alloc(orl_diffusion* d, void** p, size_t bytes) {
-  if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) return fail("orl_diffusion: hipMalloc of " + std::to_string(bytes) + " bytes failed");
-  if (hipMemset(*p, 0, bytes ? bytes : 16) != hipSuccess) return fail("orl_diffusion: hipMemset failed");
-  d->allocs.push_back(*p);
-  return 0;
-}
-template <class T>
-static int diff_alloc_t(orl_diffusion* d, T** p, size_t count) { return diff_alloc(d, (void**)p, sizeof(T) * count); }
-static void diff_free(orl_diffusion* d, void* p) {
-  if (!p) return;
-  for (auto it = d->allocs.begin(); it != d->allocs.end(); ++it)
-    if (*it == p) { d->allocs.erase(it); break; }
-  hipFree(p);
-}
 // a zero-filled [rows][rup4(cols)] matrix
-static int diff_mat(orl_diffusion* d, DView& v, long rows, int cols) {
-  diff_free(d, v.p);
-  v.pitch = v.lim = diff_rup4(cols);
-  return diff_alloc_t(d, &v.p, (size_t)rows * v.pitch);
+static int diff_mat(orl_diffusion* d, DevMat& v, long rows, int cols) {
+  d->mem.free(v.p);
+  v.pitch = v.lim = rup4(cols);
+  return d->mem.alloc(&v.p, (size_t)rows * v.pitch);
 }
 
 static int diff_ws_alloc(orl_diffusion* d, DiffWs& w, long rows, bool train) {
@@ -420,7 +376,7 @@ static int diff_ws_alloc(orl_diffusion* d, DiffWs& w, long rows, bool train) {
           diff_mat(d, w.dLAST, rows, d->start_dim) || diff_mat(d, w.dFILM, rows, d->film_cols) || diff_mat(d, w.dMC, rows, d->cond) ||
           diff_mat(d, w.dE, rows, d->dsed) || diff_mat(d, w.dM1, rows, 4 * d->dsed) || diff_mat(d, w.dZ1, rows, 4 * d->dsed) ||
           diff_mat(d, w.dH2, rows, wmax) || diff_mat(d, w.dY1, rows, wmax) ||
-          (diff_free(d, w.part), diff_alloc_t(d, &w.part, (size_t)rows * d->norm_n));
+          (d->mem.free(w.part), d->mem.alloc(&w.part, (size_t)rows * d->norm_n));
   if (bad) return -1;
   w.cap = rows; w.train = train;
   return 0;
@@ -436,52 +392,27 @@ static int diff_cfg(int M, int N) {
   const long small_tiles = (long)((M + 15) / 16) * ((N + 63) / 64);
   return (M <= 32 || small_tiles <= 1024) ? CFG_SMALL : CFG_MID;
 }
-// Y = X W^T + b with W [out][in]
-static int diff_fwd(orl_diffusion* d, const float* base, const DView& X, int M, long w, long b, int in, int out, const DView& Y) {
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.A = {X.p, 0, 0}; p.a_sr = X.pitch; p.a_sk = 1;
-  p.B = {base + w, 0, 0}; p.b_sr = in; p.b_sk = 1;
-  p.C = Y.p; p.c_sr = Y.pitch; p.c_sn = 1;
-  p.M = M; p.N = out; p.K = in;
-  p.nz1 = 1; p.ksplit = 1;
-  p.bias = {base + b, 0, 0};
-  hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(diff_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32);
-  if (e != hipSuccess) return fail(std::string("orl_diffusion forward gemm: ") + hipGetErrorString(e));
-  return 0;
+// the nn.Linear at offsets w / b of `block` (the parameters, the EMA or the gradients): W [out][in]
+static LinearP diff_linear(float* block, long w, long b, int in, int out) { return {{block + w, 0, 0}, {block + b, 0, 0}, in, out, false, 1}; }
+// Y = X W^T + b
+static int diff_fwd(orl_diffusion* d, float* base, const DevMat& X, int M, long w, long b, int in, int out, const DevMat& Y) {
+  const GemmP p = linear_fwd_p(X, M, diff_linear(base, w, b, in, out), Y);
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(diff_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32), "orl_diffusion forward");
 }
 // dX = dY W
-static int diff_dgrad(orl_diffusion* d, const DView& dY, int M, long w, int in, int out, const DView& dX) {
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.A = {dY.p, 0, 0}; p.a_sr = dY.pitch; p.a_sk = 1;
-  p.B = {d->params + w, 0, 0}; p.b_sr = 1; p.b_sk = in; p.b_rlim = in & ~3;
-  p.C = dX.p; p.c_sr = dX.pitch; p.c_sn = 1;
-  p.M = M; p.N = in; p.K = out;
-  p.nz1 = 1; p.ksplit = 1;
-  hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(diff_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32);
-  if (e != hipSuccess) return fail(std::string("orl_diffusion dgrad gemm: ") + hipGetErrorString(e));
-  return 0;
+static int diff_dgrad(orl_diffusion* d, const DevMat& dY, int M, long w, int in, int out, const DevMat& dX) {
+  const GemmP p = linear_dgrad_p(dY, M, diff_linear(d->params, w, 0, in, out), dX);
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(diff_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32), "orl_diffusion dgrad");
 }
 // dW = dY^T X ([out][in]) and db = the column sums of dY into the gradient block
-static int diff_wgrad(orl_diffusion* d, const DView& dY, const DView& X, int M, long w, long b, int in, int out) {
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.A = {dY.p, 0, 0}; p.a_sr = 1; p.a_sk = dY.pitch; p.a_rlim = dY.lim & ~3;
-  p.B = {X.p, 0, 0}; p.b_sr = 1; p.b_sk = X.pitch; p.b_rlim = X.lim & ~3;
-  p.ones_row = 1 << 30;
-  p.M = out; p.N = in; p.K = M;
-  p.nz1 = 1; p.ksplit = 1;
-  p.C = d->grads + w; p.c_sr = in; p.c_sn = 1;
-  p.bias_out = d->grads + b;
-  hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(pick_cfg(p.M, p.N, p.K, 1), p, 1, d->stream, false, false, P_F32);
-  if (e != hipSuccess) return fail(std::string("orl_diffusion wgrad gemm: ") + hipGetErrorString(e));
-  return 0;
+static int diff_wgrad(orl_diffusion* d, const DevMat& dY, const DevMat& X, int M, long w, long b, int in, int out) {
+  const GemmP p = linear_wgrad_p(dY, X, M, diff_linear(d->grads, w, b, in, out));
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(pick_cfg(p.M, p.N, p.K, 1), p, 1, d->stream, false, false, P_F32), "orl_diffusion wgrad");
 }
 
 static int diff_ew_grid(long n) { return (int)((n + 255) / 256); }
 
-static DiffNormP diff_norm_params(orl_diffusion* d, const float* base, int rows, int C, const DView& h, long noff, int groups) {
+static DiffNormP diff_norm_params(orl_diffusion* d, const float* base, int rows, int C, const DevMat& h, long noff, int groups) {
   DiffNormP p;
   memset(&p, 0, sizeof(p));
   p.rows = rows; p.C = C; p.cg = C / groups;
@@ -492,21 +423,21 @@ static DiffNormP diff_norm_params(orl_diffusion* d, const float* base, int rows,
 
 // the forward pass over `rows` rows of workspace w on the parameter block `base` (the trained one or the EMA); E0, GF[:, dsed:] and
 // x (the net's input) are already in place
-static int diff_forward(orl_diffusion* d, DiffWs& w, const float* base, int rows, const DView& x) {
+static int diff_forward(orl_diffusion* d, DiffWs& w, float* base, int rows, const DevMat& x) {
   const int ds = d->dsed;
   if (diff_fwd(d, base, w.E0, rows, d->s1w, d->s1b, ds, 4 * ds, w.Z1)) return -1;
-  DIFF_LAUNCH(k_diff_mish, dim3(diff_ew_grid((long)rows * 4 * ds)), dim3(256), w.Z1.p, w.Z1.pitch, w.M1.p, w.M1.pitch, rows, 4 * ds);
+  DEV_LAUNCH(d->stream, k_diff_mish, dim3(diff_ew_grid((long)rows * 4 * ds)), dim3(256), 0, w.Z1.p, w.Z1.pitch, w.M1.p, w.M1.pitch, rows, 4 * ds);
   if (diff_fwd(d, base, w.M1, rows, d->s2w, d->s2b, 4 * ds, ds, w.GF)) return -1;
-  DIFF_LAUNCH(k_diff_mish, dim3(diff_ew_grid((long)rows * d->cond)), dim3(256), w.GF.p, w.GF.pitch, w.MC.p, w.MC.pitch, rows, d->cond);
+  DEV_LAUNCH(d->stream, k_diff_mish, dim3(diff_ew_grid((long)rows * d->cond)), dim3(256), 0, w.GF.p, w.GF.pitch, w.MC.p, w.MC.pitch, rows, d->cond);
   if (diff_fwd(d, base, w.MC, rows, d->cw, d->cb, d->cond, d->film_cols, w.FILM)) return -1;
   for (size_t b = 0; b < d->blocks.size(); ++b) {
     const DiffBlock& k = d->blocks[b];
-    DView X = k.src < 0 ? x : w.OUT[k.src];
+    DevMat X = k.src < 0 ? x : w.OUT[k.src];
     if (k.skip >= 0) {
       const int c1 = d->blocks[k.src].out, c2 = d->blocks[k.skip].out;
-      DIFF_LAUNCH(k_diff_copy, dim3(diff_ew_grid((long)rows * c1)), dim3(256), X.p, X.pitch, (const long long*)nullptr, 0L, w.CAT[b].p,
+      DEV_LAUNCH(d->stream, k_diff_copy, dim3(diff_ew_grid((long)rows * c1)), dim3(256), 0, X.p, X.pitch, (const long long*)nullptr, 0L, w.CAT[b].p,
                   w.CAT[b].pitch, (long)rows, c1);
-      DIFF_LAUNCH(k_diff_copy, dim3(diff_ew_grid((long)rows * c2)), dim3(256), w.OUT[k.skip].p, w.OUT[k.skip].pitch, (const long long*)nullptr, 0L,
+      DEV_LAUNCH(d->stream, k_diff_copy, dim3(diff_ew_grid((long)rows * c2)), dim3(256), 0, w.OUT[k.skip].p, w.OUT[k.skip].pitch, (const long long*)nullptr, 0L,
                   w.CAT[b].p + c1, w.CAT[b].pitch, (long)rows, c2);
       X = w.CAT[b];
     }
@@ -514,32 +445,32 @@ static int diff_forward(orl_diffusion* d, DiffWs& w, const float* base, int rows
     DiffNormP n0 = diff_norm_params(d, base, rows, k.out, w.HR[b], k.n0, d->G);
     n0.film = w.FILM.p + k.film_col; n0.fp = w.FILM.pitch;
     n0.out = w.Y1[b].p; n0.op = w.Y1[b].pitch;
-    DIFF_LAUNCH(k_diff_norm_fwd, dim3(rows), dim3(64 * d->G), n0);
+    DEV_LAUNCH(d->stream, k_diff_norm_fwd, dim3(rows), dim3(64 * d->G), 0, n0);
     if (diff_fwd(d, base, w.Y1[b], rows, k.w1, k.b1, k.out, k.out, w.H2[b])) return -1;
     DiffNormP n1 = diff_norm_params(d, base, rows, k.out, w.H2[b], k.n1, d->G);
     if (k.res) { n1.res = w.HR[b].p + k.out; n1.rp = w.HR[b].pitch; }
     else { n1.res = X.p; n1.rp = X.pitch; }
     n1.out = w.OUT[b].p; n1.op = w.OUT[b].pitch;
-    DIFF_LAUNCH(k_diff_norm_fwd, dim3(rows), dim3(64 * d->G), n1);
+    DEV_LAUNCH(d->stream, k_diff_norm_fwd, dim3(rows), dim3(64 * d->G), 0, n1);
   }
-  const DView& last = w.OUT[d->last_block];
+  const DevMat& last = w.OUT[d->last_block];
   if (diff_fwd(d, base, last, rows, d->f0w, d->f0b, d->start_dim, d->start_dim, w.HF)) return -1;
   DiffNormP nf = diff_norm_params(d, base, rows, d->start_dim, w.HF, d->fn, DIFF_FINAL_GROUPS);
   nf.out = w.YF.p; nf.op = w.YF.pitch;
-  DIFF_LAUNCH(k_diff_norm_fwd, dim3(rows), dim3(64 * DIFF_FINAL_GROUPS), nf);
+  DEV_LAUNCH(d->stream, k_diff_norm_fwd, dim3(rows), dim3(64 * DIFF_FINAL_GROUPS), 0, nf);
   return diff_fwd(d, base, w.YF, rows, d->f1w, d->f1b, d->start_dim, d->ad, w.PRED);
 }
 
 // the gradient terms of a block's output: one per consumer (a column slice where the consumer read a concatenation)
 struct DiffTerms { int n = 0; const float* g[DIFF_MAX_TERMS]; int pitch[DIFF_MAX_TERMS]; };
-static int diff_add_term(DiffTerms& t, const DView& v) {
+static int diff_add_term(DiffTerms& t, const DevMat& v) {
   if (t.n >= DIFF_MAX_TERMS) return fail("orl_diffusion: more gradient terms than a block's backward sums");
   t.g[t.n] = v.p; t.pitch[t.n] = v.pitch; ++t.n;
   return 0;
 }
 
 // backward from dPRED over the first `rows` rows of the training workspace
-static int diff_backward(orl_diffusion* d, DiffWs& w, int rows, const DView& x) {
+static int diff_backward(orl_diffusion* d, DiffWs& w, int rows, const DevMat& x) {
   const float* base = d->params;
   const int sd = d->start_dim, ds = d->dsed;
   const size_t nb = d->blocks.size();
@@ -551,7 +482,7 @@ static int diff_backward(orl_diffusion* d, DiffWs& w, int rows, const DView& x) 
     nf.nterm = 1; nf.g[0] = w.dYF.p; nf.gpitch[0] = w.dYF.pitch;
     nf.dh = w.dHF.p; nf.dhp = w.dHF.pitch;
     nf.part = w.part + d->fn; nf.pn = d->norm_n;
-    DIFF_LAUNCH(k_diff_norm_bwd, dim3(rows), dim3(64 * DIFF_FINAL_GROUPS), nf);
+    DEV_LAUNCH(d->stream, k_diff_norm_bwd, dim3(rows), dim3(64 * DIFF_FINAL_GROUPS), 0, nf);
   }
   if (diff_wgrad(d, w.dHF, w.OUT[d->last_block], rows, d->f0w, d->f0b, sd, sd) || diff_dgrad(d, w.dHF, rows, d->f0w, sd, sd, w.dLAST)) return -1;
   if (diff_add_term(terms[d->last_block], w.dLAST)) return -1;
@@ -559,16 +490,16 @@ static int diff_backward(orl_diffusion* d, DiffWs& w, int rows, const DView& x) 
     const DiffBlock& k = d->blocks[b];
     const DiffTerms& tm = terms[b];
     if (tm.n == 0) return fail("orl_diffusion: a block without a consumer");
-    const DView X = k.skip >= 0 ? w.CAT[b] : (k.src < 0 ? x : w.OUT[k.src]);
-    const DView dRv = k.res ? w.D2[b].cols(k.out) : w.DR[b];
+    const DevMat X = k.skip >= 0 ? w.CAT[b] : (k.src < 0 ? x : w.OUT[k.src]);
+    const DevMat dRv = k.res ? w.D2[b].cols(k.out) : w.DR[b];
     DiffNormP n1 = diff_norm_params(d, base, rows, k.out, w.H2[b], k.n1, d->G);
     n1.nterm = tm.n;
     for (int i = 0; i < tm.n; ++i) { n1.g[i] = tm.g[i]; n1.gpitch[i] = tm.pitch[i]; }
     n1.dsum = dRv.p; n1.sp = dRv.pitch;
     n1.dh = w.dH2.p; n1.dhp = w.dH2.pitch;
     n1.part = w.part + k.n1; n1.pn = d->norm_n;
-    DIFF_LAUNCH(k_diff_norm_bwd, dim3(rows), dim3(64 * d->G), n1);
-    DView dH2 = w.dH2; dH2.lim = dH2.pitch;
+    DEV_LAUNCH(d->stream, k_diff_norm_bwd, dim3(rows), dim3(64 * d->G), 0, n1);
+    DevMat dH2 = w.dH2; dH2.lim = dH2.pitch;
     if (diff_wgrad(d, dH2, w.Y1[b], rows, k.w1, k.b1, k.out, k.out) || diff_dgrad(d, dH2, rows, k.w1, k.out, k.out, w.dY1)) return -1;
     DiffNormP n0 = diff_norm_params(d, base, rows, k.out, w.HR[b], k.n0, d->G);
     n0.film = w.FILM.p + k.film_col; n0.fp = w.FILM.pitch;
@@ -576,7 +507,7 @@ static int diff_backward(orl_diffusion* d, DiffWs& w, int rows, const DView& x) 
     n0.dh = w.D2[b].p; n0.dhp = w.D2[b].pitch;
     n0.dfilm = w.dFILM.p + k.film_col; n0.dfp = w.dFILM.pitch;
     n0.part = w.part + k.n0; n0.pn = d->norm_n;
-    DIFF_LAUNCH(k_diff_norm_bwd, dim3(rows), dim3(64 * d->G), n0);
+    DEV_LAUNCH(d->stream, k_diff_norm_bwd, dim3(rows), dim3(64 * d->G), 0, n0);
     const int so = k.res ? 2 * k.out : k.out;                 // [dH1 | dR] against [W0; Wr]
     if (diff_wgrad(d, w.D2[b], X, rows, k.w0, k.b0, k.in, so)) return -1;
     if (k.src < 0) continue;                                   // the net's input needs no gradient
@@ -593,13 +524,13 @@ static int diff_backward(orl_diffusion* d, DiffWs& w, int rows, const DView& x) 
   if (diff_wgrad(d, w.dFILM, w.MC, rows, d->cw, d->cb, d->cond, d->film_cols) ||
       diff_dgrad(d, w.dFILM, rows, d->cw, d->cond, d->film_cols, w.dMC))
     return -1;
-  DIFF_LAUNCH(k_diff_mish_bwd, dim3(diff_ew_grid((long)rows * ds)), dim3(256), w.dMC.p, w.dMC.pitch, w.GF.p, w.GF.pitch, w.dE.p, w.dE.pitch,
+  DEV_LAUNCH(d->stream, k_diff_mish_bwd, dim3(diff_ew_grid((long)rows * ds)), dim3(256), 0, w.dMC.p, w.dMC.pitch, w.GF.p, w.GF.pitch, w.dE.p, w.dE.pitch,
               rows, ds);
   if (diff_wgrad(d, w.dE, w.M1, rows, d->s2w, d->s2b, 4 * ds, ds) || diff_dgrad(d, w.dE, rows, d->s2w, 4 * ds, ds, w.dM1)) return -1;
-  DIFF_LAUNCH(k_diff_mish_bwd, dim3(diff_ew_grid((long)rows * 4 * ds)), dim3(256), w.dM1.p, w.dM1.pitch, w.Z1.p, w.Z1.pitch, w.dZ1.p,
+  DEV_LAUNCH(d->stream, k_diff_mish_bwd, dim3(diff_ew_grid((long)rows * 4 * ds)), dim3(256), 0, w.dM1.p, w.dM1.pitch, w.Z1.p, w.Z1.pitch, w.dZ1.p,
               w.dZ1.pitch, rows, 4 * ds);
   if (diff_wgrad(d, w.dZ1, w.E0, rows, d->s1w, d->s1b, ds, 4 * ds)) return -1;
-  DIFF_LAUNCH(k_diff_colsum, dim3(diff_ew_grid(d->norm_n)), dim3(256), w.part, d->norm_n, rows, d->grads + d->norm_off);
+  DEV_LAUNCH(d->stream, k_diff_colsum, dim3(diff_ew_grid(d->norm_n)), dim3(256), 0, w.part, d->norm_n, rows, d->grads + d->norm_off);
   return 0;
 }
 
@@ -623,14 +554,14 @@ static int diff_enqueue_step(orl_diffusion* d, const long long* idx, int rows, c
   ip.acp = d->acp; ip.seed = d->c.seed; ip.counter = (uint64_t)d->kstep;
   ip.XT = w.XT.p; ip.xp = w.XT.pitch; ip.EPS = d->EPS; ip.TF = d->TF;
   ip.E0 = w.E0.p; ip.ep = w.E0.pitch; ip.GF = w.GF.p; ip.gp = w.GF.pitch;
-  DIFF_LAUNCH(k_diff_input, dim3(rows), dim3(64), ip);
+  DEV_LAUNCH(d->stream, k_diff_input, dim3(rows), dim3(64), 0, ip);
   if (diff_forward(d, w, d->params, rows, w.XT)) return -1;
-  DIFF_LAUNCH(k_diff_loss, dim3(1), dim3(256), w.PRED.p, w.PRED.pitch, d->EPS, rows, d->ad, w.dPRED.p, loss_dst, d->loss_cell);
+  DEV_LAUNCH(d->stream, k_diff_loss, dim3(1), dim3(256), 0, w.PRED.p, w.PRED.pitch, d->EPS, rows, d->ad, w.dPRED.p, loss_dst, d->loss_cell);
   if (diff_backward(d, w, rows, w.XT)) return -1;
   const double tt = (double)(d->kstep + 1);
   const double bc1 = 1.0 - std::pow((double)d->c.adam_beta1, tt), bc2 = 1.0 - std::pow((double)d->c.adam_beta2, tt);
   const double decay = diff_ema_decay(d->kstep);
-  DIFF_LAUNCH(k_diff_adam_ema, dim3(diff_ew_grid(d->P)), dim3(256), d->params, d->adam_m, d->adam_v, d->grads, d->ema, d->P, d->lr_tab,
+  DEV_LAUNCH(d->stream, k_diff_adam_ema, dim3(diff_ew_grid(d->P)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, d->ema, d->P, d->lr_tab,
               (long)d->kstep, bc1, (float)std::sqrt(bc2), d->c.adam_beta1, d->c.adam_beta2, d->c.adam_eps, (float)decay, (float)(1.0 - decay));
   d->kstep += 1;
   d->last_rows = rows;
@@ -646,27 +577,10 @@ static int diff_ready(orl_diffusion* d, const char* what, bool data) {
   return 0;
 }
 
-static int diff_grow_idx(orl_diffusion* d, long n) {
-  if (n <= d->idx_cap) return 0;
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  diff_free(d, d->idx_d); d->idx_d = nullptr;
-  if (diff_alloc_t(d, &d->idx_d, (size_t)n)) return -1;
-  d->idx_cap = n;
-  return 0;
-}
-
 // the layout of the parameter block; tensors in state_dict order of the modules that own them
 static long diff_layout(orl_diffusion* d) {
-  long off = 0;
-  auto add = [&](const std::string& name, std::vector<long> shape, bool align) {
-    if (align) off = (off + 3) & ~3L;
-    long n = 1;
-    for (long s : shape) n *= s;
-    d->tensors.push_back({name, off, shape});
-    const long o = off;
-    off += n;
-    return o;
-  };
+  TensorTable& t = d->tensors;
+  auto add = [&](const std::string& name, std::initializer_list<long> shape, bool align) { return t.add(name, shape, align, false); };
   const long ds = d->dsed;
   d->s1w = add("diffusion_step_encoder.1.weight", {4 * ds, ds}, true);
   d->s1b = add("diffusion_step_encoder.1.bias", {4 * ds}, true);
@@ -731,8 +645,7 @@ static long diff_layout(orl_diffusion* d) {
     if (b == 0) d->cb = o;
   }
   // the norm region: [gamma | beta] per GroupNorm
-  off = (off + 3) & ~3L;
-  d->norm_off = off;
+  d->norm_off = t.align4();
   for (size_t b = 0; b < d->blocks.size(); ++b) {
     DiffBlock& k = d->blocks[b];
     k.n0 = add(names[b] + ".blocks.0.block.1.weight", {k.out}, false) - d->norm_off;
@@ -742,8 +655,8 @@ static long diff_layout(orl_diffusion* d) {
   }
   d->fn = add("final_conv.0.block.1.weight", {d->start_dim}, false) - d->norm_off;
   add("final_conv.0.block.1.bias", {d->start_dim}, false);
-  d->norm_n = off - d->norm_off;
-  return (off + 3) & ~3L;
+  d->norm_n = t.off - d->norm_off;
+  return t.align4();
 }
 
 extern "C" {
@@ -784,11 +697,11 @@ int orl_diffusion_create(const orl_diffusion_config* cfg, orl_diffusion** out) {
   d->B = c.batch_size; d->G = c.n_groups; d->nlev = c.n_levels;
   d->P = diff_layout(d);
   bool bad = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess;
-  bad = bad || diff_alloc_t(d, &d->params, d->P) || diff_alloc_t(d, &d->ema, d->P) || diff_alloc_t(d, &d->adam_m, d->P) ||
-        diff_alloc_t(d, &d->adam_v, d->P) || diff_alloc_t(d, &d->grads, d->P) || diff_alloc_t(d, &d->acp, d->N) ||
-        diff_alloc_t(d, &d->coef, 5 * (size_t)d->N) || diff_ws_alloc(d, d->tw, d->B, true) || diff_alloc_t(d, &d->t_d, d->B) ||
-        diff_alloc_t(d, &d->eps_in, (size_t)d->B * d->ad) || diff_alloc_t(d, &d->EPS, (size_t)d->B * d->ad) || diff_alloc_t(d, &d->TF, d->B) ||
-        diff_alloc_t(d, &d->loss_cell, 1);
+  bad = bad || d->mem.alloc(&d->params, d->P) || d->mem.alloc(&d->ema, d->P) || d->mem.alloc(&d->adam_m, d->P) ||
+        d->mem.alloc(&d->adam_v, d->P) || d->mem.alloc(&d->grads, d->P) || d->mem.alloc(&d->acp, d->N) ||
+        d->mem.alloc(&d->coef, 5 * (size_t)d->N) || diff_ws_alloc(d, d->tw, d->B, true) || d->mem.alloc(&d->t_d, d->B) ||
+        d->mem.alloc(&d->eps_in, (size_t)d->B * d->ad) || d->mem.alloc(&d->EPS, (size_t)d->B * d->ad) || d->mem.alloc(&d->TF, d->B) ||
+        d->mem.alloc(&d->loss_cell, 1);
   if (bad) {
     const std::string msg = orl_last_error();
     orl_diffusion_destroy(d);
@@ -801,7 +714,7 @@ int orl_diffusion_create(const orl_diffusion_config* cfg, orl_diffusion** out) {
 void orl_diffusion_destroy(orl_diffusion* d) {
   if (!d) return;
   if (d->stream) hipStreamSynchronize(d->stream);
-  for (void* p : d->allocs) hipFree(p);
+  d->mem.free_all();
   if (d->stream) hipStreamDestroy(d->stream);
   delete d;
 }
@@ -809,12 +722,7 @@ void orl_diffusion_destroy(orl_diffusion* d) {
 int64_t orl_diffusion_floats(orl_diffusion* d) { return d ? d->P : -1; }
 int orl_diffusion_num_tensors(orl_diffusion* d) { return d ? (int)d->tensors.size() : -1; }
 int orl_diffusion_tensor(orl_diffusion* d, int idx, char* name, int name_cap, int64_t* offset, int32_t* ndim, int64_t shape[4]) {
-  if (!d || idx < 0 || idx >= (int)d->tensors.size()) return fail("orl_diffusion_tensor: index out of range");
-  const DiffTensor& t = d->tensors[idx];
-  if (name && name_cap > 0) { strncpy(name, t.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
-  if (offset) *offset = t.off;
-  if (ndim) *ndim = (int32_t)t.shape.size();
-  if (shape) for (size_t i = 0; i < t.shape.size() && i < 4; ++i) shape[i] = t.shape[i];
+  if (!d || d->tensors.query(idx, name, name_cap, offset, ndim, shape)) return fail("orl_diffusion_tensor: index out of range");
   return 0;
 }
 
@@ -824,16 +732,12 @@ static float* diff_block_of(orl_diffusion* d, int which) {
 int orl_diffusion_set(orl_diffusion* d, int which, const float* host, int64_t n) {
   if (!d || !host || !diff_block_of(d, which)) return fail("orl_diffusion_set: bad arguments");
   if (n != d->P) return fail("orl_diffusion_set: expected " + std::to_string(d->P) + " floats");
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  DIFF_HIP(hipMemcpy(diff_block_of(d, which), host, sizeof(float) * d->P, hipMemcpyHostToDevice));
-  return 0;
+  return block_from_host(d->stream, diff_block_of(d, which), host, d->P);
 }
 int orl_diffusion_get(orl_diffusion* d, int which, float* host, int64_t n) {
   if (!d || !host || !diff_block_of(d, which)) return fail("orl_diffusion_get: bad arguments");
   if (n != d->P) return fail("orl_diffusion_get: expected " + std::to_string(d->P) + " floats");
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  DIFF_HIP(hipMemcpy(host, diff_block_of(d, which), sizeof(float) * d->P, hipMemcpyDeviceToHost));
-  return 0;
+  return block_to_host(d->stream, host, diff_block_of(d, which), d->P);
 }
 int orl_diffusion_set_step_count(orl_diffusion* d, int64_t k) {
   if (!d || k < 0) return fail("orl_diffusion_set_step_count: bad arguments");
@@ -846,18 +750,18 @@ int orl_diffusion_set_schedule(orl_diffusion* d, const float* acp, const float* 
   if (!d || !acp || !coef) return fail("orl_diffusion_set_schedule: bad arguments");
   for (int i = 0; i < d->N; ++i)
     if (!(acp[i] > 0.f && acp[i] < 1.f) || !(coef[5 * i] > 0.f)) return fail("orl_diffusion_set_schedule: alphas_cumprod must lie in (0, 1)");
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  DIFF_HIP(hipMemcpy(d->acp, acp, sizeof(float) * d->N, hipMemcpyHostToDevice));
-  DIFF_HIP(hipMemcpy(d->coef, coef, sizeof(float) * 5 * d->N, hipMemcpyHostToDevice));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpy(d->acp, acp, sizeof(float) * d->N, hipMemcpyHostToDevice));
+  ORL_HIP(hipMemcpy(d->coef, coef, sizeof(float) * 5 * d->N, hipMemcpyHostToDevice));
   d->have_sched = true;
   return 0;
 }
 int orl_diffusion_set_lr(orl_diffusion* d, const double* table, int64_t n) {
   if (!d || !table || n < 1) return fail("orl_diffusion_set_lr: bad arguments");
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  diff_free(d, d->lr_tab); d->lr_tab = nullptr; d->n_lr = 0;
-  if (diff_alloc_t(d, &d->lr_tab, (size_t)n)) return -1;
-  DIFF_HIP(hipMemcpy(d->lr_tab, table, sizeof(double) * n, hipMemcpyHostToDevice));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  d->mem.release(&d->lr_tab); d->n_lr = 0;
+  if (d->mem.alloc(&d->lr_tab, (size_t)n)) return -1;
+  ORL_HIP(hipMemcpy(d->lr_tab, table, sizeof(double) * n, hipMemcpyHostToDevice));
   d->n_lr = n;
   return 0;
 }
@@ -867,7 +771,7 @@ int orl_diffusion_attach_buffer(orl_diffusion* d, orl_buffer* b) {
   buffer_view(b, &dev, &od, &ad, &OP, &AP, &n, &obs, &act);
   if (dev != d->c.device || od != d->od || ad != d->ad) return fail("orl_diffusion_attach_buffer: the buffer's device or dims differ");
   if (n < 1 || !obs || !act) return fail("orl_diffusion_attach_buffer: the buffer is empty");
-  DIFF_HIP(hipDeviceSynchronize());
+  ORL_HIP(hipDeviceSynchronize());
   d->d_obs = obs; d->d_act = act; d->OP = OP; d->AP = AP; d->n_data = n;
   return 0;
 }
@@ -879,13 +783,13 @@ int orl_diffusion_step(orl_diffusion* d, const int64_t* idx, int32_t rows, const
     if (idx[i] < 0 || idx[i] >= d->n_data) return fail("orl_diffusion_step: row index out of range");
     if (t && (t[i] < 0 || t[i] >= d->N)) return fail("orl_diffusion_step: t out of range");
   }
-  if (diff_grow_idx(d, d->B)) return -1;
-  DIFF_HIP(hipMemcpyAsync(d->idx_d, idx, sizeof(int64_t) * rows, hipMemcpyHostToDevice, d->stream));
-  if (t) DIFF_HIP(hipMemcpyAsync(d->t_d, t, sizeof(int64_t) * rows, hipMemcpyHostToDevice, d->stream));
-  if (eps) DIFF_HIP(hipMemcpyAsync(d->eps_in, eps, sizeof(float) * rows * d->ad, hipMemcpyHostToDevice, d->stream));
+  if (d->mem.grow(&d->idx_d, &d->idx_cap, d->B, d->stream)) return -1;
+  ORL_HIP(hipMemcpyAsync(d->idx_d, idx, sizeof(int64_t) * rows, hipMemcpyHostToDevice, d->stream));
+  if (t) ORL_HIP(hipMemcpyAsync(d->t_d, t, sizeof(int64_t) * rows, hipMemcpyHostToDevice, d->stream));
+  if (eps) ORL_HIP(hipMemcpyAsync(d->eps_in, eps, sizeof(float) * rows * d->ad, hipMemcpyHostToDevice, d->stream));
   if (diff_enqueue_step(d, d->idx_d, rows, t ? d->t_d : nullptr, eps ? d->eps_in : nullptr, d->loss_cell)) return -1;
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  if (loss_out) DIFF_HIP(hipMemcpy(loss_out, d->loss_cell, sizeof(float), hipMemcpyDeviceToHost));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  if (loss_out) ORL_HIP(hipMemcpy(loss_out, d->loss_cell, sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -897,20 +801,15 @@ int orl_diffusion_learn_epoch(orl_diffusion* d, const int64_t* order, int64_t n_
       if (order[i] < 0 || order[i] >= d->n_data) return fail("orl_diffusion_learn_epoch: row index out of range");
   const long steps = (long)((n_rows + d->B - 1) / d->B);
   if (d->kstep + steps > d->n_lr) return fail("orl_diffusion_learn_epoch: the epoch runs past the learning-rate table");
-  if (diff_grow_idx(d, (long)n_rows)) return -1;
-  if (steps > d->loss_cap) {
-    DIFF_HIP(hipStreamSynchronize(d->stream));
-    diff_free(d, d->loss_steps); d->loss_steps = nullptr;
-    if (diff_alloc_t(d, &d->loss_steps, (size_t)steps)) return -1;
-    d->loss_cap = steps;
-  }
-  DIFF_HIP(hipMemcpyAsync(d->idx_d, order, sizeof(int64_t) * n_rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
+  if (d->mem.grow(&d->idx_d, &d->idx_cap, (long)n_rows, d->stream)) return -1;
+  if (d->mem.grow(&d->loss_steps, &d->loss_cap, steps, d->stream)) return -1;
+  ORL_HIP(hipMemcpyAsync(d->idx_d, order, sizeof(int64_t) * n_rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
   for (long s = 0; s < steps; ++s) {
     const int rows = (int)std::min<int64_t>(d->B, n_rows - s * d->B);
     if (diff_enqueue_step(d, d->idx_d + s * d->B, rows, nullptr, nullptr, d->loss_steps + s)) return -1;
   }
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  if (losses_out) DIFF_HIP(hipMemcpy(losses_out, d->loss_steps, sizeof(float) * steps, hipMemcpyDeviceToHost));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  if (losses_out) ORL_HIP(hipMemcpy(losses_out, d->loss_steps, sizeof(float) * steps, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -925,43 +824,38 @@ int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const fl
       if (noise_idx[i] < 0 || noise_idx[i] >= noise_rows) return fail("orl_diffusion_sample: noise index out of range");
   const int ad = d->ad, od = d->od, N = d->N;
   if (n > d->s_cap || (!on_device && noise_rows > d->s_noise_cap)) {
-    DIFF_HIP(hipStreamSynchronize(d->stream));
+    ORL_HIP(hipStreamSynchronize(d->stream));
     const long cap = std::max<long>(n, d->s_cap), ncap = std::max<long>(noise_rows, d->s_noise_cap);
-    for (float** p : {&d->sObs, &d->sX, &d->sNoise, &d->sZ, &d->sZkeep, &d->sOut}) { diff_free(d, *p); *p = nullptr; }
-    diff_free(d, d->sIdx); d->sIdx = nullptr;
-    if (diff_alloc_t(d, &d->sObs, (size_t)cap * od) || diff_alloc_t(d, &d->sX, (size_t)cap * diff_rup4(ad)) ||
-        diff_alloc_t(d, &d->sNoise, (size_t)ncap * ad) || diff_alloc_t(d, &d->sZ, (size_t)N * cap * ad) ||
-        diff_alloc_t(d, &d->sZkeep, (size_t)cap * ad) || diff_alloc_t(d, &d->sOut, (size_t)cap * ad) || diff_alloc_t(d, &d->sIdx, (size_t)cap))
+    d->mem.release(&d->sObs, &d->sX, &d->sNoise, &d->sZ, &d->sZkeep, &d->sOut, &d->sIdx);
+    if (d->mem.alloc(&d->sObs, (size_t)cap * od) || d->mem.alloc(&d->sX, (size_t)cap * rup4(ad)) ||
+        d->mem.alloc(&d->sNoise, (size_t)ncap * ad) || d->mem.alloc(&d->sZ, (size_t)N * cap * ad) ||
+        d->mem.alloc(&d->sZkeep, (size_t)cap * ad) || d->mem.alloc(&d->sOut, (size_t)cap * ad) || d->mem.alloc(&d->sIdx, (size_t)cap))
       return -1;
     if (cap > d->sw.cap && diff_ws_alloc(d, d->sw, cap, false)) return -1;
     d->s_cap = cap; d->s_noise_cap = ncap;
   }
   const float* obs_d = obs; const float* noise_d = init_noise; const float* z_d = z; const long long* nidx_d = (const long long*)noise_idx;
-  if (!on_device) {
-    DIFF_HIP(hipMemcpyAsync(d->sObs, obs, sizeof(float) * n * od, hipMemcpyHostToDevice, d->stream));
-    DIFF_HIP(hipMemcpyAsync(d->sNoise, init_noise, sizeof(float) * noise_rows * ad, hipMemcpyHostToDevice, d->stream));
-    obs_d = d->sObs; noise_d = d->sNoise;
-    if (z) { DIFF_HIP(hipMemcpyAsync(d->sZ, z, sizeof(float) * N * n * ad, hipMemcpyHostToDevice, d->stream)); z_d = d->sZ; }
-    if (noise_idx) { DIFF_HIP(hipMemcpyAsync(d->sIdx, noise_idx, sizeof(int64_t) * n, hipMemcpyHostToDevice, d->stream)); nidx_d = d->sIdx; }
-  }
+  if (stage_in(d->stream, obs_d, d->sObs, (size_t)n * od, on_device) || stage_in(d->stream, noise_d, d->sNoise, (size_t)noise_rows * ad, on_device) ||
+      stage_in(d->stream, z_d, d->sZ, (size_t)N * n * ad, on_device) || stage_in(d->stream, nidx_d, d->sIdx, (size_t)n, on_device))
+    return -1;
   DiffWs& w = d->sw;
-  DView X; X.p = d->sX; X.pitch = X.lim = diff_rup4(ad);
-  DIFF_LAUNCH(k_diff_copy, dim3(diff_ew_grid(n * ad)), dim3(256), noise_d, ad, nidx_d, (long)noise_rows, X.p, X.pitch, (long)n, ad);
+  DevMat X; X.p = d->sX; X.pitch = X.lim = rup4(ad);
+  DEV_LAUNCH(d->stream, k_diff_copy, dim3(diff_ew_grid(n * ad)), dim3(256), 0, noise_d, ad, nidx_d, (long)noise_rows, X.p, X.pitch, (long)n, ad);
   for (int t = N - 1; t >= 0; --t) {
     DiffInputP ip;
     memset(&ip, 0, sizeof(ip));
     ip.rows = (int)n; ip.od = od; ip.ad = ad; ip.dsed = d->dsed; ip.N = N;
     ip.s_obs = obs_d; ip.t_const = t;
     ip.E0 = w.E0.p; ip.ep = w.E0.pitch; ip.GF = w.GF.p; ip.gp = w.GF.pitch;
-    DIFF_LAUNCH(k_diff_input, dim3((unsigned)n), dim3(64), ip);
+    DEV_LAUNCH(d->stream, k_diff_input, dim3((unsigned)n), dim3(64), 0, ip);
     if (diff_forward(d, w, d->ema, (int)n, X)) return -1;
-    DIFF_LAUNCH(k_diff_ddpm, dim3(diff_ew_grid(n * ad)), dim3(256), X.p, X.pitch, w.PRED.p, w.PRED.pitch, d->coef, t,
+    DEV_LAUNCH(d->stream, k_diff_ddpm, dim3(diff_ew_grid(n * ad)), dim3(256), 0, X.p, X.pitch, w.PRED.p, w.PRED.pitch, d->coef, t,
                 z_d ? z_d + (long)t * n * ad : (const float*)nullptr, d->sZkeep, (long)n, ad, d->c.seed, d->sample_calls * (uint64_t)N + (uint64_t)t);
   }
-  float* dst = on_device ? act_out : d->sOut;
-  DIFF_LAUNCH(k_diff_copy, dim3(diff_ew_grid(n * ad)), dim3(256), X.p, X.pitch, (const long long*)nullptr, 0L, dst, ad, (long)n, ad);
-  if (!on_device) DIFF_HIP(hipMemcpyAsync(act_out, d->sOut, sizeof(float) * n * ad, hipMemcpyDeviceToHost, d->stream));
-  DIFF_HIP(hipStreamSynchronize(d->stream));
+  float* dst = stage_dst(act_out, d->sOut, on_device);
+  DEV_LAUNCH(d->stream, k_diff_copy, dim3(diff_ew_grid(n * ad)), dim3(256), 0, X.p, X.pitch, (const long long*)nullptr, 0L, dst, ad, (long)n, ad);
+  if (stage_out(d->stream, act_out, d->sOut, (size_t)n * ad, on_device)) return -1;
+  ORL_HIP(hipStreamSynchronize(d->stream));
   d->sample_calls += 1;
   d->last_sample_n = n;
   return 0;
@@ -980,19 +874,17 @@ int64_t orl_diffusion_debug_read(orl_diffusion* d, const char* name, float* host
   else if (nm == "film") { src = w.FILM.p; cols = d->film_cols; pitch = w.FILM.pitch; }
   else if (nm == "loss") { src = d->loss_cell; rows = 1; cols = 1; pitch = 1; }
   else if (nm == "z") { src = d->sZkeep; rows = d->last_sample_n; cols = d->ad; pitch = d->ad; }
-  else if (nm == "x") { src = d->sX; rows = d->last_sample_n; cols = d->ad; pitch = diff_rup4(d->ad); }
+  else if (nm == "x") { src = d->sX; rows = d->last_sample_n; cols = d->ad; pitch = rup4(d->ad); }
   else return fail("orl_diffusion_debug_read: unknown tap " + nm);
   if (!src || rows < 1) return fail("orl_diffusion_debug_read: nothing recorded for " + nm);
   if ((int64_t)rows * cols > cap) return fail("orl_diffusion_debug_read: " + nm + " needs " + std::to_string(rows * cols) + " floats");
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  DIFF_HIP(hipMemcpy2D(host, sizeof(float) * cols, src, sizeof(float) * pitch, sizeof(float) * cols, rows, hipMemcpyDeviceToHost));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpy2D(host, sizeof(float) * cols, src, sizeof(float) * pitch, sizeof(float) * cols, rows, hipMemcpyDeviceToHost));
   return (int64_t)rows * cols;
 }
 int orl_diffusion_debug_grads(orl_diffusion* d, float* host, int64_t n) {
   if (!d || !host || n != d->P) return fail("orl_diffusion_debug_grads: bad arguments");
-  DIFF_HIP(hipStreamSynchronize(d->stream));
-  DIFF_HIP(hipMemcpy(host, d->grads, sizeof(float) * d->P, hipMemcpyDeviceToHost));
-  return 0;
+  return block_to_host(d->stream, host, d->grads, d->P);
 }
 
 }  // extern "C"

@@ -17,9 +17,11 @@
 //
 // Every formula that more than one kernel needs exists ONCE, as a device function below: dyn_soft_clamp(_grad) and dyn_std (every
 // logvar and std of this file), dyn_nll_elem (the NLL element of k_dyn_nll and of k_dyn_adv_head's dataset rows), dyn_col_sum and
-// dyn_reduce_tail (the two reduce kernels), dyn_block_sum256, dyn_draw_elite, dyn_scale_row, and rng.h's Philox / box_muller_one.
-// A sampler that must agree with another bit for bit agrees because both call the same function.  On the host, DynWs is the one
-// workspace type (learn, adversarial update, and step as a forward-only view) and dyn_forward / dyn_backward are the only layer loops.
+// dyn_reduce_tail (the two reduce kernels), dyn_draw_elite, dyn_scale_row, reduce.h's wave_sum / block_sum256_pairwise / softplus and
+// rng.h's Philox / box_muller_one.  A sampler that must agree with another bit for bit agrees because both call the same function.
+// On the host, DynWs is the one workspace type (learn, adversarial update, and step as a forward-only view) and dyn_forward /
+// dyn_backward are the only layer loops.  Allocation, the tensor table, transfers, staging and the GemmP of a layer's products come
+// from devobj.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,18 +29,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/orl_engine.h"
-#include "gemm.h"
+#include "devobj.h"
+#include "reduce.h"
 #include "rng.h"
 
 namespace orl {
 
-int fail(const std::string& msg);      // engine.hip: sets orl_last_error(), returns -1
-
-static inline int rup4(int x) { return (x + 3) & ~3; }
-
-// torch.nn.functional.softplus (beta 1, threshold 20) and its derivative
-__device__ inline float dyn_softplus(float y) { return y > 20.f ? y : log1pf(expf(y)); }
+// the derivative of reduce.h's softplus
 __device__ inline float dyn_dsoftplus(float y) { return y > 20.f ? 1.f : 1.f / (1.f + expf(-y)); }
 
 // soft_clamp of a raw logvar x (modules/dynamics_module.py): l1 = mx - softplus(mx - x), lv = mn + softplus(l1 - mn), with
@@ -46,9 +43,9 @@ __device__ inline float dyn_dsoftplus(float y) { return y > 20.f ? 1.f : 1.f / (
 struct DynClamp { float lv, s1, s2; };
 __device__ __forceinline__ DynClamp dyn_soft_clamp_grad(float x, float mx, float mn) {
   const float y1 = mx - x;
-  const float l1 = mx - dyn_softplus(y1);
+  const float l1 = mx - softplus(y1);
   const float y2 = l1 - mn;
-  return {mn + dyn_softplus(y2), dyn_dsoftplus(y1), dyn_dsoftplus(y2)};
+  return {mn + softplus(y2), dyn_dsoftplus(y1), dyn_dsoftplus(y2)};
 }
 __device__ __forceinline__ float dyn_soft_clamp(float x, float mx, float mn) { return dyn_soft_clamp_grad(x, mx, mn).lv; }
 // std = sqrt(exp(logvar)) as the reference writes it
@@ -74,22 +71,6 @@ __device__ __forceinline__ void dyn_store_elem(const DynNll& g, long row, int d,
   lterm[row * D + d] = g.lterm;
   gmax[row * D + d] = g.gmax;
   gmin[row * D + d] = g.gmin;
-}
-
-// sum over the 64 lanes of a wave, in every lane
-template <class T>
-__device__ __forceinline__ T dyn_wave_sum(T s) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
-// sum over a 256-thread block, for thread 0: the four wave sums as (s0 + s1) + (s2 + s3)
-__device__ __forceinline__ float dyn_block_sum256(float s) {
-  __shared__ float s_red[4];
-  s = dyn_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
 // the member of a row drawn from the run's elites with the first word of a Philox draw
@@ -160,7 +141,7 @@ __device__ __forceinline__ float dyn_col_sum(const float* lterm, const float* gm
     const int k = e / rows, i = i0 + (e - k * rows);
     s += a[(((long)r * K + k) * bs + i) * D + d];
   }
-  return dyn_wave_sum(s);
+  return wave_sum(s);
 }
 // ... and their tail on the 3 D column sums: the max / min_logvar gradients (+coef / -coef of the logvar-bound term) into the gradient
 // block and the loss without the decay term, the NLL a mean over `rows` rows and D dims
@@ -247,7 +228,7 @@ __global__ __launch_bounds__(256) void k_dyn_adam(DynAdamP p) {
     }
     dec *= 0.5f * wd;
   }
-  dec = dyn_block_sum256(dec);
+  dec = block_sum256_pairwise(dec);
   if (threadIdx.x == 0) p.decay_part[(long)r * p.nblk + blockIdx.x] = dec;
 }
 
@@ -258,7 +239,7 @@ __global__ __launch_bounds__(256) void k_dyn_loss(const float* __restrict__ nll,
   if (!active[r]) return;
   float s = 0.f;
   for (int b = threadIdx.x; b < nblk; b += blockDim.x) s += decay_part[(long)r * nblk + b];
-  s = dyn_block_sum256(s);
+  s = block_sum256_pairwise(s);
   if (threadIdx.x == 0) loss_sum[r] += nll[r] + s;
 }
 
@@ -273,7 +254,7 @@ __global__ __launch_bounds__(256) void k_dyn_val_mse(const float* __restrict__ O
     const float diff = OUT[(((long)r * K + k) * H + i) * op + d] - T[((long)r * H + i) * D + d];
     s += diff * diff;
   }
-  s = dyn_block_sum256(s);
+  s = block_sum256_pairwise(s);
   if (threadIdx.x == 0) mse[r * K + k] = s / (float)n;
 }
 
@@ -531,7 +512,7 @@ __global__ void k_dyn_adv_head(DynAdvHeadP p) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
     const double ex = el ? exp(s - m) : 0.0;
-    const double sum = dyn_wave_sum(ex);
+    const double sum = wave_sum(ex);
     wk[lane] = ex / sum;
     if (lane == 0) p.rowlp[ri] = m + log(sum) - log((double)p.n_elites);
   }
@@ -587,7 +568,7 @@ __global__ __launch_bounds__(1024) void k_dyn_adv_reduce(const float* __restrict
       const bool wa = c == 3 * D;
       double s = 0.0;
       for (int i = lane; i < Ba; i += 64) s += wa ? rowlp[(long)r * Ba + i] * (double)adv[(long)r * Ba + i] : rowlp[(long)r * Ba + i];
-      s = dyn_wave_sum(s);
+      s = wave_sum(s);
       if (lane == 0) red2[c - 3 * D] = s;
     }
   }
@@ -607,7 +588,7 @@ __global__ __launch_bounds__(256) void k_dyn_adv_metrics(const float* __restrict
   float s = 0.f;
   if (active[r])
     for (int b = threadIdx.x; b < nblk; b += blockDim.x) s += decay_part[(long)r * nblk + b];
-  s = dyn_block_sum256(s);
+  s = block_sum256_pairwise(s);
   if (threadIdx.x == 0) {
     float* m = metrics + 4 * r;
     if (!active[r]) { m[0] = m[1] = m[2] = m[3] = 0.f; return; }
@@ -622,8 +603,6 @@ __global__ __launch_bounds__(256) void k_dyn_adv_metrics(const float* __restrict
 }  // namespace orl
 
 using namespace orl;
-
-struct DynTensor { std::string name; long off; std::vector<long> shape; };
 
 // A training workspace: the matrices of one forward + backward over `rows` rows per (run, member), [R][K][rows][pitch] each.
 // `shared`: layer 0's input X is ONE [R][rows][pitch] matrix for the members (member stride 0).  The forward-only step workspace is a
@@ -642,7 +621,7 @@ struct orl_dynamics {
   int width[ORL_MAX_HIDDEN + 2], pitch[ORL_MAX_HIDDEN + 2];
   long P = 0, off_max = 0, off_min = 0;
   long w_off[ORL_MAX_HIDDEN + 1], b_off[ORL_MAX_HIDDEN + 1], sw_off[ORL_MAX_HIDDEN + 1], sb_off[ORL_MAX_HIDDEN + 1];
-  std::vector<DynTensor> tensors;
+  TensorTable tensors;
   hipStream_t stream = nullptr;
   float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *grads = nullptr;
   int* elites_d = nullptr;
@@ -679,25 +658,8 @@ struct orl_dynamics {
   float *aInObs = nullptr, *aInAct = nullptr, *aSlObs = nullptr, *aSlAct = nullptr, *aSlNext = nullptr, *aSlRew = nullptr,
         *aNoise = nullptr, *aNext = nullptr, *aRew = nullptr;
   int *aMidx = nullptr, *aMidxOut = nullptr;
-  std::vector<void*> allocs;
+  DevAllocs mem{"orl_dyn"};
 };
-
-static int dyn_alloc(orl_dynamics* d, void** p, size_t bytes) {
-  if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) return fail("orl_dyn: hipMalloc of " + std::to_string(bytes) + " bytes failed");
-  if (hipMemset(*p, 0, bytes ? bytes : 16) != hipSuccess) return fail("orl_dyn: hipMemset failed");
-  d->allocs.push_back(*p);
-  return 0;
-}
-template <class T>
-static int dyn_alloc_t(orl_dynamics* d, T** p, size_t count) { return dyn_alloc(d, (void**)p, sizeof(T) * count); }
-static void dyn_free(orl_dynamics* d, void* p) {
-  if (!p) return;
-  for (auto it = d->allocs.begin(); it != d->allocs.end(); ++it)
-    if (*it == p) { d->allocs.erase(it); break; }
-  hipFree(p);
-}
-template <class... T>
-static void dyn_release(orl_dynamics* d, T**... ps) { ((dyn_free(d, *ps), *ps = nullptr), ...); }
 
 static int dyn_hmax(const orl_dynamics* d, int last) {      // widest pitch of layers 1 .. last
   int hmax = 4;
@@ -706,97 +668,54 @@ static int dyn_hmax(const orl_dynamics* d, int last) {      // widest pitch of l
 }
 
 static void dyn_ws_release(orl_dynamics* d, DynWs& w) {
-  dyn_release(d, &w.X, &w.OUT, &w.dOUT, &w.dA, &w.dB, &w.lterm, &w.gmax, &w.gmin);
-  for (int l = 0; l < d->L; ++l) dyn_release(d, &w.H[l], &w.Z[l]);
+  d->mem.release(&w.X, &w.OUT, &w.dOUT, &w.dA, &w.dB, &w.lterm, &w.gmax, &w.gmin);
+  for (int l = 0; l < d->L; ++l) d->mem.release(&w.H[l], &w.Z[l]);
   w.rows = 0;
 }
 static int dyn_ws_alloc(orl_dynamics* d, DynWs& w, long rows, bool shared) {
   dyn_ws_release(d, w);
   const long RK = (long)d->R * d->K * rows, po = d->pitch[d->L + 1], hmax = dyn_hmax(d, d->L + 1);
-  bool bad = dyn_alloc_t(d, &w.X, (shared ? d->R * rows : RK) * d->pitch[0]) || dyn_alloc_t(d, &w.OUT, RK * po) ||
-             dyn_alloc_t(d, &w.dOUT, RK * po) || dyn_alloc_t(d, &w.dA, RK * hmax) || dyn_alloc_t(d, &w.dB, RK * hmax) ||
-             dyn_alloc_t(d, &w.lterm, RK * d->D) || dyn_alloc_t(d, &w.gmax, RK * d->D) || dyn_alloc_t(d, &w.gmin, RK * d->D);
-  for (int l = 0; l < d->L && !bad; ++l) bad = dyn_alloc_t(d, &w.H[l], RK * d->pitch[l + 1]) || dyn_alloc_t(d, &w.Z[l], RK * d->pitch[l + 1]);
+  bool bad = d->mem.alloc(&w.X, (shared ? d->R * rows : RK) * d->pitch[0]) || d->mem.alloc(&w.OUT, RK * po) ||
+             d->mem.alloc(&w.dOUT, RK * po) || d->mem.alloc(&w.dA, RK * hmax) || d->mem.alloc(&w.dB, RK * hmax) ||
+             d->mem.alloc(&w.lterm, RK * d->D) || d->mem.alloc(&w.gmax, RK * d->D) || d->mem.alloc(&w.gmin, RK * d->D);
+  for (int l = 0; l < d->L && !bad; ++l) bad = d->mem.alloc(&w.H[l], RK * d->pitch[l + 1]) || d->mem.alloc(&w.Z[l], RK * d->pitch[l + 1]);
   if (bad) return -1;
   w.rows = rows; w.shared = shared;
   return 0;
 }
 
-#define DYN_HIP(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t _e = (expr);                                                                             \
-    if (_e != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(_e));               \
-  } while (0)
-// one kernel launch on the object's stream (d->stream) and its check
-#define DYN_LAUNCH(kernel, grid, block, lds, ...)                                                       \
-  do {                                                                                                  \
-    hipLaunchKernelGGL(kernel, grid, block, lds, d->stream, __VA_ARGS__);                               \
-    if (hipGetLastError() != hipSuccess) return fail(#kernel ": launch failed");                        \
-  } while (0)
-
-// ---- the matrix products (csrc/gemm.h) ----
-struct DMat {                                        // [run][member][row][pitch]; s1 = 0: one matrix shared by the members
-  float* p; long s0, s1; int pitch;
-  ZPtr z() const { return {p, s0, s1}; }
-};
+// ---- the matrix products (devobj.h's builders on csrc/gemm.h), batched over (run, member) ----
+// layer l's EnsembleLinear weight and bias inside `block` (the parameters or the gradients)
+static LinearP dyn_linear(const orl_dynamics* d, float* block, int l) {
+  const int in = d->width[l], out = d->width[l + 1];
+  return {{block + d->w_off[l], d->P, (long)in * out}, {block + d->b_off[l], d->P, (long)out}, in, out, true, d->K};
+}
 
 // Y = act(X W_l + b_l) for every (run, member); epi E_BIAS_SWISH (z to Zo when non-null) or E_BIAS
-static int dyn_fwd(orl_dynamics* d, const DMat& X, int M, int l, const DMat& Y, float* Zo, bool swish) {
-  const int in = d->width[l], out = d->width[l + 1];
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.A = X.z(); p.a_sr = X.pitch; p.a_sk = 1;
-  p.B = {d->params + d->w_off[l], d->P, (long)in * out}; p.b_sr = 1; p.b_sk = out; p.b_rlim = out & ~3;
-  p.C = Y.p; p.c_s0 = Y.s0; p.c_s1 = Y.s1; p.c_sr = Y.pitch; p.c_sn = 1;
-  p.M = M; p.N = out; p.K = in;
-  p.nz1 = d->K; p.ksplit = 1;
-  p.bias = {d->params + d->b_off[l], d->P, (long)out};
+static int dyn_fwd(orl_dynamics* d, const DevMat& X, int M, int l, const DevMat& Y, float* Zo, bool swish) {
+  GemmP p = linear_fwd_p(X, M, dyn_linear(d, d->params, l), Y);
   p.z_out = Zo;
-  const int nz = d->R * d->K;
-  const int cfg = pick_cfg(p.M, p.N, p.K, nz);
-  const bool kpad = X.pitch >= rup4(in);
-  hipError_t e = swish ? launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_SWISH>(cfg, p, nz, d->stream, kpad, false, P_F32)
-                       : launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(cfg, p, nz, d->stream, kpad, false, P_F32);
-  if (e != hipSuccess) return fail(std::string("orl_dyn forward gemm: ") + hipGetErrorString(e));
-  return 0;
+  const int nz = d->R * d->K, cfg = pick_cfg(p.M, p.N, p.K, nz);
+  const bool kpad = X.pitch >= rup4(p.K);
+  return gemm_done(swish ? launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_SWISH>(cfg, p, nz, d->stream, kpad, false, P_F32)
+                         : launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(cfg, p, nz, d->stream, kpad, false, P_F32), "orl_dyn forward");
 }
 
 // dX = (dY W_l^T) * Swish'(Zin) where Zin is the pre-activation of layer l's input
-static int dyn_dgrad(orl_dynamics* d, const DMat& dY, int M, int l, const DMat& dX, const DMat& Zin) {
-  const int in = d->width[l], out = d->width[l + 1];
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.A = dY.z(); p.a_sr = dY.pitch; p.a_sk = 1;
-  p.B = {d->params + d->w_off[l], d->P, (long)in * out}; p.b_sr = out; p.b_sk = 1;
-  p.C = dX.p; p.c_s0 = dX.s0; p.c_s1 = dX.s1; p.c_sr = dX.pitch; p.c_sn = 1;
-  p.M = M; p.N = in; p.K = out;
-  p.nz1 = d->K; p.ksplit = 1;
+static int dyn_dgrad(orl_dynamics* d, const DevMat& dY, int M, int l, const DevMat& dX, const DevMat& Zin) {
+  GemmP p = linear_dgrad_p(dY, M, dyn_linear(d, d->params, l), dX);
   p.aux = Zin.z(); p.aux_sr = Zin.pitch;
   const int nz = d->R * d->K;
-  const int cfg = pick_cfg(p.M, p.N, p.K, nz);
-  hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_SWISH_GRAD>(cfg, p, nz, d->stream, dY.pitch >= rup4(out), false, P_F32);
-  if (e != hipSuccess) return fail(std::string("orl_dyn dgrad gemm: ") + hipGetErrorString(e));
-  return 0;
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_SWISH_GRAD>(pick_cfg(p.M, p.N, p.K, nz), p, nz, d->stream, dY.pitch >= rup4(p.K),
+                                                                 false, P_F32), "orl_dyn dgrad");
 }
 
 // dW_l = X^T dY (stored (in, out)-major like the weight), db_l = column sums of dY, into the gradient block
-static int dyn_wgrad(orl_dynamics* d, const DMat& dY, const DMat& X, int M, int l) {
-  const int in = d->width[l], out = d->width[l + 1];
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.A = dY.z(); p.a_sr = 1; p.a_sk = dY.pitch;
-  p.B = X.z(); p.b_sr = 1; p.b_sk = X.pitch;
-  p.a_rlim = dY.pitch & ~3; p.b_rlim = X.pitch & ~3;
-  p.ones_row = 1 << 30;
-  p.M = out; p.N = in; p.K = M;
-  p.nz1 = d->K; p.ksplit = 1;
-  p.C = d->grads + d->w_off[l]; p.c_sr = 1; p.c_sn = out; p.c_s0 = d->P; p.c_s1 = (long)in * out; p.c_ks = 0;
-  p.bias_out = d->grads + d->b_off[l]; p.bo_s0 = d->P; p.bo_s1 = out; p.bo_ks = 0;
+static int dyn_wgrad(orl_dynamics* d, const DevMat& dY, const DevMat& X, int M, int l) {
+  const GemmP p = linear_wgrad_p(dY, X, M, dyn_linear(d, d->grads, l));
   const int nz = d->R * d->K;
-  const int cfg = pick_cfg(p.M, p.N, p.K, nz);
-  hipError_t e = launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(cfg, p, nz, d->stream, false, false, P_F32);
-  if (e != hipSuccess) return fail(std::string("orl_dyn wgrad gemm: ") + hipGetErrorString(e));
-  return 0;
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(pick_cfg(p.M, p.N, p.K, nz), p, nz, d->stream, false, false, P_F32),
+                   "orl_dyn wgrad");
 }
 
 // k_dyn_adam's arguments less the optimizer (m, v, lr, betas, eps, batch): the trainable segments with their decays
@@ -817,21 +736,21 @@ static DynAdamP dyn_adam_params(orl_dynamics* d) {
 }
 
 // matrix p of a workspace at layer l's width, and the workspace's layer-0 input
-static DMat dyn_mat(const orl_dynamics* d, const DynWs& w, float* p, int l) {
+static DevMat dyn_mat(const orl_dynamics* d, const DynWs& w, float* p, int l) {
   const long pt = d->pitch[l];
-  return {p, d->K * w.rows * pt, w.rows * pt, (int)pt};
+  return {p, d->K * w.rows * pt, w.rows * pt, (int)pt, (int)pt};
 }
-static DMat dyn_input(const orl_dynamics* d, const DynWs& w) {
-  DMat X = dyn_mat(d, w, w.X, 0);
+static DevMat dyn_input(const orl_dynamics* d, const DynWs& w) {
+  DevMat X = dyn_mat(d, w, w.X, 0);
   if (w.shared) { X.s0 = X.s1; X.s1 = 0; }
   return X;
 }
 
 // forward of the whole ensemble over the first `rows` rows of a workspace: L x E_BIAS_SWISH (pre-activations to Z when kept), E_BIAS
 static int dyn_forward(orl_dynamics* d, const DynWs& w, int rows, bool keep_z) {
-  DMat X = dyn_input(d, w);
+  DevMat X = dyn_input(d, w);
   for (int l = 0; l < d->L; ++l) {
-    const DMat Y = dyn_mat(d, w, w.H[l], l + 1);
+    const DevMat Y = dyn_mat(d, w, w.H[l], l + 1);
     if (dyn_fwd(d, X, rows, l, Y, keep_z ? w.Z[l] : nullptr, true)) return -1;
     X = Y;
   }
@@ -840,11 +759,11 @@ static int dyn_forward(orl_dynamics* d, const DynWs& w, int rows, bool keep_z) {
 
 // backward from dOUT, top down: weight / bias gradients into the gradient block, input gradients alternating between dA and dB
 static int dyn_backward(orl_dynamics* d, const DynWs& w, int rows) {
-  DMat dY = dyn_mat(d, w, w.dOUT, d->L + 1);
+  DevMat dY = dyn_mat(d, w, w.dOUT, d->L + 1);
   for (int l = d->L; l >= 0; --l) {
     if (dyn_wgrad(d, dY, l ? dyn_mat(d, w, w.H[l - 1], l) : dyn_input(d, w), rows, l)) return -1;
     if (l > 0) {
-      const DMat dX = dyn_mat(d, w, (l & 1) ? w.dB : w.dA, l);
+      const DevMat dX = dyn_mat(d, w, (l & 1) ? w.dB : w.dA, l);
       if (dyn_dgrad(d, dY, rows, l, dX, dyn_mat(d, w, w.Z[l - 1], l))) return -1;
       dY = dX;
     }
@@ -854,19 +773,19 @@ static int dyn_backward(orl_dynamics* d, const DynWs& w, int rows) {
 
 static int dyn_grow_step(orl_dynamics* d, long rows) {
   if (rows <= d->s_cap) return 0;
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
   DynWs& w = d->sw;
-  dyn_release(d, &w.X, &d->sT, &d->sH0, &d->sH1, &w.OUT, &d->sObs, &d->sAct, &d->sNoise, &d->sNext, &d->sRew, &d->sRaw, &d->sPen, &d->sIdx,
+  d->mem.release(&w.X, &d->sT, &d->sH0, &d->sH1, &w.OUT, &d->sObs, &d->sAct, &d->sNoise, &d->sNext, &d->sRew, &d->sRaw, &d->sPen, &d->sIdx,
               &d->sMidx, &d->sMidxOut);
   const long R = d->R, K = d->K;
   const int hmax = dyn_hmax(d, d->L);
-  if (dyn_alloc_t(d, &w.X, R * rows * d->pitch[0]) || dyn_alloc_t(d, &d->sT, R * rows * d->D) ||
-      dyn_alloc_t(d, &d->sH0, R * K * rows * hmax) || dyn_alloc_t(d, &d->sH1, R * K * rows * hmax) ||
-      dyn_alloc_t(d, &w.OUT, R * K * rows * d->pitch[d->L + 1]) || dyn_alloc_t(d, &d->sObs, R * rows * d->od) ||
-      dyn_alloc_t(d, &d->sAct, R * rows * d->ad) || dyn_alloc_t(d, &d->sNoise, R * K * rows * d->D) ||
-      dyn_alloc_t(d, &d->sNext, R * rows * d->od) || dyn_alloc_t(d, &d->sRew, R * rows) || dyn_alloc_t(d, &d->sRaw, R * rows) ||
-      dyn_alloc_t(d, &d->sPen, R * rows) || dyn_alloc_t(d, &d->sIdx, R * rows) || dyn_alloc_t(d, &d->sMidx, R * rows) ||
-      dyn_alloc_t(d, &d->sMidxOut, R * rows))
+  if (d->mem.alloc(&w.X, R * rows * d->pitch[0]) || d->mem.alloc(&d->sT, R * rows * d->D) ||
+      d->mem.alloc(&d->sH0, R * K * rows * hmax) || d->mem.alloc(&d->sH1, R * K * rows * hmax) ||
+      d->mem.alloc(&w.OUT, R * K * rows * d->pitch[d->L + 1]) || d->mem.alloc(&d->sObs, R * rows * d->od) ||
+      d->mem.alloc(&d->sAct, R * rows * d->ad) || d->mem.alloc(&d->sNoise, R * K * rows * d->D) ||
+      d->mem.alloc(&d->sNext, R * rows * d->od) || d->mem.alloc(&d->sRew, R * rows) || d->mem.alloc(&d->sRaw, R * rows) ||
+      d->mem.alloc(&d->sPen, R * rows) || d->mem.alloc(&d->sIdx, R * rows) || d->mem.alloc(&d->sMidx, R * rows) ||
+      d->mem.alloc(&d->sMidxOut, R * rows))
     return -1;
   for (int l = 0; l < d->L; ++l) w.H[l] = (l & 1) ? d->sH1 : d->sH0;
   w.shared = true;
@@ -876,15 +795,8 @@ static int dyn_grow_step(orl_dynamics* d, long rows) {
 
 // parameter block: state_dict order, every tensor 16-B aligned; returns its floats
 static long dyn_layout(orl_dynamics* d) {
-  long off = 0;
-  auto add = [&](const std::string& name, std::vector<long> shape) {
-    long n = 1;
-    for (long s : shape) n *= s;
-    d->tensors.push_back({name, off, shape});
-    const long o = off;
-    off += (n + 3) & ~3L;
-    return o;
-  };
+  TensorTable& t = d->tensors;
+  auto add = [&](const std::string& name, std::initializer_list<long> shape) { return t.add(name, shape, false, true); };
   const long K = d->K;
   d->off_max = add("max_logvar", {d->D});
   d->off_min = add("min_logvar", {d->D});
@@ -896,7 +808,7 @@ static long dyn_layout(orl_dynamics* d) {
     d->sw_off[l] = add(pre + "saved_weight", {K, in, o});
     d->sb_off[l] = add(pre + "saved_bias", {K, 1, o});
   }
-  return off;
+  return t.off;
 }
 
 // the elite count that every run shares, or -1 with the refusal of the call named
@@ -915,7 +827,7 @@ static int dyn_upload_midx(orl_dynamics* d, const int64_t* idx, long count, std:
     if (idx[i] < 0 || idx[i] >= d->K) return fail(std::string(what) + ": model index out of range");
     h[i] = (int)idx[i];
   }
-  DYN_HIP(hipMemcpyAsync(dst, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, d->stream));
+  ORL_HIP(hipMemcpyAsync(dst, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, d->stream));
   return 0;
 }
 
@@ -928,26 +840,8 @@ static int dyn_upload_run_state(orl_dynamics* d, const int32_t* active, const st
   auto upload = [&](void* dst, const void* src, size_t bytes) {
     return on_stream ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d->stream) : hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
   };
-  DYN_HIP(upload(d->active_d, act.data(), sizeof(int) * d->R));
-  DYN_HIP(upload(d->t0_d, tstep.data(), sizeof(long long) * d->R));
-  return 0;
-}
-
-// Staging of a call's arrays.  In: a host array is copied to `stage` on the stream and p repointed there; a device array (on_device)
-// or a null one stays.  dyn_dst: where the kernel writes an output; out: the staged output copied back to the host on the stream.
-template <class T>
-static int dyn_stage_in(orl_dynamics* d, const T*& p, T* stage, size_t count, int on_device) {
-  if (on_device || !p) return 0;
-  DYN_HIP(hipMemcpyAsync(stage, p, sizeof(T) * count, hipMemcpyHostToDevice, d->stream));
-  p = stage;
-  return 0;
-}
-template <class T>
-static T* dyn_dst(T* user, T* stage, int on_device) { return user && !on_device ? stage : user; }
-template <class T>
-static int dyn_stage_out(orl_dynamics* d, T* user, const T* stage, size_t count, int on_device) {
-  if (on_device || !user) return 0;
-  DYN_HIP(hipMemcpyAsync(user, stage, sizeof(T) * count, hipMemcpyDeviceToHost, d->stream));
+  ORL_HIP(upload(d->active_d, act.data(), sizeof(int) * d->R));
+  ORL_HIP(upload(d->t0_d, tstep.data(), sizeof(long long) * d->R));
   return 0;
 }
 
@@ -995,12 +889,12 @@ int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out) {
   d->nblk = (int)((d->P + 1023) / 1024);
   bool bad = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess;
   if (c.external_arena) d->params = c.external_arena;
-  else bad = bad || dyn_alloc_t(d, &d->params, R * d->P);
-  bad = bad || dyn_alloc_t(d, &d->adam_m, R * d->P) || dyn_alloc_t(d, &d->adam_v, R * d->P) ||
-        dyn_alloc_t(d, &d->grads, R * d->P) || dyn_alloc_t(d, &d->elites_d, R * K) || dyn_alloc_t(d, &d->mu, R * d->in) ||
-        dyn_alloc_t(d, &d->sd, R * d->in) || dyn_ws_alloc(d, d->lw, B, false) || dyn_alloc_t(d, &d->T, R * K * B * d->D) ||
-        dyn_alloc_t(d, &d->decay_part, R * d->nblk) || dyn_alloc_t(d, &d->nll, R) || dyn_alloc_t(d, &d->loss_sum, R) ||
-        dyn_alloc_t(d, &d->active_d, R) || dyn_alloc_t(d, &d->t0_d, R);
+  else bad = bad || d->mem.alloc(&d->params, R * d->P);
+  bad = bad || d->mem.alloc(&d->adam_m, R * d->P) || d->mem.alloc(&d->adam_v, R * d->P) ||
+        d->mem.alloc(&d->grads, R * d->P) || d->mem.alloc(&d->elites_d, R * K) || d->mem.alloc(&d->mu, R * d->in) ||
+        d->mem.alloc(&d->sd, R * d->in) || dyn_ws_alloc(d, d->lw, B, false) || d->mem.alloc(&d->T, R * K * B * d->D) ||
+        d->mem.alloc(&d->decay_part, R * d->nblk) || d->mem.alloc(&d->nll, R) || d->mem.alloc(&d->loss_sum, R) ||
+        d->mem.alloc(&d->active_d, R) || d->mem.alloc(&d->t0_d, R);
   if (bad) {
     const std::string msg = orl_last_error();
     orl_dyn_destroy(d);
@@ -1029,13 +923,13 @@ int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out) {
 void orl_dyn_destroy(orl_dynamics* d) {
   if (!d) return;
   if (d->stream) hipStreamSynchronize(d->stream);
-  for (void* p : d->allocs) hipFree(p);
+  d->mem.free_all();
   if (d->stream) hipStreamDestroy(d->stream);
   delete d;
 }
 
 int orl_dyn_sync(orl_dynamics* d) {
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
   return 0;
 }
 
@@ -1053,12 +947,7 @@ int64_t orl_dyn_config_floats(const orl_dyn_config* c) {
 int orl_dyn_num_tensors(orl_dynamics* d) { return d ? (int)d->tensors.size() : -1; }
 
 int orl_dyn_tensor(orl_dynamics* d, int idx, char* name, int name_cap, int64_t* offset, int32_t* ndim, int64_t shape[4]) {
-  if (!d || idx < 0 || idx >= (int)d->tensors.size()) return fail("orl_dyn_tensor: index out of range");
-  const DynTensor& t = d->tensors[idx];
-  if (name && name_cap > 0) { strncpy(name, t.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
-  if (offset) *offset = t.off;
-  if (ndim) *ndim = (int32_t)t.shape.size();
-  if (shape) for (size_t i = 0; i < t.shape.size() && i < 4; ++i) shape[i] = t.shape[i];
+  if (!d || d->tensors.query(idx, name, name_cap, offset, ndim, shape)) return fail("orl_dyn_tensor: index out of range");
   return 0;
 }
 
@@ -1072,28 +961,20 @@ static int dyn_check_run(orl_dynamics* d, int run, int64_t n, const char* what) 
 }
 
 int orl_dyn_set(orl_dynamics* d, int run, const float* host, int64_t n) {
-  if (dyn_check_run(d, run, n, "orl_dyn_set")) return -1;
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  DYN_HIP(hipMemcpy(d->params + (long)run * d->P, host, sizeof(float) * d->P, hipMemcpyHostToDevice));
-  return 0;
+  return dyn_check_run(d, run, n, "orl_dyn_set") || block_from_host(d->stream, d->params + (long)run * d->P, host, d->P) ? -1 : 0;
 }
 
 int orl_dyn_get(orl_dynamics* d, int run, float* host, int64_t n) {
-  if (dyn_check_run(d, run, n, "orl_dyn_get")) return -1;
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  DYN_HIP(hipMemcpy(host, d->params + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
-  return 0;
+  return dyn_check_run(d, run, n, "orl_dyn_get") || block_to_host(d->stream, host, d->params + (long)run * d->P, d->P) ? -1 : 0;
 }
 
 // one run's Adam moments to (get) or from (set) host arrays, either of which may be null
 static int dyn_adam_xfer(orl_dynamics* d, int run, float* dev_m, float* dev_v, const float* m, const float* v, bool get) {
-  DYN_HIP(hipStreamSynchronize(d->stream));
   const float* host[2] = {m, v};
   float* dev[2] = {dev_m + (long)run * d->P, dev_v + (long)run * d->P};
   for (int i = 0; i < 2; ++i) {
     if (!host[i]) continue;
-    if (get) DYN_HIP(hipMemcpy(const_cast<float*>(host[i]), dev[i], sizeof(float) * d->P, hipMemcpyDeviceToHost));
-    else DYN_HIP(hipMemcpy(dev[i], host[i], sizeof(float) * d->P, hipMemcpyHostToDevice));
+    if (get ? block_to_host(d->stream, const_cast<float*>(host[i]), dev[i], d->P) : block_from_host(d->stream, dev[i], host[i], d->P)) return -1;
   }
   return 0;
 }
@@ -1118,8 +999,8 @@ int orl_dyn_set_elites(orl_dynamics* d, int run, const int64_t* idx, int n) {
     if (idx[i] < 0 || idx[i] >= d->K) return fail("orl_dyn_set_elites: member index out of range");
     el[i] = (int)idx[i];
   }
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  DYN_HIP(hipMemcpy(d->elites_d + (long)run * d->K, el.data(), sizeof(int) * d->K, hipMemcpyHostToDevice));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpy(d->elites_d + (long)run * d->K, el.data(), sizeof(int) * d->K, hipMemcpyHostToDevice));
   d->elites_h[run].assign(idx, idx + n);
   return 0;
 }
@@ -1133,21 +1014,21 @@ int orl_dyn_get_elites(orl_dynamics* d, int run, int64_t* idx, int cap) {
 
 int orl_dyn_load_data(orl_dynamics* d, const float* inputs, const float* targets, int64_t n) {
   if (!d || n < 1) return fail("orl_dyn_load_data: empty dataset");
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  dyn_free(d, d->data_in); dyn_free(d, d->data_tg);
-  d->data_in = d->data_tg = nullptr; d->n_data = 0;
-  if (dyn_alloc_t(d, &d->data_in, n * d->in) || dyn_alloc_t(d, &d->data_tg, n * d->D)) return -1;
-  DYN_HIP(hipMemcpy(d->data_in, inputs, sizeof(float) * n * d->in, hipMemcpyHostToDevice));
-  DYN_HIP(hipMemcpy(d->data_tg, targets, sizeof(float) * n * d->D, hipMemcpyHostToDevice));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  d->mem.release(&d->data_in, &d->data_tg);
+  d->n_data = 0;
+  if (d->mem.alloc(&d->data_in, n * d->in) || d->mem.alloc(&d->data_tg, n * d->D)) return -1;
+  ORL_HIP(hipMemcpy(d->data_in, inputs, sizeof(float) * n * d->in, hipMemcpyHostToDevice));
+  ORL_HIP(hipMemcpy(d->data_tg, targets, sizeof(float) * n * d->D, hipMemcpyHostToDevice));
   d->n_data = n;
   return 0;
 }
 
 int orl_dyn_set_scaler(orl_dynamics* d, int run, const float* mu, const float* std) {
   if (dyn_check_run(d, run, -1, "orl_dyn_set_scaler")) return -1;
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  DYN_HIP(hipMemcpy(d->mu + (long)run * d->in, mu, sizeof(float) * d->in, hipMemcpyHostToDevice));
-  DYN_HIP(hipMemcpy(d->sd + (long)run * d->in, std, sizeof(float) * d->in, hipMemcpyHostToDevice));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpy(d->mu + (long)run * d->in, mu, sizeof(float) * d->in, hipMemcpyHostToDevice));
+  ORL_HIP(hipMemcpy(d->sd + (long)run * d->in, std, sizeof(float) * d->in, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -1157,14 +1038,9 @@ static int dyn_upload_idx(orl_dynamics* d, const int64_t* idx, long count) {
     if (idx[i] < 0 || idx[i] >= d->n_data) return fail("orl_dyn: row index " + std::to_string(idx[i]) + " outside the loaded data");
     h[i] = (int)idx[i];
   }
-  if (count > d->idx_cap) {
-    DYN_HIP(hipStreamSynchronize(d->stream));
-    dyn_free(d, d->idx_d); d->idx_d = nullptr; d->idx_cap = 0;
-    if (dyn_alloc_t(d, &d->idx_d, count)) return -1;
-    d->idx_cap = count;
-  }
-  DYN_HIP(hipMemcpyAsync(d->idx_d, h.data(), sizeof(int) * count, hipMemcpyHostToDevice, d->stream));
-  DYN_HIP(hipStreamSynchronize(d->stream));      // h is released on return
+  if (d->mem.grow(&d->idx_d, &d->idx_cap, count, d->stream)) return -1;
+  ORL_HIP(hipMemcpyAsync(d->idx_d, h.data(), sizeof(int) * count, hipMemcpyHostToDevice, d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));      // h is released on return
   return 0;
 }
 
@@ -1176,7 +1052,7 @@ int orl_dyn_learn_epoch(orl_dynamics* d, const int64_t* idx, int64_t train_size,
   if (dyn_upload_idx(d, idx, (long)R * K * train_size)) return -1;
   std::vector<int> act;
   if (dyn_upload_run_state(d, active, d->tstep, act, false)) return -1;
-  DYN_HIP(hipMemsetAsync(d->loss_sum, 0, sizeof(float) * R, d->stream));
+  ORL_HIP(hipMemsetAsync(d->loss_sum, 0, sizeof(float) * R, d->stream));
   const long nb = (train_size + B - 1) / B;
   const int p0 = d->pitch[0], po = d->pitch[d->L + 1];
   DynAdamP a = dyn_adam_params(d);
@@ -1185,26 +1061,26 @@ int orl_dyn_learn_epoch(orl_dynamics* d, const int64_t* idx, int64_t train_size,
   const long xs1 = (long)B * p0, xs0 = (long)K * xs1;
   for (long b = 0; b < nb; ++b) {
     const int rows = (int)std::min<long>(B, train_size - b * B);
-    DYN_LAUNCH(k_dyn_gather, dim3((rows + 255) / 256, K, R), dim3(256), 0, (const int*)d->idx_d, (long)K * train_size,
+    DEV_LAUNCH(d->stream, k_dyn_gather, dim3((rows + 255) / 256, K, R), dim3(256), 0, (const int*)d->idx_d, (long)K * train_size,
                 (long)train_size, b * B, rows, (const float*)d->data_in, (const float*)d->data_tg, d->in, D, (const float*)d->mu,
                 (const float*)d->sd, w.X, xs0, xs1, p0, d->T, (long)K * B * D, (long)B * D);
     if (dyn_forward(d, w, rows, true)) return -1;
     // Gaussian NLL head
     const long ne = (long)K * rows * D;
-    DYN_LAUNCH(k_dyn_nll, dim3((unsigned)((ne + 255) / 256), R), dim3(256), 0, (const float*)w.OUT, w.dOUT, po,
+    DEV_LAUNCH(d->stream, k_dyn_nll, dim3((unsigned)((ne + 255) / 256), R), dim3(256), 0, (const float*)w.OUT, w.dOUT, po,
                 (const float*)d->T, w.lterm, w.gmax, w.gmin, (const float*)d->params, d->P, d->off_max, d->off_min, K, B, rows, D);
-    DYN_LAUNCH(k_dyn_nll_reduce, dim3(R), dim3(1024), 0, (const float*)w.lterm, (const float*)w.gmax,
+    DEV_LAUNCH(d->stream, k_dyn_nll_reduce, dim3(R), dim3(1024), 0, (const float*)w.lterm, (const float*)w.gmax,
                 (const float*)w.gmin, K, B, rows, D, (const float*)d->params, d->grads, d->P, d->off_max, d->off_min,
                 d->c.logvar_loss_coef, d->nll);
     if (dyn_backward(d, w, rows)) return -1;
     a.batch = (int)b;
-    DYN_LAUNCH(k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, a);
-    DYN_LAUNCH(k_dyn_loss, dim3(R), dim3(256), 0, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
+    DEV_LAUNCH(d->stream, k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, a);
+    DEV_LAUNCH(d->stream, k_dyn_loss, dim3(R), dim3(256), 0, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
                 (const int*)d->active_d, d->loss_sum);
   }
   std::vector<float> ls(R);
-  DYN_HIP(hipMemcpyAsync(ls.data(), d->loss_sum, sizeof(float) * R, hipMemcpyDeviceToHost, d->stream));
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpyAsync(ls.data(), d->loss_sum, sizeof(float) * R, hipMemcpyDeviceToHost, d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
   for (int r = 0; r < R; ++r) {
     if (act[r]) d->tstep[r] += nb;
     if (loss_out) loss_out[r] = act[r] ? (float)((double)ls[r] / (double)nb) : 0.f;
@@ -1218,16 +1094,16 @@ int orl_dyn_validate(orl_dynamics* d, const int64_t* idx, int64_t H, float* mse_
   const int R = d->R, K = d->K, D = d->D;
   if (dyn_grow_step(d, H)) return -1;
   if (dyn_upload_idx(d, idx, (long)R * H)) return -1;
-  DYN_LAUNCH(k_dyn_gather, dim3((unsigned)((H + 255) / 256), 1, R), dim3(256), 0, (const int*)d->idx_d, (long)H, 0L, 0L,
+  DEV_LAUNCH(d->stream, k_dyn_gather, dim3((unsigned)((H + 255) / 256), 1, R), dim3(256), 0, (const int*)d->idx_d, (long)H, 0L, 0L,
               (int)H, (const float*)d->data_in, (const float*)d->data_tg, d->in, D, (const float*)d->mu, (const float*)d->sd, d->sw.X,
               (long)H * d->pitch[0], 0L, d->pitch[0], d->sT, (long)H * D, 0L);
   d->sw.rows = H;
   if (dyn_forward(d, d->sw, (int)H, false)) return -1;
   float* mse = d->sNoise;      // R * K floats of the noise staging (R * K * H * D)
-  DYN_LAUNCH(k_dyn_val_mse, dim3(K, R), dim3(256), 0, (const float*)d->sw.OUT, d->pitch[d->L + 1], (const float*)d->sT,
+  DEV_LAUNCH(d->stream, k_dyn_val_mse, dim3(K, R), dim3(256), 0, (const float*)d->sw.OUT, d->pitch[d->L + 1], (const float*)d->sT,
               (int)H, D, K, mse);
-  DYN_HIP(hipMemcpyAsync(mse_out, mse, sizeof(float) * R * K, hipMemcpyDeviceToHost, d->stream));
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpyAsync(mse_out, mse, sizeof(float) * R * K, hipMemcpyDeviceToHost, d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
   return 0;
 }
 
@@ -1238,8 +1114,8 @@ int orl_dyn_update_save(orl_dynamics* d, int run, const int32_t* mask) {
     const long nw = (long)d->width[l] * d->width[l + 1], nbias = d->width[l + 1];
     for (int k = 0; k < d->K; ++k) {
       if (!mask[k]) continue;
-      DYN_HIP(hipMemcpyAsync(base + d->sw_off[l] + k * nw, base + d->w_off[l] + k * nw, sizeof(float) * nw, hipMemcpyDeviceToDevice, d->stream));
-      DYN_HIP(hipMemcpyAsync(base + d->sb_off[l] + k * nbias, base + d->b_off[l] + k * nbias, sizeof(float) * nbias, hipMemcpyDeviceToDevice, d->stream));
+      ORL_HIP(hipMemcpyAsync(base + d->sw_off[l] + k * nw, base + d->w_off[l] + k * nw, sizeof(float) * nw, hipMemcpyDeviceToDevice, d->stream));
+      ORL_HIP(hipMemcpyAsync(base + d->sb_off[l] + k * nbias, base + d->b_off[l] + k * nbias, sizeof(float) * nbias, hipMemcpyDeviceToDevice, d->stream));
     }
   }
   return 0;
@@ -1250,15 +1126,15 @@ int orl_dyn_load_save(orl_dynamics* d, int run) {
   float* base = d->params + (long)run * d->P;
   for (int l = 0; l <= d->L; ++l) {
     const long nw = (long)d->K * d->width[l] * d->width[l + 1], nbias = (long)d->K * d->width[l + 1];
-    DYN_HIP(hipMemcpyAsync(base + d->w_off[l], base + d->sw_off[l], sizeof(float) * nw, hipMemcpyDeviceToDevice, d->stream));
-    DYN_HIP(hipMemcpyAsync(base + d->b_off[l], base + d->sb_off[l], sizeof(float) * nbias, hipMemcpyDeviceToDevice, d->stream));
+    ORL_HIP(hipMemcpyAsync(base + d->w_off[l], base + d->sw_off[l], sizeof(float) * nw, hipMemcpyDeviceToDevice, d->stream));
+    ORL_HIP(hipMemcpyAsync(base + d->b_off[l], base + d->sb_off[l], sizeof(float) * nbias, hipMemcpyDeviceToDevice, d->stream));
   }
   return 0;
 }
 
 // step() / sample_next(): scaler(concat(obs, act)) into the step workspace and the ensemble's forward over its n rows
 static int dyn_step_forward(orl_dynamics* d, const float* obs, const float* act, long n) {
-  DYN_LAUNCH(k_dyn_step_input, dim3((unsigned)((n + 255) / 256), d->R), dim3(256), 0, obs, act, n, d->od, d->ad,
+  DEV_LAUNCH(d->stream, k_dyn_step_input, dim3((unsigned)((n + 255) / 256), d->R), dim3(256), 0, obs, act, n, d->od, d->ad,
               (const float*)d->mu, (const float*)d->sd, d->sw.X, d->pitch[0]);
   d->sw.rows = n;
   return dyn_forward(d, d->sw, (int)n, false);
@@ -1271,8 +1147,8 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
   if (mode < 0 || mode > 2) return fail("orl_dyn_step: unknown penalty mode");
   const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
   if (dyn_grow_step(d, n)) return -1;
-  if (dyn_stage_in(d, obs, d->sObs, (size_t)R * n * od, on_device) || dyn_stage_in(d, act, d->sAct, (size_t)R * n * ad, on_device) ||
-      dyn_stage_in(d, noise, d->sNoise, (size_t)R * K * n * D, on_device))
+  if (stage_in(d->stream, obs, d->sObs, (size_t)R * n * od, on_device) || stage_in(d->stream, act, d->sAct, (size_t)R * n * ad, on_device) ||
+      stage_in(d->stream, noise, d->sNoise, (size_t)R * K * n * D, on_device))
     return -1;
   std::vector<int> mi;
   if (model_idx) {
@@ -1290,17 +1166,17 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
   if ((h.n_elites = dyn_n_elites(d, "orl_dyn_step")) < 0) return -1;
   h.seed = d->c.seed; h.call = d->step_calls++;
   h.mode = mode; h.coef = coef;
-  h.next_obs = dyn_dst(next_obs, d->sNext, on_device);
-  h.reward = dyn_dst(reward, d->sRew, on_device);
-  h.raw_reward = dyn_dst(raw_reward, d->sRaw, on_device);
-  h.penalty = dyn_dst(penalty, d->sPen, on_device);
-  h.midx_out = dyn_dst((int*)midx_out, d->sMidxOut, on_device);
-  DYN_LAUNCH(k_dyn_head, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, h);
-  if (dyn_stage_out(d, next_obs, d->sNext, (size_t)R * n * od, on_device) || dyn_stage_out(d, reward, d->sRew, (size_t)R * n, on_device) ||
-      dyn_stage_out(d, raw_reward, d->sRaw, (size_t)R * n, on_device) || dyn_stage_out(d, penalty, d->sPen, (size_t)R * n, on_device) ||
-      dyn_stage_out(d, (int*)midx_out, d->sMidxOut, (size_t)R * n, on_device))
+  h.next_obs = stage_dst(next_obs, d->sNext, on_device);
+  h.reward = stage_dst(reward, d->sRew, on_device);
+  h.raw_reward = stage_dst(raw_reward, d->sRaw, on_device);
+  h.penalty = stage_dst(penalty, d->sPen, on_device);
+  h.midx_out = stage_dst((int*)midx_out, d->sMidxOut, on_device);
+  DEV_LAUNCH(d->stream, k_dyn_head, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, h);
+  if (stage_out(d->stream, next_obs, d->sNext, (size_t)R * n * od, on_device) || stage_out(d->stream, reward, d->sRew, (size_t)R * n, on_device) ||
+      stage_out(d->stream, raw_reward, d->sRaw, (size_t)R * n, on_device) || stage_out(d->stream, penalty, d->sPen, (size_t)R * n, on_device) ||
+      stage_out(d->stream, (int*)midx_out, d->sMidxOut, (size_t)R * n, on_device))
     return -1;
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
   return 0;
 }
 
@@ -1317,14 +1193,14 @@ int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int6
   if (rows * ((D + 3) / 4) > (1L << 38) || n > 0x7fffffffL) return fail("orl_dynsample_next: too many rows");
   if (dyn_grow_step(d, n)) return -1;
   if (!on_device && rows > d->m_cap) {
-    DYN_HIP(hipStreamSynchronize(d->stream));
-    dyn_release(d, &d->mNoise, &d->mNext);
+    ORL_HIP(hipStreamSynchronize(d->stream));
+    d->mem.release(&d->mNoise, &d->mNext);
     d->m_cap = 0;
-    if (dyn_alloc_t(d, &d->mNoise, (size_t)R * rows * D) || dyn_alloc_t(d, &d->mNext, (size_t)R * rows * od)) return -1;
+    if (d->mem.alloc(&d->mNoise, (size_t)R * rows * D) || d->mem.alloc(&d->mNext, (size_t)R * rows * od)) return -1;
     d->m_cap = rows;
   }
-  if (dyn_stage_in(d, obs, d->sObs, (size_t)R * n * od, on_device) || dyn_stage_in(d, act, d->sAct, (size_t)R * n * ad, on_device) ||
-      dyn_stage_in(d, noise, d->mNoise, (size_t)R * rows * D, on_device))
+  if (stage_in(d->stream, obs, d->sObs, (size_t)R * n * od, on_device) || stage_in(d->stream, act, d->sAct, (size_t)R * n * ad, on_device) ||
+      stage_in(d->stream, noise, d->mNoise, (size_t)R * rows * D, on_device))
     return -1;
   if (dyn_step_forward(d, obs, act, n)) return -1;
   DynSampleNextP p;
@@ -1334,19 +1210,16 @@ int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int6
   p.params = d->params; p.P = d->P; p.off_max = d->off_max; p.off_min = d->off_min;
   p.noise = noise; p.elites = d->elites_d;
   p.seed = d->c.seed ^ 0xD1B54A32D192ED03ull; p.call = d->sample_calls++;
-  p.next_obs = dyn_dst(next_obs, d->mNext, on_device);
+  p.next_obs = stage_dst(next_obs, d->mNext, on_device);
   const long nt = rows * ((D + 3) / 4);
-  DYN_LAUNCH(k_dyn_sample_next, dim3((unsigned)((nt + 255) / 256), R), dim3(256), 0, p);
-  if (dyn_stage_out(d, next_obs, d->mNext, (size_t)R * rows * od, on_device)) return -1;
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  DEV_LAUNCH(d->stream, k_dyn_sample_next, dim3((unsigned)((nt + 255) / 256), R), dim3(256), 0, p);
+  if (stage_out(d->stream, next_obs, d->mNext, (size_t)R * rows * od, on_device)) return -1;
+  ORL_HIP(hipStreamSynchronize(d->stream));
   return 0;
 }
 
 int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n) {
-  if (dyn_check_run(d, run, n, "orl_dyn_debug_grads")) return -1;
-  DYN_HIP(hipStreamSynchronize(d->stream));
-  DYN_HIP(hipMemcpy(host, d->grads + (long)run * d->P, sizeof(float) * d->P, hipMemcpyDeviceToHost));
-  return 0;
+  return dyn_check_run(d, run, n, "orl_dyn_debug_grads") || block_to_host(d->stream, host, d->grads + (long)run * d->P, d->P) ? -1 : 0;
 }
 
 // ---- RAMBO's adversarial update ----
@@ -1355,27 +1228,27 @@ int orl_dynadv_configure(orl_dynamics* d, float lr, float beta1, float beta2, fl
   if (!d) return fail("orl_dynadv_configure: null handle");
   if (rollout_rows < 1 || sl_rows < 1) return fail("orl_dynadv_configure: need rollout_rows >= 1 and sl_rows >= 1");
   if (!d->c.with_reward) return fail("orl_dynadv_configure: needs with_reward (the sample's last dim is the reward)");
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
   const long R = d->R, K = d->K, D = d->D;
   d->adv_lr = lr; d->adv_b1 = beta1; d->adv_b2 = beta2; d->adv_eps = eps; d->adv_weight = adv_weight;
   if (!d->adv_m) {
-    if (dyn_alloc_t(d, &d->adv_m, R * d->P) || dyn_alloc_t(d, &d->adv_v, R * d->P)) return -1;
+    if (d->mem.alloc(&d->adv_m, R * d->P) || d->mem.alloc(&d->adv_v, R * d->P)) return -1;
     d->adv_tstep.assign(R, 0);
   }
   if (d->adv_on && d->aBa == rollout_rows && d->aBs == sl_rows) return 0;
   d->adv_pending = false;
   dyn_ws_release(d, d->aw);
-  dyn_release(d, &d->aT, &d->aS, &d->aObs, &d->aAdv, &d->aAdvm, &d->aMetrics, &d->aRowlp, &d->aInObs, &d->aInAct, &d->aSlObs, &d->aSlAct,
+  d->mem.release(&d->aT, &d->aS, &d->aObs, &d->aAdv, &d->aAdvm, &d->aMetrics, &d->aRowlp, &d->aInObs, &d->aInAct, &d->aSlObs, &d->aSlAct,
               &d->aSlNext, &d->aSlRew, &d->aNoise, &d->aNext, &d->aRew, &d->aMidx, &d->aMidxOut);
   d->adv_on = false;
   const long Ba = rollout_rows, Bs = sl_rows;
-  if (dyn_ws_alloc(d, d->aw, Ba + Bs, true) || dyn_alloc_t(d, &d->aT, R * Bs * D) || dyn_alloc_t(d, &d->aS, R * Ba * D) ||
-      dyn_alloc_t(d, &d->aObs, R * Ba * d->od) || dyn_alloc_t(d, &d->aAdv, R * Ba) || dyn_alloc_t(d, &d->aAdvm, R * 2) ||
-      dyn_alloc_t(d, &d->aMetrics, R * 4) || dyn_alloc_t(d, &d->aRowlp, R * Ba) || dyn_alloc_t(d, &d->aInObs, R * Ba * d->od) ||
-      dyn_alloc_t(d, &d->aInAct, R * Ba * d->ad) || dyn_alloc_t(d, &d->aSlObs, R * Bs * d->od) ||
-      dyn_alloc_t(d, &d->aSlAct, R * Bs * d->ad) || dyn_alloc_t(d, &d->aSlNext, R * Bs * d->od) ||
-      dyn_alloc_t(d, &d->aSlRew, R * Bs) || dyn_alloc_t(d, &d->aNoise, R * K * Ba * D) || dyn_alloc_t(d, &d->aNext, R * Ba * d->od) ||
-      dyn_alloc_t(d, &d->aRew, R * Ba) || dyn_alloc_t(d, &d->aMidx, R * Ba) || dyn_alloc_t(d, &d->aMidxOut, R * Ba))
+  if (dyn_ws_alloc(d, d->aw, Ba + Bs, true) || d->mem.alloc(&d->aT, R * Bs * D) || d->mem.alloc(&d->aS, R * Ba * D) ||
+      d->mem.alloc(&d->aObs, R * Ba * d->od) || d->mem.alloc(&d->aAdv, R * Ba) || d->mem.alloc(&d->aAdvm, R * 2) ||
+      d->mem.alloc(&d->aMetrics, R * 4) || d->mem.alloc(&d->aRowlp, R * Ba) || d->mem.alloc(&d->aInObs, R * Ba * d->od) ||
+      d->mem.alloc(&d->aInAct, R * Ba * d->ad) || d->mem.alloc(&d->aSlObs, R * Bs * d->od) ||
+      d->mem.alloc(&d->aSlAct, R * Bs * d->ad) || d->mem.alloc(&d->aSlNext, R * Bs * d->od) ||
+      d->mem.alloc(&d->aSlRew, R * Bs) || d->mem.alloc(&d->aNoise, R * K * Ba * D) || d->mem.alloc(&d->aNext, R * Ba * d->od) ||
+      d->mem.alloc(&d->aRew, R * Ba) || d->mem.alloc(&d->aMidx, R * Ba) || d->mem.alloc(&d->aMidxOut, R * Ba))
     return -1;
   d->aBa = rollout_rows; d->aBs = sl_rows;
   d->adv_on = true;
@@ -1392,15 +1265,15 @@ int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, cons
   const size_t Ba = d->aBa, Bs = d->aBs, N = Ba + Bs;
   const DynWs& w = d->aw;
   d->adv_pending = false;
-  if (dyn_stage_in(d, obs, d->aInObs, R * Ba * od, on_device) || dyn_stage_in(d, act, d->aInAct, R * Ba * ad, on_device) ||
-      dyn_stage_in(d, sl_obs, d->aSlObs, R * Bs * od, on_device) || dyn_stage_in(d, sl_act, d->aSlAct, R * Bs * ad, on_device) ||
-      dyn_stage_in(d, sl_next_obs, d->aSlNext, R * Bs * od, on_device) || dyn_stage_in(d, sl_rew, d->aSlRew, R * Bs, on_device) ||
-      dyn_stage_in(d, noise, d->aNoise, R * K * Ba * D, on_device))
+  if (stage_in(d->stream, obs, d->aInObs, R * Ba * od, on_device) || stage_in(d->stream, act, d->aInAct, R * Ba * ad, on_device) ||
+      stage_in(d->stream, sl_obs, d->aSlObs, R * Bs * od, on_device) || stage_in(d->stream, sl_act, d->aSlAct, R * Bs * ad, on_device) ||
+      stage_in(d->stream, sl_next_obs, d->aSlNext, R * Bs * od, on_device) || stage_in(d->stream, sl_rew, d->aSlRew, R * Bs, on_device) ||
+      stage_in(d->stream, noise, d->aNoise, R * K * Ba * D, on_device))
     return -1;
   std::vector<int> mi;
   if (model_idx && dyn_upload_midx(d, model_idx, (long)(R * Ba), mi, d->aMidx, "orl_dynadv_forward")) return -1;
   const int p0 = d->pitch[0], po = d->pitch[d->L + 1];
-  DYN_LAUNCH(k_dyn_adv_input, dim3((unsigned)((N + 255) / 256), R), dim3(256), 0, obs, act, sl_obs, sl_act, sl_next_obs,
+  DEV_LAUNCH(d->stream, k_dyn_adv_input, dim3((unsigned)((N + 255) / 256), R), dim3(256), 0, obs, act, sl_obs, sl_act, sl_next_obs,
               sl_rew, (int)Ba, (int)Bs, od, ad, (const float*)d->mu, (const float*)d->sd, w.X, p0, d->aT, D, d->aObs);
   if (dyn_forward(d, w, (int)N, true)) return -1;
   DynAdvSampleP s;
@@ -1412,16 +1285,16 @@ int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, cons
   s.elites = d->elites_d;
   if ((s.n_elites = dyn_n_elites(d, "orl_dynadv_forward")) < 0) return -1;
   s.seed = d->c.seed ^ 0x9E3779B97F4A7C15ull; s.call = d->adv_calls++;
-  s.next_obs = dyn_dst(next_obs, d->aNext, on_device);
-  s.reward = dyn_dst(reward, d->aRew, on_device);
+  s.next_obs = stage_dst(next_obs, d->aNext, on_device);
+  s.reward = stage_dst(reward, d->aRew, on_device);
   s.S = d->aS;
-  s.midx_out = dyn_dst((int*)midx_out, d->aMidxOut, on_device);
+  s.midx_out = stage_dst((int*)midx_out, d->aMidxOut, on_device);
   const long ns = Ba * ((D + 3) / 4);
-  DYN_LAUNCH(k_dyn_adv_sample, dim3((unsigned)((ns + 255) / 256), R), dim3(256), 0, s);
-  if (dyn_stage_out(d, next_obs, d->aNext, R * Ba * od, on_device) || dyn_stage_out(d, reward, d->aRew, R * Ba, on_device) ||
-      dyn_stage_out(d, (int*)midx_out, d->aMidxOut, R * Ba, on_device))
+  DEV_LAUNCH(d->stream, k_dyn_adv_sample, dim3((unsigned)((ns + 255) / 256), R), dim3(256), 0, s);
+  if (stage_out(d->stream, next_obs, d->aNext, R * Ba * od, on_device) || stage_out(d->stream, reward, d->aRew, R * Ba, on_device) ||
+      stage_out(d->stream, (int*)midx_out, d->aMidxOut, R * Ba, on_device))
     return -1;
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
   d->adv_pending = true;
   return 0;
 }
@@ -1435,7 +1308,7 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
   d->adv_pending = false;
   std::vector<int> act;
   if (dyn_upload_run_state(d, active, d->adv_tstep, act, true)) return -1;
-  if (dyn_stage_in(d, advantage, d->aAdv, (size_t)R * Ba, on_device)) return -1;
+  if (stage_in(d->stream, advantage, d->aAdv, (size_t)R * Ba, on_device)) return -1;
   DynAdvHeadP h;
   memset(&h, 0, sizeof(h));
   h.OUT = w.OUT; h.dOUT = w.dOUT; h.op = d->pitch[d->L + 1];
@@ -1449,8 +1322,8 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
   const size_t per_wave = sizeof(double) * ((size_t)K * D + 64);
   h.wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (32 * 1024) / per_wave));
   if (per_wave > 48 * 1024) return fail("orl_dynadv_update: num_ensemble * (obs_dim + 1) is too large for the head's LDS");
-  DYN_LAUNCH(k_dyn_adv_head, dim3((unsigned)((N + h.wpb - 1) / h.wpb), R), dim3(64 * h.wpb), per_wave * h.wpb, h);
-  DYN_LAUNCH(k_dyn_adv_reduce, dim3(R), dim3(1024), 0, (const float*)w.lterm, (const float*)w.gmax,
+  DEV_LAUNCH(d->stream, k_dyn_adv_head, dim3((unsigned)((N + h.wpb - 1) / h.wpb), R), dim3(64 * h.wpb), per_wave * h.wpb, h);
+  DEV_LAUNCH(d->stream, k_dyn_adv_reduce, dim3(R), dim3(1024), 0, (const float*)w.lterm, (const float*)w.gmax,
               (const float*)w.gmin, (const double*)d->aRowlp, advantage, K, (int)Ba, (int)Bs, D, (const float*)d->params, d->grads,
               d->P, d->off_max, d->off_min, 0.001f, d->nll, d->aAdvm);
   if (dyn_backward(d, w, (int)N)) return -1;      // ONE backward over the Ba + Bs rows
@@ -1458,12 +1331,12 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
   a.m = d->adv_m; a.v = d->adv_v;
   a.lr = d->adv_lr; a.b1 = d->adv_b1; a.b2 = d->adv_b2; a.eps = d->adv_eps;
   a.batch = 0;
-  DYN_LAUNCH(k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, a);
-  DYN_LAUNCH(k_dyn_adv_metrics, dim3(R), dim3(256), 0, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
+  DEV_LAUNCH(d->stream, k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, a);
+  DEV_LAUNCH(d->stream, k_dyn_adv_metrics, dim3(R), dim3(256), 0, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
               (const int*)d->active_d, (const float*)d->aAdvm, d->adv_weight, d->aMetrics);
   std::vector<float> ms((size_t)R * 4);
-  DYN_HIP(hipMemcpyAsync(ms.data(), d->aMetrics, sizeof(float) * ms.size(), hipMemcpyDeviceToHost, d->stream));
-  DYN_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpyAsync(ms.data(), d->aMetrics, sizeof(float) * ms.size(), hipMemcpyDeviceToHost, d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
   for (int r = 0; r < R; ++r)
     if (act[r]) d->adv_tstep[r] += 1;
   if (metrics_out) memcpy(metrics_out, ms.data(), sizeof(float) * ms.size());

@@ -7,32 +7,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/orl_engine.h"
-#include "gemm.h"
+#include "devobj.h"
 #include "kernels.h"
 #include "ws_gemm.h"
 #include "small_fwd.h"
 #include "small_bwd.h"
 
 namespace orl {
-
-void set_error(const std::string& msg);
-int fail(const std::string& msg);
-#define ORL_HIP(expr)                                                                            \
-  do {                                                                                           \
-    hipError_t _e = (expr);                                                                      \
-    if (_e != hipSuccess) {                                                                      \
-      ::orl::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                       \
-      return -1;                                                                                 \
-    }                                                                                            \
-  } while (0)
-
-struct TensorInfo {
-  std::string name;
-  long off;
-  int ndim;
-  long shape[4];
-};
 
 // A network (family) = MLP of L ReLU layers + one linear tail (critic last / actor head).
 // `members` identical nets are batched through blockIdx.z.  Two storage layouts:
@@ -52,7 +33,7 @@ struct NetLayout {
   long extra_off = -1;                   // IQL sigma_param; RCSL_GAUSS: the four DiagGaussian head tensors
   long size = 0;                         // floats of ONE net (ens: of the whole ensemble)
   long stride() const { return (size + 3) & ~3L; }   // arena stride: keeps every net 16-B aligned
-  std::vector<TensorInfo> tensors;
+  TensorTable tensors;
   int layer_in(int l) const { return l == 0 ? in_dim : H[l - 1]; }
   int layer_out(int l) const { return l == L ? out_dim : H[l]; }
 };

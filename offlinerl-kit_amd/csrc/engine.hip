@@ -25,15 +25,7 @@ static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 // ---------------------------------------------------------------------------------------------
 // layouts (reference state_dict key names: SURVEY Appendix B)
 // ---------------------------------------------------------------------------------------------
-static void add_tensor(NetLayout& l, const std::string& name, long off, std::initializer_list<long> shape) {
-  TensorInfo t;
-  t.name = name;
-  t.off = off;
-  t.ndim = (int)shape.size();
-  int i = 0;
-  for (long s : shape) t.shape[i++] = s;
-  l.tensors.push_back(t);
-}
+static void add_tensor(NetLayout& l, const std::string& name, long off, std::initializer_list<long> shape) { l.tensors.put(name, off, shape); }
 
 enum TailKind { TAIL_CRITIC, TAIL_TANH_GAUSS, TAIL_GAUSS, TAIL_DET, TAIL_LINEAR, TAIL_LINEAR_GAUSS };
 
@@ -1558,11 +1550,7 @@ int64_t orl_net_floats(orl_engine* h, int net) { return orl_net_present(h, net) 
 int orl_net_num_tensors(orl_engine* h, int net) { return orl_net_present(h, net) ? (int)h->e.lay[net].tensors.size() : -1; }
 int orl_net_tensor(orl_engine* h, int net, int idx, char* name, int name_cap, int64_t* offset, int32_t* ndim, int64_t shape[4]) {
   if (!orl_net_present(h, net)) return fail("net not present");
-  const auto& ts = h->e.lay[net].tensors;
-  if (idx < 0 || idx >= (int)ts.size()) return fail("tensor index out of range");
-  snprintf(name, name_cap, "%s", ts[idx].name.c_str());
-  *offset = ts[idx].off; *ndim = ts[idx].ndim;
-  for (int i = 0; i < 4; ++i) shape[i] = i < ts[idx].ndim ? ts[idx].shape[i] : 1;
+  if (h->e.lay[net].tensors.query(idx, name, name_cap, offset, ndim, shape)) return fail("tensor index out of range");
   return 0;
 }
 float* orl_net_ptr(orl_engine* h, int run, int net) {

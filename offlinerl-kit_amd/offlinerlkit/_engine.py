@@ -363,17 +363,31 @@ def default_config(algo: str, **over) -> OrlConfig:
     return cfg
 
 
-def apply_config(cfg: OrlConfig, over: Dict) -> None:
-    names = {f[0] for f in OrlConfig._fields_}
+def _fill(count_field: Optional[str], array_field: str, cast):
+    """handler of a list-valued config field: the list into ``array_field``, its length into ``count_field``"""
+    def put(cfg, v):
+        if count_field:
+            setattr(cfg, count_field, len(v))
+        for i, x in enumerate(v):
+            getattr(cfg, array_field)[i] = cast(x)
+    return put
+
+
+def _override(cfg, over: Dict, what: str, lists: Dict):
+    """``over`` into the config structure; ``lists``: field -> handler(cfg, value) of the list-valued fields"""
+    names = {f[0] for f in type(cfg)._fields_}
     for k, v in over.items():
-        if k == "hidden":
-            cfg.n_hidden = len(v)
-            for i, h in enumerate(v):
-                cfg.hidden[i] = int(h)
+        if k in lists:
+            lists[k](cfg, v)
         elif k in names:
             setattr(cfg, k, v)
         else:
-            raise KeyError(f"unknown engine config field {k!r}")
+            raise KeyError(f"unknown {what} config field {k!r}")
+    return cfg
+
+
+def apply_config(cfg: OrlConfig, over: Dict) -> None:
+    _override(cfg, over, "engine", {"hidden": _fill("n_hidden", "hidden", int)})
 
 
 def _f32(a) -> np.ndarray:
@@ -384,23 +398,45 @@ def _is_tensor(a) -> bool:
     return type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
 
 
-class Engine:
-    """Thin RAII wrapper over ``orl_engine*``."""
+def _read_tensors(num_fn, tensor_fn, *prefix_args, what: str):
+    """[(state_dict name, offset, shape)] of a parameter block from its ``*_num_tensors`` / ``*_tensor`` pair"""
+    out = []
+    for i in range(num_fn(*prefix_args)):
+        name = C.create_string_buffer(160)
+        off, ndim, shape = C.c_int64(), C.c_int32(), (C.c_int64 * 4)()
+        _check(tensor_fn(*prefix_args, i, name, 160, C.byref(off), C.byref(ndim), shape), what)
+        out.append((name.value.decode(), int(off.value), tuple(int(shape[k]) for k in range(ndim.value))))
+    return out
 
-    def __init__(self, cfg: OrlConfig):
+
+def _flatten(tensors, params: Dict, floats: int) -> np.ndarray:
+    """a tensor dict -> the flat float32 block laid out by ``tensors`` (a sub-list of the table leaves the other tensors zero)"""
+    flat = np.zeros(floats, dtype=np.float32)
+    for name, off, shape in tensors:
+        if name not in params:
+            raise KeyError(f"missing parameter {name}")
+        a = _f32(params[name])
+        if a.size != int(np.prod(shape)):
+            raise ValueError(f"{name}: expected shape {shape}, got {a.shape}")
+        flat[off:off + a.size] = a.ravel()
+    return flat
+
+
+def _unflatten(tensors, flat) -> Dict[str, np.ndarray]:
+    return {name: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in tensors}
+
+
+class _Handle:
+    """owner of one C handle: ``lib``, ``_h``, and close() / __del__ through the destroy function named by ``_destroy``"""
+    _destroy = ""
+
+    def __init__(self):
         self.lib = load_library()
-        self.cfg = cfg
         self._h = C.c_void_p()
-        _check(self.lib.orl_engine_create(C.byref(cfg), C.byref(self._h)), "orl_engine_create")
-        self.n_runs = cfg.n_runs
-        self.metric_names = [self.lib.orl_metric_name(self._h, i).decode() for i in range(self.lib.orl_num_metrics(self._h))]
-        # a step that ran but raised a health flag: warn once per new flag (EngineHealthWarning), or raise when strict
-        self.strict_health = os.environ.get("ORL_STRICT_HEALTH", "0") == "1"
-        self._health_seen = 0
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            self.lib.orl_engine_destroy(self._h)
+            getattr(self.lib, self._destroy)(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -409,18 +445,27 @@ class Engine:
         except Exception:
             pass
 
+
+class Engine(_Handle):
+    """Thin RAII wrapper over ``orl_engine*``."""
+    _destroy = "orl_engine_destroy"
+
+    def __init__(self, cfg: OrlConfig):
+        super().__init__()
+        self.cfg = cfg
+        _check(self.lib.orl_engine_create(C.byref(cfg), C.byref(self._h)), "orl_engine_create")
+        self.n_runs = cfg.n_runs
+        self.metric_names = [self.lib.orl_metric_name(self._h, i).decode() for i in range(self.lib.orl_num_metrics(self._h))]
+        # a step that ran but raised a health flag: warn once per new flag (EngineHealthWarning), or raise when strict
+        self.strict_health = os.environ.get("ORL_STRICT_HEALTH", "0") == "1"
+        self._health_seen = 0
+
     # ---- parameters ----
     def net_present(self, net: int) -> bool:
         return bool(self.lib.orl_net_present(self._h, net))
 
     def net_tensors(self, net: int):
-        out = []
-        for i in range(self.lib.orl_net_num_tensors(self._h, net)):
-            name = C.create_string_buffer(128)
-            off, ndim, shape = C.c_int64(), C.c_int32(), (C.c_int64 * 4)()
-            _check(self.lib.orl_net_tensor(self._h, net, i, name, 128, C.byref(off), C.byref(ndim), shape), "orl_net_tensor")
-            out.append((name.value.decode(), off.value, tuple(shape[k] for k in range(ndim.value))))
-        return out
+        return _read_tensors(self.lib.orl_net_num_tensors, self.lib.orl_net_tensor, self._h, net, what="orl_net_tensor")
 
     def net_floats(self, net: int) -> int:
         return self.lib.orl_net_floats(self._h, net)
@@ -429,22 +474,13 @@ class Engine:
         return self.lib.orl_net_ptr(self._h, run, net)
 
     def set_net(self, run: int, net: int, params: Dict[str, np.ndarray]):
-        flat = np.zeros(self.net_floats(net), dtype=np.float32)
-        seen = set()
-        for name, off, shape in self.net_tensors(net):
-            if name not in params:
-                raise KeyError(f"missing parameter {name}")
-            a = _f32(params[name])
-            if a.size != int(np.prod(shape)):
-                raise ValueError(f"{name}: expected shape {shape}, got {a.shape}")
-            flat[off:off + a.size] = a.ravel()
-            seen.add(name)
+        flat = _flatten(self.net_tensors(net), params, self.net_floats(net))
         _check(self.lib.orl_net_set(self._h, run, net, flat.ctypes.data, flat.size), "orl_net_set")
 
     def get_net(self, run: int, net: int) -> Dict[str, np.ndarray]:
         flat = np.empty(self.net_floats(net), dtype=np.float32)
         _check(self.lib.orl_net_get(self._h, run, net, flat.ctypes.data, flat.size), "orl_net_get")
-        return {name: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in self.net_tensors(net)}
+        return _unflatten(self.net_tensors(net), flat)
 
     def set_scalar(self, run: int, which: int, v: float):
         _check(self.lib.orl_scalar_set(self._h, run, which, float(v)), "orl_scalar_set")
@@ -668,7 +704,7 @@ class Engine:
         """Gradients of the last step for every tensor of ``net`` (reference: ``param.grad`` before ``optimizer.step()``)."""
         flat = np.empty(self.net_floats(net), dtype=np.float32)
         _check(self.lib.orl_debug_grads(self._h, run, net, flat.ctypes.data, flat.size), "orl_debug_grads")
-        return {name: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in self.net_tensors(net)}
+        return _unflatten(self.net_tensors(net), flat)
 
     def profile_enable(self, on: bool):
         self.lib.orl_profile_enable(self._h, 1 if on else 0)
@@ -688,25 +724,14 @@ class Engine:
         return rows
 
 
-class DeviceBuffer:
+class DeviceBuffer(_Handle):
     """RAII wrapper over ``orl_buffer*``: the HBM-resident SoA replay store (buffer/buffer.py)."""
+    _destroy = "orl_buffer_destroy"
 
     def __init__(self, obs_dim: int, act_dim: int, device: int = 0):
-        self.lib = load_library()
+        super().__init__()
         self.obs_dim, self.act_dim, self.device = obs_dim, act_dim, device
-        self._h = C.c_void_p()
         _check(self.lib.orl_buffer_create(obs_dim, act_dim, device, C.byref(self._h)), "orl_buffer_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.orl_buffer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def load(self, obs, act, next_obs, rew, term):
         obs, act, next_obs = _f32(obs), _f32(act), _f32(next_obs)
@@ -829,28 +854,17 @@ class DeviceBuffer:
         _check(self.lib.orl_buffer_sample(self._h, p, batch, seed, obs_ptr, act_ptr, nobs_ptr, rew_ptr, term_ptr), "orl_buffer_sample")
 
 
-class TrajStore:
+class TrajStore(_Handle):
     """RAII wrapper over ``orl_traj*``: the HBM-resident trajectory store of the RCSL rollout (rows with their trajectory index,
     accumulated return and return-to-go; per-trajectory returns; the live trajectories)."""
+    _destroy = "orl_traj_destroy"
 
     def __init__(self, obs_dim: int, act_dim: int, n_traj: int, capacity_rows: int, device: int = 0):
-        self.lib = load_library()
+        super().__init__()
         self.obs_dim, self.act_dim, self.device = int(obs_dim), int(act_dim), int(device)
         self.max_traj, self.capacity_rows, self.n_traj = int(n_traj), int(capacity_rows), int(n_traj)
-        self._h = C.c_void_p()
         _check(self.lib.orl_traj_create(self.obs_dim, self.act_dim, self.device, self.max_traj, self.capacity_rows, C.byref(self._h)),
                "orl_traj_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.orl_traj_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, n_traj: int):
         _check(self.lib.orl_traj_reset(self._h, int(n_traj)), "orl_traj_reset")
@@ -1041,51 +1055,22 @@ def default_dyn_config(**over) -> OrlDynConfig:
     """orl_dyn_config_default (run_mopo.py's dynamics defaults) with overrides; ``hidden`` / ``weight_decay`` take lists"""
     cfg = OrlDynConfig()
     load_library().orl_dyn_config_default(C.byref(cfg))
-    names = {f[0] for f in OrlDynConfig._fields_}
-    for k, v in over.items():
-        if k == "hidden":
-            cfg.n_hidden = len(v)
-            for i, h in enumerate(v):
-                cfg.hidden[i] = int(h)
-        elif k == "weight_decay":
-            for i, w in enumerate(v):
-                cfg.weight_decay[i] = float(w)
-        elif k in names:
-            setattr(cfg, k, v)
-        else:
-            raise KeyError(f"unknown dynamics config field {k!r}")
-    return cfg
+    return _override(cfg, over, "dynamics", {"hidden": _fill("n_hidden", "hidden", int), "weight_decay": _fill(None, "weight_decay", float)})
 
 
-class Dynamics:
+class Dynamics(_Handle):
     """RAII wrapper over ``orl_dynamics*``: the dynamics ensemble's parameters, Adam state, HBM dataset and kernels."""
+    _destroy = "orl_dyn_destroy"
 
     def __init__(self, cfg: OrlDynConfig):
-        self.lib = load_library()
+        super().__init__()
         self.cfg = cfg
-        self._h = C.c_void_p()
         _check(self.lib.orl_dyn_create(C.byref(cfg), C.byref(self._h)), "orl_dyn_create")
         self.n_runs, self.K = cfg.n_runs, cfg.num_ensemble
         self.od, self.ad = cfg.obs_dim, cfg.act_dim
         self.D = cfg.obs_dim + (1 if cfg.with_reward else 0)
         self.P = int(self.lib.orl_dyn_floats(self._h))
-        self.tensors = []
-        for i in range(self.lib.orl_dyn_num_tensors(self._h)):
-            name = C.create_string_buffer(128)
-            off, ndim, shape = C.c_int64(), C.c_int32(), (C.c_int64 * 4)()
-            _check(self.lib.orl_dyn_tensor(self._h, i, name, 128, C.byref(off), C.byref(ndim), shape), "orl_dyn_tensor")
-            self.tensors.append((name.value.decode(), off.value, tuple(shape[k] for k in range(ndim.value))))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.orl_dyn_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.tensors = _read_tensors(self.lib.orl_dyn_num_tensors, self.lib.orl_dyn_tensor, self._h, what="orl_dyn_tensor")
 
     def sync(self):
         _check(self.lib.orl_dyn_sync(self._h), "orl_dyn_sync")
@@ -1094,16 +1079,16 @@ class Dynamics:
         return self.lib.orl_dyn_ptr(self._h, run)
 
     def set_params(self, run: int, params: Dict[str, np.ndarray]):
-        flat = np.zeros(self.P, dtype=np.float32)
-        for name, off, shape in self.tensors:
-            a = _f32(params[name])
-            if a.size != int(np.prod(shape)):
-                raise ValueError(f"{name}: expected shape {shape}, got {a.shape}")
-            flat[off:off + a.size] = a.ravel()
+        flat = _flatten(self.tensors, params, self.P)
         _check(self.lib.orl_dyn_set(self._h, run, flat.ctypes.data, self.P), "orl_dyn_set")
 
     def _unflat(self, flat) -> Dict[str, np.ndarray]:
-        return {name: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in self.tensors}
+        return _unflatten(self.tensors, flat)
+
+    def _flat_moments(self, m: Dict, v: Dict):
+        """the two Adam blocks from tensor dicts; a tensor absent from ``m`` stays zero in both"""
+        held = [t for t in self.tensors if t[0] in m]
+        return _flatten(held, m, self.P), _flatten(held, v, self.P)
 
     def get_params(self, run: int) -> Dict[str, np.ndarray]:
         flat = np.empty(self.P, dtype=np.float32)
@@ -1117,11 +1102,7 @@ class Dynamics:
         return self._unflat(m), self._unflat(v), t.value
 
     def set_adam_state(self, run: int, m: Dict, v: Dict, step: int):
-        fm, fv = np.zeros(self.P, np.float32), np.zeros(self.P, np.float32)
-        for name, off, shape in self.tensors:
-            if name in m:
-                fm[off:off + int(np.prod(shape))] = _f32(m[name]).ravel()
-                fv[off:off + int(np.prod(shape))] = _f32(v[name]).ravel()
+        fm, fv = self._flat_moments(m, v)
         _check(self.lib.orl_dyn_adam_set(self._h, run, fm.ctypes.data, fv.ctypes.data, self.P, int(step)), "orl_dyn_adam_set")
 
     def debug_grads(self, run: int) -> Dict[str, np.ndarray]:
@@ -1322,66 +1303,36 @@ class Dynamics:
         return self._unflat(m), self._unflat(v), t.value
 
     def set_adv_adam_state(self, run: int, m: Dict, v: Dict, step: int):
-        fm, fv = np.zeros(self.P, np.float32), np.zeros(self.P, np.float32)
-        for name, off, shape in self.tensors:
-            if name in m:
-                fm[off:off + int(np.prod(shape))] = _f32(m[name]).ravel()
-                fv[off:off + int(np.prod(shape))] = _f32(v[name]).ravel()
+        fm, fv = self._flat_moments(m, v)
         _check(self.lib.orl_dynadv_adam_set(self._h, run, fm.ctypes.data, fv.ctypes.data, self.P, int(step)), "orl_dynadv_adam_set")
 
 
 def default_diffusion_config(**over) -> OrlDiffusionConfig:
-    lib = load_library()
+    def down_dims(cfg, v):
+        if len(v) > DIFF_MAX_LEVELS:
+            raise NotImplementedError(f"the HIP engine supports up to {DIFF_MAX_LEVELS} U-Net levels, down_dims has {len(v)}")
+        _fill("n_levels", "down_dims", int)(cfg, v)
     cfg = OrlDiffusionConfig()
-    lib.orl_diffusion_config_default(C.byref(cfg))
-    names = {f[0] for f in OrlDiffusionConfig._fields_}
-    for k, v in over.items():
-        if k == "down_dims":
-            if len(v) > DIFF_MAX_LEVELS:
-                raise NotImplementedError(f"the HIP engine supports up to {DIFF_MAX_LEVELS} U-Net levels, down_dims has {len(v)}")
-            cfg.n_levels = len(v)
-            for i, h in enumerate(v):
-                cfg.down_dims[i] = int(h)
-        elif k in names:
-            setattr(cfg, k, v)
-        else:
-            raise KeyError(f"unknown diffusion config field {k!r}")
-    return cfg
+    load_library().orl_diffusion_config_default(C.byref(cfg))
+    return _override(cfg, over, "diffusion", {"down_dims": down_dims})
 
 
-class Diffusion:
+class Diffusion(_Handle):
     """RAII wrapper over ``orl_diffusion*``: DiffusionBC's noise-prediction net at sequence length 1, its training step and its
     sampler on the device.  Parameter blocks travel as flat float32 arrays laid out by ``tensors()``."""
     PARAMS, EMA, EXP_AVG, EXP_AVG_SQ = 0, 1, 2, 3
+    _destroy = "orl_diffusion_destroy"
 
     def __init__(self, cfg: OrlDiffusionConfig):
-        self.lib = load_library()
+        super().__init__()
         self.cfg = cfg
-        self._h = C.c_void_p()
         _check(self.lib.orl_diffusion_create(C.byref(cfg), C.byref(self._h)), "orl_diffusion_create")
         self.floats = int(self.lib.orl_diffusion_floats(self._h))
         self._buffer = None
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.orl_diffusion_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def tensors(self):
         """[(state_dict name, offset, shape)]; a conv weight appears as its centre tap [out, in]"""
-        out = []
-        for i in range(self.lib.orl_diffusion_num_tensors(self._h)):
-            name = C.create_string_buffer(160)
-            off, nd, shape = C.c_int64(), C.c_int32(), (C.c_int64 * 4)()
-            _check(self.lib.orl_diffusion_tensor(self._h, i, name, 160, C.byref(off), C.byref(nd), shape), "orl_diffusion_tensor")
-            out.append((name.value.decode(), int(off.value), tuple(int(shape[j]) for j in range(nd.value))))
-        return out
+        return _read_tensors(self.lib.orl_diffusion_num_tensors, self.lib.orl_diffusion_tensor, self._h, what="orl_diffusion_tensor")
 
     def set(self, which: int, flat):
         flat = _f32(flat).ravel()

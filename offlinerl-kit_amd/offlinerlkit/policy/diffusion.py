@@ -147,20 +147,15 @@ class DiffusionBC:
 
     def pack(self, state_dict) -> np.ndarray:
         """a reference-shaped state_dict -> the engine's flat block (conv weights: the centre tap)"""
-        flat = np.zeros(self._eng.floats, np.float32)
-        for name, off, shape in self._table:
-            t = state_dict[name].detach().cpu().numpy()
-            if t.ndim == 3:
-                t = t[:, :, t.shape[2] // 2]
-            flat[off:off + t.size] = t.reshape(-1)
-        return flat
+        taps = {name: state_dict[name].detach().cpu().numpy() for name, _, _ in self._table}
+        return _engine._flatten(self._table, {k: t[:, :, t.shape[2] // 2] if t.ndim == 3 else t for k, t in taps.items()}, self._eng.floats)
 
     def unpack(self, flat: np.ndarray, net: torch.nn.Module) -> None:
         """the engine's flat block into ``net``'s parameters; the off-centre taps of ``net`` stay as they are"""
         sd = net.state_dict()
         with torch.no_grad():
-            for name, off, shape in self._table:
-                t = torch.from_numpy(flat[off:off + int(np.prod(shape))].reshape(shape).copy())
+            for name, a in _engine._unflatten(self._table, flat).items():
+                t = torch.from_numpy(a)
                 if sd[name].dim() == 3:
                     sd[name][:, :, sd[name].shape[2] // 2] = t
                 else:
