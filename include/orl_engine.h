@@ -503,6 +503,57 @@ typedef struct orl_ws_ex {
 int orl_debug_ws(orl_ws_ex* args);
 /* name of instantiation `idx` of the tap's table ("ws_fwd<TQ,L0,DG,SY,F32,XS>", "ws_wgrad32<MODE>", ...); NULL past its end */
 const char* orl_debug_ws_flavour(int idx);
+/* The unit-test tap of the few-rows kernels (csrc/small_fwd.h, csrc/small_bwd.h): ONE launch of launch_small_fwd (ORL_SMALL_FWD) or
+ * launch_small_abwd (ORL_SMALL_ABWD) on host arrays.  Arrays are described as in orl_debug_gemm_ex, copied to the device WHOLE and ALL
+ * copied back WHOLE (operands too).  An array named like a field of SmallFwdP / SmallABwdP IS that field; given or not picks the mode
+ * (G: QG mode; H0 / H1 null: not stored; job[i].eps / .logp null: deterministic / no log-probability).  `pitch` is the field's pitch
+ * (x_pitch, o_pitch, g_pitch, dst_pitch, xa_pitch, ga_pitch), s0 / s1 the run / member strides (qa, ga: s1 = the critic stride; a job's
+ * arrays: s0 = eps_rs / dst_rs / logp_rs), out.ks = o_ks.  small_abwd: nz0 = runs, nz1 = 1; sc is a float array [runs][16] in RunScalars'
+ * layout (csrc/scalars.h), hy 8 floats (Hyper), gstep two 32-bit words = one 64-bit value at an even offset, part [runs][64][2], ticket
+ * [runs] (zero on entry); sc, metrics_*, part and ticket are dense per run.  Before the first HIP call the tap checks every extent against
+ * the array sizes (job.dst / eps / logp and the six slab offsets against o_ks included), refuses what small_fwd_supported /
+ * small_abwd_supported refuse, a null OUT, o_pitch < out_dim, M > 2048 and nz0 * nz1 > 16, and fills the report. */
+enum { ORL_SMALL_FWD = 0, ORL_SMALL_ABWD = 1 };
+typedef struct orl_small_job {
+  int32_t head_row0, rows, rep;   /* SampleJob: output row j draws from head row head_row0 + j / rep */
+  int32_t dst_row0, dst_col;
+  orl_gemm_buf eps;               /* [runs][rows][A]; null: deterministic */
+  orl_gemm_buf dst;               /* action a of row j at off + z0 s0 + (dst_row0 + j) pitch + dst_col + a */
+  orl_gemm_buf logp;              /* [runs][rows]; null: not written */
+} orl_small_job;
+typedef struct orl_small_ex {
+  int32_t kind;          /* ORL_SMALL_* */
+  int32_t f32;           /* exact fp32 MFMA instead of the split 16-bit planes */
+  int32_t M, nz0, nz1;
+  int32_t in0;           /* input columns of the first layer (1..31) */
+  int32_t out_dim;       /* fwd: tail outputs (1..16) */
+  int32_t gc0, gn;       /* fwd, QG: differentiated input columns gc0 .. gc0 + gn */
+  int32_t njobs, A;      /* fwd: sampling jobs (out_dim = 2 A); abwd: action dimensions */
+  int32_t K;             /* abwd: critics (2) */
+  int32_t xa_col;        /* abwd: first action column inside xa's rows */
+  int32_t auto_alpha, clamp_alpha01;
+  int32_t nm, m_actor, m_alpha_loss, m_alpha;    /* abwd: metrics per run and the three slots */
+  int32_t dry_run;       /* check the arguments and fill the report only: no device call */
+  float fixed_alpha, target_entropy, adam_b1, adam_b2, adam_eps;
+  int64_t off_w0, off_b0, off_w1, off_b1, off_wh, off_bh;   /* abwd: the six tensors inside a slab */
+  /* both launchers */
+  orl_gemm_buf X, W0, b0, W1, b1, Wt, bt;   /* abwd takes X and W1 only */
+  orl_gemm_buf H0, H1;                      /* fwd: results (null: not stored); abwd: operands */
+  orl_gemm_buf OUT, G;                      /* fwd results */
+  orl_small_job job[3];
+  /* abwd */
+  orl_gemm_buf head, eps, xa, logp, qa, ga, Wh;
+  orl_gemm_buf out;                         /* slab g of run z0 at off + z0 s0 + g ks */
+  orl_gemm_buf sc, hy, gstep, metrics_last, metrics_sum, part, ticket;
+  /* report (filled before the device is touched) */
+  int32_t r_kind;             /* = kind */
+  int32_t r_flavour;          /* index into the tap's table of instantiations (orl_debug_small_flavour) */
+  int32_t r_lds;              /* dynamic LDS bytes of the launch */
+  int32_t r_groups;           /* M / 32 */
+} orl_small_ex;
+int orl_debug_small(orl_small_ex* args);
+/* name of instantiation `idx`: "small_fwd<F32,QG>" x 4, then "small_abwd<F32>" x 2; NULL past the end */
+const char* orl_debug_small_flavour(int idx);
 /* times `reps` launches of one GEMM tile configuration on random data (kind 0 forward, 1 dgrad, 2 wgrad) */
 int orl_debug_gemm_time(int cfg, int kind, int M, int N, int K, int nz, int ksplit, int reps, float* ms_out);
 /* average duration (ms) of the kernel with the largest accumulated time during the last orl_learn_n

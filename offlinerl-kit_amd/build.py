@@ -38,7 +38,8 @@ UNITS = {
     "ws_wgrad.hip": WS_H,
     "ws_debug.hip": ["gemm.h", "ws_gemm.h", ABI],
     "small_fwd.hip": ["small_fwd.h", "sample.h", "gemm.h"],
-    "small_bwd.hip": ["small_bwd.h", "scalars.h", "gemm.h"],
+    "small_bwd.hip": ["small_bwd.h", "small_fwd.h", "sample.h", "scalars.h", "gemm.h"],
+    "small_debug.hip": ["small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "gemm.h", ABI],
 }
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 

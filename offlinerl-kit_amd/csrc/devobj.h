@@ -44,6 +44,9 @@ struct DevAllocs {
     const size_t bytes = sizeof(T) * count, nb = bytes ? bytes : 16;
     if (hipMalloc((void**)p, nb) != hipSuccess) return fail(std::string(who) + ": hipMalloc of " + std::to_string(bytes) + " bytes failed");
     if (hipMemset(*p, 0, nb) != hipSuccess) return fail(std::string(who) + ": hipMemset failed");
+    // the fill runs on the null stream and need not have finished when hipMemset returns; the objects' own streams are non-blocking, so
+    // a kernel of theirs that writes the new array is not ordered behind it (a late fill would zero what the kernel wrote)
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(std::string(who) + ": hipMemset failed");
     ptrs.push_back(*p);
     return 0;
   }

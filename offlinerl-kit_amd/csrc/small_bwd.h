@@ -51,12 +51,16 @@ struct SmallABwdP {
 enum { SB_ROWS = 32, SB_N = 256, SB_NT = 512, SB_MAXGROUPS = 64 };
 
 static inline bool small_abwd_supported(const SmallABwdP& p) {
-  if (p.M < SB_ROWS || (p.M % SB_ROWS) || p.M / SB_ROWS > SB_MAXGROUPS || p.in0 + 1 > 32 || p.x_pitch > 32 || p.in0 > p.x_pitch) return false;
+  if (p.M < SB_ROWS || (p.M % SB_ROWS) || p.M / SB_ROWS > SB_MAXGROUPS || p.in0 < 1 || p.in0 + 1 > 32 || p.x_pitch > 32 || p.in0 > p.x_pitch) return false;
   if (p.A < 1 || p.A > 8 || p.K != 2 || p.ga_pitch < p.A) return false;
   if (!aligned16(p.W1) || (p.w1_s0 & 3) || !aligned16(p.H0) || (p.h0_s0 & 3) || !aligned16(p.H1) || (p.h1_s0 & 3)) return false;
   if (!aligned16(p.Wh) || (p.wh_s0 & 3)) return false;
   return true;
 }
+// The instantiations small_abwd_kernel<F32> and their selector (as in small_fwd.h): asked by the launcher and by the unit tap.
+struct SmallFlavour;
+const SmallFlavour* small_abwd_flavours(int* n);                                   // small_bwd.hip
+static inline int small_abwd_flavour(const SmallABwdP& p) { return p.f32 ? 1 : 0; }
 hipError_t launch_small_abwd(const SmallABwdP& p, int runs, hipStream_t st);      // small_bwd.hip
 
 }  // namespace orl

@@ -2,6 +2,7 @@
 #include "small_bwd.h"
 
 #include "scalars.h"
+#include "small_fwd.h"
 
 namespace orl {
 
@@ -519,6 +520,12 @@ __global__ __launch_bounds__(SB_NT) void small_abwd_kernel(const SmallABwdP p) {
   }
 }
 
+const SmallFlavour* small_abwd_flavours(int* n) {
+  static const SmallFlavour rows[] = {{"small_abwd<0>", sb_lds_bytes<false>()}, {"small_abwd<1>", sb_lds_bytes<true>()}};
+  *n = 2;
+  return rows;
+}
+
 hipError_t launch_small_abwd(const SmallABwdP& p, int runs, hipStream_t st) {
   static const hipError_t attr_err = [] {
     hipError_t e = hipFuncSetAttribute((const void*)small_abwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb_lds_bytes<false>());
@@ -527,7 +534,7 @@ hipError_t launch_small_abwd(const SmallABwdP& p, int runs, hipStream_t st) {
   }();
   if (attr_err != hipSuccess) return attr_err;
   const dim3 grid(p.M / SB_ROWS, runs), block(SB_NT);
-  if (p.f32) hipLaunchKernelGGL(small_abwd_kernel<true>, grid, block, sb_lds_bytes<true>(), st, p);
+  if (small_abwd_flavour(p) == 1) hipLaunchKernelGGL(small_abwd_kernel<true>, grid, block, sb_lds_bytes<true>(), st, p);
   else hipLaunchKernelGGL(small_abwd_kernel<false>, grid, block, sb_lds_bytes<false>(), st, p);
   return hipGetLastError();
 }

@@ -43,13 +43,18 @@ struct SmallFwdP {
 enum { SF_ROWS = 32, SF_N = 256, SF_NT = 512, SF_MAXOUT = 16 };
 
 static inline bool small_fwd_supported(const SmallFwdP& p) {
-  if (p.M < SF_ROWS || (p.M % SF_ROWS) || p.in0 + 1 > 32 || p.x_pitch > 32 || p.in0 > p.x_pitch || p.out_dim < 1 || p.out_dim > SF_MAXOUT) return false;
+  if (p.M < SF_ROWS || (p.M % SF_ROWS) || p.in0 < 1 || p.in0 + 1 > 32 || p.x_pitch > 32 || p.in0 > p.x_pitch || p.out_dim < 1 || p.out_dim > SF_MAXOUT) return false;
   if (!p.W1.vec4() || (p.H0.p && !p.H0.vec4()) || (p.H1.p && !p.H1.vec4())) return false;
   if (p.njobs && (p.njobs > 3 || p.nz1 != 1 || p.out_dim != 2 * p.A || p.A > 8 || p.G.p)) return false;
   for (int i = 0; i < p.njobs; ++i) if (p.job[i].rep < 1 || p.job[i].rep > 16) return false;      // (the epilogue prefetches its noise: rep / 2 <= 8 values per thread and job)
   if (p.G.p && (p.out_dim != 1 || p.gn < 1 || p.gn > 8 || p.gc0 < 0 || p.gc0 + p.gn > p.in0 || p.g_pitch < p.gn)) return false;
   return true;
 }
+// The instantiations small_fwd_kernel<F32, QG> and ONE selector: the row of the table that serves p.  The launcher and the unit tap
+// (small_debug.hip) both ask it, so they cannot disagree about which kernel a parameter set takes.
+struct SmallFlavour { const char* name; size_t lds; };
+const SmallFlavour* small_fwd_flavours(int* n);                                // small_fwd.hip
+static inline int small_fwd_flavour(const SmallFwdP& p) { return (p.f32 ? 1 : 0) + (p.G.p ? 2 : 0); }
 hipError_t launch_small_fwd(const SmallFwdP& p, int nz, hipStream_t st);      // small_fwd.hip
 
 }  // namespace orl

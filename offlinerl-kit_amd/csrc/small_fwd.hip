@@ -546,6 +546,13 @@ __global__ __launch_bounds__(SF_NT) void small_fwd_kernel(const SmallFwdP p) {
   SF_STAMP(6);
 }
 
+const SmallFlavour* small_fwd_flavours(int* n) {
+  static const SmallFlavour rows[] = {{"small_fwd<0,0>", sf_lds_bytes<false>()}, {"small_fwd<1,0>", sf_lds_bytes<true>()},
+                                      {"small_fwd<0,1>", sf_lds_bytes<false>()}, {"small_fwd<1,1>", sf_lds_bytes<true>()}};
+  *n = 4;
+  return rows;
+}
+
 hipError_t launch_small_fwd(const SmallFwdP& p, int nz, hipStream_t st) {
   static const hipError_t attr_err = [] {
     hipError_t e = hipFuncSetAttribute((const void*)small_fwd_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sf_lds_bytes<false>());
@@ -556,11 +563,12 @@ hipError_t launch_small_fwd(const SmallFwdP& p, int nz, hipStream_t st) {
   }();
   if (attr_err != hipSuccess) return attr_err;
   const dim3 grid(p.M / SF_ROWS, 1, nz), block(SF_NT);
-  if (p.G.p) {
-    if (p.f32) hipLaunchKernelGGL((small_fwd_kernel<true, true>), grid, block, sf_lds_bytes<true>(), st, p);
-    else hipLaunchKernelGGL((small_fwd_kernel<false, true>), grid, block, sf_lds_bytes<false>(), st, p);
-  } else if (p.f32) hipLaunchKernelGGL((small_fwd_kernel<true, false>), grid, block, sf_lds_bytes<true>(), st, p);
-  else hipLaunchKernelGGL((small_fwd_kernel<false, false>), grid, block, sf_lds_bytes<false>(), st, p);
+  switch (small_fwd_flavour(p)) {      // <F32, QG>: the rows of small_fwd_flavours
+    case 0: hipLaunchKernelGGL((small_fwd_kernel<false, false>), grid, block, sf_lds_bytes<false>(), st, p); break;
+    case 1: hipLaunchKernelGGL((small_fwd_kernel<true, false>), grid, block, sf_lds_bytes<true>(), st, p); break;
+    case 2: hipLaunchKernelGGL((small_fwd_kernel<false, true>), grid, block, sf_lds_bytes<false>(), st, p); break;
+    default: hipLaunchKernelGGL((small_fwd_kernel<true, true>), grid, block, sf_lds_bytes<true>(), st, p); break;
+  }
   return hipGetLastError();
 }
 

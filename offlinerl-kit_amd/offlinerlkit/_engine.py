@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "orl_buffer_reserve", "orl_buffer_append", "orl_buffer_append_rollout", "orl_buffer_read", "orl_engine_attach_model_buffer",
     "orl_buffer_append_rollout_runs", "orl_engine_attach_model_buffers",
     "orl_health", "orl_health_check", "orl_health_clear", "orl_num_metrics", "orl_metric_name", "orl_step_count",
-    "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_ex", "orl_debug_ws", "orl_debug_ws_flavour", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
+    "orl_debug_read", "orl_debug_read_bits", "orl_debug_grads", "orl_debug_gemm", "orl_debug_gemm_ex", "orl_debug_ws", "orl_debug_ws_flavour", "orl_debug_small", "orl_debug_small_flavour", "orl_debug_gemm_time", "orl_profile_enable", "orl_profile_query",
     # dynamics ensemble (orl_dynamics)
     "orl_dyn_config_default", "orl_dyn_create", "orl_dyn_destroy", "orl_dyn_sync", "orl_dyn_floats", "orl_dyn_config_floats",
     "orl_dyn_num_tensors", "orl_dyn_tensor", "orl_dyn_ptr", "orl_dyn_set", "orl_dyn_get", "orl_dyn_adam_get", "orl_dyn_adam_set",
@@ -165,6 +165,28 @@ class OrlWsEx(C.Structure):
     _fields_ = [(k, C.c_int32) for k in WS_EX_INTS] + [(k, OrlGemmBuf) for k in WS_EX_BUFS] + [(k, C.c_int32) for k in WS_EX_REPORT]
 
 
+SMALL_KINDS = {"fwd": 0, "abwd": 1}
+SMALL_EX_INTS = ("kind", "f32", "M", "nz0", "nz1", "in0", "out_dim", "gc0", "gn", "njobs", "A", "K", "xa_col", "auto_alpha", "clamp_alpha01", "nm", "m_actor",
+                 "m_alpha_loss", "m_alpha", "dry_run")
+SMALL_EX_FLOATS = ("fixed_alpha", "target_entropy", "adam_b1", "adam_b2", "adam_eps")
+SMALL_EX_OFFS = ("off_w0", "off_b0", "off_w1", "off_b1", "off_wh", "off_bh")
+SMALL_EX_BUFS_A = ("X", "W0", "b0", "W1", "b1", "Wt", "bt", "H0", "H1", "OUT", "G")
+SMALL_EX_BUFS_B = ("head", "eps", "xa", "logp", "qa", "ga", "Wh", "out", "sc", "hy", "gstep", "metrics_last", "metrics_sum", "part", "ticket")
+SMALL_JOB_INTS = ("head_row0", "rows", "rep", "dst_row0", "dst_col")
+SMALL_JOB_BUFS = ("eps", "dst", "logp")
+SMALL_EX_REPORT = ("r_kind", "r_flavour", "r_lds", "r_groups")
+
+
+class OrlSmallJob(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in SMALL_JOB_INTS] + [(k, OrlGemmBuf) for k in SMALL_JOB_BUFS]
+
+
+class OrlSmallEx(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in SMALL_EX_INTS] + [(k, C.c_float) for k in SMALL_EX_FLOATS] + [(k, C.c_int64) for k in SMALL_EX_OFFS] +
+                [(k, OrlGemmBuf) for k in SMALL_EX_BUFS_A] + [("job", OrlSmallJob * 3)] + [(k, OrlGemmBuf) for k in SMALL_EX_BUFS_B] +
+                [(k, C.c_int32) for k in SMALL_EX_REPORT])
+
+
 _lib = None
 
 
@@ -265,6 +287,9 @@ def load_library(path: Optional[str] = None):
     lib.orl_debug_ws.argtypes = [C.POINTER(OrlWsEx)]
     lib.orl_debug_ws_flavour.argtypes = [C.c_int]
     lib.orl_debug_ws_flavour.restype = C.c_char_p
+    lib.orl_debug_small.argtypes = [C.POINTER(OrlSmallEx)]
+    lib.orl_debug_small_flavour.argtypes = [C.c_int]
+    lib.orl_debug_small_flavour.restype = C.c_char_p
     lib.orl_debug_gemm_time.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_float)]
     lib.orl_profile_enable.argtypes = [C.c_void_p, C.c_int]
     lib.orl_profile_query.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double),
@@ -1049,6 +1074,59 @@ def debug_ws(kind: str, arrays: Dict[str, GemmArray], **ints) -> Dict[str, objec
     _check(lib.orl_debug_ws(C.byref(a)), "orl_debug_ws")
     name = lib.orl_debug_ws_flavour(a.r_flavour)
     return {"launcher": int(a.r_launcher), "flavour": name.decode(), "flavour_id": int(a.r_flavour), "lds": int(a.r_lds), "groups": int(a.r_groups)}
+
+
+def small_flavours() -> List[str]:
+    """the table of small_fwd / small_abwd instantiations inside the few-rows tap; a launch reports an index into it"""
+    lib = load_library()
+    out = []
+    while True:
+        s = lib.orl_debug_small_flavour(len(out))
+        if s is None:
+            return out
+        out.append(s.decode())
+
+
+def debug_small(kind: str, arrays: Dict[str, GemmArray], jobs=(), **scalars) -> Dict[str, object]:
+    """The unit-test tap of the few-rows kernels (orl_debug_small): one launch of launch_small_<kind> (``kind`` in SMALL_KINDS).
+    ``arrays`` maps the names of include/orl_engine.h's orl_small_ex -- the field names of SmallFwdP / SmallABwdP -- to array objects
+    with a ``desc()``; which arrays are given picks the mode (G: QG; H0 / H1 absent: not stored).  ``jobs``: up to three dicts with the
+    SampleJob integers (head_row0, rows, rep, dst_row0, dst_col) and the arrays eps (optional), dst, logp (optional); njobs is their
+    number.  ``scalars``: the integer, float and slab-offset fields; dry_run = 1 stops after the checks and the report, without a
+    device.  Every array, operands included, is updated in place from the device copy, whole.  Returns the report (kind, flavour = the
+    instantiation's name, flavour_id, lds, groups).  Refused combinations raise before any device call."""
+    lib = load_library()
+    a = OrlSmallEx()
+    a.kind = SMALL_KINDS[kind]
+    a.nz0 = a.nz1 = 1
+    a.K = 2
+    for k, v in scalars.items():
+        if k in SMALL_EX_FLOATS:
+            setattr(a, k, float(v))
+        elif (k in SMALL_EX_INTS and k not in ("kind", "njobs")) or k in SMALL_EX_OFFS:
+            setattr(a, k, int(v))
+        else:
+            raise TypeError(f"debug_small: unknown field {k}")
+    for k, v in arrays.items():
+        if k not in SMALL_EX_BUFS_A + SMALL_EX_BUFS_B:
+            raise TypeError(f"debug_small: unknown array {k}")
+        if v is not None:
+            setattr(a, k, v.desc())
+    if len(jobs) > 3:
+        raise TypeError("debug_small: at most three jobs")
+    a.njobs = len(jobs)
+    for i, job in enumerate(jobs):
+        for k, v in job.items():
+            if k in SMALL_JOB_INTS:
+                setattr(a.job[i], k, int(v))
+            elif k in SMALL_JOB_BUFS:
+                if v is not None:
+                    setattr(a.job[i], k, v.desc())
+            else:
+                raise TypeError(f"debug_small: unknown job field {k}")
+    _check(lib.orl_debug_small(C.byref(a)), "orl_debug_small")
+    name = lib.orl_debug_small_flavour(a.r_flavour)
+    return {"kind": int(a.r_kind), "flavour": name.decode(), "flavour_id": int(a.r_flavour), "lds": int(a.r_lds), "groups": int(a.r_groups)}
 
 
 def default_dyn_config(**over) -> OrlDynConfig:
