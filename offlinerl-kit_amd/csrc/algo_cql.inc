@@ -21,6 +21,13 @@ void Engine::sac_family_alloc(int Kc) {
   alloc_layers("ah", B); alloc_layers("dah", B); alloc_layers("ca", B, Kc); alloc_layers("dca", B, Kc);
   alloc("head", B, 2 * A); alloc("dhead", B, 2 * A); alloc("xa", B, XP); alloc("logp_a", B, 1);
   alloc("qa", B, 1, Kc); alloc("dqa", B, 1, Kc); alloc("dxa", B, A, Kc);
+  // operands / results of the actor phase's row kernels (k_tanh_sample, k_actor_loss, k_head_bwd), members stacked: [Kc][B]
+  taps["head"] = {W("head"), B, 2 * A};
+  taps["dhead"] = {W("dhead"), B, 2 * A};
+  taps["xa"] = {W("xa"), B, XP};
+  taps["logp_a"] = {W("logp_a"), B, 1};
+  taps["dqa"] = {W("dqa"), (long)B * Kc, 1};
+  taps["dxa"] = {W("dxa"), (long)B * Kc, A};
 }
 
 // the operands every TD-style critic loss reads the same way (TdLossP, MobileTdP, McqLossP, CqlLossP)
@@ -89,11 +96,18 @@ int Engine::cql_build() {
   taps["q2_all"] = {W("q").net(1), Mc, 1};
   taps["q1a"] = {W("qa").net(0), B, 1};
   taps["q2a"] = {W("qa").net(1), B, 1};
-  taps["logp_a"] = {W("logp_a"), B, 1};
   taps["target_q"] = {W("target_q"), B, 1};
   taps["xc"] = {W("xc"), Mc, XP};
   taps["dq1"] = {W("dq").net(0), Mc, 1};
   taps["dq2"] = {W("dq").net(1), Mc, 1};
+  // what k_tanh_sample (phase T) and k_cql_loss_rows read
+  taps["head2"] = {W("head2"), 2 * B, 2 * A};
+  taps["xt"] = {W("xt"), Bt, XP};
+  taps["qt1"] = {W("qt").net(0), Bt, 1};
+  taps["qt2"] = {W("qt").net(1), Bt, 1};
+  taps["logp_next"] = {W("logp_next"), Bt, 1};
+  taps["logp_pi"] = {W("logp_pi"), BN, 1};
+  taps["logp_npi"] = {W("logp_npi"), BN, 1};
   return 0;
 }
 

@@ -25,6 +25,11 @@ int Engine::edac_build() {
   taps["gamma"] = {W("gamma"), (long)B * Kc, A};
   taps["xq"] = {W("xq"), B, XP};                     // critic input rows (obs | act) of the TD / diversity passes
   taps["dqs"] = {W("dq"), (long)B * Kc, 1};          // dL_TD/dq of every member
+  // what k_tanh_sample (target actions) and k_td_loss read: [Kc][Bt] target Q-values, Bt = B * rep rows
+  taps["head2"] = {W("head2"), B, 2 * A};
+  taps["xt"] = {W("xt"), Bt, XP};
+  taps["qts"] = {W("qt"), (long)Bt * Kc, 1};
+  taps["logp_next"] = {W("logp_next"), Bt, 1};
   return 0;
 }
 

@@ -19,6 +19,16 @@ int Engine::iql_build() {
   taps["v"] = {W("v"), B, 1};
   taps["target_q"] = {W("target_q"), B, 1};
   taps["exp_a"] = {W("exp_a"), B, 1};
+  // operands / results of k_iql_v_loss, k_iql_q_loss, k_iql_actor_loss
+  taps["qo1"] = {W("qo").net(0), B, 1};
+  taps["qo2"] = {W("qo").net(1), B, 1};
+  taps["qmin"] = {W("qmin"), B, 1};
+  taps["v2"] = {W("v2"), 2 * B, 1};
+  taps["dv"] = {W("dv"), B, 1};
+  taps["dq1"] = {W("dq").net(0), B, 1};
+  taps["dq2"] = {W("dq").net(1), B, 1};
+  taps["mraw"] = {W("mraw"), B, A};
+  taps["dmraw"] = {W("dmraw"), B, A};
   return 0;
 }
 

@@ -18,7 +18,6 @@ void Engine::sac_alloc() {
   taps["q2"] = {W("q").net(1), B, 1};
   taps["q1a"] = {W("qa").net(0), B, 1};
   taps["q2a"] = {W("qa").net(1), B, 1};
-  taps["logp_a"] = {W("logp_a"), B, 1};
   taps["target_q"] = {W("target_q"), B, 1};
 }
 

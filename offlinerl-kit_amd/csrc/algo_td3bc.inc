@@ -16,6 +16,18 @@ int Engine::td3bc_build() {
   taps["q2"] = {W("q").net(1), B, 1};
   taps["target_q"] = {W("target_q"), B, 1};
   taps["q_pi"] = {W("qpi"), B, 1};
+  // operands / results of k_det_action, k_td_loss, k_td3_actor_loss, k_td3_actor_bwd
+  taps["qt1"] = {W("qt").net(0), B, 1};
+  taps["qt2"] = {W("qt").net(1), B, 1};
+  taps["dq1"] = {W("dq").net(0), B, 1};
+  taps["dq2"] = {W("dq").net(1), B, 1};
+  taps["mraw"] = {W("mraw"), B, A};
+  taps["mraw_t"] = {W("mraw_t"), B, A};
+  taps["xt"] = {W("xt"), B, XP};
+  taps["xa"] = {W("xa"), B, XP};
+  taps["dxa"] = {W("dxa"), B, A};
+  taps["dqpi"] = {W("dqpi"), B, 1};
+  taps["dmraw"] = {W("dmraw"), B, A};
   return 0;
 }
 
