@@ -726,8 +726,11 @@ int orl_diffusion_learn_epoch(orl_diffusion* d, const int64_t* order, int64_t n_
  * act_out [n][act_dim]; every array is a device pointer when on_device.  One host synchronisation, at the end. */
 int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const float* init_noise, const int64_t* noise_idx,
                          int64_t noise_rows, const float* z, int on_device, float* act_out);
-/* test taps of the last step: "pred", "eps", "x_t", "t" (as floats), "gf" (the condition vector), "film", "loss"; of the last
- * sample: "z" (the last noise drawn), "x".  Returns the floats written, < 0 on error. */
+/* test taps of the last step: "pred", "eps", "x_t", "t" (as floats), "gf" (the condition vector), "film", "loss", and the forward
+ * activations it left in the training workspace: "e0" (the sinusoidal embedding), "mc" (Mish of the condition vector), "y1.<b>" and
+ * "out.<b>" (block b of the layer table after its FiLM and at its output, b = 0 .. blocks - 1), "yf" (final_conv's GN + Mish); of the
+ * last sample: "z" (the last noise drawn), "x".  Unknown names and a block index out of range are refused.  Returns the floats
+ * written, < 0 on error. */
 int64_t orl_diffusion_debug_read(orl_diffusion* d, const char* name, float* host, int64_t cap);
 int orl_diffusion_debug_grads(orl_diffusion* d, float* host, int64_t n_floats);   /* parameter gradient of the last step */
 

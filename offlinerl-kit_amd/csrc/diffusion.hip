@@ -872,6 +872,19 @@ int64_t orl_diffusion_debug_read(orl_diffusion* d, const char* name, float* host
   else if (nm == "t") { src = d->TF; cols = 1; pitch = 1; }
   else if (nm == "gf") { src = w.GF.p; cols = d->cond; pitch = w.GF.pitch; }
   else if (nm == "film") { src = w.FILM.p; cols = d->film_cols; pitch = w.FILM.pitch; }
+  else if (nm == "e0") { src = w.E0.p; cols = d->dsed; pitch = w.E0.pitch; }
+  else if (nm == "mc") { src = w.MC.p; cols = d->cond; pitch = w.MC.pitch; }
+  else if (nm == "yf") { src = w.YF.p; cols = d->start_dim; pitch = w.YF.pitch; }
+  else if (nm.compare(0, 3, "y1.") == 0 || nm.compare(0, 4, "out.") == 0) {      // "y1.<b>" / "out.<b>": block b of the layer table
+    const bool y1 = nm[0] == 'y';
+    const std::string num = nm.substr(y1 ? 3 : 4);
+    if (num.empty() || num.size() > 4 || num.find_first_not_of("0123456789") != std::string::npos || (num.size() > 1 && num[0] == '0'))
+      return fail("orl_diffusion_debug_read: unknown tap " + nm);
+    const size_t b = (size_t)std::stoi(num);
+    if (b >= d->blocks.size()) return fail("orl_diffusion_debug_read: unknown tap " + nm + " (the net has " + std::to_string(d->blocks.size()) + " blocks)");
+    const DevMat& m = y1 ? w.Y1[b] : w.OUT[b];
+    src = m.p; cols = d->blocks[b].out; pitch = m.pitch;
+  }
   else if (nm == "loss") { src = d->loss_cell; rows = 1; cols = 1; pitch = 1; }
   else if (nm == "z") { src = d->sZkeep; rows = d->last_sample_n; cols = d->ad; pitch = d->ad; }
   else if (nm == "x") { src = d->sX; rows = d->last_sample_n; cols = d->ad; pitch = rup4(d->ad); }

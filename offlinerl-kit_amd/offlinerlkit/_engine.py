@@ -1500,6 +1500,8 @@ class Diffusion(_Handle):
         return out
 
     def debug_read(self, name: str, cap: int = 1 << 22) -> np.ndarray:
+        """a test tap as a flat array.  Of the last step: pred, eps, x_t, t, gf, film, loss, e0, mc, y1.<b> / out.<b> (block b), yf;
+        of the last sample: z, x"""
         buf = np.empty(cap, np.float32)
         n = int(self.lib.orl_diffusion_debug_read(self._h, name.encode(), buf.ctypes.data, cap))
         if n < 0:

@@ -99,12 +99,13 @@ def sinusoidal(t, dsed, dt):
     return np.concatenate([np.sin(arg), np.cos(arg)], axis=1).astype(dt)
 
 
-def forward(P, c, x, t, obs, dtype=np.float32, keep=False):
-    """x [B, act_dim], t [B], obs [B, obs_dim] -> the predicted noise [B, act_dim] (and the activations the backward reads)"""
+def forward(P, c, x, t, obs, dtype=np.float32, keep=False, e0=None):
+    """x [B, act_dim], t [B], obs [B, obs_dim] -> the predicted noise [B, act_dim] (and the activations the backward reads);
+    ``e0``: a given sinusoidal embedding [B, dsed] (an engine's own) in place of the one computed from t"""
     dt, G = dtype, c["n_groups"]
     plan, last = block_plan(c["act_dim"], c["down_dims"])
     x = x.astype(dt)
-    e0 = sinusoidal(t, c["dsed"], dt)
+    e0 = sinusoidal(t, c["dsed"], dt) if e0 is None else np.asarray(e0).astype(dt)
     z1 = e0 @ _w(P, "diffusion_step_encoder.1.weight", dt).T + P["diffusion_step_encoder.1.bias"].astype(dt)
     m1 = mish(z1)
     emb = m1 @ _w(P, "diffusion_step_encoder.3.weight", dt).T + P["diffusion_step_encoder.3.bias"].astype(dt)
@@ -143,12 +144,21 @@ def _set_grad(Gd, P, key, g):
     Gd[key] = full
 
 
-def loss_and_grads(P, c, act, t, eps, obs, dtype=np.float32):
-    """one training batch -> (loss, pred, {state_dict key: gradient}, x_t)"""
+def _skip_cols(dX, c1):
+    """the skip half of the gradient of a concatenation [x | skip]: the columns from c1 on"""
+    return dX[:, c1:]
+
+
+def _clip_x0(x0):
+    return np.clip(x0, -1.0, 1.0)
+
+
+def loss_and_grads(P, c, act, t, eps, obs, dtype=np.float32, e0=None, keep=False):
+    """one training batch -> (loss, pred, {state_dict key: gradient}, x_t) (and the forward's activations when ``keep``)"""
     dt, G = dtype, c["n_groups"]
     acp = alphas_cumprod(c["N"])
     xt = (np.sqrt(acp[t])[:, None] * act + np.sqrt(np.float32(1.0) - acp[t])[:, None] * eps).astype(np.float32)
-    pred, A = forward(P, c, xt, t, obs, dtype, keep=True)
+    pred, A = forward(P, c, xt, t, obs, dtype, keep=True, e0=e0)
     B = len(t)
     diff = pred - eps.astype(dt)
     loss = (diff * diff).mean()
@@ -187,13 +197,13 @@ def loss_and_grads(P, c, act, t, eps, obs, dtype=np.float32):
             c1 = plan[src][2]
             douts[src] = dX[:, :c1] if douts[src] is None else douts[src] + dX[:, :c1]
             if skip >= 0:
-                douts[skip] = dX[:, c1:] if douts[skip] is None else douts[skip] + dX[:, c1:]
+                douts[skip] = _skip_cols(dX, c1) if douts[skip] is None else douts[skip] + _skip_cols(dX, c1)
     dsed = c["dsed"]
     de = dmc[:, :dsed] * dmish(A["gf"][:, :dsed])
     Gd["diffusion_step_encoder.3.weight"] = de.T @ A["m1"]; Gd["diffusion_step_encoder.3.bias"] = de.sum(axis=0)
     dz1 = de @ P["diffusion_step_encoder.3.weight"].astype(dt) * dmish(A["z1"])
     Gd["diffusion_step_encoder.1.weight"] = dz1.T @ A["e0"]; Gd["diffusion_step_encoder.1.bias"] = dz1.sum(axis=0)
-    return loss, pred, Gd, xt
+    return (loss, pred, Gd, xt, A) if keep else (loss, pred, Gd, xt)
 
 
 def train(P, c, data, steps, total_steps):
@@ -222,20 +232,25 @@ def train(P, c, data, steps, total_steps):
     return np.array(losses, np.float64), P, ema
 
 
-def sample(P, c, obs, init_noise, z):
-    """select_action: x from init_noise [rows, 1, act_dim] through t = N-1 .. 0 with z[t] added for t > 0 -> [rows, act_dim]"""
-    f = np.float32
+def sample(P, c, obs, init_noise, z, dtype=np.float32, trace=None):
+    """select_action: x from init_noise [rows, 1, act_dim] through t = N-1 .. 0 with z[t] added for t > 0 -> [rows, act_dim].
+    The five coefficients of a step are the fp32 table of ``policy/diffusion.py::ddpm_schedule`` whatever ``dtype`` is: float64 widens
+    the net and the update, not the schedule.  ``trace``: a list that receives every step's x0 before the clip."""
+    f, dt = np.float32, dtype
     acp = alphas_cumprod(c["N"])
-    x = init_noise.reshape(len(obs), -1).astype(f)
+    x = init_noise.reshape(len(obs), -1).astype(f).astype(dt)
     one = f(1.0)
     for t in range(c["N"] - 1, -1, -1):
-        e = forward(P, c, x, np.full(len(obs), t), obs)
+        e = forward(P, c, x, np.full(len(obs), t), obs, dtype=dt)
         a, ap = acp[t], (acp[t - 1] if t > 0 else one)
         at = a / ap
-        x0 = np.clip((x - np.sqrt(one - a) * e) / np.sqrt(a), -1.0, 1.0).astype(f)
-        x = (np.sqrt(ap) * (one - at) / (one - a) * x0 + np.sqrt(at) * (one - ap) / (one - a) * x).astype(f)
+        raw = (x - np.sqrt(one - a) * e) / np.sqrt(a)
+        if trace is not None:
+            trace.append(np.array(raw, np.float64))
+        x0 = _clip_x0(raw).astype(dt)
+        x = (np.sqrt(ap) * (one - at) / (one - a) * x0 + np.sqrt(at) * (one - ap) / (one - a) * x).astype(dt)
         if t > 0:
-            x = (x + np.sqrt(max((one - ap) / (one - a) * (one - at), f(1e-20))) * z[t]).astype(f)
+            x = (x + np.sqrt(max((one - ap) / (one - a) * (one - at), f(1e-20))) * z[t]).astype(dt)
     return x
 
 
@@ -253,3 +268,58 @@ def grad_distance(a, b):
         else:
             noise = max(noise, float(np.abs(a[k]).max()))
     return rel, noise
+
+
+# ---- self-bounding float64 restatements (the bound type of tests/row_refs.py) ---------------------------------------------------
+def sinusoidal_ref(t, dsed):
+    """[sin(t f_j) | cos(t f_j)], f_j = exp(-j ln(1e4) / (half - 1)), in float64 with the first-order bound of an fp32 evaluation
+    (u = 2^-24): one rounding each for the constant ln(1e4), the division by half - 1, the product with j and the product t f_j; a
+    2 u library exp whose argument error the exponential turns into a relative one (so the constant's, the division's and the product's
+    roundings arrive multiplied by j step = the argument itself); a 2 u library sin / cos on an argument that carries all of that,
+    times |cos| / |sin|.  j = 0 is exact up to the sine: f_0 = exp(0) = 1 and the argument is the integer t.  -> a BV [len(t), dsed]"""
+    import row_refs as rr
+    half = dsed // 2
+    j = np.arange(half, dtype=np.float64)
+    const = rr.BV(np.array(math.log(10000.0)), rr.U * math.log(10000.0))             # what fp32 holds of ln(1e4): one rounding
+    prod = rr.BV.exact(j) * (const / float(half - 1))
+    f = rr.where(j == 0, 1.0, rr.exp(-prod))
+    a = rr.BV.exact(np.asarray(t, np.float64)[:, None]) * rr.BV(f.v[None, :], f.e[None, :])
+    a = rr.where(np.broadcast_to(j == 0, a.shape), rr.BV(a.v), a)                     # t * 1
+    s, co = np.sin(a.v), np.cos(a.v)
+    lib = lambda z, d: rr.BV(z, np.abs(d) * a.e + 2.0 * rr.U * np.abs(z) + rr.TINY)
+    sn, cs = lib(s, co), lib(co, s)
+    return rr.BV(np.concatenate([sn.v, cs.v], axis=1), np.concatenate([sn.e, cs.e], axis=1))
+
+
+def adam_ema_f32(p, ema, m, v, g, lr, k, decay=None):
+    """one step of ``train``'s update in fp32 numpy on flat arrays: Adam with the learning rate ``lr`` at optimizer step k (0-based),
+    then the EMA with ``decay`` (``ema_decay(k)`` unless given) -> (p, ema, m, v)"""
+    f = np.float32
+    bc1, bc2 = 1.0 - float(f(0.9)) ** (k + 1), 1.0 - float(f(0.999)) ** (k + 1)
+    step, bc2s = f(lr / bc1), f(math.sqrt(bc2))
+    d = ema_decay(k) if decay is None else decay
+    p, ema, m, v, g = (np.asarray(x, f) for x in (p, ema, m, v, g))
+    m = m + (g - m) * (f(1.0) - f(0.9))
+    v = v * f(0.999) + (f(1.0) - f(0.999)) * g * g
+    p = (p - step * (m / (np.sqrt(v) / bc2s + f(1e-8)))).astype(f)
+    ema = (ema * f(d) + p * f(1.0 - d)).astype(f)
+    return p, ema, m, v
+
+
+def adam_ema_ref(p, ema, m, v, g, lr, k, b1=0.9, b2=0.999, eps=1e-8):
+    """the same step as value-with-bound arrays: torch.optim.Adam for the engine's fp32 betas (``row_refs.adam``'s formula and constants;
+    the learning rate stays the double of the table, lr / (1 - b1^(k+1)) is rounded to fp32 once), then
+    ema <- ema decay + p (1 - decay) with the two fp32 constants the launch receives: two products and one sum on top of p's own bound
+    -> (p, ema, m, v) as BVs"""
+    import row_refs as rr
+    t = k + 1
+    b1_, b2_ = float(np.float32(b1)), float(np.float32(b2))
+    step, bc2s = float(lr) / (1.0 - b1_ ** t), math.sqrt(1.0 - b2_ ** t)
+    step, bc2s = rr.BV(step, rr.U * abs(step)), rr.BV(bc2s, rr.U * abs(bc2s))
+    p, ema, m, v, g = (rr.BV.exact(np.asarray(x, np.float32)) for x in (p, ema, m, v, g))
+    m = m + (g - m) * rr.BV(1.0 - b1_)                      # 1 - b is exact in fp32 (Sterbenz)
+    v = v * rr.BV.exact(b2_) + rr.BV(1.0 - b2_) * g * g
+    p = p - step * (m / (rr.sqrt(v) / bc2s + rr.BV.exact(eps)))
+    d = ema_decay(k)
+    ema = ema * rr.BV.exact(np.float32(d)) + p * rr.BV.exact(np.float32(1.0 - d))
+    return p, ema, m, v
