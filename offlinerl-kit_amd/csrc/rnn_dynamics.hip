@@ -1,0 +1,1020 @@
+// rnn_dynamics.hip — RNNDynamics on the device (reference: dynamics/rnn_dynamics.py, nets/rnn.py:RNNModel): orl_rnn_* of
+// include/orl_engine.h.
+//
+// Every sequence array is a [rows * T][cols] matrix, row b * T + t (batch_first).  One training step is a run of launches on one stream:
+//   k_rnn_gather       the step's sequences, targets and loss masks out of the HBM data set
+//   per GRU layer      ONE tiled GEMM for the input projections of all T steps (E_BIAS), then ONE launch of k_rnn_scan_fwd: a
+//                      workgroup owns 16 batch rows and all H hidden units of them for all T steps, keeps h_{t-1} in LDS, multiplies it
+//                      by W_hh on the fp32 MFMA and applies the gates in the same step's epilogue.  Batch rows are independent, so no
+//                      workgroup ever waits for another one: __syncthreads() only, and the bounded loop over t.
+//   the tail           tiled GEMMs (E_BIAS_SWISH keeps the pre-activation) with k_rnn_ln_fwd between them: dropout, residual, LayerNorm
+//   k_rnn_loss         the masked MSE and its gradient, one block, fixed order
+//   the backward       the tail top down (k_rnn_ln_bwd folds the dropout mask and Swish' in), then per GRU layer ONE launch of
+//                      k_rnn_scan_bwd (t = T-1 .. 0, same ownership; carries dh_{t-1} = dh_t z + dGH_t W_hh in LDS) and three tiled
+//                      GEMMs over all rows: dW_hh / db_hh from dGH and the shifted h, dW_ih / db_ih, and the dX of the layer below
+//   k_rnn_colsum_*     dgamma / dbeta: per-row terms summed in row order in two levels (64-row chunks, then the chunks)
+//   k_rnn_slab_sum     the weight gradients are split-K products into up to 8 slabs (k ranges of >= 256 rows): the slabs added in order
+//   k_rnn_adam         torch.optim.Adam over the flat block
+// Nothing accumulates with atomics: two identical calls give identical bits.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "devobj.h"
+#include "reduce.h"
+#include "rng.h"
+
+namespace orl {
+
+enum { RNN_RB = 16 };                 // batch rows of a scan workgroup: one MFMA tile
+enum { RNN_FWD_WAVES = 8, RNN_BWD_WAVES = 4 };
+// 16-deep k blocks whose weight loads a scan wave issues together.  Measured at the default shape (3 layers, 256 x 20): the backward scans
+// 1.85 -> 1.49 ms with 4; the forward scans, two waves per SIMD already, 1.15 -> 1.37 ms with 4, so they keep 1
+enum { RNN_KU_FWD = 1, RNN_KU_BWD = 4 };
+enum { RNN_MAX_H = 512, RNN_MAX_LAYERS = 4, RNN_MAX_NORMS = ORL_MAX_HIDDEN + 1 };
+enum { RNN_NJ = RNN_MAX_H / 64 };     // LayerNorm: values of a row per lane
+enum { RNN_CHUNK = 64 };              // rows of a first-level column sum
+
+__device__ __forceinline__ float rnn_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+// Swish'(z) = sigmoid(z) (1 + z (1 - sigmoid(z))) on the library exp and a true division
+__device__ __forceinline__ float rnn_dswish(float z) { const float s = rnn_sigmoid(z); return s * (1.f + z * (1.f - s)); }
+
+// ---- the GRU recurrence of one layer over all T steps ----
+struct RnnScanP {
+  int rows, T, H;
+  const float* gi; int gip;          // [rows * T][3H]: W_ih x + b_ih, gates r | z | n
+  const float* whh;                  // [3H][H]
+  const float* bhh;                  // [3H]
+  float* ho; int hop;                // [rows * T][H]: h_t
+  float *r, *z, *n, *hn, *hp; int sp;   // training: the gates, W_hn h + b_hn and h_{t-1} ([rows * T][H] each); eval: null
+};
+
+// LDS: h_{t-1} of the block's 16 rows as [16][HP], HP = 16 ceil(H / 16) + 4, columns past H zero.  Wave w owns the unit tiles
+// w, w + 8, ...: 16 hidden units each, the r, z and n accumulators of a unit side by side in the same lane.  Lane (i = l & 15, q = l >> 4)
+// reads four consecutive k of h row i (one ds_read_b128) and of the W_hh rows of its unit (three global dwordx4 along k): MFMA s of a
+// 16-deep k block carries logical k = 16 kb + 4 q + s in hardware slot q on both operands.
+__global__ __launch_bounds__(64 * RNN_FWD_WAVES) void k_rnn_scan_fwd(RnnScanP p) {
+  extern __shared__ __attribute__((aligned(16))) float rnn_lds[];
+  const int H = p.H, KB = (H + 15) >> 4, HP = KB * 16 + 4;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
+  const int b0 = blockIdx.x * RNN_RB;
+  const int nrow = min((int)RNN_RB, p.rows - b0);
+  for (int e = tid; e < RNN_RB * HP; e += 64 * RNN_FWD_WAVES) rnn_lds[e] = 0.f;
+  __syncthreads();
+  for (int t = 0; t < p.T; ++t) {
+    float hnew[4][4];
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) hnew[it][r] = 0.f;
+      const int tile = wave + RNN_FWD_WAVES * it;
+      if (tile < KB) {                                  // (unit tiles = ceil(H / 16) = KB; wave-uniform)
+        const int j = tile * 16 + li;
+        const int jc = min(j, H - 1);                   // a clamped row is read and its result dropped
+        const float* wr = p.whh + (long)jc * H;
+        const float* wz = p.whh + (long)(H + jc) * H;
+        const float* wn = p.whh + (long)(2 * H + jc) * H;
+        f32x4 ar = {0.f, 0.f, 0.f, 0.f}, az = ar, an = ar;
+        // the step's input projections of this lane's four (row, unit) pairs, asked for before the k loop so that they arrive under it
+        float gr[4], gz[4], gn[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int b = min(4 * lq + r, nrow - 1);
+          const float* g = p.gi + ((long)(b0 + b) * p.T + t) * p.gip;
+          gr[r] = g[jc]; gz[r] = g[H + jc]; gn[r] = g[2 * H + jc];
+        }
+        // RNN_KU_FWD k blocks at a time (the enum says why it is 1 here): with more, their weight loads are in flight together before the
+        // first MFMA waits for one; a k block past the end multiplies zeros
+        for (int kb0 = 0; kb0 < KB; kb0 += RNN_KU_FWD) {
+          f32x4 a[RNN_KU_FWD], vr[RNN_KU_FWD], vz[RNN_KU_FWD], vn[RNN_KU_FWD];
+#pragma unroll
+          for (int u = 0; u < RNN_KU_FWD; ++u) {
+            const int k4 = (kb0 + u) * 16 + 4 * lq;
+            a[u] = vr[u] = vz[u] = vn[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (k4 < H) {                               // (H is a multiple of 4: a quad is inside or outside)
+              vr[u] = *(const f32x4*)(wr + k4);
+              vz[u] = *(const f32x4*)(wz + k4);
+              vn[u] = *(const f32x4*)(wn + k4);
+            }
+            if (kb0 + u < KB) a[u] = *(const f32x4*)&rnn_lds[li * HP + k4];
+          }
+#pragma unroll
+          for (int u = 0; u < RNN_KU_FWD; ++u) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+              ar = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][s], vr[u][s], ar, 0, 0, 0);      // D[batch row 4 q + r][unit i]
+              az = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][s], vz[u][s], az, 0, 0, 0);
+              an = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][s], vn[u][s], an, 0, 0, 0);
+            }
+          }
+        }
+        if (j < H) {
+          const float br = p.bhh[j], bz = p.bhh[H + j], bn = p.bhh[2 * H + j];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int b = 4 * lq + r;
+            if (b < nrow) {
+              const long row = (long)(b0 + b) * p.T + t;
+              const float hn = an[r] + bn;
+              const float rg = rnn_sigmoid(gr[r] + (ar[r] + br));
+              const float zg = rnn_sigmoid(gz[r] + (az[r] + bz));
+              const float ng = tanhf(gn[r] + rg * hn);
+              const float hprev = rnn_lds[b * HP + j];
+              const float hv = (1.f - zg) * ng + zg * hprev;
+              p.ho[row * p.hop + j] = hv;
+              if (p.r) {
+                const long o = row * p.sp + j;
+                p.r[o] = rg; p.z[o] = zg; p.n[o] = ng; p.hn[o] = hn; p.hp[o] = hprev;
+              }
+              hnew[it][r] = hv;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();                                    // every wave has read h_{t-1}
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int j = (wave + RNN_FWD_WAVES * it) * 16 + li;
+      if (j < H) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rnn_lds[(4 * lq + r) * HP + j] = hnew[it][r];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+struct RnnScanBP {
+  int rows, T, H;
+  const float* dout; int dop;        // [rows * T][H]: the gradient of h_t from the layer above
+  const float* whh;
+  const float *r, *z, *n, *hn, *hp; int sp;
+  float* dgi; float* dgh; int gp;    // [rows * T][3H]: gradients of the input-side and hidden-side pre-activations
+};
+
+// LDS: dGH_t of the block's 16 rows as [16][GP], GP = 16 ceil(3H / 16) + 4 (columns past 3H zero), and the carried dh as [16][H + 4].
+// Per step every thread first does the gate backward of its elements (dh_t = dout_t + carry; carry <- dh_t z), then the waves add
+// dGH_t W_hh to the carry.  W_hh's rows run along the OUTPUT units here, so a wave owns 64 units: lane i loads units 4 i .. 4 i + 3 of
+// row k with one dwordx4 and element e feeds accumulator e, whose column i is unit 64 g + 4 i + e.
+__global__ __launch_bounds__(64 * RNN_BWD_WAVES) void k_rnn_scan_bwd(RnnScanBP p) {
+  extern __shared__ __attribute__((aligned(16))) float rnn_lds[];
+  const int H = p.H, K3 = 3 * H, KB = (K3 + 15) >> 4, GP = KB * 16 + 4, CP = H + 4;
+  float* dg = rnn_lds;
+  float* carry = rnn_lds + RNN_RB * GP;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
+  const int b0 = blockIdx.x * RNN_RB;
+  const int nrow = min((int)RNN_RB, p.rows - b0);
+  for (int e = tid; e < RNN_RB * (GP + CP); e += 64 * RNN_BWD_WAVES) rnn_lds[e] = 0.f;
+  __syncthreads();
+  for (int t = p.T - 1; t >= 0; --t) {
+    // (read-only views: the loads of several elements may be issued before the first store)
+    const float* __restrict__ s_r = p.r; const float* __restrict__ s_z = p.z; const float* __restrict__ s_n = p.n;
+    const float* __restrict__ s_hn = p.hn; const float* __restrict__ s_hp = p.hp; const float* __restrict__ s_do = p.dout;
+#pragma unroll 4
+    for (int e = tid; e < RNN_RB * H; e += 64 * RNN_BWD_WAVES) {
+      const int b = e / H, j = e - b * H;
+      float gr = 0.f, gz = 0.f, gn = 0.f, gnr = 0.f, cz = 0.f;
+      if (b < nrow) {
+        const long row = (long)(b0 + b) * p.T + t;
+        const long o = row * p.sp + j;
+        const float dh = s_do[row * p.dop + j] + carry[b * CP + j];
+        const float rg = s_r[o], zg = s_z[o], ng = s_n[o], hn = s_hn[o], hprev = s_hp[o];
+        gn = dh * (1.f - zg) * (1.f - ng * ng);
+        gz = dh * (hprev - ng) * zg * (1.f - zg);
+        gr = gn * hn * rg * (1.f - rg);
+        gnr = gn * rg;
+        cz = dh * zg;
+        float* gi = p.dgi + row * p.gp;
+        float* gh = p.dgh + row * p.gp;
+        gi[j] = gr; gi[H + j] = gz; gi[2 * H + j] = gn;
+        gh[j] = gr; gh[H + j] = gz; gh[2 * H + j] = gnr;
+      }
+      dg[b * GP + j] = gr; dg[b * GP + H + j] = gz; dg[b * GP + 2 * H + j] = gnr;
+      carry[b * CP + j] = cz;
+    }
+    __syncthreads();
+    if (t > 0) {                                        // (dh_{-1} has no consumer)
+      for (int grp = wave; grp * 64 < H; grp += RNN_BWD_WAVES) {
+        const int jl = grp * 64 + 4 * li;
+        f32x4 acc[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kb0 = 0; kb0 < KB; kb0 += RNN_KU_BWD) {      // (RNN_KU_BWD k blocks of loads in flight together, as in the forward)
+          f32x4 a[RNN_KU_BWD], w[RNN_KU_BWD][4];
+#pragma unroll
+          for (int u = 0; u < RNN_KU_BWD; ++u) {
+            const int k4 = (kb0 + u) * 16 + 4 * lq;
+            a[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+              w[u][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+              if (k4 < K3 && jl < H) w[u][s] = *(const f32x4*)(p.whh + (long)(k4 + s) * H + jl);   // (3H and H are multiples of 4)
+            }
+            if (kb0 + u < KB) a[u] = *(const f32x4*)&dg[li * GP + k4];
+          }
+#pragma unroll
+          for (int u = 0; u < RNN_KU_BWD; ++u) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][s], w[u][s][e], acc[e], 0, 0, 0);
+            }
+          }
+        }
+        if (jl < H) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) carry[(4 * lq + r) * CP + jl + e] += acc[e][r];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- the small kernels of the tail ----
+// the step's sequences out of the data set: X0 [rows * T][xp], TGT [rows * T][od], MSK [rows * T]; a row index is clamped
+__global__ void k_rnn_gather(const float* __restrict__ inputs, const float* __restrict__ targets, const float* __restrict__ masks,
+                             const long long* __restrict__ idx, long n_data, int T, int in, int od, int rows, float* __restrict__ X0, int xp,
+                             float* __restrict__ TGT, float* __restrict__ MSK) {
+  const int per = in + od + 1;
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)rows * T * per) return;
+  const long row = e / per; const int c = (int)(e - row * per);
+  const long b = row / T; const int t = (int)(row - b * T);
+  const long g = min(max((long)idx[b], 0L), n_data - 1) * T + t;
+  if (c < in) X0[row * xp + c] = inputs[g * in + c];
+  else if (c < in + od) TGT[row * od + (c - in)] = targets[g * od + (c - in)];
+  else MSK[row] = masks[g];
+}
+// dst [rows][cols] (pitch dp) = src (pitch sp); step > 1: source row = r * step + (step - 1), the last time step of sequence r
+__global__ void k_rnn_copy(const float* __restrict__ src, int sp, float* __restrict__ dst, int dp, long rows, int cols, int step) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= rows * cols) return;
+  const long r = e / cols; const int c = (int)(e - r * cols);
+  dst[r * dp + c] = src[(r * step + (step - 1)) * sp + c];
+}
+// keep masks 1[u < 1 - p] of dropout `slot`: Philox keyed by the seed, counter = (step count, slot), (row, column quad)
+__global__ void k_rnn_mask(float* __restrict__ mk, long rows, int H, float keep, uint64_t seed, uint64_t kstep, uint32_t slot) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int q4 = H >> 2;
+  if (e >= rows * q4) return;
+  const long row = e / q4; const int q = (int)(e - row * q4);
+  uint32_t rnd[4];
+  const Philox ph(seed);
+  ph((uint32_t)row, (uint32_t)q, (uint32_t)kstep, (slot << 28) | (uint32_t)((kstep >> 32) & 0x0fffffffu), rnd);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) mk[row * H + 4 * q + k] = u01(rnd[k]) < keep ? 1.f : 0.f;
+}
+
+struct RnnNormP {
+  int rows, H;
+  const float* s; int sp;            // swish(Linear(x))
+  const float* mask; float scale;    // keep mask [rows][H] and 1 / (1 - p), or null
+  const float* res; int rp;          // the residual input or null
+  const float* gamma; const float* beta;
+  float* u; int up;                  // what the LayerNorm reads: res + dropout(s)
+  float* out; int op;
+  // backward
+  int nterm; const float* g[2]; int gpitch[2];    // dOut = the sum of the terms
+  const float* zpre; int zp;         // the Linear's output (Swish' argument)
+  float* du; int dup;                // the residual path's gradient or null
+  float* dz; int dzp;                // the Linear's output gradient
+  float* part; long pn;              // [row][pn]: dgamma at [c], dbeta at [H + c]
+};
+
+// LayerNorm statistics of one row in one wave (diffusion.hip's diff_group_stats with one group): mean, then the centred second moment
+__device__ __forceinline__ void rnn_row_stats(const float* u, int H, int lane, float (&v)[RNN_NJ], float& mean, float& rstd) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < RNN_NJ; ++j) {
+    const int c = lane + 64 * j;
+    v[j] = c < H ? u[c] : 0.f;
+    s += v[j];
+  }
+  mean = wave_sum(s) / (float)H;
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < RNN_NJ; ++j) {
+    const float dlt = (lane + 64 * j) < H ? v[j] - mean : 0.f;
+    q += dlt * dlt;
+  }
+  rstd = 1.f / sqrtf(wave_sum(q) / (float)H + 1e-5f);
+}
+
+// u = res + mask s / (1 - p); out = LayerNorm(u) (eps 1e-5, affine); one wave per row
+__global__ __launch_bounds__(64) void k_rnn_ln_fwd(RnnNormP p) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  if (row >= p.rows) return;
+#pragma unroll
+  for (int j = 0; j < RNN_NJ; ++j) {
+    const int c = lane + 64 * j;
+    if (c < p.H) {
+      float y = p.s[(long)row * p.sp + c];
+      if (p.mask) y = y * p.mask[(long)row * p.H + c] * p.scale;
+      if (p.res) y = p.res[(long)row * p.rp + c] + y;
+      p.u[(long)row * p.up + c] = y;
+    }
+  }
+  float v[RNN_NJ], mean, rstd;
+  rnn_row_stats(p.u + (long)row * p.up, p.H, lane, v, mean, rstd);     // (a lane reads back what it wrote itself)
+#pragma unroll
+  for (int j = 0; j < RNN_NJ; ++j) {
+    const int c = lane + 64 * j;
+    if (c < p.H) p.out[(long)row * p.op + c] = (v[j] - mean) * rstd * p.gamma[c] + p.beta[c];
+  }
+}
+
+// the backward of k_rnn_ln_fwd: du (to the residual input), dz = du mask / (1 - p) Swish'(z), and the row's dgamma / dbeta terms
+__global__ __launch_bounds__(64) void k_rnn_ln_bwd(RnnNormP p) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  if (row >= p.rows) return;
+  float v[RNN_NJ], mean, rstd;
+  rnn_row_stats(p.u + (long)row * p.up, p.H, lane, v, mean, rstd);
+  float dxh[RNN_NJ], xh[RNN_NJ];
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < RNN_NJ; ++j) {
+    const int c = lane + 64 * j;
+    dxh[j] = 0.f; xh[j] = 0.f;
+    if (c < p.H) {
+      float dy = p.g[0][(long)row * p.gpitch[0] + c];
+      if (p.nterm > 1) dy += p.g[1][(long)row * p.gpitch[1] + c];
+      xh[j] = (v[j] - mean) * rstd;
+      p.part[(long)row * p.pn + c] = dy * xh[j];
+      p.part[(long)row * p.pn + p.H + c] = dy;
+      dxh[j] = dy * p.gamma[c];
+      s1 += dxh[j];
+      s2 += dxh[j] * xh[j];
+    }
+  }
+  s1 = wave_sum(s1) / (float)p.H;
+  s2 = wave_sum(s2) / (float)p.H;
+#pragma unroll
+  for (int j = 0; j < RNN_NJ; ++j) {
+    const int c = lane + 64 * j;
+    if (c < p.H) {
+      const float du = rstd * (dxh[j] - s1 - xh[j] * s2);
+      if (p.du) p.du[(long)row * p.dup + c] = du;
+      float ds = du;
+      if (p.mask) ds = du * p.mask[(long)row * p.H + c] * p.scale;
+      p.dz[(long)row * p.dzp + c] = ds * rnn_dswish(p.zpre[(long)row * p.zp + c]);
+    }
+  }
+}
+
+// dz = (a + b) Swish'(z): the merge layer under the first residual block
+__global__ void k_rnn_swish_bwd(const float* __restrict__ a, int ap, const float* __restrict__ b, int bp, const float* __restrict__ z, int zp,
+                                float* __restrict__ dz, int dp, long rows, int cols) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= rows * cols) return;
+  const long r = e / cols; const int c = (int)(e - r * cols);
+  dz[r * dp + c] = (a[r * ap + c] + b[r * bp + c]) * rnn_dswish(z[r * zp + c]);
+}
+
+// first level: chunk sums of 64 rows each in row order, [chunks][pn]
+__global__ void k_rnn_colsum_part(const float* __restrict__ part, long pn, long rows, float* __restrict__ chunk) {
+  const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= pn) return;
+  const long r0 = (long)blockIdx.y * RNN_CHUNK, r1 = min(r0 + (long)RNN_CHUNK, rows);
+  float s = 0.f;
+  for (long r = r0; r < r1; ++r) s += part[r * pn + j];
+  chunk[(long)blockIdx.y * pn + j] = s;
+}
+struct RnnNormDst { long gamma[RNN_MAX_NORMS], beta[RNN_MAX_NORMS]; };
+// second level: the chunks in order, into the gradient block at each norm's gamma / beta
+__global__ void k_rnn_colsum_fin(const float* __restrict__ chunk, long pn, int chunks, int H, RnnNormDst dst, float* __restrict__ G) {
+  const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= pn) return;
+  float s = 0.f;
+  for (int c = 0; c < chunks; ++c) s += chunk[(long)c * pn + j];
+  const int slot = (int)(j / (2 * H)), c2 = (int)(j - (long)slot * 2 * H);
+  G[c2 < H ? dst.gamma[slot] + c2 : dst.beta[slot] + (c2 - H)] = s;
+}
+
+// loss = mean over rows of mask[row] mean_d (pred - target)^2; dPRED = 2 (pred - target) mask / (rows od); one block, fixed order
+__global__ __launch_bounds__(256) void k_rnn_loss(const float* __restrict__ pred, int pp, const float* __restrict__ tgt, const float* __restrict__ msk,
+                                                  long rows, int od, float* __restrict__ dpred, float* loss_out, float* loss_last) {
+  const long n = rows * od;
+  const float inv = 1.f / (float)n;
+  float s = 0.f;
+  for (long e = threadIdx.x; e < n; e += 256) {
+    const long r = e / od; const int d = (int)(e - r * od);
+    const float df = pred[r * pp + d] - tgt[e], m = msk[r];
+    s += df * df * m;
+    dpred[r * pp + d] = 2.f * df * m * inv;
+  }
+  s = block_sum256_pairwise(s);
+  if (threadIdx.x == 0) {
+    const float l = s * inv;
+    *loss_out = l;
+    *loss_last = l;
+  }
+}
+
+// G[i] = the slabs' sum in slab order: the k ranges of the split weight gradients (and slab 0's dgamma / dbeta)
+__global__ __launch_bounds__(256) void k_rnn_slab_sum(const float* __restrict__ slabs, long P, int n_slabs, float* __restrict__ G) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  float s = slabs[i];
+  for (int k = 1; k < n_slabs; ++k) s += slabs[(long)k * P + i];
+  G[i] = s;
+}
+
+// torch.optim.Adam (exp_avg lerp, exp_avg_sq, the bias corrections of step k + 1).  omb1 / omb2: 1 - beta formed in double on the host and
+// rounded once, as torch forms the scalars it passes to lerp_ and addcmul_ (1 - 0.999f is 1.3e-5 away from 0.001f)
+__global__ __launch_bounds__(256) void k_rnn_adam(float* __restrict__ params, float* __restrict__ m_, float* __restrict__ v_, const float* __restrict__ G,
+                                                  long P, float step, float bc2s, float omb1, float b2, float omb2, float eps) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  const float g = G[i];
+  const float m = m_[i] + (g - m_[i]) * omb1;
+  const float v = v_[i] * b2 + omb2 * g * g;
+  m_[i] = m; v_[i] = v;
+  params[i] = params[i] - step * (m / (sqrtf(v) / bc2s + eps));
+}
+
+}  // namespace orl
+
+using namespace orl;
+
+struct RnnLin { long w, b; };
+struct RnnNorm { long g, b; };
+// activations of one pass over `cap` rows (sequences x time steps); the backward's buffers when train
+struct RnnWs {
+  long cap = 0; bool train = false;
+  DevMat X0, SI, ZI, UI, CAT, M0, ZM, PRED;
+  std::vector<DevMat> GI, HO, R, Z, NN, HN, HP;       // per GRU layer
+  std::vector<DevMat> SB, ZB, UB, XO;                 // per residual block
+  float* MK = nullptr;                                // [norms][cap][H] keep masks
+  // backward
+  DevMat dPRED, dX, DU, DZ, DT, dZM, dCAT, dGI, dGH, dXL[2];
+  float *part = nullptr, *chunk = nullptr;
+};
+
+struct orl_rnn {
+  orl_rnn_config c;
+  int in, od, H, L, nb, B, Tmax, norms;
+  long P = 0;
+  RnnLin wih[RNN_MAX_LAYERS], whh[RNN_MAX_LAYERS], lin_in, lin_merge, lin_out, lin_b[ORL_MAX_HIDDEN];
+  RnnNorm norm_in, norm_b[ORL_MAX_HIDDEN];
+  TensorTable tensors;
+  hipStream_t stream = nullptr;
+  float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *grads = nullptr;
+  float* slabs = nullptr; int max_slabs = 1;      // [max_slabs][P]: the k ranges of the split weight gradients, summed into grads
+  long long kstep = 0;
+  size_t lds_fwd = 0, lds_bwd = 0;
+  // dataset
+  float *d_in = nullptr, *d_tgt = nullptr, *d_msk = nullptr; long n_data = 0; int T = 0;
+  RnnWs tw, ew;
+  float *TGT = nullptr, *MSK = nullptr, *loss_cell = nullptr, *loss_steps = nullptr; long loss_cap = 0;
+  long long* idx_d = nullptr; long idx_cap = 0;
+  // forward staging
+  float *fIn = nullptr, *fLast = nullptr, *fAll = nullptr; long f_cap = 0;
+  const RnnWs* last_ws = nullptr; long last_rows = 0;
+  // orl_rnn_profile: events of the last step -- 0 start, 1 after the forward, 2 after the backward, 3 after Adam, then per layer
+  // [before, after] of the forward scan and of the backward scan
+  bool prof = false, prof_valid = false;
+  hipEvent_t ev[4 + 4 * RNN_MAX_LAYERS] = {};
+  DevAllocs mem{"orl_rnn"};
+};
+
+static int rnn_mat(orl_rnn* d, DevMat& v, long rows, int cols) {
+  d->mem.free(v.p);
+  v.pitch = v.lim = rup4(cols);
+  return d->mem.alloc(&v.p, (size_t)rows * v.pitch);
+}
+
+static int rnn_ws_alloc(orl_rnn* d, RnnWs& w, long rows, bool train) {
+  const int H = d->H, L = d->L, nb = d->nb;
+  w.GI.resize(L); w.HO.resize(L); w.R.resize(L); w.Z.resize(L); w.NN.resize(L); w.HN.resize(L); w.HP.resize(L);
+  w.SB.resize(nb); w.ZB.resize(nb); w.UB.resize(nb); w.XO.resize(nb);
+  bool bad = rnn_mat(d, w.X0, rows, d->in) || rnn_mat(d, w.SI, rows, H) || rnn_mat(d, w.ZI, rows, H) || rnn_mat(d, w.UI, rows, H) ||
+             rnn_mat(d, w.CAT, rows, 2 * H) || rnn_mat(d, w.M0, rows, H) || rnn_mat(d, w.ZM, rows, H) || rnn_mat(d, w.PRED, rows, d->od);
+  for (int l = 0; l < L && !bad; ++l) {
+    bad = rnn_mat(d, w.GI[l], rows, 3 * H) || (l < L - 1 && rnn_mat(d, w.HO[l], rows, H));
+    if (l == L - 1) w.HO[l] = w.CAT.cols(H);          // the last layer writes the right half of the merge layer's input
+    if (train && !bad)
+      bad = rnn_mat(d, w.R[l], rows, H) || rnn_mat(d, w.Z[l], rows, H) || rnn_mat(d, w.NN[l], rows, H) || rnn_mat(d, w.HN[l], rows, H) ||
+            rnn_mat(d, w.HP[l], rows, H);
+  }
+  for (int i = 0; i < nb && !bad; ++i)
+    bad = rnn_mat(d, w.SB[i], rows, H) || rnn_mat(d, w.ZB[i], rows, H) || rnn_mat(d, w.UB[i], rows, H) || rnn_mat(d, w.XO[i], rows, H);
+  if (train && !bad) {
+    const long pn = (long)d->norms * 2 * H, chunks = (rows + RNN_CHUNK - 1) / RNN_CHUNK;
+    bad = rnn_mat(d, w.dPRED, rows, d->od) || rnn_mat(d, w.dX, rows, H) || rnn_mat(d, w.DU, rows, H) || rnn_mat(d, w.DZ, rows, H) ||
+          rnn_mat(d, w.DT, rows, H) || rnn_mat(d, w.dZM, rows, H) || rnn_mat(d, w.dCAT, rows, 2 * H) || rnn_mat(d, w.dGI, rows, 3 * H) ||
+          rnn_mat(d, w.dGH, rows, 3 * H) || rnn_mat(d, w.dXL[0], rows, H) || rnn_mat(d, w.dXL[1], rows, H) ||
+          (d->mem.free(w.MK), d->mem.alloc(&w.MK, (size_t)d->norms * rows * H)) ||
+          (d->mem.free(w.part), d->mem.alloc(&w.part, (size_t)rows * pn)) || (d->mem.free(w.chunk), d->mem.alloc(&w.chunk, (size_t)chunks * pn));
+  }
+  if (bad) return -1;
+  w.cap = rows; w.train = train;
+  return 0;
+}
+
+// ---- the matrix products (csrc/gemm.h), one problem per launch ----
+// few rows: 16 x 64 tiles while they give at most four rounds of workgroups on the 256 CUs, 64 x 64 beyond; many rows: the 64 x 256 tile
+static int rnn_cfg(int M, int N) {
+  if (N <= 16) return CFG_TALL;
+  if (M >= 2048 && N >= 128) return CFG_BIG;
+  const long small_tiles = (long)((M + 15) / 16) * ((N + 63) / 64);
+  return (M <= 32 || small_tiles <= 1024) ? CFG_SMALL : CFG_MID;
+}
+// the weight gradients reduce over every row of the step and have few output tiles: the smallest tile that still gives the CUs work
+static int rnn_wgrad_cfg(int M, int N) {
+  if (N <= 16) return CFG_TALL;
+  const long small_tiles = (long)((M + 15) / 16) * ((N + 63) / 64);
+  return small_tiles <= 1024 ? CFG_SMALL : CFG_MID;
+}
+static LinearP rnn_linear(float* block, const RnnLin& l, int in, int out) { return {{block + l.w, 0, 0}, {block + l.b, 0, 0}, in, out, false, 1}; }
+// Y = X W^T + b, or swish of it with the pre-activation kept in Z (same pitch as Y) when Z is given
+static int rnn_fwd(orl_rnn* d, const DevMat& X, int M, const RnnLin& l, int in, int out, const DevMat& Y, bool swish, float* Z) {
+  GemmP p = linear_fwd_p(X, M, rnn_linear(d->params, l, in, out), Y);
+  p.z_out = Z;
+  const bool kpad = X.pitch >= rup4(p.K);
+  const int cfg = rnn_cfg(p.M, p.N);
+  return gemm_done(swish ? launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_SWISH>(cfg, p, 1, d->stream, kpad, false, P_F32)
+                         : launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(cfg, p, 1, d->stream, kpad, false, P_F32), "orl_rnn forward");
+}
+// dX = dY W
+static int rnn_dgrad(orl_rnn* d, const DevMat& dY, int M, const RnnLin& l, int in, int out, const DevMat& dX) {
+  const GemmP p = linear_dgrad_p(dY, M, rnn_linear(d->params, l, in, out), dX);
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(rnn_cfg(p.M, p.N), p, 1, d->stream, dY.pitch >= rup4(p.K), false, P_F32), "orl_rnn dgrad");
+}
+// The weight gradients reduce over all rows * T rows of a step and have few output tiles (600 x 200 at the default shape), so the
+// reduction is cut into k ranges of at least 256 rows, each into a slab of its own; k_rnn_slab_sum adds the slabs in order.
+static int rnn_slabs(const orl_rnn* d, long N) { return (int)std::max(1L, std::min((long)d->max_slabs, N / 256)); }
+// dW = dY^T X ([out][in]) and db = the column sums of dY into the slabs
+static int rnn_wgrad(orl_rnn* d, const DevMat& dY, const DevMat& X, int M, const RnnLin& l, int in, int out) {
+  GemmP p = linear_wgrad_p(dY, X, M, rnn_linear(d->slabs, l, in, out));
+  p.ksplit = rnn_slabs(d, M); p.c_ks = d->P; p.bo_ks = d->P;
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(rnn_wgrad_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32), "orl_rnn wgrad");
+}
+
+static int rnn_ew_grid(long n) { return (int)((n + 255) / 256); }
+// the profile's event `i` on the stream when the step is being timed
+static void rnn_mark(orl_rnn* d, bool on, int i) {
+  if (on && d->prof) hipEventRecord(d->ev[i], d->stream);
+}
+
+static RnnNormP rnn_norm_params(orl_rnn* d, const RnnWs& w, int slot, long N, const DevMat& S, const DevMat& U, const RnnNorm& nm, bool drop) {
+  RnnNormP p;
+  memset(&p, 0, sizeof(p));
+  p.rows = (int)N; p.H = d->H;
+  p.s = S.p; p.sp = S.pitch;
+  if (drop) { p.mask = w.MK + (size_t)slot * w.cap * d->H; p.scale = 1.f / (1.f - d->c.dropout_rate); }
+  p.gamma = d->params + nm.g; p.beta = d->params + nm.b;
+  p.u = U.p; p.up = U.pitch;
+  return p;
+}
+
+// the forward over `rows` sequences of T steps of workspace w (X0 in place); train: the scans save what the backward reads, the
+// pre-activations are kept and the dropouts read the keep masks of w.MK
+static int rnn_forward(orl_rnn* d, RnnWs& w, int rows, int T, bool train) {
+  const int H = d->H;
+  const long N = (long)rows * T;
+  const bool drop = train && d->c.dropout_rate > 0.f;
+  DevMat X = w.X0;
+  for (int l = 0; l < d->L; ++l) {
+    if (rnn_fwd(d, X, (int)N, d->wih[l], l ? H : d->in, 3 * H, w.GI[l], false, nullptr)) return -1;
+    RnnScanP sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.rows = rows; sp.T = T; sp.H = H;
+    sp.gi = w.GI[l].p; sp.gip = w.GI[l].pitch;
+    sp.whh = d->params + d->whh[l].w; sp.bhh = d->params + d->whh[l].b;
+    sp.ho = w.HO[l].p; sp.hop = w.HO[l].pitch;
+    if (train) { sp.r = w.R[l].p; sp.z = w.Z[l].p; sp.n = w.NN[l].p; sp.hn = w.HN[l].p; sp.hp = w.HP[l].p; sp.sp = w.R[l].pitch; }
+    rnn_mark(d, train, 4 + 4 * l);
+    DEV_LAUNCH(d->stream, k_rnn_scan_fwd, dim3((rows + RNN_RB - 1) / RNN_RB), dim3(64 * RNN_FWD_WAVES), d->lds_fwd, sp);
+    rnn_mark(d, train, 5 + 4 * l);
+    X = w.HO[l];
+  }
+  if (rnn_fwd(d, w.X0, (int)N, d->lin_in, d->in, H, w.SI, true, train ? w.ZI.p : nullptr)) return -1;
+  RnnNormP n0 = rnn_norm_params(d, w, 0, N, w.SI, w.UI, d->norm_in, drop);
+  n0.out = w.CAT.p; n0.op = w.CAT.pitch;
+  DEV_LAUNCH(d->stream, k_rnn_ln_fwd, dim3((unsigned)N), dim3(64), 0, n0);
+  if (rnn_fwd(d, w.CAT, (int)N, d->lin_merge, 2 * H, H, w.M0, true, train ? w.ZM.p : nullptr)) return -1;
+  X = w.M0;
+  for (int i = 0; i < d->nb; ++i) {
+    if (rnn_fwd(d, X, (int)N, d->lin_b[i], H, H, w.SB[i], true, train ? w.ZB[i].p : nullptr)) return -1;
+    RnnNormP nb = rnn_norm_params(d, w, 1 + i, N, w.SB[i], w.UB[i], d->norm_b[i], drop);
+    nb.res = X.p; nb.rp = X.pitch;
+    nb.out = w.XO[i].p; nb.op = w.XO[i].pitch;
+    DEV_LAUNCH(d->stream, k_rnn_ln_fwd, dim3((unsigned)N), dim3(64), 0, nb);
+    X = w.XO[i];
+  }
+  return rnn_fwd(d, X, (int)N, d->lin_out, H, d->od, w.PRED, false, nullptr);
+}
+
+// backward from dPRED over the first rows * T rows of the training workspace
+static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
+  const int H = d->H;
+  const long N = (long)rows * T;
+  const long pn = (long)d->norms * 2 * H;
+  const bool drop = d->c.dropout_rate > 0.f;
+  const DevMat& last = w.XO[d->nb - 1];
+  if (rnn_wgrad(d, w.dPRED, last, (int)N, d->lin_out, H, d->od) || rnn_dgrad(d, w.dPRED, (int)N, d->lin_out, H, d->od, w.dX)) return -1;
+  // residual block i: dOut = dX (block nb - 1: the head's dgrad) or DU + DT of the block above
+  for (int i = d->nb - 1; i >= 0; --i) {
+    const DevMat& Xin = i ? w.XO[i - 1] : w.M0;
+    RnnNormP nb = rnn_norm_params(d, w, 1 + i, N, w.SB[i], w.UB[i], d->norm_b[i], drop);
+    if (i == d->nb - 1) { nb.nterm = 1; nb.g[0] = w.dX.p; nb.gpitch[0] = w.dX.pitch; }
+    else { nb.nterm = 2; nb.g[0] = w.DU.p; nb.gpitch[0] = w.DU.pitch; nb.g[1] = w.DT.p; nb.gpitch[1] = w.DT.pitch; }
+    nb.zpre = w.ZB[i].p; nb.zp = w.ZB[i].pitch;
+    nb.du = w.DU.p; nb.dup = w.DU.pitch;            // (a lane overwrites only the elements it has read itself)
+    nb.dz = w.DZ.p; nb.dzp = w.DZ.pitch;
+    nb.part = w.part + (long)(1 + i) * 2 * H; nb.pn = pn;
+    DEV_LAUNCH(d->stream, k_rnn_ln_bwd, dim3((unsigned)N), dim3(64), 0, nb);
+    if (rnn_wgrad(d, w.DZ, Xin, (int)N, d->lin_b[i], H, H) || rnn_dgrad(d, w.DZ, (int)N, d->lin_b[i], H, H, w.DT)) return -1;
+  }
+  DEV_LAUNCH(d->stream, k_rnn_swish_bwd, dim3(rnn_ew_grid(N * H)), dim3(256), 0, w.DU.p, w.DU.pitch, w.DT.p, w.DT.pitch, w.ZM.p, w.ZM.pitch,
+              w.dZM.p, w.dZM.pitch, N, H);
+  if (rnn_wgrad(d, w.dZM, w.CAT, (int)N, d->lin_merge, 2 * H, H) || rnn_dgrad(d, w.dZM, (int)N, d->lin_merge, 2 * H, H, w.dCAT)) return -1;
+  // the input block (no residual, no gradient to the net's input)
+  {
+    RnnNormP n0 = rnn_norm_params(d, w, 0, N, w.SI, w.UI, d->norm_in, drop);
+    n0.nterm = 1; n0.g[0] = w.dCAT.p; n0.gpitch[0] = w.dCAT.pitch;
+    n0.zpre = w.ZI.p; n0.zp = w.ZI.pitch;
+    n0.dz = w.DZ.p; n0.dzp = w.DZ.pitch;
+    n0.part = w.part; n0.pn = pn;
+    DEV_LAUNCH(d->stream, k_rnn_ln_bwd, dim3((unsigned)N), dim3(64), 0, n0);
+    if (rnn_wgrad(d, w.DZ, w.X0, (int)N, d->lin_in, d->in, H)) return -1;
+  }
+  {
+    const int chunks = (int)((N + RNN_CHUNK - 1) / RNN_CHUNK);
+    RnnNormDst dst;
+    memset(&dst, 0, sizeof(dst));
+    dst.gamma[0] = d->norm_in.g; dst.beta[0] = d->norm_in.b;
+    for (int i = 0; i < d->nb; ++i) { dst.gamma[1 + i] = d->norm_b[i].g; dst.beta[1 + i] = d->norm_b[i].b; }
+    DEV_LAUNCH(d->stream, k_rnn_colsum_part, dim3(rnn_ew_grid(pn), chunks), dim3(256), 0, w.part, pn, N, w.chunk);
+    DEV_LAUNCH(d->stream, k_rnn_colsum_fin, dim3(rnn_ew_grid(pn)), dim3(256), 0, w.chunk, pn, chunks, H, dst, d->slabs);
+  }
+  // the GRU layers top down: the top layer's dh is the right half of the merge layer's input gradient
+  DevMat dOut = w.dCAT.cols(H);
+  for (int l = d->L - 1; l >= 0; --l) {
+    RnnScanBP bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.rows = rows; bp.T = T; bp.H = H;
+    bp.dout = dOut.p; bp.dop = dOut.pitch;
+    bp.whh = d->params + d->whh[l].w;
+    bp.r = w.R[l].p; bp.z = w.Z[l].p; bp.n = w.NN[l].p; bp.hn = w.HN[l].p; bp.hp = w.HP[l].p; bp.sp = w.R[l].pitch;
+    bp.dgi = w.dGI.p; bp.dgh = w.dGH.p; bp.gp = w.dGI.pitch;
+    rnn_mark(d, true, 6 + 4 * l);
+    DEV_LAUNCH(d->stream, k_rnn_scan_bwd, dim3((rows + RNN_RB - 1) / RNN_RB), dim3(64 * RNN_BWD_WAVES), d->lds_bwd, bp);
+    rnn_mark(d, true, 7 + 4 * l);
+    const DevMat& Xl = l ? w.HO[l - 1] : w.X0;
+    if (rnn_wgrad(d, w.dGH, w.HP[l], (int)N, d->whh[l], H, 3 * H) || rnn_wgrad(d, w.dGI, Xl, (int)N, d->wih[l], l ? H : d->in, 3 * H)) return -1;
+    if (l == 0) break;
+    if (rnn_dgrad(d, w.dGI, (int)N, d->wih[l], H, 3 * H, w.dXL[l & 1])) return -1;
+    dOut = w.dXL[l & 1];
+  }
+  DEV_LAUNCH(d->stream, k_rnn_slab_sum, dim3(rnn_ew_grid(d->P)), dim3(256), 0, (const float*)d->slabs, d->P, rnn_slabs(d, N), d->grads);
+  return 0;
+}
+
+// one optimizer step on the sequences idx[0 .. rows) (device); the dropouts' keep masks are in tw.MK already when forced
+static int rnn_enqueue_step(orl_rnn* d, const long long* idx, int rows, bool forced_masks, float* loss_dst) {
+  RnnWs& w = d->tw;
+  const int T = d->T, H = d->H;
+  const long N = (long)rows * T;
+  rnn_mark(d, true, 0);
+  DEV_LAUNCH(d->stream, k_rnn_gather, dim3(rnn_ew_grid(N * (d->in + d->od + 1))), dim3(256), 0, d->d_in, d->d_tgt, d->d_msk, idx, d->n_data, T,
+              d->in, d->od, rows, w.X0.p, w.X0.pitch, d->TGT, d->MSK);
+  if (d->c.dropout_rate > 0.f && !forced_masks)
+    for (int s = 0; s < d->norms; ++s)
+      DEV_LAUNCH(d->stream, k_rnn_mask, dim3(rnn_ew_grid(N * (H / 4))), dim3(256), 0, w.MK + (size_t)s * w.cap * H, N, H, 1.f - d->c.dropout_rate,
+                  d->c.seed, (uint64_t)d->kstep, (uint32_t)s);
+  if (rnn_forward(d, w, rows, T, true)) return -1;
+  rnn_mark(d, true, 1);
+  DEV_LAUNCH(d->stream, k_rnn_loss, dim3(1), dim3(256), 0, w.PRED.p, w.PRED.pitch, d->TGT, d->MSK, N, d->od, w.dPRED.p, loss_dst, d->loss_cell);
+  if (rnn_backward(d, w, rows, T)) return -1;
+  rnn_mark(d, true, 2);
+  const double tt = (double)(d->kstep + 1);
+  const double bc1 = 1.0 - std::pow(d->c.adam_beta1, tt), bc2 = 1.0 - std::pow(d->c.adam_beta2, tt);
+  DEV_LAUNCH(d->stream, k_rnn_adam, dim3(rnn_ew_grid(d->P)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, d->P, (float)(d->c.lr / bc1),
+              (float)std::sqrt(bc2), (float)(1.0 - d->c.adam_beta1), (float)d->c.adam_beta2, (float)(1.0 - d->c.adam_beta2), (float)d->c.adam_eps);
+  rnn_mark(d, true, 3);
+  d->prof_valid = d->prof;
+  d->kstep += 1;
+  d->last_ws = &w; d->last_rows = N;
+  return 0;
+}
+
+static int rnn_ready(orl_rnn* d, const char* what, bool data) {
+  if (!d) return fail(std::string(what) + ": null handle");
+  if (data && !d->d_in) return fail(std::string(what) + ": no data loaded (orl_rnn_load_data)");
+  if (hipSetDevice(d->c.device) != hipSuccess) return fail(std::string(what) + ": hipSetDevice failed");
+  return 0;
+}
+
+// the refusals of a config; empty = supported
+static std::string rnn_refusal(const orl_rnn_config& c) {
+  if (c.n_runs != 1) return "one run per object (n_runs > 1 is not supported)";
+  if (c.precision != 0) return "precision 0 (fp32 MFMA) only; the split precisions are not supported";
+  if (c.input_dim < 1 || c.output_dim < 1) return "input_dim and output_dim must be positive";
+  if (c.n_hidden < 2 || c.n_hidden > ORL_MAX_HIDDEN + 1)
+    return "len(hidden_dims) must be in [2, " + std::to_string(ORL_MAX_HIDDEN + 1) + "]";
+  for (int i = 1; i < c.n_hidden; ++i)
+    if (c.hidden[i] != c.hidden[0]) return "all hidden_dims must be equal (the residual blocks add their input)";
+  if (c.hidden[0] < 8 || c.hidden[0] > RNN_MAX_H || (c.hidden[0] & 3)) return "the hidden width must be a multiple of 4 in [8, 512]";
+  if (c.rnn_num_layers < 1 || c.rnn_num_layers > RNN_MAX_LAYERS) return "rnn_num_layers must be in [1, 4]";
+  if (!(c.dropout_rate >= 0.f && c.dropout_rate < 1.f)) return "dropout_rate must be in [0, 1)";
+  if (c.batch_size < 1 || c.max_seq_len < 1) return "batch_size and max_seq_len must be positive";
+  if ((long)c.batch_size * c.max_seq_len > 0x7fffffffL / (8 * c.hidden[0] * (ORL_MAX_HIDDEN + 1)))
+    return "batch_size * max_seq_len rows are more than one step's matrices index";
+  if (!(c.lr > 0.0)) return "lr must be positive";
+  if (!(c.adam_beta1 >= 0.0 && c.adam_beta1 < 1.0 && c.adam_beta2 >= 0.0 && c.adam_beta2 < 1.0 && c.adam_eps >= 0.0)) return "Adam's betas must be in [0, 1) and eps non-negative";
+  return "";
+}
+
+// the layout of the parameter block: RNNModel.state_dict() order, every tensor on 4 floats
+static long rnn_layout(orl_rnn* d) {
+  TensorTable& t = d->tensors;
+  auto add = [&](const std::string& name, std::initializer_list<long> shape) { return t.add(name, shape, true, false); };
+  const long H = d->H;
+  for (int l = 0; l < d->L; ++l) {
+    const std::string k = std::to_string(l);
+    d->wih[l].w = add("rnn_layer.weight_ih_l" + k, {3 * H, l ? H : (long)d->in});
+    d->whh[l].w = add("rnn_layer.weight_hh_l" + k, {3 * H, H});
+    d->wih[l].b = add("rnn_layer.bias_ih_l" + k, {3 * H});
+    d->whh[l].b = add("rnn_layer.bias_hh_l" + k, {3 * H});
+  }
+  d->lin_in.w = add("input_layer.linear.weight", {H, (long)d->in});
+  d->lin_in.b = add("input_layer.linear.bias", {H});
+  d->norm_in.g = add("input_layer.layer_norm.weight", {H});
+  d->norm_in.b = add("input_layer.layer_norm.bias", {H});
+  for (int i = 0; i < d->nb; ++i) {
+    const std::string k = "backbones." + std::to_string(i);
+    d->lin_b[i].w = add(k + ".linear.weight", {H, H});
+    d->lin_b[i].b = add(k + ".linear.bias", {H});
+    d->norm_b[i].g = add(k + ".layer_norm.weight", {H});
+    d->norm_b[i].b = add(k + ".layer_norm.bias", {H});
+  }
+  d->lin_merge.w = add("merge_layer.weight", {H, 2 * H});
+  d->lin_merge.b = add("merge_layer.bias", {H});
+  d->lin_out.w = add("output_layer.weight", {(long)d->od, H});
+  d->lin_out.b = add("output_layer.bias", {(long)d->od});
+  return t.align4();
+}
+
+static void rnn_dims(orl_rnn* d, const orl_rnn_config& c) {
+  d->c = c;
+  d->in = c.input_dim; d->od = c.output_dim; d->H = c.hidden[0]; d->L = c.rnn_num_layers; d->nb = c.n_hidden - 1;
+  d->norms = d->nb + 1; d->B = c.batch_size; d->Tmax = c.max_seq_len;
+  d->P = rnn_layout(d);
+}
+
+extern "C" {
+
+void orl_rnn_config_default(orl_rnn_config* c) {
+  memset(c, 0, sizeof(*c));
+  c->input_dim = 14; c->output_dim = 12; c->n_hidden = 4;
+  for (int i = 0; i < 4; ++i) c->hidden[i] = 200;
+  c->rnn_num_layers = 3; c->dropout_rate = 0.1f; c->batch_size = 256; c->max_seq_len = 20; c->lr = 1e-3;
+  c->adam_beta1 = 0.9; c->adam_beta2 = 0.999; c->adam_eps = 1e-8;
+  c->n_runs = 1; c->device = 0; c->precision = 0; c->seed = 0; c->external_arena = nullptr;
+}
+
+int64_t orl_rnn_config_floats(const orl_rnn_config* cfg) {
+  if (!cfg) return fail("orl_rnn_config_floats: null argument");
+  const std::string why = rnn_refusal(*cfg);
+  if (!why.empty()) return fail("orl_rnn_config_floats: " + why);
+  orl_rnn tmp;
+  rnn_dims(&tmp, *cfg);
+  return tmp.P;
+}
+
+int orl_rnn_create(const orl_rnn_config* cfg, orl_rnn** out) {
+  if (!cfg || !out) return fail("orl_rnn_create: null argument");
+  *out = nullptr;
+  const orl_rnn_config& c = *cfg;
+  const std::string why = rnn_refusal(c);
+  if (!why.empty()) return fail("orl_rnn_create: " + why);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("orl_rnn_create: no HIP device (MI355X) visible");
+  if (c.device < 0 || c.device >= ndev) return fail("orl_rnn_create: device ordinal out of range");
+  if (hipSetDevice(c.device) != hipSuccess) return fail("orl_rnn_create: hipSetDevice failed");
+  if (c.external_arena && (((uintptr_t)c.external_arena) & 15)) return fail("orl_rnn_create: external_arena must be 16-byte aligned");
+  orl_rnn* d = new orl_rnn();
+  rnn_dims(d, c);
+  const int H = d->H;
+  d->lds_fwd = sizeof(float) * RNN_RB * (size_t)(((H + 15) / 16) * 16 + 4);
+  d->lds_bwd = sizeof(float) * RNN_RB * (size_t)(((3 * H + 15) / 16) * 16 + 4 + H + 4);
+  bool bad = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess;
+  if (!bad && d->lds_bwd > 64 * 1024)
+    bad = hipFuncSetAttribute((const void*)k_rnn_scan_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->lds_bwd) != hipSuccess;
+  if (c.external_arena) d->params = (float*)c.external_arena;
+  else bad = bad || d->mem.alloc(&d->params, d->P);
+  const long cap = (long)d->B * d->Tmax;
+  d->max_slabs = (int)std::max(1L, std::min({8L, cap / 256, (64L << 20) / d->P}));
+  bad = bad || d->mem.alloc(&d->slabs, (size_t)d->max_slabs * d->P) || d->mem.alloc(&d->adam_m, d->P) || d->mem.alloc(&d->adam_v, d->P) || d->mem.alloc(&d->grads, d->P) ||
+        rnn_ws_alloc(d, d->tw, cap, true) || d->mem.alloc(&d->TGT, (size_t)cap * d->od) || d->mem.alloc(&d->MSK, (size_t)cap) ||
+        d->mem.alloc(&d->loss_cell, 1);
+  if (bad) {
+    const std::string msg = orl_last_error();
+    orl_rnn_destroy(d);
+    return fail(msg.empty() ? "orl_rnn_create: allocation failed" : msg);
+  }
+  *out = d;
+  return 0;
+}
+
+void orl_rnn_destroy(orl_rnn* d) {
+  if (!d) return;
+  if (d->stream) hipStreamSynchronize(d->stream);
+  for (hipEvent_t e : d->ev)
+    if (e) hipEventDestroy(e);
+  d->mem.free_all();
+  if (d->stream) hipStreamDestroy(d->stream);
+  delete d;
+}
+
+int64_t orl_rnn_floats(orl_rnn* d) { return d ? d->P : -1; }
+int orl_rnn_num_tensors(orl_rnn* d) { return d ? (int)d->tensors.size() : -1; }
+int orl_rnn_tensor(orl_rnn* d, int idx, char* name, int name_cap, int64_t* offset, int32_t* ndim, int64_t shape[4]) {
+  if (!d || d->tensors.query(idx, name, name_cap, offset, ndim, shape)) return fail("orl_rnn_tensor: index out of range");
+  return 0;
+}
+
+static float* rnn_block_of(orl_rnn* d, int which) { return which == 0 ? d->params : which == 1 ? d->adam_m : which == 2 ? d->adam_v : nullptr; }
+int orl_rnn_set(orl_rnn* d, int which, const float* host, int64_t n) {
+  if (!d || !host || !rnn_block_of(d, which)) return fail("orl_rnn_set: bad arguments");
+  if (n != d->P) return fail("orl_rnn_set: expected " + std::to_string(d->P) + " floats");
+  return block_from_host(d->stream, rnn_block_of(d, which), host, d->P);
+}
+int orl_rnn_get(orl_rnn* d, int which, float* host, int64_t n) {
+  if (!d || !host || !rnn_block_of(d, which)) return fail("orl_rnn_get: bad arguments");
+  if (n != d->P) return fail("orl_rnn_get: expected " + std::to_string(d->P) + " floats");
+  return block_to_host(d->stream, host, rnn_block_of(d, which), d->P);
+}
+int orl_rnn_set_step_count(orl_rnn* d, int64_t k) {
+  if (!d || k < 0) return fail("orl_rnn_set_step_count: bad arguments");
+  d->kstep = k;
+  return 0;
+}
+int64_t orl_rnn_step_count(orl_rnn* d) { return d ? d->kstep : -1; }
+
+int orl_rnn_load_data(orl_rnn* d, const float* inputs, const float* targets, const float* masks, int64_t n, int32_t T) {
+  if (rnn_ready(d, "orl_rnn_load_data", false)) return -1;
+  if (!inputs || !targets || !masks || n < 1) return fail("orl_rnn_load_data: bad arguments");
+  if (T < 1 || T > d->Tmax) return fail("orl_rnn_load_data: need 1 <= T <= max_seq_len (" + std::to_string(d->Tmax) + ")");
+  if (n > 0x7fffffffffffLL / ((int64_t)T * (d->in + d->od))) return fail("orl_rnn_load_data: too many sequences");
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  d->mem.release(&d->d_in, &d->d_tgt, &d->d_msk);
+  d->n_data = 0;
+  const size_t rows = (size_t)n * T;
+  if (d->mem.alloc(&d->d_in, rows * d->in) || d->mem.alloc(&d->d_tgt, rows * d->od) || d->mem.alloc(&d->d_msk, rows)) return -1;
+  ORL_HIP(hipMemcpy(d->d_in, inputs, sizeof(float) * rows * d->in, hipMemcpyHostToDevice));
+  ORL_HIP(hipMemcpy(d->d_tgt, targets, sizeof(float) * rows * d->od, hipMemcpyHostToDevice));
+  ORL_HIP(hipMemcpy(d->d_msk, masks, sizeof(float) * rows, hipMemcpyHostToDevice));
+  d->n_data = n; d->T = T;
+  return 0;
+}
+
+int orl_rnn_step(orl_rnn* d, const int64_t* idx, int32_t rows, const float* drop_masks, float* loss_out) {
+  if (rnn_ready(d, "orl_rnn_step", true)) return -1;
+  if (!idx || rows < 1 || rows > d->B) return fail("orl_rnn_step: need 1 <= rows <= batch_size row indices");
+  for (int i = 0; i < rows; ++i)
+    if (idx[i] < 0 || idx[i] >= d->n_data) return fail("orl_rnn_step: row index out of range");
+  if (d->mem.grow(&d->idx_d, &d->idx_cap, d->B, d->stream)) return -1;
+  ORL_HIP(hipMemcpyAsync(d->idx_d, idx, sizeof(int64_t) * rows, hipMemcpyHostToDevice, d->stream));
+  const bool forced = drop_masks && d->c.dropout_rate > 0.f;
+  if (forced) {
+    const size_t per = (size_t)rows * d->T * d->H;
+    for (int s = 0; s < d->norms; ++s)
+      ORL_HIP(hipMemcpyAsync(d->tw.MK + (size_t)s * d->tw.cap * d->H, drop_masks + s * per, sizeof(float) * per, hipMemcpyHostToDevice, d->stream));
+  }
+  if (rnn_enqueue_step(d, d->idx_d, rows, forced, d->loss_cell)) return -1;
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  if (loss_out) ORL_HIP(hipMemcpy(loss_out, d->loss_cell, sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int orl_rnn_learn_epoch(orl_rnn* d, const int64_t* order, int64_t n_rows, int on_device, float* losses_out) {
+  if (rnn_ready(d, "orl_rnn_learn_epoch", true)) return -1;
+  if (!order || n_rows < 1) return fail("orl_rnn_learn_epoch: bad arguments");
+  if (!on_device)
+    for (int64_t i = 0; i < n_rows; ++i)
+      if (order[i] < 0 || order[i] >= d->n_data) return fail("orl_rnn_learn_epoch: row index out of range");
+  const long steps = (long)((n_rows + d->B - 1) / d->B);
+  if (d->mem.grow(&d->idx_d, &d->idx_cap, std::max<long>((long)n_rows, d->B), d->stream)) return -1;
+  if (d->mem.grow(&d->loss_steps, &d->loss_cap, steps, d->stream)) return -1;
+  ORL_HIP(hipMemcpyAsync(d->idx_d, order, sizeof(int64_t) * n_rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
+  for (long s = 0; s < steps; ++s) {
+    const int rows = (int)std::min<int64_t>(d->B, n_rows - s * d->B);
+    if (rnn_enqueue_step(d, d->idx_d + s * d->B, rows, false, d->loss_steps + s)) return -1;
+  }
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  if (losses_out) ORL_HIP(hipMemcpy(losses_out, d->loss_steps, sizeof(float) * steps, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int orl_rnn_forward(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, float* out_last, float* out_all) {
+  if (rnn_ready(d, "orl_rnn_forward", false)) return -1;
+  if (!inputs || !out_last || n < 1) return fail("orl_rnn_forward: bad arguments");
+  if (T < 1 || T > d->Tmax) return fail("orl_rnn_forward: need 1 <= T <= max_seq_len (" + std::to_string(d->Tmax) + ")");
+  if (n > 0x7fffffffL / ((int64_t)T * 8 * d->H)) return fail("orl_rnn_forward: too many sequences for one call");
+  const long N = (long)n * T;
+  if (N > d->f_cap) {
+    ORL_HIP(hipStreamSynchronize(d->stream));
+    d->mem.release(&d->fIn, &d->fLast, &d->fAll);
+    d->f_cap = 0;
+    if (d->last_ws == &d->ew) d->last_ws = nullptr;
+    if (d->mem.alloc(&d->fIn, (size_t)N * d->in) || d->mem.alloc(&d->fLast, (size_t)n * d->od) || d->mem.alloc(&d->fAll, (size_t)N * d->od) ||
+        rnn_ws_alloc(d, d->ew, N, false))
+      return -1;
+    d->f_cap = N;
+  }
+  RnnWs& w = d->ew;
+  const float* in_d = inputs;
+  if (stage_in(d->stream, in_d, d->fIn, (size_t)N * d->in, on_device)) return -1;
+  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid(N * d->in)), dim3(256), 0, in_d, d->in, w.X0.p, w.X0.pitch, N, d->in, 1);
+  if (rnn_forward(d, w, (int)n, T, false)) return -1;
+  float* last = stage_dst(out_last, d->fLast, on_device);
+  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid((long)n * d->od)), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, last, d->od, (long)n, d->od, (int)T);
+  if (stage_out(d->stream, out_last, d->fLast, (size_t)n * d->od, on_device)) return -1;
+  if (out_all) {
+    float* all = stage_dst(out_all, d->fAll, on_device);
+    DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid(N * d->od)), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, all, d->od, N, d->od, 1);
+    if (stage_out(d->stream, out_all, d->fAll, (size_t)N * d->od, on_device)) return -1;
+  }
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  d->last_ws = &w; d->last_rows = N;
+  return 0;
+}
+
+// "<prefix><k>" with 0 <= k < count; -1 otherwise
+static int rnn_tap_index(const std::string& nm, const char* prefix, int count) {
+  const size_t n = strlen(prefix);
+  if (nm.compare(0, n, prefix) != 0) return -1;
+  const std::string num = nm.substr(n);
+  if (num.size() != 1 || num[0] < '0' || num[0] > '9') return -1;
+  const int k = num[0] - '0';
+  return k < count ? k : -1;
+}
+
+int64_t orl_rnn_debug_read(orl_rnn* d, const char* name, float* host, int64_t cap) {
+  if (!d || !name || !host) return fail("orl_rnn_debug_read: bad arguments");
+  const std::string nm(name);
+  const RnnWs* w = d->last_ws ? d->last_ws : &d->tw;          // (names are resolved before "nothing recorded": an unknown one is always refused)
+  const float* src = nullptr; long rows = d->last_rows; int cols = d->H, pitch = d->H, k;
+  if (nm == "loss") { src = d->loss_cell; rows = 1; cols = 1; pitch = 1; }
+  else if (nm == "pred") { src = w->PRED.p; cols = d->od; pitch = w->PRED.pitch; }
+  else if (nm == "in") { src = w->CAT.p; pitch = w->CAT.pitch; }
+  else if (nm == "merge") { src = w->M0.p; pitch = w->M0.pitch; }
+  else if ((k = rnn_tap_index(nm, "gru.", d->L)) >= 0) { src = w->HO[k].p; pitch = w->HO[k].pitch; }
+  else if ((k = rnn_tap_index(nm, "block.", d->nb)) >= 0) { src = w->XO[k].p; pitch = w->XO[k].pitch; }
+  else if ((k = rnn_tap_index(nm, "act.", d->norms)) >= 0) { const DevMat& m = k ? w->SB[k - 1] : w->SI; src = m.p; pitch = m.pitch; }
+  else if ((k = rnn_tap_index(nm, "drop.", d->norms)) >= 0) { const DevMat& m = k ? w->UB[k - 1] : w->UI; src = m.p; pitch = m.pitch; }
+  else if ((k = rnn_tap_index(nm, "mask.", d->norms)) >= 0) {
+    if (!w->train || !(d->c.dropout_rate > 0.f)) return fail("orl_rnn_debug_read: no dropout mask was applied");
+    src = w->MK + (size_t)k * w->cap * d->H;
+  }
+  else return fail("orl_rnn_debug_read: unknown tap " + nm);
+  if (!src || rows < 1 || (!d->last_ws && nm != "loss")) return fail("orl_rnn_debug_read: nothing recorded for " + nm);
+  if ((int64_t)rows * cols > cap) return fail("orl_rnn_debug_read: " + nm + " needs " + std::to_string(rows * cols) + " floats");
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpy2D(host, sizeof(float) * cols, src, sizeof(float) * pitch, sizeof(float) * cols, rows, hipMemcpyDeviceToHost));
+  return (int64_t)rows * cols;
+}
+int orl_rnn_profile(orl_rnn* d, int enable) {
+  if (rnn_ready(d, "orl_rnn_profile", false)) return -1;
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  if (enable)
+    for (hipEvent_t& e : d->ev)
+      if (!e) ORL_HIP(hipEventCreate(&e));
+  d->prof = enable != 0;
+  d->prof_valid = false;
+  return 0;
+}
+int orl_rnn_profile_read(orl_rnn* d, float ms[6]) {
+  if (!d || !ms) return fail("orl_rnn_profile_read: bad arguments");
+  if (!d->prof_valid) return fail("orl_rnn_profile_read: no timed step (orl_rnn_profile, then a step)");
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipEventElapsedTime(&ms[0], d->ev[0], d->ev[3]));
+  ORL_HIP(hipEventElapsedTime(&ms[1], d->ev[0], d->ev[1]));
+  ORL_HIP(hipEventElapsedTime(&ms[3], d->ev[1], d->ev[2]));
+  ORL_HIP(hipEventElapsedTime(&ms[5], d->ev[2], d->ev[3]));
+  ms[2] = ms[4] = 0.f;
+  for (int l = 0; l < d->L; ++l) {
+    float f = 0.f, b = 0.f;
+    ORL_HIP(hipEventElapsedTime(&f, d->ev[4 + 4 * l], d->ev[5 + 4 * l]));
+    ORL_HIP(hipEventElapsedTime(&b, d->ev[6 + 4 * l], d->ev[7 + 4 * l]));
+    ms[2] += f; ms[4] += b;
+  }
+  return 0;
+}
+int orl_rnn_debug_grads(orl_rnn* d, float* host, int64_t n) {
+  if (!d || !host || n != d->P) return fail("orl_rnn_debug_grads: bad arguments");
+  return block_to_host(d->stream, host, d->grads, d->P);
+}
+
+}  // extern "C"

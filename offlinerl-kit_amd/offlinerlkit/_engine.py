@@ -72,6 +72,10 @@ ABI_SYMBOLS = [
     "orl_diffusion_tensor", "orl_diffusion_set", "orl_diffusion_get", "orl_diffusion_set_step_count", "orl_diffusion_step_count",
     "orl_diffusion_set_schedule", "orl_diffusion_set_lr", "orl_diffusion_attach_buffer", "orl_diffusion_step", "orl_diffusion_learn_epoch",
     "orl_diffusion_sample", "orl_diffusion_debug_read", "orl_diffusion_debug_grads",
+    # RNNDynamics: the GRU sequence dynamics model
+    "orl_rnn_config_default", "orl_rnn_config_floats", "orl_rnn_create", "orl_rnn_destroy", "orl_rnn_floats", "orl_rnn_num_tensors",
+    "orl_rnn_tensor", "orl_rnn_set", "orl_rnn_get", "orl_rnn_set_step_count", "orl_rnn_step_count", "orl_rnn_load_data", "orl_rnn_step",
+    "orl_rnn_learn_epoch", "orl_rnn_forward", "orl_rnn_debug_read", "orl_rnn_debug_grads", "orl_rnn_profile", "orl_rnn_profile_read",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -124,6 +128,16 @@ class OrlDiffusionConfig(C.Structure):
         ("num_diffusion_iters", C.c_int32), ("batch_size", C.c_int32),
         ("adam_beta1", C.c_float), ("adam_beta2", C.c_float), ("adam_eps", C.c_float),
         ("n_runs", C.c_int32), ("device", C.c_int32), ("precision", C.c_int32), ("seed", C.c_uint64),
+    ]
+
+
+class OrlRnnConfig(C.Structure):
+    _fields_ = [
+        ("input_dim", C.c_int32), ("output_dim", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * (MAX_HIDDEN + 1)),
+        ("rnn_num_layers", C.c_int32), ("dropout_rate", C.c_float), ("batch_size", C.c_int32), ("max_seq_len", C.c_int32),
+        ("lr", C.c_double), ("adam_beta1", C.c_double), ("adam_beta2", C.c_double), ("adam_eps", C.c_double),
+        ("n_runs", C.c_int32), ("device", C.c_int32), ("precision", C.c_int32), ("seed", C.c_uint64),
+        ("external_arena", C.c_void_p),
     ]
 
 
@@ -296,6 +310,7 @@ def load_library(path: Optional[str] = None):
                                       C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _bind_dynamics(lib)
     _bind_diffusion(lib)
+    _bind_rnn(lib)
     if path is None:
         _lib = lib
     return lib
@@ -364,6 +379,35 @@ def _bind_diffusion(lib) -> None:
     lib.orl_diffusion_debug_read.argtypes = [P, C.c_char_p, VP, I64]
     lib.orl_diffusion_debug_read.restype = I64
     lib.orl_diffusion_debug_grads.argtypes = [P, VP, I64]
+
+
+def _bind_rnn(lib) -> None:
+    P, I64, VP = C.c_void_p, C.c_int64, C.c_void_p
+    lib.orl_rnn_config_default.argtypes = [C.POINTER(OrlRnnConfig)]
+    lib.orl_rnn_config_default.restype = None
+    lib.orl_rnn_config_floats.argtypes = [C.POINTER(OrlRnnConfig)]
+    lib.orl_rnn_config_floats.restype = I64
+    lib.orl_rnn_create.argtypes = [C.POINTER(OrlRnnConfig), C.POINTER(C.c_void_p)]
+    lib.orl_rnn_destroy.argtypes = [P]
+    lib.orl_rnn_destroy.restype = None
+    lib.orl_rnn_floats.argtypes = [P]
+    lib.orl_rnn_floats.restype = I64
+    lib.orl_rnn_num_tensors.argtypes = [P]
+    lib.orl_rnn_tensor.argtypes = [P, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    lib.orl_rnn_set.argtypes = [P, C.c_int, VP, I64]
+    lib.orl_rnn_get.argtypes = [P, C.c_int, VP, I64]
+    lib.orl_rnn_set_step_count.argtypes = [P, I64]
+    lib.orl_rnn_step_count.argtypes = [P]
+    lib.orl_rnn_step_count.restype = I64
+    lib.orl_rnn_load_data.argtypes = [P, VP, VP, VP, I64, C.c_int32]
+    lib.orl_rnn_step.argtypes = [P, VP, C.c_int32, VP, C.POINTER(C.c_float)]
+    lib.orl_rnn_learn_epoch.argtypes = [P, VP, I64, C.c_int, VP]
+    lib.orl_rnn_forward.argtypes = [P, VP, I64, C.c_int32, C.c_int, VP, VP]
+    lib.orl_rnn_debug_read.argtypes = [P, C.c_char_p, VP, I64]
+    lib.orl_rnn_debug_read.restype = I64
+    lib.orl_rnn_debug_grads.argtypes = [P, VP, I64]
+    lib.orl_rnn_profile.argtypes = [P, C.c_int]
+    lib.orl_rnn_profile_read.argtypes = [P, C.POINTER(C.c_float)]
 
 
 def split_bits() -> int:
@@ -1512,3 +1556,145 @@ class Diffusion(_Handle):
         flat = np.empty(self.floats, np.float32)
         _check(self.lib.orl_diffusion_debug_grads(self._h, flat.ctypes.data, flat.size), "orl_diffusion_debug_grads")
         return flat
+
+
+def default_rnn_config(**over) -> OrlRnnConfig:
+    def hidden(cfg, v):
+        if len(v) > MAX_HIDDEN + 1:
+            raise NotImplementedError(f"the HIP engine supports up to {MAX_HIDDEN + 1} hidden_dims in RNNModel, got {len(v)}")
+        _fill("n_hidden", "hidden", int)(cfg, v)
+    cfg = OrlRnnConfig()
+    load_library().orl_rnn_config_default(C.byref(cfg))
+    return _override(cfg, over, "rnn", {"hidden": hidden})
+
+
+def rnn_config_floats(cfg: OrlRnnConfig) -> int:
+    """floats of the parameter block ``cfg`` needs (what ``external_arena`` must hold); an unsupported config raises"""
+    n = int(load_library().orl_rnn_config_floats(C.byref(cfg)))
+    if n < 0:
+        raise RuntimeError(f"orl_rnn_config_floats failed: {last_error()}")
+    return n
+
+
+class RnnDynamicsEngine(_Handle):
+    """RAII wrapper over ``orl_rnn*``: RNNModel (GRU + residual LayerNorm blocks) with its masked-MSE training step and its eval
+    forward on the device.  Sequence arrays are ``[rows, T, cols]``; parameter blocks travel as flat float32 arrays laid out by
+    ``tensors()``."""
+    PARAMS, EXP_AVG, EXP_AVG_SQ = 0, 1, 2
+    _destroy = "orl_rnn_destroy"
+
+    def __init__(self, cfg: OrlRnnConfig):
+        super().__init__()
+        self.cfg = cfg
+        _check(self.lib.orl_rnn_create(C.byref(cfg), C.byref(self._h)), "orl_rnn_create")
+        self.floats = int(self.lib.orl_rnn_floats(self._h))
+        self.T = 0
+
+    def tensors(self):
+        """[(state_dict name, offset, shape)] in RNNModel.state_dict() order"""
+        return _read_tensors(self.lib.orl_rnn_num_tensors, self.lib.orl_rnn_tensor, self._h, what="orl_rnn_tensor")
+
+    def set(self, which: int, flat):
+        flat = _f32(flat).ravel()
+        _check(self.lib.orl_rnn_set(self._h, which, flat.ctypes.data, flat.size), "orl_rnn_set")
+
+    def get(self, which: int) -> np.ndarray:
+        flat = np.empty(self.floats, np.float32)
+        _check(self.lib.orl_rnn_get(self._h, which, flat.ctypes.data, flat.size), "orl_rnn_get")
+        return flat
+
+    def set_params(self, params: Dict):
+        self.set(self.PARAMS, _flatten(self.tensors(), params, self.floats))
+
+    def get_params(self) -> Dict[str, np.ndarray]:
+        return _unflatten(self.tensors(), self.get(self.PARAMS))
+
+    @property
+    def step_count(self) -> int:
+        return int(self.lib.orl_rnn_step_count(self._h))
+
+    @step_count.setter
+    def step_count(self, k: int):
+        _check(self.lib.orl_rnn_set_step_count(self._h, int(k)), "orl_rnn_set_step_count")
+
+    def load_data(self, inputs, targets, masks):
+        inputs, targets, masks = _f32(inputs), _f32(targets), _f32(masks)
+        n, T = int(inputs.shape[0]), int(inputs.shape[1])
+        assert inputs.shape == (n, T, int(self.cfg.input_dim)) and targets.shape == (n, T, int(self.cfg.output_dim))
+        assert masks.size == n * T
+        _check(self.lib.orl_rnn_load_data(self._h, inputs.ctypes.data, targets.ctypes.data, masks.ctypes.data, n, T), "orl_rnn_load_data")
+        self.T = T
+
+    def step(self, idx, drop_masks=None) -> float:
+        """one optimizer step on the sequences ``idx``; ``drop_masks`` [len(hidden), rows * T, H] teacher-forces the dropouts' keep masks"""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).ravel()
+        mp = None
+        if drop_masks is not None:
+            drop_masks = _f32(drop_masks)
+            assert drop_masks.size == int(self.cfg.n_hidden) * idx.size * self.T * int(self.cfg.hidden[0])
+            mp = drop_masks.ctypes.data
+        loss = C.c_float()
+        _check(self.lib.orl_rnn_step(self._h, idx.ctypes.data, idx.size, mp, C.byref(loss)), "orl_rnn_step")
+        return float(loss.value)
+
+    def learn_epoch(self, order) -> np.ndarray:
+        """one loss per step; ``order``: an int64 array or a contiguous int64 torch tensor on the engine's device"""
+        if _is_tensor(order):
+            import torch
+            assert order.dtype == torch.int64 and order.is_contiguous() and order.device.type == "cuda"
+            torch.cuda.current_stream(order.device).synchronize()
+            n, ptr, dev = int(order.numel()), order.data_ptr(), 1
+        else:
+            order = np.ascontiguousarray(order, dtype=np.int64).ravel()
+            n, ptr, dev = order.size, order.ctypes.data, 0
+        B = int(self.cfg.batch_size)
+        losses = np.empty((n + B - 1) // B, np.float32)
+        _check(self.lib.orl_rnn_learn_epoch(self._h, ptr, n, dev, losses.ctypes.data), "orl_rnn_learn_epoch")
+        return losses
+
+    def forward(self, inputs, want_all: bool = False):
+        """eval-mode predictions of ``inputs`` [n, T, input_dim]: the last time step's [n, output_dim], and every step's
+        [n, T, output_dim] when ``want_all``.  Host arrays in and out, or contiguous fp32 torch tensors on the engine's device."""
+        od = int(self.cfg.output_dim)
+        if _is_tensor(inputs):
+            import torch
+            inputs = inputs.contiguous()
+            n, T = int(inputs.shape[0]), int(inputs.shape[1])
+            last = torch.empty((n, od), dtype=torch.float32, device=inputs.device)
+            every = torch.empty((n, T, od), dtype=torch.float32, device=inputs.device) if want_all else None
+            torch.cuda.current_stream(inputs.device).synchronize()
+            _check(self.lib.orl_rnn_forward(self._h, inputs.data_ptr(), n, T, 1, last.data_ptr(), None if every is None else every.data_ptr()),
+                   "orl_rnn_forward")
+            return (last, every) if want_all else last
+        inputs = _f32(inputs)
+        n, T = int(inputs.shape[0]), int(inputs.shape[1])
+        assert inputs.shape == (n, T, int(self.cfg.input_dim))
+        last = np.empty((n, od), np.float32)
+        every = np.empty((n, T, od), np.float32) if want_all else None
+        _check(self.lib.orl_rnn_forward(self._h, inputs.ctypes.data, n, T, 0, last.ctypes.data, None if every is None else every.ctypes.data),
+               "orl_rnn_forward")
+        return (last, every) if want_all else last
+
+    def debug_read(self, name: str, cap: int = 1 << 22) -> np.ndarray:
+        """a test tap of the last step / forward as a flat array: pred, loss, gru.<l>, in, merge, block.<i>, mask.<s>, act.<s>, drop.<s>"""
+        buf = np.empty(cap, np.float32)
+        n = int(self.lib.orl_rnn_debug_read(self._h, name.encode(), buf.ctypes.data, cap))
+        if n < 0:
+            raise RuntimeError(f"orl_rnn_debug_read({name!r}) failed: {last_error()}")
+        return buf[:n].copy()
+
+    def debug_grads(self) -> np.ndarray:
+        flat = np.empty(self.floats, np.float32)
+        _check(self.lib.orl_rnn_debug_grads(self._h, flat.ctypes.data, flat.size), "orl_rnn_debug_grads")
+        return flat
+
+    def profile(self, enable: bool = True):
+        """time the phases of every following training step with device events (``profile_read``)"""
+        _check(self.lib.orl_rnn_profile(self._h, int(bool(enable))), "orl_rnn_profile")
+
+    def profile_read(self) -> Dict[str, float]:
+        """milliseconds of the last timed step: the whole step, its forward (of which the GRU scans), the loss and backward (of which
+        the GRU scans) and Adam"""
+        ms = (C.c_float * 6)()
+        _check(self.lib.orl_rnn_profile_read(self._h, ms), "orl_rnn_profile_read")
+        return dict(zip(("step", "forward", "forward_scan", "backward", "backward_scan", "adam"), (float(v) for v in ms)))

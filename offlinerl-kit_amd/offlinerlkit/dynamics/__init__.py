@@ -526,3 +526,159 @@ class EnsembleDynamics(BaseDynamics):
         if self._eng is not None:
             torch.cuda.synchronize(self._arena.device)
             self._push_elites_from_model()
+
+
+def rnn_epoch_order(n: int, generator: Optional[torch.Generator] = None) -> np.ndarray:
+    """The row order of one epoch of ``DataLoader(data, shuffle=True)`` over ``n`` items, consuming the host torch RNG (``generator``,
+    or the global one) exactly as the loader does: its iterator draws a base seed, its ``RandomSampler`` draws the seed of a fresh
+    generator, and that generator's ``randperm(n)`` is the order."""
+    torch.empty((), dtype=torch.int64).random_(generator=generator)
+    seed = int(torch.empty((), dtype=torch.int64).random_(generator=generator).item())
+    g = torch.Generator()
+    g.manual_seed(seed)
+    return torch.randperm(n, generator=g).numpy().astype(np.int64)
+
+
+class RNNDynamics(BaseDynamics):
+    """The GRU sequence dynamics model (reference: dynamics/rnn_dynamics.py over nets/rnn.py:RNNModel) on the HIP engine (``orl_rnn_*``,
+    csrc/rnn_dynamics.hip).  ``learn`` is one device step of the masked MSE with Adam, ``train`` loads the data set into HBM once and
+    runs every epoch as one call, ``step`` is one eval-mode forward over the windows.  The module's parameters alias the engine's
+    block, so ``model.state_dict()``, ``save`` and ``load`` see what the engine trains.  Dropout masks come from a device Philox
+    stream, so a training run is distributed like the reference's, not equal to it (at ``dropout_rate`` 0 it is equal)."""
+
+    def __init__(self, model: nn.Module, optim: torch.optim.Optimizer, scaler: StandardScaler,
+                 terminal_fn: Callable[[np.ndarray, np.ndarray, np.ndarray], np.ndarray]) -> None:
+        super().__init__(model, optim)
+        from ..nets import RNNModel
+        if not isinstance(model, RNNModel):
+            raise NotImplementedError(f"RNNDynamics runs offlinerlkit.nets.RNNModel on the HIP engine, got {type(model).__name__}")
+        if type(optim) is not torch.optim.Adam:
+            raise NotImplementedError(f"RNNDynamics supports torch.optim.Adam only, got {type(optim).__name__}")
+        if len(optim.param_groups) != 1:
+            raise NotImplementedError("RNNDynamics supports one parameter group")
+        g = optim.param_groups[0]
+        if g.get("weight_decay", 0.0) or g.get("amsgrad", False) or g.get("maximize", False):
+            raise NotImplementedError("RNNDynamics supports Adam without weight_decay, amsgrad or maximize")
+        dims = list(model.hidden_dims)
+        if len(set(dims)) != 1:
+            raise NotImplementedError(f"the HIP engine supports RNNModel with equal hidden_dims (the residual blocks add their input), got {dims}")
+        if not 2 <= len(dims) <= _engine.MAX_HIDDEN + 1:
+            raise NotImplementedError(f"the HIP engine supports 2 to {_engine.MAX_HIDDEN + 1} hidden_dims in RNNModel, got {len(dims)}")
+        if dims[0] % 4 or not 8 <= dims[0] <= 512:
+            raise NotImplementedError(f"the HIP engine supports a hidden width that is a multiple of 4 in [8, 512], got {dims[0]}")
+        if not 1 <= model.rnn_num_layers <= 4:
+            raise NotImplementedError(f"the HIP engine supports 1 to 4 GRU layers, got {model.rnn_num_layers}")
+        if not 0.0 <= float(model.dropout_rate or 0.0) < 1.0:
+            raise ValueError(f"dropout_rate must be in [0, 1), got {model.dropout_rate}")
+        self.scaler = scaler
+        self.terminal_fn = terminal_fn
+        self._seed = 0
+        self._eng: Optional[_engine.RnnDynamicsEngine] = None
+        self._arena = None
+        self._shape = None              # (batch_size, max_seq_len) the engine was built for
+
+    # ---- engine binding ----
+    def set_engine_options(self, seed: Optional[int] = None) -> None:
+        if self._eng is not None:
+            raise RuntimeError("set_engine_options before the first train() / learn() / step()")
+        self._seed = int(seed) if seed is not None else 0
+
+    def _device(self) -> torch.device:
+        return EnsembleDynamics._device(self)
+
+    def _bind(self, rows: int, steps: int, exact: bool = False) -> None:
+        """an engine for steps of up to ``rows`` sequences (``exact``: batch_size == rows, as learn_epoch cuts an epoch into
+        batch_size rows) of up to ``steps`` time steps; an engine that is too small is rebuilt and its state carried over"""
+        old = self._shape if self._eng is not None else (0, 0)
+        if self._eng is not None and steps <= old[1] and (rows == old[0] if exact else rows <= old[0]):
+            return
+        shape = (int(rows) if exact else max(int(rows), old[0]), max(int(steps), old[1]))
+        carried = None
+        if self._eng is not None:
+            carried = (self._eng.get(0), self._eng.get(1), self._eng.get(2), self._eng.step_count)
+            self._unbind()
+        dev = self._device()
+        m, g = self.model, self.optim.param_groups[0]
+        cfg = _engine.default_rnn_config(input_dim=m.input_dim, output_dim=m.output_dim, hidden=m.hidden_dims,
+                                         rnn_num_layers=m.rnn_num_layers, dropout_rate=float(m.dropout_rate or 0.0),
+                                         batch_size=shape[0], max_seq_len=shape[1], lr=float(g["lr"]), adam_beta1=float(g["betas"][0]),
+                                         adam_beta2=float(g["betas"][1]), adam_eps=float(g["eps"]), device=dev.index, seed=self._seed)
+        self._arena = torch.zeros(_engine.rnn_config_floats(cfg), dtype=torch.float32, device=dev)
+        cfg.external_arena = self._arena.data_ptr()
+        torch.cuda.synchronize(dev)
+        self._eng = _engine.RnnDynamicsEngine(cfg)
+        self._shape = shape
+        if carried is not None:
+            for which in range(3):
+                self._eng.set(which, carried[which])
+            self._eng.step_count = carried[3]
+        else:
+            self._eng.set_params({k: v.detach().cpu().numpy() for k, v in m.state_dict().items()})
+        m.to(dev)
+        m.device = dev
+        params = dict(m.named_parameters())
+        for name, off, tshape in self._eng.tensors():
+            params[name].data = self._arena[off: off + int(np.prod(tshape))].view(tshape)
+
+    def _unbind(self) -> None:
+        if self._eng is None:
+            return
+        torch.cuda.synchronize(self._arena.device)
+        for p in self.model.parameters():
+            p.data = p.data.clone()
+        self._eng.close()
+        self._eng, self._arena, self._shape = None, None, None
+
+    @staticmethod
+    def _host(x) -> np.ndarray:
+        return np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float32)
+
+    # ---- reference API ----
+    @torch.no_grad()
+    def step(self, obss: np.ndarray, actions: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Dict]:
+        "imagine single forward step"
+        inputs = self.scaler.transform(np.concatenate([obss, actions], axis=-1))
+        self._bind(1, inputs.shape[1])
+        preds = self._eng.forward(self._host(inputs))
+        next_obss = preds[..., :-1] + obss[:, -1]
+        rewards = preds[..., -1:]
+        terminals = self.terminal_fn(obss[:, -1], actions[:, -1], next_obss)
+        return next_obss, rewards, terminals, {}
+
+    def learn(self, batch) -> float:
+        inputs, targets, masks = (self._host(x) for x in batch)
+        if not self.model.training and float(self.model.dropout_rate or 0.0) > 0.0:
+            raise NotImplementedError("RNNDynamics.learn on a model in eval mode: the engine's training step always applies the dropout")
+        self._bind(inputs.shape[0], inputs.shape[1])
+        self._eng.load_data(inputs, targets, masks)
+        return self._eng.step(np.arange(inputs.shape[0]))
+
+    def train(self, data, batch_size: int, max_iters: int, logger) -> None:
+        self.model.train()
+        items = [data[i] for i in range(len(data))]
+        inputs, targets, masks = (np.stack([self._host(it[k]) for it in items]) for k in range(3))
+        self._bind(int(batch_size), inputs.shape[1], exact=True)
+        self._eng.load_data(inputs, targets, masks)
+        for it in range(max_iters):
+            for loss in self._eng.learn_epoch(rnn_epoch_order(len(items))):
+                logger.logkv_mean("loss/model", float(loss))
+            logger.set_timestep(it)
+            logger.dumpkvs(exclude=["policy_training_progress"])
+        self.save(logger.model_dir)
+        self.model.eval()
+
+    def save(self, save_path: str) -> None:
+        if self._eng is not None:
+            torch.cuda.synchronize(self._arena.device)
+        sd = self.model.state_dict()
+        torch.save(type(sd)((k, v.detach().clone()) for k, v in sd.items()), os.path.join(save_path, "dynamics.pth"))
+        self.scaler.save_scaler(save_path)
+
+    def load(self, load_path: str) -> None:
+        self.model.load_state_dict(torch.load(os.path.join(load_path, "dynamics.pth"), map_location=self.model.device))
+        self.scaler.load_scaler(load_path)
+        if self._eng is not None:
+            torch.cuda.synchronize(self._arena.device)
+
+
+__all__ = ["BaseDynamics", "EnsembleDynamics", "RNNDynamics", "rnn_epoch_order"]

@@ -218,3 +218,75 @@ class ConditionalUnet1D(nn.Module):
         for first, second in self.up_modules:
             x = second(first(torch.cat((x, skips.pop()), dim=1), cond), cond)
         return self.final_conv(x).moveaxis(-1, -2)
+
+
+class Swish(nn.Module):
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return x * torch.sigmoid(x)
+
+
+def soft_clamp(x: torch.Tensor, _min=None, _max=None) -> torch.Tensor:
+    """clamp with a softplus knee on either side, so the gradient never vanishes"""
+    if _max is not None:
+        x = _max - nn.functional.softplus(_max - x)
+    if _min is not None:
+        x = _min + nn.functional.softplus(x - _min)
+    return x
+
+
+class ResBlock(nn.Module):
+    """LayerNorm([x +] dropout(activation(Linear(x)))); state_dict keys ``linear.*`` and ``layer_norm.*`` (reference: nets/rnn.py)"""
+
+    def __init__(self, input_dim: int, output_dim: int, activation: Optional[nn.Module] = None, layer_norm: bool = True,
+                 with_residual: bool = True, dropout: Optional[float] = 0.1) -> None:
+        super().__init__()
+        self.linear = nn.Linear(input_dim, output_dim)
+        self.activation = activation if activation is not None else Swish()
+        self.layer_norm = nn.LayerNorm(output_dim) if layer_norm else None
+        self.dropout = nn.Dropout(dropout) if dropout else None
+        self.with_residual = with_residual
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y = self.activation(self.linear(x))
+        if self.dropout is not None:
+            y = self.dropout(y)
+        if self.with_residual:
+            y = x + y
+        return y if self.layer_norm is None else self.layer_norm(y)
+
+
+class RNNModel(nn.Module):
+    """The sequence model of ``RNNDynamics`` (reference: nets/rnn.py): an ``nn.GRU`` over the input sequence beside a ResBlock of the
+    same input (no residual), both merged by ``swish(Linear(2H -> H))``, then ``len(hidden_dims) - 1`` residual ResBlocks and a Linear
+    head, applied to every time step.  ``forward`` takes ``[batch, T, input_dim]`` and returns ``([batch, T, output_dim], h_state)``.
+    It computes in the parameters' dtype (float32 unless the module was converted)."""
+
+    def __init__(self, input_dim: int, output_dim: int, hidden_dims: Sequence[int] = (200, 200, 200, 200), rnn_num_layers: int = 3,
+                 dropout_rate: float = 0.1, device: str = "cpu") -> None:
+        super().__init__()
+        self.input_dim = int(input_dim)
+        self.hidden_dims = [int(h) for h in hidden_dims]
+        self.output_dim = int(output_dim)
+        self.rnn_num_layers = int(rnn_num_layers)
+        self.dropout_rate = dropout_rate
+        self.device = torch.device(device)
+        widths = self.hidden_dims
+        self.activation = Swish()
+        self.rnn_layer = nn.GRU(input_size=self.input_dim, hidden_size=widths[0], num_layers=self.rnn_num_layers, batch_first=True)
+        self.input_layer = ResBlock(self.input_dim, widths[0], dropout=dropout_rate, with_residual=False)
+        self.backbones = nn.ModuleList([ResBlock(a, b, dropout=dropout_rate) for a, b in zip(widths[:-1], widths[1:])])
+        self.merge_layer = nn.Linear(widths[0] + widths[-1], widths[0])
+        self.output_layer = nn.Linear(widths[-1], self.output_dim)
+        self.to(self.device)
+
+    def forward(self, input, h_state=None):
+        w = self.output_layer.weight
+        x = torch.as_tensor(input, dtype=w.dtype).to(w.device)
+        batch, steps = x.shape[0], x.shape[1]
+        seq, h_state = self.rnn_layer(x, h_state)
+        flat = x.reshape(batch * steps, self.input_dim)
+        y = torch.cat([self.input_layer(flat), seq.reshape(batch * steps, self.hidden_dims[0])], dim=-1)
+        y = self.activation(self.merge_layer(y))
+        for block in self.backbones:
+            y = block(y)
+        return self.output_layer(y).view(batch, steps, self.output_dim), h_state

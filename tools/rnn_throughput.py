@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""RNNDynamics throughput at the constructor-default shape on hopper (in 14, out 12, [200] x 4, 3 GRU layers, batch 256, T 20): one
+``learn`` step and one ``step()`` on 256 windows on the HIP engine, and the same two on the project's own torch ``RNNModel`` with
+autograd and ``torch.optim.Adam`` on the same GPU in the same call (``loss.item()`` per step, as the reference's ``learn`` does).
+
+Method: every shape is warmed up first; a timed window is a host clock around work that ends in a device synchronise; engine and torch
+windows alternate over ``--rounds`` rounds and the medians are reported with the spread.  The forward / scan / backward split of the
+engine's step comes from device events (``orl_rnn_profile``), in windows of their own.  Prints one JSON object; --out writes it too."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "offlinerl-kit_amd"))
+from offlinerlkit import _engine  # noqa: E402
+from offlinerlkit.dynamics import RNNDynamics  # noqa: E402
+from offlinerlkit.nets import RNNModel  # noqa: E402
+from offlinerlkit.utils.scaler import StandardScaler  # noqa: E402
+
+IN, OUT, HID, L, P_DROP, B, T = 14, 12, [200, 200, 200, 200], 3, 0.1, 256, 20
+OBS = OUT - 1
+
+
+def data(n, seed=0):
+    rng = np.random.default_rng(seed)
+    return (rng.normal(size=(n, T, IN)).astype(np.float32), rng.normal(size=(n, T, OUT)).astype(np.float32),
+            (rng.uniform(size=(n, T)) < 0.9).astype(np.float32))
+
+
+def window(fn, sync):
+    sync()
+    t0 = time.perf_counter()
+    n = fn()
+    sync()
+    return (time.perf_counter() - t0) / n
+
+
+def summary(xs):
+    return dict(median_ms=1e3 * statistics.median(xs), min_ms=1e3 * min(xs), max_ms=1e3 * max(xs), windows=len(xs))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, default=20, help="optimizer steps per timed window")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("rnn_throughput.py measures on the GPU: no HIP device visible")
+    dev = torch.device("cuda", 0)
+    x, tg, mk = data(a.batches * B)
+    sync = lambda: torch.cuda.synchronize(dev)                                   # noqa: E731
+
+    # the engine: an epoch of `batches` steps in one call (one host synchronisation), and learn() / step() through the class
+    torch.manual_seed(0)
+    model = RNNModel(IN, OUT, HID, L, P_DROP)
+    init = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    eng = _engine.RnnDynamicsEngine(_engine.default_rnn_config())
+    eng.set_params({k: v.numpy() for k, v in init.items()})
+    eng.load_data(x, tg, mk)
+    order = np.arange(a.batches * B, dtype=np.int64)
+    dyn = RNNDynamics(model, torch.optim.Adam(model.parameters(), lr=1e-3), StandardScaler(np.zeros((1, IN), np.float32), np.ones((1, IN), np.float32)),
+                      lambda o, ac, n: np.zeros((len(o), 1), bool))
+    obss, acts = x[:B, :, :OBS].copy(), x[:B, :, OBS:].copy()
+
+    # the torch baseline
+    tm = RNNModel(IN, OUT, HID, L, P_DROP, device="cuda")
+    tm.load_state_dict(init)
+    opt = torch.optim.Adam(tm.parameters(), lr=1e-3)
+    xd, td, md = (torch.as_tensor(v, device=dev) for v in (x, tg, mk))
+
+    def torch_learn():
+        tm.train()
+        for b in range(a.batches):
+            s = slice(b * B, (b + 1) * B)
+            pred, _ = tm(xd[s])
+            loss = (((pred - td[s]) ** 2).mean(-1) * md[s]).mean()
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            loss.item()
+        return a.batches
+
+    @torch.no_grad()
+    def torch_step():
+        tm.eval()
+        for _ in range(a.batches):
+            pred, _ = tm(xd[:B])
+            last = pred[:, -1].cpu().numpy()
+            last[:, :-1] + obss[:, -1]
+        return a.batches
+
+    def engine_epoch():
+        losses = eng.learn_epoch(order)
+        assert np.isfinite(losses).all()
+        return a.batches
+
+    def class_learn():
+        for b in range(a.batches):
+            s = slice(b * B, (b + 1) * B)
+            dyn.learn((x[s], tg[s], mk[s]))
+        return a.batches
+
+    def class_step():
+        for _ in range(a.batches):
+            dyn.step(obss, acts)
+        return a.batches
+
+    runs = {"engine_learn_epoch_step": engine_epoch, "class_learn_call": class_learn, "torch_learn_step": torch_learn,
+            "class_step_256_windows": class_step, "torch_step_256_windows": torch_step}
+    for fn in runs.values():                                                     # warm-up: code objects, first touch, library choices
+        fn()
+    times = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for k, fn in runs.items():
+            times[k].append(window(fn, sync))
+    res = {"shape": dict(input_dim=IN, output_dim=OUT, hidden=HID, rnn_num_layers=L, dropout=P_DROP, batch=B, T=T),
+           "device": torch.cuda.get_device_name(0), "steps_per_window": a.batches}
+    res.update({k: summary(v) for k, v in times.items()})
+    eng.profile(True)
+    splits = []
+    for _ in range(a.rounds):
+        eng.learn_epoch(order)
+        splits.append(eng.profile_read())
+    eng.profile(False)
+    res["engine_step_split_ms"] = {k: statistics.median(s[k] for s in splits) for k in splits[0]}
+    res["learn_ratio_torch_over_engine"] = res["torch_learn_step"]["median_ms"] / res["engine_learn_epoch_step"]["median_ms"]
+    res["step_ratio_torch_over_engine"] = res["torch_step_256_windows"]["median_ms"] / res["class_step_256_windows"]["median_ms"]
+    eng.close()
+    s = json.dumps(res, indent=1)
+    print(s)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(s + "\n")
+
+
+if __name__ == "__main__":
+    main()
