@@ -638,6 +638,21 @@ int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int6
 /* test tap: parameter gradient of the LAST minibatch of the last orl_dyn_learn_epoch, or of the last orl_dynadv_update, whichever
  * ran later (flat like orl_dyn_get; decay terms excluded) */
 int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n_floats);
+/* test taps: one run's workspaces as the last call left them (the stream is synchronised; nothing is added to any call's path).  Only
+ * the first `rows` rows of each member block come back, `rows` being that call's row count (of orl_dyn_learn_epoch: its LAST
+ * minibatch's).  With D = obs_dim + with_reward and pitch0 = obs_dim + act_dim rounded up to 4:
+ *   after orl_dyn_learn_epoch    "learn.x" [K][rows][pitch0] (pad columns included), "learn.t" [K][rows][D], "learn.out" / "learn.dout"
+ *                                [K][rows][2 D], "learn.lterm" / "learn.gmax" / "learn.gmin" [K][rows][D], "learn.nll" [1] (the loss
+ *                                without the decay term) and "learn.decay" [ceil(floats / 1024)] (the decay loss of each 1024-float
+ *                                block); the last two cells are shared with orl_dynadv_update and hold the later call's
+ *   after orl_dyn_step, orl_dynsample_next, orl_dyn_validate   "step.x" [n][pitch0], "step.out" [K][n][2 D]; after validate "step.t" [H][D]
+ *   after orl_dynadv_forward     "adv.x" [Ba + Bs][pitch0], "adv.t" [Bs][D], "adv.obs" [Ba][obs_dim], "adv.s" [Ba][D] (the kept sample),
+ *                                "adv.out" [K][Ba + Bs][2 D]
+ *   after orl_dynadv_update      "adv.dout" [K][Ba + Bs][2 D], "adv.lterm" / "adv.gmax" / "adv.gmin" [K][Ba + Bs][D], "adv.rowlp" [Ba][2]
+ *                                (each row's double log-probability x as hi = (float)x, lo = (float)(x - hi)), "adv.advm" [2]
+ * Returns the floats written; < 0 (the message names the tap) for an unknown name, a run out of range, a tap whose call has not happened
+ * yet or whose workspace has been replaced since, an "adv." tap before orl_dynadv_configure, and a cap that is too small. */
+int64_t orl_dyn_debug_read(orl_dynamics* d, int run, const char* name, float* host, int64_t cap);
 
 /* -- RAMBO's adversarial model update (policy/model_based/rambo.py:129-207) on an orl_dynamics ------------------------------------
  * One update of dynamics_step_and_forward is two calls; the caller computes the advantage (actor and critics) between them.

@@ -73,6 +73,14 @@ __device__ __forceinline__ void dyn_store_elem(const DynNll& g, long row, int d,
   gmin[row * D + d] = g.gmin;
 }
 
+// c - a b with two roundings in fp32, as numpy evaluates the reference's reward - penalty_coef * penalty.  Contraction is switched off
+// for the two operations: to this compiler __fmul_rn is a plain product, and it fuses a plain product into the subtraction.
+__device__ __forceinline__ float dyn_sub_mul(float c, float a, float b) {
+#pragma clang fp contract(off)
+  const float prod = a * b;
+  return c - prod;
+}
+
 // the member of a row drawn from the run's elites with the first word of a Philox draw
 __device__ __forceinline__ int dyn_draw_elite(const int* elites, int r, int K, int n_elites, uint32_t rnd0) {
   return elites[r * K + (int)(((uint64_t)rnd0 * (uint64_t)n_elites) >> 32)];
@@ -340,7 +348,7 @@ __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
   const float penf = (float)pen;
   const float raw = p.raw_reward[(long)r * p.n + i];
   p.penalty[(long)r * p.n + i] = penf;
-  p.reward[(long)r * p.n + i] = raw - p.coef * penf;
+  p.reward[(long)r * p.n + i] = dyn_sub_mul(raw, p.coef, penf);
   if (p.midx_out) p.midx_out[(long)r * p.n + i] = mi;
 }
 
@@ -658,6 +666,10 @@ struct orl_dynamics {
   float *aInObs = nullptr, *aInAct = nullptr, *aSlObs = nullptr, *aSlAct = nullptr, *aSlNext = nullptr, *aSlRew = nullptr,
         *aNoise = nullptr, *aNext = nullptr, *aRew = nullptr;
   int *aMidx = nullptr, *aMidxOut = nullptr;
+  // what orl_dyn_debug_read returns rows of: the row count of the last learn minibatch and of the last validate / step / sample_next
+  // (0: no such call, or its workspace has been replaced since), whether that call left targets, and how far the adversarial pair got
+  long tap_learn_rows = 0, tap_step_rows = 0;
+  bool tap_step_t = false, tap_nll = false, tap_adv_fwd = false, tap_adv_upd = false;
   DevAllocs mem{"orl_dyn"};
 };
 
@@ -790,6 +802,7 @@ static int dyn_grow_step(orl_dynamics* d, long rows) {
   for (int l = 0; l < d->L; ++l) w.H[l] = (l & 1) ? d->sH1 : d->sH0;
   w.shared = true;
   d->s_cap = rows;
+  d->tap_step_rows = 0; d->tap_step_t = false;
   return 0;
 }
 
@@ -1081,6 +1094,8 @@ int orl_dyn_learn_epoch(orl_dynamics* d, const int64_t* idx, int64_t train_size,
   std::vector<float> ls(R);
   ORL_HIP(hipMemcpyAsync(ls.data(), d->loss_sum, sizeof(float) * R, hipMemcpyDeviceToHost, d->stream));
   ORL_HIP(hipStreamSynchronize(d->stream));
+  d->tap_learn_rows = train_size - (nb - 1) * B;
+  d->tap_nll = true;
   for (int r = 0; r < R; ++r) {
     if (act[r]) d->tstep[r] += nb;
     if (loss_out) loss_out[r] = act[r] ? (float)((double)ls[r] / (double)nb) : 0.f;
@@ -1104,6 +1119,7 @@ int orl_dyn_validate(orl_dynamics* d, const int64_t* idx, int64_t H, float* mse_
               (int)H, D, K, mse);
   ORL_HIP(hipMemcpyAsync(mse_out, mse, sizeof(float) * R * K, hipMemcpyDeviceToHost, d->stream));
   ORL_HIP(hipStreamSynchronize(d->stream));
+  d->tap_step_rows = H; d->tap_step_t = true;
   return 0;
 }
 
@@ -1177,6 +1193,7 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
       stage_out(d->stream, (int*)midx_out, d->sMidxOut, (size_t)R * n, on_device))
     return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
+  d->tap_step_rows = n; d->tap_step_t = false;
   return 0;
 }
 
@@ -1215,11 +1232,91 @@ int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int6
   DEV_LAUNCH(d->stream, k_dyn_sample_next, dim3((unsigned)((nt + 255) / 256), R), dim3(256), 0, p);
   if (stage_out(d->stream, next_obs, d->mNext, (size_t)R * rows * od, on_device)) return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
+  d->tap_step_rows = n; d->tap_step_t = false;
   return 0;
 }
 
 int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n) {
   return dyn_check_run(d, run, n, "orl_dyn_debug_grads") || block_to_host(d->stream, host, d->grads + (long)run * d->P, d->P) ? -1 : 0;
+}
+
+// test tap: the workspaces as the last call left them, nothing on any call's path.  A member block [rows][cols] of src
+// [R][members][stride rows][pitch] per member; `members` 1 for the matrices the members share.
+int64_t orl_dyn_debug_read(orl_dynamics* d, int run, const char* name, float* host, int64_t cap) {
+  if (!d || !name || !host) return fail("orl_dyn_debug_read: bad arguments");
+  const std::string nm(name), who = "orl_dyn_debug_read: " + nm;
+  if (run < 0 || run >= d->R) return fail(who + ": run out of range");
+  const int K = d->K, D = d->D, p0 = d->pitch[0], po = d->pitch[d->L + 1];
+  const long N = (long)d->aBa + d->aBs;
+  const float* src = nullptr;
+  long members = 1, stride = 0, rows = 0;
+  int cols = 0, pitch = 0;
+  auto view = [&](const float* p, long mem, long st, long n, int c, int pt) {
+    src = p; members = mem; stride = st; rows = n; cols = c; pitch = pt;
+  };
+  const bool learn = nm.compare(0, 6, "learn.") == 0, step = nm.compare(0, 5, "step.") == 0, adv = nm.compare(0, 4, "adv.") == 0;
+  const std::string leaf = nm.substr(learn ? 6 : (step ? 5 : (adv ? 4 : 0)));
+  if (learn) {
+    const DynWs& w = d->lw;
+    const long n = d->tap_learn_rows, B = d->B;
+    if (leaf == "x") view(w.X, K, B, n, p0, p0);
+    else if (leaf == "t") view(d->T, K, B, n, D, D);
+    else if (leaf == "out") view(w.OUT, K, B, n, 2 * D, po);
+    else if (leaf == "dout") view(w.dOUT, K, B, n, 2 * D, po);
+    else if (leaf == "lterm") view(w.lterm, K, B, n, D, D);
+    else if (leaf == "gmax") view(w.gmax, K, B, n, D, D);
+    else if (leaf == "gmin") view(w.gmin, K, B, n, D, D);
+    else if (leaf == "nll") view(d->nll, 1, 1, d->tap_nll ? 1 : 0, 1, 1);                    // shared with orl_dynadv_update
+    else if (leaf == "decay") view(d->decay_part, 1, 1, d->tap_nll ? 1 : 0, d->nblk, d->nblk);
+    else return fail(who + ": unknown tap");
+    if (rows < 1) return fail(who + ": nothing recorded (no orl_dyn_learn_epoch yet)");
+  } else if (step) {
+    const long n = d->tap_step_rows;
+    if (leaf == "x") view(d->sw.X, 1, n, n, p0, p0);
+    else if (leaf == "out") view(d->sw.OUT, K, n, n, 2 * D, po);
+    else if (leaf == "t") view(d->sT, 1, n, d->tap_step_t ? n : 0, D, D);
+    else return fail(who + ": unknown tap");
+    if (rows < 1)
+      return fail(who + (leaf == "t" ? ": nothing recorded (the last call on the step workspace was not orl_dyn_validate)"
+                                     : ": nothing recorded (no orl_dyn_step / orl_dynsample_next / orl_dyn_validate yet)"));
+  } else if (adv) {
+    const DynWs& w = d->aw;
+    const long Ba = d->aBa, Bs = d->aBs;
+    bool upd = true;
+    if (leaf == "x") { view(w.X, 1, N, N, p0, p0); upd = false; }
+    else if (leaf == "t") { view(d->aT, 1, Bs, Bs, D, D); upd = false; }
+    else if (leaf == "obs") { view(d->aObs, 1, Ba, Ba, d->od, d->od); upd = false; }
+    else if (leaf == "s") { view(d->aS, 1, Ba, Ba, D, D); upd = false; }
+    else if (leaf == "out") { view(w.OUT, K, N, N, 2 * D, po); upd = false; }
+    else if (leaf == "dout") view(w.dOUT, K, N, N, 2 * D, po);
+    else if (leaf == "lterm") view(w.lterm, K, N, N, D, D);
+    else if (leaf == "gmax") view(w.gmax, K, N, N, D, D);
+    else if (leaf == "gmin") view(w.gmin, K, N, N, D, D);
+    else if (leaf == "rowlp") view(nullptr, 1, Ba, Ba, 2, 2);
+    else if (leaf == "advm") view(d->aAdvm, 1, 1, 1, 2, 2);
+    else return fail(who + ": unknown tap");
+    if (!d->adv_on) return fail(who + ": orl_dynadv_configure first");
+    if (!d->tap_adv_fwd) return fail(who + ": nothing recorded (no orl_dynadv_forward yet)");
+    if (upd && !d->tap_adv_upd) return fail(who + ": nothing recorded (no orl_dynadv_update since the last orl_dynadv_forward)");
+  } else {
+    return fail(who + ": unknown tap");
+  }
+  const int64_t total = (int64_t)members * rows * cols;
+  if (total > cap) return fail(who + " needs " + std::to_string(total) + " floats");
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  if (adv && leaf == "rowlp") {      // doubles as (hi, lo) float pairs
+    std::vector<double> lp((size_t)rows);
+    ORL_HIP(hipMemcpy(lp.data(), d->aRowlp + (long)run * rows, sizeof(double) * rows, hipMemcpyDeviceToHost));
+    for (long i = 0; i < rows; ++i) {
+      host[2 * i] = (float)lp[i];
+      host[2 * i + 1] = (float)(lp[i] - (double)host[2 * i]);
+    }
+    return total;
+  }
+  for (long k = 0; k < members; ++k)
+    ORL_HIP(hipMemcpy2D(host + k * rows * cols, sizeof(float) * cols, src + ((long)run * members + k) * stride * pitch,
+                        sizeof(float) * pitch, sizeof(float) * cols, rows, hipMemcpyDeviceToHost));
+  return total;
 }
 
 // ---- RAMBO's adversarial update ----
@@ -1237,6 +1334,7 @@ int orl_dynadv_configure(orl_dynamics* d, float lr, float beta1, float beta2, fl
   }
   if (d->adv_on && d->aBa == rollout_rows && d->aBs == sl_rows) return 0;
   d->adv_pending = false;
+  d->tap_adv_fwd = d->tap_adv_upd = false;
   dyn_ws_release(d, d->aw);
   d->mem.release(&d->aT, &d->aS, &d->aObs, &d->aAdv, &d->aAdvm, &d->aMetrics, &d->aRowlp, &d->aInObs, &d->aInAct, &d->aSlObs, &d->aSlAct,
               &d->aSlNext, &d->aSlRew, &d->aNoise, &d->aNext, &d->aRew, &d->aMidx, &d->aMidxOut);
@@ -1296,6 +1394,7 @@ int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, cons
     return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
   d->adv_pending = true;
+  d->tap_adv_fwd = true; d->tap_adv_upd = false;
   return 0;
 }
 
@@ -1337,6 +1436,7 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
   std::vector<float> ms((size_t)R * 4);
   ORL_HIP(hipMemcpyAsync(ms.data(), d->aMetrics, sizeof(float) * ms.size(), hipMemcpyDeviceToHost, d->stream));
   ORL_HIP(hipStreamSynchronize(d->stream));
+  d->tap_adv_upd = true; d->tap_nll = true;
   for (int r = 0; r < R; ++r)
     if (act[r]) d->adv_tstep[r] += 1;
   if (metrics_out) memcpy(metrics_out, ms.data(), sizeof(float) * ms.size());

@@ -55,7 +55,7 @@ ABI_SYMBOLS = [
     "orl_dyn_config_default", "orl_dyn_create", "orl_dyn_destroy", "orl_dyn_sync", "orl_dyn_floats", "orl_dyn_config_floats",
     "orl_dyn_num_tensors", "orl_dyn_tensor", "orl_dyn_ptr", "orl_dyn_set", "orl_dyn_get", "orl_dyn_adam_get", "orl_dyn_adam_set",
     "orl_dyn_set_elites", "orl_dyn_get_elites", "orl_dyn_load_data", "orl_dyn_set_scaler", "orl_dyn_learn_epoch", "orl_dyn_validate",
-    "orl_dyn_update_save", "orl_dyn_load_save", "orl_dyn_step", "orl_dyn_debug_grads",
+    "orl_dyn_update_save", "orl_dyn_load_save", "orl_dyn_step", "orl_dyn_debug_grads", "orl_dyn_debug_read",
     # RAMBO's adversarial update on an orl_dynamics
     "orl_dynadv_configure", "orl_dynadv_forward", "orl_dynadv_update", "orl_dynadv_adam_get", "orl_dynadv_adam_set",
     # MOBILE: next-state samples of the dynamics, their hand-over to the policy engine, compute_lcb alone
@@ -346,6 +346,8 @@ def _bind_dynamics(lib) -> None:
     lib.orl_dyn_load_save.argtypes = [P, C.c_int]
     lib.orl_dyn_step.argtypes = [P, VP, VP, I64, C.c_int, VP, VP, C.c_int, F, VP, VP, VP, VP, VP]
     lib.orl_dyn_debug_grads.argtypes = [P, C.c_int, VP, I64]
+    lib.orl_dyn_debug_read.argtypes = [P, C.c_int, C.c_char_p, VP, I64]
+    lib.orl_dyn_debug_read.restype = I64
     lib.orl_dynadv_configure.argtypes = [P, F, F, F, F, F, C.c_int32, C.c_int32]
     lib.orl_dynadv_forward.argtypes = [P] + [VP] * 6 + [C.c_int, VP, VP, VP, VP, VP]
     lib.orl_dynadv_update.argtypes = [P, VP, C.c_int, VP, VP]
@@ -1231,6 +1233,22 @@ class Dynamics(_Handle):
         flat = np.empty(self.P, dtype=np.float32)
         _check(self.lib.orl_dyn_debug_grads(self._h, run, flat.ctypes.data, self.P), "orl_dyn_debug_grads")
         return self._unflat(flat)
+
+    def debug_read(self, run: int, name: str, cap: int = 1 << 22) -> np.ndarray:
+        """test tap ``orl_dyn_debug_read``: one run's workspace matrix as the last call left it, in the shape include/orl_engine.h
+        documents: (K, rows, cols) for a matrix per member, (rows, cols) for one the members share, flat for the loss cells"""
+        buf = np.empty(cap, dtype=np.float32)
+        n = int(self.lib.orl_dyn_debug_read(self._h, run, name.encode(), buf.ctypes.data, cap))
+        if n < 0:
+            raise RuntimeError(f"orl_dyn_debug_read({name!r}) failed: {last_error()}")
+        leaf = name.split(".", 1)[1]
+        cols = {"x": (self.od + self.ad + 3) // 4 * 4, "out": 2 * self.D, "dout": 2 * self.D, "obs": self.od, "rowlp": 2}.get(leaf, self.D)
+        out = buf[:n].copy()
+        if leaf in ("nll", "decay", "advm"):
+            return out
+        if leaf in ("out", "dout", "lterm", "gmax", "gmin") or name in ("learn.x", "learn.t"):
+            return out.reshape(self.K, -1, cols)
+        return out.reshape(-1, cols)
 
     def set_elites(self, run: int, idx):
         a = np.ascontiguousarray(idx, dtype=np.int64)

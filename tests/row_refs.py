@@ -160,11 +160,18 @@ def sum_terms(n):
     return float(math.ceil(math.log2(max(n, 1)) + n / 256.0 + 2.0))
 
 
-def sum_(x, axis=None, sequential=False):
-    """sum over ``axis``; ``sequential``: one thread adds the terms one after the other (loops over the action or member index)"""
+def wave_terms(n):
+    """rounding steps of an n-term sum by ONE wave: a 64-lane strided loop (ceil(n / 64) additions per lane), then the 6-step shuffle tree"""
+    return float(math.ceil(max(n, 1) / 64.0) + 6)
+
+
+def sum_(x, axis=None, sequential=False, stride=256):
+    """sum over ``axis``; ``sequential``: one thread adds the terms one after the other (loops over the action or member index);
+    ``stride`` 64: one wave's strided loop and shuffle tree (``wave_terms``) instead of a 256-thread block's (``sum_terms``)"""
     x = BV.exact(x)
     n = x.v.size if axis is None else x.v.shape[axis]
-    k = float(max(n - 1, 0)) if sequential else sum_terms(n)
+    assert stride in (64, 256), stride
+    k = float(max(n - 1, 0)) if sequential else (wave_terms(n) if stride == 64 else sum_terms(n))
     return BV(x.v.sum(axis=axis), x.e.sum(axis=axis) + k * U * np.abs(x.v).sum(axis=axis))
 
 

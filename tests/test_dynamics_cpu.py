@@ -154,7 +154,7 @@ def test_dynamics_abi_symbols():
     from offlinerlkit import _engine
     lib = _engine.load_library()
     dyn = [s for s in _engine.ABI_SYMBOLS if s.startswith("orl_dyn_")]
-    assert len(dyn) == 23
+    assert len(dyn) == 24 and "orl_dyn_debug_read" in dyn
     for s in dyn:
         assert hasattr(lib, s), s
     cfg = _engine.default_dyn_config()
