@@ -752,7 +752,12 @@ int orl_diffusion_debug_grads(orl_diffusion* d, float* host, int64_t n_floats); 
 /* -- RNNDynamics: the GRU sequence dynamics model (dynamics/rnn_dynamics.py, nets/rnn.py:RNNModel) ------------------------------
  * nn.GRU(in, H, L layers, batch_first, h0 = 0) beside a LayerNorm(dropout(swish(Linear))) input block, both merged by
  * swish(Linear(2H -> H)), then len(hidden) - 1 residual blocks LayerNorm(x + dropout(swish(Linear(x)))) and a Linear head.  Every
- * sequence array is [rows][T][cols], row-major.  One object = one run, precision 0 (fp32 MFMA). */
+ * sequence array is [rows][T][cols], row-major.  Precision 0 (fp32 MFMA).
+ * One object trains n_runs (1 .. 64) independent runs in the same launches: parameters, Adam moments and gradients are [n_runs][P] with
+ * P = orl_rnn_floats, every run reads the one loaded data set through its own row indices, and run r draws the dropout stream of a
+ * one-run object with seed + r.  Run r's results do not depend on n_runs, bit for bit.  On an object of several runs the one-run
+ * entry points orl_rnn_set / _get / _step / _learn_epoch / _forward / _debug_read / _debug_grads are refused; use the _run / _runs
+ * forms below, which are valid for n_runs == 1 too. */
 typedef struct orl_rnn orl_rnn;
 typedef struct {
   int32_t input_dim, output_dim;
@@ -765,22 +770,25 @@ typedef struct {
   double lr, adam_beta1, adam_beta2, adam_eps;   /* doubles, as torch.optim.Adam holds them: 1 - beta is formed before the rounding to fp32 */
   int32_t n_runs, device, precision;
   uint64_t seed;                    /* of the dropout masks' Philox stream */
-  void* external_arena;             /* device memory of orl_rnn_config_floats floats that holds the parameters, or NULL */
+  void* external_arena;             /* device memory of n_runs * orl_rnn_config_floats floats that holds the parameters (run r's
+                                       block at r * orl_rnn_config_floats floats), or NULL */
 } orl_rnn_config;
 void orl_rnn_config_default(orl_rnn_config* cfg);  /* hopper: 14 / 12, [200] * 4, 3 layers, p 0.1, batch 256, T 20, lr 1e-3 */
-int64_t orl_rnn_config_floats(const orl_rnn_config* cfg);      /* floats of the parameter block such a config needs; < 0: refused */
-/* Refused: n_runs != 1, precision != 0, unequal hidden dims, H not a multiple of 4 or outside [8, 512], rnn_num_layers outside
+int64_t orl_rnn_config_floats(const orl_rnn_config* cfg);      /* floats of ONE run's parameter block of such a config; < 0: refused */
+/* Refused: n_runs outside [1, 64], precision != 0, unequal hidden dims, H not a multiple of 4 or outside [8, 512], rnn_num_layers outside
  * [1, 4], n_hidden outside [2, ORL_MAX_HIDDEN + 1], dims < 1, dropout_rate outside [0, 1). */
 int orl_rnn_create(const orl_rnn_config* cfg, orl_rnn** out);
 void orl_rnn_destroy(orl_rnn* d);
-int64_t orl_rnn_floats(orl_rnn* d);
+int64_t orl_rnn_floats(orl_rnn* d);                             /* per run */
 int orl_rnn_num_tensors(orl_rnn* d);
-/* tensor idx of the block in RNNModel.state_dict() order: name, offset (a multiple of 4 floats) and shape */
+/* tensor idx of a run's block in RNNModel.state_dict() order: name, offset within the block (a multiple of 4 floats) and shape */
 int orl_rnn_tensor(orl_rnn* d, int idx, char* name, int name_cap, int64_t* offset_floats, int32_t* ndim, int64_t shape[4]);
 /* which: 0 parameters, 1 exp_avg, 2 exp_avg_sq; host arrays of orl_rnn_floats floats */
 int orl_rnn_set(orl_rnn* d, int which, const float* host, int64_t n_floats);
 int orl_rnn_get(orl_rnn* d, int which, float* host, int64_t n_floats);
-int orl_rnn_set_step_count(orl_rnn* d, int64_t k);       /* optimizer steps taken: Adam's t and the dropout counter */
+int orl_rnn_set_run(orl_rnn* d, int run, int which, const float* host, int64_t n_floats);    /* the same on run `run`'s block */
+int orl_rnn_get_run(orl_rnn* d, int run, int which, float* host, int64_t n_floats);
+int orl_rnn_set_step_count(orl_rnn* d, int64_t k);       /* optimizer steps taken: Adam's t and the dropout counter (shared by the runs) */
 int64_t orl_rnn_step_count(orl_rnn* d);
 /* the data set into HBM, once: inputs [n][T][input_dim], targets [n][T][output_dim], masks [n][T] (host, float32); T <= max_seq_len */
 int orl_rnn_load_data(orl_rnn* d, const float* inputs, const float* targets, const float* masks, int64_t n, int32_t T);
@@ -789,18 +797,32 @@ int orl_rnn_load_data(orl_rnn* d, const float* inputs, const float* targets, con
  * (1 keep, 0 drop; entry 0 the input block, entry 1 + i residual block i) teacher-force the dropout; NULL: device Philox keyed by
  * (seed, step count, block, row, column).  All pointers are HOST pointers.  loss_out: the minibatch loss (synchronous). */
 int orl_rnn_step(orl_rnn* d, const int64_t* idx, int32_t rows, const float* drop_masks, float* loss_out);
+/* The same step of every run at once: idx [n_runs][rows] (run r trains on its own rows), drop_masks [n_runs][len(hidden)][rows * T][H]
+ * or NULL, losses_out [n_runs].  An index out of range in any run refuses the whole call. */
+int orl_rnn_step_runs(orl_rnn* d, const int64_t* idx, int32_t rows, const float* drop_masks, float* losses_out);
 /* ceil(n_rows / batch_size) steps over order[0 .. n_rows) (int64, a device pointer when on_device), the last one short; one host
  * synchronisation, at the end.  losses_out: host, one loss per step. */
 int orl_rnn_learn_epoch(orl_rnn* d, const int64_t* order, int64_t n_rows, int on_device, float* losses_out);
+/* The same with one order per run: orders [n_runs][n_rows] (a device pointer when on_device), losses_out [steps][n_runs]; one host
+ * synchronisation, at the end. */
+int orl_rnn_learn_epoch_runs(orl_rnn* d, const int64_t* orders, int64_t n_rows, int on_device, float* losses_out);
 /* eval-mode forward (no dropout) of n sequences inputs [n][T][input_dim], 1 <= T <= max_seq_len: out_last [n][output_dim] is the
  * prediction of the last time step, out_all [n][T][output_dim] (or NULL) every step's.  Device pointers when on_device. */
 int orl_rnn_forward(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, float* out_last, float* out_all);
+/* run >= 0: that run alone on inputs [n][T][input_dim], outputs as orl_rnn_forward's.  run == -1: every run, on the same inputs
+ * [n][T][input_dim] when shared_inputs != 0 and on inputs [n_runs][n][T][input_dim] otherwise; out_last [n_runs][n][output_dim],
+ * out_all [n_runs][n][T][output_dim] or NULL. */
+int orl_rnn_forward_runs(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, int shared_inputs, int run, float* out_last,
+                         float* out_all);
 /* test taps of the last step (or of the last forward when it came later), [rows * T][cols] each: "pred", "gru.<l>" (layer l's
  * output), "in" (the input block's output), "merge", "block.<i>" (residual block i's output), "mask.<s>" (the keep mask of dropout
  * s, training only), "act.<s>" (what that dropout reads) and "drop.<s>" (what its LayerNorm reads); and "loss".  Unknown names are
  * refused.  Returns the floats written, < 0 on error. */
 int64_t orl_rnn_debug_read(orl_rnn* d, const char* name, float* host, int64_t cap);
 int orl_rnn_debug_grads(orl_rnn* d, float* host, int64_t n_floats);   /* parameter gradient of the last step */
+/* the same taps of run `run` (one that the last pass computed) */
+int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* host, int64_t cap);
+int orl_rnn_debug_grads_run(orl_rnn* d, int run, float* host, int64_t n_floats);
 /* Timing of the training steps with device events (off by default).  While enabled every step records events around its phases;
  * orl_rnn_profile_read waits for the last step and writes its milliseconds: ms[0] the whole step, [1] the forward, [2] the forward
  * scans of all layers, [3] the loss and the backward, [4] the backward scans of all layers, [5] Adam. */

@@ -16,6 +16,11 @@
 //   k_rnn_slab_sum     the weight gradients are split-K products into up to 8 slabs (k ranges of >= 256 rows): the slabs added in order
 //   k_rnn_adam         torch.optim.Adam over the flat block
 // Nothing accumulates with atomics: two identical calls give identical bits.
+//
+// Runs (orl_rnn_config::n_runs = R): every launch above gets a run dimension and nothing else.  Parameters, moments, gradients and
+// slabs are [R][P] per block, every workspace matrix is [R][cap rows][pitch], the data set is one and each run gathers its own rows.
+// The scans and the row kernels add blockIdx.y * stride to their base pointers, the matrix products take the runs as launch_gemm's
+// batch.  Tile configurations and slab counts are functions of the per-run shape, so run r's bits do not depend on R.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -51,6 +56,7 @@ struct RnnScanP {
   const float* bhh;                  // [3H]
   float* ho; int hop;                // [rows * T][H]: h_t
   float *r, *z, *n, *hn, *hp; int sp;   // training: the gates, W_hn h + b_hn and h_{t-1} ([rows * T][H] each); eval: null
+  long gi_rs, par_rs, ho_rs, s_rs;   // run strides (floats) of gi, of whh / bhh, of ho and of the saved matrices: run = blockIdx.y
 };
 
 // LDS: h_{t-1} of the block's 16 rows as [16][HP], HP = 16 ceil(H / 16) + 4, columns past H zero.  Wave w owns the unit tiles
@@ -63,6 +69,11 @@ __global__ __launch_bounds__(64 * RNN_FWD_WAVES) void k_rnn_scan_fwd(RnnScanP p)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int b0 = blockIdx.x * RNN_RB;
   const int nrow = min((int)RNN_RB, p.rows - b0);
+  {                                                     // this workgroup's run: its operands, weights and outputs
+    const long run = blockIdx.y;
+    p.gi += run * p.gi_rs; p.whh += run * p.par_rs; p.bhh += run * p.par_rs; p.ho += run * p.ho_rs;
+    if (p.r) { p.r += run * p.s_rs; p.z += run * p.s_rs; p.n += run * p.s_rs; p.hn += run * p.s_rs; p.hp += run * p.s_rs; }
+  }
   for (int e = tid; e < RNN_RB * HP; e += 64 * RNN_FWD_WAVES) rnn_lds[e] = 0.f;
   __syncthreads();
   for (int t = 0; t < p.T; ++t) {
@@ -155,6 +166,7 @@ struct RnnScanBP {
   const float* whh;
   const float *r, *z, *n, *hn, *hp; int sp;
   float* dgi; float* dgh; int gp;    // [rows * T][3H]: gradients of the input-side and hidden-side pre-activations
+  long do_rs, par_rs, s_rs, g_rs;    // run strides (floats) of dout, of whh, of the saved matrices and of dgi / dgh: run = blockIdx.y
 };
 
 // LDS: dGH_t of the block's 16 rows as [16][GP], GP = 16 ceil(3H / 16) + 4 (columns past 3H zero), and the carried dh as [16][H + 4].
@@ -169,6 +181,12 @@ __global__ __launch_bounds__(64 * RNN_BWD_WAVES) void k_rnn_scan_bwd(RnnScanBP p
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
   const int b0 = blockIdx.x * RNN_RB;
   const int nrow = min((int)RNN_RB, p.rows - b0);
+  {
+    const long run = blockIdx.y;
+    p.dout += run * p.do_rs; p.whh += run * p.par_rs;
+    p.r += run * p.s_rs; p.z += run * p.s_rs; p.n += run * p.s_rs; p.hn += run * p.s_rs; p.hp += run * p.s_rs;
+    p.dgi += run * p.g_rs; p.dgh += run * p.g_rs;
+  }
   for (int e = tid; e < RNN_RB * (GP + CP); e += 64 * RNN_BWD_WAVES) rnn_lds[e] = 0.f;
   __syncthreads();
   for (int t = p.T - 1; t >= 0; --t) {
@@ -240,13 +258,16 @@ __global__ __launch_bounds__(64 * RNN_BWD_WAVES) void k_rnn_scan_bwd(RnnScanBP p
 }
 
 // ---- the small kernels of the tail ----
-// the step's sequences out of the data set: X0 [rows * T][xp], TGT [rows * T][od], MSK [rows * T]; a row index is clamped
+// the step's sequences out of the data set: X0 [rows * T][xp], TGT [rows * T][od], MSK [rows * T]; a row index is clamped.  Run
+// blockIdx.y reads its own index list (stride idx_rs) and writes its own X0 / TGT / MSK (strides x_rs, tm_rs * od, tm_rs)
 __global__ void k_rnn_gather(const float* __restrict__ inputs, const float* __restrict__ targets, const float* __restrict__ masks,
-                             const long long* __restrict__ idx, long n_data, int T, int in, int od, int rows, float* __restrict__ X0, int xp,
-                             float* __restrict__ TGT, float* __restrict__ MSK) {
+                             const long long* __restrict__ idx, long idx_rs, long n_data, int T, int in, int od, int rows, float* __restrict__ X0,
+                             int xp, long x_rs, float* __restrict__ TGT, float* __restrict__ MSK, long tm_rs) {
   const int per = in + od + 1;
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (long)rows * T * per) return;
+  const long run = blockIdx.y;
+  idx += run * idx_rs; X0 += run * x_rs; TGT += run * tm_rs * od; MSK += run * tm_rs;
   const long row = e / per; const int c = (int)(e - row * per);
   const long b = row / T; const int t = (int)(row - b * T);
   const long g = min(max((long)idx[b], 0L), n_data - 1) * T + t;
@@ -254,21 +275,26 @@ __global__ void k_rnn_gather(const float* __restrict__ inputs, const float* __re
   else if (c < in + od) TGT[row * od + (c - in)] = targets[g * od + (c - in)];
   else MSK[row] = masks[g];
 }
-// dst [rows][cols] (pitch dp) = src (pitch sp); step > 1: source row = r * step + (step - 1), the last time step of sequence r
-__global__ void k_rnn_copy(const float* __restrict__ src, int sp, float* __restrict__ dst, int dp, long rows, int cols, int step) {
+// dst [rows][cols] (pitch dp) = src (pitch sp); step > 1: source row = r * step + (step - 1), the last time step of sequence r.
+// Run blockIdx.y: src + run * s_rs, dst + run * d_rs
+__global__ void k_rnn_copy(const float* __restrict__ src, int sp, long s_rs, float* __restrict__ dst, int dp, long d_rs, long rows, int cols,
+                           int step) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= rows * cols) return;
+  src += (long)blockIdx.y * s_rs; dst += (long)blockIdx.y * d_rs;
   const long r = e / cols; const int c = (int)(e - r * cols);
   dst[r * dp + c] = src[(r * step + (step - 1)) * sp + c];
 }
-// keep masks 1[u < 1 - p] of dropout `slot`: Philox keyed by the seed, counter = (step count, slot), (row, column quad)
-__global__ void k_rnn_mask(float* __restrict__ mk, long rows, int H, float keep, uint64_t seed, uint64_t kstep, uint32_t slot) {
+// keep masks 1[u < 1 - p] of dropout `slot`: Philox keyed by the seed, counter = (step count, slot), (row, column quad).  Run
+// blockIdx.y (masks at mk + run * mk_rs) draws the stream of a one-run object with seed + run
+__global__ void k_rnn_mask(float* __restrict__ mk, long mk_rs, long rows, int H, float keep, uint64_t seed, uint64_t kstep, uint32_t slot) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int q4 = H >> 2;
   if (e >= rows * q4) return;
   const long row = e / q4; const int q = (int)(e - row * q4);
+  mk += (long)blockIdx.y * mk_rs;
   uint32_t rnd[4];
-  const Philox ph(seed);
+  const Philox ph(seed + (uint64_t)blockIdx.y);
   ph((uint32_t)row, (uint32_t)q, (uint32_t)kstep, (slot << 28) | (uint32_t)((kstep >> 32) & 0x0fffffffu), rnd);
 #pragma unroll
   for (int k = 0; k < 4; ++k) mk[row * H + 4 * q + k] = u01(rnd[k]) < keep ? 1.f : 0.f;
@@ -288,7 +314,22 @@ struct RnnNormP {
   float* du; int dup;                // the residual path's gradient or null
   float* dz; int dzp;                // the Linear's output gradient
   float* part; long pn;              // [row][pn]: dgamma at [c], dbeta at [H + c]
+  // run strides (floats): run = blockIdx.y
+  long s_rs, mask_rs, res_rs, par_rs, u_rs, out_rs, g_rs[2], z_rs, du_rs, dz_rs, part_rs;
 };
+// the views of run `run`
+__device__ __forceinline__ void rnn_norm_run(RnnNormP& p, long run) {
+  p.s += run * p.s_rs; p.gamma += run * p.par_rs; p.beta += run * p.par_rs; p.u += run * p.u_rs;
+  if (p.mask) p.mask += run * p.mask_rs;
+  if (p.res) p.res += run * p.res_rs;
+  if (p.out) p.out += run * p.out_rs;
+  if (p.g[0]) p.g[0] += run * p.g_rs[0];
+  if (p.g[1]) p.g[1] += run * p.g_rs[1];
+  if (p.zpre) p.zpre += run * p.z_rs;
+  if (p.du) p.du += run * p.du_rs;
+  if (p.dz) p.dz += run * p.dz_rs;
+  if (p.part) p.part += run * p.part_rs;
+}
 
 // LayerNorm statistics of one row in one wave (diffusion.hip's diff_group_stats with one group): mean, then the centred second moment
 __device__ __forceinline__ void rnn_row_stats(const float* u, int H, int lane, float (&v)[RNN_NJ], float& mean, float& rstd) {
@@ -313,6 +354,7 @@ __device__ __forceinline__ void rnn_row_stats(const float* u, int H, int lane, f
 __global__ __launch_bounds__(64) void k_rnn_ln_fwd(RnnNormP p) {
   const int row = blockIdx.x, lane = threadIdx.x;
   if (row >= p.rows) return;
+  rnn_norm_run(p, blockIdx.y);
 #pragma unroll
   for (int j = 0; j < RNN_NJ; ++j) {
     const int c = lane + 64 * j;
@@ -336,6 +378,7 @@ __global__ __launch_bounds__(64) void k_rnn_ln_fwd(RnnNormP p) {
 __global__ __launch_bounds__(64) void k_rnn_ln_bwd(RnnNormP p) {
   const int row = blockIdx.x, lane = threadIdx.x;
   if (row >= p.rows) return;
+  rnn_norm_run(p, blockIdx.y);
   float v[RNN_NJ], mean, rstd;
   rnn_row_stats(p.u + (long)row * p.up, p.H, lane, v, mean, rstd);
   float dxh[RNN_NJ], xh[RNN_NJ];
@@ -370,38 +413,47 @@ __global__ __launch_bounds__(64) void k_rnn_ln_bwd(RnnNormP p) {
   }
 }
 
-// dz = (a + b) Swish'(z): the merge layer under the first residual block
-__global__ void k_rnn_swish_bwd(const float* __restrict__ a, int ap, const float* __restrict__ b, int bp, const float* __restrict__ z, int zp,
-                                float* __restrict__ dz, int dp, long rows, int cols) {
+// dz = (a + b) Swish'(z): the merge layer under the first residual block; run blockIdx.y at each matrix's run stride
+__global__ void k_rnn_swish_bwd(const float* __restrict__ a, int ap, long a_rs, const float* __restrict__ b, int bp, long b_rs,
+                                const float* __restrict__ z, int zp, long z_rs, float* __restrict__ dz, int dp, long d_rs, long rows, int cols) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= rows * cols) return;
+  const long run = blockIdx.y;
+  a += run * a_rs; b += run * b_rs; z += run * z_rs; dz += run * d_rs;
   const long r = e / cols; const int c = (int)(e - r * cols);
   dz[r * dp + c] = (a[r * ap + c] + b[r * bp + c]) * rnn_dswish(z[r * zp + c]);
 }
 
-// first level: chunk sums of 64 rows each in row order, [chunks][pn]
-__global__ void k_rnn_colsum_part(const float* __restrict__ part, long pn, long rows, float* __restrict__ chunk) {
+// first level: chunk sums of 64 rows each in row order, [chunks][pn]; run blockIdx.z
+__global__ void k_rnn_colsum_part(const float* __restrict__ part, long part_rs, long pn, long rows, float* __restrict__ chunk, long chunk_rs) {
   const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= pn) return;
+  part += (long)blockIdx.z * part_rs; chunk += (long)blockIdx.z * chunk_rs;
   const long r0 = (long)blockIdx.y * RNN_CHUNK, r1 = min(r0 + (long)RNN_CHUNK, rows);
   float s = 0.f;
   for (long r = r0; r < r1; ++r) s += part[r * pn + j];
   chunk[(long)blockIdx.y * pn + j] = s;
 }
 struct RnnNormDst { long gamma[RNN_MAX_NORMS], beta[RNN_MAX_NORMS]; };
-// second level: the chunks in order, into the gradient block at each norm's gamma / beta
-__global__ void k_rnn_colsum_fin(const float* __restrict__ chunk, long pn, int chunks, int H, RnnNormDst dst, float* __restrict__ G) {
+// second level: the chunks in order, into the gradient block at each norm's gamma / beta; run blockIdx.y (G at stride g_rs)
+__global__ void k_rnn_colsum_fin(const float* __restrict__ chunk, long chunk_rs, long pn, int chunks, int H, RnnNormDst dst, float* __restrict__ G,
+                                 long g_rs) {
   const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= pn) return;
+  chunk += (long)blockIdx.y * chunk_rs; G += (long)blockIdx.y * g_rs;
   float s = 0.f;
   for (int c = 0; c < chunks; ++c) s += chunk[(long)c * pn + j];
   const int slot = (int)(j / (2 * H)), c2 = (int)(j - (long)slot * 2 * H);
   G[c2 < H ? dst.gamma[slot] + c2 : dst.beta[slot] + (c2 - H)] = s;
 }
 
-// loss = mean over rows of mask[row] mean_d (pred - target)^2; dPRED = 2 (pred - target) mask / (rows od); one block, fixed order
-__global__ __launch_bounds__(256) void k_rnn_loss(const float* __restrict__ pred, int pp, const float* __restrict__ tgt, const float* __restrict__ msk,
-                                                  long rows, int od, float* __restrict__ dpred, float* loss_out, float* loss_last) {
+// loss = mean over rows of mask[row] mean_d (pred - target)^2; dPRED = 2 (pred - target) mask / (rows od); one block per run (pred and
+// dpred at stride p_rs, tgt / msk at tm_rs * od / tm_rs, the loss cells [run]), fixed order
+__global__ __launch_bounds__(256) void k_rnn_loss(const float* __restrict__ pred, int pp, long p_rs, const float* __restrict__ tgt,
+                                                  const float* __restrict__ msk, long tm_rs, long rows, int od, float* __restrict__ dpred,
+                                                  float* loss_out, float* loss_last) {
+  const long run = blockIdx.x;
+  pred += run * p_rs; dpred += run * p_rs; tgt += run * tm_rs * od; msk += run * tm_rs;
   const long n = rows * od;
   const float inv = 1.f / (float)n;
   float s = 0.f;
@@ -414,8 +466,8 @@ __global__ __launch_bounds__(256) void k_rnn_loss(const float* __restrict__ pred
   s = block_sum256_pairwise(s);
   if (threadIdx.x == 0) {
     const float l = s * inv;
-    *loss_out = l;
-    *loss_last = l;
+    loss_out[run] = l;
+    loss_last[run] = l;
   }
 }
 
@@ -447,38 +499,43 @@ using namespace orl;
 
 struct RnnLin { long w, b; };
 struct RnnNorm { long g, b; };
-// activations of one pass over `cap` rows (sequences x time steps); the backward's buffers when train
+// activations of one pass over `cap` rows (sequences x time steps) of `runs` runs, every matrix [runs][cap][pitch] (DevMat::s0 is the
+// run stride); the backward's buffers when train
 struct RnnWs {
-  long cap = 0; bool train = false;
+  long cap = 0; int runs = 0; bool train = false;
   DevMat X0, SI, ZI, UI, CAT, M0, ZM, PRED;
   std::vector<DevMat> GI, HO, R, Z, NN, HN, HP;       // per GRU layer
   std::vector<DevMat> SB, ZB, UB, XO;                 // per residual block
-  float* MK = nullptr;                                // [norms][cap][H] keep masks
+  float* MK = nullptr;                                // [runs][norms][cap][H] keep masks
   // backward
   DevMat dPRED, dX, DU, DZ, DT, dZM, dCAT, dGI, dGH, dXL[2];
-  float *part = nullptr, *chunk = nullptr;
+  float *part = nullptr, *chunk = nullptr;            // [runs][cap][pn], [runs][chunks of cap][pn]
+  long mk_rs = 0, part_rs = 0, chunk_rs = 0;          // their run strides
 };
 
 struct orl_rnn {
   orl_rnn_config c;
   int in, od, H, L, nb, B, Tmax, norms;
+  int R = 1;                                      // runs: the blocks below are [R][P], run r's at r * P
   long P = 0;
   RnnLin wih[RNN_MAX_LAYERS], whh[RNN_MAX_LAYERS], lin_in, lin_merge, lin_out, lin_b[ORL_MAX_HIDDEN];
   RnnNorm norm_in, norm_b[ORL_MAX_HIDDEN];
   TensorTable tensors;
   hipStream_t stream = nullptr;
   float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *grads = nullptr;
-  float* slabs = nullptr; int max_slabs = 1;      // [max_slabs][P]: the k ranges of the split weight gradients, summed into grads
-  long long kstep = 0;
+  float* slabs = nullptr; int max_slabs = 1;      // [max_slabs][R][P]: the k ranges of the split weight gradients, summed into grads
+  long long kstep = 0;                            // shared by the runs
   size_t lds_fwd = 0, lds_bwd = 0;
-  // dataset
+  // dataset (one, read by every run)
   float *d_in = nullptr, *d_tgt = nullptr, *d_msk = nullptr; long n_data = 0; int T = 0;
   RnnWs tw, ew;
+  // TGT [R][cap][od], MSK [R][cap], loss_cell [R], loss_steps [steps][R]
   float *TGT = nullptr, *MSK = nullptr, *loss_cell = nullptr, *loss_steps = nullptr; long loss_cap = 0;
   long long* idx_d = nullptr; long idx_cap = 0;
   // forward staging
-  float *fIn = nullptr, *fLast = nullptr, *fAll = nullptr; long f_cap = 0;
-  const RnnWs* last_ws = nullptr; long last_rows = 0;
+  float *fIn = nullptr, *fLast = nullptr, *fAll = nullptr; long f_cap = 0; int f_runs = 0;
+  // what the taps read: the workspace of the last pass, its rows, and the runs it held (run last_r0 + i at workspace slot i)
+  const RnnWs* last_ws = nullptr; long last_rows = 0; int last_r0 = 0, last_nr = 0;
   // orl_rnn_profile: events of the last step -- 0 start, 1 after the forward, 2 after the backward, 3 after Adam, then per layer
   // [before, after] of the forward scan and of the backward scan
   bool prof = false, prof_valid = false;
@@ -486,14 +543,16 @@ struct orl_rnn {
   DevAllocs mem{"orl_rnn"};
 };
 
-static int rnn_mat(orl_rnn* d, DevMat& v, long rows, int cols) {
+static int rnn_mat_runs(orl_rnn* d, DevMat& v, long rows, int cols, int runs) {
   d->mem.free(v.p);
   v.pitch = v.lim = rup4(cols);
-  return d->mem.alloc(&v.p, (size_t)rows * v.pitch);
+  v.s0 = rows * v.pitch;
+  return d->mem.alloc(&v.p, (size_t)runs * rows * v.pitch);
 }
 
-static int rnn_ws_alloc(orl_rnn* d, RnnWs& w, long rows, bool train) {
+static int rnn_ws_alloc(orl_rnn* d, RnnWs& w, long rows, bool train, int runs) {
   const int H = d->H, L = d->L, nb = d->nb;
+  auto rnn_mat = [runs](orl_rnn* o, DevMat& v, long n, int cols) { return rnn_mat_runs(o, v, n, cols, runs); };
   w.GI.resize(L); w.HO.resize(L); w.R.resize(L); w.Z.resize(L); w.NN.resize(L); w.HN.resize(L); w.HP.resize(L);
   w.SB.resize(nb); w.ZB.resize(nb); w.UB.resize(nb); w.XO.resize(nb);
   bool bad = rnn_mat(d, w.X0, rows, d->in) || rnn_mat(d, w.SI, rows, H) || rnn_mat(d, w.ZI, rows, H) || rnn_mat(d, w.UI, rows, H) ||
@@ -512,15 +571,21 @@ static int rnn_ws_alloc(orl_rnn* d, RnnWs& w, long rows, bool train) {
     bad = rnn_mat(d, w.dPRED, rows, d->od) || rnn_mat(d, w.dX, rows, H) || rnn_mat(d, w.DU, rows, H) || rnn_mat(d, w.DZ, rows, H) ||
           rnn_mat(d, w.DT, rows, H) || rnn_mat(d, w.dZM, rows, H) || rnn_mat(d, w.dCAT, rows, 2 * H) || rnn_mat(d, w.dGI, rows, 3 * H) ||
           rnn_mat(d, w.dGH, rows, 3 * H) || rnn_mat(d, w.dXL[0], rows, H) || rnn_mat(d, w.dXL[1], rows, H) ||
-          (d->mem.free(w.MK), d->mem.alloc(&w.MK, (size_t)d->norms * rows * H)) ||
-          (d->mem.free(w.part), d->mem.alloc(&w.part, (size_t)rows * pn)) || (d->mem.free(w.chunk), d->mem.alloc(&w.chunk, (size_t)chunks * pn));
+          (d->mem.free(w.MK), d->mem.alloc(&w.MK, (size_t)runs * d->norms * rows * H)) ||
+          (d->mem.free(w.part), d->mem.alloc(&w.part, (size_t)runs * rows * pn)) ||
+          (d->mem.free(w.chunk), d->mem.alloc(&w.chunk, (size_t)runs * chunks * pn));
+    w.mk_rs = (long)d->norms * rows * H; w.part_rs = rows * pn; w.chunk_rs = chunks * pn;
   }
   if (bad) return -1;
-  w.cap = rows; w.train = train;
+  w.cap = rows; w.runs = runs; w.train = train;
   return 0;
 }
 
-// ---- the matrix products (csrc/gemm.h), one problem per launch ----
+// ---- the matrix products (csrc/gemm.h): one launch per product, the runs as its batch (z0) ----
+// The runs r0 .. r0 + n of the object that a pass computes, at slots 0 .. n of its workspace.  The tile configuration and the slab count
+// of every product are functions of the per-run shape only, so an output element's reduction order -- and run r's bits -- do not depend
+// on how many runs share the launch.
+struct RnnRuns { int r0, n; };
 // few rows: 16 x 64 tiles while they give at most four rounds of workgroups on the 256 CUs, 64 x 64 beyond; many rows: the 64 x 256 tile
 static int rnn_cfg(int M, int N) {
   if (N <= 16) return CFG_TALL;
@@ -534,29 +599,33 @@ static int rnn_wgrad_cfg(int M, int N) {
   const long small_tiles = (long)((M + 15) / 16) * ((N + 63) / 64);
   return small_tiles <= 1024 ? CFG_SMALL : CFG_MID;
 }
-static LinearP rnn_linear(float* block, const RnnLin& l, int in, int out) { return {{block + l.w, 0, 0}, {block + l.b, 0, 0}, in, out, false, 1}; }
+// layer l of the runs' blocks [.][P] starting at `block`
+static LinearP rnn_linear(const orl_rnn* d, float* block, const RnnLin& l, int in, int out) {
+  return {{block + l.w, d->P, 0}, {block + l.b, d->P, 0}, in, out, false, 1};
+}
+static float* rnn_params_of(orl_rnn* d, const RnnRuns& rs) { return d->params + (long)rs.r0 * d->P; }
 // Y = X W^T + b, or swish of it with the pre-activation kept in Z (same pitch as Y) when Z is given
-static int rnn_fwd(orl_rnn* d, const DevMat& X, int M, const RnnLin& l, int in, int out, const DevMat& Y, bool swish, float* Z) {
-  GemmP p = linear_fwd_p(X, M, rnn_linear(d->params, l, in, out), Y);
+static int rnn_fwd(orl_rnn* d, const RnnRuns& rs, const DevMat& X, int M, const RnnLin& l, int in, int out, const DevMat& Y, bool swish, float* Z) {
+  GemmP p = linear_fwd_p(X, M, rnn_linear(d, rnn_params_of(d, rs), l, in, out), Y);
   p.z_out = Z;
   const bool kpad = X.pitch >= rup4(p.K);
   const int cfg = rnn_cfg(p.M, p.N);
-  return gemm_done(swish ? launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_SWISH>(cfg, p, 1, d->stream, kpad, false, P_F32)
-                         : launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(cfg, p, 1, d->stream, kpad, false, P_F32), "orl_rnn forward");
+  return gemm_done(swish ? launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_SWISH>(cfg, p, rs.n, d->stream, kpad, false, P_F32)
+                         : launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(cfg, p, rs.n, d->stream, kpad, false, P_F32), "orl_rnn forward");
 }
 // dX = dY W
-static int rnn_dgrad(orl_rnn* d, const DevMat& dY, int M, const RnnLin& l, int in, int out, const DevMat& dX) {
-  const GemmP p = linear_dgrad_p(dY, M, rnn_linear(d->params, l, in, out), dX);
-  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(rnn_cfg(p.M, p.N), p, 1, d->stream, dY.pitch >= rup4(p.K), false, P_F32), "orl_rnn dgrad");
+static int rnn_dgrad(orl_rnn* d, const RnnRuns& rs, const DevMat& dY, int M, const RnnLin& l, int in, int out, const DevMat& dX) {
+  const GemmP p = linear_dgrad_p(dY, M, rnn_linear(d, rnn_params_of(d, rs), l, in, out), dX);
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(rnn_cfg(p.M, p.N), p, rs.n, d->stream, dY.pitch >= rup4(p.K), false, P_F32), "orl_rnn dgrad");
 }
 // The weight gradients reduce over all rows * T rows of a step and have few output tiles (600 x 200 at the default shape), so the
 // reduction is cut into k ranges of at least 256 rows, each into a slab of its own; k_rnn_slab_sum adds the slabs in order.
 static int rnn_slabs(const orl_rnn* d, long N) { return (int)std::max(1L, std::min((long)d->max_slabs, N / 256)); }
-// dW = dY^T X ([out][in]) and db = the column sums of dY into the slabs
+// dW = dY^T X ([out][in]) and db = the column sums of dY into the slabs ([slab][R][P]; the backward runs every run of the object)
 static int rnn_wgrad(orl_rnn* d, const DevMat& dY, const DevMat& X, int M, const RnnLin& l, int in, int out) {
-  GemmP p = linear_wgrad_p(dY, X, M, rnn_linear(d->slabs, l, in, out));
-  p.ksplit = rnn_slabs(d, M); p.c_ks = d->P; p.bo_ks = d->P;
-  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(rnn_wgrad_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32), "orl_rnn wgrad");
+  GemmP p = linear_wgrad_p(dY, X, M, rnn_linear(d, d->slabs, l, in, out));
+  p.ksplit = rnn_slabs(d, M); p.c_ks = (long)d->R * d->P; p.bo_ks = p.c_ks;
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(rnn_wgrad_cfg(p.M, p.N), p, d->R, d->stream, false, false, P_F32), "orl_rnn wgrad");
 }
 
 static int rnn_ew_grid(long n) { return (int)((n + 255) / 256); }
@@ -565,87 +634,97 @@ static void rnn_mark(orl_rnn* d, bool on, int i) {
   if (on && d->prof) hipEventRecord(d->ev[i], d->stream);
 }
 
-static RnnNormP rnn_norm_params(orl_rnn* d, const RnnWs& w, int slot, long N, const DevMat& S, const DevMat& U, const RnnNorm& nm, bool drop) {
+static RnnNormP rnn_norm_params(orl_rnn* d, const RnnRuns& rs, const RnnWs& w, int slot, long N, const DevMat& S, const DevMat& U, const RnnNorm& nm,
+                                bool drop) {
   RnnNormP p;
   memset(&p, 0, sizeof(p));
   p.rows = (int)N; p.H = d->H;
-  p.s = S.p; p.sp = S.pitch;
-  if (drop) { p.mask = w.MK + (size_t)slot * w.cap * d->H; p.scale = 1.f / (1.f - d->c.dropout_rate); }
-  p.gamma = d->params + nm.g; p.beta = d->params + nm.b;
-  p.u = U.p; p.up = U.pitch;
+  p.s = S.p; p.sp = S.pitch; p.s_rs = S.s0;
+  if (drop) { p.mask = w.MK + (size_t)slot * w.cap * d->H; p.mask_rs = w.mk_rs; p.scale = 1.f / (1.f - d->c.dropout_rate); }
+  p.gamma = rnn_params_of(d, rs) + nm.g; p.beta = rnn_params_of(d, rs) + nm.b; p.par_rs = d->P;
+  p.u = U.p; p.up = U.pitch; p.u_rs = U.s0;
   return p;
 }
 
-// the forward over `rows` sequences of T steps of workspace w (X0 in place); train: the scans save what the backward reads, the
-// pre-activations are kept and the dropouts read the keep masks of w.MK
-static int rnn_forward(orl_rnn* d, RnnWs& w, int rows, int T, bool train) {
+// the forward of the runs rs over `rows` sequences of T steps of workspace w (X0 in place; shared_x: every run reads slot 0's X0); train:
+// the scans save what the backward reads, the pre-activations are kept and the dropouts read the keep masks of w.MK
+static int rnn_forward(orl_rnn* d, const RnnRuns& rs, RnnWs& w, int rows, int T, bool train, bool shared_x) {
   const int H = d->H;
   const long N = (long)rows * T;
   const bool drop = train && d->c.dropout_rate > 0.f;
-  DevMat X = w.X0;
+  float* params = rnn_params_of(d, rs);
+  DevMat X0 = w.X0;
+  if (shared_x) X0.s0 = 0;
+  DevMat X = X0;
   for (int l = 0; l < d->L; ++l) {
-    if (rnn_fwd(d, X, (int)N, d->wih[l], l ? H : d->in, 3 * H, w.GI[l], false, nullptr)) return -1;
+    if (rnn_fwd(d, rs, X, (int)N, d->wih[l], l ? H : d->in, 3 * H, w.GI[l], false, nullptr)) return -1;
     RnnScanP sp;
     memset(&sp, 0, sizeof(sp));
     sp.rows = rows; sp.T = T; sp.H = H;
-    sp.gi = w.GI[l].p; sp.gip = w.GI[l].pitch;
-    sp.whh = d->params + d->whh[l].w; sp.bhh = d->params + d->whh[l].b;
-    sp.ho = w.HO[l].p; sp.hop = w.HO[l].pitch;
-    if (train) { sp.r = w.R[l].p; sp.z = w.Z[l].p; sp.n = w.NN[l].p; sp.hn = w.HN[l].p; sp.hp = w.HP[l].p; sp.sp = w.R[l].pitch; }
+    sp.gi = w.GI[l].p; sp.gip = w.GI[l].pitch; sp.gi_rs = w.GI[l].s0;
+    sp.whh = params + d->whh[l].w; sp.bhh = params + d->whh[l].b; sp.par_rs = d->P;
+    sp.ho = w.HO[l].p; sp.hop = w.HO[l].pitch; sp.ho_rs = w.HO[l].s0;
+    if (train) {
+      sp.r = w.R[l].p; sp.z = w.Z[l].p; sp.n = w.NN[l].p; sp.hn = w.HN[l].p; sp.hp = w.HP[l].p; sp.sp = w.R[l].pitch; sp.s_rs = w.R[l].s0;
+    }
     rnn_mark(d, train, 4 + 4 * l);
-    DEV_LAUNCH(d->stream, k_rnn_scan_fwd, dim3((rows + RNN_RB - 1) / RNN_RB), dim3(64 * RNN_FWD_WAVES), d->lds_fwd, sp);
+    DEV_LAUNCH(d->stream, k_rnn_scan_fwd, dim3((rows + RNN_RB - 1) / RNN_RB, rs.n), dim3(64 * RNN_FWD_WAVES), d->lds_fwd, sp);
     rnn_mark(d, train, 5 + 4 * l);
     X = w.HO[l];
   }
-  if (rnn_fwd(d, w.X0, (int)N, d->lin_in, d->in, H, w.SI, true, train ? w.ZI.p : nullptr)) return -1;
-  RnnNormP n0 = rnn_norm_params(d, w, 0, N, w.SI, w.UI, d->norm_in, drop);
-  n0.out = w.CAT.p; n0.op = w.CAT.pitch;
-  DEV_LAUNCH(d->stream, k_rnn_ln_fwd, dim3((unsigned)N), dim3(64), 0, n0);
-  if (rnn_fwd(d, w.CAT, (int)N, d->lin_merge, 2 * H, H, w.M0, true, train ? w.ZM.p : nullptr)) return -1;
+  if (rnn_fwd(d, rs, X0, (int)N, d->lin_in, d->in, H, w.SI, true, train ? w.ZI.p : nullptr)) return -1;
+  RnnNormP n0 = rnn_norm_params(d, rs, w, 0, N, w.SI, w.UI, d->norm_in, drop);
+  n0.out = w.CAT.p; n0.op = w.CAT.pitch; n0.out_rs = w.CAT.s0;
+  DEV_LAUNCH(d->stream, k_rnn_ln_fwd, dim3((unsigned)N, rs.n), dim3(64), 0, n0);
+  if (rnn_fwd(d, rs, w.CAT, (int)N, d->lin_merge, 2 * H, H, w.M0, true, train ? w.ZM.p : nullptr)) return -1;
   X = w.M0;
   for (int i = 0; i < d->nb; ++i) {
-    if (rnn_fwd(d, X, (int)N, d->lin_b[i], H, H, w.SB[i], true, train ? w.ZB[i].p : nullptr)) return -1;
-    RnnNormP nb = rnn_norm_params(d, w, 1 + i, N, w.SB[i], w.UB[i], d->norm_b[i], drop);
-    nb.res = X.p; nb.rp = X.pitch;
-    nb.out = w.XO[i].p; nb.op = w.XO[i].pitch;
-    DEV_LAUNCH(d->stream, k_rnn_ln_fwd, dim3((unsigned)N), dim3(64), 0, nb);
+    if (rnn_fwd(d, rs, X, (int)N, d->lin_b[i], H, H, w.SB[i], true, train ? w.ZB[i].p : nullptr)) return -1;
+    RnnNormP nb = rnn_norm_params(d, rs, w, 1 + i, N, w.SB[i], w.UB[i], d->norm_b[i], drop);
+    nb.res = X.p; nb.rp = X.pitch; nb.res_rs = X.s0;
+    nb.out = w.XO[i].p; nb.op = w.XO[i].pitch; nb.out_rs = w.XO[i].s0;
+    DEV_LAUNCH(d->stream, k_rnn_ln_fwd, dim3((unsigned)N, rs.n), dim3(64), 0, nb);
     X = w.XO[i];
   }
-  return rnn_fwd(d, X, (int)N, d->lin_out, H, d->od, w.PRED, false, nullptr);
+  return rnn_fwd(d, rs, X, (int)N, d->lin_out, H, d->od, w.PRED, false, nullptr);
 }
 
-// backward from dPRED over the first rows * T rows of the training workspace
+// backward of every run from dPRED over the first rows * T rows of the training workspace
 static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
-  const int H = d->H;
+  const int H = d->H, R = d->R;
+  const RnnRuns rs{0, R};
   const long N = (long)rows * T;
   const long pn = (long)d->norms * 2 * H;
   const bool drop = d->c.dropout_rate > 0.f;
   const DevMat& last = w.XO[d->nb - 1];
-  if (rnn_wgrad(d, w.dPRED, last, (int)N, d->lin_out, H, d->od) || rnn_dgrad(d, w.dPRED, (int)N, d->lin_out, H, d->od, w.dX)) return -1;
+  if (rnn_wgrad(d, w.dPRED, last, (int)N, d->lin_out, H, d->od) || rnn_dgrad(d, rs, w.dPRED, (int)N, d->lin_out, H, d->od, w.dX)) return -1;
   // residual block i: dOut = dX (block nb - 1: the head's dgrad) or DU + DT of the block above
   for (int i = d->nb - 1; i >= 0; --i) {
     const DevMat& Xin = i ? w.XO[i - 1] : w.M0;
-    RnnNormP nb = rnn_norm_params(d, w, 1 + i, N, w.SB[i], w.UB[i], d->norm_b[i], drop);
-    if (i == d->nb - 1) { nb.nterm = 1; nb.g[0] = w.dX.p; nb.gpitch[0] = w.dX.pitch; }
-    else { nb.nterm = 2; nb.g[0] = w.DU.p; nb.gpitch[0] = w.DU.pitch; nb.g[1] = w.DT.p; nb.gpitch[1] = w.DT.pitch; }
-    nb.zpre = w.ZB[i].p; nb.zp = w.ZB[i].pitch;
-    nb.du = w.DU.p; nb.dup = w.DU.pitch;            // (a lane overwrites only the elements it has read itself)
-    nb.dz = w.DZ.p; nb.dzp = w.DZ.pitch;
-    nb.part = w.part + (long)(1 + i) * 2 * H; nb.pn = pn;
-    DEV_LAUNCH(d->stream, k_rnn_ln_bwd, dim3((unsigned)N), dim3(64), 0, nb);
-    if (rnn_wgrad(d, w.DZ, Xin, (int)N, d->lin_b[i], H, H) || rnn_dgrad(d, w.DZ, (int)N, d->lin_b[i], H, H, w.DT)) return -1;
+    RnnNormP nb = rnn_norm_params(d, rs, w, 1 + i, N, w.SB[i], w.UB[i], d->norm_b[i], drop);
+    if (i == d->nb - 1) { nb.nterm = 1; nb.g[0] = w.dX.p; nb.gpitch[0] = w.dX.pitch; nb.g_rs[0] = w.dX.s0; }
+    else {
+      nb.nterm = 2; nb.g[0] = w.DU.p; nb.gpitch[0] = w.DU.pitch; nb.g_rs[0] = w.DU.s0;
+      nb.g[1] = w.DT.p; nb.gpitch[1] = w.DT.pitch; nb.g_rs[1] = w.DT.s0;
+    }
+    nb.zpre = w.ZB[i].p; nb.zp = w.ZB[i].pitch; nb.z_rs = w.ZB[i].s0;
+    nb.du = w.DU.p; nb.dup = w.DU.pitch; nb.du_rs = w.DU.s0;       // (a lane overwrites only the elements it has read itself)
+    nb.dz = w.DZ.p; nb.dzp = w.DZ.pitch; nb.dz_rs = w.DZ.s0;
+    nb.part = w.part + (long)(1 + i) * 2 * H; nb.pn = pn; nb.part_rs = w.part_rs;
+    DEV_LAUNCH(d->stream, k_rnn_ln_bwd, dim3((unsigned)N, R), dim3(64), 0, nb);
+    if (rnn_wgrad(d, w.DZ, Xin, (int)N, d->lin_b[i], H, H) || rnn_dgrad(d, rs, w.DZ, (int)N, d->lin_b[i], H, H, w.DT)) return -1;
   }
-  DEV_LAUNCH(d->stream, k_rnn_swish_bwd, dim3(rnn_ew_grid(N * H)), dim3(256), 0, w.DU.p, w.DU.pitch, w.DT.p, w.DT.pitch, w.ZM.p, w.ZM.pitch,
-              w.dZM.p, w.dZM.pitch, N, H);
-  if (rnn_wgrad(d, w.dZM, w.CAT, (int)N, d->lin_merge, 2 * H, H) || rnn_dgrad(d, w.dZM, (int)N, d->lin_merge, 2 * H, H, w.dCAT)) return -1;
+  DEV_LAUNCH(d->stream, k_rnn_swish_bwd, dim3(rnn_ew_grid(N * H), R), dim3(256), 0, w.DU.p, w.DU.pitch, w.DU.s0, w.DT.p, w.DT.pitch, w.DT.s0,
+              w.ZM.p, w.ZM.pitch, w.ZM.s0, w.dZM.p, w.dZM.pitch, w.dZM.s0, N, H);
+  if (rnn_wgrad(d, w.dZM, w.CAT, (int)N, d->lin_merge, 2 * H, H) || rnn_dgrad(d, rs, w.dZM, (int)N, d->lin_merge, 2 * H, H, w.dCAT)) return -1;
   // the input block (no residual, no gradient to the net's input)
   {
-    RnnNormP n0 = rnn_norm_params(d, w, 0, N, w.SI, w.UI, d->norm_in, drop);
-    n0.nterm = 1; n0.g[0] = w.dCAT.p; n0.gpitch[0] = w.dCAT.pitch;
-    n0.zpre = w.ZI.p; n0.zp = w.ZI.pitch;
-    n0.dz = w.DZ.p; n0.dzp = w.DZ.pitch;
-    n0.part = w.part; n0.pn = pn;
-    DEV_LAUNCH(d->stream, k_rnn_ln_bwd, dim3((unsigned)N), dim3(64), 0, n0);
+    RnnNormP n0 = rnn_norm_params(d, rs, w, 0, N, w.SI, w.UI, d->norm_in, drop);
+    n0.nterm = 1; n0.g[0] = w.dCAT.p; n0.gpitch[0] = w.dCAT.pitch; n0.g_rs[0] = w.dCAT.s0;
+    n0.zpre = w.ZI.p; n0.zp = w.ZI.pitch; n0.z_rs = w.ZI.s0;
+    n0.dz = w.DZ.p; n0.dzp = w.DZ.pitch; n0.dz_rs = w.DZ.s0;
+    n0.part = w.part; n0.pn = pn; n0.part_rs = w.part_rs;
+    DEV_LAUNCH(d->stream, k_rnn_ln_bwd, dim3((unsigned)N, R), dim3(64), 0, n0);
     if (rnn_wgrad(d, w.DZ, w.X0, (int)N, d->lin_in, d->in, H)) return -1;
   }
   {
@@ -654,8 +733,8 @@ static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
     memset(&dst, 0, sizeof(dst));
     dst.gamma[0] = d->norm_in.g; dst.beta[0] = d->norm_in.b;
     for (int i = 0; i < d->nb; ++i) { dst.gamma[1 + i] = d->norm_b[i].g; dst.beta[1 + i] = d->norm_b[i].b; }
-    DEV_LAUNCH(d->stream, k_rnn_colsum_part, dim3(rnn_ew_grid(pn), chunks), dim3(256), 0, w.part, pn, N, w.chunk);
-    DEV_LAUNCH(d->stream, k_rnn_colsum_fin, dim3(rnn_ew_grid(pn)), dim3(256), 0, w.chunk, pn, chunks, H, dst, d->slabs);
+    DEV_LAUNCH(d->stream, k_rnn_colsum_part, dim3(rnn_ew_grid(pn), chunks, R), dim3(256), 0, w.part, w.part_rs, pn, N, w.chunk, w.chunk_rs);
+    DEV_LAUNCH(d->stream, k_rnn_colsum_fin, dim3(rnn_ew_grid(pn), R), dim3(256), 0, w.chunk, w.chunk_rs, pn, chunks, H, dst, d->slabs, d->P);
   }
   // the GRU layers top down: the top layer's dh is the right half of the merge layer's input gradient
   DevMat dOut = w.dCAT.cols(H);
@@ -663,48 +742,51 @@ static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
     RnnScanBP bp;
     memset(&bp, 0, sizeof(bp));
     bp.rows = rows; bp.T = T; bp.H = H;
-    bp.dout = dOut.p; bp.dop = dOut.pitch;
-    bp.whh = d->params + d->whh[l].w;
-    bp.r = w.R[l].p; bp.z = w.Z[l].p; bp.n = w.NN[l].p; bp.hn = w.HN[l].p; bp.hp = w.HP[l].p; bp.sp = w.R[l].pitch;
-    bp.dgi = w.dGI.p; bp.dgh = w.dGH.p; bp.gp = w.dGI.pitch;
+    bp.dout = dOut.p; bp.dop = dOut.pitch; bp.do_rs = dOut.s0;
+    bp.whh = d->params + d->whh[l].w; bp.par_rs = d->P;
+    bp.r = w.R[l].p; bp.z = w.Z[l].p; bp.n = w.NN[l].p; bp.hn = w.HN[l].p; bp.hp = w.HP[l].p; bp.sp = w.R[l].pitch; bp.s_rs = w.R[l].s0;
+    bp.dgi = w.dGI.p; bp.dgh = w.dGH.p; bp.gp = w.dGI.pitch; bp.g_rs = w.dGI.s0;
     rnn_mark(d, true, 6 + 4 * l);
-    DEV_LAUNCH(d->stream, k_rnn_scan_bwd, dim3((rows + RNN_RB - 1) / RNN_RB), dim3(64 * RNN_BWD_WAVES), d->lds_bwd, bp);
+    DEV_LAUNCH(d->stream, k_rnn_scan_bwd, dim3((rows + RNN_RB - 1) / RNN_RB, R), dim3(64 * RNN_BWD_WAVES), d->lds_bwd, bp);
     rnn_mark(d, true, 7 + 4 * l);
     const DevMat& Xl = l ? w.HO[l - 1] : w.X0;
     if (rnn_wgrad(d, w.dGH, w.HP[l], (int)N, d->whh[l], H, 3 * H) || rnn_wgrad(d, w.dGI, Xl, (int)N, d->wih[l], l ? H : d->in, 3 * H)) return -1;
     if (l == 0) break;
-    if (rnn_dgrad(d, w.dGI, (int)N, d->wih[l], H, 3 * H, w.dXL[l & 1])) return -1;
+    if (rnn_dgrad(d, rs, w.dGI, (int)N, d->wih[l], H, 3 * H, w.dXL[l & 1])) return -1;
     dOut = w.dXL[l & 1];
   }
-  DEV_LAUNCH(d->stream, k_rnn_slab_sum, dim3(rnn_ew_grid(d->P)), dim3(256), 0, (const float*)d->slabs, d->P, rnn_slabs(d, N), d->grads);
+  const long RP = (long)R * d->P;
+  DEV_LAUNCH(d->stream, k_rnn_slab_sum, dim3(rnn_ew_grid(RP)), dim3(256), 0, (const float*)d->slabs, RP, rnn_slabs(d, N), d->grads);
   return 0;
 }
 
-// one optimizer step on the sequences idx[0 .. rows) (device); the dropouts' keep masks are in tw.MK already when forced
-static int rnn_enqueue_step(orl_rnn* d, const long long* idx, int rows, bool forced_masks, float* loss_dst) {
+// one optimizer step of every run, run r on the sequences idx[r * idx_rs + (0 .. rows)) (device); the dropouts' keep masks are in tw.MK
+// already when forced.  loss_dst: [R]
+static int rnn_enqueue_step(orl_rnn* d, const long long* idx, long idx_rs, int rows, bool forced_masks, float* loss_dst) {
   RnnWs& w = d->tw;
-  const int T = d->T, H = d->H;
-  const long N = (long)rows * T;
+  const int T = d->T, H = d->H, R = d->R;
+  const long N = (long)rows * T, RP = (long)R * d->P;
   rnn_mark(d, true, 0);
-  DEV_LAUNCH(d->stream, k_rnn_gather, dim3(rnn_ew_grid(N * (d->in + d->od + 1))), dim3(256), 0, d->d_in, d->d_tgt, d->d_msk, idx, d->n_data, T,
-              d->in, d->od, rows, w.X0.p, w.X0.pitch, d->TGT, d->MSK);
+  DEV_LAUNCH(d->stream, k_rnn_gather, dim3(rnn_ew_grid(N * (d->in + d->od + 1)), R), dim3(256), 0, d->d_in, d->d_tgt, d->d_msk, idx, idx_rs,
+              d->n_data, T, d->in, d->od, rows, w.X0.p, w.X0.pitch, w.X0.s0, d->TGT, d->MSK, w.cap);
   if (d->c.dropout_rate > 0.f && !forced_masks)
     for (int s = 0; s < d->norms; ++s)
-      DEV_LAUNCH(d->stream, k_rnn_mask, dim3(rnn_ew_grid(N * (H / 4))), dim3(256), 0, w.MK + (size_t)s * w.cap * H, N, H, 1.f - d->c.dropout_rate,
-                  d->c.seed, (uint64_t)d->kstep, (uint32_t)s);
-  if (rnn_forward(d, w, rows, T, true)) return -1;
+      DEV_LAUNCH(d->stream, k_rnn_mask, dim3(rnn_ew_grid(N * (H / 4)), R), dim3(256), 0, w.MK + (size_t)s * w.cap * H, w.mk_rs, N, H,
+                  1.f - d->c.dropout_rate, d->c.seed, (uint64_t)d->kstep, (uint32_t)s);
+  if (rnn_forward(d, RnnRuns{0, R}, w, rows, T, true, false)) return -1;
   rnn_mark(d, true, 1);
-  DEV_LAUNCH(d->stream, k_rnn_loss, dim3(1), dim3(256), 0, w.PRED.p, w.PRED.pitch, d->TGT, d->MSK, N, d->od, w.dPRED.p, loss_dst, d->loss_cell);
+  DEV_LAUNCH(d->stream, k_rnn_loss, dim3(R), dim3(256), 0, w.PRED.p, w.PRED.pitch, w.PRED.s0, d->TGT, d->MSK, w.cap, N, d->od, w.dPRED.p, loss_dst,
+              d->loss_cell);
   if (rnn_backward(d, w, rows, T)) return -1;
   rnn_mark(d, true, 2);
   const double tt = (double)(d->kstep + 1);
   const double bc1 = 1.0 - std::pow(d->c.adam_beta1, tt), bc2 = 1.0 - std::pow(d->c.adam_beta2, tt);
-  DEV_LAUNCH(d->stream, k_rnn_adam, dim3(rnn_ew_grid(d->P)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, d->P, (float)(d->c.lr / bc1),
+  DEV_LAUNCH(d->stream, k_rnn_adam, dim3(rnn_ew_grid(RP)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, RP, (float)(d->c.lr / bc1),
               (float)std::sqrt(bc2), (float)(1.0 - d->c.adam_beta1), (float)d->c.adam_beta2, (float)(1.0 - d->c.adam_beta2), (float)d->c.adam_eps);
   rnn_mark(d, true, 3);
   d->prof_valid = d->prof;
   d->kstep += 1;
-  d->last_ws = &w; d->last_rows = N;
+  d->last_ws = &w; d->last_rows = N; d->last_r0 = 0; d->last_nr = R;
   return 0;
 }
 
@@ -717,7 +799,7 @@ static int rnn_ready(orl_rnn* d, const char* what, bool data) {
 
 // the refusals of a config; empty = supported
 static std::string rnn_refusal(const orl_rnn_config& c) {
-  if (c.n_runs != 1) return "one run per object (n_runs > 1 is not supported)";
+  if (c.n_runs < 1 || c.n_runs > 64) return "n_runs must be in [1, 64]";
   if (c.precision != 0) return "precision 0 (fp32 MFMA) only; the split precisions are not supported";
   if (c.input_dim < 1 || c.output_dim < 1) return "input_dim and output_dim must be positive";
   if (c.n_hidden < 2 || c.n_hidden > ORL_MAX_HIDDEN + 1)
@@ -768,7 +850,7 @@ static long rnn_layout(orl_rnn* d) {
 static void rnn_dims(orl_rnn* d, const orl_rnn_config& c) {
   d->c = c;
   d->in = c.input_dim; d->od = c.output_dim; d->H = c.hidden[0]; d->L = c.rnn_num_layers; d->nb = c.n_hidden - 1;
-  d->norms = d->nb + 1; d->B = c.batch_size; d->Tmax = c.max_seq_len;
+  d->norms = d->nb + 1; d->B = c.batch_size; d->Tmax = c.max_seq_len; d->R = c.n_runs;
   d->P = rnn_layout(d);
 }
 
@@ -811,13 +893,14 @@ int orl_rnn_create(const orl_rnn_config* cfg, orl_rnn** out) {
   bool bad = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess;
   if (!bad && d->lds_bwd > 64 * 1024)
     bad = hipFuncSetAttribute((const void*)k_rnn_scan_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->lds_bwd) != hipSuccess;
+  const size_t RP = (size_t)d->R * d->P;
   if (c.external_arena) d->params = (float*)c.external_arena;
-  else bad = bad || d->mem.alloc(&d->params, d->P);
+  else bad = bad || d->mem.alloc(&d->params, RP);
   const long cap = (long)d->B * d->Tmax;
-  d->max_slabs = (int)std::max(1L, std::min({8L, cap / 256, (64L << 20) / d->P}));
-  bad = bad || d->mem.alloc(&d->slabs, (size_t)d->max_slabs * d->P) || d->mem.alloc(&d->adam_m, d->P) || d->mem.alloc(&d->adam_v, d->P) || d->mem.alloc(&d->grads, d->P) ||
-        rnn_ws_alloc(d, d->tw, cap, true) || d->mem.alloc(&d->TGT, (size_t)cap * d->od) || d->mem.alloc(&d->MSK, (size_t)cap) ||
-        d->mem.alloc(&d->loss_cell, 1);
+  d->max_slabs = (int)std::max(1L, std::min({8L, cap / 256, (64L << 20) / d->P}));      // (per run: the slab count never depends on R)
+  bad = bad || d->mem.alloc(&d->slabs, (size_t)d->max_slabs * RP) || d->mem.alloc(&d->adam_m, RP) || d->mem.alloc(&d->adam_v, RP) ||
+        d->mem.alloc(&d->grads, RP) || rnn_ws_alloc(d, d->tw, cap, true, d->R) || d->mem.alloc(&d->TGT, (size_t)d->R * cap * d->od) ||
+        d->mem.alloc(&d->MSK, (size_t)d->R * cap) || d->mem.alloc(&d->loss_cell, d->R);
   if (bad) {
     const std::string msg = orl_last_error();
     orl_rnn_destroy(d);
@@ -845,15 +928,38 @@ int orl_rnn_tensor(orl_rnn* d, int idx, char* name, int name_cap, int64_t* offse
 }
 
 static float* rnn_block_of(orl_rnn* d, int which) { return which == 0 ? d->params : which == 1 ? d->adam_m : which == 2 ? d->adam_v : nullptr; }
+// the one-run entry points on an object of several runs
+static int rnn_one_run_only(const orl_rnn* d, const char* what, const char* form) {
+  if (d->R == 1) return 0;
+  return fail(std::string(what) + ": the object has " + std::to_string(d->R) + " runs, use " + form);
+}
+static int rnn_run_ok(const orl_rnn* d, int run, const char* what) {
+  if (run < 0 || run >= d->R) return fail(std::string(what) + ": run out of range (" + std::to_string(d->R) + " runs)");
+  return 0;
+}
+int orl_rnn_set_run(orl_rnn* d, int run, int which, const float* host, int64_t n) {
+  if (!d || !host || !rnn_block_of(d, which)) return fail("orl_rnn_set_run: bad arguments");
+  if (rnn_run_ok(d, run, "orl_rnn_set_run")) return -1;
+  if (n != d->P) return fail("orl_rnn_set_run: expected " + std::to_string(d->P) + " floats");
+  return block_from_host(d->stream, rnn_block_of(d, which) + (long)run * d->P, host, d->P);
+}
+int orl_rnn_get_run(orl_rnn* d, int run, int which, float* host, int64_t n) {
+  if (!d || !host || !rnn_block_of(d, which)) return fail("orl_rnn_get_run: bad arguments");
+  if (rnn_run_ok(d, run, "orl_rnn_get_run")) return -1;
+  if (n != d->P) return fail("orl_rnn_get_run: expected " + std::to_string(d->P) + " floats");
+  return block_to_host(d->stream, host, rnn_block_of(d, which) + (long)run * d->P, d->P);
+}
 int orl_rnn_set(orl_rnn* d, int which, const float* host, int64_t n) {
   if (!d || !host || !rnn_block_of(d, which)) return fail("orl_rnn_set: bad arguments");
+  if (rnn_one_run_only(d, "orl_rnn_set", "orl_rnn_set_run")) return -1;
   if (n != d->P) return fail("orl_rnn_set: expected " + std::to_string(d->P) + " floats");
-  return block_from_host(d->stream, rnn_block_of(d, which), host, d->P);
+  return orl_rnn_set_run(d, 0, which, host, n);
 }
 int orl_rnn_get(orl_rnn* d, int which, float* host, int64_t n) {
   if (!d || !host || !rnn_block_of(d, which)) return fail("orl_rnn_get: bad arguments");
+  if (rnn_one_run_only(d, "orl_rnn_get", "orl_rnn_get_run")) return -1;
   if (n != d->P) return fail("orl_rnn_get: expected " + std::to_string(d->P) + " floats");
-  return block_to_host(d->stream, host, rnn_block_of(d, which), d->P);
+  return orl_rnn_get_run(d, 0, which, host, n);
 }
 int orl_rnn_set_step_count(orl_rnn* d, int64_t k) {
   if (!d || k < 0) return fail("orl_rnn_set_step_count: bad arguments");
@@ -879,76 +985,116 @@ int orl_rnn_load_data(orl_rnn* d, const float* inputs, const float* targets, con
   return 0;
 }
 
-int orl_rnn_step(orl_rnn* d, const int64_t* idx, int32_t rows, const float* drop_masks, float* loss_out) {
-  if (rnn_ready(d, "orl_rnn_step", true)) return -1;
-  if (!idx || rows < 1 || rows > d->B) return fail("orl_rnn_step: need 1 <= rows <= batch_size row indices");
-  for (int i = 0; i < rows; ++i)
-    if (idx[i] < 0 || idx[i] >= d->n_data) return fail("orl_rnn_step: row index out of range");
-  if (d->mem.grow(&d->idx_d, &d->idx_cap, d->B, d->stream)) return -1;
-  ORL_HIP(hipMemcpyAsync(d->idx_d, idx, sizeof(int64_t) * rows, hipMemcpyHostToDevice, d->stream));
+// orl_rnn_step / orl_rnn_step_runs (`what` names the caller in the errors): idx [R][rows], drop_masks [R][norms][rows * T][H], loss_out [R]
+static int rnn_step_runs(orl_rnn* d, const char* what, const int64_t* idx, int32_t rows, const float* drop_masks, float* loss_out) {
+  const std::string w(what);
+  if (!idx || rows < 1 || rows > d->B) return fail(w + ": need 1 <= rows <= batch_size row indices");
+  const int R = d->R;
+  for (long i = 0; i < (long)R * rows; ++i)
+    if (idx[i] < 0 || idx[i] >= d->n_data) return fail(w + ": row index out of range" + (R > 1 ? " in run " + std::to_string(i / rows) : ""));
+  if (d->mem.grow(&d->idx_d, &d->idx_cap, (long)R * d->B, d->stream)) return -1;
+  ORL_HIP(hipMemcpyAsync(d->idx_d, idx, sizeof(int64_t) * R * rows, hipMemcpyHostToDevice, d->stream));
   const bool forced = drop_masks && d->c.dropout_rate > 0.f;
   if (forced) {
     const size_t per = (size_t)rows * d->T * d->H;
-    for (int s = 0; s < d->norms; ++s)
-      ORL_HIP(hipMemcpyAsync(d->tw.MK + (size_t)s * d->tw.cap * d->H, drop_masks + s * per, sizeof(float) * per, hipMemcpyHostToDevice, d->stream));
+    for (int r = 0; r < R; ++r)
+      for (int s = 0; s < d->norms; ++s)
+        ORL_HIP(hipMemcpyAsync(d->tw.MK + (size_t)r * d->tw.mk_rs + (size_t)s * d->tw.cap * d->H, drop_masks + ((size_t)r * d->norms + s) * per,
+                               sizeof(float) * per, hipMemcpyHostToDevice, d->stream));
   }
-  if (rnn_enqueue_step(d, d->idx_d, rows, forced, d->loss_cell)) return -1;
+  if (rnn_enqueue_step(d, d->idx_d, rows, rows, forced, d->loss_cell)) return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
-  if (loss_out) ORL_HIP(hipMemcpy(loss_out, d->loss_cell, sizeof(float), hipMemcpyDeviceToHost));
+  if (loss_out) ORL_HIP(hipMemcpy(loss_out, d->loss_cell, sizeof(float) * R, hipMemcpyDeviceToHost));
   return 0;
 }
+int orl_rnn_step(orl_rnn* d, const int64_t* idx, int32_t rows, const float* drop_masks, float* loss_out) {
+  if (rnn_ready(d, "orl_rnn_step", true) || rnn_one_run_only(d, "orl_rnn_step", "orl_rnn_step_runs")) return -1;
+  return rnn_step_runs(d, "orl_rnn_step", idx, rows, drop_masks, loss_out);
+}
+int orl_rnn_step_runs(orl_rnn* d, const int64_t* idx, int32_t rows, const float* drop_masks, float* losses_out) {
+  if (rnn_ready(d, "orl_rnn_step_runs", true)) return -1;
+  return rnn_step_runs(d, "orl_rnn_step_runs", idx, rows, drop_masks, losses_out);
+}
 
-int orl_rnn_learn_epoch(orl_rnn* d, const int64_t* order, int64_t n_rows, int on_device, float* losses_out) {
-  if (rnn_ready(d, "orl_rnn_learn_epoch", true)) return -1;
-  if (!order || n_rows < 1) return fail("orl_rnn_learn_epoch: bad arguments");
+// orl_rnn_learn_epoch / orl_rnn_learn_epoch_runs: orders [R][n_rows], losses_out [steps][R]
+static int rnn_learn_epoch_runs(orl_rnn* d, const char* what, const int64_t* orders, int64_t n_rows, int on_device, float* losses_out) {
+  const std::string w(what);
+  const int R = d->R;
+  if (!orders || n_rows < 1) return fail(w + ": bad arguments");
   if (!on_device)
-    for (int64_t i = 0; i < n_rows; ++i)
-      if (order[i] < 0 || order[i] >= d->n_data) return fail("orl_rnn_learn_epoch: row index out of range");
+    for (int64_t i = 0; i < R * n_rows; ++i)
+      if (orders[i] < 0 || orders[i] >= d->n_data) return fail(w + ": row index out of range");
   const long steps = (long)((n_rows + d->B - 1) / d->B);
-  if (d->mem.grow(&d->idx_d, &d->idx_cap, std::max<long>((long)n_rows, d->B), d->stream)) return -1;
-  if (d->mem.grow(&d->loss_steps, &d->loss_cap, steps, d->stream)) return -1;
-  ORL_HIP(hipMemcpyAsync(d->idx_d, order, sizeof(int64_t) * n_rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
+  if (d->mem.grow(&d->idx_d, &d->idx_cap, (long)R * std::max<long>((long)n_rows, d->B), d->stream)) return -1;
+  if (d->mem.grow(&d->loss_steps, &d->loss_cap, steps * R, d->stream)) return -1;
+  ORL_HIP(hipMemcpyAsync(d->idx_d, orders, sizeof(int64_t) * R * n_rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
   for (long s = 0; s < steps; ++s) {
     const int rows = (int)std::min<int64_t>(d->B, n_rows - s * d->B);
-    if (rnn_enqueue_step(d, d->idx_d + s * d->B, rows, false, d->loss_steps + s)) return -1;
+    if (rnn_enqueue_step(d, d->idx_d + s * d->B, (long)n_rows, rows, false, d->loss_steps + s * R)) return -1;
   }
   ORL_HIP(hipStreamSynchronize(d->stream));
-  if (losses_out) ORL_HIP(hipMemcpy(losses_out, d->loss_steps, sizeof(float) * steps, hipMemcpyDeviceToHost));
+  if (losses_out) ORL_HIP(hipMemcpy(losses_out, d->loss_steps, sizeof(float) * steps * R, hipMemcpyDeviceToHost));
   return 0;
 }
+int orl_rnn_learn_epoch(orl_rnn* d, const int64_t* order, int64_t n_rows, int on_device, float* losses_out) {
+  if (rnn_ready(d, "orl_rnn_learn_epoch", true) || rnn_one_run_only(d, "orl_rnn_learn_epoch", "orl_rnn_learn_epoch_runs")) return -1;
+  return rnn_learn_epoch_runs(d, "orl_rnn_learn_epoch", order, n_rows, on_device, losses_out);
+}
+int orl_rnn_learn_epoch_runs(orl_rnn* d, const int64_t* orders, int64_t n_rows, int on_device, float* losses_out) {
+  if (rnn_ready(d, "orl_rnn_learn_epoch_runs", true)) return -1;
+  return rnn_learn_epoch_runs(d, "orl_rnn_learn_epoch_runs", orders, n_rows, on_device, losses_out);
+}
 
-int orl_rnn_forward(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, float* out_last, float* out_all) {
-  if (rnn_ready(d, "orl_rnn_forward", false)) return -1;
-  if (!inputs || !out_last || n < 1) return fail("orl_rnn_forward: bad arguments");
-  if (T < 1 || T > d->Tmax) return fail("orl_rnn_forward: need 1 <= T <= max_seq_len (" + std::to_string(d->Tmax) + ")");
-  if (n > 0x7fffffffL / ((int64_t)T * 8 * d->H)) return fail("orl_rnn_forward: too many sequences for one call");
+// orl_rnn_forward / orl_rnn_forward_runs: run >= 0 that run alone, -1 every run (inputs shared or [R][n][T][in])
+static int rnn_forward_runs(orl_rnn* d, const char* what, const float* inputs, int64_t n, int32_t T, int on_device, int shared, int run, float* out_last,
+                            float* out_all) {
+  const std::string wh(what);
+  if (!inputs || !out_last || n < 1) return fail(wh + ": bad arguments");
+  if (run < -1 || run >= d->R) return fail(wh + ": run out of range (" + std::to_string(d->R) + " runs, or -1 for all)");
+  if (T < 1 || T > d->Tmax) return fail(wh + ": need 1 <= T <= max_seq_len (" + std::to_string(d->Tmax) + ")");
+  if (n > 0x7fffffffL / ((int64_t)T * 8 * d->H)) return fail(wh + ": too many sequences for one call");
+  const RnnRuns rs{run < 0 ? 0 : run, run < 0 ? d->R : 1};
+  const int n_in = (shared || run >= 0) ? 1 : rs.n;      // input arrays
   const long N = (long)n * T;
-  if (N > d->f_cap) {
+  if (N > d->f_cap || rs.n > d->f_runs) {
     ORL_HIP(hipStreamSynchronize(d->stream));
     d->mem.release(&d->fIn, &d->fLast, &d->fAll);
-    d->f_cap = 0;
+    const long cap = std::max(N, d->f_cap);
+    const int runs = std::max(rs.n, d->f_runs);
+    d->f_cap = 0; d->f_runs = 0;
     if (d->last_ws == &d->ew) d->last_ws = nullptr;
-    if (d->mem.alloc(&d->fIn, (size_t)N * d->in) || d->mem.alloc(&d->fLast, (size_t)n * d->od) || d->mem.alloc(&d->fAll, (size_t)N * d->od) ||
-        rnn_ws_alloc(d, d->ew, N, false))
+    if (d->mem.alloc(&d->fIn, (size_t)runs * cap * d->in) || d->mem.alloc(&d->fLast, (size_t)runs * cap * d->od) ||
+        d->mem.alloc(&d->fAll, (size_t)runs * cap * d->od) || rnn_ws_alloc(d, d->ew, cap, false, runs))
       return -1;
-    d->f_cap = N;
+    d->f_cap = cap; d->f_runs = runs;
   }
   RnnWs& w = d->ew;
   const float* in_d = inputs;
-  if (stage_in(d->stream, in_d, d->fIn, (size_t)N * d->in, on_device)) return -1;
-  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid(N * d->in)), dim3(256), 0, in_d, d->in, w.X0.p, w.X0.pitch, N, d->in, 1);
-  if (rnn_forward(d, w, (int)n, T, false)) return -1;
+  if (stage_in(d->stream, in_d, d->fIn, (size_t)n_in * N * d->in, on_device)) return -1;
+  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid(N * d->in), n_in), dim3(256), 0, in_d, d->in, N * d->in, w.X0.p, w.X0.pitch, w.X0.s0, N, d->in, 1);
+  if (rnn_forward(d, rs, w, (int)n, T, false, n_in < rs.n)) return -1;
   float* last = stage_dst(out_last, d->fLast, on_device);
-  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid((long)n * d->od)), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, last, d->od, (long)n, d->od, (int)T);
-  if (stage_out(d->stream, out_last, d->fLast, (size_t)n * d->od, on_device)) return -1;
+  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid((long)n * d->od), rs.n), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, last, d->od,
+              (long)n * d->od, (long)n, d->od, (int)T);
+  if (stage_out(d->stream, out_last, d->fLast, (size_t)rs.n * n * d->od, on_device)) return -1;
   if (out_all) {
     float* all = stage_dst(out_all, d->fAll, on_device);
-    DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid(N * d->od)), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, all, d->od, N, d->od, 1);
-    if (stage_out(d->stream, out_all, d->fAll, (size_t)N * d->od, on_device)) return -1;
+    DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid(N * d->od), rs.n), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, all, d->od,
+                N * d->od, N, d->od, 1);
+    if (stage_out(d->stream, out_all, d->fAll, (size_t)rs.n * N * d->od, on_device)) return -1;
   }
   ORL_HIP(hipStreamSynchronize(d->stream));
-  d->last_ws = &w; d->last_rows = N;
+  d->last_ws = &w; d->last_rows = N; d->last_r0 = rs.r0; d->last_nr = rs.n;
   return 0;
+}
+int orl_rnn_forward(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, float* out_last, float* out_all) {
+  if (rnn_ready(d, "orl_rnn_forward", false) || rnn_one_run_only(d, "orl_rnn_forward", "orl_rnn_forward_runs")) return -1;
+  return rnn_forward_runs(d, "orl_rnn_forward", inputs, n, T, on_device, 1, 0, out_last, out_all);
+}
+int orl_rnn_forward_runs(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, int shared_inputs, int run, float* out_last,
+                         float* out_all) {
+  if (rnn_ready(d, "orl_rnn_forward_runs", false)) return -1;
+  return rnn_forward_runs(d, "orl_rnn_forward_runs", inputs, n, T, on_device, shared_inputs, run, out_last, out_all);
 }
 
 // "<prefix><k>" with 0 <= k < count; -1 otherwise
@@ -961,29 +1107,40 @@ static int rnn_tap_index(const std::string& nm, const char* prefix, int count) {
   return k < count ? k : -1;
 }
 
-int64_t orl_rnn_debug_read(orl_rnn* d, const char* name, float* host, int64_t cap) {
+int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* host, int64_t cap) {
   if (!d || !name || !host) return fail("orl_rnn_debug_read: bad arguments");
+  if (rnn_run_ok(d, run, "orl_rnn_debug_read")) return -1;
   const std::string nm(name);
   const RnnWs* w = d->last_ws ? d->last_ws : &d->tw;          // (names are resolved before "nothing recorded": an unknown one is always refused)
-  const float* src = nullptr; long rows = d->last_rows; int cols = d->H, pitch = d->H, k;
-  if (nm == "loss") { src = d->loss_cell; rows = 1; cols = 1; pitch = 1; }
-  else if (nm == "pred") { src = w->PRED.p; cols = d->od; pitch = w->PRED.pitch; }
-  else if (nm == "in") { src = w->CAT.p; pitch = w->CAT.pitch; }
-  else if (nm == "merge") { src = w->M0.p; pitch = w->M0.pitch; }
-  else if ((k = rnn_tap_index(nm, "gru.", d->L)) >= 0) { src = w->HO[k].p; pitch = w->HO[k].pitch; }
-  else if ((k = rnn_tap_index(nm, "block.", d->nb)) >= 0) { src = w->XO[k].p; pitch = w->XO[k].pitch; }
-  else if ((k = rnn_tap_index(nm, "act.", d->norms)) >= 0) { const DevMat& m = k ? w->SB[k - 1] : w->SI; src = m.p; pitch = m.pitch; }
-  else if ((k = rnn_tap_index(nm, "drop.", d->norms)) >= 0) { const DevMat& m = k ? w->UB[k - 1] : w->UI; src = m.p; pitch = m.pitch; }
+  const float* src = nullptr; long rows = d->last_rows, rs = 0; int cols = d->H, pitch = d->H, k;
+  auto mat = [&](const DevMat& m) { src = m.p; pitch = m.pitch; rs = m.s0; };
+  if (nm == "loss") { src = d->loss_cell + run; rows = 1; cols = 1; pitch = 1; }
+  else if (nm == "pred") { mat(w->PRED); cols = d->od; }
+  else if (nm == "in") mat(w->CAT);
+  else if (nm == "merge") mat(w->M0);
+  else if ((k = rnn_tap_index(nm, "gru.", d->L)) >= 0) mat(w->HO[k]);
+  else if ((k = rnn_tap_index(nm, "block.", d->nb)) >= 0) mat(w->XO[k]);
+  else if ((k = rnn_tap_index(nm, "act.", d->norms)) >= 0) mat(k ? w->SB[k - 1] : w->SI);
+  else if ((k = rnn_tap_index(nm, "drop.", d->norms)) >= 0) mat(k ? w->UB[k - 1] : w->UI);
   else if ((k = rnn_tap_index(nm, "mask.", d->norms)) >= 0) {
     if (!w->train || !(d->c.dropout_rate > 0.f)) return fail("orl_rnn_debug_read: no dropout mask was applied");
-    src = w->MK + (size_t)k * w->cap * d->H;
+    src = w->MK + (size_t)k * w->cap * d->H; rs = w->mk_rs;
   }
   else return fail("orl_rnn_debug_read: unknown tap " + nm);
   if (!src || rows < 1 || (!d->last_ws && nm != "loss")) return fail("orl_rnn_debug_read: nothing recorded for " + nm);
+  if (nm != "loss") {                                         // the run's slot in the workspace of the last pass
+    if (run < d->last_r0 || run >= d->last_r0 + d->last_nr) return fail("orl_rnn_debug_read: the last pass did not compute run " + std::to_string(run));
+    src += (long)(run - d->last_r0) * rs;
+  }
   if ((int64_t)rows * cols > cap) return fail("orl_rnn_debug_read: " + nm + " needs " + std::to_string(rows * cols) + " floats");
   ORL_HIP(hipStreamSynchronize(d->stream));
   ORL_HIP(hipMemcpy2D(host, sizeof(float) * cols, src, sizeof(float) * pitch, sizeof(float) * cols, rows, hipMemcpyDeviceToHost));
   return (int64_t)rows * cols;
+}
+int64_t orl_rnn_debug_read(orl_rnn* d, const char* name, float* host, int64_t cap) {
+  if (!d || !name || !host) return fail("orl_rnn_debug_read: bad arguments");
+  if (rnn_one_run_only(d, "orl_rnn_debug_read", "orl_rnn_debug_read_run")) return -1;
+  return orl_rnn_debug_read_run(d, 0, name, host, cap);
 }
 int orl_rnn_profile(orl_rnn* d, int enable) {
   if (rnn_ready(d, "orl_rnn_profile", false)) return -1;
@@ -1012,9 +1169,15 @@ int orl_rnn_profile_read(orl_rnn* d, float ms[6]) {
   }
   return 0;
 }
+int orl_rnn_debug_grads_run(orl_rnn* d, int run, float* host, int64_t n) {
+  if (!d || !host || n != d->P) return fail("orl_rnn_debug_grads: bad arguments");
+  if (rnn_run_ok(d, run, "orl_rnn_debug_grads")) return -1;
+  return block_to_host(d->stream, host, d->grads + (long)run * d->P, d->P);
+}
 int orl_rnn_debug_grads(orl_rnn* d, float* host, int64_t n) {
   if (!d || !host || n != d->P) return fail("orl_rnn_debug_grads: bad arguments");
-  return block_to_host(d->stream, host, d->grads, d->P);
+  if (rnn_one_run_only(d, "orl_rnn_debug_grads", "orl_rnn_debug_grads_run")) return -1;
+  return orl_rnn_debug_grads_run(d, 0, host, n);
 }
 
 }  // extern "C"

@@ -76,6 +76,9 @@ ABI_SYMBOLS = [
     "orl_rnn_config_default", "orl_rnn_config_floats", "orl_rnn_create", "orl_rnn_destroy", "orl_rnn_floats", "orl_rnn_num_tensors",
     "orl_rnn_tensor", "orl_rnn_set", "orl_rnn_get", "orl_rnn_set_step_count", "orl_rnn_step_count", "orl_rnn_load_data", "orl_rnn_step",
     "orl_rnn_learn_epoch", "orl_rnn_forward", "orl_rnn_debug_read", "orl_rnn_debug_grads", "orl_rnn_profile", "orl_rnn_profile_read",
+    # ... and its forms for objects of several runs
+    "orl_rnn_set_run", "orl_rnn_get_run", "orl_rnn_step_runs", "orl_rnn_learn_epoch_runs", "orl_rnn_forward_runs", "orl_rnn_debug_read_run",
+    "orl_rnn_debug_grads_run",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -408,6 +411,14 @@ def _bind_rnn(lib) -> None:
     lib.orl_rnn_debug_read.argtypes = [P, C.c_char_p, VP, I64]
     lib.orl_rnn_debug_read.restype = I64
     lib.orl_rnn_debug_grads.argtypes = [P, VP, I64]
+    lib.orl_rnn_set_run.argtypes = [P, C.c_int, C.c_int, VP, I64]
+    lib.orl_rnn_get_run.argtypes = [P, C.c_int, C.c_int, VP, I64]
+    lib.orl_rnn_step_runs.argtypes = [P, VP, C.c_int32, VP, VP]
+    lib.orl_rnn_learn_epoch_runs.argtypes = [P, VP, I64, C.c_int, VP]
+    lib.orl_rnn_forward_runs.argtypes = [P, VP, I64, C.c_int32, C.c_int, C.c_int, C.c_int, VP, VP]
+    lib.orl_rnn_debug_read_run.argtypes = [P, C.c_int, C.c_char_p, VP, I64]
+    lib.orl_rnn_debug_read_run.restype = I64
+    lib.orl_rnn_debug_grads_run.argtypes = [P, C.c_int, VP, I64]
     lib.orl_rnn_profile.argtypes = [P, C.c_int]
     lib.orl_rnn_profile_read.argtypes = [P, C.POINTER(C.c_float)]
 
@@ -1586,18 +1597,30 @@ def default_rnn_config(**over) -> OrlRnnConfig:
     return _override(cfg, over, "rnn", {"hidden": hidden})
 
 
-def rnn_config_floats(cfg: OrlRnnConfig) -> int:
-    """floats of the parameter block ``cfg`` needs (what ``external_arena`` must hold); an unsupported config raises"""
+def rnn_run_floats(cfg: OrlRnnConfig) -> int:
+    """floats of ONE run's parameter block of ``cfg`` (``orl_rnn_config_floats``; ``external_arena`` must hold ``n_runs`` times as
+    many); an unsupported config raises"""
     n = int(load_library().orl_rnn_config_floats(C.byref(cfg)))
     if n < 0:
         raise RuntimeError(f"orl_rnn_config_floats failed: {last_error()}")
     return n
 
 
+def rnn_config_floats(cfg: OrlRnnConfig) -> int:
+    """floats of the parameter block ``cfg`` needs (what ``external_arena`` must hold) for a one-run config.  Like the one-run calls
+    of the library it is refused for several runs, where a per-run size could be mistaken for the arena's: ``rnn_run_floats``."""
+    if int(cfg.n_runs) > 1:
+        raise RuntimeError(f"rnn_config_floats: one run per object only, this config has {int(cfg.n_runs)}; use rnn_run_floats "
+                           "(the per-run size: external_arena holds n_runs times that)")
+    return rnn_run_floats(cfg)
+
+
 class RnnDynamicsEngine(_Handle):
     """RAII wrapper over ``orl_rnn*``: RNNModel (GRU + residual LayerNorm blocks) with its masked-MSE training step and its eval
     forward on the device.  Sequence arrays are ``[rows, T, cols]``; parameter blocks travel as flat float32 arrays laid out by
-    ``tensors()``."""
+    ``tensors()``.  With ``n_runs=R`` in the config the object trains R independent runs in the same launches: ``run=`` selects a
+    run's block or taps, and ``step_runs`` / ``learn_epoch_runs`` / ``forward_runs`` act on all of them (the one-run ``step`` /
+    ``learn_epoch`` / ``forward`` are refused by the library then)."""
     PARAMS, EXP_AVG, EXP_AVG_SQ = 0, 1, 2
     _destroy = "orl_rnn_destroy"
 
@@ -1606,26 +1629,27 @@ class RnnDynamicsEngine(_Handle):
         self.cfg = cfg
         _check(self.lib.orl_rnn_create(C.byref(cfg), C.byref(self._h)), "orl_rnn_create")
         self.floats = int(self.lib.orl_rnn_floats(self._h))
+        self.n_runs = int(cfg.n_runs)
         self.T = 0
 
     def tensors(self):
-        """[(state_dict name, offset, shape)] in RNNModel.state_dict() order"""
+        """[(state_dict name, offset, shape)] in RNNModel.state_dict() order (offsets within a run's block)"""
         return _read_tensors(self.lib.orl_rnn_num_tensors, self.lib.orl_rnn_tensor, self._h, what="orl_rnn_tensor")
 
-    def set(self, which: int, flat):
+    def set(self, which: int, flat, run: int = 0):
         flat = _f32(flat).ravel()
-        _check(self.lib.orl_rnn_set(self._h, which, flat.ctypes.data, flat.size), "orl_rnn_set")
+        _check(self.lib.orl_rnn_set_run(self._h, int(run), which, flat.ctypes.data, flat.size), "orl_rnn_set_run")
 
-    def get(self, which: int) -> np.ndarray:
+    def get(self, which: int, run: int = 0) -> np.ndarray:
         flat = np.empty(self.floats, np.float32)
-        _check(self.lib.orl_rnn_get(self._h, which, flat.ctypes.data, flat.size), "orl_rnn_get")
+        _check(self.lib.orl_rnn_get_run(self._h, int(run), which, flat.ctypes.data, flat.size), "orl_rnn_get_run")
         return flat
 
-    def set_params(self, params: Dict):
-        self.set(self.PARAMS, _flatten(self.tensors(), params, self.floats))
+    def set_params(self, params: Dict, run: int = 0):
+        self.set(self.PARAMS, _flatten(self.tensors(), params, self.floats), run)
 
-    def get_params(self) -> Dict[str, np.ndarray]:
-        return _unflatten(self.tensors(), self.get(self.PARAMS))
+    def get_params(self, run: int = 0) -> Dict[str, np.ndarray]:
+        return _unflatten(self.tensors(), self.get(self.PARAMS, run))
 
     @property
     def step_count(self) -> int:
@@ -1643,17 +1667,30 @@ class RnnDynamicsEngine(_Handle):
         _check(self.lib.orl_rnn_load_data(self._h, inputs.ctypes.data, targets.ctypes.data, masks.ctypes.data, n, T), "orl_rnn_load_data")
         self.T = T
 
+    def _mask_ptr(self, drop_masks, rows: int, runs: int):
+        if drop_masks is None:
+            return None, None
+        drop_masks = _f32(drop_masks)
+        assert drop_masks.size == runs * int(self.cfg.n_hidden) * rows * self.T * int(self.cfg.hidden[0])
+        return drop_masks, drop_masks.ctypes.data
+
     def step(self, idx, drop_masks=None) -> float:
         """one optimizer step on the sequences ``idx``; ``drop_masks`` [len(hidden), rows * T, H] teacher-forces the dropouts' keep masks"""
         idx = np.ascontiguousarray(idx, dtype=np.int64).ravel()
-        mp = None
-        if drop_masks is not None:
-            drop_masks = _f32(drop_masks)
-            assert drop_masks.size == int(self.cfg.n_hidden) * idx.size * self.T * int(self.cfg.hidden[0])
-            mp = drop_masks.ctypes.data
+        drop_masks, mp = self._mask_ptr(drop_masks, idx.size, 1)
         loss = C.c_float()
         _check(self.lib.orl_rnn_step(self._h, idx.ctypes.data, idx.size, mp, C.byref(loss)), "orl_rnn_step")
         return float(loss.value)
+
+    def step_runs(self, idx, drop_masks=None) -> np.ndarray:
+        """one optimizer step of every run, run r on the sequences ``idx[r]`` (``idx`` [R, rows]); ``drop_masks``
+        [R, len(hidden), rows * T, H] teacher-forces each run's keep masks.  Returns the R minibatch losses."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        assert idx.ndim == 2 and idx.shape[0] == self.n_runs, f"idx must be [{self.n_runs}, rows]"
+        drop_masks, mp = self._mask_ptr(drop_masks, idx.shape[1], self.n_runs)
+        losses = np.empty(self.n_runs, np.float32)
+        _check(self.lib.orl_rnn_step_runs(self._h, idx.ctypes.data, idx.shape[1], mp, losses.ctypes.data), "orl_rnn_step_runs")
+        return losses
 
     def learn_epoch(self, order) -> np.ndarray:
         """one loss per step; ``order``: an int64 array or a contiguous int64 torch tensor on the engine's device"""
@@ -1670,40 +1707,70 @@ class RnnDynamicsEngine(_Handle):
         _check(self.lib.orl_rnn_learn_epoch(self._h, ptr, n, dev, losses.ctypes.data), "orl_rnn_learn_epoch")
         return losses
 
+    def learn_epoch_runs(self, orders) -> np.ndarray:
+        """an epoch of every run, run r in the order ``orders[r]`` (``orders`` [R, n]: an int64 array or a contiguous int64 torch
+        tensor on the engine's device).  Returns the losses [steps, R]."""
+        if _is_tensor(orders):
+            import torch
+            assert orders.dtype == torch.int64 and orders.is_contiguous() and orders.device.type == "cuda"
+            torch.cuda.current_stream(orders.device).synchronize()
+            ptr, dev = orders.data_ptr(), 1
+        else:
+            orders = np.ascontiguousarray(orders, dtype=np.int64)
+            ptr, dev = orders.ctypes.data, 0
+        assert orders.ndim == 2 and int(orders.shape[0]) == self.n_runs, f"orders must be [{self.n_runs}, n]"
+        n, B = int(orders.shape[1]), int(self.cfg.batch_size)
+        losses = np.empty(((n + B - 1) // B, self.n_runs), np.float32)
+        _check(self.lib.orl_rnn_learn_epoch_runs(self._h, ptr, n, dev, losses.ctypes.data), "orl_rnn_learn_epoch_runs")
+        return losses
+
     def forward(self, inputs, want_all: bool = False):
         """eval-mode predictions of ``inputs`` [n, T, input_dim]: the last time step's [n, output_dim], and every step's
         [n, T, output_dim] when ``want_all``.  Host arrays in and out, or contiguous fp32 torch tensors on the engine's device."""
-        od = int(self.cfg.output_dim)
-        if _is_tensor(inputs):
+        return self._forward(inputs, want_all, None)
+
+    def forward_runs(self, inputs, run: int = -1, want_all: bool = False):
+        """eval-mode predictions of several runs.  ``run=-1``: every run, on the same ``inputs`` [n, T, input_dim] or on its own
+        ``inputs[r]`` ([R, n, T, input_dim]); the outputs get a leading R.  ``run=r``: that run alone on [n, T, input_dim], shaped
+        like ``forward``'s.  Host arrays in and out, or contiguous fp32 torch tensors on the engine's device."""
+        return self._forward(inputs, want_all, int(run))
+
+    def _forward(self, inputs, want_all: bool, run):
+        od, tensor = int(self.cfg.output_dim), _is_tensor(inputs)
+        inputs = inputs.contiguous() if tensor else _f32(inputs)
+        per_run = inputs.ndim == 4
+        assert inputs.ndim in (3, 4) and int(inputs.shape[-1]) == int(self.cfg.input_dim)
+        assert not per_run or (run == -1 and int(inputs.shape[0]) == self.n_runs), "per-run inputs are [R, n, T, input_dim] with run=-1"
+        n, T = int(inputs.shape[-3]), int(inputs.shape[-2])
+        lead = (self.n_runs,) if run == -1 else ()
+        if tensor:
             import torch
-            inputs = inputs.contiguous()
-            n, T = int(inputs.shape[0]), int(inputs.shape[1])
-            last = torch.empty((n, od), dtype=torch.float32, device=inputs.device)
-            every = torch.empty((n, T, od), dtype=torch.float32, device=inputs.device) if want_all else None
+            last = torch.empty(lead + (n, od), dtype=torch.float32, device=inputs.device)
+            every = torch.empty(lead + (n, T, od), dtype=torch.float32, device=inputs.device) if want_all else None
             torch.cuda.current_stream(inputs.device).synchronize()
-            _check(self.lib.orl_rnn_forward(self._h, inputs.data_ptr(), n, T, 1, last.data_ptr(), None if every is None else every.data_ptr()),
-                   "orl_rnn_forward")
-            return (last, every) if want_all else last
-        inputs = _f32(inputs)
-        n, T = int(inputs.shape[0]), int(inputs.shape[1])
-        assert inputs.shape == (n, T, int(self.cfg.input_dim))
-        last = np.empty((n, od), np.float32)
-        every = np.empty((n, T, od), np.float32) if want_all else None
-        _check(self.lib.orl_rnn_forward(self._h, inputs.ctypes.data, n, T, 0, last.ctypes.data, None if every is None else every.ctypes.data),
-               "orl_rnn_forward")
+            ptrs = (inputs.data_ptr(), last.data_ptr(), None if every is None else every.data_ptr())
+        else:
+            last = np.empty(lead + (n, od), np.float32)
+            every = np.empty(lead + (n, T, od), np.float32) if want_all else None
+            ptrs = (inputs.ctypes.data, last.ctypes.data, None if every is None else every.ctypes.data)
+        if run is None:
+            _check(self.lib.orl_rnn_forward(self._h, ptrs[0], n, T, int(tensor), ptrs[1], ptrs[2]), "orl_rnn_forward")
+        else:
+            _check(self.lib.orl_rnn_forward_runs(self._h, ptrs[0], n, T, int(tensor), int(not per_run), run, ptrs[1], ptrs[2]),
+                   "orl_rnn_forward_runs")
         return (last, every) if want_all else last
 
-    def debug_read(self, name: str, cap: int = 1 << 22) -> np.ndarray:
+    def debug_read(self, name: str, cap: int = 1 << 22, run: int = 0) -> np.ndarray:
         """a test tap of the last step / forward as a flat array: pred, loss, gru.<l>, in, merge, block.<i>, mask.<s>, act.<s>, drop.<s>"""
         buf = np.empty(cap, np.float32)
-        n = int(self.lib.orl_rnn_debug_read(self._h, name.encode(), buf.ctypes.data, cap))
+        n = int(self.lib.orl_rnn_debug_read_run(self._h, int(run), name.encode(), buf.ctypes.data, cap))
         if n < 0:
             raise RuntimeError(f"orl_rnn_debug_read({name!r}) failed: {last_error()}")
         return buf[:n].copy()
 
-    def debug_grads(self) -> np.ndarray:
+    def debug_grads(self, run: int = 0) -> np.ndarray:
         flat = np.empty(self.floats, np.float32)
-        _check(self.lib.orl_rnn_debug_grads(self._h, flat.ctypes.data, flat.size), "orl_rnn_debug_grads")
+        _check(self.lib.orl_rnn_debug_grads_run(self._h, int(run), flat.ctypes.data, flat.size), "orl_rnn_debug_grads_run")
         return flat
 
     def profile(self, enable: bool = True):

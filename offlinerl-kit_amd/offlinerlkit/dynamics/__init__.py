@@ -539,12 +539,26 @@ def rnn_epoch_order(n: int, generator: Optional[torch.Generator] = None) -> np.n
     return torch.randperm(n, generator=g).numpy().astype(np.int64)
 
 
+def _fresh_rnn_params(model, seed: int) -> Dict[str, torch.Tensor]:
+    """the constructor's initialisation of ``RNNModel`` under torch seed ``seed`` (runs r > 0 of a multi-run ``RNNDynamics``)"""
+    from ..nets import RNNModel
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        m = RNNModel(model.input_dim, model.output_dim, model.hidden_dims, model.rnn_num_layers, model.dropout_rate)
+    return dict(m.state_dict())
+
+
 class RNNDynamics(BaseDynamics):
     """The GRU sequence dynamics model (reference: dynamics/rnn_dynamics.py over nets/rnn.py:RNNModel) on the HIP engine (``orl_rnn_*``,
     csrc/rnn_dynamics.hip).  ``learn`` is one device step of the masked MSE with Adam, ``train`` loads the data set into HBM once and
     runs every epoch as one call, ``step`` is one eval-mode forward over the windows.  The module's parameters alias the engine's
     block, so ``model.state_dict()``, ``save`` and ``load`` see what the engine trains.  Dropout masks come from a device Philox
-    stream, so a training run is distributed like the reference's, not equal to it (at ``dropout_rate`` 0 it is equal)."""
+    stream, so a training run is distributed like the reference's, not equal to it (at ``dropout_rate`` 0 it is equal).
+
+    Multi-run: ``set_engine_options(n_runs=R)`` trains R independent models (runs) in the same launches on the same data set.  Run 0
+    starts from the module's parameters and shuffles with the global torch RNG, exactly as a one-run object does; run r > 0 starts from
+    ``RNNModel``'s initialisation under torch seed ``seed + r`` and shuffles with a generator of its own seeded ``seed + r``.  The
+    scaler is shared.  The torch module shows the run chosen by ``select_run`` (run 0 by default)."""
 
     def __init__(self, model: nn.Module, optim: torch.optim.Optimizer, scaler: StandardScaler,
                  terminal_fn: Callable[[np.ndarray, np.ndarray, np.ndarray], np.ndarray]) -> None:
@@ -572,53 +586,81 @@ class RNNDynamics(BaseDynamics):
             raise ValueError(f"dropout_rate must be in [0, 1), got {model.dropout_rate}")
         self.scaler = scaler
         self.terminal_fn = terminal_fn
-        self._seed = 0
+        self._n_runs, self._seed = 1, 0
+        self._cur_run = 0
+        self._gens: Optional[List[torch.Generator]] = None      # the epoch-order generators of runs 1 .. R - 1, carried across epochs
         self._eng: Optional[_engine.RnnDynamicsEngine] = None
         self._arena = None
         self._shape = None              # (batch_size, max_seq_len) the engine was built for
 
     # ---- engine binding ----
-    def set_engine_options(self, seed: Optional[int] = None) -> None:
+    def set_engine_options(self, n_runs: int = 1, seed: Optional[int] = None) -> None:
         if self._eng is not None:
             raise RuntimeError("set_engine_options before the first train() / learn() / step()")
+        if not 1 <= int(n_runs) <= 64:
+            raise ValueError(f"n_runs must be in [1, 64], got {n_runs}")
+        self._n_runs = int(n_runs)
         self._seed = int(seed) if seed is not None else 0
+        self._gens = None
 
     def _device(self) -> torch.device:
         return EnsembleDynamics._device(self)
 
     def _bind(self, rows: int, steps: int, exact: bool = False) -> None:
         """an engine for steps of up to ``rows`` sequences (``exact``: batch_size == rows, as learn_epoch cuts an epoch into
-        batch_size rows) of up to ``steps`` time steps; an engine that is too small is rebuilt and its state carried over"""
+        batch_size rows) of up to ``steps`` time steps; an engine that is too small is rebuilt and its state (every run's three
+        blocks and the step count) carried over"""
         old = self._shape if self._eng is not None else (0, 0)
         if self._eng is not None and steps <= old[1] and (rows == old[0] if exact else rows <= old[0]):
             return
         shape = (int(rows) if exact else max(int(rows), old[0]), max(int(steps), old[1]))
+        R = self._n_runs
         carried = None
         if self._eng is not None:
-            carried = (self._eng.get(0), self._eng.get(1), self._eng.get(2), self._eng.step_count)
+            carried = ([[self._eng.get(which, r) for which in range(3)] for r in range(R)], self._eng.step_count)
             self._unbind()
         dev = self._device()
         m, g = self.model, self.optim.param_groups[0]
         cfg = _engine.default_rnn_config(input_dim=m.input_dim, output_dim=m.output_dim, hidden=m.hidden_dims,
                                          rnn_num_layers=m.rnn_num_layers, dropout_rate=float(m.dropout_rate or 0.0),
                                          batch_size=shape[0], max_seq_len=shape[1], lr=float(g["lr"]), adam_beta1=float(g["betas"][0]),
-                                         adam_beta2=float(g["betas"][1]), adam_eps=float(g["eps"]), device=dev.index, seed=self._seed)
-        self._arena = torch.zeros(_engine.rnn_config_floats(cfg), dtype=torch.float32, device=dev)
+                                         adam_beta2=float(g["betas"][1]), adam_eps=float(g["eps"]), n_runs=R, device=dev.index,
+                                         seed=self._seed)
+        self._arena = torch.zeros(R * _engine.rnn_run_floats(cfg), dtype=torch.float32, device=dev)
         cfg.external_arena = self._arena.data_ptr()
         torch.cuda.synchronize(dev)
         self._eng = _engine.RnnDynamicsEngine(cfg)
         self._shape = shape
+        for r in range(R):
+            if carried is not None:
+                for which in range(3):
+                    self._eng.set(which, carried[0][r][which], r)
+                continue
+            src = m.state_dict() if r == 0 else _fresh_rnn_params(m, self._seed + r)
+            self._eng.set_params({k: v.detach().cpu().numpy() for k, v in src.items()}, r)
         if carried is not None:
-            for which in range(3):
-                self._eng.set(which, carried[which])
-            self._eng.step_count = carried[3]
-        else:
-            self._eng.set_params({k: v.detach().cpu().numpy() for k, v in m.state_dict().items()})
+            self._eng.step_count = carried[1]
         m.to(dev)
         m.device = dev
-        params = dict(m.named_parameters())
+        run, self._cur_run = self._cur_run, -1
+        self.select_run(run)
+
+    def select_run(self, run: int) -> None:
+        """point the torch module (forward, state_dict, save, load, step on one set of windows) at run ``run``"""
+        if not 0 <= int(run) < self._n_runs:
+            raise ValueError(f"run {run} out of range ({self._n_runs} runs)")
+        if self._eng is None:
+            if run != 0:
+                raise RuntimeError("select_run before the engine exists: only run 0")
+            return
+        if run == self._cur_run:
+            return
+        torch.cuda.synchronize(self._arena.device)
+        base = int(run) * self._eng.floats
+        params = dict(self.model.named_parameters())
         for name, off, tshape in self._eng.tensors():
-            params[name].data = self._arena[off: off + int(np.prod(tshape))].view(tshape)
+            params[name].data = self._arena[base + off: base + off + int(np.prod(tshape))].view(tshape)
+        self._cur_run = int(run)
 
     def _unbind(self) -> None:
         if self._eng is None:
@@ -636,22 +678,56 @@ class RNNDynamics(BaseDynamics):
     # ---- reference API ----
     @torch.no_grad()
     def step(self, obss: np.ndarray, actions: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Dict]:
-        "imagine single forward step"
+        """imagine single forward step.  Windows ``(N, T, .)``: the selected run.  Windows ``(R, N, T, .)``: run r on ``obss[r]``, every
+        result with a leading R (the scaler is shared, ``terminal_fn`` is applied per run)."""
         inputs = self.scaler.transform(np.concatenate([obss, actions], axis=-1))
-        self._bind(1, inputs.shape[1])
-        preds = self._eng.forward(self._host(inputs))
+        self._bind(1, inputs.shape[-2])
+        if inputs.ndim == 4:
+            if inputs.shape[0] != self._n_runs:
+                raise ValueError(f"windows of {inputs.shape[0]} runs for an object of {self._n_runs}")
+            preds = self._eng.forward_runs(self._host(inputs), run=-1)
+            next_obss = preds[..., :-1] + obss[:, :, -1]
+            rewards = preds[..., -1:]
+            terminals = np.stack([self.terminal_fn(obss[r, :, -1], actions[r, :, -1], next_obss[r]) for r in range(self._n_runs)])
+            return next_obss, rewards, terminals, {}
+        if self._n_runs == 1:
+            preds = self._eng.forward(self._host(inputs))
+        else:
+            preds = self._eng.forward_runs(self._host(inputs), run=self._cur_run)
         next_obss = preds[..., :-1] + obss[:, -1]
         rewards = preds[..., -1:]
         terminals = self.terminal_fn(obss[:, -1], actions[:, -1], next_obss)
         return next_obss, rewards, terminals, {}
 
-    def learn(self, batch) -> float:
+    def _load_batch(self, batch) -> int:
         inputs, targets, masks = (self._host(x) for x in batch)
         if not self.model.training and float(self.model.dropout_rate or 0.0) > 0.0:
             raise NotImplementedError("RNNDynamics.learn on a model in eval mode: the engine's training step always applies the dropout")
         self._bind(inputs.shape[0], inputs.shape[1])
         self._eng.load_data(inputs, targets, masks)
-        return self._eng.step(np.arange(inputs.shape[0]))
+        return inputs.shape[0]
+
+    def learn(self, batch) -> float:
+        """one step of every run on ``batch``; the selected run's loss"""
+        if self._n_runs > 1:
+            return float(self.learn_runs(batch)[self._cur_run])
+        n = self._load_batch(batch)
+        return self._eng.step(np.arange(n))
+
+    def learn_runs(self, batch) -> np.ndarray:
+        """one step of every run on ``batch``; the R losses"""
+        n = self._load_batch(batch)
+        return self._eng.step_runs(np.tile(np.arange(n, dtype=np.int64), (self._n_runs, 1)))
+
+    def _epoch_orders(self, n: int) -> np.ndarray:
+        """[R, n]: run 0's order from the global torch RNG (as a one-run object draws it), run r's from its own generator"""
+        if self._gens is None:
+            self._gens = []
+            for r in range(1, self._n_runs):
+                g = torch.Generator()
+                g.manual_seed(self._seed + r)
+                self._gens.append(g)
+        return np.stack([rnn_epoch_order(n)] + [rnn_epoch_order(n, g) for g in self._gens])
 
     def train(self, data, batch_size: int, max_iters: int, logger) -> None:
         self.model.train()
@@ -659,12 +735,25 @@ class RNNDynamics(BaseDynamics):
         inputs, targets, masks = (np.stack([self._host(it[k]) for it in items]) for k in range(3))
         self._bind(int(batch_size), inputs.shape[1], exact=True)
         self._eng.load_data(inputs, targets, masks)
+        R = self._n_runs
         for it in range(max_iters):
-            for loss in self._eng.learn_epoch(rnn_epoch_order(len(items))):
-                logger.logkv_mean("loss/model", float(loss))
+            if R == 1:
+                for loss in self._eng.learn_epoch(rnn_epoch_order(len(items))):
+                    logger.logkv_mean("loss/model", float(loss))
+            else:
+                for losses in self._eng.learn_epoch_runs(self._epoch_orders(len(items))):
+                    logger.logkv_mean("loss/model", float(np.mean(losses, dtype=np.float64)))
+                    for r in range(R):
+                        logger.logkv_mean(f"run{r}/loss/model", float(losses[r]))
             logger.set_timestep(it)
             logger.dumpkvs(exclude=["policy_training_progress"])
         self.save(logger.model_dir)
+        if R > 1:
+            names = list(self.model.state_dict().keys())
+            for r in range(1, R):
+                params = self._eng.get_params(r)
+                sd = type(self.model.state_dict())((k, torch.from_numpy(params[k].copy())) for k in names)
+                torch.save(sd, os.path.join(logger.model_dir, f"dynamics_run{r}.pth"))
         self.model.eval()
 
     def save(self, save_path: str) -> None:

@@ -5,7 +5,11 @@ autograd and ``torch.optim.Adam`` on the same GPU in the same call (``loss.item(
 
 Method: every shape is warmed up first; a timed window is a host clock around work that ends in a device synchronise; engine and torch
 windows alternate over ``--rounds`` rounds and the medians are reported with the spread.  The forward / scan / backward split of the
-engine's step comes from device events (``orl_rnn_profile``), in windows of their own.  Prints one JSON object; --out writes it too."""
+engine's step comes from device events (``orl_rnn_profile``), in windows of their own.  Prints one JSON object; --out writes it too.
+
+``--runs R [R ...]`` measures the multi-run objects instead: one ``step_runs`` of an R-run engine against R one-run engines stepped one
+after the other (same GPU, same call, same alternating windows and medians), with the device events of the R-run step and of a
+one-run step beside them (``profiles/rnn_throughput_runs.json`` holds R = 1, 2, 4, 8, 16)."""
 import argparse
 import json
 import os
@@ -45,14 +49,82 @@ def summary(xs):
     return dict(median_ms=1e3 * statistics.median(xs), min_ms=1e3 * min(xs), max_ms=1e3 * max(xs), windows=len(xs))
 
 
+def emit(res, out):
+    s = json.dumps(res, indent=1)
+    print(s)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write(s + "\n")
+
+
+def main_runs(a):
+    """--runs: one ``step_runs`` of an R-run object against R one-run objects stepped one after the other, for every R given; same
+    data set, run r on rows of its own, same method as the rest of the tool (alternating windows, medians)"""
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)                                   # noqa: E731
+    x, tg, mk = data(4 * B)
+    res = {"shape": dict(input_dim=IN, output_dim=OUT, hidden=HID, rnn_num_layers=L, dropout=P_DROP, batch=B, T=T),
+           "device": torch.cuda.get_device_name(0), "steps_per_window": a.batches, "runs": {}}
+    for R in a.runs:
+        many = _engine.RnnDynamicsEngine(_engine.default_rnn_config(n_runs=R))
+        ones = [_engine.RnnDynamicsEngine(_engine.default_rnn_config(seed=r)) for r in range(R)]
+        for r in range(R):
+            torch.manual_seed(r)
+            init = {k: v.numpy() for k, v in RNNModel(IN, OUT, HID, L, P_DROP).state_dict().items()}
+            many.set_params(init, run=r)
+            ones[r].set_params(init)
+        for e in [many] + ones:
+            e.load_data(x, tg, mk)
+        idx = np.stack([np.random.default_rng(100 + r).permutation(4 * B)[:B] for r in range(R)]).astype(np.int64)
+
+        def many_steps():
+            for _ in range(a.batches):
+                losses = many.step_runs(idx)
+            assert np.isfinite(losses).all()
+            return a.batches
+
+        def one_steps():
+            for _ in range(a.batches):
+                losses = [ones[r].step(idx[r]) for r in range(R)]
+            assert np.isfinite(losses).all()
+            return a.batches
+
+        fns = {"step_runs": many_steps, "one_run_steps": one_steps}
+        for fn in fns.values():
+            fn()
+        times = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                times[k].append(window(fn, sync))
+        row = {k: summary(v) for k, v in times.items()}
+        row["ratio_one_run_steps_over_step_runs"] = row["one_run_steps"]["median_ms"] / row["step_runs"]["median_ms"]
+        for name, e in (("step_runs_split_ms", many), ("one_run_step_split_ms", ones[0])):      # device events, in windows of their own
+            e.profile(True)
+            splits = []
+            for _ in range(a.rounds):
+                e.step_runs(idx) if e is many else e.step(idx[0])
+                splits.append(e.profile_read())
+            e.profile(False)
+            row[name] = {k: statistics.median(s[k] for s in splits) for k in splits[0]}
+        res["runs"][str(R)] = row
+        for e in [many] + ones:
+            e.close()
+    emit(res, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=20, help="optimizer steps per timed window")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--runs", type=int, nargs="+", default=None, metavar="R",
+                    help="instead: one step_runs of an R-run object against R one-run objects stepped in turn, for every R given")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rnn_throughput.py measures on the GPU: no HIP device visible")
+    if a.runs:
+        return main_runs(a)
     dev = torch.device("cuda", 0)
     x, tg, mk = data(a.batches * B)
     sync = lambda: torch.cuda.synchronize(dev)                                   # noqa: E731
@@ -133,12 +205,7 @@ def main():
     res["learn_ratio_torch_over_engine"] = res["torch_learn_step"]["median_ms"] / res["engine_learn_epoch_step"]["median_ms"]
     res["step_ratio_torch_over_engine"] = res["torch_step_256_windows"]["median_ms"] / res["class_step_256_windows"]["median_ms"]
     eng.close()
-    s = json.dumps(res, indent=1)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(s + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":
