@@ -823,6 +823,23 @@ int orl_rnn_debug_grads(orl_rnn* d, float* host, int64_t n_floats);   /* paramet
 /* the same taps of run `run` (one that the last pass computed) */
 int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* host, int64_t cap);
 int orl_rnn_debug_grads_run(orl_rnn* d, int run, float* host, int64_t n_floats);
+/* Further taps, of both forms: "x0" (the gathered or given inputs, [rows * T][input_dim]) and "gi.<l>" (layer l's input projections,
+ * [rows * T][3H]) after a step or a forward; and what only a training step computes, refused after a forward:
+ *   "tgt" [rows * T][output_dim], "msk" [rows * T]          the gathered targets and loss masks
+ *   "r.<l>", "z.<l>", "n.<l>", "hn.<l>", "hp.<l>"          what layer l's forward scan saves: the gates, W_hn h + b_hn, h_{t-1}
+ *   "zpre.<s>", "zmerge"                                   the Swish pre-activations of norm slot s's Linear and of the merge layer
+ *   "dpred", "dx", "dzm", "dcat" ([rows * T][2H])          gradients of pred, of the last block's output, of zmerge, of the merge input
+ *   "du.<i>", "dt.<i>"                                     block i's LayerNorm-input gradient and its Linear's input gradient
+ *   "dz.<s>"                                               the Linear-output gradient of norm slot s (0 the input block, 1 + i block i)
+ *   "dgi.<l>", "dgh.<l>" ([rows * T][3H]), "dxl.<l>"       layer l's backward scan outputs; the gradient of layer l's input, l >= 1
+ *   "part" [rows * T][2 H len(hidden)], "chunk" [ceil(rows * T / 64)][..]   the dgamma | dbeta row terms and their 64-row sums
+ *   "slab.<k>" [orl_rnn_floats]                            slab k of the split weight gradients (one the last step wrote)
+ * du, dt, dz, dgi, dgh and dxl live in buffers that the stages of a step share: the name of a stage that a later one has overwritten
+ * is refused (readable: index 0, and dxl.1 / dxl.2), unless orl_rnn_debug_keep is on. */
+/* Tests only.  on != 0: every backward stage of the following steps writes a matrix of its own (same pitches and run strides as the
+ * shared ones; no kernel, launch or copy is added, and the results are the same bits), so that all of them can be read back; 0: the
+ * shared buffers again (the default) and the extra matrices freed.  Either change waits for the stream and forgets the last step's taps. */
+int orl_rnn_debug_keep(orl_rnn* d, int on);
 /* Timing of the training steps with device events (off by default).  While enabled every step records events around its phases;
  * orl_rnn_profile_read waits for the last step and writes its milliseconds: ms[0] the whole step, [1] the forward, [2] the forward
  * scans of all layers, [3] the loss and the backward, [4] the backward scans of all layers, [5] Adam. */

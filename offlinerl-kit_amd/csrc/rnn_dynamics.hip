@@ -511,6 +511,11 @@ struct RnnWs {
   DevMat dPRED, dX, DU, DZ, DT, dZM, dCAT, dGI, dGH, dXL[2];
   float *part = nullptr, *chunk = nullptr;            // [runs][cap][pn], [runs][chunks of cap][pn]
   long mk_rs = 0, part_rs = 0, chunk_rs = 0;          // their run strides
+  // What each stage of the backward writes: GRU layer l's dGI / dGH and the dXL of its input, block i's DU and DT, norm slot s's DZ.
+  // By default they are views of the shared buffers above (every layer's dGI is dGI, layer l's dXL is dXL[l & 1], ...), which a later
+  // stage overwrites; with keep (orl_rnn_debug_keep, tests only) every stage owns a matrix of the same pitch and run stride
+  std::vector<DevMat> dGIl, dGHl, dXLl, DUb, DTb, DZs;
+  bool keep = false;
 };
 
 struct orl_rnn {
@@ -550,6 +555,8 @@ static int rnn_mat_runs(orl_rnn* d, DevMat& v, long rows, int cols, int runs) {
   return d->mem.alloc(&v.p, (size_t)runs * rows * v.pitch);
 }
 
+static int rnn_ws_stages(orl_rnn* d, RnnWs& w, bool keep);
+
 static int rnn_ws_alloc(orl_rnn* d, RnnWs& w, long rows, bool train, int runs) {
   const int H = d->H, L = d->L, nb = d->nb;
   auto rnn_mat = [runs](orl_rnn* o, DevMat& v, long n, int cols) { return rnn_mat_runs(o, v, n, cols, runs); };
@@ -578,6 +585,34 @@ static int rnn_ws_alloc(orl_rnn* d, RnnWs& w, long rows, bool train, int runs) {
   }
   if (bad) return -1;
   w.cap = rows; w.runs = runs; w.train = train;
+  return train ? rnn_ws_stages(d, w, false) : 0;
+}
+
+// the per-stage views of the backward: onto the shared buffers, or (keep) onto matrices of their own.  The stream is idle
+static int rnn_ws_stages(orl_rnn* d, RnnWs& w, bool keep) {
+  const int H = d->H, L = d->L, nb = d->nb;
+  std::vector<DevMat>* all[] = {&w.dGIl, &w.dGHl, &w.dXLl, &w.DUb, &w.DTb, &w.DZs};
+  if (w.keep)
+    for (auto* v : all)
+      for (DevMat& m : *v) d->mem.free(m.p);
+  w.keep = false;
+  w.dGIl.assign(L, w.dGI); w.dGHl.assign(L, w.dGH); w.dXLl.resize(L);
+  for (int l = 0; l < L; ++l) w.dXLl[l] = w.dXL[l & 1];
+  w.DUb.assign(nb, w.DU); w.DTb.assign(nb, w.DT); w.DZs.assign(nb + 1, w.DZ);
+  if (!keep) return 0;
+  for (auto* v : all)
+    for (DevMat& m : *v) m = DevMat();
+  w.keep = true;
+  bool bad = false;
+  for (int l = 0; l < L && !bad; ++l)
+    bad = rnn_mat_runs(d, w.dGIl[l], w.cap, 3 * H, w.runs) || rnn_mat_runs(d, w.dGHl[l], w.cap, 3 * H, w.runs) ||
+          rnn_mat_runs(d, w.dXLl[l], w.cap, H, w.runs);
+  for (int i = 0; i < nb && !bad; ++i) bad = rnn_mat_runs(d, w.DUb[i], w.cap, H, w.runs) || rnn_mat_runs(d, w.DTb[i], w.cap, H, w.runs);
+  for (int s = 0; s <= nb && !bad; ++s) bad = rnn_mat_runs(d, w.DZs[s], w.cap, H, w.runs);
+  if (bad) {
+    rnn_ws_stages(d, w, false);
+    return -1;
+  }
   return 0;
 }
 
@@ -704,17 +739,20 @@ static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
     RnnNormP nb = rnn_norm_params(d, rs, w, 1 + i, N, w.SB[i], w.UB[i], d->norm_b[i], drop);
     if (i == d->nb - 1) { nb.nterm = 1; nb.g[0] = w.dX.p; nb.gpitch[0] = w.dX.pitch; nb.g_rs[0] = w.dX.s0; }
     else {
-      nb.nterm = 2; nb.g[0] = w.DU.p; nb.gpitch[0] = w.DU.pitch; nb.g_rs[0] = w.DU.s0;
-      nb.g[1] = w.DT.p; nb.gpitch[1] = w.DT.pitch; nb.g_rs[1] = w.DT.s0;
+      const DevMat &gu = w.DUb[i + 1], &gt = w.DTb[i + 1];
+      nb.nterm = 2; nb.g[0] = gu.p; nb.gpitch[0] = gu.pitch; nb.g_rs[0] = gu.s0;
+      nb.g[1] = gt.p; nb.gpitch[1] = gt.pitch; nb.g_rs[1] = gt.s0;
     }
+    const DevMat &DU = w.DUb[i], &DZ = w.DZs[1 + i];
     nb.zpre = w.ZB[i].p; nb.zp = w.ZB[i].pitch; nb.z_rs = w.ZB[i].s0;
-    nb.du = w.DU.p; nb.dup = w.DU.pitch; nb.du_rs = w.DU.s0;       // (a lane overwrites only the elements it has read itself)
-    nb.dz = w.DZ.p; nb.dzp = w.DZ.pitch; nb.dz_rs = w.DZ.s0;
+    nb.du = DU.p; nb.dup = DU.pitch; nb.du_rs = DU.s0;             // (shared: a lane overwrites only the elements it has read itself)
+    nb.dz = DZ.p; nb.dzp = DZ.pitch; nb.dz_rs = DZ.s0;
     nb.part = w.part + (long)(1 + i) * 2 * H; nb.pn = pn; nb.part_rs = w.part_rs;
     DEV_LAUNCH(d->stream, k_rnn_ln_bwd, dim3((unsigned)N, R), dim3(64), 0, nb);
-    if (rnn_wgrad(d, w.DZ, Xin, (int)N, d->lin_b[i], H, H) || rnn_dgrad(d, rs, w.DZ, (int)N, d->lin_b[i], H, H, w.DT)) return -1;
+    if (rnn_wgrad(d, DZ, Xin, (int)N, d->lin_b[i], H, H) || rnn_dgrad(d, rs, DZ, (int)N, d->lin_b[i], H, H, w.DTb[i])) return -1;
   }
-  DEV_LAUNCH(d->stream, k_rnn_swish_bwd, dim3(rnn_ew_grid(N * H), R), dim3(256), 0, w.DU.p, w.DU.pitch, w.DU.s0, w.DT.p, w.DT.pitch, w.DT.s0,
+  const DevMat &DU0 = w.DUb[0], &DT0 = w.DTb[0];
+  DEV_LAUNCH(d->stream, k_rnn_swish_bwd, dim3(rnn_ew_grid(N * H), R), dim3(256), 0, DU0.p, DU0.pitch, DU0.s0, DT0.p, DT0.pitch, DT0.s0,
               w.ZM.p, w.ZM.pitch, w.ZM.s0, w.dZM.p, w.dZM.pitch, w.dZM.s0, N, H);
   if (rnn_wgrad(d, w.dZM, w.CAT, (int)N, d->lin_merge, 2 * H, H) || rnn_dgrad(d, rs, w.dZM, (int)N, d->lin_merge, 2 * H, H, w.dCAT)) return -1;
   // the input block (no residual, no gradient to the net's input)
@@ -722,10 +760,11 @@ static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
     RnnNormP n0 = rnn_norm_params(d, rs, w, 0, N, w.SI, w.UI, d->norm_in, drop);
     n0.nterm = 1; n0.g[0] = w.dCAT.p; n0.gpitch[0] = w.dCAT.pitch; n0.g_rs[0] = w.dCAT.s0;
     n0.zpre = w.ZI.p; n0.zp = w.ZI.pitch; n0.z_rs = w.ZI.s0;
-    n0.dz = w.DZ.p; n0.dzp = w.DZ.pitch; n0.dz_rs = w.DZ.s0;
+    const DevMat& DZ = w.DZs[0];
+    n0.dz = DZ.p; n0.dzp = DZ.pitch; n0.dz_rs = DZ.s0;
     n0.part = w.part; n0.pn = pn; n0.part_rs = w.part_rs;
     DEV_LAUNCH(d->stream, k_rnn_ln_bwd, dim3((unsigned)N, R), dim3(64), 0, n0);
-    if (rnn_wgrad(d, w.DZ, w.X0, (int)N, d->lin_in, d->in, H)) return -1;
+    if (rnn_wgrad(d, DZ, w.X0, (int)N, d->lin_in, d->in, H)) return -1;
   }
   {
     const int chunks = (int)((N + RNN_CHUNK - 1) / RNN_CHUNK);
@@ -745,15 +784,16 @@ static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
     bp.dout = dOut.p; bp.dop = dOut.pitch; bp.do_rs = dOut.s0;
     bp.whh = d->params + d->whh[l].w; bp.par_rs = d->P;
     bp.r = w.R[l].p; bp.z = w.Z[l].p; bp.n = w.NN[l].p; bp.hn = w.HN[l].p; bp.hp = w.HP[l].p; bp.sp = w.R[l].pitch; bp.s_rs = w.R[l].s0;
-    bp.dgi = w.dGI.p; bp.dgh = w.dGH.p; bp.gp = w.dGI.pitch; bp.g_rs = w.dGI.s0;
+    const DevMat &dGI = w.dGIl[l], &dGH = w.dGHl[l];
+    bp.dgi = dGI.p; bp.dgh = dGH.p; bp.gp = dGI.pitch; bp.g_rs = dGI.s0;
     rnn_mark(d, true, 6 + 4 * l);
     DEV_LAUNCH(d->stream, k_rnn_scan_bwd, dim3((rows + RNN_RB - 1) / RNN_RB, R), dim3(64 * RNN_BWD_WAVES), d->lds_bwd, bp);
     rnn_mark(d, true, 7 + 4 * l);
     const DevMat& Xl = l ? w.HO[l - 1] : w.X0;
-    if (rnn_wgrad(d, w.dGH, w.HP[l], (int)N, d->whh[l], H, 3 * H) || rnn_wgrad(d, w.dGI, Xl, (int)N, d->wih[l], l ? H : d->in, 3 * H)) return -1;
+    if (rnn_wgrad(d, dGH, w.HP[l], (int)N, d->whh[l], H, 3 * H) || rnn_wgrad(d, dGI, Xl, (int)N, d->wih[l], l ? H : d->in, 3 * H)) return -1;
     if (l == 0) break;
-    if (rnn_dgrad(d, rs, w.dGI, (int)N, d->wih[l], H, 3 * H, w.dXL[l & 1])) return -1;
-    dOut = w.dXL[l & 1];
+    if (rnn_dgrad(d, rs, dGI, (int)N, d->wih[l], H, 3 * H, w.dXLl[l])) return -1;
+    dOut = w.dXLl[l];
   }
   const long RP = (long)R * d->P;
   DEV_LAUNCH(d->stream, k_rnn_slab_sum, dim3(rnn_ew_grid(RP)), dim3(256), 0, (const float*)d->slabs, RP, rnn_slabs(d, N), d->grads);
@@ -1126,7 +1166,47 @@ int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* hos
     if (!w->train || !(d->c.dropout_rate > 0.f)) return fail("orl_rnn_debug_read: no dropout mask was applied");
     src = w->MK + (size_t)k * w->cap * d->H; rs = w->mk_rs;
   }
-  else return fail("orl_rnn_debug_read: unknown tap " + nm);
+  else if ((k = rnn_tap_index(nm, "gi.", d->L)) >= 0) { mat(w->GI[k]); cols = 3 * d->H; }
+  else if (nm == "x0") { mat(w->X0); cols = d->in; }
+  else {
+    // what only a training step computes.  st: the stage's index when the matrix is one of a shared buffer's stages, last: the stage
+    // that writes the shared buffer last (the one still readable without orl_rnn_debug_keep)
+    int st = -1, last = 0;
+    const int H = d->H, L = d->L, nb = d->nb;
+    const long pn = (long)d->norms * 2 * H;
+    bool tr = true;
+    if (nm == "tgt") { src = d->TGT; rs = w->cap * d->od; cols = pitch = d->od; }
+    else if (nm == "msk") { src = d->MSK; rs = w->cap; cols = pitch = 1; }
+    else if ((k = rnn_tap_index(nm, "r.", L)) >= 0) { if (w->train) mat(w->R[k]); }
+    else if ((k = rnn_tap_index(nm, "z.", L)) >= 0) { if (w->train) mat(w->Z[k]); }
+    else if ((k = rnn_tap_index(nm, "n.", L)) >= 0) { if (w->train) mat(w->NN[k]); }
+    else if ((k = rnn_tap_index(nm, "hn.", L)) >= 0) { if (w->train) mat(w->HN[k]); }
+    else if ((k = rnn_tap_index(nm, "hp.", L)) >= 0) { if (w->train) mat(w->HP[k]); }
+    else if ((k = rnn_tap_index(nm, "zpre.", d->norms)) >= 0) mat(k ? w->ZB[k - 1] : w->ZI);
+    else if (nm == "zmerge") mat(w->ZM);
+    else if (nm == "dpred") { mat(w->dPRED); cols = d->od; }
+    else if (nm == "dx") mat(w->dX);
+    else if (nm == "dzm") mat(w->dZM);
+    else if (nm == "dcat") { mat(w->dCAT); cols = 2 * H; }
+    else if ((k = rnn_tap_index(nm, "du.", nb)) >= 0) { if (w->train) mat(w->DUb[k]); st = k; }
+    else if ((k = rnn_tap_index(nm, "dt.", nb)) >= 0) { if (w->train) mat(w->DTb[k]); st = k; }
+    else if ((k = rnn_tap_index(nm, "dz.", d->norms)) >= 0) { if (w->train) mat(w->DZs[k]); st = k; }
+    else if ((k = rnn_tap_index(nm, "dgi.", L)) >= 0) { if (w->train) mat(w->dGIl[k]); cols = 3 * H; st = k; }
+    else if ((k = rnn_tap_index(nm, "dgh.", L)) >= 0) { if (w->train) mat(w->dGHl[k]); cols = 3 * H; st = k; }
+    else if ((k = rnn_tap_index(nm, "dxl.", L)) >= 1) { if (w->train) mat(w->dXLl[k]); st = k; last = k < 3 ? k : k - 2; }   // (layer 1 reuses layer 3's)
+    else if (nm == "part") { src = w->part; rs = w->part_rs; cols = pitch = (int)pn; }
+    else if (nm == "chunk") { src = w->chunk; rs = w->chunk_rs; cols = pitch = (int)pn; rows = (rows + RNN_CHUNK - 1) / RNN_CHUNK; }
+    else if ((k = rnn_tap_index(nm, "slab.", 8)) >= 0) {
+      if (d->last_ws && w->train && k >= rnn_slabs(d, d->last_rows))
+        return fail("orl_rnn_debug_read: the last step wrote " + std::to_string(rnn_slabs(d, d->last_rows)) + " slabs, " + nm + " is none of them");
+      src = d->slabs + (long)k * d->R * d->P; rs = d->P; rows = d->last_ws ? 1 : 0; cols = pitch = (int)d->P;
+    }
+    else tr = false;
+    if (!tr) return fail("orl_rnn_debug_read: unknown tap " + nm);
+    if (d->last_ws && !w->train) return fail("orl_rnn_debug_read: only a training step computes " + nm + " (the last pass was a forward)");
+    if (d->last_ws && !w->keep && st >= 0 && st != last)
+      return fail("orl_rnn_debug_read: a later stage of the step has overwritten " + nm + " (orl_rnn_debug_keep keeps every stage's)");
+  }
   if (!src || rows < 1 || (!d->last_ws && nm != "loss")) return fail("orl_rnn_debug_read: nothing recorded for " + nm);
   if (nm != "loss") {                                         // the run's slot in the workspace of the last pass
     if (run < d->last_r0 || run >= d->last_r0 + d->last_nr) return fail("orl_rnn_debug_read: the last pass did not compute run " + std::to_string(run));
@@ -1141,6 +1221,13 @@ int64_t orl_rnn_debug_read(orl_rnn* d, const char* name, float* host, int64_t ca
   if (!d || !name || !host) return fail("orl_rnn_debug_read: bad arguments");
   if (rnn_one_run_only(d, "orl_rnn_debug_read", "orl_rnn_debug_read_run")) return -1;
   return orl_rnn_debug_read_run(d, 0, name, host, cap);
+}
+int orl_rnn_debug_keep(orl_rnn* d, int on) {
+  if (rnn_ready(d, "orl_rnn_debug_keep", false)) return -1;
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  if ((on != 0) == d->tw.keep) return 0;
+  if (d->last_ws == &d->tw) d->last_ws = nullptr;          // the stages of the last step are not where the views point any more
+  return rnn_ws_stages(d, d->tw, on != 0);
 }
 int orl_rnn_profile(orl_rnn* d, int enable) {
   if (rnn_ready(d, "orl_rnn_profile", false)) return -1;

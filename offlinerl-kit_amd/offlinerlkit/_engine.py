@@ -79,6 +79,8 @@ ABI_SYMBOLS = [
     # ... and its forms for objects of several runs
     "orl_rnn_set_run", "orl_rnn_get_run", "orl_rnn_step_runs", "orl_rnn_learn_epoch_runs", "orl_rnn_forward_runs", "orl_rnn_debug_read_run",
     "orl_rnn_debug_grads_run",
+    # ... and the tests' switch that keeps every backward stage readable
+    "orl_rnn_debug_keep",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -419,6 +421,7 @@ def _bind_rnn(lib) -> None:
     lib.orl_rnn_debug_read_run.argtypes = [P, C.c_int, C.c_char_p, VP, I64]
     lib.orl_rnn_debug_read_run.restype = I64
     lib.orl_rnn_debug_grads_run.argtypes = [P, C.c_int, VP, I64]
+    lib.orl_rnn_debug_keep.argtypes = [P, C.c_int]
     lib.orl_rnn_profile.argtypes = [P, C.c_int]
     lib.orl_rnn_profile_read.argtypes = [P, C.POINTER(C.c_float)]
 
@@ -1767,6 +1770,11 @@ class RnnDynamicsEngine(_Handle):
         if n < 0:
             raise RuntimeError(f"orl_rnn_debug_read({name!r}) failed: {last_error()}")
         return buf[:n].copy()
+
+    def debug_keep(self, on: bool = True):
+        """tests only: every backward stage of the following steps writes a matrix of its own, so that ``debug_read`` reaches all of
+        them (``dgi.<l>``, ``dz.<s>``, ...); off: the shared buffers again.  Same launches, same bits either way."""
+        _check(self.lib.orl_rnn_debug_keep(self._h, int(bool(on))), "orl_rnn_debug_keep")
 
     def debug_grads(self, run: int = 0) -> np.ndarray:
         flat = np.empty(self.floats, np.float32)
