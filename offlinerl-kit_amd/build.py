@@ -29,8 +29,8 @@ UNITS = {
     "gemm_inst_swish.hip": GEMM_H,
     "gemm_inst_leaky.hip": GEMM_H,
     "dynamics.hip": ["devobj.h", "reduce.h", "gemm.h", "rng.h", ABI],
-    "diffusion.hip": ["devobj.h", "reduce.h", "gemm.h", "rng.h", ABI],
-    "rnn_dynamics.hip": ["devobj.h", "reduce.h", "gemm.h", "rng.h", ABI],
+    "diffusion.hip": ["devobj.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
+    "rnn_dynamics.hip": ["devobj.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
     "ws_fwd.hip": WS_H,
     "ws_dgrad.hip": WS_H,
     "ws_fwd3.hip": WS_H,

@@ -1,9 +1,10 @@
 // devobj.h — the host layer under every device object of the C ABI (engine.h, dynamics.hip, diffusion.hip): error plumbing, the
-// tracked allocator, the parameter block's tensor table, flat-block transfers, call staging, and the GemmP of a linear layer's three
-// products from matrix views.  A new stand-alone model starts from these instead of copying them ("Device-object layer").
+// tracked allocator, the parameter block's tensor table, flat-block transfers, call staging, the GemmP of a linear layer's three
+// products from matrix views with their workspace matrices and tile choice, and the learn-epoch driver.  A new stand-alone model starts from these instead of copying them ("Device-object layer").
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -209,6 +210,50 @@ static inline GemmP linear_wgrad_p(const DevMat& dY, const DevMat& X, int M, con
 }
 static inline int gemm_done(hipError_t e, const char* what) {
   return e == hipSuccess ? 0 : fail(std::string(what) + " gemm: " + hipGetErrorString(e));
+}
+// a zero-filled [runs][rows][rup4(cols)] matrix (s0: the run stride) in place of whatever v held
+static inline int dev_mat(DevAllocs& mem, DevMat& v, long rows, int cols, int runs = 1) {
+  mem.free(v.p);
+  v.pitch = v.lim = rup4(cols);
+  v.s0 = rows * v.pitch;
+  return mem.alloc(&v.p, (size_t)runs * rows * v.pitch);
+}
+// Tile choice of the forward and dgrad products.  pick_cfg's rule for long reductions (K >= 1024 -> 256 x 128 tiles) is meant for
+// split weight gradients; at 256 rows it leaves a 1024-wide layer with 8 workgroups.  Few rows: 16 x 64 tiles while they give at most
+// four rounds of workgroups on the 256 CUs, 64 x 64 beyond; many rows (a large sampling batch): the 64 x 256 forward tile.
+static inline int linear_cfg(int M, int N) {
+  if (N <= 16) return CFG_TALL;
+  if (M >= 2048 && N >= 128) return CFG_BIG;
+  const long small_tiles = (long)((M + 15) / 16) * ((N + 63) / 64);
+  return (M <= 32 || small_tiles <= 1024) ? CFG_SMALL : CFG_MID;
+}
+// blocks of 256 threads over n elements
+static inline int ew_grid(long n) { return (int)((n + 255) / 256); }
+
+// One epoch of R runs in steps of B rows, without a host round trip: run r visits the rows orders[r][0 .. n_rows) of its n_data (host
+// indices are checked, device ones are the kernels' to clamp).  The orders go to idx_d ([R][n_rows], grown on demand) in one copy,
+// enqueue(idx_d + s B, rows, loss_steps + s R) queues step s (run r's indices start r n_rows entries past the pointer it is given), and
+// the [steps][R] losses come back after one synchronisation.  `what` names the entry point in the errors.
+template <class Enqueue>
+static int learn_epoch_steps(hipStream_t stream, DevAllocs& mem, long long** idx_d, long* idx_cap, float** loss_steps, long* loss_cap, int B,
+                             long n_data, int R, const char* what, const int64_t* orders, int64_t n_rows, int on_device, float* losses_out,
+                             Enqueue enqueue) {
+  const std::string w(what);
+  if (!orders || n_rows < 1) return fail(w + ": bad arguments");
+  if (!on_device)
+    for (int64_t i = 0; i < R * n_rows; ++i)
+      if (orders[i] < 0 || orders[i] >= n_data) return fail(w + ": row index out of range");
+  const long steps = (long)((n_rows + B - 1) / B);
+  if (mem.grow(idx_d, idx_cap, (long)R * std::max<long>((long)n_rows, B), stream)) return -1;
+  if (mem.grow(loss_steps, loss_cap, steps * R, stream)) return -1;
+  ORL_HIP(hipMemcpyAsync(*idx_d, orders, sizeof(int64_t) * R * n_rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  for (long s = 0; s < steps; ++s) {
+    const int rows = (int)std::min<int64_t>(B, n_rows - s * B);
+    if (enqueue(*idx_d + s * B, rows, *loss_steps + s * R)) return -1;
+  }
+  ORL_HIP(hipStreamSynchronize(stream));
+  if (losses_out) ORL_HIP(hipMemcpy(losses_out, *loss_steps, sizeof(float) * steps * R, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 }  // namespace orl

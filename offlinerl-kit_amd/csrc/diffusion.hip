@@ -17,11 +17,12 @@
 //                     the FiLM or the residual tail
 //   k_diff_norm_bwd   its backward: sums the gradient terms of the block's consumers, dX, the FiLM dscale / dbias, and the row's
 //                     terms of dgamma / dbeta into a [rows][norm floats] slab that k_diff_colsum adds in row order (no atomics)
-//   k_diff_loss       the MSE, its seed 2 (pred - eps) / (rows act_dim)
+//   k_mse_loss<false> the MSE, its seed 2 (pred - eps) / (rows act_dim) (train_ops.h)
 //   k_diff_adam_ema   torch.optim.Adam with lr[k] read from the device table, then ema <- ema decay + p (1 - decay)
 // Sampling is N forward-only passes on the EMA block with k_diff_ddpm between them and one host synchronisation at the end.
-// Allocation, the tensor table, transfers, staging and the GemmP of a Linear's products come from devobj.h; the wave / block sums
-// and softplus from reduce.h.
+// Allocation, the tensor table, transfers, staging, the workspace matrices, the GemmP and tile choice of a Linear's products and the
+// learn-epoch driver come from devobj.h; the wave / block sums and softplus from reduce.h; the norm statistics and backward core, the
+// loss and Adam's element update from train_ops.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -32,6 +33,7 @@
 #include "devobj.h"
 #include "reduce.h"
 #include "rng.h"
+#include "train_ops.h"
 
 namespace orl {
 
@@ -124,6 +126,7 @@ __global__ void k_diff_mish_bwd(const float* __restrict__ dy, int dp, const floa
   dz[(long)r * op + c] = dy[(long)r * dp + c] * diff_mish_grad(z[(long)r * zp + c]).dy;
 }
 // dst[r][c] = src[idx ? idx[r] : r][c]; a gathered row index is clamped to [0, src_rows)
+// (not merged with k_rnn_copy: that one addresses by run and time step, this one through a row index)
 __global__ void k_diff_copy(const float* __restrict__ src, int sp, const long long* __restrict__ idx, long src_rows,
                             float* __restrict__ dst, int dp, long rows, int cols) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -147,32 +150,13 @@ struct DiffNormP {
   float* part; long pn;            // [row][pn]: dgamma at [c], dbeta at [C + c]
 };
 
-// statistics of one (row, group) in one wave: the group's values in registers, mean, then the centred second moment
-__device__ __forceinline__ void diff_group_stats(const DiffNormP& p, int row, int c0, int lane, float (&v)[DIFF_NJ], float& mean, float& rstd) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < DIFF_NJ; ++j) {
-    const int c = lane + 64 * j;
-    v[j] = c < p.cg ? p.h[(long)row * p.hp + c0 + c] : 0.f;
-    s += v[j];
-  }
-  mean = wave_sum(s) / (float)p.cg;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < DIFF_NJ; ++j) {
-    const float dlt = (lane + 64 * j) < p.cg ? v[j] - mean : 0.f;
-    q += dlt * dlt;
-  }
-  rstd = 1.f / sqrtf(wave_sum(q) / (float)p.cg + 1e-5f);
-}
-
 // GroupNorm (eps 1e-5, affine) + Mish + the optional FiLM or residual tail; one block per row, one wave per group
 __global__ void k_diff_norm_fwd(DiffNormP p) {
   const int row = blockIdx.x, g = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (row >= p.rows) return;
   const int c0 = g * p.cg;
   float v[DIFF_NJ], mean, rstd;
-  diff_group_stats(p, row, c0, lane, v, mean, rstd);
+  norm_stats(p.h + (long)row * p.hp + c0, p.cg, lane, v, mean, rstd);
 #pragma unroll
   for (int j = 0; j < DIFF_NJ; ++j) {
     const int c = c0 + lane + 64 * j;
@@ -189,7 +173,7 @@ __global__ void k_diff_norm_bwd(DiffNormP p) {
   if (row >= p.rows) return;
   const int c0 = g * p.cg;
   float v[DIFF_NJ], mean, rstd;
-  diff_group_stats(p, row, c0, lane, v, mean, rstd);
+  norm_stats(p.h + (long)row * p.hp + c0, p.cg, lane, v, mean, rstd);
   float dxh[DIFF_NJ], xh[DIFF_NJ];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -217,42 +201,22 @@ __global__ void k_diff_norm_bwd(DiffNormP p) {
       s2 += dxh[j] * xh[j];
     }
   }
-  s1 = wave_sum(s1) / (float)p.cg;
-  s2 = wave_sum(s2) / (float)p.cg;
+  const NormBwd nb(s1, s2, rstd, p.cg);
 #pragma unroll
   for (int j = 0; j < DIFF_NJ; ++j) {
     if (lane + 64 * j >= p.cg) break;
-    p.dh[(long)row * p.dhp + c0 + lane + 64 * j] = rstd * (dxh[j] - s1 - xh[j] * s2);
+    p.dh[(long)row * p.dhp + c0 + lane + 64 * j] = nb.dx(dxh[j], xh[j]);
   }
 }
 
 // G[j] = sum over rows (in row order) of part[row][j]: the dgamma / dbeta of every norm in one launch
+// (not merged with rnn_dynamics.hip's two-level column sums: the orders of summation differ and the tests pin both)
 __global__ void k_diff_colsum(const float* __restrict__ part, long pn, int rows, float* __restrict__ G) {
   const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= pn) return;
   float s = 0.f;
   for (int r = 0; r < rows; ++r) s += part[(long)r * pn + j];
   G[j] = s;
-}
-
-// loss = mean over (rows x ad) of (pred - eps)^2, dPRED = 2 (pred - eps) / (rows ad); one block, fixed order
-__global__ __launch_bounds__(256) void k_diff_loss(const float* __restrict__ pred, int pp, const float* __restrict__ eps, int rows, int ad,
-                                                   float* __restrict__ dpred, float* loss_out, float* loss_last) {      // (the two may be one cell)
-  const int n = rows * ad;
-  const float inv = 1.f / (float)n;
-  float s = 0.f;
-  for (int e = threadIdx.x; e < n; e += 256) {
-    const int r = e / ad, d = e - r * ad;
-    const float df = pred[(long)r * pp + d] - eps[e];
-    s += df * df;
-    dpred[(long)r * pp + d] = 2.f * df * inv;
-  }
-  s = block_sum256_pairwise(s);
-  if (threadIdx.x == 0) {
-    const float l = s * inv;
-    *loss_out = l;
-    *loss_last = l;
-  }
 }
 
 // torch.optim.Adam (exp_avg lerp, exp_avg_sq, the bias corrections of step k + 1) with lr[k] from the device table, then the EMA
@@ -263,11 +227,9 @@ __global__ __launch_bounds__(256) void k_diff_adam_ema(float* __restrict__ param
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
   const float step = (float)(lr_tab[k] / bc1);
-  const float g = G[i];
-  const float m = m_[i] + (g - m_[i]) * (1.0f - b1);
-  const float v = v_[i] * b2 + (1.0f - b2) * g * g;
+  float m = m_[i], v = v_[i];
+  const float w = adam_update(params[i], m, v, G[i], step, bc2s, 1.0f - b1, b2, 1.0f - b2, eps);
   m_[i] = m; v_[i] = v;
-  const float w = params[i] - step * (m / (sqrtf(v) / bc2s + eps));
   params[i] = w;
   ema[i] = __fadd_rn(__fmul_rn(ema[i], decay), __fmul_rn(w, omd));
 }
@@ -346,36 +308,29 @@ struct orl_diffusion {
   DevAllocs mem{"orl_diffusion"};
 };
 
-// a zero-filled [rows][rup4(cols)] matrix
-static int diff_mat(orl_diffusion* d, DevMat& v, long rows, int cols) {
-  d->mem.free(v.p);
-  v.pitch = v.lim = rup4(cols);
-  return d->mem.alloc(&v.p, (size_t)rows * v.pitch);
-}
-
 static int diff_ws_alloc(orl_diffusion* d, DiffWs& w, long rows, bool train) {
   const size_t nb = d->blocks.size();
   w.CAT.resize(nb); w.HR.resize(nb); w.Y1.resize(nb); w.H2.resize(nb); w.OUT.resize(nb);
   w.D2.resize(nb); w.DR.resize(nb); w.DX.resize(nb);
-  bool bad = diff_mat(d, w.XT, rows, d->ad) || diff_mat(d, w.E0, rows, d->dsed) || diff_mat(d, w.Z1, rows, 4 * d->dsed) ||
-             diff_mat(d, w.M1, rows, 4 * d->dsed) || diff_mat(d, w.GF, rows, d->cond) || diff_mat(d, w.MC, rows, d->cond) ||
-             diff_mat(d, w.FILM, rows, d->film_cols) || diff_mat(d, w.HF, rows, d->start_dim) || diff_mat(d, w.YF, rows, d->start_dim) ||
-             diff_mat(d, w.PRED, rows, d->ad);
+  bool bad = dev_mat(d->mem, w.XT, rows, d->ad) || dev_mat(d->mem, w.E0, rows, d->dsed) || dev_mat(d->mem, w.Z1, rows, 4 * d->dsed) ||
+             dev_mat(d->mem, w.M1, rows, 4 * d->dsed) || dev_mat(d->mem, w.GF, rows, d->cond) || dev_mat(d->mem, w.MC, rows, d->cond) ||
+             dev_mat(d->mem, w.FILM, rows, d->film_cols) || dev_mat(d->mem, w.HF, rows, d->start_dim) || dev_mat(d->mem, w.YF, rows, d->start_dim) ||
+             dev_mat(d->mem, w.PRED, rows, d->ad);
   int wmax = 4;
   for (size_t b = 0; b < nb && !bad; ++b) {
     const DiffBlock& k = d->blocks[b];
     wmax = std::max(wmax, k.out);
-    bad = (k.skip >= 0 && diff_mat(d, w.CAT[b], rows, k.in)) || diff_mat(d, w.HR[b], rows, k.res ? 2 * k.out : k.out) ||
-          diff_mat(d, w.Y1[b], rows, k.out) || diff_mat(d, w.H2[b], rows, k.out) || diff_mat(d, w.OUT[b], rows, k.out);
+    bad = (k.skip >= 0 && dev_mat(d->mem, w.CAT[b], rows, k.in)) || dev_mat(d->mem, w.HR[b], rows, k.res ? 2 * k.out : k.out) ||
+          dev_mat(d->mem, w.Y1[b], rows, k.out) || dev_mat(d->mem, w.H2[b], rows, k.out) || dev_mat(d->mem, w.OUT[b], rows, k.out);
     if (train && !bad)
-      bad = diff_mat(d, w.D2[b], rows, k.res ? 2 * k.out : k.out) || (!k.res && diff_mat(d, w.DR[b], rows, k.out)) ||
-            (k.src >= 0 && diff_mat(d, w.DX[b], rows, k.in));
+      bad = dev_mat(d->mem, w.D2[b], rows, k.res ? 2 * k.out : k.out) || (!k.res && dev_mat(d->mem, w.DR[b], rows, k.out)) ||
+            (k.src >= 0 && dev_mat(d->mem, w.DX[b], rows, k.in));
   }
   if (train && !bad)
-    bad = diff_mat(d, w.dPRED, rows, d->ad) || diff_mat(d, w.dYF, rows, d->start_dim) || diff_mat(d, w.dHF, rows, d->start_dim) ||
-          diff_mat(d, w.dLAST, rows, d->start_dim) || diff_mat(d, w.dFILM, rows, d->film_cols) || diff_mat(d, w.dMC, rows, d->cond) ||
-          diff_mat(d, w.dE, rows, d->dsed) || diff_mat(d, w.dM1, rows, 4 * d->dsed) || diff_mat(d, w.dZ1, rows, 4 * d->dsed) ||
-          diff_mat(d, w.dH2, rows, wmax) || diff_mat(d, w.dY1, rows, wmax) ||
+    bad = dev_mat(d->mem, w.dPRED, rows, d->ad) || dev_mat(d->mem, w.dYF, rows, d->start_dim) || dev_mat(d->mem, w.dHF, rows, d->start_dim) ||
+          dev_mat(d->mem, w.dLAST, rows, d->start_dim) || dev_mat(d->mem, w.dFILM, rows, d->film_cols) || dev_mat(d->mem, w.dMC, rows, d->cond) ||
+          dev_mat(d->mem, w.dE, rows, d->dsed) || dev_mat(d->mem, w.dM1, rows, 4 * d->dsed) || dev_mat(d->mem, w.dZ1, rows, 4 * d->dsed) ||
+          dev_mat(d->mem, w.dH2, rows, wmax) || dev_mat(d->mem, w.dY1, rows, wmax) ||
           (d->mem.free(w.part), d->mem.alloc(&w.part, (size_t)rows * d->norm_n));
   if (bad) return -1;
   w.cap = rows; w.train = train;
@@ -383,34 +338,23 @@ static int diff_ws_alloc(orl_diffusion* d, DiffWs& w, long rows, bool train) {
 }
 
 // ---- the matrix products (csrc/gemm.h), one problem per launch ----
-// Tile choice of the forward and dgrad products.  pick_cfg's rule for long reductions (K >= 1024 -> 256 x 128 tiles) is meant for
-// split weight gradients; at 256 rows it leaves a 1024-wide layer with 8 workgroups.  Few rows: 16 x 64 tiles while they give at most
-// four rounds of workgroups on the 256 CUs, 64 x 64 beyond; many rows (a large sampling batch): the 64 x 256 forward tile.
-static int diff_cfg(int M, int N) {
-  if (N <= 16) return CFG_TALL;
-  if (M >= 2048 && N >= 128) return CFG_BIG;
-  const long small_tiles = (long)((M + 15) / 16) * ((N + 63) / 64);
-  return (M <= 32 || small_tiles <= 1024) ? CFG_SMALL : CFG_MID;
-}
 // the nn.Linear at offsets w / b of `block` (the parameters, the EMA or the gradients): W [out][in]
 static LinearP diff_linear(float* block, long w, long b, int in, int out) { return {{block + w, 0, 0}, {block + b, 0, 0}, in, out, false, 1}; }
 // Y = X W^T + b
 static int diff_fwd(orl_diffusion* d, float* base, const DevMat& X, int M, long w, long b, int in, int out, const DevMat& Y) {
   const GemmP p = linear_fwd_p(X, M, diff_linear(base, w, b, in, out), Y);
-  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(diff_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32), "orl_diffusion forward");
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(linear_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32), "orl_diffusion forward");
 }
 // dX = dY W
 static int diff_dgrad(orl_diffusion* d, const DevMat& dY, int M, long w, int in, int out, const DevMat& dX) {
   const GemmP p = linear_dgrad_p(dY, M, diff_linear(d->params, w, 0, in, out), dX);
-  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(diff_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32), "orl_diffusion dgrad");
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(linear_cfg(p.M, p.N), p, 1, d->stream, false, false, P_F32), "orl_diffusion dgrad");
 }
 // dW = dY^T X ([out][in]) and db = the column sums of dY into the gradient block
 static int diff_wgrad(orl_diffusion* d, const DevMat& dY, const DevMat& X, int M, long w, long b, int in, int out) {
   const GemmP p = linear_wgrad_p(dY, X, M, diff_linear(d->grads, w, b, in, out));
   return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(pick_cfg(p.M, p.N, p.K, 1), p, 1, d->stream, false, false, P_F32), "orl_diffusion wgrad");
 }
-
-static int diff_ew_grid(long n) { return (int)((n + 255) / 256); }
 
 static DiffNormP diff_norm_params(orl_diffusion* d, const float* base, int rows, int C, const DevMat& h, long noff, int groups) {
   DiffNormP p;
@@ -426,18 +370,18 @@ static DiffNormP diff_norm_params(orl_diffusion* d, const float* base, int rows,
 static int diff_forward(orl_diffusion* d, DiffWs& w, float* base, int rows, const DevMat& x) {
   const int ds = d->dsed;
   if (diff_fwd(d, base, w.E0, rows, d->s1w, d->s1b, ds, 4 * ds, w.Z1)) return -1;
-  DEV_LAUNCH(d->stream, k_diff_mish, dim3(diff_ew_grid((long)rows * 4 * ds)), dim3(256), 0, w.Z1.p, w.Z1.pitch, w.M1.p, w.M1.pitch, rows, 4 * ds);
+  DEV_LAUNCH(d->stream, k_diff_mish, dim3(ew_grid((long)rows * 4 * ds)), dim3(256), 0, w.Z1.p, w.Z1.pitch, w.M1.p, w.M1.pitch, rows, 4 * ds);
   if (diff_fwd(d, base, w.M1, rows, d->s2w, d->s2b, 4 * ds, ds, w.GF)) return -1;
-  DEV_LAUNCH(d->stream, k_diff_mish, dim3(diff_ew_grid((long)rows * d->cond)), dim3(256), 0, w.GF.p, w.GF.pitch, w.MC.p, w.MC.pitch, rows, d->cond);
+  DEV_LAUNCH(d->stream, k_diff_mish, dim3(ew_grid((long)rows * d->cond)), dim3(256), 0, w.GF.p, w.GF.pitch, w.MC.p, w.MC.pitch, rows, d->cond);
   if (diff_fwd(d, base, w.MC, rows, d->cw, d->cb, d->cond, d->film_cols, w.FILM)) return -1;
   for (size_t b = 0; b < d->blocks.size(); ++b) {
     const DiffBlock& k = d->blocks[b];
     DevMat X = k.src < 0 ? x : w.OUT[k.src];
     if (k.skip >= 0) {
       const int c1 = d->blocks[k.src].out, c2 = d->blocks[k.skip].out;
-      DEV_LAUNCH(d->stream, k_diff_copy, dim3(diff_ew_grid((long)rows * c1)), dim3(256), 0, X.p, X.pitch, (const long long*)nullptr, 0L, w.CAT[b].p,
+      DEV_LAUNCH(d->stream, k_diff_copy, dim3(ew_grid((long)rows * c1)), dim3(256), 0, X.p, X.pitch, (const long long*)nullptr, 0L, w.CAT[b].p,
                   w.CAT[b].pitch, (long)rows, c1);
-      DEV_LAUNCH(d->stream, k_diff_copy, dim3(diff_ew_grid((long)rows * c2)), dim3(256), 0, w.OUT[k.skip].p, w.OUT[k.skip].pitch, (const long long*)nullptr, 0L,
+      DEV_LAUNCH(d->stream, k_diff_copy, dim3(ew_grid((long)rows * c2)), dim3(256), 0, w.OUT[k.skip].p, w.OUT[k.skip].pitch, (const long long*)nullptr, 0L,
                   w.CAT[b].p + c1, w.CAT[b].pitch, (long)rows, c2);
       X = w.CAT[b];
     }
@@ -524,13 +468,13 @@ static int diff_backward(orl_diffusion* d, DiffWs& w, int rows, const DevMat& x)
   if (diff_wgrad(d, w.dFILM, w.MC, rows, d->cw, d->cb, d->cond, d->film_cols) ||
       diff_dgrad(d, w.dFILM, rows, d->cw, d->cond, d->film_cols, w.dMC))
     return -1;
-  DEV_LAUNCH(d->stream, k_diff_mish_bwd, dim3(diff_ew_grid((long)rows * ds)), dim3(256), 0, w.dMC.p, w.dMC.pitch, w.GF.p, w.GF.pitch, w.dE.p, w.dE.pitch,
+  DEV_LAUNCH(d->stream, k_diff_mish_bwd, dim3(ew_grid((long)rows * ds)), dim3(256), 0, w.dMC.p, w.dMC.pitch, w.GF.p, w.GF.pitch, w.dE.p, w.dE.pitch,
               rows, ds);
   if (diff_wgrad(d, w.dE, w.M1, rows, d->s2w, d->s2b, 4 * ds, ds) || diff_dgrad(d, w.dE, rows, d->s2w, 4 * ds, ds, w.dM1)) return -1;
-  DEV_LAUNCH(d->stream, k_diff_mish_bwd, dim3(diff_ew_grid((long)rows * 4 * ds)), dim3(256), 0, w.dM1.p, w.dM1.pitch, w.Z1.p, w.Z1.pitch, w.dZ1.p,
+  DEV_LAUNCH(d->stream, k_diff_mish_bwd, dim3(ew_grid((long)rows * 4 * ds)), dim3(256), 0, w.dM1.p, w.dM1.pitch, w.Z1.p, w.Z1.pitch, w.dZ1.p,
               w.dZ1.pitch, rows, 4 * ds);
   if (diff_wgrad(d, w.dZ1, w.E0, rows, d->s1w, d->s1b, ds, 4 * ds)) return -1;
-  DEV_LAUNCH(d->stream, k_diff_colsum, dim3(diff_ew_grid(d->norm_n)), dim3(256), 0, w.part, d->norm_n, rows, d->grads + d->norm_off);
+  DEV_LAUNCH(d->stream, k_diff_colsum, dim3(ew_grid(d->norm_n)), dim3(256), 0, w.part, d->norm_n, rows, d->grads + d->norm_off);
   return 0;
 }
 
@@ -556,12 +500,13 @@ static int diff_enqueue_step(orl_diffusion* d, const long long* idx, int rows, c
   ip.E0 = w.E0.p; ip.ep = w.E0.pitch; ip.GF = w.GF.p; ip.gp = w.GF.pitch;
   DEV_LAUNCH(d->stream, k_diff_input, dim3(rows), dim3(64), 0, ip);
   if (diff_forward(d, w, d->params, rows, w.XT)) return -1;
-  DEV_LAUNCH(d->stream, k_diff_loss, dim3(1), dim3(256), 0, w.PRED.p, w.PRED.pitch, d->EPS, rows, d->ad, w.dPRED.p, loss_dst, d->loss_cell);
+  DEV_LAUNCH(d->stream, k_mse_loss<false>, dim3(1), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, 0L, (const float*)d->EPS, (const float*)nullptr, 0L,
+              (long)rows, d->ad, w.dPRED.p, loss_dst, d->loss_cell);
   if (diff_backward(d, w, rows, w.XT)) return -1;
   const double tt = (double)(d->kstep + 1);
   const double bc1 = 1.0 - std::pow((double)d->c.adam_beta1, tt), bc2 = 1.0 - std::pow((double)d->c.adam_beta2, tt);
   const double decay = diff_ema_decay(d->kstep);
-  DEV_LAUNCH(d->stream, k_diff_adam_ema, dim3(diff_ew_grid(d->P)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, d->ema, d->P, d->lr_tab,
+  DEV_LAUNCH(d->stream, k_diff_adam_ema, dim3(ew_grid(d->P)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, d->ema, d->P, d->lr_tab,
               (long)d->kstep, bc1, (float)std::sqrt(bc2), d->c.adam_beta1, d->c.adam_beta2, d->c.adam_eps, (float)decay, (float)(1.0 - decay));
   d->kstep += 1;
   d->last_rows = rows;
@@ -795,22 +740,13 @@ int orl_diffusion_step(orl_diffusion* d, const int64_t* idx, int32_t rows, const
 
 int orl_diffusion_learn_epoch(orl_diffusion* d, const int64_t* order, int64_t n_rows, int on_device, float* losses_out) {
   if (diff_ready(d, "orl_diffusion_learn_epoch", true)) return -1;
-  if (!order || n_rows < 1) return fail("orl_diffusion_learn_epoch: bad arguments");
-  if (!on_device)
-    for (int64_t i = 0; i < n_rows; ++i)
-      if (order[i] < 0 || order[i] >= d->n_data) return fail("orl_diffusion_learn_epoch: row index out of range");
-  const long steps = (long)((n_rows + d->B - 1) / d->B);
-  if (d->kstep + steps > d->n_lr) return fail("orl_diffusion_learn_epoch: the epoch runs past the learning-rate table");
-  if (d->mem.grow(&d->idx_d, &d->idx_cap, (long)n_rows, d->stream)) return -1;
-  if (d->mem.grow(&d->loss_steps, &d->loss_cap, steps, d->stream)) return -1;
-  ORL_HIP(hipMemcpyAsync(d->idx_d, order, sizeof(int64_t) * n_rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
-  for (long s = 0; s < steps; ++s) {
-    const int rows = (int)std::min<int64_t>(d->B, n_rows - s * d->B);
-    if (diff_enqueue_step(d, d->idx_d + s * d->B, rows, nullptr, nullptr, d->loss_steps + s)) return -1;
-  }
-  ORL_HIP(hipStreamSynchronize(d->stream));
-  if (losses_out) ORL_HIP(hipMemcpy(losses_out, d->loss_steps, sizeof(float) * steps, hipMemcpyDeviceToHost));
-  return 0;
+  // (the epoch must stay inside the learning-rate table: refused before anything is queued)
+  if (order && n_rows >= 1 && d->kstep + (n_rows + d->B - 1) / d->B > d->n_lr)
+    return fail("orl_diffusion_learn_epoch: the epoch runs past the learning-rate table");
+  return learn_epoch_steps(d->stream, d->mem, &d->idx_d, &d->idx_cap, &d->loss_steps, &d->loss_cap, d->B, d->n_data, 1, "orl_diffusion_learn_epoch",
+                           order, n_rows, on_device, losses_out, [d](const long long* idx, int rows, float* loss_dst) {
+                             return diff_enqueue_step(d, idx, rows, nullptr, nullptr, loss_dst);
+                           });
 }
 
 int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const float* init_noise, const int64_t* noise_idx, int64_t noise_rows,
@@ -840,7 +776,7 @@ int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const fl
     return -1;
   DiffWs& w = d->sw;
   DevMat X; X.p = d->sX; X.pitch = X.lim = rup4(ad);
-  DEV_LAUNCH(d->stream, k_diff_copy, dim3(diff_ew_grid(n * ad)), dim3(256), 0, noise_d, ad, nidx_d, (long)noise_rows, X.p, X.pitch, (long)n, ad);
+  DEV_LAUNCH(d->stream, k_diff_copy, dim3(ew_grid(n * ad)), dim3(256), 0, noise_d, ad, nidx_d, (long)noise_rows, X.p, X.pitch, (long)n, ad);
   for (int t = N - 1; t >= 0; --t) {
     DiffInputP ip;
     memset(&ip, 0, sizeof(ip));
@@ -849,11 +785,11 @@ int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const fl
     ip.E0 = w.E0.p; ip.ep = w.E0.pitch; ip.GF = w.GF.p; ip.gp = w.GF.pitch;
     DEV_LAUNCH(d->stream, k_diff_input, dim3((unsigned)n), dim3(64), 0, ip);
     if (diff_forward(d, w, d->ema, (int)n, X)) return -1;
-    DEV_LAUNCH(d->stream, k_diff_ddpm, dim3(diff_ew_grid(n * ad)), dim3(256), 0, X.p, X.pitch, w.PRED.p, w.PRED.pitch, d->coef, t,
+    DEV_LAUNCH(d->stream, k_diff_ddpm, dim3(ew_grid(n * ad)), dim3(256), 0, X.p, X.pitch, w.PRED.p, w.PRED.pitch, d->coef, t,
                 z_d ? z_d + (long)t * n * ad : (const float*)nullptr, d->sZkeep, (long)n, ad, d->c.seed, d->sample_calls * (uint64_t)N + (uint64_t)t);
   }
   float* dst = stage_dst(act_out, d->sOut, on_device);
-  DEV_LAUNCH(d->stream, k_diff_copy, dim3(diff_ew_grid(n * ad)), dim3(256), 0, X.p, X.pitch, (const long long*)nullptr, 0L, dst, ad, (long)n, ad);
+  DEV_LAUNCH(d->stream, k_diff_copy, dim3(ew_grid(n * ad)), dim3(256), 0, X.p, X.pitch, (const long long*)nullptr, 0L, dst, ad, (long)n, ad);
   if (stage_out(d->stream, act_out, d->sOut, (size_t)n * ad, on_device)) return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
   d->sample_calls += 1;

@@ -8,7 +8,7 @@
 //                      by W_hh on the fp32 MFMA and applies the gates in the same step's epilogue.  Batch rows are independent, so no
 //                      workgroup ever waits for another one: __syncthreads() only, and the bounded loop over t.
 //   the tail           tiled GEMMs (E_BIAS_SWISH keeps the pre-activation) with k_rnn_ln_fwd between them: dropout, residual, LayerNorm
-//   k_rnn_loss         the masked MSE and its gradient, one block, fixed order
+//   k_mse_loss<true>   the masked MSE and its gradient, one block per run, fixed order (train_ops.h)
 //   the backward       the tail top down (k_rnn_ln_bwd folds the dropout mask and Swish' in), then per GRU layer ONE launch of
 //                      k_rnn_scan_bwd (t = T-1 .. 0, same ownership; carries dh_{t-1} = dh_t z + dGH_t W_hh in LDS) and three tiled
 //                      GEMMs over all rows: dW_hh / db_hh from dGH and the shifted h, dW_ih / db_ih, and the dX of the layer below
@@ -32,6 +32,7 @@
 #include "devobj.h"
 #include "reduce.h"
 #include "rng.h"
+#include "train_ops.h"
 
 namespace orl {
 
@@ -276,7 +277,7 @@ __global__ void k_rnn_gather(const float* __restrict__ inputs, const float* __re
   else MSK[row] = masks[g];
 }
 // dst [rows][cols] (pitch dp) = src (pitch sp); step > 1: source row = r * step + (step - 1), the last time step of sequence r.
-// Run blockIdx.y: src + run * s_rs, dst + run * d_rs
+// Run blockIdx.y: src + run * s_rs, dst + run * d_rs  (not merged with k_diff_copy: that one gathers through a row index)
 __global__ void k_rnn_copy(const float* __restrict__ src, int sp, long s_rs, float* __restrict__ dst, int dp, long d_rs, long rows, int cols,
                            int step) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -331,25 +332,6 @@ __device__ __forceinline__ void rnn_norm_run(RnnNormP& p, long run) {
   if (p.part) p.part += run * p.part_rs;
 }
 
-// LayerNorm statistics of one row in one wave (diffusion.hip's diff_group_stats with one group): mean, then the centred second moment
-__device__ __forceinline__ void rnn_row_stats(const float* u, int H, int lane, float (&v)[RNN_NJ], float& mean, float& rstd) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < RNN_NJ; ++j) {
-    const int c = lane + 64 * j;
-    v[j] = c < H ? u[c] : 0.f;
-    s += v[j];
-  }
-  mean = wave_sum(s) / (float)H;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < RNN_NJ; ++j) {
-    const float dlt = (lane + 64 * j) < H ? v[j] - mean : 0.f;
-    q += dlt * dlt;
-  }
-  rstd = 1.f / sqrtf(wave_sum(q) / (float)H + 1e-5f);
-}
-
 // u = res + mask s / (1 - p); out = LayerNorm(u) (eps 1e-5, affine); one wave per row
 __global__ __launch_bounds__(64) void k_rnn_ln_fwd(RnnNormP p) {
   const int row = blockIdx.x, lane = threadIdx.x;
@@ -366,7 +348,7 @@ __global__ __launch_bounds__(64) void k_rnn_ln_fwd(RnnNormP p) {
     }
   }
   float v[RNN_NJ], mean, rstd;
-  rnn_row_stats(p.u + (long)row * p.up, p.H, lane, v, mean, rstd);     // (a lane reads back what it wrote itself)
+  norm_stats(p.u + (long)row * p.up, p.H, lane, v, mean, rstd);     // (a lane reads back what it wrote itself)
 #pragma unroll
   for (int j = 0; j < RNN_NJ; ++j) {
     const int c = lane + 64 * j;
@@ -380,7 +362,7 @@ __global__ __launch_bounds__(64) void k_rnn_ln_bwd(RnnNormP p) {
   if (row >= p.rows) return;
   rnn_norm_run(p, blockIdx.y);
   float v[RNN_NJ], mean, rstd;
-  rnn_row_stats(p.u + (long)row * p.up, p.H, lane, v, mean, rstd);
+  norm_stats(p.u + (long)row * p.up, p.H, lane, v, mean, rstd);
   float dxh[RNN_NJ], xh[RNN_NJ];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -398,13 +380,12 @@ __global__ __launch_bounds__(64) void k_rnn_ln_bwd(RnnNormP p) {
       s2 += dxh[j] * xh[j];
     }
   }
-  s1 = wave_sum(s1) / (float)p.H;
-  s2 = wave_sum(s2) / (float)p.H;
+  const NormBwd nb(s1, s2, rstd, p.H);
 #pragma unroll
   for (int j = 0; j < RNN_NJ; ++j) {
     const int c = lane + 64 * j;
     if (c < p.H) {
-      const float du = rstd * (dxh[j] - s1 - xh[j] * s2);
+      const float du = nb.dx(dxh[j], xh[j]);
       if (p.du) p.du[(long)row * p.dup + c] = du;
       float ds = du;
       if (p.mask) ds = du * p.mask[(long)row * p.H + c] * p.scale;
@@ -425,6 +406,7 @@ __global__ void k_rnn_swish_bwd(const float* __restrict__ a, int ap, long a_rs, 
 }
 
 // first level: chunk sums of 64 rows each in row order, [chunks][pn]; run blockIdx.z
+// (not merged with diffusion.hip's k_diff_colsum, which adds all rows in one pass: the orders of summation differ and the tests pin both)
 __global__ void k_rnn_colsum_part(const float* __restrict__ part, long part_rs, long pn, long rows, float* __restrict__ chunk, long chunk_rs) {
   const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= pn) return;
@@ -447,30 +429,6 @@ __global__ void k_rnn_colsum_fin(const float* __restrict__ chunk, long chunk_rs,
   G[c2 < H ? dst.gamma[slot] + c2 : dst.beta[slot] + (c2 - H)] = s;
 }
 
-// loss = mean over rows of mask[row] mean_d (pred - target)^2; dPRED = 2 (pred - target) mask / (rows od); one block per run (pred and
-// dpred at stride p_rs, tgt / msk at tm_rs * od / tm_rs, the loss cells [run]), fixed order
-__global__ __launch_bounds__(256) void k_rnn_loss(const float* __restrict__ pred, int pp, long p_rs, const float* __restrict__ tgt,
-                                                  const float* __restrict__ msk, long tm_rs, long rows, int od, float* __restrict__ dpred,
-                                                  float* loss_out, float* loss_last) {
-  const long run = blockIdx.x;
-  pred += run * p_rs; dpred += run * p_rs; tgt += run * tm_rs * od; msk += run * tm_rs;
-  const long n = rows * od;
-  const float inv = 1.f / (float)n;
-  float s = 0.f;
-  for (long e = threadIdx.x; e < n; e += 256) {
-    const long r = e / od; const int d = (int)(e - r * od);
-    const float df = pred[r * pp + d] - tgt[e], m = msk[r];
-    s += df * df * m;
-    dpred[r * pp + d] = 2.f * df * m * inv;
-  }
-  s = block_sum256_pairwise(s);
-  if (threadIdx.x == 0) {
-    const float l = s * inv;
-    loss_out[run] = l;
-    loss_last[run] = l;
-  }
-}
-
 // G[i] = the slabs' sum in slab order: the k ranges of the split weight gradients (and slab 0's dgamma / dbeta)
 __global__ __launch_bounds__(256) void k_rnn_slab_sum(const float* __restrict__ slabs, long P, int n_slabs, float* __restrict__ G) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -486,11 +444,9 @@ __global__ __launch_bounds__(256) void k_rnn_adam(float* __restrict__ params, fl
                                                   long P, float step, float bc2s, float omb1, float b2, float omb2, float eps) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
-  const float g = G[i];
-  const float m = m_[i] + (g - m_[i]) * omb1;
-  const float v = v_[i] * b2 + omb2 * g * g;
+  float m = m_[i], v = v_[i];
+  params[i] = adam_update(params[i], m, v, G[i], step, bc2s, omb1, b2, omb2, eps);
   m_[i] = m; v_[i] = v;
-  params[i] = params[i] - step * (m / (sqrtf(v) / bc2s + eps));
 }
 
 }  // namespace orl
@@ -548,18 +504,11 @@ struct orl_rnn {
   DevAllocs mem{"orl_rnn"};
 };
 
-static int rnn_mat_runs(orl_rnn* d, DevMat& v, long rows, int cols, int runs) {
-  d->mem.free(v.p);
-  v.pitch = v.lim = rup4(cols);
-  v.s0 = rows * v.pitch;
-  return d->mem.alloc(&v.p, (size_t)runs * rows * v.pitch);
-}
-
 static int rnn_ws_stages(orl_rnn* d, RnnWs& w, bool keep);
 
 static int rnn_ws_alloc(orl_rnn* d, RnnWs& w, long rows, bool train, int runs) {
   const int H = d->H, L = d->L, nb = d->nb;
-  auto rnn_mat = [runs](orl_rnn* o, DevMat& v, long n, int cols) { return rnn_mat_runs(o, v, n, cols, runs); };
+  auto rnn_mat = [runs](orl_rnn* o, DevMat& v, long n, int cols) { return dev_mat(o->mem, v, n, cols, runs); };
   w.GI.resize(L); w.HO.resize(L); w.R.resize(L); w.Z.resize(L); w.NN.resize(L); w.HN.resize(L); w.HP.resize(L);
   w.SB.resize(nb); w.ZB.resize(nb); w.UB.resize(nb); w.XO.resize(nb);
   bool bad = rnn_mat(d, w.X0, rows, d->in) || rnn_mat(d, w.SI, rows, H) || rnn_mat(d, w.ZI, rows, H) || rnn_mat(d, w.UI, rows, H) ||
@@ -605,10 +554,10 @@ static int rnn_ws_stages(orl_rnn* d, RnnWs& w, bool keep) {
   w.keep = true;
   bool bad = false;
   for (int l = 0; l < L && !bad; ++l)
-    bad = rnn_mat_runs(d, w.dGIl[l], w.cap, 3 * H, w.runs) || rnn_mat_runs(d, w.dGHl[l], w.cap, 3 * H, w.runs) ||
-          rnn_mat_runs(d, w.dXLl[l], w.cap, H, w.runs);
-  for (int i = 0; i < nb && !bad; ++i) bad = rnn_mat_runs(d, w.DUb[i], w.cap, H, w.runs) || rnn_mat_runs(d, w.DTb[i], w.cap, H, w.runs);
-  for (int s = 0; s <= nb && !bad; ++s) bad = rnn_mat_runs(d, w.DZs[s], w.cap, H, w.runs);
+    bad = dev_mat(d->mem, w.dGIl[l], w.cap, 3 * H, w.runs) || dev_mat(d->mem, w.dGHl[l], w.cap, 3 * H, w.runs) ||
+          dev_mat(d->mem, w.dXLl[l], w.cap, H, w.runs);
+  for (int i = 0; i < nb && !bad; ++i) bad = dev_mat(d->mem, w.DUb[i], w.cap, H, w.runs) || dev_mat(d->mem, w.DTb[i], w.cap, H, w.runs);
+  for (int s = 0; s <= nb && !bad; ++s) bad = dev_mat(d->mem, w.DZs[s], w.cap, H, w.runs);
   if (bad) {
     rnn_ws_stages(d, w, false);
     return -1;
@@ -621,13 +570,6 @@ static int rnn_ws_stages(orl_rnn* d, RnnWs& w, bool keep) {
 // of every product are functions of the per-run shape only, so an output element's reduction order -- and run r's bits -- do not depend
 // on how many runs share the launch.
 struct RnnRuns { int r0, n; };
-// few rows: 16 x 64 tiles while they give at most four rounds of workgroups on the 256 CUs, 64 x 64 beyond; many rows: the 64 x 256 tile
-static int rnn_cfg(int M, int N) {
-  if (N <= 16) return CFG_TALL;
-  if (M >= 2048 && N >= 128) return CFG_BIG;
-  const long small_tiles = (long)((M + 15) / 16) * ((N + 63) / 64);
-  return (M <= 32 || small_tiles <= 1024) ? CFG_SMALL : CFG_MID;
-}
 // the weight gradients reduce over every row of the step and have few output tiles: the smallest tile that still gives the CUs work
 static int rnn_wgrad_cfg(int M, int N) {
   if (N <= 16) return CFG_TALL;
@@ -644,14 +586,14 @@ static int rnn_fwd(orl_rnn* d, const RnnRuns& rs, const DevMat& X, int M, const 
   GemmP p = linear_fwd_p(X, M, rnn_linear(d, rnn_params_of(d, rs), l, in, out), Y);
   p.z_out = Z;
   const bool kpad = X.pitch >= rup4(p.K);
-  const int cfg = rnn_cfg(p.M, p.N);
+  const int cfg = linear_cfg(p.M, p.N);
   return gemm_done(swish ? launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS_SWISH>(cfg, p, rs.n, d->stream, kpad, false, P_F32)
                          : launch_gemm<PA_PLAIN, PB_PLAIN, E_BIAS>(cfg, p, rs.n, d->stream, kpad, false, P_F32), "orl_rnn forward");
 }
 // dX = dY W
 static int rnn_dgrad(orl_rnn* d, const RnnRuns& rs, const DevMat& dY, int M, const RnnLin& l, int in, int out, const DevMat& dX) {
   const GemmP p = linear_dgrad_p(dY, M, rnn_linear(d, rnn_params_of(d, rs), l, in, out), dX);
-  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(rnn_cfg(p.M, p.N), p, rs.n, d->stream, dY.pitch >= rup4(p.K), false, P_F32), "orl_rnn dgrad");
+  return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_PLAIN>(linear_cfg(p.M, p.N), p, rs.n, d->stream, dY.pitch >= rup4(p.K), false, P_F32), "orl_rnn dgrad");
 }
 // The weight gradients reduce over all rows * T rows of a step and have few output tiles (600 x 200 at the default shape), so the
 // reduction is cut into k ranges of at least 256 rows, each into a slab of its own; k_rnn_slab_sum adds the slabs in order.
@@ -663,7 +605,6 @@ static int rnn_wgrad(orl_rnn* d, const DevMat& dY, const DevMat& X, int M, const
   return gemm_done(launch_gemm<PA_PLAIN, PB_PLAIN, E_WGRAD>(rnn_wgrad_cfg(p.M, p.N), p, d->R, d->stream, false, false, P_F32), "orl_rnn wgrad");
 }
 
-static int rnn_ew_grid(long n) { return (int)((n + 255) / 256); }
 // the profile's event `i` on the stream when the step is being timed
 static void rnn_mark(orl_rnn* d, bool on, int i) {
   if (on && d->prof) hipEventRecord(d->ev[i], d->stream);
@@ -752,7 +693,7 @@ static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
     if (rnn_wgrad(d, DZ, Xin, (int)N, d->lin_b[i], H, H) || rnn_dgrad(d, rs, DZ, (int)N, d->lin_b[i], H, H, w.DTb[i])) return -1;
   }
   const DevMat &DU0 = w.DUb[0], &DT0 = w.DTb[0];
-  DEV_LAUNCH(d->stream, k_rnn_swish_bwd, dim3(rnn_ew_grid(N * H), R), dim3(256), 0, DU0.p, DU0.pitch, DU0.s0, DT0.p, DT0.pitch, DT0.s0,
+  DEV_LAUNCH(d->stream, k_rnn_swish_bwd, dim3(ew_grid(N * H), R), dim3(256), 0, DU0.p, DU0.pitch, DU0.s0, DT0.p, DT0.pitch, DT0.s0,
               w.ZM.p, w.ZM.pitch, w.ZM.s0, w.dZM.p, w.dZM.pitch, w.dZM.s0, N, H);
   if (rnn_wgrad(d, w.dZM, w.CAT, (int)N, d->lin_merge, 2 * H, H) || rnn_dgrad(d, rs, w.dZM, (int)N, d->lin_merge, 2 * H, H, w.dCAT)) return -1;
   // the input block (no residual, no gradient to the net's input)
@@ -772,8 +713,8 @@ static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
     memset(&dst, 0, sizeof(dst));
     dst.gamma[0] = d->norm_in.g; dst.beta[0] = d->norm_in.b;
     for (int i = 0; i < d->nb; ++i) { dst.gamma[1 + i] = d->norm_b[i].g; dst.beta[1 + i] = d->norm_b[i].b; }
-    DEV_LAUNCH(d->stream, k_rnn_colsum_part, dim3(rnn_ew_grid(pn), chunks, R), dim3(256), 0, w.part, w.part_rs, pn, N, w.chunk, w.chunk_rs);
-    DEV_LAUNCH(d->stream, k_rnn_colsum_fin, dim3(rnn_ew_grid(pn), R), dim3(256), 0, w.chunk, w.chunk_rs, pn, chunks, H, dst, d->slabs, d->P);
+    DEV_LAUNCH(d->stream, k_rnn_colsum_part, dim3(ew_grid(pn), chunks, R), dim3(256), 0, w.part, w.part_rs, pn, N, w.chunk, w.chunk_rs);
+    DEV_LAUNCH(d->stream, k_rnn_colsum_fin, dim3(ew_grid(pn), R), dim3(256), 0, w.chunk, w.chunk_rs, pn, chunks, H, dst, d->slabs, d->P);
   }
   // the GRU layers top down: the top layer's dh is the right half of the merge layer's input gradient
   DevMat dOut = w.dCAT.cols(H);
@@ -796,7 +737,7 @@ static int rnn_backward(orl_rnn* d, RnnWs& w, int rows, int T) {
     dOut = w.dXLl[l];
   }
   const long RP = (long)R * d->P;
-  DEV_LAUNCH(d->stream, k_rnn_slab_sum, dim3(rnn_ew_grid(RP)), dim3(256), 0, (const float*)d->slabs, RP, rnn_slabs(d, N), d->grads);
+  DEV_LAUNCH(d->stream, k_rnn_slab_sum, dim3(ew_grid(RP)), dim3(256), 0, (const float*)d->slabs, RP, rnn_slabs(d, N), d->grads);
   return 0;
 }
 
@@ -807,21 +748,21 @@ static int rnn_enqueue_step(orl_rnn* d, const long long* idx, long idx_rs, int r
   const int T = d->T, H = d->H, R = d->R;
   const long N = (long)rows * T, RP = (long)R * d->P;
   rnn_mark(d, true, 0);
-  DEV_LAUNCH(d->stream, k_rnn_gather, dim3(rnn_ew_grid(N * (d->in + d->od + 1)), R), dim3(256), 0, d->d_in, d->d_tgt, d->d_msk, idx, idx_rs,
+  DEV_LAUNCH(d->stream, k_rnn_gather, dim3(ew_grid(N * (d->in + d->od + 1)), R), dim3(256), 0, d->d_in, d->d_tgt, d->d_msk, idx, idx_rs,
               d->n_data, T, d->in, d->od, rows, w.X0.p, w.X0.pitch, w.X0.s0, d->TGT, d->MSK, w.cap);
   if (d->c.dropout_rate > 0.f && !forced_masks)
     for (int s = 0; s < d->norms; ++s)
-      DEV_LAUNCH(d->stream, k_rnn_mask, dim3(rnn_ew_grid(N * (H / 4)), R), dim3(256), 0, w.MK + (size_t)s * w.cap * H, w.mk_rs, N, H,
+      DEV_LAUNCH(d->stream, k_rnn_mask, dim3(ew_grid(N * (H / 4)), R), dim3(256), 0, w.MK + (size_t)s * w.cap * H, w.mk_rs, N, H,
                   1.f - d->c.dropout_rate, d->c.seed, (uint64_t)d->kstep, (uint32_t)s);
   if (rnn_forward(d, RnnRuns{0, R}, w, rows, T, true, false)) return -1;
   rnn_mark(d, true, 1);
-  DEV_LAUNCH(d->stream, k_rnn_loss, dim3(R), dim3(256), 0, w.PRED.p, w.PRED.pitch, w.PRED.s0, d->TGT, d->MSK, w.cap, N, d->od, w.dPRED.p, loss_dst,
-              d->loss_cell);
+  DEV_LAUNCH(d->stream, k_mse_loss<true>, dim3(R), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, (const float*)d->TGT,
+              (const float*)d->MSK, w.cap, N, d->od, w.dPRED.p, loss_dst, d->loss_cell);
   if (rnn_backward(d, w, rows, T)) return -1;
   rnn_mark(d, true, 2);
   const double tt = (double)(d->kstep + 1);
   const double bc1 = 1.0 - std::pow(d->c.adam_beta1, tt), bc2 = 1.0 - std::pow(d->c.adam_beta2, tt);
-  DEV_LAUNCH(d->stream, k_rnn_adam, dim3(rnn_ew_grid(RP)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, RP, (float)(d->c.lr / bc1),
+  DEV_LAUNCH(d->stream, k_rnn_adam, dim3(ew_grid(RP)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, RP, (float)(d->c.lr / bc1),
               (float)std::sqrt(bc2), (float)(1.0 - d->c.adam_beta1), (float)d->c.adam_beta2, (float)(1.0 - d->c.adam_beta2), (float)d->c.adam_eps);
   rnn_mark(d, true, 3);
   d->prof_valid = d->prof;
@@ -1058,23 +999,10 @@ int orl_rnn_step_runs(orl_rnn* d, const int64_t* idx, int32_t rows, const float*
 
 // orl_rnn_learn_epoch / orl_rnn_learn_epoch_runs: orders [R][n_rows], losses_out [steps][R]
 static int rnn_learn_epoch_runs(orl_rnn* d, const char* what, const int64_t* orders, int64_t n_rows, int on_device, float* losses_out) {
-  const std::string w(what);
-  const int R = d->R;
-  if (!orders || n_rows < 1) return fail(w + ": bad arguments");
-  if (!on_device)
-    for (int64_t i = 0; i < R * n_rows; ++i)
-      if (orders[i] < 0 || orders[i] >= d->n_data) return fail(w + ": row index out of range");
-  const long steps = (long)((n_rows + d->B - 1) / d->B);
-  if (d->mem.grow(&d->idx_d, &d->idx_cap, (long)R * std::max<long>((long)n_rows, d->B), d->stream)) return -1;
-  if (d->mem.grow(&d->loss_steps, &d->loss_cap, steps * R, d->stream)) return -1;
-  ORL_HIP(hipMemcpyAsync(d->idx_d, orders, sizeof(int64_t) * R * n_rows, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
-  for (long s = 0; s < steps; ++s) {
-    const int rows = (int)std::min<int64_t>(d->B, n_rows - s * d->B);
-    if (rnn_enqueue_step(d, d->idx_d + s * d->B, (long)n_rows, rows, false, d->loss_steps + s * R)) return -1;
-  }
-  ORL_HIP(hipStreamSynchronize(d->stream));
-  if (losses_out) ORL_HIP(hipMemcpy(losses_out, d->loss_steps, sizeof(float) * steps * R, hipMemcpyDeviceToHost));
-  return 0;
+  return learn_epoch_steps(d->stream, d->mem, &d->idx_d, &d->idx_cap, &d->loss_steps, &d->loss_cap, d->B, d->n_data, d->R, what, orders, n_rows,
+                           on_device, losses_out, [d, n_rows](const long long* idx, int rows, float* loss_dst) {
+                             return rnn_enqueue_step(d, idx, (long)n_rows, rows, false, loss_dst);
+                           });
 }
 int orl_rnn_learn_epoch(orl_rnn* d, const int64_t* order, int64_t n_rows, int on_device, float* losses_out) {
   if (rnn_ready(d, "orl_rnn_learn_epoch", true) || rnn_one_run_only(d, "orl_rnn_learn_epoch", "orl_rnn_learn_epoch_runs")) return -1;
@@ -1111,15 +1039,15 @@ static int rnn_forward_runs(orl_rnn* d, const char* what, const float* inputs, i
   RnnWs& w = d->ew;
   const float* in_d = inputs;
   if (stage_in(d->stream, in_d, d->fIn, (size_t)n_in * N * d->in, on_device)) return -1;
-  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid(N * d->in), n_in), dim3(256), 0, in_d, d->in, N * d->in, w.X0.p, w.X0.pitch, w.X0.s0, N, d->in, 1);
+  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid(N * d->in), n_in), dim3(256), 0, in_d, d->in, N * d->in, w.X0.p, w.X0.pitch, w.X0.s0, N, d->in, 1);
   if (rnn_forward(d, rs, w, (int)n, T, false, n_in < rs.n)) return -1;
   float* last = stage_dst(out_last, d->fLast, on_device);
-  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid((long)n * d->od), rs.n), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, last, d->od,
+  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid((long)n * d->od), rs.n), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, last, d->od,
               (long)n * d->od, (long)n, d->od, (int)T);
   if (stage_out(d->stream, out_last, d->fLast, (size_t)rs.n * n * d->od, on_device)) return -1;
   if (out_all) {
     float* all = stage_dst(out_all, d->fAll, on_device);
-    DEV_LAUNCH(d->stream, k_rnn_copy, dim3(rnn_ew_grid(N * d->od), rs.n), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, all, d->od,
+    DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid(N * d->od), rs.n), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, all, d->od,
                 N * d->od, N, d->od, 1);
     if (stage_out(d->stream, out_all, d->fAll, (size_t)rs.n * N * d->od, on_device)) return -1;
   }

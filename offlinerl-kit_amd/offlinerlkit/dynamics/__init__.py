@@ -40,6 +40,39 @@ class BaseDynamics(object):
     def step(self, obs: np.ndarray, action: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Dict]:
         raise NotImplementedError
 
+    # ---- what the engine-backed models share.  They keep ``_eng`` (the engine object), ``_arena`` (the torch tensor its parameter
+    # blocks live in), ``_shape`` (what the engine was built for) and ``scaler``, and provide ``_drain()``: wait for the engine's
+    # work on the arena ----
+    def _device(self) -> torch.device:
+        dev = self.model.device
+        if dev.type != "cuda":
+            if not torch.cuda.is_available():
+                raise RuntimeError("the dynamics ensemble runs on the HIP engine: no HIP device (MI355X) visible")
+            dev = torch.device("cuda", 0)
+        return torch.device("cuda", dev.index or 0)
+
+    def _alias_params(self, base: int, tensors) -> None:
+        """point the module's parameters at the block ``base`` floats into the arena, laid out by ``tensors``"""
+        params = dict(self.model.named_parameters())
+        for name, off, shape in tensors:
+            params[name].data = self._arena[base + off: base + off + int(np.prod(shape))].view(shape)
+
+    def _unbind(self) -> None:
+        if self._eng is None:
+            return
+        self._drain()
+        for p in self.model.parameters():
+            p.data = p.data.clone()
+        self._eng.close()
+        self._eng, self._arena, self._shape = None, None, None
+
+    def save(self, save_path: str) -> None:
+        if self._eng is not None:
+            self._drain()
+        sd = self.model.state_dict()
+        torch.save(type(sd)((k, v.detach().clone()) for k, v in sd.items()), os.path.join(save_path, "dynamics.pth"))
+        self.scaler.save_scaler(save_path)
+
 
 def _fresh_model_params(model, seed: int) -> Dict[str, torch.Tensor]:
     """the constructor's initialisation under torch seed ``seed`` (runs r > 0 of a multi-run ensemble)"""
@@ -78,14 +111,6 @@ class EnsembleDynamics(BaseDynamics):
         self._n_runs = int(n_runs)
         self._seed = int(seed) if seed is not None else 0
         self.scalers = [self.scaler] + [StandardScaler(self.scaler.mu, self.scaler.std) for _ in range(self._n_runs - 1)]
-
-    def _device(self) -> torch.device:
-        dev = self.model.device
-        if dev.type != "cuda":
-            if not torch.cuda.is_available():
-                raise RuntimeError("the dynamics ensemble runs on the HIP engine: no HIP device (MI355X) visible")
-            dev = torch.device("cuda", 0)
-        return torch.device("cuda", dev.index or 0)
 
     def _bind(self, batch_size: int = 256, logvar_loss_coef: float = 0.01) -> None:
         shape = (int(batch_size), float(logvar_loss_coef))
@@ -132,20 +157,8 @@ class EnsembleDynamics(BaseDynamics):
         self.select_run(0)
         self._data_key = None
 
-    def _unbind(self) -> None:
-        if self._eng is None:
-            return
+    def _drain(self) -> None:
         self._eng.sync()
-        for p in self.model.parameters():
-            p.data = p.data.clone()
-        self._eng.close()
-        self._eng, self._arena, self._shape = None, None, None
-
-    def _views(self, run: int):
-        off0 = (self._eng.ptr(run) - self._arena.data_ptr()) // 4
-        for name, off, shape in self._eng.tensors:
-            n = int(np.prod(shape))
-            yield name, self._arena[off0 + off: off0 + off + n].view(shape)
 
     def select_run(self, run: int) -> None:
         """point the torch module (forward, state_dict, save) and ``self.scaler`` at run ``run``"""
@@ -155,9 +168,7 @@ class EnsembleDynamics(BaseDynamics):
             return
         if run == self._cur_run:
             return
-        params = dict(self.model.named_parameters())
-        for name, view in self._views(run):
-            params[name].data = view
+        self._alias_params((self._eng.ptr(run) - self._arena.data_ptr()) // 4, self._eng.tensors)
         self.model.set_elites([int(i) for i in self._eng.get_elites(run)])
         self.scaler = self.scalers[run]
         self._cur_run = run
@@ -507,13 +518,6 @@ class EnsembleDynamics(BaseDynamics):
         pairs = sorted(pairs, key=lambda x: x[0])
         return [pairs[i][1] for i in range(self.model.num_elites)]
 
-    def save(self, save_path: str) -> None:
-        if self._eng is not None:
-            self._eng.sync()
-        sd = self.model.state_dict()
-        torch.save(type(sd)((k, v.detach().clone()) for k, v in sd.items()), os.path.join(save_path, "dynamics.pth"))
-        self.scaler.save_scaler(save_path)
-
     def load(self, load_path: str) -> None:
         if self._eng is not None:
             self._sync_torch()
@@ -603,9 +607,6 @@ class RNNDynamics(BaseDynamics):
         self._seed = int(seed) if seed is not None else 0
         self._gens = None
 
-    def _device(self) -> torch.device:
-        return EnsembleDynamics._device(self)
-
     def _bind(self, rows: int, steps: int, exact: bool = False) -> None:
         """an engine for steps of up to ``rows`` sequences (``exact``: batch_size == rows, as learn_epoch cuts an epoch into
         batch_size rows) of up to ``steps`` time steps; an engine that is too small is rebuilt and its state (every run's three
@@ -656,20 +657,11 @@ class RNNDynamics(BaseDynamics):
         if run == self._cur_run:
             return
         torch.cuda.synchronize(self._arena.device)
-        base = int(run) * self._eng.floats
-        params = dict(self.model.named_parameters())
-        for name, off, tshape in self._eng.tensors():
-            params[name].data = self._arena[base + off: base + off + int(np.prod(tshape))].view(tshape)
+        self._alias_params(int(run) * self._eng.floats, self._eng.tensors())
         self._cur_run = int(run)
 
-    def _unbind(self) -> None:
-        if self._eng is None:
-            return
+    def _drain(self) -> None:
         torch.cuda.synchronize(self._arena.device)
-        for p in self.model.parameters():
-            p.data = p.data.clone()
-        self._eng.close()
-        self._eng, self._arena, self._shape = None, None, None
 
     @staticmethod
     def _host(x) -> np.ndarray:
@@ -755,13 +747,6 @@ class RNNDynamics(BaseDynamics):
                 sd = type(self.model.state_dict())((k, torch.from_numpy(params[k].copy())) for k in names)
                 torch.save(sd, os.path.join(logger.model_dir, f"dynamics_run{r}.pth"))
         self.model.eval()
-
-    def save(self, save_path: str) -> None:
-        if self._eng is not None:
-            torch.cuda.synchronize(self._arena.device)
-        sd = self.model.state_dict()
-        torch.save(type(sd)((k, v.detach().clone()) for k, v in sd.items()), os.path.join(save_path, "dynamics.pth"))
-        self.scaler.save_scaler(save_path)
 
     def load(self, load_path: str) -> None:
         self.model.load_state_dict(torch.load(os.path.join(load_path, "dynamics.pth"), map_location=self.model.device))
