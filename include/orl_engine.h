@@ -845,6 +845,38 @@ int orl_rnn_debug_keep(orl_rnn* d, int on);
  * scans of all layers, [3] the loss and the backward, [4] the backward scans of all layers, [5] Adam. */
 int orl_rnn_profile(orl_rnn* d, int enable);
 int orl_rnn_profile_read(orl_rnn* d, float ms[6]);
+/* -- carried GRU state: one model step at a time (what a rollout needs) ----------------------------------------------------------
+ * The object keeps the h of every GRU layer of n_traj trajectories in HBM, [n_runs][L][n_traj][H]: trajectory j in slot j.  A step of
+ * n rows reads the h of each row's trajectory, applies ONE GRU step per layer (k_rnn_cell: the input projection, the recurrent
+ * product and the gates in one launch per layer), writes the new h back to the slot, and runs the tail of the window forward on the
+ * n rows: O(1) work per model step at any horizon, no history on the host.  In exact arithmetic k steps from a zero state equal the
+ * window forward over the k inputs; in fp32 the two differ by rounding (other products, other orders).  The state is kept twice, with
+ * a side bit per (run, slot) that names the buffer holding the slot's h: a step reads that buffer and writes the other one (the
+ * workgroups of a row each read the whole previous row while their neighbours write parts of the new one), and its last launch flips
+ * the bits of the slots it stepped.  A slot that a step does not name keeps its bits, so any subset may be stepped at any time.
+ * No atomics: identical call sequences give identical bits, and run r's bits do not depend on n_runs.
+ *
+ * orl_rnn_set_scaler: the input scaler (StandardScaler's mu and std, input_dim host floats each, shared by the runs).
+ * orl_rnn_state_reset: (re)allocates the state for n_traj trajectories and zeroes it, in every run.
+ * orl_rnn_state_prime: starts slots 0 .. n - 1 of every run from a history: the eval forward over the ALREADY SCALED windows inputs
+ *   [n][T][input_dim] (shared_inputs != 0) or [n_runs][n][T][input_dim], then each layer's h of the last time step into the slots.
+ *   n <= n_traj; the other slots are untouched.  Device pointer when on_device.
+ * orl_rnn_state_step: one model step of n <= n_traj rows.  obs [n][obs_dim], act [n][act_dim] (unscaled: the step applies the scaler),
+ *   obs_dim = output_dim - 1 (the model predicts [delta obs | reward]) and act_dim = input_dim - obs_dim, refused when < 1.  index
+ *   [n] int64: the trajectory of row i, NULL: 0 .. n - 1; the indices must be distinct and < n_traj (host indices are checked, device
+ *   ones are clamped into the state by the kernels and are the caller's to keep distinct).  run >= 0: that run alone; run == -1: every
+ *   run, obs / act / next_obs / reward with a leading n_runs and the index shared.  next_obs [n][obs_dim] = pred[:, :-1] + obs, reward
+ *   [n] = pred[:, -1].  All pointers are device pointers when on_device, host pointers otherwise.  Synchronous.
+ * orl_rnn_state_set: plants layer `layer` of run `run`, host [n_traj][H] (tests).
+ * Taps (orl_rnn_debug_read_run): "state.<l>" [n_traj][H], the carried h of layer l; after a state step "roll.x" [n][input_dim] (the
+ * scaled inputs), "roll.h.<l>" [n][H] (the new h in row order), "roll.pred" [n][output_dim], and the tail's names above with n rows
+ * ("gi.<l>" is refused: the one-step path keeps no input projections). */
+int orl_rnn_set_scaler(orl_rnn* d, const float* mu, const float* std, int64_t n);
+int orl_rnn_state_reset(orl_rnn* d, int64_t n_traj);
+int orl_rnn_state_prime(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, int shared_inputs);
+int orl_rnn_state_step(orl_rnn* d, const float* obs, const float* act, const int64_t* index, int64_t n, int on_device, int run, float* next_obs,
+                       float* reward);
+int orl_rnn_state_set(orl_rnn* d, int run, int layer, const float* host, int64_t n_traj);
 
 #ifdef __cplusplus
 }

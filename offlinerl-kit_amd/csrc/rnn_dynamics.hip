@@ -21,6 +21,14 @@
 // slabs are [R][P] per block, every workspace matrix is [R][cap rows][pitch], the data set is one and each run gathers its own rows.
 // The scans and the row kernels add blockIdx.y * stride to their base pointers, the matrix products take the runs as launch_gemm's
 // batch.  Tile configurations and slab counts are functions of the per-run shape, so run r's bits do not depend on R.
+//
+// Rollouts (orl_rnn_state_*): the h of every GRU layer of n_traj trajectories stays in HBM, and one model step of n rows is
+//   k_rnn_roll_in      x = ([obs | act] - mu) / std
+//   per GRU layer      ONE launch of k_rnn_cell: gathers h_prev of each row's trajectory, W_ih x and W_hh h on the fp32 MFMA, the gates,
+//                      the new h to the trajectory's slot and to the layer's output rows; a workgroup owns 16 rows x 16 units
+//   the tail           the window forward's own (rnn_tail), on n rows
+//   k_rnn_roll_head    next_obs = pred[:, :-1] + obs, reward = pred[:, -1]
+// O(1) per model step at any horizon; no atomics here either.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -449,6 +457,141 @@ __global__ __launch_bounds__(256) void k_rnn_adam(float* __restrict__ params, fl
   m_[i] = m; v_[i] = v;
 }
 
+// ---- the carried state: one model step of n rows (orl_rnn_state_step) ----
+// Every trajectory has a slot in the state [R][L][n_traj][H], kept twice (st[0], st[1]) with a side bit per (run, slot): a step reads a
+// slot's h from the buffer its bit names and writes the new h to the other one, and the step's last launch flips the bits of the slots
+// it stepped.  The unit tiles of a row are spread over workgroups, each of which reads the WHOLE previous row as its k operand, so the
+// new row must not land where a neighbour still reads; a slot no step names keeps its buffer, its bit and its bits.
+// The trajectory of row i: idx[i] clamped into the state, or i
+__device__ __forceinline__ long rnn_traj_of(const long long* idx, long i, long n_traj) {
+  return idx ? min(max((long)idx[i], 0L), n_traj - 1) : i;
+}
+
+// x [n][in] = ([obs | act] - mu) / std: StandardScaler.transform's two fp32 operations (a subtraction and a division, nothing to fuse).
+// Run blockIdx.y: its own obs / act ([n][od], [n][ad]; strides o_rs, a_rs, 0: shared) and its own x; the scaler is shared
+__global__ void k_rnn_roll_in(const float* __restrict__ obs, long o_rs, const float* __restrict__ act, long a_rs, int od, int ad,
+                              const float* __restrict__ mu, const float* __restrict__ sd, long n, float* __restrict__ X, int xp, long x_rs) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int in = od + ad;
+  if (e >= n * in) return;
+  const long run = blockIdx.y;
+  const long i = e / in; const int c = (int)(e - i * in);
+  const float v = c < od ? obs[run * o_rs + i * od + c] : act[run * a_rs + i * ad + (c - od)];
+  X[run * x_rs + i * xp + c] = (v - mu[c]) / sd[c];
+}
+
+struct RnnCellP {
+  int n, H, K;                       // rows of the step, hidden units, the layer's input width
+  const float* x; int xp; long x_rs; // [n][K], pitch xp >= 4 ceil(K / 4) with zero pads: the step's scaled inputs or the h of the layer below
+  const float *wih, *whh, *bih, *bhh; long par_rs;     // [3H][K], [3H][H], [3H], [3H]
+  const long long* idx;              // [n]: the trajectory of row i, or null (= i); shared by the runs
+  float* st[2]; long st_rs;          // this layer's [n_traj][H] in both buffers
+  const int* side; long n_traj;      // [R][n_traj]: the buffer that holds each slot's h
+  float* ho; int hop; long ho_rs;    // [n][H]: the new h in row order
+};
+
+// torch.nn.GRU's cell on one workgroup of one wave: 16 rows x 16 hidden units, grid (row tiles, unit tiles, runs).  Lane
+// (i = l & 15, q = l >> 4) carries k = 16 kb + 4 q + s of input row i (x, then the gathered h) and of the three weight rows of unit i,
+// as the scan does.  The x and h products of r and of z share an accumulator (first every k of x, then every k of h: one fixed order
+// per element); n keeps W_in x and W_hn h apart.  A row past n repeats row n - 1 and its results are dropped, so an element's value
+// does not depend on its tile's other rows.  Layer 0's W_ih rows are K floats long, no multiple of 4: those are loaded one by one
+__global__ __launch_bounds__(64) void k_rnn_cell(RnnCellP p) {
+  const int H = p.H, K = p.K;
+  const int lane = threadIdx.x, li = lane & 15, lq = lane >> 4;
+  const int b0 = blockIdx.x * RNN_RB;
+  const int nrow = min((int)RNN_RB, p.n - b0);
+  {
+    const long run = blockIdx.z;
+    p.x += run * p.x_rs; p.wih += run * p.par_rs; p.whh += run * p.par_rs; p.bih += run * p.par_rs; p.bhh += run * p.par_rs;
+    p.st[0] += run * p.st_rs; p.st[1] += run * p.st_rs; p.side += run * p.n_traj; p.ho += run * p.ho_rs;
+  }
+  const int j = blockIdx.y * 16 + li;
+  const int jc = min(j, H - 1);                         // a clamped unit is computed and dropped
+  const long ra = b0 + min(li, nrow - 1);
+  const long ta = rnn_traj_of(p.idx, ra, p.n_traj);
+  const float* xrow = p.x + ra * p.xp;
+  const float* hrow = p.st[p.side[ta] & 1] + ta * H;
+  f32x4 ar = {0.f, 0.f, 0.f, 0.f}, az = ar, anx = ar, anh = ar;
+  {
+    const float* wr = p.wih + (long)jc * K;
+    const float* wz = p.wih + (long)(H + jc) * K;
+    const float* wn = p.wih + (long)(2 * H + jc) * K;
+    const bool quads = (K & 3) == 0;
+    for (int k4 = 4 * lq; k4 < ((K + 15) & ~15); k4 += 16) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f}, vr = a, vz = a, vn = a;
+      if (k4 < K) {
+        a = *(const f32x4*)(xrow + k4);                 // (inside the pitch; the pads are zero)
+        if (quads) {
+          vr = *(const f32x4*)(wr + k4); vz = *(const f32x4*)(wz + k4); vn = *(const f32x4*)(wn + k4);
+        } else {
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+            if (k4 + s < K) { vr[s] = wr[k4 + s]; vz[s] = wz[k4 + s]; vn[s] = wn[k4 + s]; }
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        ar = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], vr[s], ar, 0, 0, 0);      // D[row 4 q + r][unit i]
+        az = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], vz[s], az, 0, 0, 0);
+        anx = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], vn[s], anx, 0, 0, 0);
+      }
+    }
+  }
+  {
+    const float* wr = p.whh + (long)jc * H;
+    const float* wz = p.whh + (long)(H + jc) * H;
+    const float* wn = p.whh + (long)(2 * H + jc) * H;
+    for (int k4 = 4 * lq; k4 < ((H + 15) & ~15); k4 += 16) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f}, vr = a, vz = a, vn = a;
+      if (k4 < H) {                                     // (H is a multiple of 4: a quad is inside or outside)
+        a = *(const f32x4*)(hrow + k4);
+        vr = *(const f32x4*)(wr + k4); vz = *(const f32x4*)(wz + k4); vn = *(const f32x4*)(wn + k4);
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        ar = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], vr[s], ar, 0, 0, 0);
+        az = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], vz[s], az, 0, 0, 0);
+        anh = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], vn[s], anh, 0, 0, 0);
+      }
+    }
+  }
+  if (j >= H) return;
+  const float bir = p.bih[j], biz = p.bih[H + j], bin = p.bih[2 * H + j];
+  const float bhr = p.bhh[j], bhz = p.bhh[H + j], bhn = p.bhh[2 * H + j];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = 4 * lq + r;
+    if (b < nrow) {
+      const long t = rnn_traj_of(p.idx, b0 + b, p.n_traj);
+      const int sd = p.side[t] & 1;
+      const float hprev = p.st[sd][t * H + j];
+      const float rg = rnn_sigmoid((ar[r] + bir) + bhr);
+      const float zg = rnn_sigmoid((az[r] + biz) + bhz);
+      const float ng = tanhf((anx[r] + bin) + rg * (anh[r] + bhn));
+      const float hv = (1.f - zg) * ng + zg * hprev;
+      p.st[sd ^ 1][t * H + j] = hv;
+      p.ho[(long)(b0 + b) * p.hop + j] = hv;
+    }
+  }
+}
+
+// next_obs [n][od - 1] = pred[:, :-1] + obs, reward [n] = pred[:, -1] (plain fp32), and the side bits of the stepped slots flipped: the
+// step's last launch, after every layer has read them.  Run blockIdx.y
+__global__ void k_rnn_roll_head(const float* __restrict__ pred, int pp, long p_rs, const float* __restrict__ obs, long o_rs, int od, long n,
+                                float* __restrict__ next_obs, float* __restrict__ reward, const long long* __restrict__ idx, int* __restrict__ side,
+                                long n_traj) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * od) return;
+  const long run = blockIdx.y;
+  const long i = e / od; const int c = (int)(e - i * od);
+  const float v = pred[run * p_rs + i * pp + c];
+  if (c < od - 1) next_obs[(run * n + i) * (od - 1) + c] = v + obs[run * o_rs + i * (od - 1) + c];
+  else {
+    reward[run * n + i] = v;
+    side[run * n_traj + rnn_traj_of(idx, i, n_traj)] ^= 1;
+  }
+}
+
 }  // namespace orl
 
 using namespace orl;
@@ -495,8 +638,15 @@ struct orl_rnn {
   long long* idx_d = nullptr; long idx_cap = 0;
   // forward staging
   float *fIn = nullptr, *fLast = nullptr, *fAll = nullptr; long f_cap = 0; int f_runs = 0;
-  // what the taps read: the workspace of the last pass, its rows, and the runs it held (run last_r0 + i at workspace slot i)
-  const RnnWs* last_ws = nullptr; long last_rows = 0; int last_r0 = 0, last_nr = 0;
+  // what the taps read: the workspace of the last pass, its rows, and the runs it held (run last_r0 + i at workspace slot i); last_roll:
+  // that pass was a state step (no input projections kept, the roll.* names readable)
+  const RnnWs* last_ws = nullptr; long last_rows = 0; int last_r0 = 0, last_nr = 0; bool last_roll = false;
+  // the carried state (orl_rnn_state_*): st[0], st[1] [R][L][n_traj][H], side [R][n_traj] (k_rnn_cell says how they take turns); the
+  // input scaler [in] each; a step's host arrays staged as obs | act | next_obs | reward, and its trajectory indices
+  float* st[2] = {nullptr, nullptr}; int* side = nullptr; long n_traj = 0;
+  float *sc_mu = nullptr, *sc_std = nullptr; bool has_scaler = false;
+  float* r_stage = nullptr; long r_stage_cap = 0;
+  long long* r_idx = nullptr; long r_idx_cap = 0;
   // orl_rnn_profile: events of the last step -- 0 start, 1 after the forward, 2 after the backward, 3 after Adam, then per layer
   // [before, after] of the forward scan and of the backward scan
   bool prof = false, prof_valid = false;
@@ -622,15 +772,12 @@ static RnnNormP rnn_norm_params(orl_rnn* d, const RnnRuns& rs, const RnnWs& w, i
   return p;
 }
 
-// the forward of the runs rs over `rows` sequences of T steps of workspace w (X0 in place; shared_x: every run reads slot 0's X0); train:
-// the scans save what the backward reads, the pre-activations are kept and the dropouts read the keep masks of w.MK
-static int rnn_forward(orl_rnn* d, const RnnRuns& rs, RnnWs& w, int rows, int T, bool train, bool shared_x) {
+// the GRU layers of the runs rs over `rows` sequences of T steps from h = 0: per layer the input projections of every step in one
+// product, then the scan.  X0: the input rows; layer l's h_t goes to w.HO[l]
+static int rnn_gru_windows(orl_rnn* d, const RnnRuns& rs, RnnWs& w, const DevMat& X0, int rows, int T, bool train) {
   const int H = d->H;
   const long N = (long)rows * T;
-  const bool drop = train && d->c.dropout_rate > 0.f;
   float* params = rnn_params_of(d, rs);
-  DevMat X0 = w.X0;
-  if (shared_x) X0.s0 = 0;
   DevMat X = X0;
   for (int l = 0; l < d->L; ++l) {
     if (rnn_fwd(d, rs, X, (int)N, d->wih[l], l ? H : d->in, 3 * H, w.GI[l], false, nullptr)) return -1;
@@ -648,12 +795,20 @@ static int rnn_forward(orl_rnn* d, const RnnRuns& rs, RnnWs& w, int rows, int T,
     rnn_mark(d, train, 5 + 4 * l);
     X = w.HO[l];
   }
+  return 0;
+}
+
+// the tail over N rows: the input block on X0, the merge layer on [its output | the top GRU layer's h] (w.CAT), the residual blocks and the
+// head into w.PRED.  The window forward and the one-step path (orl_rnn_state_step) both end here
+static int rnn_tail(orl_rnn* d, const RnnRuns& rs, RnnWs& w, const DevMat& X0, long N, bool train) {
+  const int H = d->H;
+  const bool drop = train && d->c.dropout_rate > 0.f;
   if (rnn_fwd(d, rs, X0, (int)N, d->lin_in, d->in, H, w.SI, true, train ? w.ZI.p : nullptr)) return -1;
   RnnNormP n0 = rnn_norm_params(d, rs, w, 0, N, w.SI, w.UI, d->norm_in, drop);
   n0.out = w.CAT.p; n0.op = w.CAT.pitch; n0.out_rs = w.CAT.s0;
   DEV_LAUNCH(d->stream, k_rnn_ln_fwd, dim3((unsigned)N, rs.n), dim3(64), 0, n0);
   if (rnn_fwd(d, rs, w.CAT, (int)N, d->lin_merge, 2 * H, H, w.M0, true, train ? w.ZM.p : nullptr)) return -1;
-  X = w.M0;
+  DevMat X = w.M0;
   for (int i = 0; i < d->nb; ++i) {
     if (rnn_fwd(d, rs, X, (int)N, d->lin_b[i], H, H, w.SB[i], true, train ? w.ZB[i].p : nullptr)) return -1;
     RnnNormP nb = rnn_norm_params(d, rs, w, 1 + i, N, w.SB[i], w.UB[i], d->norm_b[i], drop);
@@ -663,6 +818,14 @@ static int rnn_forward(orl_rnn* d, const RnnRuns& rs, RnnWs& w, int rows, int T,
     X = w.XO[i];
   }
   return rnn_fwd(d, rs, X, (int)N, d->lin_out, H, d->od, w.PRED, false, nullptr);
+}
+
+// the forward of the runs rs over `rows` sequences of T steps of workspace w (X0 in place; shared_x: every run reads slot 0's X0); train:
+// the scans save what the backward reads, the pre-activations are kept and the dropouts read the keep masks of w.MK
+static int rnn_forward(orl_rnn* d, const RnnRuns& rs, RnnWs& w, int rows, int T, bool train, bool shared_x) {
+  DevMat X0 = w.X0;
+  if (shared_x) X0.s0 = 0;
+  return rnn_gru_windows(d, rs, w, X0, rows, T, train) || rnn_tail(d, rs, w, X0, (long)rows * T, train) ? -1 : 0;
 }
 
 // backward of every run from dPRED over the first rows * T rows of the training workspace
@@ -767,7 +930,7 @@ static int rnn_enqueue_step(orl_rnn* d, const long long* idx, long idx_rs, int r
   rnn_mark(d, true, 3);
   d->prof_valid = d->prof;
   d->kstep += 1;
-  d->last_ws = &w; d->last_rows = N; d->last_r0 = 0; d->last_nr = R;
+  d->last_ws = &w; d->last_rows = N; d->last_r0 = 0; d->last_nr = R; d->last_roll = false;
   return 0;
 }
 
@@ -1013,6 +1176,33 @@ int orl_rnn_learn_epoch_runs(orl_rnn* d, const int64_t* orders, int64_t n_rows, 
   return rnn_learn_epoch_runs(d, "orl_rnn_learn_epoch_runs", orders, n_rows, on_device, losses_out);
 }
 
+// the eval workspace and the forward staging for N rows of `runs` runs, grown on demand
+static int rnn_eval_ws(orl_rnn* d, long N, int runs) {
+  if (N <= d->f_cap && runs <= d->f_runs) return 0;
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  d->mem.release(&d->fIn, &d->fLast, &d->fAll);
+  const long cap = std::max(N, d->f_cap);
+  runs = std::max(runs, d->f_runs);
+  d->f_cap = 0; d->f_runs = 0;
+  if (d->last_ws == &d->ew) d->last_ws = nullptr;
+  if (d->mem.alloc(&d->fIn, (size_t)runs * cap * d->in) || d->mem.alloc(&d->fLast, (size_t)runs * cap * d->od) ||
+      d->mem.alloc(&d->fAll, (size_t)runs * cap * d->od) || rnn_ws_alloc(d, d->ew, cap, false, runs))
+    return -1;
+  d->f_cap = cap; d->f_runs = runs;
+  return 0;
+}
+// the eval forward of the runs rs over the windows inputs [n][T][in] (one array when shared or one run, else one per run), enqueued
+static int rnn_eval_windows(orl_rnn* d, const RnnRuns& rs, const float* inputs, int64_t n, int32_t T, int on_device, int shared) {
+  const int n_in = (shared || rs.n == 1) ? 1 : rs.n;     // input arrays
+  const long N = (long)n * T;
+  if (rnn_eval_ws(d, N, rs.n)) return -1;
+  RnnWs& w = d->ew;
+  const float* in_d = inputs;
+  if (stage_in(d->stream, in_d, d->fIn, (size_t)n_in * N * d->in, on_device)) return -1;
+  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid(N * d->in), n_in), dim3(256), 0, in_d, d->in, N * d->in, w.X0.p, w.X0.pitch, w.X0.s0, N, d->in, 1);
+  return rnn_forward(d, rs, w, (int)n, T, false, n_in < rs.n);
+}
+
 // orl_rnn_forward / orl_rnn_forward_runs: run >= 0 that run alone, -1 every run (inputs shared or [R][n][T][in])
 static int rnn_forward_runs(orl_rnn* d, const char* what, const float* inputs, int64_t n, int32_t T, int on_device, int shared, int run, float* out_last,
                             float* out_all) {
@@ -1022,25 +1212,9 @@ static int rnn_forward_runs(orl_rnn* d, const char* what, const float* inputs, i
   if (T < 1 || T > d->Tmax) return fail(wh + ": need 1 <= T <= max_seq_len (" + std::to_string(d->Tmax) + ")");
   if (n > 0x7fffffffL / ((int64_t)T * 8 * d->H)) return fail(wh + ": too many sequences for one call");
   const RnnRuns rs{run < 0 ? 0 : run, run < 0 ? d->R : 1};
-  const int n_in = (shared || run >= 0) ? 1 : rs.n;      // input arrays
   const long N = (long)n * T;
-  if (N > d->f_cap || rs.n > d->f_runs) {
-    ORL_HIP(hipStreamSynchronize(d->stream));
-    d->mem.release(&d->fIn, &d->fLast, &d->fAll);
-    const long cap = std::max(N, d->f_cap);
-    const int runs = std::max(rs.n, d->f_runs);
-    d->f_cap = 0; d->f_runs = 0;
-    if (d->last_ws == &d->ew) d->last_ws = nullptr;
-    if (d->mem.alloc(&d->fIn, (size_t)runs * cap * d->in) || d->mem.alloc(&d->fLast, (size_t)runs * cap * d->od) ||
-        d->mem.alloc(&d->fAll, (size_t)runs * cap * d->od) || rnn_ws_alloc(d, d->ew, cap, false, runs))
-      return -1;
-    d->f_cap = cap; d->f_runs = runs;
-  }
+  if (rnn_eval_windows(d, rs, inputs, n, T, on_device, shared)) return -1;
   RnnWs& w = d->ew;
-  const float* in_d = inputs;
-  if (stage_in(d->stream, in_d, d->fIn, (size_t)n_in * N * d->in, on_device)) return -1;
-  DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid(N * d->in), n_in), dim3(256), 0, in_d, d->in, N * d->in, w.X0.p, w.X0.pitch, w.X0.s0, N, d->in, 1);
-  if (rnn_forward(d, rs, w, (int)n, T, false, n_in < rs.n)) return -1;
   float* last = stage_dst(out_last, d->fLast, on_device);
   DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid((long)n * d->od), rs.n), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, last, d->od,
               (long)n * d->od, (long)n, d->od, (int)T);
@@ -1052,7 +1226,7 @@ static int rnn_forward_runs(orl_rnn* d, const char* what, const float* inputs, i
     if (stage_out(d->stream, out_all, d->fAll, (size_t)rs.n * N * d->od, on_device)) return -1;
   }
   ORL_HIP(hipStreamSynchronize(d->stream));
-  d->last_ws = &w; d->last_rows = N; d->last_r0 = rs.r0; d->last_nr = rs.n;
+  d->last_ws = &w; d->last_rows = N; d->last_r0 = rs.r0; d->last_nr = rs.n; d->last_roll = false;
   return 0;
 }
 int orl_rnn_forward(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, float* out_last, float* out_all) {
@@ -1063,6 +1237,140 @@ int orl_rnn_forward_runs(orl_rnn* d, const float* inputs, int64_t n, int32_t T, 
                          float* out_all) {
   if (rnn_ready(d, "orl_rnn_forward_runs", false)) return -1;
   return rnn_forward_runs(d, "orl_rnn_forward_runs", inputs, n, T, on_device, shared_inputs, run, out_last, out_all);
+}
+
+// ---- the carried state ----
+// layer l of run r in state buffer s
+static float* rnn_state_at(orl_rnn* d, int s, int run, int l) { return d->st[s] + (((long)run * d->L + l) * d->n_traj) * d->H; }
+static int rnn_has_state(const orl_rnn* d, const char* what) {
+  return d->st[0] ? 0 : fail(std::string(what) + ": no state yet (orl_rnn_state_reset)");
+}
+
+int orl_rnn_set_scaler(orl_rnn* d, const float* mu, const float* std_, int64_t n) {
+  if (rnn_ready(d, "orl_rnn_set_scaler", false)) return -1;
+  if (!mu || !std_) return fail("orl_rnn_set_scaler: bad arguments");
+  if (n != d->in) return fail("orl_rnn_set_scaler: expected input_dim = " + std::to_string(d->in) + " floats each");
+  for (int c = 0; c < d->in; ++c)
+    if (!(std_[c] != 0.f) || !std::isfinite(std_[c]) || !std::isfinite(mu[c])) return fail("orl_rnn_set_scaler: mu must be finite, std finite and not 0");
+  if (!d->sc_mu && (d->mem.alloc(&d->sc_mu, d->in) || d->mem.alloc(&d->sc_std, d->in))) return -1;
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  ORL_HIP(hipMemcpy(d->sc_mu, mu, sizeof(float) * d->in, hipMemcpyHostToDevice));
+  ORL_HIP(hipMemcpy(d->sc_std, std_, sizeof(float) * d->in, hipMemcpyHostToDevice));
+  d->has_scaler = true;
+  return 0;
+}
+
+int orl_rnn_state_reset(orl_rnn* d, int64_t n_traj) {
+  if (rnn_ready(d, "orl_rnn_state_reset", false)) return -1;
+  if (n_traj < 1 || n_traj > 0x7fffffffL / ((int64_t)8 * d->H)) return fail("orl_rnn_state_reset: n_traj must be positive and index one step's matrices");
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  const size_t per = (size_t)d->R * d->L * n_traj * d->H;
+  if (n_traj != d->n_traj) {
+    d->mem.release(&d->st[0], &d->st[1], &d->side);
+    d->n_traj = 0;
+    if (d->mem.alloc(&d->st[0], per) || d->mem.alloc(&d->st[1], per) || d->mem.alloc(&d->side, (size_t)d->R * n_traj)) return -1;   // (zero-filled)
+    d->n_traj = n_traj;
+    return 0;
+  }
+  ORL_HIP(hipMemsetAsync(d->st[0], 0, sizeof(float) * per, d->stream));
+  ORL_HIP(hipMemsetAsync(d->st[1], 0, sizeof(float) * per, d->stream));
+  ORL_HIP(hipMemsetAsync(d->side, 0, sizeof(int) * d->R * n_traj, d->stream));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+int orl_rnn_state_set(orl_rnn* d, int run, int layer, const float* host, int64_t n_traj) {
+  if (rnn_ready(d, "orl_rnn_state_set", false) || rnn_has_state(d, "orl_rnn_state_set") || rnn_run_ok(d, run, "orl_rnn_state_set")) return -1;
+  if (!host) return fail("orl_rnn_state_set: bad arguments");
+  if (layer < 0 || layer >= d->L) return fail("orl_rnn_state_set: layer out of range (" + std::to_string(d->L) + " GRU layers)");
+  if (n_traj != d->n_traj) return fail("orl_rnn_state_set: the state has " + std::to_string(d->n_traj) + " trajectories");
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  for (int s = 0; s < 2; ++s)                             // both buffers: whichever a slot's side bit names holds the planted row
+    ORL_HIP(hipMemcpy(rnn_state_at(d, s, run, layer), host, sizeof(float) * n_traj * d->H, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int orl_rnn_state_prime(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, int shared_inputs) {
+  if (rnn_ready(d, "orl_rnn_state_prime", false) || rnn_has_state(d, "orl_rnn_state_prime")) return -1;
+  if (!inputs || n < 1) return fail("orl_rnn_state_prime: bad arguments");
+  if (n > d->n_traj) return fail("orl_rnn_state_prime: " + std::to_string(n) + " windows for a state of " + std::to_string(d->n_traj) + " trajectories");
+  if (T < 1 || T > d->Tmax) return fail("orl_rnn_state_prime: need 1 <= T <= max_seq_len (" + std::to_string(d->Tmax) + ")");
+  if (n > 0x7fffffffL / ((int64_t)T * 8 * d->H)) return fail("orl_rnn_state_prime: too many sequences for one call");
+  const RnnRuns rs{0, d->R};
+  if (rnn_eval_windows(d, rs, inputs, n, T, on_device, shared_inputs)) return -1;
+  const RnnWs& w = d->ew;
+  const long st_rs = (long)d->L * d->n_traj * d->H;
+  for (int l = 0; l < d->L; ++l)
+    for (int s = 0; s < 2; ++s)                           // slots 0 .. n - 1 of both buffers <- row b T + T - 1 of the layer's h
+      DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid((long)n * d->H), rs.n), dim3(256), 0, (const float*)w.HO[l].p, w.HO[l].pitch, w.HO[l].s0,
+                 rnn_state_at(d, s, 0, l), d->H, st_rs, (long)n, d->H, (int)T);
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  d->last_ws = &w; d->last_rows = (long)n * T; d->last_r0 = 0; d->last_nr = rs.n; d->last_roll = false;
+  return 0;
+}
+
+int orl_rnn_state_step(orl_rnn* d, const float* obs, const float* act, const int64_t* index, int64_t n, int on_device, int run, float* next_obs,
+                       float* reward) {
+  if (rnn_ready(d, "orl_rnn_state_step", false) || rnn_has_state(d, "orl_rnn_state_step")) return -1;
+  const int odim = d->od - 1, adim = d->in - odim;        // the model predicts [delta obs | reward] from [obs | act]
+  if (adim < 1)
+    return fail("orl_rnn_state_step: output_dim " + std::to_string(d->od) + " means obs_dim " + std::to_string(odim) + ", which leaves act_dim = input_dim - obs_dim = " +
+                std::to_string(adim) + " < 1");
+  if (odim < 1) return fail("orl_rnn_state_step: output_dim must be obs_dim + 1 with obs_dim >= 1");
+  if (!d->has_scaler) return fail("orl_rnn_state_step: no input scaler (orl_rnn_set_scaler)");
+  if (!obs || !act || !next_obs || !reward || n < 1) return fail("orl_rnn_state_step: bad arguments");
+  if (run < -1 || run >= d->R) return fail("orl_rnn_state_step: run out of range (" + std::to_string(d->R) + " runs, or -1 for all)");
+  if (n > d->n_traj) return fail("orl_rnn_state_step: " + std::to_string(n) + " rows for a state of " + std::to_string(d->n_traj) + " trajectories");
+  const RnnRuns rs{run < 0 ? 0 : run, run < 0 ? d->R : 1};
+  const int H = d->H;
+  if (rnn_eval_ws(d, n, rs.n)) return -1;
+  const long long* idx_d = nullptr;
+  if (index && on_device) idx_d = (const long long*)index;      // (the kernels clamp what they read)
+  else if (index) {
+    std::vector<char> seen((size_t)d->n_traj, 0);
+    for (int64_t i = 0; i < n; ++i) {
+      if (index[i] < 0 || index[i] >= d->n_traj)
+        return fail("orl_rnn_state_step: trajectory index out of range (" + std::to_string(d->n_traj) + " trajectories)");
+      if (seen[index[i]]) return fail("orl_rnn_state_step: trajectory index " + std::to_string(index[i]) + " twice in one step");
+      seen[index[i]] = 1;
+    }
+    if (d->mem.grow(&d->r_idx, &d->r_idx_cap, d->n_traj, d->stream)) return -1;
+    ORL_HIP(hipMemcpyAsync(d->r_idx, index, sizeof(int64_t) * n, hipMemcpyHostToDevice, d->stream));
+    idx_d = d->r_idx;
+  }
+  // host arrays: obs | act | next_obs | reward of the step's runs, staged
+  const size_t no = (size_t)rs.n * n * odim, na = (size_t)rs.n * n * adim, nr = (size_t)rs.n * n;
+  if (!on_device && d->mem.grow(&d->r_stage, &d->r_stage_cap, (long)(2 * no + na + nr), d->stream)) return -1;
+  const float *obs_d = obs, *act_d = act;
+  if (stage_in(d->stream, obs_d, d->r_stage, no, on_device) || stage_in(d->stream, act_d, d->r_stage + no, na, on_device)) return -1;
+  float* next_d = stage_dst(next_obs, d->r_stage + no + na, on_device);
+  float* rew_d = stage_dst(reward, d->r_stage + 2 * no + na, on_device);
+  RnnWs& w = d->ew;
+  DEV_LAUNCH(d->stream, k_rnn_roll_in, dim3(ew_grid(n * d->in), rs.n), dim3(256), 0, obs_d, (long)n * odim, act_d, (long)n * adim, odim, adim,
+             (const float*)d->sc_mu, (const float*)d->sc_std, (long)n, w.X0.p, w.X0.pitch, w.X0.s0);
+  float* params = rnn_params_of(d, rs);
+  DevMat X = w.X0;
+  for (int l = 0; l < d->L; ++l) {
+    RnnCellP cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.n = (int)n; cp.H = H; cp.K = l ? H : d->in;
+    cp.x = X.p; cp.xp = X.pitch; cp.x_rs = X.s0;
+    cp.wih = params + d->wih[l].w; cp.whh = params + d->whh[l].w; cp.bih = params + d->wih[l].b; cp.bhh = params + d->whh[l].b; cp.par_rs = d->P;
+    cp.idx = idx_d;
+    cp.st[0] = rnn_state_at(d, 0, rs.r0, l); cp.st[1] = rnn_state_at(d, 1, rs.r0, l); cp.st_rs = (long)d->L * d->n_traj * H;
+    cp.side = d->side + (long)rs.r0 * d->n_traj; cp.n_traj = d->n_traj;
+    cp.ho = w.HO[l].p; cp.hop = w.HO[l].pitch; cp.ho_rs = w.HO[l].s0;
+    DEV_LAUNCH(d->stream, k_rnn_cell, dim3((unsigned)((n + RNN_RB - 1) / RNN_RB), (H + 15) / 16, rs.n), dim3(64), 0, cp);
+    X = w.HO[l];
+  }
+  if (rnn_tail(d, rs, w, w.X0, (long)n, false)) return -1;
+  DEV_LAUNCH(d->stream, k_rnn_roll_head, dim3(ew_grid(n * d->od), rs.n), dim3(256), 0, (const float*)w.PRED.p, w.PRED.pitch, w.PRED.s0, obs_d,
+             (long)n * odim, d->od, (long)n, next_d, rew_d, idx_d, d->side + (long)rs.r0 * d->n_traj, d->n_traj);
+  if (stage_out(d->stream, next_obs, d->r_stage + no + na, no, on_device) || stage_out(d->stream, reward, d->r_stage + 2 * no + na, nr, on_device))
+    return -1;
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  d->last_ws = &w; d->last_rows = (long)n; d->last_r0 = rs.r0; d->last_nr = rs.n; d->last_roll = true;
+  return 0;
 }
 
 // "<prefix><k>" with 0 <= k < count; -1 otherwise
@@ -1079,8 +1387,25 @@ int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* hos
   if (!d || !name || !host) return fail("orl_rnn_debug_read: bad arguments");
   if (rnn_run_ok(d, run, "orl_rnn_debug_read")) return -1;
   const std::string nm(name);
+  int k;
+  if ((k = rnn_tap_index(nm, "state.", d->L)) >= 0) {         // the carried h of every slot: each from the buffer its side bit names
+    if (rnn_has_state(d, "orl_rnn_debug_read")) return -1;
+    const long n = d->n_traj * d->H;
+    if (n > cap) return fail("orl_rnn_debug_read: " + nm + " needs " + std::to_string(n) + " floats");
+    ORL_HIP(hipStreamSynchronize(d->stream));
+    std::vector<float> other((size_t)n);
+    std::vector<int> side((size_t)d->n_traj);
+    ORL_HIP(hipMemcpy(host, rnn_state_at(d, 0, run, k), sizeof(float) * n, hipMemcpyDeviceToHost));
+    ORL_HIP(hipMemcpy(other.data(), rnn_state_at(d, 1, run, k), sizeof(float) * n, hipMemcpyDeviceToHost));
+    ORL_HIP(hipMemcpy(side.data(), d->side + (long)run * d->n_traj, sizeof(int) * d->n_traj, hipMemcpyDeviceToHost));
+    for (long t = 0; t < d->n_traj; ++t)
+      if (side[t] & 1) memcpy(host + t * d->H, other.data() + t * d->H, sizeof(float) * d->H);
+    return n;
+  }
   const RnnWs* w = d->last_ws ? d->last_ws : &d->tw;          // (names are resolved before "nothing recorded": an unknown one is always refused)
-  const float* src = nullptr; long rows = d->last_rows, rs = 0; int cols = d->H, pitch = d->H, k;
+  const float* src = nullptr; long rows = d->last_rows, rs = 0; int cols = d->H, pitch = d->H;
+  bool roll = false;                                          // a name of the one-step path
+  const bool rolled = d->last_ws && d->last_roll;             // ... which the last pass was
   auto mat = [&](const DevMat& m) { src = m.p; pitch = m.pitch; rs = m.s0; };
   if (nm == "loss") { src = d->loss_cell + run; rows = 1; cols = 1; pitch = 1; }
   else if (nm == "pred") { mat(w->PRED); cols = d->od; }
@@ -1094,8 +1419,14 @@ int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* hos
     if (!w->train || !(d->c.dropout_rate > 0.f)) return fail("orl_rnn_debug_read: no dropout mask was applied");
     src = w->MK + (size_t)k * w->cap * d->H; rs = w->mk_rs;
   }
-  else if ((k = rnn_tap_index(nm, "gi.", d->L)) >= 0) { mat(w->GI[k]); cols = 3 * d->H; }
+  else if ((k = rnn_tap_index(nm, "gi.", d->L)) >= 0) {
+    if (rolled) return fail("orl_rnn_debug_read: a state step keeps no input projections (" + nm + "): k_rnn_cell forms them in registers");
+    mat(w->GI[k]); cols = 3 * d->H;
+  }
   else if (nm == "x0") { mat(w->X0); cols = d->in; }
+  else if (nm == "roll.x") { roll = true; cols = d->in; if (rolled) mat(w->X0); }
+  else if (nm == "roll.pred") { roll = true; cols = d->od; if (rolled) mat(w->PRED); }
+  else if ((k = rnn_tap_index(nm, "roll.h.", d->L)) >= 0) { roll = true; if (rolled) mat(w->HO[k]); }
   else {
     // what only a training step computes.  st: the stage's index when the matrix is one of a shared buffer's stages, last: the stage
     // that writes the shared buffer last (the one still readable without orl_rnn_debug_keep)
@@ -1135,6 +1466,7 @@ int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* hos
     if (d->last_ws && !w->keep && st >= 0 && st != last)
       return fail("orl_rnn_debug_read: a later stage of the step has overwritten " + nm + " (orl_rnn_debug_keep keeps every stage's)");
   }
+  if (roll && !rolled) return fail("orl_rnn_debug_read: nothing recorded for " + nm + " (the last pass was no state step)");
   if (!src || rows < 1 || (!d->last_ws && nm != "loss")) return fail("orl_rnn_debug_read: nothing recorded for " + nm);
   if (nm != "loss") {                                         // the run's slot in the workspace of the last pass
     if (run < d->last_r0 || run >= d->last_r0 + d->last_nr) return fail("orl_rnn_debug_read: the last pass did not compute run " + std::to_string(run));

@@ -81,6 +81,8 @@ ABI_SYMBOLS = [
     "orl_rnn_debug_grads_run",
     # ... and the tests' switch that keeps every backward stage readable
     "orl_rnn_debug_keep",
+    # ... and its carried GRU state: one model step at a time
+    "orl_rnn_set_scaler", "orl_rnn_state_reset", "orl_rnn_state_prime", "orl_rnn_state_step", "orl_rnn_state_set",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -422,6 +424,11 @@ def _bind_rnn(lib) -> None:
     lib.orl_rnn_debug_read_run.restype = I64
     lib.orl_rnn_debug_grads_run.argtypes = [P, C.c_int, VP, I64]
     lib.orl_rnn_debug_keep.argtypes = [P, C.c_int]
+    lib.orl_rnn_set_scaler.argtypes = [P, VP, VP, I64]
+    lib.orl_rnn_state_reset.argtypes = [P, I64]
+    lib.orl_rnn_state_prime.argtypes = [P, VP, I64, C.c_int32, C.c_int, C.c_int]
+    lib.orl_rnn_state_step.argtypes = [P, VP, VP, VP, I64, C.c_int, C.c_int, VP, VP]
+    lib.orl_rnn_state_set.argtypes = [P, C.c_int, C.c_int, VP, I64]
     lib.orl_rnn_profile.argtypes = [P, C.c_int]
     lib.orl_rnn_profile_read.argtypes = [P, C.POINTER(C.c_float)]
 
@@ -1746,8 +1753,82 @@ class RnnDynamicsEngine(_FlatBlocks, _Handle):
                    "orl_rnn_forward_runs")
         return (last, every) if want_all else last
 
+    # ---- the carried GRU state: one model step at a time (orl_rnn_state_*) ----
+    def set_scaler(self, mu, std):
+        """the input scaler of ``state_step`` (``StandardScaler``'s mu and std, ``input_dim`` values each; shared by the runs)"""
+        mu, std = _f32(mu).ravel(), _f32(std).ravel()
+        assert mu.size == std.size
+        _check(self.lib.orl_rnn_set_scaler(self._h, mu.ctypes.data, std.ctypes.data, mu.size), "orl_rnn_set_scaler")
+
+    def state_reset(self, n_traj: int):
+        """(re)allocate the state of ``n_traj`` trajectories and zero it, in every run"""
+        _check(self.lib.orl_rnn_state_reset(self._h, int(n_traj)), "orl_rnn_state_reset")
+        self.n_traj = int(n_traj)
+
+    def state_prime(self, inputs):
+        """start slots 0 .. n - 1 of every run from the already scaled windows ``inputs`` [n, T, input_dim] (every run reads them) or
+        [R, n, T, input_dim]: host arrays or contiguous fp32 torch tensors on the engine's device"""
+        tensor = _is_tensor(inputs)
+        inputs = inputs.contiguous() if tensor else _f32(inputs)
+        assert inputs.ndim in (3, 4) and int(inputs.shape[-1]) == int(self.cfg.input_dim)
+        assert inputs.ndim == 3 or int(inputs.shape[0]) == self.n_runs, "per-run windows are [R, n, T, input_dim]"
+        if tensor:
+            import torch
+            torch.cuda.current_stream(inputs.device).synchronize()
+        _check(self.lib.orl_rnn_state_prime(self._h, inputs.data_ptr() if tensor else inputs.ctypes.data, int(inputs.shape[-3]),
+                                            int(inputs.shape[-2]), int(tensor), int(inputs.ndim == 3)), "orl_rnn_state_prime")
+
+    def state_step(self, obs, act, index=None, run: int = 0):
+        """one model step of the rows ``obs`` [n, obs_dim] / ``act`` [n, act_dim] (unscaled) of run ``run``, or with ``run=-1`` of every
+        run on [R, n, .]; ``index`` [n] int64: the trajectory of each row (default 0 .. n - 1; shared by the runs).  Contiguous torch
+        tensors on the engine's device in and out (no host copy), or numpy arrays.  -> (next_obs [.., n, obs_dim], reward [.., n])"""
+        tensor = _is_tensor(obs)
+        od = int(self.cfg.output_dim) - 1
+        lead = (self.n_runs,) if run == -1 else ()
+        if tensor:
+            import torch
+            obs, act = obs.contiguous(), act.contiguous()
+            if obs.dtype != torch.float32 or act.dtype != torch.float32 or act.device != obs.device:
+                raise ValueError("state_step: obs and act must be fp32 tensors on one device")
+            if index is not None:
+                index = index.contiguous()
+                if index.dtype != torch.int64 or index.device != obs.device:
+                    raise ValueError("state_step: index must be an int64 tensor on the device of obs")
+        else:
+            obs, act = _f32(obs), _f32(act)
+            if index is not None:
+                index = np.ascontiguousarray(index, dtype=np.int64)
+        n = int(obs.shape[-2]) if obs.ndim >= 2 else -1
+        if obs.ndim != len(lead) + 2 or tuple(obs.shape) != lead + (n, od) or tuple(act.shape) != lead + (n, int(self.cfg.input_dim) - od):
+            raise ValueError(f"state_step: obs {tuple(obs.shape)} / act {tuple(act.shape)} must be {lead + ('n', od)} / "
+                             f"{lead + ('n', int(self.cfg.input_dim) - od)}")
+        if index is not None and tuple(index.shape) != (n,):
+            raise ValueError(f"state_step: index {tuple(index.shape)} must be ({n},), one trajectory per row")
+        if tensor:
+            nxt = torch.empty(lead + (n, od), dtype=torch.float32, device=obs.device)
+            rew = torch.empty(lead + (n,), dtype=torch.float32, device=obs.device)
+            torch.cuda.current_stream(obs.device).synchronize()
+            ptrs = (obs.data_ptr(), act.data_ptr(), None if index is None else index.data_ptr(), nxt.data_ptr(), rew.data_ptr())
+        else:
+            nxt, rew = np.empty(lead + (n, od), np.float32), np.empty(lead + (n,), np.float32)
+            ptrs = (obs.ctypes.data, act.ctypes.data, None if index is None else index.ctypes.data, nxt.ctypes.data, rew.ctypes.data)
+        _check(self.lib.orl_rnn_state_step(self._h, ptrs[0], ptrs[1], ptrs[2], n, int(tensor), int(run), ptrs[3], ptrs[4]), "orl_rnn_state_step")
+        return nxt, rew
+
+    def state_get(self, layer: int, run: int = 0) -> np.ndarray:
+        """the carried h of GRU layer ``layer`` of run ``run``: [n_traj, H]"""
+        H = int(self.cfg.hidden[0])
+        return self.debug_read(f"state.{int(layer)}", run=run).reshape(-1, H)
+
+    def state_set(self, layer: int, h, run: int = 0):
+        """plant the carried h of GRU layer ``layer`` of run ``run``: [n_traj, H] (tests)"""
+        h = _f32(h)
+        assert h.ndim == 2 and int(h.shape[1]) == int(self.cfg.hidden[0])
+        _check(self.lib.orl_rnn_state_set(self._h, int(run), int(layer), h.ctypes.data, int(h.shape[0])), "orl_rnn_state_set")
+
     def debug_read(self, name: str, cap: int = 1 << 22, run: int = 0) -> np.ndarray:
-        """a test tap of the last step / forward as a flat array: pred, loss, gru.<l>, in, merge, block.<i>, mask.<s>, act.<s>, drop.<s>"""
+        """a test tap of the last step / forward as a flat array: pred, loss, gru.<l>, in, merge, block.<i>, mask.<s>, act.<s>, drop.<s>;
+        state.<l>; after a ``state_step`` roll.x, roll.h.<l>, roll.pred"""
         return _read_tap(self.lib.orl_rnn_debug_read_run, f"orl_rnn_debug_read({name!r})", name, cap, self._h, int(run))
 
     def debug_keep(self, on: bool = True):

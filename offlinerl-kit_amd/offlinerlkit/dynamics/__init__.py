@@ -555,7 +555,10 @@ def _fresh_rnn_params(model, seed: int) -> Dict[str, torch.Tensor]:
 class RNNDynamics(BaseDynamics):
     """The GRU sequence dynamics model (reference: dynamics/rnn_dynamics.py over nets/rnn.py:RNNModel) on the HIP engine (``orl_rnn_*``,
     csrc/rnn_dynamics.hip).  ``learn`` is one device step of the masked MSE with Adam, ``train`` loads the data set into HBM once and
-    runs every epoch as one call, ``step`` is one eval-mode forward over the windows.  The module's parameters alias the engine's
+    runs every epoch as one call, ``step`` is one eval-mode forward over the windows.  A rollout goes through the carried state
+    instead: ``reset_state`` once, then ``step_state`` (numpy) or ``step_device`` (tensors) per model step, O(1) work each at any
+    horizon (``RcslPolicy.rollout`` / ``rollout_device`` do this for a ``stateful`` dynamics); ``MBPolicyTrainer``'s MOPO / COMBO
+    rollouts and training through the carried state are not supported.  The module's parameters alias the engine's
     block, so ``model.state_dict()``, ``save`` and ``load`` see what the engine trains.  Dropout masks come from a device Philox
     stream, so a training run is distributed like the reference's, not equal to it (at ``dropout_rate`` 0 it is equal).
 
@@ -596,6 +599,11 @@ class RNNDynamics(BaseDynamics):
         self._eng: Optional[_engine.RnnDynamicsEngine] = None
         self._arena = None
         self._shape = None              # (batch_size, max_seq_len) the engine was built for
+        self._state_n: Optional[int] = None     # trajectories of the carried state (reset_state), None: no state
+
+    # a rollout carries this model's recurrent state on the device: RcslPolicy.rollout / rollout_device call reset_state and pass the
+    # live trajectory indices to step_state / step_device
+    stateful = True
 
     # ---- engine binding ----
     def set_engine_options(self, n_runs: int = 1, seed: Optional[int] = None) -> None:
@@ -632,6 +640,7 @@ class RNNDynamics(BaseDynamics):
         torch.cuda.synchronize(dev)
         self._eng = _engine.RnnDynamicsEngine(cfg)
         self._shape = shape
+        self._state_n = None            # (the carried state lived in the old engine)
         for r in range(R):
             if carried is not None:
                 for which in range(3):
@@ -690,6 +699,117 @@ class RNNDynamics(BaseDynamics):
         rewards = preds[..., -1:]
         terminals = self.terminal_fn(obss[:, -1], actions[:, -1], next_obss)
         return next_obss, rewards, terminals, {}
+
+    # ---- the carried state: one model step at a time (orl_rnn_state_* of the engine) ----
+    @property
+    def term_kind(self) -> Optional[int]:
+        """the ``TERM_*`` kind of the termination function (utils.termination_fns), None when it is not a fixed row-wise test"""
+        from ..utils import termination_fns
+        return termination_fns.term_kind(self.terminal_fn)
+
+    def _roll_dims(self, what: str) -> Tuple[int, int]:
+        """(obs_dim, act_dim) of the one-step interface: the model predicts [delta obs | reward] from [obs | action]"""
+        obs_dim = int(self.model.output_dim) - 1
+        act_dim = int(self.model.input_dim) - obs_dim
+        if obs_dim < 1 or act_dim < 1:
+            raise ValueError(f"{what}: output_dim {self.model.output_dim} must be obs_dim + 1 and input_dim {self.model.input_dim} "
+                             f"obs_dim + act_dim with act_dim >= 1")
+        if self.scaler is None or self.scaler.mu is None:
+            raise RuntimeError(f"{what}: the scaler is not fitted: fit or load it first")
+        return obs_dim, act_dim
+
+    def _roll_rows(self, what: str, obs, act, index, lead: int):
+        """the refusals of a step's arrays: rank, widths (output_dim == obs_dim + 1), a state to step, the index's length"""
+        obs_dim, act_dim = self._roll_dims(what)
+        if obs.ndim != lead + 2 or act.ndim != lead + 2 or tuple(obs.shape[:-1]) != tuple(act.shape[:-1]):
+            shape = ("R, " if lead else "") + "N, "
+            raise ValueError(f"{what}: obs {tuple(obs.shape)} / action {tuple(act.shape)} must be ({shape}obs_dim) / ({shape}act_dim)")
+        if int(obs.shape[-1]) + 1 != int(self.model.output_dim):
+            raise ValueError(f"{what}: output_dim {self.model.output_dim} != obs_dim + 1 for observations of {int(obs.shape[-1])} columns")
+        if int(act.shape[-1]) != act_dim:
+            raise ValueError(f"{what}: actions of {int(act.shape[-1])} columns, input_dim - obs_dim = {act_dim}")
+        if lead and int(obs.shape[0]) != self._n_runs:
+            raise ValueError(f"{what}: rows of {int(obs.shape[0])} runs for an object of {self._n_runs}")
+        if self._state_n is None or self._eng is None:
+            raise RuntimeError(f"{what}: no carried state: reset_state(n_traj) first")
+        n = int(obs.shape[-2])
+        if index is not None and (index.ndim != 1 or int(index.shape[0]) != n):
+            raise ValueError(f"{what}: index {tuple(index.shape)} must name one trajectory per row ({n},)")
+        if n > self._state_n:
+            raise ValueError(f"{what}: {n} rows (index of {n}) for a state of {self._state_n} trajectories")
+
+    def reset_state(self, n_traj: int, windows=None) -> None:
+        """Start a rollout of ``n_traj`` trajectories: their GRU state, kept on the device, is zero (the reference's ``h_state=None``),
+        or with ``windows=(obss, actions)`` of shape ``(n_traj, T, .)`` (``(R, n_traj, T, .)``: one history per run) the state after
+        those T steps.  The scaler is read here: fit or load it before."""
+        self._roll_dims("reset_state")
+        if int(n_traj) < 1:
+            raise ValueError(f"reset_state: n_traj {n_traj}")
+        T = 1
+        if windows is not None:
+            obss, actions = (np.asarray(self._host(x)) for x in windows)
+            inputs = self.scaler.transform(np.concatenate([obss, actions], axis=-1))
+            if inputs.ndim not in (3, 4) or inputs.shape[-3] != int(n_traj) or (inputs.ndim == 4 and inputs.shape[0] != self._n_runs):
+                raise ValueError(f"reset_state: windows {tuple(inputs.shape)} must be ({n_traj}, T, .) or ({self._n_runs}, {n_traj}, T, .)")
+            T = int(inputs.shape[-2])
+        self._bind(1, T)
+        self._drain()
+        self._eng.set_scaler(self.scaler.mu, self.scaler.std)
+        self._eng.state_reset(int(n_traj))
+        self._state_n = int(n_traj)
+        if windows is not None:
+            self._eng.state_prime(self._host(inputs))
+
+    @torch.no_grad()
+    def step_state(self, obs: np.ndarray, actions: np.ndarray, index=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Dict]:
+        """one model step from the carried state on numpy rows: obs (N, obs_dim), actions (N, act_dim) of the selected run, or
+        (R, N, .) of every run; ``index`` (N,): the trajectory of each row (default 0 .. N - 1).  -> (next_obs, reward (.., N, 1),
+        terminals, {}), ``terminal_fn`` applied on the host.  The launches of ``step_device``."""
+        obs, actions = self._host(obs), self._host(actions)
+        index = None if index is None else np.ascontiguousarray(self._index_host(index), dtype=np.int64)
+        runs = obs.ndim == 3
+        self._roll_rows("step_state", obs, actions, index, int(runs))
+        if index is not None and index.size and (index.min() < 0 or index.max() >= self._state_n):
+            raise ValueError(f"step_state: trajectory index out of range ({self._state_n} trajectories)")
+        self._drain()
+        nxt, rew = self._eng.state_step(obs, actions, index, run=-1 if runs else self._cur_run)
+        if runs:
+            terminals = np.stack([self.terminal_fn(obs[r], actions[r], nxt[r]) for r in range(self._n_runs)])
+        else:
+            terminals = self.terminal_fn(obs, actions, nxt)
+        return nxt, rew[..., None], terminals, {}
+
+    @staticmethod
+    def _index_host(index):
+        return index.detach().cpu().numpy() if torch.is_tensor(index) else np.asarray(index)
+
+    def _roll_tensors(self, what: str, obs, action, index, lead: int):
+        dev = self._arena.device if self._arena is not None else None
+        if dev is None:
+            raise RuntimeError(f"{what}: no carried state: reset_state(n_traj) first")
+        o = torch.as_tensor(obs, dtype=torch.float32, device=dev).contiguous()
+        a = torch.as_tensor(action, dtype=torch.float32, device=dev).contiguous()
+        ix = None if index is None else torch.as_tensor(index, dtype=torch.int64, device=dev).contiguous()
+        self._roll_rows(what, o, a, ix, lead)
+        return o, a, ix
+
+    @torch.no_grad()
+    def step_device(self, obs: torch.Tensor, action: torch.Tensor, index=None) -> Tuple[torch.Tensor, torch.Tensor, Dict]:
+        """``step_state`` without the termination function, on tensors of the engine's device and without a host copy: obs (N, obs_dim),
+        action (N, act_dim), ``index`` (N,) int64 (the live trajectories, e.g. ``TrajStore.live_index()``; distinct and inside the
+        state: device indices are not read back, the kernels clamp them) -> (next_obs (N, obs_dim), reward (N,), {}) of the selected
+        run.  The termination test is left to the consumer (``TrajStore.append_step`` runs ``term_kind`` on the device)."""
+        o, a, ix = self._roll_tensors("step_device", obs, action, index, 0)
+        nxt, rew = self._eng.state_step(o, a, ix, run=self._cur_run)
+        return nxt, rew, {}
+
+    @torch.no_grad()
+    def step_device_runs(self, obs: torch.Tensor, action: torch.Tensor, index=None) -> Tuple[torch.Tensor, torch.Tensor, Dict]:
+        """``step_device`` of every run at once: obs (R, N, obs_dim), action (R, N, act_dim), run r on block r; ``index`` (N,) is
+        shared by the runs -> (next_obs (R, N, obs_dim), reward (R, N), {})"""
+        o, a, ix = self._roll_tensors("step_device_runs", obs, action, index, 1)
+        nxt, rew = self._eng.state_step(o, a, ix, run=-1)
+        return nxt, rew, {}
 
     def _load_batch(self, batch) -> int:
         inputs, targets, masks = (self._host(x) for x in batch)

@@ -163,9 +163,17 @@ class _RcslBase(_EpochPolicy):
         observations = init_obss
         frozen = hasattr(self.rollout_policy, "sample_init_noise")
         frozen_noise = self.rollout_policy.sample_init_noise(init_obss.shape[0]) if frozen else None
+        # a dynamics that carries recurrent state per trajectory (RNNDynamics) starts it here and is told every step which trajectories
+        # the rows belong to; any other one takes the rows alone
+        stateful = bool(getattr(self.dynamics, "stateful", False))
+        if stateful:
+            self.dynamics.reset_state(init_obss.shape[0])
         for _ in range(rollout_length):
             actions = self.rollout_policy.select_action(observations, frozen_noise)
-            next_observations, rewards, terminals, info = self.dynamics.step(observations, actions)
+            if stateful:
+                next_observations, rewards, terminals, info = self.dynamics.step_state(observations, actions, valid_idxs)
+            else:
+                next_observations, rewards, terminals, info = self.dynamics.step(observations, actions)
             rollout_transitions["obss"].append(observations)
             rollout_transitions["next_obss"].append(next_observations)
             rollout_transitions["actions"].append(actions)
@@ -229,6 +237,9 @@ class _RcslBase(_EpochPolicy):
         # the frozen-noise interface on the device (DiffusionBC): one draw per trajectory; every step the sampler gathers the rows of
         # the live trajectories -- the rows rollout() keeps by thinning its copy
         noise = pol.sample_init_noise(n_traj) if frozen else None
+        stateful = bool(getattr(dyn, "stateful", False))      # (as in rollout(): the recurrent state of the trajectories, by index)
+        if stateful:
+            dyn.reset_state(n_traj)
         with torch.no_grad():
             for _ in range(L):
                 if frozen:
@@ -236,7 +247,7 @@ class _RcslBase(_EpochPolicy):
                 else:
                     act = pol.select_action_device(obs)
                 act = act.to(torch.float32).contiguous()
-                nxt, rew, _ = dyn.step_device(obs, act)
+                nxt, rew, _ = dyn.step_device(obs, act, store.live_index()) if stateful else dyn.step_device(obs, act)
                 alive = torch.empty_like(nxt)
                 n_alive = store.append_step(kind, obs, act, nxt.contiguous(), rew.contiguous(), alive)
                 if n_alive == 0:

@@ -9,7 +9,13 @@ engine's step comes from device events (``orl_rnn_profile``), in windows of thei
 
 ``--runs R [R ...]`` measures the multi-run objects instead: one ``step_runs`` of an R-run engine against R one-run engines stepped one
 after the other (same GPU, same call, same alternating windows and medians), with the device events of the R-run step and of a
-one-run step beside them (``profiles/rnn_throughput_runs.json`` holds R = 1, 2, 4, 8, 16)."""
+one-run step beside them (``profiles/rnn_throughput_runs.json`` holds R = 1, 2, 4, 8, 16).
+
+``--rollout`` measures ONE model step of a rollout of 256 trajectories four ways (same GPU, same call, same alternating windows and
+medians): (a) ``step_device`` on the carried state, (b) the engine's ``forward`` on device tensors at T = 1 (what there was for that
+step before the carried state: no history, so not the same model output), (c) ``step`` on 20-step windows, (d) the torch ``RNNModel``
+in eval mode with ``h_state`` carried; and one ``rollout_device`` of 256 trajectories x 200 steps with an untrained
+``AutoregressivePolicy`` (``profiles/rnn_rollout_throughput.json``)."""
 import argparse
 import json
 import os
@@ -113,18 +119,105 @@ def main_runs(a):
     emit(res, a.out)
 
 
+def main_rollout(a):
+    """--rollout: one model step of 256 trajectories through the carried state against the other ways to make it, and a whole
+    ``rollout_device``"""
+    from offlinerlkit.modules import RcslModule
+    from offlinerlkit.nets import MLP
+    from offlinerlkit.policy import AutoregressivePolicy, RcslPolicy
+    from offlinerlkit.utils.termination_fns import termination_fn_default
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)                                   # noqa: E731
+    act_dim, horizon = IN - OBS, 200
+    torch.manual_seed(0)
+    model = RNNModel(IN, OUT, HID, L, P_DROP)
+    with torch.no_grad():                                                        # small steps: 200 of them stay finite
+        model.output_layer.weight.mul_(0.01)
+        model.output_layer.bias.zero_()
+    init = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    dyn = RNNDynamics(model, torch.optim.Adam(model.parameters(), lr=1e-3), StandardScaler(np.zeros((1, IN), np.float32), np.ones((1, IN), np.float32)),
+                      termination_fn_default)
+    x, _, _ = data(B)
+    obss, acts = x[:, :, :OBS].copy(), x[:, :, OBS:].copy()
+    obs_d, act_d, x1_d = (torch.as_tensor(v, device=dev).contiguous() for v in (obss[:, -1], acts[:, -1], x[:, -1:]))
+    dyn.step(obss, acts)                                                         # binds the engine for 20-step windows
+    dyn.reset_state(B)
+    tm = RNNModel(IN, OUT, HID, L, P_DROP, device="cuda")
+    tm.load_state_dict(init)
+    tm.eval()
+
+    def step_device():
+        for _ in range(a.batches):
+            dyn.step_device(obs_d, act_d)
+        return a.batches
+
+    def forward_t1():
+        for _ in range(a.batches):
+            dyn._eng.forward(x1_d)
+        return a.batches
+
+    def step_windows():
+        for _ in range(a.batches):
+            dyn.step(obss, acts)
+        return a.batches
+
+    @torch.no_grad()
+    def torch_carried():
+        h = None
+        for _ in range(a.batches):
+            pred, h = tm(x1_d, h)
+            pred[:, -1, :-1] + obs_d
+        return a.batches
+
+    runs = {"a_step_device": step_device, "b_engine_forward_T1_device": forward_t1, "c_step_20_step_windows": step_windows,
+            "d_torch_eval_h_state_carried": torch_carried}
+    for fn in runs.values():
+        fn()
+    times = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for k, fn in runs.items():
+            times[k].append(window(fn, sync))
+    res = {"shape": dict(input_dim=IN, output_dim=OUT, hidden=HID, rnn_num_layers=L, rows=B, window_T=T),
+           "device": torch.cuda.get_device_name(0), "steps_per_window": a.batches, "model_step": {k: summary(v) for k, v in times.items()}}
+    ms = res["model_step"]
+    res["ratio_b_over_a"] = ms["b_engine_forward_T1_device"]["median_ms"] / ms["a_step_device"]["median_ms"]
+    res["ratio_c_over_a"] = ms["c_step_20_step_windows"]["median_ms"] / ms["a_step_device"]["median_ms"]
+    res["ratio_d_over_a"] = ms["d_torch_eval_h_state_carried"]["median_ms"] / ms["a_step_device"]["median_ms"]
+    # one whole rollout: 256 trajectories x 200 steps, nothing terminates
+    mod = RcslModule(MLP(input_dim=OBS + 1, hidden_dims=[32, 32], output_dim=act_dim), "cuda:0")
+    pol = RcslPolicy(dyn, AutoregressivePolicy(OBS, act_dim, [200, 200], 1e-3, "cuda:0"), mod, torch.optim.Adam(mod.parameters(), lr=1e-3), "cuda:0")
+    store = _engine.TrajStore(OBS, act_dim, B, B * horizon)
+    init_obs = obss[:, 0].copy()
+
+    def rollout():
+        _, info = pol.rollout_device(init_obs, horizon, store=store)
+        assert info["num_transitions"] == B * horizon and np.isfinite(info["reward_mean"])
+        return 1
+
+    rollout()
+    roll = [window(rollout, sync) for _ in range(a.rounds)]
+    res["rollout_device_256x200"] = summary(roll)
+    res["rollout_device_256x200"]["ms_per_model_step"] = res["rollout_device_256x200"]["median_ms"] / horizon
+    emit(res, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=20, help="optimizer steps per timed window")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--runs", type=int, nargs="+", default=None, metavar="R",
                     help="instead: one step_runs of an R-run object against R one-run objects stepped in turn, for every R given")
+    ap.add_argument("--rollout", action="store_true",
+                    help="instead: one model step through the carried state (step_device) against forward at T = 1, step() on 20-step "
+                         "windows and the torch model with h_state carried, and one rollout_device of 256 x 200")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rnn_throughput.py measures on the GPU: no HIP device visible")
     if a.runs:
         return main_runs(a)
+    if a.rollout:
+        return main_rollout(a)
     dev = torch.device("cuda", 0)
     x, tg, mk = data(a.batches * B)
     sync = lambda: torch.cuda.synchronize(dev)                                   # noqa: E731
