@@ -30,6 +30,12 @@ int Engine::edac_build() {
   taps["xt"] = {W("xt"), Bt, XP};
   taps["qts"] = {W("qt"), (long)Bt * Kc, 1};
   taps["logp_next"] = {W("logp_next"), Bt, 1};
+  // the first step of the diversity sweep: t_0 of every member, the stored first hidden activation (the mask source when no packed bits are
+  // live) and, as a host tap, which launch made t_0 in the last step: {1 = k_edac_t0 / 0 = tiled GEMM with E_MASK, 1 = packed mask bits /
+  // 0 = stored values}; {-1, -1} while no sweep has run (eta = 0)
+  taps["tt0"] = {W("tt0"), (long)B * Kc, cfg.hidden[0]};
+  taps["ch0"] = {W("ch0"), (long)B * Kc, cfg.hidden[0]};
+  host_taps["edac.t0_path"] = {-1.f, -1.f};
   return 0;
 }
 
@@ -100,6 +106,9 @@ int Engine::edac_step() {
       const float* w0 = crit.base + cl.w_off[0] + (long)od * N0;
       const bool vec = cl.ens && (N0 & 3) == 0 && A <= EDAC_T0_AMAX && tt[0].pitch == N0 && ch[0].pitch == N0 && aligned16(w0) && (crit.rs & 3) == 0 && (cl.w_ms[0] & 3) == 0 &&
                        aligned16(tt[0].p) && (tt[0].rs & 3) == 0 && (tt[0].cs & 3) == 0 && aligned16(ch[0].p) && (ch[0].rs & 3) == 0 && (ch[0].cs & 3) == 0;
+      // (test tap: which launch makes t_0 and where it takes the mask from -- linear_fwd's own condition for the tiled launch)
+      const bool live = ch[0].bits && bits_live.count(ch[0].bits);
+      host_taps["edac.t0_path"] = {vec ? 1.f : 0.f, (vec ? live : live && N0 == ch[0].pitch && aligned16(ch[0].p) && (ch[0].pitch & 3) == 0) ? 1.f : 0.f};
       if (vec) {            // A-wide product: one HBM-rate launch instead of a GEMM that is all epilogue
         EdacT0P t; memset(&t, 0, sizeof(t));
         t.gamma = gam.p; t.g_rs = gam.rs; t.g_cs = gam.cs; t.gpitch = gam.pitch;

@@ -29,6 +29,22 @@ int Engine::mcq_build() {
   taps["target_q"] = {W("target_q"), B, 1};
   taps["target_ood"] = {W("target_ood"), B2, 1};
   taps["sampled_actions"] = {W("xto").cols(od), BN2, A};
+  // operands / results of k_vae_latent, k_vae_loss, k_vae_head_bwd, k_clamp_latent, the OOD k_assemble / k_det_action and k_mcq_loss
+  // (both nets stacked: [2][rows]).  Every workspace is its own allocation and no later launch of the step writes one of them.
+  taps["ehead"] = {W("ehead"), B, 2 * Z};
+  taps["vstd"] = {W("vstd"), B, Z};
+  taps["xd"] = {W("xd"), B, DP};
+  taps["m3"] = {W("m3"), B, A};
+  taps["dm3"] = {W("dm3"), B, A};
+  taps["dxd"] = {W("dxd"), B, Z};
+  taps["dehead"] = {W("dehead"), B, 2 * Z};
+  taps["xdo"] = {W("xdo"), BN2, DP};
+  taps["m3o"] = {W("m3o"), BN2, A};
+  taps["qt"] = {W("qt"), 2L * B, 1};
+  taps["qto"] = {W("qto"), 2L * BN2, 1};
+  taps["logp_next"] = {W("logp_next"), B, 1};
+  taps["q"] = {W("q"), 6L * B, 1};
+  taps["dq"] = {W("dq"), 6L * B, 1};
   return 0;
 }
 

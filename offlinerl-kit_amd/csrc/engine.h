@@ -171,6 +171,7 @@ struct Engine {
   std::set<const void*> bits_live;   // mask-bit buffers whose producer launch emitted them this step (decided on the host)
   struct Tap { Mat m; long rows; int cols; };
   std::map<std::string, Tap> taps;
+  std::map<std::string, std::vector<float>> host_taps;   // host-side decisions of the last step (same values for every run), read like a tap
   struct NoiseSlot { std::string name; int kind; int rows; int cols = 0; };      // cols 0 = act_dim
   std::vector<NoiseSlot> noise_slots;
   // k_prepare job list (algorithms that use it skip the separate gather / noise / assemble launches)

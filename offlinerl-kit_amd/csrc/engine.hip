@@ -2454,9 +2454,15 @@ int64_t orl_step_count(orl_engine* h) { return (int64_t)h->e.step_host; }
 
 int64_t orl_debug_read(orl_engine* h, int run, const char* name, float* host, int64_t cap) {
   Engine& e = h->e;
+  if (run < 0 || run >= e.R) { fail("bad run"); return -1; }
+  auto ht = e.host_taps.find(name);
+  if (ht != e.host_taps.end()) {
+    if (cap < (int64_t)ht->second.size()) { fail("tap buffer too small"); return -1; }
+    std::copy(ht->second.begin(), ht->second.end(), host);
+    return (int64_t)ht->second.size();
+  }
   auto it = e.taps.find(name);
   if (it == e.taps.end()) { fail(std::string("unknown tap ") + name); return -1; }
-  if (run < 0 || run >= e.R) { fail("bad run"); return -1; }
   const Engine::Tap& t = it->second;
   const int64_t n = t.rows * t.cols;
   if (cap < n) { fail("tap buffer too small"); return -1; }

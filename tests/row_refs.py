@@ -1,5 +1,6 @@
 """Self-bounding float64 restatements of the engine's row kernels (csrc/kernels.h: sampling, loss, gradient-seed, head-backward and
-optimizer kernels), written from the formulas of the reference that the kernel comments cite -- not from the kernel code.
+optimizer kernels; at the end of the file MCQ's VAE / critic-loss kernels and EDAC's gradient-diversity kernels), written from the formulas
+of the reference that the kernel comments cite -- not from the kernel code.
 
 ``BV`` is a float64 array that carries, element by element, a first-order bound on what fp32 arithmetic may lose when it evaluates
 the same expression on the same fp32 operands (u = 2^-24, the unit roundoff of fp32):
@@ -433,3 +434,95 @@ def adam(p, m, v, g, lr, b1, b2, eps, t, tau=None, target=None, torch_scalars=Fa
         return p, m, v
     tau = BV.exact(tau)
     return p, m, v, BV.exact(target) * (1.0 - tau) + p * tau
+
+
+# =====================================================================================================================================
+# MCQ (policy/model_free/mcq.py:48-126; behaviour policy nets/vae.py:36-58) and EDAC's gradient-diversity term (edac.py:136-149)
+# =====================================================================================================================================
+VAE_LS_MIN, VAE_LS_MAX, VAE_Z_CLIP = -4.0, 15.0, 0.5
+
+
+def vae_latent(ehead, eps):
+    """VAE.forward (vae.py:44-50): ehead [B, 2Z] = (mean | log-std), log-std clamped to [-4, 15] (on the fp32 operand: exact),
+    std = exp(log-std), z = mean + std eps.  Returns (std [B, Z], z [B, Z])."""
+    ehead = np.asarray(ehead, np.float32)
+    Z = ehead.shape[1] // 2
+    std = exp(clip(ehead[:, Z:], VAE_LS_MIN, VAE_LS_MAX))
+    return std, BV.exact(ehead[:, :Z]) + std * BV.exact(eps)
+
+
+def vae_loss(m3, act, ehead, std, max_action, B, A, Z):
+    """mcq.py:53-56 on vae.py:51-53: u = max_action tanh(m3) ; L = mean((u - a)^2) - 0.5 mean(1 + log(std^2) - mean^2 - std^2) ;
+    dL/dm3 = 2 (u - a) / (B A) max_action (1 - tanh^2).  ``std``: the fp32 values the latent kernel stored.  Both means are a
+    256-strided sum over all B A (B Z) elements.  Returns (L, dm3 [B, A])."""
+    th = tanh(BV.exact(m3))
+    ma = BV.exact(max_action)
+    d = ma * th - BV.exact(act)
+    recon = sum_((d * d).reshape(-1)) / float(B * A)
+    mean, sd = BV.exact(np.asarray(ehead, np.float32)[:, :Z]), BV.exact(std)
+    kl = sum_((((1.0 + log(sd * sd)) - mean * mean) - sd * sd).reshape(-1)) / float(B * Z)
+    dm3 = 2.0 * d / float(B * A) * ma * (1.0 - th * th)
+    return recon - 0.5 * kl, dm3
+
+
+def vae_head_bwd(dz, ehead, std, eps, B, Z):
+    """autograd of vae.py:44-50 + the KL term of mcq.py:54 for dL/dz = ``dz``: d mean = dz + mean / (B Z) ;
+    d log-std = dz std eps + (std^2 - 1) / (B Z), passed by the clamp where -4 <= raw <= 15 (BOTH ends included: torch.clamp's
+    backward) and exactly 0 elsewhere.  Returns dehead [B, 2Z]."""
+    ehead = np.asarray(ehead, np.float32)
+    mean, lsr, sd = BV.exact(ehead[:, :Z]), ehead[:, Z:], BV.exact(std)
+    dz = BV.exact(dz)
+    dmean = dz + mean / float(B * Z)
+    dls = dz * sd * BV.exact(eps) + (sd * sd - 1.0) / float(B * Z)
+    dls = where((lsr >= f32(VAE_LS_MIN)) & (lsr <= f32(VAE_LS_MAX)), dls, 0.0)
+    return BV(np.concatenate([dmean.v, dls.v], axis=1), np.concatenate([dmean.e, dls.e], axis=1))
+
+
+def clamp_latent(z):
+    """VAE.decode (vae.py:57-58): the drawn latent clamped to [-0.5, 0.5] -- exact"""
+    return clip(z, -VAE_Z_CLIP, VAE_Z_CLIP)
+
+
+def mcq_loss(q, qt, qto, rew, term, logp_next, alpha, gamma, lam, B, N, stored=None):
+    """mcq.py:62-94.  q [2, 3B] fp32: the critics on the B data rows, then on the 2B rows ([s; s'], pi([s; s'])) ; qt [2, B]: the
+    target critics on (s', a') ; qto [2, 2B N]: the target critics on the N decoded actions of each of the 2B states.
+        y_in = r + gamma (1 - d) (min_c qt_c - alpha logp') ;  y_ood[j] = min_c max_n qto_c[j N + n]
+        L_c = lam mean_B((q_c[:B] - y_in)^2) + (1 - lam) mean_2B((q_c[B:] - y_ood)^2) ;  dq_c accordingly.
+    ``stored``: the fp32 (target_q, target_ood) the kernel stored -- the losses and dq are then taken at them, as the kernel does.
+    Returns (y_in [B], y_ood [2B], dq [2, 3B], L [2])."""
+    q, qt, qto = np.asarray(q, np.float32), np.asarray(qt, np.float32), np.asarray(qto, np.float32)
+    nq = BV.exact(qt.min(axis=0)) - BV.exact(alpha) * BV.exact(logp_next)
+    y_in = BV.exact(rew) + BV.exact(gamma) * (1.0 - BV.exact(term)) * nq
+    y_ood = BV.exact(qto.reshape(2, 2 * B, N).max(axis=2).min(axis=0))
+    ti, to = (y_in, y_ood) if stored is None else (BV.exact(stored[0]), BV.exact(stored[1]))
+    lam = BV.exact(lam)
+    d_in, d_ood = BV.exact(q[:, :B]) - ti.reshape(1, -1), BV.exact(q[:, B:]) - to.reshape(1, -1)
+    loss = lam * (sum_(d_in * d_in, axis=1) / float(B)) + (1.0 - lam) * (sum_(d_ood * d_ood, axis=1) / float(2 * B))
+    dq_in, dq_ood = lam * 2.0 * d_in / float(B), (1.0 - lam) * 2.0 * d_ood / float(2 * B)
+    return y_in, y_ood, BV(np.concatenate([dq_in.v, dq_ood.v], axis=1), np.concatenate([dq_in.e, dq_ood.e], axis=1)), loss
+
+
+def edac_gamma(g, eta, K, B):
+    """edac.py:136-149 for g [K, B, A] = dQ_k / da: g^ = g / (|g| + 1e-10) ; L_g = mean_b sum_{i != j} <g^_i, g^_j> / (K - 1)
+    (= |sum_k g^_k|^2 - sum_k |g^_k|^2 per row) ; gamma = d(eta L_g) / dg, whose projection term divides by |g| -- guarded where |g| is
+    exactly 0 (autograd of sqrt at 0 would be NaN; the term it multiplies is 0 there).  Sums over the actions and the members are one
+    thread's; the batch mean is a 256-strided sum.  Returns (gamma [K, B, A], eta L_g)."""
+    g = BV.exact(g)
+    A = g.shape[2]
+    nrm = sqrt(sum_(g * g, axis=2, sequential=True)).reshape(K, B, 1)
+    nk = nrm + 1e-10
+    gh = g / nk
+    S = sum_(gh, axis=0, sequential=True).reshape(1, B, A)
+    gram_off = sum_((S * S).reshape(B, A), axis=1, sequential=True) - sum_(sum_(gh * gh, axis=2, sequential=True), axis=0, sequential=True)
+    lg = BV.exact(eta) * (sum_(gram_off) / float(B)) / float(K - 1)
+    c = (BV.exact(eta) * 2.0 / float((K - 1) * B)) * (S - gh)
+    safe = where(nrm.v > 0, nrm, 1.0)
+    gc = sum_(g * c, axis=2, sequential=True).reshape(K, B, 1)
+    return c / nk - g * (gc / (nk * nk * safe)), lg
+
+
+def edac_t0(gamma, w0_action_rows, mask):
+    """first step of the adjoint sweep (oracle/edac.py: t_0 = (gamma W_0[action rows]) (.) m_0): gamma [K, B, A], the action rows of the
+    ensemble's first layer [K, A, N0], mask [K, B, N0] = 1[h_0 > 0].  An A-term sum by one thread per element; exactly 0 where the mask is."""
+    prod = BV.exact(np.asarray(gamma, np.float32)[:, :, :, None]) * BV.exact(np.asarray(w0_action_rows, np.float32)[:, None, :, :])
+    return where(np.asarray(mask, bool), sum_(prod, axis=2, sequential=True), 0.0)

@@ -68,19 +68,21 @@ def holds(got, ref, key, tag):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # engines at ad-hoc shapes
 # ---------------------------------------------------------------------------------------------------------------------------------
-NETS = {"cql": tc.NETS, **ta.NET_IDS}
+NETS = {"cql": tc.NETS, **ta.NET_IDS, "mcq": dict(tc.NETS, vae_enc=7, vae_dec=8)}
 
 
 class Ctx:
     pass
 
 
-def _state(algo, rng, od, A, hid, K):
+def _state(algo, rng, od, A, hid, K, Z=None, vae_hidden=None):
     st = {}
-    if algo == "cql":
+    if algo in ("cql", "mcq"):
         st["actor"] = synth.make_tanh_actor(rng, od, A, hid)
         st["critic1"], st["critic2"] = synth.make_critic(rng, od + A, hid), synth.make_critic(rng, od + A, hid)
         st["critic1_old"], st["critic2_old"] = synth._perturbed(rng, st["critic1"]), synth._perturbed(rng, st["critic2"])
+        if algo == "mcq":        # one state_dict (e1, e2, mean, log_std | d1, d2, d3): the engine's encoder and decoder nets each take their tensors
+            st["vae_enc"] = st["vae_dec"] = st["behavior_policy"] = synth.make_vae(rng, od, A, vae_hidden, Z)
     elif algo == "edac":
         st["actor"] = synth.make_tanh_actor(rng, od, A, hid)
         c = ta._strip_saved(synth.make_ensemble_critic(rng, od + A, hid, K))
@@ -100,18 +102,18 @@ def _state(algo, rng, od, A, hid, K):
     return st
 
 
-def make(algo, B=32, A=3, od=5, R=1, precision=0, hidden=(32, 32), seed=0, N=2, K=4, env=None, monkeypatch=None, mutate=None,
-         log_alpha=-0.3, cql_log_alpha=0.2, **over):
-    from offlinerlkit import _engine
+def inputs(algo, B=32, A=3, od=5, R=1, hidden=(32, 32), seed=0, N=2, K=4, Z=6, vae_hidden=24, mutate=None, **over):
+    """nets, batch and noise of every run of a case (host arrays only: the CPU tests run the oracle on the same inputs)"""
     c = Ctx()
     c.algo, c.B, c.A, c.od, c.R, c.N, c.K, c.hidden = algo, B, A, od, R, N, (K if algo == "edac" else 2), list(hidden)
+    c.Z, c.vae_hidden = Z, vae_hidden
     c.XP = (od + A + 3) // 4 * 4
     c.maxq = bool(over.get("max_q_backup", 0))
     c.rep = (N if algo == "cql" else 10) if c.maxq else 1
     c.sts, c.batches, c.noises = [], [], []
     for r in range(R):
         rng = np.random.RandomState(7919 * seed + 31 * r + B + 64 * A)
-        c.sts.append(_state(algo, rng, od, A, c.hidden, K))
+        c.sts.append(_state(algo, rng, od, A, c.hidden, K, Z, vae_hidden))
         c.batches.append(synth.make_batch(rng, B, od, A))
         if algo == "cql":
             c.noises.append(synth.make_cql_noise(rng, B, N, A, max_q_backup=c.maxq))
@@ -119,15 +121,27 @@ def make(algo, B=32, A=3, od=5, R=1, precision=0, hidden=(32, 32), seed=0, N=2, 
             c.noises.append(synth.make_sac_noise(rng, B, A, rows_next=B * c.rep))
         elif algo == "td3bc":
             c.noises.append(synth.make_td3_noise(rng, B, A))
+        elif algo == "mcq":      # the reference's draw order (oracle/mcq.py)
+            c.noises.append({k: rng.standard_normal(s).astype(f32) for k, s in (("eps_vae", (B, Z)), ("eps_next", (B, A)), ("z_ood", (2 * B * N, Z)),
+                                                                                ("eps_ood", (2 * B, A)), ("eps_actor", (B, A)))})
         else:
             c.noises.append({})
     if mutate:
         mutate(c)
+    return c
+
+
+def make(algo, B=32, A=3, od=5, R=1, precision=0, hidden=(32, 32), seed=0, N=2, K=4, env=None, monkeypatch=None, mutate=None,
+         log_alpha=-0.3, cql_log_alpha=0.2, Z=6, vae_hidden=24, **over):
+    from offlinerlkit import _engine
+    c = inputs(algo, B=B, A=A, od=od, R=R, hidden=hidden, seed=seed, N=N, K=K, Z=Z, vae_hidden=vae_hidden, mutate=mutate, **over)
     cfg = dict(obs_dim=od, act_dim=A, hidden=c.hidden, batch_size=B, n_runs=R, precision=precision)
     if algo == "cql":
         cfg.update(num_repeat_actions=N, target_entropy=-float(A))
     elif algo == "edac":
         cfg.update(num_critics=K, eta=0.0, target_entropy=-float(A))
+    elif algo == "mcq":
+        cfg.update(num_repeat_actions=N, vae_latent=Z, vae_hidden=vae_hidden, target_entropy=-float(A))
     cfg.update(over)
     for k, v in (env or {}).items():
         monkeypatch.setenv(k, v)
@@ -140,7 +154,7 @@ def make(algo, B=32, A=3, od=5, R=1, precision=0, hidden=(32, 32), seed=0, N=2, 
     for r in range(R):
         for nm, nid in NETS[algo].items():
             c.eng.set_net(r, nid, c.sts[r][nm])
-        if algo in ("cql", "edac"):
+        if algo in ("cql", "edac", "mcq"):
             c.eng.set_scalar(r, _engine.SCALAR_LOG_ALPHA, log_alpha)
         if algo == "cql":
             c.eng.set_scalar(r, _engine.SCALAR_CQL_LOG_ALPHA, cql_log_alpha)
@@ -148,7 +162,8 @@ def make(algo, B=32, A=3, od=5, R=1, precision=0, hidden=(32, 32), seed=0, N=2, 
     return c
 
 
-NOISE_KEYS = {"cql": ("eps_actor", "eps_next", "u_rand", "eps_pi", "eps_next_pi"), "edac": ("eps_actor", "eps_next"), "td3bc": ("eps_target",), "iql": ()}
+NOISE_KEYS = {"cql": ("eps_actor", "eps_next", "u_rand", "eps_pi", "eps_next_pi"), "edac": ("eps_actor", "eps_next"), "td3bc": ("eps_target",), "iql": (),
+              "mcq": ("eps_vae", "eps_next", "z_ood", "eps_ood", "eps_actor")}
 SC = ("LOG_ALPHA", "LOG_ALPHA_M", "LOG_ALPHA_V", "CQL_LOG_ALPHA", "CQL_LOG_ALPHA_M", "CQL_LOG_ALPHA_V", "ALPHA", "LAST_ACTOR_LOSS")
 
 
