@@ -380,6 +380,21 @@ int orl_engine_set_next_samples(orl_engine* e, const float* samples, int on_devi
  * the actor's draws (NULL: device Philox); penalty_out [n_runs][batch]; both are device pointers when on_device.  The "penalty" and
  * "lcb_q" taps hold the result afterwards. */
 int orl_engine_lcb_penalty(orl_engine* e, const float* eps_lcb, float* penalty_out, int on_device);
+/* RAMBO's advantage (policy/model_based/rambo.py:164-181) on an ORL_ALGO_SAC engine, forward only and run-batched: obs / next_obs
+ * [n_runs][rows][obs_dim], act [n_runs][rows][act_dim], reward [n_runs][rows] (device pointers when on_device) ->
+ *   a' = tanh(mu(s')), logp' = TanhNormal log-prob at the mode (log sigma clamped to [-5, 2]), q' = min(Q1, Q2)(s', a') on the LIVE
+ *   critics [- alpha logp' when include_ent; alpha = the device temperature when auto_alpha, the configured one otherwise],
+ *   value = r + (1 - term) gamma q' with term = the termination test term_kind (the codes of orl_buffer_append_rollout) on next_obs,
+ *   raw = value - min(Q1, Q2)(s, a), advantage = (raw - mean) / (std + 1e-6) with the unbiased std over the rows of the run.
+ * advantage [n_runs][rows] and stats [n_runs][2] = {mean of the normalised advantage, raw std} (device pointers when on_device; either
+ * may be NULL).  One assemble launch ([s | a] and [s' | a'] are ONE 2 rows-row critic operand), the actor pass, one pass of both
+ * critics, one reduction launch of one workgroup per run: fixed summation order, no float atomics.  Workspaces are sized for `rows`
+ * at the first call and regrown when rows grows.  Parameters, optimizer state, the step counter and the noise streams of orl_learn_n
+ * are not touched.  Taps afterwards ([rows] each): "adv.q_next", "adv.q_base", "adv.logp_next", "adv.term", "adv.raw", "adv.norm".
+ * Refused: any other engine, rows < 2 (the unbiased std is NaN) or > 2^22, an unknown term_kind or one that reads an observation
+ * column the engine does not have.  Synchronises the engine stream before returning. */
+int orl_engine_adv_advantage(orl_engine* e, const float* obs, const float* act, const float* next_obs, const float* reward,
+                             int32_t rows, int32_t term_kind, int32_t include_ent, float* advantage, float* stats, int on_device);
 /* Sticky per-run health flags (ORL_HEALTH_* bits), flags_out: host uint32[n_runs] (may be NULL); returns the OR over the runs, < 0 on
  * error.  orl_step / orl_learn_n update the flags from what they already read back (metrics; one word per run that k_adam raises on a
  * non-finite gradient) and, at precision 1, scan the step's MFMA operands for the fp16-plane range when a run turned non-finite.
@@ -655,7 +670,8 @@ int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n_floats)
 int64_t orl_dyn_debug_read(orl_dynamics* d, int run, const char* name, float* host, int64_t cap);
 
 /* -- RAMBO's adversarial model update (policy/model_based/rambo.py:129-207) on an orl_dynamics ------------------------------------
- * One update of dynamics_step_and_forward is two calls; the caller computes the advantage (actor and critics) between them.
+ * One update of dynamics_step_and_forward is two calls; the caller computes the advantage (actor and critics) between them
+ * (orl_engine_adv_advantage does, on a SAC engine; orl_rambo_update_dynamics runs whole updates of many steps without the host).
  * The optimizer (dynamics_adv_optim) has its own exp_avg / exp_avg_sq / step count: orl_dyn_learn_epoch's Adam state is never touched,
  * and the forward's activations, workspaces and kept sample belong to these calls alone (orl_dyn_step / validate / learn_epoch
  * between the two calls leave them alone).  fp32, run-batched like every orl_dyn_* call. */
@@ -682,6 +698,31 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
 /* the adversarial optimizer's state, as orl_dyn_adam_get / orl_dyn_adam_set */
 int orl_dynadv_adam_get(orl_dynamics* d, int run, float* exp_avg, float* exp_avg_sq, int64_t n_floats, int64_t* step);
 int orl_dynadv_adam_set(orl_dynamics* d, int run, const float* exp_avg, const float* exp_avg_sq, int64_t n_floats, int64_t step);
+
+/* RAMBO's update_dynamics (rambo.py:95-127) without a host round trip per step.  A segment is one draw of `rows` initial observations
+ * from `real` followed by segment_steps[s] steps; a step is: a ~ pi(. | obs) by the engine's actor on the unscaled observations
+ * (noise from a Philox stream of this entry point alone), a fresh draw of `rows` dataset rows, the adversarial forward, the advantage
+ * (orl_engine_adv_advantage's pass), the adversarial update, obs <- next_obs (all rows carry on, terminated or not). */
+typedef struct orl_rambo_loop {
+  int32_t rows;                 /* adv_rollout_batch_size: rollout rows = dataset rows per step, as given to orl_dynadv_configure */
+  int32_t term_kind;            /* the codes of orl_buffer_append_rollout */
+  int32_t include_ent;
+  int32_t n_segments;
+  const int32_t* segment_steps; /* host [n_segments], each >= 1 */
+} orl_rambo_loop;
+/* Every launch of the loop goes to the engine's stream (the dynamics' own stream is waited for through an event first), the host
+ * synchronises once at the end.  The five logged values (all_loss, sl_loss, adv_loss, adv_advantage, adv_log_prob) are summed in a
+ * device array, read once and divided by the step count into metrics_mean[5]; elapsed_ms (optional) is the HIP-event time of the loop.
+ * Step i draws from the dynamics what orl_dynadv_forward(noise = NULL, model_idx = NULL) at the same call counter draws and advances
+ * that counter; a buffer draw is orl_buffer_sample(idx = NULL, seed = the engine's seed) at the buffer's draw counter and advances it;
+ * the adversarial optimizer's step count advances by the number of steps.  A non-finite value raises the engine's
+ * ORL_HEALTH_NONFINITE_LOSS like orl_learn_n (return code ORL_RC_UNHEALTHY).  Taps of the LAST step's unscaled rows on the engine:
+ * "loop.obs", "loop.act", "loop.sl_obs", "loop.sl_act", "loop.sl_next_obs", "loop.sl_rew", "loop.next_obs", "loop.reward"; the
+ * "adv.*" taps of both objects hold the last step's.  Refused before anything is launched or any counter moves: an engine that is
+ * not ORL_ALGO_SAC, n_runs != 1 on either side, no orl_dynadv_configure, rows that differ from the configured row counts, different
+ * devices or dims, an empty buffer, an unknown term_kind (or one that reads a missing observation column), rows < 2, no steps. */
+int orl_rambo_update_dynamics(orl_engine* e, orl_dynamics* d, orl_buffer* real, const orl_rambo_loop* a, float* metrics_mean /*[5]*/,
+                              float* elapsed_ms);
 
 /* the int32 indices of the live trajectories of the current rollout, in row order, widened to int64 into the DEVICE array
  * out_device (room for the live count, which is returned; < 0 on error).  Live indices ascend and are never compacted, so a per-trajectory

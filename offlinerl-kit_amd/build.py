@@ -20,7 +20,7 @@ GEMM_H = ["gemm.h", "gemm_kernel.h"]
 WS_H = ["gemm.h", "ws_gemm.h", "ws_device.h"]
 # translation unit -> headers it depends on
 UNITS = {
-    "engine.hip": ["engine.h", "devobj.h", "gemm.h", "ws_gemm.h", "small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "kernels.h", "rng.h", "algo_cql.inc", "algo_iql.inc", "algo_td3bc.inc", "algo_edac.inc", "algo_sac.inc", "algo_mcq.inc", "algo_mobile.inc", "algo_rcsl.inc", "algo_rcsl_gauss.inc", "algo_autoreg.inc", ABI],
+    "engine.hip": ["engine.h", "devobj.h", "gemm.h", "ws_gemm.h", "small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "kernels.h", "rng.h", "algo_cql.inc", "algo_iql.inc", "algo_td3bc.inc", "algo_edac.inc", "algo_sac.inc", "algo_mcq.inc", "algo_mobile.inc", "algo_rcsl.inc", "algo_rcsl_gauss.inc", "algo_autoreg.inc", "algo_rambo.inc", ABI],
     "gemm_inst_fwd.hip": GEMM_H,
     "gemm_inst_plain.hip": GEMM_H,
     "gemm_inst_rank1.hip": GEMM_H,

@@ -19,6 +19,23 @@ void set_error(const std::string& msg);   // engine.hip: the text orl_last_error
 int fail(const std::string& msg);         // set_error, returns -1
 void buffer_view(const orl_buffer* b, int* dev, int* od, int* ad, int* OP, int* AP, long* n, const float** obs, const float** act);
 
+// The adversarial pair of an orl_dynamics (dynamics.hip) as the RAMBO device loop of engine.hip drives it: the launches of
+// orl_dynadv_forward / orl_dynadv_update on device arrays, without their staging, synchronisation and metric read-back.  Between
+// loop_begin and loop_end the object's launches go to `loop_stream` (the engine's: one stream orders the whole loop); begin uploads
+// the optimizer's step counts, update_enqueue(step) is Adam step t0 + step + 1, end adds the steps done to the host's count.
+struct DynAdvInfo {
+  int dev, R, od, ad, Ba, Bs;
+  bool on;                 // orl_dynadv_configure has run
+  hipStream_t stream;      // the object's own stream
+  const float* metrics;    // device [R][4] of the last update: all_loss, sl_loss, adv_loss, mean log_prob
+};
+int dynadv_info(orl_dynamics* d, DynAdvInfo* out);
+int dynadv_loop_begin(orl_dynamics* d, hipStream_t loop_stream, hipStream_t* own);
+int dynadv_forward_enqueue(orl_dynamics* d, const float* obs, const float* act, const float* sl_obs, const float* sl_act,
+                           const float* sl_next_obs, const float* sl_rew, float* next_obs, float* reward);
+int dynadv_update_enqueue(orl_dynamics* d, const float* advantage, int step);
+void dynadv_loop_end(orl_dynamics* d, hipStream_t own, long steps_done);
+
 #define ORL_HIP(expr)                                                                            \
   do {                                                                                           \
     hipError_t _e = (expr);                                                                      \

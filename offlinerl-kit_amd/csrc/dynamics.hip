@@ -399,6 +399,8 @@ __global__ __launch_bounds__(256) void k_dyn_sample_next(DynSampleNextP p) {
 //             the supervised target), L x E_BIAS_SWISH + E_BIAS with the pre-activations kept, k_dyn_adv_sample
 //   update    k_dyn_adv_head (mixture log-prob + policy-gradient term on the rollout rows, the Gaussian NLL on the dataset rows),
 //             k_dyn_adv_reduce, ONE backward over the Ba + Bs rows, k_dyn_adam on the adversarial optimizer's state, k_dyn_adv_metrics
+// The launches of either call are one host function each (dynadv_forward_launches / dynadv_update_launches): the public entries add
+// staging, the synchronise and the metric read-back, the RAMBO device loop of engine.hip (orl::dynadv_*_enqueue, devobj.h) adds nothing
 
 // rows [0, Ba): scaler(concat(obs, act)), obs kept for the head; rows [Ba, Ba + Bs): scaler(concat(sl_obs, sl_act)) and the target
 // T[r][j] = [sl_next_obs - sl_obs, sl_rew]
@@ -1353,23 +1355,14 @@ int orl_dynadv_configure(orl_dynamics* d, float lr, float beta1, float beta2, fl
   return 0;
 }
 
-int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, const float* sl_obs, const float* sl_act,
-                       const float* sl_next_obs, const float* sl_rew, int on_device, const float* noise, const int64_t* model_idx,
-                       float* next_obs, float* reward, int32_t* midx_out) {
-  if (!d || !obs || !act || !sl_obs || !sl_act || !sl_next_obs || !sl_rew || !next_obs || !reward)
-    return fail("orl_dynadv_forward: bad arguments");
-  if (!d->adv_on) return fail("orl_dynadv_forward: orl_dynadv_configure first");
+// the launches of a forward on device arrays: input, ensemble forward, sample.  Draws at the call counter, which it advances.  No
+// host synchronisation: orl_dynadv_forward and the RAMBO device loop (orl::dynadv_forward_enqueue) share it
+static int dynadv_forward_launches(orl_dynamics* d, const float* obs, const float* act, const float* sl_obs, const float* sl_act,
+                                   const float* sl_next_obs, const float* sl_rew, const float* noise, const int* midx, float* next_obs,
+                                   float* reward, int* midx_out, const char* who) {
   const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
   const size_t Ba = d->aBa, Bs = d->aBs, N = Ba + Bs;
   const DynWs& w = d->aw;
-  d->adv_pending = false;
-  if (stage_in(d->stream, obs, d->aInObs, R * Ba * od, on_device) || stage_in(d->stream, act, d->aInAct, R * Ba * ad, on_device) ||
-      stage_in(d->stream, sl_obs, d->aSlObs, R * Bs * od, on_device) || stage_in(d->stream, sl_act, d->aSlAct, R * Bs * ad, on_device) ||
-      stage_in(d->stream, sl_next_obs, d->aSlNext, R * Bs * od, on_device) || stage_in(d->stream, sl_rew, d->aSlRew, R * Bs, on_device) ||
-      stage_in(d->stream, noise, d->aNoise, R * K * Ba * D, on_device))
-    return -1;
-  std::vector<int> mi;
-  if (model_idx && dyn_upload_midx(d, model_idx, (long)(R * Ba), mi, d->aMidx, "orl_dynadv_forward")) return -1;
   const int p0 = d->pitch[0], po = d->pitch[d->L + 1];
   DEV_LAUNCH(d->stream, k_dyn_adv_input, dim3((unsigned)((N + 255) / 256), R), dim3(256), 0, obs, act, sl_obs, sl_act, sl_next_obs,
               sl_rew, (int)Ba, (int)Bs, od, ad, (const float*)d->mu, (const float*)d->sd, w.X, p0, d->aT, D, d->aObs);
@@ -1379,16 +1372,39 @@ int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, cons
   s.OUT = w.OUT; s.op = po;
   s.obs = d->aObs; s.Ba = (int)Ba; s.N = (int)N; s.od = od; s.D = D; s.K = K;
   s.params = d->params; s.P = d->P; s.off_max = d->off_max; s.off_min = d->off_min;
-  s.noise = noise; s.midx = model_idx ? d->aMidx : nullptr;
+  s.noise = noise; s.midx = midx;
   s.elites = d->elites_d;
-  if ((s.n_elites = dyn_n_elites(d, "orl_dynadv_forward")) < 0) return -1;
+  if ((s.n_elites = dyn_n_elites(d, who)) < 0) return -1;
   s.seed = d->c.seed ^ 0x9E3779B97F4A7C15ull; s.call = d->adv_calls++;
-  s.next_obs = stage_dst(next_obs, d->aNext, on_device);
-  s.reward = stage_dst(reward, d->aRew, on_device);
+  s.next_obs = next_obs;
+  s.reward = reward;
   s.S = d->aS;
-  s.midx_out = stage_dst((int*)midx_out, d->aMidxOut, on_device);
+  s.midx_out = midx_out;
   const long ns = Ba * ((D + 3) / 4);
   DEV_LAUNCH(d->stream, k_dyn_adv_sample, dim3((unsigned)((ns + 255) / 256), R), dim3(256), 0, s);
+  return 0;
+}
+
+int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, const float* sl_obs, const float* sl_act,
+                       const float* sl_next_obs, const float* sl_rew, int on_device, const float* noise, const int64_t* model_idx,
+                       float* next_obs, float* reward, int32_t* midx_out) {
+  if (!d || !obs || !act || !sl_obs || !sl_act || !sl_next_obs || !sl_rew || !next_obs || !reward)
+    return fail("orl_dynadv_forward: bad arguments");
+  if (!d->adv_on) return fail("orl_dynadv_forward: orl_dynadv_configure first");
+  const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
+  const size_t Ba = d->aBa, Bs = d->aBs;
+  d->adv_pending = false;
+  if (stage_in(d->stream, obs, d->aInObs, R * Ba * od, on_device) || stage_in(d->stream, act, d->aInAct, R * Ba * ad, on_device) ||
+      stage_in(d->stream, sl_obs, d->aSlObs, R * Bs * od, on_device) || stage_in(d->stream, sl_act, d->aSlAct, R * Bs * ad, on_device) ||
+      stage_in(d->stream, sl_next_obs, d->aSlNext, R * Bs * od, on_device) || stage_in(d->stream, sl_rew, d->aSlRew, R * Bs, on_device) ||
+      stage_in(d->stream, noise, d->aNoise, R * K * Ba * D, on_device))
+    return -1;
+  std::vector<int> mi;
+  if (model_idx && dyn_upload_midx(d, model_idx, (long)(R * Ba), mi, d->aMidx, "orl_dynadv_forward")) return -1;
+  if (dynadv_forward_launches(d, obs, act, sl_obs, sl_act, sl_next_obs, sl_rew, noise, model_idx ? d->aMidx : nullptr,
+                              stage_dst(next_obs, d->aNext, on_device), stage_dst(reward, d->aRew, on_device),
+                              stage_dst((int*)midx_out, d->aMidxOut, on_device), "orl_dynadv_forward"))
+    return -1;
   if (stage_out(d->stream, next_obs, d->aNext, R * Ba * od, on_device) || stage_out(d->stream, reward, d->aRew, R * Ba, on_device) ||
       stage_out(d->stream, (int*)midx_out, d->aMidxOut, R * Ba, on_device))
     return -1;
@@ -1398,16 +1414,12 @@ int orl_dynadv_forward(orl_dynamics* d, const float* obs, const float* act, cons
   return 0;
 }
 
-int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, const int32_t* active, float* metrics_out) {
-  if (!d || !advantage) return fail("orl_dynadv_update: bad arguments");
-  if (!d->adv_on || !d->adv_pending) return fail("orl_dynadv_update: no pending forward (orl_dynadv_forward first; one update per forward)");
+// the launches of an update on a device advantage: head, reduce, ONE backward over the Ba + Bs rows, Adam step t0 + batch + 1 of the
+// adversarial optimizer, metrics into aMetrics.  The run state (active flags, t0) has been uploaded.  No host synchronisation
+static int dynadv_update_launches(orl_dynamics* d, const float* advantage, int batch, const char* who) {
   const int R = d->R, K = d->K, D = d->D;
   const long Ba = d->aBa, Bs = d->aBs, N = Ba + Bs;
   const DynWs& w = d->aw;
-  d->adv_pending = false;
-  std::vector<int> act;
-  if (dyn_upload_run_state(d, active, d->adv_tstep, act, true)) return -1;
-  if (stage_in(d->stream, advantage, d->aAdv, (size_t)R * Ba, on_device)) return -1;
   DynAdvHeadP h;
   memset(&h, 0, sizeof(h));
   h.OUT = w.OUT; h.dOUT = w.dOUT; h.op = d->pitch[d->L + 1];
@@ -1415,12 +1427,12 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
   h.lterm = w.lterm; h.gmax = w.gmax; h.gmin = w.gmin; h.rowlp = d->aRowlp;
   h.params = d->params; h.P = d->P; h.off_max = d->off_max; h.off_min = d->off_min;
   h.elites = d->elites_d;
-  if ((h.n_elites = dyn_n_elites(d, "orl_dynadv_update")) < 0) return -1;
+  if ((h.n_elites = dyn_n_elites(d, who)) < 0) return -1;
   h.K = K; h.D = D; h.od = d->od; h.Ba = (int)Ba; h.Bs = (int)Bs;
   h.adv_weight = d->adv_weight;
   const size_t per_wave = sizeof(double) * ((size_t)K * D + 64);
   h.wpb = (int)std::max<size_t>(1, std::min<size_t>(4, (32 * 1024) / per_wave));
-  if (per_wave > 48 * 1024) return fail("orl_dynadv_update: num_ensemble * (obs_dim + 1) is too large for the head's LDS");
+  if (per_wave > 48 * 1024) return fail(std::string(who) + ": num_ensemble * (obs_dim + 1) is too large for the head's LDS");
   DEV_LAUNCH(d->stream, k_dyn_adv_head, dim3((unsigned)((N + h.wpb - 1) / h.wpb), R), dim3(64 * h.wpb), per_wave * h.wpb, h);
   DEV_LAUNCH(d->stream, k_dyn_adv_reduce, dim3(R), dim3(1024), 0, (const float*)w.lterm, (const float*)w.gmax,
               (const float*)w.gmin, (const double*)d->aRowlp, advantage, K, (int)Ba, (int)Bs, D, (const float*)d->params, d->grads,
@@ -1429,10 +1441,23 @@ int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, co
   DynAdamP a = dyn_adam_params(d);
   a.m = d->adv_m; a.v = d->adv_v;
   a.lr = d->adv_lr; a.b1 = d->adv_b1; a.b2 = d->adv_b2; a.eps = d->adv_eps;
-  a.batch = 0;
+  a.batch = batch;
   DEV_LAUNCH(d->stream, k_dyn_adam, dim3(d->nblk, R), dim3(256), 0, a);
   DEV_LAUNCH(d->stream, k_dyn_adv_metrics, dim3(R), dim3(256), 0, (const float*)d->nll, (const float*)d->decay_part, d->nblk,
               (const int*)d->active_d, (const float*)d->aAdvm, d->adv_weight, d->aMetrics);
+  return 0;
+}
+
+int orl_dynadv_update(orl_dynamics* d, const float* advantage, int on_device, const int32_t* active, float* metrics_out) {
+  if (!d || !advantage) return fail("orl_dynadv_update: bad arguments");
+  if (!d->adv_on || !d->adv_pending) return fail("orl_dynadv_update: no pending forward (orl_dynadv_forward first; one update per forward)");
+  const int R = d->R;
+  const long Ba = d->aBa;
+  d->adv_pending = false;
+  std::vector<int> act;
+  if (dyn_upload_run_state(d, active, d->adv_tstep, act, true)) return -1;
+  if (stage_in(d->stream, advantage, d->aAdv, (size_t)R * Ba, on_device)) return -1;
+  if (dynadv_update_launches(d, advantage, 0, "orl_dynadv_update")) return -1;
   std::vector<float> ms((size_t)R * 4);
   ORL_HIP(hipMemcpyAsync(ms.data(), d->aMetrics, sizeof(float) * ms.size(), hipMemcpyDeviceToHost, d->stream));
   ORL_HIP(hipStreamSynchronize(d->stream));
@@ -1460,3 +1485,40 @@ int orl_dynadv_adam_set(orl_dynamics* d, int run, const float* m, const float* v
 }
 
 }  // extern "C"
+
+// ---- the adversarial pair as the RAMBO device loop drives it (engine.hip: orl_rambo_update_dynamics; declared in devobj.h) ----
+namespace orl {
+
+int dynadv_info(orl_dynamics* d, DynAdvInfo* o) {
+  if (!d || !o) return fail("dynadv_info: null handle");
+  o->dev = d->c.device; o->R = d->R; o->od = d->od; o->ad = d->ad; o->Ba = d->aBa; o->Bs = d->aBs; o->on = d->adv_on;
+  o->stream = d->stream; o->metrics = d->aMetrics;
+  return 0;
+}
+
+int dynadv_loop_begin(orl_dynamics* d, hipStream_t loop_stream, hipStream_t* own) {
+  *own = d->stream;
+  d->stream = loop_stream;
+  d->adv_pending = false;
+  std::vector<int> act;
+  // (blocking copies: the sources are locals; nothing of the loop has been enqueued yet)
+  return dyn_upload_run_state(d, nullptr, d->adv_tstep, act, false);
+}
+
+int dynadv_forward_enqueue(orl_dynamics* d, const float* obs, const float* act, const float* sl_obs, const float* sl_act,
+                           const float* sl_next_obs, const float* sl_rew, float* next_obs, float* reward) {
+  return dynadv_forward_launches(d, obs, act, sl_obs, sl_act, sl_next_obs, sl_rew, nullptr, nullptr, next_obs, reward, nullptr,
+                                 "orl_rambo_update_dynamics");
+}
+
+int dynadv_update_enqueue(orl_dynamics* d, const float* advantage, int step) {
+  return dynadv_update_launches(d, advantage, step, "orl_rambo_update_dynamics");
+}
+
+void dynadv_loop_end(orl_dynamics* d, hipStream_t own, long steps_done) {
+  d->stream = own;
+  for (int r = 0; r < d->R; ++r) d->adv_tstep[r] += steps_done;
+  if (steps_done > 0) { d->tap_adv_fwd = d->tap_adv_upd = d->tap_nll = true; }
+}
+
+}  // namespace orl

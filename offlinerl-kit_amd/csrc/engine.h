@@ -367,6 +367,22 @@ struct Engine {
   long ar_cap = 0;
   Mat ar_sx, ar_sz, ar_seps, ar_sobs; std::vector<Mat> ar_sh;
   unsigned long long* ar_calls = nullptr;
+  // RAMBO (algo_rambo.inc; SAC engines).  orl_engine_adv_advantage: workspaces for Ba rows per run (the actor's input and hidden
+  // activations, the 2 Ba-row critic operand with the critics' activations, head, log-prob, Q, the five tap vectors, host staging),
+  // regrown when Ba grows.  The device loop orl_rambo_update_dynamics adds its row buffers (two observation buffers that swap roles,
+  // action, noise, the dataset sample, reward, advantage), the five running sums and the call counter of its own action-noise stream.
+  int adv_room(long Ba);
+  int adv_advantage(const float* obs, const float* act, const float* nobs, const float* rew, long Ba, int term_kind, int include_ent,
+                    float* adv_dev);
+  int adv_act(const float* obs, long Ba, float* act_out);      // a ~ pi(. | obs) on device rows, noise from the loop's own stream
+  int rambo_room(long rows);
+  long adv_cap = 0, rambo_cap = 0;
+  Mat adv_xs, adv_xc, adv_head, adv_logp, adv_q, adv_v[5], adv_in[4];
+  std::vector<Mat> adv_ah, adv_ch;
+  float* adv_stats = nullptr;
+  Mat rb_obs[2], rb_act, rb_eps, rb_sl[5], rb_rew, rb_adv;
+  float* rb_acc = nullptr;
+  unsigned long long* rb_calls = nullptr;
 };
 
 }  // namespace orl

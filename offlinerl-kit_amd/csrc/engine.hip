@@ -1135,6 +1135,7 @@ static SampleJob make_job(int head_row0, int rows, int rep, const Mat& eps, cons
 #include "algo_rcsl.inc"
 #include "algo_rcsl_gauss.inc"
 #include "algo_autoreg.inc"
+#include "algo_rambo.inc"
 
 namespace orl {
 
@@ -2084,6 +2085,22 @@ int orl_buffer_normalize_obs(orl_buffer* h, float eps, float* mean_out, float* s
   if (std_out) memcpy(std_out, sd.data(), sizeof(float) * b.od);
   return 0;
 }
+// one draw of `batch` rows into packed device arrays on `stream`: the rows idx[] or, without, Philox draws keyed by (seed, row, the
+// buffer's draw counter), which advances.  orl_buffer_sample and the RAMBO device loop share it
+static int buffer_gather(Buffer& b, const long long* idx_dev, int batch, uint64_t seed, float* obs_out, float* act_out, float* next_obs_out,
+                         float* rew_out, float* term_out, hipStream_t stream) {
+  GatherP g;
+  memset(&g, 0, sizeof(g));
+  g.obs = b.obs; g.nobs = b.nobs; g.act = b.act; g.rew = b.rew; g.term = b.term; g.n = b.n;
+  g.OP = b.OP; g.AP = b.AP; g.od = b.od; g.ad = b.ad; g.B = batch; g.W = std::max(b.od, b.ad);
+  g.idx = idx_dev; g.idx_rs = batch;
+  g.b_obs = obs_out; g.b_nobs = next_obs_out; g.b_act = act_out; g.b_rew = rew_out; g.b_term = term_out;
+  g.d_op = b.od; g.d_ap = b.ad;
+  g.seed = seed; g.gstep = nullptr; g.counter = b.counter++;
+  hipLaunchKernelGGL(k_gather, dim3((unsigned)(((long)batch * g.W + 255) / 256), 1), dim3(256), 0, stream, g);
+  ORL_HIP(hipGetLastError());
+  return 0;
+}
 int orl_buffer_sample(orl_buffer* h, const int64_t* idx, int32_t batch, uint64_t seed, float* obs_out, float* act_out,
                       float* next_obs_out, float* rew_out, float* term_out) {
   Buffer& b = h->b;
@@ -2099,16 +2116,7 @@ int orl_buffer_sample(orl_buffer* h, const int64_t* idx, int32_t batch, uint64_t
     }
     ORL_HIP(hipMemcpy(b.idx, idx, sizeof(long long) * batch, hipMemcpyHostToDevice));
   }
-  GatherP g;
-  memset(&g, 0, sizeof(g));
-  g.obs = b.obs; g.nobs = b.nobs; g.act = b.act; g.rew = b.rew; g.term = b.term; g.n = b.n;
-  g.OP = b.OP; g.AP = b.AP; g.od = b.od; g.ad = b.ad; g.B = batch; g.W = std::max(b.od, b.ad);
-  g.idx = idx ? b.idx : nullptr; g.idx_rs = batch;
-  g.b_obs = obs_out; g.b_nobs = next_obs_out; g.b_act = act_out; g.b_rew = rew_out; g.b_term = term_out;
-  g.d_op = b.od; g.d_ap = b.ad;
-  g.seed = seed; g.gstep = nullptr; g.counter = b.counter++;
-  hipLaunchKernelGGL(k_gather, dim3((unsigned)(((long)batch * g.W + 255) / 256), 1), dim3(256), 0, 0, g);
-  ORL_HIP(hipGetLastError());
+  if (buffer_gather(b, idx ? b.idx : nullptr, batch, seed, obs_out, act_out, next_obs_out, rew_out, term_out, 0)) return -1;
   ORL_HIP(hipStreamSynchronize(0));
   return 0;
 }
@@ -2422,6 +2430,130 @@ int orl_engine_lcb_penalty(orl_engine* h, const float* eps_lcb, float* penalty_o
   ORL_HIP(hipStreamSynchronize(e.stream));
   e.mobile_samples = nullptr;
   return 0;
+}
+
+// the refusals orl_engine_adv_advantage and the device loop share; `who` prefixes the message
+static int adv_refuse(const Engine& e, long rows, int term_kind, const char* who) {
+  const std::string w(who);
+  if (e.cfg.algo != ORL_ALGO_SAC) return fail(w + ": not a SAC engine");
+  if (rows < 2) return fail(w + ": rows must be >= 2 (the unbiased standard deviation of one advantage is NaN)");
+  if (rows > (1 << 22)) return fail(w + ": more than 2^22 rows per run");
+  if (term_kind < 0 || term_kind >= ORL_TERM_KINDS) return fail(w + ": unknown termination kind");
+  const int need = term_kind == ORL_TERM_PEN ? 27 : ((term_kind == ORL_TERM_HOPPER || term_kind == ORL_TERM_WALKER2D) ? 2 : 1);
+  if (e.od < need) {
+    char msg[224];
+    snprintf(msg, sizeof(msg), "%s: termination kind %d reads observation column %d, the engine has %d columns", who, term_kind, need - 1, e.od);
+    return fail(msg);
+  }
+  return 0;
+}
+
+int orl_engine_adv_advantage(orl_engine* h, const float* obs, const float* act, const float* next_obs, const float* reward, int32_t rows,
+                             int32_t term_kind, int32_t include_ent, float* advantage, float* stats, int on_device) {
+  if (!h || !obs || !act || !next_obs || !reward) return fail("orl_engine_adv_advantage: bad arguments");
+  Engine& e = h->e;
+  if (adv_refuse(e, rows, term_kind, "orl_engine_adv_advantage")) return -1;
+  ORL_HIP(hipSetDevice(e.dev));
+  if (e.adv_room(rows)) return -1;
+  const size_t n = (size_t)e.R * rows;
+  if (stage_in(e.stream, obs, e.adv_in[0].p, n * e.od, on_device) || stage_in(e.stream, act, e.adv_in[1].p, n * e.ad, on_device) ||
+      stage_in(e.stream, next_obs, e.adv_in[2].p, n * e.od, on_device) || stage_in(e.stream, reward, e.adv_in[3].p, n, on_device))
+    return -1;
+  if (e.adv_advantage(obs, act, next_obs, reward, rows, term_kind, include_ent != 0, nullptr)) return -1;
+  const hipMemcpyKind out_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (advantage) ORL_HIP(hipMemcpyAsync(advantage, e.adv_v[4].p, sizeof(float) * n, out_kind, e.stream));
+  if (stats) ORL_HIP(hipMemcpyAsync(stats, e.adv_stats, sizeof(float) * 2 * e.R, out_kind, e.stream));
+  ORL_HIP(hipStreamSynchronize(e.stream));
+  return 0;
+}
+
+int orl_rambo_update_dynamics(orl_engine* h, orl_dynamics* d, orl_buffer* real, const orl_rambo_loop* a, float* metrics_mean, float* elapsed_ms) {
+  const char* F = "orl_rambo_update_dynamics";
+  if (!h || !d || !real || !a || !metrics_mean) return fail(std::string(F) + ": bad arguments");
+  Engine& e = h->e;
+  Buffer& b = real->b;
+  DynAdvInfo di;
+  if (dynadv_info(d, &di)) return -1;
+  if (adv_refuse(e, a->rows, a->term_kind, F)) return -1;
+  if (e.R != 1 || di.R != 1) return fail(std::string(F) + ": one run per policy and per dynamics ensemble (n_runs == 1 on both)");
+  if (!di.on) return fail(std::string(F) + ": orl_dynadv_configure first");
+  if (a->rows != di.Ba || a->rows != di.Bs) {
+    char msg[224];
+    snprintf(msg, sizeof(msg), "%s: rows = %d, the adversary is configured for %d rollout and %d dataset rows", F, (int)a->rows, di.Ba, di.Bs);
+    return fail(msg);
+  }
+  if (di.dev != e.dev || b.dev != e.dev) return fail(std::string(F) + ": engine, dynamics and buffer must live on one device");
+  if (di.od != e.od || di.ad != e.ad || b.od != e.od || b.ad != e.ad) return fail(std::string(F) + ": obs / act dims of engine, dynamics and buffer differ");
+  if (!b.obs || b.n < 1) return fail(std::string(F) + ": empty buffer");
+  if (a->n_segments < 1 || !a->segment_steps) return fail(std::string(F) + ": no segments");
+  long total = 0;
+  for (int s = 0; s < a->n_segments; ++s) {
+    if (a->segment_steps[s] < 1) return fail(std::string(F) + ": a segment needs at least one step");
+    total += a->segment_steps[s];
+  }
+  if (total > (1L << 30)) return fail(std::string(F) + ": too many steps");
+  ORL_HIP(hipSetDevice(e.dev));
+  const int rows = a->rows;
+  if (e.adv_room(rows) || e.rambo_room(rows)) return -1;
+  struct Events {
+    hipEvent_t a = nullptr, b = nullptr, order = nullptr;
+    ~Events() { for (hipEvent_t x : {a, b, order}) if (x) hipEventDestroy(x); }
+  } ev;
+  ORL_HIP(hipEventCreate(&ev.a));
+  ORL_HIP(hipEventCreate(&ev.b));
+  ORL_HIP(hipEventCreateWithFlags(&ev.order, hipEventDisableTiming));
+  // whatever the dynamics' own stream still holds comes first; from here to the end every launch of both objects is on e.stream
+  ORL_HIP(hipEventRecord(ev.order, di.stream));
+  ORL_HIP(hipStreamWaitEvent(e.stream, ev.order, 0));
+  hipStream_t own = nullptr;
+  if (dynadv_loop_begin(d, e.stream, &own)) { dynadv_loop_end(d, own, 0); return -1; }
+  if (e.prof_on) { e.prof.clear(); e.ev_used = 0; }
+  long done = 0;
+  int cur = 0;
+  const auto body = [&]() -> int {
+    ORL_HIP(hipMemsetAsync(e.rb_acc, 0, sizeof(float) * 8, e.stream));
+    ORL_HIP(hipEventRecord(ev.a, e.stream));
+    for (int s = 0; s < a->n_segments; ++s) {
+      // the segment's initial observations: one draw, of which the observation rows are kept
+      if (buffer_gather(b, nullptr, rows, e.cfg.seed, e.rb_obs[cur].p, e.rb_sl[1].p, e.rb_sl[2].p, e.rb_sl[3].p, e.rb_sl[4].p, e.stream)) return -1;
+      for (int k = 0; k < a->segment_steps[s]; ++k) {
+        float* obs = e.rb_obs[cur].p;
+        float* nxt = e.rb_obs[cur ^ 1].p;
+        if (e.adv_act(obs, rows, e.rb_act.p)) return -1;
+        if (buffer_gather(b, nullptr, rows, e.cfg.seed, e.rb_sl[0].p, e.rb_sl[1].p, e.rb_sl[2].p, e.rb_sl[3].p, e.rb_sl[4].p, e.stream)) return -1;
+        if (dynadv_forward_enqueue(d, obs, e.rb_act.p, e.rb_sl[0].p, e.rb_sl[1].p, e.rb_sl[2].p, e.rb_sl[3].p, nxt, e.rb_rew.p)) return -1;
+        if (e.adv_advantage(obs, e.rb_act.p, nxt, e.rb_rew.p, rows, a->term_kind, a->include_ent != 0, e.rb_adv.p)) return -1;
+        if (dynadv_update_enqueue(d, e.rb_adv.p, (int)done)) return -1;
+        hipLaunchKernelGGL(k_rambo_accum, dim3(1), dim3(1), 0, e.stream, e.rb_acc, di.metrics, (const float*)e.adv_stats);
+        if (hipGetLastError() != hipSuccess) return fail(std::string(F) + ": accumulate launch failed");
+        ++done;
+        cur ^= 1;
+      }
+    }
+    ORL_HIP(hipEventRecord(ev.b, e.stream));
+    return 0;
+  };
+  const int rc = body();
+  const hipError_t se = hipStreamSynchronize(e.stream);      // the one host synchronisation (also on an error path: the launches made so far ran)
+  dynadv_loop_end(d, own, done);
+  if (rc) return -1;
+  if (se != hipSuccess) return fail(std::string(F) + ": " + hipGetErrorString(se));
+  // the last step's rows: cur now names the buffer its next_obs went to
+  const auto tap = [&](const char* name, const Mat& m, int cols) { Mat v = m; v.rs = (long)rows * cols; e.taps[name] = {v, rows, cols}; };
+  tap("loop.obs", e.rb_obs[cur ^ 1], e.od); tap("loop.next_obs", e.rb_obs[cur], e.od); tap("loop.act", e.rb_act, e.ad);
+  tap("loop.sl_obs", e.rb_sl[0], e.od); tap("loop.sl_act", e.rb_sl[1], e.ad); tap("loop.sl_next_obs", e.rb_sl[2], e.od);
+  tap("loop.sl_rew", e.rb_sl[3], 1); tap("loop.reward", e.rb_rew, 1);
+  float ms = 0.f;
+  ORL_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+  if (elapsed_ms) *elapsed_ms = ms;
+  float acc[5];
+  ORL_HIP(hipMemcpy(acc, e.rb_acc, sizeof(acc), hipMemcpyDeviceToHost));
+  bool finite = true;
+  for (int k = 0; k < 5; ++k) { finite = finite && std::isfinite(acc[k]); metrics_mean[k] = acc[k] / (float)done; }
+  if (!finite) e.health_host[0] |= ORL_HEALTH_NONFINITE_LOSS;
+  unsigned int bad = 0;
+  if (e.health_update(nullptr, 0, &bad)) return -1;
+  return bad ? ORL_RC_UNHEALTHY : 0;
 }
 
 int orl_health(orl_engine* h, uint32_t* flags_out) {

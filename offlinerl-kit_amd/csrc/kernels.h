@@ -2085,4 +2085,103 @@ __global__ void k_autoreg_draw(AutoregDrawP p) {
   if (p.j + 1 < p.A) x[p.od + p.A + p.j + 1] = 1.0f;
 }
 
+
+// ================================================================================================
+// RAMBO's advantage (policy/model_based/rambo.py:164-181): orl_engine_adv_advantage and the device loop of update_dynamics
+// ================================================================================================
+// The packed rows of a call as the operands of its two passes: the actor's input xs[i] = src[i] (pitch OP, zero padded) and, when xc
+// is given, the ONE 2 Ba-row critic operand: rows [0, Ba) = [s | a], rows [Ba, 2 Ba) = [s' | . ] whose action columns the sampling job
+// of the actor pass fills (a' = tanh(mu(s'))); the padding is zeroed.  src = s' there, = s for the loop's action draw.
+// grid (ceil(Ba / 256), R)
+struct AdvInP {
+  const float* src;                   // [R][Ba][od] the actor's rows
+  const float *obs, *act;             // [R][Ba][od], [R][Ba][ad] (with xc)
+  float* xs; long xs_rs; int OP;      // [R][Ba][OP]
+  float* xc; long xc_rs; int XP;      // [R][2 Ba][XP] or null
+  int Ba, od, ad;
+};
+__global__ void k_adv_assemble(AdvInP p) {
+  const int r = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.Ba) return;
+  const long ri = (long)r * p.Ba + i;
+  const float* s = p.src + ri * p.od;
+  float* a = p.xs + (long)r * p.xs_rs + (long)i * p.OP;
+  for (int c = 0; c < p.od; ++c) a[c] = s[c];
+  for (int c = p.od; c < p.OP; ++c) a[c] = 0.f;
+  if (!p.xc) return;
+  float* x0 = p.xc + (long)r * p.xc_rs + (long)i * p.XP;
+  float* x1 = x0 + (long)p.Ba * p.XP;
+  const float* o = p.obs + ri * p.od;
+  const float* ac = p.act + ri * p.ad;
+  for (int c = 0; c < p.od; ++c) { x0[c] = o[c]; x1[c] = s[c]; }
+  for (int c = 0; c < p.ad; ++c) x0[p.od + c] = ac[c];
+  for (int c = p.od + p.ad; c < p.XP; ++c) { x0[c] = 0.f; x1[c] = 0.f; }
+}
+
+// The rest of the advantage, ONE workgroup of 256 threads per run, rows strided over the threads (row b belongs to thread b % 256 in
+// every pass, so a thread re-reads only what it wrote):
+//   term = the termination test on s' (orl_term_done: the numpy comparisons on the same fp32 values), q' = min(Q1, Q2)(s', a')
+//   [- alpha logp'], value = r + ((1 - term) gamma) q', raw = value - min(Q1, Q2)(s, a)      -- torch's separate roundings: the
+//   kernel body is compiled with fp contraction off (the _rn intrinsics alone do not keep hipcc from fusing a product into a sum)
+//   mean = sum(raw) / Ba, std = sqrt(sum((raw - mean)^2) / (Ba - 1)) (torch's unbiased default), norm = (raw - mean) / (std + 1e-6)
+//   stats = {sum(norm) / Ba, std}
+// Every sum is block_sum256 over per-thread partial sums in row order: ceil(Ba / 256) - 1 additions in the thread, 6 across the
+// lanes (__shfl_down tree), 3 across the four waves through LDS -- a fixed order, no atomics, the result does not depend on scheduling.
+struct AdvNormP {
+  ZPtr q;                              // [R][2][2 Ba] the live critics on k_adv_assemble's operand
+  const float* logp; long lp_rs;       // [R][Ba] log pi(a' | s') at the mode
+  const float *nobs, *rew;             // packed [R][Ba][od], [R][Ba]
+  float *term, *qn, *qb, *raw, *norm;  // [R][Ba] each (the taps)
+  float* adv_out;                      // [R][Ba] device destination of the normalised advantage, or null
+  float* stats;                        // [R][2]
+  int Ba, od, kind, include_ent;
+  float gamma;
+  const RunScalars* sc; int auto_alpha; float fixed_alpha;
+};
+__global__ __launch_bounds__(256) void k_adv_norm(AdvNormP p) {
+#pragma clang fp contract(off)      // every product below is rounded before it is added, as torch's separate kernels round it
+  __shared__ float sh[4];
+  const int r = blockIdx.x;
+  const int Ba = p.Ba;
+  const long r0 = (long)r * Ba;
+  const float alpha = p.auto_alpha ? p.sc[r].alpha : p.fixed_alpha;
+  const float* q1 = p.q.p + (long)r * p.q.s0;
+  const float* q2 = q1 + p.q.s1;
+  float s = 0.f;
+  for (int b = threadIdx.x; b < Ba; b += 256) {
+    const float t = orl_term_done(p.kind, p.nobs + (r0 + b) * p.od, p.od) ? 1.0f : 0.0f;
+    float nq = fminf(q1[Ba + b], q2[Ba + b]);
+    if (p.include_ent) nq = nq - alpha * p.logp[(long)r * p.lp_rs + b];
+    const float value = p.rew[r0 + b] + ((1.0f - t) * p.gamma) * nq;
+    const float base = fminf(q1[b], q2[b]);
+    const float raw = value - base;
+    p.term[r0 + b] = t; p.qn[r0 + b] = nq; p.qb[r0 + b] = base; p.raw[r0 + b] = raw;
+    s += raw;
+  }
+  const float mean = block_sum256(s, sh) / (float)Ba;
+  s = 0.f;
+  for (int b = threadIdx.x; b < Ba; b += 256) {
+    const float d = p.raw[r0 + b] - mean;
+    s += d * d;
+  }
+  const float sd = sqrtf(block_sum256(s, sh) / (float)(Ba - 1));
+  const float den = sd + 1e-6f;
+  s = 0.f;
+  for (int b = threadIdx.x; b < Ba; b += 256) {
+    const float n = (p.raw[r0 + b] - mean) / den;
+    p.norm[r0 + b] = n;
+    if (p.adv_out) p.adv_out[r0 + b] = n;
+    s += n;
+  }
+  const float nm = block_sum256(s, sh) / (float)Ba;
+  if (threadIdx.x == 0) { p.stats[2 * r] = nm; p.stats[2 * r + 1] = sd; }
+}
+
+// one step's five logged values of the device loop added to its running sums (one run, one thread): all_loss, sl_loss, adv_loss from
+// the dynamics' metrics, the mean normalised advantage from k_adv_norm's stats, the mean log-probability
+__global__ void k_rambo_accum(float* __restrict__ acc, const float* __restrict__ dyn_metrics, const float* __restrict__ stats) {
+  acc[0] += dyn_metrics[0]; acc[1] += dyn_metrics[1]; acc[2] += dyn_metrics[2]; acc[3] += stats[0]; acc[4] += dyn_metrics[3];
+}
+
 }  // namespace orl

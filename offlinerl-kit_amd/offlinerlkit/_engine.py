@@ -58,6 +58,8 @@ ABI_SYMBOLS = [
     "orl_dyn_update_save", "orl_dyn_load_save", "orl_dyn_step", "orl_dyn_debug_grads", "orl_dyn_debug_read",
     # RAMBO's adversarial update on an orl_dynamics
     "orl_dynadv_configure", "orl_dynadv_forward", "orl_dynadv_update", "orl_dynadv_adam_get", "orl_dynadv_adam_set",
+    # ... its advantage on the policy engine and the device loop of update_dynamics around both
+    "orl_engine_adv_advantage", "orl_rambo_update_dynamics",
     # MOBILE: next-state samples of the dynamics, their hand-over to the policy engine, compute_lcb alone
     "orl_dynsample_next", "orl_engine_set_next_samples", "orl_engine_lcb_penalty",
     # RCSL: one ordered pass over the attached buffer
@@ -211,6 +213,14 @@ class OrlSmallEx(C.Structure):
 _lib = None
 
 
+class OrlRamboLoop(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("term_kind", C.c_int32), ("include_ent", C.c_int32), ("n_segments", C.c_int32),
+                ("segment_steps", C.POINTER(C.c_int32))]
+
+
+RAMBO_KEYS = ("all_loss", "sl_loss", "adv_loss", "adv_advantage", "adv_log_prob")      # orl_rambo_update_dynamics' metrics_mean[5]
+
+
 def load_library(path: Optional[str] = None):
     """dlopen the engine; raises (never falls back) when it is absent."""
     global _lib
@@ -290,6 +300,8 @@ def load_library(path: Optional[str] = None):
     lib.orl_autoreg_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
     lib.orl_engine_set_next_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_lcb_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.orl_engine_adv_advantage.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int]
+    lib.orl_rambo_update_dynamics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OrlRamboLoop), C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_health.argtypes = [C.c_void_p, C.c_void_p]
     lib.orl_health_check.argtypes = [C.c_void_p, C.c_void_p]
     lib.orl_health_clear.argtypes = [C.c_void_p]
@@ -761,6 +773,43 @@ class Engine(_Handle):
         out = np.zeros((self.n_runs, self.cfg.batch_size), dtype=np.float32)
         _check(self.lib.orl_engine_lcb_penalty(self._h, None if e is None else e.ctypes.data, out.ctypes.data, 0), "orl_engine_lcb_penalty")
         return out
+
+    def adv_advantage(self, obs, act, next_obs, reward, term_kind: int, include_ent: bool = False, rows: Optional[int] = None,
+                      out_ptr: Optional[int] = None, stats_ptr: Optional[int] = None, on_device=False):
+        """RAMBO's normalised advantage (orl_engine_adv_advantage; SAC engines).  Host arrays [n_runs][rows][..] in, (advantage
+        [n_runs][rows], stats [n_runs][2] = mean of the normalised advantage, raw std) out; with ``on_device`` the four inputs,
+        ``out_ptr`` and ``stats_ptr`` (either may be None) are raw device pointers and ``rows`` the rows per run.  The "adv.*" taps
+        hold the intermediates afterwards."""
+        if on_device:
+            _check(self.lib.orl_engine_adv_advantage(self._h, int(obs), int(act), int(next_obs), int(reward), int(rows), int(term_kind),
+                                                     1 if include_ent else 0, None if out_ptr is None else int(out_ptr),
+                                                     None if stats_ptr is None else int(stats_ptr), 1), "orl_engine_adv_advantage")
+            return None
+        o, a, n, r = _f32(obs), _f32(act), _f32(next_obs), _f32(reward)
+        R, od, ad = self.n_runs, self.cfg.obs_dim, self.cfg.act_dim
+        if o.ndim != 3 or o.shape[0] != R or o.shape[2] != od:
+            raise ValueError(f"obs: expected [n_runs = {R}, rows, obs_dim = {od}], got {o.shape}")
+        Ba = int(o.shape[1])
+        r = np.ascontiguousarray(r.reshape(R, -1))
+        for name, x, shp in (("act", a, (R, Ba, ad)), ("next_obs", n, (R, Ba, od)), ("reward", r, (R, Ba))):
+            if x.shape != shp:
+                raise ValueError(f"{name}: expected {shp}, got {x.shape}")
+        adv, st = np.zeros((R, Ba), np.float32), np.zeros((R, 2), np.float32)
+        _check(self.lib.orl_engine_adv_advantage(self._h, o.ctypes.data, a.ctypes.data, n.ctypes.data, r.ctypes.data, Ba, int(term_kind),
+                                                 1 if include_ent else 0, adv.ctypes.data, st.ctypes.data, 0), "orl_engine_adv_advantage")
+        return adv, st
+
+    def rambo_update_dynamics(self, dyn: "Dynamics", real: "DeviceBuffer", rows: int, term_kind: int, include_ent: bool,
+                              segment_steps: Sequence[int]):
+        """RAMBO's update_dynamics on the device (orl_rambo_update_dynamics): ``segment_steps`` = the model steps of each segment
+        (``rambo_adv_schedule``).  Returns ({key: mean over the steps} for ``RAMBO_KEYS``, elapsed ms); one host synchronisation."""
+        seg = (C.c_int32 * len(segment_steps))(*[int(x) for x in segment_steps])
+        a = OrlRamboLoop(int(rows), int(term_kind), 1 if include_ent else 0, len(segment_steps), seg)
+        m = np.zeros(len(RAMBO_KEYS), dtype=np.float32)
+        ms = C.c_float()
+        self._check_step(self.lib.orl_rambo_update_dynamics(self._h, dyn._h, real._h, C.byref(a), m.ctypes.data, C.byref(ms)),
+                         "orl_rambo_update_dynamics")
+        return {k: float(v) for k, v in zip(RAMBO_KEYS, m)}, ms.value
 
     def learn_n(self, n_steps: int):
         m = np.zeros((self.n_runs, MAX_METRICS), dtype=np.float32)

@@ -17,7 +17,7 @@ from .sac_family import CQLPolicy, EDACPolicy
 from .td3bc import TD3BCPolicy
 from .model_based import SACPolicy, MOPOPolicy, COMBOPolicy
 from .mcq import MCQPolicy
-from .rambo import RAMBOPolicy
+from .rambo import RAMBOPolicy, rambo_adv_schedule
 from .mobile import MOBILEPolicy
 from .rcsl import RcslPolicy, RcslGaussianPolicy
 from .autoregressive import AutoregressivePolicy

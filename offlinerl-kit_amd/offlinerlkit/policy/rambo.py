@@ -8,13 +8,19 @@ backward and one Adam step of ``dynamics_adv_optim``.  Between them the advantag
 and the critics (the engine's live weights) under ``no_grad``; the termination function runs on the host like the reference's.
 ``pretrain`` (behaviour cloning of the actor, once) is plain torch autograd on the same views.
 
+``update_dynamics_device`` is the same update as ONE call into the device loop (``orl_rambo_update_dynamics``): the actor's draws, the
+buffer draws (device Philox instead of numpy's), the adversarial forward, the advantage on the policy engine
+(``orl_engine_adv_advantage``'s pass: termination test, TD value and normalisation in one kernel) and the adversarial update of every
+step are enqueued on one stream, and the five logged values are read once at the end.  ``MBPolicyTrainer(fused=True,
+dynamics_update_freq > 0)`` calls it; ``rambo_adv_schedule`` is the reference loop's segment structure as a pure function.
+
 One run per policy: ``set_engine_options(n_runs > 1)`` is refused (the calls underneath are run-batched).
 """
 from __future__ import annotations
 
 import os
 from collections import defaultdict
-from typing import Dict, Tuple, Union
+from typing import Dict, List, Tuple, Union
 
 import numpy as np
 import torch
@@ -23,6 +29,25 @@ import torch.nn as nn
 from .model_based import MOPOPolicy
 
 _KEYS = ("all_loss", "sl_loss", "adv_loss", "adv_advantage", "adv_log_prob")
+
+
+def rambo_adv_schedule(adv_train_steps: int, rollout_length: int) -> List[int]:
+    """The segment lengths of ``update_dynamics``' loop (rambo.py:101-125): ``while steps < adv_train_steps`` draws initial states, the
+    ``for`` over ``rollout_length`` steps them, and ``if steps == 1000: break`` leaves the ``for`` -- at the literal 1000, whatever
+    ``adv_train_steps`` is, and the ``while`` then starts a new segment if steps are still missing.  The ``for`` is not left when
+    ``adv_train_steps`` is reached, so the total overshoots to the end of the segment.  A pure function of its two arguments."""
+    if rollout_length < 1:
+        raise ValueError("rollout_length must be >= 1")
+    segments, steps = [], 0
+    while steps < adv_train_steps:
+        n = 0
+        for _ in range(rollout_length):
+            n += 1
+            steps += 1
+            if steps == 1000:
+                break
+        segments.append(n)
+    return segments
 
 
 class RAMBOPolicy(MOPOPolicy):
@@ -108,6 +133,39 @@ class RAMBOPolicy(MOPOPolicy):
                     break
         self.dynamics.model.eval()
         return {_key: _value / steps for _key, _value in all_loss_info.items()}
+
+    def update_dynamics_device(self, real_buffer) -> Dict[str, float]:
+        """``update_dynamics`` as ONE call into the device loop (``orl_rambo_update_dynamics``): the actor's draws, the buffer draws,
+        the adversarial forward, the advantage on the engine and the adversarial update of every step are enqueued without a host
+        round trip, and the five values are read once.  The draws come from the device Philox streams (the buffer's, the dynamics' and
+        the loop's own for the actions) instead of numpy's and torch's: reproducible from the seeds, not index-identical to
+        ``update_dynamics``.  ``last_update_dynamics_ms`` holds the HIP-event time of the loop."""
+        dyn = self.dynamics
+        if int(getattr(dyn, "_n_runs", 1)) != 1 or self._n_runs != 1:
+            raise NotImplementedError("RAMBOPolicy.update_dynamics_device: one run per policy and per dynamics ensemble (n_runs == 1)")
+        kind = getattr(dyn, "term_kind", None)
+        if kind is None:
+            raise NotImplementedError("rollout_device: the dynamics' termination function is not one of the fixed row-wise tests of "
+                                      "utils.termination_fns (an obs_unnormalization wrapper, door or another callable carries no term_kind): "
+                                      "the device rollout cannot evaluate it; use rollout() / MBPolicyTrainer(fused=False)")
+        if not hasattr(real_buffer, "device_buffer"):
+            raise NotImplementedError("RAMBOPolicy.update_dynamics_device: the buffer has no device_buffer() (an HBM-resident "
+                                      "offlinerlkit.buffer.ReplayBuffer is needed); use update_dynamics()")
+        rows = int(self._adv_rollout_batch_size)
+        if self._eng is None:
+            self._bind(256)
+        dyn.bind_adversary(self._dynmics_adv_optim, self._adv_weight, rows, rows)
+        dyn._adv_ready()
+        real = real_buffer.device_buffer()
+        dyn.model.train()
+        torch.cuda.current_stream(self._torch_device()).synchronize()
+        try:
+            m, ms = self._eng.rambo_update_dynamics(dyn._eng, real, rows, int(kind), bool(self._include_ent_in_adv),
+                                                    rambo_adv_schedule(self._adv_train_steps, self._adv_rollout_length))
+        finally:
+            dyn.model.eval()
+        self.last_update_dynamics_ms = ms
+        return {"adv_dynamics_update/" + k: m[k] for k in _KEYS}
 
     def dynamics_step_and_forward(self, observations, actions, sl_observations, sl_actions, sl_next_observations, sl_rewards):
         """rambo.py:129-207 -> (next_observations, terminals, the five ``adv_dynamics_update/*`` values)"""

@@ -23,7 +23,8 @@ MBPolicyTrainer is the reference's model-based loop (MOPO / COMBO): per step, a 
 split by ``real_ratio`` and one ``policy.learn({"real": ..., "fake": ...})``.  The draw order, logged keys, checkpoints and the final
 ``dynamics.save`` are the reference's; evaluation, the multi-run ``run<i>/...`` keys and the per-run checkpoints are MFPolicyTrainer's.
 ``MBPolicyTrainer(fused=True)`` keeps the model buffer in an HBM ring and runs an epoch as device rollouts at the reference's
-timesteps with ONE ``policy.learn_n`` between two of them (``fused_mb_schedule``).
+timesteps with ONE ``policy.learn_n`` between two of them (``fused_mb_schedule``); with ``dynamics_update_freq > 0`` (RAMBO) the chunks
+are also cut at the model-update points (``fused_mb_dyn_schedule``) and ``policy.update_dynamics_device`` runs there.
 
 RcslPolicyTrainer (reference: offlinerlkit/policy_trainer/rcsl_policy_trainer.py:21-365) is at the end of the module: one shuffled pass
 over the dataset per epoch, in-process batches (``fused=False``) or one ``policy.learn_epoch`` on the device (``fused=True``).
@@ -280,6 +281,24 @@ def fused_mb_schedule(num_timesteps: int, step_per_epoch: int, rollout_freq: int
     return out
 
 
+def fused_mb_dyn_schedule(num_timesteps: int, step_per_epoch: int, rollout_freq: int, dynamics_update_freq: int = 0
+                          ) -> List[Tuple[bool, int, bool]]:
+    """``fused_mb_schedule`` with RAMBO's model updates (mb_policy_trainer.py:95-99): chunks ``(rollout_first, n_steps,
+    update_dynamics_after)``, cut at the rollout points AND behind every timestep ``t`` with ``(t + 1) % dynamics_update_freq == 0``,
+    where the model update runs after the chunk's training steps.  ``dynamics_update_freq`` 0: ``fused_mb_schedule``'s chunks, no update."""
+    if dynamics_update_freq < 0:
+        raise ValueError("dynamics_update_freq must be >= 0")
+    out = []
+    for rollout_first, steps in fused_mb_schedule(num_timesteps, step_per_epoch, rollout_freq):
+        t, end = num_timesteps, num_timesteps + steps
+        while t < end:
+            nxt = min(end, (t // dynamics_update_freq + 1) * dynamics_update_freq) if dynamics_update_freq > 0 else end
+            out.append((rollout_first and t == num_timesteps, nxt - t, dynamics_update_freq > 0 and nxt % dynamics_update_freq == 0))
+            t = nxt
+        num_timesteps = end
+    return out
+
+
 class MBPolicyTrainer(MFPolicyTrainer):
     """Constructor = mb_policy_trainer.py:18-55.  ``rollout_setting`` = (rollout_freq, rollout_batch_size, rollout_length).
 
@@ -292,8 +311,11 @@ class MBPolicyTrainer(MFPolicyTrainer):
     sampled by run r only; ``run<r>/rollout_info/*`` per run, the plain keys their mean (``fused=True`` only).  What differs from the host loop: the minibatch indices
     of both buffers come from the device Philox stream instead of numpy's (as for ``MFPolicyTrainer(fused=True)``), and the model
     draws of a rollout from the dynamics' device stream; runs are reproducible from the seed but not index-identical to the
-    reference.  Refused at construction: ``dynamics_update_freq > 0`` (only RAMBO updates its dynamics), a policy without
-    ``rollout_device``, a dynamics whose termination function is not one of the fixed row-wise tests (no ``term_kind``)."""
+    reference.  ``dynamics_update_freq > 0`` needs a policy with ``update_dynamics_device`` (RAMBO): the chunks are then also cut behind
+    every timestep ``t`` with ``(t + 1) % dynamics_update_freq == 0`` (``fused_mb_dyn_schedule``), the model update runs there as one
+    device loop and its five values go through ``logkv_mean`` as in the host loop.  Refused at construction:
+    ``dynamics_update_freq > 0`` with any other policy (its dynamics has no device update), a policy without ``rollout_device``,
+    a dynamics whose termination function is not one of the fixed row-wise tests (no ``term_kind``)."""
 
     def __init__(self, policy, eval_env, real_buffer, fake_buffer, logger, rollout_setting: Tuple[int, int, int], epoch: int = 1000,
                  step_per_epoch: int = 1000, batch_size: int = 256, real_ratio: float = 0.05, eval_episodes: int = 10,
@@ -311,7 +333,7 @@ class MBPolicyTrainer(MFPolicyTrainer):
         assert (not self.is_gymnasium_env) or (self.horizon is not None), "Horizon must be specified for Gymnasium env"
         self._fused_mb = bool(fused)
         if self._fused_mb:
-            if dynamics_update_freq > 0:
+            if dynamics_update_freq > 0 and not hasattr(policy, "update_dynamics_device"):
                 raise ValueError("MBPolicyTrainer(fused=True): dynamics_update_freq > 0 is not supported (only RAMBO has update_dynamics, "
                                  "and its dynamics changes between the steps of a chunk)")
             if not (hasattr(policy, "rollout_device") and hasattr(policy, "learn_n")):
@@ -364,13 +386,17 @@ class MBPolicyTrainer(MFPolicyTrainer):
 
     def _train_mb_epoch_fused(self, e: int, num_timesteps: int) -> int:
         sums: Dict[str, float] = {}
-        for rollout_first, steps in fused_mb_schedule(num_timesteps, self._step_per_epoch, self._rollout_freq):
+        for rollout_first, steps, update_after in fused_mb_dyn_schedule(num_timesteps, self._step_per_epoch, self._rollout_freq,
+                                                                        self._dynamics_update_freq):
             if rollout_first:
                 self._rollout_fused()
             means = self.policy.learn_n(steps, self.real_buffer, self.fake_buffer, self._batch_size, self._real_ratio)
             for k, v in means.items():
                 sums[k] = sums.get(k, 0.0) + float(v) * steps
             num_timesteps += steps
+            if update_after:      # RAMBO (mb_policy_trainer.py:95-99): the adversarial model update, one call into the device loop
+                for k, v in self.policy.update_dynamics_device(self.real_buffer).items():
+                    self.logger.logkv_mean(k, v)
         for k, v in sums.items():
             self.logger.logkv(k, v / self._step_per_epoch)
         self._check_health()

@@ -15,8 +15,10 @@ run-steps per second: R x block steps / seconds of the block, rollouts included.
 --rambo measures, instead, RAMBO's adversarial model update at run_rambo.py's shape (dynamics [200] x 4, 7 members, 5 elites, policy
 [256, 256], 256 rollout + 256 dataset rows per step, adv_rollout_length 5, adv_weight 3e-4, 1000 steps per update):
 ``RAMBOPolicy.update_dynamics`` on the engine against a stock-torch restatement of the same update (the reference's
-``dynamics_step_and_forward`` with torch autograd and torch.optim.Adam on the same GPU, same buffer draws, actor and critics), a warm-up
-of each and then alternating timed updates.  The figure is model-update steps per second.
+``dynamics_step_and_forward`` with torch autograd and torch.optim.Adam on the same GPU, same buffer draws, actor and critics) and against
+``RAMBOPolicy.update_dynamics_device`` (the whole update as one device loop, ``orl_rambo_update_dynamics``), a warm-up of each and then
+alternating timed updates, each window ending in a device synchronise.  The figure is model-update steps per second (means and medians
+over the windows; ``--blocks 5`` for medians of five).
 
 --mobile measures, instead, ``MOBILEPolicy.learn`` in the host loop at run_mobile.py's shape (policy [256, 256], dynamics [200] x 4, 7
 members, 5 elites, 10 samples: 12 800 penalty rows per step, batch 256 with 12 real rows, penalty_coef 1.5, deterministic backup) against
@@ -265,11 +267,14 @@ def measure_rambo(ds, blocks, steps):
         if name == "engine":
             pol._adv_train_steps = n
             last[name] = pol.update_dynamics(real)
+        elif name == "device":
+            pol._adv_train_steps = n
+            last[name] = pol.update_dynamics_device(real)
         else:
             last[name] = torch_update_dynamics(pol, tmodel, topt, mu, std, real, n, rows, length, w, gamma)
         torch.cuda.synchronize()
         return time.perf_counter() - t0
-    names = ("torch", "engine")
+    names = ("torch", "engine", "device")
     np.random.seed(0)
     torch.manual_seed(0)
     warm = {name: block(name, 100) for name in names}
@@ -280,7 +285,11 @@ def measure_rambo(ds, blocks, steps):
     sps = {name: [steps / x for x in v] for name, v in secs.items()}
     return dict(mode="rambo_update_dynamics", steps=steps, rows=[rows, rows], rollout_length=length, adv_weight=w,
                 warmup_seconds_100_steps=warm, seconds=secs, steps_per_s=sps, steps_per_s_mean={k: float(np.mean(v)) for k, v in sps.items()},
+                steps_per_s_median={k: float(np.median(v)) for k, v in sps.items()},
                 speedup=float(np.mean(sps["engine"]) / np.mean(sps["torch"])),
+                device_over_engine_median=float(np.median(sps["device"]) / np.median(sps["engine"])),
+                device_over_torch_median=float(np.median(sps["device"]) / np.median(sps["torch"])),
+                device_loop_event_ms_last=float(pol.last_update_dynamics_ms),
                 last_losses={k: {a: float(b) for a, b in v.items()} for k, v in last.items()})
 
 
@@ -398,7 +407,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--runs", type=int, default=0, help="R > 1: per-run model rings at R runs against R sequential single-run fused trainings")
     ap.add_argument("--profile-block", action="store_true", help="a warm-up and one fused MOPO block only (for a kernel trace)")
-    ap.add_argument("--rambo", action="store_true", help="RAMBO's update_dynamics (engine) against its stock-torch restatement")
+    ap.add_argument("--rambo", action="store_true", help="RAMBO's update_dynamics (engine, host loop) against its stock-torch restatement and the device loop")
     ap.add_argument("--rambo-steps", type=int, default=1000)
     ap.add_argument("--mobile", action="store_true", help="MOBILEPolicy.learn (engine, host loop) against its stock-torch restatement")
     ap.add_argument("--mobile-steps", type=int, default=500)
