@@ -15,6 +15,8 @@ int Engine::autoreg_build() {
   if (!ar_calls) return fail("hipMalloc sample counter");
   if (hipMemset(ar_calls, 0, sizeof(unsigned long long)) != hipSuccess) return fail("hipMemset sample counter");
   taps["ar_x"] = {W("ar_x"), M, od + 2 * A};
+  taps["ar_z"] = {W("ar_z"), M, 2};                 // k_autoreg_head's operand (tail pre-activation) and its seed
+  taps["ar_dz"] = {W("ar_dz"), M, 2};
   taps["ar_out"] = {W("ar_out"), M, 2};
   taps["ar_target"] = {W("ar_target"), M, 1};
   return 0;
@@ -78,6 +80,9 @@ int Engine::autoreg_sample(const float* obs, long n, const float* eps, bool on_d
   const Mat x = view(ar_sx), z = view(ar_sz), ep = view(ar_seps);
   std::vector<Mat> hs;
   for (auto& m : ar_sh) hs.push_back(view(m));
+  // the workspaces of THIS call as taps (a host map write, no launch): the input rows as the last draw left them, the tail of the last
+  // pass and the noise, n rows each (the workspaces may be regrown by a later call, which registers them anew)
+  taps["ar_sx"] = {x, n, x.pitch}; taps["ar_sz"] = {z, n, 2}; taps["ar_seps"] = {ep, n, A};
   const float* d_obs = obs;
   if (!on_device) {
     ORL_HIP(hipMemcpyAsync(ar_sobs.p, obs, sizeof(float) * (size_t)R * n * od, hipMemcpyHostToDevice, stream));

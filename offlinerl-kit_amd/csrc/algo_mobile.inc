@@ -24,6 +24,13 @@ int Engine::mobile_build() {
   alloc("samples_in", M, od);                                                            // a host array of orl_engine_set_next_samples lands here
   taps["penalty"] = {W("penalty"), B, 1};
   taps["lcb_q"] = {W("lcb_q"), M, 1};
+  // the penalty pass's own operands: what k_mobile_assemble wrote (the action columns of xl are the sampling job's) and what
+  // k_lcb_penalty read; no launch behind the penalty pass writes any of them
+  taps["ql1"] = {W("ql").net(0), M, 1};
+  taps["ql2"] = {W("ql").net(1), M, 1};
+  taps["xs"] = {W("xs"), M, OP};
+  taps["xl"] = {W("xl"), M, XP};
+  taps["logp_l"] = {W("logp_l"), M, 1};
   return 0;
 }
 

@@ -47,6 +47,7 @@ int Engine::rcsl_build() {
   alloc("rcsl_x", B, rup(od + 1, 4));
   alloc("pred", B, A); alloc("dpred", B, A);
   taps["pred"] = {W("pred"), B, A};
+  taps["dpred"] = {W("dpred"), B, A};              // k_rcsl_loss's seed (the backward pass reads it, nothing writes it again)
   taps["rcsl_x"] = {W("rcsl_x"), B, od + 1};
   return 0;
 }

@@ -12,6 +12,7 @@ int Engine::rcslg_build() {
   alloc("rcsl_x", B, rup(od + 1, 4));
   alloc("z", B, A); alloc("dz", B, A); alloc("mu", B, A); alloc("logvar", B, A);
   taps["z"] = {W("z"), B, A};
+  taps["dz"] = {W("dz"), B, A};                    // k_rcslg_head's seed; its head gradients are slab 0 of the arena (orl_debug_grads)
   taps["mu"] = {W("mu"), B, A};
   taps["logvar"] = {W("logvar"), B, A};
   taps["rcsl_x"] = {W("rcsl_x"), B, od + 1};

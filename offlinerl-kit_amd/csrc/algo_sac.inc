@@ -19,6 +19,12 @@ void Engine::sac_alloc() {
   taps["q1a"] = {W("qa").net(0), B, 1};
   taps["q2a"] = {W("qa").net(1), B, 1};
   taps["target_q"] = {W("target_q"), B, 1};
+  // operands and seed of the critic loss (k_td_loss / k_mobile_td_loss), named as CQL and TD3+BC name them
+  taps["qt1"] = {W("qt").net(0), B, 1};
+  taps["qt2"] = {W("qt").net(1), B, 1};
+  taps["dq1"] = {W("dq").net(0), B, 1};
+  taps["dq2"] = {W("dq").net(1), B, 1};
+  taps["logp_next"] = {W("logp_next"), B, 1};
 }
 
 int Engine::sac_build() {

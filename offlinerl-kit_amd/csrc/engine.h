@@ -224,6 +224,10 @@ struct Engine {
   float* gscale_buf = nullptr;       // [GSCALE_SLOTS][R]
   enum { GSCALE_SLOTS = 24 };
   int gscale_next = 0;
+  // test tap "gscale": the slots the last step handed out, in the order of its schedule's gscale_slot() / grad_scale() calls (written down
+  // per schedule next to orl_debug_read); gscale_count[v]: how many step variant v takes, noted when the variant is enqueued or captured
+  int gscale_count[2] = {0, 0};
+  int last_step_variant() const;
   const float* cur_gscale = nullptr; // scale array [R] of the current backward pass (null: precision 0 or outside a backward pass)
   const float* grad_scale(const Mat& seed, int rows, int cols, int nets, const char* tag);
   float* gscale_slot();              // next slot for a seed kernel that publishes the scale itself (GradScaleP-free path); null at precision 0

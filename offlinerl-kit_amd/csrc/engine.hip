@@ -1395,6 +1395,11 @@ int Engine::step_variant() const {
   const int f = cfg.update_actor_freq > 0 ? cfg.update_actor_freq : 1;
   return (step_host % f == 0) ? 1 : 0;   // 1 = actor + target-sync step (td3bc.py:107)
 }
+int Engine::last_step_variant() const {
+  if (cfg.algo != ORL_ALGO_TD3BC || step_host == 0) return 0;
+  const int f = cfg.update_actor_freq > 0 ? cfg.update_actor_freq : 1;
+  return ((step_host - 1) % f == 0) ? 1 : 0;
+}
 
 int Engine::enqueue_step(int variant) {
   int rc = -1;
@@ -1412,6 +1417,7 @@ int Engine::enqueue_step(int variant) {
     case ORL_ALGO_AUTOREG: rc = autoreg_step(); break;
   }
   if (rc) return rc;
+  gscale_count[variant == 1 ? 1 : 0] = gscale_next;      // (host bookkeeping of the "gscale" tap; a captured variant keeps its count)
   if (tick_folded) return 0;               // the step's own kernels advanced the counter
   hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, stream, gstep);
   return hipGetLastError() == hipSuccess ? 0 : fail("tick launch");
@@ -2592,6 +2598,25 @@ int64_t orl_debug_read(orl_engine* h, int run, const char* name, float* host, in
     if (cap < (int64_t)ht->second.size()) { fail("tap buffer too small"); return -1; }
     std::copy(ht->second.begin(), ht->second.end(), host);
     return (int64_t)ht->second.size();
+  }
+  // "gscale": this run's dynamic gradient scales of the last step, one per backward pass; the count is the number of values returned
+  // (0 at precision 0).  Order of the slots, per schedule (a seed kernel that is one workgroup per run publishes its own; the others
+  // come from a k_grad_scale launch, "<tag>.gscale" in the profile):
+  //   RCSL, Gaussian RCSL, AUTOREG   [0] the seed kernel's dpred / dz / ar_dz
+  //   SAC, MOBILE                    [0] dq (k_td_loss / k_mobile_td_loss)  [1] dhead
+  //   CQL                            [0] dhead  [1] dq (k_cql_loss_rows: the largest entry of both critics' seeds)
+  //   EDAC                           [0] dhead  [1] dq (k_td_loss), with eta > 0:  [2] the tail weights (edac.delta)  [3] gamma
+  //   TD3+BC                         [0] dq, on an actor step:  [1] dqpi (k_td3_actor_loss: lambda / B)  [2] dmraw
+  //   IQL                            [0] dv  [1] dq  [2] dmraw
+  //   MCQ                            [0] dm3  [1] dehead  [2] dq (these three by k_grad_scale)  [3] dhead
+  // dhead: k_head_bwd's own up to 256 rows, k_grad_scale ("actor.bwd.gscale") beyond; no slot when the fused actor update applies.
+  if (!strcmp(name, "gscale")) {
+    const int64_t n = e.gscale_count[e.last_step_variant()];
+    if (cap < n) { fail("tap buffer too small"); return -1; }
+    if (hipStreamSynchronize(e.stream) != hipSuccess) { fail("sync"); return -1; }
+    if (n > 0 && hipMemcpy2D(host, sizeof(float), e.gscale_buf + run, sizeof(float) * e.R, sizeof(float), (size_t)n,
+                             hipMemcpyDeviceToHost) != hipSuccess) { fail("tap copy"); return -1; }
+    return n;
   }
   auto it = e.taps.find(name);
   if (it == e.taps.end()) { fail(std::string("unknown tap ") + name); return -1; }

@@ -1,6 +1,7 @@
 """Self-bounding float64 restatements of the engine's row kernels (csrc/kernels.h: sampling, loss, gradient-seed, head-backward and
-optimizer kernels; at the end of the file MCQ's VAE / critic-loss kernels and EDAC's gradient-diversity kernels), written from the formulas
-of the reference that the kernel comments cite -- not from the kernel code.
+optimizer kernels; then MCQ's VAE / critic-loss kernels and EDAC's gradient-diversity kernels; at the end of the file the supervised
+heads -- RCSL, Gaussian RCSL, the autoregressive policy --, MOBILE's penalty and critic loss, and the dynamic power-of-two scale),
+written from the formulas of the reference that the kernel comments cite -- not from the kernel code.
 
 ``BV`` is a float64 array that carries, element by element, a first-order bound on what fp32 arithmetic may lose when it evaluates
 the same expression on the same fp32 operands (u = 2^-24, the unit roundoff of fp32):
@@ -526,3 +527,166 @@ def edac_t0(gamma, w0_action_rows, mask):
     ensemble's first layer [K, A, N0], mask [K, B, N0] = 1[h_0 > 0].  An A-term sum by one thread per element; exactly 0 where the mask is."""
     prod = BV.exact(np.asarray(gamma, np.float32)[:, :, :, None]) * BV.exact(np.asarray(w0_action_rows, np.float32)[:, None, :, :])
     return where(np.asarray(mask, bool), sum_(prod, axis=2, sequential=True), 0.0)
+
+
+# =====================================================================================================================================
+# the supervised heads -- RCSL (policy/rcsl/rcsl.py:123-151), Gaussian RCSL (rcsl_gauss.py:123-154 on dist_module.py:80-93), the
+# autoregressive policy (policy/others/autoregressive.py:28-54, :64-96) -- and MOBILE (policy/model_based/mobile.py:130-167).
+# ``valid`` (bool [B], default: every row): the rows of an ordered epoch's step that are no padding; every mean divides by
+# valid rows x A, as the reference's partial last batch does.
+# =====================================================================================================================================
+RG_LO, RG_HI = -5.0, 2.0                  # DiagGaussian's sigma_min / sigma_max
+LEAKY_SLOPE = 0.01                        # nn.LeakyReLU's default
+HALF_LOG_2PI = float(f32(0.9189385332046727))
+RG_HEAD = ("dist_net.mu.weight", "dist_net.mu.bias", "dist_net.sigma.weight", "dist_net.sigma.bias")      # the arena's order
+
+
+def _valid(valid, B):
+    return np.ones(B, bool) if valid is None else np.asarray(valid, bool).reshape(B)
+
+
+def rcsl_loss(pred, act, valid=None):
+    """rcsl.py:139-141: L = mean over (valid rows x A) of (pred - a)^2 ; dL/dpred = 2 (pred - a) / (valid rows x A), exactly 0 on a padding
+    row.  pred, act [B, A] fp32.  Returns (L, dpred [B, A])."""
+    pred = np.asarray(pred, np.float32)
+    B, A = pred.shape
+    v = _valid(valid, B)[:, None]
+    cnt = float(int(v.sum()) * A)
+    d = BV.exact(pred) - BV.exact(act)
+    return sum_(where(v, d * d, 0.0).reshape(-1)) / cnt, where(v, 2.0 * d / cnt, 0.0)
+
+
+def _chain(terms):
+    """one thread's multiply-add chain over the last axis (``sequential`` sum of the products, the bias being the first term)"""
+    return sum_(terms, axis=terms.v.ndim - 1, sequential=True)
+
+
+def _affine(z, w, b):
+    """z [B, K] fp32, w [A, K], b [A] -> b + z w^T [B, A]"""
+    prod = BV.exact(np.asarray(z, np.float32)[:, None, :]) * BV.exact(np.asarray(w, np.float32)[None, :, :])
+    bias = np.broadcast_to(np.asarray(b, np.float64).reshape(1, -1, 1), prod.v.shape[:2] + (1,))
+    out = _chain(BV(np.concatenate([bias, prod.v], axis=2), np.concatenate([np.zeros_like(bias), prod.e], axis=2)))
+    return BV(out.v, np.where((prod.v == 0).all(axis=2), 0.0, out.e))      # every product exactly 0 (a zeroed head): the bias itself, exact
+
+
+def rcslg_head(z, act, head, valid=None, raw32=None, logvar32=None):
+    """rcsl_gauss.py:139-146 on dist_module.py:80-93: mu = W_mu z + b_mu ; s = clamp(W_sigma z + b_sigma, -5, 2), read as a log-variance ;
+    L = mean((mu - a)^2 e^-s) + mean(s) over valid rows x A ; and its autograd: dmu = 2 (mu - a) e^-s / cnt ; ds = (1 - (mu - a)^2 e^-s) / cnt
+    where the clamp passes the gradient (-5 <= raw <= 2, BOTH ends included: torch.clamp's backward), exactly 0 elsewhere and on padding
+    rows ; dz = dmu W_mu + ds W_sigma ; head gradients = sums over the rows (one thread adds them one after the other).
+    The clamp's branch is the one fp32 took: ``raw32`` -- the fp32 pre-clamp values -- decides it where they are at hand (the CPU proof);
+    the engine stores only the clamped value ``logvar32``: strictly inside (-5, 2) that IS the raw value and the gate is open; on an end
+    the raw value was on or beyond it, and the gate is open only where the float64 raw value equals the end within its own bound (a
+    constant head's raw value is its bias, with bound 0: the comparison is then exact).
+    z, act [B, A] fp32 ; head: the four tensors by name.  Returns dict(mu, logvar, loss, dmu, ds, dz, grads{name: BV})."""
+    z = np.asarray(z, np.float32)
+    B, A = z.shape
+    v = _valid(valid, B)[:, None]
+    cnt = float(int(v.sum()) * A)
+    w_mu, b_mu, w_sg, b_sg = (np.asarray(head[k], np.float32) for k in RG_HEAD)
+    mu, raw = _affine(z, w_mu, b_mu), _affine(z, w_sg, b_sg)
+    lo, hi = f32(RG_LO), f32(RG_HI)
+    if raw32 is not None:
+        r32 = np.asarray(raw32, np.float32).reshape(B, A)
+        at_lo, at_hi, gate = r32 <= lo, r32 >= hi, (r32 >= lo) & (r32 <= hi)
+    elif logvar32 is not None:
+        s32 = np.asarray(logvar32, np.float32).reshape(B, A)
+        at_lo, at_hi = s32 == lo, s32 == hi
+        on_end = np.abs(raw.v - np.where(at_lo, RG_LO, RG_HI)) <= FACTOR * raw.e
+        gate = ~(at_lo | at_hi) | on_end
+    else:
+        r32 = raw.v.astype(np.float32)
+        at_lo, at_hi, gate = r32 <= lo, r32 >= hi, (r32 >= lo) & (r32 <= hi)
+    s = where(at_lo, RG_LO, where(at_hi, RG_HI, raw))
+    inv = BV.exact(1.0) / cnt
+    d = mu - BV.exact(act)
+    iv = exp(-s)
+    q = d * d * iv
+    loss = sum_(where(v, q + s, 0.0).reshape(-1)) * inv
+    dmu = where(v, 2.0 * d * iv * inv, 0.0)
+    ds = where(v & gate, (1.0 - q) * inv, 0.0)
+    # dz[i, k] = sum_a W_mu[a, k] dmu[i, a] + W_sigma[a, k] ds[i, a]: 2 A products, one chain
+    pm = dmu.reshape(B, 1, A) * BV.exact(w_mu.T[None])
+    ps = ds.reshape(B, 1, A) * BV.exact(w_sg.T[None])
+    dz = _chain(BV(np.stack([ps.v, pm.v], axis=3).reshape(B, A, 2 * A), np.stack([ps.e, pm.e], axis=3).reshape(B, A, 2 * A)))
+    dz = where(v, dz, 0.0)                # (products with the exact zeros of a padding row add up to exactly 0)
+    zb = BV.exact(z)
+    grads = {}
+    for name, g in zip(RG_HEAD, (dmu, dmu, ds, ds)):
+        if name.endswith("weight"):
+            t = g.reshape(B, A, 1) * zb.reshape(B, 1, A)                # [i, a, k]
+            grads[name] = sum_(t, axis=0, sequential=True)
+        else:
+            grads[name] = sum_(g, axis=0, sequential=True)
+    return dict(mu=mu, logvar=s, loss=loss, dmu=dmu, ds=ds, dz=dz, grads=grads, gate=gate)
+
+
+def leaky(z):
+    """nn.LeakyReLU(0.01) on fp32 operands: the branch is the operand's own sign, and exactly 0 takes the slope branch (torch: x > 0 ? x : 0.01 x).
+    Returns (value, slope the backward multiplies by)."""
+    z = np.asarray(z, np.float32)
+    pos = z > 0
+    return where(pos, BV.exact(z), BV.exact(LEAKY_SLOPE) * BV.exact(z)), where(pos, 1.0, BV.exact(LEAKY_SLOPE))
+
+
+def autoreg_head(z, target, A, valid=None):
+    """autoregressive.py:64-96 behind the net's last LeakyReLU: out = leaky(z_tail) = (mean, logstd) of expanded row m = j B + b ;
+    L = mean over valid expanded rows of logstd + ((t - mean) e^-logstd)^2 / 2 + log(2 pi) / 2 ; dz_tail = dL/dout leaky'(z_tail).
+    A padding batch row b invalidates its A expanded rows m = j B + b (m % B == b).  z [A B, 2], target [A B] fp32.
+    Returns (out [M, 2], L, dz [M, 2])."""
+    z = np.asarray(z, np.float32)
+    M = z.shape[0]
+    B = M // A
+    v = np.tile(_valid(valid, B), A)
+    inv = BV.exact(1.0) / float(int(v.sum()))
+    out, slope = leaky(z)
+    mean, ls = out[:, 0], out[:, 1]
+    ist = exp(-ls)
+    d = (BV.exact(target) - mean) * ist
+    loss = sum_(where(v, ls + 0.5 * d * d + HALF_LOG_2PI, 0.0)) * inv
+    g0 = where(v, -(d * ist) * inv * slope[:, 0], 0.0)
+    g1 = where(v, (1.0 - d * d) * inv * slope[:, 1], 0.0)
+    return out, loss, stack([g0, g1], axis=1)
+
+
+def autoreg_draw(z, eps):
+    """autoregressive.py:28-54, one pass: a_j = mean + e^logstd eps_j with (mean, logstd) = leaky(z_tail).  z [n, 2], eps [n] fp32."""
+    out, _ = leaky(z)
+    return out[:, 0] + exp(out[:, 1]) * BV.exact(eps)
+
+
+def lcb_penalty(ql, B, S, E, real_rows):
+    """compute_lcb (mobile.py:130-142) behind the target critics: ql [2, S E B] fp32 on the sample rows (s E + e) B + b.
+    qmin = min(Q1, Q2) (exact) ; m[e, b] = mean over the S samples ; penalty[b] = the unbiased standard deviation of m over the E elites
+    (torch.std), and the leading ``real_rows`` entries are 0 (mobile.py:154).  Returns (qmin [S E B] fp32, penalty [B])."""
+    ql = np.asarray(ql, np.float32)
+    qmin = ql.min(axis=0)
+    m = sum_(BV.exact(qmin.reshape(S, E, B)), axis=0, sequential=True) / float(S)
+    d = m - (sum_(m, axis=0, sequential=True) / float(E)).reshape(1, B)
+    pen = sqrt(sum_(d * d, axis=0, sequential=True) / float(E - 1))
+    return qmin, where(np.arange(B) < real_rows, 0.0, pen)
+
+
+def mobile_td_loss(q, qt, rew, term, pen, gamma, pen_coef, B, logp_next=None, alpha=None, stored=None):
+    """mobile.py:151-167: y = clamp((r - c pen) + gamma (1 - d) (min(Qt1, Qt2) [- alpha logp']), 0, None) ; ONE loss = mean over (2, B) of
+    (q_c - y)^2, so dq_c = 2 (q_c - y) / (2 B).  ``stored``: the fp32 target the kernel stored -- loss and dq are then taken at it.
+    q, qt [2, B] fp32.  Returns (y [B], L, dq [2, B])."""
+    qt = np.asarray(qt, np.float32)
+    nq = BV.exact(qt.min(axis=0))
+    if logp_next is not None:
+        nq = nq - BV.exact(alpha) * BV.exact(logp_next)
+    y = maximum((BV.exact(rew) - BV.exact(pen_coef) * BV.exact(pen)) + BV.exact(gamma) * (1.0 - BV.exact(term)) * nq, 0.0)
+    inv = BV.exact(1.0) / float(2 * B)
+    d = BV.exact(q) - (y if stored is None else BV.exact(stored)).reshape(1, -1)
+    return y, sum_(sum_(d * d, axis=1), sequential=True) * inv, 2.0 * d * inv
+
+
+def pow2_scale(a):
+    """the dynamic scale of a split-precision backward pass (csrc/kernels.h: 2^(3 - floor(log2 a)) for the seed's largest magnitude a, so
+    that a * scale lands in [8, 16); 1 for 0 and for a non-finite a; the exponent is kept within +-100 so that the scale is an fp32
+    number).  A power of two: exact, compared with ==."""
+    a = float(np.float32(a))
+    if not (a > 0.0) or not (a < 3.0e38):
+        return 1.0
+    e = math.frexp(a)[1] - 1                  # floor(log2 a), subnormals included
+    return math.ldexp(1.0, 3 - max(-100, min(100, e)))

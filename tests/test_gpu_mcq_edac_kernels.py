@@ -40,7 +40,7 @@ Measured worst |err| / bound over the whole module (MI355X; the bar is 4, a corr
 Every figure sits below 1, i.e. inside the first-order bound itself, a factor 4 inside the bar.  t_0 launches seen: both launches with
 both mask sources.
 
-Still open: the dynamic-scale kernels k_grad_scale / grad_scale_publish -- the scale slots are not reachable through any tap."""
+The dynamic-scale kernels k_grad_scale / grad_scale_publish of these two schedules are held by tests/test_gpu_headmob_kernels.py (tap ``"gscale"``)."""
 import numpy as np
 import pytest
 
