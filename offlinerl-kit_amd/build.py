@@ -20,7 +20,8 @@ GEMM_H = ["gemm.h", "gemm_kernel.h"]
 WS_H = ["gemm.h", "ws_gemm.h", "ws_device.h"]
 # translation unit -> headers it depends on
 UNITS = {
-    "engine.hip": ["engine.h", "devobj.h", "gemm.h", "ws_gemm.h", "small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "kernels.h", "rng.h", "algo_cql.inc", "algo_iql.inc", "algo_td3bc.inc", "algo_edac.inc", "algo_sac.inc", "algo_mcq.inc", "algo_mobile.inc", "algo_rcsl.inc", "algo_rcsl_gauss.inc", "algo_autoreg.inc", "algo_rambo.inc", ABI],
+    "engine.hip": ["engine.h", "devobj.h", "gemm.h", "ws_gemm.h", "small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "kernels.h", "store.h", "rng.h", "algo_cql.inc", "algo_iql.inc", "algo_td3bc.inc", "algo_edac.inc", "algo_sac.inc", "algo_mcq.inc", "algo_mobile.inc", "algo_rcsl.inc", "algo_rcsl_gauss.inc", "algo_autoreg.inc", "algo_rambo.inc", ABI],
+    "store.hip": ["store.h", "devobj.h", "gemm.h", "rng.h", ABI],
     "gemm_inst_fwd.hip": GEMM_H,
     "gemm_inst_plain.hip": GEMM_H,
     "gemm_inst_rank1.hip": GEMM_H,
@@ -87,6 +88,14 @@ def _compile(unit, hipcc, verbose, objdir=None, defines=()):
     return obj
 
 
+def _jobs():
+    """compile jobs: one per unit, within the machine's CPUs and within MAX_JOBS where that is set (a job on a shared machine may
+    use fewer CPUs than os.cpu_count() reports)"""
+    jobs = min(len(UNITS), max(1, (os.cpu_count() or 2) - 1))
+    cap = os.environ.get("MAX_JOBS", "")
+    return max(1, min(jobs, int(cap))) if cap.isdigit() else jobs
+
+
 def build(force=False, verbose=True, jobs=None):
     if not force and not needs_build():
         return LIB
@@ -97,8 +106,7 @@ def build(force=False, verbose=True, jobs=None):
             if os.path.exists(_obj(u) + ".srchash"):
                 os.remove(_obj(u) + ".srchash")
     h = source_hash()                      # hash what is about to be compiled
-    jobs = jobs or min(len(UNITS), max(1, (os.cpu_count() or 2) - 1))
-    with ThreadPoolExecutor(max_workers=jobs) as ex:
+    with ThreadPoolExecutor(max_workers=jobs or _jobs()) as ex:
         objs = list(ex.map(lambda u: _compile(u, hipcc, verbose), UNITS))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
@@ -115,7 +123,7 @@ def build_variant(name, defines, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(OBJ, name)
     os.makedirs(objdir, exist_ok=True)
-    with ThreadPoolExecutor(max_workers=min(len(UNITS), max(1, (os.cpu_count() or 2) - 1))) as ex:
+    with ThreadPoolExecutor(max_workers=_jobs()) as ex:
         objs = list(ex.map(lambda u: _compile(u, hipcc, verbose, objdir, tuple(defines)), UNITS))
     lib = os.path.join(HERE, f"liborlengine_{name}.so")
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)

@@ -17,6 +17,7 @@ namespace orl {
 
 void set_error(const std::string& msg);   // engine.hip: the text orl_last_error() returns
 int fail(const std::string& msg);         // set_error, returns -1
+// store.hip: the dataset rows a DiffusionBC gathers (device, dims, pitches, size, the obs / act arrays)
 void buffer_view(const orl_buffer* b, int* dev, int* od, int* ad, int* OP, int* AP, long* n, const float** obs, const float** act);
 
 // The adversarial pair of an orl_dynamics (dynamics.hip) as the RAMBO device loop of engine.hip drives it: the launches of

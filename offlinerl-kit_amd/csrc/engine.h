@@ -9,6 +9,7 @@
 
 #include "devobj.h"
 #include "kernels.h"
+#include "store.h"
 #include "ws_gemm.h"
 #include "small_fwd.h"
 #include "small_bwd.h"
@@ -70,42 +71,6 @@ struct ProfEntry {
   double flops;
   double bytes = 0;   // algorithmic HBM bytes of the launch (operands read once + results written once)
   hipEvent_t a, b;
-};
-
-struct Buffer {             // HBM-resident replay buffer (buffer/buffer.py)
-  int dev = 0, od = 0, ad = 0, OP = 0, AP = 0;
-  long n = 0;
-  float *obs = nullptr, *nobs = nullptr, *act = nullptr, *rew = nullptr, *term = nullptr;
-  long long* idx = nullptr; long idx_cap = 0;
-  unsigned long long counter = 0;
-  float absmax = -1.f; unsigned long long absmax_gen = ~0ull;   // max |obs|, |next_obs|, |act| of generation absmax_gen (engines at precision 1 ask for it)
-  float rew_absmax = -1.f; unsigned long long rew_absmax_gen = ~0ull;   // max |rew| likewise (RCSL engines: the column holds the return-to-go, an MFMA operand)
-  unsigned long long gen = 0;   // bumped by every orl_buffer_load / orl_buffer_reserve: engines re-capture graphs that hold the old dataset pointers / size
-  // growable ring (orl_buffer_reserve): `cap` rows allocated once, rows land at (ptr + i) % cap, n = min(n + i, cap) as in add_batch
-  // (buffer.py:52-70).  d_n mirrors n in a device cell: kernels that sample the ring as the MODEL source read the size from it, so a
-  // captured graph stays valid while the ring grows.
-  long cap = 0, ptr = 0;
-  long long* d_n = nullptr;
-  int* roll_alive = nullptr; double* roll_rew = nullptr; long roll_blocks = 0;   // per-block scratch of k_roll_term / k_roll_scatter, then 2 result cells
-  // orl_buffer_append_rollout_runs keeps its scratch with the FIRST ring of the call: [runs] ring table, [runs] alive counts, [runs]
-  // reward sums (the two read back in one copy), then [runs][blocks] reward sums and alive counts
-  void* runs_scratch = nullptr; long runs_scratch_runs = 0, runs_scratch_blocks = 0;
-  ~Buffer();
-};
-
-struct Traj {               // HBM-resident trajectory store of the RCSL rollout (policy/rcsl/rcsl.py:57-120): orl_traj
-  int dev = 0, od = 0, ad = 0, OP = 0, AP = 0;
-  long n_traj_cap = 0, cap = 0;           // sizes given at creation: trajectories, rows
-  long n_traj = 0, rows = 0, live = 0;    // of the current rollout: trajectories, rows appended, trajectories still running
-  int half = 0;                           // which of the two live arrays holds the running trajectories
-  bool finished = false;                  // rtg[] is valid for rows [0, rows)
-  float *obs = nullptr, *nobs = nullptr, *act = nullptr, *rew = nullptr, *term = nullptr;
-  int* tidx = nullptr; double *acc = nullptr, *rtg = nullptr;
-  double* returns = nullptr;
-  int* live_idx[2] = {nullptr, nullptr}; double* live_acc[2] = {nullptr, nullptr};
-  int* blk_cnt = nullptr; double* blk_rew = nullptr;      // per-block scratch: max(blocks of a step, blocks of an export)
-  long long* cells = nullptr; double* rew_total = nullptr; // 3 result cells, the running reward sum
-  ~Traj();
 };
 
 struct DY;  // backward seed description (engine.hip)

@@ -207,26 +207,6 @@ static int build_layouts(const orl_config& c, NetLayout* lay, long* net_off, boo
 }
 
 // ---------------------------------------------------------------------------------------------
-// Buffer
-// ---------------------------------------------------------------------------------------------
-Buffer::~Buffer() {
-  hipSetDevice(dev);
-  for (float* p : {obs, nobs, act, rew, term}) if (p) hipFree(p);
-  if (idx) hipFree(idx);
-  if (d_n) hipFree(d_n);
-  if (roll_alive) hipFree(roll_alive);
-  if (roll_rew) hipFree(roll_rew);
-  if (runs_scratch) hipFree(runs_scratch);
-}
-Traj::~Traj() {
-  hipSetDevice(dev);
-  for (void* p : {(void*)obs, (void*)nobs, (void*)act, (void*)rew, (void*)term, (void*)tidx, (void*)acc, (void*)rtg, (void*)returns,
-                  (void*)live_idx[0], (void*)live_idx[1], (void*)live_acc[0], (void*)live_acc[1], (void*)blk_cnt, (void*)blk_rew,
-                  (void*)cells, (void*)rew_total})
-    if (p) hipFree(p);
-}
-
-// ---------------------------------------------------------------------------------------------
 // Engine basics
 // ---------------------------------------------------------------------------------------------
 Engine::~Engine() {
@@ -1301,19 +1281,16 @@ int Engine::enqueue_sample() {
   if (!buf || !buf->obs) return fail("no replay buffer attached (orl_engine_attach_buffer)");
   GatherP g;
   memset(&g, 0, sizeof(g));
-  g.obs = buf->obs; g.nobs = buf->nobs; g.act = buf->act; g.rew = buf->rew; g.term = buf->term; g.n = buf->n;
-  g.OP = buf->OP; g.AP = buf->AP; g.od = od; g.ad = ad; g.B = B; g.W = std::max(OP, AP);
+  g.src = *buf; g.n = buf->n;
+  g.B = B; g.W = std::max(OP, AP);
   Mat o2 = W("b_obs2");
   g.b_obs = o2.p; g.b_nobs = o2.p + (long)B * OP; g.obs_rs = o2.rs; g.nobs_rs = o2.rs; g.d_op = OP;
   g.b_act = W("b_act").p; g.act_rs = W("b_act").rs; g.d_ap = AP;
   g.b_rew = W("b_rew").p; g.rew_rs = W("b_rew").rs; g.b_term = W("b_term").p; g.term_rs = W("b_term").rs;
   g.seed = cfg.seed; g.gstep = gstep;
-  if (mbuf) {
-    g.m_obs = mbuf->obs; g.m_nobs = mbuf->nobs; g.m_act = mbuf->act; g.m_rew = mbuf->rew; g.m_term = mbuf->term;
-    g.m_n = mbuf->d_n; g.real_rows = mbuf_real_rows;
-  }
-  if (!mbufs.empty()) {      // per-run rings: the table carries the sources, m_obs only says that there is a model source
-    g.m_tab = m_tab; g.m_obs = mbufs[0]->obs; g.real_rows = mbuf_real_rows;
+  if (mbuf) { g.m = mbuf->model_src(); g.real_rows = mbuf_real_rows; }
+  if (!mbufs.empty()) {      // per-run rings: the table carries the sources, m.obs only says that there is a model source
+    g.m_tab = m_tab; g.m.obs = mbufs[0]->obs; g.real_rows = mbuf_real_rows;
   }
   ORL_LAUNCH("gather", k_gather, dim3((unsigned)(((long)B * g.W + 255) / 256), R), dim3(256), g);
   return 0;
@@ -1482,19 +1459,6 @@ using namespace orl;
 struct orl_engine {
   Engine e;
 };
-struct orl_buffer {
-  Buffer b;
-};
-struct orl_traj {
-  Traj t;
-};
-namespace orl {
-// diffusion.hip: the dataset rows a DiffusionBC gathers (device, dims, pitches, size, the obs / act arrays)
-void buffer_view(const orl_buffer* b, int* dev, int* od, int* ad, int* OP, int* AP, long* n, const float** obs, const float** act) {
-  *dev = b->b.dev; *od = b->b.od; *ad = b->b.ad; *OP = b->b.OP; *AP = b->b.AP; *n = b->b.n; *obs = b->b.obs; *act = b->b.act;
-}
-}  // namespace orl
-
 extern "C" {
 
 const char* orl_last_error(void) { return g_err.c_str(); }
@@ -1662,518 +1626,28 @@ int orl_set_step_count(orl_engine* h, int64_t steps) {
   return 0;
 }
 
-// ---- replay buffer ----
-int orl_buffer_create(int32_t obs_dim, int32_t act_dim, int32_t device, orl_buffer** out) {
-  if (!out || obs_dim < 1 || act_dim < 1) return fail("orl_buffer_create: bad arguments");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device available: the replay buffer lives in MI355X HBM");
-  if (device < 0 || device >= ndev) return fail("bad device ordinal");
-  orl_buffer* h = new orl_buffer();
-  h->b.dev = device; h->b.od = obs_dim; h->b.ad = act_dim; h->b.OP = rup(obs_dim, 4); h->b.AP = rup(act_dim, 4);
-  *out = h;
-  return 0;
-}
-void orl_buffer_destroy(orl_buffer* h) { delete h; }
-static int upload_padded(float** dst, const float* src, long n, int dim, int pitch) {
-  ORL_HIP(hipMalloc((void**)dst, sizeof(float) * n * pitch));
-  ORL_HIP(hipMemset(*dst, 0, sizeof(float) * n * pitch));
-  ORL_HIP(hipMemcpy2D(*dst, sizeof(float) * pitch, src, sizeof(float) * dim, sizeof(float) * dim, n, hipMemcpyHostToDevice));
-  return 0;
-}
-int orl_buffer_load(orl_buffer* h, const float* obs, const float* act, const float* next_obs, const float* rew, const float* term, int64_t n) {
-  Buffer& b = h->b;
-  if (n <= 0) return fail("empty dataset");
-  ORL_HIP(hipSetDevice(b.dev));
-  for (float** p : {&b.obs, &b.nobs, &b.act, &b.rew, &b.term}) if (*p) { hipFree(*p); *p = nullptr; }
-  if (upload_padded(&b.obs, obs, n, b.od, b.OP)) return -1;
-  if (upload_padded(&b.nobs, next_obs, n, b.od, b.OP)) return -1;
-  if (upload_padded(&b.act, act, n, b.ad, b.AP)) return -1;
-  if (upload_padded(&b.rew, rew, n, 1, 1)) return -1;
-  if (upload_padded(&b.term, term, n, 1, 1)) return -1;
-  b.n = n;
-  b.cap = 0; b.ptr = 0;  // (a loaded dataset is not a ring)
-  if (b.d_n) { const long long nn = n; ORL_HIP(hipMemcpy(b.d_n, &nn, sizeof(nn), hipMemcpyHostToDevice)); }
-  b.gen++;               // the arrays moved: engines that captured them re-capture (orl_learn_n)
-  return 0;
-}
-
-// ---- growable ring ----
-static int ring_publish(Buffer& b) {
-  const long long nn = b.n;
-  ORL_HIP(hipMemcpy(b.d_n, &nn, sizeof(nn), hipMemcpyHostToDevice));
-  ORL_HIP(hipDeviceSynchronize());        // the appended rows and the new size are visible to every stream of the process
-  b.absmax_gen = ~0ull; b.rew_absmax_gen = ~0ull;
-  return 0;
-}
-int orl_buffer_reserve(orl_buffer* h, int64_t capacity) {
-  if (!h || capacity < 1) return fail("orl_buffer_reserve: bad arguments");
-  Buffer& b = h->b;
-  ORL_HIP(hipSetDevice(b.dev));
-  ORL_HIP(hipDeviceSynchronize());
-  for (float** p : {&b.obs, &b.nobs, &b.act, &b.rew, &b.term}) if (*p) { hipFree(*p); *p = nullptr; }
-  const long pitch[5] = {b.OP, b.OP, b.AP, 1, 1};
-  float** arr[5] = {&b.obs, &b.nobs, &b.act, &b.rew, &b.term};
-  for (int k = 0; k < 5; ++k) {
-    ORL_HIP(hipMalloc((void**)arr[k], sizeof(float) * capacity * pitch[k]));
-    ORL_HIP(hipMemset(*arr[k], 0, sizeof(float) * capacity * pitch[k]));
-  }
-  if (!b.d_n) ORL_HIP(hipMalloc((void**)&b.d_n, sizeof(long long)));
-  b.cap = capacity; b.ptr = 0; b.n = 0;
-  b.gen++;
-  return ring_publish(b);
-}
-// rows [0, n) of a packed source -> ring rows (ptr + i) % cap: at most two contiguous pieces
-static int ring_copy(float* dst, int pitch, const float* src, int dim, long cap, long ptr, long n, hipMemcpyKind kind) {
-  const long first = std::min(n, cap - ptr);
-  ORL_HIP(hipMemcpy2D(dst + ptr * pitch, sizeof(float) * pitch, src, sizeof(float) * dim, sizeof(float) * dim, first, kind));
-  if (n > first)
-    ORL_HIP(hipMemcpy2D(dst, sizeof(float) * pitch, src + first * dim, sizeof(float) * dim, sizeof(float) * dim, n - first, kind));
-  return 0;
-}
-int orl_buffer_append(orl_buffer* h, const float* obs, const float* act, const float* next_obs, const float* rew, const float* term,
-                      int64_t n, int on_device) {
-  if (!h || !obs || !act || !next_obs || !rew || !term || n < 1) return fail("orl_buffer_append: bad arguments");
-  Buffer& b = h->b;
-  if (b.cap < 1) return fail("orl_buffer_append: not a ring (orl_buffer_reserve first)");
-  if (n > b.cap) return fail("orl_buffer_append: more rows than the ring's capacity");
-  ORL_HIP(hipSetDevice(b.dev));
-  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  if (ring_copy(b.obs, b.OP, obs, b.od, b.cap, b.ptr, n, kind)) return -1;
-  if (ring_copy(b.nobs, b.OP, next_obs, b.od, b.cap, b.ptr, n, kind)) return -1;
-  if (ring_copy(b.act, b.AP, act, b.ad, b.cap, b.ptr, n, kind)) return -1;
-  if (ring_copy(b.rew, 1, rew, 1, b.cap, b.ptr, n, kind)) return -1;
-  if (ring_copy(b.term, 1, term, 1, b.cap, b.ptr, n, kind)) return -1;
-  b.ptr = (b.ptr + n) % b.cap;
-  b.n = std::min(b.n + (long)n, b.cap);
-  return ring_publish(b);
-}
-int orl_buffer_append_rollout(orl_buffer* h, int32_t term_kind, const float* obs, const float* act, const float* next_obs, const float* rew,
-                              int64_t n, float* alive_next_obs, int64_t* n_alive, double* rew_sum) {
-  if (!h || !obs || !act || !next_obs || !rew || !alive_next_obs || !n_alive || !rew_sum || n < 1) return fail("orl_buffer_append_rollout: bad arguments");
-  Buffer& b = h->b;
-  if (b.cap < 1) return fail("orl_buffer_append_rollout: not a ring (orl_buffer_reserve first)");
-  if (n > b.cap) return fail("orl_buffer_append_rollout: more rows than the ring's capacity");
-  if (term_kind < 0 || term_kind >= ORL_TERM_KINDS) return fail("orl_buffer_append_rollout: unknown termination kind");
-  const int need = term_kind == ORL_TERM_PEN ? 27 : ((term_kind == ORL_TERM_HOPPER || term_kind == ORL_TERM_WALKER2D) ? 2 : 1);
-  if (b.od < need) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "orl_buffer_append_rollout: termination kind %d reads observation column %d, the buffer has %d columns", (int)term_kind, need - 1, b.od);
-    return fail(msg);
-  }
-  if (alive_next_obs == next_obs) return fail("orl_buffer_append_rollout: alive_next_obs must not overlap next_obs");
-  ORL_HIP(hipSetDevice(b.dev));
-  const long blocks = (n + 255) / 256;
-  if (blocks > b.roll_blocks) {
-    if (b.roll_alive) hipFree(b.roll_alive);
-    if (b.roll_rew) hipFree(b.roll_rew);
-    b.roll_alive = nullptr; b.roll_rew = nullptr; b.roll_blocks = 0;
-    ORL_HIP(hipMalloc((void**)&b.roll_alive, sizeof(int) * blocks + sizeof(long long) * 2));
-    ORL_HIP(hipMalloc((void**)&b.roll_rew, sizeof(double) * (blocks + 1)));
-    b.roll_blocks = blocks;
-  }
-  RollP p;
-  memset(&p, 0, sizeof(p));
-  p.kind = term_kind; p.obs = obs; p.act = act; p.nobs = next_obs; p.rew = rew; p.row_stride = n; p.od = b.od; p.ad = b.ad;
-  RollRing& g = p.ring;
-  g.obs = b.obs; g.nobs = b.nobs; g.act = b.act; g.rew = b.rew; g.term = b.term; g.OP = b.OP; g.AP = b.AP; g.cap = b.cap; g.ptr = b.ptr; g.n = n;
-  p.alive_nobs = alive_next_obs;
-  p.blk_alive = b.roll_alive; p.blk_rew = b.roll_rew;
-  p.n_alive_out = (long long*)(b.roll_alive + ((b.roll_blocks + 1) & ~1L));      // 8-byte aligned, behind the block counts
-  p.rew_sum_out = b.roll_rew + b.roll_blocks;
-  hipLaunchKernelGGL(k_roll_term, dim3((unsigned)blocks), dim3(256), 0, 0, p);
-  hipLaunchKernelGGL(k_roll_scatter, dim3((unsigned)blocks), dim3(256), 0, 0, p);
-  ORL_HIP(hipGetLastError());
-  long long na = 0; double rs = 0.0;
-  ORL_HIP(hipMemcpy(&na, p.n_alive_out, sizeof(na), hipMemcpyDeviceToHost));
-  ORL_HIP(hipMemcpy(&rs, p.rew_sum_out, sizeof(rs), hipMemcpyDeviceToHost));
-  *n_alive = na; *rew_sum = rs;
-  b.ptr = (b.ptr + n) % b.cap;
-  b.n = std::min(b.n + (long)n, b.cap);
-  return ring_publish(b);
-}
-int orl_buffer_append_rollout_runs(orl_buffer* const* rings, int32_t n_runs, int32_t term_kind, const float* obs, const float* act,
-                                   const float* next_obs, const float* rew, int64_t row_stride, const int64_t* n, float* alive_next_obs,
-                                   int64_t* n_alive, double* rew_sum) {
-  const char* F = "orl_buffer_append_rollout_runs";
-  if (!rings || n_runs < 1 || !obs || !act || !next_obs || !rew || !alive_next_obs || !n || !n_alive || !rew_sum || row_stride < 1)
-    return fail(std::string(F) + ": bad arguments");
-  if (term_kind < 0 || term_kind >= ORL_TERM_KINDS) return fail(std::string(F) + ": unknown termination kind");
-  if (alive_next_obs == next_obs) return fail(std::string(F) + ": alive_next_obs must not overlap next_obs");
-  const int need = term_kind == ORL_TERM_PEN ? 27 : ((term_kind == ORL_TERM_HOPPER || term_kind == ORL_TERM_WALKER2D) ? 2 : 1);
-  char msg[224];
-  long nmax = 0;
-  for (int r = 0; r < n_runs; ++r) {
-    if (!rings[r]) { snprintf(msg, sizeof(msg), "%s: run %d: null ring", F, r); return fail(msg); }
-    const Buffer& b = rings[r]->b;
-    const Buffer& b0 = rings[0]->b;
-    for (int q = 0; q < r; ++q)
-      if (rings[q] == rings[r]) { snprintf(msg, sizeof(msg), "%s: run %d: the ring of run %d again (one ring per run)", F, r, q); return fail(msg); }
-    if (b.cap < 1) { snprintf(msg, sizeof(msg), "%s: run %d: not a ring (orl_buffer_reserve first)", F, r); return fail(msg); }
-    if (b.od != b0.od || b.ad != b0.ad || b.dev != b0.dev) {
-      snprintf(msg, sizeof(msg), "%s: run %d: dims / device (%d, %d, device %d) differ from run 0's (%d, %d, device %d)", F, r, b.od, b.ad, b.dev,
-               b0.od, b0.ad, b0.dev);
-      return fail(msg);
-    }
-    if (n[r] < 0 || n[r] > row_stride) { snprintf(msg, sizeof(msg), "%s: run %d: %lld rows do not fit the row stride %lld", F, r, (long long)n[r], (long long)row_stride); return fail(msg); }
-    if (n[r] > b.cap) { snprintf(msg, sizeof(msg), "%s: run %d: more rows than the ring's capacity", F, r); return fail(msg); }
-    if (b.od < need) {
-      snprintf(msg, sizeof(msg), "%s: run %d: termination kind %d reads observation column %d, the buffer has %d columns", F, r, (int)term_kind, need - 1, b.od);
-      return fail(msg);
-    }
-    nmax = std::max(nmax, (long)n[r]);
-  }
-  Buffer& b0 = rings[0]->b;
-  ORL_HIP(hipSetDevice(b0.dev));
-  const long R = n_runs, blocks = std::max(1L, (nmax + 255) / 256);
-  if (R > b0.runs_scratch_runs || blocks > b0.runs_scratch_blocks) {
-    const long cr = std::max(R, b0.runs_scratch_runs), cb = std::max(blocks, b0.runs_scratch_blocks);
-    if (b0.runs_scratch) hipFree(b0.runs_scratch);
-    b0.runs_scratch = nullptr; b0.runs_scratch_runs = 0; b0.runs_scratch_blocks = 0;
-    ORL_HIP(hipMalloc(&b0.runs_scratch, cr * (sizeof(RollRing) + 16) + cr * cb * 12));
-    b0.runs_scratch_runs = cr; b0.runs_scratch_blocks = cb;
-  }
-  // (every piece is a multiple of 8 bytes long except the last)
-  RollRing* tab = (RollRing*)b0.runs_scratch;
-  long long* out_n = (long long*)(tab + b0.runs_scratch_runs);
-  double* out_rew = (double*)(out_n + R);
-  double* blk_rew = (double*)(out_n + 2 * b0.runs_scratch_runs);
-  int* blk_alive = (int*)(blk_rew + b0.runs_scratch_runs * b0.runs_scratch_blocks);
-  std::vector<RollRing> host(R);
-  for (int r = 0; r < n_runs; ++r) {
-    const Buffer& b = rings[r]->b;
-    RollRing& g = host[r];
-    g.obs = b.obs; g.nobs = b.nobs; g.act = b.act; g.rew = b.rew; g.term = b.term; g.OP = b.OP; g.AP = b.AP; g.cap = b.cap; g.ptr = b.ptr;
-    g.n = n[r]; g.size_cell = b.d_n; g.size = std::min(b.n + (long)n[r], b.cap);
-  }
-  ORL_HIP(hipMemcpy(tab, host.data(), sizeof(RollRing) * R, hipMemcpyHostToDevice));
-  RollP p;
-  memset(&p, 0, sizeof(p));
-  p.kind = term_kind; p.obs = obs; p.act = act; p.nobs = next_obs; p.rew = rew; p.row_stride = row_stride; p.od = b0.od; p.ad = b0.ad;
-  p.tab = tab; p.alive_nobs = alive_next_obs; p.blk_alive = blk_alive; p.blk_rew = blk_rew; p.n_alive_out = out_n; p.rew_sum_out = out_rew;
-  hipLaunchKernelGGL(k_roll_term, dim3((unsigned)blocks, (unsigned)R), dim3(256), 0, 0, p);
-  hipLaunchKernelGGL(k_roll_scatter, dim3((unsigned)blocks, (unsigned)R), dim3(256), 0, 0, p);
-  ORL_HIP(hipGetLastError());
-  std::vector<long long> res(2 * R);          // [R] alive counts, then [R] reward sums (doubles): one read for both
-  ORL_HIP(hipMemcpy(res.data(), out_n, sizeof(long long) * 2 * R, hipMemcpyDeviceToHost));
-  for (int r = 0; r < n_runs; ++r) {
-    Buffer& b = rings[r]->b;
-    n_alive[r] = res[r];
-    memcpy(&rew_sum[r], &res[R + r], sizeof(double));
-    b.ptr = (b.ptr + n[r]) % b.cap;
-    b.n = std::min(b.n + (long)n[r], b.cap);     // (the kernel published the same value to the ring's size cell)
-    b.absmax_gen = ~0ull; b.rew_absmax_gen = ~0ull;
-  }
-  ORL_HIP(hipDeviceSynchronize());            // the appended rows and the new sizes are visible to every stream of the process
-  return 0;
-}
-int orl_buffer_read(orl_buffer* h, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term) {
-  if (!h || n < 1 || row0 < 0 || !obs || !act || !next_obs || !rew || !term) return fail("orl_buffer_read: bad arguments");
-  Buffer& b = h->b;
-  const long rows = b.cap > 0 ? b.cap : b.n;
-  if (!b.obs || row0 + n > rows) return fail("orl_buffer_read: rows beyond the store");
-  ORL_HIP(hipSetDevice(b.dev));
-  ORL_HIP(hipDeviceSynchronize());
-  ORL_HIP(hipMemcpy2D(obs, sizeof(float) * b.od, b.obs + row0 * b.OP, sizeof(float) * b.OP, sizeof(float) * b.od, n, hipMemcpyDeviceToHost));
-  ORL_HIP(hipMemcpy2D(next_obs, sizeof(float) * b.od, b.nobs + row0 * b.OP, sizeof(float) * b.OP, sizeof(float) * b.od, n, hipMemcpyDeviceToHost));
-  ORL_HIP(hipMemcpy2D(act, sizeof(float) * b.ad, b.act + row0 * b.AP, sizeof(float) * b.AP, sizeof(float) * b.ad, n, hipMemcpyDeviceToHost));
-  ORL_HIP(hipMemcpy(rew, b.rew + row0, sizeof(float) * n, hipMemcpyDeviceToHost));
-  ORL_HIP(hipMemcpy(term, b.term + row0, sizeof(float) * n, hipMemcpyDeviceToHost));
-  return 0;
-}
-int64_t orl_buffer_size(orl_buffer* h) { return h->b.n; }
-
-// ---- trajectory store (the RCSL rollout) ----
-static int traj_alloc_bytes(void** p, size_t bytes) {
-  ORL_HIP(hipMalloc(p, bytes));
-  ORL_HIP(hipMemset(*p, 0, bytes));
-  return 0;
-}
-#define traj_alloc(pp, n) traj_alloc_bytes((void**)(pp), sizeof(**(pp)) * (size_t)(n))
-static TrajP traj_params(Traj& t) {
-  TrajP p;
-  memset(&p, 0, sizeof(p));
-  p.obs = t.obs; p.nobs = t.nobs; p.act = t.act; p.rew = t.rew; p.term = t.term; p.tidx = t.tidx; p.acc = t.acc; p.rtg = t.rtg;
-  p.OP = t.OP; p.AP = t.AP; p.od = t.od; p.ad = t.ad; p.returns = t.returns; p.n_traj = t.n_traj;
-  p.live_idx = t.live_idx[t.half]; p.live_acc = t.live_acc[t.half]; p.next_idx = t.live_idx[t.half ^ 1]; p.next_acc = t.live_acc[t.half ^ 1];
-  p.blk_cnt = t.blk_cnt; p.blk_rew = t.blk_rew; p.cells = t.cells; p.rew_total = t.rew_total;
-  return p;
-}
-int orl_traj_create(int32_t obs_dim, int32_t act_dim, int32_t device, int64_t n_traj, int64_t capacity_rows, orl_traj** out) {
-  if (!out || obs_dim < 1 || act_dim < 1 || n_traj < 1 || capacity_rows < 1 || n_traj > 0x7fffffffLL || capacity_rows > 0x7fffffffLL)
-    return fail("orl_traj_create: bad arguments");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device available: the trajectory store lives in MI355X HBM");
-  if (device < 0 || device >= ndev) return fail("bad device ordinal");
-  ORL_HIP(hipSetDevice(device));
-  orl_traj* h = new orl_traj();
-  Traj& t = h->t;
-  t.dev = device; t.od = obs_dim; t.ad = act_dim; t.OP = rup(obs_dim, 4); t.AP = rup(act_dim, 4);
-  t.n_traj_cap = n_traj; t.cap = capacity_rows;
-  const long blocks = (std::max((long)n_traj, (long)capacity_rows) + 255) / 256;
-  if (traj_alloc(&t.obs, t.cap * t.OP) || traj_alloc(&t.nobs, t.cap * t.OP) || traj_alloc(&t.act, t.cap * t.AP) || traj_alloc(&t.rew, t.cap) ||
-      traj_alloc(&t.term, t.cap) || traj_alloc(&t.tidx, t.cap) || traj_alloc(&t.acc, t.cap) || traj_alloc(&t.rtg, t.cap) ||
-      traj_alloc(&t.returns, n_traj) || traj_alloc(&t.live_idx[0], n_traj) || traj_alloc(&t.live_idx[1], n_traj) ||
-      traj_alloc(&t.live_acc[0], n_traj) || traj_alloc(&t.live_acc[1], n_traj) || traj_alloc(&t.blk_cnt, blocks) ||
-      traj_alloc(&t.blk_rew, blocks) || traj_alloc(&t.cells, 3) || traj_alloc(&t.rew_total, 1)) {
-    delete h;
-    *out = nullptr;
-    return -1;
-  }
-  *out = h;
-  return orl_traj_reset(h, n_traj);
-}
-void orl_traj_destroy(orl_traj* h) { delete h; }
-int orl_traj_reset(orl_traj* h, int64_t n_traj) {
-  if (!h || n_traj < 1) return fail("orl_traj_reset: bad arguments");
-  Traj& t = h->t;
-  if (n_traj > t.n_traj_cap) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "orl_traj_reset: %lld trajectories, the store was created for %lld", (long long)n_traj, (long long)t.n_traj_cap);
-    return fail(msg);
-  }
-  ORL_HIP(hipSetDevice(t.dev));
-  t.n_traj = n_traj; t.rows = 0; t.live = n_traj; t.half = 1; t.finished = false;
-  TrajP p = traj_params(t);                 // (half = 1: the kernel fills the `next` half, 0, which then becomes the current one)
-  hipLaunchKernelGGL(k_traj_reset, dim3((unsigned)((n_traj + 255) / 256)), dim3(256), 0, 0, p);
-  ORL_HIP(hipGetLastError());
-  t.half = 0;
-  return 0;
-}
-int orl_traj_append_step(orl_traj* h, int32_t term_kind, const float* obs, const float* act, const float* next_obs, const float* rew, int64_t n,
-                         float* alive_next_obs, int64_t* n_alive) {
-  if (!h || !obs || !act || !next_obs || !rew || !alive_next_obs || !n_alive || n < 1) return fail("orl_traj_append_step: bad arguments");
-  Traj& t = h->t;
-  char msg[200];
-  if (n != t.live) {
-    snprintf(msg, sizeof(msg), "orl_traj_append_step: %lld rows, %lld trajectories are live", (long long)n, (long long)t.live);
-    return fail(msg);
-  }
-  if (t.rows + n > t.cap) {
-    snprintf(msg, sizeof(msg), "orl_traj_append_step: %lld rows + %lld more than the store's capacity %lld", (long long)t.rows, (long long)n, (long long)t.cap);
-    return fail(msg);
-  }
-  if (term_kind < 0 || term_kind >= ORL_TERM_KINDS) return fail("orl_traj_append_step: unknown termination kind");
-  const int need = term_kind == ORL_TERM_PEN ? 27 : ((term_kind == ORL_TERM_HOPPER || term_kind == ORL_TERM_WALKER2D) ? 2 : 1);
-  if (t.od < need) {
-    snprintf(msg, sizeof(msg), "orl_traj_append_step: termination kind %d reads observation column %d, the buffer has %d columns", (int)term_kind, need - 1, t.od);
-    return fail(msg);
-  }
-  if (alive_next_obs == next_obs) return fail("orl_traj_append_step: alive_next_obs must not overlap next_obs");
-  ORL_HIP(hipSetDevice(t.dev));
-  TrajP p = traj_params(t);
-  p.kind = term_kind; p.s_obs = obs; p.s_act = act; p.s_nobs = next_obs; p.s_rew = rew; p.row0 = t.rows; p.n = n; p.alive_nobs = alive_next_obs;
-  const unsigned blocks = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(k_traj_term, dim3(blocks), dim3(256), 0, 0, p);
-  ORL_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_traj_scatter, dim3(blocks), dim3(256), 0, 0, p);
-  ORL_HIP(hipGetLastError());
-  long long na = 0;
-  ORL_HIP(hipMemcpy(&na, t.cells, sizeof(na), hipMemcpyDeviceToHost));      // the one read of a step: it sizes the next one
-  t.rows += n; t.live = na; t.half ^= 1; t.finished = false;
-  *n_alive = na;
-  return 0;
-}
-int orl_traj_finish(orl_traj* h, int64_t* rows, double* reward_sum, double* returns_host) {
-  if (!h) return fail("orl_traj_finish: bad arguments");
-  Traj& t = h->t;
-  ORL_HIP(hipSetDevice(t.dev));
-  if (t.rows > 0) {
-    TrajP p = traj_params(t);
-    p.n = t.rows;
-    hipLaunchKernelGGL(k_traj_finish, dim3((unsigned)((t.rows + 255) / 256)), dim3(256), 0, 0, p);
-    ORL_HIP(hipGetLastError());
-  }
-  ORL_HIP(hipDeviceSynchronize());
-  t.finished = true;
-  if (rows) *rows = t.rows;
-  if (reward_sum) ORL_HIP(hipMemcpy(reward_sum, t.rew_total, sizeof(double), hipMemcpyDeviceToHost));
-  if (returns_host) ORL_HIP(hipMemcpy(returns_host, t.returns, sizeof(double) * t.n_traj, hipMemcpyDeviceToHost));
-  return 0;
-}
-int64_t orl_traj_live(orl_traj* h, int64_t* out_device) {
-  if (!h || !out_device) return fail("orl_traj_live: bad arguments");
-  Traj& t = h->t;
-  if (hipSetDevice(t.dev) != hipSuccess) return fail("orl_traj_live: hipSetDevice failed");
-  if (t.live > 0) {
-    hipLaunchKernelGGL(k_traj_live, dim3((unsigned)((t.live + 255) / 256)), dim3(256), 0, 0, t.live_idx[t.half], t.live, (long long*)out_device);
-    if (hipGetLastError() != hipSuccess) return fail("orl_traj_live: launch failed");
-  }
-  return t.live;
-}
-int orl_traj_read(orl_traj* h, int64_t row0, int64_t n, float* obs, float* act, float* next_obs, float* rew, float* term, int32_t* traj_idx,
-                  double* acc_ret, double* rtg) {
-  if (!h || n < 0 || row0 < 0) return fail("orl_traj_read: bad arguments");
-  Traj& t = h->t;
-  if (row0 + n > t.rows) return fail("orl_traj_read: rows beyond the store");
-  if (rtg && !t.finished) return fail("orl_traj_read: the returns-to-go exist after orl_traj_finish");
-  if (n == 0) return 0;
-  ORL_HIP(hipSetDevice(t.dev));
-  ORL_HIP(hipDeviceSynchronize());
-  if (obs) ORL_HIP(hipMemcpy2D(obs, sizeof(float) * t.od, t.obs + row0 * t.OP, sizeof(float) * t.OP, sizeof(float) * t.od, n, hipMemcpyDeviceToHost));
-  if (next_obs) ORL_HIP(hipMemcpy2D(next_obs, sizeof(float) * t.od, t.nobs + row0 * t.OP, sizeof(float) * t.OP, sizeof(float) * t.od, n, hipMemcpyDeviceToHost));
-  if (act) ORL_HIP(hipMemcpy2D(act, sizeof(float) * t.ad, t.act + row0 * t.AP, sizeof(float) * t.AP, sizeof(float) * t.ad, n, hipMemcpyDeviceToHost));
-  if (rew) ORL_HIP(hipMemcpy(rew, t.rew + row0, sizeof(float) * n, hipMemcpyDeviceToHost));
-  if (term) ORL_HIP(hipMemcpy(term, t.term + row0, sizeof(float) * n, hipMemcpyDeviceToHost));
-  if (traj_idx) ORL_HIP(hipMemcpy(traj_idx, t.tidx + row0, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  if (acc_ret) ORL_HIP(hipMemcpy(acc_ret, t.acc + row0, sizeof(double) * n, hipMemcpyDeviceToHost));
-  if (rtg) ORL_HIP(hipMemcpy(rtg, t.rtg + row0, sizeof(double) * n, hipMemcpyDeviceToHost));
-  return 0;
-}
-int orl_traj_export(orl_traj* h, int use_threshold, double threshold, orl_buffer* dst, int64_t* rows_kept, int64_t* traj_kept) {
-  if (!h || !dst) return fail("orl_traj_export: bad arguments");
-  Traj& t = h->t;
-  Buffer& b = dst->b;
-  char msg[224];
-  if (!t.finished) return fail("orl_traj_export: the returns-to-go exist after orl_traj_finish");
-  if (b.cap < 1) return fail("orl_traj_export: the destination is not a ring (orl_buffer_reserve first)");
-  if (b.od != t.od || b.ad != t.ad || b.dev != t.dev) {
-    snprintf(msg, sizeof(msg), "orl_traj_export: the ring's dims / device (%d, %d, device %d) differ from the store's (%d, %d, device %d)", b.od, b.ad,
-             b.dev, t.od, t.ad, t.dev);
-    return fail(msg);
-  }
-  ORL_HIP(hipSetDevice(t.dev));
-  long long res[2] = {0, 0};
-  TrajP p = traj_params(t);
-  p.n = t.rows; p.use_thr = use_threshold ? 1 : 0; p.thr = threshold;
-  const long blocks = (t.rows + 255) / 256;
-  if (blocks > 0) {
-    hipLaunchKernelGGL(k_traj_count, dim3((unsigned)blocks), dim3(256), 0, 0, p);
-    ORL_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_traj_total, dim3(1), dim3(256), 0, 0, p, blocks);
-  ORL_HIP(hipGetLastError());
-  ORL_HIP(hipMemcpy(res, t.cells + 1, sizeof(res), hipMemcpyDeviceToHost));
-  if (res[0] > b.cap - b.n) {               // (an RCSL dataset does not wrap; nothing has been written)
-    snprintf(msg, sizeof(msg), "orl_traj_export: %lld rows to keep, the ring has room for %lld (capacity %lld, size %lld)", res[0],
-             (long long)(b.cap - b.n), (long long)b.cap, (long long)b.n);
-    return fail(msg);
-  }
-  if (rows_kept) *rows_kept = res[0];
-  if (traj_kept) *traj_kept = res[1];
-  if (res[0] == 0) return 0;
-  p.d_obs = b.obs; p.d_nobs = b.nobs; p.d_act = b.act; p.d_rew = b.rew; p.d_term = b.term; p.d_row0 = b.ptr;      // (size < capacity: ptr == size)
-  hipLaunchKernelGGL(k_traj_export, dim3((unsigned)blocks), dim3(256), 0, 0, p);
-  ORL_HIP(hipGetLastError());
-  b.ptr = (b.ptr + res[0]) % b.cap;
-  b.n += res[0];
-  return ring_publish(b);
-}
-int orl_buffer_normalize_obs(orl_buffer* h, float eps, float* mean_out, float* std_out) {
-  Buffer& b = h->b;
-  if (!b.obs || b.n < 1) return fail("normalize_obs: empty buffer");
-  ORL_HIP(hipSetDevice(b.dev));
-  double* sums = nullptr;
-  ORL_HIP(hipMalloc((void**)&sums, sizeof(double) * 2 * b.od));
-  ORL_HIP(hipMemset(sums, 0, sizeof(double) * 2 * b.od));
-  hipLaunchKernelGGL(k_colstats, dim3(128, b.od), dim3(256), 0, 0, (const float*)b.obs, b.n, b.OP, b.od, sums);
-  std::vector<double> hs(2 * b.od);
-  ORL_HIP(hipMemcpy(hs.data(), sums, sizeof(double) * 2 * b.od, hipMemcpyDeviceToHost));
-  hipFree(sums);
-  std::vector<float> mean(b.od), sd(b.od);
-  for (int c = 0; c < b.od; ++c) {
-    const double m = hs[c] / (double)b.n;
-    double var = hs[b.od + c] / (double)b.n - m * m;
-    if (var < 0) var = 0;
-    mean[c] = (float)m;
-    sd[c] = (float)sqrt(var) + eps;        // buffer.py:90: std + eps
-  }
-  float *dm = nullptr, *ds = nullptr;
-  ORL_HIP(hipMalloc((void**)&dm, sizeof(float) * b.od));
-  ORL_HIP(hipMalloc((void**)&ds, sizeof(float) * b.od));
-  ORL_HIP(hipMemcpy(dm, mean.data(), sizeof(float) * b.od, hipMemcpyHostToDevice));
-  ORL_HIP(hipMemcpy(ds, sd.data(), sizeof(float) * b.od, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_normalize, dim3((unsigned)((b.n * b.od + 255) / 256)), dim3(256), 0, 0, b.obs, b.nobs, b.n, b.OP, b.od,
-                     (const float*)dm, (const float*)ds);
-  ORL_HIP(hipDeviceSynchronize());
-  hipFree(dm); hipFree(ds);
-  b.absmax_gen = ~0ull;                    // the values changed in place (same arrays: captured graphs stay valid, the cached range does not)
-  if (mean_out) memcpy(mean_out, mean.data(), sizeof(float) * b.od);
-  if (std_out) memcpy(std_out, sd.data(), sizeof(float) * b.od);
-  return 0;
-}
-// one draw of `batch` rows into packed device arrays on `stream`: the rows idx[] or, without, Philox draws keyed by (seed, row, the
-// buffer's draw counter), which advances.  orl_buffer_sample and the RAMBO device loop share it
-static int buffer_gather(Buffer& b, const long long* idx_dev, int batch, uint64_t seed, float* obs_out, float* act_out, float* next_obs_out,
-                         float* rew_out, float* term_out, hipStream_t stream) {
-  GatherP g;
-  memset(&g, 0, sizeof(g));
-  g.obs = b.obs; g.nobs = b.nobs; g.act = b.act; g.rew = b.rew; g.term = b.term; g.n = b.n;
-  g.OP = b.OP; g.AP = b.AP; g.od = b.od; g.ad = b.ad; g.B = batch; g.W = std::max(b.od, b.ad);
-  g.idx = idx_dev; g.idx_rs = batch;
-  g.b_obs = obs_out; g.b_nobs = next_obs_out; g.b_act = act_out; g.b_rew = rew_out; g.b_term = term_out;
-  g.d_op = b.od; g.d_ap = b.ad;
-  g.seed = seed; g.gstep = nullptr; g.counter = b.counter++;
-  hipLaunchKernelGGL(k_gather, dim3((unsigned)(((long)batch * g.W + 255) / 256), 1), dim3(256), 0, stream, g);
-  ORL_HIP(hipGetLastError());
-  return 0;
-}
-int orl_buffer_sample(orl_buffer* h, const int64_t* idx, int32_t batch, uint64_t seed, float* obs_out, float* act_out,
-                      float* next_obs_out, float* rew_out, float* term_out) {
-  Buffer& b = h->b;
-  if (!b.obs || b.n < 1) return fail("sample: empty buffer");
-  if (batch < 1 || !obs_out || !act_out || !next_obs_out || !rew_out || !term_out) return fail("sample: bad arguments");
-  ORL_HIP(hipSetDevice(b.dev));
-  if (idx) {
-    for (int i = 0; i < batch; ++i) if (idx[i] < 0 || idx[i] >= b.n) return fail("sample index out of range");
-    if (b.idx_cap < batch) {
-      if (b.idx) hipFree(b.idx);
-      ORL_HIP(hipMalloc((void**)&b.idx, sizeof(long long) * batch));
-      b.idx_cap = batch;
-    }
-    ORL_HIP(hipMemcpy(b.idx, idx, sizeof(long long) * batch, hipMemcpyHostToDevice));
-  }
-  if (buffer_gather(b, idx ? b.idx : nullptr, batch, seed, obs_out, act_out, next_obs_out, rew_out, term_out, 0)) return -1;
-  ORL_HIP(hipStreamSynchronize(0));
-  return 0;
-}
 int orl_engine_attach_buffer(orl_engine* h, orl_buffer* b) {
   if (!b) { h->e.buf = nullptr; h->e.drop_graphs(); return 0; }
   if (b->b.od != h->e.od || b->b.ad != h->e.ad) return fail("attach_buffer: obs/act dims differ from the engine's");
   if (b->b.dev != h->e.dev) return fail("attach_buffer: buffer lives on another device");
+  // split precision multiplies fp16 hi + lo planes: an observation or action component of 65504 or more is +-inf there.  The dataset is
+  // checked once per load (buffer_absmax: a reduction over the HBM arrays, cached), not per sampled batch.
+  float amax = 0.f;
+  char msg[256];
   if (h->e.split_scales() && b->b.obs) {
-    // split precision multiplies fp16 hi + lo planes: an observation or action component of 65504 or more is +-inf there.  The dataset is
-    // checked once per load (a 40 us reduction over the HBM arrays), not per sampled batch.
-    Buffer& bb = b->b;
-    if (bb.absmax_gen != bb.gen) {
-      ORL_HIP(hipSetDevice(bb.dev));
-      unsigned int* d = nullptr;
-      ORL_HIP(hipMalloc((void**)&d, sizeof(unsigned int)));
-      ORL_HIP(hipMemset(d, 0, sizeof(unsigned int)));
-      hipLaunchKernelGGL(k_absmax, dim3(1024), dim3(256), 0, 0, (const float*)bb.obs, bb.n * bb.OP, d);
-      hipLaunchKernelGGL(k_absmax, dim3(1024), dim3(256), 0, 0, (const float*)bb.nobs, bb.n * bb.OP, d);
-      hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, 0, (const float*)bb.act, bb.n * bb.AP, d);
-      unsigned int bits = 0;
-      ORL_HIP(hipMemcpy(&bits, d, sizeof(bits), hipMemcpyDeviceToHost));
-      hipFree(d);
-      memcpy(&bb.absmax, &bits, sizeof(float));
-      bb.absmax_gen = bb.gen;
-    }
-    if (!(bb.absmax < 65504.0f)) {
-      char msg[256];
+    if (buffer_absmax(b->b, false, &amax)) return -1;
+    if (!(amax < 65504.0f)) {
       snprintf(msg, sizeof(msg), "attach_buffer: the dataset's observations / actions reach |x| = %g, beyond the operand range of precision 1 "
-               "(fp16 hi + lo planes, |x| < 65504): normalise the observations (ReplayBuffer.normalize_obs) or use precision 0", (double)bb.absmax);
+               "(fp16 hi + lo planes, |x| < 65504): normalise the observations (ReplayBuffer.normalize_obs) or use precision 0", (double)amax);
       return fail(msg);
     }
   }
+  // the reward column holds the return-to-go, column obs_dim of the net's input: an MFMA operand like the observations
   if (h->e.split_scales() && is_rcsl(h->e.cfg.algo) && b->b.rew) {
-    // the reward column holds the return-to-go, column obs_dim of the net's input: an MFMA operand like the observations
-    Buffer& bb = b->b;
-    if (bb.rew_absmax_gen != bb.gen) {
-      ORL_HIP(hipSetDevice(bb.dev));
-      unsigned int* d = nullptr;
-      ORL_HIP(hipMalloc((void**)&d, sizeof(unsigned int)));
-      ORL_HIP(hipMemset(d, 0, sizeof(unsigned int)));
-      hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, 0, (const float*)bb.rew, bb.n, d);
-      unsigned int bits = 0;
-      ORL_HIP(hipMemcpy(&bits, d, sizeof(bits), hipMemcpyDeviceToHost));
-      hipFree(d);
-      memcpy(&bb.rew_absmax, &bits, sizeof(float));
-      bb.rew_absmax_gen = bb.gen;
-    }
-    if (!(bb.rew_absmax < 65504.0f)) {
-      char msg[256];
+    if (buffer_absmax(b->b, true, &amax)) return -1;
+    if (!(amax < 65504.0f)) {
       snprintf(msg, sizeof(msg), "attach_buffer: the dataset's returns-to-go (reward column) reach |x| = %g, beyond the operand range of "
-               "precision 1 (fp16 hi + lo planes, |x| < 65504): scale the returns or use precision 0", (double)bb.rew_absmax);
+               "precision 1 (fp16 hi + lo planes, |x| < 65504): scale the returns or use precision 0", (double)amax);
       return fail(msg);
     }
   }
@@ -2202,9 +1676,8 @@ int Engine::upload_model_table() {
   std::vector<ModelSrc> host(mbufs.size());
   mbufs_gen.resize(mbufs.size());
   for (size_t r = 0; r < mbufs.size(); ++r) {
-    const Buffer& b = *mbufs[r];
-    host[r].obs = b.obs; host[r].nobs = b.nobs; host[r].act = b.act; host[r].rew = b.rew; host[r].term = b.term; host[r].n = b.d_n;
-    mbufs_gen[r] = b.gen;
+    host[r] = mbufs[r]->model_src();
+    mbufs_gen[r] = mbufs[r]->gen;
   }
   ORL_HIP(hipStreamSynchronize(stream));
   ORL_HIP(hipMemcpy(m_tab, host.data(), sizeof(ModelSrc) * host.size(), hipMemcpyHostToDevice));
@@ -2444,14 +1917,7 @@ static int adv_refuse(const Engine& e, long rows, int term_kind, const char* who
   if (e.cfg.algo != ORL_ALGO_SAC) return fail(w + ": not a SAC engine");
   if (rows < 2) return fail(w + ": rows must be >= 2 (the unbiased standard deviation of one advantage is NaN)");
   if (rows > (1 << 22)) return fail(w + ": more than 2^22 rows per run");
-  if (term_kind < 0 || term_kind >= ORL_TERM_KINDS) return fail(w + ": unknown termination kind");
-  const int need = term_kind == ORL_TERM_PEN ? 27 : ((term_kind == ORL_TERM_HOPPER || term_kind == ORL_TERM_WALKER2D) ? 2 : 1);
-  if (e.od < need) {
-    char msg[224];
-    snprintf(msg, sizeof(msg), "%s: termination kind %d reads observation column %d, the engine has %d columns", who, term_kind, need - 1, e.od);
-    return fail(msg);
-  }
-  return 0;
+  return term_refusal(w, term_kind, e.od, "engine");
 }
 
 int orl_engine_adv_advantage(orl_engine* h, const float* obs, const float* act, const float* next_obs, const float* reward, int32_t rows,

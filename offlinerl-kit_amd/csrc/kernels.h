@@ -1,4 +1,4 @@
-// kernels.h — non-GEMM device kernels of the update engine: replay gather + device RNG, tanh-Gaussian
+// kernels.h — non-GEMM device kernels of the update engine: the step's input launch + device RNG, tanh-Gaussian
 // sampling and its backward, loss / gradient-seed kernels, fused Adam + split-K slab reduce + Polyak.
 // Every kernel is batched over runs (and nets where it applies) through blockIdx.y / blockIdx.z.
 #pragma once
@@ -8,6 +8,7 @@
 #include "rng.h"         // Philox4x32-10, u01, box_muller: device sampling of indices / noise in orl_learn_n
 #include "sample.h"
 #include "scalars.h"
+#include "store.h"       // the termination test (orl_term_done) and the model-ring source (ModelSrc) that k_prepare and the RAMBO / MOBILE kernels share with the row stores; k_gather
 
 namespace orl {
 
@@ -64,407 +65,6 @@ __global__ void k_grad_scale(GradScaleP p) {
     __syncthreads();
   }
   if (threadIdx.x == 0) p.out[r] = orl_pow2_scale(sh[0]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// replay gather (buffer.py:96-106).  Dataset = SoA in HBM, rows padded to 16 B (obs/next_obs pitch OP,
-// act pitch AP).  idx == nullptr -> Philox indices (np.random.randint(0, size, B) restated on device).
-// One thread per (row, column) of the widest array; consecutive lanes read consecutive floats of a row
-// (coalesced within the row) and rows are independent random 64-128 B segments.
-// grid (ceil(B*W/256), R) with W = max(OP, AP).
-// ------------------------------------------------------------------------------------------------
-// one model ring as the samplers see it: the arrays and the device cell that holds the current size.  With per-run model rings
-// (orl_engine_attach_model_buffers) a table of these, one per run, sits in engine-owned device memory: the captured graph holds the
-// table's address, the rings grow behind it.
-struct ModelSrc { const float *obs, *nobs, *act, *rew, *term; const long long* n; };
-// (r = blockIdx.y: block-uniform, the table entry comes by scalar loads; `one` is the single ring of the launch parameters, handed over
-// field by field: a reference to the parameter block itself put k_prepare's 2 KB job table into scratch memory)
-__device__ inline ModelSrc orl_model_src(const ModelSrc* tab, int r, ModelSrc one) { return tab ? tab[r] : one; }
-struct GatherP {
-  const float *obs, *nobs, *act, *rew, *term;  // dataset [n][OP], [n][OP], [n][AP], [n], [n]
-  long n;
-  int OP, AP, od, ad, B, W;
-  const long long* idx; long idx_rs;           // [R][B] or null
-  float *b_obs, *b_nobs, *b_act, *b_rew, *b_term;  // destinations
-  long obs_rs, nobs_rs, act_rs, rew_rs, term_rs;   // run strides of the destinations
-  int d_op, d_ap;                                  // destination row pitches (>= od / ad; extra columns zeroed)
-  unsigned long long seed;
-  const unsigned long long* gstep;
-  unsigned long long counter;                      // used when gstep == nullptr
-  // second source (orl_engine_attach_model_buffer): batch rows [real_rows, B) come from the model ring, whose current size is read from
-  // its device cell (the ring grows between replays of a captured graph); m_obs == nullptr: one source, the path above
-  const float *m_obs, *m_nobs, *m_act, *m_rew, *m_term;
-  const long long* m_n;
-  int real_rows;
-  const ModelSrc* m_tab;                           // per-run model rings (orl_engine_attach_model_buffers), or null: the ring above for every run
-};
-__global__ void k_gather(GatherP p) {
-  const int r = blockIdx.y;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int row = t / p.W, c = t - row * p.W;
-  if (row >= p.B) return;
-  // the source of a batch row is a function of the row alone: real rows first, model rows behind them (mopo.py:81-84); the row keeps
-  // its Philox counter, only the range and the base pointers change
-  const bool mdl = p.m_obs && row >= p.real_rows;
-  const ModelSrc m = orl_model_src(p.m_tab, r, ModelSrc{p.m_obs, p.m_nobs, p.m_act, p.m_rew, p.m_term, p.m_n});
-  const float *s_obs = mdl ? m.obs : p.obs, *s_nobs = mdl ? m.nobs : p.nobs, *s_act = mdl ? m.act : p.act;
-  const float *s_rew = mdl ? m.rew : p.rew, *s_term = mdl ? m.term : p.term;
-  long j;
-  if (p.idx) j = p.idx[(long)r * p.idx_rs + row];
-  else {
-    const unsigned long long ctr = p.gstep ? *p.gstep : p.counter;
-    const long n = mdl ? (long)*m.n : p.n;
-    Philox ph(p.seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(r + 1));
-    uint32_t o[4];
-    ph((uint32_t)row, 0x51u, (uint32_t)ctr, 0x1D5u ^ (uint32_t)(ctr >> 32), o);
-    j = (long)(((unsigned long long)o[0] * (unsigned long long)n) >> 32);
-  }
-  if (c < p.d_op) {
-    const float vo = c < p.od ? s_obs[j * p.OP + c] : 0.f, vn = c < p.od ? s_nobs[j * p.OP + c] : 0.f;
-    p.b_obs[(long)r * p.obs_rs + (long)row * p.d_op + c] = vo;
-    p.b_nobs[(long)r * p.nobs_rs + (long)row * p.d_op + c] = vn;
-  }
-  if (c < p.d_ap) p.b_act[(long)r * p.act_rs + (long)row * p.d_ap + c] = c < p.ad ? s_act[j * p.AP + c] : 0.f;
-  if (c == 0) { p.b_rew[(long)r * p.rew_rs + row] = s_rew[j]; p.b_term[(long)r * p.term_rs + row] = s_term[j]; }
-}
-
-// ------------------------------------------------------------------------------------------------
-// one model-rollout step's bookkeeping (policy/model_based/mopo.py:45-79) on the device: the termination test of
-// utils/termination_fns.py on next_obs, all n transitions appended to the HBM ring (rows (ptr + i) % cap), the next_obs rows of the
-// transitions that did NOT terminate compacted densely and IN THEIR ORIGINAL ORDER (the dynamics' Philox draws are keyed by row
-// position), their count and the float64 sum of the rewards.  Two passes over ceil(n / 256) blocks: k_roll_term writes the 0 / 1
-// terminals and per-block (alive count, reward sum); k_roll_scatter turns the counts of the blocks in front of it into its offset,
-// ranks its own rows with wave ballots (64 lanes, 64-bit masks) and copies.  A fixed block order, no tickets: the result does not
-// depend on which block runs first.  Sources are packed [n][od] / [n][ad] arrays (not 16-byte aligned at od = 17), so the copies are
-// coalesced scalar loads; the pad columns of the ring rows are written as zeros.
-// ------------------------------------------------------------------------------------------------
-enum { ORL_TERM_NONE = 0, ORL_TERM_HALFCHEETAH, ORL_TERM_HOPPER, ORL_TERM_WALKER2D, ORL_TERM_ANT, ORL_TERM_HUMANOID, ORL_TERM_PEN, ORL_TERM_KINDS };
-__device__ inline bool orl_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-// the numpy comparisons of the reference restated: every test below is false on NaN, like numpy's
-__device__ inline bool orl_term_done(int kind, const float* x, int od) {
-  switch (kind) {
-    case ORL_TERM_HALFCHEETAH: {
-      bool in = true;
-      for (int c = 0; c < od; ++c) in = in && (x[c] > -100.f) && (x[c] < 100.f);
-      return !in;
-    }
-    case ORL_TERM_HOPPER: {             // abs(next_obs[:, 1:] < 100): an upper bound only, on columns 1..
-      bool ok = true;
-      for (int c = 0; c < od; ++c) ok = ok && orl_finite(x[c]) && (c == 0 || x[c] < 100.f);
-      return !(ok && x[0] > .7f && fabsf(x[1]) < .2f);
-    }
-    case ORL_TERM_WALKER2D: {
-      bool in = true;
-      for (int c = 0; c < od; ++c) in = in && (x[c] > -100.f) && (x[c] < 100.f);
-      return !(in && x[0] > 0.8f && x[0] < 2.0f && x[1] > -1.0f && x[1] < 1.0f);
-    }
-    case ORL_TERM_ANT: {
-      bool fin = true;
-      for (int c = 0; c < od; ++c) fin = fin && orl_finite(x[c]);
-      return !(fin && x[0] >= 0.2f && x[0] <= 1.0f);
-    }
-    case ORL_TERM_HUMANOID: return (x[0] < 1.0f) || (x[0] > 2.0f);      // NaN: not done
-    case ORL_TERM_PEN: return x[26] < 0.075f;                           // (od >= 27 is checked on the host)
-    default: return false;
-  }
-}
-// Several rings in one launch pair (orl_buffer_append_rollout_runs): blockIdx.y is the run, the sources are [runs][row_stride][dim]
-// arrays of which run r owns the first tab[r].n rows, and the ring of a run is read from a table in device memory (uploaded per call:
-// at 128 runs it does not fit the kernel arguments).  A block whose first row lies at or past its run's row count leaves before any
-// barrier (the test is uniform per block); the per-block scratch is [runs][gridDim.x] and the totals of a run are summed over the blocks
-// that had rows, in block order.
-struct RollRing {
-  float *obs, *nobs, *act, *rew, *term; int OP, AP; long cap, ptr;   // the ring
-  long n;                                // rows of this call
-  long long* size_cell; long long size;  // non-null: the ring's device size cell and its value after this call
-};
-struct RollP {
-  int kind;
-  const float *obs, *act, *nobs, *rew;   // packed [runs][row_stride][od], [..][ad], [..][od], [runs][row_stride]
-  long row_stride; int od, ad;
-  RollRing ring;                         // tab == nullptr: the one ring (gridDim.y == 1)
-  const RollRing* tab;                   // [gridDim.y], device memory
-  float* alive_nobs;                     // [runs][row_stride][od] packed, run r compacted into its own block; must not overlap nobs
-  int* blk_alive; double* blk_rew;       // [gridDim.y][gridDim.x] scratch
-  long long* n_alive_out; double* rew_sum_out;   // [gridDim.y]
-};
-__global__ void k_roll_term(RollP p) {
-  __shared__ int sh_a[4];
-  __shared__ double sh_r[4];
-  const int r = blockIdx.y;
-  const RollRing g = p.tab ? p.tab[r] : p.ring;
-  if ((long)blockIdx.x * 256 >= g.n) return;
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const float* nobs = p.nobs + (long)r * p.row_stride * p.od;
-  bool alive = false;
-  double rw = 0.0;
-  if (i < g.n) {
-    const bool done = orl_term_done(p.kind, nobs + i * p.od, p.od);
-    g.term[(g.ptr + i) % g.cap] = done ? 1.0f : 0.0f;
-    alive = !done;
-    rw = (double)p.rew[(long)r * p.row_stride + i];
-  }
-  const unsigned long long m = __ballot(alive);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rw += __shfl_down(rw, o, 64);
-  if ((threadIdx.x & 63) == 0) { sh_a[threadIdx.x >> 6] = __popcll(m); sh_r[threadIdx.x >> 6] = rw; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    p.blk_alive[(long)r * gridDim.x + blockIdx.x] = sh_a[0] + sh_a[1] + sh_a[2] + sh_a[3];
-    p.blk_rew[(long)r * gridDim.x + blockIdx.x] = ((sh_r[0] + sh_r[1]) + sh_r[2]) + sh_r[3];
-  }
-}
-// The stable rank of a flagged row among ALL flagged rows of a launch of 256-thread blocks, -1 for a row that is not flagged: the flagged
-// rows of the blocks in front (blk_cnt[0 .. blockIdx.x), written by the counting pass; integers, so the order of the sum does not
-// matter), those of the waves in front within the block, and the wave-ballot rank (64 lanes, 64-bit masks).  Every thread of the block
-// calls it, once per kernel (it owns its shared memory and has barriers inside).  k_roll_scatter, k_traj_scatter and k_traj_export
-// compact with it.
-__device__ inline int orl_stable_rank(bool flag, const int* blk_cnt) {
-  __shared__ int sh_part[256];
-  __shared__ int sh_w[4];
-  const int tid = threadIdx.x;
-  int part = 0;
-  for (int b = tid; b < (int)blockIdx.x; b += 256) part += blk_cnt[b];
-  sh_part[tid] = part;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) sh_part[tid] += sh_part[tid + o];
-    __syncthreads();
-  }
-  const int blk_off = sh_part[0];
-  const unsigned long long m = __ballot(flag);
-  const int lane = tid & 63, w = tid >> 6;
-  if (lane == 0) sh_w[w] = __popcll(m);
-  __syncthreads();
-  int woff = 0;
-  for (int k = 0; k < w; ++k) woff += sh_w[k];
-  return flag ? blk_off + woff + __popcll(m & ((1ull << lane) - 1ull)) : -1;
-}
-__global__ void k_roll_scatter(RollP p) {
-  __shared__ int sh_dst[256];
-  const int tid = threadIdx.x, r = blockIdx.y;
-  const RollRing g = p.tab ? p.tab[r] : p.ring;
-  const long row0 = (long)blockIdx.x * 256, i = row0 + tid;
-  if (row0 >= g.n) {                      // (a run without rows: its block 0 still reports the totals)
-    if (blockIdx.x == 0 && tid == 0) {
-      p.n_alive_out[r] = 0; p.rew_sum_out[r] = 0.0;
-      if (g.size_cell) *g.size_cell = g.size;
-    }
-    return;
-  }
-  const float *s_obs = p.obs + (long)r * p.row_stride * p.od, *s_nobs = p.nobs + (long)r * p.row_stride * p.od;
-  const float *s_act = p.act + (long)r * p.row_stride * p.ad, *s_rew = p.rew + (long)r * p.row_stride;
-  float* alive_nobs = p.alive_nobs + (long)r * p.row_stride * p.od;
-  const int* blk_alive = p.blk_alive + (long)r * gridDim.x;
-  const bool alive = i < g.n && g.term[(g.ptr + i) % g.cap] == 0.0f;
-  sh_dst[tid] = orl_stable_rank(alive, blk_alive);
-  __syncthreads();
-  const int rows = (int)(g.n - row0 < 256 ? g.n - row0 : 256);
-  for (int e = tid; e < rows * g.OP; e += 256) {
-    const int row = e / g.OP, c = e - row * g.OP;
-    const long src = (row0 + row) * p.od + c, dst = ((g.ptr + row0 + row) % g.cap) * g.OP + c;
-    g.obs[dst] = c < p.od ? s_obs[src] : 0.f;
-    g.nobs[dst] = c < p.od ? s_nobs[src] : 0.f;
-  }
-  for (int e = tid; e < rows * g.AP; e += 256) {
-    const int row = e / g.AP, c = e - row * g.AP;
-    g.act[((g.ptr + row0 + row) % g.cap) * g.AP + c] = c < p.ad ? s_act[(row0 + row) * p.ad + c] : 0.f;
-  }
-  for (int e = tid; e < rows * p.od; e += 256) {
-    const int row = e / p.od, c = e - row * p.od;
-    const int d = sh_dst[row];
-    if (d >= 0) alive_nobs[(long)d * p.od + c] = s_nobs[(row0 + row) * p.od + c];
-  }
-  if (i < g.n) g.rew[(g.ptr + i) % g.cap] = s_rew[i];
-  if (blockIdx.x == 0 && tid == 0) {      // totals in block order (a few hundred terms at 50 000 rows)
-    long long na = 0; double rs = 0.0;
-    const int nb = (int)((g.n + 255) / 256);
-    const double* blk_rew = p.blk_rew + (long)r * gridDim.x;
-    for (int b = 0; b < nb; ++b) { na += blk_alive[b]; rs += blk_rew[b]; }
-    p.n_alive_out[r] = na; p.rew_sum_out[r] = rs;
-    if (g.size_cell) *g.size_cell = g.size;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// the trajectory store (orl_traj): the bookkeeping of the RCSL rollout (policy/rcsl/rcsl.py:57-120) on the device.  A row carries, next to
-// the transition, its trajectory, the return accumulated BEFORE it and -- after k_traj_finish -- its return-to-go; returns / accumulated
-// returns are float64 because the host keeps them in np.zeros arrays (float64 + float32 promoted, one add per step: the same rounding).
-// A step is the launch pair of the ring rollout: k_traj_term (terminals, per-block alive count and reward sum), k_traj_scatter (rows,
-// stable compaction of the survivors' next_obs and of the live (trajectory, accumulated return) pairs into the other half of the
-// ping-pong arrays).  A trajectory has at most one live row, so returns[] is updated by a plain read-add-store.  The export is the
-// same two-pass compaction over the stored rows: k_traj_count / k_traj_total count (the host refuses a ring that is too small before a
-// row is written), k_traj_export scatters.  Fixed block order everywhere, no tickets, no atomics.
-// ------------------------------------------------------------------------------------------------
-struct TrajP {
-  float *obs, *nobs, *act, *rew, *term; int* tidx; double *acc, *rtg;   // the rows: [cap][OP], [cap][OP], [cap][AP], [cap] each
-  int OP, AP, od, ad;
-  double* returns;                                                       // [n_traj]
-  long n_traj;
-  const int* live_idx; const double* live_acc;                           // the live trajectories of this step, [n]
-  int* next_idx; double* next_acc;                                       // ... of the next one (the other half)
-  int kind;
-  const float *s_obs, *s_act, *s_nobs, *s_rew;                           // packed sources [n][od], [n][ad], [n][od], [n]
-  long row0, n;                                                          // step: rows [row0, row0 + n) are appended; finish / export: rows [0, n)
-  float* alive_nobs;
-  int* blk_cnt; double* blk_rew;                                         // per-block scratch
-  long long* cells;                                                      // [0] survivors of the step, [1] rows kept, [2] trajectories kept
-  double* rew_total;                                                     // running sum of every appended reward
-  int use_thr; double thr;                                               // export: keep rows of trajectories with returns > thr
-  float *d_obs, *d_nobs, *d_act, *d_rew, *d_term; long d_row0;           // export: the destination ring (same pitches) and its first free row
-};
-__global__ void k_traj_reset(TrajP p) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < p.n_traj) { p.returns[i] = 0.0; p.next_idx[i] = (int)i; p.next_acc[i] = 0.0; }
-  if (i == 0) *p.rew_total = 0.0;
-}
-__global__ void k_traj_term(TrajP p) {
-  __shared__ int sh_a[4];
-  __shared__ double sh_r[4];
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  bool alive = false;
-  double rw = 0.0;
-  if (i < p.n) {
-    const bool done = orl_term_done(p.kind, p.s_nobs + i * p.od, p.od);
-    p.term[p.row0 + i] = done ? 1.0f : 0.0f;
-    alive = !done;
-    rw = (double)p.s_rew[i];
-  }
-  const unsigned long long m = __ballot(alive);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rw += __shfl_down(rw, o, 64);
-  if ((threadIdx.x & 63) == 0) { sh_a[threadIdx.x >> 6] = __popcll(m); sh_r[threadIdx.x >> 6] = rw; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    p.blk_cnt[blockIdx.x] = sh_a[0] + sh_a[1] + sh_a[2] + sh_a[3];
-    p.blk_rew[blockIdx.x] = ((sh_r[0] + sh_r[1]) + sh_r[2]) + sh_r[3];
-  }
-}
-__global__ void k_traj_scatter(TrajP p) {
-  __shared__ int sh_dst[256];
-  const int tid = threadIdx.x;
-  const long b0 = (long)blockIdx.x * 256, i = b0 + tid;
-  const bool alive = i < p.n && p.term[p.row0 + i] == 0.0f;
-  const int d = orl_stable_rank(alive, p.blk_cnt);
-  sh_dst[tid] = d;
-  __syncthreads();
-  const int rows = (int)(p.n - b0 < 256 ? p.n - b0 : 256);
-  for (int e = tid; e < rows * p.OP; e += 256) {
-    const int row = e / p.OP, c = e - row * p.OP;
-    const long src = (b0 + row) * p.od + c, dst = (p.row0 + b0 + row) * p.OP + c;
-    p.obs[dst] = c < p.od ? p.s_obs[src] : 0.f;
-    p.nobs[dst] = c < p.od ? p.s_nobs[src] : 0.f;
-  }
-  for (int e = tid; e < rows * p.AP; e += 256) {
-    const int row = e / p.AP, c = e - row * p.AP;
-    p.act[(p.row0 + b0 + row) * p.AP + c] = c < p.ad ? p.s_act[(b0 + row) * p.ad + c] : 0.f;
-  }
-  for (int e = tid; e < rows * p.od; e += 256) {
-    const int row = e / p.od, c = e - row * p.od;
-    const int dd = sh_dst[row];
-    if (dd >= 0) p.alive_nobs[(long)dd * p.od + c] = p.s_nobs[(b0 + row) * p.od + c];
-  }
-  if (i < p.n) {
-    const int t = p.live_idx[i];
-    const double a = p.live_acc[i], r = (double)p.s_rew[i];
-    p.rew[p.row0 + i] = p.s_rew[i];
-    p.tidx[p.row0 + i] = t;
-    p.acc[p.row0 + i] = a;
-    p.returns[t] = p.returns[t] + r;        // (the only live row of trajectory t)
-    if (d >= 0) { p.next_idx[d] = t; p.next_acc[d] = a + r; }
-  }
-  if (blockIdx.x == 0 && tid == 0) {        // totals in block order
-    long long na = 0; double rs = 0.0;
-    for (int b = 0; b < (int)gridDim.x; ++b) { na += p.blk_cnt[b]; rs += p.blk_rew[b]; }
-    p.cells[0] = na;
-    *p.rew_total = *p.rew_total + rs;
-  }
-}
-__global__ void k_traj_finish(TrajP p) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < p.n) p.rtg[i] = p.returns[p.tidx[i]] - p.acc[i];
-}
-// orl_traj_live: the live trajectory indices, widened to int64 (an index tensor for a per-trajectory table)
-__global__ void k_traj_live(const int* __restrict__ live_idx, long n, long long* __restrict__ out) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = live_idx[i];
-}
-// (a NaN return is not above any threshold, as in numpy)
-__device__ inline bool orl_traj_keep(int use_thr, double thr, const double* returns, int t) { return !use_thr || returns[t] > thr; }
-__global__ void k_traj_count(TrajP p) {
-  __shared__ int sh_a[4];
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const bool keep = i < p.n && orl_traj_keep(p.use_thr, p.thr, p.returns, p.tidx[i]);
-  const unsigned long long m = __ballot(keep);
-  if ((threadIdx.x & 63) == 0) sh_a[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) p.blk_cnt[blockIdx.x] = sh_a[0] + sh_a[1] + sh_a[2] + sh_a[3];
-}
-// one block: the kept rows (the sum of k_traj_count's `nblk` block counts) and the kept trajectories
-__global__ void k_traj_total(TrajP p, long nblk) {
-  __shared__ long long sh_r[256], sh_t[256];
-  const int tid = threadIdx.x;
-  long long r = 0, t = 0;
-  for (long b = tid; b < nblk; b += 256) r += p.blk_cnt[b];
-  for (long j = tid; j < p.n_traj; j += 256) t += orl_traj_keep(p.use_thr, p.thr, p.returns, (int)j) ? 1 : 0;
-  sh_r[tid] = r; sh_t[tid] = t;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) { sh_r[tid] += sh_r[tid + o]; sh_t[tid] += sh_t[tid + o]; }
-    __syncthreads();
-  }
-  if (tid == 0) { p.cells[1] = sh_r[0]; p.cells[2] = sh_t[0]; }
-}
-// kept rows -> ring rows d_row0 + rank (the host has checked that they fit without wrapping), rew := (float)rtg
-__global__ void k_traj_export(TrajP p) {
-  __shared__ int sh_dst[256];
-  const int tid = threadIdx.x;
-  const long b0 = (long)blockIdx.x * 256, i = b0 + tid;
-  const bool keep = i < p.n && orl_traj_keep(p.use_thr, p.thr, p.returns, p.tidx[i]);
-  const int d = orl_stable_rank(keep, p.blk_cnt);
-  sh_dst[tid] = d;
-  __syncthreads();
-  const int rows = (int)(p.n - b0 < 256 ? p.n - b0 : 256);
-  for (int e = tid; e < rows * p.OP; e += 256) {
-    const int row = e / p.OP, c = e - row * p.OP;
-    const int dd = sh_dst[row];
-    if (dd >= 0) {
-      const long src = (b0 + row) * p.OP + c, dst = (p.d_row0 + dd) * p.OP + c;
-      p.d_obs[dst] = p.obs[src];
-      p.d_nobs[dst] = p.nobs[src];
-    }
-  }
-  for (int e = tid; e < rows * p.AP; e += 256) {
-    const int row = e / p.AP, c = e - row * p.AP;
-    const int dd = sh_dst[row];
-    if (dd >= 0) p.d_act[(p.d_row0 + dd) * p.AP + c] = p.act[(b0 + row) * p.AP + c];
-  }
-  if (d >= 0) { p.d_rew[p.d_row0 + d] = (float)p.rtg[i]; p.d_term[p.d_row0 + d] = p.term[i]; }
-}
-
-// normalize_obs (buffer.py:88-94): per-column mean / population std in double, then in-place scaling
-__global__ void k_colstats(const float* x, long n, int pitch, int dim, double* sums /*[2*dim]*/) {
-  __shared__ double sh[2][256];
-  const int c = blockIdx.y;
-  double s = 0.0, q = 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const double v = x[i * pitch + c];
-    s += v; q += v * v;
-  }
-  sh[0][threadIdx.x] = s; sh[1][threadIdx.x] = q;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { atomicAdd(&sums[c], sh[0][0]); atomicAdd(&sums[dim + c], sh[1][0]); }
-}
-__global__ void k_normalize(float* x, float* y, long n, int pitch, int dim, const float* mean, const float* stdv) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long i = t / dim; const int c = (int)(t - i * dim);
-  if (i >= n) return;
-  x[i * pitch + c] = (x[i * pitch + c] - mean[c]) / stdv[c];
-  y[i * pitch + c] = (y[i * pitch + c] - mean[c]) / stdv[c];
 }
 
 __global__ void k_fill(float* p, long n, float v) {
@@ -1085,15 +685,6 @@ __global__ void k_range_scan(const float* x, long rs, long cs, int nets, int row
     hit |= fabsf(x[(long)r * rs + z * cs + row * pitch + c]) >= limit;      // (NaN compares false: a diverged run is reported as non-finite, not as out of range)
   }
   if (__syncthreads_or(hit) && threadIdx.x == 0) atomicOr(health + r, (unsigned int)ORL_HEALTH_SPLIT_RANGE);
-}
-// max |x| of a dataset array (orl_engine_attach_buffer at precision 1: observations / actions beyond the split range are refused up front)
-__global__ void k_absmax(const float* x, long n, unsigned int* out_bits) {
-  float m = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float a = fabsf(x[i]);
-    m = (a > m || a != a) ? a : m;                                            // a NaN sticks
-  }
-  atomicMax(out_bits, __float_as_uint(m));                                    // non-negative floats (and NaNs above them) order like their bit patterns
 }
 
 // q[m] += part[0][m] + part[1][m] + ... (column-tile partial sums of a tail fused into the last hidden layer's epilogue)

@@ -923,6 +923,23 @@ class Engine(_Handle):
         return rows
 
 
+def _device_rows(who: str, owner: str, dev, lead: tuple, obs, act, next_obs, rew, alive_next_obs, alive_shaped: bool = False):
+    """The check of the device-side appends (``who`` names the caller in the messages): contiguous fp32 torch tensors on the device of
+    ``dev`` -- ``owner`` is "the buffer's", ... -- with obs / next_obs ``lead + (obs_dim,)``, act ``lead + (act_dim,)`` and, where
+    ``alive_shaped``, alive_next_obs like obs.  Then the current stream is synchronised: the engine's launches run on the default stream
+    and read what torch wrote on its own."""
+    import torch
+    so, sa = lead + (dev.obs_dim,), lead + (dev.act_dim,)
+    for name, t, shape in (("obs", obs, so), ("act", act, sa), ("next_obs", next_obs, so), ("rew", rew, None),
+                           ("alive_next_obs", alive_next_obs, so if alive_shaped else None)):
+        if not _is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" \
+                or (t.device.index or 0) != dev.device:
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 tensor on {owner} device")
+        if shape is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {shape}")
+    torch.cuda.current_stream(obs.device).synchronize()
+
+
 class DeviceBuffer(_Handle):
     """RAII wrapper over ``orl_buffer*``: the HBM-resident SoA replay store (buffer/buffer.py)."""
     _destroy = "orl_buffer_destroy"
@@ -983,18 +1000,10 @@ class DeviceBuffer(_Handle):
     def append_rollout(self, term_kind: int, obs, act, next_obs, rew, alive_next_obs):
         """one rollout step (orl_buffer_append_rollout): torch tensors on this buffer's device, packed fp32; ``alive_next_obs`` has
         room for every row.  Returns (n_alive, float64 reward sum)."""
-        import torch
         n = int(obs.shape[0])
-        for name, t, shape in (("obs", obs, (n, self.obs_dim)), ("act", act, (n, self.act_dim)), ("next_obs", next_obs, (n, self.obs_dim)),
-                               ("rew", rew, None), ("alive_next_obs", alive_next_obs, None)):
-            if not _is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" \
-                    or (t.device.index or 0) != self.device:
-                raise ValueError(f"append_rollout: {name} must be a contiguous fp32 tensor on the buffer's device")
-            if shape is not None and tuple(t.shape) != shape:
-                raise ValueError(f"append_rollout: {name} has shape {tuple(t.shape)}, expected {shape}")
+        _device_rows("append_rollout", "the buffer's", self, (n,), obs, act, next_obs, rew, alive_next_obs)
         if rew.numel() != n or alive_next_obs.numel() < n * self.obs_dim:
             raise ValueError("append_rollout: rew needs n values, alive_next_obs room for n rows")
-        torch.cuda.current_stream(obs.device).synchronize()
         na, rs = C.c_int64(), C.c_double()
         _check(self.lib.orl_buffer_append_rollout(self._h, int(term_kind), obs.data_ptr(), act.data_ptr(), next_obs.data_ptr(), rew.data_ptr(),
                                                   n, alive_next_obs.data_ptr(), C.byref(na), C.byref(rs)), "orl_buffer_append_rollout")
@@ -1005,7 +1014,6 @@ class DeviceBuffer(_Handle):
         """one rollout step of every run (orl_buffer_append_rollout_runs): ``rings[r]`` receives the first ``n[r]`` rows of run r.
         obs / next_obs / alive_next_obs [R, stride, obs_dim], act [R, stride, act_dim], rew [R, stride]: contiguous fp32 tensors on the
         rings' device.  Returns (n_alive int64 [R], float64 reward sums [R])."""
-        import torch
         rings = list(rings)
         if not rings:
             raise ValueError("append_rollout_runs: no rings")
@@ -1013,19 +1021,11 @@ class DeviceBuffer(_Handle):
         if obs.dim() != 3:
             raise ValueError(f"append_rollout_runs: obs has shape {tuple(obs.shape)}, expected [{R}, stride, {b0.obs_dim}]")
         stride = int(obs.shape[1])
-        for name, t, shape in (("obs", obs, (R, stride, b0.obs_dim)), ("act", act, (R, stride, b0.act_dim)),
-                               ("next_obs", next_obs, (R, stride, b0.obs_dim)), ("rew", rew, None),
-                               ("alive_next_obs", alive_next_obs, (R, stride, b0.obs_dim))):
-            if not _is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" \
-                    or (t.device.index or 0) != b0.device:
-                raise ValueError(f"append_rollout_runs: {name} must be a contiguous fp32 tensor on the rings' device")
-            if shape is not None and tuple(t.shape) != shape:
-                raise ValueError(f"append_rollout_runs: {name} has shape {tuple(t.shape)}, expected {shape}")
+        _device_rows("append_rollout_runs", "the rings'", b0, (R, stride), obs, act, next_obs, rew, alive_next_obs, alive_shaped=True)
         if rew.numel() != R * stride:
             raise ValueError(f"append_rollout_runs: rew needs {R} x {stride} values")
         if len(n) != R:
             raise ValueError(f"append_rollout_runs: {len(n)} row counts for {R} rings")
-        torch.cuda.current_stream(obs.device).synchronize()
         hs = (C.c_void_p * R)(*[b._h.value for b in rings])
         cn = (C.c_int64 * R)(*[int(x) for x in n])
         na, rs = (C.c_int64 * R)(), (C.c_double * R)()
@@ -1072,18 +1072,10 @@ class TrajStore(_Handle):
     def append_step(self, term_kind: int, obs, act, next_obs, rew, alive_next_obs) -> int:
         """one model step of the rollout (orl_traj_append_step): contiguous fp32 torch tensors on the store's device, row i of the i-th
         live trajectory; ``alive_next_obs`` has room for every row.  Returns the survivor count."""
-        import torch
         n = int(obs.shape[0])
-        for name, t, shape in (("obs", obs, (n, self.obs_dim)), ("act", act, (n, self.act_dim)), ("next_obs", next_obs, (n, self.obs_dim)),
-                               ("rew", rew, None), ("alive_next_obs", alive_next_obs, None)):
-            if not _is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" \
-                    or (t.device.index or 0) != self.device:
-                raise ValueError(f"append_step: {name} must be a contiguous fp32 tensor on the store's device")
-            if shape is not None and tuple(t.shape) != shape:
-                raise ValueError(f"append_step: {name} has shape {tuple(t.shape)}, expected {shape}")
+        _device_rows("append_step", "the store's", self, (n,), obs, act, next_obs, rew, alive_next_obs)
         if rew.numel() != n or alive_next_obs.numel() < n * self.obs_dim:
             raise ValueError("append_step: rew needs n values, alive_next_obs room for n rows")
-        torch.cuda.current_stream(obs.device).synchronize()
         na = C.c_int64()
         _check(self.lib.orl_traj_append_step(self._h, int(term_kind), obs.data_ptr(), act.data_ptr(), next_obs.data_ptr(), rew.data_ptr(), n,
                                              alive_next_obs.data_ptr(), C.byref(na)), "orl_traj_append_step")
