@@ -315,6 +315,18 @@ int orl_traj_reset(orl_traj* t, int64_t n_traj);
  * column the store does not have (pen: column 26; hopper / walker2d: column 1), alive_next_obs == next_obs. */
 int orl_traj_append_step(orl_traj* t, int32_t term_kind, const float* obs, const float* act, const float* next_obs, const float* rew,
                          int64_t n, float* alive_next_obs, int64_t* n_alive);
+/* The same step with the rows counted on the device: nothing is read back, so the host need not wait for the step before it enqueues
+ * the next.  `bound` is any host-known upper bound on the live count (survivor counts never increase, so an older count is one); it
+ * sizes the grid and the arrays the caller provides (obs / act / next_obs / rew: `bound` rows, of which only the first `live` are read;
+ * alive_next_obs: room for the survivors).  The kernels take the live count and the row base from device cells and publish the next
+ * step's; the cells are kept twice, alternating by step, so no launch reads a cell it writes.  live == 0 writes nothing.  Same
+ * kernels, same fixed order and bits as orl_traj_append_step.  The host keeps upper bounds (rows: the sum of the bounds) and refuses,
+ * before any launch, a bound that could exceed the capacity, next to orl_traj_append_step's refusals of kinds and overlap; the kernels
+ * clamp as well and raise a sticky cell that orl_traj_finish / orl_traj_live report as an error (a bound below the live count does
+ * that too; orl_traj_reset clears it).  orl_traj_finish and orl_traj_live refresh the host's rows / live from the cells (one read);
+ * orl_traj_append_step and orl_traj_read before such a refresh are refused.  Null stream, like every orl_traj_* call. */
+int orl_traj_append_step_counted(orl_traj* t, int32_t term_kind, const float* obs, const float* act, const float* next_obs,
+                                 const float* rew, int64_t bound, float* alive_next_obs);
 /* the end of rollout() (rcsl.py:107-112): rtg[row] = returns[traj_idx[row]] - acc_ret[row] in float64.  HOST outputs, each may be
  * NULL: the row count, the running reward sum, the n_traj returns.  Calling it twice is harmless; a later append_step needs a new
  * finish before the returns-to-go are read or exported. */
@@ -723,6 +735,25 @@ typedef struct orl_rambo_loop {
  * devices or dims, an empty buffer, an unknown term_kind (or one that reads a missing observation column), rows < 2, no steps. */
 int orl_rambo_update_dynamics(orl_engine* e, orl_dynamics* d, orl_buffer* real, const orl_rambo_loop* a, float* metrics_mean /*[5]*/,
                               float* elapsed_ms);
+
+/* RcslPolicy.rollout (rcsl.py:57-120) as one device loop: `policy` an ORL_ALGO_AUTOREG engine, `d` its dynamics, `store` the
+ * trajectory store (reset here for n_traj trajectories).  Every launch of the three objects goes to the policy engine's stream (the
+ * dynamics' own stream and the store's reset are waited for through events first).  Step t: orl_autoreg_sample's launches on the
+ * current observation rows, orl_dyn_step's launches, orl_traj_append_step_counted into the other of two observation buffers, an
+ * asynchronous copy of the survivor count into slot t of a pinned host array, an event.  Before enqueueing step t the host waits for
+ * the event of step t - 1 - lag (if any) and uses that count as the row bound of all three parts: a stale count is a valid bound, rows
+ * in [live, bound) are computed from finite stale data and never stored.  lag = 0: exact sizes, one wait per step.  When a known count
+ * is 0 the host stops (at most `lag` steps run with nothing live); one stream synchronisation at the end, then orl_traj_finish, whose
+ * three HOST outputs these are.  init_obs: DEVICE [n_traj][obs_dim].  eps: DEVICE [length][n_traj][act_dim] standard normals, step t
+ * reads the first `bound` rows of slice t (noise keyed by step and row position); NULL: the sampler's own Philox stream.  The dynamics
+ * draws what orl_dyn_step(noise = NULL, model_idx = NULL) draws at the same call counter, which advances once per step enqueued.
+ * steps_enqueued, elapsed_ms (the HIP-event time of the loop): optional HOST outputs.  Refused before any launch, the store and every
+ * counter untouched: n_runs != 1 on either object, an engine that is not ORL_ALGO_AUTOREG, different devices or dims, a store created
+ * for fewer than n_traj trajectories or n_traj * length rows, an unknown term_kind (or one that reads a missing observation column),
+ * an unknown penalty_mode, lag < 0, a dynamics without reward. */
+int orl_mbrcsl_rollout(orl_engine* policy, orl_dynamics* d, orl_traj* store, const float* init_obs, int32_t n_traj, int32_t length,
+                       int32_t term_kind, int32_t penalty_mode, float penalty_coef, const float* eps, int32_t lag, int64_t* rows,
+                       double* reward_sum, double* returns_host, int32_t* steps_enqueued, float* elapsed_ms);
 
 /* the int32 indices of the live trajectories of the current rollout, in row order, widened to int64 into the DEVICE array
  * out_device (room for the live count, which is returned; < 0 on error).  Live indices ascend and are never compacted, so a per-trajectory

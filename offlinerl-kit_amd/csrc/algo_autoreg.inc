@@ -73,8 +73,29 @@ int Engine::autoreg_sample_room(long n) {
 
 int Engine::autoreg_sample(const float* obs, long n, const float* eps, bool on_device, float* act_out) {
   if (autoreg_sample_room(n)) return -1;
-  const int A = ad;
   const hipMemcpyKind in_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const float* d_obs = obs;
+  if (!on_device) {
+    ORL_HIP(hipMemcpyAsync(ar_sobs.p, obs, sizeof(float) * (size_t)R * n * od, hipMemcpyHostToDevice, stream));
+    d_obs = ar_sobs.p;
+  }
+  // (the noise is staged in the workspace for device callers too: the tap "ar_seps" reads it there)
+  if (eps) ORL_HIP(hipMemcpyAsync(ar_seps.p, eps, sizeof(float) * (size_t)R * n * ad, in_kind, stream));
+  if (autoreg_sample_launches(d_obs, n, eps ? ar_seps.p : nullptr, act_out, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost)) return -1;
+  ORL_HIP(hipStreamSynchronize(stream));      // the only host synchronisation of the call
+  return 0;
+}
+
+// The MBRCSL rollout loop's form: the launches of a call on device rows, nothing staged and no synchronisation.  The workspaces hold
+// the rows already (autoreg_sample_room, once, for the most rows of the loop); the kernels read `eps` ([n][act_dim] normals) where it lies.
+int Engine::autoreg_sample_enqueue(const float* obs, long n, const float* eps, float* act_out) {
+  if (n > ar_cap) return fail("autoreg_sample_enqueue: more rows than autoreg_sample_room made room for");
+  return autoreg_sample_launches(obs, n, eps, act_out, hipMemcpyDeviceToDevice);
+}
+
+// what both forms launch: obs / eps are DEVICE arrays of n rows per run (eps null: drawn into the workspace), act_out by `out_kind`
+int Engine::autoreg_sample_launches(const float* d_obs, long n, const float* eps, float* act_out, hipMemcpyKind out_kind) {
+  const int A = ad;
   // the n rows of every run lie packed at the front of the workspaces (which may hold more rows)
   auto view = [&](Mat m) { m.rs = n * m.pitch; m.cs = m.rs; return m; };
   const Mat x = view(ar_sx), z = view(ar_sz), ep = view(ar_seps);
@@ -83,13 +104,7 @@ int Engine::autoreg_sample(const float* obs, long n, const float* eps, bool on_d
   // the workspaces of THIS call as taps (a host map write, no launch): the input rows as the last draw left them, the tail of the last
   // pass and the noise, n rows each (the workspaces may be regrown by a later call, which registers them anew)
   taps["ar_sx"] = {x, n, x.pitch}; taps["ar_sz"] = {z, n, 2}; taps["ar_seps"] = {ep, n, A};
-  const float* d_obs = obs;
-  if (!on_device) {
-    ORL_HIP(hipMemcpyAsync(ar_sobs.p, obs, sizeof(float) * (size_t)R * n * od, hipMemcpyHostToDevice, stream));
-    d_obs = ar_sobs.p;
-  }
-  if (eps) ORL_HIP(hipMemcpyAsync(ep.p, eps, sizeof(float) * (size_t)R * n * A, in_kind, stream));
-  else {
+  if (!eps) {
     // device draws: Philox keyed by (seed, this entry point's call counter, run, element = row * A + dim) on a stream id no step uses
     hipLaunchKernelGGL(k_noise, dim3((unsigned)((n * A / 4 + 256) / 256), R), dim3(256), 0, stream, ep.p, n * A, 0, 0.f, 0.f, cfg.seed,
                        (const unsigned long long*)ar_calls, 0x5A5u);
@@ -97,7 +112,7 @@ int Engine::autoreg_sample(const float* obs, long n, const float* eps, bool on_d
     if (hipGetLastError() != hipSuccess) return fail("orl_autoreg_sample: noise launch failed");
   }
   AutoregDrawP d; memset(&d, 0, sizeof(d));
-  d.z = z.p; d.z_rs = z.rs; d.eps = ep.p; d.e_rs = ep.rs; d.obs = d_obs; d.o_rs = n * od;
+  d.z = z.p; d.z_rs = z.rs; d.eps = eps ? eps : ep.p; d.e_rs = ep.rs; d.obs = d_obs; d.o_rs = n * od;
   d.X = x.p; d.x_rs = x.rs; d.XP = x.pitch; d.n = n; d.od = od; d.A = A; d.first = 1;
   const dim3 grid((unsigned)((n + 255) / 256), R);
   ORL_LAUNCH("autoreg_draw", k_autoreg_draw, grid, dim3(256), d);
@@ -110,8 +125,7 @@ int Engine::autoreg_sample(const float* obs, long n, const float* eps, bool on_d
     ORL_LAUNCH("autoreg_draw", k_autoreg_draw, grid, dim3(256), d);
   }
   ORL_HIP(hipMemcpy2DAsync(act_out, sizeof(float) * A, x.p + od, sizeof(float) * x.pitch, sizeof(float) * A, (size_t)R * n,
-                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-  ORL_HIP(hipStreamSynchronize(stream));      // the only host synchronisation of the call
+                           out_kind, stream));
   return 0;
 }
 

@@ -37,6 +37,23 @@ int dynadv_forward_enqueue(orl_dynamics* d, const float* obs, const float* act, 
 int dynadv_update_enqueue(orl_dynamics* d, const float* advantage, int step);
 void dynadv_loop_end(orl_dynamics* d, hipStream_t own, long steps_done);
 
+// The trajectory store (store.hip) as the MBRCSL rollout loop of engine.hip drives it: orl_traj_append_step_counted's two launches on
+// `stream` (`who` prefixes the refusals), and what the loop checks and reads of the store -- `survivors` is the device cell that holds
+// the survivor count of the last step enqueued.
+struct TrajInfo { int dev, od, ad; long n_traj_cap, cap; const long long* survivors; };
+int traj_info(orl_traj* t, TrajInfo* out);
+int traj_append_enqueue(orl_traj* t, hipStream_t stream, int term_kind, const float* obs, const float* act, const float* next_obs,
+                        const float* rew, long bound, float* alive_next_obs, const char* who);
+
+// orl_dyn_step (dynamics.hip) as the same loop drives it: device rows in, next_obs / reward out, no staging and no synchronisation.
+// Between loop_begin and loop_end the object's launches go to `loop_stream`; begin grows the step workspaces for n_max rows, every
+// enqueue advances the call counter as orl_dyn_step does.
+struct DynStepInfo { int dev, R, od, ad; bool with_reward; hipStream_t stream; };
+int dynstep_info(orl_dynamics* d, DynStepInfo* out);
+int dynstep_loop_begin(orl_dynamics* d, hipStream_t loop_stream, long n_max, hipStream_t* own);
+int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n, int mode, float coef, float* next_obs, float* reward);
+void dynstep_loop_end(orl_dynamics* d, hipStream_t own);
+
 #define ORL_HIP(expr)                                                                            \
   do {                                                                                           \
     hipError_t _e = (expr);                                                                      \

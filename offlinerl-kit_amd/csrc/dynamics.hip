@@ -1158,6 +1158,26 @@ static int dyn_step_forward(orl_dynamics* d, const float* obs, const float* act,
   return dyn_forward(d, d->sw, (int)n, false);
 }
 
+// the launches of a step on device rows: k_dyn_step_input, the ensemble's forward, k_dyn_head; the call counter advances.  orl_dyn_step
+// stages around them, dynstep_enqueue (the MBRCSL rollout loop) is nothing else
+static int dyn_step_launches(orl_dynamics* d, const float* obs, const float* act, long n, const float* noise, const int* midx, int mode,
+                             float coef, float* next_obs, float* reward, float* raw_reward, float* penalty, int* midx_out, const char* who) {
+  if (dyn_step_forward(d, obs, act, n)) return -1;
+  DynHeadP h;
+  memset(&h, 0, sizeof(h));
+  h.OUT = d->sw.OUT; h.op = d->pitch[d->L + 1];
+  h.obs = obs; h.n = n; h.od = d->od; h.D = d->D; h.K = d->K;
+  h.params = d->params; h.P = d->P; h.off_max = d->off_max; h.off_min = d->off_min;
+  h.noise = noise; h.midx = midx;
+  h.elites = d->elites_d;
+  if ((h.n_elites = dyn_n_elites(d, who)) < 0) return -1;
+  h.seed = d->c.seed; h.call = d->step_calls++;
+  h.mode = mode; h.coef = coef;
+  h.next_obs = next_obs; h.reward = reward; h.raw_reward = raw_reward; h.penalty = penalty; h.midx_out = midx_out;
+  DEV_LAUNCH(d->stream, k_dyn_head, dim3((unsigned)((n + 255) / 256), d->R), dim3(256), 0, h);
+  return 0;
+}
+
 int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n, int on_device, const float* noise, const int64_t* model_idx,
                  int mode, float coef, float* next_obs, float* reward, float* raw_reward, float* penalty, int32_t* midx_out) {
   if (!d || !obs || !act || n < 1 || !next_obs || !reward || !raw_reward || !penalty) return fail("orl_dyn_step: bad arguments");
@@ -1173,23 +1193,10 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
     if (on_device) return fail("orl_dyn_step: teacher-forced model indices are host arrays");
     if (dyn_upload_midx(d, model_idx, (long)R * n, mi, d->sMidx, "orl_dyn_step")) return -1;
   }
-  if (dyn_step_forward(d, obs, act, n)) return -1;
-  DynHeadP h;
-  memset(&h, 0, sizeof(h));
-  h.OUT = d->sw.OUT; h.op = d->pitch[d->L + 1];
-  h.obs = obs; h.n = n; h.od = od; h.D = D; h.K = K;
-  h.params = d->params; h.P = d->P; h.off_max = d->off_max; h.off_min = d->off_min;
-  h.noise = noise; h.midx = model_idx ? d->sMidx : nullptr;
-  h.elites = d->elites_d;
-  if ((h.n_elites = dyn_n_elites(d, "orl_dyn_step")) < 0) return -1;
-  h.seed = d->c.seed; h.call = d->step_calls++;
-  h.mode = mode; h.coef = coef;
-  h.next_obs = stage_dst(next_obs, d->sNext, on_device);
-  h.reward = stage_dst(reward, d->sRew, on_device);
-  h.raw_reward = stage_dst(raw_reward, d->sRaw, on_device);
-  h.penalty = stage_dst(penalty, d->sPen, on_device);
-  h.midx_out = stage_dst((int*)midx_out, d->sMidxOut, on_device);
-  DEV_LAUNCH(d->stream, k_dyn_head, dim3((unsigned)((n + 255) / 256), R), dim3(256), 0, h);
+  if (dyn_step_launches(d, obs, act, n, noise, model_idx ? d->sMidx : nullptr, mode, coef, stage_dst(next_obs, d->sNext, on_device),
+                        stage_dst(reward, d->sRew, on_device), stage_dst(raw_reward, d->sRaw, on_device),
+                        stage_dst(penalty, d->sPen, on_device), stage_dst((int*)midx_out, d->sMidxOut, on_device), "orl_dyn_step"))
+    return -1;
   if (stage_out(d->stream, next_obs, d->sNext, (size_t)R * n * od, on_device) || stage_out(d->stream, reward, d->sRew, (size_t)R * n, on_device) ||
       stage_out(d->stream, raw_reward, d->sRaw, (size_t)R * n, on_device) || stage_out(d->stream, penalty, d->sPen, (size_t)R * n, on_device) ||
       stage_out(d->stream, (int*)midx_out, d->sMidxOut, (size_t)R * n, on_device))
@@ -1520,5 +1527,28 @@ void dynadv_loop_end(orl_dynamics* d, hipStream_t own, long steps_done) {
   for (int r = 0; r < d->R; ++r) d->adv_tstep[r] += steps_done;
   if (steps_done > 0) { d->tap_adv_fwd = d->tap_adv_upd = d->tap_nll = true; }
 }
+
+// ---- the model step as the MBRCSL rollout loop drives it (engine.hip: orl_mbrcsl_rollout; declared in devobj.h) ----
+int dynstep_info(orl_dynamics* d, DynStepInfo* o) {
+  if (!d || !o) return fail("dynstep_info: null handle");
+  o->dev = d->c.device; o->R = d->R; o->od = d->od; o->ad = d->ad; o->with_reward = d->c.with_reward != 0; o->stream = d->stream;
+  return 0;
+}
+
+int dynstep_loop_begin(orl_dynamics* d, hipStream_t loop_stream, long n_max, hipStream_t* own) {
+  *own = d->stream;
+  if (dyn_grow_step(d, n_max)) return -1;      // (on the object's own stream, which the loop's has already waited for)
+  d->stream = loop_stream;
+  return 0;
+}
+
+// (the raw reward and the penalty land in the step workspace, as they do for a host caller of orl_dyn_step)
+int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n, int mode, float coef, float* next_obs, float* reward) {
+  if (dyn_step_launches(d, obs, act, n, nullptr, nullptr, mode, coef, next_obs, reward, d->sRaw, d->sPen, nullptr, "orl_mbrcsl_rollout")) return -1;
+  d->tap_step_rows = n; d->tap_step_t = false;
+  return 0;
+}
+
+void dynstep_loop_end(orl_dynamics* d, hipStream_t own) { d->stream = own; }
 
 }  // namespace orl

@@ -333,6 +333,8 @@ struct Engine {
   // the device-drawn stream lives in a device cell of its own (the step counter and orl_learn_n's streams stay untouched)
   int autoreg_sample(const float* obs, long n, const float* eps, bool on_device, float* act_out);
   int autoreg_sample_room(long n);
+  int autoreg_sample_enqueue(const float* obs, long n, const float* eps, float* act_out);
+  int autoreg_sample_launches(const float* d_obs, long n, const float* eps, float* act_out, hipMemcpyKind out_kind);
   long ar_cap = 0;
   Mat ar_sx, ar_sz, ar_seps, ar_sobs; std::vector<Mat> ar_sh;
   unsigned long long* ar_calls = nullptr;
@@ -352,6 +354,14 @@ struct Engine {
   Mat rb_obs[2], rb_act, rb_eps, rb_sl[5], rb_rew, rb_adv;
   float* rb_acc = nullptr;
   unsigned long long* rb_calls = nullptr;
+  // The MBRCSL rollout loop (orl_mbrcsl_rollout; AUTOREG engines): two observation buffers that swap roles, action, next observation
+  // and reward rows for n_traj trajectories, the pinned host array the survivor count of every step is copied to, and one event per
+  // step in flight (a ring of lag + 1)
+  int mbrcsl_room(long n_traj, long length, long events);
+  long ml_cap = 0, ml_counts_cap = 0;
+  Mat ml_obs[2], ml_act, ml_next, ml_rew;
+  long long* ml_counts = nullptr;
+  std::vector<hipEvent_t> ml_events;
 };
 
 }  // namespace orl

@@ -215,6 +215,8 @@ Engine::~Engine() {
     if (graph[i]) hipGraphDestroy(graph[i]);
   }
   for (auto& e : ev_pool) hipEventDestroy(e);
+  for (auto& e : ml_events) hipEventDestroy(e);
+  if (ml_counts) hipHostFree(ml_counts);
   for (void* p : allocs) hipFree(p);
   if (stream) hipStreamDestroy(stream);
 }
@@ -2026,6 +2028,119 @@ int orl_rambo_update_dynamics(orl_engine* h, orl_dynamics* d, orl_buffer* real, 
   unsigned int bad = 0;
   if (e.health_update(nullptr, 0, &bad)) return -1;
   return bad ? ORL_RC_UNHEALTHY : 0;
+}
+
+// row buffers, count slots and events of the MBRCSL rollout loop; the row buffers are zero-filled, so a row no step has written holds zeros
+int Engine::mbrcsl_room(long n_traj, long length, long events) {
+  if (n_traj > ml_cap) {
+    ORL_HIP(hipStreamSynchronize(stream));
+    for (Mat* m : {&ml_obs[0], &ml_obs[1], &ml_act, &ml_next, &ml_rew}) adv_drop(this, *m);
+    ml_cap = 0;
+    if (!(adv_make(this, ml_obs[0], n_traj, od) && adv_make(this, ml_obs[1], n_traj, od) && adv_make(this, ml_act, n_traj, ad) &&
+          adv_make(this, ml_next, n_traj, od) && adv_make(this, ml_rew, n_traj, 1)))
+      return fail("orl_mbrcsl_rollout: hipMalloc row buffers");
+    ml_cap = n_traj;
+  }
+  if (length > ml_counts_cap) {
+    ORL_HIP(hipStreamSynchronize(stream));
+    if (ml_counts) hipHostFree(ml_counts);
+    ml_counts = nullptr; ml_counts_cap = 0;
+    ORL_HIP(hipHostMalloc((void**)&ml_counts, sizeof(long long) * length, hipHostMallocDefault));
+    ml_counts_cap = length;
+  }
+  while ((long)ml_events.size() < events) {
+    hipEvent_t ev;
+    ORL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    ml_events.push_back(ev);
+  }
+  return 0;
+}
+
+int orl_mbrcsl_rollout(orl_engine* h, orl_dynamics* d, orl_traj* store, const float* init_obs, int32_t n_traj, int32_t length, int32_t term_kind,
+                       int32_t penalty_mode, float penalty_coef, const float* eps, int32_t lag, int64_t* rows, double* reward_sum,
+                       double* returns_host, int32_t* steps_enqueued, float* elapsed_ms) {
+  const char* F = "orl_mbrcsl_rollout";
+  const std::string f(F);
+  if (!h || !d || !store || !init_obs || n_traj < 1 || length < 1) return fail(f + ": bad arguments");
+  Engine& e = h->e;
+  DynStepInfo di;
+  TrajInfo ti;
+  if (dynstep_info(d, &di) || traj_info(store, &ti)) return -1;
+  char msg[256];
+  if (e.cfg.algo != ORL_ALGO_AUTOREG) return fail(f + ": not an AUTOREG engine");
+  if (e.R != 1 || di.R != 1) return fail(f + ": one run per policy and per dynamics ensemble (n_runs == 1 on both)");
+  if (di.dev != e.dev || ti.dev != e.dev) return fail(f + ": engine, dynamics and trajectory store must live on one device");
+  if (di.od != e.od || di.ad != e.ad || ti.od != e.od || ti.ad != e.ad) return fail(f + ": obs / act dims of engine, dynamics and trajectory store differ");
+  if (!di.with_reward) return fail(f + ": needs a dynamics with_reward (the step splits the reward off the last output)");
+  if (penalty_mode < 0 || penalty_mode > 2) return fail(f + ": unknown penalty mode");
+  if (term_refusal(f, term_kind, e.od, "engine")) return -1;
+  if (lag < 0) return fail(f + ": lag must be >= 0 (the steps enqueued before a survivor count is read)");
+  if (n_traj > (1 << 24)) return fail(f + ": more than 2^24 trajectories");
+  if (n_traj > ti.n_traj_cap) {
+    snprintf(msg, sizeof(msg), "%s: %d trajectories, the store was created for %lld", F, (int)n_traj, (long long)ti.n_traj_cap);
+    return fail(msg);
+  }
+  if ((long)n_traj * length > ti.cap) {
+    snprintf(msg, sizeof(msg), "%s: %d trajectories x %d steps need %lld rows, the store's capacity is %lld", F, (int)n_traj, (int)length,
+             (long long)n_traj * length, (long long)ti.cap);
+    return fail(msg);
+  }
+  ORL_HIP(hipSetDevice(e.dev));
+  const long n_ev = std::min<long>((long)lag + 1, length);
+  if (e.autoreg_sample_room(n_traj) || e.mbrcsl_room(n_traj, length, n_ev)) return -1;
+  struct Events {
+    hipEvent_t a = nullptr, b = nullptr, order = nullptr;
+    ~Events() { for (hipEvent_t x : {a, b, order}) if (x) hipEventDestroy(x); }
+  } ev;
+  ORL_HIP(hipEventCreate(&ev.a));
+  ORL_HIP(hipEventCreate(&ev.b));
+  ORL_HIP(hipEventCreateWithFlags(&ev.order, hipEventDisableTiming));
+  if (orl_traj_reset(store, n_traj)) return -1;
+  // the store's reset (null stream) and whatever the dynamics' own stream still holds come first; from here to the end every launch of
+  // the three objects is on e.stream
+  ORL_HIP(hipEventRecord(ev.order, nullptr));
+  ORL_HIP(hipStreamWaitEvent(e.stream, ev.order, 0));
+  ORL_HIP(hipEventRecord(ev.order, di.stream));
+  ORL_HIP(hipStreamWaitEvent(e.stream, ev.order, 0));
+  hipStream_t own = nullptr;
+  if (dynstep_loop_begin(d, e.stream, n_traj, &own)) { dynstep_loop_end(d, own); return -1; }
+  if (e.prof_on) { e.prof.clear(); e.ev_used = 0; }
+  int enq = 0, cur = 0;
+  const auto body = [&]() -> int {
+    ORL_HIP(hipEventRecord(ev.a, e.stream));
+    ORL_HIP(hipMemcpyAsync(e.ml_obs[0].p, init_obs, sizeof(float) * (size_t)n_traj * e.od, hipMemcpyDeviceToDevice, e.stream));
+    long bound = n_traj;
+    for (int t = 0; t < length; ++t) {
+      // the newest survivor count the host may wait for without stalling on a step it has just enqueued: counts never increase, so it
+      // bounds the live rows of step t
+      const int k = t - 1 - lag;
+      if (k >= 0) {
+        ORL_HIP(hipEventSynchronize(e.ml_events[k % n_ev]));
+        bound = (long)e.ml_counts[k];
+      }
+      if (bound == 0) break;
+      float *obs = e.ml_obs[cur].p, *nxt = e.ml_obs[cur ^ 1].p;
+      if (e.autoreg_sample_enqueue(obs, bound, eps ? eps + (size_t)t * n_traj * e.ad : nullptr, e.ml_act.p)) return -1;
+      if (dynstep_enqueue(d, obs, e.ml_act.p, bound, penalty_mode, penalty_coef, e.ml_next.p, e.ml_rew.p)) return -1;
+      if (traj_append_enqueue(store, e.stream, term_kind, obs, e.ml_act.p, e.ml_next.p, e.ml_rew.p, bound, nxt, F)) return -1;
+      ORL_HIP(hipMemcpyAsync(e.ml_counts + t, ti.survivors, sizeof(long long), hipMemcpyDeviceToHost, e.stream));
+      ORL_HIP(hipEventRecord(e.ml_events[t % n_ev], e.stream));
+      ++enq;
+      cur ^= 1;
+    }
+    ORL_HIP(hipEventRecord(ev.b, e.stream));
+    return 0;
+  };
+  const int rc = body();
+  const hipError_t se = hipStreamSynchronize(e.stream);      // the one unconditional host synchronisation (also on an error path)
+  dynstep_loop_end(d, own);
+  if (steps_enqueued) *steps_enqueued = enq;
+  if (rc) return -1;
+  if (se != hipSuccess) return fail(f + ": " + hipGetErrorString(se));
+  float ms = 0.f;
+  ORL_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+  if (elapsed_ms) *elapsed_ms = ms;
+  return orl_traj_finish(store, rows, reward_sum, returns_host);
 }
 
 int orl_health(orl_engine* h, uint32_t* flags_out) {

@@ -102,11 +102,14 @@ struct Traj : Rows {        // HBM-resident trajectory store of the RCSL rollout
   long n_traj = 0, rows = 0, live = 0;    // of the current rollout: trajectories, rows appended, trajectories still running
   int half = 0;                           // which of the two live arrays holds the running trajectories
   bool finished = false;                  // rtg[] is valid for rows [0, rows)
+  // counted steps (orl_traj_append_step_counted) count on the device: until a refresh `live` is an upper bound and `rows` is stale
+  long rows_bound = 0;                    // upper bound on the rows written: rows + the bounds enqueued since the last refresh
+  bool stale = false;
   int* tidx = nullptr; double *acc = nullptr, *rtg = nullptr;
   double* returns = nullptr;
   int* live_idx[2] = {nullptr, nullptr}; double* live_acc[2] = {nullptr, nullptr};
   int* blk_cnt = nullptr; double* blk_rew = nullptr;      // per-block scratch: max(blocks of a step, blocks of an export)
-  long long* cells = nullptr; double* rew_total = nullptr; // 3 result cells, the running reward sum
+  long long* cells = nullptr; double* rew_total = nullptr; // the result and count cells (store.hip: CELL_*), the running reward sum
   ~Traj();
 };
 

@@ -165,6 +165,7 @@ __global__ void k_roll_scatter(RollP p) {
 // k_traj_total count (the host refuses a ring that is too small before a row is written), k_traj_export scatters.  Fixed block order
 // everywhere, no tickets, no atomics.
 // ------------------------------------------------------------------------------------------------
+enum { CELL_LIVE = 3, CELL_ROWS = 5, CELL_OVERFLOW = 7, TRAJ_CELLS = 8 };
 struct TrajP {
   Rows c; int* tidx; double *acc, *rtg;                                  // the rows: [cap][OP], [cap][OP], [cap][AP], [cap] each
   double* returns;                                                       // [n_traj]
@@ -174,9 +175,11 @@ struct TrajP {
   int kind;
   const float *s_obs, *s_act, *s_nobs, *s_rew;                           // packed sources [n][od], [n][ad], [n][od], [n]
   long row0, n;                                                          // step: rows [row0, row0 + n) are appended; finish / export: rows [0, n)
+  long cap; int half;                                                    // counted step: the store's row capacity, the parity of the step
   float* alive_nobs;
   int* blk_cnt; double* blk_rew;                                         // per-block scratch
-  long long* cells;                                                      // [0] survivors of the step, [1] rows kept, [2] trajectories kept
+  long long* cells;                                                      // [0] survivors of the step, [1] rows kept, [2] trajectories kept,
+                                                                         // [3 + h] live count, [5 + h] rows written (h: step parity), [7] overflow
   double* rew_total;                                                     // running sum of every appended reward
   int use_thr; double thr;                                               // export: keep rows of trajectories with returns > thr
   Rows d; long d_row0;                                                   // export: the destination ring (same pitches) and its first free row
@@ -184,12 +187,31 @@ struct TrajP {
 __global__ void k_traj_reset(TrajP p) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < p.n_traj) { p.returns[i] = 0.0; p.next_idx[i] = (int)i; p.next_acc[i] = 0.0; }
-  if (i == 0) *p.rew_total = 0.0;
+  if (i == 0) { *p.rew_total = 0.0; p.cells[CELL_LIVE + (p.half ^ 1)] = p.n_traj; p.cells[CELL_ROWS + (p.half ^ 1)] = 0; p.cells[CELL_OVERFLOW] = 0; }
 }
+// The rows of a step and where they go.  Host-counted (orl_traj_append_step): both by value.  COUNTED (orl_traj_append_step_counted): the
+// launch covers p.n rows, a host-known upper bound; the live count and the rows written so far come from the cells of the step's parity,
+// which no block of this step writes (block 0 of k_traj_scatter publishes the next step's values into the other pair while blocks of
+// its launch may still be reading).  The count is clamped to the bound and to the room left; either clamp raises the sticky overflow cell.
+struct StepRows { long row0, n; bool over; };
+template <bool COUNTED>
+__device__ inline StepRows step_rows(const TrajP& p) {
+  if (!COUNTED) return {p.row0, p.n, false};
+  const long live = (long)p.cells[CELL_LIVE + p.half], row0 = (long)p.cells[CELL_ROWS + p.half];
+  long n = live < p.n ? live : p.n;
+  if (n > p.cap - row0) n = p.cap - row0;
+  if (n < 0) n = 0;
+  return {row0, n, n != live};
+}
+template <bool COUNTED>
 __global__ void k_traj_term(TrajP p) {
-  term_count(p.kind, p.s_nobs, p.s_rew, p.c.od, p.n, p.c.term, FlatRow{p.row0}, p.blk_cnt + blockIdx.x, p.blk_rew + blockIdx.x);
+  const StepRows s = step_rows<COUNTED>(p);
+  term_count(p.kind, p.s_nobs, p.s_rew, p.c.od, s.n, p.c.term, FlatRow{s.row0}, p.blk_cnt + blockIdx.x, p.blk_rew + blockIdx.x);
 }
+template <bool COUNTED>
 __global__ void k_traj_scatter(TrajP p) {
+  const StepRows s = step_rows<COUNTED>(p);
+  p.row0 = s.row0; p.n = s.n;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const FlatRow at{p.row0};
   const bool alive = i < p.n && p.c.term[at(i)] == 0.0f;
@@ -207,6 +229,9 @@ __global__ void k_traj_scatter(TrajP p) {
     long long na; double rs;
     block_totals(p.blk_cnt, p.blk_rew, (int)gridDim.x, &na, &rs);
     p.cells[0] = na;
+    p.cells[CELL_LIVE + (p.half ^ 1)] = na;
+    p.cells[CELL_ROWS + (p.half ^ 1)] = p.row0 + p.n;
+    if (s.over) p.cells[CELL_OVERFLOW] = 1;
     *p.rew_total = *p.rew_total + rs;
   }
 }
@@ -503,7 +528,60 @@ static TrajP traj_params(Traj& t) {
   p.returns = t.returns; p.n_traj = t.n_traj;
   p.live_idx = t.live_idx[t.half]; p.live_acc = t.live_acc[t.half]; p.next_idx = t.live_idx[t.half ^ 1]; p.next_acc = t.live_acc[t.half ^ 1];
   p.blk_cnt = t.blk_cnt; p.blk_rew = t.blk_rew; p.cells = t.cells; p.rew_total = t.rew_total;
+  p.cap = t.cap; p.half = t.half;
   return p;
+}
+
+// the two launches of a step on `stream`; COUNTED: p.n is the bound that sizes the grid
+template <bool COUNTED>
+static int traj_step_launches(const TrajP& p, hipStream_t stream) {
+  const unsigned blocks = (unsigned)((p.n + 255) / 256);
+  DEV_LAUNCH(stream, k_traj_term<COUNTED>, dim3(blocks), dim3(256), 0, p);
+  DEV_LAUNCH(stream, k_traj_scatter<COUNTED>, dim3(blocks), dim3(256), 0, p);
+  return 0;
+}
+// what a step refuses whoever counts its rows
+static int traj_step_refusal(const Traj& t, const std::string& who, int term_kind, const float* next_obs, const float* alive_next_obs, long n) {
+  if (t.rows_bound + n > t.cap) {
+    char msg[224];
+    snprintf(msg, sizeof(msg), "%s: %lld rows + %lld more than the store's capacity %lld", who.c_str(), (long long)t.rows_bound, (long long)n,
+             (long long)t.cap);
+    return fail(msg);
+  }
+  if (term_refusal(who, term_kind, t.od, "buffer")) return -1;
+  if (alive_next_obs == next_obs) return fail(who + ": alive_next_obs must not overlap next_obs");
+  return 0;
+}
+// the host's rows / live after counted steps: one read of the cells once the device has drained.  -1 also when a counted step overflowed
+static int traj_refresh(Traj& t, const char* who) {
+  if (!t.stale) return 0;
+  ORL_HIP(hipDeviceSynchronize());
+  long long c[TRAJ_CELLS];
+  ORL_HIP(hipMemcpy(c, t.cells, sizeof(c), hipMemcpyDeviceToHost));
+  t.live = (long)c[CELL_LIVE + t.half]; t.rows = t.rows_bound = (long)c[CELL_ROWS + t.half];
+  t.stale = false;
+  if (c[CELL_OVERFLOW])
+    return fail(std::string(who) + ": a counted step found more live trajectories than its bound, or rows beyond the capacity (orl_traj_reset clears)");
+  return 0;
+}
+
+// orl_traj_append_step_counted on `stream` (declared in devobj.h: the MBRCSL rollout loop places it on the policy engine's stream)
+int traj_append_enqueue(orl_traj* h, hipStream_t stream, int term_kind, const float* obs, const float* act, const float* next_obs,
+                        const float* rew, long bound, float* alive_next_obs, const char* who) {
+  Traj& t = h->t;
+  if (traj_step_refusal(t, who, term_kind, next_obs, alive_next_obs, bound)) return -1;
+  TrajP p = traj_params(t);
+  p.kind = term_kind; p.s_obs = obs; p.s_act = act; p.s_nobs = next_obs; p.s_rew = rew; p.n = bound; p.alive_nobs = alive_next_obs;
+  if (traj_step_launches<true>(p, stream)) return -1;
+  // (the host keeps upper bounds until traj_refresh: survivors <= min(live, bound), rows <= the sum of the bounds)
+  t.rows_bound += bound; t.live = std::min(t.live, bound); t.half ^= 1; t.finished = false; t.stale = true;
+  return 0;
+}
+int traj_info(orl_traj* h, TrajInfo* o) {
+  if (!h || !o) return fail("traj_info: null handle");
+  const Traj& t = h->t;
+  o->dev = t.dev; o->od = t.od; o->ad = t.ad; o->n_traj_cap = t.n_traj_cap; o->cap = t.cap; o->survivors = t.cells;
+  return 0;
 }
 
 }  // namespace orl
@@ -664,7 +742,7 @@ int orl_traj_create(int32_t obs_dim, int32_t act_dim, int32_t device, int64_t n_
   if (t.alloc_rows(t.cap) || alloc_zeroed(&t.tidx, t.cap) || alloc_zeroed(&t.acc, t.cap) || alloc_zeroed(&t.rtg, t.cap) ||
       alloc_zeroed(&t.returns, n_traj) || alloc_zeroed(&t.live_idx[0], n_traj) || alloc_zeroed(&t.live_idx[1], n_traj) ||
       alloc_zeroed(&t.live_acc[0], n_traj) || alloc_zeroed(&t.live_acc[1], n_traj) || alloc_zeroed(&t.blk_cnt, blocks) ||
-      alloc_zeroed(&t.blk_rew, blocks) || alloc_zeroed(&t.cells, 3) || alloc_zeroed(&t.rew_total, 1)) {
+      alloc_zeroed(&t.blk_rew, blocks) || alloc_zeroed(&t.cells, TRAJ_CELLS) || alloc_zeroed(&t.rew_total, 1)) {
     delete h;
     *out = nullptr;
     return -1;
@@ -682,7 +760,7 @@ int orl_traj_reset(orl_traj* h, int64_t n_traj) {
     return fail(msg);
   }
   ORL_HIP(hipSetDevice(t.dev));
-  t.n_traj = n_traj; t.rows = 0; t.live = n_traj; t.half = 1; t.finished = false;
+  t.n_traj = n_traj; t.rows = t.rows_bound = 0; t.live = n_traj; t.half = 1; t.finished = false; t.stale = false;
   TrajP p = traj_params(t);                 // (half = 1: the kernel fills the `next` half, 0, which then becomes the current one)
   hipLaunchKernelGGL(k_traj_reset, dim3((unsigned)((n_traj + 255) / 256)), dim3(256), 0, 0, p);
   ORL_HIP(hipGetLastError());
@@ -694,34 +772,35 @@ int orl_traj_append_step(orl_traj* h, int32_t term_kind, const float* obs, const
   if (!h || !obs || !act || !next_obs || !rew || !alive_next_obs || !n_alive || n < 1) return fail("orl_traj_append_step: bad arguments");
   Traj& t = h->t;
   char msg[200];
+  if (t.stale)
+    return fail("orl_traj_append_step: the row counts are on the device after orl_traj_append_step_counted; orl_traj_live or orl_traj_finish "
+                "refreshes the host's before a host-counted step");
   if (n != t.live) {
     snprintf(msg, sizeof(msg), "orl_traj_append_step: %lld rows, %lld trajectories are live", (long long)n, (long long)t.live);
     return fail(msg);
   }
-  if (t.rows + n > t.cap) {
-    snprintf(msg, sizeof(msg), "orl_traj_append_step: %lld rows + %lld more than the store's capacity %lld", (long long)t.rows, (long long)n, (long long)t.cap);
-    return fail(msg);
-  }
-  if (term_refusal("orl_traj_append_step", term_kind, t.od, "buffer")) return -1;
-  if (alive_next_obs == next_obs) return fail("orl_traj_append_step: alive_next_obs must not overlap next_obs");
+  if (traj_step_refusal(t, "orl_traj_append_step", term_kind, next_obs, alive_next_obs, n)) return -1;
   ORL_HIP(hipSetDevice(t.dev));
   TrajP p = traj_params(t);
   p.kind = term_kind; p.s_obs = obs; p.s_act = act; p.s_nobs = next_obs; p.s_rew = rew; p.row0 = t.rows; p.n = n; p.alive_nobs = alive_next_obs;
-  const unsigned blocks = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(k_traj_term, dim3(blocks), dim3(256), 0, 0, p);
-  ORL_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_traj_scatter, dim3(blocks), dim3(256), 0, 0, p);
-  ORL_HIP(hipGetLastError());
+  if (traj_step_launches<false>(p, 0)) return -1;
   long long na = 0;
   ORL_HIP(hipMemcpy(&na, t.cells, sizeof(na), hipMemcpyDeviceToHost));      // the one read of a step: it sizes the next one
-  t.rows += n; t.live = na; t.half ^= 1; t.finished = false;
+  t.rows += n; t.rows_bound = t.rows; t.live = na; t.half ^= 1; t.finished = false;
   *n_alive = na;
   return 0;
+}
+int orl_traj_append_step_counted(orl_traj* h, int32_t term_kind, const float* obs, const float* act, const float* next_obs, const float* rew,
+                                 int64_t bound, float* alive_next_obs) {
+  if (!h || !obs || !act || !next_obs || !rew || !alive_next_obs || bound < 1) return fail("orl_traj_append_step_counted: bad arguments");
+  ORL_HIP(hipSetDevice(h->t.dev));
+  return traj_append_enqueue(h, 0, term_kind, obs, act, next_obs, rew, (long)bound, alive_next_obs, "orl_traj_append_step_counted");
 }
 int orl_traj_finish(orl_traj* h, int64_t* rows, double* reward_sum, double* returns_host) {
   if (!h) return fail("orl_traj_finish: bad arguments");
   Traj& t = h->t;
   ORL_HIP(hipSetDevice(t.dev));
+  if (traj_refresh(t, "orl_traj_finish")) return -1;
   if (t.rows > 0) {
     TrajP p = traj_params(t);
     p.n = t.rows;
@@ -739,6 +818,7 @@ int64_t orl_traj_live(orl_traj* h, int64_t* out_device) {
   if (!h || !out_device) return fail("orl_traj_live: bad arguments");
   Traj& t = h->t;
   if (hipSetDevice(t.dev) != hipSuccess) return fail("orl_traj_live: hipSetDevice failed");
+  if (traj_refresh(t, "orl_traj_live")) return -1;
   if (t.live > 0) {
     hipLaunchKernelGGL(k_traj_live, dim3((unsigned)((t.live + 255) / 256)), dim3(256), 0, 0, t.live_idx[t.half], t.live, (long long*)out_device);
     if (hipGetLastError() != hipSuccess) return fail("orl_traj_live: launch failed");
@@ -749,6 +829,7 @@ int orl_traj_read(orl_traj* h, int64_t row0, int64_t n, float* obs, float* act, 
                   double* acc_ret, double* rtg) {
   if (!h || n < 0 || row0 < 0) return fail("orl_traj_read: bad arguments");
   Traj& t = h->t;
+  if (t.stale) return fail("orl_traj_read: the row counts are on the device after orl_traj_append_step_counted (orl_traj_live or orl_traj_finish first)");
   if (row0 + n > t.rows) return fail("orl_traj_read: rows beyond the store");
   if (rtg && !t.finished) return fail("orl_traj_read: the returns-to-go exist after orl_traj_finish");
   if (n == 0) return 0;

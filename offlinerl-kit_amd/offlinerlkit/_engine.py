@@ -69,6 +69,8 @@ ABI_SYMBOLS = [
     # the RCSL rollout's trajectory store
     "orl_traj_create", "orl_traj_destroy", "orl_traj_reset", "orl_traj_append_step", "orl_traj_finish", "orl_traj_read", "orl_traj_export",
     "orl_traj_live",
+    # ... its device-counted step and the MBRCSL rollout as one device loop around it
+    "orl_traj_append_step_counted", "orl_mbrcsl_rollout",
     # DiffusionBC: the diffusion behaviour policy
     "orl_diffusion_config_default", "orl_diffusion_create", "orl_diffusion_destroy", "orl_diffusion_floats", "orl_diffusion_num_tensors",
     "orl_diffusion_tensor", "orl_diffusion_set", "orl_diffusion_get", "orl_diffusion_set_step_count", "orl_diffusion_step_count",
@@ -289,6 +291,7 @@ def load_library(path: Optional[str] = None):
     lib.orl_traj_destroy.restype = None
     lib.orl_traj_reset.argtypes = [C.c_void_p, C.c_int64]
     lib.orl_traj_append_step.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.orl_traj_append_step_counted.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]
     lib.orl_traj_finish.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p]
     lib.orl_traj_read.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 8
     lib.orl_traj_export.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -302,6 +305,9 @@ def load_library(path: Optional[str] = None):
     lib.orl_engine_lcb_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_adv_advantage.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_rambo_update_dynamics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OrlRamboLoop), C.c_void_p, C.POINTER(C.c_float)]
+    lib.orl_mbrcsl_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                       C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_float)]
     lib.orl_health.argtypes = [C.c_void_p, C.c_void_p]
     lib.orl_health_check.argtypes = [C.c_void_p, C.c_void_p]
     lib.orl_health_clear.argtypes = [C.c_void_p]
@@ -811,6 +817,19 @@ class Engine(_Handle):
                          "orl_rambo_update_dynamics")
         return {k: float(v) for k, v in zip(RAMBO_KEYS, m)}, ms.value
 
+    def mbrcsl_rollout(self, dyn: "Dynamics", store: "TrajStore", init_obs_ptr: int, n_traj: int, length: int, term_kind: int,
+                       penalty_mode: int, penalty_coef: float, eps_ptr: Optional[int] = None, lag: int = 2):
+        """The RCSL rollout as one device loop (orl_mbrcsl_rollout) on an AUTOREG engine: ``init_obs_ptr`` a device pointer to
+        [n_traj][obs_dim], ``eps_ptr`` one to [length][n_traj][act_dim] standard normals (None: the sampler's Philox stream).  Resets
+        and finishes ``store``.  Returns (rows, float64 reward sum, returns float64 [n_traj], steps enqueued, elapsed ms)."""
+        rows, rs, enq, ms = C.c_int64(), C.c_double(), C.c_int32(), C.c_float()
+        returns = np.empty(int(n_traj), dtype=np.float64)
+        _check(self.lib.orl_mbrcsl_rollout(self._h, dyn._h, store._h, int(init_obs_ptr), int(n_traj), int(length), int(term_kind),
+                                           int(penalty_mode), float(penalty_coef), None if eps_ptr is None else int(eps_ptr), int(lag),
+                                           C.byref(rows), C.byref(rs), returns.ctypes.data, C.byref(enq), C.byref(ms)), "orl_mbrcsl_rollout")
+        store.n_traj = int(n_traj)
+        return int(rows.value), float(rs.value), returns, int(enq.value), ms.value
+
     def learn_n(self, n_steps: int):
         m = np.zeros((self.n_runs, MAX_METRICS), dtype=np.float32)
         ms = C.c_float()
@@ -1080,6 +1099,21 @@ class TrajStore(_Handle):
         _check(self.lib.orl_traj_append_step(self._h, int(term_kind), obs.data_ptr(), act.data_ptr(), next_obs.data_ptr(), rew.data_ptr(), n,
                                              alive_next_obs.data_ptr(), C.byref(na)), "orl_traj_append_step")
         return int(na.value)
+
+    def append_step_counted(self, term_kind: int, obs, act, next_obs, rew, bound: int, alive_next_obs) -> None:
+        """``append_step`` with the rows counted on the device (orl_traj_append_step_counted): ``bound`` is any upper bound on the live
+        count, the tensors hold at least ``bound`` rows of which the first ``live`` are read, and nothing comes back -- ``live_count()``
+        or ``finish()`` refresh the host's counts."""
+        bound = int(bound)
+        _device_rows("append_step_counted", "the store's", self, (int(obs.shape[0]),), obs, act, next_obs, rew, alive_next_obs)
+        if min(int(obs.shape[0]), rew.numel()) < bound:
+            raise ValueError(f"append_step_counted: the sources need {bound} rows")
+        _check(self.lib.orl_traj_append_step_counted(self._h, int(term_kind), obs.data_ptr(), act.data_ptr(), next_obs.data_ptr(), rew.data_ptr(),
+                                                     bound, alive_next_obs.data_ptr()), "orl_traj_append_step_counted")
+
+    def live_count(self) -> int:
+        """the number of trajectories still running: a synchronising read of the device's count (for tests)"""
+        return int(self.live_index().shape[0])
 
     def live_index(self):
         """the indices of the trajectories still running, in row order: an int64 tensor on the store's device (orl_traj_live), written

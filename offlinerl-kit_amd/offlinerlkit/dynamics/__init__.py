@@ -250,6 +250,19 @@ class EnsembleDynamics(BaseDynamics):
             info["penalty"] = pen[r]
         return nxt[r], (rew[r] if self._penalty_coef else raw[r]), info
 
+    def loop_engine(self):
+        """What a device loop steps through (``RcslPolicy.rollout_device(fused=True)``): the engine after what ``step_device`` does
+        before every step -- bind, elites, scaler --, once.  -> (engine, penalty mode code, penalty coefficient)"""
+        self._bind(*(self._shape or (256, 0.01)))
+        self._sync_torch()
+        self._push_elites_from_model()
+        for r in range(self._n_runs):
+            sc = self.scalers[r]
+            if sc.mu is None:
+                raise RuntimeError("the scaler is not fitted: train() or load() the dynamics first")
+            self._eng.set_scaler(r, sc.mu, sc.std)
+        return self._eng, _engine.DYN_PENALTY[self._uncertainty_mode], float(self._penalty_coef)
+
     @torch.no_grad()
     def step_device_runs(self, obs: torch.Tensor, action: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, Dict]:
         """``step_device`` for R row blocks at once: obs (R, N, obs_dim), action (R, N, act_dim) -> (next_obs (R, N, obs_dim), reward

@@ -139,6 +139,12 @@ class AutoregressivePolicy(_EpochPolicy):
             return self._sample(o.unsqueeze(0).expand(R, -1, -1), eps_all)[r]
         return self._sample(o.unsqueeze(0), eps.unsqueeze(0))[0]
 
+    def loop_engine(self) -> "_engine.Engine":
+        """the engine a device loop samples through (``RcslPolicy.rollout_device(fused=True)``), bound like ``select_action_device`` binds it"""
+        if self._eng is None:
+            self._bind(256)
+        return self._eng
+
     def select_action_runs(self, obs: np.ndarray, rtg=None) -> np.ndarray:
         """Sampled actions of EVERY run in one call: ``obs`` [n_runs, E, obs_dim] -> [n_runs, E, act_dim]; the normals are one
         ``torch.randn((n_runs, E, act_dim))`` on the device's torch generator"""

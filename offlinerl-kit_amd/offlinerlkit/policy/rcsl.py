@@ -199,7 +199,8 @@ class _RcslBase(_EpochPolicy):
         rollout_transitions["rtgs"] = rtgs[..., None]
         return rollout_transitions, {"num_transitions": num_transitions, "reward_mean": rewards_arr.mean(), "returns": returns}
 
-    def rollout_device(self, init_obss, rollout_length: int, store: Optional["_engine.TrajStore"] = None) -> Tuple[DeviceRollout, Dict]:
+    def rollout_device(self, init_obss, rollout_length: int, store: Optional["_engine.TrajStore"] = None, fused: bool = False,
+                       lag: int = 2) -> Tuple[DeviceRollout, Dict]:
         """``rollout`` with every array on the device: actions from ``rollout_policy.select_action_device``, the model step from
         ``dynamics.step_device``, the bookkeeping in a ``TrajStore`` (termination test, rows, per-trajectory returns, the stable compaction
         of the survivors).  One host read per model step -- the survivor count, which sizes the next step --, then the returns and the
@@ -208,11 +209,23 @@ class _RcslBase(_EpochPolicy):
         ``sample_init_noise`` and ``select_action_device(obs, init_noise)`` (``DiffusionBC``) gets its per-trajectory noise [n_traj, 1,
         act_dim], drawn once, and every step the live trajectory indices (``store.live_index()``) as ``noise_index``: the policy's sampler
         gathers the rows.  ``store``: a ``TrajStore`` to reuse (reset here);
-        by default a new one of ``len(init_obss) * rollout_length`` rows.  -> (DeviceRollout, info with the keys of ``rollout``)"""
+        by default a new one of ``len(init_obss) * rollout_length`` rows.  -> (DeviceRollout, info with the keys of ``rollout``)
+
+        ``fused=True`` runs the whole rollout as one device loop (``orl_mbrcsl_rollout``): every launch of every model step is enqueued
+        on the policy engine's stream and the host never waits for the step it has just enqueued -- step t is sized by the survivor
+        count of step ``t - 1 - lag``, a valid upper bound because survivor counts never increase (``lag = 0``: exact sizes, one wait per
+        step).  The normals are ONE ``torch.randn((rollout_length, n_traj, act_dim))`` on the device, step t reading the first rows of
+        slice t, so ``torch.manual_seed`` still reproduces a rollout; that draw differs from the per-step ``randn((n, act_dim))`` of
+        ``rollout`` and of ``fused=False``, so the results are equal in distribution, not in bits.  The reward is ``raw - penalty_coef *
+        penalty`` also at ``penalty_coef = 0``.  ``info`` additionally carries ``steps_enqueued`` and ``loop_ms`` (the HIP-event time of
+        the loop).  Not implemented (``NotImplementedError``): a stateful dynamics, a frozen-noise policy, several runs on either side, a
+        policy that is not an ``AutoregressivePolicy``."""
         if self.dynamics is None or self.rollout_policy is None:
             raise NotImplementedError(f"{type(self).__name__}.rollout_device needs both a dynamics model and a rollout (behaviour) policy; "
                                       f"this policy was built with dynamics={self.dynamics!r}, rollout_policy={self.rollout_policy!r}")
         dyn, pol = self.dynamics, self.rollout_policy
+        if fused:
+            return self._rollout_fused(dyn, pol, init_obss, rollout_length, store, lag)
         kind = getattr(dyn, "term_kind", None)
         if kind is None or not hasattr(dyn, "step_device"):
             raise NotImplementedError("rollout_device: the dynamics' termination function is not one of the fixed row-wise tests of "
@@ -255,6 +268,44 @@ class _RcslBase(_EpochPolicy):
                 obs = alive[:n_alive]
         rows, rew_sum, returns = store.finish()
         return DeviceRollout(store, rows), {"num_transitions": rows, "reward_mean": rew_sum / rows, "returns": returns}
+
+    def _rollout_fused(self, dyn, pol, init_obss, rollout_length: int, store, lag: int) -> Tuple[DeviceRollout, Dict]:
+        """``rollout_device(fused=True)``"""
+        who = "rollout_device(fused=True)"
+        kind = getattr(dyn, "term_kind", None)
+        if kind is None:
+            raise NotImplementedError(f"{who}: the dynamics carries no term_kind (its termination function is not one of the fixed row-wise "
+                                      "tests of utils.termination_fns): the device loop cannot evaluate it; use rollout()")
+        if bool(getattr(dyn, "stateful", False)):
+            raise NotImplementedError(f"{who}: a stateful dynamics ({type(dyn).__name__} carries recurrent state per trajectory) is stepped "
+                                      "through the live trajectory indices, which the loop does not hand out; use fused=False")
+        if bool(getattr(pol, "device_frozen_noise", False)) or hasattr(pol, "sample_init_noise"):
+            raise NotImplementedError(f"{who}: a frozen-noise policy ({type(pol).__name__} has sample_init_noise) gathers its noise by "
+                                      "live trajectory index every step; use fused=False")
+        for name, obj in (("rollout policy", pol), ("dynamics", dyn)):
+            runs = int(getattr(obj, "n_runs", getattr(obj, "_n_runs", 1)))
+            if runs != 1:
+                raise NotImplementedError(f"{who}: the {name} has n_runs = {runs}; the loop rolls one run through one run")
+        if not hasattr(pol, "loop_engine") or not hasattr(dyn, "loop_engine"):
+            raise NotImplementedError(f"{who}: needs an AutoregressivePolicy and an EnsembleDynamics (the device loop drives their engines "
+                                      f"directly), got {type(pol).__name__} and {type(dyn).__name__}; use fused=False")
+        n_traj, L = int(len(init_obss)), int(rollout_length)
+        if n_traj < 1 or L < 1:
+            raise ValueError(f"rollout_device: {n_traj} initial states, rollout_length {L}")
+        if int(lag) < 0:
+            raise ValueError(f"rollout_device: lag {lag} must be >= 0")
+        peng = pol.loop_engine()
+        deng, mode, coef = dyn.loop_engine()
+        dev = torch.device("cuda", int(peng.cfg.device))
+        obs = init_obss if isinstance(init_obss, torch.Tensor) else torch.as_tensor(np.asarray(init_obss, dtype=np.float32))
+        obs = obs.to(device=dev, dtype=torch.float32).reshape(n_traj, -1).contiguous()
+        if store is None:
+            store = _engine.TrajStore(int(obs.shape[1]), int(pol.act_dim), n_traj, n_traj * L, dev.index or 0)
+        eps = torch.randn((L, n_traj, int(pol.act_dim)), device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        rows, rew_sum, returns, enq, ms = peng.mbrcsl_rollout(deng, store, obs.data_ptr(), n_traj, L, kind, mode, coef, eps.data_ptr(), int(lag))
+        return DeviceRollout(store, rows), {"num_transitions": rows, "reward_mean": rew_sum / rows, "returns": returns,
+                                            "steps_enqueued": enq, "loop_ms": ms}
 
     def learn(self, batch: Dict) -> Dict[str, float]:
         """One gradient step on ``{"observations", "actions", "rtgs"}``: [B, ...] arrays shared by every run or [n_runs, B, ...]."""
@@ -336,11 +387,11 @@ class RcslGaussianPolicy(_RcslBase):
 
 
 def collect_rollouts_device(policy, init_obss_dataset, rollout_batch: int, horizon: int, threshold: float, num_need_traj: int, max_epochs: int,
-                            capacity_rows: int, rng=np.random):
+                            capacity_rows: int, rng=np.random, fused: bool = False):
     """The collection loop of run_mbrcsl.py (``get_rollout_trajs``) on the device: per epoch ``rollout_batch`` initial states drawn with
     ``rng.randint`` from ``init_obss_dataset`` [M, obs_dim], one ``policy.rollout_device`` of up to ``horizon`` steps, and the export of
     the trajectories with ``returns > threshold`` into ONE ring of ``capacity_rows`` rows; until ``num_need_traj`` trajectories have been
-    kept or ``max_epochs`` epochs have run.  -> (the ring: a ``DeviceBuffer`` with returns-to-go in its reward column, ready for
+    kept or ``max_epochs`` epochs have run.  ``fused``: passed to ``rollout_device``.  -> (the ring: a ``DeviceBuffer`` with returns-to-go in its reward column, ready for
     ``learn_epoch``; info: num_traj, returns (of the kept trajectories, float64), max_return (their maximum, -inf when none was
     kept), epochs)"""
     if int(max_epochs) < 1 or int(rollout_batch) < 1 or int(num_need_traj) < 1:
@@ -352,7 +403,7 @@ def collect_rollouts_device(policy, init_obss_dataset, rollout_batch: int, horiz
     kept, num_traj, epochs = [], 0, 0
     while num_traj < int(num_need_traj) and epochs < int(max_epochs):
         idx = rng.randint(len(init), size=int(rollout_batch))
-        roll, info = policy.rollout_device(init[idx], horizon, store=store)
+        roll, info = policy.rollout_device(init[idx], horizon, store=store, **({"fused": True} if fused else {}))
         if store is None:                      # (the first rollout made the store; every later one reuses it)
             store = roll.store
             ring = _engine.DeviceBuffer(store.obs_dim, store.act_dim, store.device)

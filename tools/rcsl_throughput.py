@@ -19,7 +19,10 @@ every model step) against ``RcslPolicy.rollout_device`` (``TrajStore``: orl_traj
 function that never fires so the length is fixed, freshly initialised nets (the work per step does not depend on the weights).  A warm-up
 rollout of each, then ``--blocks`` timed rollouts of each, alternating; the figure is transitions per second.  Then, once, the wall time
 of the device path's pieces over one more rollout (action sampling, dynamics step, store append; each ends in a host synchronisation).
-Writes profiles/rcsl_rollout_throughput.json unless --out names another file.
+A third contestant runs in the same alternation: ``rollout_device(fused=True)`` (orl_mbrcsl_rollout: every launch of every step on one
+stream, step t sized by the survivor count of step t - 1 - lag) at the default ``lag`` = 2, with the HIP-event time of its loop next to
+the wall time of the call; then one rollout each at ``lag`` 0, 1, 2 and 4.
+Writes profiles/rcsl_rollout_fused_throughput.json unless --out names another file.
 ``--diffusion``: ``DiffusionBC`` at the default shape on hopper (ConditionalUnet1D [256, 512, 1024], embedding 256, N = 10, batch 256), three
 figures from one run: (1) one training epoch over ``--rows`` rows (orl_diffusion_learn_epoch) against autograd + torch.optim.Adam on the
 project's own ``ConditionalUnet1D`` on the same GPU (steps per second); (2) ``select_action`` on 256 rows (orl_diffusion_sample: 10
@@ -193,10 +196,22 @@ def measure_rollout(n_traj, horizon, blocks):
         _, info = pol.rollout_device(init, horizon, store=store)
         torch.cuda.synchronize()
         return info["num_transitions"] / (time.perf_counter() - t0)
-    host(); device()                                   # warm-up: engine binding, allocator
-    h, d = [], []
+
+    def fused(lag=2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, info = pol.rollout_device(init, horizon, store=store, fused=True, lag=lag)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        return info["num_transitions"] / wall, dict(lag=lag, transitions_per_s=info["num_transitions"] / wall, wall_ms=1e3 * wall,
+                                                    loop_event_ms=float(info["loop_ms"]), steps_enqueued=int(info["steps_enqueued"]))
+    host(); device(); fused()                          # warm-up: engine binding, allocator
+    h, d, f, f_info = [], [], [], []
     for _ in range(blocks):
         h.append(host()); d.append(device())
+        rate, info = fused()
+        f.append(rate); f_info.append(info)
+    per_lag = [fused(lag)[1] for lag in (0, 1, 2, 4)]
     # where the device path's time goes: the same loop with a clock around each piece (every piece ends in a host synchronisation)
     parts = dict(select_action_device=0.0, step_device=0.0, append_step=0.0)
     obs = torch.as_tensor(init, device=DEV)
@@ -220,6 +235,8 @@ def measure_rollout(n_traj, horizon, blocks):
     rows, rew_sum, _ = store.finish()
     return dict(trajectories=n_traj, horizon=horizon, transitions=rows, host_transitions_per_s=h, device_transitions_per_s=d,
                 host_median=float(np.median(h)), device_median=float(np.median(d)), speedup=float(np.median(d) / np.median(h)),
+                fused_transitions_per_s=f, fused_median=float(np.median(f)), fused_over_device=float(np.median(f) / np.median(d)),
+                fused_ranges_disjoint=bool(min(f) > max(d)), fused_rollouts=f_info, fused_per_lag=per_lag,
                 device_ms_per_step={k: 1e3 * v / horizon for k, v in parts.items()}, device_ms_per_step_total=1e3 * total / horizon,
                 rewards_finite=bool(np.isfinite(rew_sum)))
 
@@ -366,11 +383,11 @@ def main():
             json.dump(res, f, indent=1)
         return
     if a.rollout:
-        res = dict(stage="RcslPolicy.rollout vs rollout_device", shape=dict(obs_dim=OD, act_dim=AD, dynamics_hidden=HID, ensemble=7, elites=5,
+        res = dict(stage="RcslPolicy.rollout vs rollout_device vs rollout_device(fused=True)", shape=dict(obs_dim=OD, act_dim=AD, dynamics_hidden=HID, ensemble=7, elites=5,
                                                                           behaviour_hidden=HID, termination="none"),
                    device=torch.cuda.get_device_name(0), result=measure_rollout(a.trajectories, a.horizon, a.blocks))
         print(json.dumps(res))
-        with open(a.out or os.path.join(ROOT, "profiles", "rcsl_rollout_throughput.json"), "w") as f:
+        with open(a.out or os.path.join(ROOT, "profiles", "rcsl_rollout_fused_throughput.json"), "w") as f:
             json.dump(res, f, indent=1)
         return
     ds = dataset(a.rows)
