@@ -38,10 +38,11 @@ UNITS = {
     "ws_dgrad3.hip": WS_H,
     "ws_wgrad3p.hip": WS_H,
     "ws_wgrad.hip": WS_H,
-    "ws_debug.hip": ["gemm.h", "ws_gemm.h", ABI],
+    "ws_debug.hip": ["debug_tap.h", "gemm.h", "ws_gemm.h", ABI],
     "small_fwd.hip": ["small_fwd.h", "sample.h", "gemm.h"],
     "small_bwd.hip": ["small_bwd.h", "small_fwd.h", "sample.h", "scalars.h", "gemm.h"],
-    "small_debug.hip": ["small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "gemm.h", ABI],
+    "small_debug.hip": ["debug_tap.h", "small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "gemm.h", ABI],
+    "gemm_debug.hip": ["debug_tap.h", "devobj.h", "gemm.h", ABI],
 }
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 

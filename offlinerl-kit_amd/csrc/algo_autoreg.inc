@@ -3,6 +3,7 @@
 // k_autoreg_prepare (B rows -> M = A * B expanded rows, targets, row indices), the forward on the tiled GEMM's E_BIAS_LEAKY flavour down to
 // the plain-linear tail, k_autoreg_head (the output LeakyReLU, masked Gaussian NLL, dz_tail, metric, split-precision scale), the generic
 // backward with E_LEAKY_MASK, one Adam step.  orl_autoreg_sample: A forward-only passes over n rows with k_autoreg_draw between them.
+// mbrcsl_loop (the body of orl_mbrcsl_rollout): sampling, the model step and the trajectory store's append as one device loop.
 namespace orl {
 
 int Engine::autoreg_build() {
@@ -13,7 +14,6 @@ int Engine::autoreg_build() {
   alloc("ar_z", M, 2); alloc("ar_dz", M, 2); alloc("ar_out", M, 2); alloc("ar_target", M, 1);
   ar_calls = (unsigned long long*)raw_alloc(sizeof(unsigned long long));
   if (!ar_calls) return fail("hipMalloc sample counter");
-  if (hipMemset(ar_calls, 0, sizeof(unsigned long long)) != hipSuccess) return fail("hipMemset sample counter");
   taps["ar_x"] = {W("ar_x"), M, od + 2 * A};
   taps["ar_z"] = {W("ar_z"), M, 2};                 // k_autoreg_head's operand (tail pre-activation) and its seed
   taps["ar_dz"] = {W("ar_dz"), M, 2};
@@ -45,30 +45,14 @@ int Engine::autoreg_step() {
 
 // workspaces of orl_autoreg_sample for n rows per run; regrown (never shrunk) when n grows
 int Engine::autoreg_sample_room(long n) {
-  if (n <= ar_cap) return 0;
-  auto drop = [&](Mat& m) {
-    if (!m.p) return;
-    range_watch.erase(m.p);
-    allocs.erase(std::remove(allocs.begin(), allocs.end(), (void*)m.p), allocs.end());
-    hipFree(m.p);
-    m = Mat();
-  };
-  auto make = [&](Mat& m, int pitch) {
-    m = Mat();
-    m.p = raw_alloc(sizeof(float) * (size_t)n * pitch * R);
-    m.pitch = pitch;
-    return m.p != nullptr;
-  };
-  ORL_HIP(hipStreamSynchronize(stream));
-  drop(ar_sx); drop(ar_sz); drop(ar_seps); drop(ar_sobs);
-  for (auto& m : ar_sh) drop(m);
-  ar_sh.assign(L, Mat());
-  ar_cap = 0;
-  bool ok = make(ar_sx, rup(od + 2 * ad, 4)) && make(ar_sz, 2) && make(ar_seps, ad) && make(ar_sobs, od);
-  for (int i = 0; i < L && ok; ++i) ok = make(ar_sh[i], cfg.hidden[i]);
-  if (!ok) return fail("orl_autoreg_sample: hipMalloc workspaces");
-  ar_cap = n;
-  return 0;
+  RowScratch& s = ar_ws;
+  if (s.mats.empty()) {
+    s.what = "orl_autoreg_sample: hipMalloc workspaces";
+    ar_sh.assign(L, Mat());
+    s.add(ar_sx, rup(od + 2 * ad, 4)); s.add(ar_sz, 2); s.add(ar_seps, ad); s.add(ar_sobs, od);
+    for (int i = 0; i < L; ++i) s.add(ar_sh[i], cfg.hidden[i]);
+  }
+  return room(s, n);
 }
 
 int Engine::autoreg_sample(const float* obs, long n, const float* eps, bool on_device, float* act_out) {
@@ -89,8 +73,76 @@ int Engine::autoreg_sample(const float* obs, long n, const float* eps, bool on_d
 // The MBRCSL rollout loop's form: the launches of a call on device rows, nothing staged and no synchronisation.  The workspaces hold
 // the rows already (autoreg_sample_room, once, for the most rows of the loop); the kernels read `eps` ([n][act_dim] normals) where it lies.
 int Engine::autoreg_sample_enqueue(const float* obs, long n, const float* eps, float* act_out) {
-  if (n > ar_cap) return fail("autoreg_sample_enqueue: more rows than autoreg_sample_room made room for");
+  if (n > ar_ws.cap) return fail("autoreg_sample_enqueue: more rows than autoreg_sample_room made room for");
   return autoreg_sample_launches(obs, n, eps, act_out, hipMemcpyDeviceToDevice);
+}
+
+// row buffers, count slots and events of the MBRCSL rollout loop; the row buffers are zero-filled, so a row no step has written holds zeros
+int Engine::mbrcsl_room(long n_traj, long length, long events) {
+  RowScratch& s = ml_ws;
+  if (s.mats.empty()) {
+    s.what = "orl_mbrcsl_rollout: hipMalloc row buffers";
+    s.add(ml_obs[0], od); s.add(ml_obs[1], od); s.add(ml_act, ad); s.add(ml_next, od); s.add(ml_rew, 1);
+  }
+  if (room(s, n_traj)) return -1;
+  if (length > ml_counts_cap) {
+    ORL_HIP(hipStreamSynchronize(stream));
+    if (ml_counts) hipHostFree(ml_counts);
+    ml_counts = nullptr; ml_counts_cap = 0;
+    ORL_HIP(hipHostMalloc((void**)&ml_counts, sizeof(long long) * length, hipHostMallocDefault));
+    ml_counts_cap = length;
+  }
+  while ((long)ml_events.size() < events) {
+    hipEvent_t ev;
+    ORL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    ml_events.push_back(ev);
+  }
+  return 0;
+}
+
+// The rollout without a host read per model step (orl_mbrcsl_rollout has refused what it refuses): every launch of the policy, the
+// dynamics and the trajectory store on the engine's stream; the host reads survivor counts `lag` steps behind what it enqueues
+int Engine::mbrcsl_loop(orl_dynamics* d, const DynStepInfo& di, orl_traj* store, const TrajInfo& ti, const float* init_obs, int n_traj, int length,
+                        int term_kind, int penalty_mode, float penalty_coef, const float* eps, int lag, int64_t* rows, double* reward_sum,
+                        double* returns_host, int32_t* steps_enqueued, float* elapsed_ms) {
+  const char* F = "orl_mbrcsl_rollout";
+  const long n_ev = std::min<long>((long)lag + 1, length);
+  if (autoreg_sample_room(n_traj) || mbrcsl_room(n_traj, length, n_ev)) return -1;
+  if (orl_traj_reset(store, n_traj)) return -1;
+  if (dynstep_loop_begin(d, n_traj)) return -1;
+  // the store's reset (null stream) and whatever the dynamics' own stream still holds come first; from here to the end every launch of
+  // the three objects is on the engine's stream
+  LoopScope loop;
+  if (loop_begin(loop, {nullptr, di.stream})) return -1;
+  DynStreamLease lease(d, stream);
+  int enq = 0, cur = 0;
+  const auto body = [&]() -> int {
+    ORL_HIP(hipMemcpyAsync(ml_obs[0].p, init_obs, sizeof(float) * (size_t)n_traj * od, hipMemcpyDeviceToDevice, stream));
+    long bound = n_traj;
+    for (int t = 0; t < length; ++t) {
+      // the newest survivor count the host may wait for without stalling on a step it has just enqueued: counts never increase, so it
+      // bounds the live rows of step t
+      const int k = t - 1 - lag;
+      if (k >= 0) {
+        ORL_HIP(hipEventSynchronize(ml_events[k % n_ev]));
+        bound = (long)ml_counts[k];
+      }
+      if (bound == 0) break;
+      float *obs = ml_obs[cur].p, *nxt = ml_obs[cur ^ 1].p;
+      if (autoreg_sample_enqueue(obs, bound, eps ? eps + (size_t)t * n_traj * ad : nullptr, ml_act.p)) return -1;
+      if (dynstep_enqueue(d, obs, ml_act.p, bound, penalty_mode, penalty_coef, ml_next.p, ml_rew.p)) return -1;
+      if (traj_append_enqueue(store, stream, term_kind, obs, ml_act.p, ml_next.p, ml_rew.p, bound, nxt, F)) return -1;
+      ORL_HIP(hipMemcpyAsync(ml_counts + t, ti.survivors, sizeof(long long), hipMemcpyDeviceToHost, stream));
+      ORL_HIP(hipEventRecord(ml_events[t % n_ev], stream));
+      ++enq;
+      cur ^= 1;
+    }
+    return 0;
+  };
+  const int rc = loop.end(body(), F, elapsed_ms);      // the one unconditional host synchronisation (also on an error path)
+  if (steps_enqueued) *steps_enqueued = enq;
+  if (rc) return -1;
+  return orl_traj_finish(store, rows, reward_sum, returns_host);
 }
 
 // what both forms launch: obs / eps are DEVICE arrays of n rows per run (eps null: drawn into the workspace), act_out by `out_kind`

@@ -1,5 +1,5 @@
 // algo_rambo.inc — RAMBO's advantage on a SAC engine (policy/model_based/rambo.py:164-181) and the engine's share of the device loop of
-// update_dynamics (rambo.py:95-127; orl_rambo_update_dynamics in engine.hip strings it together with the dynamics' adversarial pair).
+// update_dynamics (rambo.py:95-127; rambo_loop, the body of orl_rambo_update_dynamics, strings it together with the dynamics' adversarial pair).
 // Forward-only passes on workspaces of their own: no parameter, optimizer state, step counter or noise stream of orl_learn_n is touched.
 //   advantage   k_adv_assemble ([s | a] and [s' | .] as ONE 2 Ba-row critic operand, s' as the actor's input), the actor pass with the
 //               deterministic sampling job (a' = tanh(mu(s')) into the operand, logp' at the mode), ONE pass of both live critics over the
@@ -11,41 +11,20 @@ namespace orl {
 // the first `rows` rows of every run of a matrix allocated for more: runs packed at the front
 static Mat adv_view(Mat m, long rows, int nets = 1) { m.cs = rows * m.pitch; m.rs = m.cs * nets; return m; }
 
-static void adv_drop(Engine* e, Mat& m) {
-  if (!m.p) return;
-  e->range_watch.erase(m.p);
-  e->vals_dead.erase(m.p);
-  e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), (void*)m.p), e->allocs.end());
-  hipFree(m.p);
-  m = Mat();
-}
-static bool adv_make(Engine* e, Mat& m, long rows, int pitch, int nets = 1) {
-  m = Mat();
-  m.p = e->raw_alloc(sizeof(float) * (size_t)rows * pitch * nets * e->R);
-  m.pitch = pitch;
-  return m.p != nullptr;
-}
-
 // workspaces of orl_engine_adv_advantage for Ba rows per run; regrown (never shrunk) when Ba grows
 int Engine::adv_room(long Ba) {
-  if (Ba <= adv_cap) return 0;
-  ORL_HIP(hipStreamSynchronize(stream));
-  for (Mat* m : {&adv_xs, &adv_xc, &adv_head, &adv_logp, &adv_q}) adv_drop(this, *m);
-  for (Mat& m : adv_v) adv_drop(this, m);
-  for (Mat& m : adv_in) adv_drop(this, m);
-  for (Mat& m : adv_ah) adv_drop(this, m);
-  for (Mat& m : adv_ch) adv_drop(this, m);
-  for (const char* t : {"adv.term", "adv.q_next", "adv.q_base", "adv.raw", "adv.norm", "adv.logp_next"}) taps.erase(t);
-  adv_ah.assign(L, Mat()); adv_ch.assign(L, Mat());
-  adv_cap = 0;
-  bool ok = adv_make(this, adv_xs, Ba, OP) && adv_make(this, adv_xc, 2 * Ba, XP) && adv_make(this, adv_head, Ba, 2 * ad) &&
-            adv_make(this, adv_logp, Ba, 1) && adv_make(this, adv_q, 2 * Ba, 1, 2) && adv_make(this, adv_in[0], Ba, od) &&
-            adv_make(this, adv_in[1], Ba, ad) && adv_make(this, adv_in[2], Ba, od) && adv_make(this, adv_in[3], Ba, 1);
-  for (Mat& m : adv_v) ok = ok && adv_make(this, m, Ba, 1);
-  for (int i = 0; i < L && ok; ++i) ok = adv_make(this, adv_ah[i], Ba, cfg.hidden[i]) && adv_make(this, adv_ch[i], 2 * Ba, cfg.hidden[i], 2);
-  if (ok && !adv_stats) ok = (adv_stats = raw_alloc(sizeof(float) * 2 * R)) != nullptr;
-  if (!ok) return fail("orl_engine_adv_advantage: hipMalloc workspaces");
-  adv_cap = Ba;
+  RowScratch& s = adv_ws;
+  if (s.mats.empty()) {
+    s.what = "orl_engine_adv_advantage: hipMalloc workspaces";
+    s.taps = {"adv.term", "adv.q_next", "adv.q_base", "adv.raw", "adv.norm", "adv.logp_next"};
+    adv_ah.assign(L, Mat()); adv_ch.assign(L, Mat());
+    s.add(adv_xs, OP); s.add(adv_xc, XP, 2); s.add(adv_head, 2 * ad); s.add(adv_logp, 1); s.add(adv_q, 1, 2, 2);
+    s.add(adv_in[0], od); s.add(adv_in[1], ad); s.add(adv_in[2], od); s.add(adv_in[3], 1);
+    for (Mat& m : adv_v) s.add(m, 1);
+    for (int i = 0; i < L; ++i) { s.add(adv_ah[i], cfg.hidden[i]); s.add(adv_ch[i], cfg.hidden[i], 2, 2); }
+  }
+  if (room(s, Ba)) return -1;
+  if (!adv_stats && !(adv_stats = raw_alloc(sizeof(float) * 2 * R))) return fail(s.what);
   return 0;
 }
 
@@ -94,22 +73,69 @@ int Engine::adv_advantage(const float* obs, const float* act, const float* nobs,
 
 // row buffers of the device loop for `rows` rows (one run)
 int Engine::rambo_room(long rows) {
-  if (rows <= rambo_cap) return 0;
-  ORL_HIP(hipStreamSynchronize(stream));
-  for (Mat* m : {&rb_obs[0], &rb_obs[1], &rb_act, &rb_eps, &rb_rew, &rb_adv}) adv_drop(this, *m);
-  for (Mat& m : rb_sl) adv_drop(this, m);
-  for (const char* t : {"loop.obs", "loop.act", "loop.sl_obs", "loop.sl_act", "loop.sl_next_obs", "loop.sl_rew", "loop.next_obs", "loop.reward"})
-    taps.erase(t);
-  rambo_cap = 0;
-  bool ok = adv_make(this, rb_obs[0], rows, od) && adv_make(this, rb_obs[1], rows, od) && adv_make(this, rb_act, rows, ad) &&
-            adv_make(this, rb_eps, rows, ad) && adv_make(this, rb_rew, rows, 1) && adv_make(this, rb_adv, rows, 1) &&
-            adv_make(this, rb_sl[0], rows, od) && adv_make(this, rb_sl[1], rows, ad) && adv_make(this, rb_sl[2], rows, od) &&
-            adv_make(this, rb_sl[3], rows, 1) && adv_make(this, rb_sl[4], rows, 1);
-  if (ok && !rb_acc) ok = (rb_acc = raw_alloc(sizeof(float) * 8)) != nullptr;
-  if (ok && !rb_calls) ok = (rb_calls = (unsigned long long*)raw_alloc(sizeof(unsigned long long))) != nullptr;
-  if (!ok) return fail("orl_rambo_update_dynamics: hipMalloc row buffers");
-  rambo_cap = rows;
+  RowScratch& s = rambo_ws;
+  if (s.mats.empty()) {
+    s.what = "orl_rambo_update_dynamics: hipMalloc row buffers";
+    s.taps = {"loop.obs", "loop.act", "loop.sl_obs", "loop.sl_act", "loop.sl_next_obs", "loop.sl_rew", "loop.next_obs", "loop.reward"};
+    s.add(rb_obs[0], od); s.add(rb_obs[1], od); s.add(rb_act, ad); s.add(rb_eps, ad); s.add(rb_rew, 1); s.add(rb_adv, 1);
+    s.add(rb_sl[0], od); s.add(rb_sl[1], ad); s.add(rb_sl[2], od); s.add(rb_sl[3], 1); s.add(rb_sl[4], 1);
+  }
+  if (room(s, rows)) return -1;
+  if (!rb_acc && !(rb_acc = raw_alloc(sizeof(float) * 8))) return fail(s.what);
+  if (!rb_calls && !(rb_calls = (unsigned long long*)raw_alloc(sizeof(unsigned long long)))) return fail(s.what);
   return 0;
+}
+
+// update_dynamics without coming back to the host (orl_rambo_update_dynamics has refused what it refuses): every launch of the engine and
+// of the dynamics' adversarial pair on the engine's stream, one synchronisation at the end
+int Engine::rambo_loop(orl_dynamics* d, const DynAdvInfo& di, Buffer& b, const orl_rambo_loop* a, float* metrics_mean, float* elapsed_ms) {
+  const char* F = "orl_rambo_update_dynamics";
+  const int rows = a->rows;
+  if (adv_room(rows) || rambo_room(rows)) return -1;
+  if (dynadv_loop_begin(d)) return -1;
+  // whatever the dynamics' own stream still holds comes first; from here to the end every launch of both objects is on the engine's stream
+  LoopScope loop;
+  if (loop_begin(loop, {di.stream})) return -1;
+  DynStreamLease lease(d, stream);
+  long done = 0;
+  int cur = 0;
+  const auto body = [&]() -> int {
+    ORL_HIP(hipMemsetAsync(rb_acc, 0, sizeof(float) * 8, stream));
+    for (int s = 0; s < a->n_segments; ++s) {
+      // the segment's initial observations: one draw, of which the observation rows are kept
+      if (buffer_gather(b, nullptr, rows, cfg.seed, rb_obs[cur].p, rb_sl[1].p, rb_sl[2].p, rb_sl[3].p, rb_sl[4].p, stream)) return -1;
+      for (int k = 0; k < a->segment_steps[s]; ++k) {
+        float* obs = rb_obs[cur].p;
+        float* nxt = rb_obs[cur ^ 1].p;
+        if (adv_act(obs, rows, rb_act.p)) return -1;
+        if (buffer_gather(b, nullptr, rows, cfg.seed, rb_sl[0].p, rb_sl[1].p, rb_sl[2].p, rb_sl[3].p, rb_sl[4].p, stream)) return -1;
+        if (dynadv_forward_enqueue(d, obs, rb_act.p, rb_sl[0].p, rb_sl[1].p, rb_sl[2].p, rb_sl[3].p, nxt, rb_rew.p)) return -1;
+        if (adv_advantage(obs, rb_act.p, nxt, rb_rew.p, rows, a->term_kind, a->include_ent != 0, rb_adv.p)) return -1;
+        if (dynadv_update_enqueue(d, rb_adv.p, (int)done)) return -1;
+        hipLaunchKernelGGL(k_rambo_accum, dim3(1), dim3(1), 0, stream, rb_acc, di.metrics, (const float*)adv_stats);
+        if (hipGetLastError() != hipSuccess) return fail(std::string(F) + ": accumulate launch failed");
+        ++done;
+        cur ^= 1;
+      }
+    }
+    return 0;
+  };
+  const int rc = loop.end(body(), F, elapsed_ms);      // the one host synchronisation (also on an error path: the launches made so far ran)
+  dynadv_loop_end(d, done);
+  if (rc) return -1;
+  // the last step's rows: cur now names the buffer its next_obs went to
+  const auto tap = [&](const char* name, const Mat& m, int cols) { Mat v = m; v.rs = (long)rows * cols; taps[name] = {v, rows, cols}; };
+  tap("loop.obs", rb_obs[cur ^ 1], od); tap("loop.next_obs", rb_obs[cur], od); tap("loop.act", rb_act, ad);
+  tap("loop.sl_obs", rb_sl[0], od); tap("loop.sl_act", rb_sl[1], ad); tap("loop.sl_next_obs", rb_sl[2], od);
+  tap("loop.sl_rew", rb_sl[3], 1); tap("loop.reward", rb_rew, 1);
+  float acc[5];
+  ORL_HIP(hipMemcpy(acc, rb_acc, sizeof(acc), hipMemcpyDeviceToHost));
+  bool finite = true;
+  for (int k = 0; k < 5; ++k) { finite = finite && std::isfinite(acc[k]); metrics_mean[k] = acc[k] / (float)done; }
+  if (!finite) health_host[0] |= ORL_HEALTH_NONFINITE_LOSS;
+  unsigned int bad = 0;
+  if (health_update(nullptr, 0, &bad)) return -1;
+  return bad ? ORL_RC_UNHEALTHY : 0;
 }
 
 // MOPOPolicy.select_action on device rows: a = tanh(mu + sigma eps), eps from Philox keyed by (seed, the loop's own call counter, run,

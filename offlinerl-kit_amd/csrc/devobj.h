@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -20,10 +21,19 @@ int fail(const std::string& msg);         // set_error, returns -1
 // store.hip: the dataset rows a DiffusionBC gathers (device, dims, pitches, size, the obs / act arrays)
 void buffer_view(const orl_buffer* b, int* dev, int* od, int* ad, int* OP, int* AP, long* n, const float** obs, const float** act);
 
-// The adversarial pair of an orl_dynamics (dynamics.hip) as the RAMBO device loop of engine.hip drives it: the launches of
-// orl_dynadv_forward / orl_dynadv_update on device arrays, without their staging, synchronisation and metric read-back.  Between
-// loop_begin and loop_end the object's launches go to `loop_stream` (the engine's: one stream orders the whole loop); begin uploads
-// the optimizer's step counts, update_enqueue(step) is Adam step t0 + step + 1, end adds the steps done to the host's count.
+// While a lease lives, the launches of an orl_dynamics (dynamics.hip) go to `loop_stream` -- the engine's, so that one stream orders a
+// whole device loop; the destructor hands the object's own stream back on every return path.
+struct DynStreamLease {
+  orl_dynamics* d;
+  hipStream_t own;
+  DynStreamLease(orl_dynamics* d, hipStream_t loop_stream);
+  ~DynStreamLease();
+};
+
+// The adversarial pair of an orl_dynamics (dynamics.hip) as the RAMBO device loop drives it under a DynStreamLease (algo_rambo.inc:
+// Engine::rambo_loop): the launches of orl_dynadv_forward / orl_dynadv_update on device arrays, without their staging, synchronisation
+// and metric read-back.  loop_begin (before the lease) uploads the optimizer's step counts, update_enqueue(step) is Adam step
+// t0 + step + 1, loop_end adds the steps done to the host's count.
 struct DynAdvInfo {
   int dev, R, od, ad, Ba, Bs;
   bool on;                 // orl_dynadv_configure has run
@@ -31,28 +41,27 @@ struct DynAdvInfo {
   const float* metrics;    // device [R][4] of the last update: all_loss, sl_loss, adv_loss, mean log_prob
 };
 int dynadv_info(orl_dynamics* d, DynAdvInfo* out);
-int dynadv_loop_begin(orl_dynamics* d, hipStream_t loop_stream, hipStream_t* own);
+int dynadv_loop_begin(orl_dynamics* d);
 int dynadv_forward_enqueue(orl_dynamics* d, const float* obs, const float* act, const float* sl_obs, const float* sl_act,
                            const float* sl_next_obs, const float* sl_rew, float* next_obs, float* reward);
 int dynadv_update_enqueue(orl_dynamics* d, const float* advantage, int step);
-void dynadv_loop_end(orl_dynamics* d, hipStream_t own, long steps_done);
+void dynadv_loop_end(orl_dynamics* d, long steps_done);
 
-// The trajectory store (store.hip) as the MBRCSL rollout loop of engine.hip drives it: orl_traj_append_step_counted's two launches on
-// `stream` (`who` prefixes the refusals), and what the loop checks and reads of the store -- `survivors` is the device cell that holds
-// the survivor count of the last step enqueued.
+// The trajectory store (store.hip) as the MBRCSL rollout loop drives it (algo_autoreg.inc: Engine::mbrcsl_loop):
+// orl_traj_append_step_counted's two launches on `stream` (`who` prefixes the refusals), and what the loop checks and reads of the store
+// -- `survivors` is the device cell that holds the survivor count of the last step enqueued.
 struct TrajInfo { int dev, od, ad; long n_traj_cap, cap; const long long* survivors; };
 int traj_info(orl_traj* t, TrajInfo* out);
 int traj_append_enqueue(orl_traj* t, hipStream_t stream, int term_kind, const float* obs, const float* act, const float* next_obs,
                         const float* rew, long bound, float* alive_next_obs, const char* who);
 
-// orl_dyn_step (dynamics.hip) as the same loop drives it: device rows in, next_obs / reward out, no staging and no synchronisation.
-// Between loop_begin and loop_end the object's launches go to `loop_stream`; begin grows the step workspaces for n_max rows, every
+// orl_dyn_step (dynamics.hip) as the same loop drives it under a DynStreamLease: device rows in, next_obs / reward out, no staging and
+// no synchronisation.  loop_begin (before the lease, on the object's own stream) grows the step workspaces for n_max rows, every
 // enqueue advances the call counter as orl_dyn_step does.
 struct DynStepInfo { int dev, R, od, ad; bool with_reward; hipStream_t stream; };
 int dynstep_info(orl_dynamics* d, DynStepInfo* out);
-int dynstep_loop_begin(orl_dynamics* d, hipStream_t loop_stream, long n_max, hipStream_t* own);
+int dynstep_loop_begin(orl_dynamics* d, long n_max);
 int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n, int mode, float coef, float* next_obs, float* reward);
-void dynstep_loop_end(orl_dynamics* d, hipStream_t own);
 
 #define ORL_HIP(expr)                                                                            \
   do {                                                                                           \
@@ -70,6 +79,38 @@ void dynstep_loop_end(orl_dynamics* d, hipStream_t own);
   } while (0)
 
 static inline int rup4(int x) { return (x + 3) & ~3; }
+
+// The frame of a device loop: a run of launches on one stream between two timing events, with one host synchronisation at its end.
+// begin: `stream` waits for what each of `wait_for` holds so far, then the start event is recorded.  end(rc of the launches, ...):
+// records the stop event, synchronises once -- also when the launches failed: those made so far ran -- and returns -1 for rc != 0 or,
+// with "<who>: <hip error>", for a failed synchronisation; on success *elapsed_ms (may be null) is the time between the two events.
+struct LoopScope {
+  hipStream_t stream = nullptr;
+  hipEvent_t a = nullptr, b = nullptr, order = nullptr;
+  ~LoopScope() { for (hipEvent_t x : {a, b, order}) if (x) hipEventDestroy(x); }
+  int begin(hipStream_t s, std::initializer_list<hipStream_t> wait_for) {
+    stream = s;
+    ORL_HIP(hipEventCreate(&a));
+    ORL_HIP(hipEventCreate(&b));
+    if (wait_for.size()) ORL_HIP(hipEventCreateWithFlags(&order, hipEventDisableTiming));
+    for (hipStream_t w : wait_for) {
+      ORL_HIP(hipEventRecord(order, w));
+      ORL_HIP(hipStreamWaitEvent(stream, order, 0));
+    }
+    ORL_HIP(hipEventRecord(a, stream));
+    return 0;
+  }
+  int end(int rc, const char* who, float* elapsed_ms) {
+    const hipError_t re = rc ? hipSuccess : hipEventRecord(b, stream);
+    const hipError_t se = hipStreamSynchronize(stream);
+    if (rc) return -1;
+    if (re != hipSuccess || se != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(re != hipSuccess ? re : se));
+    float ms = 0.f;
+    ORL_HIP(hipEventElapsedTime(&ms, a, b));
+    if (elapsed_ms) *elapsed_ms = ms;
+    return 0;
+  }
+};
 
 // Device allocations of one object.  alloc: zero-filled, an empty request gets 16 bytes; `who` prefixes the error texts.
 struct DevAllocs {

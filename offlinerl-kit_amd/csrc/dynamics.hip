@@ -400,7 +400,7 @@ __global__ __launch_bounds__(256) void k_dyn_sample_next(DynSampleNextP p) {
 //   update    k_dyn_adv_head (mixture log-prob + policy-gradient term on the rollout rows, the Gaussian NLL on the dataset rows),
 //             k_dyn_adv_reduce, ONE backward over the Ba + Bs rows, k_dyn_adam on the adversarial optimizer's state, k_dyn_adv_metrics
 // The launches of either call are one host function each (dynadv_forward_launches / dynadv_update_launches): the public entries add
-// staging, the synchronise and the metric read-back, the RAMBO device loop of engine.hip (orl::dynadv_*_enqueue, devobj.h) adds nothing
+// staging, the synchronise and the metric read-back, the RAMBO device loop of the engine (orl::dynadv_*_enqueue, devobj.h) adds nothing
 
 // rows [0, Ba): scaler(concat(obs, act)), obs kept for the head; rows [Ba, Ba + Bs): scaler(concat(sl_obs, sl_act)) and the target
 // T[r][j] = [sl_next_obs - sl_obs, sl_rew]
@@ -1493,8 +1493,11 @@ int orl_dynadv_adam_set(orl_dynamics* d, int run, const float* m, const float* v
 
 }  // extern "C"
 
-// ---- the adversarial pair as the RAMBO device loop drives it (engine.hip: orl_rambo_update_dynamics; declared in devobj.h) ----
+// ---- the adversarial pair as the RAMBO device loop drives it (algo_rambo.inc: Engine::rambo_loop; declared in devobj.h) ----
 namespace orl {
+
+DynStreamLease::DynStreamLease(orl_dynamics* d, hipStream_t loop_stream) : d(d), own(d->stream) { d->stream = loop_stream; }
+DynStreamLease::~DynStreamLease() { d->stream = own; }
 
 int dynadv_info(orl_dynamics* d, DynAdvInfo* o) {
   if (!d || !o) return fail("dynadv_info: null handle");
@@ -1503,9 +1506,7 @@ int dynadv_info(orl_dynamics* d, DynAdvInfo* o) {
   return 0;
 }
 
-int dynadv_loop_begin(orl_dynamics* d, hipStream_t loop_stream, hipStream_t* own) {
-  *own = d->stream;
-  d->stream = loop_stream;
+int dynadv_loop_begin(orl_dynamics* d) {
   d->adv_pending = false;
   std::vector<int> act;
   // (blocking copies: the sources are locals; nothing of the loop has been enqueued yet)
@@ -1522,25 +1523,20 @@ int dynadv_update_enqueue(orl_dynamics* d, const float* advantage, int step) {
   return dynadv_update_launches(d, advantage, step, "orl_rambo_update_dynamics");
 }
 
-void dynadv_loop_end(orl_dynamics* d, hipStream_t own, long steps_done) {
-  d->stream = own;
+void dynadv_loop_end(orl_dynamics* d, long steps_done) {
   for (int r = 0; r < d->R; ++r) d->adv_tstep[r] += steps_done;
   if (steps_done > 0) { d->tap_adv_fwd = d->tap_adv_upd = d->tap_nll = true; }
 }
 
-// ---- the model step as the MBRCSL rollout loop drives it (engine.hip: orl_mbrcsl_rollout; declared in devobj.h) ----
+// ---- the model step as the MBRCSL rollout loop drives it (algo_autoreg.inc: Engine::mbrcsl_loop; declared in devobj.h) ----
 int dynstep_info(orl_dynamics* d, DynStepInfo* o) {
   if (!d || !o) return fail("dynstep_info: null handle");
   o->dev = d->c.device; o->R = d->R; o->od = d->od; o->ad = d->ad; o->with_reward = d->c.with_reward != 0; o->stream = d->stream;
   return 0;
 }
 
-int dynstep_loop_begin(orl_dynamics* d, hipStream_t loop_stream, long n_max, hipStream_t* own) {
-  *own = d->stream;
-  if (dyn_grow_step(d, n_max)) return -1;      // (on the object's own stream, which the loop's has already waited for)
-  d->stream = loop_stream;
-  return 0;
-}
+// (before the lease: growing waits for the object's own stream)
+int dynstep_loop_begin(orl_dynamics* d, long n_max) { return dyn_grow_step(d, n_max); }
 
 // (the raw reward and the penalty land in the step workspace, as they do for a host caller of orl_dyn_step)
 int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n, int mode, float coef, float* next_obs, float* reward) {
@@ -1548,7 +1544,5 @@ int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n,
   d->tap_step_rows = n; d->tap_step_t = false;
   return 0;
 }
-
-void dynstep_loop_end(orl_dynamics* d, hipStream_t own) { d->stream = own; }
 
 }  // namespace orl

@@ -75,6 +75,18 @@ struct ProfEntry {
 
 struct DY;  // backward seed description (engine.hip)
 
+// A grow-only set of row workspaces (Engine::room): entry i is a zero-filled [R][nets][factor * rows][pitch] matrix.  When a call needs
+// more rows than `cap`, every matrix is dropped and made anew for that many, and the taps named here -- views of the old ones -- are
+// forgotten; `what` is the error text when an allocation fails.  Callers view the rows they use at the front (adv_view).
+struct RowScratch {
+  struct Entry { Mat* m; int factor, pitch, nets; };
+  long cap = 0;
+  std::vector<Entry> mats;
+  std::vector<const char*> taps;
+  const char* what = "";
+  void add(Mat& m, int pitch, int factor = 1, int nets = 1) { mats.push_back({&m, factor, pitch, nets}); }
+};
+
 struct Engine {
   orl_config cfg;
   int dev = 0;
@@ -129,7 +141,7 @@ struct Engine {
   void drop_graphs();
   // split-K slab table of the last adam() launch per net (orl_debug_grads sums the slabs the way k_adam does)
   std::vector<std::pair<long, int>> last_segs[ORL_NUM_NETS];
-  std::vector<void*> allocs;
+  DevAllocs mem{"engine"};     // every device array of the engine (raw_alloc / drop)
   std::map<std::string, Mat> ws;
   std::map<std::string, long> ws_len;
   std::set<const void*> vals_dead;   // activations whose VALUES the forward pass did not store (mask bits only); consumers of the values fail
@@ -226,7 +238,15 @@ struct Engine {
   std::vector<std::string> alloc_layers(const std::string& stem, long rows, int nets = 1, int upto = -1, int width = 0);
   std::vector<Mat> layers(const std::string& stem) const { return families.at(stem); }
   std::map<std::string, std::vector<Mat>> families;
+  // zero-filled (the fill has finished on return: init and regrowth only, never inside a captured step), 16 bytes for an empty request; null on failure
   float* raw_alloc(size_t bytes);
+  void drop(Mat& m);                  // frees a matrix raw_alloc made (and its mask words), forgets its health / liveness marks, resets it
+  int room(RowScratch& s, long rows);
+  // the frame of a device loop on the engine's stream (devobj.h); a profiled loop starts from an empty profile
+  int loop_begin(LoopScope& loop, std::initializer_list<hipStream_t> wait_for) {
+    if (prof_on) { prof.clear(); ev_used = 0; }
+    return loop.begin(stream, wait_for);
+  }
   float* net_ptr(int run, int net) const;
   NetRef net_ref(int net, int members) const;
   MetricsP mp() const { return MetricsP{metrics_last, metrics_sum, nm}; }
@@ -303,7 +323,7 @@ struct Engine {
   int enqueue_step(int variant);
   int step_variant() const;
   int n_variants() const;
-  // n_steps steps between two timing events: variant v of the step is the captured graph slot0 + v (captured here when missing; eager launches
+  // n_steps steps inside a LoopScope: variant v of the step is the captured graph slot0 + v (captured here when missing; eager launches
   // when graphs are off or the run is profiled), with_inputs: every step draws its batch first.  Ends in finish() on the metric sums.
   int run_steps(int slot0, long n_steps, bool with_inputs, float* metrics_mean, float* elapsed_ms);
   // reads [R][nm] metrics back from `src`, hands them out divided by `divisor` in rows of ORL_MAX_METRICS, updates the health words
@@ -333,32 +353,38 @@ struct Engine {
   // the device-drawn stream lives in a device cell of its own (the step counter and orl_learn_n's streams stay untouched)
   int autoreg_sample(const float* obs, long n, const float* eps, bool on_device, float* act_out);
   int autoreg_sample_room(long n);
+  RowScratch ar_ws;
   int autoreg_sample_enqueue(const float* obs, long n, const float* eps, float* act_out);
   int autoreg_sample_launches(const float* d_obs, long n, const float* eps, float* act_out, hipMemcpyKind out_kind);
-  long ar_cap = 0;
   Mat ar_sx, ar_sz, ar_seps, ar_sobs; std::vector<Mat> ar_sh;
   unsigned long long* ar_calls = nullptr;
   // RAMBO (algo_rambo.inc; SAC engines).  orl_engine_adv_advantage: workspaces for Ba rows per run (the actor's input and hidden
   // activations, the 2 Ba-row critic operand with the critics' activations, head, log-prob, Q, the five tap vectors, host staging),
-  // regrown when Ba grows.  The device loop orl_rambo_update_dynamics adds its row buffers (two observation buffers that swap roles,
-  // action, noise, the dataset sample, reward, advantage), the five running sums and the call counter of its own action-noise stream.
+  // regrown when Ba grows.  The device loop (rambo_loop: orl_rambo_update_dynamics behind its refusals) adds its row buffers (two observation
+  // buffers that swap roles, action, noise, the dataset sample, reward, advantage), the five running sums and the call counter of its own
+  // action-noise stream.
   int adv_room(long Ba);
   int adv_advantage(const float* obs, const float* act, const float* nobs, const float* rew, long Ba, int term_kind, int include_ent,
                     float* adv_dev);
   int adv_act(const float* obs, long Ba, float* act_out);      // a ~ pi(. | obs) on device rows, noise from the loop's own stream
   int rambo_room(long rows);
-  long adv_cap = 0, rambo_cap = 0;
+  int rambo_loop(orl_dynamics* d, const DynAdvInfo& di, Buffer& real, const orl_rambo_loop* a, float* metrics_mean, float* elapsed_ms);
+  RowScratch adv_ws, rambo_ws;
   Mat adv_xs, adv_xc, adv_head, adv_logp, adv_q, adv_v[5], adv_in[4];
   std::vector<Mat> adv_ah, adv_ch;
   float* adv_stats = nullptr;
   Mat rb_obs[2], rb_act, rb_eps, rb_sl[5], rb_rew, rb_adv;
   float* rb_acc = nullptr;
   unsigned long long* rb_calls = nullptr;
-  // The MBRCSL rollout loop (orl_mbrcsl_rollout; AUTOREG engines): two observation buffers that swap roles, action, next observation
-  // and reward rows for n_traj trajectories, the pinned host array the survivor count of every step is copied to, and one event per
-  // step in flight (a ring of lag + 1)
+  // The MBRCSL rollout loop (algo_autoreg.inc; mbrcsl_loop: orl_mbrcsl_rollout behind its refusals; AUTOREG engines): two observation
+  // buffers that swap roles, action, next observation and reward rows for n_traj trajectories, the pinned host array the survivor count
+  // of every step is copied to, and one event per step in flight (a ring of lag + 1)
   int mbrcsl_room(long n_traj, long length, long events);
-  long ml_cap = 0, ml_counts_cap = 0;
+  int mbrcsl_loop(orl_dynamics* d, const DynStepInfo& di, orl_traj* store, const TrajInfo& ti, const float* init_obs, int n_traj, int length,
+                  int term_kind, int penalty_mode, float penalty_coef, const float* eps, int lag, int64_t* rows, double* reward_sum,
+                  double* returns_host, int32_t* steps_enqueued, float* elapsed_ms);
+  RowScratch ml_ws;
+  long ml_counts_cap = 0;
   Mat ml_obs[2], ml_act, ml_next, ml_rew;
   long long* ml_counts = nullptr;
   std::vector<hipEvent_t> ml_events;

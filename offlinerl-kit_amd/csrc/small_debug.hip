@@ -7,20 +7,13 @@
 #include <vector>
 
 #include "../../include/orl_engine.h"
+#include "debug_tap.h"
 #include "scalars.h"
 #include "small_bwd.h"
 #include "small_fwd.h"
 
 namespace orl {
-
-int fail(const std::string& msg);      // engine.hip: sets orl_last_error(), returns -1
-
 namespace {
-
-struct SmallDev {      // device copies of the tap's arrays: freed on every return path
-  std::vector<void*> ptrs;
-  ~SmallDev() { for (void* q : ptrs) hipFree(q); }
-};
 
 struct SmallBuf { const char* name; orl_gemm_buf* b; };
 
@@ -75,19 +68,10 @@ int orl_debug_small(orl_small_ex* a) {
     if (fwd ? i >= first_abwd : (i < first_abwd && !shared)) return bad(std::string(bufs[i].name) + " does not belong to this launcher");
   }
 
-  // one array: `ext` elements per problem from off + z0 s0 + z1 s1 must lie inside [0, n); the problems of a result must not overlap
+  // (no slabs here; use_z1 = false: an array that s1 does not walk)
   std::string why;
   auto fits = [&](orl_gemm_buf* bp, long ext, bool result, bool use_z1 = true) {
-    const orl_gemm_buf& b = *bp;
-    const std::string name = bufs[idx_of(bp)].name;
-    if (!b.host) { why = name + " is required"; return false; }
-    if (b.n <= 0 || b.n > (1L << 28)) { why = name + ": bad element count"; return false; }
-    if (b.off < 0 || b.s0 < 0 || b.s1 < 0 || b.ks < 0 || b.pitch < 0) { why = name + ": negative offset, pitch or stride"; return false; }
-    if (ext < 1) { why = name + ": empty extent"; return false; }
-    const int n1 = use_z1 ? nz1 : 1;
-    if (result && ((nz0 > 1 && b.s0 < ext) || (n1 > 1 && b.s1 < ext))) { why = name + ": problems of a result overlap"; return false; }
-    if (b.off + (long)(nz0 - 1) * b.s0 + (long)(n1 - 1) * b.s1 + ext > b.n) { why = name + ": the array is shorter than its offset, strides and pitch need"; return false; }
-    return true;
+    return tap_fits(*bp, bufs[idx_of(bp)].name, ext, nz0, use_z1 ? nz1 : 1, 0, result, why);
   };
   auto rows_fit = [&](orl_gemm_buf* bp, long rows, long cols, bool result, long col0 = 0) {      // row-major [rows][pitch], columns col0 .. col0 + cols
     if (bp->host && bp->pitch < col0 + cols) { why = std::string(bufs[idx_of(bp)].name) + ": the pitch is below the width"; return false; }
@@ -231,29 +215,23 @@ int orl_debug_small(orl_small_ex* a) {
   // ---- device ----
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device");
-  SmallDev dev;
-  std::vector<char*> base(bufs.size(), nullptr);
-  for (size_t i = 0; i < bufs.size(); ++i) {
-    const orl_gemm_buf& b = *bufs[i].b;
-    if (!b.host) continue;
-    if (b.n <= 0 || b.n > (1L << 28)) return bad(std::string(bufs[i].name) + ": bad element count");
-    void* d = nullptr;
-    if (hipMalloc(&d, sizeof(float) * b.n) != hipSuccess) return fail("orl_debug_small device: hipMalloc failed");
-    dev.ptrs.push_back(d);
-    base[i] = (char*)d;
-    if (hipMemcpy(d, b.host, sizeof(float) * b.n, hipMemcpyHostToDevice) != hipSuccess) return fail("orl_debug_small device: copy to the device failed");
+  // everything comes back, operands included: the caller checks that they are bit-identical
+  TapDev dev;
+  std::vector<TapArray> arrays;
+  for (const SmallBuf& sb : bufs) {
+    const orl_gemm_buf& b = *sb.b;
+    if (b.host && (b.n <= 0 || b.n > (1L << 28))) return bad(std::string(sb.name) + ": bad element count");
+    arrays.push_back({b.host, b.host, b.n});
   }
+  std::vector<char*> base(bufs.size(), nullptr);
+  if (tap_upload(dev, arrays, base.data(), "orl_debug_small")) return -1;
   params(base);
   hipStream_t st = nullptr;
   hipError_t err = fwd ? launch_small_fwd(pf, nz, st) : launch_small_abwd(pb, nz0, st);
   if (err != hipSuccess) return fail(std::string("orl_debug_small device: launch: ") + hipGetErrorString(err));
   err = hipDeviceSynchronize();
   if (err != hipSuccess) return fail(std::string("orl_debug_small device: ") + hipGetErrorString(err));
-  // everything comes back, operands included: the caller checks that they are bit-identical
-  for (size_t i = 0; i < bufs.size(); ++i)
-    if (base[i] && hipMemcpy(bufs[i].b->host, base[i], sizeof(float) * bufs[i].b->n, hipMemcpyDeviceToHost) != hipSuccess)
-      return fail("orl_debug_small device: copy from the device failed");
-  return 0;
+  return tap_download(arrays, base.data(), "orl_debug_small");
 }
 
 }  // extern "C"

@@ -7,12 +7,10 @@
 #include <vector>
 
 #include "../../include/orl_engine.h"
+#include "debug_tap.h"
 #include "ws_gemm.h"
 
 namespace orl {
-
-int fail(const std::string& msg);      // engine.hip: sets orl_last_error(), returns -1
-
 namespace {
 
 // Every instantiation of the ws_* kernels = the launchers' own tables (ws_gemm.h: WsTable), in the order of the tap's kinds; a launch reports the
@@ -21,11 +19,6 @@ namespace {
 //   ws_wgrad<MODE> / ws_wgrad32<MODE>  ws_wgrad3p
 typedef const WsTable& (*WsTableFn)();
 static const WsTableFn WS_TABLES[] = {ws_fwd_table, ws_fwd3_table, ws_dgrad_table, ws_dgrad3_table, ws_wgrad_table, ws_wgrad3p_table};
-
-struct WsDev {      // device copies of the tap's arrays: freed on every return path
-  std::vector<void*> ptrs;
-  ~WsDev() { for (void* q : ptrs) hipFree(q); }
-};
 
 enum { B_X, B_W, B_BIAS, B_TW, B_TB, B_X0, B_W0, B_B0, B_DMASK, B_ABITS, B_XBITS, B_DQ, B_WT, B_Z, B_H0, B_H1, B_W1, B_B1, B_DZ, B_GSCALE,
        B_Y, B_MB, B_MB0, B_TQ, B_TQ2, B_C, B_W0O, B_B0O, B_DW, B_DB, B_DWT, B_DBT, B_COUNT };
@@ -89,20 +82,8 @@ int orl_debug_ws(orl_ws_ex* a) {
   for (int i = 0; i < B_COUNT; ++i)
     if (has(i) && !ws_buf_allowed(kind, i)) return bad(std::string(WS_BUF_NAMES[i]) + " does not belong to this launcher");
 
-  // one array: `ext` elements per (problem, slab) from off + z0 s0 + z1 s1 + ks ks must lie inside [0, n); results must not overlap
   std::string why;
-  auto fits = [&](int i, long ext, int nslab, bool result) {
-    const orl_gemm_buf& b = *bufs[i];
-    const std::string name = WS_BUF_NAMES[i];
-    if (!b.host) { why = name + " is required"; return false; }
-    if (b.n <= 0 || b.n > (1L << 28)) { why = name + ": bad element count"; return false; }
-    if (b.off < 0 || b.s0 < 0 || b.s1 < 0 || b.ks < 0 || b.pitch < 0) { why = name + ": negative offset, pitch or stride"; return false; }
-    if (ext < 1) { why = name + ": empty extent"; return false; }
-    if (result && ((nz0 > 1 && b.s0 < ext) || (nz1 > 1 && b.s1 < ext) || (nslab > 1 && b.ks < ext))) { why = name + ": problems or slabs of a result overlap"; return false; }
-    const long last = b.off + (long)(nz0 - 1) * b.s0 + (long)(nz1 - 1) * b.s1 + (long)(nslab - 1) * b.ks + ext;
-    if (last > b.n) { why = name + ": the array is shorter than its offset, strides and pitch need"; return false; }
-    return true;
-  };
+  auto fits = [&](int i, long ext, int nslab, bool result) { return tap_fits(*bufs[i], WS_BUF_NAMES[i], ext, nz0, nz1, nslab, result, why); };
   // a row-major [M][cols] matrix with a pitch
   auto rows_fit = [&](int i, long cols, bool result) {
     if (has(i) && bufs[i]->pitch < cols) { why = std::string(WS_BUF_NAMES[i]) + ": the pitch is below the width"; return false; }
@@ -268,22 +249,14 @@ int orl_debug_ws(orl_ws_ex* a) {
   // ---- device ----
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device");
-  WsDev dev;
+  // everything comes back, operands included: the caller checks that they are bit-identical (X under the fused first layer is a result)
+  TapDev dev;
+  std::vector<TapArray> arrays;
+  for (int i = 0; i < B_COUNT; ++i) arrays.push_back({bufs[i]->host, bufs[i]->host, bufs[i]->n});
   char* base[B_COUNT];
-  for (int i = 0; i < B_COUNT; ++i) {
-    base[i] = nullptr;
-    if (!has(i)) continue;
-    void* d = nullptr;
-    if (hipMalloc(&d, sizeof(float) * bufs[i]->n) != hipSuccess) return fail("orl_debug_ws device: hipMalloc failed");
-    dev.ptrs.push_back(d);
-    base[i] = (char*)d;
-    if (hipMemcpy(d, bufs[i]->host, sizeof(float) * bufs[i]->n, hipMemcpyHostToDevice) != hipSuccess) return fail("orl_debug_ws device: copy to the device failed");
-  }
+  if (tap_upload(dev, arrays, base, "orl_debug_ws")) return -1;
   float* dump = nullptr;
-  if (kind == ORL_WS_FWD3) {
-    if (hipMalloc((void**)&dump, sizeof(float) * (size_t)WS_DUMP_SLOTS * WS_N) != hipSuccess) return fail("orl_debug_ws device: hipMalloc failed");
-    dev.ptrs.push_back(dump);
-  }
+  if (kind == ORL_WS_FWD3 && dev.alloc(&dump, (size_t)WS_DUMP_SLOTS * WS_N, "orl_debug_ws")) return -1;
   params(base, dump);
   hipStream_t st = nullptr;
   hipError_t err = hipErrorInvalidValue;
@@ -298,10 +271,7 @@ int orl_debug_ws(orl_ws_ex* a) {
   if (err != hipSuccess) return fail(std::string("orl_debug_ws device: launch: ") + hipGetErrorString(err));
   err = hipDeviceSynchronize();
   if (err != hipSuccess) return fail(std::string("orl_debug_ws device: ") + hipGetErrorString(err));
-  // everything comes back, operands included: the caller checks that they are bit-identical (X under the fused first layer is a result)
-  for (int i = 0; i < B_COUNT; ++i)
-    if (base[i] && hipMemcpy(bufs[i]->host, base[i], sizeof(float) * bufs[i]->n, hipMemcpyDeviceToHost) != hipSuccess) return fail("orl_debug_ws device: copy from the device failed");
-  return 0;
+  return tap_download(arrays, base, "orl_debug_ws");
 }
 
 }  // extern "C"

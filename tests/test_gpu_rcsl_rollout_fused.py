@@ -1,7 +1,8 @@
 """GPU: the MBRCSL rollout as one device loop -- the trajectory store's device-counted step (orl_traj_append_step_counted) against the
 numpy bookkeeping of rcsl_rollout_ref.py bit for bit, under stale and exact row bounds; the refusals of the step and of the loop; the
 loop (orl_mbrcsl_rollout) against a replay of every step through the public calls on its own stored rows; a rollout in which
-everything dies at once; reproducibility, and the host-counted path around a fused rollout."""
+everything dies at once; the same replay around a regrowth of the loop's workspaces; reproducibility, and the host-counted path around a
+fused rollout."""
 import os
 
 import numpy as np
@@ -178,12 +179,13 @@ def world(tmp_path_factory):
     return dict(twin=twin, dynamics=dynamics, ar=ar, init=init, od=OD, ad=AD, kind=TERM_ANT, term_fn=termination_fn_ant, scaler=first.scaler)
 
 
-def _loop(world, dyn, store, init, length, lag, eps, kind=None, mode=None, coef=None):
-    """orl_mbrcsl_rollout through the engines of ``dyn`` and the world's policy -> (rows, reward sum, returns, steps enqueued, ms)"""
+def _loop(world, dyn, store, init, length, lag, eps, kind=None, mode=None, coef=None, pol=None):
+    """orl_mbrcsl_rollout through the engines of ``dyn`` and of ``pol`` (the world's policy when none is given) -> (rows, reward sum,
+    returns, steps enqueued, ms)"""
     deng, m, c = dyn.loop_engine()
     io = t(np.ascontiguousarray(init, dtype=np.float32))
     torch.cuda.synchronize()
-    return world["ar"].loop_engine().mbrcsl_rollout(deng, store, io.data_ptr(), len(init), length, world["kind"] if kind is None else kind,
+    return (pol or world["ar"]).loop_engine().mbrcsl_rollout(deng, store, io.data_ptr(), len(init), length, world["kind"] if kind is None else kind,
                                                     m if mode is None else mode, c if coef is None else coef,
                                                     None if eps is None else eps.data_ptr(), lag)
 
@@ -342,26 +344,23 @@ def test_loop_refusals_leave_everything_as_it_was(world):
 
 
 # ---- 3. the loop against a per-step replay through the public calls ---------------------------------------------------------------------------
-@pytest.mark.parametrize("lag", [0, 2, 6])
-def test_loop_matches_a_per_step_replay(world, lag):
-    from offlinerlkit import _engine
-    od, ad, init = world["od"], world["ad"], world["init"]
-    dyn, twin = world["twin"](), world["twin"]()
-    torch.manual_seed(123)
-    eps = torch.randn((LENGTH, N_TRAJ, ad), device=DEV)
-    store = _engine.TrajStore(od, ad, N_TRAJ, N_TRAJ * LENGTH)
-    rows, rew_sum, returns, enq, ms = _loop(world, dyn, store, init, LENGTH, lag, eps)
-    got, sizes = _store_equals_its_book(world, store, rows, returns, N_TRAJ)
-    per_traj = np.bincount(got["traj_idx"], minlength=N_TRAJ)
-    print(f"lag {lag}: {rows} transitions, survivors {sizes}, {int((per_traj == LENGTH).sum())} of full length, {enq} steps enqueued, "
+def _loop_equals_its_replay(world, dyn, twin, store, init, length, lag, eps, pol=None):
+    """One loop of ``dyn`` and ``pol`` over ``init`` into ``store``, checked against the store's own book, the enqueue plan and a replay of
+    every step through orl_autoreg_sample / orl_dyn_step on the loop's own rows (bit for bit at lag 0, where the replay launches the
+    loop's shapes).  ``twin``'s call counter must equal ``dyn``'s before the call and does so again after it.  -> (rows, step sizes, got)"""
+    n_traj = len(init)
+    rows, rew_sum, returns, enq, ms = _loop(world, dyn, store, init, length, lag, eps, pol=pol)
+    got, sizes = _store_equals_its_book(world, store, rows, returns, n_traj)
+    per_traj = np.bincount(got["traj_idx"], minlength=n_traj)
+    print(f"lag {lag}: {rows} transitions, survivors {sizes}, {int((per_traj == length).sum())} of full length, {enq} steps enqueued, "
           f"loop {ms:.3f} ms")
-    assert sizes[0] == N_TRAJ and len(sizes) >= 3 and 0 < sizes[1] < N_TRAJ and 0 < sizes[2] < sizes[1]      # the thinning is not vacuous
-    assert np.array_equal(ref.bits(got["obs"][:N_TRAJ]), ref.bits(init))
-    counts = sizes[1:] + [int((got["term"][rows - sizes[-1]:] == 0).sum())] + [0] * LENGTH
-    assert enq == len(fref.enqueue_plan(N_TRAJ, counts[:LENGTH], lag))
+    assert sizes[0] == n_traj
+    assert np.array_equal(ref.bits(got["obs"][:n_traj]), ref.bits(init))
+    counts = sizes[1:] + [int((got["term"][rows - sizes[-1]:] == 0).sum())] + [0] * length
+    assert enq == len(fref.enqueue_plan(n_traj, counts[:length], lag))
     assert abs(rew_sum - got["rew"].astype(np.float64).sum()) <= 1e-9 * np.abs(got["rew"]).astype(np.float64).sum()
     # step k through orl_autoreg_sample / orl_dyn_step on the loop's own rows; the twin's call counter runs with the loop's
-    peng = world["ar"].loop_engine()
+    peng = (pol or world["ar"]).loop_engine()
     teng, mode, coef = twin.loop_engine()
     eps_h, off, worst = eps.cpu().numpy(), 0, {}
     for k, n in enumerate(sizes):
@@ -377,6 +376,42 @@ def test_loop_matches_a_per_step_replay(world, lag):
         off += n
     print(f"lag {lag}: largest difference to the replay, relative to each array's scale: {worst}")
     assert all(v <= 1e-4 for v in worst.values()), worst
+    for _ in range(enq - len(sizes)):       # the steps the loop enqueued on rows that had all ended advanced its dynamics' call counter too
+        twin.step_device(torch.zeros((3, world["od"]), device=DEV), torch.zeros((3, world["ad"]), device=DEV))
+    return rows, sizes, got
+
+
+@pytest.mark.parametrize("lag", [0, 2, 6])
+def test_loop_matches_a_per_step_replay(world, lag):
+    from offlinerlkit import _engine
+    od, ad, init = world["od"], world["ad"], world["init"]
+    dyn, twin = world["twin"](), world["twin"]()
+    torch.manual_seed(123)
+    eps = torch.randn((LENGTH, N_TRAJ, ad), device=DEV)
+    store = _engine.TrajStore(od, ad, N_TRAJ, N_TRAJ * LENGTH)
+    _, sizes, _ = _loop_equals_its_replay(world, dyn, twin, store, init, LENGTH, lag, eps)
+    assert len(sizes) >= 3 and 0 < sizes[1] < N_TRAJ and 0 < sizes[2] < sizes[1]      # the thinning is not vacuous
+    store.close()
+
+
+@pytest.mark.parametrize("lag", [0, 2])
+def test_loop_matches_its_replay_around_a_regrowth(world, lag):
+    """ONE policy engine (a fresh one: its loop workspaces start empty), one dynamics and one store, three loops of 8, 40 and 8
+    trajectories: the second regrows the row workspaces of the sampling and of the loop, the third views 8 rows at the front of the
+    40-row allocation.  Every call equals its replay the way a first call does."""
+    from offlinerlkit import _engine
+    from offlinerlkit.policy import AutoregressivePolicy
+    od, ad, init, length = world["od"], world["ad"], world["init"], 3
+    torch.manual_seed(17)
+    pol = AutoregressivePolicy(od, ad, [32, 32], 1e-3, DEV)
+    dyn, twin = world["twin"](), world["twin"]()
+    store = _engine.TrajStore(od, ad, 40, 40 * length)
+    row0 = 0
+    for n in (8, 40, 8):
+        eps = torch.randn((length, n, ad), device=DEV)
+        rows, sizes, _ = _loop_equals_its_replay(world, dyn, twin, store, init[row0:row0 + n], length, lag, eps, pol=pol)
+        assert n <= rows <= n * length
+        row0 += n
     store.close()
 
 

@@ -4,7 +4,9 @@
 Compiles the device side of every translation unit of build.UNITS (or of the units named) from both csrc folders with the
 build's own flags plus `--cuda-device-only -S` and compares the assembly texts.  A host-only refactor must leave every unit
 identical; the __hip_cuid_<hash of the source text> symbol is normalised.  A differing unit is listed with its first differing
-lines.  Exit status 0 = all identical.  Both folders must sit in FULL trees (the sources include ../../include/orl_engine.h):
+lines.  A unit that only one tree has (a unit split off another, or merged into one) is listed with the kernels its assembly holds:
+none for a host-only unit; otherwise the unit they moved from or to shows them missing or added in its own diff.  Exit status 0 = all
+identical.  Both folders must sit in FULL trees (the sources include ../../include/orl_engine.h):
 take the parent with `git worktree`, not with an archive of csrc alone.
 
     git worktree add /tmp/parent HEAD~1
@@ -26,6 +28,8 @@ CUID = re.compile(r"__hip_cuid_[0-9a-f]+")      # per-unit symbol named after a 
 
 
 def isa(csrc, unit, out):
+    if not os.path.exists(os.path.join(csrc, unit)):
+        return None
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     subprocess.check_call([hipcc] + build.FLAGS + ["--cuda-device-only", "-S", os.path.join(csrc, unit), "-o", out])
     with open(out) as fh:
@@ -43,6 +47,11 @@ def main():
                 for u in units}
         for u, (fa, fb) in jobs.items():
             a, b = fa.result(), fb.result()
+            if a is None or b is None:
+                have = a if b is None else b
+                names = [x.split()[1] for x in have if x.strip().startswith(".amdhsa_kernel ")]
+                print("%-22s only in the %s tree: %d kernels %s" % (u, "parent" if b is None else "new", len(names), " ".join(names)), flush=True)
+                continue
             if a == b:
                 print("%-22s identical (%d lines)" % (u, len(a)), flush=True)
                 continue
