@@ -662,6 +662,9 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
  * elites, runs with different elite counts.  (Named orl_dynsample_*, not orl_dyn_*, like orl_dynadv_*.) */
 int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int64_t n, int32_t num_samples, int on_device,
                        const float* noise, float* next_obs);
+/* how many sample calls the object has made: orl_dynsample_next's call counter, which also advances once per step of
+ * orl_mobile_learn_n (the Philox key of the next call's draws); < 0 for a null handle */
+int64_t orl_dynsample_calls(orl_dynamics* d);
 /* test tap: parameter gradient of the LAST minibatch of the last orl_dyn_learn_epoch, or of the last orl_dynadv_update, whichever
  * ran later (flat like orl_dyn_get; decay terms excluded) */
 int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n_floats);
@@ -735,6 +738,24 @@ typedef struct orl_rambo_loop {
  * devices or dims, an empty buffer, an unknown term_kind (or one that reads a missing observation column), rows < 2, no steps. */
 int orl_rambo_update_dynamics(orl_engine* e, orl_dynamics* d, orl_buffer* real, const orl_rambo_loop* a, float* metrics_mean /*[5]*/,
                               float* elapsed_ms);
+
+/* MOBILE's learn (mobile.py:144-196) n_steps times without a host round trip per step: `e` an ORL_ALGO_MOBILE engine with a dataset
+ * buffer (orl_engine_attach_buffer) and a model ring (orl_engine_attach_model_buffer, real_rows = the engine's mobile_real_rows), `d`
+ * its dynamics.  Every launch of both objects goes to the engine's stream (the dynamics' own stream is waited for through an event
+ * first), launched eagerly, and the host synchronises once at the end.  Step i: the minibatch draw and the three noise slots of
+ * orl_learn_n at the step counter (rows [0, real_rows) from the dataset, the rest from the ring; same Philox keys as a SAC engine's
+ * orl_learn_n); the launches of orl_dynsample_next(noise = NULL) on the drawn observation / action rows at the dynamics' sample call
+ * counter, with the S * E * B samples written straight into the operands of the penalty pass (no sample array, no assemble launch:
+ * the same values bit for bit); orl_step's launches behind the assemble.  Metrics are summed on the device and divided by n_steps
+ * into metrics_mean [n_runs][ORL_MAX_METRICS]; elapsed_ms (optional) is the HIP-event time of the loop; health flags and the return
+ * code ORL_RC_UNHEALTHY as for orl_learn_n.  The engine's step counter and the dynamics' sample call counter advance by n_steps;
+ * orl_dyn_step's and orl_dynadv_*'s counters do not move and a pending orl_dynadv_forward stays pending.  The taps "penalty", "lcb_q",
+ * "xs", "xl", "ql1", "ql2", "logp_l", the batch slots and the noise slots hold the last step's values.  Refused before anything is
+ * launched or any counter moves: an engine that is not ORL_ALGO_MOBILE, n_runs != 1 on either object, different devices or dims, a
+ * dynamics without reward, fewer than 2 elites or a count that differs from mobile_num_elites, no dataset buffer, no or an empty model
+ * ring (or one attached with another real_rows), n_steps < 1, pending samples of orl_engine_set_next_samples (they stay usable by
+ * the next orl_step).  orl_learn_n keeps refusing MOBILE engines. */
+int orl_mobile_learn_n(orl_engine* e, orl_dynamics* d, int n_steps, float* metrics_mean /*[n_runs][ORL_MAX_METRICS]*/, float* elapsed_ms);
 
 /* RcslPolicy.rollout (rcsl.py:57-120) as one device loop: `policy` an ORL_ALGO_AUTOREG engine, `d` its dynamics, `store` the
  * trajectory store (reset here for n_traj trajectories).  Every launch of the three objects goes to the policy engine's stream (the

@@ -63,7 +63,24 @@ int dynstep_info(orl_dynamics* d, DynStepInfo* out);
 int dynstep_loop_begin(orl_dynamics* d, long n_max);
 int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n, int mode, float coef, float* next_obs, float* reward);
 
-#define ORL_HIP(expr)                                                                            \
+// orl_dynsample_next (dynamics.hip) as the MOBILE device loop drives it under a DynStreamLease (algo_mobile.inc: Engine::mobile_loop):
+// the input rows are the policy engine's pitched batch slots (row b of run r at obs + r obs_rs + b obs_pitch), and the S * E * n samples
+// go straight into the operands of the penalty pass -- xs [R][S E n][OP] and the observation columns of xl [R][S E n][XP], pads zeroed,
+// the action columns of xl left alone -- instead of a packed [R][S E n][od] array.  No staging and no synchronisation; the step
+// workspaces are grown before the loop (dynstep_loop_begin), every enqueue advances the sample call counter as orl_dynsample_next does
+// and takes its refusals (`who` prefixes them).
+struct DynSampleInfo { int dev, R, od, ad, n_elites; bool with_reward; hipStream_t stream; };
+int dynsample_info(orl_dynamics* d, DynSampleInfo* out);
+struct DynSampleRows {
+  const float* obs; long obs_rs; int obs_pitch;
+  const float* act; long act_rs; int act_pitch;
+  long n; int num_samples;
+  float* xs; long xs_rs; int OP;
+  float* xl; long xl_rs; int XP;
+};
+int dynsample_enqueue(orl_dynamics* d, const DynSampleRows& rows, const char* who);
+
+#define ORL_HIP(expr)                                                                           \
   do {                                                                                           \
     hipError_t _e = (expr);                                                                      \
     if (_e != hipSuccess) {                                                                      \

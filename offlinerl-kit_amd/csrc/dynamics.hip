@@ -120,6 +120,18 @@ __global__ void k_dyn_step_input(const float* __restrict__ obs, const float* __r
   dyn_scale_row(obs + ri * od, od, act + ri * ad, ad, mu + (long)r * (od + ad), sd + (long)r * (od + ad), X + ri * xp, xp);
 }
 
+// k_dyn_step_input on pitched source rows (the policy engine's batch slots): obs[r][i] at obs + r obs_rs + i obs_pitch, act likewise;
+// dyn_scale_row's arithmetic, so the forward sees the bits it sees from packed rows
+__global__ void k_dyn_step_input_rows(const float* __restrict__ obs, long obs_rs, int obs_pitch, const float* __restrict__ act, long act_rs,
+                                      int act_pitch, long n, int od, int ad, const float* __restrict__ mu, const float* __restrict__ sd,
+                                      float* __restrict__ X, int xp) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  if (i >= n) return;
+  dyn_scale_row(obs + r * obs_rs + i * obs_pitch, od, act + r * act_rs + i * act_pitch, ad, mu + (long)r * (od + ad),
+                sd + (long)r * (od + ad), X + ((long)r * n + i) * xp, xp);
+}
+
 // Gaussian NLL head, one thread per (run, member, row, dim).  OUT / dOUT [r][k][i][op] (mean: cols 0..D, raw logvar: D..2D),
 // T / lterm / gmax / gmin [r][k][i][D] with row stride `bs` rows per (r, k).
 __global__ void k_dyn_nll(const float* __restrict__ OUT, float* __restrict__ dOUT, int op, const float* __restrict__ T,
@@ -390,6 +402,65 @@ __global__ __launch_bounds__(256) void k_dyn_sample_next(DynSampleNextP p) {
     const float mean = out[d] + obs[d];
     // two roundings in fp32: the reference's mean + torch.randn_like(std) * std
     dst[d] = __fadd_rn(mean, __fmul_rn(eps, dyn_std(out[D + d], mx[d], mn[d])));
+  }
+}
+
+// k_dyn_sample_next's samples written straight into the operands of MOBILE's penalty pass (orl::dynsample_enqueue, the device loop of
+// orl_mobile_learn_n): the actor's input rows xs (pitch OP) and the observation columns of the target critics' input rows xl (pitch XP)
+struct DynSampleRowsP {
+  const float* OUT; int op;
+  const float* obs; long obs_rs; int obs_pitch;   // the engine's pitched batch slot: row b of run r at obs + r obs_rs + b obs_pitch
+  long n; int od, D, K, S, E;
+  const float* params; long P, off_max, off_min;
+  const int* elites;                  // [R][K], the first E entries in set_elites order
+  uint64_t seed; uint64_t call;
+  float* xs; long xs_rs; int OP;      // [R][S * E * n][OP], row (s * E + e) * n + b
+  float* xl; long xl_rs; int XP;      // [R][S * E * n][XP]
+  int ad;
+  int vec;                            // both operands 16-byte aligned with pitches and run strides of whole quads: a full quad is one store
+};
+
+// one thread per (run, sample s, elite position e, row b, four output dims), the values of k_dyn_sample_next (same Philox counter, same
+// two roundings; the reward column is drawn and dropped).  The row's last quad also zeroes the pad columns [od, OP) of xs and
+// [od + ad, XP) of xl; the action columns [od, od + ad) of xl are the sampling job's
+__global__ __launch_bounds__(256) void k_dyn_sample_rows(DynSampleRowsP p) {
+  const int nq = (p.D + 3) >> 2;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  const long rows = (long)p.S * p.E * p.n;
+  if (t >= rows * nq) return;
+  const long row = t / nq;
+  const int q = (int)(t - row * nq);
+  const long se = row / p.n, b = row - se * p.n;
+  const int e = (int)(se % p.E);
+  const int D = p.D, od = p.od, K = p.K;
+  const int mi = p.elites[r * K + e];
+  const float* mx = p.params + r * p.P + p.off_max;
+  const float* mn = p.params + r * p.P + p.off_min;
+  uint32_t rnd[4];
+  Philox(p.seed)((uint32_t)b, (uint32_t)se, (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)q, rnd);
+  const float* out = p.OUT + (((long)r * K + mi) * p.n + b) * p.op;
+  const float* obs = p.obs + r * p.obs_rs + b * p.obs_pitch;
+  float* a = p.xs + r * p.xs_rs + row * p.OP;
+  float* x = p.xl + r * p.xl_rs + row * p.XP;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < 4 && 4 * q + j < od; ++j) {
+    const int d = 4 * q + j;
+    const float eps = box_muller_one(rnd, j);
+    const float mean = out[d] + obs[d];
+    // two roundings in fp32: the reference's mean + torch.randn_like(std) * std
+    v[j] = __fadd_rn(mean, __fmul_rn(eps, dyn_std(out[D + d], mx[d], mn[d])));
+  }
+  if (p.vec && 4 * q + 3 < od) {
+    const float4 v4 = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(a + 4 * q) = v4;
+    *reinterpret_cast<float4*>(x + 4 * q) = v4;
+  } else {
+    for (int j = 0; j < 4 && 4 * q + j < od; ++j) { a[4 * q + j] = v[j]; x[4 * q + j] = v[j]; }
+  }
+  if (q == nq - 1) {
+    for (int c = od; c < p.OP; ++c) a[c] = 0.f;
+    for (int c = od + p.ad; c < p.XP; ++c) x[c] = 0.f;
   }
 }
 
@@ -1207,16 +1278,24 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
 }
 
 // ---- MOBILE's next-state samples ----
+// what orl_dynsample_next and orl::dynsample_enqueue refuse; returns the elite count
+static int dyn_sample_elites(orl_dynamics* d, long n, long num_samples, const char* who) {
+  const std::string w(who);
+  if (num_samples < 1) return fail(w + ": num_samples must be >= 1");
+  const int E = dyn_n_elites(d, who);
+  if (E < 0) return -1;
+  if (E < 2) return fail(w + ": needs at least 2 elites (the standard deviation over one elite is NaN)");
+  if (num_samples * E * n * ((d->D + 3) / 4) > (1L << 38) || n > 0x7fffffffL) return fail(w + ": too many rows");
+  return E;
+}
+
 int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int64_t n, int32_t num_samples, int on_device,
                        const float* noise, float* next_obs) {
   if (!d || !obs || !act || n < 1 || !next_obs) return fail("orl_dynsample_next: bad arguments");
-  if (num_samples < 1) return fail("orl_dynsample_next: num_samples must be >= 1");
   const int R = d->R, K = d->K, D = d->D, od = d->od, ad = d->ad;
-  const int E = dyn_n_elites(d, "orl_dynsample_next");
+  const int E = dyn_sample_elites(d, (long)n, num_samples, "orl_dynsample_next");
   if (E < 0) return -1;
-  if (E < 2) return fail("orl_dynsample_next: needs at least 2 elites (the standard deviation over one elite is NaN)");
   const long S = num_samples, rows = S * E * n;
-  if (rows * ((D + 3) / 4) > (1L << 38) || n > 0x7fffffffL) return fail("orl_dynsample_next: too many rows");
   if (dyn_grow_step(d, n)) return -1;
   if (!on_device && rows > d->m_cap) {
     ORL_HIP(hipStreamSynchronize(d->stream));
@@ -1243,6 +1322,11 @@ int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int6
   ORL_HIP(hipStreamSynchronize(d->stream));
   d->tap_step_rows = n; d->tap_step_t = false;
   return 0;
+}
+
+int64_t orl_dynsample_calls(orl_dynamics* d) {
+  if (!d) return fail("orl_dynsample_calls: null handle");
+  return (int64_t)d->sample_calls;
 }
 
 int orl_dyn_debug_grads(orl_dynamics* d, int run, float* host, int64_t n) {
@@ -1541,6 +1625,45 @@ int dynstep_loop_begin(orl_dynamics* d, long n_max) { return dyn_grow_step(d, n_
 // (the raw reward and the penalty land in the step workspace, as they do for a host caller of orl_dyn_step)
 int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n, int mode, float coef, float* next_obs, float* reward) {
   if (dyn_step_launches(d, obs, act, n, nullptr, nullptr, mode, coef, next_obs, reward, d->sRaw, d->sPen, nullptr, "orl_mbrcsl_rollout")) return -1;
+  d->tap_step_rows = n; d->tap_step_t = false;
+  return 0;
+}
+
+// ---- MOBILE's samples as the device loop of orl_mobile_learn_n drives them (algo_mobile.inc: Engine::mobile_loop; declared in devobj.h) ----
+int dynsample_info(orl_dynamics* d, DynSampleInfo* o) {
+  if (!d || !o) return fail("dynsample_info: null handle");
+  o->dev = d->c.device; o->R = d->R; o->od = d->od; o->ad = d->ad; o->with_reward = d->c.with_reward != 0; o->stream = d->stream;
+  o->n_elites = (int)d->elites_h[0].size();
+  return 0;
+}
+
+// the launches of orl_dynsample_next on the engine's pitched batch rows with the samples written in place: k_dyn_step_input_rows, the
+// ensemble's forward, k_dyn_sample_rows; the call counter advances.  No staging, no synchronisation, nothing grown (dynstep_loop_begin
+// before the loop)
+int dynsample_enqueue(orl_dynamics* d, const DynSampleRows& a, const char* who) {
+  if (!d || !a.obs || !a.act || a.n < 1 || !a.xs || !a.xl) return fail(std::string(who) + ": bad arguments");
+  const int E = dyn_sample_elites(d, a.n, a.num_samples, who);
+  if (E < 0) return -1;
+  const long n = a.n;
+  if (n > d->s_cap) return fail(std::string(who) + ": the step workspaces hold fewer rows (dynstep_loop_begin before the loop)");
+  DEV_LAUNCH(d->stream, k_dyn_step_input_rows, dim3((unsigned)((n + 255) / 256), d->R), dim3(256), 0, a.obs, a.obs_rs, a.obs_pitch, a.act,
+             a.act_rs, a.act_pitch, n, d->od, d->ad, (const float*)d->mu, (const float*)d->sd, d->sw.X, d->pitch[0]);
+  d->sw.rows = n;
+  if (dyn_forward(d, d->sw, (int)n, false)) return -1;
+  DynSampleRowsP p;
+  memset(&p, 0, sizeof(p));
+  p.OUT = d->sw.OUT; p.op = d->pitch[d->L + 1];
+  p.obs = a.obs; p.obs_rs = a.obs_rs; p.obs_pitch = a.obs_pitch;
+  p.n = n; p.od = d->od; p.D = d->D; p.K = d->K; p.S = a.num_samples; p.E = E;
+  p.params = d->params; p.P = d->P; p.off_max = d->off_max; p.off_min = d->off_min;
+  p.elites = d->elites_d;
+  p.seed = d->c.seed ^ 0xD1B54A32D192ED03ull; p.call = d->sample_calls++;
+  p.xs = a.xs; p.xs_rs = a.xs_rs; p.OP = a.OP;
+  p.xl = a.xl; p.xl_rs = a.xl_rs; p.XP = a.XP;
+  p.ad = d->ad;
+  p.vec = ((((uintptr_t)a.xs | (uintptr_t)a.xl) & 15) == 0 && ((a.OP | a.XP) & 3) == 0 && ((a.xs_rs | a.xl_rs) & 3) == 0) ? 1 : 0;
+  const long nt = (long)a.num_samples * E * n * ((d->D + 3) / 4);
+  DEV_LAUNCH(d->stream, k_dyn_sample_rows, dim3((unsigned)((nt + 255) / 256), d->R), dim3(256), 0, p);
   d->tap_step_rows = n; d->tap_step_t = false;
   return 0;
 }

@@ -335,7 +335,10 @@ struct Engine {
   int edac_build(); int edac_step();
   int sac_build(); int sac_step();
   int mcq_build(); int mcq_step();
-  int mobile_build(); int mobile_step(); int mobile_penalty(int real_rows);
+  int mobile_build(); int mobile_step(); int mobile_penalty(int real_rows, bool rows_in_place = false);
+  // the device loop of orl_mobile_learn_n (algo_mobile.inc): while it enqueues, mobile_step's penalty pass finds its rows in place
+  bool mobile_rows_in_place = false;
+  int mobile_loop(orl_dynamics* d, const DynSampleInfo& di, int n_steps, float* metrics_mean, float* elapsed_ms);
   int rcsl_build(); int rcsl_step(); int rcsl_prepare(int mode);
   int rcslg_build(); int rcslg_step();
   int autoreg_build(); int autoreg_step(); int autoreg_prepare(int mode);

@@ -1968,6 +1968,36 @@ int orl_rambo_update_dynamics(orl_engine* h, orl_dynamics* d, orl_buffer* real, 
   return e.rambo_loop(d, di, b, a, metrics_mean, elapsed_ms);
 }
 
+int orl_mobile_learn_n(orl_engine* h, orl_dynamics* d, int n_steps, float* metrics_mean, float* elapsed_ms) {
+  const std::string f("orl_mobile_learn_n");
+  if (!h || !d) return fail(f + ": bad arguments");
+  Engine& e = h->e;
+  DynSampleInfo di;
+  if (dynsample_info(d, &di)) return -1;
+  if (e.cfg.algo != ORL_ALGO_MOBILE) return fail(f + ": not a MOBILE engine");
+  if (e.R != 1 || di.R != 1) return fail(f + ": one run per policy and per dynamics ensemble (n_runs == 1 on both)");
+  if (di.dev != e.dev) return fail(f + ": engine and dynamics must live on one device");
+  if (di.od != e.od || di.ad != e.ad) return fail(f + ": obs / act dims of engine and dynamics differ");
+  if (!di.with_reward) return fail(f + ": needs a dynamics with_reward (MOBILE's ensemble predicts the reward; its column is drawn and dropped)");
+  if (di.n_elites < 2) return fail(f + ": needs at least 2 elites (the standard deviation over one elite is NaN)");
+  if (di.n_elites != e.cfg.mobile_num_elites) {
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: the dynamics has %d elites, the engine's row layout is built for mobile_num_elites = %d", f.c_str(),
+             di.n_elites, (int)e.cfg.mobile_num_elites);
+    return fail(msg);
+  }
+  if (!e.buf || !e.buf->obs || e.buf->n < 1) return fail(f + ": no replay buffer attached (orl_engine_attach_buffer)");
+  if (!e.mbuf) return fail(f + ": no model ring attached (orl_engine_attach_model_buffer)");
+  if (!e.mbuf->obs || e.mbuf->n < 1) return fail(f + ": the model buffer is empty (roll the dynamics out into it first)");
+  if (e.mbuf_real_rows != e.cfg.mobile_real_rows)
+    return fail(f + ": the model buffer's real_rows differs from the engine's mobile_real_rows (the penalty is zeroed on the real rows)");
+  if (n_steps < 1) return fail(f + ": n_steps must be positive");
+  if (e.mobile_pending)
+    return fail(f + ": samples of orl_engine_set_next_samples are pending (the next orl_step consumes them; the loop draws its own)");
+  ORL_HIP(hipSetDevice(e.dev));
+  return e.mobile_loop(d, di, n_steps, metrics_mean, elapsed_ms);
+}
+
 int orl_mbrcsl_rollout(orl_engine* h, orl_dynamics* d, orl_traj* store, const float* init_obs, int32_t n_traj, int32_t length, int32_t term_kind,
                        int32_t penalty_mode, float penalty_coef, const float* eps, int32_t lag, int64_t* rows, double* reward_sum,
                        double* returns_host, int32_t* steps_enqueued, float* elapsed_ms) {

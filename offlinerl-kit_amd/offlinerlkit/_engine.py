@@ -62,6 +62,8 @@ ABI_SYMBOLS = [
     "orl_engine_adv_advantage", "orl_rambo_update_dynamics",
     # MOBILE: next-state samples of the dynamics, their hand-over to the policy engine, compute_lcb alone
     "orl_dynsample_next", "orl_engine_set_next_samples", "orl_engine_lcb_penalty",
+    # ... whole MOBILE steps as one device loop around both objects, and the sample call counter it advances
+    "orl_mobile_learn_n", "orl_dynsample_calls",
     # RCSL: one ordered pass over the attached buffer
     "orl_learn_epoch",
     # the autoregressive behaviour policy: sequential sampling
@@ -305,6 +307,7 @@ def load_library(path: Optional[str] = None):
     lib.orl_engine_lcb_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_adv_advantage.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_rambo_update_dynamics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OrlRamboLoop), C.c_void_p, C.POINTER(C.c_float)]
+    lib.orl_mobile_learn_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_mbrcsl_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                        C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_float)]
@@ -379,6 +382,8 @@ def _bind_dynamics(lib) -> None:
     lib.orl_dynadv_adam_get.argtypes = [P, C.c_int, VP, VP, I64, C.POINTER(C.c_int64)]
     lib.orl_dynadv_adam_set.argtypes = [P, C.c_int, VP, VP, I64, I64]
     lib.orl_dynsample_next.argtypes = [P, VP, VP, I64, C.c_int32, C.c_int, VP, VP]
+    lib.orl_dynsample_calls.argtypes = [P]
+    lib.orl_dynsample_calls.restype = I64
 
 
 def _bind_diffusion(lib) -> None:
@@ -829,6 +834,15 @@ class Engine(_Handle):
                                            C.byref(rows), C.byref(rs), returns.ctypes.data, C.byref(enq), C.byref(ms)), "orl_mbrcsl_rollout")
         store.n_traj = int(n_traj)
         return int(rows.value), float(rs.value), returns, int(enq.value), ms.value
+
+    def mobile_learn_n(self, dyn: "Dynamics", n_steps: int):
+        """``n_steps`` whole MOBILE steps as one device loop (orl_mobile_learn_n): every step draws its batch from the attached dataset
+        buffer and model ring, takes the next-state samples of the drawn rows from ``dyn`` in place and runs the update.  Returns
+        (mean metrics [n_runs][n_metrics], elapsed ms); one host synchronisation."""
+        m = np.zeros((self.n_runs, MAX_METRICS), dtype=np.float32)
+        ms = C.c_float()
+        self._check_step(self.lib.orl_mobile_learn_n(self._h, dyn._h, int(n_steps), m.ctypes.data, C.byref(ms)), "orl_mobile_learn_n")
+        return m[:, :len(self.metric_names)], ms.value
 
     def learn_n(self, n_steps: int):
         m = np.zeros((self.n_runs, MAX_METRICS), dtype=np.float32)
@@ -1497,6 +1511,13 @@ class Dynamics(_Handle):
         _check(self.lib.orl_dynsample_next(self._h, o.ctypes.data, a.ctypes.data, n, S, 0, None if nz is None else nz.ctypes.data,
                                            out.ctypes.data), "orl_dynsample_next")
         return out
+
+    def sample_calls(self) -> int:
+        """the sample call counter (orl_dynsample_calls): calls of ``sample_next*`` plus steps of ``Engine.mobile_learn_n``"""
+        n = int(self.lib.orl_dynsample_calls(self._h))
+        if n < 0:
+            raise RuntimeError(f"orl_dynsample_calls failed: {last_error()}")
+        return n
 
     def sample_next_device(self, obs, act, num_samples: int, noise=None):
         """``sample_next`` on contiguous fp32 torch tensors of the engine's device (noise too, when given); nothing visits the host"""

@@ -18,10 +18,10 @@ from .td3bc import TD3BCPolicy
 from .model_based import SACPolicy, MOPOPolicy, COMBOPolicy
 from .mcq import MCQPolicy
 from .rambo import RAMBOPolicy, rambo_adv_schedule
-from .mobile import MOBILEPolicy
+from .mobile import MOBILEDevicePolicy, MOBILEPolicy
 from .rcsl import RcslPolicy, RcslGaussianPolicy
 from .autoregressive import AutoregressivePolicy
 from .diffusion import DiffusionBC
 
 __all__ = ["BasePolicy", "EnginePolicy", "CQLPolicy", "IQLPolicy", "TD3BCPolicy", "EDACPolicy", "SACPolicy", "MOPOPolicy", "COMBOPolicy", "MCQPolicy",
-           "RAMBOPolicy", "MOBILEPolicy", "RcslPolicy", "RcslGaussianPolicy", "AutoregressivePolicy", "DiffusionBC"]
+           "RAMBOPolicy", "MOBILEPolicy", "MOBILEDevicePolicy", "RcslPolicy", "RcslGaussianPolicy", "AutoregressivePolicy", "DiffusionBC"]

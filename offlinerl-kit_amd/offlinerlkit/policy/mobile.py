@@ -9,8 +9,14 @@ One ``learn`` is three calls, and the next-state samples never visit the host be
      clamped target and one loss over both critics.
 ``compute_lcb`` is the penalty pass alone (``orl_engine_lcb_penalty``).
 
-Exactly two critics (``--num-q-ensemble``'s default) and one run per policy.  There is no ``learn_n`` / ``rollout_device``: every step
-needs the dynamics forward of its own batch, so ``MBPolicyTrainer(fused=True)`` refuses the policy and ``fused=False`` trains it.
+Exactly two critics (``--num-q-ensemble``'s default) and one run per policy.  ``MOBILEPolicy`` has no ``learn_n`` / ``rollout_device``:
+``MBPolicyTrainer(fused=True)`` refuses it and ``fused=False`` trains it through the three calls above.
+
+``MOBILEDevicePolicy`` is the same policy with the fused epoch: ``learn_n`` is ``orl_mobile_learn_n``, whole steps as one device loop on
+the engine's stream.  Each step draws its batch from the dataset buffer and the model ring as ``orl_learn_n`` does, runs the ensemble
+forward on the drawn rows and lets ``k_dyn_sample_rows`` write the ``S * E * B`` samples straight into the actor's and the target
+critics' input rows of the penalty pass (no sample array, no assemble launch; the same bits as calls 1-2), then the launches of call 3.
+One host synchronisation per ``learn_n``.  ``rollout_device`` is MOPO's device rollout.
 """
 from __future__ import annotations
 
@@ -22,7 +28,7 @@ import torch.nn as nn
 
 from .. import _engine
 from .base_policy import _backbone_dims, clone_target
-from .model_based import _cat, _rollout
+from .model_based import _cat, _rollout, _rollout_device_any
 from .sac_family import _TanhGaussPolicy
 
 
@@ -150,3 +156,44 @@ class MOBILEPolicy(_TanhGaussPolicy):
 
     def rollout(self, init_obss: np.ndarray, rollout_length: int):
         return _rollout(self, init_obss, rollout_length, False)
+
+
+class MOBILEDevicePolicy(MOBILEPolicy):
+    """``MOBILEPolicy`` with the fused epoch of ``MBPolicyTrainer(fused=True)``: same constructor, ``state_dict``, ``learn``,
+    ``compute_lcb`` and ``rollout``; ``learn_n`` runs whole steps as one device loop (``orl_mobile_learn_n``) and ``rollout_device`` is
+    MOPO's device rollout (the reference's ``MOBILEPolicy.rollout`` is the same loop as MOPO's).  One run per policy, one model ring."""
+
+    def _one_ring(self, fake_buffer, what: str) -> None:
+        if isinstance(fake_buffer, (list, tuple)):
+            raise NotImplementedError(f"MOBILEDevicePolicy.{what}: one model ring (a sequence of per-run rings needs n_runs > 1, and "
+                                      "MOBILE trains one run per policy object)")
+        if int(getattr(self.dynamics, "_n_runs", 1)) != 1 or self._n_runs != 1:
+            raise NotImplementedError(f"MOBILEDevicePolicy.{what}: one run per policy and per dynamics ensemble (n_runs == 1)")
+
+    def rollout_device(self, real_buffer, fake_buffer, rollout_batch_size: int, rollout_length: int, init_obss=None) -> Dict:
+        """``rollout`` + ``fake_buffer.add_batch`` on the device (``MOPOPolicy.rollout_device``); returns the reference's rollout info"""
+        self._one_ring(fake_buffer, "rollout_device")
+        return _rollout_device_any(self, real_buffer, fake_buffer, rollout_batch_size, rollout_length, init_obss, False)
+
+    def learn_n(self, n_steps: int, real_buffer, fake_buffer=None, batch_size: int = 256, real_ratio: float = 0.05) -> Dict[str, float]:
+        """the inner loop of MBPolicyTrainer (mb_policy_trainer.py:78-90) as one device loop: rows [0, int(batch_size * real_ratio)) of
+        every minibatch from ``real_buffer``, the rest from ``fake_buffer``'s ring, the dynamics' next-state samples of the drawn rows
+        written straight into the penalty pass's operands; returns the per-key means"""
+        if real_buffer is None or fake_buffer is None:
+            raise NotImplementedError("MOBILEDevicePolicy mixes a real and a model-rollout buffer per batch: "
+                                      "learn_n(n_steps, real_buffer, fake_buffer, ...), or learn({'real': ..., 'fake': ...})")
+        self._one_ring(fake_buffer, "learn_n")
+        real_rows = int(batch_size * real_ratio)               # mb_policy_trainer.py:81-82
+        self._bind_layout(int(batch_size), real_rows)
+        real = real_buffer.device_buffer() if hasattr(real_buffer, "device_buffer") else real_buffer
+        model = fake_buffer.reserve_device() if hasattr(fake_buffer, "reserve_device") else fake_buffer
+        key = (real, model, real_rows)
+        if self._attached != key:
+            self._eng.attach_buffer(real)
+            self._eng.attach_model_buffer(model, real_rows)
+            self._attached = key
+        self._push_lrs()
+        dyn, _, _ = self.dynamics.loop_engine()
+        m, ms = self._eng.mobile_learn_n(dyn, int(n_steps))
+        self.last_learn_n_ms = ms
+        return self._result(m)

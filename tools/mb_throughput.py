@@ -24,7 +24,10 @@ over the windows; ``--blocks 5`` for medians of five).
 members, 5 elites, 10 samples: 12 800 penalty rows per step, batch 256 with 12 real rows, penalty_coef 1.5, deterministic backup) against
 a stock-torch restatement of the same step (mobile.py:130-196 with torch autograd and torch.optim.Adam on the same GPU, same batches), a
 warm-up of each and then alternating timed blocks; the figure is gradient steps per second.  It also prints the HIP-event split of one
-block into the penalty pass (the ``lcb`` launches of orl_profile_query) and the rest of the step."""
+block into the penalty pass (the ``lcb`` launches of orl_profile_query) and the rest of the step.  The third contestant is
+``MOBILEDevicePolicy.learn_n``: the same steps as one device loop (``orl_mobile_learn_n``; batches drawn on the device from the same
+dataset and the same model rows held in an HBM ring), one call per block, with the HIP-event time of the loop next to the wall time
+(``--blocks 5`` for medians of five)."""
 import argparse
 import json
 import os
@@ -40,7 +43,7 @@ from offlinerlkit.buffer import ReplayBuffer  # noqa: E402
 from offlinerlkit.dynamics import EnsembleDynamics  # noqa: E402
 from offlinerlkit.modules import ActorProb, Critic, EnsembleDynamicsModel, TanhDiagGaussian  # noqa: E402
 from offlinerlkit.nets import MLP  # noqa: E402
-from offlinerlkit.policy import COMBOPolicy, MOBILEPolicy, MOPOPolicy, RAMBOPolicy  # noqa: E402
+from offlinerlkit.policy import COMBOPolicy, MOBILEDevicePolicy, MOBILEPolicy, MOPOPolicy, RAMBOPolicy  # noqa: E402
 from offlinerlkit.policy_trainer import MBPolicyTrainer  # noqa: E402
 from offlinerlkit.utils.scaler import StandardScaler  # noqa: E402
 from offlinerlkit.utils.termination_fns import termination_fn_halfcheetah  # noqa: E402
@@ -333,13 +336,18 @@ def measure_mobile(ds, blocks, steps):
     half = len(ds["rewards"]) // 2
     fake = ReplayBuffer(half, (OD,), np.float32, AD, np.float32, device=DEV)      # model rows: any transitions do for the arithmetic
     fake.load_dataset({k: v[:half] for k, v in ds.items()})
+    ring = ReplayBuffer(half, (OD,), np.float32, AD, np.float32, device=DEV)      # the same model rows as the device loop's HBM ring
+    ring.reserve_device()
+    ring.add_batch(ds["observations"][:half], ds["next_observations"][:half], ds["actions"][:half], ds["rewards"][:half], ds["terminals"][:half])
     torch.manual_seed(1)
     adam = lambda m, lr: torch.optim.Adam(m.parameters(), lr=lr)
     mk_model = lambda: EnsembleDynamicsModel(OD, AD, DYN_HID, num_ensemble=K, num_elites=E, weight_decays=DECAYS, device=DEV)
-    model, tmodel = mk_model(), mk_model()
+    model, tmodel, dmodel = mk_model(), mk_model(), mk_model()
     tmodel.load_state_dict(model.state_dict())
+    dmodel.load_state_dict(model.state_dict())
     scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
     dyn = EnsembleDynamics(model, adam(model, 1e-3), scaler, termination_fn_halfcheetah)
+    ddyn = EnsembleDynamics(dmodel, adam(dmodel, 1e-3), StandardScaler(scaler.mu, scaler.std), termination_fn_halfcheetah)
     mk_actor = lambda: ActorProb(MLP(OD, [256, 256]), TanhDiagGaussian(256, AD, unbounded=True, conditioned_sigma=True), DEV)
     mk_critics = lambda: torch.nn.ModuleList([Critic(MLP(OD + AD, [256, 256]), DEV), Critic(MLP(OD + AD, [256, 256]), DEV)])
     actor, critics = mk_actor(), mk_critics()
@@ -350,6 +358,14 @@ def measure_mobile(ds, blocks, steps):
                        deterministic_backup=True)
     pol.set_engine_options(seed=3)
     pol.train()
+    dactor, dcritics = deepcopy(actor), deepcopy(critics)
+    dla = torch.zeros(1, requires_grad=True, device=DEV)
+    dpol = MOBILEDevicePolicy(ddyn, dactor, dcritics, adam(dactor, 1e-4), adam(dcritics, 3e-4), tau=tau, gamma=gamma,
+                              alpha=(-float(AD), dla, torch.optim.Adam([dla], lr=1e-4)), penalty_coef=coef, num_samples=S,
+                              deterministic_backup=True)
+    dpol.set_engine_options(seed=3)
+    dpol.train()
+    event_ms = []
     tla = torch.zeros(1, requires_grad=True, device=DEV)
 
     def actforward(o):
@@ -364,7 +380,10 @@ def measure_mobile(ds, blocks, steps):
     def block(name, n):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(n):
+        if name == "device":
+            last[name] = dpol.learn_n(n, real, ring, B, 0.05)
+            event_ms.append(float(dpol.last_learn_n_ms))
+        for _ in range(n if name != "device" else 0):
             rb, fb = real.sample(real_rows), fake.sample(B - real_rows)
             if name == "engine":
                 last[name] = pol.learn({"real": rb, "fake": fb})
@@ -374,10 +393,11 @@ def measure_mobile(ds, blocks, steps):
                                                 mix["terminals"], real_rows, S, coef, gamma, tau, -float(AD))
         torch.cuda.synchronize()
         return time.perf_counter() - t0
-    names = ("torch", "engine")
+    names = ("torch", "engine", "device")
     np.random.seed(0)
     torch.manual_seed(0)
     warm = {name: block(name, 100) for name in names}
+    del event_ms[:]
     secs = {name: [] for name in names}
     for _ in range(blocks):
         for name in names:
@@ -393,7 +413,12 @@ def measure_mobile(ds, blocks, steps):
     rest_ms = sum(r["total_ms"] for r in table if "lcb" not in r["name"]) / n_prof
     return dict(mode="mobile_learn", steps=steps, batch=B, real_rows=real_rows, num_samples=S, elites=E, penalty_rows=S * E * B,
                 warmup_seconds_100_steps=warm, seconds=secs, steps_per_s=sps, steps_per_s_mean={k: float(np.mean(v)) for k, v in sps.items()},
+                steps_per_s_median={k: float(np.median(v)) for k, v in sps.items()},
                 speedup=float(np.mean(sps["engine"]) / np.mean(sps["torch"])),
+                device_over_engine_median=float(np.median(sps["device"]) / np.median(sps["engine"])),
+                device_over_torch_median=float(np.median(sps["device"]) / np.median(sps["torch"])),
+                device_loop_event_ms=event_ms, device_loop_wall_ms=[1e3 * x for x in secs["device"]],
+                device_loop_event_over_wall_median=float(np.median(event_ms) / (1e3 * np.median(secs["device"]))),
                 engine_kernel_ms_per_step=dict(penalty_pass=pen_ms, rest=rest_ms),
                 penalty_launches={r["name"]: r["total_ms"] / n_prof for r in table if "lcb" in r["name"]},
                 last_losses={k: {a: float(b) for a, b in v.items()} for k, v in last.items()})
@@ -409,7 +434,7 @@ def main():
     ap.add_argument("--profile-block", action="store_true", help="a warm-up and one fused MOPO block only (for a kernel trace)")
     ap.add_argument("--rambo", action="store_true", help="RAMBO's update_dynamics (engine, host loop) against its stock-torch restatement and the device loop")
     ap.add_argument("--rambo-steps", type=int, default=1000)
-    ap.add_argument("--mobile", action="store_true", help="MOBILEPolicy.learn (engine, host loop) against its stock-torch restatement")
+    ap.add_argument("--mobile", action="store_true", help="MOBILEPolicy.learn (engine, host loop) against its stock-torch restatement and MOBILEDevicePolicy.learn_n (the device loop)")
     ap.add_argument("--mobile-steps", type=int, default=500)
     a = ap.parse_args()
     if not torch.cuda.is_available():
