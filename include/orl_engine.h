@@ -834,10 +834,20 @@ int orl_diffusion_learn_epoch(orl_diffusion* d, const int64_t* order, int64_t n_
  * act_out [n][act_dim]; every array is a device pointer when on_device.  One host synchronisation, at the end. */
 int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const float* init_noise, const int64_t* noise_idx,
                          int64_t noise_rows, const float* z, int on_device, float* act_out);
+/* The arithmetic of orl_diffusion_sample (orl_diffusion_config::precision stays the training arithmetic).  0, the default: the fp32
+ * MFMA launches.  1: every Linear of a pass on one fused split-fp16 kernel (x = hi + lo fp16 planes, three products, fp32
+ * accumulators) with GroupNorm, Mish and the FiLM / residual tail applied to the accumulators; the EMA block's weights are split
+ * into planes once and again after every change of the EMA (orl_diffusion_step / _learn_epoch, orl_diffusion_set(which = 1)).
+ * Refused: any other value, and at 1 a net with a GroupNorm group wider than 128 channels (what the kernel holds in one workgroup
+ * slab).  At 1 orl_diffusion_sample fails with a "range flag" error after a call in which an activation was not finite or reached
+ * |x| >= 32768, or while an EMA weight reaches |w| * 64 >= 65504; the next call starts with the activation flag clear. */
+int orl_diffusion_set_sample_precision(orl_diffusion* d, int32_t precision);
+int32_t orl_diffusion_sample_precision(orl_diffusion* d);
 /* test taps of the last step: "pred", "eps", "x_t", "t" (as floats), "gf" (the condition vector), "film", "loss", and the forward
  * activations it left in the training workspace: "e0" (the sinusoidal embedding), "mc" (Mish of the condition vector), "y1.<b>" and
  * "out.<b>" (block b of the layer table after its FiLM and at its output, b = 0 .. blocks - 1), "yf" (final_conv's GN + Mish); of the
- * last sample: "z" (the last noise drawn), "x".  Unknown names and a block index out of range are refused.  Returns the floats
+ * last sample: "z" (the last noise drawn), "x", and what its last pass (t = 0) left in the sampling workspace at either sample
+ * precision: "s.film", "s.y1.<b>", "s.out.<b>", "s.yf", "s.pred".  Unknown names and a block index out of range are refused.  Returns the floats
  * written, < 0 on error. */
 int64_t orl_diffusion_debug_read(orl_diffusion* d, const char* name, float* host, int64_t cap);
 int orl_diffusion_debug_grads(orl_diffusion* d, float* host, int64_t n_floats);   /* parameter gradient of the last step */

@@ -30,7 +30,8 @@ UNITS = {
     "gemm_inst_swish.hip": GEMM_H,
     "gemm_inst_leaky.hip": GEMM_H,
     "dynamics.hip": ["devobj.h", "reduce.h", "gemm.h", "rng.h", ABI],
-    "diffusion.hip": ["devobj.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
+    "diffusion.hip": ["devobj.h", "diffusion_fused.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
+    "diffusion_fused.hip": ["diffusion_fused.h", "reduce.h", "gemm.h"],
     "rnn_dynamics.hip": ["devobj.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
     "ws_fwd.hip": WS_H,
     "ws_dgrad.hip": WS_H,
@@ -45,10 +46,12 @@ UNITS = {
     "gemm_debug.hip": ["debug_tap.h", "devobj.h", "gemm.h", ABI],
 }
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
+# extra flags of single units.  diffusion_fused.hip: no packed fp32 vector instructions (v_pk_*_f32) in its kernels
+UNIT_FLAGS = {"diffusion_fused.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hash(files):
-    h = hashlib.sha256(" ".join(FLAGS).encode())
+    h = hashlib.sha256(" ".join(FLAGS + [f"{u}:{' '.join(x)}" for u, x in sorted(UNIT_FLAGS.items())]).encode())
     for f in files:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(f.encode() + b"\0" + fh.read())
@@ -80,7 +83,7 @@ def _compile(unit, hipcc, verbose, objdir=None, defines=()):
     stamp = obj + ".srchash"
     if os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read().strip() == want:
         return obj
-    cmd = [hipcc] + FLAGS + ["-D" + d for d in defines] + ["-c", os.path.join(CSRC, unit), "-o", obj]
+    cmd = [hipcc] + FLAGS + UNIT_FLAGS.get(unit, []) + ["-D" + d for d in defines] + ["-c", os.path.join(CSRC, unit), "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

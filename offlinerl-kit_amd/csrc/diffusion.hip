@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "devobj.h"
+#include "diffusion_fused.h"
 #include "reduce.h"
 #include "rng.h"
 #include "train_ops.h"
@@ -41,9 +42,8 @@ enum { DIFF_NJ = 8, DIFF_MAX_TERMS = 4 };
 enum { DIFF_FINAL_GROUPS = 8 };      // final_conv's Conv1dBlock is built without n_groups: always GroupNorm(8)
 enum { DIFF_TAG_T = 1u, DIFF_TAG_EPS = 2u, DIFF_TAG_Z = 3u };     // Philox streams: c3 = tag << 28 | high bits of the counter
 
-// nn.Mish: x tanh(softplus(x)), and what its backward needs
+// nn.Mish (diff_mish: diffusion_fused.h) and what its backward needs
 struct DiffMish { float y, dy; };
-__device__ __forceinline__ float diff_mish(float x) { return x * tanhf(softplus(x)); }
 __device__ __forceinline__ DiffMish diff_mish_grad(float x) {
   const float ts = tanhf(softplus(x));
   const float sg = 1.f / (1.f + expf(-x));
@@ -281,6 +281,10 @@ struct DiffWs {
   float* part = nullptr;
 };
 
+// one Linear of the EMA block as the fused kernel reads it: weight / bias offsets, [N][K], the plane pitch Kp and the planes' offset
+enum { DPL_S1 = 0, DPL_S2, DPL_FILM, DPL_F0, DPL_F1, DPL_BLOCK0 };     // DPL_BLOCK0 + 2 b: block b's [W0; Wr], + 1: its W1
+struct DiffPlane { long w, b; int N, K, Kp; long off; };
+
 struct orl_diffusion {
   orl_diffusion_config c;
   int od, ad, dsed, cond, N, B, G, nlev;
@@ -305,6 +309,12 @@ struct orl_diffusion {
   float *sObs = nullptr, *sX = nullptr, *sNoise = nullptr, *sZ = nullptr, *sZkeep = nullptr, *sOut = nullptr;
   long long* sIdx = nullptr;
   long last_sample_n = 0; int last_rows = 0;
+  // sample precision 1 (diffusion_fused.h): the EMA block's Linears as fp16 hi / lo planes, rebuilt when ema_gen has moved on
+  int sample_prec = 0;
+  uint64_t ema_gen = 1, planes_gen = 0;
+  std::vector<DiffPlane> plane_tab; long plane_halves = 0;
+  hx_t* planes = nullptr;          // [2][plane_halves]: hi, lo
+  unsigned int *dflags = nullptr, *hflags = nullptr;     // the range words on the device and their pinned host copy
   DevAllocs mem{"orl_diffusion"};
 };
 
@@ -403,6 +413,85 @@ static int diff_forward(orl_diffusion* d, DiffWs& w, float* base, int rows, cons
   nf.out = w.YF.p; nf.op = w.YF.pitch;
   DEV_LAUNCH(d->stream, k_diff_norm_fwd, dim3(rows), dim3(64 * DIFF_FINAL_GROUPS), 0, nf);
   return diff_fwd(d, base, w.YF, rows, d->f1w, d->f1b, d->start_dim, d->ad, w.PRED);
+}
+
+// ---- sample precision 1: the same pass on the fused split-fp16 kernel (diffusion_fused.h), 3 + 2 blocks + 2 launches ----
+static void diff_plane_table(orl_diffusion* d) {
+  d->plane_tab.clear(); d->plane_halves = 0;
+  auto add = [&](long w, long b, int N, int K) {
+    const DiffPlane p{w, b, N, K, (K + 31) & ~31, d->plane_halves};
+    d->plane_halves += (long)N * p.Kp;
+    d->plane_tab.push_back(p);
+  };
+  const int ds = d->dsed, sd = d->start_dim;
+  add(d->s1w, d->s1b, 4 * ds, ds); add(d->s2w, d->s2b, ds, 4 * ds); add(d->cw, d->cb, d->film_cols, d->cond);
+  add(d->f0w, d->f0b, sd, sd); add(d->f1w, d->f1b, d->ad, sd);
+  for (const DiffBlock& k : d->blocks) { add(k.w0, k.b0, k.res ? 2 * k.out : k.out, k.in); add(k.w1, k.b1, k.out, k.out); }
+}
+// the planes of the current EMA block: allocated at the first call, rebuilt when the EMA has changed since they were written
+static int diff_planes_ready(orl_diffusion* d) {
+  if (!d->planes) {
+    diff_plane_table(d);
+    if (d->mem.alloc(&d->planes, 2 * (size_t)d->plane_halves) || d->mem.alloc(&d->dflags, DFU_FLAGS)) return -1;
+    ORL_HIP(hipHostMalloc((void**)&d->hflags, sizeof(unsigned int) * DFU_FLAGS, hipHostMallocDefault));
+  }
+  if (d->planes_gen == d->ema_gen) return 0;
+  if (dfu_clear_flag(d->dflags, DFU_FLAG_W, d->stream) != hipSuccess) return fail("orl_diffusion: k_diff_clear_flag: launch failed");
+  for (const DiffPlane& p : d->plane_tab)
+    if (dfu_split_weights(d->ema + p.w, p.N, p.K, p.Kp, d->planes + p.off, d->planes + d->plane_halves + p.off, d->dflags, d->stream) != hipSuccess)
+      return fail("orl_diffusion: k_diff_split_weights: launch failed");
+  d->planes_gen = d->ema_gen;
+  return 0;
+}
+static DfuCols diff_cols(const DevMat& m) { return {m.p, m.pitch, 0, nullptr, 0}; }
+// Linear `idx` of the plane table on A; the caller adds the norm part and / or the plain columns' destination
+static DfuP diff_fused_p(orl_diffusion* d, int idx, int rows, const DfuCols& A) {
+  const DiffPlane& pl = d->plane_tab[idx];
+  DfuP p;
+  memset(&p, 0, sizeof(p));
+  p.rows = rows; p.K = pl.K; p.Kp = pl.Kp; p.N = pl.N; p.A = A;
+  p.Bh = d->planes + pl.off; p.Bl = p.Bh + d->plane_halves;
+  p.bias = d->ema + pl.b; p.flags = d->dflags;
+  return p;
+}
+static void diff_fused_norm(orl_diffusion* d, DfuP& p, int C, long noff, int groups, const DevMat& out) {
+  p.Cn = C; p.cg = C / groups;
+  p.gamma = d->ema + d->norm_off + noff; p.beta = p.gamma + C;
+  p.out = out.p; p.op = out.pitch;
+}
+static void diff_fused_plain(DfuP& p, float* out2, int pitch) { p.out2 = out2; p.o2p = pitch; }
+
+static int diff_forward_split(orl_diffusion* d, DiffWs& w, int rows, const DevMat& x) {
+  auto run = [&](const DfuP& p) { return gemm_done(dfu_launch(p, d->stream), "orl_diffusion fused forward"); };
+  DfuP p = diff_fused_p(d, DPL_S1, rows, diff_cols(w.E0));                 // M1 = Mish(E0 W^T + b): Z1 is not stored
+  p.plain_mish = 1; diff_fused_plain(p, w.M1.p, w.M1.pitch);
+  if (run(p)) return -1;
+  p = diff_fused_p(d, DPL_S2, rows, diff_cols(w.M1));
+  diff_fused_plain(p, w.GF.p, w.GF.pitch);
+  if (run(p)) return -1;
+  p = diff_fused_p(d, DPL_FILM, rows, diff_cols(w.GF));                    // FILM = Mish(GF) Wc^T + bc: MC is not stored
+  p.a_mish = 1; diff_fused_plain(p, w.FILM.p, w.FILM.pitch);
+  if (run(p)) return -1;
+  for (size_t b = 0; b < d->blocks.size(); ++b) {
+    const DiffBlock& k = d->blocks[b];
+    DfuCols X = diff_cols(k.src < 0 ? x : w.OUT[k.src]);
+    if (k.skip >= 0) { X.k0 = d->blocks[k.src].out; X.p1 = w.OUT[k.skip].p; X.s1 = w.OUT[k.skip].pitch; }      // [x | skip] in place
+    p = diff_fused_p(d, DPL_BLOCK0 + 2 * (int)b, rows, X);
+    diff_fused_norm(d, p, k.out, k.n0, d->G, w.Y1[b]);
+    p.film = w.FILM.p + k.film_col; p.fp = w.FILM.pitch;
+    if (k.res) diff_fused_plain(p, w.HR[b].p + k.out, w.HR[b].pitch);      // x Wr^T + br from the plain slabs of the same launch
+    if (run(p)) return -1;
+    p = diff_fused_p(d, DPL_BLOCK0 + 2 * (int)b + 1, rows, diff_cols(w.Y1[b]));
+    diff_fused_norm(d, p, k.out, k.n1, d->G, w.OUT[b]);
+    p.res = k.res ? diff_cols(w.HR[b].cols(k.out)) : X;
+    if (run(p)) return -1;
+  }
+  p = diff_fused_p(d, DPL_F0, rows, diff_cols(w.OUT[d->last_block]));
+  diff_fused_norm(d, p, d->start_dim, d->fn, DIFF_FINAL_GROUPS, w.YF);
+  if (run(p)) return -1;
+  p = diff_fused_p(d, DPL_F1, rows, diff_cols(w.YF));
+  diff_fused_plain(p, w.PRED.p, w.PRED.pitch);
+  return run(p);
 }
 
 // the gradient terms of a block's output: one per consumer (a column slice where the consumer read a concatenation)
@@ -509,6 +598,7 @@ static int diff_enqueue_step(orl_diffusion* d, const long long* idx, int rows, c
   DEV_LAUNCH(d->stream, k_diff_adam_ema, dim3(ew_grid(d->P)), dim3(256), 0, d->params, d->adam_m, d->adam_v, d->grads, d->ema, d->P, d->lr_tab,
               (long)d->kstep, bc1, (float)std::sqrt(bc2), d->c.adam_beta1, d->c.adam_beta2, d->c.adam_eps, (float)decay, (float)(1.0 - decay));
   d->kstep += 1;
+  d->ema_gen += 1;
   d->last_rows = rows;
   return 0;
 }
@@ -660,6 +750,7 @@ void orl_diffusion_destroy(orl_diffusion* d) {
   if (!d) return;
   if (d->stream) hipStreamSynchronize(d->stream);
   d->mem.free_all();
+  if (d->hflags) hipHostFree(d->hflags);
   if (d->stream) hipStreamDestroy(d->stream);
   delete d;
 }
@@ -677,6 +768,7 @@ static float* diff_block_of(orl_diffusion* d, int which) {
 int orl_diffusion_set(orl_diffusion* d, int which, const float* host, int64_t n) {
   if (!d || !host || !diff_block_of(d, which)) return fail("orl_diffusion_set: bad arguments");
   if (n != d->P) return fail("orl_diffusion_set: expected " + std::to_string(d->P) + " floats");
+  if (which == 1) d->ema_gen += 1;
   return block_from_host(d->stream, diff_block_of(d, which), host, d->P);
 }
 int orl_diffusion_get(orl_diffusion* d, int which, float* host, int64_t n) {
@@ -690,6 +782,22 @@ int orl_diffusion_set_step_count(orl_diffusion* d, int64_t k) {
   return 0;
 }
 int64_t orl_diffusion_step_count(orl_diffusion* d) { return d ? d->kstep : -1; }
+
+int orl_diffusion_set_sample_precision(orl_diffusion* d, int32_t precision) {
+  if (!d) return fail("orl_diffusion_set_sample_precision: null handle");
+  if (precision != 0 && precision != 1)
+    return fail("orl_diffusion_set_sample_precision: sample precision must be 0 (fp32 MFMA) or 1 (split fp16), got " + std::to_string(precision));
+  if (precision == 1) {
+    int widest = d->start_dim / DIFF_FINAL_GROUPS;
+    for (const DiffBlock& k : d->blocks) widest = std::max(widest, k.out / d->G);
+    if (widest > ORL_DIFF_FUSED_MAX_GROUP)
+      return fail("orl_diffusion_set_sample_precision: a GroupNorm group of " + std::to_string(widest) + " channels is wider than the " +
+                  std::to_string(ORL_DIFF_FUSED_MAX_GROUP) + " the fused kernel holds in one workgroup slab");
+  }
+  d->sample_prec = precision;
+  return 0;
+}
+int32_t orl_diffusion_sample_precision(orl_diffusion* d) { return d ? d->sample_prec : -1; }
 
 int orl_diffusion_set_schedule(orl_diffusion* d, const float* acp, const float* coef) {
   if (!d || !acp || !coef) return fail("orl_diffusion_set_schedule: bad arguments");
@@ -775,6 +883,11 @@ int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const fl
       stage_in(d->stream, z_d, d->sZ, (size_t)N * n * ad, on_device) || stage_in(d->stream, nidx_d, d->sIdx, (size_t)n, on_device))
     return -1;
   DiffWs& w = d->sw;
+  const bool split = d->sample_prec == 1;
+  if (split) {
+    if (diff_planes_ready(d)) return -1;
+    if (dfu_clear_flag(d->dflags, DFU_FLAG_ACT, d->stream) != hipSuccess) return fail("orl_diffusion_sample: k_diff_clear_flag: launch failed");
+  }
   DevMat X; X.p = d->sX; X.pitch = X.lim = rup4(ad);
   DEV_LAUNCH(d->stream, k_diff_copy, dim3(ew_grid(n * ad)), dim3(256), 0, noise_d, ad, nidx_d, (long)noise_rows, X.p, X.pitch, (long)n, ad);
   for (int t = N - 1; t >= 0; --t) {
@@ -784,24 +897,37 @@ int orl_diffusion_sample(orl_diffusion* d, const float* obs, int64_t n, const fl
     ip.s_obs = obs_d; ip.t_const = t;
     ip.E0 = w.E0.p; ip.ep = w.E0.pitch; ip.GF = w.GF.p; ip.gp = w.GF.pitch;
     DEV_LAUNCH(d->stream, k_diff_input, dim3((unsigned)n), dim3(64), 0, ip);
-    if (diff_forward(d, w, d->ema, (int)n, X)) return -1;
+    if (split ? diff_forward_split(d, w, (int)n, X) : diff_forward(d, w, d->ema, (int)n, X)) return -1;
     DEV_LAUNCH(d->stream, k_diff_ddpm, dim3(ew_grid(n * ad)), dim3(256), 0, X.p, X.pitch, w.PRED.p, w.PRED.pitch, d->coef, t,
                 z_d ? z_d + (long)t * n * ad : (const float*)nullptr, d->sZkeep, (long)n, ad, d->c.seed, d->sample_calls * (uint64_t)N + (uint64_t)t);
   }
   float* dst = stage_dst(act_out, d->sOut, on_device);
   DEV_LAUNCH(d->stream, k_diff_copy, dim3(ew_grid(n * ad)), dim3(256), 0, X.p, X.pitch, (const long long*)nullptr, 0L, dst, ad, (long)n, ad);
   if (stage_out(d->stream, act_out, d->sOut, (size_t)n * ad, on_device)) return -1;
+  if (split) ORL_HIP(hipMemcpyAsync(d->hflags, d->dflags, sizeof(unsigned int) * DFU_FLAGS, hipMemcpyDeviceToHost, d->stream));
   ORL_HIP(hipStreamSynchronize(d->stream));
   d->sample_calls += 1;
   d->last_sample_n = n;
+  if (split && d->hflags[DFU_FLAG_W])
+    return fail("orl_diffusion_sample: sample precision 1 range flag: a weight of the EMA block is not finite or reaches |w| * 64 >= 65504");
+  if (split && d->hflags[DFU_FLAG_ACT])
+    return fail("orl_diffusion_sample: sample precision 1 range flag: an activation was not finite or reached |x| >= 32768");
   return 0;
 }
 
 int64_t orl_diffusion_debug_read(orl_diffusion* d, const char* name, float* host, int64_t cap) {
   if (!d || !name || !host) return fail("orl_diffusion_debug_read: bad arguments");
-  const std::string nm(name);
+  std::string nm(name);
   const float* src = nullptr; long rows = d->last_rows; int cols = 0, pitch = 0;
-  const DiffWs& w = d->tw;
+  const bool s_tap = nm.compare(0, 2, "s.") == 0;             // "s.<name>": the sampling workspace after the last pass (t = 0)
+  const DiffWs& w = s_tap ? d->sw : d->tw;
+  if (s_tap) {
+    nm = nm.substr(2);
+    rows = d->last_sample_n;
+    if (nm != "film" && nm != "yf" && nm != "pred" && nm.compare(0, 3, "y1.") != 0 && nm.compare(0, 4, "out.") != 0)
+      return fail("orl_diffusion_debug_read: unknown tap s." + nm);
+    if (rows < 1) return fail("orl_diffusion_debug_read: nothing recorded for s." + nm);
+  }
   if (nm == "pred") { src = w.PRED.p; cols = d->ad; pitch = w.PRED.pitch; }
   else if (nm == "x_t") { src = w.XT.p; cols = d->ad; pitch = w.XT.pitch; }
   else if (nm == "eps") { src = d->EPS; cols = d->ad; pitch = d->ad; }

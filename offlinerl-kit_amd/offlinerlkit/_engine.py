@@ -77,7 +77,8 @@ ABI_SYMBOLS = [
     "orl_diffusion_config_default", "orl_diffusion_create", "orl_diffusion_destroy", "orl_diffusion_floats", "orl_diffusion_num_tensors",
     "orl_diffusion_tensor", "orl_diffusion_set", "orl_diffusion_get", "orl_diffusion_set_step_count", "orl_diffusion_step_count",
     "orl_diffusion_set_schedule", "orl_diffusion_set_lr", "orl_diffusion_attach_buffer", "orl_diffusion_step", "orl_diffusion_learn_epoch",
-    "orl_diffusion_sample", "orl_diffusion_debug_read", "orl_diffusion_debug_grads",
+    "orl_diffusion_sample", "orl_diffusion_set_sample_precision", "orl_diffusion_sample_precision", "orl_diffusion_debug_read",
+    "orl_diffusion_debug_grads",
     # RNNDynamics: the GRU sequence dynamics model
     "orl_rnn_config_default", "orl_rnn_config_floats", "orl_rnn_create", "orl_rnn_destroy", "orl_rnn_floats", "orl_rnn_num_tensors",
     "orl_rnn_tensor", "orl_rnn_set", "orl_rnn_get", "orl_rnn_set_step_count", "orl_rnn_step_count", "orl_rnn_load_data", "orl_rnn_step",
@@ -408,6 +409,9 @@ def _bind_diffusion(lib) -> None:
     lib.orl_diffusion_step.argtypes = [P, VP, C.c_int32, VP, VP, C.POINTER(C.c_float)]
     lib.orl_diffusion_learn_epoch.argtypes = [P, VP, I64, C.c_int, VP]
     lib.orl_diffusion_sample.argtypes = [P, VP, I64, VP, VP, I64, VP, C.c_int, VP]
+    lib.orl_diffusion_set_sample_precision.argtypes = [P, C.c_int32]
+    lib.orl_diffusion_sample_precision.argtypes = [P]
+    lib.orl_diffusion_sample_precision.restype = C.c_int32
     lib.orl_diffusion_debug_read.argtypes = [P, C.c_char_p, VP, I64]
     lib.orl_diffusion_debug_read.restype = I64
     lib.orl_diffusion_debug_grads.argtypes = [P, VP, I64]
@@ -1705,9 +1709,17 @@ class Diffusion(_FlatBlocks, _Handle):
                                              None if z is None else z.ctypes.data, 0, out.ctypes.data), "orl_diffusion_sample")
         return out
 
+    def set_sample_precision(self, p: int):
+        """the arithmetic of ``sample``: 0 the fp32 launches (default), 1 the fused split-fp16 kernel; training is unaffected"""
+        _check(self.lib.orl_diffusion_set_sample_precision(self._h, int(p)), "orl_diffusion_set_sample_precision")
+
+    @property
+    def sample_precision(self) -> int:
+        return int(self.lib.orl_diffusion_sample_precision(self._h))
+
     def debug_read(self, name: str, cap: int = 1 << 22) -> np.ndarray:
         """a test tap as a flat array.  Of the last step: pred, eps, x_t, t, gf, film, loss, e0, mc, y1.<b> / out.<b> (block b), yf;
-        of the last sample: z, x"""
+        of the last sample: z, x, and of its last pass s.film, s.y1.<b>, s.out.<b>, s.yf, s.pred"""
         return _read_tap(self.lib.orl_diffusion_debug_read, f"orl_diffusion_debug_read({name!r})", name, cap, self._h)
 
 

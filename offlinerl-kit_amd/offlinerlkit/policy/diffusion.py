@@ -118,6 +118,7 @@ class DiffusionBC:
         self.start_epoch = 0
         self._eng: Optional[_engine.Diffusion] = None
         self._ema_sd = None             # the EMA weights as a state_dict (after train() or load_checkpoint(final=True))
+        self._sample_precision = 0
 
     # -- engine ------------------------------------------------------------------------------
     def _torch_device(self) -> torch.device:
@@ -138,6 +139,7 @@ class DiffusionBC:
             eng = _engine.Diffusion(cfg)
             eng.set_schedule(self.alphas_cumprod, self.ddpm_coef)
             eng.set_lr(self.lr_table)
+            eng.set_sample_precision(self._sample_precision)
             self._table = eng.tensors()
             self._eng = eng
             flat = self.pack(self.noise_pred_net.state_dict())
@@ -201,6 +203,16 @@ class DiffusionBC:
         self._ema_sd = self.ema_noise_pred_net.state_dict()
 
     # -- sampling ----------------------------------------------------------------------------
+    def set_sample_precision(self, p: int) -> None:
+        """0 (default): ``select_action`` on the fp32 launches; 1: on the fused split-fp16 kernel (fp16 hi + lo planes, fp32
+        accumulators; an activation beyond +-32768 makes the call raise).  Usable before or after the engine exists; training is
+        unaffected."""
+        if int(p) not in (0, 1):
+            raise ValueError(f"DiffusionBC.set_sample_precision: 0 or 1, got {p!r}")
+        if self._eng is not None:
+            self._eng.set_sample_precision(int(p))
+        self._sample_precision = int(p)
+
     def sample_init_noise(self, batch: int = 1) -> torch.Tensor:
         return torch.randn((batch, 1, self.act_dim), device=self._torch_device())
 

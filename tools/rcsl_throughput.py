@@ -28,7 +28,11 @@ figures from one run: (1) one training epoch over ``--rows`` rows (orl_diffusion
 project's own ``ConditionalUnet1D`` on the same GPU (steps per second); (2) ``select_action`` on 256 rows (orl_diffusion_sample: 10
 forward-only passes) against the same DDPM loop in torch on that module (calls per second); (3) ``RcslPolicy.rollout_device`` with the
 frozen noise in HBM against the host ``rollout()`` (transitions per second; ``--trajectories`` x ``--horizon``).  Writes
-profiles/diffusion_throughput.json unless --out names another file."""
+profiles/diffusion_throughput.json unless --out names another file.
+``--diffusion --split``: the sampler alone at sample precision 0 (the fp32 launches) and 1 (the fused split-fp16 kernel,
+csrc/diffusion_fused.hip) on one policy object, alternating windows in one run: ``select_action_device`` on 256 rows (calls per second)
+and ``rollout_device`` of ``--trajectories`` x ``--horizon`` (transitions per second); medians of ``--blocks`` windows after a warm-up
+of each.  Writes profiles/diffusion_sample_split_throughput.json unless --out names another file."""
 import argparse
 import json
 import os
@@ -359,6 +363,65 @@ def measure_diffusion(rows, blocks, sample_calls, n_traj, horizon):
     return dict(training_epoch=train, select_action=sampling, rollout=rollout)
 
 
+def measure_diffusion_split(blocks, sample_calls, n_traj, horizon):
+    from offlinerlkit.dynamics import EnsembleDynamics
+    from offlinerlkit.modules import EnsembleDynamicsModel
+    from offlinerlkit.policy import DiffusionBC
+    from offlinerlkit.utils.diffusion_logger import Logger
+    from offlinerlkit.utils.scaler import StandardScaler
+    from offlinerlkit.utils.termination_fns import termination_fn_default
+
+    class Cfg:
+        act_dim, obs_dim, num_epochs, num_diffusion_iters, batch_size, save_ckpt_freq = AD, OD, 1, 10, B, 10 ** 9
+        device, path, num_workers, spectral_norm = DEV, None, 1, False
+    ds = dataset(1024)
+    torch.manual_seed(0)
+    bc = DiffusionBC(Cfg(), (ds["observations"], ds["actions"]), Logger(None))
+    o256 = torch.as_tensor(ds["observations"][:256], device=DEV).contiguous()
+    noise = bc.sample_init_noise(256)
+    torch.manual_seed(1)
+    model = EnsembleDynamicsModel(OD, AD, HID, num_ensemble=7, num_elites=5, weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=DEV)
+    scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
+    dyn = EnsembleDynamics(model, torch.optim.Adam(model.parameters(), lr=1e-3), scaler, termination_fn_default)
+    dyn.set_engine_options(seed=3)
+    mod = make_module(False)
+    pol = RcslPolicy(dyn, bc, mod, torch.optim.Adam(mod.parameters(), lr=LR), DEV)
+    init = np.random.default_rng(0).normal(size=(n_traj, OD)).astype(np.float32)
+    store = _engine.TrajStore(OD, AD, n_traj, n_traj * horizon, 0)
+
+    def sample(prec):
+        bc.set_sample_precision(prec)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(sample_calls):
+            act = bc.select_action_device(o256, noise)
+        torch.cuda.synchronize()
+        return sample_calls / (time.perf_counter() - t0), act
+
+    def rollout(prec):
+        bc.set_sample_precision(prec)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, info = pol.rollout_device(init, horizon, store=store)
+        torch.cuda.synchronize()
+        return info["num_transitions"] / (time.perf_counter() - t0)
+    a0, a1 = sample(0)[1], sample(1)[1]                     # warm-up; the two precisions on the same inputs and z stream position differ
+    s0, s1, r0, r1 = [], [], [], []
+    for _ in range(blocks):
+        s0.append(sample(0)[0]); s1.append(sample(1)[0])
+    rollout(0); rollout(1)
+    for _ in range(blocks):
+        r0.append(rollout(0)); r1.append(rollout(1))
+    med = lambda v: float(np.median(v))
+    return dict(select_action=dict(rows=256, calls_per_window=sample_calls, precision0_calls_per_s=s0, precision1_calls_per_s=s1,
+                                   precision0_median=med(s0), precision1_median=med(s1), speedup=med(s1) / med(s0),
+                                   ranges_disjoint=bool(min(s1) > max(s0) or min(s0) > max(s1)),
+                                   actions_finite=bool(torch.isfinite(a0).all() and torch.isfinite(a1).all())),
+                rollout_device=dict(trajectories=n_traj, horizon=horizon, precision0_transitions_per_s=r0, precision1_transitions_per_s=r1,
+                                    precision0_median=med(r0), precision1_median=med(r1), speedup=med(r1) / med(r0),
+                                    ranges_disjoint=bool(min(r1) > max(r0) or min(r0) > max(r1))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000)
@@ -372,7 +435,17 @@ def main():
     ap.add_argument("--horizon", type=int, default=1000)
     ap.add_argument("--out", default=None)
     ap.add_argument("--diffusion", action="store_true", help="DiffusionBC at the default shape: a training epoch, select_action on 256 rows, the rollout")
+    ap.add_argument("--split", action="store_true", help="with --diffusion: the sampler alone at sample precision 0 and 1 (fused split-fp16 kernel)")
     a = ap.parse_args()
+    if a.diffusion and a.split:
+        res = dict(policy="DiffusionBC", stage="sampling at sample precision 0 (fp32 launches) and 1 (fused split-fp16 kernel)",
+                   shape=dict(obs_dim=OD, act_dim=AD, down_dims=[256, 512, 1024], step_embed_dim=256, n_groups=8, num_diffusion_iters=10),
+                   device=torch.cuda.get_device_name(0), blocks=a.blocks,
+                   result=measure_diffusion_split(a.blocks, a.sample_calls, a.trajectories, a.horizon))
+        print(json.dumps(res))
+        with open(a.out or os.path.join(ROOT, "profiles", "diffusion_sample_split_throughput.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if a.diffusion:
         res = dict(policy="DiffusionBC", shape=dict(obs_dim=OD, act_dim=AD, down_dims=[256, 512, 1024], step_embed_dim=256, kernel_size=5,
                                                     n_groups=8, num_diffusion_iters=10, batch=B),
