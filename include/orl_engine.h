@@ -595,7 +595,14 @@ int orl_profile_query(orl_engine* e, int idx, char* name, int name_cap, double* 
  * host array has a leading run dimension.  Parameters per run, in the reference's state_dict order (orl_dyn_tensor): max_logvar,
  * min_logvar, then backbones.{i}.{weight,bias,saved_weight,saved_bias} and output_layer.* (weights (K, in, out), biases (K, 1, out));
  * each tensor starts on a 16-byte boundary of the flat per-run block.  `elites` (int64 in the reference) lives outside the fp32 block
- * (orl_dyn_set_elites / orl_dyn_get_elites).  Only precision 0 (fp32 MFMA) is implemented. */
+ * (orl_dyn_set_elites / orl_dyn_get_elites).
+ * precision 0: fp32 MFMA everywhere.  precision 1: split-fp16 inference calls and fp32 training -- the forward of orl_dyn_step,
+ * orl_dynsample_next and of the device loops that enqueue them runs on one fused kernel with fp16 hi + lo operand planes
+ * (csrc/dynamics_fused.hip; every layer at most 512 wide, else refused), while orl_dyn_learn_epoch, orl_dyn_validate and orl_dynadv_*
+ * stay the precision-0 arithmetic bit for bit, so a training trace does not depend on the option.  At precision 1 a scaled input or
+ * hidden activation that is not finite or reaches 32768, or a weight with |w| * 64 >= 65504, raises a sticky device word; orl_dyn_step,
+ * orl_dynsample_next, orl_dyn_sync and the device loops read the words at their synchronisation, fail with "range flag" in the
+ * message and clear them.  precision 2 is refused. */
 typedef struct orl_dyn_config {
   int32_t obs_dim, act_dim;
   int32_t n_hidden;                 /* <= ORL_MAX_HIDDEN */

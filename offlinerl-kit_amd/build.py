@@ -29,7 +29,8 @@ UNITS = {
     "gemm_inst_tune.hip": GEMM_H,
     "gemm_inst_swish.hip": GEMM_H,
     "gemm_inst_leaky.hip": GEMM_H,
-    "dynamics.hip": ["devobj.h", "reduce.h", "gemm.h", "rng.h", ABI],
+    "dynamics.hip": ["devobj.h", "dynamics_fused.h", "reduce.h", "gemm.h", "rng.h", ABI],
+    "dynamics_fused.hip": ["dynamics_fused.h", "gemm.h", ABI],
     "diffusion.hip": ["devobj.h", "diffusion_fused.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
     "diffusion_fused.hip": ["diffusion_fused.h", "reduce.h", "gemm.h"],
     "rnn_dynamics.hip": ["devobj.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],

@@ -141,7 +141,7 @@ int Engine::mbrcsl_loop(orl_dynamics* d, const DynStepInfo& di, orl_traj* store,
   };
   const int rc = loop.end(body(), F, elapsed_ms);      // the one unconditional host synchronisation (also on an error path)
   if (steps_enqueued) *steps_enqueued = enq;
-  if (rc) return -1;
+  if (rc || dynstep_loop_end(d, F)) return -1;
   return orl_traj_finish(store, rows, reward_sum, returns_host);
 }
 

@@ -124,7 +124,7 @@ int Engine::mobile_loop(orl_dynamics* d, const DynSampleInfo& di, int n_steps, f
   mobile_rows_in_place = true;
   const int rc = loop.end(body(), F, elapsed_ms);      // the one host synchronisation (also on an error path: the launches made so far ran)
   mobile_rows_in_place = false;
-  if (rc) return -1;
+  if (rc || dynstep_loop_end(d, F)) return -1;
   return finish(metrics_sum, (float)n_steps, metrics_mean, done);      // (a non-finite metric of ANY of the steps stays in its sum)
 }
 

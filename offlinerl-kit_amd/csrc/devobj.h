@@ -57,10 +57,12 @@ int traj_append_enqueue(orl_traj* t, hipStream_t stream, int term_kind, const fl
 
 // orl_dyn_step (dynamics.hip) as the same loop drives it under a DynStreamLease: device rows in, next_obs / reward out, no staging and
 // no synchronisation.  loop_begin (before the lease, on the object's own stream) grows the step workspaces for n_max rows, every
-// enqueue advances the call counter as orl_dyn_step does.
+// enqueue advances the call counter as orl_dyn_step does.  loop_end (after the loop's final synchronisation; the MOBILE loop below ends
+// with it too) refuses with the range flag of a precision-1 ensemble that one of the enqueued forwards raised, and clears it.
 struct DynStepInfo { int dev, R, od, ad; bool with_reward; hipStream_t stream; };
 int dynstep_info(orl_dynamics* d, DynStepInfo* out);
 int dynstep_loop_begin(orl_dynamics* d, long n_max);
+int dynstep_loop_end(orl_dynamics* d, const char* who);
 int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n, int mode, float coef, float* next_obs, float* reward);
 
 // orl_dynsample_next (dynamics.hip) as the MOBILE device loop drives it under a DynStreamLease (algo_mobile.inc: Engine::mobile_loop):

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "devobj.h"
+#include "dynamics_fused.h"
 #include "reduce.h"
 #include "rng.h"
 
@@ -722,6 +723,11 @@ struct orl_dynamics {
   float *sNext = nullptr, *sRew = nullptr, *sRaw = nullptr, *sPen = nullptr;
   int *sIdx = nullptr, *sMidx = nullptr, *sMidxOut = nullptr;
   uint64_t step_calls = 0;
+  // precision 1 (dynamics_fused.h): the fused forward's geometry, the weight planes (hi, then lo; packed anew by every forward-only
+  // call) and the range words on the device with their pinned host copy
+  DyfP fused;
+  hx_t* planes = nullptr;
+  unsigned int *dflags = nullptr, *hflags = nullptr;
   // MOBILE's samples (orl_dynsample_next): its own call counter, host-noise staging and host-output staging, grown on demand
   uint64_t sample_calls = 0;
   long m_cap = 0;
@@ -842,6 +848,35 @@ static int dyn_forward(orl_dynamics* d, const DynWs& w, int rows, bool keep_z) {
   return dyn_fwd(d, X, rows, d->L, dyn_mat(d, w, w.OUT, d->L + 1), nullptr, false);
 }
 
+// The forward of a forward-only call -- step, sample_next and the device loops' enqueues -- over the first `rows` rows of the step
+// workspace: dyn_forward, or at precision 1 the pack launch and the fused launch (dynamics_fused.h) from the same X into the same OUT.
+// The planes are packed by every call: the parameter block may be aliased and written from torch, so nothing here can know when a kept
+// copy is stale.  Training, validation and the adversarial update do not come here: they are exact fp32 at either precision.
+static int dyn_forward_only(orl_dynamics* d, long rows) {
+  if (d->c.precision == 0) return dyn_forward(d, d->sw, (int)rows, false);
+  DyfP p = d->fused;
+  p.X = d->sw.X; p.n = rows; p.OUT = d->sw.OUT;
+  if (dyf_pack(p, d->stream) != hipSuccess) return fail("orl_dyn: k_dyn_pack_planes: launch failed");
+  if (dyf_forward(p, d->stream) != hipSuccess) return fail("orl_dyn: k_dyn_fused_fwd: launch failed");
+  return 0;
+}
+
+// The range words of precision 1, read by every call that synchronises after a forward-only pass: enqueue() copies them to the host on
+// the stream before the synchronisation, check() after it refuses with "range flag" and clears both words -- a weight that is still out
+// of range raises its word again at the next pack.
+static int dyn_flags_enqueue(orl_dynamics* d) {
+  if (d->dflags) ORL_HIP(hipMemcpyAsync(d->hflags, d->dflags, sizeof(unsigned int) * DYF_FLAGS, hipMemcpyDeviceToHost, d->stream));
+  return 0;
+}
+static int dyn_flags_check(orl_dynamics* d, const char* who) {
+  if (!d->dflags || !(d->hflags[DYF_FLAG_ACT] | d->hflags[DYF_FLAG_W])) return 0;
+  const bool w = d->hflags[DYF_FLAG_W] != 0;
+  d->hflags[DYF_FLAG_ACT] = d->hflags[DYF_FLAG_W] = 0u;
+  ORL_HIP(hipMemcpy(d->dflags, d->hflags, sizeof(unsigned int) * DYF_FLAGS, hipMemcpyHostToDevice));
+  return fail(std::string(who) + (w ? ": precision 1 range flag: a weight of the ensemble is not finite or reaches |w| * 64 >= 65504"
+                                    : ": precision 1 range flag: a scaled input or a hidden activation was not finite or reached |x| >= 32768"));
+}
+
 // backward from dOUT, top down: weight / bias gradients into the gradient block, input gradients alternating between dA and dB
 static int dyn_backward(orl_dynamics* d, const DynWs& w, int rows) {
   DevMat dY = dyn_mat(d, w, w.dOUT, d->L + 1);
@@ -956,8 +991,16 @@ int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out) {
     return fail("orl_dyn_create: need 1 <= num_elites <= num_ensemble <= 64");
   if (c.obs_dim + (c.with_reward ? 1 : 0) > DYN_MAXD) return fail("orl_dyn_create: obs_dim + with_reward must be <= 64");
   for (int i = 0; i < c.n_hidden; ++i) if (c.hidden[i] < 1) return fail("orl_dyn_create: bad hidden width");
-  if (c.precision != 0)
-    return fail("orl_dyn_create: the dynamics ensemble implements precision 0 (fp32 MFMA) only; precision 1 / 2 are not supported");
+  if (c.precision != 0 && c.precision != 1)
+    return fail("orl_dyn_create: the dynamics ensemble implements precision 0 (fp32 MFMA) and 1 (split-fp16 step / sample_next); "
+                "precision 2 is not supported");
+  if (c.precision == 1) {
+    int wmax = std::max(c.obs_dim + c.act_dim, 2 * (c.obs_dim + (c.with_reward ? 1 : 0)));
+    for (int i = 0; i < c.n_hidden; ++i) wmax = std::max(wmax, (int)c.hidden[i]);
+    if (wmax > ORL_DYN_FUSED_MAX_WIDTH)
+      return fail("orl_dyn_create: precision 1 takes layers (input, hidden, output) of at most " + std::to_string(ORL_DYN_FUSED_MAX_WIDTH) +
+                  " columns, got " + std::to_string(wmax));
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("orl_dyn_create: no HIP device (MI355X) visible");
   if (c.device < 0 || c.device >= ndev) return fail("orl_dyn_create: device ordinal out of range");
@@ -981,6 +1024,21 @@ int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out) {
         d->mem.alloc(&d->sd, R * d->in) || dyn_ws_alloc(d, d->lw, B, false) || d->mem.alloc(&d->T, R * K * B * d->D) ||
         d->mem.alloc(&d->decay_part, R * d->nblk) || d->mem.alloc(&d->nll, R) || d->mem.alloc(&d->loss_sum, R) ||
         d->mem.alloc(&d->active_d, R) || d->mem.alloc(&d->t0_d, R);
+  if (c.precision == 1 && !bad) {
+    DyfP& f = d->fused;
+    memset(&f, 0, sizeof(f));
+    f.R = d->R; f.K = d->K; f.nl = d->L + 1;
+    for (int l = 0; l <= d->L + 1; ++l) f.width[l] = d->width[l];
+    for (int l = 0; l <= d->L; ++l) { f.w_off[l] = d->w_off[l]; f.b_off[l] = d->b_off[l]; }
+    const long halves = dyf_layout(f);
+    bad = d->mem.alloc(&d->planes, 2 * (size_t)halves) || d->mem.alloc(&d->dflags, DYF_FLAGS) ||
+          hipHostMalloc((void**)&d->hflags, sizeof(unsigned int) * DYF_FLAGS, hipHostMallocDefault) != hipSuccess;
+    if (!bad) d->hflags[DYF_FLAG_ACT] = d->hflags[DYF_FLAG_W] = 0u;
+    f.params = d->params; f.P = d->P;
+    f.Bh = d->planes; f.Bl = d->planes + halves;
+    f.xp = d->pitch[0]; f.op = d->pitch[d->L + 1];
+    f.flags = d->dflags;
+  }
   if (bad) {
     const std::string msg = orl_last_error();
     orl_dyn_destroy(d);
@@ -1010,13 +1068,15 @@ void orl_dyn_destroy(orl_dynamics* d) {
   if (!d) return;
   if (d->stream) hipStreamSynchronize(d->stream);
   d->mem.free_all();
+  if (d->hflags) hipHostFree(d->hflags);
   if (d->stream) hipStreamDestroy(d->stream);
   delete d;
 }
 
 int orl_dyn_sync(orl_dynamics* d) {
+  if (dyn_flags_enqueue(d)) return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
-  return 0;
+  return dyn_flags_check(d, "orl_dyn_sync");
 }
 
 int64_t orl_dyn_floats(orl_dynamics* d) { return d ? d->P : -1; }
@@ -1226,7 +1286,7 @@ static int dyn_step_forward(orl_dynamics* d, const float* obs, const float* act,
   DEV_LAUNCH(d->stream, k_dyn_step_input, dim3((unsigned)((n + 255) / 256), d->R), dim3(256), 0, obs, act, n, d->od, d->ad,
               (const float*)d->mu, (const float*)d->sd, d->sw.X, d->pitch[0]);
   d->sw.rows = n;
-  return dyn_forward(d, d->sw, (int)n, false);
+  return dyn_forward_only(d, n);
 }
 
 // the launches of a step on device rows: k_dyn_step_input, the ensemble's forward, k_dyn_head; the call counter advances.  orl_dyn_step
@@ -1272,9 +1332,10 @@ int orl_dyn_step(orl_dynamics* d, const float* obs, const float* act, int64_t n,
       stage_out(d->stream, raw_reward, d->sRaw, (size_t)R * n, on_device) || stage_out(d->stream, penalty, d->sPen, (size_t)R * n, on_device) ||
       stage_out(d->stream, (int*)midx_out, d->sMidxOut, (size_t)R * n, on_device))
     return -1;
+  if (dyn_flags_enqueue(d)) return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
   d->tap_step_rows = n; d->tap_step_t = false;
-  return 0;
+  return dyn_flags_check(d, "orl_dyn_step");
 }
 
 // ---- MOBILE's next-state samples ----
@@ -1319,9 +1380,10 @@ int orl_dynsample_next(orl_dynamics* d, const float* obs, const float* act, int6
   const long nt = rows * ((D + 3) / 4);
   DEV_LAUNCH(d->stream, k_dyn_sample_next, dim3((unsigned)((nt + 255) / 256), R), dim3(256), 0, p);
   if (stage_out(d->stream, next_obs, d->mNext, (size_t)R * rows * od, on_device)) return -1;
+  if (dyn_flags_enqueue(d)) return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
   d->tap_step_rows = n; d->tap_step_t = false;
-  return 0;
+  return dyn_flags_check(d, "orl_dynsample_next");
 }
 
 int64_t orl_dynsample_calls(orl_dynamics* d) {
@@ -1622,6 +1684,12 @@ int dynstep_info(orl_dynamics* d, DynStepInfo* o) {
 // (before the lease: growing waits for the object's own stream)
 int dynstep_loop_begin(orl_dynamics* d, long n_max) { return dyn_grow_step(d, n_max); }
 
+// (after the loop's own synchronisation: a blocking read of the words the enqueued forwards may have raised)
+int dynstep_loop_end(orl_dynamics* d, const char* who) {
+  if (d->dflags) ORL_HIP(hipMemcpy(d->hflags, d->dflags, sizeof(unsigned int) * DYF_FLAGS, hipMemcpyDeviceToHost));
+  return dyn_flags_check(d, who);
+}
+
 // (the raw reward and the penalty land in the step workspace, as they do for a host caller of orl_dyn_step)
 int dynstep_enqueue(orl_dynamics* d, const float* obs, const float* act, long n, int mode, float coef, float* next_obs, float* reward) {
   if (dyn_step_launches(d, obs, act, n, nullptr, nullptr, mode, coef, next_obs, reward, d->sRaw, d->sPen, nullptr, "orl_mbrcsl_rollout")) return -1;
@@ -1649,7 +1717,7 @@ int dynsample_enqueue(orl_dynamics* d, const DynSampleRows& a, const char* who) 
   DEV_LAUNCH(d->stream, k_dyn_step_input_rows, dim3((unsigned)((n + 255) / 256), d->R), dim3(256), 0, a.obs, a.obs_rs, a.obs_pitch, a.act,
              a.act_rs, a.act_pitch, n, d->od, d->ad, (const float*)d->mu, (const float*)d->sd, d->sw.X, d->pitch[0]);
   d->sw.rows = n;
-  if (dyn_forward(d, d->sw, (int)n, false)) return -1;
+  if (dyn_forward_only(d, n)) return -1;
   DynSampleRowsP p;
   memset(&p, 0, sizeof(p));
   p.OUT = d->sw.OUT; p.op = d->pitch[d->L + 1];

@@ -1368,6 +1368,11 @@ class Dynamics(_Handle):
         self.P = int(self.lib.orl_dyn_floats(self._h))
         self.tensors = _read_tensors(self.lib.orl_dyn_num_tensors, self.lib.orl_dyn_tensor, self._h, what="orl_dyn_tensor")
 
+    @property
+    def precision(self) -> int:
+        """0: fp32 MFMA; 1: ``step`` / ``sample_next`` on the fused split-fp16 forward, training and validation in fp32"""
+        return int(self.cfg.precision)
+
     def sync(self):
         _check(self.lib.orl_dyn_sync(self._h), "orl_dyn_sync")
 

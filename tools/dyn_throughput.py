@@ -2,7 +2,8 @@
 """Dynamics-ensemble throughput at the MOPO halfcheetah shape (17 / 6, [200] x 4, 7 members, batch 256): learn() minibatch steps/s of
 the HIP engine (orl_dyn_learn_epoch) at n_runs 1 and 8, rollout rows/s of step() at 50 000 rows, and the same two measured on a stock
 torch implementation written here (bmm EnsembleLinear forward, autograd, torch.optim.Adam, loss.item() per minibatch as the
-reference's learn() does).  Prints one JSON object; --out writes it too."""
+reference's learn() does).  Prints one JSON object; --out writes it too.
+--split: step() on device tensors at precision 0 (fp32 GEMM per layer) against precision 1 (the fused split-fp16 forward) instead."""
 import argparse
 import json
 import os
@@ -65,6 +66,58 @@ def engine_step(rows, reps):
     return dict(rows=rows, seconds=dt / reps, rows_per_s=rows * reps / dt)
 
 
+def fused_tile(rows):
+    """rows per workgroup of k_dyn_fused_fwd at this shape (dyf_pick_tile: widest Kp 224, 4 fragments per wave): the largest of 64 / 32
+    whose two LDS planes fit 64 KB and that still gives 256 workgroups, else 16"""
+    for rt in (64, 32):
+        if 4 * rt * (224 + 8) <= 65536 and -(-rows // rt) * K >= 256:
+            return rt
+    return 16
+
+
+def split_step(rows_list, windows=5, window_s=0.4, only=None):
+    """step() on device tensors at precision 0 and 1, two objects of this build timed in alternating windows; every call ends in the
+    engine's own synchronise.  Medians of `windows` windows per precision and row count.  only = (precision, rows): that one engine in a
+    plain loop, for a kernel trace."""
+    torch.manual_seed(0)
+    m = EnsembleDynamicsModel(OD, AD, HID, K, E, weight_decays=DECAYS)
+    p = {k: v.detach().numpy() for k, v in m.state_dict().items() if k != "elites"}
+    engs = {}
+    for prec in ((0, 1) if only is None else (only[0],)):
+        engs[prec] = eng = _engine.Dynamics(_engine.default_dyn_config(precision=prec))
+        eng.set_params(0, p)
+        eng.set_scaler(0, np.zeros(OD + AD, np.float32), np.ones(OD + AD, np.float32))
+    dev = torch.device("cuda", 0)
+    out = []
+    for rows in rows_list if only is None else (only[1],):
+        g = torch.Generator(device=dev).manual_seed(rows)
+        obs = torch.randn(1, rows, OD, device=dev, generator=g)
+        act = torch.rand(1, rows, AD, device=dev, generator=g) * 2 - 1
+
+        def window(eng, reps):
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                eng.step_device(obs, act, "aleatoric", 2.5)
+            return (time.perf_counter() - t0) / reps
+        for eng in engs.values():
+            window(eng, 5)                                  # warm-up: code objects, workspaces grown to this row count
+        if only is not None:
+            window(engs[only[0]], 200)
+            continue
+        reps = {prec: max(10, int(window_s / window(eng, 10))) for prec, eng in engs.items()}
+        t = {0: [], 1: []}
+        for _ in range(windows):
+            for prec, eng in engs.items():
+                t[prec].append(window(eng, reps[prec]))
+        med = {prec: float(np.median(v)) for prec, v in t.items()}
+        out.append(dict(rows=rows, fused_rows_per_workgroup=fused_tile(rows), reps_per_window=reps, windows=windows,
+                        p0_ms=med[0] * 1e3, p1_ms=med[1] * 1e3, p0_ms_windows=[x * 1e3 for x in t[0]], p1_ms_windows=[x * 1e3 for x in t[1]],
+                        p0_rows_per_s=rows / med[0], p1_rows_per_s=rows / med[1], p1_over_p0_speed=med[0] / med[1]))
+    for eng in engs.values():
+        eng.close()
+    return out
+
+
 def torch_learn(batches):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -125,9 +178,27 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--profile-epoch", action="store_true", help="one n_runs = 1 epoch of 50 minibatches only (for a kernel trace)")
+    ap.add_argument("--split", action="store_true", help="step() on device tensors at precision 0 against precision 1 (256, 12 800 and "
+                    "50 000 rows); --out defaults to profiles/dyn_step_split_throughput.json")
+    ap.add_argument("--split-trace", type=int, nargs=2, metavar=("PRECISION", "ROWS"), default=None,
+                    help="with --split: 200 steps of one precision at one row count only (for a kernel trace: the pack launch's share)")
     a = ap.parse_args()
     if a.profile_epoch:
         print(json.dumps(engine_learn(1, 256 * 50, 1)))
+        return
+    if a.split:
+        if a.split_trace:
+            split_step((), only=tuple(a.split_trace))
+            return
+        res = {"shape": dict(obs=OD, act=AD, hidden=HID, members=K), "device": torch.cuda.get_device_name(0),
+               "what": "orl_dyn_step on device tensors, ms per call incl. its synchronise: medians of alternating windows",
+               "step": split_step((256, 12800, 50000))}
+        s = json.dumps(res, indent=1)
+        print(s)
+        out = a.out or os.path.join(ROOT, "profiles", "dyn_step_split_throughput.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write(s + "\n")
         return
     res = {"shape": dict(obs=OD, act=AD, hidden=HID, members=K, batch=B), "device": torch.cuda.get_device_name(0),
            "engine_learn": [engine_learn(1, a.train_size, a.epochs), engine_learn(8, a.train_size, a.epochs)],
