@@ -988,6 +988,21 @@ int orl_rnn_state_step(orl_rnn* d, const float* obs, const float* act, const int
                        float* reward);
 int orl_rnn_state_set(orl_rnn* d, int run, int layer, const float* host, int64_t n_traj);
 
+/* The arithmetic of the forward-only window pass: orl_rnn_forward, orl_rnn_forward_runs and orl_rnn_state_prime
+ * (orl_rnn_config::precision stays 0, the training arithmetic).  0, the default: the fp32 MFMA launches, bit for bit as before.
+ * 1: the GRU layers on two launches of csrc/rnn_fused.hip -- k_rnn_pack_planes splits [W_ih | W_hh] * 64 of every layer into fp16 hi /
+ * lo planes on every call (nothing is cached: the parameter block can be an external_arena that torch writes), k_rnn_fused_fwd takes a
+ * 16 / 32 / 64-sequence tile through every layer and every time step in one workgroup (three products per split operand pair, fp32
+ * accumulators, h as two fp16 planes in LDS); the tail keeps its fp32 launches.  Refused: any other value, and at 1 a shape whose
+ * 16-sequence tile does not fit 160 KB of LDS (H = 512 with 4 layers fits).  orl_rnn_step*, orl_rnn_learn_epoch* and
+ * orl_rnn_state_step stay fp32 bit for bit at either setting (the one-step cell spreads 256 rows over 16 x 13 workgroups, which the
+ * fused kernel cannot match).  At 1 the three calls fail with a "range flag" error after a pass in which an input (an activation of
+ * layer 0; hidden states lie in [-1, 1]) was not finite or reached |x| >= 32768, or while a GRU weight is not finite or reaches
+ * |w| * 64 >= 65504; both words are cleared by the report.  Taps after a pass at 1: "gi.<l>", and "gru.<l>" below the top layer, are
+ * refused (they never reach memory); "x0", the top layer's "gru.<L-1>", the tail's names, "pred" and "state.<l>" stay readable. */
+int orl_rnn_set_eval_precision(orl_rnn* d, int32_t precision);
+int32_t orl_rnn_eval_precision(orl_rnn* d);
+
 #ifdef __cplusplus
 }
 #endif

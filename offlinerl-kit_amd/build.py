@@ -33,7 +33,8 @@ UNITS = {
     "dynamics_fused.hip": ["dynamics_fused.h", "gemm.h", ABI],
     "diffusion.hip": ["devobj.h", "diffusion_fused.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
     "diffusion_fused.hip": ["diffusion_fused.h", "reduce.h", "gemm.h"],
-    "rnn_dynamics.hip": ["devobj.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
+    "rnn_dynamics.hip": ["devobj.h", "rnn_fused.h", "dynamics_fused.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
+    "rnn_fused.hip": ["rnn_fused.h", "dynamics_fused.h", "gemm.h", ABI],
     "ws_fwd.hip": WS_H,
     "ws_dgrad.hip": WS_H,
     "ws_fwd3.hip": WS_H,

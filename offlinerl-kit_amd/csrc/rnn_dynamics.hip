@@ -29,6 +29,11 @@
 //   the tail           the window forward's own (rnn_tail), on n rows
 //   k_rnn_roll_head    next_obs = pred[:, :-1] + obs, reward = pred[:, -1]
 // O(1) per model step at any horizon; no atomics here either.
+//
+// Eval precision 1 (orl_rnn_set_eval_precision, rnn_fused.h): the GRU layers of a forward-only window pass -- orl_rnn_forward,
+// orl_rnn_forward_runs, orl_rnn_state_prime -- are two launches, k_rnn_pack_planes and k_rnn_fused_fwd (split fp16, every layer and
+// step of a row tile in one workgroup); the tail is unchanged.  Training and orl_rnn_state_step stay fp32 at either setting: at 256 rows
+// k_rnn_cell spreads over 16 x 13 workgroups, which a kernel that keeps a row tile's whole stack in one workgroup cannot match.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +45,7 @@
 #include "devobj.h"
 #include "reduce.h"
 #include "rng.h"
+#include "rnn_fused.h"
 #include "train_ops.h"
 
 namespace orl {
@@ -53,7 +59,6 @@ enum { RNN_MAX_H = 512, RNN_MAX_LAYERS = 4, RNN_MAX_NORMS = ORL_MAX_HIDDEN + 1 }
 enum { RNN_NJ = RNN_MAX_H / 64 };     // LayerNorm: values of a row per lane
 enum { RNN_CHUNK = 64 };              // rows of a first-level column sum
 
-__device__ __forceinline__ float rnn_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 // Swish'(z) = sigmoid(z) (1 + z (1 - sigmoid(z))) on the library exp and a true division
 __device__ __forceinline__ float rnn_dswish(float z) { const float s = rnn_sigmoid(z); return s * (1.f + z * (1.f - s)); }
 
@@ -641,6 +646,13 @@ struct orl_rnn {
   // what the taps read: the workspace of the last pass, its rows, and the runs it held (run last_r0 + i at workspace slot i); last_roll:
   // that pass was a state step (no input projections kept, the roll.* names readable)
   const RnnWs* last_ws = nullptr; long last_rows = 0; int last_r0 = 0, last_nr = 0; bool last_roll = false;
+  // orl_rnn_set_eval_precision: 1 runs the GRU stack of the window forward on rnn_fused.h.  The weight planes (hi, then lo; packed anew
+  // by every such forward), the range words on the device and their pinned host copy; last_fused: the last pass was such a forward (no
+  // input projections and no lower-layer h_t to tap)
+  int eval_prec = 0, cus = 0;
+  hx_t* planes = nullptr; long plane_halves = 0;
+  unsigned int *dflags = nullptr, *hflags = nullptr;
+  bool last_fused = false;
   // the carried state (orl_rnn_state_*): st[0], st[1] [R][L][n_traj][H], side [R][n_traj] (k_rnn_cell says how they take turns); the
   // input scaler [in] each; a step's host arrays staged as obs | act | next_obs | reward, and its trajectory indices
   float* st[2] = {nullptr, nullptr}; int* side = nullptr; long n_traj = 0;
@@ -773,11 +785,30 @@ static RnnNormP rnn_norm_params(orl_rnn* d, const RnnRuns& rs, const RnnWs& w, i
 }
 
 // the GRU layers of the runs rs over `rows` sequences of T steps from h = 0: per layer the input projections of every step in one
-// product, then the scan.  X0: the input rows; layer l's h_t goes to w.HO[l]
-static int rnn_gru_windows(orl_rnn* d, const RnnRuns& rs, RnnWs& w, const DevMat& X0, int rows, int T, bool train) {
+// product, then the scan.  X0: the input rows; layer l's h_t goes to w.HO[l].  A forward-only pass at eval precision 1 is the pack
+// launch and the fused launch of rnn_fused.h instead: only the top layer's h_t reaches w.HO, and with prime (all runs) every layer's
+// h_{T-1} goes to slots 0 .. rows - 1 of both state buffers
+static int rnn_gru_windows(orl_rnn* d, const RnnRuns& rs, RnnWs& w, const DevMat& X0, int rows, int T, bool train, bool prime) {
   const int H = d->H;
   const long N = (long)rows * T;
   float* params = rnn_params_of(d, rs);
+  if (!train && d->eval_prec == 1) {
+    RnfP p;
+    memset(&p, 0, sizeof(p));
+    p.L = d->L; p.H = H; p.in = d->in; p.rows = rows; p.T = T; p.cus = d->cus;
+    rnf_layout(p);
+    p.params = params; p.P = d->P;
+    for (int l = 0; l < d->L; ++l) { p.wih[l] = d->wih[l].w; p.whh[l] = d->whh[l].w; p.bih[l] = d->wih[l].b; p.bhh[l] = d->whh[l].b; }
+    p.Bh = d->planes; p.Bl = d->planes + d->plane_halves;
+    p.X0 = X0.p; p.xp = X0.pitch; p.x_rs = X0.s0;
+    const DevMat& top = w.HO[d->L - 1];
+    p.HO = top.p; p.hop = top.pitch; p.ho_rs = top.s0;
+    if (prime) { p.st[0] = d->st[0]; p.st[1] = d->st[1]; p.st_rs = (long)d->L * d->n_traj * H; p.n_traj = d->n_traj; }
+    p.flags = d->dflags;
+    if (rnf_pack(p, rs.n, d->stream) != hipSuccess) return fail("orl_rnn: k_rnn_pack_planes: launch failed");
+    if (rnf_forward(p, rs.n, d->stream) != hipSuccess) return fail("orl_rnn: k_rnn_fused_fwd: launch failed");
+    return 0;
+  }
   DevMat X = X0;
   for (int l = 0; l < d->L; ++l) {
     if (rnn_fwd(d, rs, X, (int)N, d->wih[l], l ? H : d->in, 3 * H, w.GI[l], false, nullptr)) return -1;
@@ -822,10 +853,10 @@ static int rnn_tail(orl_rnn* d, const RnnRuns& rs, RnnWs& w, const DevMat& X0, l
 
 // the forward of the runs rs over `rows` sequences of T steps of workspace w (X0 in place; shared_x: every run reads slot 0's X0); train:
 // the scans save what the backward reads, the pre-activations are kept and the dropouts read the keep masks of w.MK
-static int rnn_forward(orl_rnn* d, const RnnRuns& rs, RnnWs& w, int rows, int T, bool train, bool shared_x) {
+static int rnn_forward(orl_rnn* d, const RnnRuns& rs, RnnWs& w, int rows, int T, bool train, bool shared_x, bool prime = false) {
   DevMat X0 = w.X0;
   if (shared_x) X0.s0 = 0;
-  return rnn_gru_windows(d, rs, w, X0, rows, T, train) || rnn_tail(d, rs, w, X0, (long)rows * T, train) ? -1 : 0;
+  return rnn_gru_windows(d, rs, w, X0, rows, T, train, prime) || rnn_tail(d, rs, w, X0, (long)rows * T, train) ? -1 : 0;
 }
 
 // backward of every run from dPRED over the first rows * T rows of the training workspace
@@ -930,7 +961,7 @@ static int rnn_enqueue_step(orl_rnn* d, const long long* idx, long idx_rs, int r
   rnn_mark(d, true, 3);
   d->prof_valid = d->prof;
   d->kstep += 1;
-  d->last_ws = &w; d->last_rows = N; d->last_r0 = 0; d->last_nr = R; d->last_roll = false;
+  d->last_ws = &w; d->last_rows = N; d->last_r0 = 0; d->last_nr = R; d->last_roll = false; d->last_fused = false;
   return 0;
 }
 
@@ -1060,6 +1091,7 @@ void orl_rnn_destroy(orl_rnn* d) {
   for (hipEvent_t e : d->ev)
     if (e) hipEventDestroy(e);
   d->mem.free_all();
+  if (d->hflags) hipHostFree(d->hflags);
   if (d->stream) hipStreamDestroy(d->stream);
   delete d;
 }
@@ -1105,6 +1137,31 @@ int orl_rnn_get(orl_rnn* d, int which, float* host, int64_t n) {
   if (n != d->P) return fail("orl_rnn_get: expected " + std::to_string(d->P) + " floats");
   return orl_rnn_get_run(d, 0, which, host, n);
 }
+int orl_rnn_set_eval_precision(orl_rnn* d, int32_t precision) {
+  if (rnn_ready(d, "orl_rnn_set_eval_precision", false)) return -1;
+  if (precision != 0 && precision != 1)
+    return fail("orl_rnn_set_eval_precision: eval precision must be 0 (fp32 MFMA) or 1 (split fp16), got " + std::to_string(precision));
+  ORL_HIP(hipStreamSynchronize(d->stream));
+  if (precision == 1 && !d->hflags) {
+    RnfP p;
+    memset(&p, 0, sizeof(p));
+    p.L = d->L; p.H = d->H; p.in = d->in;
+    d->plane_halves = (long)d->R * rnf_layout(p);
+    if (rnf_lds_bytes(p, 16) > RNF_LDS_BYTES)
+      return fail("orl_rnn_set_eval_precision: k_rnn_fused_fwd: the planes of a 16-row tile at this shape (" + std::to_string(rnf_lds_bytes(p, 16)) +
+                  " bytes) do not fit the " + std::to_string((int)RNF_LDS_BYTES) + " bytes of LDS");
+    hipDeviceProp_t prop;
+    ORL_HIP(hipGetDeviceProperties(&prop, d->c.device));
+    d->cus = prop.multiProcessorCount;
+    if ((!d->planes && d->mem.alloc(&d->planes, 2 * (size_t)d->plane_halves)) || (!d->dflags && d->mem.alloc(&d->dflags, RNF_FLAGS))) return -1;
+    ORL_HIP(hipHostMalloc((void**)&d->hflags, sizeof(unsigned int) * RNF_FLAGS, hipHostMallocDefault));
+    d->hflags[RNF_FLAG_ACT] = d->hflags[RNF_FLAG_W] = 0u;
+  }
+  d->eval_prec = precision;
+  return 0;
+}
+int32_t orl_rnn_eval_precision(orl_rnn* d) { return d ? d->eval_prec : -1; }
+
 int orl_rnn_set_step_count(orl_rnn* d, int64_t k) {
   if (!d || k < 0) return fail("orl_rnn_set_step_count: bad arguments");
   d->kstep = k;
@@ -1192,7 +1249,7 @@ static int rnn_eval_ws(orl_rnn* d, long N, int runs) {
   return 0;
 }
 // the eval forward of the runs rs over the windows inputs [n][T][in] (one array when shared or one run, else one per run), enqueued
-static int rnn_eval_windows(orl_rnn* d, const RnnRuns& rs, const float* inputs, int64_t n, int32_t T, int on_device, int shared) {
+static int rnn_eval_windows(orl_rnn* d, const RnnRuns& rs, const float* inputs, int64_t n, int32_t T, int on_device, int shared, bool prime = false) {
   const int n_in = (shared || rs.n == 1) ? 1 : rs.n;     // input arrays
   const long N = (long)n * T;
   if (rnn_eval_ws(d, N, rs.n)) return -1;
@@ -1200,7 +1257,24 @@ static int rnn_eval_windows(orl_rnn* d, const RnnRuns& rs, const float* inputs, 
   const float* in_d = inputs;
   if (stage_in(d->stream, in_d, d->fIn, (size_t)n_in * N * d->in, on_device)) return -1;
   DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid(N * d->in), n_in), dim3(256), 0, in_d, d->in, N * d->in, w.X0.p, w.X0.pitch, w.X0.s0, N, d->in, 1);
-  return rnn_forward(d, rs, w, (int)n, T, false, n_in < rs.n);
+  return rnn_forward(d, rs, w, (int)n, T, false, n_in < rs.n, prime);
+}
+
+// The range words of eval precision 1, read by the calls that synchronise after a fused forward: rnn_flags_enqueue copies them to the
+// host on the stream before the synchronisation, rnn_flags_check after it refuses with "range flag" and clears both words -- a weight
+// that is still out of range raises its word again in the next call's pack launch.
+static int rnn_flags_enqueue(orl_rnn* d) {
+  if (d->eval_prec == 1) ORL_HIP(hipMemcpyAsync(d->hflags, d->dflags, sizeof(unsigned int) * RNF_FLAGS, hipMemcpyDeviceToHost, d->stream));
+  return 0;
+}
+static int rnn_flags_check(orl_rnn* d, const char* who) {
+  if (d->eval_prec != 1 || !(d->hflags[RNF_FLAG_ACT] | d->hflags[RNF_FLAG_W])) return 0;
+  const bool w = d->hflags[RNF_FLAG_W] != 0;
+  d->hflags[RNF_FLAG_ACT] = d->hflags[RNF_FLAG_W] = 0u;
+  ORL_HIP(hipMemcpy(d->dflags, d->hflags, sizeof(unsigned int) * RNF_FLAGS, hipMemcpyHostToDevice));
+  d->last_ws = nullptr;
+  return fail(std::string(who) + (w ? ": eval precision 1 range flag: a GRU weight is not finite or reaches |w| * 64 >= 65504"
+                                    : ": eval precision 1 range flag: an activation (a scaled input) was not finite or reached |x| >= 32768"));
 }
 
 // orl_rnn_forward / orl_rnn_forward_runs: run >= 0 that run alone, -1 every run (inputs shared or [R][n][T][in])
@@ -1225,8 +1299,10 @@ static int rnn_forward_runs(orl_rnn* d, const char* what, const float* inputs, i
                 N * d->od, N, d->od, 1);
     if (stage_out(d->stream, out_all, d->fAll, (size_t)rs.n * N * d->od, on_device)) return -1;
   }
+  if (rnn_flags_enqueue(d)) return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
-  d->last_ws = &w; d->last_rows = N; d->last_r0 = rs.r0; d->last_nr = rs.n; d->last_roll = false;
+  if (rnn_flags_check(d, what)) return -1;
+  d->last_ws = &w; d->last_rows = N; d->last_r0 = rs.r0; d->last_nr = rs.n; d->last_roll = false; d->last_fused = d->eval_prec == 1;
   return 0;
 }
 int orl_rnn_forward(orl_rnn* d, const float* inputs, int64_t n, int32_t T, int on_device, float* out_last, float* out_all) {
@@ -1297,15 +1373,17 @@ int orl_rnn_state_prime(orl_rnn* d, const float* inputs, int64_t n, int32_t T, i
   if (T < 1 || T > d->Tmax) return fail("orl_rnn_state_prime: need 1 <= T <= max_seq_len (" + std::to_string(d->Tmax) + ")");
   if (n > 0x7fffffffL / ((int64_t)T * 8 * d->H)) return fail("orl_rnn_state_prime: too many sequences for one call");
   const RnnRuns rs{0, d->R};
-  if (rnn_eval_windows(d, rs, inputs, n, T, on_device, shared_inputs)) return -1;
+  if (rnn_eval_windows(d, rs, inputs, n, T, on_device, shared_inputs, true)) return -1;
   const RnnWs& w = d->ew;
   const long st_rs = (long)d->L * d->n_traj * d->H;
-  for (int l = 0; l < d->L; ++l)
+  for (int l = 0; l < d->L && d->eval_prec == 0; ++l)     // (at eval precision 1 the fused kernel has stored them)
     for (int s = 0; s < 2; ++s)                           // slots 0 .. n - 1 of both buffers <- row b T + T - 1 of the layer's h
       DEV_LAUNCH(d->stream, k_rnn_copy, dim3(ew_grid((long)n * d->H), rs.n), dim3(256), 0, (const float*)w.HO[l].p, w.HO[l].pitch, w.HO[l].s0,
                  rnn_state_at(d, s, 0, l), d->H, st_rs, (long)n, d->H, (int)T);
+  if (rnn_flags_enqueue(d)) return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
-  d->last_ws = &w; d->last_rows = (long)n * T; d->last_r0 = 0; d->last_nr = rs.n; d->last_roll = false;
+  if (rnn_flags_check(d, "orl_rnn_state_prime")) return -1;
+  d->last_ws = &w; d->last_rows = (long)n * T; d->last_r0 = 0; d->last_nr = rs.n; d->last_roll = false; d->last_fused = d->eval_prec == 1;
   return 0;
 }
 
@@ -1369,7 +1447,7 @@ int orl_rnn_state_step(orl_rnn* d, const float* obs, const float* act, const int
   if (stage_out(d->stream, next_obs, d->r_stage + no + na, no, on_device) || stage_out(d->stream, reward, d->r_stage + 2 * no + na, nr, on_device))
     return -1;
   ORL_HIP(hipStreamSynchronize(d->stream));
-  d->last_ws = &w; d->last_rows = (long)n; d->last_r0 = rs.r0; d->last_nr = rs.n; d->last_roll = true;
+  d->last_ws = &w; d->last_rows = (long)n; d->last_r0 = rs.r0; d->last_nr = rs.n; d->last_roll = true; d->last_fused = false;
   return 0;
 }
 
@@ -1406,12 +1484,17 @@ int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* hos
   const float* src = nullptr; long rows = d->last_rows, rs = 0; int cols = d->H, pitch = d->H;
   bool roll = false;                                          // a name of the one-step path
   const bool rolled = d->last_ws && d->last_roll;             // ... which the last pass was
+  const bool fused = d->last_ws && d->last_fused;             // the last pass ran the GRU stack on the fused kernel
   auto mat = [&](const DevMat& m) { src = m.p; pitch = m.pitch; rs = m.s0; };
   if (nm == "loss") { src = d->loss_cell + run; rows = 1; cols = 1; pitch = 1; }
   else if (nm == "pred") { mat(w->PRED); cols = d->od; }
   else if (nm == "in") mat(w->CAT);
   else if (nm == "merge") mat(w->M0);
-  else if ((k = rnn_tap_index(nm, "gru.", d->L)) >= 0) mat(w->HO[k]);
+  else if ((k = rnn_tap_index(nm, "gru.", d->L)) >= 0) {
+    if (fused && k < d->L - 1)
+      return fail("orl_rnn_debug_read: a forward at eval precision 1 keeps no " + nm + ": the fused kernel holds the lower layers' h in LDS");
+    mat(w->HO[k]);
+  }
   else if ((k = rnn_tap_index(nm, "block.", d->nb)) >= 0) mat(w->XO[k]);
   else if ((k = rnn_tap_index(nm, "act.", d->norms)) >= 0) mat(k ? w->SB[k - 1] : w->SI);
   else if ((k = rnn_tap_index(nm, "drop.", d->norms)) >= 0) mat(k ? w->UB[k - 1] : w->UI);
@@ -1421,6 +1504,7 @@ int64_t orl_rnn_debug_read_run(orl_rnn* d, int run, const char* name, float* hos
   }
   else if ((k = rnn_tap_index(nm, "gi.", d->L)) >= 0) {
     if (rolled) return fail("orl_rnn_debug_read: a state step keeps no input projections (" + nm + "): k_rnn_cell forms them in registers");
+    if (fused) return fail("orl_rnn_debug_read: a forward at eval precision 1 keeps no input projections (" + nm + "): k_rnn_fused_fwd forms them in registers");
     mat(w->GI[k]); cols = 3 * d->H;
   }
   else if (nm == "x0") { mat(w->X0); cols = d->in; }

@@ -90,6 +90,8 @@ ABI_SYMBOLS = [
     "orl_rnn_debug_keep",
     # ... and its carried GRU state: one model step at a time
     "orl_rnn_set_scaler", "orl_rnn_state_reset", "orl_rnn_state_prime", "orl_rnn_state_step", "orl_rnn_state_set",
+    # ... and the arithmetic of its window forward
+    "orl_rnn_set_eval_precision", "orl_rnn_eval_precision",
 ]
 ADV_METRICS = ("all_loss", "sl_loss", "adv_loss", "adv_log_prob")
 DYN_PENALTY = {"aleatoric": 0, "pairwise-diff": 1, "ensemble_std": 2}
@@ -456,6 +458,9 @@ def _bind_rnn(lib) -> None:
     lib.orl_rnn_state_prime.argtypes = [P, VP, I64, C.c_int32, C.c_int, C.c_int]
     lib.orl_rnn_state_step.argtypes = [P, VP, VP, VP, I64, C.c_int, C.c_int, VP, VP]
     lib.orl_rnn_state_set.argtypes = [P, C.c_int, C.c_int, VP, I64]
+    lib.orl_rnn_set_eval_precision.argtypes = [P, C.c_int32]
+    lib.orl_rnn_eval_precision.argtypes = [P]
+    lib.orl_rnn_eval_precision.restype = C.c_int32
     lib.orl_rnn_profile.argtypes = [P, C.c_int]
     lib.orl_rnn_profile_read.argtypes = [P, C.POINTER(C.c_float)]
 
@@ -1772,6 +1777,15 @@ class RnnDynamicsEngine(_FlatBlocks, _Handle):
         self.floats = int(self.lib.orl_rnn_floats(self._h))
         self.n_runs = int(cfg.n_runs)
         self.T = 0
+
+    def set_eval_precision(self, p: int):
+        """arithmetic of ``forward`` / ``forward_runs`` / ``state_prime``: 0 the fp32 MFMA launches (default), 1 the fused split-fp16
+        GRU-stack kernel; training and ``state_step`` are fp32 at either setting"""
+        _check(self.lib.orl_rnn_set_eval_precision(self._h, int(p)), "orl_rnn_set_eval_precision")
+
+    @property
+    def eval_precision(self) -> int:
+        return int(self.lib.orl_rnn_eval_precision(self._h))
 
     def set_params(self, params: Dict, run: int = 0):
         self.set(self.PARAMS, _flatten(self.tensors(), params, self.floats), run)

@@ -615,6 +615,7 @@ class RNNDynamics(BaseDynamics):
         self._arena = None
         self._shape = None              # (batch_size, max_seq_len) the engine was built for
         self._state_n: Optional[int] = None     # trajectories of the carried state (reset_state), None: no state
+        self._eval_precision = 0        # kept here and applied whenever an engine is bound
 
     # a rollout carries this model's recurrent state on the device: RcslPolicy.rollout / rollout_device call reset_state and pass the
     # live trajectory indices to step_state / step_device
@@ -629,6 +630,16 @@ class RNNDynamics(BaseDynamics):
         self._n_runs = int(n_runs)
         self._seed = int(seed) if seed is not None else 0
         self._gens = None
+
+    def set_eval_precision(self, p: int) -> None:
+        """0 (default): ``step`` and the priming of the carried state on the fp32 launches; 1: their GRU layers on the fused split-fp16
+        kernel (fp16 hi + lo planes, fp32 accumulators; a scaled input beyond +-32768 makes the call raise).  Usable before or after
+        the engine exists; training, ``step_state`` and ``step_device`` are unaffected."""
+        if int(p) not in (0, 1):
+            raise ValueError(f"RNNDynamics.set_eval_precision: 0 or 1, got {p!r}")
+        if self._eng is not None:
+            self._eng.set_eval_precision(int(p))
+        self._eval_precision = int(p)
 
     def _bind(self, rows: int, steps: int, exact: bool = False) -> None:
         """an engine for steps of up to ``rows`` sequences (``exact``: batch_size == rows, as learn_epoch cuts an epoch into
@@ -654,6 +665,7 @@ class RNNDynamics(BaseDynamics):
         cfg.external_arena = self._arena.data_ptr()
         torch.cuda.synchronize(dev)
         self._eng = _engine.RnnDynamicsEngine(cfg)
+        self._eng.set_eval_precision(self._eval_precision)
         self._shape = shape
         self._state_n = None            # (the carried state lived in the old engine)
         for r in range(R):

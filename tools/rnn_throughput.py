@@ -15,7 +15,12 @@ one-run step beside them (``profiles/rnn_throughput_runs.json`` holds R = 1, 2, 
 medians): (a) ``step_device`` on the carried state, (b) the engine's ``forward`` on device tensors at T = 1 (what there was for that
 step before the carried state: no history, so not the same model output), (c) ``step`` on 20-step windows, (d) the torch ``RNNModel``
 in eval mode with ``h_state`` carried; and one ``rollout_device`` of 256 trajectories x 200 steps with an untrained
-``AutoregressivePolicy`` (``profiles/rnn_rollout_throughput.json``)."""
+``AutoregressivePolicy`` (``profiles/rnn_rollout_throughput.json``).
+
+``--split`` measures the window forward at eval precision 0 (fp32 launches) against 1 (the fused split-fp16 GRU-stack kernel) on two
+engines with the same parameters, alternating in the same call: ``forward`` on 256 x 20 device windows (16-row tiles) and on 8192 x 20
+(32-row tiles, the largest whose planes fit the LDS at this shape), and ``state_prime`` on 256 x 20
+(``profiles/rnn_eval_split_throughput.json``)."""
 import argparse
 import json
 import os
@@ -201,6 +206,45 @@ def main_rollout(a):
     emit(res, a.out)
 
 
+def main_split(a):
+    """--split: forward and state_prime at eval precision 0 against 1, alternating windows, medians"""
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)                                   # noqa: E731
+    torch.manual_seed(0)
+    init = {k: v.numpy() for k, v in RNNModel(IN, OUT, HID, L, P_DROP).state_dict().items()}
+    engs = {}
+    for prec in (0, 1):
+        engs[prec] = _engine.RnnDynamicsEngine(_engine.default_rnn_config())
+        engs[prec].set_params(init)
+        engs[prec].set_eval_precision(prec)
+        engs[prec].state_reset(B)
+    xs = {n: torch.as_tensor(data(n)[0], device=dev).contiguous() for n in (B, 32 * B)}
+
+    def call(prec, what, n):
+        def fn():
+            for _ in range(a.batches):
+                engs[prec].forward(xs[n]) if what == "forward" else engs[prec].state_prime(xs[n])
+            return a.batches
+        return fn
+
+    runs = {f"{what}_{n}x{T}_precision_{prec}": call(prec, what, n)
+            for what, n in (("forward", B), ("forward", 32 * B), ("state_prime", B)) for prec in (0, 1)}
+    for fn in runs.values():
+        fn()
+    times = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for k, fn in runs.items():
+            times[k].append(window(fn, sync))
+    res = {"shape": dict(input_dim=IN, output_dim=OUT, hidden=HID, rnn_num_layers=L, T=T), "device": torch.cuda.get_device_name(0),
+           "calls_per_window": a.batches}
+    res.update({k: summary(v) for k, v in times.items()})
+    for k in [k for k in runs if k.endswith("_0")]:
+        res["ratio_0_over_1_" + k[:-12]] = res[k]["median_ms"] / res[k[:-1] + "1"]["median_ms"]
+    for e in engs.values():
+        e.close()
+    emit(res, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=20, help="optimizer steps per timed window")
@@ -210,6 +254,8 @@ def main():
     ap.add_argument("--rollout", action="store_true",
                     help="instead: one model step through the carried state (step_device) against forward at T = 1, step() on 20-step "
                          "windows and the torch model with h_state carried, and one rollout_device of 256 x 200")
+    ap.add_argument("--split", action="store_true",
+                    help="instead: forward (256 and 8192 windows) and state_prime at eval precision 0 against 1")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -218,6 +264,8 @@ def main():
         return main_runs(a)
     if a.rollout:
         return main_rollout(a)
+    if a.split:
+        return main_split(a)
     dev = torch.device("cuda", 0)
     x, tg, mk = data(a.batches * B)
     sync = lambda: torch.cuda.synchronize(dev)                                   # noqa: E731
