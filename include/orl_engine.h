@@ -381,6 +381,17 @@ int orl_learn_epoch(orl_engine* e, const int64_t* order, int64_t order_len, int 
  * Workspaces are sized for n at the first call and regrown when n grows.  Parameters, optimizer state, the step counter and the
  * noise streams of orl_learn_n are not touched.  Refused on any other engine. */
 int orl_autoreg_sample(orl_engine* e, const float* obs, int64_t n, const float* eps, int on_device, float* act_out);
+/* AUTOREG: how orl_autoreg_sample and the sampling leg of orl_mbrcsl_rollout compute.  0 (default): the launches above on the engine's
+ * forward-only GEMMs, bit for bit what they were, whatever orl_config::precision is.  1: one launch packs the weights into fp16 hi / lo
+ * planes of w * 64 (every orl_autoreg_sample call; once at the start of orl_mbrcsl_rollout) and ONE launch takes a row tile through all
+ * act_dim passes and all layers on split-fp16 MFMAs (three products, fp32 accumulators), the draw included; the random stream and the
+ * "ar_seps" tap are unchanged, the taps "ar_sx" / "ar_sz" are not produced by such a call.  An observation or hidden activation that is
+ * not finite or reaches 32768, or a weight with |w| * 64 >= 65504, raises a sticky device word: the call that synchronises fails with a
+ * message containing "range flag" and clears it.  Training (orl_step, orl_learn_n, orl_learn_epoch) never looks at the option.
+ * Refused: a value other than 0 / 1, an engine that is not ORL_ALGO_AUTOREG, obs_dim or a hidden width above 512 (for 1).
+ * orl_autoreg_sample_precision returns the current value (-1: not an AUTOREG engine). */
+int orl_autoreg_set_sample_precision(orl_engine* e, int32_t precision);
+int32_t orl_autoreg_sample_precision(orl_engine* e);
 /* MOBILE: the next-state samples of the batch the NEXT orl_step learns, [n_runs][S * E * batch][obs_dim] in the row order of
  * orl_dynsample_next (row (s * E + e) * batch + b).  A device pointer (on_device) is borrowed until that step has run -- nothing is
  * copied, the producer must have finished writing (orl_dynsample_next synchronises its stream) --; a host pointer is copied in.  One

@@ -2,7 +2,8 @@
 // One net [Linear, LeakyReLU(0.01)] x (L + 1) on [obs | masked act | one-hot], two outputs (mean, logstd) per expanded row.  A step:
 // k_autoreg_prepare (B rows -> M = A * B expanded rows, targets, row indices), the forward on the tiled GEMM's E_BIAS_LEAKY flavour down to
 // the plain-linear tail, k_autoreg_head (the output LeakyReLU, masked Gaussian NLL, dz_tail, metric, split-precision scale), the generic
-// backward with E_LEAKY_MASK, one Adam step.  orl_autoreg_sample: A forward-only passes over n rows with k_autoreg_draw between them.
+// backward with E_LEAKY_MASK, one Adam step.  orl_autoreg_sample: A forward-only passes over n rows with k_autoreg_draw between them, or
+// (orl_autoreg_set_sample_precision(1)) the weight pack and ONE launch of the fused split-fp16 kernel of autoreg_fused.h.
 // mbrcsl_loop (the body of orl_mbrcsl_rollout): sampling, the model step and the trajectory store's append as one device loop.
 namespace orl {
 
@@ -65,16 +66,17 @@ int Engine::autoreg_sample(const float* obs, long n, const float* eps, bool on_d
   }
   // (the noise is staged in the workspace for device callers too: the tap "ar_seps" reads it there)
   if (eps) ORL_HIP(hipMemcpyAsync(ar_seps.p, eps, sizeof(float) * (size_t)R * n * ad, in_kind, stream));
-  if (autoreg_sample_launches(d_obs, n, eps ? ar_seps.p : nullptr, act_out, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost)) return -1;
+  if (autoreg_sample_launches(d_obs, n, eps ? ar_seps.p : nullptr, act_out, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, true)) return -1;
+  if (autoreg_flags_fetch()) return -1;
   ORL_HIP(hipStreamSynchronize(stream));      // the only host synchronisation of the call
-  return 0;
+  return autoreg_flags_check("orl_autoreg_sample");
 }
 
 // The MBRCSL rollout loop's form: the launches of a call on device rows, nothing staged and no synchronisation.  The workspaces hold
 // the rows already (autoreg_sample_room, once, for the most rows of the loop); the kernels read `eps` ([n][act_dim] normals) where it lies.
 int Engine::autoreg_sample_enqueue(const float* obs, long n, const float* eps, float* act_out) {
   if (n > ar_ws.cap) return fail("autoreg_sample_enqueue: more rows than autoreg_sample_room made room for");
-  return autoreg_sample_launches(obs, n, eps, act_out, hipMemcpyDeviceToDevice);
+  return autoreg_sample_launches(obs, n, eps, act_out, hipMemcpyDeviceToDevice, false);      // (the loop packed the planes at its start)
 }
 
 // row buffers, count slots and events of the MBRCSL rollout loop; the row buffers are zero-filled, so a row no step has written holds zeros
@@ -118,6 +120,7 @@ int Engine::mbrcsl_loop(orl_dynamics* d, const DynStepInfo& di, orl_traj* store,
   int enq = 0, cur = 0;
   const auto body = [&]() -> int {
     ORL_HIP(hipMemcpyAsync(ml_obs[0].p, init_obs, sizeof(float) * (size_t)n_traj * od, hipMemcpyDeviceToDevice, stream));
+    if (ar_sample_prec == 1 && autoreg_fused_pack()) return -1;      // (nothing trains inside the loop: the planes hold for all of it)
     long bound = n_traj;
     for (int t = 0; t < length; ++t) {
       // the newest survivor count the host may wait for without stalling on a step it has just enqueued: counts never increase, so it
@@ -137,31 +140,47 @@ int Engine::mbrcsl_loop(orl_dynamics* d, const DynStepInfo& di, orl_traj* store,
       ++enq;
       cur ^= 1;
     }
-    return 0;
+    return autoreg_flags_fetch();
   };
   const int rc = loop.end(body(), F, elapsed_ms);      // the one unconditional host synchronisation (also on an error path)
   if (steps_enqueued) *steps_enqueued = enq;
-  if (rc || dynstep_loop_end(d, F)) return -1;
+  if (rc || dynstep_loop_end(d, F) || autoreg_flags_check(F)) return -1;
   return orl_traj_finish(store, rows, reward_sum, returns_host);
 }
 
 // what both forms launch: obs / eps are DEVICE arrays of n rows per run (eps null: drawn into the workspace), act_out by `out_kind`
-int Engine::autoreg_sample_launches(const float* d_obs, long n, const float* eps, float* act_out, hipMemcpyKind out_kind) {
+// `pack` (sample precision 1): the weight planes are packed first (false: the caller has packed them and nothing has trained since)
+int Engine::autoreg_sample_launches(const float* d_obs, long n, const float* eps, float* act_out, hipMemcpyKind out_kind, bool pack) {
   const int A = ad;
+  const bool fused = ar_sample_prec == 1;
   // the n rows of every run lie packed at the front of the workspaces (which may hold more rows)
   auto view = [&](Mat m) { m.rs = n * m.pitch; m.cs = m.rs; return m; };
   const Mat x = view(ar_sx), z = view(ar_sz), ep = view(ar_seps);
   std::vector<Mat> hs;
   for (auto& m : ar_sh) hs.push_back(view(m));
   // the workspaces of THIS call as taps (a host map write, no launch): the input rows as the last draw left them, the tail of the last
-  // pass and the noise, n rows each (the workspaces may be regrown by a later call, which registers them anew)
-  taps["ar_sx"] = {x, n, x.pitch}; taps["ar_sz"] = {z, n, 2}; taps["ar_seps"] = {ep, n, A};
+  // pass and the noise, n rows each (the workspaces may be regrown by a later call, which registers them anew).  The fused kernel
+  // produces neither input rows nor a tail: only the noise is a tap of such a call
+  taps["ar_seps"] = {ep, n, A};
+  if (fused) { taps.erase("ar_sx"); taps.erase("ar_sz"); }
+  else { taps["ar_sx"] = {x, n, x.pitch}; taps["ar_sz"] = {z, n, 2}; }
   if (!eps) {
     // device draws: Philox keyed by (seed, this entry point's call counter, run, element = row * A + dim) on a stream id no step uses
     hipLaunchKernelGGL(k_noise, dim3((unsigned)((n * A / 4 + 256) / 256), R), dim3(256), 0, stream, ep.p, n * A, 0, 0.f, 0.f, cfg.seed,
                        (const unsigned long long*)ar_calls, 0x5A5u);
     hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, stream, ar_calls);
     if (hipGetLastError() != hipSuccess) return fail("orl_autoreg_sample: noise launch failed");
+  }
+  if (fused) {
+    // the pack and ONE launch; the kernel stores the actions itself -- into the caller's device array, or for a host caller into the
+    // front of the (otherwise idle) input workspace, [R][n][A] packed, which one copy takes to the host
+    if (pack && autoreg_fused_pack()) return -1;
+    const bool to_host = out_kind == hipMemcpyDeviceToHost;
+    ArfP f = ar_f;
+    f.g.n = n; f.obs = d_obs; f.eps = eps ? eps : ep.p; f.e_rs = ep.rs; f.act = to_host ? ar_sx.p : act_out;
+    if (timed("orl_autoreg_sample", "autoreg_fused_sample", false, 0, 0, [&] { return arf_sample(f, stream); })) return -1;
+    if (to_host) ORL_HIP(hipMemcpyAsync(act_out, ar_sx.p, sizeof(float) * (size_t)R * n * A, hipMemcpyDeviceToHost, stream));
+    return 0;
   }
   AutoregDrawP d; memset(&d, 0, sizeof(d));
   d.z = z.p; d.z_rs = z.rs; d.eps = eps ? eps : ep.p; d.e_rs = ep.rs; d.obs = d_obs; d.o_rs = n * od;
@@ -179,6 +198,63 @@ int Engine::autoreg_sample_launches(const float* d_obs, long n, const float* eps
   ORL_HIP(hipMemcpy2DAsync(act_out, sizeof(float) * A, x.p + od, sizeof(float) * x.pitch, sizeof(float) * A, (size_t)R * n,
                            out_kind, stream));
   return 0;
+}
+
+// ---- sample precision 1: the fused split-fp16 kernel (autoreg_fused.h) ----
+// 0: the launches above, whatever orl_config::precision is; 1: k_autoreg_pack_planes + k_autoreg_fused_sample.  The planes, the two
+// sticky range words and their pinned host copy are made when 1 is first asked for.  Training never looks at the option.
+int Engine::autoreg_set_sample_precision(int prec) {
+  const std::string F = "orl_autoreg_set_sample_precision";
+  if (prec != 0 && prec != 1) return fail(F + ": sample precision must be 0 (the fp32 launches) or 1 (split fp16), got " + std::to_string(prec));
+  if (prec == 1 && !ar_planes) {
+    const int MAXW = ORL_AUTOREG_FUSED_MAX_WIDTH;
+    if (od > MAXW) return fail(F + ": obs_dim " + std::to_string(od) + " is wider than the " + std::to_string(MAXW) + " columns the fused kernel takes");
+    for (int i = 0; i < L; ++i)
+      if (cfg.hidden[i] > MAXW)
+        return fail(F + ": a hidden layer of " + std::to_string(cfg.hidden[i]) + " units is wider than the " + std::to_string(MAXW) + " columns the fused kernel takes");
+    const NetLayout& nl = lay[ORL_NET_ACTOR];
+    ArfP f; memset(&f, 0, sizeof(f));
+    f.g.R = R; f.g.K = 1; f.g.nl = L + 1;
+    f.g.width[0] = od;
+    for (int i = 0; i < L; ++i) f.g.width[i + 1] = cfg.hidden[i];
+    f.g.width[L + 1] = 2;
+    for (int l = 0; l <= L; ++l) { f.g.w_off[l] = nl.w_off[l]; f.g.b_off[l] = nl.b_off[l]; }
+    f.g.params = net_ptr(0, ORL_NET_ACTOR); f.g.P = P_train;
+    f.A = ad; f.in0 = od + 2 * ad;
+    const long halves = arf_layout(f);
+    ORL_HIP(hipSetDevice(dev));
+    hx_t* planes = (hx_t*)raw_alloc(sizeof(hx_t) * 2 * (size_t)halves);
+    unsigned int* fl = (unsigned int*)raw_alloc(sizeof(unsigned int) * DYF_FLAGS);
+    if (!planes || !fl) return fail(F + ": hipMalloc weight planes");
+    if (!ar_hflags) ORL_HIP(hipHostMalloc((void**)&ar_hflags, sizeof(unsigned int) * DYF_FLAGS, hipHostMallocDefault));
+    ar_hflags[DYF_FLAG_ACT] = ar_hflags[DYF_FLAG_W] = 0u;
+    f.g.Bh = planes; f.g.Bl = planes + halves; f.g.flags = fl;
+    ar_f = f; ar_planes = planes;
+  }
+  ar_sample_prec = prec;
+  return 0;
+}
+
+// runs on every orl_autoreg_sample call: the arena is aliased by the caller's tensors, nothing about it may be cached across calls
+int Engine::autoreg_fused_pack() {
+  return timed("orl_autoreg_sample", "autoreg_pack_planes", false, 0, 0, [&] { return arf_pack(ar_f, stream); });
+}
+
+// The range words are sticky on the device; a synchronising call copies them to the pinned host words on the stream before it
+// synchronises (fetch), and refuses after it with "range flag", clearing both (check): a weight that is still out of range raises its
+// word again at the next pack, a call on good rows and weights is clean again.
+int Engine::autoreg_flags_fetch() {
+  if (ar_sample_prec == 1) ORL_HIP(hipMemcpyAsync(ar_hflags, ar_f.g.flags, sizeof(unsigned int) * DYF_FLAGS, hipMemcpyDeviceToHost, stream));
+  return 0;
+}
+
+int Engine::autoreg_flags_check(const char* who) {
+  if (ar_sample_prec != 1 || !(ar_hflags[DYF_FLAG_ACT] | ar_hflags[DYF_FLAG_W])) return 0;
+  const bool w = ar_hflags[DYF_FLAG_W] != 0;
+  ar_hflags[DYF_FLAG_ACT] = ar_hflags[DYF_FLAG_W] = 0u;
+  ORL_HIP(hipMemcpy(ar_f.g.flags, ar_hflags, sizeof(unsigned int) * DYF_FLAGS, hipMemcpyHostToDevice));
+  return fail(std::string(who) + (w ? ": sample precision 1 range flag: a weight of the policy is not finite or reaches |w| * 64 >= 65504"
+                                    : ": sample precision 1 range flag: an observation or a hidden activation was not finite or reached |x| >= 32768"));
 }
 
 }  // namespace orl

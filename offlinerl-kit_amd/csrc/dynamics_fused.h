@@ -33,6 +33,42 @@ struct DyfP {
   unsigned int* flags;                 // [DYF_FLAGS]
 };
 
+// the fragments [f0, f0 + cnt) of an N-column layer that wave `wave` of 4 multiplies (cnt may be 0)
+__device__ __forceinline__ void dyf_wave_frags(int N, int wave, int& f0, int& cnt) {
+  const int nfrag = (N + 15) >> 4, per = (nfrag + 3) >> 2;
+  f0 = wave * per;
+  cnt = max(0, min(per, nfrag - f0));
+}
+
+// The pack of one thread: 4 k of a plane row of (run r, member k), element e of pmember / 4.  KCONT = false: the weight of layer l is
+// (in, out)-major (EnsembleLinear) and adjacent threads take adjacent output columns; KCONT = true: it is nn.Linear's [out][ld] with
+// ld = ld0 for layer 0 (which packs only its first width[0] columns) and width[l] above, and adjacent threads take adjacent k.
+template <bool KCONT>
+__device__ __forceinline__ void dyf_pack_one(const DyfP& p, long e, int k, int r, int ld0) {
+  if (e >= (p.pmember >> 2)) return;
+  int l = 0;
+  while (l + 1 < p.nl && e >= (p.poff[l + 1] >> 2)) ++l;
+  const long le = e - (p.poff[l] >> 2);
+  const int in = p.width[l], N = p.width[l + 1], q = p.Kp[l] >> 2;
+  const int o = KCONT ? (int)(le / q) : (int)(le % N), kk = (KCONT ? (int)(le - (long)o * q) : (int)(le / N)) * 4;
+  const int ld = l ? in : ld0;
+  const float* const W = p.params + (long)r * p.P + p.w_off[l] + (KCONT ? (long)o * ld : (long)k * in * N + o);
+  const long sk = KCONT ? 1 : N;
+  f32x4 v;
+  unsigned int bad = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[j] = kk + j < in ? W[(long)(kk + j) * sk] * ORL_WSCALE : 0.f;
+    bad |= !(fabsf(v[j]) < 65504.f);
+  }
+  hx4 h, lo;
+  orl_split4(v, h, lo);
+  const long at = ((long)r * p.K + k) * p.pmember + p.poff[l] + (long)o * p.Kp[l] + kk;
+  *(hx4*)(p.Bh + at) = h;
+  *(hx4*)(p.Bl + at) = lo;
+  if (bad) p.flags[DYF_FLAG_W] = 1u;
+}
+
 // fills Kp, poff, pmember and Wp from nl and width; returns the halves of one plane of the whole object (R K pmember)
 long dyf_layout(DyfP& p);
 // rows per workgroup the launcher picks for n rows: the largest of 64 / 32 / 16 whose planes fit the LDS and that still gives 256

@@ -19,13 +19,6 @@
 
 namespace orl {
 
-// the fragments [f0, f0 + cnt) of an N-column layer that wave `wave` multiplies (cnt may be 0)
-__device__ __forceinline__ void dyf_wave_frags(int N, int wave, int& f0, int& cnt) {
-  const int nfrag = (N + 15) >> 4, per = (nfrag + 3) >> 2;
-  f0 = wave * per;
-  cnt = max(0, min(per, nfrag - f0));
-}
-
 template <int RT, int NF>
 __global__ __launch_bounds__(256) void k_dyn_fused_fwd(DyfP p) {
   constexpr int MA = RT / 16;
@@ -182,28 +175,7 @@ __global__ __launch_bounds__(256) void k_dyn_fused_fwd(DyfP p) {
 
 // one thread per 4 k of a plane row of one (run, member); adjacent threads read adjacent output columns of the (in, out)-major weight
 __global__ __launch_bounds__(256) void k_dyn_pack_planes(DyfP p) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int k = blockIdx.y, r = blockIdx.z;
-  if (e >= (p.pmember >> 2)) return;
-  int l = 0;
-  while (l + 1 < p.nl && e >= (p.poff[l + 1] >> 2)) ++l;
-  const long le = e - (p.poff[l] >> 2);
-  const int in = p.width[l], N = p.width[l + 1];
-  const int o = (int)(le % N), kk = (int)(le / N) * 4;
-  const float* const W = p.params + (long)r * p.P + p.w_off[l] + (long)k * in * N;
-  f32x4 v;
-  unsigned int bad = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[j] = kk + j < in ? W[(long)(kk + j) * N + o] * ORL_WSCALE : 0.f;
-    bad |= !(fabsf(v[j]) < 65504.f);
-  }
-  hx4 h, lo;
-  orl_split4(v, h, lo);
-  const long at = ((long)r * p.K + k) * p.pmember + p.poff[l] + (long)o * p.Kp[l] + kk;
-  *(hx4*)(p.Bh + at) = h;
-  *(hx4*)(p.Bl + at) = lo;
-  if (bad) p.flags[DYF_FLAG_W] = 1u;
+  dyf_pack_one<false>(p, (long)blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y, blockIdx.z, 0);
 }
 
 long dyf_layout(DyfP& p) {

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "autoreg_fused.h"
 #include "devobj.h"
 #include "kernels.h"
 #include "store.h"
@@ -358,9 +359,19 @@ struct Engine {
   int autoreg_sample_room(long n);
   RowScratch ar_ws;
   int autoreg_sample_enqueue(const float* obs, long n, const float* eps, float* act_out);
-  int autoreg_sample_launches(const float* d_obs, long n, const float* eps, float* act_out, hipMemcpyKind out_kind);
+  int autoreg_sample_launches(const float* d_obs, long n, const float* eps, float* act_out, hipMemcpyKind out_kind, bool pack);
   Mat ar_sx, ar_sz, ar_seps, ar_sobs; std::vector<Mat> ar_sh;
   unsigned long long* ar_calls = nullptr;
+  // orl_autoreg_set_sample_precision (autoreg_fused.h): 1 samples on the fused split-fp16 kernel.  ar_f: the net's plane layout, the
+  // planes and the device range words (rows, observations, noise and output are filled per call); ar_hflags: their pinned host copy
+  int ar_sample_prec = 0;
+  ArfP ar_f;
+  hx_t* ar_planes = nullptr;
+  unsigned int* ar_hflags = nullptr;
+  int autoreg_set_sample_precision(int prec);
+  int autoreg_fused_pack();
+  int autoreg_flags_fetch();
+  int autoreg_flags_check(const char* who);
   // RAMBO (algo_rambo.inc; SAC engines).  orl_engine_adv_advantage: workspaces for Ba rows per run (the actor's input and hidden
   // activations, the 2 Ba-row critic operand with the critics' activations, head, log-prob, Q, the five tap vectors, host staging),
   // regrown when Ba grows.  The device loop (rambo_loop: orl_rambo_update_dynamics behind its refusals) adds its row buffers (two observation

@@ -217,6 +217,7 @@ Engine::~Engine() {
   for (auto& e : ev_pool) hipEventDestroy(e);
   for (auto& e : ml_events) hipEventDestroy(e);
   if (ml_counts) hipHostFree(ml_counts);
+  if (ar_hflags) hipHostFree(ar_hflags);
   mem.free_all();
   if (stream) hipStreamDestroy(stream);
 }
@@ -1866,6 +1867,14 @@ int orl_autoreg_sample(orl_engine* h, const float* obs, int64_t n, const float* 
   ORL_HIP(hipSetDevice(e.dev));
   return e.autoreg_sample(obs, (long)n, eps, on_device != 0, act_out);
 }
+
+int orl_autoreg_set_sample_precision(orl_engine* h, int32_t precision) {
+  if (!h) return fail("orl_autoreg_set_sample_precision: null handle");
+  if (h->e.cfg.algo != ORL_ALGO_AUTOREG) return fail("orl_autoreg_set_sample_precision: not an AUTOREG engine");
+  return h->e.autoreg_set_sample_precision((int)precision);
+}
+
+int32_t orl_autoreg_sample_precision(orl_engine* h) { return h && h->e.cfg.algo == ORL_ALGO_AUTOREG ? h->e.ar_sample_prec : -1; }
 
 int orl_engine_set_next_samples(orl_engine* h, const float* samples, int on_device) {
   Engine& e = h->e;

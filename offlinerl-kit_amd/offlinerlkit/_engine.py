@@ -66,8 +66,8 @@ ABI_SYMBOLS = [
     "orl_mobile_learn_n", "orl_dynsample_calls",
     # RCSL: one ordered pass over the attached buffer
     "orl_learn_epoch",
-    # the autoregressive behaviour policy: sequential sampling
-    "orl_autoreg_sample",
+    # the autoregressive behaviour policy: sequential sampling, and its opt-in fused split-fp16 kernel
+    "orl_autoreg_sample", "orl_autoreg_set_sample_precision", "orl_autoreg_sample_precision",
     # the RCSL rollout's trajectory store
     "orl_traj_create", "orl_traj_destroy", "orl_traj_reset", "orl_traj_append_step", "orl_traj_finish", "orl_traj_read", "orl_traj_export",
     "orl_traj_live",
@@ -306,6 +306,9 @@ def load_library(path: Optional[str] = None):
     lib.orl_learn_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_learn_epoch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     lib.orl_autoreg_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+    lib.orl_autoreg_set_sample_precision.argtypes = [C.c_void_p, C.c_int32]
+    lib.orl_autoreg_sample_precision.argtypes = [C.c_void_p]
+    lib.orl_autoreg_sample_precision.restype = C.c_int32
     lib.orl_engine_set_next_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_lcb_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_adv_advantage.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int]
@@ -893,6 +896,14 @@ class Engine(_Handle):
         _check(self.lib.orl_autoreg_sample(self._h, o.ctypes.data, o.shape[1], None if e is None else e.ctypes.data, 0, out.ctypes.data),
                "orl_autoreg_sample")
         return out
+
+    def autoreg_set_sample_precision(self, p: int):
+        """AUTOREG: 0 (default) samples on the fp32 launches, 1 on the fused split-fp16 kernel (orl_autoreg_set_sample_precision)"""
+        _check(self.lib.orl_autoreg_set_sample_precision(self._h, int(p)), "orl_autoreg_set_sample_precision")
+
+    @property
+    def autoreg_sample_precision(self) -> int:
+        return int(self.lib.orl_autoreg_sample_precision(self._h))
 
     # ---- health (include/orl_engine.h: ORL_HEALTH_*) ----
     def _check_step(self, rc: int, what: str):

@@ -51,7 +51,23 @@ class AutoregressivePolicy(_EpochPolicy):
         self.rcsl_optim = torch.optim.Adam(self.model.parameters(), lr=lr)
         self.device = device
         self.model = self.model.to(self.device)
+        self._sample_precision = 0
         self._dims()
+
+    def set_sample_precision(self, p: int) -> None:
+        """0 (default): sampling (``select_action*``, the device rollout's policy leg) on the fp32 launches; 1: on the fused split-fp16
+        kernel (fp16 hi + lo planes, fp32 accumulators; an observation or activation beyond +-32768 makes the call raise).  Usable
+        before or after an engine is bound -- every engine this policy binds gets the value --; training is unaffected."""
+        if isinstance(p, bool) or p not in (0, 1):
+            raise ValueError(f"AutoregressivePolicy.set_sample_precision: 0 or 1, got {p!r}")
+        if self._eng is not None:
+            self._eng.autoreg_set_sample_precision(int(p))
+        self._sample_precision = int(p)
+
+    def _bind(self, batch_size: int) -> None:
+        super()._bind(batch_size)
+        if self._eng.autoreg_sample_precision != self._sample_precision:      # (a fresh engine starts at 0)
+            self._eng.autoreg_set_sample_precision(self._sample_precision)
 
     # -- engine hooks ----------------------------------------------------------------------
     def _dims(self):

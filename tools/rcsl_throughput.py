@@ -32,7 +32,12 @@ profiles/diffusion_throughput.json unless --out names another file.
 ``--diffusion --split``: the sampler alone at sample precision 0 (the fp32 launches) and 1 (the fused split-fp16 kernel,
 csrc/diffusion_fused.hip) on one policy object, alternating windows in one run: ``select_action_device`` on 256 rows (calls per second)
 and ``rollout_device`` of ``--trajectories`` x ``--horizon`` (transitions per second); medians of ``--blocks`` windows after a warm-up
-of each.  Writes profiles/diffusion_sample_split_throughput.json unless --out names another file."""
+of each.  Writes profiles/diffusion_sample_split_throughput.json unless --out names another file.
+``--autoreg --split`` (or ``--rollout --split``): AutoregressivePolicy's sampling at sample precision 0 (a GEMM launch per layer and a
+draw per pass) and 1 (the fused split-fp16 kernel, csrc/autoreg_fused.hip) on one policy object, alternating windows in one run:
+``select_action_device`` on 256 and 50 000 rows with the kernel launches of a call, and ``rollout_device(fused=True)`` of
+``--trajectories`` x ``--horizon`` for the policy's option crossed with the dynamics' precision.  Writes
+profiles/autoreg_sample_split_throughput.json unless --out names another file."""
 import argparse
 import json
 import os
@@ -422,6 +427,85 @@ def measure_diffusion_split(blocks, sample_calls, n_traj, horizon):
                                     ranges_disjoint=bool(min(r1) > max(r0) or min(r0) > max(r1))))
 
 
+def measure_autoreg_split(blocks, sample_calls, n_traj, horizon):
+    """``--autoreg --split`` / ``--rollout --split``: AutoregressivePolicy's sampling at sample precision 0 (the per-layer launches) and 1
+    (the fused split-fp16 kernel) -- select_action_device at 256 and 50 000 rows, and rollout_device(fused=True) with the policy's
+    option crossed with the dynamics' precision; contestants alternate inside every window pair, medians over the windows"""
+    from offlinerlkit.dynamics import EnsembleDynamics
+    from offlinerlkit.modules import EnsembleDynamicsModel
+    from offlinerlkit.utils.scaler import StandardScaler
+    from offlinerlkit.utils.termination_fns import termination_fn_default
+    med = lambda v: float(np.median(v))
+    torch.manual_seed(1)
+    ar = AutoregressivePolicy(OD, AD, HID, LR, DEV)
+    eng = ar.loop_engine()
+    rng = np.random.default_rng(0)
+
+    def launches(prec, obs):
+        """kernel launches of one sampling call, from the engine's own profile"""
+        ar.set_sample_precision(prec)
+        count = lambda: int(sum(r["launches"] for r in eng.profile_table()))      # (the profile accumulates: a difference)
+        before = count()
+        eng.profile_enable(True)
+        ar.select_action_device(obs)
+        eng.profile_enable(False)
+        return count() - before
+
+    def sample(prec, obs, calls):
+        ar.set_sample_precision(prec)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            act = ar.select_action_device(obs)
+        torch.cuda.synchronize()
+        return calls / (time.perf_counter() - t0), act
+    legs = []
+    for rows, calls in ((256, sample_calls), (50_000, max(sample_calls // 5, 5))):
+        obs = torch.as_tensor(rng.normal(size=(rows, OD)).astype(np.float32), device=DEV)
+        a0, a1 = sample(0, obs, 3)[1], sample(1, obs, 3)[1]      # warm-up
+        n0, n1 = launches(0, obs), launches(1, obs)
+        s0, s1 = [], []
+        for _ in range(blocks):
+            s0.append(sample(0, obs, calls)[0]); s1.append(sample(1, obs, calls)[0])
+        legs.append(dict(rows=rows, calls_per_window=calls, precision0_calls_per_s=s0, precision1_calls_per_s=s1, precision0_median=med(s0),
+                         precision1_median=med(s1), speedup=med(s1) / med(s0), ranges_disjoint=bool(min(s1) > max(s0) or min(s0) > max(s1)),
+                         launches_per_call=dict(precision0=n0, precision1=n1),
+                         actions_finite=bool(torch.isfinite(a0).all() and torch.isfinite(a1).all())))
+    # the rollout: one dynamics per precision (the option is fixed when its engine is bound), the same policy object toggled
+    init = rng.normal(size=(n_traj, OD)).astype(np.float32)
+    store = _engine.TrajStore(OD, AD, n_traj, n_traj * horizon, 0)
+    mod = make_module(False)
+    pols = {}
+    for dp in (0, 1):
+        torch.manual_seed(1)
+        model = EnsembleDynamicsModel(OD, AD, HID, num_ensemble=7, num_elites=5, weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=DEV)
+        scaler = StandardScaler(np.zeros((1, OD + AD), np.float32), np.ones((1, OD + AD), np.float32))
+        dyn = EnsembleDynamics(model, torch.optim.Adam(model.parameters(), lr=1e-3), scaler, termination_fn_default)
+        dyn.set_engine_options(seed=3, precision=dp)
+        pols[dp] = RcslPolicy(dyn, ar, mod, torch.optim.Adam(mod.parameters(), lr=LR), DEV)
+
+    def rollout(pp, dp):
+        ar.set_sample_precision(pp)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, info = pols[dp].rollout_device(init, horizon, store=store, fused=True)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        return info["num_transitions"] / wall, float(info["loop_ms"]) / max(int(info["steps_enqueued"]), 1)
+    combos = [(0, 0), (1, 0), (0, 1), (1, 1)]
+    for c in combos:
+        rollout(*c)                                          # warm-up
+    rate, step_ms = {c: [] for c in combos}, {c: [] for c in combos}
+    for _ in range(blocks):
+        for c in combos:
+            r, ms = rollout(*c)
+            rate[c].append(r); step_ms[c].append(ms)
+    roll = [dict(policy_sample_precision=c[0], dynamics_precision=c[1], transitions_per_s=rate[c], median=med(rate[c]),
+                 loop_event_ms_per_model_step=med(step_ms[c]), policy_launches_per_model_step=legs[0]["launches_per_call"][f"precision{c[0]}"] - c[0])
+            for c in combos]      # (precision 1: the pack runs once per rollout, not per step)
+    return dict(select_action_device=legs, rollout_device_fused=dict(trajectories=n_traj, horizon=horizon, lag=2, results=roll))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000)
@@ -435,8 +519,16 @@ def main():
     ap.add_argument("--horizon", type=int, default=1000)
     ap.add_argument("--out", default=None)
     ap.add_argument("--diffusion", action="store_true", help="DiffusionBC at the default shape: a training epoch, select_action on 256 rows, the rollout")
-    ap.add_argument("--split", action="store_true", help="with --diffusion: the sampler alone at sample precision 0 and 1 (fused split-fp16 kernel)")
+    ap.add_argument("--split", action="store_true", help="with --diffusion, --autoreg or --rollout: the sampler alone at sample precision 0 and 1 (fused split-fp16 kernel)")
     a = ap.parse_args()
+    if (a.autoreg or a.rollout) and a.split:
+        res = dict(policy="AutoregressivePolicy", stage="sampling at sample precision 0 (per-layer launches) and 1 (fused split-fp16 kernel)",
+                   shape=dict(obs_dim=OD, act_dim=AD, hidden=HID, dynamics_hidden=HID, ensemble=7, elites=5), device=torch.cuda.get_device_name(0),
+                   blocks=a.blocks, result=measure_autoreg_split(a.blocks, a.sample_calls, a.trajectories, a.horizon))
+        print(json.dumps(res))
+        with open(a.out or os.path.join(ROOT, "profiles", "autoreg_sample_split_throughput.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if a.diffusion and a.split:
         res = dict(policy="DiffusionBC", stage="sampling at sample precision 0 (fp32 launches) and 1 (fused split-fp16 kernel)",
                    shape=dict(obs_dim=OD, act_dim=AD, down_dims=[256, 512, 1024], step_embed_dim=256, n_groups=8, num_diffusion_iters=10),
