@@ -392,6 +392,21 @@ int orl_autoreg_sample(orl_engine* e, const float* obs, int64_t n, const float* 
  * orl_autoreg_sample_precision returns the current value (-1: not an AUTOREG engine). */
 int orl_autoreg_set_sample_precision(orl_engine* e, int32_t precision);
 int32_t orl_autoreg_sample_precision(orl_engine* e);
+/* The tanh-Gaussian actor of a SAC / CQL / MCQ / EDAC / MOBILE engine sampled for n rows per run, as the model-based rollouts sample it:
+ *   act = tanh(mu(obs) + exp(clamp(log_sigma(obs), -5, 2)) * eps),   deterministic: act = tanh(mu(obs)).
+ * One launch packs the actor's weights into fp16 hi / lo planes of w * 64 (every call: the weights train between rollouts) and ONE
+ * launch takes a row tile through the backbone, the [mu ; sigma] head and the draw on split-fp16 MFMAs (three products, fp32
+ * accumulators; csrc/actor_fused.hip).  run = -1: every run, obs [n_runs][n][obs_dim], eps and act [n_runs][n][act_dim]; run = r: run
+ * r's actor on arrays without the run dimension.  eps NULL (and not deterministic): device Philox draws keyed by (seed, the call
+ * counter of this entry point, run, element).  live: NULL, or a HOST array (also with on_device) of n_runs counts (one count for run =
+ * r): only the first live[r] rows of run r count, the others are not computed and their act rows are written as zeros.  on_device: obs
+ * / eps / act are device pointers of the engine's GPU and the caller's writes have finished; else host arrays that are staged.  The
+ * call synchronises the engine's stream.  An observation or hidden activation that is not finite or reaches 32768, or a weight with
+ * |w| * 64 >= 65504, makes the call fail with a message containing "range flag"; the next call starts clean.  Training never looks at
+ * anything here.  Refused, each by name: an engine whose ORL_NET_ACTOR is not a tanh-Gaussian with a state-conditioned sigma (IQL, TD3+BC,
+ * RCSL, Gaussian RCSL, AUTOREG), an actor with dropout, obs_dim or a hidden width above 512, act_dim above 32. */
+int orl_actor_sample(orl_engine* e, int32_t run, const float* obs, int64_t n, const float* eps, const int32_t* live, int deterministic,
+                     int on_device, float* act);
 /* MOBILE: the next-state samples of the batch the NEXT orl_step learns, [n_runs][S * E * batch][obs_dim] in the row order of
  * orl_dynsample_next (row (s * E + e) * batch + b).  A device pointer (on_device) is borrowed until that step has run -- nothing is
  * copied, the producer must have finished writing (orl_dynsample_next synchronises its stream) --; a host pointer is copied in.  One

@@ -20,7 +20,7 @@ GEMM_H = ["gemm.h", "gemm_kernel.h"]
 WS_H = ["gemm.h", "ws_gemm.h", "ws_device.h"]
 # translation unit -> headers it depends on
 UNITS = {
-    "engine.hip": ["engine.h", "autoreg_fused.h", "dynamics_fused.h", "devobj.h", "gemm.h", "ws_gemm.h", "small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "kernels.h", "store.h", "rng.h", "algo_cql.inc", "algo_iql.inc", "algo_td3bc.inc", "algo_edac.inc", "algo_sac.inc", "algo_mcq.inc", "algo_mobile.inc", "algo_rcsl.inc", "algo_rcsl_gauss.inc", "algo_autoreg.inc", "algo_rambo.inc", ABI],
+    "engine.hip": ["engine.h", "actor_fused.h", "actor_sample.inc", "autoreg_fused.h", "dynamics_fused.h", "devobj.h", "gemm.h", "ws_gemm.h", "small_fwd.h", "small_bwd.h", "sample.h", "scalars.h", "kernels.h", "store.h", "rng.h", "algo_cql.inc", "algo_iql.inc", "algo_td3bc.inc", "algo_edac.inc", "algo_sac.inc", "algo_mcq.inc", "algo_mobile.inc", "algo_rcsl.inc", "algo_rcsl_gauss.inc", "algo_autoreg.inc", "algo_rambo.inc", ABI],
     "store.hip": ["store.h", "devobj.h", "gemm.h", "rng.h", ABI],
     "gemm_inst_fwd.hip": GEMM_H,
     "gemm_inst_plain.hip": GEMM_H,
@@ -32,6 +32,7 @@ UNITS = {
     "dynamics.hip": ["devobj.h", "dynamics_fused.h", "reduce.h", "gemm.h", "rng.h", ABI],
     "dynamics_fused.hip": ["dynamics_fused.h", "gemm.h", ABI],
     "autoreg_fused.hip": ["autoreg_fused.h", "dynamics_fused.h", "gemm.h", ABI],
+    "actor_fused.hip": ["actor_fused.h", "dynamics_fused.h", "sample.h", "gemm.h", ABI],
     "diffusion.hip": ["devobj.h", "diffusion_fused.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],
     "diffusion_fused.hip": ["diffusion_fused.h", "reduce.h", "gemm.h"],
     "rnn_dynamics.hip": ["devobj.h", "rnn_fused.h", "dynamics_fused.h", "reduce.h", "train_ops.h", "gemm.h", "rng.h", ABI],

@@ -249,12 +249,17 @@ int Engine::autoreg_flags_fetch() {
 }
 
 int Engine::autoreg_flags_check(const char* who) {
-  if (ar_sample_prec != 1 || !(ar_hflags[DYF_FLAG_ACT] | ar_hflags[DYF_FLAG_W])) return 0;
-  const bool w = ar_hflags[DYF_FLAG_W] != 0;
-  ar_hflags[DYF_FLAG_ACT] = ar_hflags[DYF_FLAG_W] = 0u;
-  ORL_HIP(hipMemcpy(ar_f.g.flags, ar_hflags, sizeof(unsigned int) * DYF_FLAGS, hipMemcpyHostToDevice));
-  return fail(std::string(who) + (w ? ": sample precision 1 range flag: a weight of the policy is not finite or reaches |w| * 64 >= 65504"
-                                    : ": sample precision 1 range flag: an observation or a hidden activation was not finite or reached |x| >= 32768"));
+  return ar_sample_prec == 1 ? range_flags_check(std::string(who) + ": sample precision 1", "policy", ar_hflags, ar_f.g.flags) : 0;
+}
+
+// the check of a fused split-fp16 sampling call (autoreg_fused.h, actor_fused.h) on the fetched host words `h` of the device words `d`
+int Engine::range_flags_check(const std::string& who, const char* net, unsigned int* h, unsigned int* d) {
+  if (!(h[DYF_FLAG_ACT] | h[DYF_FLAG_W])) return 0;
+  const bool w = h[DYF_FLAG_W] != 0;
+  h[DYF_FLAG_ACT] = h[DYF_FLAG_W] = 0u;
+  ORL_HIP(hipMemcpy(d, h, sizeof(unsigned int) * DYF_FLAGS, hipMemcpyHostToDevice));
+  return fail(who + (w ? std::string(" range flag: a weight of the ") + net + " is not finite or reaches |w| * 64 >= 65504"
+                       : std::string(" range flag: an observation or a hidden activation was not finite or reached |x| >= 32768")));
 }
 
 }  // namespace orl

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "actor_fused.h"
 #include "autoreg_fused.h"
 #include "devobj.h"
 #include "kernels.h"
@@ -372,6 +373,20 @@ struct Engine {
   int autoreg_fused_pack();
   int autoreg_flags_fetch();
   int autoreg_flags_check(const char* who);
+  int range_flags_check(const std::string& who, const char* net, unsigned int* h, unsigned int* d);
+  // orl_actor_sample (actor_sample.inc, actor_fused.h): the SAC family's tanh-Gaussian actor sampled on the fused split-fp16 kernel.
+  // as_f: the net's plane layout, the planes and the device range words (rows, arrays and the runs of a launch are filled per call);
+  // as_hflags: their pinned host copy; as_live: the device table of live counts [R]; as_calls: the call counter of the device draws;
+  // as_ws: staging rows of host callers and the drawn normals
+  AcfP as_f;
+  hx_t* as_planes = nullptr;
+  unsigned int* as_hflags = nullptr;
+  int* as_live = nullptr;
+  unsigned long long* as_calls = nullptr;
+  RowScratch as_ws;
+  Mat as_obs, as_eps, as_act;
+  int actor_sample_setup();
+  int actor_sample(int run, const float* obs, long n, const float* eps, const int* live, bool det, bool on_device, float* act);
   // RAMBO (algo_rambo.inc; SAC engines).  orl_engine_adv_advantage: workspaces for Ba rows per run (the actor's input and hidden
   // activations, the 2 Ba-row critic operand with the critics' activations, head, log-prob, Q, the five tap vectors, host staging),
   // regrown when Ba grows.  The device loop (rambo_loop: orl_rambo_update_dynamics behind its refusals) adds its row buffers (two observation

@@ -218,6 +218,7 @@ Engine::~Engine() {
   for (auto& e : ml_events) hipEventDestroy(e);
   if (ml_counts) hipHostFree(ml_counts);
   if (ar_hflags) hipHostFree(ar_hflags);
+  if (as_hflags) hipHostFree(as_hflags);
   mem.free_all();
   if (stream) hipStreamDestroy(stream);
 }
@@ -1136,6 +1137,7 @@ static SampleJob make_job(int head_row0, int rows, int rep, const Mat& eps, cons
 #include "algo_rcsl_gauss.inc"
 #include "algo_autoreg.inc"
 #include "algo_rambo.inc"
+#include "actor_sample.inc"
 
 namespace orl {
 
@@ -1875,6 +1877,17 @@ int orl_autoreg_set_sample_precision(orl_engine* h, int32_t precision) {
 }
 
 int32_t orl_autoreg_sample_precision(orl_engine* h) { return h && h->e.cfg.algo == ORL_ALGO_AUTOREG ? h->e.ar_sample_prec : -1; }
+
+int orl_actor_sample(orl_engine* h, int32_t run, const float* obs, int64_t n, const float* eps, const int32_t* live, int deterministic,
+                     int on_device, float* act) {
+  if (!h) return fail("orl_actor_sample: null handle");
+  Engine& e = h->e;
+  if (!obs || !act) return fail("orl_actor_sample: null observations / output");
+  if (run < -1 || run >= e.R) return fail("orl_actor_sample: run must be -1 (every run) or in [0, n_runs)");
+  if (n < 1 || n > (1 << 24)) return fail("orl_actor_sample: n must be in [1, 2^24] rows per run");
+  ORL_HIP(hipSetDevice(e.dev));
+  return e.actor_sample((int)run, obs, (long)n, eps, live, deterministic != 0, on_device != 0, act);
+}
 
 int orl_engine_set_next_samples(orl_engine* h, const float* samples, int on_device) {
   Engine& e = h->e;

@@ -68,6 +68,8 @@ ABI_SYMBOLS = [
     "orl_learn_epoch",
     # the autoregressive behaviour policy: sequential sampling, and its opt-in fused split-fp16 kernel
     "orl_autoreg_sample", "orl_autoreg_set_sample_precision", "orl_autoreg_sample_precision",
+    # the SAC family's tanh-Gaussian actor sampled for the rollouts on its fused split-fp16 kernel
+    "orl_actor_sample",
     # the RCSL rollout's trajectory store
     "orl_traj_create", "orl_traj_destroy", "orl_traj_reset", "orl_traj_append_step", "orl_traj_finish", "orl_traj_read", "orl_traj_export",
     "orl_traj_live",
@@ -309,6 +311,7 @@ def load_library(path: Optional[str] = None):
     lib.orl_autoreg_set_sample_precision.argtypes = [C.c_void_p, C.c_int32]
     lib.orl_autoreg_sample_precision.argtypes = [C.c_void_p]
     lib.orl_autoreg_sample_precision.restype = C.c_int32
+    lib.orl_actor_sample.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.orl_engine_set_next_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_lcb_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.orl_engine_adv_advantage.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int]
@@ -904,6 +907,35 @@ class Engine(_Handle):
     @property
     def autoreg_sample_precision(self) -> int:
         return int(self.lib.orl_autoreg_sample_precision(self._h))
+
+    def actor_sample(self, obs, eps=None, run: int = -1, live=None, deterministic: bool = False, n: Optional[int] = None,
+                     out_ptr: Optional[int] = None, on_device=False):
+        """The tanh-Gaussian actor's actions on the fused split-fp16 kernel (orl_actor_sample).  ``run = -1``: ``obs``
+        [n_runs][n][obs_dim], ``eps`` [n_runs][n][act_dim] (None: device Philox; ignored when ``deterministic``); ``run = r``: run r's
+        actor, arrays without the run dimension.  ``live``: host counts per run (one for ``run = r``), rows past them come back as zeros.
+        Host arrays in, a host array out; with ``on_device`` ``obs`` / ``eps`` / ``out_ptr`` are raw device pointers and ``n`` the rows
+        per run."""
+        R = self.n_runs if run < 0 else 1
+        lv = None if live is None else np.ascontiguousarray(np.asarray(live).reshape(-1), dtype=np.int32)
+        if lv is not None and lv.shape != (R,):
+            raise ValueError(f"live: expected {R} counts, got {lv.shape}")
+        lp = None if lv is None else lv.ctypes.data
+        if on_device:
+            _check(self.lib.orl_actor_sample(self._h, int(run), int(obs), int(n), None if eps is None else int(eps), lp, int(bool(deterministic)),
+                                             1, int(out_ptr)), "orl_actor_sample")
+            return None
+        o = _f32(obs)
+        lead = (self.n_runs,) if run < 0 else ()
+        if o.shape[:-2] != lead or o.ndim != len(lead) + 2 or o.shape[-1] != self.cfg.obs_dim:
+            raise ValueError(f"obs: expected {lead + ('n', self.cfg.obs_dim)}, got {o.shape}")
+        shape = o.shape[:-1] + (self.cfg.act_dim,)
+        e = None if eps is None else _f32(eps)
+        if e is not None and e.shape != shape:
+            raise ValueError(f"eps: expected {shape}, got {e.shape}")
+        out = np.zeros(shape, dtype=np.float32)
+        _check(self.lib.orl_actor_sample(self._h, int(run), o.ctypes.data, o.shape[-2], None if e is None else e.ctypes.data, lp,
+                                         int(bool(deterministic)), 0, out.ctypes.data), "orl_actor_sample")
+        return out
 
     # ---- health (include/orl_engine.h: ORL_HEALTH_*) ----
     def _check_step(self, rc: int, what: str):

@@ -91,6 +91,8 @@ def _rollout_device(policy, real_buffer, fake_buffer, rollout_batch_size: int, r
             if uniform:
                 sp = policy.action_space
                 act = torch.empty((n, sp.shape[0]), dtype=torch.float32, device=dev).uniform_(float(sp.low[0]), float(sp.high[0]))
+            elif getattr(policy, "_rollout_precision", 0) == 1:
+                act = policy.actforward_device(obs, False)
             else:
                 act, _ = policy.actforward(obs, False)
                 act = act.to(torch.float32).contiguous()
@@ -154,6 +156,8 @@ def _rollout_device_runs(policy, real_buffer, bufs, rollout_batch_size: int, rol
             if uniform:
                 sp = policy.action_space
                 act = torch.empty((R, nmax, sp.shape[0]), dtype=torch.float32, device=dev).uniform_(float(sp.low[0]), float(sp.high[0]))
+            elif getattr(policy, "_rollout_precision", 0) == 1:
+                act = policy.actforward_runs(obs, False, live=live)
             else:
                 act = policy.actforward_runs(obs, False).contiguous()
             nxt, rew, _ = dyn.step_device_runs(obs, act)

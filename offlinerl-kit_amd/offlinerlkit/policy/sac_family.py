@@ -15,6 +15,58 @@ class _TanhGaussPolicy(EnginePolicy):
     """Shared pieces of the SAC family: tanh-Gaussian actor, (auto-)temperature, actforward / select_action
     (sac.py:42-48, 66-86)."""
 
+    _rollout_precision = 0
+
+    def set_rollout_precision(self, p: int) -> None:
+        """0 (default): the model-based rollouts (``rollout_device``; ``actforward_device`` / ``actforward_runs``) sample the actor in
+        torch, as they always did; 1: on the engine's fused split-fp16 kernel (``orl_actor_sample``: weight pack + one launch; fp16
+        hi + lo planes, fp32 accumulators; an observation or activation beyond +-32768 makes the call raise).  Usable before or after an
+        engine is bound; an actor the kernel does not take is refused here when an engine is bound, else at the bind.  Training,
+        ``actforward`` and ``select_action`` are unaffected."""
+        if isinstance(p, bool) or p not in (0, 1):
+            raise ValueError(f"{type(self).__name__}.set_rollout_precision: 0 or 1, got {p!r}")
+        if p == 1 and self._eng is not None:
+            self._check_rollout_actor()
+        self._rollout_precision = int(p)
+
+    def _check_rollout_actor(self) -> None:
+        """the limits of csrc/actor_fused.h, by name and number"""
+        od, hid = _backbone_dims(self.actor.backbone)
+        ad = self.actor.dist_net.mu.out_features
+        if any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.actor.modules()):
+            raise NotImplementedError("rollout precision 1: an actor with dropout is not supported (the fused kernel has no dropout masks)")
+        for w in [od] + list(hid):
+            if w > 512:
+                raise NotImplementedError(f"rollout precision 1: a layer of {w} units is wider than the 512 columns the fused kernel takes")
+        if ad > 32:
+            raise NotImplementedError(f"rollout precision 1: act_dim {ad} is more than the 32 action dimensions the fused kernel takes")
+
+    def _bind(self, batch_size: int) -> None:
+        if self._rollout_precision == 1:
+            self._check_rollout_actor()
+        super()._bind(batch_size)
+
+    def _actor_sample(self, obs: torch.Tensor, shape, run: int, deterministic: bool, live) -> torch.Tensor:
+        """``obs`` on the engine's device, contiguous fp32 -> actions of ``shape`` ([..., n, act_dim]) from ``orl_actor_sample``; the
+        normals are one ``torch.randn(shape)`` on the device's torch generator, so ``torch.manual_seed`` reproduces"""
+        eps = None if deterministic else torch.randn(shape, device=obs.device)
+        out = torch.empty(shape, dtype=torch.float32, device=obs.device)
+        torch.cuda.current_stream(obs.device).synchronize()
+        self._eng.actor_sample(obs.data_ptr(), None if eps is None else eps.data_ptr(), run=run, live=live, deterministic=deterministic,
+                               n=int(shape[-2]), out_ptr=out.data_ptr(), on_device=True)
+        return out
+
+    def actforward_device(self, obs, deterministic: bool = False) -> torch.Tensor:
+        """the squashed actions of ``actforward`` for ``obs`` [n, obs_dim] on the engine's device, through the selected run's actor;
+        binds an engine at batch 256 when there is none.  Rollout precision 0: ``actforward(obs, deterministic)[0]``; 1: the fused kernel"""
+        if self._eng is None:
+            self._bind(256)
+        if self._rollout_precision == 0:
+            return self.actforward(obs, deterministic)[0]
+        o = torch.as_tensor(obs, dtype=torch.float32, device=self._arena.device)
+        o = o.reshape(-1, o.shape[-1]).contiguous()
+        return self._actor_sample(o, (o.shape[0], self.actor.dist_net.mu.out_features), max(self._cur_run, 0), deterministic, None)
+
     def _init_alpha(self, alpha) -> None:
         self._is_auto_alpha = False
         if isinstance(alpha, tuple):
@@ -73,17 +125,21 @@ class _TanhGaussPolicy(EnginePolicy):
         squashed, raw = dist.mode() if deterministic else dist.rsample()
         return squashed, dist.log_prob(squashed, raw)
 
-    def actforward_runs(self, obs: torch.Tensor, deterministic: bool = False) -> torch.Tensor:
+    def actforward_runs(self, obs: torch.Tensor, deterministic: bool = False, live=None) -> torch.Tensor:
         """``actforward`` of EVERY run in one batched forward (the rollouts of a multi-run model-based policy): ``obs``
         [n_runs, N, obs_dim] on the engine's device -> squashed actions [n_runs, N, act_dim]; block r goes through run r's live actor
         (``_stacked_net``).  Sampling is ``TanhNormalWrapper.rsample``: mu + exp(clamp(log_sigma, -5, 2)) * eps, eps from torch's
-        device generator, then tanh."""
+        device generator, then tanh.  Rollout precision 1: the same draw, the forward on the fused kernel (``orl_actor_sample``), and
+        ``live`` (rows per run that count; the rest come back as zeros) skips the row tiles of runs that have ended."""
         if self._eng is None:
             raise RuntimeError("actforward_runs before the engine is bound (learn / learn_n binds it)")
         if any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.actor.modules()):
             raise NotImplementedError("actforward_runs: an actor with dropout is not supported (the batched forward has no dropout masks)")
         if obs.dim() != 3 or obs.shape[0] != self._n_runs:
             raise ValueError(f"obs: expected [n_runs = {self._n_runs}, N, obs_dim], got {tuple(obs.shape)}")
+        if self._rollout_precision == 1:
+            o = obs.to(device=self._arena.device, dtype=torch.float32).contiguous()
+            return self._actor_sample(o, tuple(o.shape[:2]) + (self.actor.dist_net.mu.out_features,), -1, deterministic, live)
         P = self._stacked_net(_engine.NET_ACTOR)
         lin = lambda h, name: torch.baddbmm(P[name + ".bias"].unsqueeze(1), h, P[name + ".weight"].transpose(1, 2))
         with torch.no_grad():

@@ -27,7 +27,13 @@ warm-up of each and then alternating timed blocks; the figure is gradient steps 
 block into the penalty pass (the ``lcb`` launches of orl_profile_query) and the rest of the step.  The third contestant is
 ``MOBILEDevicePolicy.learn_n``: the same steps as one device loop (``orl_mobile_learn_n``; batches drawn on the device from the same
 dataset and the same model rows held in an HBM ring), one call per block, with the HIP-event time of the loop next to the wall time
-(``--blocks 5`` for medians of five)."""
+(``--blocks 5`` for medians of five).
+
+--actor-split measures, instead, the actor of the rollouts at rollout precision 0 (the torch ``ActorProb`` forward) and 1 (the fused
+split-fp16 kernel behind ``orl_actor_sample``, csrc/actor_fused.hip) on ONE MOPO policy object toggled by ``set_rollout_precision``:
+``actforward_device`` on 256, 12 800 and 50 000 rows (calls per second) and one ``rollout_device`` of 50 000 x 5 into an HBM ring (ms
+per rollout) at dynamics precision 0 and 1 -- a warm-up of each, then ``--blocks`` window pairs in which the two alternate, each window
+ending in a device synchronise; medians over the windows (``--blocks 5`` for medians of five)."""
 import argparse
 import json
 import os
@@ -424,6 +430,63 @@ def measure_mobile(ds, blocks, steps):
                 last_losses={k: {a: float(b) for a, b in v.items()} for k, v in last.items()})
 
 
+def measure_actor_split(ds, blocks):
+    """``--actor-split``: rollout precision 0 / 1 alternating inside every window pair, medians over the windows"""
+    med = lambda v: float(np.median(v))
+    disjoint = lambda a, b: bool(min(a) > max(b) or min(b) > max(a))
+    pol = make_policy("mopo")
+    pol._bind(B)
+    rng = np.random.default_rng(0)
+
+    def sample(p, obs, calls):
+        pol.set_rollout_precision(p)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            for _ in range(calls):
+                act = pol.actforward_device(obs)
+        torch.cuda.synchronize()
+        return calls / (time.perf_counter() - t0), act
+    legs = []
+    for rows, calls in ((256, 2000), (12_800, 1000), (50_000, 400)):
+        obs = torch.as_tensor(rng.normal(size=(rows, OD)).astype(np.float32), device=DEV)
+        a0, a1 = sample(0, obs, 5)[1], sample(1, obs, 5)[1]      # warm-up
+        s0, s1 = [], []
+        for _ in range(blocks):
+            s0.append(sample(0, obs, calls)[0]); s1.append(sample(1, obs, calls)[0])
+        legs.append(dict(rows=rows, calls_per_window=calls, precision0_calls_per_s=s0, precision1_calls_per_s=s1, precision0_median=med(s0),
+                         precision1_median=med(s1), speedup=med(s1) / med(s0), ranges_disjoint=disjoint(s0, s1),
+                         actions_finite=bool(torch.isfinite(a0).all() and torch.isfinite(a1).all())))
+    # the rollout: one dynamics per precision (the option is fixed when its engine is bound), the same policy object toggled
+    real = ReplayBuffer(len(ds["rewards"]), (OD,), np.float32, AD, np.float32, device=DEV)
+    real.load_dataset(ds)
+    fake = ReplayBuffer(MODEL_ROWS, (OD,), np.float32, AD, np.float32, device=DEV)
+    dyns = {0: pol.dynamics, 1: make_policy("mopo").dynamics}
+    dyns[1].set_engine_options(n_runs=1, seed=7, precision=1)
+    _, n, length = ROLLOUT
+    per_window = 10
+
+    def rollout(pp, dp):
+        pol.set_rollout_precision(pp)
+        pol.dynamics = dyns[dp]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(per_window):
+            info = pol.rollout_device(real, fake, n, length)
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / per_window, int(info["num_transitions"])
+    combos = [(0, 0), (1, 0), (0, 1), (1, 1)]
+    rows_out = {c: rollout(*c)[1] for c in combos}               # warm-up
+    ms = {c: [] for c in combos}
+    for _ in range(blocks):
+        for c in combos:
+            ms[c].append(rollout(*c)[0])
+    rolls = [dict(dynamics_precision=dp, rollouts_per_window=per_window, transitions=rows_out[(0, dp)], precision0_ms=ms[(0, dp)],
+                  precision1_ms=ms[(1, dp)], precision0_median_ms=med(ms[(0, dp)]), precision1_median_ms=med(ms[(1, dp)]),
+                  speedup=med(ms[(0, dp)]) / med(ms[(1, dp)]), ranges_disjoint=disjoint(ms[(0, dp)], ms[(1, dp)])) for dp in (0, 1)]
+    return dict(actforward_device=legs, rollout_device=rolls)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=3)
@@ -436,9 +499,20 @@ def main():
     ap.add_argument("--rambo-steps", type=int, default=1000)
     ap.add_argument("--mobile", action="store_true", help="MOBILEPolicy.learn (engine, host loop) against its stock-torch restatement and MOBILEDevicePolicy.learn_n (the device loop)")
     ap.add_argument("--mobile-steps", type=int, default=500)
+    ap.add_argument("--actor-split", action="store_true", help="the rollouts' actor at rollout precision 0 (torch) and 1 (the fused split-fp16 kernel): actforward_device and rollout_device")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mb_throughput: no HIP device visible (the loops under test run on the GPU)")
+    if a.actor_split:
+        res = {"shape": dict(obs=OD, act=AD, dynamics_hidden=DYN_HID, members=K, elites=E, policy_hidden=[256, 256], rollout=ROLLOUT),
+               "device": torch.cuda.get_device_name(0), "results": [measure_actor_split(dataset(200_000), a.blocks)]}
+        s = json.dumps(res, indent=1)
+        print(s)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(s + "\n")
+        return
     if a.mobile:
         res = {"shape": dict(obs=OD, act=AD, dynamics_hidden=DYN_HID, members=K, elites=E, policy_hidden=[256, 256]),
                "device": torch.cuda.get_device_name(0), "results": [measure_mobile(dataset(200_000), a.blocks, a.mobile_steps)]}
