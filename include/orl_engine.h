@@ -641,6 +641,8 @@ typedef struct orl_dyn_config {
   int32_t n_runs, device, precision;
   uint64_t seed;                    /* device Philox seed of orl_dyn_step without teacher-forced noise */
   float* external_arena;            /* optional caller-owned device block of n_runs * orl_dyn_floats floats (torch aliasing); NULL = hipMalloc */
+  int32_t step_head;                /* head kernel of orl_dyn_step and of the device loops that enqueue it: 0 k_dyn_head (a thread per row),
+                                       1 k_dyn_head_tile (a workgroup per tile of rows; the same outputs bit for bit); else refused */
 } orl_dyn_config;
 
 #define ORL_DYN_PENALTY_ALEATORIC 0      /* max_k || std_k ||  (all out dims) */

@@ -17,7 +17,7 @@
 //
 // Every formula that more than one kernel needs exists ONCE, as a device function below: dyn_soft_clamp(_grad) and dyn_std (every
 // logvar and std of this file), dyn_nll_elem (the NLL element of k_dyn_nll and of k_dyn_adv_head's dataset rows), dyn_col_sum and
-// dyn_reduce_tail (the two reduce kernels), dyn_draw_elite, dyn_scale_row, reduce.h's wave_sum / block_sum256_pairwise / softplus and
+// dyn_reduce_tail (the two reduce kernels), dyn_draw_elite, dyn_scale_row, dyn_sample and dyn_add_sq (the step's two head kernels), reduce.h's wave_sum / block_sum256_pairwise / softplus and
 // rng.h's Philox / box_muller_one.  A sampler that must agree with another bit for bit agrees because both call the same function.
 // On the host, DynWs is the one workspace type (learn, adversarial update, and step as a forward-only view) and dyn_forward /
 // dyn_backward are the only layer loops.  Allocation, the tensor table, transfers, staging and the GemmP of a layer's products come
@@ -292,6 +292,11 @@ struct DynHeadP {
   float* next_obs; float* reward; float* raw_reward; float* penalty; int* midx_out;
 };
 
+// The two accumulations that k_dyn_head and k_dyn_head_tile must round alike: one function each, so that the compiler contracts (or
+// does not contract) the product into the sum in both kernels.  The sample mean + eps std in double, then fp32; ss += v v in double.
+__device__ __forceinline__ float dyn_sample(float mean, double eps, float std) { return (float)((double)mean + eps * (double)std); }
+__device__ __forceinline__ void dyn_add_sq(double& ss, double v) { ss += v * v; }
+
 // step()'s head, one thread per (run, row): soft_clamp, mean[:-1] += obs, std = sqrt(exp(logvar)), the sample of the chosen member
 // (mean + eps std: double like the reference's float64 noise, then fp32) and the penalty over ALL members
 __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
@@ -323,7 +328,7 @@ __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
     for (int j = 0; j < 4 && d0 + j < D; ++j) {
       const int d = d0 + j;
       const double eps = p.noise ? (double)p.noise[(((long)r * K + mi) * p.n + i) * D + d] : (double)box_muller_one(rnd, j);
-      const float s = (float)((double)mean_at(mi, d) + eps * (double)std_at(mi, d));
+      const float s = dyn_sample(mean_at(mi, d), eps, std_at(mi, d));
       if (d < od) p.next_obs[((long)r * p.n + i) * od + d] = s;
       else p.raw_reward[(long)r * p.n + i] = s;
     }
@@ -332,7 +337,7 @@ __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
   if (p.mode == ORL_DYN_PENALTY_ALEATORIC) {
     for (int k = 0; k < K; ++k) {
       double ss = 0.0;
-      for (int d = 0; d < D; ++d) { const double s = std_at(k, d); ss += s * s; }
+      for (int d = 0; d < D; ++d) dyn_add_sq(ss, (double)std_at(k, d));
       pen = fmax(pen, sqrt(ss));
     }
   } else {
@@ -345,14 +350,14 @@ __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
     if (p.mode == ORL_DYN_PENALTY_PAIRWISE_DIFF) {
       for (int k = 0; k < K; ++k) {
         double ss = 0.0;
-        for (int d = 0; d < od; ++d) { const double df = (double)(mean_at(k, d) - mbar[d]); ss += df * df; }
+        for (int d = 0; d < od; ++d) dyn_add_sq(ss, (double)(mean_at(k, d) - mbar[d]));
         pen = fmax(pen, sqrt(ss));
       }
     } else {
       double vs = 0.0;
       for (int d = 0; d < od; ++d) {
         double s = 0.0;
-        for (int k = 0; k < K; ++k) { const double df = (double)mean_at(k, d) - (double)mbar[d]; s += df * df; }
+        for (int k = 0; k < K; ++k) dyn_add_sq(s, (double)mean_at(k, d) - (double)mbar[d]);
         vs += s / K;
       }
       pen = sqrt(vs / od);
@@ -363,6 +368,149 @@ __global__ __launch_bounds__(256) void k_dyn_head(DynHeadP p) {
   p.penalty[(long)r * p.n + i] = penf;
   p.reward[(long)r * p.n + i] = dyn_sub_mul(raw, p.coef, penf);
   if (p.midx_out) p.midx_out[(long)r * p.n + i] = mi;
+}
+
+// ---- step_head = 1: k_dyn_head's values from a workgroup per tile of RH rows of one run ----
+// The LDS image of a tile, in this order: red [RH][max(K, D)] doubles (the penalty's partial results), M and S [K][RH][Dp] floats (the
+// means with obs added, the stds), bnd [2][D] (max / min_logvar), mbar [RH][D], raw [RH], then RH member indices.  Dp = D | 1: with an
+// odd row stride the readers of one column of RH x K different rows fall on different banks.
+__host__ __device__ inline int dyn_tile_dp(int D) { return D | 1; }
+__host__ __device__ inline size_t dyn_tile_lds_bytes(int K, int D, int rh) {
+  return 8 * (size_t)rh * (K > D ? K : D) + 4 * ((size_t)2 * K * rh * dyn_tile_dp(D) + 2 * D + (size_t)rh * D + rh) + 4 * (size_t)rh;
+}
+enum { DYN_TILE_LDS_MAX = 65536, DYN_TILE_UNROLL = 4 };
+
+// grid (ceil(n / RH), R), 256 threads.  Stage: OUT's rows are copied with the row's 2 D columns fastest (coalesced; DYN_TILE_UNROLL loads
+// in flight per thread), obs added by mean_at's fp32 add; after a barrier every raw logvar becomes its dyn_std in place, ONCE, with all
+// lanes on that path.  Sample: a thread per (row, d), k_dyn_head's noise element or Philox counter.  Penalty: a thread per (row, k) or
+// (row, d) runs k_dyn_head's inner sum in its order through dyn_add_sq, the outer max / sum runs per row in its order: the same double.
+template <int RH>
+__global__ __launch_bounds__(256) void k_dyn_head_tile(DynHeadP p) {
+  extern __shared__ double dyn_tile_lds[];
+  const int D = p.D, od = p.od, K = p.K, Dp = dyn_tile_dp(D), W = K > D ? K : D;
+  const int r = blockIdx.y, tid = threadIdx.x;
+  const long i0 = (long)blockIdx.x * RH;
+  const int rows = (int)min((long)RH, p.n - i0);        // rows at or past n are neither loaded nor stored
+  double* red = dyn_tile_lds;
+  float* M = (float*)(red + RH * W);
+  float* S = M + K * RH * Dp;
+  float* bnd = S + K * RH * Dp;
+  float* mbar = bnd + 2 * D;
+  float* raws = mbar + RH * D;
+  int* smi = (int*)(raws + RH);
+  const Philox ph(p.seed);
+  uint32_t rnd[4];
+
+  // ---- stage ----
+  const int C = 2 * D, KR = K * RH, total = KR * C;
+  for (int e0 = tid; e0 < total; e0 += 256 * DYN_TILE_UNROLL) {
+    float v[DYN_TILE_UNROLL], o[DYN_TILE_UNROLL];
+    int at[DYN_TILE_UNROLL];
+    bool add[DYN_TILE_UNROLL];
+#pragma unroll
+    for (int u = 0; u < DYN_TILE_UNROLL; ++u) {
+      const int e = e0 + 256 * u;
+      const int t = e / C, c = e - t * C, k = t / RH, row = t - k * RH;      // t = k RH + row, the row of M and of S
+      at[u] = -1; add[u] = false;
+      if (e < total && row < rows) {
+        at[u] = c < D ? t * Dp + c : (KR + t) * Dp + c - D;                  // S follows M
+        add[u] = c < od;
+        v[u] = p.OUT[(((long)r * K + k) * p.n + i0 + row) * p.op + c];
+        if (add[u]) o[u] = p.obs[((long)r * p.n + i0 + row) * od + c];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < DYN_TILE_UNROLL; ++u)
+      if (at[u] >= 0) M[at[u]] = add[u] ? v[u] + o[u] : v[u];                // mean_at's add; the reward's mean gets none (not even + 0)
+  }
+  if (tid < D) {
+    bnd[tid] = p.params[r * p.P + p.off_max + tid];
+    bnd[D + tid] = p.params[r * p.P + p.off_min + tid];
+  }
+  if (tid < rows) {
+    const long i = i0 + tid;
+    if (p.midx) smi[tid] = p.midx[(long)r * p.n + i];
+    else {
+      ph((uint32_t)i, (uint32_t)(i >> 32), (uint32_t)r, (uint32_t)(0x80000000u | (uint32_t)p.call), rnd);
+      smi[tid] = dyn_draw_elite(p.elites, r, K, p.n_elites, rnd[0]);
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < KR * D; e += 256) {
+    const int t = e / D, d = e - t * D;
+    if (t % RH < rows) S[t * Dp + d] = dyn_std(S[t * Dp + d], bnd[d], bnd[D + d]);
+  }
+  __syncthreads();
+
+  // ---- sample ----
+  for (int e = tid; e < rows * D; e += 256) {
+    const int row = e / D, d = e - row * D, mi = smi[row];
+    const long i = i0 + row;
+    double eps;
+    if (p.noise) eps = (double)p.noise[(((long)r * K + mi) * p.n + i) * D + d];
+    else {
+      ph((uint32_t)i, (uint32_t)(i >> 32), (uint32_t)r, ((uint32_t)p.call << 8) | (uint32_t)(d >> 2), rnd);
+      eps = (double)box_muller_one(rnd, d & 3);
+    }
+    const float s = dyn_sample(M[(mi * RH + row) * Dp + d], eps, S[(mi * RH + row) * Dp + d]);
+    if (d < od) p.next_obs[((long)r * p.n + i) * od + d] = s;
+    else { p.raw_reward[(long)r * p.n + i] = s; raws[row] = s; }
+  }
+
+  // ---- penalty ----
+  double pen = 0.0;
+  if (p.mode == ORL_DYN_PENALTY_ALEATORIC) {
+    for (int t = tid; t < KR; t += 256) {
+      const int k = t / RH, row = t - k * RH;
+      if (row >= rows) continue;
+      double ss = 0.0;
+      for (int d = 0; d < D; ++d) dyn_add_sq(ss, (double)S[t * Dp + d]);
+      red[row * W + k] = sqrt(ss);
+    }
+    __syncthreads();
+    if (tid < rows)
+      for (int k = 0; k < K; ++k) pen = fmax(pen, red[tid * W + k]);
+  } else {
+    for (int e = tid; e < rows * od; e += 256) {
+      const int row = e / od, d = e - row * od;
+      double s = 0.0;
+      for (int k = 0; k < K; ++k) s += M[(k * RH + row) * Dp + d];
+      mbar[row * D + d] = (float)(s / K);
+    }
+    __syncthreads();
+    if (p.mode == ORL_DYN_PENALTY_PAIRWISE_DIFF) {
+      for (int t = tid; t < KR; t += 256) {
+        const int k = t / RH, row = t - k * RH;
+        if (row >= rows) continue;
+        double ss = 0.0;
+        for (int d = 0; d < od; ++d) dyn_add_sq(ss, (double)(M[t * Dp + d] - mbar[row * D + d]));
+        red[row * W + k] = sqrt(ss);
+      }
+      __syncthreads();
+      if (tid < rows)
+        for (int k = 0; k < K; ++k) pen = fmax(pen, red[tid * W + k]);
+    } else {
+      for (int e = tid; e < rows * od; e += 256) {
+        const int row = e / od, d = e - row * od;
+        double s = 0.0;
+        for (int k = 0; k < K; ++k) dyn_add_sq(s, (double)M[(k * RH + row) * Dp + d] - (double)mbar[row * D + d]);
+        red[row * W + d] = s / K;
+      }
+      __syncthreads();
+      if (tid < rows) {
+        double vs = 0.0;
+        for (int d = 0; d < od; ++d) vs += red[tid * W + d];
+        pen = sqrt(vs / od);
+      }
+    }
+  }
+  if (tid < rows) {                                   // raws: written before the penalty's barriers
+    const long ri = (long)r * p.n + i0 + tid;
+    const float penf = (float)pen;
+    p.penalty[ri] = penf;
+    p.reward[ri] = dyn_sub_mul(raws[tid], p.coef, penf);
+    if (p.midx_out) p.midx_out[ri] = smi[tid];
+  }
 }
 
 // ---- MOBILE's next-state samples (reference: dynamics/ensemble_dynamics.py:82-99): orl_dynsample_next ----
@@ -966,6 +1114,20 @@ static int dyn_upload_run_state(orl_dynamics* d, const int32_t* active, const st
   return 0;
 }
 
+// step_head = 1: k_dyn_head_tile<RH> at the largest RH of 16 / 8 / 4 / 2 / 1 whose LDS image fits DYN_TILE_LDS_MAX and whose grid
+// fits; returns 1, with nothing launched, where none does (the caller launches k_dyn_head)
+template <int RH>
+static int dyn_head_tile_try(orl_dynamics* d, const DynHeadP& h) {
+  const size_t lds = dyn_tile_lds_bytes(h.K, h.D, RH);
+  const long nb = (h.n + RH - 1) / RH;
+  if (lds <= DYN_TILE_LDS_MAX && nb <= 0x7fffffffL) {
+    DEV_LAUNCH(d->stream, k_dyn_head_tile<RH>, dim3((unsigned)nb, d->R), dim3(256), lds, h);
+    return 0;
+  }
+  if constexpr (RH > 1) return dyn_head_tile_try<RH / 2>(d, h);
+  return 1;
+}
+
 extern "C" {
 
 void orl_dyn_config_default(orl_dyn_config* c) {
@@ -978,7 +1140,7 @@ void orl_dyn_config_default(orl_dyn_config* c) {
   for (int i = 0; i < 5; ++i) c->weight_decay[i] = wd[i];
   c->lr = 1e-3f; c->adam_beta1 = 0.9f; c->adam_beta2 = 0.999f; c->adam_eps = 1e-8f;
   c->batch_size = 256; c->logvar_loss_coef = 0.01f;
-  c->n_runs = 1; c->device = 0; c->precision = 0; c->seed = 0;
+  c->n_runs = 1; c->device = 0; c->precision = 0; c->seed = 0; c->step_head = 0;
 }
 
 int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out) {
@@ -994,8 +1156,10 @@ int orl_dyn_create(const orl_dyn_config* cfg, orl_dynamics** out) {
   if (c.precision != 0 && c.precision != 1)
     return fail("orl_dyn_create: the dynamics ensemble implements precision 0 (fp32 MFMA) and 1 (split-fp16 step / sample_next); "
                 "precision 2 is not supported");
+  if (c.step_head != 0 && c.step_head != 1)
+    return fail("orl_dyn_create: step_head must be 0 (k_dyn_head) or 1 (k_dyn_head_tile), got " + std::to_string(c.step_head));
   if (c.precision == 1) {
-    int wmax = std::max(c.obs_dim + c.act_dim, 2 * (c.obs_dim + (c.with_reward ? 1 : 0)));
+    int wmax =std::max(c.obs_dim + c.act_dim, 2 * (c.obs_dim + (c.with_reward ? 1 : 0)));
     for (int i = 0; i < c.n_hidden; ++i) wmax = std::max(wmax, (int)c.hidden[i]);
     if (wmax > ORL_DYN_FUSED_MAX_WIDTH)
       return fail("orl_dyn_create: precision 1 takes layers (input, hidden, output) of at most " + std::to_string(ORL_DYN_FUSED_MAX_WIDTH) +
@@ -1289,8 +1453,8 @@ static int dyn_step_forward(orl_dynamics* d, const float* obs, const float* act,
   return dyn_forward_only(d, n);
 }
 
-// the launches of a step on device rows: k_dyn_step_input, the ensemble's forward, k_dyn_head; the call counter advances.  orl_dyn_step
-// stages around them, dynstep_enqueue (the MBRCSL rollout loop) is nothing else
+// the launches of a step on device rows: k_dyn_step_input, the ensemble's forward, k_dyn_head (or k_dyn_head_tile: the one switch of
+// step_head); the call counter advances.  orl_dyn_step stages around them, dynstep_enqueue (the MBRCSL rollout loop) is nothing else
 static int dyn_step_launches(orl_dynamics* d, const float* obs, const float* act, long n, const float* noise, const int* midx, int mode,
                              float coef, float* next_obs, float* reward, float* raw_reward, float* penalty, int* midx_out, const char* who) {
   if (dyn_step_forward(d, obs, act, n)) return -1;
@@ -1305,6 +1469,10 @@ static int dyn_step_launches(orl_dynamics* d, const float* obs, const float* act
   h.seed = d->c.seed; h.call = d->step_calls++;
   h.mode = mode; h.coef = coef;
   h.next_obs = next_obs; h.reward = reward; h.raw_reward = raw_reward; h.penalty = penalty; h.midx_out = midx_out;
+  if (d->c.step_head == 1) {
+    const int rc = dyn_head_tile_try<16>(d, h);
+    if (rc <= 0) return rc;
+  }
   DEV_LAUNCH(d->stream, k_dyn_head, dim3((unsigned)((n + 255) / 256), d->R), dim3(256), 0, h);
   return 0;
 }

@@ -133,6 +133,7 @@ class OrlDynConfig(C.Structure):
         ("batch_size", C.c_int32), ("logvar_loss_coef", C.c_float),
         ("n_runs", C.c_int32), ("device", C.c_int32), ("precision", C.c_int32), ("seed", C.c_uint64),
         ("external_arena", C.c_void_p),
+        ("step_head", C.c_int32),
     ]
 
 
@@ -1420,6 +1421,11 @@ class Dynamics(_Handle):
     def precision(self) -> int:
         """0: fp32 MFMA; 1: ``step`` / ``sample_next`` on the fused split-fp16 forward, training and validation in fp32"""
         return int(self.cfg.precision)
+
+    @property
+    def step_head(self) -> int:
+        """0: ``k_dyn_head`` (a thread per row); 1: ``k_dyn_head_tile`` (a workgroup per tile of rows), the same outputs bit for bit"""
+        return int(self.cfg.step_head)
 
     def sync(self):
         _check(self.lib.orl_dyn_sync(self._h), "orl_dyn_sync")

@@ -95,7 +95,7 @@ class EnsembleDynamics(BaseDynamics):
         self.terminal_fn = terminal_fn
         self._penalty_coef = penalty_coef
         self._uncertainty_mode = uncertainty_mode
-        self._n_runs, self._seed, self._precision = 1, 0, 0
+        self._n_runs, self._seed, self._precision, self._step_head = 1, 0, 0, 0
         self._eng: Optional[_engine.Dynamics] = None
         self._arena = None
         self._shape = None             # (batch_size, logvar_loss_coef) the engine was built for
@@ -105,11 +105,13 @@ class EnsembleDynamics(BaseDynamics):
         self._adv_key = None           # (lr, betas, eps, adv_weight, rollout rows, dataset rows) of the bound adversarial optimizer
 
     # ---- engine binding ----
-    def set_engine_options(self, n_runs: int = 1, seed: Optional[int] = None, precision: int = 0) -> None:
-        """``precision=1``: step / sample_next run the ensemble's forward on the fused split-fp16 kernel; training stays fp32"""
+    def set_engine_options(self, n_runs: int = 1, seed: Optional[int] = None, precision: int = 0, step_head: int = 0) -> None:
+        """``precision=1``: step / sample_next run the ensemble's forward on the fused split-fp16 kernel; training stays fp32.
+        ``step_head=1``: the step's head runs on the row-tile kernel (the same outputs bit for bit)"""
         if self._eng is not None:
             raise RuntimeError("set_engine_options before the first train() / step()")
         self._precision = int(precision)
+        self._step_head = int(step_head)
         self._n_runs = int(n_runs)
         self._seed = int(seed) if seed is not None else 0
         self.scalers = [self.scaler] + [StandardScaler(self.scaler.mu, self.scaler.std) for _ in range(self._n_runs - 1)]
@@ -132,7 +134,8 @@ class EnsembleDynamics(BaseDynamics):
                                          num_elites=m.num_elites, with_reward=int(bool(m._with_reward)), weight_decay=m.weight_decays,
                                          lr=float(g["lr"]), adam_beta1=float(g["betas"][0]), adam_beta2=float(g["betas"][1]),
                                          adam_eps=float(g["eps"]), batch_size=shape[0], logvar_loss_coef=shape[1],
-                                         n_runs=self._n_runs, device=dev.index, precision=self._precision, seed=self._seed)
+                                         n_runs=self._n_runs, device=dev.index, precision=self._precision, seed=self._seed,
+                                         step_head=self._step_head)
         P = int(_engine.load_library().orl_dyn_config_floats(cfg))
         self._arena = torch.zeros(self._n_runs * P, dtype=torch.float32, device=dev)
         cfg.external_arena = self._arena.data_ptr()

@@ -3,7 +3,8 @@
 the HIP engine (orl_dyn_learn_epoch) at n_runs 1 and 8, rollout rows/s of step() at 50 000 rows, and the same two measured on a stock
 torch implementation written here (bmm EnsembleLinear forward, autograd, torch.optim.Adam, loss.item() per minibatch as the
 reference's learn() does).  Prints one JSON object; --out writes it too.
---split: step() on device tensors at precision 0 (fp32 GEMM per layer) against precision 1 (the fused split-fp16 forward) instead."""
+--split: step() on device tensors at precision 0 (fp32 GEMM per layer) against precision 1 (the fused split-fp16 forward) instead.
+--head: step() on device tensors with step_head 0 (k_dyn_head) against 1 (k_dyn_head_tile) at precision 0 and 1 instead."""
 import argparse
 import json
 import os
@@ -75,16 +76,16 @@ def fused_tile(rows):
     return 16
 
 
-def split_step(rows_list, windows=5, window_s=0.4, only=None):
-    """step() on device tensors at precision 0 and 1, two objects of this build timed in alternating windows; every call ends in the
-    engine's own synchronise.  Medians of `windows` windows per precision and row count.  only = (precision, rows): that one engine in a
-    plain loop, for a kernel trace."""
+def ab_step(variants, rows_list, windows=5, window_s=0.4, only=None):
+    """step() on device tensors by two objects of this build (variants: two dicts of config overrides), timed in alternating windows;
+    every call ends in the engine's own synchronise.  Returns [(rows, reps per window [2], window means in s [2][windows])].
+    only = (variant index, rows): that one engine in a plain loop, for a kernel trace."""
     torch.manual_seed(0)
     m = EnsembleDynamicsModel(OD, AD, HID, K, E, weight_decays=DECAYS)
     p = {k: v.detach().numpy() for k, v in m.state_dict().items() if k != "elites"}
     engs = {}
-    for prec in ((0, 1) if only is None else (only[0],)):
-        engs[prec] = eng = _engine.Dynamics(_engine.default_dyn_config(precision=prec))
+    for v in ((0, 1) if only is None else (only[0],)):
+        engs[v] = eng = _engine.Dynamics(_engine.default_dyn_config(**variants[v]))
         eng.set_params(0, p)
         eng.set_scaler(0, np.zeros(OD + AD, np.float32), np.ones(OD + AD, np.float32))
     dev = torch.device("cuda", 0)
@@ -104,17 +105,37 @@ def split_step(rows_list, windows=5, window_s=0.4, only=None):
         if only is not None:
             window(engs[only[0]], 200)
             continue
-        reps = {prec: max(10, int(window_s / window(eng, 10))) for prec, eng in engs.items()}
+        reps = {v: max(10, int(window_s / window(eng, 10))) for v, eng in engs.items()}
         t = {0: [], 1: []}
         for _ in range(windows):
-            for prec, eng in engs.items():
-                t[prec].append(window(eng, reps[prec]))
+            for v, eng in engs.items():
+                t[v].append(window(eng, reps[v]))
+        out.append((rows, reps, t))
+    for eng in engs.values():
+        eng.close()
+    return out
+
+
+def split_step(rows_list, windows=5, window_s=0.4, only=None):
+    """precision 0 against 1 (ab_step).  Medians of `windows` windows per precision and row count."""
+    out = []
+    for rows, reps, t in ab_step((dict(precision=0), dict(precision=1)), rows_list, windows, window_s, only):
         med = {prec: float(np.median(v)) for prec, v in t.items()}
         out.append(dict(rows=rows, fused_rows_per_workgroup=fused_tile(rows), reps_per_window=reps, windows=windows,
                         p0_ms=med[0] * 1e3, p1_ms=med[1] * 1e3, p0_ms_windows=[x * 1e3 for x in t[0]], p1_ms_windows=[x * 1e3 for x in t[1]],
                         p0_rows_per_s=rows / med[0], p1_rows_per_s=rows / med[1], p1_over_p0_speed=med[0] / med[1]))
-    for eng in engs.values():
-        eng.close()
+    return out
+
+
+def head_step(precision, rows_list, windows=5, window_s=0.4, only=None):
+    """step_head 0 (k_dyn_head) against 1 (k_dyn_head_tile) at one precision (ab_step): medians and ranges of `windows` windows"""
+    out = []
+    for rows, reps, t in ab_step((dict(precision=precision, step_head=0), dict(precision=precision, step_head=1)), rows_list, windows,
+                                 window_s, only):
+        med = {h: float(np.median(v)) for h, v in t.items()}
+        out.append(dict(precision=precision, rows=rows, reps_per_window=reps, windows=windows, head0_ms=med[0] * 1e3, head1_ms=med[1] * 1e3,
+                        head0_ms_windows=[x * 1e3 for x in t[0]], head1_ms_windows=[x * 1e3 for x in t[1]],
+                        head1_over_head0_speed=med[0] / med[1]))
     return out
 
 
@@ -182,7 +203,25 @@ def main():
                     "50 000 rows); --out defaults to profiles/dyn_step_split_throughput.json")
     ap.add_argument("--split-trace", type=int, nargs=2, metavar=("PRECISION", "ROWS"), default=None,
                     help="with --split: 200 steps of one precision at one row count only (for a kernel trace: the pack launch's share)")
+    ap.add_argument("--head", action="store_true", help="step() on device tensors with step_head 0 against 1 at precision 0 and 1 (256, "
+                    "12 800 and 50 000 rows); --out defaults to profiles/dyn_step_head_throughput.json")
+    ap.add_argument("--head-trace", type=int, nargs=3, metavar=("PRECISION", "STEP_HEAD", "ROWS"), default=None,
+                    help="with --head: 200 steps of one setting at one row count only (for a kernel trace)")
     a = ap.parse_args()
+    if a.head:
+        if a.head_trace:
+            head_step(a.head_trace[0], (), only=tuple(a.head_trace[1:]))
+            return
+        res = {"shape": dict(obs=OD, act=AD, hidden=HID, members=K), "device": torch.cuda.get_device_name(0),
+               "what": "orl_dyn_step on device tensors, ms per call incl. its synchronise: medians of alternating windows, step_head 0 / 1",
+               "step": head_step(0, (256, 12800, 50000)) + head_step(1, (256, 12800, 50000))}
+        s = json.dumps(res, indent=1)
+        print(s)
+        out = a.out or os.path.join(ROOT, "profiles", "dyn_step_head_throughput.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write(s + "\n")
+        return
     if a.profile_epoch:
         print(json.dumps(engine_learn(1, 256 * 50, 1)))
         return
